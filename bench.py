@@ -9,7 +9,9 @@ says n_gpus = N.  A "step" = one pass of the whole encode hot path (BGR24 in HBM
 work with no data-path collective; the only collectives are the 32-byte work descriptor broadcast and the all-gather of
 per-rank {bytes, checksum, images ok}.  Default: weak scaling (`--batch` images per GPU).  `--total-images T` (BASELINE
 configs[3]: 65536 over 8 GPUs) cuts ONE job of T images into contiguous per-rank ranges instead (strong scaling).
-`--dry` runs the multi-process plumbing alone on CPU over gloo (tests).
+`--dry` runs the multi-process plumbing alone on CPU over gloo (tests).  `--dump-outputs DIR` writes what the last timed encode
+step (and the last timed decode step) returned as DIR/<name>.npy, so that two builds can be compared output for output on the same
+seeded inputs.
 
 Rank 0 prints ONE JSON line.  `roofline` is measured with HIP events on the launch stream inside the timed
 region; `cpu_baseline` times the reference encoder (oracle/_ref, kind "reference") or, if that build is
@@ -343,6 +345,68 @@ def timed_steps(enc, bgr, q, out, steps, warmup, dist, dev, max_over_ranks):
     return dt, front_ms, color_ms, tim
 
 
+DUMP_SEED = 20240611             # --dump-outputs: the fixed seed of the sampled files / pictures
+DUMP_SAMPLE_BYTES = 40 << 20     # at most this much of sampled .nhw bytes (float32); decoded pictures and per-file figures come on top, < 64 MB in all
+
+
+def _sha52(b) -> float:
+    """the first 52 bits of a sha256, exact in a float64"""
+    import hashlib
+    return float(int(hashlib.sha256(b).hexdigest()[:13], 16))
+
+
+def dump_encode(out, n):
+    """What a caller of encode_device receives from the last timed step, as float arrays: every file's size, status and sha256 (52 bits), and
+    the bytes of a fixed, seeded sample of the files (zero past each file's end)."""
+    import numpy as np
+    import nhwcodec_amd
+    o, sizes, status = out
+    sz = sizes.cpu().numpy().astype(np.int64)
+    digest = np.zeros(n, np.float64)
+    for c0 in range(0, n, 256):
+        c1 = min(n, c0 + 256)
+        w = int(min(max(int(sz[c0:c1].max()), 0), nhwcodec_amd.OUT_STRIDE))
+        host = o[c0:c1, :w].cpu().numpy()
+        for i in range(c0, c1):
+            digest[i] = _sha52(host[i - c0, : max(int(sz[i]), 0)].tobytes())
+    k = min(64, n)
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    width = int(max(1, min(nhwcodec_amd.OUT_STRIDE, sz[pick].max())))
+    pick = pick[: max(1, min(k, DUMP_SAMPLE_BYTES // (4 * width)))]
+    sample = o[torch_index(pick, o.device), :width].cpu().numpy().astype(np.float32)
+    for r, i in enumerate(pick):
+        sample[r, max(int(sz[i]), 0):] = 0
+    return {"enc_sizes": sz.astype(np.float64), "enc_status": status.cpu().numpy().astype(np.float64), "enc_nhw_sha52": digest,
+            "enc_sample_index": pick.astype(np.float64), "enc_sample_bytes": sample}
+
+
+def dump_decode(pix, status, quality, n):
+    """What a caller of decode_device receives from the last timed step: every picture's status, quality and sha256 (52 bits), and a fixed,
+    seeded sample of four decoded pictures (BGR24 as float32)."""
+    import numpy as np
+    digest = np.zeros(n, np.float64)
+    for c0 in range(0, n, 256):
+        host = pix[c0:min(n, c0 + 256)].cpu().numpy()
+        for i in range(host.shape[0]):
+            digest[c0 + i] = _sha52(host[i].tobytes())
+    pick = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, min(4, n), replace=False))
+    return {"dec_status": status.cpu().numpy().astype(np.float64), "dec_quality": quality.cpu().numpy().astype(np.float64),
+            "dec_pixels_sha52": digest, "dec_sample_index": pick.astype(np.float64),
+            "dec_sample_pixels": pix[torch_index(pick, pix.device)].cpu().numpy().astype(np.float32)}
+
+
+def torch_index(a, device):
+    import torch
+    return torch.as_tensor(a, dtype=torch.int64, device=device)
+
+
+def write_dump(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -358,7 +422,12 @@ def main():
     ap.add_argument("--no-chroma-l1", action="store_true", help="skip the separate timing of the two chroma level-1 launches (roofline.frac_incl_chroma_l1); the profile scripts use it so that kernel tables hold the encoder's own launches only")
     ap.add_argument("--no-config4-shape", action="store_true", help="skip the leg that times BASELINE config 4's PER-GPU shape (8192 images = 65536 / 8) on this one GPU")
     ap.add_argument("--dry", action="store_true", help="CPU only: rendezvous over gloo, descriptor broadcast, sharding, gather -- no encode (tests of the N>1 plumbing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last headline encode step (and the last decode step) returned, as DIR/<name>.npy "
+                         "(float32 / float64, under 64 MB; rank 0's images): per-file sizes, status and digests, a seeded sample of the files and pictures")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args))
@@ -413,6 +482,7 @@ def main():
     torch.cuda.synchronize()
 
     dt, front_ms, color_ms, tim = timed_steps(enc, bgr, q, out, args.steps, args.warmup, dist, dev, max_over_ranks)
+    dump = dump_encode(out, batch) if (args.dump_outputs and rank == 0) else None     # before any later leg reuses the arena
 
     # the two chroma level-1 launches, timed on the planes the headline batch just left (the hook refuses anything but the handle's last whole batch)
     cl1 = chroma_l1_ms(enc, tim.front_images or batch) if (rank == 0 and q >= 17 and not args.no_chroma_l1) else None
@@ -497,6 +567,8 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
             ddt = max_over_ranks(dist, dev, time.perf_counter() - t1)
+        if dump is not None:
+            dump.update(dump_decode(pix, dst, dq, batch))
         dec_ok = int((dst == 0).sum().item())
         err = (pix[:64].float() - bgr[:64].float()).pow(2).mean().item()
         dec_line = {"metric": "decode Mpixels/s (512x512 .nhw batch -> BGR24, BASELINE config 5)", "value": round(total_per_step * args.steps * MPIX_PER_IMAGE / ddt, 2),
@@ -594,6 +666,8 @@ def main():
             line["decode"] = dec_line
         if not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(q)
+        if dump is not None:
+            write_dump(args.dump_outputs, dump)
         print(json.dumps(line), flush=True)
     enc.close()
     if dist:

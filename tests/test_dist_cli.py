@@ -102,14 +102,25 @@ def cli():
     return CLI
 
 
-@pytest.mark.parametrize("args", [["-q99", "a.bmp", "b.nhw"], ["-qx", "a.bmp", "b.nhw"], ["-z", "a", "b"], ["only_one"], ["same", "same"], ["-h"]])
-def test_cli_argument_handling_matches_reference_binary(cli, args):
-    if not os.path.exists(REF_CLI):
-        pytest.skip("reference binary not built")
+# what the stock reference binaries (oracle/_ref/nhw-enc, nhw-dec) answered to these command lines and files: recorded in
+# tests/golden/ref_record.json by tests/golden/make_ref_golden.py
+ENC_ARGS = [["-q99", "a.bmp", "b.nhw"], ["-qx", "a.bmp", "b.nhw"], ["-z", "a", "b"], ["only_one"], ["same", "same"], ["-h"]]
+BAD_BMPS = {"nosig.bmp": b"XX" + bytes(60), "short.bmp": b"BM" + bytes(10),
+            "wrongsize.bmp": b"BM" + bytes(8) + (54).to_bytes(4, "little") + (40).to_bytes(4, "little") + (256).to_bytes(4, "little") + (256).to_bytes(4, "little") + (1).to_bytes(2, "little") + (24).to_bytes(2, "little") + bytes(4)}
+DEC_ARGS = [[], ["only_one.nhw"]]
+
+
+@pytest.fixture(scope="module")
+def cli_record(ref_record):
+    return ref_record["cli"]
+
+
+@pytest.mark.parametrize("args", ENC_ARGS)
+def test_cli_argument_handling_matches_reference_binary(cli, cli_record, args):
     rc, out, err = _run(cli, *args)
-    rrc, rout, rerr = _run(REF_CLI, *args)
-    assert rc == rrc
-    assert out.splitlines()[:1] == rout.splitlines()[:1] and err == rerr
+    want = cli_record["enc_args"][" ".join(args)]
+    assert rc == want["rc"]
+    assert out.splitlines()[:1] == want["stdout_lines"][:1] and err == want["stderr"]
 
 
 def test_cli_rejects_unimplemented_quality_loudly(cli):
@@ -127,17 +138,13 @@ def test_cli_rejects_malformed_device_lists_and_chunks(cli, tmp_path, args, msg)
     assert not list(tmp_path.iterdir())
 
 
-def test_cli_bad_bmp_exit_codes_match_reference(cli, tmp_path):
-    if not os.path.exists(REF_CLI):
-        pytest.skip("reference binary not built")
-    cases = {"nosig.bmp": b"XX" + bytes(60), "short.bmp": b"BM" + bytes(10),
-             "wrongsize.bmp": b"BM" + bytes(8) + (54).to_bytes(4, "little") + (40).to_bytes(4, "little") + (256).to_bytes(4, "little") + (256).to_bytes(4, "little") + (1).to_bytes(2, "little") + (24).to_bytes(2, "little") + bytes(4)}
-    for name, data in cases.items():
+def test_cli_bad_bmp_exit_codes_match_reference(cli, cli_record, tmp_path):
+    for name, data in BAD_BMPS.items():
         p = tmp_path / name
         p.write_bytes(data)
         rc, out, _ = _run(cli, str(p), str(tmp_path / "o.nhw"))
-        rrc, rout, _ = _run(REF_CLI, str(p), str(tmp_path / "r.nhw"))
-        assert (rc, out) == (rrc, rout), name
+        want = cli_record["bad_bmp"][name]
+        assert (rc, out) == (want["rc"], want["stdout"]), name
 
 
 @pytest.mark.gpu
@@ -208,14 +215,12 @@ def dec_cli():
     return DEC_CLI
 
 
-def test_dec_cli_usage_matches_reference_binary(dec_cli):
-    if not os.path.exists(REF_DEC_CLI):
-        pytest.skip("reference binary not built")
-    for args in ([], ["only_one.nhw"]):
+def test_dec_cli_usage_matches_reference_binary(dec_cli, cli_record):
+    for args in DEC_ARGS:
         rc, out, err = _run(dec_cli, *args)
-        rrc, rout, rerr = _run(REF_DEC_CLI, *args)
-        assert rc == rrc == 0
-        assert out.splitlines()[:5] == rout.splitlines()[:5] and err == rerr
+        want = cli_record["dec_args"][" ".join(args)]
+        assert rc == want["rc"] == 0
+        assert out.splitlines()[:5] == want["stdout_lines"][:5] and err == want["stderr"]
 
 
 @pytest.mark.gpu
