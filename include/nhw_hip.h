@@ -39,7 +39,8 @@ enum {
 	NHW_E_SPACE = -3,     /* output arena too small */
 	NHW_E_ARG = -4,
 	NHW_E_HIP = -5,       /* a HIP call failed; see nhw_last_error() */
-	NHW_E_FORMAT = -6     /* decoder: not a well-formed .nhw file (the reference prints "Not an .nhw file" and exits, or reads out of bounds) */
+	NHW_E_FORMAT = -6,    /* decoder: not a well-formed .nhw file (the reference prints "Not an .nhw file" and exits, or reads out of bounds) */
+	NHW_E_BUDGET = -7     /* nhw_enc_fit_batch*: no quality of the ladder gives a file within the image's byte budget */
 };
 
 typedef struct nhw_enc nhw_enc;
@@ -100,6 +101,34 @@ void  nhw_host_free(void *p);
 int   nhw_device_count(void);
 
 int nhw_enc_last_timing(nhw_enc *e, nhw_timing *t);
+
+/* ---- encode to a byte budget: a per-image quality search on the device ----
+ * ladder: host array of ladder_len (1..23) distinct qualities 1..23, tried in order; NULL (with ladder_len 0) = 23, 22, ..., 1.
+ * For every image the result is the .nhw file of the FIRST rung whose encode succeeds (NHW_OK) with a size <= that image's budget,
+ * byte-identical to what nhw_enc_batch_device gives for the image at that quality; d_quality[i] = that quality.  A rung where the image
+ * reports NHW_E_CODEBOOK does not fit and the search goes on down the ladder.  The search is exact: file size is not monotonic in
+ * quality, and no rung is skipped on a guess.  If no rung fits, slot i holds the outputs of the LAST rung (file, size, quality) with
+ * status NHW_E_BUDGET -- or NHW_E_CODEBOOK and size 0 if that rung overflowed the code book.
+ * Each rung encodes only the images still open, as one batch at that rung's quality; rungs after the first gather those images out of
+ * d_bgr (which must be 16-byte aligned) into a staging slab first.  The handle's compat mode applies to every rung.
+ * d_max_bytes: n budgets in device memory (indexed like the images); d_out / d_sizes / d_status / d_quality as in nhw_enc_batch_device.
+ * Bad arguments are refused before anything is launched: a duplicate or out-of-range ladder entry NHW_E_QUALITY; NULL pointers, n outside
+ * 1..max_batch, ladder_len outside 0..23 (0 only with ladder NULL), a handle with nhw_debug_stop_after set, or a stream being captured
+ * NHW_E_ARG.
+ * NOT asynchronous: after every rung but the last the call waits on `stream` for the number of images still open (the search stops when
+ * it reaches 0), so it cannot be captured in a graph.  After it, nhw_enc_last_timing and nhw_stage_chroma_l1 see the last rung's encode.
+ * The first fit call on a handle allocates the search's buffers for max_batch images (1.3 MB per image: a staging input and output slot);
+ * that one call pays for it, later ones do not allocate. */
+int nhw_enc_fit_batch_device(nhw_enc *e, const void *d_bgr, int n, const uint32_t *d_max_bytes, const int *ladder, int ladder_len,
+                             void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, void *stream);
+/* host convenience: H2D of the images and budgets (max_bytes: n entries, host), the search, then the files compacted and brought back
+ * like nhw_enc_batch does (out_off n+1 entries; status, quality n entries).  Synchronous. */
+int nhw_enc_fit_batch(nhw_enc *e, const uint8_t *bgr, int n, const uint32_t *max_bytes, const int *ladder, int ladder_len,
+                      uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality);
+/* the last fit call: rungs run, the quality and the number of images encoded at each rung (ladder order), and the wall time between
+ * its first and its last event on the stream */
+typedef struct { int rungs; int quality[23]; int images[23]; float total_ms; } nhw_fit_stats;
+int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s);
 
 /* ---- stage-level entry points (kernel parity tests; same stream rules) ----
  * colour + 4:2:0 (colorspace.c:55-260), any quality 1..23: d_y n*262144 int16, d_u/d_v n*65536 uint8 */

@@ -6,6 +6,7 @@ used only as plumbing: device buffers, streams, torch.distributed.  There is no 
 library is missing or no GPU is visible, construction fails.
 """
 import ctypes
+import numbers
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -15,12 +16,18 @@ OUT_STRIDE = 512 << 10
 QUALITY_DEFAULT = 20          # reference nhw_encoder_cli.c:95 (NORM)
 # per-image / call status (include/nhw_hip.h)
 NHW_OK, NHW_E_QUALITY, NHW_E_CODEBOOK, NHW_E_SPACE, NHW_E_ARG, NHW_E_HIP, NHW_E_FORMAT = 0, -1, -2, -3, -4, -5, -6
+NHW_E_BUDGET = -7             # encode_fit*: no quality of the ladder fits the image's byte budget
 
 P = ctypes.c_void_p
 
 
 class Timing(ctypes.Structure):
     _fields_ = [(n, ctypes.c_float) for n in ("total_ms", "front_ms", "color_dwt_ms", "luma_ms", "chroma_ms", "entropy_ms")] + [("parts", ctypes.c_int), ("front_images", ctypes.c_int), ("prefilter_ms", ctypes.c_float)]
+
+
+class FitStats(ctypes.Structure):
+    """the last fit call (nhw_fit_stats): rungs run, quality and images encoded at each rung (ladder order), wall time"""
+    _fields_ = [("rungs", ctypes.c_int), ("quality", ctypes.c_int * 23), ("images", ctypes.c_int * 23), ("total_ms", ctypes.c_float)]
 
 
 class NhwError(RuntimeError):
@@ -49,6 +56,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_host_alloc.argtypes = [ctypes.c_size_t]
     L.nhw_host_free.argtypes = [P]
     L.nhw_device_count.restype = ctypes.c_int
+    L.nhw_enc_fit_batch_device.argtypes = [P, P, ctypes.c_int, P, P, ctypes.c_int, P, P, P, P, P]
+    L.nhw_enc_fit_batch.argtypes = [P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P]
+    L.nhw_enc_last_fit_stats.argtypes = [P, ctypes.POINTER(FitStats)]
     L.nhw_stage_color.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P]
     L.nhw_stage_prefilter.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_chroma_l1.argtypes = [P, ctypes.c_int, P]
@@ -140,6 +150,77 @@ class Encoder:
         if (status != 0).any():
             raise NhwError(f"per-image status {status.tolist()}")
         return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+
+    @staticmethod
+    def _ladder(ladder):
+        """-> (ctypes int array or None, length); None = the library's default ladder 23, 22, ..., 1"""
+        if ladder is None:
+            return None, 0
+        ladder = [int(q) for q in ladder]
+        return (ctypes.c_int * len(ladder))(*ladder), len(ladder)
+
+    def encode_fit_device(self, bgr, max_bytes, ladder=None, out=None):
+        """The best picture within a byte budget: for image i the file of the first quality of `ladder` (default 23, 22, ..., 1) whose
+        encode succeeds with at most max_bytes[i] bytes, identical to encode_device at that quality (nhw_enc_fit_batch_device).
+        bgr as for encode_device; max_bytes: an int for every image, or a contiguous int32 / uint32 CUDA tensor [n] (read as uint32).
+        Returns (out[n,OUT_STRIDE], sizes[n], status[n], quality[n]) on the device; status NHW_E_BUDGET where no rung fits (the slot
+        then holds the last rung's file).  Waits on the host between rungs: not for graph capture."""
+        t = self.torch
+        if not (bgr.is_cuda and bgr.dtype == t.uint8 and bgr.is_contiguous() and bgr.dim() == 4 and tuple(bgr.shape[1:]) == (512, 512, 3)):
+            raise NhwError("encode_fit_device wants a contiguous uint8 CUDA tensor of shape [n, 512, 512, 3]")
+        if bgr.device.index != self.device:
+            raise NhwError(f"the batch is on cuda:{bgr.device.index}, this encoder on cuda:{self.device}")
+        n = bgr.shape[0]
+        dev = f"cuda:{self.device}"
+        if isinstance(max_bytes, numbers.Integral):
+            if max_bytes < 0:
+                raise NhwError(f"max_bytes must not be negative, got {max_bytes}")
+            budget = t.full((n,), min(int(max_bytes), 2**31 - 1), dtype=t.int32, device=dev)   # (a file is at most OUT_STRIDE bytes)
+        else:
+            budget = max_bytes
+            if not (isinstance(budget, t.Tensor) and budget.dtype in (t.int32, getattr(t, "uint32", t.int32)) and budget.is_cuda
+                    and budget.device.index == self.device and budget.is_contiguous() and budget.numel() == n):
+                raise NhwError("encode_fit_device: max_bytes must be an int or a contiguous int32 / uint32 tensor [n] on this encoder's device")
+        if out is None:
+            out = self.alloc_out(n) + (t.empty(n, dtype=t.int32, device=dev),)
+        o, sizes, status, quality = out
+        for t_, dt_, cnt_ in ((o, t.uint8, n * OUT_STRIDE), (sizes, t.int32, n), (status, t.int32, n), (quality, t.int32, n)):
+            if not (t_.is_cuda and t_.device.index == self.device and t_.dtype == dt_ and t_.is_contiguous() and t_.numel() >= cnt_):
+                raise NhwError("encode_fit_device: output tensors must be contiguous, on this encoder's device, uint8 [n, OUT_STRIDE] / int32 [n] x 3")
+        lad, lad_n = self._ladder(ladder)
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_enc_fit_batch_device(self.h, bgr.data_ptr(), n, budget.data_ptr(), lad, lad_n, o.data_ptr(), sizes.data_ptr(),
+                                                        status.data_ptr(), quality.data_ptr(), st))
+        return o, sizes, status, quality
+
+    def encode_fit(self, images, max_bytes, ladder=None):
+        """images: numpy uint8 [n,512,512,3] on the host; max_bytes: an int or n ints -> (files, qualities, status), lists of n.
+        A per-image NHW_E_BUDGET (files[i] = the last rung's file) or NHW_E_CODEBOOK (files[i] = b"") is reported, not raised."""
+        import numpy as np
+        images = np.asarray(images)
+        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (512, 512, 3):
+            raise NhwError(f"encode_fit wants uint8 [n, 512, 512, 3] (BMP file order), got {images.dtype} {images.shape}")
+        images = np.ascontiguousarray(images)
+        n = images.shape[0]
+        mb = np.asarray(max_bytes, dtype=np.int64)
+        if mb.ndim == 0:
+            mb = np.full(n, int(mb), np.int64)
+        if mb.shape != (n,) or (mb < 0).any():
+            raise NhwError(f"max_bytes must be one non-negative int or {n} of them")
+        budget = np.minimum(mb, 2**32 - 1).astype(np.uint32)
+        arena = np.empty(n * OUT_STRIDE, np.uint8)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        quality = np.empty(n, np.int32)
+        lad, lad_n = self._ladder(ladder)
+        self._chk(self.lib.nhw_enc_fit_batch(self.h, images.ctypes.data, n, budget.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size,
+                                             offs.ctypes.data, status.ctypes.data, quality.ctypes.data))
+        return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)], quality.tolist(), status.tolist()
+
+    def fit_stats(self) -> FitStats:
+        s = FitStats()
+        self._chk(self.lib.nhw_enc_last_fit_stats(self.h, ctypes.byref(s)))
+        return s
 
     def encode_tiled(self, big, quality: int = QUALITY_DEFAULT):
         """a picture whose sides are multiples of 512 -> (list of .nhw byte strings, one per tile, row-major, (ny, nx)); `nhw-enc --tiles`"""

@@ -40,6 +40,12 @@ void nhw_launch_low_prefilter_chroma(const uint8_t *src, size_t src_stride, int1
 void nhw_launch_low_chroma_thin(int16_t *plane, size_t plane_stride, int n, hipStream_t s);
 void nhw_launch_low_ll2(int16_t *proc, size_t plane_stride, int q, int n, hipStream_t s);
 
+/* the byte-budget search (nhw_fit.hip) */
+void nhw_launch_fit_gather(const uint8_t *d_bgr, const int *idx, int m, uint8_t *staging, hipStream_t s);
+void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const uint32_t *budget,
+                           int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status, int32_t *qual, uint8_t *open, hipStream_t s);
+void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *next, int *count, hipStream_t s);
+
 int nhw_front_set_attrs(const char **where);   /* nhw_front.hip, nhw_tail.hip: dynamic-LDS opt-ins of the device the handle lives on */
 int nhw_tail_set_attrs(const char **where);
 static thread_local std::string g_err;
@@ -75,6 +81,17 @@ struct nhw_enc {
 	int front_fallback; /* debug: every row / segment of the pre-filter carry takes its exact fallback path (tests) */
 	int stop_after;   /* debug: leave the batch driver after this many stages (0 = run everything) */
 	int last_n, last_q; /* images and quality of the last whole batch (nhw_stage_chroma_l1 works on what it left in the 4:2:0 planes) */
+	/* the byte-budget search (nhw_enc_fit_batch_device): allocated for max_batch images by the first fit call */
+	uint8_t *d_fit_in, *d_fit_out;           /* staging: the gathered open images, the files of their rung */
+	uint32_t *d_fit_sizes, *d_fit_budget;    /* (the budgets: the host path's upload) */
+	int32_t *d_fit_status, *d_fit_quality;   /* (the qualities: the host path's) */
+	int *d_fit_idx[2], *d_fit_count;         /* the open list of this rung and of the next; its length */
+	uint8_t *d_fit_open;                     /* per list entry: still open after this rung */
+	int *h_fit_count;                        /* page-locked */
+	hipEvent_t fit_ev[2];
+	bool fit_ready;
+	nhw_fit_stats fit_stats;
+	bool fit_done;
 };
 
 static const size_t k_buf_bytes[B_COUNT] = {
@@ -112,6 +129,7 @@ extern "C" int nhw_enc_set_compat(nhw_enc *e, int mode)
 
 extern "C" void nhw_enc_destroy(nhw_enc *e);
 static int host_buffers(nhw_enc *e, int n);
+static void fit_free(nhw_enc *e);
 /* device bytes per image of the host path's staging (nhw_enc_batch / nhw_enc_synth_batch): input slot, output slot, compacted output */
 #define HOST_PATH_BYTES ((size_t)NHW_IMG_BYTES + 2 * (size_t)NHW_OUT_STRIDE + 24)
 extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_enc **out)
@@ -187,6 +205,7 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	if (e->d_sizes) (void)hipFree(e->d_sizes);
 	if (e->d_status) (void)hipFree(e->d_status);
 	if (e->d_offs) (void)hipFree(e->d_offs);
+	fit_free(e);
 	for (int i = 0; i < 7; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
 	if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
 	for (int i = 0; i < 4; i++) if (e->part_stream[i]) (void)hipStreamDestroy(e->part_stream[i]);
@@ -564,6 +583,154 @@ extern "C" int nhw_enc_synth_batch(nhw_enc *e, int n, uint32_t seed_base, int qu
 	HIPCHK(hipGetLastError());
 	{ const int rc = nhw_enc_batch_device(e, e->d_in, n, quality, e->d_out, e->d_sizes, e->d_status, e->own_stream); if (rc) return rc; }
 	return host_download(e, n, out_arena, arena_cap, out_off, status);
+}
+
+/* ------------------------------------------------------------------------------------------------ encode to a byte budget */
+/* device bytes per image of the search's buffers: staging input and output slot, staging size / status, two list entries, budget,
+ * quality, open flag */
+#define FIT_BYTES ((size_t)NHW_IMG_BYTES + (size_t)NHW_OUT_STRIDE + 4 * 7 + 1)
+
+static void fit_free(nhw_enc *e)
+{
+	void *dev[] = { e->d_fit_in, e->d_fit_out, e->d_fit_sizes, e->d_fit_budget, e->d_fit_status, e->d_fit_quality, e->d_fit_idx[0], e->d_fit_idx[1],
+	                e->d_fit_count, e->d_fit_open };
+	for (void *p : dev) if (p) (void)hipFree(p);
+	if (e->h_fit_count) (void)hipHostFree(e->h_fit_count);
+	for (int k = 0; k < 2; k++) if (e->fit_ev[k]) (void)hipEventDestroy(e->fit_ev[k]);
+	e->d_fit_in = e->d_fit_out = nullptr; e->d_fit_sizes = e->d_fit_budget = nullptr; e->d_fit_status = e->d_fit_quality = nullptr;
+	e->d_fit_idx[0] = e->d_fit_idx[1] = e->d_fit_count = nullptr; e->d_fit_open = nullptr; e->h_fit_count = nullptr;
+	e->fit_ev[0] = e->fit_ev[1] = nullptr;
+	e->fit_ready = false;
+}
+
+/* the search's buffers for max_batch images, on the first fit call; a failure half-way leaves none behind */
+static int fit_buffers(nhw_enc *e)
+{
+	if (e->fit_ready) return NHW_OK;
+	const size_t mb = (size_t)e->max_batch;
+	size_t free_b = 0, total_b = 0;
+	HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const size_t need = FIT_BYTES * mb;
+	if (need > free_b) {
+		char b[200];
+		snprintf(b, sizeof b, "budget search buffers for max_batch %d need %zu MiB (%.1f MiB per image), %zu MiB of HBM are free", e->max_batch, need >> 20, (double)need / mb / 1048576.0, free_b >> 20);
+		g_err = b;
+		return NHW_E_ARG;
+	}
+	const int rc = [&]() -> int {
+		HIPCHK(hipMalloc((void **)&e->d_fit_in, mb * NHW_IMG_BYTES));
+		HIPCHK(hipMalloc((void **)&e->d_fit_out, mb * NHW_OUT_STRIDE));
+		HIPCHK(hipMalloc((void **)&e->d_fit_sizes, mb * sizeof(uint32_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_budget, mb * sizeof(uint32_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_status, mb * sizeof(int32_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_quality, mb * sizeof(int32_t)));
+		for (int k = 0; k < 2; k++) HIPCHK(hipMalloc((void **)&e->d_fit_idx[k], mb * sizeof(int)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_count, sizeof(int)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_open, mb));
+		HIPCHK(hipHostMalloc((void **)&e->h_fit_count, sizeof(int), hipHostMallocDefault));
+		for (int k = 0; k < 2; k++) HIPCHK(hipEventCreate(&e->fit_ev[k]));
+		return NHW_OK;
+	}();
+	if (rc != NHW_OK) { fit_free(e); return rc; }
+	e->fit_ready = true;
+	return NHW_OK;
+}
+
+/* everything a fit call can refuse without touching the device; fills the ladder (NULL = 23 .. 1) */
+static int fit_args(nhw_enc *e, int n, const int *ladder, int ladder_len, int q[23], int *len)
+{
+	if (n < 1 || n > e->max_batch || ladder_len < 0 || ladder_len > 23 || (ladder_len == 0) != (ladder == nullptr)) { g_err = "bad argument"; return NHW_E_ARG; }
+	if (e->stop_after) { g_err = "nhw_enc_fit_batch: not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
+	*len = ladder ? ladder_len : 23;
+	bool seen[24] = {};
+	for (int r = 0; r < *len; r++) {
+		q[r] = ladder ? ladder[r] : 23 - r;
+		if (!nhw_quality_supported(q[r]) || seen[q[r]]) { g_err = "ladder: qualities must be distinct and in 1..23"; return NHW_E_QUALITY; }
+		seen[q[r]] = true;
+	}
+	return NHW_OK;
+}
+
+/* Top-down walk of the ladder.  Rung 1 encodes the whole batch straight into the caller's slots (the open list is the identity); every
+ * later rung gathers the still-open images from d_bgr (by original index: never from a staging slot, so nothing is copied onto itself),
+ * encodes them as a batch of their own into the staging output and copies the files of the images that close into the caller's slots.
+ * Between rungs the open list is compacted on the device and its length waited for on the host. */
+extern "C" int nhw_enc_fit_batch_device(nhw_enc *e, const void *d_bgr, int n, const uint32_t *d_max_bytes, const int *ladder, int ladder_len,
+                                        void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	if (!e || !d_bgr || !d_max_bytes || !d_out || !d_sizes || !d_status || !d_quality) { g_err = "bad argument"; return NHW_E_ARG; }
+	if ((uintptr_t)d_bgr & 15) { g_err = "nhw_enc_fit_batch_device: d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
+	int q[23], len = 0;
+	{ const int rc = fit_args(e, n, ladder, ladder_len, q, &len); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	{ hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	  HIPCHK(hipStreamIsCapturing(s, &cs));
+	  if (cs != hipStreamCaptureStatusNone) { g_err = "nhw_enc_fit_batch_device waits on the host between rungs and cannot be captured"; return NHW_E_ARG; } }
+	{ const int rc = fit_buffers(e); if (rc) return rc; }
+	e->fit_done = false;
+	nhw_fit_stats st;
+	memset(&st, 0, sizeof st);
+	const uint32_t *budget = d_max_bytes;
+	uint8_t *out = (uint8_t *)d_out;
+	int m = n, cur = 0;
+	HIPCHK(hipEventRecord(e->fit_ev[0], s));
+	for (int r = 0; r < len; r++) {
+		const bool first = r == 0, last = r == len - 1;
+		const int *idx = first ? nullptr : e->d_fit_idx[cur];
+		st.quality[r] = q[r]; st.images[r] = m; st.rungs = r + 1;
+		if (first) {
+			const int rc = nhw_enc_batch_device(e, d_bgr, m, q[r], d_out, d_sizes, d_status, s);
+			if (rc) return rc;
+		} else {
+			nhw_launch_fit_gather((const uint8_t *)d_bgr, idx, m, e->d_fit_in, s);
+			HIPCHK(hipGetLastError());
+			const int rc = nhw_enc_batch_device(e, e->d_fit_in, m, q[r], e->d_fit_out, e->d_fit_sizes, e->d_fit_status, s);
+			if (rc) return rc;
+		}
+		nhw_launch_fit_select(idx, m, e->d_fit_out, e->d_fit_sizes, e->d_fit_status, budget, q[r], last, out, d_sizes, d_status, d_quality, e->d_fit_open, s);
+		HIPCHK(hipGetLastError());
+		if (last) break;
+		nhw_launch_fit_compact(e->d_fit_open, idx, m, e->d_fit_idx[cur ^ 1], e->d_fit_count, s);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(e->h_fit_count, e->d_fit_count, sizeof(int), hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+		m = *e->h_fit_count;
+		cur ^= 1;
+		if (m == 0) break;
+	}
+	HIPCHK(hipEventRecord(e->fit_ev[1], s));
+	e->fit_stats = st;
+	e->fit_done = true;
+	return NHW_OK;
+}
+
+extern "C" int nhw_enc_fit_batch(nhw_enc *e, const uint8_t *bgr, int n, const uint32_t *max_bytes, const int *ladder, int ladder_len,
+                                 uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality)
+{
+	if (!e || !bgr || !max_bytes || !out_arena || !out_off || !status || !quality) { g_err = "bad argument"; return NHW_E_ARG; }
+	int q[23], len = 0;
+	{ const int rc = fit_args(e, n, ladder, ladder_len, q, &len); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, n); if (rc) return rc; }
+	{ const int rc = fit_buffers(e); if (rc) return rc; }
+	hipStream_t s = e->own_stream;
+	HIPCHK(hipMemcpyAsync(e->d_in, bgr, (size_t)n * NHW_IMG_BYTES, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(e->d_fit_budget, max_bytes, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+	{ const int rc = nhw_enc_fit_batch_device(e, e->d_in, n, e->d_fit_budget, ladder, ladder_len, e->d_out, e->d_sizes, e->d_status, e->d_fit_quality, s); if (rc) return rc; }
+	{ const int rc = host_download(e, n, out_arena, arena_cap, out_off, status); if (rc) return rc; }
+	HIPCHK(hipMemcpy(quality, e->d_fit_quality, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+	return NHW_OK;
+}
+
+extern "C" int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s)
+{
+	if (!e || !s || !e->fit_done) { g_err = "no completed fit call"; return NHW_E_ARG; }
+	HIPCHK(hipSetDevice(e->device));
+	HIPCHK(hipEventSynchronize(e->fit_ev[1]));
+	*s = e->fit_stats;
+	HIPCHK(hipEventElapsedTime(&s->total_ms, e->fit_ev[0], e->fit_ev[1]));
+	return NHW_OK;
 }
 
 /* ------------------------------------------------------------------------------------------------ stage entry points */
