@@ -40,10 +40,11 @@ enum {
 	NHW_E_ARG = -4,
 	NHW_E_HIP = -5,       /* a HIP call failed; see nhw_last_error() */
 	NHW_E_FORMAT = -6,    /* decoder: not a well-formed .nhw file (the reference prints "Not an .nhw file" and exits, or reads out of bounds) */
-	NHW_E_BUDGET = -7     /* nhw_enc_fit_batch*: no quality of the ladder gives a file within the image's byte budget */
+	NHW_E_BUDGET = -7     /* nhw_enc_fit_batch*, nhw_enc_fit_sse_batch*: no quality of the ladder gives a file within the image's byte or distortion budget */
 };
 
 typedef struct nhw_enc nhw_enc;
+typedef struct nhw_dec nhw_dec;
 
 /* stage timings of the last nhw_enc_batch_device call, measured with hipEvents on the launch stream */
 typedef struct {
@@ -130,6 +131,36 @@ int nhw_enc_fit_batch(nhw_enc *e, const uint8_t *bgr, int n, const uint32_t *max
 typedef struct { int rungs; int quality[23]; int images[23]; float total_ms; } nhw_fit_stats;
 int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s);
 
+/* ---- distortion: the sum of squared differences (SSE) over all NHW_IMG_BYTES bytes of a picture, B, G and R together ----
+ * d_a, d_b: n pictures each (n*NHW_IMG_BYTES bytes, 16-byte aligned); d_sse[i] = the exact SSE of picture i of d_a against picture i of
+ * d_b (at most 786432 * 255^2, beyond 32 bits).  PSNR = 10 log10(255^2 * 786432 / SSE).  No handle: the launch goes to the calling
+ * thread's current device; stream NULL is the null stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers,
+ * n outside 1..65535, unaligned pictures or a d_sse that is not 8-byte aligned. */
+int nhw_sse_batch_device(const void *d_a, const void *d_b, int n, uint64_t *d_sse, void *stream);
+
+/* ---- encode to a distortion budget: a per-image quality search on the device, with a decode and an error pass per rung ----
+ * The byte-budget search's walk (above) with a different test for "fits".  ladder: as there, but NULL (with ladder_len 0) = 1, 2, ..., 23,
+ * so by default the answer is the lowest quality that reaches the target.  d_max_sse: n targets in device memory.  For every image the
+ * result is the .nhw file of the FIRST rung whose encode returns NHW_OK and whose decode (by the decoder handle d, the device decoder
+ * that is bit-exact against the reference's) returns NHW_OK with an SSE against the input picture <= d_max_sse[i]; the file is
+ * byte-identical to what nhw_enc_batch_device gives at that quality, d_quality[i] = that quality and d_sse[i] = that SSE.  Neither the
+ * PSNR nor the size is monotonic in quality, so no rung is skipped on a guess.  If no rung meets the target, slot i holds the LAST rung's
+ * outputs (file, size, quality, SSE) with status NHW_E_BUDGET -- NHW_E_CODEBOOK, size 0 and SSE UINT64_MAX if that rung overflowed the
+ * code book, NHW_E_FORMAT (SSE UINT64_MAX) if the decoder refused the encoder's file.
+ * Per rung: the open images are encoded as one batch, the rung's files decoded as one batch by d on `stream` into a buffer of the
+ * search, the SSE of every open image computed, and the images that meet their target closed.  Arguments are refused as for
+ * nhw_enc_fit_batch_device, with the same codes, and NHW_E_ARG also when d is NULL, d's max_batch is below n, d is on another device than
+ * e, or d has a debug stop set.  NOT asynchronous: the call waits on `stream` after every rung but the last, so it cannot be captured in
+ * a graph.  After it, nhw_enc_last_fit_stats describes it as for the byte search, nhw_enc_last_timing sees the last rung's encode and
+ * nhw_dec_last_timing the last rung's decode.  The first call of this kind on a handle allocates, besides the byte search's buffers, a
+ * decoded picture per image for max_batch images (0.75 MB each); byte-budget callers never allocate it. */
+int nhw_enc_fit_sse_batch_device(nhw_enc *e, nhw_dec *d, const void *d_bgr, int n, const uint64_t *d_max_sse, const int *ladder, int ladder_len,
+                                 void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, uint64_t *d_sse, void *stream);
+/* host convenience: H2D of the images and targets (max_sse: n entries, host), the search, then the files compacted and brought back like
+ * nhw_enc_batch does (out_off n+1 entries; status, quality, sse n entries).  Synchronous. */
+int nhw_enc_fit_sse_batch(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
+                          uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse);
+
 /* ---- stage-level entry points (kernel parity tests; same stream rules) ----
  * colour + 4:2:0 (colorspace.c:55-260), any quality 1..23: d_y n*262144 int16, d_u/d_v n*65536 uint8 */
 int nhw_stage_color(nhw_enc *e, const void *d_bgr, int n, int quality, void *d_y, void *d_u, void *d_v, void *stream);
@@ -163,7 +194,6 @@ int nhw_stage_chroma_l1(nhw_enc *e, int n, void *stream);
  * arena is such an arena with d_off[i] = i*NHW_OUT_STRIDE and d_len = d_sizes).  d_bgr: n*NHW_IMG_BYTES,
  * the pixel bytes in the order nhw-dec writes them behind its 54-byte header (nhw_dec_bmp_header).  d_status[i] =
  * NHW_OK / NHW_E_FORMAT, d_quality[i] (may be NULL) = the quality setting stored in file i.  Asynchronous on `stream`. */
-typedef struct nhw_dec nhw_dec;
 int  nhw_dec_create(int device, int max_batch, nhw_dec **out);
 void nhw_dec_destroy(nhw_dec *d);
 const char *nhw_dec_last_error(void);

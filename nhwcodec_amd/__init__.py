@@ -16,7 +16,8 @@ OUT_STRIDE = 512 << 10
 QUALITY_DEFAULT = 20          # reference nhw_encoder_cli.c:95 (NORM)
 # per-image / call status (include/nhw_hip.h)
 NHW_OK, NHW_E_QUALITY, NHW_E_CODEBOOK, NHW_E_SPACE, NHW_E_ARG, NHW_E_HIP, NHW_E_FORMAT = 0, -1, -2, -3, -4, -5, -6
-NHW_E_BUDGET = -7             # encode_fit*: no quality of the ladder fits the image's byte budget
+NHW_E_BUDGET = -7             # encode_fit*: no quality of the ladder fits the image's byte or distortion budget
+PEAK_SSE_NUMERATOR = 65025 * IMG_BYTES   # 255^2 * 786432: PSNR = 10 log10(PEAK_SSE_NUMERATOR / SSE)
 
 P = ctypes.c_void_p
 
@@ -59,12 +60,59 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_enc_fit_batch_device.argtypes = [P, P, ctypes.c_int, P, P, ctypes.c_int, P, P, P, P, P]
     L.nhw_enc_fit_batch.argtypes = [P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P]
     L.nhw_enc_last_fit_stats.argtypes = [P, ctypes.POINTER(FitStats)]
+    L.nhw_sse_batch_device.argtypes = [P, P, ctypes.c_int, P, P]
+    L.nhw_enc_fit_sse_batch_device.argtypes = [P, P, P, ctypes.c_int, P, P, ctypes.c_int, P, P, P, P, P, P]
+    L.nhw_enc_fit_sse_batch.argtypes = [P, P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P, P]
     L.nhw_stage_color.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P, P, P, P]
     L.nhw_stage_prefilter.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_chroma_l1.argtypes = [P, ctypes.c_int, P]
     L.nhw_stage_analysis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_synthesis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, P]
     return L
+
+
+_LIB = None
+
+
+def _library():
+    global _LIB
+    if _LIB is None:
+        _LIB = load_library()
+    return _LIB
+
+
+def psnr_to_max_sse(db):
+    """the largest SSE whose PSNR is at least `db`: floor(65025 * 786432 * 10**(-db/10)) in float64, for finite db > 0.  A number gives an int,
+    an array (or list) of them an int64 numpy array."""
+    import numpy as np
+    try:
+        a = np.asarray(db, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise NhwError(f"a PSNR target must be a finite number of dB above 0, got {db!r}") from None
+    if a.size == 0 or not np.all(np.isfinite(a)) or not np.all(a > 0):
+        raise NhwError(f"a PSNR target must be a finite number of dB above 0, got {db!r}")
+    m = np.floor(float(PEAK_SSE_NUMERATOR) * np.power(10.0, -a / 10.0)).astype(np.int64)
+    return int(m) if m.ndim == 0 else m
+
+
+def sse_device(a, b):
+    """The exact sum of squared differences of every picture of `a` against the same picture of `b` (nhw_sse_batch_device): two contiguous
+    uint8 CUDA tensors of n * 786432 bytes each (e.g. [n, 512, 512, 3]) on one device, 16-byte aligned -> int64 tensor [n] on that device.
+    Ordered on torch's current stream."""
+    import torch
+    for name, x in (("a", a), ("b", b)):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous() and x.numel() > 0 and x.numel() % IMG_BYTES == 0):
+            raise NhwError(f"sse_device: `{name}` must be a contiguous uint8 CUDA tensor of n * {IMG_BYTES} bytes")
+    if a.numel() != b.numel() or a.device != b.device:
+        raise NhwError("sse_device: `a` and `b` must hold as many pictures, on one device")
+    n = a.numel() // IMG_BYTES
+    L = _library()
+    out = torch.empty(n, dtype=torch.int64, device=a.device)
+    with torch.cuda.device(a.device):
+        rc = L.nhw_sse_batch_device(a.data_ptr(), b.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream(a.device).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
 
 
 class Encoder:
@@ -216,6 +264,95 @@ class Encoder:
         self._chk(self.lib.nhw_enc_fit_batch(self.h, images.ctypes.data, n, budget.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size,
                                              offs.ctypes.data, status.ctypes.data, quality.ctypes.data))
         return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)], quality.tolist(), status.tolist()
+
+    def _max_sse(self, n, min_psnr, max_sse, what):
+        """the per-image SSE targets as a contiguous int64 CUDA tensor [n] (read as uint64) from exactly one of min_psnr / max_sse"""
+        import numpy as np
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        if (min_psnr is None) == (max_sse is None):
+            raise NhwError(f"{what}: give exactly one of min_psnr and max_sse")
+        if min_psnr is not None:
+            if isinstance(min_psnr, t.Tensor):
+                min_psnr = min_psnr.detach().cpu().numpy()
+            m = psnr_to_max_sse(min_psnr)
+            if isinstance(m, int):
+                return t.full((n,), m, dtype=t.int64, device=dev)
+            if m.shape != (n,):
+                raise NhwError(f"{what}: min_psnr must be one number or {n} of them")
+            return t.from_numpy(np.ascontiguousarray(m)).to(dev)
+        if isinstance(max_sse, numbers.Integral):
+            if max_sse < 0:
+                raise NhwError(f"max_sse must not be negative, got {max_sse}")
+            return t.full((n,), min(int(max_sse), 2**63 - 1), dtype=t.int64, device=dev)
+        if not (isinstance(max_sse, t.Tensor) and max_sse.dtype in (t.int64, getattr(t, "uint64", t.int64)) and max_sse.is_cuda
+                and max_sse.device.index == self.device and max_sse.is_contiguous() and max_sse.numel() == n):
+            raise NhwError(f"{what}: max_sse must be an int or a contiguous int64 / uint64 tensor [n] on this encoder's device")
+        return max_sse
+
+    def _decoder(self, decoder, n, what):
+        if not isinstance(decoder, Decoder) or not getattr(decoder, "h", None):
+            raise NhwError(f"{what} needs an open Decoder")
+        if decoder.device != self.device:
+            raise NhwError(f"{what}: the decoder is on cuda:{decoder.device}, this encoder on cuda:{self.device}")
+        if decoder.max_batch < n:
+            raise NhwError(f"{what}: the decoder's max_batch {decoder.max_batch} is below n = {n}")
+        return decoder.h
+
+    def encode_fit_psnr_device(self, bgr, decoder, min_psnr=None, max_sse=None, ladder=None, out=None):
+        """The smallest quality that looks good enough: for image i the file of the first quality of `ladder` (default 1, 2, ..., 23) whose
+        encode succeeds and whose decode by `decoder` (the bit-exact device decoder) is within image i's target, identical to encode_device at
+        that quality (nhw_enc_fit_sse_batch_device).  The target is given by exactly one of min_psnr (dB: a float, or float64 values per
+        image; see psnr_to_max_sse) and max_sse (the largest sum of squared differences over the picture's 786432 bytes: an int, or a
+        contiguous int64 / uint64 CUDA tensor [n], read as uint64).  bgr as for encode_device.
+        Returns (out[n,OUT_STRIDE], sizes[n], status[n], quality[n], sse[n]) on the device: sse int64, the achieved SSE (UINT64_MAX, i.e.
+        -1, where there is no decoded picture).  status NHW_E_BUDGET where no rung meets the target (the slot then holds the last rung's
+        file).  Waits on the host between rungs: not for graph capture."""
+        t = self.torch
+        what = "encode_fit_psnr_device"
+        if not (bgr.is_cuda and bgr.dtype == t.uint8 and bgr.is_contiguous() and bgr.dim() == 4 and tuple(bgr.shape[1:]) == (512, 512, 3)):
+            raise NhwError(f"{what} wants a contiguous uint8 CUDA tensor of shape [n, 512, 512, 3]")
+        if bgr.device.index != self.device:
+            raise NhwError(f"the batch is on cuda:{bgr.device.index}, this encoder on cuda:{self.device}")
+        n = bgr.shape[0]
+        dh = self._decoder(decoder, n, what)
+        target = self._max_sse(n, min_psnr, max_sse, what)
+        dev = f"cuda:{self.device}"
+        if out is None:
+            out = self.alloc_out(n) + (t.empty(n, dtype=t.int32, device=dev), t.empty(n, dtype=t.int64, device=dev))
+        o, sizes, status, quality, sse = out
+        for t_, dt_, cnt_ in ((o, t.uint8, n * OUT_STRIDE), (sizes, t.int32, n), (status, t.int32, n), (quality, t.int32, n), (sse, t.int64, n)):
+            if not (t_.is_cuda and t_.device.index == self.device and t_.dtype == dt_ and t_.is_contiguous() and t_.numel() >= cnt_):
+                raise NhwError(f"{what}: output tensors must be contiguous, on this encoder's device, uint8 [n, OUT_STRIDE] / int32 [n] x 3 / int64 [n]")
+        lad, lad_n = self._ladder(ladder)
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_enc_fit_sse_batch_device(self.h, dh, bgr.data_ptr(), n, target.data_ptr(), lad, lad_n, o.data_ptr(), sizes.data_ptr(),
+                                                            status.data_ptr(), quality.data_ptr(), sse.data_ptr(), st))
+        return o, sizes, status, quality, sse
+
+    def encode_fit_psnr(self, images, decoder, min_psnr, ladder=None):
+        """images: numpy uint8 [n,512,512,3] on the host; min_psnr: dB, one number or n of them -> (files, qualities, status, sse), lists of n.
+        A per-image NHW_E_BUDGET (files[i] = the last rung's file) or NHW_E_CODEBOOK (files[i] = b"", sse 2**64 - 1) is reported, not raised."""
+        import numpy as np
+        images = np.asarray(images)
+        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (512, 512, 3):
+            raise NhwError(f"encode_fit_psnr wants uint8 [n, 512, 512, 3] (BMP file order), got {images.dtype} {images.shape}")
+        images = np.ascontiguousarray(images)
+        n = images.shape[0]
+        dh = self._decoder(decoder, n, "encode_fit_psnr")
+        target = psnr_to_max_sse(min_psnr)
+        target = np.full(n, target, np.uint64) if isinstance(target, int) else target.astype(np.uint64)
+        if target.shape != (n,):
+            raise NhwError(f"encode_fit_psnr: min_psnr must be one number or {n} of them")
+        arena = np.empty(n * OUT_STRIDE, np.uint8)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        quality = np.empty(n, np.int32)
+        sse = np.empty(n, np.uint64)
+        lad, lad_n = self._ladder(ladder)
+        self._chk(self.lib.nhw_enc_fit_sse_batch(self.h, dh, images.ctypes.data, n, target.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size,
+                                                 offs.ctypes.data, status.ctypes.data, quality.ctypes.data, sse.ctypes.data))
+        return ([arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)], quality.tolist(), status.tolist(), [int(x) for x in sse])
 
     def fit_stats(self) -> FitStats:
         s = FitStats()

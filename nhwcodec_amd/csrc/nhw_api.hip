@@ -45,6 +45,12 @@ void nhw_launch_fit_gather(const uint8_t *d_bgr, const int *idx, int m, uint8_t 
 void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const uint32_t *budget,
                            int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status, int32_t *qual, uint8_t *open, hipStream_t s);
 void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *next, int *count, hipStream_t s);
+/* the distortion search (nhw_fit.hip, nhw_metric.hip, nhw_dec.hip) */
+void nhw_launch_fit_select_sse(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const int32_t *dec_status,
+                               const uint64_t *sse, const uint64_t *max_sse, int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status,
+                               int32_t *qual, uint64_t *sse_out, uint8_t *open, hipStream_t s);
+hipError_t nhw_launch_sse(const uint8_t *a, const uint8_t *b, int n, uint64_t *sse, hipStream_t s);
+void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after);
 
 int nhw_front_set_attrs(const char **where);   /* nhw_front.hip, nhw_tail.hip: dynamic-LDS opt-ins of the device the handle lives on */
 int nhw_tail_set_attrs(const char **where);
@@ -92,6 +98,13 @@ struct nhw_enc {
 	bool fit_ready;
 	nhw_fit_stats fit_stats;
 	bool fit_done;
+	/* the distortion search (nhw_enc_fit_sse_batch_device): allocated for max_batch images by the first SSE-fit call */
+	uint8_t *d_fit_px;                       /* the rung's decoded pictures */
+	uint64_t *d_fit_doff;                    /* decoder offsets: entry j at j * NHW_OUT_STRIDE (the caller's arena and the staging one alike) */
+	uint64_t *d_fit_sse, *d_fit_maxsse;      /* per list entry: the SSE of its picture; (the targets: the host path's upload) */
+	uint64_t *d_fit_sse_out;                 /* (the achieved SSE: the host path's) */
+	int32_t *d_fit_dstatus;                  /* per list entry: the decoder's status */
+	bool fit_sse_ready;
 };
 
 static const size_t k_buf_bytes[B_COUNT] = {
@@ -130,6 +143,7 @@ extern "C" int nhw_enc_set_compat(nhw_enc *e, int mode)
 extern "C" void nhw_enc_destroy(nhw_enc *e);
 static int host_buffers(nhw_enc *e, int n);
 static void fit_free(nhw_enc *e);
+static void fit_sse_free(nhw_enc *e);
 /* device bytes per image of the host path's staging (nhw_enc_batch / nhw_enc_synth_batch): input slot, output slot, compacted output */
 #define HOST_PATH_BYTES ((size_t)NHW_IMG_BYTES + 2 * (size_t)NHW_OUT_STRIDE + 24)
 extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_enc **out)
@@ -206,6 +220,7 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	if (e->d_status) (void)hipFree(e->d_status);
 	if (e->d_offs) (void)hipFree(e->d_offs);
 	fit_free(e);
+	fit_sse_free(e);
 	for (int i = 0; i < 7; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
 	if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
 	for (int i = 0; i < 4; i++) if (e->part_stream[i]) (void)hipStreamDestroy(e->part_stream[i]);
@@ -636,15 +651,15 @@ static int fit_buffers(nhw_enc *e)
 	return NHW_OK;
 }
 
-/* everything a fit call can refuse without touching the device; fills the ladder (NULL = 23 .. 1) */
-static int fit_args(nhw_enc *e, int n, const int *ladder, int ladder_len, int q[23], int *len)
+/* everything a fit call can refuse without touching the device; fills the ladder (NULL = 23 .. 1, or with `ascending` 1 .. 23) */
+static int fit_args(nhw_enc *e, int n, const int *ladder, int ladder_len, bool ascending, int q[23], int *len)
 {
 	if (n < 1 || n > e->max_batch || ladder_len < 0 || ladder_len > 23 || (ladder_len == 0) != (ladder == nullptr)) { g_err = "bad argument"; return NHW_E_ARG; }
-	if (e->stop_after) { g_err = "nhw_enc_fit_batch: not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
+	if (e->stop_after) { g_err = "fit call: not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
 	*len = ladder ? ladder_len : 23;
 	bool seen[24] = {};
 	for (int r = 0; r < *len; r++) {
-		q[r] = ladder ? ladder[r] : 23 - r;
+		q[r] = ladder ? ladder[r] : ascending ? r + 1 : 23 - r;
 		if (!nhw_quality_supported(q[r]) || seen[q[r]]) { g_err = "ladder: qualities must be distinct and in 1..23"; return NHW_E_QUALITY; }
 		seen[q[r]] = true;
 	}
@@ -661,7 +676,7 @@ extern "C" int nhw_enc_fit_batch_device(nhw_enc *e, const void *d_bgr, int n, co
 	if (!e || !d_bgr || !d_max_bytes || !d_out || !d_sizes || !d_status || !d_quality) { g_err = "bad argument"; return NHW_E_ARG; }
 	if ((uintptr_t)d_bgr & 15) { g_err = "nhw_enc_fit_batch_device: d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
 	int q[23], len = 0;
-	{ const int rc = fit_args(e, n, ladder, ladder_len, q, &len); if (rc) return rc; }
+	{ const int rc = fit_args(e, n, ladder, ladder_len, false, q, &len); if (rc) return rc; }
 	HIPCHK(hipSetDevice(e->device));
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
 	{ hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -710,7 +725,7 @@ extern "C" int nhw_enc_fit_batch(nhw_enc *e, const uint8_t *bgr, int n, const ui
 {
 	if (!e || !bgr || !max_bytes || !out_arena || !out_off || !status || !quality) { g_err = "bad argument"; return NHW_E_ARG; }
 	int q[23], len = 0;
-	{ const int rc = fit_args(e, n, ladder, ladder_len, q, &len); if (rc) return rc; }
+	{ const int rc = fit_args(e, n, ladder, ladder_len, false, q, &len); if (rc) return rc; }
 	HIPCHK(hipSetDevice(e->device));
 	{ const int rc = host_buffers(e, n); if (rc) return rc; }
 	{ const int rc = fit_buffers(e); if (rc) return rc; }
@@ -730,6 +745,165 @@ extern "C" int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s)
 	HIPCHK(hipEventSynchronize(e->fit_ev[1]));
 	*s = e->fit_stats;
 	HIPCHK(hipEventElapsedTime(&s->total_ms, e->fit_ev[0], e->fit_ev[1]));
+	return NHW_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ distortion */
+extern "C" int nhw_sse_batch_device(const void *d_a, const void *d_b, int n, uint64_t *d_sse, void *stream)
+{
+	if (!d_a || !d_b || !d_sse || n < 1 || n > 65535) { g_err = "bad argument"; return NHW_E_ARG; }
+	if (((uintptr_t)d_a | (uintptr_t)d_b) & 15) { g_err = "nhw_sse_batch_device: the pictures must be 16-byte aligned"; return NHW_E_ARG; }
+	if ((uintptr_t)d_sse & 7) { g_err = "nhw_sse_batch_device: d_sse must be 8-byte aligned"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_sse((const uint8_t *)d_a, (const uint8_t *)d_b, n, d_sse, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ encode to a distortion budget */
+/* device bytes per image of the distortion search's own buffers: a decoded picture, offset, SSE, target, achieved SSE, decoder status */
+#define FIT_SSE_BYTES ((size_t)NHW_IMG_BYTES + 8 * 4 + 4)
+
+static void fit_sse_free(nhw_enc *e)
+{
+	void *dev[] = { e->d_fit_px, e->d_fit_doff, e->d_fit_sse, e->d_fit_maxsse, e->d_fit_sse_out, e->d_fit_dstatus };
+	for (void *p : dev) if (p) (void)hipFree(p);
+	e->d_fit_px = nullptr; e->d_fit_doff = e->d_fit_sse = e->d_fit_maxsse = e->d_fit_sse_out = nullptr; e->d_fit_dstatus = nullptr;
+	e->fit_sse_ready = false;
+}
+
+/* i * NHW_OUT_STRIDE for i < n */
+__global__ void k_fit_doff(uint64_t *off, int n)
+{
+	const int i = blockIdx.x * 256 + threadIdx.x;
+	if (i < n) off[i] = (uint64_t)i * NHW_OUT_STRIDE;
+}
+
+/* the distortion search's buffers for max_batch images, on the first SSE-fit call (byte-budget callers never pay for them) */
+static int fit_sse_buffers(nhw_enc *e)
+{
+	if (e->fit_sse_ready) return NHW_OK;
+	const size_t mb = (size_t)e->max_batch;
+	size_t free_b = 0, total_b = 0;
+	HIPCHK(hipMemGetInfo(&free_b, &total_b));
+	const size_t need = FIT_SSE_BYTES * mb;
+	if (need > free_b) {
+		char b[200];
+		snprintf(b, sizeof b, "distortion search buffers for max_batch %d need %zu MiB (%.1f MiB per image), %zu MiB of HBM are free", e->max_batch, need >> 20, (double)need / mb / 1048576.0, free_b >> 20);
+		g_err = b;
+		return NHW_E_ARG;
+	}
+	const int rc = [&]() -> int {
+		HIPCHK(hipMalloc((void **)&e->d_fit_px, mb * NHW_IMG_BYTES));
+		HIPCHK(hipMalloc((void **)&e->d_fit_doff, mb * sizeof(uint64_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_sse, mb * sizeof(uint64_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_maxsse, mb * sizeof(uint64_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_sse_out, mb * sizeof(uint64_t)));
+		HIPCHK(hipMalloc((void **)&e->d_fit_dstatus, mb * sizeof(int32_t)));
+		k_fit_doff<<<(e->max_batch + 255) / 256, 256, 0, e->own_stream>>>(e->d_fit_doff, e->max_batch);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(e->own_stream));
+		return NHW_OK;
+	}();
+	if (rc != NHW_OK) { fit_sse_free(e); return rc; }
+	e->fit_sse_ready = true;
+	return NHW_OK;
+}
+
+/* everything nhw_enc_fit_sse_batch* can refuse about the decoder handle */
+static int fit_dec_args(nhw_enc *e, nhw_dec *d, int n)
+{
+	if (!d) { g_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
+	int device = 0, max_batch = 0, stop_after = 0;
+	nhw_dec_props(d, &device, &max_batch, &stop_after);
+	if (max_batch < n) { g_err = "nhw_enc_fit_sse_batch: the decoder's max_batch is below n"; return NHW_E_ARG; }
+	if (device != e->device) { g_err = "nhw_enc_fit_sse_batch: the decoder is on another device than the encoder"; return NHW_E_ARG; }
+	if (stop_after) { g_err = "nhw_enc_fit_sse_batch: not with a decoder debug stop set (every rung must be a whole decode)"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+/* The byte search's walk (nhw_enc_fit_batch_device) with a different verdict: after a rung's encode its files are decoded as one batch
+ * on `stream` (rung 1 from the caller's arena, later rungs from the staging one; both hold file j at j * NHW_OUT_STRIDE) and the decoded
+ * pictures are compared with the rung's input pictures (rung 1: d_bgr; later rungs: the gathered staging slab), so list entry j's SSE
+ * lines up with its status.  An image whose encode failed decodes an empty file (NHW_E_FORMAT) and is not counted as fitting. */
+extern "C" int nhw_enc_fit_sse_batch_device(nhw_enc *e, nhw_dec *d, const void *d_bgr, int n, const uint64_t *d_max_sse, const int *ladder, int ladder_len,
+                                            void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, uint64_t *d_sse, void *stream)
+{
+	if (!e || !d_bgr || !d_max_sse || !d_out || !d_sizes || !d_status || !d_quality || !d_sse) { g_err = "bad argument"; return NHW_E_ARG; }
+	if ((uintptr_t)d_bgr & 15) { g_err = "nhw_enc_fit_sse_batch_device: d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
+	int q[23], len = 0;
+	{ const int rc = fit_args(e, n, ladder, ladder_len, true, q, &len); if (rc) return rc; }
+	{ const int rc = fit_dec_args(e, d, n); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	{ hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	  HIPCHK(hipStreamIsCapturing(s, &cs));
+	  if (cs != hipStreamCaptureStatusNone) { g_err = "nhw_enc_fit_sse_batch_device waits on the host between rungs and cannot be captured"; return NHW_E_ARG; } }
+	{ const int rc = fit_buffers(e); if (rc) return rc; }
+	{ const int rc = fit_sse_buffers(e); if (rc) return rc; }
+	e->fit_done = false;
+	nhw_fit_stats st;
+	memset(&st, 0, sizeof st);
+	uint8_t *out = (uint8_t *)d_out;
+	int m = n, cur = 0;
+	HIPCHK(hipEventRecord(e->fit_ev[0], s));
+	for (int r = 0; r < len; r++) {
+		const bool first = r == 0, last = r == len - 1;
+		const int *idx = first ? nullptr : e->d_fit_idx[cur];
+		st.quality[r] = q[r]; st.images[r] = m; st.rungs = r + 1;
+		const uint8_t *pics = first ? (const uint8_t *)d_bgr : e->d_fit_in;
+		const uint8_t *files = first ? out : e->d_fit_out;
+		const uint32_t *lens = first ? d_sizes : e->d_fit_sizes;
+		if (first) {
+			const int rc = nhw_enc_batch_device(e, d_bgr, m, q[r], d_out, d_sizes, d_status, s);
+			if (rc) return rc;
+		} else {
+			nhw_launch_fit_gather((const uint8_t *)d_bgr, idx, m, e->d_fit_in, s);
+			HIPCHK(hipGetLastError());
+			const int rc = nhw_enc_batch_device(e, e->d_fit_in, m, q[r], e->d_fit_out, e->d_fit_sizes, e->d_fit_status, s);
+			if (rc) return rc;
+		}
+		{
+			const int rc = nhw_dec_batch_device(d, files, e->d_fit_doff, lens, m, e->d_fit_px, e->d_fit_dstatus, nullptr, s);
+			if (rc) { g_err = std::string("decode of a rung: ") + nhw_dec_last_error(); return rc; }
+		}
+		HIPCHK(nhw_launch_sse(pics, e->d_fit_px, m, e->d_fit_sse, s));
+		nhw_launch_fit_select_sse(idx, m, e->d_fit_out, e->d_fit_sizes, e->d_fit_status, e->d_fit_dstatus, e->d_fit_sse, d_max_sse, q[r], last, out, d_sizes,
+		                          d_status, d_quality, d_sse, e->d_fit_open, s);
+		HIPCHK(hipGetLastError());
+		if (last) break;
+		nhw_launch_fit_compact(e->d_fit_open, idx, m, e->d_fit_idx[cur ^ 1], e->d_fit_count, s);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(e->h_fit_count, e->d_fit_count, sizeof(int), hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+		m = *e->h_fit_count;
+		cur ^= 1;
+		if (m == 0) break;
+	}
+	HIPCHK(hipEventRecord(e->fit_ev[1], s));
+	e->fit_stats = st;
+	e->fit_done = true;
+	return NHW_OK;
+}
+
+extern "C" int nhw_enc_fit_sse_batch(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
+                                     uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	if (!e || !bgr || !max_sse || !out_arena || !out_off || !status || !quality || !sse) { g_err = "bad argument"; return NHW_E_ARG; }
+	int q[23], len = 0;
+	{ const int rc = fit_args(e, n, ladder, ladder_len, true, q, &len); if (rc) return rc; }
+	{ const int rc = fit_dec_args(e, d, n); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, n); if (rc) return rc; }
+	{ const int rc = fit_buffers(e); if (rc) return rc; }
+	{ const int rc = fit_sse_buffers(e); if (rc) return rc; }
+	hipStream_t s = e->own_stream;
+	HIPCHK(hipMemcpyAsync(e->d_in, bgr, (size_t)n * NHW_IMG_BYTES, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(e->d_fit_maxsse, max_sse, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
+	{ const int rc = nhw_enc_fit_sse_batch_device(e, d, e->d_in, n, e->d_fit_maxsse, ladder, ladder_len, e->d_out, e->d_sizes, e->d_status, e->d_fit_quality,
+	                                              e->d_fit_sse_out, s);
+	  if (rc) return rc; }
+	{ const int rc = host_download(e, n, out_arena, arena_cap, out_off, status); if (rc) return rc; }
+	HIPCHK(hipMemcpy(quality, e->d_fit_quality, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(sse, e->d_fit_sse_out, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
 	return NHW_OK;
 }
 

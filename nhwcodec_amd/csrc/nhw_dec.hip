@@ -2459,6 +2459,12 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 
 extern "C" void nhw_dec_debug_stop_after(nhw_dec *d, int stage) { if (d) d->stop_after = stage; }
 
+/* internal (nhw_api.hip's distortion search; not in the public header): what a caller needs to know about a handle before it hands it work */
+void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after)
+{
+	*device = d->device; *max_batch = d->max_batch; *stop_after = d->stop_after;
+}
+
 /* debug: copy a workspace buffer of one image to the host (what = D_* index) */
 extern "C" int nhw_dec_debug_colour(int quality, const void *d_yuv, void *d_rgb, int n)
 {

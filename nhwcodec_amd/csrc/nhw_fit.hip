@@ -1,5 +1,6 @@
 /*
- * nhw_fit.hip -- the device side of the byte-budget search (nhw_enc_fit_batch_device, include/nhw_hip.h): gfx950 only.
+ * nhw_fit.hip -- the device side of the byte-budget search (nhw_enc_fit_batch_device, include/nhw_hip.h) and of the distortion search
+ * (nhw_enc_fit_sse_batch_device, the same walk with a decode and an error pass per rung): gfx950 only.
  *
  * The search walks a ladder of qualities from the top.  At every rung the images that are still open are encoded at that rung's quality
  * as an ordinary batch (nhw_api.hip); the three kernels here move the images and files between the caller's per-image slots and the
@@ -7,7 +8,8 @@
  *
  *   k_fit_gather   staging[j] = d_bgr[idx[j]]: the open images, 786 432 bytes each, in list order (rungs 2 and later)
  *   k_fit_select   one workgroup per open image: does the rung's file fit the image's budget?  A closed image (or any image on the last
- *                  rung) gets its file, size, status and quality in the caller's slot i = idx[j]; an open one a flag
+ *                  rung) gets its file, size, status and quality in the caller's slot i = idx[j]; an open one a flag.  The budget is a
+ *                  template criterion: FitBytes (the file's size) or FitSse (the decoded picture's SSE, also written to the caller's slot)
  *   k_fit_compact  one workgroup: the flags -> the next open list, in ascending original order, and its length (a scan, not an atomic
  *                  append, so a rung's membership does not depend on the order the workgroups ran in)
  */
@@ -36,11 +38,30 @@ __global__ __launch_bounds__(FIT_GATHER_T) void k_fit_gather(const uint4 *__rest
 	for (int k = 0; k < FIT_GATHER_U; k++) d[k * FIT_GATHER_T] = v[k];
 }
 
+/* The criteria of k_fit_select.  verdict(): NHW_OK if the rung's file of list entry j (image i) fits, else the status the image gets if
+ * this is the last rung.  record(): anything else the criterion writes to the caller's slot of an image that closes. */
+struct FitBytes {                /* a file within the image's byte budget */
+	const uint32_t *budget;
+	__device__ int32_t verdict(int, int i, uint32_t size, int32_t rc) const { return rc != NHW_OK ? rc : size <= budget[i] ? NHW_OK : NHW_E_BUDGET; }
+	__device__ void record(int, int, int32_t) const {}
+};
+struct FitSse {                  /* a decoded picture within the image's SSE budget (rung entry j: its decode status and SSE) */
+	const uint64_t *max_sse, *sse;
+	const int32_t *dec_status;
+	uint64_t *sse_out;
+	__device__ int32_t verdict(int j, int i, uint32_t, int32_t rc) const
+	{
+		return rc != NHW_OK ? rc : dec_status[j] != NHW_OK ? NHW_E_FORMAT : sse[j] <= max_sse[i] ? NHW_OK : NHW_E_BUDGET;
+	}
+	__device__ void record(int j, int i, int32_t rc) const { sse_out[i] = rc == NHW_OK && dec_status[j] == NHW_OK ? sse[j] : UINT64_MAX; }
+};
+
 /* grid m, 256 threads.  idx == nullptr: the first rung, whose sub-batch is the whole batch in order and whose encode wrote the caller's
  * slots itself (nothing to copy: only the quality, and on the last rung the budget status).  Otherwise the rung's files are in staging
  * slot j (st_out / st_sizes / st_status) and a closed image's file is copied to slot idx[j] of the caller's arena.  open[j] = still open. */
-__global__ __launch_bounds__(256) void k_fit_select(const int *__restrict__ idx, const uint8_t *__restrict__ st_out, const uint32_t *__restrict__ st_sizes,
-                                                    const int32_t *__restrict__ st_status, const uint32_t *__restrict__ budget, int quality, int last,
+template <class Crit>
+__global__ __launch_bounds__(256) void k_fit_select(Crit crit, const int *__restrict__ idx, const uint8_t *__restrict__ st_out, const uint32_t *__restrict__ st_sizes,
+                                                    const int32_t *__restrict__ st_status, int quality, int last,
                                                     uint8_t *__restrict__ out, uint32_t *__restrict__ sizes, int32_t *__restrict__ status,
                                                     int32_t *__restrict__ qual, uint8_t *__restrict__ open, int out_aligned)
 {
@@ -48,7 +69,8 @@ __global__ __launch_bounds__(256) void k_fit_select(const int *__restrict__ idx,
 	const int i = idx ? idx[j] : j;
 	const uint32_t size = idx ? st_sizes[j] : sizes[i];
 	const int32_t rc = idx ? st_status[j] : status[i];
-	const bool fits = rc == NHW_OK && size <= budget[i];
+	const int32_t verdict = crit.verdict(j, i, size, rc);
+	const bool fits = verdict == NHW_OK;
 	if (!fits && !last) {
 		if (threadIdx.x == 0) open[j] = 1;
 		return;
@@ -56,8 +78,9 @@ __global__ __launch_bounds__(256) void k_fit_select(const int *__restrict__ idx,
 	if (threadIdx.x == 0) {
 		open[j] = 0;
 		sizes[i] = size;
-		status[i] = fits ? NHW_OK : rc == NHW_OK ? NHW_E_BUDGET : rc;
+		status[i] = verdict;
 		qual[i] = quality;
+		crit.record(j, i, rc);
 	}
 	if (!idx || rc != NHW_OK) return;
 	const uint8_t *s = st_out + (size_t)j * NHW_OUT_STRIDE;
@@ -106,7 +129,16 @@ void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const u
                            int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status, int32_t *qual, uint8_t *open, hipStream_t s)
 {
 	const int aligned = ((uintptr_t)out & 15) == 0;     /* the staging arena is hipMalloc'd; the caller's may sit anywhere */
-	k_fit_select<<<m, 256, 0, s>>>(idx, st_out, st_sizes, st_status, budget, quality, last, out, sizes, status, qual, open, aligned);
+	k_fit_select<<<m, 256, 0, s>>>(FitBytes{ budget }, idx, st_out, st_sizes, st_status, quality, last, out, sizes, status, qual, open, aligned);
+}
+
+void nhw_launch_fit_select_sse(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const int32_t *dec_status,
+                               const uint64_t *sse, const uint64_t *max_sse, int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status,
+                               int32_t *qual, uint64_t *sse_out, uint8_t *open, hipStream_t s)
+{
+	const int aligned = ((uintptr_t)out & 15) == 0;
+	k_fit_select<<<m, 256, 0, s>>>(FitSse{ max_sse, sse, dec_status, sse_out }, idx, st_out, st_sizes, st_status, quality, last, out, sizes, status, qual,
+	                               open, aligned);
 }
 
 void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *next, int *count, hipStream_t s)

@@ -14,12 +14,16 @@
  *   --stock-compat   reproduce the stock one-image-per-process binary instead of the canonical output (include/nhw_hip.h)
  *   --max-bytes N [--min-quality M]   (single file, --batch, --tiles) every image at the highest quality from -q down to M (default 1)
  *                    whose file has at most N bytes (nhw_enc_fit_batch); an image that no quality fits is reported and not written
+ *   --min-psnr DB [--min-quality M]   (single file, --batch, --tiles) every image at the lowest quality from M (default 1) up to -q whose
+ *                    decoded picture reaches DB dB of PSNR (nhw_enc_fit_sse_batch); an image that reaches it at no quality is reported
+ *                    and not written
  * --gpus G: images are independent (encoder/nhw_encoder_cli.c:175-183 is a per-image sequence), so the job is a queue of chunks of up
  * to 1024 images; one host thread per GPU, each with its own encoder handle, takes the next chunk until the queue is empty.  The work
  * descriptor {first image, count, quality, seed} lives in this process; between processes (one per GPU under torchrun) it travels by
  * RCCL broadcast: nhwcodec_amd/dist.py, bench.py.
  */
 #include <dirent.h>
+#include <math.h>
 #include <pthread.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -51,8 +55,9 @@ static void usage(void)
 	        "Batch (MI355X build): %s [-q#] [--gpus g | --devices a,b,..] --batch <dir> | --synthetic <n> [--seed s] --outdir <dir>\n"
 	        "Tiles (MI355X build): %s [-q#] --tiles <big.bmp> <stem>   (width, height multiples of 512: one <stem>_y<r>_x<c>.nhw per 512x512 tile)\n"
 	        "Tar   (MI355X build): %s [-q#] --tar <in.tar> <out.tar>    (every x.bmp member of a ustar archive -> member x.nhw, in order)\n"
-	        "Budget (MI355X build): %s [-q#] --max-bytes <n> [--min-quality <m>] ...   (single file, --batch, --tiles: the highest quality from -q# down to m whose file fits n bytes)\n",
-	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
+	        "Budget (MI355X build): %s [-q#] --max-bytes <n> [--min-quality <m>] ...   (single file, --batch, --tiles: the highest quality from -q# down to m whose file fits n bytes)\n"
+	        "PSNR (MI355X build): %s [-q#] --min-psnr <dB> [--min-quality <m>] ...   (single file, --batch, --tiles: the lowest quality from m up to -q# whose decoded picture reaches dB)\n",
+	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
 }
 
 static void version(void)
@@ -160,26 +165,56 @@ static uint8_t *load_bmp_tiles(const char *path, int *ny, int *nx)
 	return tiles;
 }
 
-/* --max-bytes: the byte budget of every image (0: off) and the ladder, -q down to --min-quality */
+/* --max-bytes: the byte budget of every image (0: off) and the ladder, -q down to --min-quality;
+ * --min-psnr: the PSNR target in dB (0: off), its SSE bound and the ladder, --min-quality up to -q */
 static uint32_t g_max_bytes;
+static double g_min_psnr;
+static uint64_t g_max_sse;
 static int g_ladder[23], g_ladder_len;
 
-/* encode n images: at one quality, or with --max-bytes at the first quality of the ladder that fits (qual[i], may be NULL without it) */
-static int encode_images(nhw_enc *enc, const uint8_t *imgs, int n, int quality, uint8_t *arena, size_t cap, uint64_t *off, int32_t *st, int32_t *qual)
+/* encode n images: at one quality, with --max-bytes at the first quality of the ladder that fits, with --min-psnr at the first whose decode
+ * by `dec` reaches the target (qual[i], sse[i] may be NULL without them) */
+static int encode_images(nhw_enc *enc, nhw_dec *dec, const uint8_t *imgs, int n, int quality, uint8_t *arena, size_t cap, uint64_t *off, int32_t *st,
+                         int32_t *qual, uint64_t *sse)
 {
-	uint32_t *budget;
 	int i, rc;
-	if (!g_max_bytes) return nhw_enc_batch(enc, imgs, n, quality, arena, cap, off, st);
-	budget = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n);
-	for (i = 0; i < n; i++) budget[i] = g_max_bytes;
-	rc = nhw_enc_fit_batch(enc, imgs, n, budget, g_ladder, g_ladder_len, arena, cap, off, st, qual);
-	free(budget);
-	return rc;
+	if (g_min_psnr > 0) {
+		uint64_t *target = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n);
+		for (i = 0; i < n; i++) target[i] = g_max_sse;
+		rc = nhw_enc_fit_sse_batch(enc, dec, imgs, n, target, g_ladder, g_ladder_len, arena, cap, off, st, qual, sse);
+		free(target);
+		return rc;
+	}
+	if (g_max_bytes) {
+		uint32_t *budget = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n);
+		for (i = 0; i < n; i++) budget[i] = g_max_bytes;
+		rc = nhw_enc_fit_batch(enc, imgs, n, budget, g_ladder, g_ladder_len, arena, cap, off, st, qual);
+		free(budget);
+		return rc;
+	}
+	return nhw_enc_batch(enc, imgs, n, quality, arena, cap, off, st);
 }
 
-/* write one image's file, or say why there is none; returns the number of failures (0 or 1) */
-static int emit(const char *path, int32_t st, int32_t qual, const uint8_t *p, size_t n)
+/* a decoder handle next to the encoder when --min-psnr needs one, else NULL */
+static nhw_dec *psnr_decoder(int device, int max_batch)
 {
+	nhw_dec *dec = NULL;
+	int rc;
+	if (g_min_psnr <= 0) return NULL;
+	if ((rc = nhw_dec_create(device, max_batch, &dec))) { fprintf(stderr, "%s: nhw_dec_create failed (%d): %s\n", PROGRAM, rc, nhw_dec_last_error()); exit(2); }
+	return dec;
+}
+
+static double psnr_of(uint64_t sse) { return sse ? 10.0 * log10(65025.0 * (double)NHW_IMG_BYTES / (double)sse) : INFINITY; }
+
+/* write one image's file, or say why there is none; returns the number of failures (0 or 1) */
+static int emit(const char *path, int32_t st, int32_t qual, uint64_t sse, const uint8_t *p, size_t n)
+{
+	if (st == NHW_E_BUDGET && g_min_psnr > 0) {
+		fprintf(stderr, "%s: %s: no quality in q%d..q%d reaches %.2f dB (best, q%d: %.2f dB)\n", PROGRAM, path, g_ladder[0], g_ladder[g_ladder_len - 1], g_min_psnr,
+		        (int)qual, psnr_of(sse));
+		return 1;
+	}
 	if (st == NHW_E_BUDGET) {
 		fprintf(stderr, "%s: %s: no quality in q%d..q%d fits %u bytes (q%d: %zu bytes)\n", PROGRAM, path, g_ladder[0], g_ladder[g_ladder_len - 1], (unsigned)g_max_bytes, (int)qual, n);
 		return 1;
@@ -188,17 +223,18 @@ static int emit(const char *path, int32_t st, int32_t qual, const uint8_t *p, si
 	return write_file(path, p, n) ? 1 : 0;
 }
 
-static int encode_host_batch(nhw_enc *enc, const uint8_t *imgs, int n, int quality, char **out_names)
+static int encode_host_batch(nhw_enc *enc, nhw_dec *dec, const uint8_t *imgs, int n, int quality, char **out_names)
 {
 	uint8_t *arena = (uint8_t *)malloc((size_t)n * NHW_OUT_STRIDE);
 	uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)(n + 1));
 	int32_t *st = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
 	int32_t *qual = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
+	uint64_t *sse = (uint64_t *)calloc((size_t)n, sizeof(uint64_t));
 	int i, rc, bad = 0;
-	rc = encode_images(enc, imgs, n, quality, arena, (size_t)n * NHW_OUT_STRIDE, off, st, qual);
-	if (rc) die_lib(g_max_bytes ? "nhw_enc_fit_batch" : "nhw_enc_batch", rc);
-	for (i = 0; i < n; i++) bad += emit(out_names[i], st[i], qual[i], arena + off[i], (size_t)(off[i + 1] - off[i]));
-	free(qual); free(st); free(off); free(arena);
+	rc = encode_images(enc, dec, imgs, n, quality, arena, (size_t)n * NHW_OUT_STRIDE, off, st, qual, sse);
+	if (rc) die_lib(g_min_psnr > 0 ? "nhw_enc_fit_sse_batch" : g_max_bytes ? "nhw_enc_fit_batch" : "nhw_enc_batch", rc);
+	for (i = 0; i < n; i++) bad += emit(out_names[i], st[i], qual[i], sse[i], arena + off[i], (size_t)(off[i + 1] - off[i]));
+	free(sse); free(qual); free(st); free(off); free(arena);
 	return bad;
 }
 
@@ -231,10 +267,13 @@ static void *worker_main(void *arg)
 	uint64_t *off = (uint64_t *)malloc(sizeof(uint64_t) * (CHUNK + 1));
 	int32_t *st = (int32_t *)malloc(sizeof(int32_t) * CHUNK);
 	int32_t *qual = (int32_t *)malloc(sizeof(int32_t) * CHUNK);
+	uint64_t *sse = (uint64_t *)calloc(CHUNK, sizeof(uint64_t));
 	const int cap = jb->n < g_chunk ? jb->n : g_chunk;
+	nhw_dec *dec = NULL;
 	int rc, i;
 	if ((rc = nhw_enc_create(w->device, cap, &enc))) die_lib("nhw_enc_create", rc);
 	if (jb->stock_compat) nhw_enc_set_compat(enc, NHW_COMPAT_GLIBC_ONESHOT);
+	dec = psnr_decoder(w->device, cap);
 	arena = (uint8_t *)malloc((size_t)cap * NHW_OUT_STRIDE);
 	if (!jb->outdir) {                                 /* page-locked input buffer: the upload runs at PCIe speed next to the encode */
 		imgs = (uint8_t *)nhw_host_alloc((size_t)cap * NHW_IMG_BYTES);
@@ -251,7 +290,7 @@ static void *worker_main(void *arg)
 		if (jb->outdir) rc = nhw_enc_synth_batch(enc, m, jb->seed + (uint32_t)base, jb->quality, arena, (size_t)cap * NHW_OUT_STRIDE, off, st);
 		else {
 			for (i = 0; i < m; i++) load_bmp(jb->in[base + i], imgs + (size_t)i * NHW_IMG_BYTES);
-			rc = encode_images(enc, imgs, m, jb->quality, arena, (size_t)cap * NHW_OUT_STRIDE, off, st, qual);
+			rc = encode_images(enc, dec, imgs, m, jb->quality, arena, (size_t)cap * NHW_OUT_STRIDE, off, st, qual, sse);
 		}
 		if (rc) die_lib("encode", rc);
 		for (i = 0; i < m; i++) {
@@ -259,12 +298,13 @@ static void *worker_main(void *arg)
 			const char *path = name;
 			if (jb->outdir) snprintf(name, sizeof name, "%s/synth_%u.nhw", jb->outdir, (unsigned)(jb->seed + (uint32_t)(base + i)));
 			else path = jb->out[base + i];
-			w->bad += emit(path, st[i], qual[i], arena + off[i], (size_t)(off[i + 1] - off[i]));
+			w->bad += emit(path, st[i], qual[i], sse[i], arena + off[i], (size_t)(off[i + 1] - off[i]));
 		}
 	}
 	if (imgs_pinned) nhw_host_free(imgs); else free(imgs);        /* before the handle goes: page-locked memory belongs to its device context */
 	nhw_enc_destroy(enc);
-	free(qual); free(st); free(off); free(arena);
+	if (dec) nhw_dec_destroy(dec);
+	free(sse); free(qual); free(st); free(off); free(arena);
 	return NULL;
 }
 
@@ -404,7 +444,9 @@ int main(int argc, char **argv)
 	const char *batch_dir = NULL, *outdir = NULL;
 	int tiles = 0, tar = 0;
 	int stock_compat = 0;   /* --stock-compat: NHW_COMPAT_GLIBC_ONESHOT, the stock binary's out-of-bounds reads (include/nhw_hip.h) */
-	const char *max_bytes_arg = NULL, *min_quality_arg = NULL;   /* --max-bytes, --min-quality: checked once the flags are read */
+	const char *max_bytes_arg = NULL, *min_quality_arg = NULL;   /* --max-bytes, --min-quality, --min-psnr: checked once the flags are read */
+	const char *min_psnr_arg = NULL;
+	nhw_dec *dec = NULL;
 	nhw_enc *enc = NULL;
 	int rc;
 
@@ -435,6 +477,7 @@ int main(int argc, char **argv)
 			argc -= 2; argv += 2; continue;
 		}
 		if (!strcmp(argv[1], "--max-bytes") && argc > 2) { max_bytes_arg = argv[2]; argc -= 2; argv += 2; continue; }
+		if (!strcmp(argv[1], "--min-psnr") && argc > 2) { min_psnr_arg = argv[2]; argc -= 2; argv += 2; continue; }
 		if (!strcmp(argv[1], "--min-quality") && argc > 2) { min_quality_arg = argv[2]; argc -= 2; argv += 2; continue; }
 		if (!strcmp(argv[1], "--stock-compat")) { stock_compat = 1; argc -= 1; argv += 1; continue; }
 		if (!strcmp(argv[1], "--tiles")) { tiles = 1; argc -= 1; argv += 1; continue; }
@@ -462,22 +505,31 @@ int main(int argc, char **argv)
 		fprintf(stderr, "%s: quality %d is not implemented (supported: 1..23; the reference accepts -q0 but has no tables for it)\n", PROGRAM, quality);
 		return 3;
 	}
-	if (max_bytes_arg || min_quality_arg) {                          /* before any GPU work */
+	if (max_bytes_arg || min_quality_arg || min_psnr_arg) {          /* before any GPU work */
 		char *end;
 		long v;
 		int min_q = 1;
-		if (!max_bytes_arg) { fprintf(stderr, "%s: --min-quality needs --max-bytes\n", PROGRAM); return 1; }
-		v = strtol(max_bytes_arg, &end, 10);
-		if (end == max_bytes_arg || *end || v < 1 || v > 0x7FFFFFFFL) { fprintf(stderr, "%s: --max-bytes wants a positive number of bytes, got '%s'\n", PROGRAM, max_bytes_arg); return 1; }
-		g_max_bytes = (uint32_t)v;
+		if (!max_bytes_arg && !min_psnr_arg) { fprintf(stderr, "%s: --min-quality needs --max-bytes or --min-psnr\n", PROGRAM); return 1; }
+		if (max_bytes_arg && min_psnr_arg) { fprintf(stderr, "%s: --max-bytes and --min-psnr are mutually exclusive\n", PROGRAM); return 1; }
+		if (min_psnr_arg) {
+			const double db = strtod(min_psnr_arg, &end);
+			if (end == min_psnr_arg || *end || !isfinite(db) || !(db > 0)) { fprintf(stderr, "%s: --min-psnr wants a positive number of dB, got '%s'\n", PROGRAM, min_psnr_arg); return 1; }
+			g_min_psnr = db;
+			g_max_sse = (uint64_t)floor(65025.0 * (double)NHW_IMG_BYTES * pow(10.0, -db / 10.0));   /* nhwcodec_amd.psnr_to_max_sse */
+		} else {
+			v = strtol(max_bytes_arg, &end, 10);
+			if (end == max_bytes_arg || *end || v < 1 || v > 0x7FFFFFFFL) { fprintf(stderr, "%s: --max-bytes wants a positive number of bytes, got '%s'\n", PROGRAM, max_bytes_arg); return 1; }
+			g_max_bytes = (uint32_t)v;
+		}
 		if (min_quality_arg) {
 			v = strtol(min_quality_arg, &end, 10);
 			if (end == min_quality_arg || *end || !nhw_quality_supported((int)v)) { fprintf(stderr, "%s: --min-quality wants a quality 1..23, got '%s'\n", PROGRAM, min_quality_arg); return 1; }
 			min_q = (int)v;
 		}
 		if (min_q > quality) { fprintf(stderr, "%s: --min-quality %d is above the top quality q%d\n", PROGRAM, min_q, quality); return 1; }
-		if (synthetic > 0 || tar) { fprintf(stderr, "%s: --max-bytes works with a single file, --batch and --tiles, not with --synthetic or --tar\n", PROGRAM); return 1; }
-		for (g_ladder_len = 0; quality - g_ladder_len >= min_q; g_ladder_len++) g_ladder[g_ladder_len] = quality - g_ladder_len;
+		if (synthetic > 0 || tar) { fprintf(stderr, "%s: %s works with a single file, --batch and --tiles, not with --synthetic or --tar\n", PROGRAM, min_psnr_arg ? "--min-psnr" : "--max-bytes"); return 1; }
+		if (min_psnr_arg) for (g_ladder_len = 0; min_q + g_ladder_len <= quality; g_ladder_len++) g_ladder[g_ladder_len] = min_q + g_ladder_len;
+		else for (g_ladder_len = 0; quality - g_ladder_len >= min_q; g_ladder_len++) g_ladder[g_ladder_len] = quality - g_ladder_len;
 	}
 
 	if (synthetic > 0 || batch_dir) {
@@ -537,8 +589,10 @@ int main(int argc, char **argv)
 		}
 		if ((rc = nhw_enc_create(0, n, &enc))) die_lib("nhw_enc_create", rc);
 		if (stock_compat) nhw_enc_set_compat(enc, NHW_COMPAT_GLIBC_ONESHOT);
-		bad = encode_host_batch(enc, imgs, n, quality, names);
+		dec = psnr_decoder(0, n);
+		bad = encode_host_batch(enc, dec, imgs, n, quality, names);
 		nhw_enc_destroy(enc);
+		if (dec) nhw_dec_destroy(dec);
 		printf("%d x %d tiles\n", ny, nx);
 		free(imgs);
 		return bad ? 1 : 0;
@@ -551,9 +605,11 @@ int main(int argc, char **argv)
 		load_bmp(argv[1], img);
 		if ((rc = nhw_enc_create(0, 1, &enc))) die_lib("nhw_enc_create", rc);
 		if (stock_compat) nhw_enc_set_compat(enc, NHW_COMPAT_GLIBC_ONESHOT);
+		dec = psnr_decoder(0, 1);
 		names[0] = argv[2];
-		bad = encode_host_batch(enc, img, 1, quality, names);
+		bad = encode_host_batch(enc, dec, img, 1, quality, names);
 		nhw_enc_destroy(enc);
+		if (dec) nhw_dec_destroy(dec);
 		free(img);
 		return bad ? 1 : 0;
 	}
