@@ -10,12 +10,16 @@ work with no data-path collective; the only collectives are the 32-byte work des
 per-rank {bytes, checksum, images ok}.  Default: weak scaling (`--batch` images per GPU).  `--total-images T` (BASELINE
 configs[3]: 65536 over 8 GPUs) cuts ONE job of T images into contiguous per-rank ranges instead (strong scaling).
 `--dry` runs the multi-process plumbing alone on CPU over gloo (tests).  `--dump-outputs DIR` writes what the last timed encode
-step (and the last timed decode step) returned as DIR/<name>.npy, so that two builds can be compared output for output on the same
+step (and the decode of its files) returned as DIR/<name>.npy, so that two builds can be compared output for output on the same
 seeded inputs.
 
-Rank 0 prints ONE JSON line.  `roofline` is measured with HIP events on the launch stream inside the timed
-region; `cpu_baseline` times the reference encoder (oracle/_ref, kind "reference") or, if that build is
-absent, the plain-C port (oracle/, kind "port") on the host cores over a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the dump if
+`--dump-outputs` is given (its decoded pictures come from one untimed decode of the last step's files) and the line.  `roofline` there is
+what the timed steps' HIP events on the launch stream give, with the committed PMC files.  `--full` adds everything else: the quality
+sweep, config 4's per-GPU shape, the timed decode leg, the PCIe-inclusive host path, the chroma level-1 launches and the device copy
+that the roofline is also read against, and `cpu_baseline`, which times the reference encoder (oracle/_ref, kind "reference") or, if
+that build is absent, the plain-C port (oracle/, kind "port") on the host cores over a bounded sample.  The `--no-*` switches and
+`--sweep` pick among these legs of a `--full` run.
 """
 import argparse
 import math
@@ -415,7 +419,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="images per GPU per step (weak scaling)")
     ap.add_argument("--total-images", type=int, default=0, help="strong scaling: ONE job of this many images per step, cut into contiguous per-rank ranges (BASELINE configs[3]: 65536 over 8 GPUs)")
     ap.add_argument("--quality", type=int, default=20)
-    ap.add_argument("--sweep", type=str, default="1,8,10,17,23", help="BASELINE configs[2]: quality settings timed after the headline measurement (N=1 only; 8 stands for the slowest band of qualities, 6 .. 9: DESIGN 4.7); '' = none")
+    ap.add_argument("--full", action="store_true", help="after the headline measurement, also run every other leg (quality sweep, config 4's per-GPU shape, timed decode, host path, "
+                                                        "chroma level-1 timing, device copy, CPU baselines), each unless its --no-* switch says otherwise; a plain run does none of them")
+    ap.add_argument("--sweep", type=str, default="1,8,10,17,23", help="BASELINE configs[2]: quality settings timed after the headline measurement in a --full run (N=1 only; 8 stands for the slowest band of qualities, 6 .. 9: DESIGN 4.7); '' = none")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive leg (host buffers through nhw_enc_batch) reported next to the metric")
     ap.add_argument("--no-decode", action="store_true", help="skip the decode leg (BASELINE config 5) reported next to the encode metric")
@@ -423,7 +429,7 @@ def main():
     ap.add_argument("--no-config4-shape", action="store_true", help="skip the leg that times BASELINE config 4's PER-GPU shape (8192 images = 65536 / 8) on this one GPU")
     ap.add_argument("--dry", action="store_true", help="CPU only: rendezvous over gloo, descriptor broadcast, sharding, gather -- no encode (tests of the N>1 plumbing)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
-                    help="after the timed steps, write what the last headline encode step (and the last decode step) returned, as DIR/<name>.npy "
+                    help="after the timed steps, write what the last headline encode step and the decode of its files (the last timed decode step of a --full run) returned, as DIR/<name>.npy "
                          "(float32 / float64, under 64 MB; rank 0's images): per-file sizes, status and digests, a seeded sample of the files and pictures")
     args = ap.parse_args()
     if args.steps < 1:
@@ -485,7 +491,7 @@ def main():
     dump = dump_encode(out, batch) if (args.dump_outputs and rank == 0) else None     # before any later leg reuses the arena
 
     # the two chroma level-1 launches, timed on the planes the headline batch just left (the hook refuses anything but the handle's last whole batch)
-    cl1 = chroma_l1_ms(enc, tim.front_images or batch) if (rank == 0 and q >= 17 and not args.no_chroma_l1) else None
+    cl1 = chroma_l1_ms(enc, tim.front_images or batch) if (args.full and rank == 0 and q >= 17 and not args.no_chroma_l1) else None
 
     _, sizes, status = out
     ok = int((status == 0).sum().item())
@@ -499,7 +505,7 @@ def main():
     # BASELINE config 2/3: the other quality settings, each under the same timed contract (barrier + synchronize on both sides), on the
     # same resident batch.  The rationed settings (q <= 16) take much longer per step, so they get fewer steps; the count is reported.
     sweep = []
-    if world == 1 and args.sweep:
+    if args.full and world == 1 and args.sweep:
         for sq in [int(v) for v in args.sweep.split(",") if v.strip()]:
             if sq == q:
                 continue
@@ -525,7 +531,7 @@ def main():
     # BASELINE config 4 is 65536 images over 8 GPUs = 8192 per GPU: what ONE rank of that job costs, on record from a one-GPU box (the 8-GPU run is
     # the driver's).  Twice the headline batch is not twice the time for the kernels that hold a wavefront per image, so it is measured.
     c4_line = None
-    if world == 1 and not strong and not args.no_config4_shape:
+    if args.full and world == 1 and not strong and not args.no_config4_shape:
         n8 = 8192
         enc8 = nhwcodec_amd.Encoder(local_rank, max_batch=n8)
         bgr8 = enc8.synth_device(n8, seed_base=first_seed)
@@ -544,7 +550,16 @@ def main():
     # BASELINE config 5 beside the headline metric: the batch just encoded goes back through the decoder, HBM to HBM
     # (the encoder's output arena is the decoder's input arena).  Timed after, and apart from, the encode region.
     dec_line = None
-    if not args.no_decode:
+    if dump is not None and not args.full and not args.no_decode:
+        # a plain run decodes only for the dump: the files of the last timed encode step, once, untimed
+        dec = nhwcodec_amd.Decoder(local_rank, max_batch=batch)
+        offs = torch.arange(batch, dtype=torch.int64, device=dev) * nhwcodec_amd.OUT_STRIDE
+        pix = torch.empty((batch, 512, 512, 3), dtype=torch.uint8, device=dev)
+        _, dst, dq = dec.decode_device(out[0], offs, sizes, pix)
+        torch.cuda.synchronize()
+        dump.update(dump_decode(pix, dst, dq, batch))
+        dec.close()
+    if args.full and not args.no_decode:
         dec = nhwcodec_amd.Decoder(local_rank, max_batch=batch)
         offs = torch.arange(batch, dtype=torch.int64, device=dev) * nhwcodec_amd.OUT_STRIDE
         pix = torch.empty((batch, 512, 512, 3), dtype=torch.uint8, device=dev)
@@ -591,7 +606,7 @@ def main():
     # the same encoder behind the host-buffer entry point (page-locked BGR in host memory -> chunked H2D on a copy stream next
     # to the encode of the chunk before -> files compacted on the device -> D2H).  PCIe-inclusive, reported apart; never `value`.
     host_line = None
-    if world == 1 and not args.no_host_path:
+    if args.full and world == 1 and not args.no_host_path:
         import numpy as np
         hn = min(batch, 2048)
         pinned = enc.pinned_images(hn)
@@ -618,7 +633,7 @@ def main():
         achieved = front_images * FRONT_BYTES_PER_IMAGE / front_s / 1e9
         achieved_all = front_images * FRONT_BYTES_PER_IMAGE / (front_s + (cl1 or 0.0) / 1e3) / 1e9
         traffic, traffic_note = front_traffic(q, front_images)
-        copy_gbs = hbm_copy_gbs()
+        copy_gbs = hbm_copy_gbs() if args.full else None
         ev = valu_evidence()
         vk = (ev or {}).get("k_front_image" if q < 22 else "k_front_plain")
         line = {
@@ -638,13 +653,14 @@ def main():
                          # what limits the kernel is not the roofline it is priced against: it issues vector instructions most of its cycles (PMC, below)
                          "limiter": "valu_issue", **({"valu_roofline_frac": vk["issue_frac_of_1_per_cu_cycle"], "lane_ops_per_pixel": vk["lane_ops_per_pixel"]} if vk else {}),
                          # the peak confirmed with a device copy on this box (1 GiB, read + written bytes, best of 5) and `frac` against it
-                         "hbm_copy_measured": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved_all / copy_gbs, 4),
+                         **({"hbm_copy_measured": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved_all / copy_gbs, 4)} if copy_gbs else {}),
                          "traffic": traffic, "traffic_unit": "bytes per launch group; " + traffic_note,
                          "algorithmic_bytes_per_launch": front_images * FRONT_BYTES_PER_IMAGE, "images_per_launch": front_images,
                          # SURVEY 8(d) also states its >= 0.50 target on the READ side alone (n x 786 432 B of BGR / t): half of `frac`
                          "frac_on_reads_only": round(front_images * 786432 / front_s / 1e9 / HBM_PEAK_GBS, 4),
-                         "reads_only_target_note": ("north_star's literal target, >= 0.50 of the HBM READ roofline on this kernel, means 4 TB/s of reads next to as many bytes written = 8 TB/s of "
-                                                    f"combined traffic, {8000.0 / copy_gbs:.2f} x what a plain device copy reaches on this box (hbm_copy_measured): out of reach for any kernel; the figure held to is 0.50 of the 6 B/pixel (<= 1.61 ms per 4096 images)"),
+                         **({"reads_only_target_note": ("north_star's literal target, >= 0.50 of the HBM READ roofline on this kernel, means 4 TB/s of reads next to as many bytes written = 8 TB/s of "
+                                                        f"combined traffic, {8000.0 / copy_gbs:.2f} x what a plain device copy reaches on this box (hbm_copy_measured): out of reach for any kernel; the figure held to is 0.50 of the 6 B/pixel (<= 1.61 ms per 4096 images)")}
+                            if copy_gbs else {}),
                          # the same bytes over the front group PLUS the two chroma level-1 launches whose output the 6 B/pixel include (measured apart, see chroma_l1_ms)
                          "chroma_l1_in_frac": bool(cl1),
                          **({"frac_incl_chroma_l1": round(front_images * FRONT_BYTES_PER_IMAGE / ((front_s + cl1 / 1e3)) / 1e9 / HBM_PEAK_GBS, 4), "chroma_l1_ms": round(cl1, 3)} if cl1 else {}), "sub_batches": tim.parts, "algorithmic_bytes_per_image": FRONT_BYTES_PER_IMAGE, "ms_per_launch_group": round(front_s * 1e3, 3)},
@@ -664,7 +680,7 @@ def main():
             line["host_path"] = host_line
         if dec_line:
             line["decode"] = dec_line
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(q)
         if dump is not None:
             write_dump(args.dump_outputs, dump)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Developer tool (GPU box): the decode leg with two builds of the library on the same box, alternating.  usage: bash tools/dev/ab_dec.sh <old.so> [q]
 OLD=$1; Q=${2:-20}
-B="python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-path --no-chroma-l1 --no-config4-shape --sweep= --quality $Q"
+B="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-host-path --no-chroma-l1 --no-config4-shape --sweep= --quality $Q"
 cp nhwcodec_amd/libnhwhip.so /tmp/new.so
 for i in 1 2 3; do
   for v in new old; do
