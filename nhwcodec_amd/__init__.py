@@ -166,19 +166,40 @@ class Encoder:
                 self.torch.empty(n, dtype=self.torch.int32, device=dev),
                 self.torch.empty(n, dtype=self.torch.int32, device=dev))
 
-    def encode_device(self, bgr, quality: int = QUALITY_DEFAULT, out=None):
-        """bgr: uint8 CUDA tensor [n,512,512,3] (BMP file order).  Returns (out[n,OUT_STRIDE], sizes[n], status[n]) on device."""
+    def _device_batch(self, bgr, what):
+        """bgr: a contiguous uint8 CUDA tensor [n,512,512,3] on this encoder's device -> n"""
         if not (bgr.is_cuda and bgr.dtype == self.torch.uint8 and bgr.is_contiguous() and bgr.dim() == 4 and tuple(bgr.shape[1:]) == (512, 512, 3)):
-            raise NhwError("encode_device wants a contiguous uint8 CUDA tensor of shape [n, 512, 512, 3]")
+            raise NhwError(f"{what} wants a contiguous uint8 CUDA tensor of shape [n, 512, 512, 3]")
         if bgr.device.index != self.device:
             raise NhwError(f"the batch is on cuda:{bgr.device.index}, this encoder on cuda:{self.device}")
-        n = bgr.shape[0]
+        return bgr.shape[0]
+
+    def _device_outputs(self, what, n, out, extra=()):
+        """out (None: new tensors), checked: uint8 [n, OUT_STRIDE], int32 sizes [n] and status [n], then an [n] tensor of each dtype in `extra`"""
+        t = self.torch
+        kinds = [(t.uint8, n * OUT_STRIDE), (t.int32, n), (t.int32, n)] + [(dt, n) for dt in extra]
         if out is None:
-            out = self.alloc_out(n)
-        o, sizes, status = out
-        for t_, dt_, cnt_ in ((o, self.torch.uint8, n * OUT_STRIDE), (sizes, self.torch.int32, n), (status, self.torch.int32, n)):
-            if not (t_.is_cuda and t_.device.index == self.device and t_.dtype == dt_ and t_.is_contiguous() and t_.numel() >= cnt_):
-                raise NhwError("encode_device: output tensors must be contiguous, on this encoder's device, uint8 [n, OUT_STRIDE] / int32 [n] / int32 [n]")
+            out = self.alloc_out(n) + tuple(t.empty(n, dtype=dt, device=f"cuda:{self.device}") for dt in extra)
+        if len(out) != len(kinds):
+            raise ValueError(f"{what}: `out` holds {len(out)} tensors, not {len(kinds)}")
+        if not all(x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous() and x.numel() >= cnt for x, (dt, cnt) in zip(out, kinds)):
+            shapes = " / ".join(["uint8 [n, OUT_STRIDE]"] + [f"{str(dt).split('.')[-1]} [n]" for dt, _ in kinds[1:]])
+            raise NhwError(f"{what}: output tensors must be contiguous, on this encoder's device, {shapes}")
+        return out
+
+    @staticmethod
+    def _host_images(images, what):
+        """images as a contiguous numpy uint8 [n,512,512,3]"""
+        import numpy as np
+        images = np.asarray(images)
+        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (512, 512, 3):
+            raise NhwError(f"{what} wants uint8 [n, 512, 512, 3] (BMP file order), got {images.dtype} {images.shape}")
+        return np.ascontiguousarray(images)
+
+    def encode_device(self, bgr, quality: int = QUALITY_DEFAULT, out=None):
+        """bgr: uint8 CUDA tensor [n,512,512,3] (BMP file order).  Returns (out[n,OUT_STRIDE], sizes[n], status[n]) on device."""
+        n = self._device_batch(bgr, "encode_device")
+        o, sizes, status = self._device_outputs("encode_device", n, out)
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_enc_batch_device(self.h, bgr.data_ptr(), n, quality, o.data_ptr(), sizes.data_ptr(), status.data_ptr(), st))
         return o, sizes, status
@@ -186,10 +207,7 @@ class Encoder:
     def encode(self, images, quality: int = QUALITY_DEFAULT):
         """images: numpy uint8 [n,512,512,3] on the host -> list of .nhw byte strings (raises on a per-image failure)."""
         import numpy as np
-        images = np.asarray(images)
-        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (512, 512, 3):
-            raise NhwError(f"encode wants uint8 [n, 512, 512, 3] (BMP file order), got {images.dtype} {images.shape}")
-        images = np.ascontiguousarray(images)
+        images = self._host_images(images, "encode")
         n = images.shape[0]
         arena = np.empty(n * OUT_STRIDE, np.uint8)
         offs = np.empty(n + 1, np.uint64)
@@ -197,7 +215,7 @@ class Encoder:
         self._chk(self.lib.nhw_enc_batch(self.h, images.ctypes.data, n, quality, arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
         if (status != 0).any():
             raise NhwError(f"per-image status {status.tolist()}")
-        return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+        return _split(arena, offs)
 
     @staticmethod
     def _ladder(ladder):
@@ -214,27 +232,17 @@ class Encoder:
         Returns (out[n,OUT_STRIDE], sizes[n], status[n], quality[n]) on the device; status NHW_E_BUDGET where no rung fits (the slot
         then holds the last rung's file).  Waits on the host between rungs: not for graph capture."""
         t = self.torch
-        if not (bgr.is_cuda and bgr.dtype == t.uint8 and bgr.is_contiguous() and bgr.dim() == 4 and tuple(bgr.shape[1:]) == (512, 512, 3)):
-            raise NhwError("encode_fit_device wants a contiguous uint8 CUDA tensor of shape [n, 512, 512, 3]")
-        if bgr.device.index != self.device:
-            raise NhwError(f"the batch is on cuda:{bgr.device.index}, this encoder on cuda:{self.device}")
-        n = bgr.shape[0]
-        dev = f"cuda:{self.device}"
+        n = self._device_batch(bgr, "encode_fit_device")
         if isinstance(max_bytes, numbers.Integral):
             if max_bytes < 0:
                 raise NhwError(f"max_bytes must not be negative, got {max_bytes}")
-            budget = t.full((n,), min(int(max_bytes), 2**31 - 1), dtype=t.int32, device=dev)   # (a file is at most OUT_STRIDE bytes)
+            budget = t.full((n,), min(int(max_bytes), 2**31 - 1), dtype=t.int32, device=f"cuda:{self.device}")   # (a file is at most OUT_STRIDE bytes)
         else:
             budget = max_bytes
             if not (isinstance(budget, t.Tensor) and budget.dtype in (t.int32, getattr(t, "uint32", t.int32)) and budget.is_cuda
                     and budget.device.index == self.device and budget.is_contiguous() and budget.numel() == n):
                 raise NhwError("encode_fit_device: max_bytes must be an int or a contiguous int32 / uint32 tensor [n] on this encoder's device")
-        if out is None:
-            out = self.alloc_out(n) + (t.empty(n, dtype=t.int32, device=dev),)
-        o, sizes, status, quality = out
-        for t_, dt_, cnt_ in ((o, t.uint8, n * OUT_STRIDE), (sizes, t.int32, n), (status, t.int32, n), (quality, t.int32, n)):
-            if not (t_.is_cuda and t_.device.index == self.device and t_.dtype == dt_ and t_.is_contiguous() and t_.numel() >= cnt_):
-                raise NhwError("encode_fit_device: output tensors must be contiguous, on this encoder's device, uint8 [n, OUT_STRIDE] / int32 [n] x 3")
+        o, sizes, status, quality = self._device_outputs("encode_fit_device", n, out, (t.int32,))
         lad, lad_n = self._ladder(ladder)
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_enc_fit_batch_device(self.h, bgr.data_ptr(), n, budget.data_ptr(), lad, lad_n, o.data_ptr(), sizes.data_ptr(),
@@ -245,10 +253,7 @@ class Encoder:
         """images: numpy uint8 [n,512,512,3] on the host; max_bytes: an int or n ints -> (files, qualities, status), lists of n.
         A per-image NHW_E_BUDGET (files[i] = the last rung's file) or NHW_E_CODEBOOK (files[i] = b"") is reported, not raised."""
         import numpy as np
-        images = np.asarray(images)
-        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (512, 512, 3):
-            raise NhwError(f"encode_fit wants uint8 [n, 512, 512, 3] (BMP file order), got {images.dtype} {images.shape}")
-        images = np.ascontiguousarray(images)
+        images = self._host_images(images, "encode_fit")
         n = images.shape[0]
         mb = np.asarray(max_bytes, dtype=np.int64)
         if mb.ndim == 0:
@@ -263,7 +268,7 @@ class Encoder:
         lad, lad_n = self._ladder(ladder)
         self._chk(self.lib.nhw_enc_fit_batch(self.h, images.ctypes.data, n, budget.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size,
                                              offs.ctypes.data, status.ctypes.data, quality.ctypes.data))
-        return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)], quality.tolist(), status.tolist()
+        return _split(arena, offs), quality.tolist(), status.tolist()
 
     def _max_sse(self, n, min_psnr, max_sse, what):
         """the per-image SSE targets as a contiguous int64 CUDA tensor [n] (read as uint64) from exactly one of min_psnr / max_sse"""
@@ -310,20 +315,10 @@ class Encoder:
         file).  Waits on the host between rungs: not for graph capture."""
         t = self.torch
         what = "encode_fit_psnr_device"
-        if not (bgr.is_cuda and bgr.dtype == t.uint8 and bgr.is_contiguous() and bgr.dim() == 4 and tuple(bgr.shape[1:]) == (512, 512, 3)):
-            raise NhwError(f"{what} wants a contiguous uint8 CUDA tensor of shape [n, 512, 512, 3]")
-        if bgr.device.index != self.device:
-            raise NhwError(f"the batch is on cuda:{bgr.device.index}, this encoder on cuda:{self.device}")
-        n = bgr.shape[0]
+        n = self._device_batch(bgr, what)
         dh = self._decoder(decoder, n, what)
         target = self._max_sse(n, min_psnr, max_sse, what)
-        dev = f"cuda:{self.device}"
-        if out is None:
-            out = self.alloc_out(n) + (t.empty(n, dtype=t.int32, device=dev), t.empty(n, dtype=t.int64, device=dev))
-        o, sizes, status, quality, sse = out
-        for t_, dt_, cnt_ in ((o, t.uint8, n * OUT_STRIDE), (sizes, t.int32, n), (status, t.int32, n), (quality, t.int32, n), (sse, t.int64, n)):
-            if not (t_.is_cuda and t_.device.index == self.device and t_.dtype == dt_ and t_.is_contiguous() and t_.numel() >= cnt_):
-                raise NhwError(f"{what}: output tensors must be contiguous, on this encoder's device, uint8 [n, OUT_STRIDE] / int32 [n] x 3 / int64 [n]")
+        o, sizes, status, quality, sse = self._device_outputs(what, n, out, (t.int32, t.int64))
         lad, lad_n = self._ladder(ladder)
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_enc_fit_sse_batch_device(self.h, dh, bgr.data_ptr(), n, target.data_ptr(), lad, lad_n, o.data_ptr(), sizes.data_ptr(),
@@ -334,10 +329,7 @@ class Encoder:
         """images: numpy uint8 [n,512,512,3] on the host; min_psnr: dB, one number or n of them -> (files, qualities, status, sse), lists of n.
         A per-image NHW_E_BUDGET (files[i] = the last rung's file) or NHW_E_CODEBOOK (files[i] = b"", sse 2**64 - 1) is reported, not raised."""
         import numpy as np
-        images = np.asarray(images)
-        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[1:] != (512, 512, 3):
-            raise NhwError(f"encode_fit_psnr wants uint8 [n, 512, 512, 3] (BMP file order), got {images.dtype} {images.shape}")
-        images = np.ascontiguousarray(images)
+        images = self._host_images(images, "encode_fit_psnr")
         n = images.shape[0]
         dh = self._decoder(decoder, n, "encode_fit_psnr")
         target = psnr_to_max_sse(min_psnr)
@@ -352,7 +344,7 @@ class Encoder:
         lad, lad_n = self._ladder(ladder)
         self._chk(self.lib.nhw_enc_fit_sse_batch(self.h, dh, images.ctypes.data, n, target.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size,
                                                  offs.ctypes.data, status.ctypes.data, quality.ctypes.data, sse.ctypes.data))
-        return ([arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)], quality.tolist(), status.tolist(), [int(x) for x in sse])
+        return _split(arena, offs), quality.tolist(), status.tolist(), [int(x) for x in sse]
 
     def fit_stats(self) -> FitStats:
         s = FitStats()
@@ -378,7 +370,7 @@ class Encoder:
         self._chk(self.lib.nhw_enc_synth_batch(self.h, n, seed_base, quality, arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
         if (status != 0).any():
             raise NhwError(f"per-image status {status.tolist()}")
-        return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(n)]
+        return _split(arena, offs)
 
     def pinned_images(self, n: int):
         """uint8 [n,512,512,3] in page-locked host memory (nhw_host_alloc): encode() uploads such a batch by DMA at PCIe speed while the
@@ -396,6 +388,11 @@ class Encoder:
         for p in getattr(self, "_pinned", []):
             self.lib.nhw_host_free(p)
         self._pinned = []
+
+
+def _split(arena, offs):
+    """the files of a host-path arena: file i is arena[offs[i]:offs[i + 1]] -> a list of bytes"""
+    return [arena[int(offs[i]):int(offs[i + 1])].tobytes() for i in range(len(offs) - 1)]
 
 
 def tile_images(big):

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <vector>
 
 #include "../../include/nhw_hip.h"
 #include "nhw_ws.h"
@@ -40,15 +41,12 @@ void nhw_launch_low_prefilter_chroma(const uint8_t *src, size_t src_stride, int1
 void nhw_launch_low_chroma_thin(int16_t *plane, size_t plane_stride, int n, hipStream_t s);
 void nhw_launch_low_ll2(int16_t *proc, size_t plane_stride, int q, int n, hipStream_t s);
 
-/* the byte-budget search (nhw_fit.hip) */
+/* the quality searches (nhw_fit.hip; the distortion search also nhw_metric.hip, nhw_dec.hip) */
 void nhw_launch_fit_gather(const uint8_t *d_bgr, const int *idx, int m, uint8_t *staging, hipStream_t s);
-void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const uint32_t *budget,
-                           int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status, int32_t *qual, uint8_t *open, hipStream_t s);
+void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const void *limit,
+                           const int32_t *dec_status, const uint64_t *sse, int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status,
+                           int32_t *qual, uint64_t *sse_out, uint8_t *open, hipStream_t s);
 void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *next, int *count, hipStream_t s);
-/* the distortion search (nhw_fit.hip, nhw_metric.hip, nhw_dec.hip) */
-void nhw_launch_fit_select_sse(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const int32_t *dec_status,
-                               const uint64_t *sse, const uint64_t *max_sse, int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status,
-                               int32_t *qual, uint64_t *sse_out, uint8_t *open, hipStream_t s);
 hipError_t nhw_launch_sse(const uint8_t *a, const uint8_t *b, int n, uint64_t *sse, hipStream_t s);
 void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after);
 
@@ -87,24 +85,26 @@ struct nhw_enc {
 	int front_fallback; /* debug: every row / segment of the pre-filter carry takes its exact fallback path (tests) */
 	int stop_after;   /* debug: leave the batch driver after this many stages (0 = run everything) */
 	int last_n, last_q; /* images and quality of the last whole batch (nhw_stage_chroma_l1 works on what it left in the 4:2:0 planes) */
-	/* the byte-budget search (nhw_enc_fit_batch_device): allocated for max_batch images by the first fit call */
-	uint8_t *d_fit_in, *d_fit_out;           /* staging: the gathered open images, the files of their rung */
-	uint32_t *d_fit_sizes, *d_fit_budget;    /* (the budgets: the host path's upload) */
-	int32_t *d_fit_status, *d_fit_quality;   /* (the qualities: the host path's) */
-	int *d_fit_idx[2], *d_fit_count;         /* the open list of this rung and of the next; its length */
-	uint8_t *d_fit_open;                     /* per list entry: still open after this rung */
-	int *h_fit_count;                        /* page-locked */
+	/* the quality searches (fit_walk): two sets of buffers for max_batch images, each allocated all or nothing by the first call that
+	 * needs it (fit_buffers) and present while its first pointer is */
+	struct {                              /* every search */
+		uint8_t *in, *out;                /* staging: the gathered open images, the files of their rung */
+		uint32_t *sizes, *budget;         /* (the budgets: the host path's upload) */
+		int32_t *status, *quality;        /* (the qualities: the host path's) */
+		int *idx[2], *count;              /* the open list of this rung and of the next; its length */
+		uint8_t *open;                    /* per list entry: still open after this rung */
+	} fit;
+	struct {                              /* the distortion search only: byte-budget callers never allocate it */
+		uint8_t *px;                      /* the rung's decoded pictures */
+		uint64_t *doff;                   /* decoder offsets: entry j at j * NHW_OUT_STRIDE (the caller's arena and the staging one alike) */
+		uint64_t *sse, *maxsse;           /* per list entry: the SSE of its picture; (the targets: the host path's upload) */
+		uint64_t *sse_out;                /* (the achieved SSE: the host path's) */
+		int32_t *dstatus;                 /* per list entry: the decoder's status */
+	} fit_sse;
+	int *h_fit_count;                     /* page-locked: the open count the host waits for between rungs */
 	hipEvent_t fit_ev[2];
-	bool fit_ready;
 	nhw_fit_stats fit_stats;
 	bool fit_done;
-	/* the distortion search (nhw_enc_fit_sse_batch_device): allocated for max_batch images by the first SSE-fit call */
-	uint8_t *d_fit_px;                       /* the rung's decoded pictures */
-	uint64_t *d_fit_doff;                    /* decoder offsets: entry j at j * NHW_OUT_STRIDE (the caller's arena and the staging one alike) */
-	uint64_t *d_fit_sse, *d_fit_maxsse;      /* per list entry: the SSE of its picture; (the targets: the host path's upload) */
-	uint64_t *d_fit_sse_out;                 /* (the achieved SSE: the host path's) */
-	int32_t *d_fit_dstatus;                  /* per list entry: the decoder's status */
-	bool fit_sse_ready;
 };
 
 static const size_t k_buf_bytes[B_COUNT] = {
@@ -140,10 +140,57 @@ extern "C" int nhw_enc_set_compat(nhw_enc *e, int mode)
 	return NHW_OK;
 }
 
+/* The handle's lazily allocated sets of device buffers, each a table of (pointer, bytes): the host path's staging and the two sets of the
+ * quality searches.  dev_alloc gets all of a set or none of it; dev_free frees a set and nulls its pointers. */
+struct DevBuf { void **p; size_t bytes; };
+using DevSet = std::vector<DevBuf>;
+template <class T> static DevBuf dev_buf(T *&p, size_t count) { return { (void **)&p, count * sizeof(T) }; }
+
+static void dev_free(const DevSet &set)
+{
+	for (const DevBuf &b : set) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+}
+
+/* what != nullptr: first refuse (NHW_E_ARG) a set larger than the free HBM, with a message that names it, instead of failing inside hipMalloc */
+static int dev_alloc(const DevSet &set, const char *what, int images)
+{
+	if (what) {
+		size_t need = 0, free_b = 0, total_b = 0;
+		for (const DevBuf &b : set) need += b.bytes;
+		HIPCHK(hipMemGetInfo(&free_b, &total_b));
+		if (need > free_b) {
+			char m[200];
+			snprintf(m, sizeof m, "%s for max_batch %d need %zu MiB (%.1f MiB per image), %zu MiB of HBM are free", what, images, need >> 20, (double)need / images / 1048576.0, free_b >> 20);
+			g_err = m;
+			return NHW_E_ARG;
+		}
+	}
+	const int rc = [&]() -> int { for (const DevBuf &b : set) HIPCHK(hipMalloc(b.p, b.bytes)); return NHW_OK; }();
+	if (rc != NHW_OK) dev_free(set);
+	return rc;
+}
+
+static DevSet host_set(nhw_enc *e, size_t n)   /* input slot, output slot, compacted output, sizes, status, offsets: the host path for n images */
+{
+	return { dev_buf(e->d_in, n * NHW_IMG_BYTES), dev_buf(e->d_out, n * NHW_OUT_STRIDE), dev_buf(e->d_compact, n * NHW_OUT_STRIDE), dev_buf(e->d_sizes, n),
+	         dev_buf(e->d_status, n), dev_buf(e->d_offs, n + 1) };
+}
+static DevSet fit_set(nhw_enc *e)
+{
+	const size_t mb = (size_t)e->max_batch;
+	return { dev_buf(e->fit.in, mb * NHW_IMG_BYTES), dev_buf(e->fit.out, mb * NHW_OUT_STRIDE), dev_buf(e->fit.sizes, mb), dev_buf(e->fit.budget, mb),
+	         dev_buf(e->fit.status, mb), dev_buf(e->fit.quality, mb), dev_buf(e->fit.idx[0], mb), dev_buf(e->fit.idx[1], mb), dev_buf(e->fit.count, 1),
+	         dev_buf(e->fit.open, mb) };
+}
+static DevSet fit_sse_set(nhw_enc *e)
+{
+	const size_t mb = (size_t)e->max_batch;
+	return { dev_buf(e->fit_sse.px, mb * NHW_IMG_BYTES), dev_buf(e->fit_sse.doff, mb), dev_buf(e->fit_sse.sse, mb), dev_buf(e->fit_sse.maxsse, mb),
+	         dev_buf(e->fit_sse.sse_out, mb), dev_buf(e->fit_sse.dstatus, mb) };
+}
+
 extern "C" void nhw_enc_destroy(nhw_enc *e);
 static int host_buffers(nhw_enc *e, int n);
-static void fit_free(nhw_enc *e);
-static void fit_sse_free(nhw_enc *e);
 /* device bytes per image of the host path's staging (nhw_enc_batch / nhw_enc_synth_batch): input slot, output slot, compacted output */
 #define HOST_PATH_BYTES ((size_t)NHW_IMG_BYTES + 2 * (size_t)NHW_OUT_STRIDE + 24)
 extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_enc **out)
@@ -185,6 +232,8 @@ extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_
 		{ const char *lc = getenv("NHW_LOW_CHROMA"); e->low_chroma = lc ? atoi(lc) : 2; }
 		HIPCHK(hipStreamCreateWithFlags(&e->ll_stream, hipStreamNonBlocking));
 		for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&e->ll_ev[i], hipEventDisableTiming));
+		for (int i = 0; i < 2; i++) HIPCHK(hipEventCreate(&e->fit_ev[i]));
+		HIPCHK(hipHostMalloc((void **)&e->h_fit_count, sizeof(int), hipHostMallocDefault));
 		/* the host path's staging buffers, for the whole of max_batch, now: allocated on the first nhw_enc_batch they made that call twice as
 		 * slow as the ones behind it (gigabytes of hipMalloc inside the timed region of whoever measured it).  A caller that only ever hands over
 		 * device buffers says NHW_CREATE_DEVICE_ONLY and does not pay for them; should it call the host path after all, that call allocates. */
@@ -213,14 +262,11 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	(void)hipSetDevice(e->device);
 	(void)hipDeviceSynchronize();
 	if (e->ws.base) (void)hipFree(e->ws.base);
-	if (e->d_in) (void)hipFree(e->d_in);
-	if (e->d_out) (void)hipFree(e->d_out);
-	if (e->d_compact) (void)hipFree(e->d_compact);
-	if (e->d_sizes) (void)hipFree(e->d_sizes);
-	if (e->d_status) (void)hipFree(e->d_status);
-	if (e->d_offs) (void)hipFree(e->d_offs);
-	fit_free(e);
-	fit_sse_free(e);
+	dev_free(host_set(e, 0));
+	dev_free(fit_set(e));
+	dev_free(fit_sse_set(e));
+	if (e->h_fit_count) (void)hipHostFree(e->h_fit_count);
+	for (int i = 0; i < 2; i++) if (e->fit_ev[i]) (void)hipEventDestroy(e->fit_ev[i]);
 	for (int i = 0; i < 7; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
 	if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
 	for (int i = 0; i < 4; i++) if (e->part_stream[i]) (void)hipStreamDestroy(e->part_stream[i]);
@@ -530,17 +576,11 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t *out, const uint3
 static int host_buffers(nhw_enc *e, int n)
 {
 	if (e->conv_cap >= n) return NHW_OK;
-	void **ptrs[6] = { (void **)&e->d_in, (void **)&e->d_out, (void **)&e->d_compact, (void **)&e->d_sizes, (void **)&e->d_status, (void **)&e->d_offs };
-	for (auto pp : ptrs) { if (*pp) (void)hipFree(*pp); *pp = nullptr; }
+	dev_free(host_set(e, 0));
 	e->conv_cap = 0;
-	HIPCHK(hipMalloc((void **)&e->d_in, (size_t)n * NHW_IMG_BYTES));
-	HIPCHK(hipMalloc((void **)&e->d_out, (size_t)n * NHW_OUT_STRIDE));
-	HIPCHK(hipMalloc((void **)&e->d_compact, (size_t)n * NHW_OUT_STRIDE));
-	HIPCHK(hipMalloc((void **)&e->d_sizes, sizeof(uint32_t) * n));
-	HIPCHK(hipMalloc((void **)&e->d_status, sizeof(int32_t) * n));
-	HIPCHK(hipMalloc((void **)&e->d_offs, sizeof(uint64_t) * (n + 1)));
-	e->conv_cap = n;
-	return NHW_OK;
+	const int rc = dev_alloc(host_set(e, (size_t)n), nullptr, n);
+	if (rc == NHW_OK) e->conv_cap = n;
+	return rc;
 }
 
 /* compact the per-image output slots and bring them to the host */
@@ -600,154 +640,6 @@ extern "C" int nhw_enc_synth_batch(nhw_enc *e, int n, uint32_t seed_base, int qu
 	return host_download(e, n, out_arena, arena_cap, out_off, status);
 }
 
-/* ------------------------------------------------------------------------------------------------ encode to a byte budget */
-/* device bytes per image of the search's buffers: staging input and output slot, staging size / status, two list entries, budget,
- * quality, open flag */
-#define FIT_BYTES ((size_t)NHW_IMG_BYTES + (size_t)NHW_OUT_STRIDE + 4 * 7 + 1)
-
-static void fit_free(nhw_enc *e)
-{
-	void *dev[] = { e->d_fit_in, e->d_fit_out, e->d_fit_sizes, e->d_fit_budget, e->d_fit_status, e->d_fit_quality, e->d_fit_idx[0], e->d_fit_idx[1],
-	                e->d_fit_count, e->d_fit_open };
-	for (void *p : dev) if (p) (void)hipFree(p);
-	if (e->h_fit_count) (void)hipHostFree(e->h_fit_count);
-	for (int k = 0; k < 2; k++) if (e->fit_ev[k]) (void)hipEventDestroy(e->fit_ev[k]);
-	e->d_fit_in = e->d_fit_out = nullptr; e->d_fit_sizes = e->d_fit_budget = nullptr; e->d_fit_status = e->d_fit_quality = nullptr;
-	e->d_fit_idx[0] = e->d_fit_idx[1] = e->d_fit_count = nullptr; e->d_fit_open = nullptr; e->h_fit_count = nullptr;
-	e->fit_ev[0] = e->fit_ev[1] = nullptr;
-	e->fit_ready = false;
-}
-
-/* the search's buffers for max_batch images, on the first fit call; a failure half-way leaves none behind */
-static int fit_buffers(nhw_enc *e)
-{
-	if (e->fit_ready) return NHW_OK;
-	const size_t mb = (size_t)e->max_batch;
-	size_t free_b = 0, total_b = 0;
-	HIPCHK(hipMemGetInfo(&free_b, &total_b));
-	const size_t need = FIT_BYTES * mb;
-	if (need > free_b) {
-		char b[200];
-		snprintf(b, sizeof b, "budget search buffers for max_batch %d need %zu MiB (%.1f MiB per image), %zu MiB of HBM are free", e->max_batch, need >> 20, (double)need / mb / 1048576.0, free_b >> 20);
-		g_err = b;
-		return NHW_E_ARG;
-	}
-	const int rc = [&]() -> int {
-		HIPCHK(hipMalloc((void **)&e->d_fit_in, mb * NHW_IMG_BYTES));
-		HIPCHK(hipMalloc((void **)&e->d_fit_out, mb * NHW_OUT_STRIDE));
-		HIPCHK(hipMalloc((void **)&e->d_fit_sizes, mb * sizeof(uint32_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_budget, mb * sizeof(uint32_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_status, mb * sizeof(int32_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_quality, mb * sizeof(int32_t)));
-		for (int k = 0; k < 2; k++) HIPCHK(hipMalloc((void **)&e->d_fit_idx[k], mb * sizeof(int)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_count, sizeof(int)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_open, mb));
-		HIPCHK(hipHostMalloc((void **)&e->h_fit_count, sizeof(int), hipHostMallocDefault));
-		for (int k = 0; k < 2; k++) HIPCHK(hipEventCreate(&e->fit_ev[k]));
-		return NHW_OK;
-	}();
-	if (rc != NHW_OK) { fit_free(e); return rc; }
-	e->fit_ready = true;
-	return NHW_OK;
-}
-
-/* everything a fit call can refuse without touching the device; fills the ladder (NULL = 23 .. 1, or with `ascending` 1 .. 23) */
-static int fit_args(nhw_enc *e, int n, const int *ladder, int ladder_len, bool ascending, int q[23], int *len)
-{
-	if (n < 1 || n > e->max_batch || ladder_len < 0 || ladder_len > 23 || (ladder_len == 0) != (ladder == nullptr)) { g_err = "bad argument"; return NHW_E_ARG; }
-	if (e->stop_after) { g_err = "fit call: not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
-	*len = ladder ? ladder_len : 23;
-	bool seen[24] = {};
-	for (int r = 0; r < *len; r++) {
-		q[r] = ladder ? ladder[r] : ascending ? r + 1 : 23 - r;
-		if (!nhw_quality_supported(q[r]) || seen[q[r]]) { g_err = "ladder: qualities must be distinct and in 1..23"; return NHW_E_QUALITY; }
-		seen[q[r]] = true;
-	}
-	return NHW_OK;
-}
-
-/* Top-down walk of the ladder.  Rung 1 encodes the whole batch straight into the caller's slots (the open list is the identity); every
- * later rung gathers the still-open images from d_bgr (by original index: never from a staging slot, so nothing is copied onto itself),
- * encodes them as a batch of their own into the staging output and copies the files of the images that close into the caller's slots.
- * Between rungs the open list is compacted on the device and its length waited for on the host. */
-extern "C" int nhw_enc_fit_batch_device(nhw_enc *e, const void *d_bgr, int n, const uint32_t *d_max_bytes, const int *ladder, int ladder_len,
-                                        void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, void *stream)
-{
-	if (!e || !d_bgr || !d_max_bytes || !d_out || !d_sizes || !d_status || !d_quality) { g_err = "bad argument"; return NHW_E_ARG; }
-	if ((uintptr_t)d_bgr & 15) { g_err = "nhw_enc_fit_batch_device: d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
-	int q[23], len = 0;
-	{ const int rc = fit_args(e, n, ladder, ladder_len, false, q, &len); if (rc) return rc; }
-	HIPCHK(hipSetDevice(e->device));
-	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-	{ hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	  HIPCHK(hipStreamIsCapturing(s, &cs));
-	  if (cs != hipStreamCaptureStatusNone) { g_err = "nhw_enc_fit_batch_device waits on the host between rungs and cannot be captured"; return NHW_E_ARG; } }
-	{ const int rc = fit_buffers(e); if (rc) return rc; }
-	e->fit_done = false;
-	nhw_fit_stats st;
-	memset(&st, 0, sizeof st);
-	const uint32_t *budget = d_max_bytes;
-	uint8_t *out = (uint8_t *)d_out;
-	int m = n, cur = 0;
-	HIPCHK(hipEventRecord(e->fit_ev[0], s));
-	for (int r = 0; r < len; r++) {
-		const bool first = r == 0, last = r == len - 1;
-		const int *idx = first ? nullptr : e->d_fit_idx[cur];
-		st.quality[r] = q[r]; st.images[r] = m; st.rungs = r + 1;
-		if (first) {
-			const int rc = nhw_enc_batch_device(e, d_bgr, m, q[r], d_out, d_sizes, d_status, s);
-			if (rc) return rc;
-		} else {
-			nhw_launch_fit_gather((const uint8_t *)d_bgr, idx, m, e->d_fit_in, s);
-			HIPCHK(hipGetLastError());
-			const int rc = nhw_enc_batch_device(e, e->d_fit_in, m, q[r], e->d_fit_out, e->d_fit_sizes, e->d_fit_status, s);
-			if (rc) return rc;
-		}
-		nhw_launch_fit_select(idx, m, e->d_fit_out, e->d_fit_sizes, e->d_fit_status, budget, q[r], last, out, d_sizes, d_status, d_quality, e->d_fit_open, s);
-		HIPCHK(hipGetLastError());
-		if (last) break;
-		nhw_launch_fit_compact(e->d_fit_open, idx, m, e->d_fit_idx[cur ^ 1], e->d_fit_count, s);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(e->h_fit_count, e->d_fit_count, sizeof(int), hipMemcpyDeviceToHost, s));
-		HIPCHK(hipStreamSynchronize(s));
-		m = *e->h_fit_count;
-		cur ^= 1;
-		if (m == 0) break;
-	}
-	HIPCHK(hipEventRecord(e->fit_ev[1], s));
-	e->fit_stats = st;
-	e->fit_done = true;
-	return NHW_OK;
-}
-
-extern "C" int nhw_enc_fit_batch(nhw_enc *e, const uint8_t *bgr, int n, const uint32_t *max_bytes, const int *ladder, int ladder_len,
-                                 uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality)
-{
-	if (!e || !bgr || !max_bytes || !out_arena || !out_off || !status || !quality) { g_err = "bad argument"; return NHW_E_ARG; }
-	int q[23], len = 0;
-	{ const int rc = fit_args(e, n, ladder, ladder_len, false, q, &len); if (rc) return rc; }
-	HIPCHK(hipSetDevice(e->device));
-	{ const int rc = host_buffers(e, n); if (rc) return rc; }
-	{ const int rc = fit_buffers(e); if (rc) return rc; }
-	hipStream_t s = e->own_stream;
-	HIPCHK(hipMemcpyAsync(e->d_in, bgr, (size_t)n * NHW_IMG_BYTES, hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(e->d_fit_budget, max_bytes, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-	{ const int rc = nhw_enc_fit_batch_device(e, e->d_in, n, e->d_fit_budget, ladder, ladder_len, e->d_out, e->d_sizes, e->d_status, e->d_fit_quality, s); if (rc) return rc; }
-	{ const int rc = host_download(e, n, out_arena, arena_cap, out_off, status); if (rc) return rc; }
-	HIPCHK(hipMemcpy(quality, e->d_fit_quality, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-	return NHW_OK;
-}
-
-extern "C" int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s)
-{
-	if (!e || !s || !e->fit_done) { g_err = "no completed fit call"; return NHW_E_ARG; }
-	HIPCHK(hipSetDevice(e->device));
-	HIPCHK(hipEventSynchronize(e->fit_ev[1]));
-	*s = e->fit_stats;
-	HIPCHK(hipEventElapsedTime(&s->total_ms, e->fit_ev[0], e->fit_ev[1]));
-	return NHW_OK;
-}
-
 /* ------------------------------------------------------------------------------------------------ distortion */
 extern "C" int nhw_sse_batch_device(const void *d_a, const void *d_b, int n, uint64_t *d_sse, void *stream)
 {
@@ -758,18 +650,7 @@ extern "C" int nhw_sse_batch_device(const void *d_a, const void *d_b, int n, uin
 	return NHW_OK;
 }
 
-/* ------------------------------------------------------------------------------------------------ encode to a distortion budget */
-/* device bytes per image of the distortion search's own buffers: a decoded picture, offset, SSE, target, achieved SSE, decoder status */
-#define FIT_SSE_BYTES ((size_t)NHW_IMG_BYTES + 8 * 4 + 4)
-
-static void fit_sse_free(nhw_enc *e)
-{
-	void *dev[] = { e->d_fit_px, e->d_fit_doff, e->d_fit_sse, e->d_fit_maxsse, e->d_fit_sse_out, e->d_fit_dstatus };
-	for (void *p : dev) if (p) (void)hipFree(p);
-	e->d_fit_px = nullptr; e->d_fit_doff = e->d_fit_sse = e->d_fit_maxsse = e->d_fit_sse_out = nullptr; e->d_fit_dstatus = nullptr;
-	e->fit_sse_ready = false;
-}
-
+/* ------------------------------------------------------------------------------------------------ encode to a byte or distortion budget */
 /* i * NHW_OUT_STRIDE for i < n */
 __global__ void k_fit_doff(uint64_t *off, int n)
 {
@@ -777,102 +658,111 @@ __global__ void k_fit_doff(uint64_t *off, int n)
 	if (i < n) off[i] = (uint64_t)i * NHW_OUT_STRIDE;
 }
 
-/* the distortion search's buffers for max_batch images, on the first SSE-fit call (byte-budget callers never pay for them) */
-static int fit_sse_buffers(nhw_enc *e)
+/* the search's buffers for max_batch images on the first fit call, and the distortion search's own (`sse`) on the first SSE-fit call */
+static int fit_buffers(nhw_enc *e, bool sse)
 {
-	if (e->fit_sse_ready) return NHW_OK;
-	const size_t mb = (size_t)e->max_batch;
-	size_t free_b = 0, total_b = 0;
-	HIPCHK(hipMemGetInfo(&free_b, &total_b));
-	const size_t need = FIT_SSE_BYTES * mb;
-	if (need > free_b) {
-		char b[200];
-		snprintf(b, sizeof b, "distortion search buffers for max_batch %d need %zu MiB (%.1f MiB per image), %zu MiB of HBM are free", e->max_batch, need >> 20, (double)need / mb / 1048576.0, free_b >> 20);
-		g_err = b;
-		return NHW_E_ARG;
-	}
+	if (!e->fit.in) { const int rc = dev_alloc(fit_set(e), "budget search buffers", e->max_batch); if (rc) return rc; }
+	if (!sse || e->fit_sse.px) return NHW_OK;
 	const int rc = [&]() -> int {
-		HIPCHK(hipMalloc((void **)&e->d_fit_px, mb * NHW_IMG_BYTES));
-		HIPCHK(hipMalloc((void **)&e->d_fit_doff, mb * sizeof(uint64_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_sse, mb * sizeof(uint64_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_maxsse, mb * sizeof(uint64_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_sse_out, mb * sizeof(uint64_t)));
-		HIPCHK(hipMalloc((void **)&e->d_fit_dstatus, mb * sizeof(int32_t)));
-		k_fit_doff<<<(e->max_batch + 255) / 256, 256, 0, e->own_stream>>>(e->d_fit_doff, e->max_batch);
+		{ const int rc_ = dev_alloc(fit_sse_set(e), "distortion search buffers", e->max_batch); if (rc_) return rc_; }
+		k_fit_doff<<<(e->max_batch + 255) / 256, 256, 0, e->own_stream>>>(e->fit_sse.doff, e->max_batch);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipStreamSynchronize(e->own_stream));
 		return NHW_OK;
 	}();
-	if (rc != NHW_OK) { fit_sse_free(e); return rc; }
-	e->fit_sse_ready = true;
-	return NHW_OK;
+	if (rc != NHW_OK) dev_free(fit_sse_set(e));
+	return rc;
 }
 
-/* everything nhw_enc_fit_sse_batch* can refuse about the decoder handle */
-static int fit_dec_args(nhw_enc *e, nhw_dec *d, int n)
-{
-	if (!d) { g_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
-	int device = 0, max_batch = 0, stop_after = 0;
-	nhw_dec_props(d, &device, &max_batch, &stop_after);
-	if (max_batch < n) { g_err = "nhw_enc_fit_sse_batch: the decoder's max_batch is below n"; return NHW_E_ARG; }
-	if (device != e->device) { g_err = "nhw_enc_fit_sse_batch: the decoder is on another device than the encoder"; return NHW_E_ARG; }
-	if (stop_after) { g_err = "nhw_enc_fit_sse_batch: not with a decoder debug stop set (every rung must be a whole decode)"; return NHW_E_ARG; }
-	return NHW_OK;
-}
+/* One fit call: the images, the per-image limits in device memory (uint32_t bytes, or with `by_sse` uint64_t SSE scored by a decode of every
+ * rung by `dec`), the ladder and the caller's outputs.  fit_check fills in the ladder's qualities and the stream. */
+struct FitCall {
+	const char *who;                     /* the entry point, for the messages */
+	bool by_sse;
+	nhw_dec *dec;
+	const void *bgr;
+	int n;
+	const void *limit;
+	const int *ladder;
+	int ladder_len;
+	void *out = nullptr; uint32_t *sizes = nullptr; int32_t *status = nullptr; int32_t *quality = nullptr; uint64_t *sse = nullptr;
+	hipStream_t s = nullptr;
+	int q[23] = {}, len = 0;
+};
 
-/* The byte search's walk (nhw_enc_fit_batch_device) with a different verdict: after a rung's encode its files are decoded as one batch
- * on `stream` (rung 1 from the caller's arena, later rungs from the staging one; both hold file j at j * NHW_OUT_STRIDE) and the decoded
- * pictures are compared with the rung's input pictures (rung 1: d_bgr; later rungs: the gathered staging slab), so list entry j's SSE
- * lines up with its status.  An image whose encode failed decodes an empty file (NHW_E_FORMAT) and is not counted as fitting. */
-extern "C" int nhw_enc_fit_sse_batch_device(nhw_enc *e, nhw_dec *d, const void *d_bgr, int n, const uint64_t *d_max_sse, const int *ladder, int ladder_len,
-                                            void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, uint64_t *d_sse, void *stream)
+/* Everything a fit call refuses before it launches anything, in this order: NULL pointers (`ptrs` false), an unaligned c.bgr (NULL while
+ * the host path checks: it uploads into an aligned buffer), n, the ladder (NULL = 23 .. 1 for bytes, 1 .. 23 for SSE), a debug stop, the
+ * SSE search's decoder, a capturing stream.  Makes e's device current. */
+static int fit_check(nhw_enc *e, FitCall &c, bool ptrs, void *stream)
 {
-	if (!e || !d_bgr || !d_max_sse || !d_out || !d_sizes || !d_status || !d_quality || !d_sse) { g_err = "bad argument"; return NHW_E_ARG; }
-	if ((uintptr_t)d_bgr & 15) { g_err = "nhw_enc_fit_sse_batch_device: d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
-	int q[23], len = 0;
-	{ const int rc = fit_args(e, n, ladder, ladder_len, true, q, &len); if (rc) return rc; }
-	{ const int rc = fit_dec_args(e, d, n); if (rc) return rc; }
+	if (!e || !ptrs) { g_err = "bad argument"; return NHW_E_ARG; }
+	const std::string who = c.who;
+	if ((uintptr_t)c.bgr & 15) { g_err = who + ": d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
+	if (c.n < 1 || c.n > e->max_batch || c.ladder_len < 0 || c.ladder_len > 23 || (c.ladder_len == 0) != (c.ladder == nullptr)) { g_err = "bad argument"; return NHW_E_ARG; }
+	if (e->stop_after) { g_err = who + ": not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
+	c.len = c.ladder ? c.ladder_len : 23;
+	bool seen[24] = {};
+	for (int r = 0; r < c.len; r++) {
+		c.q[r] = c.ladder ? c.ladder[r] : c.by_sse ? r + 1 : 23 - r;
+		if (!nhw_quality_supported(c.q[r]) || seen[c.q[r]]) { g_err = "ladder: qualities must be distinct and in 1..23"; return NHW_E_QUALITY; }
+		seen[c.q[r]] = true;
+	}
+	if (c.by_sse) {
+		if (!c.dec) { g_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
+		int device = 0, max_batch = 0, stop_after = 0;
+		nhw_dec_props(c.dec, &device, &max_batch, &stop_after);
+		if (max_batch < c.n) { g_err = who + ": the decoder's max_batch is below n"; return NHW_E_ARG; }
+		if (device != e->device) { g_err = who + ": the decoder is on another device than the encoder"; return NHW_E_ARG; }
+		if (stop_after) { g_err = who + ": not with a decoder debug stop set (every rung must be a whole decode)"; return NHW_E_ARG; }
+	}
 	HIPCHK(hipSetDevice(e->device));
-	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
-	{ hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-	  HIPCHK(hipStreamIsCapturing(s, &cs));
-	  if (cs != hipStreamCaptureStatusNone) { g_err = "nhw_enc_fit_sse_batch_device waits on the host between rungs and cannot be captured"; return NHW_E_ARG; } }
-	{ const int rc = fit_buffers(e); if (rc) return rc; }
-	{ const int rc = fit_sse_buffers(e); if (rc) return rc; }
+	c.s = stream ? (hipStream_t)stream : e->own_stream;
+	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+	HIPCHK(hipStreamIsCapturing(c.s, &cs));
+	if (cs != hipStreamCaptureStatusNone) { g_err = who + " waits on the host between rungs and cannot be captured"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+/* The one walk of both searches, down the ladder.  Rung 1 encodes the whole batch straight into the caller's slots (the open list is the
+ * identity); every later rung gathers the still-open images from c.bgr (by original index: never from a staging slot, so nothing is copied
+ * onto itself) and encodes them as a batch of their own into the staging output.  The SSE search then decodes the rung's files as one batch
+ * on the same stream (both arenas hold file j at j * NHW_OUT_STRIDE) and compares the decoded pictures with the rung's input pictures, so
+ * list entry j's SSE lines up with its status; an image whose encode failed decodes an empty file (NHW_E_FORMAT) and is not counted as
+ * fitting.  k_fit_select copies the files of the images that close into the caller's slots.  Between rungs the open list is compacted on
+ * the device and its length waited for on the host. */
+static int fit_walk(nhw_enc *e, const FitCall &c)
+{
+	const hipStream_t s = c.s;
 	e->fit_done = false;
 	nhw_fit_stats st;
 	memset(&st, 0, sizeof st);
-	uint8_t *out = (uint8_t *)d_out;
-	int m = n, cur = 0;
+	int m = c.n, cur = 0;
 	HIPCHK(hipEventRecord(e->fit_ev[0], s));
-	for (int r = 0; r < len; r++) {
-		const bool first = r == 0, last = r == len - 1;
-		const int *idx = first ? nullptr : e->d_fit_idx[cur];
-		st.quality[r] = q[r]; st.images[r] = m; st.rungs = r + 1;
-		const uint8_t *pics = first ? (const uint8_t *)d_bgr : e->d_fit_in;
-		const uint8_t *files = first ? out : e->d_fit_out;
-		const uint32_t *lens = first ? d_sizes : e->d_fit_sizes;
-		if (first) {
-			const int rc = nhw_enc_batch_device(e, d_bgr, m, q[r], d_out, d_sizes, d_status, s);
-			if (rc) return rc;
-		} else {
-			nhw_launch_fit_gather((const uint8_t *)d_bgr, idx, m, e->d_fit_in, s);
+	for (int r = 0; r < c.len; r++) {
+		const bool first = r == 0, last = r == c.len - 1;
+		const int *idx = first ? nullptr : e->fit.idx[cur];
+		st.quality[r] = c.q[r]; st.images[r] = m; st.rungs = r + 1;
+		const uint8_t *pics = first ? (const uint8_t *)c.bgr : e->fit.in;   /* the rung's encode: its pictures and its outputs */
+		uint8_t *files = first ? (uint8_t *)c.out : e->fit.out;
+		uint32_t *lens = first ? c.sizes : e->fit.sizes;
+		int32_t *codes = first ? c.status : e->fit.status;
+		if (!first) {
+			nhw_launch_fit_gather((const uint8_t *)c.bgr, idx, m, e->fit.in, s);
 			HIPCHK(hipGetLastError());
-			const int rc = nhw_enc_batch_device(e, e->d_fit_in, m, q[r], e->d_fit_out, e->d_fit_sizes, e->d_fit_status, s);
-			if (rc) return rc;
 		}
-		{
-			const int rc = nhw_dec_batch_device(d, files, e->d_fit_doff, lens, m, e->d_fit_px, e->d_fit_dstatus, nullptr, s);
+		{ const int rc = nhw_enc_batch_device(e, pics, m, c.q[r], files, lens, codes, s); if (rc) return rc; }
+		if (c.by_sse) {
+			const int rc = nhw_dec_batch_device(c.dec, files, e->fit_sse.doff, lens, m, e->fit_sse.px, e->fit_sse.dstatus, nullptr, s);
 			if (rc) { g_err = std::string("decode of a rung: ") + nhw_dec_last_error(); return rc; }
+			HIPCHK(nhw_launch_sse(pics, e->fit_sse.px, m, e->fit_sse.sse, s));
 		}
-		HIPCHK(nhw_launch_sse(pics, e->d_fit_px, m, e->d_fit_sse, s));
-		nhw_launch_fit_select_sse(idx, m, e->d_fit_out, e->d_fit_sizes, e->d_fit_status, e->d_fit_dstatus, e->d_fit_sse, d_max_sse, q[r], last, out, d_sizes,
-		                          d_status, d_quality, d_sse, e->d_fit_open, s);
+		nhw_launch_fit_select(idx, m, e->fit.out, e->fit.sizes, e->fit.status, c.limit, e->fit_sse.dstatus, c.by_sse ? e->fit_sse.sse : nullptr, c.q[r], last,
+		                      (uint8_t *)c.out, c.sizes, c.status, c.quality, c.sse, e->fit.open, s);
 		HIPCHK(hipGetLastError());
 		if (last) break;
-		nhw_launch_fit_compact(e->d_fit_open, idx, m, e->d_fit_idx[cur ^ 1], e->d_fit_count, s);
+		nhw_launch_fit_compact(e->fit.open, idx, m, e->fit.idx[cur ^ 1], e->fit.count, s);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(e->h_fit_count, e->d_fit_count, sizeof(int), hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(e->h_fit_count, e->fit.count, sizeof(int), hipMemcpyDeviceToHost, s));
 		HIPCHK(hipStreamSynchronize(s));
 		m = *e->h_fit_count;
 		cur ^= 1;
@@ -884,26 +774,69 @@ extern "C" int nhw_enc_fit_sse_batch_device(nhw_enc *e, nhw_dec *d, const void *
 	return NHW_OK;
 }
 
+/* the device entry points: check, allocate, walk */
+static int fit_device(nhw_enc *e, FitCall &c, bool ptrs, void *stream)
+{
+	int rc = fit_check(e, c, ptrs, stream);
+	if (rc == NHW_OK) rc = fit_buffers(e, c.by_sse);
+	return rc != NHW_OK ? rc : fit_walk(e, c);
+}
+
+/* the host conveniences: the images and the n limits uploaded, the search on the handle's own stream, the files compacted and brought back
+ * as nhw_enc_batch does, then the qualities and (the SSE search) the achieved SSE */
+static int fit_host(nhw_enc *e, FitCall &c, bool ptrs, const uint8_t *bgr, const void *limit, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off,
+                    int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	{ const int rc = fit_check(e, c, ptrs, nullptr); if (rc) return rc; }
+	{ const int rc = host_buffers(e, c.n); if (rc) return rc; }
+	{ const int rc = fit_buffers(e, c.by_sse); if (rc) return rc; }
+	void *d_limit = c.by_sse ? (void *)e->fit_sse.maxsse : (void *)e->fit.budget;
+	HIPCHK(hipMemcpyAsync(e->d_in, bgr, (size_t)c.n * NHW_IMG_BYTES, hipMemcpyHostToDevice, c.s));
+	HIPCHK(hipMemcpyAsync(d_limit, limit, (c.by_sse ? sizeof(uint64_t) : sizeof(uint32_t)) * c.n, hipMemcpyHostToDevice, c.s));
+	c.bgr = e->d_in; c.limit = d_limit;
+	c.out = e->d_out; c.sizes = e->d_sizes; c.status = e->d_status; c.quality = e->fit.quality; c.sse = e->fit_sse.sse_out;
+	{ const int rc = fit_walk(e, c); if (rc) return rc; }
+	{ const int rc = host_download(e, c.n, out_arena, arena_cap, out_off, status); if (rc) return rc; }
+	HIPCHK(hipMemcpy(quality, e->fit.quality, sizeof(int32_t) * c.n, hipMemcpyDeviceToHost));
+	if (c.by_sse) HIPCHK(hipMemcpy(sse, e->fit_sse.sse_out, sizeof(uint64_t) * c.n, hipMemcpyDeviceToHost));
+	return NHW_OK;
+}
+
+extern "C" int nhw_enc_fit_batch_device(nhw_enc *e, const void *d_bgr, int n, const uint32_t *d_max_bytes, const int *ladder, int ladder_len,
+                                        void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	FitCall c = { "nhw_enc_fit_batch_device", false, nullptr, d_bgr, n, d_max_bytes, ladder, ladder_len, d_out, d_sizes, d_status, d_quality, nullptr };
+	return fit_device(e, c, d_bgr && d_max_bytes && d_out && d_sizes && d_status && d_quality, stream);
+}
+
+extern "C" int nhw_enc_fit_batch(nhw_enc *e, const uint8_t *bgr, int n, const uint32_t *max_bytes, const int *ladder, int ladder_len,
+                                 uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality)
+{
+	FitCall c = { "nhw_enc_fit_batch", false, nullptr, nullptr, n, nullptr, ladder, ladder_len };
+	return fit_host(e, c, bgr && max_bytes && out_arena && out_off && status && quality, bgr, max_bytes, out_arena, arena_cap, out_off, status, quality, nullptr);
+}
+
+extern "C" int nhw_enc_fit_sse_batch_device(nhw_enc *e, nhw_dec *d, const void *d_bgr, int n, const uint64_t *d_max_sse, const int *ladder, int ladder_len,
+                                            void *d_out, uint32_t *d_sizes, int32_t *d_status, int32_t *d_quality, uint64_t *d_sse, void *stream)
+{
+	FitCall c = { "nhw_enc_fit_sse_batch_device", true, d, d_bgr, n, d_max_sse, ladder, ladder_len, d_out, d_sizes, d_status, d_quality, d_sse };
+	return fit_device(e, c, d_bgr && d_max_sse && d_out && d_sizes && d_status && d_quality && d_sse, stream);
+}
+
 extern "C" int nhw_enc_fit_sse_batch(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
                                      uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse)
 {
-	if (!e || !bgr || !max_sse || !out_arena || !out_off || !status || !quality || !sse) { g_err = "bad argument"; return NHW_E_ARG; }
-	int q[23], len = 0;
-	{ const int rc = fit_args(e, n, ladder, ladder_len, true, q, &len); if (rc) return rc; }
-	{ const int rc = fit_dec_args(e, d, n); if (rc) return rc; }
+	FitCall c = { "nhw_enc_fit_sse_batch", true, d, nullptr, n, nullptr, ladder, ladder_len };
+	return fit_host(e, c, bgr && max_sse && out_arena && out_off && status && quality && sse, bgr, max_sse, out_arena, arena_cap, out_off, status, quality, sse);
+}
+
+extern "C" int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s)
+{
+	if (!e || !s || !e->fit_done) { g_err = "no completed fit call"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(e->device));
-	{ const int rc = host_buffers(e, n); if (rc) return rc; }
-	{ const int rc = fit_buffers(e); if (rc) return rc; }
-	{ const int rc = fit_sse_buffers(e); if (rc) return rc; }
-	hipStream_t s = e->own_stream;
-	HIPCHK(hipMemcpyAsync(e->d_in, bgr, (size_t)n * NHW_IMG_BYTES, hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(e->d_fit_maxsse, max_sse, sizeof(uint64_t) * n, hipMemcpyHostToDevice, s));
-	{ const int rc = nhw_enc_fit_sse_batch_device(e, d, e->d_in, n, e->d_fit_maxsse, ladder, ladder_len, e->d_out, e->d_sizes, e->d_status, e->d_fit_quality,
-	                                              e->d_fit_sse_out, s);
-	  if (rc) return rc; }
-	{ const int rc = host_download(e, n, out_arena, arena_cap, out_off, status); if (rc) return rc; }
-	HIPCHK(hipMemcpy(quality, e->d_fit_quality, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
-	HIPCHK(hipMemcpy(sse, e->d_fit_sse_out, sizeof(uint64_t) * n, hipMemcpyDeviceToHost));
+	HIPCHK(hipEventSynchronize(e->fit_ev[1]));
+	*s = e->fit_stats;
+	HIPCHK(hipEventElapsedTime(&s->total_ms, e->fit_ev[0], e->fit_ev[1]));
 	return NHW_OK;
 }
 

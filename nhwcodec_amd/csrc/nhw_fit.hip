@@ -125,20 +125,19 @@ void nhw_launch_fit_gather(const uint8_t *d_bgr, const int *idx, int m, uint8_t 
 	k_fit_gather<<<dim3(FIT_GATHER_X, m), FIT_GATHER_T, 0, s>>>(reinterpret_cast<const uint4 *>(d_bgr), idx, reinterpret_cast<uint4 *>(staging));
 }
 
-void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const uint32_t *budget,
-                           int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status, int32_t *qual, uint8_t *open, hipStream_t s)
+/* one launcher for both criteria: sse == nullptr selects FitBytes (limit: uint32_t budgets), otherwise FitSse (limit: uint64_t targets, with
+ * the rung's decode status and SSE per list entry, and the caller's d_sse) */
+void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const void *limit,
+                           const int32_t *dec_status, const uint64_t *sse, int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status,
+                           int32_t *qual, uint64_t *sse_out, uint8_t *open, hipStream_t s)
 {
 	const int aligned = ((uintptr_t)out & 15) == 0;     /* the staging arena is hipMalloc'd; the caller's may sit anywhere */
-	k_fit_select<<<m, 256, 0, s>>>(FitBytes{ budget }, idx, st_out, st_sizes, st_status, quality, last, out, sizes, status, qual, open, aligned);
-}
-
-void nhw_launch_fit_select_sse(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const int32_t *dec_status,
-                               const uint64_t *sse, const uint64_t *max_sse, int quality, int last, uint8_t *out, uint32_t *sizes, int32_t *status,
-                               int32_t *qual, uint64_t *sse_out, uint8_t *open, hipStream_t s)
-{
-	const int aligned = ((uintptr_t)out & 15) == 0;
-	k_fit_select<<<m, 256, 0, s>>>(FitSse{ max_sse, sse, dec_status, sse_out }, idx, st_out, st_sizes, st_status, quality, last, out, sizes, status, qual,
-	                               open, aligned);
+	if (sse)
+		k_fit_select<<<m, 256, 0, s>>>(FitSse{ (const uint64_t *)limit, sse, dec_status, sse_out }, idx, st_out, st_sizes, st_status, quality, last, out, sizes,
+		                               status, qual, open, aligned);
+	else
+		k_fit_select<<<m, 256, 0, s>>>(FitBytes{ (const uint32_t *)limit }, idx, st_out, st_sizes, st_status, quality, last, out, sizes, status, qual, open,
+		                               aligned);
 }
 
 void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *next, int *count, hipStream_t s)
