@@ -161,6 +161,33 @@ int nhw_enc_fit_sse_batch_device(nhw_enc *e, nhw_dec *d, const void *d_bgr, int 
 int nhw_enc_fit_sse_batch(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
                           uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse);
 
+/* ---- pictures of any size as padded 512 x 512 tiles ----
+ * A picture is W x H pixels (1 <= W, H <= 65535), 3 bytes a pixel (B, G, R), rows in BMP file order.  It is padded to 512 nx x 512 ny
+ * (nx = ceil(W / 512), ny = ceil(H / 512)) by edge replication: padded pixel (r, c) = picture pixel (min(r, H - 1), min(c, W - 1)).
+ * Tile (ty, tx) is padded rows 512 ty .. and columns 512 tx .., index ty nx + tx; every tile is encoded as an ordinary 512 x 512 image.
+ * Descriptor of a picture in device memory: addr = device address of its first byte (any alignment), pitch = bytes from one row to the
+ * next (>= 3 W, any value), first_tile = global number of its first tile (first_tile[k + 1] = first_tile[k] + tiles(k)), reserved 0. */
+typedef struct { uint64_t addr, pitch; uint32_t width, height, first_tile, reserved; } nhw_picture;   /* 32 bytes */
+/* nx * ny, or NHW_E_ARG for a side outside 1..65535 */
+int nhw_picture_tiles(uint32_t width, uint32_t height);
+/* The global tiles [tile0, tile0 + m) of the pictures d_pics[0 .. n_pics) (a table in device memory, the caller's responsibility), tile t
+ * padded into d_tiles + (t - tile0) * NHW_IMG_BYTES (16-byte aligned); untile: the inverse, from decoded tiles it writes exactly the
+ * pictures' bytes (not the bytes between rows, nothing outside the pictures).  No handle: the current device; stream NULL is the null
+ * stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_pics < 1, m < 1, tile0 < 0, an unaligned d_tiles. */
+int nhw_tile_pictures_device(const nhw_picture *d_pics, int n_pics, int tile0, int m, void *d_tiles, void *stream);
+int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, void *stream);
+/* The .nhwp container (version 1, little-endian): "NHWP", version 1, 3 zero bytes, W (4 bytes), H (4), T = nx ny tile lengths (4 each,
+ * 1 .. NHW_OUT_STRIDE, tile order), then the T .nhw files back to back; exactly 16 + 4 T + the sum of the lengths bytes.  A .nhw file
+ * starts with a byte <= 6, so a stock decoder refuses a container ("Not an .nhw file").  nhw_picture_info: NHW_OK and W, H for a
+ * well-formed container, else NHW_E_FORMAT. */
+int nhw_picture_info(const uint8_t *container, size_t len, uint32_t *width, uint32_t *height);
+/* Host convenience, synchronous: n packed pictures (pitch 3 W), picture i at bgr + in_off[i] with width[i] x height[i] pixels, padded and
+ * tiled on the device in chunks of at most max_batch tiles, encoded at `quality`; picture i's container is out_arena[out_off[i] ..
+ * out_off[i + 1]) (out_off: n + 1 entries; NHW_E_SPACE if arena_cap is short).  status[i] = NHW_OK or the first failing tile's status
+ * (NHW_E_CODEBOOK); a failed picture gets an empty container.  NHW_E_ARG for a bad argument or a side outside 1..65535. */
+int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                     int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status);
+
 /* ---- stage-level entry points (kernel parity tests; same stream rules) ----
  * colour + 4:2:0 (colorspace.c:55-260), any quality 1..23: d_y n*262144 int16, d_u/d_v n*65536 uint8 */
 int nhw_stage_color(nhw_enc *e, const void *d_bgr, int n, int quality, void *d_y, void *d_u, void *d_v, void *stream);
@@ -202,6 +229,10 @@ int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, c
 /* host convenience: H2D of the files (nhw[off[i]..off[i+1])), decode, D2H.  Synchronous. */
 int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality);
 void nhw_dec_bmp_header(uint8_t h[54]);
+/* host convenience for .nhwp containers, synchronous: container i is blob[off[i] .. off[i + 1]) (off: n + 1 entries); its tiles are
+ * decoded in chunks of max_batch, cropped on the device, and picture i (W x H x 3 bytes, pitch 3 W) lands at bgr + out_off[i] (n entries).
+ * status[i] = NHW_OK, or NHW_E_FORMAT for a malformed container or a tile the decoder refuses; that picture's bytes are left untouched. */
+int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status);
 /* hipEvent timings of the last nhw_dec_batch_device call (events on its launch stream): the whole sequence, the entropy stages
  * (parse, prefix-code walk, un-zig-zag), the two level-1 luma synthesis passes and the colour kernel -- the last three are the kernels
  * SURVEY.md 8(d) prices against the HBM roofline for the decode path */

@@ -68,6 +68,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_stage_chroma_l1.argtypes = [P, ctypes.c_int, P]
     L.nhw_stage_analysis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_synthesis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_picture_tiles.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    L.nhw_tile_pictures_device.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]
+    L.nhw_untile_pictures_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_picture_info.argtypes = [P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    L.nhw_enc_pictures.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P, P]
+    L.nhw_dec_pictures.argtypes = [P, P, P, ctypes.c_int, P, P, P]
     return L
 
 
@@ -113,6 +119,82 @@ def sse_device(a, b):
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
+
+
+# ---------------------------------------------------------------- pictures of any size as padded tiles
+PICTURE_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("width", "<u4"), ("height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_picture
+
+
+def picture_tiles(width: int, height: int) -> int:
+    """ceil(width / 512) * ceil(height / 512): the tiles of a width x height picture (sides 1..65535)"""
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise NhwError(f"a picture side must be 1..65535, got {width} x {height}")
+    return ((width + 511) // 512) * ((height + 511) // 512)
+
+
+def _picture_table(pictures, what):
+    """the checked nhw_picture table of a list of uint8 CUDA tensors [H, W, 3] with strides (pitch, 3, 1), on one device -> (table as an
+    int64 CUDA tensor, total tiles, device)"""
+    import numpy as np
+    import torch
+    if not isinstance(pictures, (list, tuple)) or not pictures:
+        raise NhwError(f"{what} wants a non-empty list of uint8 CUDA tensors [H, W, 3]")
+    dev = pictures[0].device if isinstance(pictures[0], torch.Tensor) else None
+    table = np.zeros(len(pictures), PICTURE_DTYPE)
+    tiles = 0
+    for i, x in enumerate(pictures):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 3 and x.shape[2] == 3):
+            raise NhwError(f"{what}: picture {i} is not a uint8 CUDA tensor [H, W, 3]")
+        if x.device != dev:
+            raise NhwError(f"{what}: picture {i} is on {x.device}, picture 0 on {dev}")
+        h, w = int(x.shape[0]), int(x.shape[1])
+        t = picture_tiles(w, h)
+        if x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w):
+            raise NhwError(f"{what}: picture {i} must have strides (pitch >= 3 W, 3, 1), got {tuple(x.stride())}")
+        table[i] = (x.data_ptr(), x.stride(0) if h > 1 else 3 * w, w, h, tiles, 0)
+        tiles += t
+    return torch.from_numpy(table.view(np.int64).copy()).to(dev), tiles, dev
+
+
+def tile_pictures_device(pictures):
+    """Pad every picture to whole 512 x 512 tiles by edge replication and cut the tiles out on the device (k_tile_pad): a list of uint8 CUDA
+    tensors [H, W, 3] (BMP file row order) on one device, rows any pitch (crop views of a larger tensor work without a copy) -> tiles uint8
+    [T, 512, 512, 3], picture after picture, each row-major.  Ordered on torch's current stream; feeds Encoder.encode_device."""
+    import torch
+    table, tiles, dev = _picture_table(pictures, "tile_pictures_device")
+    out = torch.empty((tiles, 512, 512, 3), dtype=torch.uint8, device=dev)
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_tile_pictures_device(table.data_ptr(), len(pictures), 0, tiles, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
+
+
+def untile_pictures_device(tiles, pictures):
+    """The inverse of tile_pictures_device (k_untile_crop): decoded tiles uint8 [T, 512, 512, 3] (e.g. Decoder.decode_device's pixels) into
+    the preallocated pictures (as for tile_pictures_device); only the pictures' own bytes are written.  Ordered on torch's current stream."""
+    import torch
+    table, n_tiles, dev = _picture_table(pictures, "untile_pictures_device")
+    if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.device == dev and tiles.dtype == torch.uint8 and tiles.is_contiguous()
+            and tiles.numel() == n_tiles * IMG_BYTES):
+        raise NhwError(f"untile_pictures_device: `tiles` must be a contiguous uint8 tensor [{n_tiles}, 512, 512, 3] on {dev}")
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_untile_pictures_device(tiles.data_ptr(), table.data_ptr(), len(pictures), 0, n_tiles, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+
+
+def picture_info(container) -> tuple:
+    """(W, H) of a well-formed .nhwp container (nhw_picture_info); raises NhwError otherwise"""
+    import numpy as np
+    b = np.frombuffer(bytes(container), np.uint8)
+    w, h = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = _library().nhw_picture_info(b.ctypes.data if b.size else None, b.size, ctypes.byref(w), ctypes.byref(h))
+    if rc != NHW_OK:
+        raise NhwError(f"not a well-formed .nhwp container (rc={rc})")
+    return w.value, h.value
 
 
 class Encoder:
@@ -356,6 +438,34 @@ class Encoder:
         tiles, shape = tile_images(big)
         return self.encode(tiles, quality), shape
 
+    def encode_pictures(self, pictures, quality: int = QUALITY_DEFAULT):
+        """pictures: a list of numpy uint8 [H, W, 3] (BMP file row order, sides 1..65535) -> a list of .nhwp containers (bytes): every
+        picture padded to whole tiles on the device, the tiles encoded in chunks of max_batch (nhw_enc_pictures).  Raises on a per-picture
+        failure, like encode."""
+        import numpy as np
+        if not isinstance(pictures, (list, tuple)) or not pictures:
+            raise NhwError("encode_pictures wants a non-empty list of uint8 [H, W, 3] arrays")
+        arrs = [np.ascontiguousarray(p) for p in pictures]
+        for i, a in enumerate(arrs):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise NhwError(f"encode_pictures: picture {i} is not uint8 [H, W, 3], got {a.dtype} {a.shape}")
+            picture_tiles(a.shape[1], a.shape[0])
+        n = len(arrs)
+        width = np.array([a.shape[1] for a in arrs], np.uint32)
+        height = np.array([a.shape[0] for a in arrs], np.uint32)
+        in_off = np.zeros(n + 1, np.uint64)
+        in_off[1:] = np.cumsum([a.size for a in arrs])
+        blob = np.concatenate([a.reshape(-1) for a in arrs])
+        tiles = sum(picture_tiles(int(w), int(h)) for w, h in zip(width, height))
+        arena = np.empty(16 * n + tiles * (4 + OUT_STRIDE), np.uint8)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_enc_pictures(self.h, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n, quality,
+                                            arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-picture status {status.tolist()}")
+        return _split(arena, offs)
+
     def timing(self) -> Timing:
         t = Timing()
         self._chk(self.lib.nhw_enc_last_timing(self.h, ctypes.byref(t)))
@@ -525,6 +635,26 @@ class Decoder:
             self._chk(self.lib.nhw_dec_batch_device(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, out.data_ptr(), status.data_ptr(),
                                                     quality.data_ptr(), st))
         return out, status, quality
+
+    def decode_pictures(self, containers):
+        """containers: a list of .nhwp containers (bytes) -> a list of numpy uint8 [H, W, 3]: the tiles decoded in chunks of max_batch and
+        cropped on the device (nhw_dec_pictures).  Raises on a malformed container or a tile the decoder refuses."""
+        import numpy as np
+        n = len(containers)
+        if n < 1:
+            raise NhwError("decode_pictures wants a non-empty list of containers")
+        shapes = [picture_info(c) for c in containers]
+        offs = np.zeros(n + 1, np.uint64)
+        offs[1:] = np.cumsum([len(c) for c in containers])
+        blob = np.frombuffer(b"".join(bytes(c) for c in containers), np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        out_off[1:] = np.cumsum([3 * w * h for w, h in shapes])
+        out = np.empty(int(out_off[n]), np.uint8)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_dec_pictures(self.h, blob.ctypes.data, offs.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-container status {status.tolist()}")
+        return [out[int(out_off[i]):int(out_off[i + 1])].reshape(h, w, 3) for i, (w, h) in enumerate(shapes)]
 
     def decode(self, files):
         """files: list of .nhw byte strings -> (uint8 [n,512,512,3] in nhw-dec's output byte order, quality list)."""

@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <climits>
 #include <string>
 #include <vector>
 
@@ -49,6 +50,12 @@ void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const u
 void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *next, int *count, hipStream_t s);
 hipError_t nhw_launch_sse(const uint8_t *a, const uint8_t *b, int n, uint64_t *sse, hipStream_t s);
 void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after);
+
+/* pictures of any size (nhw_picture.hip) */
+hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s);
+hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s);
+size_t nhw_container_head(uint8_t *dst, uint32_t width, uint32_t height, const uint32_t *lens, int t);
+hipError_t nhw_grow(void **p, size_t *cap, size_t bytes);
 
 int nhw_front_set_attrs(const char **where);   /* nhw_front.hip, nhw_tail.hip: dynamic-LDS opt-ins of the device the handle lives on */
 int nhw_tail_set_attrs(const char **where);
@@ -105,6 +112,9 @@ struct nhw_enc {
 	hipEvent_t fit_ev[2];
 	nhw_fit_stats fit_stats;
 	bool fit_done;
+	/* nhw_enc_pictures: the uploaded pictures and their descriptor table, grow-only */
+	uint8_t *pic_px; size_t pic_cap;
+	nhw_picture *pic_desc; size_t pic_desc_cap;
 };
 
 static const size_t k_buf_bytes[B_COUNT] = {
@@ -265,6 +275,8 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	dev_free(host_set(e, 0));
 	dev_free(fit_set(e));
 	dev_free(fit_sse_set(e));
+	if (e->pic_px) (void)hipFree(e->pic_px);
+	if (e->pic_desc) (void)hipFree(e->pic_desc);
 	if (e->h_fit_count) (void)hipHostFree(e->h_fit_count);
 	for (int i = 0; i < 2; i++) if (e->fit_ev[i]) (void)hipEventDestroy(e->fit_ev[i]);
 	for (int i = 0; i < 7; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
@@ -638,6 +650,108 @@ extern "C" int nhw_enc_synth_batch(nhw_enc *e, int n, uint32_t seed_base, int qu
 	HIPCHK(hipGetLastError());
 	{ const int rc = nhw_enc_batch_device(e, e->d_in, n, quality, e->d_out, e->d_sizes, e->d_status, e->own_stream); if (rc) return rc; }
 	return host_download(e, n, out_arena, arena_cap, out_off, status);
+}
+
+/* ------------------------------------------------------------------------------------------------ pictures of any size */
+static int picture_args(const void *d_pics, int n_pics, int tile0, int m, const void *d_tiles, const char *who)
+{
+	if (!d_pics || !d_tiles || n_pics < 1 || m < 1 || tile0 < 0 || m > INT_MAX / 16 || tile0 > INT_MAX - m) { g_err = "bad argument"; return NHW_E_ARG; }
+	if ((uintptr_t)d_tiles & 15) { g_err = std::string(who) + ": d_tiles must be 16-byte aligned"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+extern "C" int nhw_tile_pictures_device(const nhw_picture *d_pics, int n_pics, int tile0, int m, void *d_tiles, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_tile_pictures_device")) return rc;
+	HIPCHK(nhw_launch_tile_pad(d_pics, n_pics, tile0, m, (uint8_t *)d_tiles, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_untile_pictures_device")) return rc;
+	HIPCHK(nhw_launch_untile_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, m, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* Upload the pictures (one copy of the span they lie in when they lie close together, as a packed host array does; else one copy each),
+ * pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch its files; then one
+ * container per picture. */
+extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { g_err = "bad argument"; return NHW_E_ARG; }
+	if (!nhw_quality_supported(quality)) { g_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	std::vector<nhw_picture> desc((size_t)n);
+	std::vector<int> first((size_t)n + 1);
+	uint64_t tiles = 0, bytes = 0, lo = UINT64_MAX, hi = 0;
+	for (int i = 0; i < n; i++) {
+		const int t = nhw_picture_tiles(width[i], height[i]);
+		if (t < 1) { g_err = "nhw_enc_pictures: a picture side outside 1..65535"; return NHW_E_ARG; }
+		const uint64_t sz = 3ull * width[i] * height[i];
+		desc[i] = { 0, 3ull * width[i], width[i], height[i], (uint32_t)tiles, 0 };
+		first[i] = (int)tiles;
+		tiles += (uint64_t)t; bytes += sz;
+		lo = in_off[i] < lo ? in_off[i] : lo;
+		hi = in_off[i] + sz > hi ? in_off[i] + sz : hi;
+		if (tiles > INT_MAX / 16) { g_err = "nhw_enc_pictures: too many tiles in one call"; return NHW_E_ARG; }
+	}
+	first[n] = (int)tiles;
+	HIPCHK(hipSetDevice(e->device));
+	const int chunk = (int)(tiles < (uint64_t)e->max_batch ? tiles : (uint64_t)e->max_batch);
+	{ const int rc = host_buffers(e, chunk); if (rc) return rc; }
+	const bool span = hi - lo <= bytes + bytes / 4 + (1u << 20);
+	HIPCHK(nhw_grow((void **)&e->pic_px, &e->pic_cap, span ? hi - lo : bytes));
+	HIPCHK(nhw_grow((void **)&e->pic_desc, &e->pic_desc_cap, (size_t)n * sizeof(nhw_picture)));
+	hipStream_t s = e->own_stream;
+	if (span) HIPCHK(hipMemcpyAsync(e->pic_px, bgr + lo, hi - lo, hipMemcpyHostToDevice, s));
+	for (uint64_t i = 0, at = 0; i < (uint64_t)n; i++) {
+		const uint64_t sz = 3ull * width[i] * height[i];
+		if (span) desc[i].addr = (uint64_t)(uintptr_t)(e->pic_px + (in_off[i] - lo));
+		else {
+			HIPCHK(hipMemcpyAsync(e->pic_px + at, bgr + in_off[i], sz, hipMemcpyHostToDevice, s));
+			desc[i].addr = (uint64_t)(uintptr_t)(e->pic_px + at);
+			at += sz;
+		}
+	}
+	HIPCHK(hipMemcpyAsync(e->pic_desc, desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
+	std::vector<uint8_t> files;
+	std::vector<uint32_t> lens((size_t)tiles);
+	std::vector<int32_t> tst((size_t)tiles);
+	std::vector<uint64_t> offs((size_t)chunk + 1);
+	for (int t0 = 0; t0 < (int)tiles; t0 += chunk) {
+		const int m = (int)tiles - t0 < chunk ? (int)tiles - t0 : chunk;
+		HIPCHK(nhw_launch_tile_pad(e->pic_desc, n, t0, m, e->d_in, s));
+		{ const int rc = nhw_enc_batch_device(e, e->d_in, m, quality, e->d_out, e->d_sizes, e->d_status, s); if (rc) return rc; }
+		k_offsets<<<1, 1, 0, s>>>(e->d_sizes, e->d_offs, m);
+		k_compact<<<m, 256, 0, s>>>(e->d_out, e->d_sizes, e->d_offs, e->d_compact);
+		HIPCHK(hipMemcpyAsync(offs.data(), e->d_offs, sizeof(uint64_t) * (m + 1), hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(tst.data() + t0, e->d_status, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+		const size_t used = files.size();
+		files.resize(used + offs[m]);
+		HIPCHK(hipMemcpy(files.data() + used, e->d_compact, offs[m], hipMemcpyDeviceToHost));
+		for (int k = 0; k < m; k++) lens[(size_t)t0 + k] = (uint32_t)(offs[k + 1] - offs[k]);
+	}
+	uint64_t at = 0, fpos = 0;
+	for (int i = 0; i < n; i++) {
+		const int t = first[i + 1] - first[i];
+		uint64_t sum = 0;
+		int32_t st = NHW_OK;
+		for (int k = first[i]; k < first[i + 1]; k++) { sum += lens[k]; if (st == NHW_OK) st = tst[k]; }
+		out_off[i] = at;
+		status[i] = st;
+		if (st == NHW_OK) {
+			const uint64_t size = 16 + 4 * (uint64_t)t + sum;
+			if (at + size > arena_cap) { g_err = "output arena too small"; return NHW_E_SPACE; }
+			const size_t head = nhw_container_head(out_arena + at, width[i], height[i], lens.data() + first[i], t);
+			memcpy(out_arena + at + head, files.data() + fpos, sum);
+			at += size;
+		}
+		fpos += sum;
+	}
+	out_off[n] = at;
+	return NHW_OK;
 }
 
 /* ------------------------------------------------------------------------------------------------ distortion */

@@ -25,7 +25,9 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <climits>
 #include <string>
+#include <vector>
 
 #include "../../include/nhw_hip.h"
 
@@ -2399,6 +2401,10 @@ struct nhw_dec {
 	/* host convenience path */
 	uint8_t *d_blob; size_t blob_cap;
 	uint64_t *d_off; uint32_t *d_len; uint8_t *d_out; int32_t *d_status; int32_t *d_quality;
+	/* nhw_dec_pictures: the cropped pictures, their descriptor table and the per-tile offsets, lengths and status, grow-only */
+	uint8_t *pic_px; size_t pic_cap;
+	void *pic_desc; size_t pic_desc_cap;
+	void *pic_tiles; size_t pic_tiles_cap;
 };
 
 extern "C" void nhw_dec_destroy(nhw_dec *d);
@@ -2448,6 +2454,9 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 	if (d->d_out) (void)hipFree(d->d_out);
 	if (d->d_status) (void)hipFree(d->d_status);
 	if (d->d_quality) (void)hipFree(d->d_quality);
+	if (d->pic_px) (void)hipFree(d->pic_px);
+	if (d->pic_desc) (void)hipFree(d->pic_desc);
+	if (d->pic_tiles) (void)hipFree(d->pic_tiles);
 	if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
 	if (d->chroma_stream) (void)hipStreamDestroy(d->chroma_stream);
 	if (d->vlc_table) (void)hipFree(d->vlc_table);
@@ -2578,12 +2587,10 @@ extern "C" int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t)
 	return NHW_OK;
 }
 
-/* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1]. */
-extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality)
+/* the host paths' buffers: the blob (grow-only, room for `total` bytes of files) and, on the first call, the per-file arrays and the
+ * decoded pictures of max_batch files */
+static int host_buffers(nhw_dec *d, size_t total)
 {
-	if (!d || !nhw || !off || !bgr || !status || n < 1 || n > d->max_batch) { g_derr = "bad argument"; return NHW_E_ARG; }
-	HIPCHK(hipSetDevice(d->device));
-	const size_t total = (size_t)(off[n] - off[0]);
 	if (total + 64 > d->blob_cap) {
 		if (d->d_blob) (void)hipFree(d->d_blob);
 		d->d_blob = nullptr; d->blob_cap = 0;                      /* nothing dangling if the allocation below fails */
@@ -2600,6 +2607,16 @@ extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off
 		d->d_off = (decltype(d->d_off))b[0]; d->d_len = (decltype(d->d_len))b[1]; d->d_out = (decltype(d->d_out))b[2];
 		d->d_status = (decltype(d->d_status))b[3]; d->d_quality = (decltype(d->d_quality))b[4];
 	}
+	return NHW_OK;
+}
+
+/* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1]. */
+extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality)
+{
+	if (!d || !nhw || !off || !bgr || !status || n < 1 || n > d->max_batch) { g_derr = "bad argument"; return NHW_E_ARG; }
+	HIPCHK(hipSetDevice(d->device));
+	const size_t total = (size_t)(off[n] - off[0]);
+	{ const int rc = host_buffers(d, total); if (rc) return rc; }
 	uint64_t *rel = (uint64_t *)malloc(((size_t)n + 1) * 12);
 	if (!rel) return NHW_E_ARG;
 	uint32_t *len = (uint32_t *)(rel + n + 1);
@@ -2620,6 +2637,83 @@ extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off
 	HIPCHK(hipMemcpyAsync(status, d->d_status, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
 	if (quality) HIPCHK(hipMemcpyAsync(quality, d->d_quality, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
 	HIPCHK(hipStreamSynchronize(d->own_stream));
+	return NHW_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------- pictures of any size */
+hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s);
+int nhw_container_parse(const uint8_t *c, size_t len, uint32_t *width, uint32_t *height, int *tiles, const uint8_t **dir);
+hipError_t nhw_grow(void **p, size_t *cap, size_t bytes);
+
+/* Parse every container on the host; upload the blob once (a container's tile files lie back to back, so the decoder's offsets and lengths
+ * come from its directory); decode the tiles in chunks of max_batch into the host path's picture slots and crop each chunk into the
+ * picture buffer (k_untile_crop); then bring back the pictures whose tiles all decoded. */
+extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+{
+	if (!d || !blob || !off || !bgr || !out_off || !status || n < 1) { g_derr = "bad argument"; return NHW_E_ARG; }
+	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { g_derr = "nhw_dec_pictures: off[] must not decrease"; return NHW_E_ARG; }
+	std::vector<nhw_picture> desc;
+	std::vector<int> which;                                      /* desc[k] is container which[k] */
+	std::vector<uint64_t> toff;
+	std::vector<uint32_t> tlen;
+	uint64_t bytes = 0;
+	for (int i = 0; i < n; i++) {
+		uint32_t w = 0, h = 0;
+		int t = 0;
+		const uint8_t *dir = nullptr;
+		status[i] = NHW_E_FORMAT;
+		if (nhw_container_parse(blob + off[i], (size_t)(off[i + 1] - off[i]), &w, &h, &t, &dir) != NHW_OK) continue;
+		if (toff.size() + (size_t)t > (size_t)(INT_MAX / 16)) { g_derr = "nhw_dec_pictures: too many tiles in one call"; return NHW_E_ARG; }
+		status[i] = NHW_OK;
+		desc.push_back({ bytes, 3ull * w, w, h, (uint32_t)toff.size(), 0 });
+		which.push_back(i);
+		uint64_t fo = off[i] - off[0] + 16 + 4 * (uint64_t)t;
+		for (int k = 0; k < t; k++) {
+			const uint32_t l = (uint32_t)dir[4 * k] | ((uint32_t)dir[4 * k + 1] << 8) | ((uint32_t)dir[4 * k + 2] << 16) | ((uint32_t)dir[4 * k + 3] << 24);
+			toff.push_back(fo); tlen.push_back(l); fo += l;
+		}
+		bytes += 3ull * w * h;
+	}
+	if (desc.empty()) return NHW_OK;
+	const int tiles = (int)toff.size(), np = (int)desc.size();
+	HIPCHK(hipSetDevice(d->device));
+	{ const int rc = host_buffers(d, (size_t)(off[n] - off[0])); if (rc) return rc; }
+	HIPCHK(nhw_grow((void **)&d->pic_px, &d->pic_cap, bytes));
+	HIPCHK(nhw_grow(&d->pic_desc, &d->pic_desc_cap, (size_t)np * sizeof(nhw_picture)));
+	HIPCHK(nhw_grow(&d->pic_tiles, &d->pic_tiles_cap, (size_t)tiles * 16));
+	for (nhw_picture &p : desc) p.addr += (uint64_t)(uintptr_t)d->pic_px;
+	uint64_t *d_toff = (uint64_t *)d->pic_tiles;
+	uint32_t *d_tlen = (uint32_t *)(d_toff + tiles);
+	int32_t *d_tst = (int32_t *)(d_tlen + tiles);
+	const nhw_picture *d_desc = (const nhw_picture *)d->pic_desc;
+	hipStream_t s = d->own_stream;
+	HIPCHK(hipMemcpyAsync(d->d_blob, blob + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d_toff, toff.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d_tlen, tlen.data(), (size_t)tiles * 4, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d->pic_desc, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
+	for (int t0 = 0; t0 < tiles; t0 += d->max_batch) {
+		const int m = tiles - t0 < d->max_batch ? tiles - t0 : d->max_batch;
+		const int rc = nhw_dec_batch_device(d, d->d_blob, d_toff + t0, d_tlen + t0, m, d->d_out, d_tst + t0, nullptr, s);
+		if (rc) return rc;
+		HIPCHK(nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, s));
+	}
+	std::vector<int32_t> tst((size_t)tiles);
+	HIPCHK(hipMemcpyAsync(tst.data(), d_tst, (size_t)tiles * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	for (int k = 0; k < np; k++) {
+		const int t1 = k + 1 < np ? (int)desc[k + 1].first_tile : tiles;
+		for (int t = (int)desc[k].first_tile; t < t1; t++) if (tst[t] != NHW_OK) { status[which[k]] = NHW_E_FORMAT; break; }
+	}
+	/* the pictures that decoded, in runs that are contiguous on both sides: one copy a run */
+	for (int k = 0; k < np;) {
+		if (status[which[k]] != NHW_OK) { k++; continue; }
+		const uint64_t dev0 = desc[k].addr, host0 = out_off[which[k]];
+		uint64_t len = 3ull * desc[k].width * desc[k].height;
+		int j = k + 1;
+		while (j < np && status[which[j]] == NHW_OK && out_off[which[j]] == host0 + len) { len += 3ull * desc[j].width * desc[j].height; j++; }
+		HIPCHK(hipMemcpy(bgr + host0, (const void *)(uintptr_t)dev0, len, hipMemcpyDeviceToHost));
+		k = j;
+	}
 	return NHW_OK;
 }
 

@@ -1,0 +1,247 @@
+/*
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles: the padding kernel k_tile_pad, its inverse
+ * k_untile_crop, and the .nhwp container that holds a picture's width, height and tile files.
+ *
+ * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
+ * ny = ceil(H / 512), by edge replication: padded pixel (r, c) = picture pixel (min(r, H - 1), min(c, W - 1)).  Tile (ty, tx) is padded
+ * rows 512 ty .. and columns 512 tx .., index ty nx + tx; a picture's tiles are numbered from its descriptor's first_tile on.
+ *
+ * Both kernels are copies: a workgroup moves one band of TP_ROWS rows of one tile.  The picture side may have any alignment and any
+ * pitch, so its bytes are reached through the naturally aligned dwords that hold them, funnelled together with v_alignbyte_b32 (fetch);
+ * the tile side is 16-byte aligned and moves in dwordx4.  No load touches a word that holds no byte of a picture row (or, for
+ * k_untile_crop, of the tile rows it reads), and no store touches a byte outside a picture row.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/nhw_hip.h"
+
+namespace {
+
+constexpr int TP_ROWS = 32;                 /* tile rows per workgroup */
+constexpr int TP_BANDS = 512 / TP_ROWS;     /* workgroups per tile */
+constexpr int TP_WORDS = 1536 / 16;         /* 16-byte words per tile row */
+constexpr int TP_THREADS = 256;
+
+/* Bytes [j, e) of the 16 bytes at address p, at their places in the result (the other bytes 0).  Loads only the naturally aligned dwords
+ * that hold one of those bytes (one dwordx4 when p is 16-byte aligned and all 16 are wanted), so it never reads a word the caller did not
+ * name a byte of. */
+__device__ __forceinline__ uint4 fetch(uintptr_t p, int j, int e)
+{
+	if (j == 0 && e == 16 && !(p & 15)) return *reinterpret_cast<const uint4 *>(p);
+	const uint32_t *a = reinterpret_cast<const uint32_t *>(p & ~(uintptr_t)3);
+	const int sh = (int)(p & 3), lo = sh + j, hi = sh + e;
+	uint32_t d[5];
+#pragma unroll
+	for (int q = 0; q < 5; q++) d[q] = (4 * q + 4 > lo && 4 * q < hi) ? a[q] : 0u;
+	return make_uint4(__builtin_amdgcn_alignbyte(d[1], d[0], sh), __builtin_amdgcn_alignbyte(d[2], d[1], sh),
+	                  __builtin_amdgcn_alignbyte(d[3], d[2], sh), __builtin_amdgcn_alignbyte(d[4], d[3], sh));
+}
+
+/* the picture holding global tile t: the last descriptor with first_tile <= t.  A wave probes 64 evenly spaced entries at a time, so a
+ * table of 65535 pictures takes three rounds of loads; the answer is the same in every lane. */
+__device__ __forceinline__ int find_picture(const nhw_picture *pics, int n, uint32_t t)
+{
+	int lo = 0, hi = n;
+	const int lane = threadIdx.x & 63;
+	while (hi - lo > 1) {
+		const int step = (hi - lo + 63) / 64, idx = lo + lane * step;
+		const bool le = idx < hi && pics[idx].first_tile <= t;
+		const int c = __popcll(__ballot(le));
+		lo += (c > 0 ? c - 1 : 0) * step;
+		hi = lo + step < hi ? lo + step : hi;
+	}
+	return __builtin_amdgcn_readfirstlane(lo);
+}
+
+struct TileRef {
+	nhw_picture p;
+	uint32_t ty, tx;
+};
+
+/* the workgroup's tile (tile0 + blockIdx.x / TP_BANDS) and its picture; false for a tile no picture of the table holds */
+__device__ __forceinline__ bool tile_of(const nhw_picture *pics, int n, int tile0, TileRef &r)
+{
+	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
+	r.p = pics[find_picture(pics, n, t)];
+	if (!r.p.width || !r.p.height || t < r.p.first_tile) return false;
+	const uint32_t nx = (r.p.width + 511) / 512, ny = (r.p.height + 511) / 512, in = t - r.p.first_tile;
+	if (in >= nx * ny) return false;
+	r.ty = in / nx; r.tx = in % nx;
+	return true;
+}
+
+/* padded word w of padded row rr of the tile: 16 bytes of picture row min(512 ty + rr, H - 1) from byte column 1536 tx + 16 w on.
+ * EDGE: the tile reaches column 3W, so a word may cross it or lie beyond it; those bytes repeat the row's last pixel (a 3-byte period). */
+template <bool EDGE>
+__device__ __forceinline__ uint4 pad_word(const TileRef &r, int rr, int w)
+{
+	const uint32_t row = 512 * r.ty + rr < r.p.height ? 512 * r.ty + rr : r.p.height - 1;
+	const uintptr_t R = (uintptr_t)(r.p.addr + (uint64_t)row * r.p.pitch);
+	const int rb = 3 * (int)r.p.width, b0 = 1536 * (int)r.tx + 16 * w, nin = rb - b0;
+	if (!EDGE || nin >= 16) return fetch(R + b0, 0, 16);
+	uint4 v = nin > 0 ? fetch(R + b0, 0, nin) : make_uint4(0, 0, 0, 0);
+	const uint32_t px = fetch(R + rb - 3, 0, 3).x;                     /* B, G, R of the last pixel */
+	const int r0 = b0 % 3;                                             /* padded column b0 + j holds component (r0 + j) % 3 */
+	uint32_t o[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+	for (int j = 0; j < 16; j++) {
+		int c = r0 + j % 3;
+		c -= c >= 3 ? 3 : 0;
+		const uint32_t byte = (px >> (8 * c)) & 0xFF, sh = 8 * (j & 3);
+		if (j >= nin) o[j >> 2] = (o[j >> 2] & ~(0xFFu << sh)) | (byte << sh);
+	}
+	return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <bool EDGE>
+__device__ __forceinline__ void pad_band(const TileRef &r, uint4 *__restrict__ dst, int band)
+{
+	constexpr int WORDS = TP_ROWS * TP_WORDS, PER = WORDS / TP_THREADS, GROUP = 4;
+	static_assert(WORDS % TP_THREADS == 0 && PER % GROUP == 0, "band layout");
+#pragma unroll
+	for (int g = 0; g < PER; g += GROUP) {
+		uint4 v[GROUP];
+#pragma unroll
+		for (int k = 0; k < GROUP; k++) {
+			const int i = (g + k) * TP_THREADS + threadIdx.x;
+			v[k] = pad_word<EDGE>(r, band * TP_ROWS + i / TP_WORDS, i % TP_WORDS);
+		}
+#pragma unroll
+		for (int k = 0; k < GROUP; k++) dst[(g + k) * TP_THREADS + threadIdx.x] = v[k];
+	}
+}
+
+__global__ __launch_bounds__(TP_THREADS) void k_tile_pad(const nhw_picture *__restrict__ pics, int n_pics, int tile0, uint8_t *__restrict__ tiles)
+{
+	TileRef r;
+	if (!tile_of(pics, n_pics, tile0, r)) return;
+	const int band = blockIdx.x % TP_BANDS;
+	uint4 *dst = reinterpret_cast<uint4 *>(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES) + band * TP_ROWS * TP_WORDS;
+	if (1536 * (r.tx + 1) <= 3 * r.p.width) pad_band<false>(r, dst, band);   /* an interior tile column: never the replication path */
+	else pad_band<true>(r, dst, band);
+}
+
+/* the bytes [j, e) of v to the 16-byte-aligned destination word A, each store inside them: dwords where a whole one is covered, else
+ * shorts and bytes (never a read-modify-write: the neighbouring bytes may be another row's, another thread's) */
+__device__ __forceinline__ void store_part(uint8_t *A, uint4 v, int j, int e)
+{
+	const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+	for (int s = 0; s < 4; s++) {
+		const int b = 4 * s;
+		if (j <= b && b + 4 <= e) { *reinterpret_cast<uint32_t *>(A + b) = w[s]; continue; }
+#pragma unroll
+		for (int h = 0; h < 2; h++) {
+			const int c = b + 2 * h;
+			const bool c0 = j <= c && c < e, c1 = j <= c + 1 && c + 1 < e;
+			if (c0 && c1) *reinterpret_cast<uint16_t *>(A + c) = (uint16_t)(w[s] >> (16 * h));
+			else if (c0) A[c] = (uint8_t)(w[s] >> (16 * h));
+			else if (c1) A[c + 1] = (uint8_t)(w[s] >> (16 * h + 8));
+		}
+	}
+}
+
+/* the inverse: tile row rr (a picture row r = 512 ty + rr < H) holds picture bytes [1536 tx, min(1536 tx + 1536, 3W)) of row r.  They go
+ * out as the 16-byte-aligned destination words that cover them (at most 97 a row): whole words as dwordx4, the ragged head and tail with
+ * store_part.  The source side reads the tile row through fetch, only the bytes it stores. */
+__global__ __launch_bounds__(TP_THREADS) void k_untile_crop(const uint8_t *__restrict__ tiles, const nhw_picture *__restrict__ pics, int n_pics, int tile0)
+{
+	TileRef r;
+	if (!tile_of(pics, n_pics, tile0, r)) return;
+	const int band = blockIdx.x % TP_BANDS;
+	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES);
+	const int rb = 3 * (int)r.p.width, s0 = 1536 * (int)r.tx, seg = rb - s0 < 1536 ? rb - s0 : 1536;
+	constexpr int SLOTS = TP_WORDS + 1;
+	for (int i = threadIdx.x; i < TP_ROWS * SLOTS; i += TP_THREADS) {
+		const int rr = band * TP_ROWS + i / SLOTS, k = i % SLOTS;
+		const uint32_t row = 512 * r.ty + rr;
+		if (row >= r.p.height) break;                                 /* (rows only grow with i) */
+		const uintptr_t D0 = (uintptr_t)(r.p.addr + (uint64_t)row * r.p.pitch) + s0, D1 = D0 + seg;
+		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
+		if (A >= D1) continue;
+		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
+		const uint4 v = fetch(src + (uintptr_t)rr * 1536 + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
+		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
+		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
+	}
+}
+
+} /* namespace */
+
+hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
+{
+	k_tile_pad<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_pics, n_pics, tile0, d_tiles);
+	return hipGetLastError();
+}
+
+hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s)
+{
+	k_untile_crop<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	return hipGetLastError();
+}
+
+/* the host paths' grow-only device buffers (nhw_enc_pictures, nhw_dec_pictures): *p holds at least `bytes` afterwards, its old contents
+ * not kept; on a failed allocation *p is NULL and *cap 0 */
+hipError_t nhw_grow(void **p, size_t *cap, size_t bytes)
+{
+	if (*cap >= bytes) return hipSuccess;
+	if (*p) (void)hipFree(*p);
+	*p = nullptr; *cap = 0;
+	const hipError_t err = hipMalloc(p, bytes);
+	if (err == hipSuccess) *cap = bytes;
+	else *p = nullptr;
+	return err;
+}
+
+/* ------------------------------------------------------------------------------------------------ the .nhwp container (host) */
+static uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+static void wr32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+
+extern "C" int nhw_picture_tiles(uint32_t width, uint32_t height)
+{
+	if (width < 1 || width > 65535 || height < 1 || height > 65535) return NHW_E_ARG;
+	return (int)(((width + 511) / 512) * ((height + 511) / 512));
+}
+
+/* A well-formed container: magic, version 1, zero reserved bytes, W and H in 1..65535, T = nhw_picture_tiles(W, H) lengths of 1 ..
+ * NHW_OUT_STRIDE each, and exactly 16 + 4 T + the sum of them bytes.  Returns NHW_OK with W, H, T and a pointer to the directory. */
+int nhw_container_parse(const uint8_t *c, size_t len, uint32_t *width, uint32_t *height, int *tiles, const uint8_t **dir)
+{
+	if (!c || len < 16 || memcmp(c, "NHWP", 4) || c[4] != 1 || c[5] || c[6] || c[7]) return NHW_E_FORMAT;
+	const uint32_t w = rd32(c + 8), h = rd32(c + 12);
+	const int t = nhw_picture_tiles(w, h);
+	if (t < 1 || (len - 16) / 4 < (size_t)t) return NHW_E_FORMAT;
+	uint64_t total = 16 + 4 * (uint64_t)t;
+	for (int i = 0; i < t; i++) {
+		const uint32_t l = rd32(c + 16 + 4 * (size_t)i);
+		if (l < 1 || l > NHW_OUT_STRIDE) return NHW_E_FORMAT;
+		total += l;
+	}
+	if (total != len) return NHW_E_FORMAT;
+	*width = w; *height = h; *tiles = t; *dir = c + 16;
+	return NHW_OK;
+}
+
+/* header and directory of a container for a W x H picture whose T tile files have the lengths lens[]; returns 16 + 4 T (the files go
+ * behind, back to back) */
+size_t nhw_container_head(uint8_t *dst, uint32_t width, uint32_t height, const uint32_t *lens, int t)
+{
+	memcpy(dst, "NHWP\1\0\0\0", 8);
+	wr32(dst + 8, width); wr32(dst + 12, height);
+	for (int i = 0; i < t; i++) wr32(dst + 16 + 4 * (size_t)i, lens[i]);
+	return 16 + 4 * (size_t)t;
+}
+
+extern "C" int nhw_picture_info(const uint8_t *container, size_t len, uint32_t *width, uint32_t *height)
+{
+	uint32_t w = 0, h = 0;
+	int t = 0;
+	const uint8_t *dir = nullptr;
+	const int rc = nhw_container_parse(container, len, &w, &h, &t, &dir);
+	if (rc != NHW_OK) return rc;
+	if (width) *width = w;
+	if (height) *height = h;
+	return NHW_OK;
+}

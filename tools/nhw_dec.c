@@ -6,7 +6,8 @@
  * The BMP is the 54-byte header of decoder/nhw_decoder_cli.c:61-65,293-312 followed by the pixel bytes in the order
  * write_image_bmp (:108-291) writes them.  Exit codes: 0 ok, 1 cannot read / write a file (the reference prints and
  * carries on into undefined behaviour), 3 not an .nhw file (reference: "Not an .nhw file", exit(-1)).
- * Extension: --batch <dir> decodes every *.nhw of a directory to <name>.bmp in one GPU batch.
+ * Extension: --batch <dir> decodes every *.nhw of a directory to <name>.bmp in one GPU batch; --picture <in.nhwp> <out.bmp> decodes a
+ * container of nhw-enc --picture to a bottom-up 24-bit BMP of the picture's own size.
  */
 #include <dirent.h>
 #include <stdint.h>
@@ -28,7 +29,8 @@ static void show_usage(void)
 	"  example: nhw-dec image.nhw image.bmp\n"
 	"  batch:   nhw-dec --batch <directory of .nhw files>\n"
 	"  tiles:   nhw-dec --tiles <rows> <columns> <stem> <image.bmp>   (joins <stem>_y<r>_x<c>.nhw, as written by nhw-enc --tiles)\n"
-	"  tar:     nhw-dec --tar <in.tar> <out.tar>   (every x.nhw member of a ustar archive -> member x.bmp, in order)\n",
+	"  tar:     nhw-dec --tar <in.tar> <out.tar>   (every x.nhw member of a ustar archive -> member x.bmp, in order)\n"
+	"  picture: nhw-dec --picture <in.nhwp> <image.bmp>   (a container of nhw-enc --picture, any size)\n",
 	PROGRAM);
 }
 
@@ -140,6 +142,55 @@ static int decode_tiles(int ny, int nx, const char *stem, const char *out_path)
 	return 0;
 }
 
+/* --picture: the inverse of nhw-enc --picture.  The container's tiles are decoded and cropped by the library (nhw_dec_pictures); the
+ * rows go out under the reference's 54-byte header with the size fields of the picture, each padded to 4 bytes. */
+static int decode_picture(const char *in_path, const char *out_path)
+{
+	uint8_t *blob = NULL, *pix, hdr[54], pad[3] = { 0, 0, 0 };
+	size_t len = 0;
+	uint32_t width = 0, height = 0, row, stride, bytes, r;
+	uint64_t off[2], out_off[1] = { 0 };
+	int32_t status = 0;
+	nhw_dec *d = NULL;
+	int t;
+	FILE *f;
+	if (read_file(in_path, &blob, &len)) return 1;
+	if (nhw_picture_info(blob, len, &width, &height) != NHW_OK) { printf("\nNot an .nhwp file\n"); free(blob); return 3; }
+	row = width * 3; stride = (row + 3) & ~3u;
+	if ((uint64_t)stride * height + 54u > 0xFFFFFFFFull) {           /* the BMP header's 32-bit size fields */
+		fprintf(stderr, "%s: a %u x %u picture does not fit a BMP file (4 GiB)\n", PROGRAM, (unsigned)width, (unsigned)height);
+		free(blob);
+		return 1;
+	}
+	bytes = stride * height;
+	t = nhw_picture_tiles(width, height);
+	pix = (uint8_t *)malloc((size_t)row * height);
+	off[0] = 0; off[1] = len;
+	if (!pix || nhw_dec_create(0, t < 1024 ? t : 1024, &d) || nhw_dec_pictures(d, blob, off, 1, pix, out_off, &status)) {
+		fprintf(stderr, "%s: GPU decoder unavailable: %s\n", PROGRAM, nhw_dec_last_error());
+		return 2;
+	}
+	nhw_dec_destroy(d);
+	free(blob);
+	if (status) { printf("\nNot an .nhwp file\n"); free(pix); return 3; }
+	nhw_dec_bmp_header(hdr);                                          /* the reference's 54 bytes, with the size fields of the picture */
+	hdr[2] = (uint8_t)(bytes + 54); hdr[3] = (uint8_t)((bytes + 54) >> 8); hdr[4] = (uint8_t)((bytes + 54) >> 16); hdr[5] = (uint8_t)((bytes + 54) >> 24);
+	hdr[18] = (uint8_t)width; hdr[19] = (uint8_t)(width >> 8); hdr[20] = (uint8_t)(width >> 16); hdr[21] = (uint8_t)(width >> 24);
+	hdr[22] = (uint8_t)height; hdr[23] = (uint8_t)(height >> 8); hdr[24] = (uint8_t)(height >> 16); hdr[25] = (uint8_t)(height >> 24);
+	hdr[34] = (uint8_t)bytes; hdr[35] = (uint8_t)(bytes >> 8); hdr[36] = (uint8_t)(bytes >> 16); hdr[37] = (uint8_t)(bytes >> 24);
+	f = fopen(out_path, "wb");
+	if (!f) { printf("Failed to open output decompressed .bmp file %s\n", out_path); free(pix); return 1; }
+	fwrite(hdr, 54, 1, f);
+	for (r = 0; r < height; r++) {
+		fwrite(pix + (size_t)r * row, 1, row, f);
+		fwrite(pad, 1, stride - row, f);
+	}
+	fclose(f);
+	free(pix);
+	printf("%u x %u picture\n", (unsigned)width, (unsigned)height);
+	return 0;
+}
+
 /* --tar: the inverse of nhw-enc --tar; members are decoded in batches of up to 1024 */
 static unsigned long tar_octal(const uint8_t *p, int n) { unsigned long v = 0; int i; for (i = 0; i < n && p[i] >= '0' && p[i] <= '7'; i++) v = v * 8 + (unsigned long)(p[i] - '0'); return v; }
 static int tar_write_member(FILE *f, const char *name, const uint8_t *head, size_t head_len, const uint8_t *data, size_t len)
@@ -241,6 +292,10 @@ int main(int argc, char **argv)
 	if (!strcmp(argv[1], "--tar")) {
 		if (argc < 4) { show_usage(); return 1; }
 		return decode_tar(argv[2], argv[3]);
+	}
+	if (!strcmp(argv[1], "--picture")) {
+		if (argc < 4) { show_usage(); return 1; }
+		return decode_picture(argv[2], argv[3]);
 	}
 	if (!strcmp(argv[1], "--tiles")) {
 		int ny, nx;

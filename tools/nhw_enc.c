@@ -17,6 +17,8 @@
  *   --min-psnr DB [--min-quality M]   (single file, --batch, --tiles) every image at the lowest quality from M (default 1) up to -q whose
  *                    decoded picture reaches DB dB of PSNR (nhw_enc_fit_sse_batch); an image that reaches it at no quality is reported
  *                    and not written
+ *   --picture <in.bmp> <out.nhwp>   any 24-bit BMP (W, H >= 1): padded to whole 512 x 512 tiles on the device, one .nhwp container
+ *                    (nhw_enc_pictures); alone, not with --max-bytes, --min-psnr, --synthetic, --tar, --tiles or --batch
  * --gpus G: images are independent (encoder/nhw_encoder_cli.c:175-183 is a per-image sequence), so the job is a queue of chunks of up
  * to 1024 images; one host thread per GPU, each with its own encoder handle, takes the next chunk until the queue is empty.  The work
  * descriptor {first image, count, quality, seed} lives in this process; between processes (one per GPU under torchrun) it travels by
@@ -56,8 +58,9 @@ static void usage(void)
 	        "Tiles (MI355X build): %s [-q#] --tiles <big.bmp> <stem>   (width, height multiples of 512: one <stem>_y<r>_x<c>.nhw per 512x512 tile)\n"
 	        "Tar   (MI355X build): %s [-q#] --tar <in.tar> <out.tar>    (every x.bmp member of a ustar archive -> member x.nhw, in order)\n"
 	        "Budget (MI355X build): %s [-q#] --max-bytes <n> [--min-quality <m>] ...   (single file, --batch, --tiles: the highest quality from -q# down to m whose file fits n bytes)\n"
-	        "PSNR (MI355X build): %s [-q#] --min-psnr <dB> [--min-quality <m>] ...   (single file, --batch, --tiles: the lowest quality from m up to -q# whose decoded picture reaches dB)\n",
-	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
+	        "PSNR (MI355X build): %s [-q#] --min-psnr <dB> [--min-quality <m>] ...   (single file, --batch, --tiles: the lowest quality from m up to -q# whose decoded picture reaches dB)\n"
+	        "Picture (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp>   (any size: padded 512x512 tiles and the real size in one container)\n",
+	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
 }
 
 static void version(void)
@@ -163,6 +166,68 @@ static uint8_t *load_bmp_tiles(const char *path, int *ny, int *nx)
 	free(row);
 	fclose(f);
 	return tiles;
+}
+
+/* --picture: any 24-bit uncompressed BMP (W, H >= 1) as W x H x 3 bytes in file row order (rows are padded to 4 bytes in the file; a
+ * top-down file is flipped as a whole first, as load_bmp_tiles does; a short file leaves the rest zero).  Returns the pixels (malloc). */
+static uint8_t *load_bmp_picture(const char *path, uint32_t *w, uint32_t *h)
+{
+	FILE *f = fopen(path, "rb");
+	uint8_t h34[34], *px;
+	int bih, width, height, planes, bpp, compr, flipped, r;
+	long off;
+	size_t row, stride;
+	if (!f) { printf("menu(): Could not open file: %s\n", path); exit(-1); }
+	if (fread(h34, 1, sizeof h34, f) < sizeof h34) { printf("invalid image file.\n"); exit(HDR_NO_DATA); }
+	if (h34[0] != 'B' || h34[1] != 'M') { printf("invalid image file.\n"); exit(HDR_NO_SIG); }
+	off = (long)(int)le32(h34 + 10);
+	bih = (int)le32(h34 + 14);
+	if (bih != 40 && bih != 52 && bih != 56 && bih != 108 && bih != 124) { printf("invalid image file.\n"); exit(HDR_BIH); }
+	width = (int)le32(h34 + 18); height = (int)le32(h34 + 22); planes = (short)le16(h34 + 26); bpp = (short)le16(h34 + 28); compr = (int)le32(h34 + 30);
+	if (planes != 1) { printf("invalid image file.\n"); exit(HDR_PLANES); }
+	flipped = height < 0;
+	if (flipped) height = -height;
+	if (width < 1 || width > 65535 || height < 1 || height > 65535 || bpp != 24 || compr != 0) {
+		printf("invalid image file.\n");
+		fprintf(stderr, "%s: --picture wants a 24-bit uncompressed BMP with sides 1..65535 (got %dx%d, %d bpp)\n", PROGRAM, width, height, bpp);
+		exit(HDR_FORMAT);
+	}
+	if (fseek(f, off, SEEK_SET) != 0) { printf("unable to seek to actual data.\n"); exit(-2); }
+	row = (size_t)width * 3; stride = (row + 3) & ~(size_t)3;
+	px = (uint8_t *)calloc((size_t)height, row);
+	if (!px) { fprintf(stderr, "%s: out of memory for a %dx%d picture\n", PROGRAM, width, height); exit(-1); }
+	for (r = 0; r < height; r++) {
+		const int fr = flipped ? height - 1 - r : r;                  /* row of the picture as the encoder sees it */
+		if (fread(px + (size_t)fr * row, 1, row, f) < row) break;      /* short file: the rest stays zero */
+		if (stride > row && fseek(f, (long)(stride - row), SEEK_CUR) != 0) break;
+	}
+	fclose(f);
+	*w = (uint32_t)width; *h = (uint32_t)height;
+	return px;
+}
+
+static int encode_picture(const char *in_path, const char *out_path, int quality, int stock_compat)
+{
+	uint32_t w = 0, h = 0;
+	uint8_t *px = load_bmp_picture(in_path, &w, &h), *arena;
+	const int t = nhw_picture_tiles(w, h);
+	const size_t cap = 16 + (size_t)t * (4 + NHW_OUT_STRIDE);
+	uint64_t in_off[2] = { 0, 3ull * w * h }, off[2];
+	int32_t st = 0;
+	nhw_enc *enc = NULL;
+	int rc;
+	if ((rc = nhw_enc_create(0, t < 1024 ? t : 1024, &enc))) die_lib("nhw_enc_create", rc);   /* (the batch modes' chunk) */
+	if (stock_compat) nhw_enc_set_compat(enc, NHW_COMPAT_GLIBC_ONESHOT);
+	arena = (uint8_t *)malloc(cap);
+	if (!arena) { fprintf(stderr, "%s: out of memory\n", PROGRAM); exit(-1); }
+	if ((rc = nhw_enc_pictures(enc, px, in_off, &w, &h, 1, quality, arena, cap, off, &st))) die_lib("nhw_enc_pictures", rc);
+	nhw_enc_destroy(enc);
+	free(px);
+	if (st) { fprintf(stderr, "%s: %s: encoder status %d (code book overflow)\n", PROGRAM, in_path, st); free(arena); return 1; }
+	rc = write_file(out_path, arena + off[0], (size_t)(off[1] - off[0])) ? 1 : 0;
+	if (!rc) printf("%u x %u picture, %d tile(s)\n", (unsigned)w, (unsigned)h, t);
+	free(arena);
+	return rc;
 }
 
 /* --max-bytes: the byte budget of every image (0: off) and the ladder, -q down to --min-quality;
@@ -442,7 +507,7 @@ int main(int argc, char **argv)
 	int devlist[16], ndevlist = 0;
 	uint32_t seed = 0;
 	const char *batch_dir = NULL, *outdir = NULL;
-	int tiles = 0, tar = 0;
+	int tiles = 0, tar = 0, picture = 0;
 	int stock_compat = 0;   /* --stock-compat: NHW_COMPAT_GLIBC_ONESHOT, the stock binary's out-of-bounds reads (include/nhw_hip.h) */
 	const char *max_bytes_arg = NULL, *min_quality_arg = NULL;   /* --max-bytes, --min-quality, --min-psnr: checked once the flags are read */
 	const char *min_psnr_arg = NULL;
@@ -482,6 +547,7 @@ int main(int argc, char **argv)
 		if (!strcmp(argv[1], "--stock-compat")) { stock_compat = 1; argc -= 1; argv += 1; continue; }
 		if (!strcmp(argv[1], "--tiles")) { tiles = 1; argc -= 1; argv += 1; continue; }
 		if (!strcmp(argv[1], "--tar")) { tar = 1; argc -= 1; argv += 1; continue; }
+		if (!strcmp(argv[1], "--picture")) { picture = 1; argc -= 1; argv += 1; continue; }
 		for (i = 1; argv[1][i] != '\0'; i++) {
 			const char ch = argv[1][i];
 			if (ch >= '0' && ch <= '9') continue;
@@ -504,6 +570,10 @@ int main(int argc, char **argv)
 	if (!nhw_quality_supported(quality)) {
 		fprintf(stderr, "%s: quality %d is not implemented (supported: 1..23; the reference accepts -q0 but has no tables for it)\n", PROGRAM, quality);
 		return 3;
+	}
+	if (picture && (max_bytes_arg || min_psnr_arg || min_quality_arg || synthetic > 0 || tar || tiles || batch_dir)) {   /* before any GPU work */
+		fprintf(stderr, "%s: --picture works alone, not with --max-bytes, --min-psnr, --min-quality, --synthetic, --tar, --tiles or --batch\n", PROGRAM);
+		return 1;
 	}
 	if (max_bytes_arg || min_quality_arg || min_psnr_arg) {          /* before any GPU work */
 		char *end;
@@ -577,6 +647,7 @@ int main(int argc, char **argv)
 
 	if (argc < 3) { printf("Not enough arguments. Check help.\n"); usage(); return 0; }
 	if (tar) return encode_tar(argv[1], argv[2], quality, stock_compat);
+	if (picture) return encode_picture(argv[1], argv[2], quality, stock_compat);
 	if (tiles) {
 		int ny = 0, nx = 0, n, bad, t;
 		uint8_t *imgs = load_bmp_tiles(argv[1], &ny, &nx);
