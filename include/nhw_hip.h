@@ -188,6 +188,36 @@ int nhw_picture_info(const uint8_t *container, size_t len, uint32_t *width, uint
 int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
                      int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status);
 
+/* ---- pictures of any size to a byte budget or a PSNR target ----
+ * The error of decoded tiles against the pictures' own bytes: adds to d_sse[k] the SSE between the decoded tiles [tile0, tile0 + m)
+ * (d_tiles, tile t at (t - tile0) * NHW_IMG_BYTES, 16-byte aligned) and the bytes of picture k of d_pics that those tiles cover: tile row
+ * rr of tile (ty, tx) against picture row 512 ty + rr < H, bytes [1536 tx, min(1536 tx + 1536, 3W)).  Padding never counts.  Accumulates
+ * (the caller zeroes d_sse), so chunked calls add up; exact, independent of scheduling; asynchronous and capturable.  NHW_E_ARG as for
+ * nhw_untile_pictures_device, and for a d_sse not 8-byte aligned.  PSNR of a picture = 10 log10(65025 * 3 W H / SSE). */
+int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, void *stream);
+/* Host conveniences, synchronous; inputs and outputs as for nhw_enc_pictures, plus the ladder (as for nhw_enc_fit_batch /
+ * nhw_enc_fit_sse_batch: NULL with ladder_len 0 = 23, 22, ..., 1 for bytes, 1, 2, ..., 23 for SSE), the limits (host arrays of n) and
+ * quality (n), sse (n).  All tiles of a picture get ONE quality.  Picture i's result is the container of the FIRST rung whose test it
+ * passes, byte-identical to what nhw_enc_pictures writes for it at that quality:
+ *   bytes: every tile encodes NHW_OK and the container (16 + 4 T + the sum of the tile lengths) is at most max_bytes[i] bytes;
+ *   SSE:   every tile encodes NHW_OK, every tile decodes NHW_OK by d, and the SSE over the picture's own 3 W H bytes (the decoded tiles
+ *          cropped, against the input: what a user measures between nhw_dec_pictures(container) and the input) is at most max_sse[i].
+ * Size and PSNR are not monotonic in quality: the walk goes rung by rung and skips none; a picture closes at its first passing rung and
+ * later rungs encode only the tiles of the pictures still open.  If no rung passes, the picture gets the last rung's container, quality and
+ * SSE with status NHW_E_BUDGET -- NHW_E_CODEBOOK, an empty container and SSE UINT64_MAX if a tile of that rung overflowed the code book,
+ * NHW_E_FORMAT (SSE UINT64_MAX) if the decoder refused one of its tiles.
+ * Refused before anything is launched: a bad ladder NHW_E_QUALITY; NULL pointers, n < 1, a side outside 1..65535, a debug stop on either
+ * handle, a decoder on another device or with a max_batch below min(e's max_batch, the call's tiles) NHW_E_ARG.  NHW_E_SPACE if arena_cap
+ * is short.  After a call nhw_enc_last_fit_stats gives rungs and quality[r] as for the image searches, images[r] = the number of TILES
+ * encoded at rung r, and total_ms from the upload of the pictures to the end of the last rung.  The SSE search allocates (grow-only) a
+ * decoded tile for each of min(max_batch, tiles) tiles, not the image searches' buffers. */
+int nhw_enc_fit_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                         const uint64_t *max_bytes, const int *ladder, int ladder_len,
+                         uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality);
+int nhw_enc_fit_sse_pictures(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height,
+                             int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
+                             uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse);
+
 /* ---- stage-level entry points (kernel parity tests; same stream rules) ----
  * colour + 4:2:0 (colorspace.c:55-260), any quality 1..23: d_y n*262144 int16, d_u/d_v n*65536 uint8 */
 int nhw_stage_color(nhw_enc *e, const void *d_bgr, int n, int quality, void *d_y, void *d_u, void *d_v, void *stream);

@@ -74,6 +74,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_picture_info.argtypes = [P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.nhw_enc_pictures.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t, P, P]
     L.nhw_dec_pictures.argtypes = [P, P, P, ctypes.c_int, P, P, P]
+    L.nhw_sse_pictures_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]
+    L.nhw_enc_fit_pictures.argtypes = [P, P, P, P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P]
+    L.nhw_enc_fit_sse_pictures.argtypes = [P, P, P, P, P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P, P]
     return L
 
 
@@ -171,19 +174,59 @@ def tile_pictures_device(pictures):
     return out
 
 
+def _picture_tiles_arg(tiles, pictures, what):
+    """the checked table of `pictures` (as for tile_pictures_device) and `tiles`, a contiguous uint8 tensor of all their tiles on their device"""
+    import torch
+    table, n_tiles, dev = _picture_table(pictures, what)
+    if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.device == dev and tiles.dtype == torch.uint8 and tiles.is_contiguous()
+            and tiles.numel() == n_tiles * IMG_BYTES):
+        raise NhwError(f"{what}: `tiles` must be a contiguous uint8 tensor [{n_tiles}, 512, 512, 3] on {dev}")
+    return table, n_tiles, dev
+
+
 def untile_pictures_device(tiles, pictures):
     """The inverse of tile_pictures_device (k_untile_crop): decoded tiles uint8 [T, 512, 512, 3] (e.g. Decoder.decode_device's pixels) into
     the preallocated pictures (as for tile_pictures_device); only the pictures' own bytes are written.  Ordered on torch's current stream."""
     import torch
-    table, n_tiles, dev = _picture_table(pictures, "untile_pictures_device")
-    if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.device == dev and tiles.dtype == torch.uint8 and tiles.is_contiguous()
-            and tiles.numel() == n_tiles * IMG_BYTES):
-        raise NhwError(f"untile_pictures_device: `tiles` must be a contiguous uint8 tensor [{n_tiles}, 512, 512, 3] on {dev}")
+    table, n_tiles, dev = _picture_tiles_arg(tiles, pictures, "untile_pictures_device")
     L = _library()
     with torch.cuda.device(dev):
         rc = L.nhw_untile_pictures_device(tiles.data_ptr(), table.data_ptr(), len(pictures), 0, n_tiles, torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+
+
+def sse_pictures_device(tiles, pictures):
+    """The exact SSE of decoded tiles against the pictures' own bytes (k_sse_crop, nhw_sse_pictures_device): tiles and pictures as for
+    untile_pictures_device -> int64 tensor [n] on their device, zeroed and filled on torch's current stream.  The padding never counts:
+    entry k equals the SSE between untile_pictures_device(tiles) and picture k."""
+    import torch
+    table, n_tiles, dev = _picture_tiles_arg(tiles, pictures, "sse_pictures_device")
+    out = torch.zeros(len(pictures), dtype=torch.int64, device=dev)
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_sse_pictures_device(tiles.data_ptr(), table.data_ptr(), len(pictures), 0, n_tiles, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
+
+
+def picture_psnr_to_max_sse(db, width, height):
+    """psnr_to_max_sse for a width x height picture: the largest SSE over its 3 W H bytes whose PSNR is at least `db`,
+    floor(65025 * 3 W H * 10**(-db/10)) in float64 (exact: 65025 * 3 * 65535**2 < 2**53), for finite db > 0 and sides 1..65535.
+    A number gives an int, an array (or list) of them an int64 numpy array.  For 512 x 512 it is psnr_to_max_sse(db)."""
+    import numpy as np
+    try:
+        a = np.asarray(db, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise NhwError(f"a PSNR target must be a finite number of dB above 0, got {db!r}") from None
+    if a.size == 0 or not np.all(np.isfinite(a)) or not np.all(a > 0):
+        raise NhwError(f"a PSNR target must be a finite number of dB above 0, got {db!r}")
+    if not (isinstance(width, numbers.Integral) and isinstance(height, numbers.Integral)):
+        raise NhwError(f"a picture's sides must be integers, got {width!r} x {height!r}")
+    picture_tiles(int(width), int(height))
+    m = np.floor(float(65025 * 3 * int(width) * int(height)) * np.power(10.0, -a / 10.0)).astype(np.int64)
+    return int(m) if m.ndim == 0 else m
 
 
 def picture_info(container) -> tuple:
@@ -438,17 +481,16 @@ class Encoder:
         tiles, shape = tile_images(big)
         return self.encode(tiles, quality), shape
 
-    def encode_pictures(self, pictures, quality: int = QUALITY_DEFAULT):
-        """pictures: a list of numpy uint8 [H, W, 3] (BMP file row order, sides 1..65535) -> a list of .nhwp containers (bytes): every
-        picture padded to whole tiles on the device, the tiles encoded in chunks of max_batch (nhw_enc_pictures).  Raises on a per-picture
-        failure, like encode."""
+    @staticmethod
+    def _host_pictures(pictures, what):
+        """a list of numpy uint8 [H, W, 3] -> (n, packed blob, in_off, width, height, tiles, an output arena that holds every container)"""
         import numpy as np
         if not isinstance(pictures, (list, tuple)) or not pictures:
-            raise NhwError("encode_pictures wants a non-empty list of uint8 [H, W, 3] arrays")
+            raise NhwError(f"{what} wants a non-empty list of uint8 [H, W, 3] arrays")
         arrs = [np.ascontiguousarray(p) for p in pictures]
         for i, a in enumerate(arrs):
             if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise NhwError(f"encode_pictures: picture {i} is not uint8 [H, W, 3], got {a.dtype} {a.shape}")
+                raise NhwError(f"{what}: picture {i} is not uint8 [H, W, 3], got {a.dtype} {a.shape}")
             picture_tiles(a.shape[1], a.shape[0])
         n = len(arrs)
         width = np.array([a.shape[1] for a in arrs], np.uint32)
@@ -458,6 +500,14 @@ class Encoder:
         blob = np.concatenate([a.reshape(-1) for a in arrs])
         tiles = sum(picture_tiles(int(w), int(h)) for w, h in zip(width, height))
         arena = np.empty(16 * n + tiles * (4 + OUT_STRIDE), np.uint8)
+        return n, blob, in_off, width, height, tiles, arena
+
+    def encode_pictures(self, pictures, quality: int = QUALITY_DEFAULT):
+        """pictures: a list of numpy uint8 [H, W, 3] (BMP file row order, sides 1..65535) -> a list of .nhwp containers (bytes): every
+        picture padded to whole tiles on the device, the tiles encoded in chunks of max_batch (nhw_enc_pictures).  Raises on a per-picture
+        failure, like encode."""
+        import numpy as np
+        n, blob, in_off, width, height, _, arena = self._host_pictures(pictures, "encode_pictures")
         offs = np.empty(n + 1, np.uint64)
         status = np.empty(n, np.int32)
         self._chk(self.lib.nhw_enc_pictures(self.h, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n, quality,
@@ -465,6 +515,53 @@ class Encoder:
         if (status != 0).any():
             raise NhwError(f"per-picture status {status.tolist()}")
         return _split(arena, offs)
+
+    def encode_pictures_fit(self, pictures, max_bytes, ladder=None):
+        """The best .nhwp within a byte budget (nhw_enc_fit_pictures): pictures as for encode_pictures; max_bytes: an int or one per picture,
+        the budget for the whole container -> (containers, qualities, status), lists of n.  Picture i gets the container of the first quality
+        of `ladder` (default 23, 22, ..., 1) at which all its tiles encode and the container fits, identical to encode_pictures at that quality;
+        every tile of a picture has that one quality.  A per-picture NHW_E_BUDGET (the last rung's container) or NHW_E_CODEBOOK (b"") is
+        reported, not raised."""
+        import numpy as np
+        n, blob, in_off, width, height, _, arena = self._host_pictures(pictures, "encode_pictures_fit")
+        mb = np.asarray(max_bytes, dtype=object)
+        mb = np.full(n, mb.item(), dtype=object) if mb.ndim == 0 else mb
+        if mb.shape != (n,) or not all(isinstance(x, numbers.Integral) and x >= 0 for x in mb):
+            raise NhwError(f"max_bytes must be one non-negative int or {n} of them")
+        budget = np.array([min(int(x), 2**64 - 1) for x in mb], np.uint64)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        quality = np.empty(n, np.int32)
+        lad, lad_n = self._ladder(ladder)
+        self._chk(self.lib.nhw_enc_fit_pictures(self.h, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n,
+                                                budget.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data,
+                                                quality.ctypes.data))
+        return _split(arena, offs), quality.tolist(), status.tolist()
+
+    def encode_pictures_fit_psnr(self, pictures, decoder, min_psnr, ladder=None):
+        """The smallest quality whose .nhwp looks good enough (nhw_enc_fit_sse_pictures): pictures as for encode_pictures; min_psnr: dB, one
+        number or one per picture, over the picture's own pixels (picture_psnr_to_max_sse) -> (containers, qualities, status, sse), lists of
+        n.  Picture i gets the container of the first quality of `ladder` (default 1, 2, ..., 23) whose decode by `decoder` reaches the target,
+        identical to encode_pictures at that quality; sse[i] is the SSE a user measures between decode_pictures of it and the picture.  A
+        per-picture NHW_E_BUDGET (the last rung's container) or NHW_E_CODEBOOK (b"", sse 2**64 - 1) is reported, not raised."""
+        import numpy as np
+        n, blob, in_off, width, height, tiles, arena = self._host_pictures(pictures, "encode_pictures_fit_psnr")
+        dh = self._decoder(decoder, min(self.max_batch, tiles), "encode_pictures_fit_psnr")
+        db = np.asarray(min_psnr, dtype=object)
+        db = [db.item()] * n if db.ndim == 0 else list(db)
+        if len(db) != n:
+            raise NhwError(f"encode_pictures_fit_psnr: min_psnr must be one number or {n} of them")
+        target = np.array([picture_psnr_to_max_sse(float(x) if isinstance(x, numbers.Real) else x, int(w), int(h))
+                           for x, w, h in zip(db, width, height)], np.uint64)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        quality = np.empty(n, np.int32)
+        sse = np.empty(n, np.uint64)
+        lad, lad_n = self._ladder(ladder)
+        self._chk(self.lib.nhw_enc_fit_sse_pictures(self.h, dh, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n,
+                                                    target.ctypes.data, lad, lad_n, arena.ctypes.data, arena.size, offs.ctypes.data,
+                                                    status.ctypes.data, quality.ctypes.data, sse.ctypes.data))
+        return _split(arena, offs), quality.tolist(), status.tolist(), [int(x) for x in sse]
 
     def timing(self) -> Timing:
         t = Timing()

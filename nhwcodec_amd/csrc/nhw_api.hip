@@ -54,6 +54,7 @@ void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_afte
 /* pictures of any size (nhw_picture.hip) */
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s);
 hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s);
+hipError_t nhw_launch_sse_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, hipStream_t s);
 size_t nhw_container_head(uint8_t *dst, uint32_t width, uint32_t height, const uint32_t *lens, int t);
 hipError_t nhw_grow(void **p, size_t *cap, size_t bytes);
 
@@ -112,9 +113,13 @@ struct nhw_enc {
 	hipEvent_t fit_ev[2];
 	nhw_fit_stats fit_stats;
 	bool fit_done;
-	/* nhw_enc_pictures: the uploaded pictures and their descriptor table, grow-only */
+	/* nhw_enc_pictures and the picture searches: the uploaded pictures and their descriptor table, grow-only */
 	uint8_t *pic_px; size_t pic_cap;
 	nhw_picture *pic_desc; size_t pic_desc_cap;
+	/* nhw_enc_fit_sse_pictures, grow-only: a chunk's decoded tiles; the decoder's offsets (a chunk), the open pictures' SSE, the decoder's
+	 * status (a chunk) */
+	uint8_t *pfit_px; size_t pfit_px_cap;
+	uint64_t *pfit_aux; size_t pfit_aux_cap;
 };
 
 static const size_t k_buf_bytes[B_COUNT] = {
@@ -277,6 +282,8 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	dev_free(fit_sse_set(e));
 	if (e->pic_px) (void)hipFree(e->pic_px);
 	if (e->pic_desc) (void)hipFree(e->pic_desc);
+	if (e->pfit_px) (void)hipFree(e->pfit_px);
+	if (e->pfit_aux) (void)hipFree(e->pfit_aux);
 	if (e->h_fit_count) (void)hipHostFree(e->h_fit_count);
 	for (int i = 0; i < 2; i++) if (e->fit_ev[i]) (void)hipEventDestroy(e->fit_ev[i]);
 	for (int i = 0; i < 7; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);
@@ -674,79 +681,156 @@ extern "C" int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture
 	return NHW_OK;
 }
 
-/* Upload the pictures (one copy of the span they lie in when they lie close together, as a packed host array does; else one copy each),
- * pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch its files; then one
- * container per picture. */
-extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
-                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+extern "C" int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, void *stream)
 {
-	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { g_err = "bad argument"; return NHW_E_ARG; }
-	if (!nhw_quality_supported(quality)) { g_err = "quality outside 1..23"; return NHW_E_QUALITY; }
-	std::vector<nhw_picture> desc((size_t)n);
-	std::vector<int> first((size_t)n + 1);
-	uint64_t tiles = 0, bytes = 0, lo = UINT64_MAX, hi = 0;
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_sse_pictures_device")) return rc;
+	if (!d_sse || ((uintptr_t)d_sse & 7)) { g_err = "nhw_sse_pictures_device: d_sse must be 8-byte aligned"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_sse_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, m, d_sse, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* The pictures of a host call (nhw_enc_pictures, the picture searches): packed (pitch 3 W) at bgr + in_off[i].  pictures_check: the sides
+ * and the tile count; first[i] = picture i's first tile, first[n] = all tiles; the descriptors numbered so (addr still 0). */
+struct PicCall {
+	std::vector<nhw_picture> desc;
+	std::vector<int> first;
+	int tiles = 0;
+};
+
+static int pictures_check(const uint32_t *width, const uint32_t *height, int n, const char *who, PicCall &pc)
+{
+	pc.desc.assign((size_t)n, nhw_picture{});
+	pc.first.assign((size_t)n + 1, 0);
+	uint64_t tiles = 0;
 	for (int i = 0; i < n; i++) {
 		const int t = nhw_picture_tiles(width[i], height[i]);
-		if (t < 1) { g_err = "nhw_enc_pictures: a picture side outside 1..65535"; return NHW_E_ARG; }
-		const uint64_t sz = 3ull * width[i] * height[i];
-		desc[i] = { 0, 3ull * width[i], width[i], height[i], (uint32_t)tiles, 0 };
-		first[i] = (int)tiles;
-		tiles += (uint64_t)t; bytes += sz;
+		if (t < 1) { g_err = std::string(who) + ": a picture side outside 1..65535"; return NHW_E_ARG; }
+		pc.desc[i] = { 0, 3ull * width[i], width[i], height[i], (uint32_t)tiles, 0 };
+		pc.first[i] = (int)tiles;
+		tiles += (uint64_t)t;
+		if (tiles > INT_MAX / 16) { g_err = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
+	}
+	pc.first[n] = (int)tiles;
+	pc.tiles = (int)tiles;
+	return NHW_OK;
+}
+
+/* Upload the pictures into the handle's grow-only buffer (one copy of the span they lie in when they lie close together, as a packed host
+ * array does; else one copy each) on the handle's stream and fill in the descriptors' addresses; the table itself is the caller's to upload. */
+static int pictures_upload(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, PicCall &pc)
+{
+	const int n = (int)pc.desc.size();
+	uint64_t bytes = 0, lo = UINT64_MAX, hi = 0;
+	for (int i = 0; i < n; i++) {
+		const uint64_t sz = 3ull * pc.desc[i].width * pc.desc[i].height;
+		bytes += sz;
 		lo = in_off[i] < lo ? in_off[i] : lo;
 		hi = in_off[i] + sz > hi ? in_off[i] + sz : hi;
-		if (tiles > INT_MAX / 16) { g_err = "nhw_enc_pictures: too many tiles in one call"; return NHW_E_ARG; }
 	}
-	first[n] = (int)tiles;
-	HIPCHK(hipSetDevice(e->device));
-	const int chunk = (int)(tiles < (uint64_t)e->max_batch ? tiles : (uint64_t)e->max_batch);
-	{ const int rc = host_buffers(e, chunk); if (rc) return rc; }
 	const bool span = hi - lo <= bytes + bytes / 4 + (1u << 20);
 	HIPCHK(nhw_grow((void **)&e->pic_px, &e->pic_cap, span ? hi - lo : bytes));
 	HIPCHK(nhw_grow((void **)&e->pic_desc, &e->pic_desc_cap, (size_t)n * sizeof(nhw_picture)));
 	hipStream_t s = e->own_stream;
 	if (span) HIPCHK(hipMemcpyAsync(e->pic_px, bgr + lo, hi - lo, hipMemcpyHostToDevice, s));
 	for (uint64_t i = 0, at = 0; i < (uint64_t)n; i++) {
-		const uint64_t sz = 3ull * width[i] * height[i];
-		if (span) desc[i].addr = (uint64_t)(uintptr_t)(e->pic_px + (in_off[i] - lo));
+		const uint64_t sz = 3ull * pc.desc[i].width * pc.desc[i].height;
+		if (span) pc.desc[i].addr = (uint64_t)(uintptr_t)(e->pic_px + (in_off[i] - lo));
 		else {
 			HIPCHK(hipMemcpyAsync(e->pic_px + at, bgr + in_off[i], sz, hipMemcpyHostToDevice, s));
-			desc[i].addr = (uint64_t)(uintptr_t)(e->pic_px + at);
+			pc.desc[i].addr = (uint64_t)(uintptr_t)(e->pic_px + at);
 			at += sz;
 		}
 	}
-	HIPCHK(hipMemcpyAsync(e->pic_desc, desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
-	std::vector<uint8_t> files;
-	std::vector<uint32_t> lens((size_t)tiles);
-	std::vector<int32_t> tst((size_t)tiles);
+	return NHW_OK;
+}
+
+/* The SSE search's per-chunk step (nhw_enc_fit_sse_pictures): decode the chunk's files from the host path's output slots by `dec` and add
+ * their picture-cropped error to `sse` (one entry per picture of the table). */
+struct ChunkSse {
+	nhw_dec *dec;
+	uint8_t *px;             /* the chunk's decoded tiles */
+	const uint64_t *doff;    /* decoder offsets: tile j at j * NHW_OUT_STRIDE */
+	int32_t *dstatus;        /* the decoder's status, a chunk */
+	uint64_t *sse;
+	int32_t *h_dstatus;      /* host: the decoder's status, every tile of the call */
+};
+
+/* Encode the global tiles [0, tiles) of the table d_desc (np pictures) at `quality` in chunks of at most max_batch into the host path's
+ * slots: k_tile_pad straight from the uploaded pictures, the encode, (the SSE step), then the chunk's files compacted and brought back.
+ * Tile t's file is files[.. + lens[t]) (back to back in tile order), its status tst[t]. */
+static int encode_tiles(nhw_enc *e, const nhw_picture *d_desc, int np, int tiles, int quality, const ChunkSse *cs, std::vector<uint8_t> &files,
+                        uint32_t *lens, int32_t *tst)
+{
+	hipStream_t s = e->own_stream;
+	const int chunk = tiles < e->max_batch ? tiles : e->max_batch;
 	std::vector<uint64_t> offs((size_t)chunk + 1);
-	for (int t0 = 0; t0 < (int)tiles; t0 += chunk) {
-		const int m = (int)tiles - t0 < chunk ? (int)tiles - t0 : chunk;
-		HIPCHK(nhw_launch_tile_pad(e->pic_desc, n, t0, m, e->d_in, s));
+	files.clear();
+	for (int t0 = 0; t0 < tiles; t0 += chunk) {
+		const int m = tiles - t0 < chunk ? tiles - t0 : chunk;
+		HIPCHK(nhw_launch_tile_pad(d_desc, np, t0, m, e->d_in, s));
 		{ const int rc = nhw_enc_batch_device(e, e->d_in, m, quality, e->d_out, e->d_sizes, e->d_status, s); if (rc) return rc; }
+		if (cs) {
+			const int rc = nhw_dec_batch_device(cs->dec, e->d_out, cs->doff, e->d_sizes, m, cs->px, cs->dstatus, nullptr, s);
+			if (rc) { g_err = std::string("decode of a rung: ") + nhw_dec_last_error(); return rc; }
+			HIPCHK(nhw_launch_sse_crop(cs->px, d_desc, np, t0, m, cs->sse, s));
+			HIPCHK(hipMemcpyAsync(cs->h_dstatus + t0, cs->dstatus, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+		}
 		k_offsets<<<1, 1, 0, s>>>(e->d_sizes, e->d_offs, m);
 		k_compact<<<m, 256, 0, s>>>(e->d_out, e->d_sizes, e->d_offs, e->d_compact);
 		HIPCHK(hipMemcpyAsync(offs.data(), e->d_offs, sizeof(uint64_t) * (m + 1), hipMemcpyDeviceToHost, s));
-		HIPCHK(hipMemcpyAsync(tst.data() + t0, e->d_status, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(tst + t0, e->d_status, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
 		HIPCHK(hipStreamSynchronize(s));
 		const size_t used = files.size();
 		files.resize(used + offs[m]);
 		HIPCHK(hipMemcpy(files.data() + used, e->d_compact, offs[m], hipMemcpyDeviceToHost));
 		for (int k = 0; k < m; k++) lens[(size_t)t0 + k] = (uint32_t)(offs[k + 1] - offs[k]);
 	}
+	return NHW_OK;
+}
+
+/* picture i's container (t tiles of lengths lens[], files back to back) at out_arena + *at, which it advances; NHW_E_SPACE if it does not fit */
+static int put_container(uint8_t *out_arena, size_t arena_cap, uint64_t *at, uint32_t width, uint32_t height, const uint32_t *lens, int t,
+                         const uint8_t *files)
+{
+	uint64_t sum = 0;
+	for (int k = 0; k < t; k++) sum += lens[k];
+	const uint64_t size = 16 + 4 * (uint64_t)t + sum;
+	if (*at + size > arena_cap) { g_err = "output arena too small"; return NHW_E_SPACE; }
+	const size_t head = nhw_container_head(out_arena + *at, width, height, lens, t);
+	memcpy(out_arena + *at + head, files, sum);
+	*at += size;
+	return NHW_OK;
+}
+
+/* Upload the pictures, pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch
+ * its files; then one container per picture. */
+extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { g_err = "bad argument"; return NHW_E_ARG; }
+	if (!nhw_quality_supported(quality)) { g_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	PicCall pc;
+	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures", pc); if (rc) return rc; }
+	const int tiles = pc.tiles;
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, tiles < e->max_batch ? tiles : e->max_batch); if (rc) return rc; }
+	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
+	HIPCHK(hipMemcpyAsync(e->pic_desc, pc.desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, e->own_stream));
+	std::vector<uint8_t> files;
+	std::vector<uint32_t> lens((size_t)tiles);
+	std::vector<int32_t> tst((size_t)tiles);
+	{ const int rc = encode_tiles(e, e->pic_desc, n, tiles, quality, nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
+	const int *first = pc.first.data();
 	uint64_t at = 0, fpos = 0;
 	for (int i = 0; i < n; i++) {
-		const int t = first[i + 1] - first[i];
 		uint64_t sum = 0;
 		int32_t st = NHW_OK;
 		for (int k = first[i]; k < first[i + 1]; k++) { sum += lens[k]; if (st == NHW_OK) st = tst[k]; }
 		out_off[i] = at;
 		status[i] = st;
 		if (st == NHW_OK) {
-			const uint64_t size = 16 + 4 * (uint64_t)t + sum;
-			if (at + size > arena_cap) { g_err = "output arena too small"; return NHW_E_SPACE; }
-			const size_t head = nhw_container_head(out_arena + at, width[i], height[i], lens.data() + first[i], t);
-			memcpy(out_arena + at + head, files.data() + fpos, sum);
-			at += size;
+			const int rc = put_container(out_arena, arena_cap, &at, width[i], height[i], lens.data() + first[i], first[i + 1] - first[i], files.data() + fpos);
+			if (rc) return rc;
 		}
 		fpos += sum;
 	}
@@ -804,31 +888,45 @@ struct FitCall {
 	int q[23] = {}, len = 0;
 };
 
+/* A search's ladder: ladder_len 0..23, 0 exactly with ladder NULL (NHW_E_ARG); NULL = 23 .. 1 for bytes, 1 .. 23 for SSE (`ascending`);
+ * the entries distinct and in 1..23 (NHW_E_QUALITY).  The qualities go to q[0 .. *len). */
+static int ladder_check(const int *ladder, int ladder_len, bool ascending, int *q, int *len)
+{
+	if (ladder_len < 0 || ladder_len > 23 || (ladder_len == 0) != (ladder == nullptr)) { g_err = "bad argument"; return NHW_E_ARG; }
+	*len = ladder ? ladder_len : 23;
+	bool seen[24] = {};
+	for (int r = 0; r < *len; r++) {
+		q[r] = ladder ? ladder[r] : ascending ? r + 1 : 23 - r;
+		if (!nhw_quality_supported(q[r]) || seen[q[r]]) { g_err = "ladder: qualities must be distinct and in 1..23"; return NHW_E_QUALITY; }
+		seen[q[r]] = true;
+	}
+	return NHW_OK;
+}
+
+/* the SSE searches' decoder: present, max_batch >= need, on e's device, no debug stop (NHW_E_ARG) */
+static int dec_check(const nhw_enc *e, nhw_dec *d, int need, const std::string &who, const char *need_name)
+{
+	if (!d) { g_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
+	int device = 0, max_batch = 0, stop_after = 0;
+	nhw_dec_props(d, &device, &max_batch, &stop_after);
+	if (max_batch < need) { g_err = who + ": the decoder's max_batch is below " + need_name; return NHW_E_ARG; }
+	if (device != e->device) { g_err = who + ": the decoder is on another device than the encoder"; return NHW_E_ARG; }
+	if (stop_after) { g_err = who + ": not with a decoder debug stop set (every rung must be a whole decode)"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
 /* Everything a fit call refuses before it launches anything, in this order: NULL pointers (`ptrs` false), an unaligned c.bgr (NULL while
- * the host path checks: it uploads into an aligned buffer), n, the ladder (NULL = 23 .. 1 for bytes, 1 .. 23 for SSE), a debug stop, the
- * SSE search's decoder, a capturing stream.  Makes e's device current. */
+ * the host path checks: it uploads into an aligned buffer), n, a debug stop, the ladder (ladder_check), the SSE search's decoder, a
+ * capturing stream.  Makes e's device current. */
 static int fit_check(nhw_enc *e, FitCall &c, bool ptrs, void *stream)
 {
 	if (!e || !ptrs) { g_err = "bad argument"; return NHW_E_ARG; }
 	const std::string who = c.who;
 	if ((uintptr_t)c.bgr & 15) { g_err = who + ": d_bgr must be 16-byte aligned"; return NHW_E_ARG; }
-	if (c.n < 1 || c.n > e->max_batch || c.ladder_len < 0 || c.ladder_len > 23 || (c.ladder_len == 0) != (c.ladder == nullptr)) { g_err = "bad argument"; return NHW_E_ARG; }
+	if (c.n < 1 || c.n > e->max_batch) { g_err = "bad argument"; return NHW_E_ARG; }
 	if (e->stop_after) { g_err = who + ": not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
-	c.len = c.ladder ? c.ladder_len : 23;
-	bool seen[24] = {};
-	for (int r = 0; r < c.len; r++) {
-		c.q[r] = c.ladder ? c.ladder[r] : c.by_sse ? r + 1 : 23 - r;
-		if (!nhw_quality_supported(c.q[r]) || seen[c.q[r]]) { g_err = "ladder: qualities must be distinct and in 1..23"; return NHW_E_QUALITY; }
-		seen[c.q[r]] = true;
-	}
-	if (c.by_sse) {
-		if (!c.dec) { g_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
-		int device = 0, max_batch = 0, stop_after = 0;
-		nhw_dec_props(c.dec, &device, &max_batch, &stop_after);
-		if (max_batch < c.n) { g_err = who + ": the decoder's max_batch is below n"; return NHW_E_ARG; }
-		if (device != e->device) { g_err = who + ": the decoder is on another device than the encoder"; return NHW_E_ARG; }
-		if (stop_after) { g_err = who + ": not with a decoder debug stop set (every rung must be a whole decode)"; return NHW_E_ARG; }
-	}
+	{ const int rc = ladder_check(c.ladder, c.ladder_len, c.by_sse, c.q, &c.len); if (rc) return rc; }
+	if (c.by_sse) { const int rc = dec_check(e, c.dec, c.n, who, "n"); if (rc) return rc; }
 	HIPCHK(hipSetDevice(e->device));
 	c.s = stream ? (hipStream_t)stream : e->own_stream;
 	hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -942,6 +1040,141 @@ extern "C" int nhw_enc_fit_sse_batch(nhw_enc *e, nhw_dec *d, const uint8_t *bgr,
 {
 	FitCall c = { "nhw_enc_fit_sse_batch", true, d, nullptr, n, nullptr, ladder, ladder_len };
 	return fit_host(e, c, bgr && max_sse && out_arena && out_off && status && quality && sse, bgr, max_sse, out_arena, arena_cap, out_off, status, quality, sse);
+}
+
+/* ------------------------------------------------------------------------------------------------ pictures to a byte or distortion budget */
+/* One picture search: the byte test (limit = max_bytes) or, with a decoder, the SSE test (limit = max_sse). */
+struct PicFit {
+	const char *who;
+	nhw_dec *dec;                        /* NULL: the byte search */
+	const uint64_t *limit;
+	int q[23] = {}, len = 0;
+};
+
+/* The walk over pictures.  Every picture is open at the first rung.  A rung uploads the table of the open pictures only, first_tile
+ * renumbered, and encodes their tiles (encode_tiles: k_tile_pad re-tiles them straight from the uploaded picture bytes); the SSE search
+ * decodes each chunk and adds the picture-cropped error into one entry per open picture, zeroed once a rung.  After the rung the host
+ * closes every open picture that passes (all tiles NHW_OK; the container size, or the SSE, within its limit; the SSE search: every tile
+ * decoded NHW_OK) and keeps its files; at the last rung every picture still open keeps that rung's. */
+static int fit_pictures(nhw_enc *e, const PicFit &f, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height,
+                        int n, PicCall &pc, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	hipStream_t s = e->own_stream;
+	const int chunk = pc.tiles < e->max_batch ? pc.tiles : e->max_batch;
+	e->fit_done = false;
+	nhw_fit_stats st;
+	memset(&st, 0, sizeof st);
+	HIPCHK(hipEventRecord(e->fit_ev[0], s));
+	{ const int rc = host_buffers(e, chunk); if (rc) return rc; }
+	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
+	ChunkSse cs = {};
+	std::vector<int32_t> tdst;
+	if (f.dec) {
+		HIPCHK(nhw_grow((void **)&e->pfit_px, &e->pfit_px_cap, (size_t)chunk * NHW_IMG_BYTES));
+		HIPCHK(nhw_grow((void **)&e->pfit_aux, &e->pfit_aux_cap, (size_t)(chunk + n) * 8 + (size_t)chunk * 4));
+		k_fit_doff<<<(chunk + 255) / 256, 256, 0, s>>>(e->pfit_aux, chunk);
+		HIPCHK(hipGetLastError());
+		tdst.resize((size_t)pc.tiles);
+		cs = { f.dec, e->pfit_px, e->pfit_aux, (int32_t *)(e->pfit_aux + chunk + n), e->pfit_aux + chunk, tdst.data() };
+	}
+	std::vector<std::vector<uint8_t>> kept((size_t)n);    /* a closed picture's tile files, back to back */
+	std::vector<std::vector<uint32_t>> kept_len((size_t)n);
+	std::vector<uint64_t> psse((size_t)n);
+	std::vector<int> open((size_t)n);                      /* the open pictures, ascending */
+	for (int i = 0; i < n; i++) open[i] = i;
+	std::vector<nhw_picture> desc;
+	std::vector<uint8_t> files;
+	std::vector<uint32_t> lens((size_t)pc.tiles);
+	std::vector<int32_t> tst((size_t)pc.tiles);
+	for (int r = 0; r < f.len && !open.empty(); r++) {
+		const bool last = r == f.len - 1;
+		const int no = (int)open.size();
+		desc.resize((size_t)no);
+		int tiles = 0;
+		for (int j = 0; j < no; j++) {
+			const int i = open[j];
+			desc[j] = pc.desc[i];
+			desc[j].first_tile = (uint32_t)tiles;
+			tiles += pc.first[i + 1] - pc.first[i];
+		}
+		st.quality[r] = f.q[r]; st.images[r] = tiles; st.rungs = r + 1;
+		HIPCHK(hipMemcpyAsync(e->pic_desc, desc.data(), (size_t)no * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
+		if (f.dec) HIPCHK(hipMemsetAsync(cs.sse, 0, (size_t)no * 8, s));
+		{ const int rc = encode_tiles(e, e->pic_desc, no, tiles, f.q[r], f.dec ? &cs : nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
+		if (f.dec) HIPCHK(hipMemcpy(psse.data(), cs.sse, (size_t)no * 8, hipMemcpyDeviceToHost));
+		std::vector<int> still;
+		uint64_t fpos = 0;
+		for (int j = 0; j < no; j++) {
+			const int i = open[j], t0 = (int)desc[j].first_tile, t = pc.first[i + 1] - pc.first[i];
+			uint64_t sum = 0;
+			int32_t enc_st = NHW_OK, dec_st = NHW_OK;
+			for (int k = t0; k < t0 + t; k++) {
+				sum += lens[k];
+				if (enc_st == NHW_OK) enc_st = tst[k];
+				if (f.dec && dec_st == NHW_OK) dec_st = tdst[k];
+			}
+			const bool pass = enc_st == NHW_OK && (f.dec ? dec_st == NHW_OK && psse[j] <= f.limit[i] : 16 + 4 * (uint64_t)t + sum <= f.limit[i]);
+			if (pass || last) {
+				quality[i] = f.q[r];
+				status[i] = pass ? NHW_OK : enc_st != NHW_OK ? enc_st : dec_st != NHW_OK ? NHW_E_FORMAT : NHW_E_BUDGET;
+				if (sse) sse[i] = enc_st != NHW_OK || dec_st != NHW_OK ? UINT64_MAX : psse[j];
+				if (enc_st == NHW_OK) {
+					kept[i].assign(files.begin() + fpos, files.begin() + fpos + sum);
+					kept_len[i].assign(lens.begin() + t0, lens.begin() + t0 + t);
+				}
+			} else still.push_back(i);
+			fpos += sum;
+		}
+		open.swap(still);
+	}
+	HIPCHK(hipEventRecord(e->fit_ev[1], s));
+	e->fit_stats = st;
+	e->fit_done = true;
+	uint64_t at = 0;
+	for (int i = 0; i < n; i++) {
+		out_off[i] = at;
+		if (status[i] == NHW_E_CODEBOOK) continue;                 /* an empty container, as nhw_enc_pictures gives */
+		const int rc = put_container(out_arena, arena_cap, &at, width[i], height[i], kept_len[i].data(), (int)kept_len[i].size(), kept[i].data());
+		if (rc) return rc;
+	}
+	out_off[n] = at;
+	return NHW_OK;
+}
+
+/* the picture searches' checks, in this order: NULL pointers, n, the sides (and the tile count), a debug stop, the ladder, the decoder;
+ * nothing is launched before all of them pass */
+static int fit_pictures_host(nhw_enc *e, PicFit &f, bool ptrs, const int *ladder, int ladder_len, const uint8_t *bgr, const uint64_t *in_off,
+                             const uint32_t *width, const uint32_t *height, int n, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off,
+                             int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	if (!e || !ptrs || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || !quality || n < 1) { g_err = "bad argument"; return NHW_E_ARG; }
+	const std::string who = f.who;
+	PicCall pc;
+	{ const int rc = pictures_check(width, height, n, f.who, pc); if (rc) return rc; }
+	if (e->stop_after) { g_err = who + ": not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
+	{ const int rc = ladder_check(ladder, ladder_len, f.dec != nullptr, f.q, &f.len); if (rc) return rc; }
+	if (f.dec) { const int rc = dec_check(e, f.dec, pc.tiles < e->max_batch ? pc.tiles : e->max_batch, who, "min(encoder max_batch, tiles)"); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	return fit_pictures(e, f, bgr, in_off, width, height, n, pc, out_arena, arena_cap, out_off, status, quality, sse);
+}
+
+extern "C" int nhw_enc_fit_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                    const uint64_t *max_bytes, const int *ladder, int ladder_len,
+                                    uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality)
+{
+	PicFit f;
+	f.who = "nhw_enc_fit_pictures"; f.dec = nullptr; f.limit = max_bytes;
+	return fit_pictures_host(e, f, max_bytes != nullptr, ladder, ladder_len, bgr, in_off, width, height, n, out_arena, arena_cap, out_off, status, quality, nullptr);
+}
+
+extern "C" int nhw_enc_fit_sse_pictures(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height,
+                                        int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
+                                        uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	PicFit f;
+	f.who = "nhw_enc_fit_sse_pictures"; f.dec = d; f.limit = max_sse;
+	if (!d) { g_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
+	return fit_pictures_host(e, f, max_sse != nullptr && sse != nullptr, ladder, ladder_len, bgr, in_off, width, height, n, out_arena, arena_cap, out_off, status, quality, sse);
 }
 
 extern "C" int nhw_enc_last_fit_stats(nhw_enc *e, nhw_fit_stats *s)

@@ -5,14 +5,15 @@
  *           sse[i] with one 64-bit integer atomic.  Integer addition is associative, so the result is exact and does not depend on the
  *           order the workgroups ran in.  sse[] is zeroed on the stream first.
  *
- * Per dword of four bytes, sum (a_k - b_k)^2 = udot4(a,a) + udot4(b,b) - 2 udot4(a,b): three v_dot4_u32_u8, exact in 32 bits (at most
- * 4 * 255^2 = 260 100 a dword).  A thread's sum over its 48 dwords (at most 12.5 M) and a wavefront's (at most 800 M) stay in 32 bits;
- * the workgroup's four wavefronts are added in 64 bits.
+ * Per dword of four bytes, sum (a_k - b_k)^2 = udot4(a,a) + udot4(b,b) - 2 udot4(a,b): three v_dot4_u32_u8 (sse4, nhw_sse.h), exact in
+ * 32 bits (at most 4 * 255^2 = 260 100 a dword).  A thread's sum over its 48 dwords (at most 12.5 M) and a wavefront's (at most 800 M)
+ * stay in 32 bits; the workgroup's four wavefronts are added in 64 bits.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/nhw_hip.h"
+#include "nhw_sse.h"
 
 #define SSE_IMG_V4 (NHW_IMG_BYTES / 16u)     /* 49 152 sixteen-byte words an image */
 #define SSE_T      256
@@ -20,16 +21,6 @@
 #define SSE_R      3                         /* rounds of SSE_U words a thread */
 #define SSE_X      (SSE_IMG_V4 / (SSE_T * SSE_U * SSE_R))   /* 16 workgroups an image */
 static_assert(SSE_X * SSE_T * SSE_U * SSE_R == SSE_IMG_V4, "an image is a whole number of workgroup slices");
-
-__device__ __forceinline__ uint32_t sse4(uint32_t a, uint32_t b)
-{
-	return __builtin_amdgcn_udot4(a, a, 0u, false) + __builtin_amdgcn_udot4(b, b, 0u, false) - 2u * __builtin_amdgcn_udot4(a, b, 0u, false);
-}
-
-__device__ __forceinline__ uint32_t sse16(const uint4 &a, const uint4 &b)
-{
-	return sse4(a.x, b.x) + sse4(a.y, b.y) + sse4(a.z, b.z) + sse4(a.w, b.w);
-}
 
 /* workgroup (x, i): words [x * 3072, x * 3072 + 3072) of image i, in three rounds; in a round the eight loads of a thread go out together */
 __global__ __launch_bounds__(SSE_T) void k_sse(const uint4 *__restrict__ a, const uint4 *__restrict__ b, unsigned long long *__restrict__ sse)

@@ -1,12 +1,12 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles: the padding kernel k_tile_pad, its inverse
- * k_untile_crop, and the .nhwp container that holds a picture's width, height and tile files.
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11, 12): the padding kernel k_tile_pad, its inverse
+ * k_untile_crop, the picture-cropped error k_sse_crop, and the .nhwp container that holds a picture's width, height and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
  * ny = ceil(H / 512), by edge replication: padded pixel (r, c) = picture pixel (min(r, H - 1), min(c, W - 1)).  Tile (ty, tx) is padded
  * rows 512 ty .. and columns 512 tx .., index ty nx + tx; a picture's tiles are numbered from its descriptor's first_tile on.
  *
- * Both kernels are copies: a workgroup moves one band of TP_ROWS rows of one tile.  The picture side may have any alignment and any
+ * The first two kernels are copies: a workgroup moves one band of TP_ROWS rows of one tile (k_sse_crop reads one the same way).  The picture side may have any alignment and any
  * pitch, so its bytes are reached through the naturally aligned dwords that hold them, funnelled together with v_alignbyte_b32 (fetch);
  * the tile side is 16-byte aligned and moves in dwordx4.  No load touches a word that holds no byte of a picture row (or, for
  * k_untile_crop, of the tile rows it reads), and no store touches a byte outside a picture row.
@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include "../../include/nhw_hip.h"
+#include "nhw_sse.h"
 
 namespace {
 
@@ -58,13 +59,15 @@ __device__ __forceinline__ int find_picture(const nhw_picture *pics, int n, uint
 struct TileRef {
 	nhw_picture p;
 	uint32_t ty, tx;
+	int k;                                  /* the picture's index in the table */
 };
 
 /* the workgroup's tile (tile0 + blockIdx.x / TP_BANDS) and its picture; false for a tile no picture of the table holds */
 __device__ __forceinline__ bool tile_of(const nhw_picture *pics, int n, int tile0, TileRef &r)
 {
 	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
-	r.p = pics[find_picture(pics, n, t)];
+	r.k = find_picture(pics, n, t);
+	r.p = pics[r.k];
 	if (!r.p.width || !r.p.height || t < r.p.first_tile) return false;
 	const uint32_t nx = (r.p.width + 511) / 512, ny = (r.p.height + 511) / 512, in = t - r.p.first_tile;
 	if (in >= nx * ny) return false;
@@ -168,6 +171,81 @@ __global__ __launch_bounds__(TP_THREADS) void k_untile_crop(const uint8_t *__res
 	}
 }
 
+/* The SSE of decoded tiles against the pictures' own bytes: tile row rr of tile (ty, tx) against picture row 512 ty + rr < H, bytes
+ * [1536 tx, min(1536 tx + 1536, 3W)); rows past H and bytes past 3W (the padding) never count.  Word w of a row: the picture side through
+ * fetch (only the dwords that hold picture bytes, any alignment and pitch), the tile side as an aligned dwordx4.  In a word that crosses
+ * 3W the bytes from 3W on are masked to zero on both sides (on the picture side the dword that holds the row's last byte brings the bytes
+ * behind it along: another row's, or whatever follows the picture), so they add 0.  Per word sse16 (nhw_sse.h): three v_dot4_u32_u8 a dword, exact.
+ * Bounds: a band is 32 rows x 96 words; a thread takes 12 words (at most 12 x 16 x 255^2 = 12.5 M), a wavefront 64 threads (at most 799 M),
+ * both in 32 bits; the four wavefronts are added in 64 bits (a band's sum is at most 49 152 x 255^2 = 3.2 G, a picture's far beyond 32 bits)
+ * and the workgroup adds its band to sse[k] with one 64-bit integer atomic.  Integer addition is associative: the result is exact and does
+ * not depend on the order the workgroups ran in.  Accumulates: the caller zeroes sse[]. */
+/* bytes [0, nin) of v, the others 0 */
+__device__ __forceinline__ uint4 keep_bytes(uint4 v, int nin)
+{
+	uint32_t o[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+	for (int d = 0; d < 4; d++) {
+		const int keep = nin - 4 * d;                                  /* bytes of dword d that are wanted */
+		o[d] = keep >= 4 ? o[d] : keep <= 0 ? 0u : o[d] & ((1u << (8 * keep)) - 1u);
+	}
+	return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <bool EDGE>
+__device__ __forceinline__ uint32_t sse_band(const TileRef &r, const uint4 *__restrict__ tile, int band)
+{
+	constexpr int WORDS = TP_ROWS * TP_WORDS, PER = WORDS / TP_THREADS, GROUP = 4;
+	static_assert(WORDS % TP_THREADS == 0 && PER % GROUP == 0, "band layout");
+	const int seg = 3 * (int)r.p.width - 1536 * (int)r.tx;              /* picture bytes in a tile row (at least 1536 without EDGE) */
+	const uint32_t row0 = 512 * r.ty + band * TP_ROWS;
+	uint32_t acc = 0;
+#pragma unroll
+	for (int g = 0; g < PER; g += GROUP) {
+		uint4 a[GROUP], b[GROUP];
+#pragma unroll
+		for (int k = 0; k < GROUP; k++) {
+			const int i = (g + k) * TP_THREADS + threadIdx.x, rr = i / TP_WORDS, w = i % TP_WORDS;
+			const int nin = EDGE ? (seg - 16 * w < 16 ? seg - 16 * w : 16) : 16;
+			a[k] = b[k] = make_uint4(0, 0, 0, 0);
+			if (row0 + rr < r.p.height && nin > 0) {
+				const uintptr_t R = (uintptr_t)(r.p.addr + (uint64_t)(row0 + rr) * r.p.pitch) + 1536 * r.tx + 16 * w;
+				a[k] = fetch(R, 0, nin);
+				b[k] = tile[(band * TP_ROWS + rr) * TP_WORDS + w];
+				if (EDGE && nin < 16) {
+					a[k] = keep_bytes(a[k], nin);
+					b[k] = keep_bytes(b[k], nin);
+				}
+			}
+		}
+#pragma unroll
+		for (int k = 0; k < GROUP; k++) acc += sse16(a[k], b[k]);
+	}
+	return acc;
+}
+
+__global__ __launch_bounds__(TP_THREADS) void k_sse_crop(const uint8_t *__restrict__ tiles, const nhw_picture *__restrict__ pics, int n_pics, int tile0,
+                                                          unsigned long long *__restrict__ sse)
+{
+	__shared__ uint32_t wsum[TP_THREADS / 64];
+	TileRef r;
+	if (!tile_of(pics, n_pics, tile0, r)) return;
+	const int band = blockIdx.x % TP_BANDS;
+	if (512 * r.ty + band * TP_ROWS >= r.p.height) return;             /* a band wholly below the picture: padding only */
+	const uint4 *tile = reinterpret_cast<const uint4 *>(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES);
+	uint32_t acc = 1536 * (r.tx + 1) <= 3 * r.p.width ? sse_band<false>(r, tile, band) : sse_band<true>(r, tile, band);
+#pragma unroll
+	for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+	if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		unsigned long long s = 0;
+#pragma unroll
+		for (int w = 0; w < TP_THREADS / 64; w++) s += wsum[w];
+		atomicAdd(sse + r.k, s);
+	}
+}
+
 } /* namespace */
 
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
@@ -179,6 +257,12 @@ hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0,
 hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s)
 {
 	k_untile_crop<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	return hipGetLastError();
+}
+
+hipError_t nhw_launch_sse_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, hipStream_t s)
+{
+	k_sse_crop<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0, reinterpret_cast<unsigned long long *>(d_sse));
 	return hipGetLastError();
 }
 
