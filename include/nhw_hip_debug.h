@@ -28,6 +28,14 @@ int nhw_debug_hash(nhw_enc *e, int buf, size_t bytes, int n, void *d_out, void *
  * that the production launch sequence -- which leaves out stores nothing reads -- never reads what an earlier batch left in a plane */
 int nhw_debug_fill(nhw_enc *e, int buf, int byte, size_t bytes, int n);
 
+/* 0: production launches; 1: every kernel that splits an item runs one slice per launch, slices in ascending order, on the same stream;
+ * 2: the same in descending order.  A slice is one value of a kernel's per-item split (a band, a quarter, a window, a row band); each
+ * serial launch covers that slice for every item of the batch.  Successive launches on a stream do not overlap, so a slice that reads what
+ * another slice of the same item writes sees it written (mode 1: the slices before it; mode 2: the ones behind it).  The kernels in the mode
+ * and the ones that cannot have the hazard: DESIGN.md, "Kernels that split an item". */
+int nhw_debug_slice_order(nhw_enc *e, int mode);
+int nhw_dec_debug_slice_order(nhw_dec *d, int mode);
+
 /* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip) */
 void nhw_dec_debug_stop_after(nhw_dec *d, int stage);
 int  nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size_t bytes);

@@ -68,6 +68,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_stage_chroma_l1.argtypes = [P, ctypes.c_int, P]
     L.nhw_stage_analysis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_synthesis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_debug_slice_order.argtypes = [P, ctypes.c_int]
+    L.nhw_dec_debug_slice_order.argtypes = [P, ctypes.c_int]
     L.nhw_picture_tiles.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
     L.nhw_tile_pictures_device.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]
     L.nhw_untile_pictures_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]

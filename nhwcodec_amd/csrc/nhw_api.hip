@@ -15,6 +15,7 @@
 
 #include "../../include/nhw_hip.h"
 #include "nhw_ws.h"
+#include "nhw_slice.h"
 
 /* launchers (nhw_front.hip, nhw_tail.hip) */
 void nhw_launch_color(const uint8_t *bgr, int n, int q, int16_t *y, size_t y_stride, uint8_t *u, uint8_t *v, size_t c_stride, hipStream_t s);
@@ -92,6 +93,7 @@ struct nhw_enc {
 	int lists_fork;   /* the position lists (Y24/Y25) on a third stream (NHW_LISTS_FORK=0 turns it off: +0.75 ms per q20 batch) */
 	int front_fallback; /* debug: every row / segment of the pre-filter carry takes its exact fallback path (tests) */
 	int stop_after;   /* debug: leave the batch driver after this many stages (0 = run everything) */
+	int slice_order;  /* debug: the forced slice order of the kernels that split a picture (nhw_slice.h; 0 = production) */
 	int last_n, last_q; /* images and quality of the last whole batch (nhw_stage_chroma_l1 works on what it left in the 4:2:0 planes) */
 	/* the quality searches (fit_walk): two sets of buffers for max_batch images, each allocated all or nothing by the first call that
 	 * needs it (fit_buffers) and present while its first pointer is */
@@ -296,6 +298,8 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	for (int i = 0; i < 2; i++) if (e->ll_ev[i]) (void)hipEventDestroy(e->ll_ev[i]);
 	delete e;
 }
+
+thread_local int nhw_slice_mode = 0;
 
 static inline int16_t *plane16(const NhwWs &ws, int b) { return (int16_t *)(ws.base + ws.off[b]); }
 static inline uint8_t *plane8(const NhwWs &ws, int b) { return ws.base + ws.off[b]; }
@@ -517,6 +521,7 @@ extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int qu
 	if (!nhw_quality_supported(quality)) { g_err = "quality outside 1..23"; return NHW_E_QUALITY; }
 	HIPCHK(hipSetDevice(e->device));
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	const NhwSliceScope slices(e->slice_order);
 	NhwWs ws = e->ws;
 	ws.n = n; ws.q = quality; ws.dbg = e->stop_after != 0;
 	e->timed = false;                                              /* set again only when a whole, un-stopped batch has recorded every event of nhw_timing */
@@ -1305,6 +1310,7 @@ extern "C" int nhw_stage_synthesis(nhw_enc *e, void *d_jpeg, void *d_proc, int n
 /* ------------------------------------------------------------------------------------------------ debug hooks (tests only) */
 extern "C" int nhw_debug_front_fallback(nhw_enc *e, int on) { if (!e) return NHW_E_ARG; e->front_fallback = on; return NHW_OK; }
 extern "C" int nhw_debug_stop_after(nhw_enc *e, int stage) { if (!e) return NHW_E_ARG; e->stop_after = stage; return NHW_OK; }
+extern "C" int nhw_debug_slice_order(nhw_enc *e, int mode) { if (!e || mode < 0 || mode > 2) return NHW_E_ARG; e->slice_order = mode; return NHW_OK; }
 /* developer hook: order-independent 64-bit digest of the first `bytes` bytes of workspace buffer `buf`, one per image, into device memory */
 __global__ __launch_bounds__(256) void k_debug_hash(const uint8_t *base, size_t stride, size_t words, unsigned long long *out)
 {

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/nhw_hip.h"
+#include "nhw_slice.h"
 
 #define DW 512
 #define DH 256
@@ -85,6 +86,10 @@ struct DecWs {
 
 /* plane A starts 4096 bytes into its buffer (the reference writes one cell in front of a plane in a corner case) */
 DEV int16_t *plane_a(const DecWs &ws, int img) { return ws.buf<int16_t>(D_A, img) + 2048; }
+/* the level-1 LL as level 2 of the luma leaves it (rows 0 .. 255, columns 0 .. 255 at plane A's pitch, 4096 bytes into its buffer like plane
+ * A): in D_B, the luma value list, which nothing reads once k_dec_expand is through.  The level-2 kernels read plane A and write here, so a
+ * quarter of k_dec_luma_l2q never reads rows another quarter has already written; k_dec_marks and k_dec_final take the LL from here. */
+DEV int16_t *plane_l1(const DecWs &ws, int img) { return ws.buf<int16_t>(D_B, img) + 2048; }
 /* D_B / D_CB: what the prefix-code walk found, as a list in stream order -- (value << 18) | position in the stream, one word per value that
  * is not part of a zero run (at most one per cell, plus a few words of slack) -- and D_SEG: the index of the first entry at or behind the
  * start of each of the 128 strips (2048 symbols) of the luma stream, the total behind them (k_dec_expand follows every strip with a
@@ -434,11 +439,11 @@ DEV int poslist_wave(const uint8_t *list, int len, T *pos, int cap, int row_step
 /* One wavefront per workgroup and side stream -- role 0: the LL2 DPCM bytes (+ the chroma bit planes on top of them, + the file's
  * header record for the kernels behind); roles 1..3: the position lists res1, res3, res5 + res6 with their bit planes -- the long role
  * first for the whole batch.  (As four wavefronts of one workgroup the three list walks waited at a barrier for the LL2 walk.) */
-__global__ __launch_bounds__(64) void k_dec_parse(DecWs ws)
+__global__ __launch_bounds__(64) void k_dec_parse(DecWs ws, int slice /* -1: production; else the role (nhw_slice.h) */)
 {
 	__shared__ DecMeta sm;
 	__shared__ uint8_t hdr[HDR_STAGE];
-	const int role = (int)blockIdx.x / ws.n, img = (int)blockIdx.x - role * ws.n, lane = threadIdx.x;
+	const int role = slice < 0 ? (int)blockIdx.x / ws.n : slice, img = (int)blockIdx.x - (slice < 0 ? role * ws.n : 0), lane = threadIdx.x;
 	const uint8_t *f = ws.blob + ws.blob_off[img];
 	const uint64_t flen = ws.blob_len[img];
 	for (int k = lane; k < HDR_STAGE; k += 64) stage_hdr(hdr, f, flen, k);   /* the header's bytes by the wavefront, then one lane reads them from LDS */
@@ -786,7 +791,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc_table(uint16_t *tab /* [256 + 10
 /* One wavefront per workgroup and stream: the luma streams of the batch first (they are the long ones), then the chroma streams -- as two
  * wavefronts of one workgroup the short chroma walk kept its half of the workgroup's LDS until the luma walk was through, and LDS is what
  * bounds the number of resident walks. */
-__global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__restrict__ table)
+__global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__restrict__ table, int slice /* -1: production; else the stream (nhw_slice.h) */)
 {
 	__shared__ uint16_t lut[256 + 16 * 64];
 	__shared__ uint16_t book1[354];
@@ -796,7 +801,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__rest
 	/* The kernel runs next to k_dec_parse on a stream of its own, so it reads the file header itself (a few dozen bytes) instead of the
 	 * workspace copy, and reports into a word of its own (D_SPARE[0] / [1]: one per stream) that k_dec_verdict folds into the file's status. */
 	__shared__ DecMeta hm;
-	const int part = (int)blockIdx.x >= ws.n ? 1 : 0, img = (int)blockIdx.x - part * ws.n, lane = threadIdx.x;
+	const int part = slice < 0 ? ((int)blockIdx.x >= ws.n ? 1 : 0) : slice, img = (int)blockIdx.x - (slice < 0 ? part * ws.n : 0), lane = threadIdx.x;
 	const uint16_t *lut2 = lut + 256;
 	uint16_t *book = book1, *syms = syms1;
 	int16_t *level = level1;
@@ -1544,9 +1549,9 @@ __global__ __launch_bounds__(1024) void k_dec_luma_l2(DecWs ws, int items, int u
 		}
 		lds_barrier();
 		if (!skip)
-		for (int i = 0; i < 16; i++) {                               /* column c of the block is row c of the plane */
+		for (int i = 0; i < 16; i++) {                               /* column c of the block is row c of the plane (the whole pass: of plane_l1) */
 			const int c = wv * 16 + i;
-			uint32_t *dst = reinterpret_cast<uint32_t *>(pl + (size_t)c * DW);
+			uint32_t *dst = reinterpret_cast<uint32_t *>((upto >= 3 ? plane_l1(ws, img) : pl) + (size_t)c * DW);
 #pragma unroll
 			for (int u = 0; u < PPL; u++) {
 				const int k = lane + 64 * u;
@@ -1565,11 +1570,11 @@ __global__ __launch_bounds__(1024) void k_dec_luma_l2(DecWs ws, int items, int u
  * it reads (from the values as they were, all before any is applied), filters in place, adds the residuals whose plane row is its own and
  * writes 64 whole rows of the plane.  Block b -> file ((b >> 5) << 3) | (b & 7), quarter (b >> 3) & 3 (a file's quarters on one XCD). */
 #define LQ_LS 74                      /* pitch of a row of the tile in shorts (37 dwords: column walks on 32 banks) */
-__global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items)
+__global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int slice /* -1: production; else the quarter (nhw_slice.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t T[DH * LQ_LS];
 	constexpr int S = DH, HLF = S / 2;
-	const int b = blockIdx.x, img = ((b >> 5) << 3) | (b & 7), p = (b >> 3) & 3;
+	const int b = blockIdx.x, img = slice < 0 ? ((b >> 5) << 3) | (b & 7) : b, p = slice < 0 ? (b >> 3) & 3 : slice;
 	if (img >= items) return;
 	const DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (m->status) return;
@@ -1708,9 +1713,10 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items)
 #undef ACC
 	}
 	lds_barrier();
-	for (int i = 0; i < 16; i++) {                                   /* column j of the tile is row 64 p + j of the plane */
+	int16_t *l1 = plane_l1(ws, img);
+	for (int i = 0; i < 16; i++) {                                   /* column j of the tile is row 64 p + j of the level-1 LL (plane_l1: plane A is what the other quarters read) */
 		const int j = wv * 16 + i;
-		uint32_t *dst = reinterpret_cast<uint32_t *>(pl + (size_t)(64 * p + j) * DW);
+		uint32_t *dst = reinterpret_cast<uint32_t *>(l1 + (size_t)(64 * p + j) * DW);
 #pragma unroll
 		for (int u = 0; u < 2; u++) {
 			const int k = lane + 64 * u;
@@ -1878,7 +1884,7 @@ __global__ __launch_bounds__(256) void k_dec_marks(DecWs ws)
 	if (img >= ws.n) return;
 	DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (m->status) return;
-	const int16_t *c = plane_a(ws, img);
+	const int16_t *c = plane_l1(ws, img);
 	uint16_t *marks = ws.buf<uint16_t>(D_MARKS, img);
 	uint16_t *rowstart = mark_rows(ws, img);                        /* [257]: index of the first mark of row i (the list is in row order) */
 	int total = 0;
@@ -2159,7 +2165,8 @@ __global__ void k_dec_colour_probe(const uint8_t *__restrict__ yuv, uint8_t *__r
 #define FM (FR / 2 + 1)              /* values of m a band computes: r0/2 - 1 .. r0/2 + FR/2 - 1 */
 #define F_T_BYTES (2 * DH * FBP * 2)
 #define F_LDS_BYTES (F_T_BYTES + FR * DW + 2 * (FR / 2 + 1) * DH)   /* T, the luma bytes, the chroma rows: 31 KB, five bands to a CU */
-__global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int dev_stop /* developer builds: end every band after phase dev_stop (0: run it all) */)
+__global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int dev_stop /* developer builds: end every band after phase dev_stop (0: run it all) */,
+                                                  int slice /* -1: production; else the band (nhw_slice.h) */)
 {
 #ifdef NHW_DEV
 #define F_STOP(i) do { if (dev_stop == (i)) return; } while (0)
@@ -2176,11 +2183,12 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 		const int nb = DW / FR, total = nb * ws.n, w = blockIdx.x, per = total >> 3;
 		const int item = (total & 7) ? w : (w & 7) * per + (w >> 3);            /* workgroup w runs on XCD w % 8: consecutive items stay on one XCD */
 		img = item / nb; band = item % nb;
+		if (slice >= 0) { img = w; band = slice; }
 	}
 	const DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (m->status) return;
 	const int q = m->q, r0 = FR * band, m0 = r0 / 2 - 1;                       /* m0: first m of the band (-1 in band 0: skipped) */
-	const int16_t *A = plane_a(ws, img);
+	const int16_t *A = plane_a(ws, img), *L1 = plane_l1(ws, img);              /* the detail bands; the level-1 LL */
 
 	for (int k = tid; k < 2 * (FR / 2 + 1) * (DH / 16); k += 256) {
 		const int pl = k / ((FR / 2 + 1) * (DH / 16)), rem = k % ((FR / 2 + 1) * (DH / 16)), rr = rem / (DH / 16), o = rem % (DH / 16);
@@ -2222,7 +2230,7 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 		} else {
 			lo[0] = 0; lo[11] = 0;
 #pragma unroll
-			for (int e = 0; e <= FM; e++) lo[1 + e] = A[(ptrdiff_t)(m0 + e) * DW + k];
+			for (int e = 0; e <= FM; e++) lo[1 + e] = L1[(ptrdiff_t)(m0 + e) * DW + k];
 		}
 #pragma unroll
 		for (int mi = 0; mi < FM; mi++) {
@@ -2396,6 +2404,8 @@ struct nhw_dec {
 	uint16_t *vlc_table;         /* the prefix code's two-level lookup table (k_dec_vlc_table), 2.5 KB */
 	int chroma_fork;
 	int stop_after;
+	bool l1_moved;               /* the last batch ran level 2 of the luma whole: the level-1 LL is in plane_l1 (D_B), not plane A (nhw_dec_debug_read) */
+	int slice_order;             /* debug: the forced slice order of the kernels that split a file (nhw_slice.h; 0 = production) */
 	hipEvent_t ev[4];         /* start, after the entropy stages, around the final reconstruction kernel (= end) */
 	bool timed;
 	/* host convenience path */
@@ -2467,6 +2477,7 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 }
 
 extern "C" void nhw_dec_debug_stop_after(nhw_dec *d, int stage) { if (d) d->stop_after = stage; }
+extern "C" int nhw_dec_debug_slice_order(nhw_dec *d, int mode) { if (!d || mode < 0 || mode > 2) return NHW_E_ARG; d->slice_order = mode; return NHW_OK; }
 
 /* internal (nhw_api.hip's distortion search; not in the public header): what a caller needs to know about a handle before it hands it work */
 void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after)
@@ -2487,6 +2498,11 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 	HIPCHK(hipSetDevice(d->device));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(dst, d->ws.base + d->ws.off[what] + (size_t)img * k_dec_bytes[what], bytes, hipMemcpyDeviceToHost));
+	if (what == D_A && d->l1_moved)                                 /* plane A as the stage checks know it: with the level-1 LL where the reference keeps it */
+		for (int r = 0; r < DH && 4096 + (size_t)r * DW * 2 < bytes; r++) {
+			const size_t at = 4096 + (size_t)r * DW * 2, len = bytes - at < (size_t)DH * 2 ? bytes - at : (size_t)DH * 2;
+			HIPCHK(hipMemcpy((uint8_t *)dst + at, d->ws.base + d->ws.off[D_B] + (size_t)img * k_dec_bytes[D_B] + at, len, hipMemcpyDeviceToHost));
+		}
 	return NHW_OK;
 }
 
@@ -2496,10 +2512,12 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { g_derr = "bad argument"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(d->device));                              /* the handle's device, whatever the calling thread had current */
 	hipStream_t s = stream ? (hipStream_t)stream : d->own_stream;
+	const NhwSliceScope slices(d->slice_order);
 	DecWs ws = d->ws;
 	ws.n = n; ws.blob = (const uint8_t *)d_nhw; ws.blob_off = d_off; ws.blob_len = d_len; ws.dense = d->stop_after != 0;
 	int stage = 0;
 	d->timed = false;
+	d->l1_moved = false;
 	const bool fork = (d->chroma_fork & 2) && !d->stop_after;          /* the chroma sequence beside the luma one */
 	const bool fork_e = (d->chroma_fork & 1) && !d->stop_after;        /* the two entropy branches side by side */
 	hipStream_t cs = fork ? d->chroma_stream : s;
@@ -2511,9 +2529,9 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 	/* Two entropy branches that only meet at the expansion: the side streams (LL2 DPCM, position lists; latency-bound scans) on the caller's
 	 * stream, the prefix-code walk and the un-zig-zag on the second one. */
 	if (fork_e) { HIPCHK(hipEventRecord(d->fork_ev, s)); HIPCHK(hipStreamWaitEvent(es, d->fork_ev, 0)); }
-	k_dec_parse<<<4 * n, 64, 0, s>>>(ws);
+	nhw_slices(4, [&](int sl) { k_dec_parse<<<sl < 0 ? 4 * n : n, 64, 0, s>>>(ws, sl); });
 	STAGE_END();                                                                  /* 1 */
-	k_dec_vlc<<<2 * n, 64, 0, es>>>(ws, d->vlc_table);
+	nhw_slices(2, [&](int sl) { k_dec_vlc<<<sl < 0 ? 2 * n : n, 64, 0, es>>>(ws, d->vlc_table, sl); });
 	if (fork_e) { HIPCHK(hipEventRecord(d->join_ev, es)); HIPCHK(hipStreamWaitEvent(s, d->join_ev, 0)); }
 	if (fork) { HIPCHK(hipEventRecord(d->fork_ev, s)); HIPCHK(hipStreamWaitEvent(cs, d->fork_ev, 0)); }   /* chroma goes on once both branches are in */
 	k_dec_verdict<<<(n + 255) / 256, 256, 0, s>>>(ws);
@@ -2534,8 +2552,9 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 		/* level 2 of the luma: shrink, synthesis, residual lists on A's top-left 256 x 256 -> the level-1 LL in the same place */
 		const int upto = d->stop_after == 4 ? 1 : d->stop_after == 5 ? 2 : 3;
 		static const int quarters = getenv("NHW_DEC_L2Q") ? atoi(getenv("NHW_DEC_L2Q")) : 1;
-		if (upto == 3 && quarters) k_dec_luma_l2q<<<4 * ((n + 7) & ~7), 256, 0, s>>>(ws, n);
+		if (upto == 3 && quarters) nhw_slices(4, [&](int sl) { k_dec_luma_l2q<<<sl < 0 ? 4 * ((n + 7) & ~7) : n, 256, 0, s>>>(ws, n, sl); });
 		else k_dec_luma_l2<<<n < SYNTH_WGS ? n : SYNTH_WGS, 1024, 256 * 258 * sizeof(int16_t), s>>>(ws, n, upto);
+		d->l1_moved = upto == 3;
 	}
 	STAGE_END();                                                                  /* 4 (the block as the shrink leaves it) */
 	STAGE_END();                                                                  /* 5 (after the synthesis) */
@@ -2564,7 +2583,7 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 #ifdef NHW_DEV
 		if (const char *e = getenv("NHW_FINAL_STOP")) dev_stop = atoi(e);
 #endif
-		k_dec_final<<<(DW / FR) * n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop);
+		nhw_slices(DW / FR, [&](int sl) { k_dec_final<<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl); });
 	}
 	EV(3);
 	d->timed = true;

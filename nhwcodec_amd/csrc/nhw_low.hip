@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "nhw_ws.h"
+#include "nhw_slice.h"
 
 #define DEVI __device__ static __forceinline__
 #define DEVN __device__ static
@@ -398,18 +399,22 @@ DEVI int final_pair(const PfP &pp, const int16_t *km, int f0, int f1, int p, int
 /* Passes A..C of the quality 1..16 luma pre-filter as THREE kernels (round 6; until round 5 one kernel, k_low_machine, did all of it a row at
  * a time on one wavefront: its vector stages -- pass A, codes, apply -- and its scalar chain took turns, and each waited for the other).
  *
- *   k_low_pre     pass A (contrast map, :601-764) with its few order-dependent cells, the picture copy with the q <= 14 smoothing (:780-807),
- *                 and the CODE of every pixel pair (four threshold tests of its two map cells: all the pair machine ever asks about the
- *                 picture) as ONE stream of 510 x 255 bytes in pass B's order -- the reference's pass B (:770-1992) walks the rows one after
- *                 the other with its counters running on, so a row's end means nothing to the machine;
- *   k_low_chain   the pair machine and nothing else: codes in, three answer bits a pair out.  Bursts run across row ends;
- *   k_low_apply   the answers applied to the picture and the map (pass B's picture side, :840-917 / :996-1001 / :1912-1990), the marker
- *                 classes, and pass C (:1994-2310) of the rows that hold a marker, in row order (its counters run on from marker to marker).
+ *   k_low_pre     pass A (contrast map, :601-764) but for its few order-dependent cells, a wavefront a band of 32 rows, and the five
+ *                 candidate masks a row that k_low_mapfix (a wavefront a picture) walks to settle those cells;
+ *   k_low_chain   the pair machine: the CODE of every pixel pair (four threshold tests of its two map cells: all the machine ever asks about
+ *                 the picture), made on the fly in pass B's order -- the reference's pass B (:770-1992) walks the rows one after the other
+ *                 with its counters running on, so a row's end means nothing to the machine -- and three answer bits a pair out, a byte a
+ *                 pair.  Bursts run across row ends.  It also copies, for every band of k_low_apply, the map cells of pair 254 of the row
+ *                 above the band (see there);
+ *   k_low_apply   the picture copy with the q <= 14 smoothing (:780-807), the answers applied to the picture and the map (pass B's picture
+ *                 side, :840-917 / :996-1001 / :1912-1990) and the list of rows that hold a marker, a wavefront a band of 32 rows;
+ *                 k_low_markrows (pass C of the marker rows, in row order: its counters run on from marker to marker) and k_low_marks
+ *                 (pass C of the other rows and pass D) follow.
  *
  * What makes the split legal: a row's codes are made from the map as pass A left it (source plane + pass A's own state only) and the
  * machine's answers touch the map only behind the chain, so row r + 1's codes never depend on row r's answers.
  * src: the luma plane as the colour kernel wrote it (read only); y: the filtered plane (every row is written); km: the contrast map.
- * Codes and answers: B_KEEP (the q >= 22 plane, free below): CH_BYTES of codes, then CH_BYTES of answers. */
+ * B_KEEP (the q >= 22 plane, free below): CH_BYTES of answers, then k_low_chain's PRE_NB words of entry cells for k_low_apply. */
 #define CH_N ((W - 2) * 255)                                           /* pixel pairs of a picture in pass B's order: rows 1 .. 510, pairs 0 .. 254 (cells 1 + 2 p, 2 + 2 p) */
 #define CH_CHUNKS ((CH_N + 255) / 256)
 #define CH_BYTES (CH_CHUNKS * 256)
@@ -424,13 +429,13 @@ DEVI int final_pair(const PfP &pp, const int16_t *km, int f0, int f1, int p, int
  * and the marker counters (MapState), which only the few candidate cells move: those are left to k_low_mapfix, with the cells marked here
  * for every state the counters can be in (five bit masks a row). */
 __global__ __launch_bounds__(64) void k_low_pre(const int16_t *__restrict__ srcb, size_t src_stride, int16_t *__restrict__ kmb, size_t km_stride,
-                                                uint8_t *__restrict__ maskb, size_t mask_stride, int q, int dbg)
+                                                uint8_t *__restrict__ maskb, size_t mask_stride, int q, int dbg, int slice /* -1: production; else the band (nhw_slice.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t s_src[3][W];
 	__shared__ __attribute__((aligned(16))) int16_t s_km[W + 8];
 	__shared__ __attribute__((aligned(16))) int16_t s_vb[W];              /* pass A's base values */
 	__shared__ int s_misc[4];
-	const int lane = threadIdx.x, band = blockIdx.x, img = blockIdx.y;
+	const int lane = threadIdx.x, band = slice < 0 ? (int)blockIdx.x : slice, img = blockIdx.y;
 	const PfP pp = pf_params(q);
 	const int c0 = lane * 8;
 	const int16_t *src = srcb + (size_t)img * src_stride;
@@ -656,6 +661,10 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 	/* the codes of my four pairs of chunk k, made from their map cells (pair n of the stream: row 1 + n / 255, cells 1 + 2 (n % 255) and the next;
 	 * 0 behind the stream's end): all the machine ever asks about the picture (nhw_low_machine.h) */
 	const PfP pp = pf_params(q);
+	if (threadIdx.x >= 1 && threadIdx.x < PRE_NB) {                     /* for k_low_apply's band b: pair 254 of row PRE_RB b, the band above's last, before that band rewrites it */
+		const int16_t *c = km + (size_t)(PRE_RB * threadIdx.x) * W + W - 3;
+		reinterpret_cast<uint32_t *>(actb + (size_t)img * act_stride + CH_BYTES)[threadIdx.x] = (uint32_t)(uint16_t)c[0] | ((uint32_t)(uint16_t)c[1] << 16);
+	}
 	auto load_codes = [&](int k) -> uint32_t {
 		uint32_t w = 0;
 		for (int j = 0; j < 4; j++) {
@@ -826,20 +835,23 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 /* Pass B's picture side, a wavefront a band of 32 rows: the picture copy with the q <= 14 smoothing (:566, :780-807), the machine's answers
  * applied to the picture, the map and the flags (pair_apply: :840-917 / :996-1001 / :1912-1924), the tail rules (:1927-1990), and the list
  * of rows that hold a marker (pass C walks those in row order: k_low_markrows).  What ties the rows together here is one bit, the tail
- * rules' flag: it is a function of the pair before alone, so a band takes it from the last pair of the row above (one pair_apply).
+ * rules' flag: it is a function of the pair before alone, so a band takes it from the last pair of the row above (one pair_apply) -- on
+ * that pair's map cells as k_low_chain copied them: the map row itself is the band above's, rewritten with its pass-B values in this launch.
  * act: the chain's answers (a byte a pair, stream order); km in: as passes A left it; out: y, km, flags as pass B leaves them. */
 __global__ __launch_bounds__(64) void k_low_apply(const int16_t *__restrict__ srcb, size_t src_stride, int16_t *__restrict__ yb, size_t y_stride, int16_t *__restrict__ kmb, size_t km_stride,
-                                                  uint8_t *__restrict__ sob, size_t so_stride, const uint8_t *__restrict__ actb, size_t act_stride, int q, int dbg)
+                                                  uint8_t *__restrict__ sob, size_t so_stride, const uint8_t *__restrict__ actb, size_t act_stride, int q, int dbg,
+                                                  int slice /* -1: production; else the band (nhw_slice.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t s_src[3][W];
 	__shared__ __attribute__((aligned(16))) int16_t s_km[W + 8];
-	const int lane = threadIdx.x, band = blockIdx.x, img = blockIdx.y;
+	const int lane = threadIdx.x, band = slice < 0 ? (int)blockIdx.x : slice, img = blockIdx.y;
 	const PfP pp = pf_params(q);
 	const int c0 = lane * 8;
 	int16_t *yo = yb + (size_t)img * y_stride;
 	int16_t *kmo = kmb + (size_t)img * km_stride;
 	uint8_t *soo = sob + (size_t)img * so_stride;
 	const uint8_t *act = actb + (size_t)img * act_stride;
+	const uint32_t *entry = reinterpret_cast<const uint32_t *>(act + CH_BYTES);   /* k_low_chain: cells 509, 510 of row PRE_RB b as pass A left them */
 	const int16_t *src = srcb + (size_t)img * src_stride;
 	const int r0 = 1 + PRE_RB * band, r1 = r0 + PRE_RB - 1 < W - 2 ? r0 + PRE_RB - 1 : W - 2;
 	for (int k = lane; k < W + 8; k += 64) s_km[k] = 0;
@@ -863,14 +875,11 @@ __global__ __launch_bounds__(64) void k_low_apply(const int16_t *__restrict__ sr
 	};
 	int prev_big = 0;                                                  /* wave-uniform: the tail rules' flag behind the last pair of the row above */
 	if (r0 > 1 && pp.tail_rules && !(dbg & 2)) {
-		*reinterpret_cast<uint4 *>(&s_km[c0]) = *reinterpret_cast<const uint4 *>(kmo + (size_t)(r0 - 1) * W + c0);
-		const uint32_t aw = load_act(r0 - 1);
-		__syncthreads();
-		int kc[9], e0 = 0, e1 = 0, d0 = 0, d1 = 0, f0 = 0, f1 = 0;
-		cells9(kc);
-		pair_apply(pp, (int)((aw >> 16) & 7), kc[5], kc[6], e0, e1, d0, d1, f0, f1);      /* lane 63's third pair is pair 254 */
+		/* not from the map: row r0 - 1 is the band above's last row, which that band overwrites with its pass-B values in this launch */
+		const uint32_t aw = load_act(r0 - 1), cw = entry[band];
+		int k0 = (int16_t)(cw & 0xFFFF), k1 = (int16_t)(cw >> 16), e0 = 0, e1 = 0, d0 = 0, d1 = 0, f0 = 0, f1 = 0;
+		pair_apply(pp, (int)((aw >> 16) & 7), k0, k1, e0, e1, d0, d1, f0, f1);          /* lane 63's third pair is pair 254 */
 		prev_big = __builtin_amdgcn_readlane(tail_flag(e0, e1), 63);
-		__syncthreads();
 	}
 	uint4 nk = *reinterpret_cast<const uint4 *>(kmo + (size_t)r0 * W + c0), ns = *reinterpret_cast<const uint4 *>(src + (size_t)(r0 + 1) * W + c0);
 	uint32_t na = load_act(r0);
@@ -1051,6 +1060,7 @@ __global__ __launch_bounds__(64) void k_low_markrows(int16_t *__restrict__ yb, s
  * (Round 2 ran pass C on the chain lane of the pre-filter kernel, 30 % of its 271 ms, and pass D as a kernel over the three planes: 21 GB;
  * the first row-parallel form -- LDS loads and compares at every visit -- took 15.5 ms per batch at quality 10.) */
 #define MK_R 192                                                       /* lanes: 191 rows + the row below them */
+#define MK_NW ((W - 2 + MK_R - 2) / (MK_R - 1))                         /* windows of k_low_marks a picture (overlapping by one row) */
 #define MK_A 48                                                        /* columns a window advances */
 #define MK_BP 68                                                       /* pitch of the byte planes */
 namespace {
@@ -1070,13 +1080,13 @@ struct MkFx {
 };
 }
 __global__ __launch_bounds__(MK_R) void k_low_marks(int16_t *__restrict__ yb, size_t y_stride, const int16_t *__restrict__ kmb, size_t km_stride,
-                                                    uint8_t *__restrict__ sob, size_t so_stride, int q, int dbg)
+                                                    uint8_t *__restrict__ sob, size_t so_stride, int q, int dbg, int slice /* -1: production; else the window (nhw_slice.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int8_t own[MK_R * MK_BP], upd[MK_R * MK_BP];   /* what a lane adds to its row / to the row above */
 	__shared__ uint64_t s_upflag[MK_R + 1], s_updirty[MK_R + 1];          /* of the lane's additions to the row above: flags raised, cells touched */
 	__shared__ uint32_t s_mask[16];
 	const int tid = threadIdx.x, img = blockIdx.y;
-	const int R0 = 1 + (MK_R - 1) * blockIdx.x;                        /* rows R0 .. R0 + 190 are this workgroup's; the last lane walks pass C of the row below them for what it adds to the last one */
+	const int R0 = 1 + (MK_R - 1) * (slice < 0 ? (int)blockIdx.x : slice);                       /* rows R0 .. R0 + 190 are this workgroup's; the last lane walks pass C of the row below them for what it adds to the last one */
 	const int r = R0 + tid;
 	const PfP pp = pf_params(q);
 	const int sharp = pp.sharp, s2 = pp.s2, half = pp.half;
@@ -1544,17 +1554,23 @@ int nhw_launch_low_prefilter(const int16_t *src, size_t src_stride, int16_t *y, 
 	{ const char *e = getenv("NHW_LOW_DBG"); dbg = e ? atoi(e) : 0; }
 #endif
 	auto head = [&](int i0, int m, hipStream_t st) {                    /* pass A of images i0 .. i0 + m - 1 */
-		k_low_pre<<<dim3(PRE_NB, m), 64, 0, st>>>(src + (size_t)i0 * src_stride, src_stride, km + (size_t)i0 * km_stride, km_stride, reinterpret_cast<uint8_t *>(tab) + (size_t)i0 * tab_stride, tab_stride, q, dbg | force);
+		nhw_slices(PRE_NB, [&](int sl) {
+			k_low_pre<<<dim3(sl < 0 ? PRE_NB : 1, m), 64, 0, st>>>(src + (size_t)i0 * src_stride, src_stride, km + (size_t)i0 * km_stride, km_stride, reinterpret_cast<uint8_t *>(tab) + (size_t)i0 * tab_stride, tab_stride, q, dbg | force, sl);
+		});
 		k_low_mapfix<<<m, 64, 0, st>>>(km + (size_t)i0 * km_stride, km_stride, reinterpret_cast<const uint8_t *>(tab) + (size_t)i0 * tab_stride, tab_stride, so + (size_t)i0 * so_stride, so_stride, q, dbg);
 	};
 	auto machine = [&](int i0, int m, hipStream_t st) {                 /* pass B's machine */
 		k_low_chain<<<m, 128, 0, st>>>(km + (size_t)i0 * km_stride, km_stride, chain + (size_t)i0 * chain_stride, chain_stride, q, dbg);
 	};
 	auto rest = [&](int i0, int m, hipStream_t st) {                    /* pass B's picture side, passes C and D */
-		k_low_apply<<<dim3(PRE_NB, m), 64, 0, st>>>(src + (size_t)i0 * src_stride, src_stride, y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride,
-		                                           chain + (size_t)i0 * chain_stride, chain_stride, q, dbg);
+		nhw_slices(PRE_NB, [&](int sl) {
+			k_low_apply<<<dim3(sl < 0 ? PRE_NB : 1, m), 64, 0, st>>>(src + (size_t)i0 * src_stride, src_stride, y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride,
+			                                                          chain + (size_t)i0 * chain_stride, chain_stride, q, dbg, sl);
+		});
 		k_low_markrows<<<m, 64, 0, st>>>(y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride, q);
-		k_low_marks<<<dim3((W - 2 + MK_R - 2) / (MK_R - 1), m), MK_R, 0, st>>>(y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride, q, dbg);
+		nhw_slices(MK_NW, [&](int sl) {
+			k_low_marks<<<dim3(sl < 0 ? MK_NW : 1, m), MK_R, 0, st>>>(y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride, q, dbg, sl);
+		});
 	};
 	if (parts <= 1 || !aux || !ev) { head(0, n, s); machine(0, n, s); rest(0, n, s); return (int)hipGetLastError(); }
 #define LOWCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
