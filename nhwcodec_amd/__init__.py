@@ -658,8 +658,7 @@ class Decoder:
     """One decoder handle on one GPU: mirror of the reference's decode_image + write_image_bmp
     (decoder/nhw_decoder.c:54, decoder/nhw_decoder_cli.c:108) for batches of .nhw files."""
 
-    def __init__(self, device: int = 0, max_batch: int = 64, device_only: bool = False):
-        """device_only: the handle is for encode_device() -- no staging buffers of the host path (nhw_enc_create_ex, NHW_CREATE_DEVICE_ONLY)"""
+    def __init__(self, device: int = 0, max_batch: int = 64):
         import torch
         if not torch.cuda.is_available():
             raise NhwError("no GPU visible: nhwcodec_amd has no CPU path")

@@ -21,16 +21,12 @@
  * Everything is int16/uint8 arithmetic; the only floating point is the colour matrix (compiled with
  * -ffp-contract=off like the rest of the library).  No stage falls back to the host.
  */
-#include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <climits>
-#include <string>
-#include <vector>
 
-#include "../../include/nhw_hip.h"
-#include "nhw_slice.h"
+#include "nhw_host.h"
 
 #define DW 512
 #define DH 256
@@ -439,7 +435,7 @@ DEV int poslist_wave(const uint8_t *list, int len, T *pos, int cap, int row_step
 /* One wavefront per workgroup and side stream -- role 0: the LL2 DPCM bytes (+ the chroma bit planes on top of them, + the file's
  * header record for the kernels behind); roles 1..3: the position lists res1, res3, res5 + res6 with their bit planes -- the long role
  * first for the whole batch.  (As four wavefronts of one workgroup the three list walks waited at a barrier for the LL2 walk.) */
-__global__ __launch_bounds__(64) void k_dec_parse(DecWs ws, int slice /* -1: production; else the role (nhw_slice.h) */)
+__global__ __launch_bounds__(64) void k_dec_parse(DecWs ws, int slice /* -1: production; else the role (nhw_host.h) */)
 {
 	__shared__ DecMeta sm;
 	__shared__ uint8_t hdr[HDR_STAGE];
@@ -791,7 +787,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc_table(uint16_t *tab /* [256 + 10
 /* One wavefront per workgroup and stream: the luma streams of the batch first (they are the long ones), then the chroma streams -- as two
  * wavefronts of one workgroup the short chroma walk kept its half of the workgroup's LDS until the luma walk was through, and LDS is what
  * bounds the number of resident walks. */
-__global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__restrict__ table, int slice /* -1: production; else the stream (nhw_slice.h) */)
+__global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__restrict__ table, int slice /* -1: production; else the stream (nhw_host.h) */)
 {
 	__shared__ uint16_t lut[256 + 16 * 64];
 	__shared__ uint16_t book1[354];
@@ -1570,7 +1566,7 @@ __global__ __launch_bounds__(1024) void k_dec_luma_l2(DecWs ws, int items, int u
  * it reads (from the values as they were, all before any is applied), filters in place, adds the residuals whose plane row is its own and
  * writes 64 whole rows of the plane.  Block b -> file ((b >> 5) << 3) | (b & 7), quarter (b >> 3) & 3 (a file's quarters on one XCD). */
 #define LQ_LS 74                      /* pitch of a row of the tile in shorts (37 dwords: column walks on 32 banks) */
-__global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int slice /* -1: production; else the quarter (nhw_slice.h) */)
+__global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int slice /* -1: production; else the quarter (nhw_host.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t T[DH * LQ_LS];
 	constexpr int S = DH, HLF = S / 2;
@@ -2166,7 +2162,7 @@ __global__ void k_dec_colour_probe(const uint8_t *__restrict__ yuv, uint8_t *__r
 #define F_T_BYTES (2 * DH * FBP * 2)
 #define F_LDS_BYTES (F_T_BYTES + FR * DW + 2 * (FR / 2 + 1) * DH)   /* T, the luma bytes, the chroma rows: 31 KB, five bands to a CU */
 __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int dev_stop /* developer builds: end every band after phase dev_stop (0: run it all) */,
-                                                  int slice /* -1: production; else the band (nhw_slice.h) */)
+                                                  int slice /* -1: production; else the band (nhw_host.h) */)
 {
 #ifdef NHW_DEV
 #define F_STOP(i) do { if (dev_stop == (i)) return; } while (0)
@@ -2391,13 +2387,12 @@ __global__ __launch_bounds__(256) void k_dec_status(DecWs ws, int32_t *status, i
 
 /* ---------------------------------------------------------------------------------------------- host side */
 static thread_local std::string g_derr;
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s:%d %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); g_derr = b_; return NHW_E_HIP; } } while (0)
+#define NHW_ERR g_derr
 extern "C" const char *nhw_dec_last_error(void) { return g_derr.c_str(); }
 
 struct nhw_dec {
 	int device, max_batch;
 	DecWs ws;
-	size_t slab_bytes;
 	hipStream_t own_stream;
 	hipStream_t chroma_stream;   /* the chroma sequence runs here, next to the luma one (NHW_CHROMA_FORK=0: behind it, on the caller's stream) */
 	hipEvent_t fork_ev, join_ev;
@@ -2405,19 +2400,22 @@ struct nhw_dec {
 	int chroma_fork;
 	int stop_after;
 	bool l1_moved;               /* the last batch ran level 2 of the luma whole: the level-1 LL is in plane_l1 (D_B), not plane A (nhw_dec_debug_read) */
-	int slice_order;             /* debug: the forced slice order of the kernels that split a file (nhw_slice.h; 0 = production) */
+	int slice_order;             /* debug: the forced slice order of the kernels that split a file (nhw_host.h; 0 = production) */
 	hipEvent_t ev[4];         /* start, after the entropy stages, around the final reconstruction kernel (= end) */
 	bool timed;
-	/* host convenience path */
-	uint8_t *d_blob; size_t blob_cap;
+	/* host convenience path: the files (grow-only) and, for max_batch files, their offsets and lengths, the pictures, status and quality */
+	GrowBuf blob;
 	uint64_t *d_off; uint32_t *d_len; uint8_t *d_out; int32_t *d_status; int32_t *d_quality;
 	/* nhw_dec_pictures: the cropped pictures, their descriptor table and the per-tile offsets, lengths and status, grow-only */
-	uint8_t *pic_px; size_t pic_cap;
-	void *pic_desc; size_t pic_desc_cap;
-	void *pic_tiles; size_t pic_tiles_cap;
+	GrowBuf pic_px, pic_desc, pic_tiles;
 };
 
-extern "C" void nhw_dec_destroy(nhw_dec *d);
+static DevSet host_set(nhw_dec *d)
+{
+	const size_t mb = (size_t)d->max_batch;
+	return { dev_buf(d->d_off, mb + 1), dev_buf(d->d_len, mb + 1), dev_buf(d->d_out, mb * NHW_IMG_BYTES), dev_buf(d->d_status, mb), dev_buf(d->d_quality, mb) };
+}
+
 extern "C" int nhw_dec_create(int device, int max_batch, nhw_dec **out)
 {
 	if (!out || max_batch < 1) { g_derr = "bad argument"; return NHW_E_ARG; }
@@ -2427,7 +2425,6 @@ extern "C" int nhw_dec_create(int device, int max_batch, nhw_dec **out)
 	d->device = device; d->max_batch = max_batch;
 	size_t at = 0;
 	for (int b = 0; b < D_COUNT; b++) { d->ws.off[b] = at; at += k_dec_bytes[b] * (size_t)max_batch; at = (at + 255) & ~(size_t)255; }
-	d->slab_bytes = at;
 	const int rc = [&]() -> int {                                  /* a failure half-way leaves nothing behind: the handle is destroyed below */
 		size_t free_b = 0, total_b = 0;
 		HIPCHK(hipMemGetInfo(&free_b, &total_b));
@@ -2458,15 +2455,8 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 	if (!d) return;
 	(void)hipSetDevice(d->device);
 	if (d->ws.base) (void)hipFree(d->ws.base);
-	if (d->d_blob) (void)hipFree(d->d_blob);
-	if (d->d_off) (void)hipFree(d->d_off);
-	if (d->d_len) (void)hipFree(d->d_len);
-	if (d->d_out) (void)hipFree(d->d_out);
-	if (d->d_status) (void)hipFree(d->d_status);
-	if (d->d_quality) (void)hipFree(d->d_quality);
-	if (d->pic_px) (void)hipFree(d->pic_px);
-	if (d->pic_desc) (void)hipFree(d->pic_desc);
-	if (d->pic_tiles) (void)hipFree(d->pic_tiles);
+	dev_free(host_set(d));
+	for (GrowBuf *g : { &d->blob, &d->pic_px, &d->pic_desc, &d->pic_tiles }) nhw_grow_free(*g);
 	if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
 	if (d->chroma_stream) (void)hipStreamDestroy(d->chroma_stream);
 	if (d->vlc_table) (void)hipFree(d->vlc_table);
@@ -2479,7 +2469,7 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 extern "C" void nhw_dec_debug_stop_after(nhw_dec *d, int stage) { if (d) d->stop_after = stage; }
 extern "C" int nhw_dec_debug_slice_order(nhw_dec *d, int mode) { if (!d || mode < 0 || mode > 2) return NHW_E_ARG; d->slice_order = mode; return NHW_OK; }
 
-/* internal (nhw_api.hip's distortion search; not in the public header): what a caller needs to know about a handle before it hands it work */
+/* internal (the encoder's distortion searches; nhw_host.h, not the public header): what a caller needs to know about a handle before it hands it work */
 void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after)
 {
 	*device = d->device; *max_batch = d->max_batch; *stop_after = d->stop_after;
@@ -2610,23 +2600,8 @@ extern "C" int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t)
  * decoded pictures of max_batch files */
 static int host_buffers(nhw_dec *d, size_t total)
 {
-	if (total + 64 > d->blob_cap) {
-		if (d->d_blob) (void)hipFree(d->d_blob);
-		d->d_blob = nullptr; d->blob_cap = 0;                      /* nothing dangling if the allocation below fails */
-		const size_t want = total + (total >> 2) + (1u << 20);
-		HIPCHK(hipMalloc(&d->d_blob, want));
-		d->blob_cap = want;
-	}
-	if (!d->d_off) {                                               /* all five or none: a half-made set would hand null pointers to the next call */
-		void *b[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
-		const size_t bytes[5] = { ((size_t)d->max_batch + 1) * 8, ((size_t)d->max_batch + 1) * 4, (size_t)d->max_batch * NHW_IMG_BYTES, (size_t)d->max_batch * 4, (size_t)d->max_batch * 4 };
-		hipError_t err = hipSuccess;
-		for (int i = 0; i < 5 && err == hipSuccess; i++) err = hipMalloc(&b[i], bytes[i]);
-		if (err != hipSuccess) { for (int i = 0; i < 5; i++) if (b[i]) (void)hipFree(b[i]); HIPCHK(err); }
-		d->d_off = (decltype(d->d_off))b[0]; d->d_len = (decltype(d->d_len))b[1]; d->d_out = (decltype(d->d_out))b[2];
-		d->d_status = (decltype(d->d_status))b[3]; d->d_quality = (decltype(d->d_quality))b[4];
-	}
-	return NHW_OK;
+	if (total + 64 > d->blob.cap) HIPCHK(nhw_grow(d->blob, total + (total >> 2) + (1u << 20)));   /* 64 spare bytes at least; a quarter and 1 MiB more when it grows, so that batches of a similar size do not reallocate */
+	return d->d_off ? NHW_OK : dev_alloc(host_set(d), nullptr, d->max_batch, g_derr);   /* all five or none: a half-made set would hand null pointers to the next call */
 }
 
 /* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1]. */
@@ -2644,13 +2619,13 @@ extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off
 		const uint64_t l = off[i + 1] - off[i];
 		len[i] = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
 	}
-	hipError_t e1 = hipMemcpyAsync(d->d_blob, nhw + off[0], total, hipMemcpyHostToDevice, d->own_stream);
+	hipError_t e1 = hipMemcpyAsync(d->blob.p, nhw + off[0], total, hipMemcpyHostToDevice, d->own_stream);
 	hipError_t e2 = hipMemcpyAsync(d->d_off, rel, (size_t)n * 8, hipMemcpyHostToDevice, d->own_stream);
 	hipError_t e4 = hipMemcpyAsync(d->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, d->own_stream);
 	hipError_t e3 = hipStreamSynchronize(d->own_stream);
 	free(rel);
 	HIPCHK(e1); HIPCHK(e2); HIPCHK(e4); HIPCHK(e3);
-	const int rc = nhw_dec_batch_device(d, d->d_blob, d->d_off, d->d_len, n, d->d_out, d->d_status, d->d_quality, d->own_stream);
+	const int rc = nhw_dec_batch_device(d, d->blob.p, d->d_off, d->d_len, n, d->d_out, d->d_status, d->d_quality, d->own_stream);
 	if (rc) return rc;
 	HIPCHK(hipMemcpyAsync(bgr, d->d_out, (size_t)n * NHW_IMG_BYTES, hipMemcpyDeviceToHost, d->own_stream));
 	HIPCHK(hipMemcpyAsync(status, d->d_status, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
@@ -2660,10 +2635,6 @@ extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off
 }
 
 /* ---------------------------------------------------------------------------------------------- pictures of any size */
-hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s);
-int nhw_container_parse(const uint8_t *c, size_t len, uint32_t *width, uint32_t *height, int *tiles, const uint8_t **dir);
-hipError_t nhw_grow(void **p, size_t *cap, size_t bytes);
-
 /* Parse every container on the host; upload the blob once (a container's tile files lie back to back, so the decoder's offsets and lengths
  * come from its directory); decode the tiles in chunks of max_batch into the host path's picture slots and crop each chunk into the
  * picture buffer (k_untile_crop); then bring back the pictures whose tiles all decoded. */
@@ -2697,22 +2668,22 @@ extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t 
 	const int tiles = (int)toff.size(), np = (int)desc.size();
 	HIPCHK(hipSetDevice(d->device));
 	{ const int rc = host_buffers(d, (size_t)(off[n] - off[0])); if (rc) return rc; }
-	HIPCHK(nhw_grow((void **)&d->pic_px, &d->pic_cap, bytes));
-	HIPCHK(nhw_grow(&d->pic_desc, &d->pic_desc_cap, (size_t)np * sizeof(nhw_picture)));
-	HIPCHK(nhw_grow(&d->pic_tiles, &d->pic_tiles_cap, (size_t)tiles * 16));
-	for (nhw_picture &p : desc) p.addr += (uint64_t)(uintptr_t)d->pic_px;
-	uint64_t *d_toff = (uint64_t *)d->pic_tiles;
+	HIPCHK(nhw_grow(d->pic_px, bytes));
+	HIPCHK(nhw_grow(d->pic_desc, (size_t)np * sizeof(nhw_picture)));
+	HIPCHK(nhw_grow(d->pic_tiles, (size_t)tiles * 16));
+	for (nhw_picture &p : desc) p.addr += (uint64_t)(uintptr_t)d->pic_px.p;
+	uint64_t *d_toff = d->pic_tiles.as<uint64_t>();
 	uint32_t *d_tlen = (uint32_t *)(d_toff + tiles);
 	int32_t *d_tst = (int32_t *)(d_tlen + tiles);
-	const nhw_picture *d_desc = (const nhw_picture *)d->pic_desc;
+	const nhw_picture *d_desc = d->pic_desc.as<nhw_picture>();
 	hipStream_t s = d->own_stream;
-	HIPCHK(hipMemcpyAsync(d->d_blob, blob + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d->blob.p, blob + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(d_toff, toff.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(d_tlen, tlen.data(), (size_t)tiles * 4, hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(d->pic_desc, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
 	for (int t0 = 0; t0 < tiles; t0 += d->max_batch) {
 		const int m = tiles - t0 < d->max_batch ? tiles - t0 : d->max_batch;
-		const int rc = nhw_dec_batch_device(d, d->d_blob, d_toff + t0, d_tlen + t0, m, d->d_out, d_tst + t0, nullptr, s);
+		const int rc = nhw_dec_batch_device(d, d->blob.p, d_toff + t0, d_tlen + t0, m, d->d_out, d_tst + t0, nullptr, s);
 		if (rc) return rc;
 		HIPCHK(nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, s));
 	}

@@ -1,0 +1,406 @@
+/*
+ * nhw_enc_hostpath.hip -- the encoder's host conveniences: images and pictures of any size come from host memory and the files go back
+ * there (nhw_enc_batch, nhw_enc_synth_batch, nhw_enc_pictures, the picture searches of DESIGN.md section 12), and the device entry points
+ * of the picture kernels and the SSE.
+ */
+#include "nhw_enc.h"
+
+/* ------------------------------------------------------------------------------------------------ host path */
+__global__ void k_offsets(const uint32_t *sizes, uint64_t *offs, int n)
+{
+	if (blockIdx.x || threadIdx.x) return;
+	uint64_t acc = 0;
+	for (int i = 0; i < n; i++) { offs[i] = acc; acc += sizes[i]; }
+	offs[n] = acc;
+}
+__global__ __launch_bounds__(256) void k_compact(const uint8_t *out, const uint32_t *sizes, const uint64_t *offs, uint8_t *dst)
+{
+	const int img = blockIdx.x;
+	const uint8_t *s = out + (size_t)img * NHW_OUT_STRIDE;
+	uint8_t *d = dst + offs[img];
+	for (uint32_t i = threadIdx.x; i < sizes[img]; i += 256) d[i] = s[i];
+}
+
+/* Compact the first m output slots of the host path behind what is queued on the handle's stream and bring them to the host: the offsets
+ * offs[0 .. m] and the status first; then, the stream waited for, the files back to back to room(bytes) (nullptr: they do not fit). */
+template <class Room> static int compact_download(nhw_enc *e, int m, uint64_t *offs, int32_t *status, Room room)
+{
+	hipStream_t s = e->own_stream;
+	k_offsets<<<1, 1, 0, s>>>(e->d_sizes, e->d_offs, m);
+	k_compact<<<m, 256, 0, s>>>(e->d_out, e->d_sizes, e->d_offs, e->d_compact);
+	HIPCHK(hipMemcpyAsync(offs, e->d_offs, sizeof(uint64_t) * (m + 1), hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(status, e->d_status, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	uint8_t *dst = room(offs[m]);
+	if (!dst && offs[m]) { nhw_enc_err = "output arena too small"; return NHW_E_SPACE; }
+	HIPCHK(hipMemcpy(dst, e->d_compact, offs[m], hipMemcpyDeviceToHost));
+	return NHW_OK;
+}
+
+int host_download(nhw_enc *e, int n, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	return compact_download(e, n, out_off, status, [&](uint64_t bytes) { return bytes > arena_cap ? nullptr : out_arena; });
+}
+
+/* page-locked host memory: buffers handed to nhw_enc_batch that come from here travel by DMA at PCIe speed while the previous chunk
+ * is being encoded (pageable memory is staged by the runtime and moves at about half of that) */
+extern "C" void *nhw_host_alloc(size_t bytes) { void *p = nullptr; return hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess ? p : nullptr; }
+extern "C" void nhw_host_free(void *p) { if (p) (void)hipHostFree(p); }
+extern "C" int nhw_device_count(void) { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }
+
+extern "C" int nhw_enc_batch(nhw_enc *e, const uint8_t *bgr, int n, int quality, uint8_t *out_arena, size_t arena_cap,
+                             uint64_t *out_off, int32_t *status)
+{
+	if (!e || !bgr || !out_arena || !out_off || !status || n < 1 || n > e->max_batch) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, n); if (rc) return rc; }
+	hipStream_t s = e->own_stream, cs = e->part_stream[3];
+	/* chunks of 1024 images: the upload of a chunk (its own stream) overlaps the encode of the one before; every chunk is
+	 * encoded in the first workspace slots, one after the other on `s` */
+	const int chunk = 1024;
+	for (int i0 = 0; i0 < n; i0 += chunk) {
+		const int m = n - i0 < chunk ? n - i0 : chunk;
+		hipEvent_t up;
+		HIPCHK(hipEventCreateWithFlags(&up, hipEventDisableTiming));
+		HIPCHK(hipMemcpyAsync(e->d_in + (size_t)i0 * NHW_IMG_BYTES, bgr + (size_t)i0 * NHW_IMG_BYTES, (size_t)m * NHW_IMG_BYTES, hipMemcpyHostToDevice, cs));
+		HIPCHK(hipEventRecord(up, cs));
+		HIPCHK(hipStreamWaitEvent(s, up, 0));
+		HIPCHK(hipEventDestroy(up));
+		const int rc = nhw_enc_batch_device(e, e->d_in + (size_t)i0 * NHW_IMG_BYTES, m, quality, e->d_out + (size_t)i0 * NHW_OUT_STRIDE, e->d_sizes + i0, e->d_status + i0, s);
+		if (rc) return rc;
+	}
+	return host_download(e, n, out_arena, arena_cap, out_off, status);
+}
+
+/* SURVEY.md 8(d) synthetic images seed_base .. seed_base+n-1, generated on the device, encoded, and the files brought to the host:
+ * `nhw-enc --synthetic` (tools/nhw_enc.c) */
+extern "C" int nhw_enc_synth_batch(nhw_enc *e, int n, uint32_t seed_base, int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	if (!e || !out_arena || !out_off || !status || n < 1 || n > e->max_batch) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, n); if (rc) return rc; }
+	nhw_launch_synth(e->d_in, n, seed_base, e->own_stream);
+	HIPCHK(hipGetLastError());
+	{ const int rc = nhw_enc_batch_device(e, e->d_in, n, quality, e->d_out, e->d_sizes, e->d_status, e->own_stream); if (rc) return rc; }
+	return host_download(e, n, out_arena, arena_cap, out_off, status);
+}
+
+/* ------------------------------------------------------------------------------------------------ pictures of any size */
+static int picture_args(const void *d_pics, int n_pics, int tile0, int m, const void *d_tiles, const char *who)
+{
+	if (!d_pics || !d_tiles || n_pics < 1 || m < 1 || tile0 < 0 || m > INT_MAX / 16 || tile0 > INT_MAX - m) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if ((uintptr_t)d_tiles & 15) { nhw_enc_err = std::string(who) + ": d_tiles must be 16-byte aligned"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+extern "C" int nhw_tile_pictures_device(const nhw_picture *d_pics, int n_pics, int tile0, int m, void *d_tiles, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_tile_pictures_device")) return rc;
+	HIPCHK(nhw_launch_tile_pad(d_pics, n_pics, tile0, m, (uint8_t *)d_tiles, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_untile_pictures_device")) return rc;
+	HIPCHK(nhw_launch_untile_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, m, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_sse_pictures_device")) return rc;
+	if (!d_sse || ((uintptr_t)d_sse & 7)) { nhw_enc_err = "nhw_sse_pictures_device: d_sse must be 8-byte aligned"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_sse_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, m, d_sse, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* The pictures of a host call (nhw_enc_pictures, the picture searches): packed (pitch 3 W) at bgr + in_off[i].  pictures_check: the sides
+ * and the tile count; first[i] = picture i's first tile, first[n] = all tiles; the descriptors numbered so (addr still 0). */
+struct PicCall {
+	std::vector<nhw_picture> desc;
+	std::vector<int> first;
+	int tiles = 0;
+};
+
+static int pictures_check(const uint32_t *width, const uint32_t *height, int n, const char *who, PicCall &pc)
+{
+	pc.desc.assign((size_t)n, nhw_picture{});
+	pc.first.assign((size_t)n + 1, 0);
+	uint64_t tiles = 0;
+	for (int i = 0; i < n; i++) {
+		const int t = nhw_picture_tiles(width[i], height[i]);
+		if (t < 1) { nhw_enc_err = std::string(who) + ": a picture side outside 1..65535"; return NHW_E_ARG; }
+		pc.desc[i] = { 0, 3ull * width[i], width[i], height[i], (uint32_t)tiles, 0 };
+		pc.first[i] = (int)tiles;
+		tiles += (uint64_t)t;
+		if (tiles > INT_MAX / 16) { nhw_enc_err = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
+	}
+	pc.first[n] = (int)tiles;
+	pc.tiles = (int)tiles;
+	return NHW_OK;
+}
+
+/* Upload the pictures into the handle's grow-only buffer (one copy of the span they lie in when they lie close together, as a packed host
+ * array does; else one copy each) on the handle's stream and fill in the descriptors' addresses; the table itself is the caller's to upload. */
+static int pictures_upload(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, PicCall &pc)
+{
+	const int n = (int)pc.desc.size();
+	uint64_t bytes = 0, lo = UINT64_MAX, hi = 0;
+	for (int i = 0; i < n; i++) {
+		const uint64_t sz = 3ull * pc.desc[i].width * pc.desc[i].height;
+		bytes += sz;
+		lo = in_off[i] < lo ? in_off[i] : lo;
+		hi = in_off[i] + sz > hi ? in_off[i] + sz : hi;
+	}
+	const bool span = hi - lo <= bytes + bytes / 4 + (1u << 20);
+	HIPCHK(nhw_grow(e->pic_px, span ? hi - lo : bytes));
+	HIPCHK(nhw_grow(e->pic_desc, (size_t)n * sizeof(nhw_picture)));
+	hipStream_t s = e->own_stream;
+	uint8_t *px = e->pic_px.as<uint8_t>();
+	if (span) HIPCHK(hipMemcpyAsync(px, bgr + lo, hi - lo, hipMemcpyHostToDevice, s));
+	for (uint64_t i = 0, at = 0; i < (uint64_t)n; i++) {
+		const uint64_t sz = 3ull * pc.desc[i].width * pc.desc[i].height;
+		if (span) pc.desc[i].addr = (uint64_t)(uintptr_t)(px + (in_off[i] - lo));
+		else {
+			HIPCHK(hipMemcpyAsync(px + at, bgr + in_off[i], sz, hipMemcpyHostToDevice, s));
+			pc.desc[i].addr = (uint64_t)(uintptr_t)(px + at);
+			at += sz;
+		}
+	}
+	return NHW_OK;
+}
+
+/* The SSE search's per-chunk step (nhw_enc_fit_sse_pictures): decode the chunk's files from the host path's output slots by `dec` and add
+ * their picture-cropped error to `sse` (one entry per picture of the table). */
+struct ChunkSse {
+	nhw_dec *dec;
+	uint8_t *px;             /* the chunk's decoded tiles */
+	const uint64_t *doff;    /* decoder offsets: tile j at j * NHW_OUT_STRIDE */
+	int32_t *dstatus;        /* the decoder's status, a chunk */
+	uint64_t *sse;
+	int32_t *h_dstatus;      /* host: the decoder's status, every tile of the call */
+};
+
+/* Encode the global tiles [0, tiles) of the table d_desc (np pictures) at `quality` in chunks of at most max_batch into the host path's
+ * slots: k_tile_pad straight from the uploaded pictures, the encode, (the SSE step), then the chunk's files compacted and brought back.
+ * Tile t's file is files[.. + lens[t]) (back to back in tile order), its status tst[t]. */
+static int encode_tiles(nhw_enc *e, const nhw_picture *d_desc, int np, int tiles, int quality, const ChunkSse *cs, std::vector<uint8_t> &files,
+                        uint32_t *lens, int32_t *tst)
+{
+	hipStream_t s = e->own_stream;
+	const int chunk = tiles < e->max_batch ? tiles : e->max_batch;
+	std::vector<uint64_t> offs((size_t)chunk + 1);
+	files.clear();
+	for (int t0 = 0; t0 < tiles; t0 += chunk) {
+		const int m = tiles - t0 < chunk ? tiles - t0 : chunk;
+		HIPCHK(nhw_launch_tile_pad(d_desc, np, t0, m, e->d_in, s));
+		{ const int rc = nhw_enc_batch_device(e, e->d_in, m, quality, e->d_out, e->d_sizes, e->d_status, s); if (rc) return rc; }
+		if (cs) {
+			const int rc = nhw_dec_batch_device(cs->dec, e->d_out, cs->doff, e->d_sizes, m, cs->px, cs->dstatus, nullptr, s);
+			if (rc) { nhw_enc_err = std::string("decode of a rung: ") + nhw_dec_last_error(); return rc; }
+			HIPCHK(nhw_launch_sse_crop(cs->px, d_desc, np, t0, m, cs->sse, s));
+			HIPCHK(hipMemcpyAsync(cs->h_dstatus + t0, cs->dstatus, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+		}
+		const int rc = compact_download(e, m, offs.data(), tst + t0, [&](uint64_t bytes) { const size_t used = files.size(); files.resize(used + bytes); return files.data() + used; });
+		if (rc) return rc;
+		for (int k = 0; k < m; k++) lens[(size_t)t0 + k] = (uint32_t)(offs[k + 1] - offs[k]);
+	}
+	return NHW_OK;
+}
+
+/* picture i's container (t tiles of lengths lens[], files back to back) at out_arena + *at, which it advances; NHW_E_SPACE if it does not fit */
+static int put_container(uint8_t *out_arena, size_t arena_cap, uint64_t *at, uint32_t width, uint32_t height, const uint32_t *lens, int t,
+                         const uint8_t *files)
+{
+	uint64_t sum = 0;
+	for (int k = 0; k < t; k++) sum += lens[k];
+	const uint64_t size = 16 + 4 * (uint64_t)t + sum;
+	if (*at + size > arena_cap) { nhw_enc_err = "output arena too small"; return NHW_E_SPACE; }
+	const size_t head = nhw_container_head(out_arena + *at, width, height, lens, t);
+	memcpy(out_arena + *at + head, files, sum);
+	*at += size;
+	return NHW_OK;
+}
+
+/* Upload the pictures, pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch
+ * its files; then one container per picture. */
+extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	PicCall pc;
+	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures", pc); if (rc) return rc; }
+	const int tiles = pc.tiles;
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, tiles < e->max_batch ? tiles : e->max_batch); if (rc) return rc; }
+	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
+	HIPCHK(hipMemcpyAsync(e->pic_desc.p, pc.desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, e->own_stream));
+	std::vector<uint8_t> files;
+	std::vector<uint32_t> lens((size_t)tiles);
+	std::vector<int32_t> tst((size_t)tiles);
+	{ const int rc = encode_tiles(e, e->pic_desc.as<nhw_picture>(), n, tiles, quality, nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
+	const int *first = pc.first.data();
+	uint64_t at = 0, fpos = 0;
+	for (int i = 0; i < n; i++) {
+		uint64_t sum = 0;
+		int32_t st = NHW_OK;
+		for (int k = first[i]; k < first[i + 1]; k++) { sum += lens[k]; if (st == NHW_OK) st = tst[k]; }
+		out_off[i] = at;
+		status[i] = st;
+		if (st == NHW_OK) {
+			const int rc = put_container(out_arena, arena_cap, &at, width[i], height[i], lens.data() + first[i], first[i + 1] - first[i], files.data() + fpos);
+			if (rc) return rc;
+		}
+		fpos += sum;
+	}
+	out_off[n] = at;
+	return NHW_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ distortion */
+extern "C" int nhw_sse_batch_device(const void *d_a, const void *d_b, int n, uint64_t *d_sse, void *stream)
+{
+	if (!d_a || !d_b || !d_sse || n < 1 || n > 65535) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (((uintptr_t)d_a | (uintptr_t)d_b) & 15) { nhw_enc_err = "nhw_sse_batch_device: the pictures must be 16-byte aligned"; return NHW_E_ARG; }
+	if ((uintptr_t)d_sse & 7) { nhw_enc_err = "nhw_sse_batch_device: d_sse must be 8-byte aligned"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_sse((const uint8_t *)d_a, (const uint8_t *)d_b, n, d_sse, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* ------------------------------------------------------------------------------------------------ pictures to a byte or distortion budget */
+/* One picture search: the byte test (limit = max_bytes) or, with a decoder, the SSE test (limit = max_sse). */
+struct PicFit {
+	const char *who;
+	nhw_dec *dec;                        /* NULL: the byte search */
+	const uint64_t *limit;
+	int q[23] = {}, len = 0;
+};
+
+/* The walk over pictures.  Every picture is open at the first rung.  A rung uploads the table of the open pictures only, first_tile
+ * renumbered, and encodes their tiles (encode_tiles: k_tile_pad re-tiles them straight from the uploaded picture bytes); the SSE search
+ * decodes each chunk and adds the picture-cropped error into one entry per open picture, zeroed once a rung.  After the rung the host
+ * closes every open picture that passes (all tiles NHW_OK; the container size, or the SSE, within its limit; the SSE search: every tile
+ * decoded NHW_OK) and keeps its files; at the last rung every picture still open keeps that rung's. */
+static int fit_pictures(nhw_enc *e, const PicFit &f, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height,
+                        int n, PicCall &pc, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	hipStream_t s = e->own_stream;
+	const int chunk = pc.tiles < e->max_batch ? pc.tiles : e->max_batch;
+	e->fit_done = false;
+	nhw_fit_stats st;
+	memset(&st, 0, sizeof st);
+	HIPCHK(hipEventRecord(e->fit_ev[0], s));
+	{ const int rc = host_buffers(e, chunk); if (rc) return rc; }
+	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
+	ChunkSse cs = {};
+	std::vector<int32_t> tdst;
+	if (f.dec) {
+		HIPCHK(nhw_grow(e->pfit_px, (size_t)chunk * NHW_IMG_BYTES));
+		HIPCHK(nhw_grow(e->pfit_aux, (size_t)(chunk + n) * 8 + (size_t)chunk * 4));
+		uint64_t *aux = e->pfit_aux.as<uint64_t>();
+		fit_doff(aux, chunk, s);
+		HIPCHK(hipGetLastError());
+		tdst.resize((size_t)pc.tiles);
+		cs = { f.dec, e->pfit_px.as<uint8_t>(), aux, (int32_t *)(aux + chunk + n), aux + chunk, tdst.data() };
+	}
+	std::vector<std::vector<uint8_t>> kept((size_t)n);    /* a closed picture's tile files, back to back */
+	std::vector<std::vector<uint32_t>> kept_len((size_t)n);
+	std::vector<uint64_t> psse((size_t)n);
+	std::vector<int> open((size_t)n);                      /* the open pictures, ascending */
+	for (int i = 0; i < n; i++) open[i] = i;
+	std::vector<nhw_picture> desc;
+	std::vector<uint8_t> files;
+	std::vector<uint32_t> lens((size_t)pc.tiles);
+	std::vector<int32_t> tst((size_t)pc.tiles);
+	for (int r = 0; r < f.len && !open.empty(); r++) {
+		const bool last = r == f.len - 1;
+		const int no = (int)open.size();
+		desc.resize((size_t)no);
+		int tiles = 0;
+		for (int j = 0; j < no; j++) {
+			const int i = open[j];
+			desc[j] = pc.desc[i];
+			desc[j].first_tile = (uint32_t)tiles;
+			tiles += pc.first[i + 1] - pc.first[i];
+		}
+		st.quality[r] = f.q[r]; st.images[r] = tiles; st.rungs = r + 1;
+		HIPCHK(hipMemcpyAsync(e->pic_desc.p, desc.data(), (size_t)no * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
+		if (f.dec) HIPCHK(hipMemsetAsync(cs.sse, 0, (size_t)no * 8, s));
+		{ const int rc = encode_tiles(e, e->pic_desc.as<nhw_picture>(), no, tiles, f.q[r], f.dec ? &cs : nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
+		if (f.dec) HIPCHK(hipMemcpy(psse.data(), cs.sse, (size_t)no * 8, hipMemcpyDeviceToHost));
+		std::vector<int> still;
+		uint64_t fpos = 0;
+		for (int j = 0; j < no; j++) {
+			const int i = open[j], t0 = (int)desc[j].first_tile, t = pc.first[i + 1] - pc.first[i];
+			uint64_t sum = 0;
+			int32_t enc_st = NHW_OK, dec_st = NHW_OK;
+			for (int k = t0; k < t0 + t; k++) {
+				sum += lens[k];
+				if (enc_st == NHW_OK) enc_st = tst[k];
+				if (f.dec && dec_st == NHW_OK) dec_st = tdst[k];
+			}
+			const bool pass = enc_st == NHW_OK && (f.dec ? dec_st == NHW_OK && psse[j] <= f.limit[i] : 16 + 4 * (uint64_t)t + sum <= f.limit[i]);
+			if (pass || last) {
+				quality[i] = f.q[r];
+				status[i] = pass ? NHW_OK : enc_st != NHW_OK ? enc_st : dec_st != NHW_OK ? NHW_E_FORMAT : NHW_E_BUDGET;
+				if (sse) sse[i] = enc_st != NHW_OK || dec_st != NHW_OK ? UINT64_MAX : psse[j];
+				if (enc_st == NHW_OK) {
+					kept[i].assign(files.begin() + fpos, files.begin() + fpos + sum);
+					kept_len[i].assign(lens.begin() + t0, lens.begin() + t0 + t);
+				}
+			} else still.push_back(i);
+			fpos += sum;
+		}
+		open.swap(still);
+	}
+	HIPCHK(hipEventRecord(e->fit_ev[1], s));
+	e->fit_stats = st;
+	e->fit_done = true;
+	uint64_t at = 0;
+	for (int i = 0; i < n; i++) {
+		out_off[i] = at;
+		if (status[i] == NHW_E_CODEBOOK) continue;                 /* an empty container, as nhw_enc_pictures gives */
+		const int rc = put_container(out_arena, arena_cap, &at, width[i], height[i], kept_len[i].data(), (int)kept_len[i].size(), kept[i].data());
+		if (rc) return rc;
+	}
+	out_off[n] = at;
+	return NHW_OK;
+}
+
+/* the picture searches' checks, in this order: NULL pointers, n, the sides (and the tile count), a debug stop, the ladder, the decoder;
+ * nothing is launched before all of them pass */
+static int fit_pictures_host(nhw_enc *e, PicFit &f, bool ptrs, const int *ladder, int ladder_len, const uint8_t *bgr, const uint64_t *in_off,
+                             const uint32_t *width, const uint32_t *height, int n, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off,
+                             int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	if (!e || !ptrs || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || !quality || n < 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	const std::string who = f.who;
+	PicCall pc;
+	{ const int rc = pictures_check(width, height, n, f.who, pc); if (rc) return rc; }
+	if (e->stop_after) { nhw_enc_err = who + ": not with nhw_debug_stop_after set (every rung must be a whole encode)"; return NHW_E_ARG; }
+	{ const int rc = ladder_check(ladder, ladder_len, f.dec != nullptr, f.q, &f.len); if (rc) return rc; }
+	if (f.dec) { const int rc = dec_check(e, f.dec, pc.tiles < e->max_batch ? pc.tiles : e->max_batch, who, "min(encoder max_batch, tiles)"); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	return fit_pictures(e, f, bgr, in_off, width, height, n, pc, out_arena, arena_cap, out_off, status, quality, sse);
+}
+
+extern "C" int nhw_enc_fit_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                    const uint64_t *max_bytes, const int *ladder, int ladder_len,
+                                    uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality)
+{
+	PicFit f;
+	f.who = "nhw_enc_fit_pictures"; f.dec = nullptr; f.limit = max_bytes;
+	return fit_pictures_host(e, f, max_bytes != nullptr, ladder, ladder_len, bgr, in_off, width, height, n, out_arena, arena_cap, out_off, status, quality, nullptr);
+}
+
+extern "C" int nhw_enc_fit_sse_pictures(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height,
+                                        int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
+                                        uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse)
+{
+	PicFit f;
+	f.who = "nhw_enc_fit_sse_pictures"; f.dec = d; f.limit = max_sse;
+	if (!d) { nhw_enc_err = "bad argument: no decoder handle"; return NHW_E_ARG; }
+	return fit_pictures_host(e, f, max_sse != nullptr && sse != nullptr, ladder, ladder_len, bgr, in_off, width, height, n, out_arena, arena_cap, out_off, status, quality, sse);
+}

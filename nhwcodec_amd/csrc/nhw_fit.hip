@@ -3,7 +3,7 @@
  * (nhw_enc_fit_sse_batch_device, the same walk with a decode and an error pass per rung): gfx950 only.
  *
  * The search walks a ladder of qualities from the top.  At every rung the images that are still open are encoded at that rung's quality
- * as an ordinary batch (nhw_api.hip); the three kernels here move the images and files between the caller's per-image slots and the
+ * as an ordinary batch (nhw_enc_fit.hip); the three kernels here move the images and files between the caller's per-image slots and the
  * compacted sub-batch the encoder works on:
  *
  *   k_fit_gather   staging[j] = d_bgr[idx[j]]: the open images, 786 432 bytes each, in list order (rungs 2 and later)
@@ -13,10 +13,7 @@
  *   k_fit_compact  one workgroup: the flags -> the next open list, in ascending original order, and its length (a scan, not an atomic
  *                  append, so a rung's membership does not depend on the order the workgroups ran in)
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/nhw_hip.h"
+#include "nhw_host.h"
 
 #define FIT_IMG_V4   (NHW_IMG_BYTES / 16u)    /* 49 152 sixteen-byte words an image */
 #define FIT_GATHER_T 256

@@ -15,9 +15,9 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include "nhw_host.h"
 #include "nhw_ws.h"
 #include "nhw_dwt.h"
-#include "nhw_slice.h"
 
 #pragma clang fp contract(off)
 
@@ -507,7 +507,7 @@ __global__ __launch_bounds__(S * 4) void k_dwt_ana(int16_t *__restrict__ jpegb, 
 #define CQ_ROW(r) ((((r) & 1) * 128 + ((r) >> 1)) * CQ_LS)   /* even rows first, then the odd ones: the column pass reads a lane's even row and odd row at a pitch of 33 dwords each -- no bank conflicts (k_dwt_ana's 129-dword pitch puts rows 2k on 16 banks) */
 __global__ __launch_bounds__(256) void k_chroma_l1q(const uint8_t *__restrict__ src8b, size_t src8_plane, int16_t *__restrict__ procb, int16_t *__restrict__ jpegb, size_t plane_stride,
                                                     int16_t *__restrict__ saveb, size_t save_plane, int save_row, int n, int ll_to_jpeg /* 0: the LL quadrant only goes to its copy (the level-2 analysis reads it there) */,
-                                                    int slice /* -1: production; else the quarter (nhw_slice.h) */)
+                                                    int slice /* -1: production; else the quarter (nhw_host.h) */)
 {
 	constexpr int S = 256, HLF = 128, PPL = 2, stride = 256;
 	__shared__ __attribute__((aligned(16))) int16_t A[S * CQ_LS];
@@ -680,8 +680,6 @@ int nhw_front_set_attrs(const char **where)
 #undef SETATTR
 	return 0;
 }
-
-void nhw_launch_copy_block(const int16_t *src, size_t src_plane, int src_row, int16_t *dst, size_t dst_plane, int dst_row, int rows, int cols, int n, hipStream_t s);
 
 /* save (optional): a second destination for the block the reference copies right after the transform -- the S x S coefficient block
  * (save_kind 1) or the LL quadrant in natural orientation (save_kind 2) -- written by the fused kernels, by a block copy otherwise */

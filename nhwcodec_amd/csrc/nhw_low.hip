@@ -20,11 +20,9 @@
  *     fifteen wavefronts of its CU.
  * Traffic per image: 512 KiB read, 512 KiB written (the reference makes four passes over three planes).
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdlib.h>
+#include "nhw_host.h"
 #include "nhw_ws.h"
-#include "nhw_slice.h"
 
 #define DEVI __device__ static __forceinline__
 #define DEVN __device__ static
@@ -429,7 +427,7 @@ DEVI int final_pair(const PfP &pp, const int16_t *km, int f0, int f1, int p, int
  * and the marker counters (MapState), which only the few candidate cells move: those are left to k_low_mapfix, with the cells marked here
  * for every state the counters can be in (five bit masks a row). */
 __global__ __launch_bounds__(64) void k_low_pre(const int16_t *__restrict__ srcb, size_t src_stride, int16_t *__restrict__ kmb, size_t km_stride,
-                                                uint8_t *__restrict__ maskb, size_t mask_stride, int q, int dbg, int slice /* -1: production; else the band (nhw_slice.h) */)
+                                                uint8_t *__restrict__ maskb, size_t mask_stride, int q, int dbg, int slice /* -1: production; else the band (nhw_host.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t s_src[3][W];
 	__shared__ __attribute__((aligned(16))) int16_t s_km[W + 8];
@@ -840,7 +838,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
  * act: the chain's answers (a byte a pair, stream order); km in: as passes A left it; out: y, km, flags as pass B leaves them. */
 __global__ __launch_bounds__(64) void k_low_apply(const int16_t *__restrict__ srcb, size_t src_stride, int16_t *__restrict__ yb, size_t y_stride, int16_t *__restrict__ kmb, size_t km_stride,
                                                   uint8_t *__restrict__ sob, size_t so_stride, const uint8_t *__restrict__ actb, size_t act_stride, int q, int dbg,
-                                                  int slice /* -1: production; else the band (nhw_slice.h) */)
+                                                  int slice /* -1: production; else the band (nhw_host.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t s_src[3][W];
 	__shared__ __attribute__((aligned(16))) int16_t s_km[W + 8];
@@ -1080,7 +1078,7 @@ struct MkFx {
 };
 }
 __global__ __launch_bounds__(MK_R) void k_low_marks(int16_t *__restrict__ yb, size_t y_stride, const int16_t *__restrict__ kmb, size_t km_stride,
-                                                    uint8_t *__restrict__ sob, size_t so_stride, int q, int dbg, int slice /* -1: production; else the window (nhw_slice.h) */)
+                                                    uint8_t *__restrict__ sob, size_t so_stride, int q, int dbg, int slice /* -1: production; else the window (nhw_host.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int8_t own[MK_R * MK_BP], upd[MK_R * MK_BP];   /* what a lane adds to its row / to the row above */
 	__shared__ uint64_t s_upflag[MK_R + 1], s_updirty[MK_R + 1];          /* of the lane's additions to the row above: flags raised, cells touched */
@@ -1543,7 +1541,7 @@ void nhw_launch_low_ll2(int16_t *proc, size_t plane_stride, int q, int n, hipStr
 /* The pre-filter of a batch.  parts > 1: the batch is cut into sub-batches whose sequences run on streams of their own (aux), the next one's
  * pass A starting when the one before has finished its own -- the chain (k_low_chain) is two wavefronts a picture that live on the scalar
  * unit and on look-ups, and leaves the vector units and the memory system to the streaming kernels of the sub-batches before and behind it
- * (pass A, the answers' application, passes C and D).  ev: 1 + 2 * parts events.  Returns a hipError_t. */
+ * (pass A, the answers' application, passes C and D).  ev: the LOW_EV_COUNT events of nhw_host.h.  Returns a hipError_t. */
 int nhw_launch_low_prefilter(const int16_t *src, size_t src_stride, int16_t *y, size_t y_stride, int16_t *km, size_t km_stride, uint8_t *so, size_t so_stride,
                              uint8_t *chain /* CH_BYTES an image: the machine's answers */, size_t chain_stride,
                              uint16_t *tab /* MASK_ROW * W bytes an image: pass A's candidate masks */, size_t tab_stride, int q, int n, hipStream_t s, int force /* 32: the bands of pass A go back three rows for their entry state (tests) */,
@@ -1574,18 +1572,18 @@ int nhw_launch_low_prefilter(const int16_t *src, size_t src_stride, int16_t *y, 
 	};
 	if (parts <= 1 || !aux || !ev) { head(0, n, s); machine(0, n, s); rest(0, n, s); return (int)hipGetLastError(); }
 #define LOWCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
-	LOWCHK(hipEventRecord(ev[0], s));
+	LOWCHK(hipEventRecord(ev[LOW_EV_START], s));
 	for (int p = 0; p < parts; p++) {
 		const int i0 = (int)((long long)n * p / parts), i1 = (int)((long long)n * (p + 1) / parts);
-		LOWCHK(hipStreamWaitEvent(aux[p], ev[0], 0));
-		if (p) LOWCHK(hipStreamWaitEvent(aux[p], ev[p], 0));              /* the sub-batch before is through its pass A */
+		LOWCHK(hipStreamWaitEvent(aux[p], ev[LOW_EV_START], 0));
+		if (p) LOWCHK(hipStreamWaitEvent(aux[p], ev[low_ev_pass_a(p - 1)], 0));              /* the sub-batch before is through its pass A */
 		head(i0, i1 - i0, aux[p]);
-		LOWCHK(hipEventRecord(ev[1 + p], aux[p]));
+		LOWCHK(hipEventRecord(ev[low_ev_pass_a(p)], aux[p]));
 		machine(i0, i1 - i0, aux[p]);
 		rest(i0, i1 - i0, aux[p]);
-		LOWCHK(hipEventRecord(ev[1 + parts + p], aux[p]));
+		LOWCHK(hipEventRecord(ev[low_ev_done(parts, p)], aux[p]));
 	}
-	for (int p = 0; p < parts; p++) LOWCHK(hipStreamWaitEvent(s, ev[1 + parts + p], 0));
+	for (int p = 0; p < parts; p++) LOWCHK(hipStreamWaitEvent(s, ev[low_ev_done(parts, p)], 0));
 #undef LOWCHK
 	return (int)hipGetLastError();
 }

@@ -9,10 +9,7 @@
  * 32 bits (at most 4 * 255^2 = 260 100 a dword).  A thread's sum over its 48 dwords (at most 12.5 M) and a wavefront's (at most 800 M)
  * stay in 32 bits; the workgroup's four wavefronts are added in 64 bits.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/nhw_hip.h"
+#include "nhw_host.h"
 #include "nhw_sse.h"
 
 #define SSE_IMG_V4 (NHW_IMG_BYTES / 16u)     /* 49 152 sixteen-byte words an image */

@@ -11,11 +11,9 @@
  * the tile side is 16-byte aligned and moves in dwordx4.  No load touches a word that holds no byte of a picture row (or, for
  * k_untile_crop, of the tile rows it reads), and no store touches a byte outside a picture row.
  */
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <string.h>
 
-#include "../../include/nhw_hip.h"
+#include "nhw_host.h"
 #include "nhw_sse.h"
 
 namespace {
@@ -264,19 +262,6 @@ hipError_t nhw_launch_sse_crop(const uint8_t *d_tiles, const nhw_picture *d_pics
 {
 	k_sse_crop<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0, reinterpret_cast<unsigned long long *>(d_sse));
 	return hipGetLastError();
-}
-
-/* the host paths' grow-only device buffers (nhw_enc_pictures, nhw_dec_pictures): *p holds at least `bytes` afterwards, its old contents
- * not kept; on a failed allocation *p is NULL and *cap 0 */
-hipError_t nhw_grow(void **p, size_t *cap, size_t bytes)
-{
-	if (*cap >= bytes) return hipSuccess;
-	if (*p) (void)hipFree(*p);
-	*p = nullptr; *cap = 0;
-	const hipError_t err = hipMalloc(p, bytes);
-	if (err == hipSuccess) *cap = bytes;
-	else *p = nullptr;
-	return err;
 }
 
 /* ------------------------------------------------------------------------------------------------ the .nhwp container (host) */

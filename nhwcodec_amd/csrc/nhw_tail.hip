@@ -2,6 +2,7 @@
  * nhw_tail.hip -- kernels that run the order-dependent phases of the NHW encoder, one 256-thread workgroup
  * per image (see nhw_tail_par.h / nhw_tail_dev.h), plus the small block-copy kernel used between them.
  */
+#include "nhw_host.h"
 #include "nhw_tail_par.h"
 #include "nhw_dwt.h"
 
@@ -10,7 +11,6 @@ using namespace nhw;
 #ifndef NHW_DENSE_STREAM
 #define NHW_DENSE_STREAM 0          /* 1: the luma byte stream is written (and rewritten by the dense Y31) next to the list -- a developer switch for comparing the two forms */
 #endif
-enum { PH_L1, PH_L2, PH_L3, PH_L4A, PH_C0, PH_C2, PH_C3, PH_C4, PH_C5, PH_FINAL, PH_L4B, PH_L4C, PH_L4D, PH_LLC, PH_L4C2 };
 
 template <int PH>
 __global__ __launch_bounds__(256) void k_phase(NhwWs ws, int comp, uint8_t *out, uint32_t *sizes, int32_t *status)
@@ -78,7 +78,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NHW_L4A_WAV
 }
 
 /* passes that run one wavefront per image (nhw_tail_wave.h): four images per workgroup, no workgroup barriers */
-enum { WV_DQ1, WV_DQ0, WV_EMIT, WV_QUANT };
 template <int PH>
 __global__ __launch_bounds__(256) void k_wave(NhwWs ws)
 {

@@ -776,12 +776,13 @@ def test_odd_batch_sizes(oracle, q):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env", [{"NHW_CHROMA_FORK": "0"}, {"NHW_LISTS_FORK": "0"}, {"NHW_LL_FORK": "0"}, {"NHW_QUANT_JOIN": "0"}])
+@pytest.mark.parametrize("env", [{"NHW_CHROMA_FORK": "0"}, {"NHW_LISTS_FORK": "0"}, {"NHW_LL_FORK": "0"}, {"NHW_QUANT_JOIN": "0"}, {"NHW_LOW_CHROMA": "7"}])
 def test_encoder_stream_modes_give_the_same_files(oracle, env):
     """The chroma sequence, the position lists and the LL2 coder run on streams of their own beside the luma tail; NHW_CHROMA_FORK=0 /
     NHW_LISTS_FORK=0 / NHW_LL_FORK=0 put them back in line (the last one also moves the putting back of the verbatim LL2 samples from the
     synthesis kernel to the dequantiser simulation again).  Same arithmetic under another schedule: 512 images at q20 and q23, every file equal to the
-    default schedule's, a sample of them to the oracle's."""
+    default schedule's, a sample of them to the oracle's.  NHW_LOW_CHROMA (quality 1..16: where the chroma sequence starts) takes 0, 1 or 2;
+    any other value means the default, so with 7 the q10 files are the default's."""
     import torch
     import nhwcodec_amd
     n = 512
@@ -792,7 +793,7 @@ def test_encoder_stream_modes_give_the_same_files(oracle, env):
     finally:
         for k in env: del os.environ[k]
     bgr = base.synth_device(n, seed_base=61000)
-    for q in (20, 23):
+    for q in (10,) if "NHW_LOW_CHROMA" in env else (20, 23):
         o0, s0, st0 = base.encode_device(bgr, q)
         o1, s1, st1 = e.encode_device(bgr, q)
         torch.cuda.synchronize()
