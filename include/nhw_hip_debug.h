@@ -36,6 +36,15 @@ int nhw_debug_fill(nhw_enc *e, int buf, int byte, size_t bytes, int n);
 int nhw_debug_slice_order(nhw_enc *e, int mode);
 int nhw_dec_debug_slice_order(nhw_dec *d, int mode);
 
+/* The chroma closed loops of component comp (0: U, 1: V) for the first n images of the handle's last whole batch, at that batch's quality, on the
+ * handle's first set of chroma planes (B_CPROC, B_CLL1, B_CL2SAVE; B_CJPEG for the staged forms).  form 0: the head as a production batch
+ * launches it, from the 4:2:0 byte planes that batch left (pre-filter / level-1 analysis, then the fused level-2 kernel); form 1: the fused
+ * kernel alone on cll1 and cproc as they stand; form 2 .. 8: the first form - 1 of the seven staged kernels alone on the same inputs (8: all
+ * of them; 4: up to the first synthesis).  The tests write planes with nhw_debug_write (host bytes into workspace buffer buf of image img,
+ * the counterpart of nhw_debug_read) and read them behind the call. */
+int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, void *stream);
+int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes);
+
 /* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip) */
 void nhw_dec_debug_stop_after(nhw_dec *d, int stage);
 int  nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size_t bytes);

@@ -139,6 +139,49 @@ int host_buffers(nhw_enc *e, int n)
 }
 
 
+/* a chroma component's launches up to the second dequantiser simulation, on stream cs (run_batch; nhw_stage_chroma_loops).  1 = carry on;
+ * NHW_OK: the debug stop fell in here */
+#define STAGE_DONE() do { if (e->stop_after && ++stage == e->stop_after) { HIPCHK(hipGetLastError()); return NHW_OK; } } while (0)
+static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hipStream_t cs, int &stage)
+{
+	const int q = ws.q;
+	const bool low = q <= 16;
+	const size_t cps = ws.stride[B_CJPEG] / 2;
+	uint8_t *out = nullptr; uint32_t *d_sizes = nullptr; int32_t *d_status = nullptr;   /* (the chroma phases write none of them) */
+	const bool vp = comp && ws.split_chroma;
+	int16_t *cjpeg = plane16(ws, vp ? B_CJPEG_V : B_CJPEG), *cproc = plane16(ws, vp ? B_CPROC_V : B_CPROC);
+	int16_t *cll1 = plane16(ws, vp ? B_CLL1_V : B_CLL1), *cl2save = plane16(ws, vp ? B_CL2SAVE_V : B_CL2SAVE);
+	const bool widen_in_analysis = q > 14 && !ws.dbg;              /* the analysis reads the byte plane itself (the stage checks keep the copy as a stage of its own) */
+	if (q <= 14) nhw_launch_low_prefilter_chroma(comp ? plane8(ws, B_PV) : plane8(ws, B_PU), ws.stride[B_PU], cjpeg, cps, q, n, cs);   /* :2263 / :2579 */
+	else if (!widen_in_analysis) nhw_launch_phase(PH_C0, ws, comp, out, d_sizes, d_status, cs);
+	STAGE_DONE();
+	nhw_launch_analysis(cjpeg, cproc, n, cps, H, H, 0, cs, cll1, ws.stride[B_CLL1] / 2, H / 2, 2,   /* + the copy of LL1 */
+	                    widen_in_analysis ? (comp ? plane8(ws, B_PV) : plane8(ws, B_PU)) : nullptr, ws.stride[B_PU], ws.dbg ? 0 : 2);   /* 2: nor the LL quadrant back into the work plane -- the level-2 analysis below reads its copy */
+	if (low) nhw_launch_low_chroma_thin(cproc, cps, n, cs);      /* :2277-2308 / :2590-2621 */
+	STAGE_DONE();
+	STAGE_DONE();
+	if (!ws.dbg) {   /* both closed loops on one residency of the level-2 block, from the copy of LL1 (k_chroma_loops); the stage checks take the seven kernels */
+		nhw_launch_chroma_loops(cproc, cps, cll1, ws.stride[B_CLL1] / 2, cl2save, ws.stride[B_CL2SAVE] / 2, plane8(ws, B_PU), ws.stride[B_PU], q, comp, ws.compat, n, cs);
+		return 1;
+	}
+	nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs);
+	STAGE_DONE();
+	nhw_launch_phase(PH_C2, ws, comp, out, d_sizes, d_status, cs);
+	STAGE_DONE();
+	nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, cs);
+	STAGE_DONE();
+	nhw_launch_phase(PH_C3, ws, comp, out, d_sizes, d_status, cs);
+	STAGE_DONE();
+	nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs, cl2save, ws.stride[B_CL2SAVE] / 2, H / 2, 1);   /* + the copy of the level-2 block */
+	STAGE_DONE();
+	STAGE_DONE();
+	nhw_launch_phase(PH_C4, ws, comp, out, d_sizes, d_status, cs);
+	STAGE_DONE();
+	nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, cs);
+	STAGE_DONE();
+	return 1;
+}
+
 /* the whole launch sequence for the images of one workspace view on one stream; `timed`: record the stage events of nhw_timing */
 static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, hipStream_t s,
                      int timed /* 0: no events, 1: EV_START .. EV_END (whole batch), 2: EV_LUMA, EV_CHROMA (tail of the first sub-batch; the caller closes with EV_END) */,
@@ -154,7 +197,6 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 
 	e->low_parts_used = 1;         /* until the pre-filter below runs in sub-batches: the chroma fork never waits on an event of an earlier batch */
 	int stage = 0;
-#define STAGE_DONE() do { if (e->stop_after && ++stage == e->stop_after) { HIPCHK(hipGetLastError()); return NHW_OK; } } while (0)   
 	(void)n;
 	if (what & 1) {
 	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_START], s));
@@ -202,37 +244,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	ws.defer_verbatim = fork_ll;
 	hipStream_t cs = fork ? e->part_stream[0] : s;
 	ws.split_chroma = fork;                                          /* (the stage checks and the in-line order keep the reference's one set of planes) */
-	auto chroma_head = [&](int comp) -> int {                        /* everything up to the second dequantiser simulation */
-		const bool vp = comp && ws.split_chroma;
-		int16_t *cjpeg = plane16(ws, vp ? B_CJPEG_V : B_CJPEG), *cproc = plane16(ws, vp ? B_CPROC_V : B_CPROC);
-		int16_t *cll1 = plane16(ws, vp ? B_CLL1_V : B_CLL1), *cl2save = plane16(ws, vp ? B_CL2SAVE_V : B_CL2SAVE);
-		const bool widen_in_analysis = q > 14 && !ws.dbg;              /* the analysis reads the byte plane itself (the stage checks keep the copy as a stage of its own) */
-		if (q <= 14) nhw_launch_low_prefilter_chroma(comp ? plane8(ws, B_PV) : plane8(ws, B_PU), ws.stride[B_PU], cjpeg, cps, q, n, cs);   /* :2263 / :2579 */
-		else if (!widen_in_analysis) nhw_launch_phase(PH_C0, ws, comp, out, d_sizes, d_status, cs);
-		STAGE_DONE();
-		nhw_launch_analysis(cjpeg, cproc, n, cps, H, H, 0, cs, cll1, ws.stride[B_CLL1] / 2, H / 2, 2,   /* + the copy of LL1 */
-		                    widen_in_analysis ? (comp ? plane8(ws, B_PV) : plane8(ws, B_PU)) : nullptr, ws.stride[B_PU], ws.dbg ? 0 : 2);   /* 2: nor the LL quadrant back into the work plane -- the level-2 analysis below reads its copy */
-		if (low) nhw_launch_low_chroma_thin(cproc, cps, n, cs);      /* :2277-2308 / :2590-2621 */
-		STAGE_DONE();
-		STAGE_DONE();
-		if (ws.dbg) nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs, nullptr, 0, 0, 0, nullptr, 0, 0);
-		else nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs, nullptr, 0, 0, 0, nullptr, 0, 1, cll1, ws.stride[B_CLL1] / 2, H / 2);   /* from the copy of LL1 */
-		STAGE_DONE();
-		nhw_launch_phase(PH_C2, ws, comp, out, d_sizes, d_status, cs);
-		STAGE_DONE();
-		nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, cs, !ws.dbg);
-		STAGE_DONE();
-		nhw_launch_phase(PH_C3, ws, comp, out, d_sizes, d_status, cs);
-		STAGE_DONE();
-		nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs, cl2save, ws.stride[B_CL2SAVE] / 2, H / 2, 1, nullptr, 0, !ws.dbg);   /* + the copy of the level-2 block */
-		STAGE_DONE();
-		STAGE_DONE();
-		nhw_launch_phase(PH_C4, ws, comp, out, d_sizes, d_status, cs);
-		STAGE_DONE();
-		nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, cs, !ws.dbg);
-		STAGE_DONE();
-		return 1;
-	};
+	auto chroma_head = [&](int comp) -> int { return chroma_head_launches(e, ws, comp, n, cs, stage); };   /* everything up to the second dequantiser simulation */
 	auto chroma_tail = [&](int comp) -> int {                        /* marks, LL2 emission (appends to the exception list), quantiser, stream bytes */
 		nhw_launch_phase(PH_C5, ws, comp, out, d_sizes, d_status, cs);
 		STAGE_DONE();
@@ -521,6 +533,49 @@ extern "C" int nhw_stage_chroma_l1(nhw_enc *e, int n, void *stream)
 	return NHW_OK;
 }
 
+/* A test hook for the chroma closed loops of component comp, on the handle's first set of chroma planes, for the first n images of its last
+ * whole batch at that batch's quality.
+ *   form 0: the head exactly as a production batch launches it (pre-filter / level-1 analysis from the 4:2:0 byte plane, then k_chroma_loops).
+ *           Behind a whole batch the marks and the quantiser have rewritten cproc, so the planes the fused kernel leaves are read behind this
+ *           call.  It relies on the byte planes of that batch still standing (nothing behind the front writes them);
+ *   form 1: k_chroma_loops alone, on cll1 and cproc as they stand (a test may have written them: nhw_debug_write);
+ *   form 2 .. 8: the first form - 1 of the seven staged kernels alone (analysis from cll1, simulation 1, synthesis, pre-compensation, analysis
+ *           + cl2save, simulation 2, synthesis), every plane stored, on the same inputs: 8 is the whole sequence, 4 stops behind the first
+ *           synthesis (cproc = the reconstruction the pre-compensation compares with cll1). */
+extern "C" int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, void *stream)
+{
+	if (!e || n < 1 || n > e->max_batch || comp < 0 || comp > 1 || form < 0 || form > 8) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after) {
+		nhw_enc_err = "nhw_stage_chroma_loops: needs a completed whole batch of >= n images and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = 0; ws.split_chroma = false;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	int16_t *cjpeg = plane16(ws, B_CJPEG), *cproc = plane16(ws, B_CPROC), *cll1 = plane16(ws, B_CLL1), *cl2save = plane16(ws, B_CL2SAVE);
+	const size_t cps = ws.stride[B_CJPEG] / 2;
+	if (form == 0) {
+		int stage = 0;
+		const int rc = chroma_head_launches(e, ws, comp, n, s, stage);
+		if (rc != 1) return rc;
+	} else if (form == 1)
+		nhw_launch_chroma_loops(cproc, cps, cll1, ws.stride[B_CLL1] / 2, cl2save, ws.stride[B_CL2SAVE] / 2, plane8(ws, B_PU), ws.stride[B_PU], ws.q, comp, ws.compat, n, s);
+	else {
+		const int k = form - 1;
+		nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, cll1, ws.stride[B_CLL1] / 2, H / 2);
+		if (k > 1) nhw_launch_phase(PH_C2, ws, comp, nullptr, nullptr, nullptr, s);
+		if (k > 2) nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, s);
+		if (k > 3) nhw_launch_phase(PH_C3, ws, comp, nullptr, nullptr, nullptr, s);
+		if (k > 4) nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, s, cl2save, ws.stride[B_CL2SAVE] / 2, H / 2, 1);
+		if (k > 5) nhw_launch_phase(PH_C4, ws, comp, nullptr, nullptr, nullptr, s);
+		if (k > 6) nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, s);
+	}
+	HIPCHK(hipGetLastError());
+	return NHW_OK;
+}
+
 extern "C" int nhw_stage_synthesis(nhw_enc *e, void *d_jpeg, void *d_proc, int n_img, size_t plane_stride, int stride, int size, void *stream)
 {
 	if (!e || n_img < 1) return NHW_E_ARG;
@@ -564,6 +619,14 @@ extern "C" int nhw_debug_fill(nhw_enc *e, int buf, int byte, size_t bytes, int n
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemset2D(e->ws.base + e->ws.off[buf], e->ws.stride[buf], byte, bytes, (size_t)n));
 	HIPCHK(hipDeviceSynchronize());
+	return NHW_OK;
+}
+extern "C" int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes)
+{
+	if (!e || !src || buf < 0 || buf >= B_COUNT || img < 0 || img >= e->max_batch || bytes + GUARD > e->ws.stride[buf]) return NHW_E_ARG;
+	HIPCHK(hipSetDevice(e->device));
+	HIPCHK(hipDeviceSynchronize());
+	HIPCHK(hipMemcpy(e->ws.base + e->ws.off[buf] + (size_t)img * e->ws.stride[buf], src, bytes, hipMemcpyHostToDevice));
 	return NHW_OK;
 }
 extern "C" int nhw_debug_read(nhw_enc *e, int buf, int img, void *dst, size_t bytes)

@@ -38,14 +38,6 @@ __device__ __forceinline__ unsigned sad_u16(unsigned a, unsigned b, unsigned acc
 	asm("v_sad_u16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(acc));
 	return d;
 }
-/* two 16-bit sums in a dword (no carry between the halves) */
-__device__ __forceinline__ unsigned pk_add16(unsigned a, unsigned b)
-{
-	unsigned d;
-	asm("v_pk_add_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-	return d;
-}
-
 /* ------------------------------------------------------------------------------------------------
  * colour + 4:2:0.  One workgroup per pair of luma rows (2r, 2r+1) = one chroma row r.
  * The three BGR rows 2r-1..2r+1 are staged in LDS with coalesced 16-byte loads.
@@ -284,7 +276,6 @@ void nhw_launch_color(const uint8_t *bgr, int n, int q, int16_t *y, size_t y_str
 }
 
 /* keep != nullptr: copy of the first 256 rows x 512 of the transposed pass-1 plane (q>=22, level 0) */
-__device__ __forceinline__ uint32_t pk_max_u16x(uint32_t a, uint32_t b) { uint32_t d; asm("v_pk_max_u16 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
 /* ------------------------------------------------------------------------------------------------
  * Whole-block filterbank kernels for the 256- and 128-sized levels: one workgroup keeps the S x S block in
  * LDS (row stride S + 2 shorts: column walks hit 64 different banks), runs both directions there and writes
@@ -300,93 +291,6 @@ __device__ __forceinline__ uint4 ana_piece(const int16_t *src, const uint8_t *sr
 	const uint2 b = *reinterpret_cast<const uint2 *>(src8 + (size_t)row * S + 8 * o);
 	return make_uint4((b.x & 0xFF) | ((b.x >> 8 & 0xFF) << 16), (b.x >> 16 & 0xFF) | ((b.x >> 24) << 16), (b.y & 0xFF) | ((b.y >> 8 & 0xFF) << 16), (b.y >> 16 & 0xFF) | ((b.y >> 24) << 16));
 }
-/* The second direction (filters.c:88-287) of two columns at once: Ew / Ow hold the even / odd rows' cells of the two columns, a lane its own row pair
- * k = lane + 64 u; lo / hi: what the pair leaves for its two columns.  left: the columns lie in the first direction's low-pass half. */
-template <int PPL, int HLF, bool IN_RANGE = false /* the caller vouches for the 16-bit range (cells made from bytes): no test, no 32-bit form */>
-__device__ __forceinline__ void ana_col_pair(const uint32_t (&Ew)[PPL], const uint32_t (&Ow)[PPL], bool left, int lane, int (&lo)[PPL][2], int (&hi)[PPL][2])
-{
-	/* Two columns side by side in packed 16-bit arithmetic wherever nothing can leave 16 bits: with every cell of the wavefront's two columns in
-	 * -1300 .. 3000 the un-normalised sums stay inside (10 x 3000 + 2 x 1300 < 32768) -- which is every block of a real picture (the level-2
-	 * input is LL1, the level-1 chroma input a byte plane).  A block outside that range takes the 32-bit form below, which follows the
-	 * reference's int arithmetic where it wraps. */
-	bool wide = false;
-	if (!IN_RANGE)
-#pragma unroll
-	for (int u = 0; u < PPL; u++) {
-		const uint32_t mx = pk_max_u16x(pk_add16(Ew[u], 0x05140514u), pk_add16(Ow[u], 0x05140514u));   /* + 1300: in range = at most 4300 as unsigned */
-		wide |= (mx & 0xFFFFu) > 4300u || (mx >> 16) > 4300u;
-	}
-	if (IN_RANGE || !__any(wide)) {
-		uint32_t rlast = 0;
-#pragma unroll
-		for (int u = 0; u < PPL; u++) {
-			const int k = lane + 64 * u;
-			uint32_t em = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Ew[u], 0x138, 0xF, 0xF, false), om = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Ow[u], 0x138, 0xF, 0xF, false);
-			uint32_t en = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Ew[u], 0x130, 0xF, 0xF, false);
-			if (u > 0) {
-				const uint32_t se = (uint32_t)__builtin_amdgcn_readlane((int)Ew[u > 0 ? u - 1 : 0], 63), so_ = (uint32_t)__builtin_amdgcn_readlane((int)Ow[u > 0 ? u - 1 : 0], 63);
-				if (lane == 0) { em = se; om = so_; }
-			}
-			if (u + 1 < PPL) { const uint32_t se = (uint32_t)__builtin_amdgcn_readlane((int)Ew[u + 1 < PPL ? u + 1 : u], 0); if (lane == 63) en = se; }
-			else if (lane == 63) en = Ew[u];
-			if (u == 0 && lane == 0) { em = en; om = Ow[u]; }
-			const s16x2 e0 = as_s(Ew[u]), o0 = as_s(Ow[u]), em1 = as_s(em), om1 = as_s(om), e1 = as_s(en);
-			const s16x2 r = e0 * (s16x2)(short)6 + ((om1 + o0) << 1) - (em1 + e1);
-			s16x2 a = e0 + e1;
-			a = a + (a & (em1 + e0) & as_s((k & 1) ? 0x00010001u : 0u));
-			const s16x2 pp = o0 - (a >> 1), tail = o0 - e0;
-			s16x2 l, h;
-			if (left) {
-				uint32_t rp = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)as_w(r), 0x138, 0xF, 0xF, false);
-				if (lane == 0) rp = rlast;
-				const s16x2 carry = k > 0 ? pk_diffuse(as_s(rp)) : (s16x2)(short)0;
-				rlast = (uint32_t)__builtin_amdgcn_readlane((int)as_w(r), 63);
-				l = pk_rnd_half_away(r + carry, 6);
-				h = k < HLF - 1 ? pk_rnd_half_away(pp, 3) : (tail >> 3);
-			} else {
-				l = pk_rnd_half_away(r, 4);
-				h = k < HLF - 1 ? pk_rnd_half_away(pp, 1) : ((tail + (s16x2)(short)1) >> 1);   /* pp > 0 ? (pp + 1) >> 1 : pp >> 1 is rounding half away at shift 1 */
-			}
-			lo[u][0] = l.x; lo[u][1] = l.y; hi[u][0] = h.x; hi[u][1] = h.y;
-		}
-	} else {
-	int rlast[2] = { 0, 0 };                                    /* r of cell 63 of the half before (the seam of the carry) */
-#pragma unroll
-		for (int u = 0; u < PPL; u++) {
-			const int k = lane + 64 * u;
-			uint32_t em = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Ew[u], 0x138, 0xF, 0xF, false), om = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Ow[u], 0x138, 0xF, 0xF, false);
-			uint32_t en = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Ew[u], 0x130, 0xF, 0xF, false);
-			if (u > 0) {
-				const uint32_t se = (uint32_t)__builtin_amdgcn_readlane((int)Ew[u > 0 ? u - 1 : 0], 63), so_ = (uint32_t)__builtin_amdgcn_readlane((int)Ow[u > 0 ? u - 1 : 0], 63);
-				if (lane == 0) { em = se; om = so_; }
-			}
-			if (u + 1 < PPL) { const uint32_t se = (uint32_t)__builtin_amdgcn_readlane((int)Ew[u + 1 < PPL ? u + 1 : u], 0); if (lane == 63) en = se; }
-			else if (lane == 63) en = Ew[u];                           /* x[S] = x[S - 2] */
-			if (u == 0 && lane == 0) { em = en; om = Ow[u]; }           /* x[-2] = x[2], x[-1] = x[1] */
-#pragma unroll
-			for (int h = 0; h < 2; h++) {
-				const int e0 = h ? (int)Ew[u] >> 16 : (int16_t)(Ew[u] & 0xFFFF), o0 = h ? (int)Ow[u] >> 16 : (int16_t)(Ow[u] & 0xFFFF);
-				const int em1 = h ? (int)em >> 16 : (int16_t)(em & 0xFFFF), om1 = h ? (int)om >> 16 : (int16_t)(om & 0xFFFF), e1 = h ? (int)en >> 16 : (int16_t)(en & 0xFFFF);
-				const int r = 6 * e0 + 2 * (om1 + o0) - (em1 + e1);
-				int a = e0 + e1;
-				if ((k & 1) && (a & 1) && ((em1 + e0) & 1)) a++;
-				const int pp = o0 - (a >> 1), tail = o0 - e0;          /* the predicted odd sample; the last one: x[S-1] - x[S-2] */
-				if (left) {
-					int rp = __builtin_amdgcn_update_dpp(0, r, 0x138, 0xF, 0xF, false);   /* the cell before: its carry comes in (filters.c:203-287) */
-					if (lane == 0) rp = rlast[h];
-					const int carry = k > 0 ? diffuse(rp) : 0;
-					rlast[h] = __builtin_amdgcn_readlane(r, 63);
-					lo[u][h] = rnd_half_away((int16_t)(r + carry), 6);
-					hi[u][h] = k < HLF - 1 ? rnd_half_away(pp, 3) : (tail >> 3);
-				} else {
-					lo[u][h] = rnd_half_away(r, 4);
-					hi[u][h] = k < HLF - 1 ? (pp > 0 ? (pp + 1) >> 1 : pp >> 1) : ((tail + 1) >> 1);
-				}
-			}
-		}
-	}
-}
-
 template <int S>
 __global__ __launch_bounds__(S * 4) void k_dwt_ana(int16_t *__restrict__ jpegb, int16_t *__restrict__ procb, size_t plane_stride, int stride, int final_level,
                                                    int16_t *__restrict__ saveb, size_t save_plane, int save_row, int save_kind /* 1: copy of the S x S coefficient block, 2: of the LL quadrant copied back */, int n,
@@ -432,19 +336,7 @@ __global__ __launch_bounds__(S * 4) void k_dwt_ana(int16_t *__restrict__ jpegb, 
 		int lo[PPL], hi[PPL];
 #pragma unroll
 		for (int u = 0; u < PPL; u++) Dw[u] = reinterpret_cast<const uint32_t *>(x)[lane + 64 * u];
-#pragma unroll
-		for (int u = 0; u < PPL; u++) {
-			uint32_t pv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Dw[u], 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
-			uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)Dw[u], 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
-			if (u > 0) { const uint32_t seam = (uint32_t)__builtin_amdgcn_readlane((int)Dw[u > 0 ? u - 1 : 0], 63); if (lane == 0) pv = seam; }
-			if (u + 1 < PPL) { const uint32_t seam = (uint32_t)__builtin_amdgcn_readlane((int)Dw[u + 1 < PPL ? u + 1 : u], 0); if (lane == 63) nx = seam; }
-			else if (lane == 63) nx = Dw[u];                           /* x[S] = x[S - 2] */
-			const int e0 = (int16_t)(Dw[u] & 0xFFFF), o0 = (int)Dw[u] >> 16, e1 = (int16_t)(nx & 0xFFFF);
-			int em1 = (int16_t)(pv & 0xFFFF), om1 = (int)pv >> 16;
-			if (u == 0 && lane == 0) { em1 = e1; om1 = o0; }           /* x[-2] = x[2], x[-1] = x[1] */
-			lo[u] = 6 * e0 + 2 * (om1 + o0) - (em1 + e1);
-			hi[u] = (o0 << 1) - (e0 + e1);                             /* the last one: (x[S-1] - x[S-2]) << 1, which is what e1 = e0 gives */
-		}
+		ana_row_pair<PPL>(Dw, lane, lo, hi);
 #pragma unroll
 		for (int u = 0; u < PPL; u++) { x[lane + 64 * u] = (int16_t)lo[u]; x[HLF + lane + 64 * u] = (int16_t)hi[u]; }
 	}

@@ -61,12 +61,6 @@ static_assert(FI_STG_OFF % 16 == 0 && FI_CR_OFF % 16 == 0 && FI_PT_OFF % 16 == 0
 static_assert(32 * 512 <= 16 * FI_RS * 2, "the chroma staging fits into rows 5..20 of the contrast map");
 static_assert(FI_LDS_BYTES <= 81920, "two workgroups to a CU");
 
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ s16x2 as_s(uint32_t x) { return __builtin_bit_cast(s16x2, x); }
-__device__ __forceinline__ u16x2 as_us(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
-__device__ __forceinline__ uint32_t as_w(s16x2 x) { return __builtin_bit_cast(uint32_t, x); }
-__device__ __forceinline__ uint32_t as_w(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
 /* (lo half of a) | (lo half of b) << 16, and the same of the high halves */
 __device__ __forceinline__ uint32_t pack_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
 __device__ __forceinline__ uint32_t pack_hi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
@@ -222,15 +216,6 @@ __device__ __forceinline__ uint2 chroma_h8(const uint32_t c[4], uint32_t left)
  *     most 2 (10 U + 2 L) + 1; the high-pass rows' taps see first-pass differences, |2 x1 - x0 - x2| <= 2 (U + L), so their tap is at most
  *     24 (U + L) + 8 with the rounding offset.
  * The encoder's own luma is 0 .. 255 plus what the pre-filters add (at most +-4 a pixel): 104 * 259 + 40 * 4 = 27 096. */
-__device__ __forceinline__ s16x2 pk_rnd_half_away(s16x2 v, int shift) { return (v + (s16x2)(short)(1 << (shift - 1)) + (v >> 15)) >> shift; }
-__device__ __forceinline__ s16x2 pk_diffuse(s16x2 r)
-{
-	const s16x2 s = r >> 15, a = (r ^ s) - s;
-	const s16x2 t = (s16x2)(a << 10) >> 10;                           /* |r| mod 64 read as a signed 6-bit number */
-	const s16x2 d = (t + ((t >> 15) & (s16x2)(short)3)) >> 2;
-	return (d ^ s) - s;
-}
-
 /* The kernel is one long loop over the bands; left alone, the compiler computes every phase's per-thread offsets once in front of the loop and
  * then has 40 more values alive than there are registers (they went to scratch memory).  A thread index taken through this at the start of
  * a phase is opaque to it: the few adds and shifts are redone every band, and nothing of one phase is alive in another. */

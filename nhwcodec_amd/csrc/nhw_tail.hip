@@ -249,6 +249,144 @@ void nhw_launch_l2_recon(int16_t *jpeg, const int16_t *proc, size_t plane_stride
 	k_l2_recon<<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg, proc, plane_stride, ll1, ll1_stride, n);
 }
 
+/* Both closed loops of a chroma component on one LDS residency of its 128 x 128 level-2 block (nhw_encoder.c:2310-2370 for U, :2623-2680 for V):
+ * level-2 analysis, dequantiser simulation 1, synthesis, the LL1 pre-compensation (chroma_p3_par), analysis, simulation 2, synthesis.  As seven
+ * kernels the 32 KB block went to HBM and back seven times (4.7 GB per 4096 images, both components); here the LL1 copy comes in once and two
+ * blocks go out: the coefficients behind the second analysis (cl2save) and the second reconstruction (the upper left of cproc).
+ *   * The staged kernels transpose in every filterbank call (ana: proc[c][k] from column c; syn: proc[c][.] from column c again) and the
+ *     pointwise passes in between work on the transposed plane.  In LDS nothing is transposed: cell (r, j) of the coefficient plane sits at
+ *     A[j][r], so a row of the coefficient plane (what a wavefront of the simulation owns) is a column of A -- 65 dwords apart, no bank conflicts --
+ *     and after the synthesis' second direction A is the reconstruction in natural orientation.
+ *   * A wavefront owns 16 rows in the row phases (synthesis second direction -> pre-compensation -> analysis first direction, a row at a time in
+ *     registers) and 16 columns in the column phases (analysis second direction -> simulation -> synthesis first direction): every pass reads its
+ *     line into registers before it writes it, and what it reads was written by the same wavefront or lies behind a barrier.  Four barriers.
+ *   * The original LL1 rows are read a second time for the pre-compensation, in the row phases' own layout, a window of four rows ahead: kept
+ *     in registers from the first load (16 dwords a thread) the kernel does not fit the 64 registers that four workgroups a CU allow, and
+ *     the compiler spills.  The second read does reach HBM (2 x FETCH_SIZE + WRITE_SIZE: 1.11 GB per 4096 images and both components, 0.8 without it).
+ *   * Cells outside the block: column 128 of cproc's rows (a level-1 detail cell, the right neighbour of column 127 in all three pointwise
+ *     passes), the first LL1 cell of the row behind a wavefront's last, and the cell behind cll1 (chroma_ll1_neighbour: worked out here, and still
+ *     written for chroma_p5_par).  All are constant during the sequence and fetched at the start.
+ *   * What is no longer stored: the block of cjpeg (read by nobody behind the head: chroma_p5_par, ll_code_chroma_par and final_phase_par take
+ *     cproc, cll1 and cl2save) and the three earlier versions of cproc's block.  Cells outside the block are not touched.
+ * The stage checks (nhw_debug_stop_after) run the seven kernels, which leave every intermediate plane. */
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_chroma_loops(int16_t *__restrict__ cprocb, size_t plane_stride, int16_t *__restrict__ cll1b, size_t ll1_stride,
+                                                      int16_t *__restrict__ saveb, size_t save_stride, const uint8_t *__restrict__ pub, size_t pu_stride,
+                                                      int q, int comp, int compat)
+{
+	constexpr int S = H / 2, LS = S + 2, HLF = S / 2;
+	__shared__ __attribute__((aligned(16))) int16_t A[S * LS];
+	const int t = threadIdx.x, lane = t & 63, wv = t >> 6, img = blockIdx.x, r0 = wv * 16;
+	int16_t *p = cprocb + (size_t)img * plane_stride, *o = cll1b + (size_t)img * ll1_stride, *save = saveb + (size_t)img * save_stride;
+	const uint8_t *pu = pub + (size_t)img * pu_stride;
+	const int behind = compat ? (int16_t)(pu[32768] | (pu[32769] << 8)) : 0;   /* chroma_ll1_neighbour */
+	auto ll1_row = [&](int i) { return reinterpret_cast<const uint32_t *>(o + (size_t)(r0 + (i < 16 ? i : 15)) * S)[lane]; };   /* row i of my 16 rows of LL1, a lane cells 2 lane, 2 lane + 1 */
+	uint32_t w0 = ll1_row(0), w1 = ll1_row(1), w2 = ll1_row(2), w3 = ll1_row(3);   /* a window of four rows, requested three rows ahead of their use (rolled loops: unrolled, the compiler interleaves the rows and spills) */
+	int side = 0;                                                  /* lane l < 16: column 128 of row (= coefficient row) r0 + l of cproc; lane 16: the LL1 cell behind my last row */
+	if (lane < 16) side = p[(size_t)(r0 + lane) * H + S];
+	else if (lane == 16) side = wv < 7 ? o[(size_t)(r0 + 16) * S] : behind;
+	if (t == 0) o[Q >> 2] = (int16_t)behind;
+	auto ana_row = [&](int16_t *x, uint32_t w) {                   /* analysis, first direction, of a row in registers */
+		const uint32_t Dw[1] = { w };
+		int lo[1], hi[1];
+		ana_row_pair<1>(Dw, lane, lo, hi);
+		x[lane] = (int16_t)lo[0]; x[HLF + lane] = (int16_t)hi[0];
+	};
+	auto columns = [&](const int loop /* dequant_sim_chroma_par's: 1 = the first simulation */, int16_t *out) {
+		for (int i = 0; i < 8; i++) {                              /* analysis, second direction, two columns at a time, in place: cell (c, k) of the coefficient plane at A[k][c] */
+			const int c = r0 + 2 * i;
+			uint32_t Ew[1], Ow[1];
+			int lo[1][2], hi[1][2];
+			Ew[0] = *reinterpret_cast<const uint32_t *>(A + (2 * lane) * LS + c); Ow[0] = *reinterpret_cast<const uint32_t *>(A + (2 * lane + 1) * LS + c);
+			ana_col_pair<1, HLF>(Ew, Ow, c < HLF, lane, lo, hi);
+			*reinterpret_cast<uint32_t *>(A + lane * LS + c) = (uint32_t)(uint16_t)lo[0][0] | ((uint32_t)(uint16_t)lo[0][1] << 16);
+			*reinterpret_cast<uint32_t *>(A + (HLF + lane) * LS + c) = (uint32_t)(uint16_t)hi[0][0] | ((uint32_t)(uint16_t)hi[0][1] << 16);
+			if (out)
+#pragma unroll
+				for (int h = 0; h < 2; h++) { int16_t *d = out + (size_t)(c + h) * S; d[lane] = (int16_t)lo[0][h]; d[HLF + lane] = (int16_t)hi[0][h]; }
+		}
+		for (int i = 0; i < 16; i++) {                             /* dequant_sim_chroma_par on coefficient row r, then the synthesis' first direction along it */
+			const int r = r0 + i, col0 = r < HLF ? HLF : 0;
+			int16_t *x = A + r;
+			int v[3] = { x[lane * LS], x[(HLF + lane) * LS], __builtin_amdgcn_readlane(side, i) };
+			int ll = v[0];                                             /* r < 64: the LL2 cell (r, lane) */
+			if (loop) {
+				if (q <= 15) ll = (int16_t)((ll & 0xFFFC) + 1);
+				else if ((r == 0) == (bool)(lane & 1)) ll = clear_bit0(ll);   /* row 0: the odd columns lose bit 0, every other row: the even ones */
+			} else if (ll > 0 && ll < 256) ll = clear_bit0(ll);
+			if (col0) v[0] = 0;
+			uint64_t pair[2] = { 0, 0 };
+			if (!loop) {
+				const uint64_t m0 = __ballot(v[0] == -7 || v[0] == -8), m1 = __ballot(v[1] == -7 || v[1] == -8);
+				const M4 m = M4{ { col0 ? 0 : m0, m1, 0, 0 } };
+				const M4 fired = alt_runs(m & dn1(m) & col_range(col0, S - 2));
+				const M4 both = fired | up1(fired);
+				pair[0] = both.w[0]; pair[1] = both.w[1];
+			}
+			int dv[2] = { ll, 0 };
+			for (int k = col0 ? 1 : 0; k < 2; k++) {
+				int a = v[k];
+				const int nx = right_of(v, k, 3, 1, lane);
+				if (a < 0) {
+					a = -a;
+					if (nx < 0 && nx > -8) { if ((a & 7) < 6) a &= 0xFFF8; }
+					else { if ((a & 7) < 7) a &= 0xFFF8; }
+					a = -a;
+				}
+				dv[k] = ((pair[k] >> lane) & 1) ? -11 : dequant_value(a);
+			}
+			x[lane * LS] = (int16_t)dv[0]; x[(HLF + lane) * LS] = (int16_t)dv[1];
+			int e, od;
+			syn_pair<S>(x, LS, lane, false, &e, &od);
+			x[(2 * lane) * LS] = (int16_t)e; x[(2 * lane + 1) * LS] = (int16_t)od;
+		}
+	};
+	auto p3_step = [&](int d, int nx) {                            /* chroma_p3_par */
+		int step = 0;
+		if (d > 10) step = -6; else if (d > 7) step = -3; else if (d > 4) step = -2; else if (d > 3) step = -1;
+		else if (d > 2 && (comp ? nx > 0 : nx >= 0)) step = -1;
+		else if (d < -10) step = 6; else if (d < -7) step = 3; else if (d < -4) step = 2; else if (d < -3) step = 1;
+		else if (d < -2 && (comp ? nx < 0 : nx <= 0)) step = 1;
+		return step;
+	};
+#pragma unroll 1
+	for (int i = 0; i < 16; i++) { ana_row(A + (r0 + i) * LS, w0); w0 = w1; w1 = w2; w2 = w3; w3 = ll1_row(i + 4); }
+	lds_barrier();
+	columns(1, nullptr);
+	w0 = ll1_row(0); w1 = ll1_row(1); w2 = ll1_row(2); w3 = ll1_row(3);
+	lds_barrier();
+#pragma unroll 1
+	for (int i = 0; i < 16; i++) {                                 /* synthesis, second direction -> the pre-compensated LL1 row -> analysis, first direction */
+		int16_t *x = A + (r0 + i) * LS;
+		int e, od;
+		syn_pair<S>(x, 1, lane, true, &e, &od);
+		const uint32_t ow = w0, ow_next = w1;
+		w0 = w1; w1 = w2; w2 = w3; w3 = ll1_row(i + 4);
+		const int oc0 = (int16_t)(ow & 0xFFFF), oc1 = (int)ow >> 16;
+		int pn = __builtin_amdgcn_update_dpp(0, e, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
+		int on = (int16_t)(__builtin_amdgcn_update_dpp(0, (int)ow, 0x130, 0xF, 0xF, false) & 0xFFFF);
+		if (lane == 63) {                                          /* behind column 127: column 128 of the row; the first LL1 cell of the next row */
+			pn = __builtin_amdgcn_readlane(side, i);
+			on = i < 15 ? (int16_t)(__builtin_amdgcn_readlane((int)ow_next, 0) & 0xFFFF) : __builtin_amdgcn_readlane(side, 16);
+		}
+		const int d0 = e - oc0, d1 = od - oc1, d2 = pn - on;
+		ana_row(x, (uint32_t)(uint16_t)(oc0 + p3_step(d0, d1)) | ((uint32_t)(uint16_t)(oc1 + p3_step(d1, d2)) << 16));
+	}
+	lds_barrier();
+	columns(0, save);
+	lds_barrier();
+#pragma unroll 1
+	for (int i = 0; i < 16; i++) {                                 /* synthesis, second direction: the reconstruction, row r0 + i of cproc */
+		int e, od;
+		syn_pair<S>(A + (r0 + i) * LS, 1, lane, true, &e, &od);
+		reinterpret_cast<uint32_t *>(p + (size_t)(r0 + i) * H)[lane] = (uint32_t)(uint16_t)e | ((uint32_t)(uint16_t)od << 16);
+	}
+}
+void nhw_launch_chroma_loops(int16_t *cproc, size_t plane_stride, int16_t *cll1, size_t ll1_stride, int16_t *cl2save, size_t save_stride,
+                             const uint8_t *pu, size_t pu_stride, int q, int comp, int compat, int n, hipStream_t s)
+{
+	k_chroma_loops<<<n, 512, 0, s>>>(cproc, plane_stride, cll1, ll1_stride, cl2save, save_stride, pu, pu_stride, q, comp, compat);
+}
+
 /* rows x cols block of shorts between two strided planes, every image of the batch: a workgroup an image, 16 bytes a thread and turn, four
  * turns in flight (cols and both pitches are multiples of 8, every row 16-byte aligned: asserted by the launcher).  Until round 5 a thread
  * moved ONE short and a workgroup one row: 1.6 ms for the 128 KB block of 4096 images (q <= 12), 0.7 TB/s. */

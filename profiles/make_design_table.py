@@ -1,11 +1,11 @@
 """Regenerates the kernel table of DESIGN.md (between the KERNEL_TABLE markers) from the committed profile summaries, so that the numbers
 cannot drift from the files they cite.   usage: python profiles/make_design_table.py [--check]
-inputs: profiles/round6_kernel_stats_1stream.txt (rocprofv3 --kernel-trace --stats, one stream), profiles/round6_pmc.json (FETCH_SIZE and
+inputs: profiles/round7_kernel_stats_1stream.txt (rocprofv3 --kernel-trace --stats, one stream), profiles/round7_pmc.json (FETCH_SIZE and
 WRITE_SIZE per kernel from separate --pmc passes; KiB; FETCH_SIZE doubled for gfx950 as MI355X_MICROARCH.md prescribes)."""
 import json, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STATS = os.path.join(ROOT, "profiles", "round6_kernel_stats_1stream.txt")
-PMC = os.path.join(ROOT, "profiles", "round6_pmc.json")
+STATS = os.path.join(ROOT, "profiles", "round7_kernel_stats_1stream.txt")
+PMC = os.path.join(ROOT, "profiles", "round7_pmc.json")
 BATCHES = 7.0            # bench.py --steps 5 --warmup 2 in profiles/collect.sh
 PH = ["L1", "L2", "L3", "L4A", "C0", "C2", "C3", "C4", "C5", "FINAL", "L4B", "L4C", "L4D", "LLC", "L4C2"]
 WV = ["DQ1", "DQ0", "EMIT", "QUANT"]
@@ -14,9 +14,10 @@ WHAT = {
     "k_front_plain": "the same without the pre-filter (q >= 22; q <= 16 and the analysis stage from a luma plane): horizontal pass from registers, 64 rows a band",
     "k_dwt_ana<256>": "level-2 luma analysis of both closed loops (whole block in LDS, persistent workgroups); level-1 chroma analysis only for q <= 14 and the stage checks",
     "k_chroma_l1q": "level-1 chroma analysis from the 4:2:0 byte plane, a quarter of the 256 x 256 block to a workgroup (four a CU); its coefficients are part of SURVEY's 6 B/pixel",
-    "k_dwt_ana<128>": "level-2 chroma analysis",
+    "k_dwt_ana<128>": "level-2 chroma analysis (only the tests' stage checks run it)",
+    "k_chroma_loops": "both chroma closed loops of a component on one LDS residency of its level-2 block: analysis, simulation 1, synthesis, pre-compensation, analysis (+ cl2save), simulation 2, synthesis (four workgroups a CU)",
     "k_dwt_syn<256>": "level-2 luma synthesis of the second closed loop",
-    "k_dwt_syn<128>": "level-2 chroma synthesis",
+    "k_dwt_syn<128>": "level-2 chroma synthesis (only the tests' stage checks run it)",
     "k_l2_recon": "first closed loop: level-2 synthesis + Y8 (tags -> reconstruction) + Y9 (LL1 pre-compensation) on one LDS residency of the block",
     "L1": "Y5 tag level-2 details", "L2": "Y8, Y9 as a kernel of their own (only the tests' stage checks run it)", "L3": "Y16 LL2 coder (parse), on a stream of its own beside the second dequantiser simulation",
     "L4A": "Y19-Y23: small runs (wavefront per row), residual classification (one table-driven step for every kind) and coding (column walks on LDS tiles)",
