@@ -218,6 +218,25 @@ int nhw_enc_fit_sse_pictures(nhw_enc *e, nhw_dec *d, const uint8_t *bgr, const u
                              int n, const uint64_t *max_sse, const int *ladder, int ladder_len,
                              uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status, int32_t *quality, uint64_t *sse);
 
+/* ---- a rectangle of a picture from only the tiles it touches ----
+ * A region of a W x H picture is a rectangle x, y, width, height (width, height >= 1, x + width <= W, y + height <= H) in the coordinates
+ * of the array nhw_dec_pictures returns (row 0 = its first row, BMP file order); its result is that array's rows y .. y + height - 1,
+ * columns x .. x + width - 1, byte for byte.  It is made from the selected tiles only: columns x / 512 .. (x + width - 1) / 512 times rows
+ * y / 512 .. (y + height - 1) / 512 of the picture's tile grid, in row-major order (ty, then tx).
+ * Descriptor of a region in device memory: addr = device address of its first destination byte (any alignment), pitch = bytes from one
+ * destination row to the next (>= 3 width, any value), first_tile = running number of the region's first selected tile within the call
+ * (first_tile[k + 1] = first_tile[k] + nhw_region_tiles(k)), reserved 0. */
+typedef struct { uint64_t addr, pitch; uint32_t x, y, width, height, pic_width, pic_height, first_tile, reserved; } nhw_region;   /* 48 bytes */
+/* the number of tiles the region selects, or NHW_E_ARG for a picture side outside 1..65535, an empty rectangle or one not inside the picture */
+int nhw_region_tiles(uint32_t pic_width, uint32_t pic_height, uint32_t x, uint32_t y, uint32_t width, uint32_t height); /* count, or NHW_E_ARG */
+/* d_tiles holds the decoded tiles [tile0, tile0 + m) of the running selection of the regions d_regs[0 .. n_regs) (a table in device memory,
+ * the caller's responsibility), NHW_IMG_BYTES each, 16-byte aligned.  Of selected tile (ty, tx), tile row rr is picture row 512 ty + rr;
+ * if y <= 512 ty + rr < y + height, its picture columns [max(512 tx, x), min(512 tx + 512, x + width)) go to destination byte 3 (col - x)
+ * of row 512 ty + rr - y.  Writes exactly the regions' bytes: never a byte outside [addr + r pitch, addr + r pitch + 3 width) of a row r,
+ * never a read-modify-write (two regions may share destination dwords, not bytes).  No handle: the current device; stream NULL is the null
+ * stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG as for nhw_untile_pictures_device. */
+int nhw_untile_regions_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, void *stream);
+
 /* ---- stage-level entry points (kernel parity tests; same stream rules) ----
  * colour + 4:2:0 (colorspace.c:55-260), any quality 1..23: d_y n*262144 int16, d_u/d_v n*65536 uint8 */
 int nhw_stage_color(nhw_enc *e, const void *d_bgr, int n, int quality, void *d_y, void *d_u, void *d_v, void *stream);
@@ -263,6 +282,28 @@ void nhw_dec_bmp_header(uint8_t h[54]);
  * decoded in chunks of max_batch, cropped on the device, and picture i (W x H x 3 bytes, pitch 3 W) lands at bgr + out_off[i] (n entries).
  * status[i] = NHW_OK, or NHW_E_FORMAT for a malformed container or a tile the decoder refuses; that picture's bytes are left untouched. */
 int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status);
+/* ---- regions of .nhwp containers: host conveniences, synchronous ----
+ * Containers as for nhw_dec_pictures (container c is blob[off[c] .. off[c + 1]), off: n_containers + 1 entries); rect i is a region of
+ * container rects[i].container, and several rects may name one container.  Only the tile files the rects select are uploaded and decoded
+ * (in chunks of max_batch, each chunk cropped on the device by k_untile_region); a tile selected by two rects is uploaded and decoded twice.
+ * status[i] = NHW_OK; NHW_E_ARG for a container index out of range or a rectangle that is empty or not inside that picture; NHW_E_FORMAT
+ * for a malformed container or a selected tile the decoder refuses.  A rect that is not NHW_OK does not disturb the others.
+ * nhw_dec_regions: region i (width x height x 3 bytes, pitch 3 width) lands at bgr + out_off[i] (n_rects entries); a rect that is not
+ * NHW_OK leaves its bytes untouched.
+ * nhw_dec_regions_to_device: region i is cropped straight into device memory at dst_addr[i] with row pitch dst_pitch[i] (any alignment,
+ * any pitch >= 3 width: e.g. slot i of an [n, h, w, 3] batch tensor); no pixels are downloaded.  A rect that is NHW_E_ARG or names a
+ * malformed container leaves its destination untouched; one that fails on a refused tile may have had bytes of its own rows written by its
+ * other tiles, never a byte outside them.
+ * The call itself fails (NHW_E_ARG) only for NULL pointers, counts < 1, a decreasing off[], a dst_addr of 0, a dst_pitch below 3 width,
+ * or more selected tiles than nhw_dec_pictures accepts. */
+typedef struct { uint32_t container, x, y, width, height; } nhw_rect;
+int nhw_dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
+                    uint8_t *bgr, const uint64_t *out_off, int32_t *status);
+int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
+                              const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status);
+/* the last region call on the handle: the selected tiles that were handed to the decoder (those of the NHW_OK rects and of the rects that
+ * failed on a refused tile) and the tile-file bytes uploaded for them */
+int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded);
 /* hipEvent timings of the last nhw_dec_batch_device call (events on its launch stream): the whole sequence, the entropy stages
  * (parse, prefix-code walk, un-zig-zag), the two level-1 luma synthesis passes and the colour kernel -- the last three are the kernels
  * SURVEY.md 8(d) prices against the HBM roofline for the decode path */

@@ -81,6 +81,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_sse_pictures_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]
     L.nhw_enc_fit_pictures.argtypes = [P, P, P, P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P]
     L.nhw_enc_fit_sse_pictures.argtypes = [P, P, P, P, P, P, ctypes.c_int, P, P, ctypes.c_int, P, ctypes.c_size_t, P, P, P, P]
+    L.nhw_region_tiles.argtypes = [ctypes.c_uint32] * 6
+    L.nhw_untile_regions_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_dec_regions.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, P, P, P]
+    L.nhw_dec_regions_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, P, P, P]
+    L.nhw_dec_last_region_stats.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     return L
 
 
@@ -137,6 +142,21 @@ def picture_tiles(width: int, height: int) -> int:
     if not (1 <= width <= 65535 and 1 <= height <= 65535):
         raise NhwError(f"a picture side must be 1..65535, got {width} x {height}")
     return ((width + 511) // 512) * ((height + 511) // 512)
+
+
+# ---------------------------------------------------------------- a rectangle of a picture from the tiles it touches
+REGION_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("x", "<u4"), ("y", "<u4"), ("width", "<u4"), ("height", "<u4"), ("pic_width", "<u4"),
+                ("pic_height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_region
+RECT_DTYPE = [("container", "<u4"), ("x", "<u4"), ("y", "<u4"), ("width", "<u4"), ("height", "<u4")]   # nhw_rect
+
+
+def region_tiles(pic_width: int, pic_height: int, x: int, y: int, width: int, height: int) -> int:
+    """the tiles the region x, y, width, height of a pic_width x pic_height picture selects (nhw_region_tiles): columns x // 512 ..
+    (x + width - 1) // 512 times rows y // 512 .. (y + height - 1) // 512"""
+    picture_tiles(pic_width, pic_height)
+    if not (width >= 1 and height >= 1 and x >= 0 and y >= 0 and x + width <= pic_width and y + height <= pic_height):
+        raise NhwError(f"the region {x}, {y}, {width} x {height} is empty or not inside the {pic_width} x {pic_height} picture")
+    return ((x + width - 1) // 512 - x // 512 + 1) * ((y + height - 1) // 512 - y // 512 + 1)
 
 
 def _picture_table(pictures, what):
@@ -755,6 +775,75 @@ class Decoder:
         if (status != 0).any():
             raise NhwError(f"per-container status {status.tolist()}")
         return [out[int(out_off[i]):int(out_off[i + 1])].reshape(h, w, 3) for i, (w, h) in enumerate(shapes)]
+
+    def _region_args(self, containers, rects, what):
+        """the packed containers and the checked nhw_rect table of a region call -> (blob, offsets, rect table)"""
+        import numpy as np
+        if len(containers) < 1 or len(rects) < 1:
+            raise NhwError(f"{what} wants a non-empty list of containers and a non-empty list of (container, x, y, w, h)")
+        offs = np.zeros(len(containers) + 1, np.uint64)
+        offs[1:] = np.cumsum([len(c) for c in containers])
+        blob = np.frombuffer(b"".join(bytes(c) for c in containers), np.uint8)
+        table = np.zeros(len(rects), RECT_DTYPE)
+        for i, r in enumerate(rects):
+            if len(r) != 5 or not all(isinstance(v, numbers.Integral) and 0 <= v <= 0xFFFFFFFF for v in r):
+                raise NhwError(f"{what}: rect {i} must be (container, x, y, w, h), integers of 32 bits, got {r!r}")
+            table[i] = tuple(int(v) for v in r)
+        return blob, offs, table
+
+    def _region_raise(self, status):
+        if (status != 0).any():
+            raise NhwError(f"per-region status {status.tolist()}")
+
+    def decode_regions(self, containers, rects):
+        """Rectangles of .nhwp pictures from only the tiles they touch (nhw_dec_regions): containers a list of containers (bytes), rects a
+        sequence of (container index, x, y, w, h) in the coordinates of decode_pictures' arrays -> a list of numpy uint8 [h, w, 3], region i
+        equal to decode_pictures(containers)[container][y:y + h, x:x + w].  Raises on any status that is not NHW_OK."""
+        import numpy as np
+        blob, offs, table = self._region_args(containers, rects, "decode_regions")
+        n = len(table)
+        out_off = np.zeros(n + 1, np.uint64)
+        out_off[1:] = np.cumsum(3 * table["width"].astype(np.uint64) * table["height"].astype(np.uint64))
+        out = np.empty(max(int(out_off[n]), 1), np.uint8)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_dec_regions(self.h, blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, out.ctypes.data,
+                                           out_off.ctypes.data, status.ctypes.data))
+        self._region_raise(status)
+        return [out[int(out_off[i]):int(out_off[i + 1])].reshape(int(r["height"]), int(r["width"]), 3) for i, r in enumerate(table)]
+
+    def decode_regions_device(self, containers, rects, out=None):
+        """decode_regions with the pixels left on the device (nhw_dec_regions_to_device): -> a list of uint8 CUDA tensors [h, w, 3] on this
+        decoder's device.  out: a list of preallocated tensors, one a rect, with strides (pitch >= 3 w, 3, 1) -- views into an [n, h, w, 3]
+        batch tensor work --, which are filled and returned.  The work is ordered after torch's current stream and complete on return."""
+        import numpy as np
+        t = self.torch
+        blob, offs, table = self._region_args(containers, rects, "decode_regions_device")
+        n = len(table)
+        dev = t.device("cuda", self.device)
+        if out is None:
+            out = [t.empty((int(r["height"]), int(r["width"]), 3), dtype=t.uint8, device=dev) for r in table]
+        elif not isinstance(out, (list, tuple)) or len(out) != n:
+            raise NhwError(f"decode_regions_device: `out` must be a list of {n} tensors")
+        addr, pitch = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
+        for i, (x, r) in enumerate(zip(out, table)):
+            h, w = int(r["height"]), int(r["width"])
+            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device == dev and x.dtype == t.uint8 and tuple(x.shape) == (h, w, 3)):
+                raise NhwError(f"decode_regions_device: out[{i}] is not a uint8 tensor [{h}, {w}, 3] on {dev}")
+            if x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w):
+                raise NhwError(f"decode_regions_device: out[{i}] must have strides (pitch >= 3 w, 3, 1), got {tuple(x.stride())}")
+            addr[i], pitch[i] = x.data_ptr(), x.stride(0) if h > 1 else 3 * w
+        status = np.empty(n, np.int32)
+        t.cuda.current_stream(dev).synchronize()                     # the call runs on the handle's own stream and waits for it
+        self._chk(self.lib.nhw_dec_regions_to_device(self.h, blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, addr.ctypes.data,
+                                                     pitch.ctypes.data, status.ctypes.data))
+        self._region_raise(status)
+        return list(out)
+
+    def region_stats(self):
+        """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region call (nhw_dec_last_region_stats)"""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._chk(self.lib.nhw_dec_last_region_stats(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def decode(self, files):
         """files: list of .nhw byte strings -> (uint8 [n,512,512,3] in nhw-dec's output byte order, quality list)."""

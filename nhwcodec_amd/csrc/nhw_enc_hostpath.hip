@@ -107,6 +107,13 @@ extern "C" int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture
 	return NHW_OK;
 }
 
+extern "C" int nhw_untile_regions_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, void *stream)
+{
+	if (const int rc = picture_args(d_regs, n_regs, tile0, m, d_tiles, "nhw_untile_regions_device")) return rc;
+	HIPCHK(nhw_launch_untile_region((const uint8_t *)d_tiles, d_regs, n_regs, tile0, m, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 extern "C" int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, void *stream)
 {
 	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_sse_pictures_device")) return rc;

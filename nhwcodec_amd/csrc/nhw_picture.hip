@@ -1,6 +1,7 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11, 12): the padding kernel k_tile_pad, its inverse
- * k_untile_crop, the picture-cropped error k_sse_crop, and the .nhwp container that holds a picture's width, height and tile files.
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11, 12, 13): the padding kernel k_tile_pad, its inverse
+ * k_untile_crop, the rectangle-of-a-picture crop k_untile_region, the picture-cropped error k_sse_crop, and the .nhwp container that
+ * holds a picture's width, height and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
  * ny = ceil(H / 512), by edge replication: padded pixel (r, c) = picture pixel (min(r, H - 1), min(c, W - 1)).  Tile (ty, tx) is padded
@@ -244,6 +245,62 @@ __global__ __launch_bounds__(TP_THREADS) void k_sse_crop(const uint8_t *__restri
 	}
 }
 
+/* ---- a rectangle of a picture from the tiles it touches ----
+ * the region holding tile t of the call's running selection: the last descriptor with first_tile <= t (find_picture's search on the
+ * 48-byte descriptors) */
+__device__ __forceinline__ int find_region(const nhw_region *regs, int n, uint32_t t)
+{
+	int lo = 0, hi = n;
+	const int lane = threadIdx.x & 63;
+	while (hi - lo > 1) {
+		const int step = (hi - lo + 63) / 64, idx = lo + lane * step;
+		const bool le = idx < hi && regs[idx].first_tile <= t;
+		const int c = __popcll(__ballot(le));
+		lo += (c > 0 ? c - 1 : 0) * step;
+		hi = lo + step < hi ? lo + step : hi;
+	}
+	return __builtin_amdgcn_readfirstlane(lo);
+}
+
+/* Selected tile (ty, tx) of a region x, y, w, h: tile row rr is picture row 512 ty + rr, wanted if y <= row < y + h; of it the picture
+ * columns [c0, c1) = [max(512 tx, x), min(512 tx + 512, x + w)) go from tile byte 3 (c0 - 512 tx) of the row to destination byte
+ * 3 (c0 - x) of destination row (row - y).  The same copy as k_untile_crop -- the 16-byte-aligned destination words that cover the
+ * bytes, whole ones as dwordx4, the ragged head and tail with store_part, the tile side through fetch -- but the source starts anywhere
+ * inside a tile row, so the two sides have independent phases, and the words a row needs (at most seg / 16 + 2) depend on the region:
+ * the band's wanted rows x that many slots are dealt out flat over the threads (slot -> row by a multiply-high with the reciprocal,
+ * exact for the 32 x 97 slots a band can have), so that a 224-pixel crop does not walk 97 slots a row. */
+__global__ __launch_bounds__(TP_THREADS) void k_untile_region(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs, int tile0)
+{
+	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
+	const nhw_region g = regs[find_region(regs, n_regs, t)];
+	if (!g.width || !g.height || t < g.first_tile) return;
+	if (g.pic_width > 65535 || g.pic_height > 65535 || (uint64_t)g.x + g.width > g.pic_width || (uint64_t)g.y + g.height > g.pic_height) return;   /* not a region of a picture */
+	const uint32_t tx0 = g.x / 512, ty0 = g.y / 512, nx = (g.x + g.width - 1) / 512 - tx0 + 1, ny = (g.y + g.height - 1) / 512 - ty0 + 1;
+	const uint32_t in = t - g.first_tile;
+	if (in >= nx * ny) return;
+	const uint32_t ty = ty0 + in / nx, tx = tx0 + in % nx;
+	/* the band's rows inside the region: tile rows [r0, r1) */
+	const uint32_t top = 512 * ty + (blockIdx.x % TP_BANDS) * TP_ROWS;   /* picture row of the band's first row */
+	const uint32_t lo = top > g.y ? top : g.y, hi = top + TP_ROWS < g.y + g.height ? top + TP_ROWS : g.y + g.height;
+	if (lo >= hi) return;                                                /* a band with no row inside the region */
+	const uint32_t c0 = 512 * tx > g.x ? 512 * tx : g.x, c1 = 512 * tx + 512 < g.x + g.width ? 512 * tx + 512 : g.x + g.width;
+	const int seg = 3 * (int)(c1 - c0);                                  /* 3 .. 1536 bytes a row */
+	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES) + (uintptr_t)(lo - 512 * ty) * 1536 + 3 * (c0 - 512 * tx);
+	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
+	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = (hi - lo) * slots;   /* 2 .. 97 words cover seg bytes at any phase */
+	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots */
+	for (uint32_t i = threadIdx.x; i < total; i += TP_THREADS) {
+		const uint32_t q = __umulhi(i, rcp), k = i - q * slots;            /* row q of the band's wanted rows, word k of it */
+		const uintptr_t D0 = dst + (uint64_t)q * g.pitch, D1 = D0 + seg;
+		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
+		if (A >= D1) continue;
+		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
+		const uint4 v = fetch(src + (uintptr_t)q * 1536 + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
+		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
+		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
+	}
+}
+
 } /* namespace */
 
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
@@ -255,6 +312,12 @@ hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0,
 hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s)
 {
 	k_untile_crop<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	return hipGetLastError();
+}
+
+hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, hipStream_t s)
+{
+	k_untile_region<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, tile0);
 	return hipGetLastError();
 }
 
@@ -272,6 +335,14 @@ extern "C" int nhw_picture_tiles(uint32_t width, uint32_t height)
 {
 	if (width < 1 || width > 65535 || height < 1 || height > 65535) return NHW_E_ARG;
 	return (int)(((width + 511) / 512) * ((height + 511) / 512));
+}
+
+/* the tiles a region x, y, w, h of a W x H picture selects: columns x / 512 .. (x + w - 1) / 512 times rows y / 512 .. (y + h - 1) / 512 */
+extern "C" int nhw_region_tiles(uint32_t pic_width, uint32_t pic_height, uint32_t x, uint32_t y, uint32_t width, uint32_t height)
+{
+	if (nhw_picture_tiles(pic_width, pic_height) < 1 || width < 1 || height < 1) return NHW_E_ARG;
+	if ((uint64_t)x + width > pic_width || (uint64_t)y + height > pic_height) return NHW_E_ARG;
+	return (int)(((x + width - 1) / 512 - x / 512 + 1) * ((y + height - 1) / 512 - y / 512 + 1));
 }
 
 /* A well-formed container: magic, version 1, zero reserved bytes, W and H in 1..65535, T = nhw_picture_tiles(W, H) lengths of 1 ..

@@ -7,7 +7,8 @@
  * write_image_bmp (:108-291) writes them.  Exit codes: 0 ok, 1 cannot read / write a file (the reference prints and
  * carries on into undefined behaviour), 3 not an .nhw file (reference: "Not an .nhw file", exit(-1)).
  * Extension: --batch <dir> decodes every *.nhw of a directory to <name>.bmp in one GPU batch; --picture <in.nhwp> <out.bmp> decodes a
- * container of nhw-enc --picture to a bottom-up 24-bit BMP of the picture's own size.
+ * container of nhw-enc --picture to a bottom-up 24-bit BMP of the picture's own size; with --region X,Y,W,H behind it, only that rectangle
+ * (X, Y from the left and the top of the picture as a viewer shows it), decoded from the tiles it touches.
  */
 #include <dirent.h>
 #include <stdint.h>
@@ -30,7 +31,8 @@ static void show_usage(void)
 	"  batch:   nhw-dec --batch <directory of .nhw files>\n"
 	"  tiles:   nhw-dec --tiles <rows> <columns> <stem> <image.bmp>   (joins <stem>_y<r>_x<c>.nhw, as written by nhw-enc --tiles)\n"
 	"  tar:     nhw-dec --tar <in.tar> <out.tar>   (every x.nhw member of a ustar archive -> member x.bmp, in order)\n"
-	"  picture: nhw-dec --picture <in.nhwp> <image.bmp>   (a container of nhw-enc --picture, any size)\n",
+	"  picture: nhw-dec --picture <in.nhwp> <image.bmp>   (a container of nhw-enc --picture, any size)\n"
+	"  region:  nhw-dec --picture <in.nhwp> <image.bmp> --region X,Y,W,H   (that rectangle only, X,Y from the top left; decodes the tiles it touches)\n",
 	PROGRAM);
 }
 
@@ -142,9 +144,26 @@ static int decode_tiles(int ny, int nx, const char *stem, const char *out_path)
 	return 0;
 }
 
+/* --region X,Y,W,H: four decimal numbers, nothing else; 0 if the argument is one */
+static int parse_region(const char *arg, uint32_t reg[4])
+{
+	int i;
+	for (i = 0; i < 4; i++) {
+		unsigned long v = 0;
+		int digits = 0;
+		for (; *arg >= '0' && *arg <= '9'; arg++, digits++) { v = v * 10 + (unsigned long)(*arg - '0'); if (v > 0xFFFFFFFFul) return 1; }
+		if (!digits || *arg != (i < 3 ? ',' : '\0')) return 1;
+		arg++;
+		reg[i] = (uint32_t)v;
+	}
+	return 0;
+}
+
 /* --picture: the inverse of nhw-enc --picture.  The container's tiles are decoded and cropped by the library (nhw_dec_pictures); the
- * rows go out under the reference's 54-byte header with the size fields of the picture, each padded to 4 bytes. */
-static int decode_picture(const char *in_path, const char *out_path)
+ * rows go out under the reference's 54-byte header with the size fields of the picture, each padded to 4 bytes.  With a region (X, Y from
+ * the top left as a viewer shows the BMP, W, H; NULL: the whole picture) only the tiles it touches are decoded (nhw_dec_regions): the files
+ * are bottom-up, so it is the library's rows H - Y - Hr .. H - Y - 1, and the BMP is that rectangle of the whole picture's BMP. */
+static int decode_picture(const char *in_path, const char *out_path, const uint32_t *region)
 {
 	uint8_t *blob = NULL, *pix, hdr[54], pad[3] = { 0, 0, 0 };
 	size_t len = 0;
@@ -152,10 +171,26 @@ static int decode_picture(const char *in_path, const char *out_path)
 	uint64_t off[2], out_off[1] = { 0 };
 	int32_t status = 0;
 	nhw_dec *d = NULL;
+	nhw_rect rect;
 	int t;
 	FILE *f;
 	if (read_file(in_path, &blob, &len)) return 1;
 	if (nhw_picture_info(blob, len, &width, &height) != NHW_OK) { printf("\nNot an .nhwp file\n"); free(blob); return 3; }
+	if (region) {
+		t = NHW_E_ARG;
+		if (region[3] >= 1 && (uint64_t)region[1] + region[3] <= height) {
+			rect.container = 0; rect.x = region[0]; rect.y = height - region[1] - region[3]; rect.width = region[2]; rect.height = region[3];
+			t = nhw_region_tiles(width, height, rect.x, rect.y, rect.width, rect.height);
+		}
+		if (t < 1) {
+			fprintf(stderr, "%s: --region %u,%u,%u,%u is empty or not inside the %u x %u picture\n", PROGRAM, (unsigned)region[0], (unsigned)region[1],
+			        (unsigned)region[2], (unsigned)region[3], (unsigned)width, (unsigned)height);
+			free(blob);
+			return 1;
+		}
+		width = rect.width; height = rect.height;
+	}
+	else t = nhw_picture_tiles(width, height);
 	row = width * 3; stride = (row + 3) & ~3u;
 	if ((uint64_t)stride * height + 54u > 0xFFFFFFFFull) {           /* the BMP header's 32-bit size fields */
 		fprintf(stderr, "%s: a %u x %u picture does not fit a BMP file (4 GiB)\n", PROGRAM, (unsigned)width, (unsigned)height);
@@ -163,10 +198,10 @@ static int decode_picture(const char *in_path, const char *out_path)
 		return 1;
 	}
 	bytes = stride * height;
-	t = nhw_picture_tiles(width, height);
 	pix = (uint8_t *)malloc((size_t)row * height);
 	off[0] = 0; off[1] = len;
-	if (!pix || nhw_dec_create(0, t < 1024 ? t : 1024, &d) || nhw_dec_pictures(d, blob, off, 1, pix, out_off, &status)) {
+	if (!pix || nhw_dec_create(0, t < 1024 ? t : 1024, &d) ||
+	    (region ? nhw_dec_regions(d, blob, off, 1, &rect, 1, pix, out_off, &status) : nhw_dec_pictures(d, blob, off, 1, pix, out_off, &status))) {
 		fprintf(stderr, "%s: GPU decoder unavailable: %s\n", PROGRAM, nhw_dec_last_error());
 		return 2;
 	}
@@ -187,7 +222,7 @@ static int decode_picture(const char *in_path, const char *out_path)
 	}
 	fclose(f);
 	free(pix);
-	printf("%u x %u picture\n", (unsigned)width, (unsigned)height);
+	printf(region ? "%u x %u region\n" : "%u x %u picture\n", (unsigned)width, (unsigned)height);
 	return 0;
 }
 
@@ -288,6 +323,14 @@ static int decode_tar(const char *in_path, const char *out_path)
 
 int main(int argc, char **argv)
 {
+	int a;
+	for (a = 1; a < argc; a++)                                        /* --region: behind --picture <in> <out> only, checked before any file is touched */
+		if (!strncmp(argv[a], "--region", 8)) {
+			uint32_t reg[4];
+			if (strcmp(argv[a], "--region") || strcmp(argv[1], "--picture") || a != 4) { fprintf(stderr, "%s: --region X,Y,W,H goes behind --picture <in.nhwp> <image.bmp>\n", PROGRAM); return 1; }
+			if (argc != 6 || parse_region(argv[5], reg)) { fprintf(stderr, "%s: --region wants X,Y,W,H: four decimal numbers\n", PROGRAM); return 1; }
+			return decode_picture(argv[2], argv[3], reg);
+		}
 	if (argc < 3) { show_usage(); return 0; }
 	if (!strcmp(argv[1], "--tar")) {
 		if (argc < 4) { show_usage(); return 1; }
@@ -295,7 +338,7 @@ int main(int argc, char **argv)
 	}
 	if (!strcmp(argv[1], "--picture")) {
 		if (argc < 4) { show_usage(); return 1; }
-		return decode_picture(argv[2], argv[3]);
+		return decode_picture(argv[2], argv[3], NULL);
 	}
 	if (!strcmp(argv[1], "--tiles")) {
 		int ny, nx;
