@@ -44,6 +44,11 @@ int nhw_dec_debug_slice_order(nhw_dec *d, int mode);
  * the counterpart of nhw_debug_read) and read them behind the call. */
 int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, void *stream);
 int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes);
+/* The luma plane's first closed loop for the first n images of the handle's last whole batch, at that batch's quality (7 .. 23), on B_JPEG, B_PROC,
+ * B_LL1 and B_L2SAVE as they stand.  form 0: the production launches from the first level-2 analysis to the second; form 1: their last part
+ * alone (synthesis, Y8, Y9 and, for q > 12 on the same LDS residency, the second analysis with Y13's copy); form 2: the staged kernels for
+ * form 1's part; form 3: the staged kernels for form 0's part; form 4: form 3 stopped behind the synthesis; form 5: the staged synthesis alone. */
+int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream);
 
 /* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip) */
 void nhw_dec_debug_stop_after(nhw_dec *d, int stage);

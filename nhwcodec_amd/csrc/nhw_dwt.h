@@ -1,5 +1,5 @@
 /*
- * nhw_dwt.h -- what the block-resident filterbank kernels share (nhw_front.hip: k_dwt_ana / k_dwt_syn; nhw_tail.hip: k_l2_recon).
+ * nhw_dwt.h -- what the block-resident filterbank kernels share (nhw_front.hip: k_dwt_ana / k_dwt_syn; nhw_tail.hip: k_l2_recon, k_chroma_loops).
  */
 #ifndef NHW_DWT_H
 #define NHW_DWT_H
@@ -88,7 +88,18 @@ __device__ __forceinline__ s16x2 pk_diffuse(s16x2 r)
 	return (d ^ s) - s;
 }
 
-/* The first direction (filters.c:40-86) of one line held two cells to a dword, a lane its own pair (cells 2k, 2k+1, k = lane + 64 u): the pair on the
+/* The first direction's two un-normalised taps (filters.c:40-86) of one pair of cells (2k, 2k+1) of a line: d the pair, pv the pair before it, nx the
+ * pair behind it (only its first cell counts; the line's last pair hands in itself: x[S] = x[S - 2]).  first: the line's first pair. */
+__device__ __forceinline__ void ana_row_taps(uint32_t d, uint32_t pv, uint32_t nx, bool first, int *lo, int *hi)
+{
+	const int e0 = (int16_t)(d & 0xFFFF), o0 = (int)d >> 16, e1 = (int16_t)(nx & 0xFFFF);
+	int em1 = (int16_t)(pv & 0xFFFF), om1 = (int)pv >> 16;
+	if (first) { em1 = e1; om1 = o0; }                             /* x[-2] = x[2], x[-1] = x[1] */
+	*lo = 6 * e0 + 2 * (om1 + o0) - (em1 + e1);
+	*hi = (o0 << 1) - (e0 + e1);                                   /* the last one: (x[S-1] - x[S-2]) << 1, which is what e1 = e0 gives */
+}
+
+/* The first direction of one line held two cells to a dword, a lane its own pair (cells 2k, 2k+1, k = lane + 64 u): the pair on the
  * left and the first cell on the right come over the lanes (DPP shifts by one lane, the seam between the two halves of a 256-cell line through a
  * readlane).  lo / hi: the un-normalised taps the pair leaves. */
 template <int PPL>
@@ -101,12 +112,19 @@ __device__ __forceinline__ void ana_row_pair(const uint32_t (&Dw)[PPL], int lane
 		if (u > 0) { const uint32_t seam = (uint32_t)__builtin_amdgcn_readlane((int)Dw[u > 0 ? u - 1 : 0], 63); if (lane == 0) pv = seam; }
 		if (u + 1 < PPL) { const uint32_t seam = (uint32_t)__builtin_amdgcn_readlane((int)Dw[u + 1 < PPL ? u + 1 : u], 0); if (lane == 63) nx = seam; }
 		else if (lane == 63) nx = Dw[u];                           /* x[S] = x[S - 2] */
-		const int e0 = (int16_t)(Dw[u] & 0xFFFF), o0 = (int)Dw[u] >> 16, e1 = (int16_t)(nx & 0xFFFF);
-		int em1 = (int16_t)(pv & 0xFFFF), om1 = (int)pv >> 16;
-		if (u == 0 && lane == 0) { em1 = e1; om1 = o0; }           /* x[-2] = x[2], x[-1] = x[1] */
-		lo[u] = 6 * e0 + 2 * (om1 + o0) - (em1 + e1);
-		hi[u] = (o0 << 1) - (e0 + e1);                             /* the last one: (x[S-1] - x[S-2]) << 1, which is what e1 = e0 gives */
+		ana_row_taps(Dw[u], pv, nx, u == 0 && lane == 0, &lo[u], &hi[u]);
 	}
+}
+
+/* The same of a 256-cell line held FOUR adjacent cells to a lane (a, b: cells 4 lane .. 4 lane + 3, as k_l2_recon's Y9 leaves a row): lo / hi [0] are
+ * the taps of pair 2 lane, [1] those of pair 2 lane + 1.  Only the pair before a and the first cell behind b come over the lanes. */
+__device__ __forceinline__ void ana_row_quad(uint32_t a, uint32_t b, int lane, int (&lo)[2], int (&hi)[2])
+{
+	const uint32_t pv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)b, 0x138 /* wave_shr:1 */, 0xF, 0xF, false);
+	uint32_t nx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
+	if (lane == 63) nx = b;                                        /* x[S] = x[S - 2] */
+	ana_row_taps(a, pv, b, lane == 0, &lo[0], &hi[0]);
+	ana_row_taps(b, a, nx, false, &lo[1], &hi[1]);
 }
 
 /* The second direction (filters.c:88-287) of two columns at once: Ew / Ow hold the even / odd rows' cells of the two columns, a lane its own row pair

@@ -182,6 +182,37 @@ static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hi
 	return 1;
 }
 
+/* the luma plane's launches from the first level-2 analysis to the second, on stream s (run_batch; nhw_stage_luma_loop).  1 = carry on;
+ * NHW_OK: the debug stop fell in here */
+static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage)
+{
+	const int q = ws.q;
+	int16_t *jpeg = plane16(ws, B_JPEG), *proc = plane16(ws, B_PROC);
+	const size_t ps = ws.stride[B_JPEG] / 2;
+	uint8_t *out = nullptr; uint32_t *d_sizes = nullptr; int32_t *d_status = nullptr;   /* (these phases write none of them) */
+	/* Y4: level-2 analysis (:139) */
+	/* the LL rows come from ll1 (the front's copy of them in natural orientation, res256): the front does not write them into the work plane as well
+	 * outside the stage checks, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane) */
+	nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, H);
+	STAGE_DONE();
+	if (q > 6) {                                                     /* first closed loop (:141-283) */
+	nhw_launch_phase(PH_L1, ws, 0, out, d_sizes, d_status, s);
+	nhw_launch_wave(WV_DQ1, ws, s);          /* every quality (1..16: rationed low bits, no marking passes) */
+	STAGE_DONE();
+	if (ws.dbg) {
+	nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s);
+	STAGE_DONE();
+	nhw_launch_phase(PH_L2, ws, 0, out, d_sizes, d_status, s);
+	STAGE_DONE();
+	} else nhw_launch_l2_recon(jpeg, proc, ps, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, n, s,   /* synthesis + Y8 + Y9 on one residency of the block; the stage checks take the three kernels */
+	                           q > 12 ? plane16(ws, B_L2SAVE) : nullptr, ws.stride[B_L2SAVE] / 2);   /* q > 12: + the second analysis and Y13 (:623-631), still on that residency */
+	if (q <= 12) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);   /* (Y11 / Y12 follow, and Y13's copy behind them) */
+	else if (ws.dbg) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, plane16(ws, B_L2SAVE), ws.stride[B_L2SAVE] / 2, H, 1);   /* + Y13: copy of the coefficient block */
+	STAGE_DONE();
+	}
+	return 1;
+}
+
 /* the whole launch sequence for the images of one workspace view on one stream; `timed`: record the stage events of nhw_timing */
 static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, hipStream_t s,
                      int timed /* 0: no events, 1: EV_START .. EV_END (whole batch), 2: EV_LUMA, EV_CHROMA (tail of the first sub-batch; the caller closes with EV_END) */,
@@ -256,25 +287,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		CHROMA(chroma_head(0));
 		CHROMA(chroma_head(1));                                      /* V's head in planes of its own, right behind U's: U's quantiser waits for the luma tail, and this stream stood idle until then (2 ms of a q20 step).  (Measured and not taken: V's head on a stream of its own beside U's, +0.3 ms; V's head held back until the second dequantiser simulation is through, +0.4 ms.) */
 	}
-	/* Y4: level-2 analysis (:139) */
-	/* the LL rows come from ll1 (the front's copy of them in natural orientation, res256): the front does not write them into the work plane as well
-	 * outside the stage checks, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane) */
-	nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, H);
-	STAGE_DONE();
-	if (q > 6) {                                                     /* first closed loop (:141-283) */
-	nhw_launch_phase(PH_L1, ws, 0, out, d_sizes, d_status, s);
-	nhw_launch_wave(WV_DQ1, ws, s);          /* every quality (1..16: rationed low bits, no marking passes) */
-	STAGE_DONE();
-	if (ws.dbg) {
-	nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s);
-	STAGE_DONE();
-	nhw_launch_phase(PH_L2, ws, 0, out, d_sizes, d_status, s);
-	STAGE_DONE();
-	} else nhw_launch_l2_recon(jpeg, proc, ps, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, n, s);   /* synthesis + Y8 + Y9 on one residency of the block; the stage checks take the three kernels */
-	if (q > 12) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, plane16(ws, B_L2SAVE), ws.stride[B_L2SAVE] / 2, H, 1);   /* + Y13 (:623-631): copy of the coefficient block */
-	else nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);
-	STAGE_DONE();
-	}
+	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12) */
 	if (q <= 12) {                                                   /* Y11 (q <= 11), Y12, then Y13 */
 		nhw_launch_low_ll2(proc, ps, q, n, s);
 		nhw_launch_copy_block(proc, ps, W, plane16(ws, B_L2SAVE), ws.stride[B_L2SAVE] / 2, H, H, H, n, s);
@@ -571,6 +584,52 @@ extern "C" int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, voi
 		if (k > 4) nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, s, cl2save, ws.stride[B_CL2SAVE] / 2, H / 2, 1);
 		if (k > 5) nhw_launch_phase(PH_C4, ws, comp, nullptr, nullptr, nullptr, s);
 		if (k > 6) nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, s);
+	}
+	HIPCHK(hipGetLastError());
+	return NHW_OK;
+}
+
+/* A test hook for the luma plane's first closed loop, on B_JPEG, B_PROC, B_LL1 and B_L2SAVE as they stand (a test writes them: nhw_debug_write), for
+ * the first n images of the handle's last whole batch at that batch's quality (7 .. 23: below it there is no first closed loop).
+ *   form 0: the production launches from the first level-2 analysis to the second (luma_loop_launches);
+ *   form 1: their last part alone, from the synthesis on: k_l2_recon<true> for q > 12, k_l2_recon<false> and the analysis below it;
+ *   form 2: the staged kernels for form 1's part (synthesis, Y8 + Y9, analysis + Y13's copy), every plane stored;
+ *   form 3: the staged kernels for form 0's part; form 4: the same, stopped behind the synthesis (proc = the reconstruction before Y8's nudges,
+ *           B_LL1 with Y5's tags); form 5: the staged synthesis alone. */
+extern "C" int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream)
+{
+	if (!e || n < 1 || n > e->max_batch || form < 0 || form > 5) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after || e->last_q < 7) {
+		nhw_enc_err = "nhw_stage_luma_loop: needs a completed whole batch of >= n images at quality >= 7 and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = 0;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	int16_t *jpeg = plane16(ws, B_JPEG), *proc = plane16(ws, B_PROC), *ll1 = plane16(ws, B_LL1), *l2save = plane16(ws, B_L2SAVE);
+	const size_t ps = ws.stride[B_JPEG] / 2;
+	const bool save = ws.q > 12;
+	if (form == 0) {
+		int stage = 0;
+		const int rc = luma_loop_launches(e, ws, n, s, stage);
+		if (rc != 1) return rc;
+	} else if (form == 1) {
+		nhw_launch_l2_recon(jpeg, proc, ps, ll1, ws.stride[B_LL1] / 2, n, s, save ? l2save : nullptr, ws.stride[B_L2SAVE] / 2);
+		if (!save) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);
+	} else {
+		if (form == 3 || form == 4) {
+			nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, ll1, ws.stride[B_LL1] / 2, H);
+			nhw_launch_phase(PH_L1, ws, 0, nullptr, nullptr, nullptr, s);
+			nhw_launch_wave(WV_DQ1, ws, s);
+		}
+		nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s);
+		if (form < 4) {
+			nhw_launch_phase(PH_L2, ws, 0, nullptr, nullptr, nullptr, s);
+			if (save) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, l2save, ws.stride[B_L2SAVE] / 2, H, 1);
+			else nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);
+		}
 	}
 	HIPCHK(hipGetLastError());
 	return NHW_OK;

@@ -64,7 +64,7 @@ enum { PH_L1, PH_L2, PH_L3, PH_L4A, PH_C0, PH_C2, PH_C3, PH_C4, PH_C5, PH_FINAL,
 enum { WV_DQ1, WV_DQ0, WV_EMIT, WV_QUANT };
 void nhw_launch_phase(int ph, const NhwWs &ws, int comp, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s);
 void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s);
-void nhw_launch_l2_recon(int16_t *jpeg, const int16_t *proc, size_t plane_stride, int16_t *ll1, size_t ll1_stride, int n, hipStream_t s);
+void nhw_launch_l2_recon(int16_t *jpeg, int16_t *proc, size_t plane_stride, int16_t *ll1, size_t ll1_stride, int n, hipStream_t s, int16_t *l2save = nullptr, size_t save_stride = 0);
 void nhw_launch_chroma_loops(int16_t *cproc, size_t plane_stride, int16_t *cll1, size_t ll1_stride, int16_t *cl2save, size_t save_stride,
                              const uint8_t *pu, size_t pu_stride, int q, int comp, int compat, int n, hipStream_t s);   /* both chroma closed loops of one component, from cll1 */
 void nhw_launch_copy_block(const int16_t *src, size_t src_plane, int src_row, int16_t *dst, size_t dst_plane, int dst_row, int rows, int cols, int n, hipStream_t s);

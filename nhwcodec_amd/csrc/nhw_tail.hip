@@ -121,8 +121,23 @@ void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s)
  *   * Y9 walks a row of proc = a column of the block (odd dword stride: no bank conflicts), a lane four cells, the step handed from lane to
  *     lane until nothing moves (precompensate_ll1_par).  Its two outer neighbours are cells of the planes outside the block.
  * One 1024-thread workgroup per CU works through the batch, the next block on its way in registers (k_dwt_syn).  The tests' stage checks
- * (nhw_debug_stop_after) run the three kernels instead, which leave every intermediate plane. */
-__global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, const int16_t *__restrict__ procb, size_t plane_stride, int16_t *__restrict__ ll1b, size_t ll1_stride, int n)
+ * (nhw_debug_stop_after) run the three kernels instead, which leave every intermediate plane.
+ *
+ * ANA (q > 12): the kernel carries on into the level-2 analysis of the pre-compensated block (nhw_encoder.c:281, k_dwt_ana<256> until then) and
+ * Y13's copy of the coefficient block.  The pre-compensated rows had one reader, a kernel of the same shape that loaded them into the same
+ * LDS: 0.54 GB out and 0.54 GB back in per 4096 images, a launch and a drain of a one-workgroup-a-CU grid.  Here they never leave the CU:
+ *   * Y9's wavefront reads only its own 16 columns of A (A[(c0 + k) * LS + r], r one of its 16 rows) and nobody else reads them behind the
+ *     barrier in front of Y9, so it may write into them while the others are still in Y9.  It filters the settled row in registers
+ *     (ana_row_quad: the analysis' first direction runs along an LL1 row) and parks output pos of row r at A[pos * LS + r];
+ *   * behind ONE barrier A[i][j] is cell (i, j) of the TRANSPOSED first-direction plane, which is what the work plane keeps
+ *     (jpeg[i * stride + j]: k_dwt_ana gathers it): a straight row copy.  The second direction runs along rows of A, and output row c is row
+ *     c of proc and of l2save.  A wavefront takes its own 16 rows through all three steps (copy, filter in place, copy), two rows at a
+ *     time: no further barrier, and every global store is 16 bytes a lane on whole 512-byte rows;
+ *   * the block of the work plane is still stored: wave_dequant_sim_luma writes only some cells of it.
+ * The arithmetic is ana_row_taps' and ana_col_pair's (nhw_dwt.h), as in k_dwt_ana. */
+template <bool ANA>
+__global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, int16_t *__restrict__ procb, size_t plane_stride, int16_t *__restrict__ ll1b, size_t ll1_stride, int n,
+                                                   int16_t *__restrict__ saveb, size_t save_stride)
 {
 	extern __shared__ __attribute__((aligned(16))) int16_t smem[];
 	constexpr int S = H, LS = S + 2, HLF = S / 2, PPL = HLF / 64, NT_ = 1024, NPRE = S * (S / 8) / NT_;
@@ -138,7 +153,7 @@ __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, 
 	}
 	for (int img = blockIdx.x; img < n; img += gridDim.x) {
 		int16_t *jp = jpegb + (size_t)img * plane_stride, *o = ll1b + (size_t)img * ll1_stride;
-		const int16_t *p = procb + (size_t)img * plane_stride;
+		int16_t *p = procb + (size_t)img * plane_stride;
 #pragma unroll
 		for (int u = 0; u < NPRE; u++) {
 			const int v = t + u * NT_, row = v / (S / 8), c8 = v % (S / 8);
@@ -169,6 +184,7 @@ __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, 
 			for (int u = 0; u < PPL; u++) reinterpret_cast<uint32_t *>(x)[lane + 64 * u] = (uint32_t)(uint16_t)e[u] | ((uint32_t)(uint16_t)od[u] << 16);
 		}
 		lds_barrier();
+#pragma unroll 4                                                   /* (unrolled 16 times the compiler keeps every column's addresses across the image loop and spills 20 - 29 dwords) */
 		for (int i = 0; i < 16; i++) {                             /* second direction along the columns, normalised, in place */
 			int16_t *x = A + wv * 16 + i;
 			int e[PPL], od[PPL];
@@ -239,14 +255,52 @@ __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, 
 			}
 			uint2 w;
 			w.x = (uint32_t)(uint16_t)(ov[0] + st[0]) | ((uint32_t)(uint16_t)(ov[1] + st[1]) << 16); w.y = (uint32_t)(uint16_t)(ov[2] + st[2]) | ((uint32_t)(uint16_t)(ov[3] + st[3]) << 16);
-			*reinterpret_cast<uint2 *>(jp + (size_t)r * W + c0) = w;
+			if (!ANA) *reinterpret_cast<uint2 *>(jp + (size_t)r * W + c0) = w;
+			else {                                                     /* analysis, first direction, of the row in hand: into my own column r */
+				int lo[2], hi[2];
+				ana_row_quad(w.x, w.y, lane, lo, hi);
+				int16_t *x = A + (2 * lane) * LS + r;
+				x[0] = (int16_t)lo[0]; x[LS] = (int16_t)lo[1]; x[HLF * LS] = (int16_t)hi[0]; x[(HLF + 1) * LS] = (int16_t)hi[1];
+			}
+		}
+		if (ANA) {
+			lds_barrier();                                         /* the transposed first-direction plane */
+			int16_t *save = saveb + (size_t)img * save_stride;
+			const int rr = lane >> 5, c8 = lane & 31;              /* the copies: two rows a turn, a lane eight cells */
+#pragma unroll 1
+			for (int i = 0; i < 8; i++) {                          /* my rows c, c + 1 = two columns of the first-direction plane (filters.c:88-287) */
+				const int c = r0 + 2 * i;
+				const uint32_t *g = reinterpret_cast<const uint32_t *>(A + (c + rr) * LS + 8 * c8);
+				*reinterpret_cast<uint4 *>(jp + (size_t)(c + rr) * W + 8 * c8) = make_uint4(g[0], g[1], g[2], g[3]);
+				uint32_t Ew[PPL], Ow[PPL];
+				int lo[PPL][2], hi[PPL][2];
+#pragma unroll
+				for (int u = 0; u < PPL; u++) {                        /* a dword of row c holds column c's even and odd cell: regrouped into ana_col_pair's two columns side by side */
+					const uint32_t a = reinterpret_cast<const uint32_t *>(A + c * LS)[lane + 64 * u], b = reinterpret_cast<const uint32_t *>(A + (c + 1) * LS)[lane + 64 * u];
+					Ew[u] = (a & 0xFFFFu) | (b << 16); Ow[u] = (a >> 16) | (b & 0xFFFF0000u);
+				}
+				ana_col_pair<PPL, HLF>(Ew, Ow, c < HLF, lane, lo, hi);
+				asm volatile("" ::: "memory");                         /* (the rows are read as dwords and written as shorts: the compiler keeps the order) */
+#pragma unroll
+				for (int h = 0; h < 2; h++) {
+					int16_t *x = A + (c + h) * LS;
+#pragma unroll
+					for (int u = 0; u < PPL; u++) { x[lane + 64 * u] = (int16_t)lo[u][h]; x[HLF + lane + 64 * u] = (int16_t)hi[u][h]; }
+				}
+				asm volatile("" ::: "memory");
+				const uint4 w = make_uint4(g[0], g[1], g[2], g[3]);   /* rows c, c + 1 of the coefficient block (written by this wavefront: LDS operations of a wavefront keep their order) */
+				*reinterpret_cast<uint4 *>(p + (size_t)(c + rr) * W + 8 * c8) = w;
+				*reinterpret_cast<uint4 *>(save + (size_t)(c + rr) * H + 8 * c8) = w;   /* Y13 (:623-631) */
+			}
 		}
 		lds_barrier();                                             /* the block is done with before the next one moves in */
 	}
 }
-void nhw_launch_l2_recon(int16_t *jpeg, const int16_t *proc, size_t plane_stride, int16_t *ll1, size_t ll1_stride, int n, hipStream_t s)
+void nhw_launch_l2_recon(int16_t *jpeg, int16_t *proc, size_t plane_stride, int16_t *ll1, size_t ll1_stride, int n, hipStream_t s,
+                         int16_t *l2save /* non-null: + the level-2 analysis of the pre-compensated block and its copy (rows of H cells) */, size_t save_stride)
 {
-	k_l2_recon<<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg, proc, plane_stride, ll1, ll1_stride, n);
+	if (l2save) k_l2_recon<true><<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg, proc, plane_stride, ll1, ll1_stride, n, l2save, save_stride);
+	else k_l2_recon<false><<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg, proc, plane_stride, ll1, ll1_stride, n, nullptr, 0);
 }
 
 /* Both closed loops of a chroma component on one LDS residency of its 128 x 128 level-2 block (nhw_encoder.c:2310-2370 for U, :2623-2680 for V):
@@ -429,8 +483,10 @@ int nhw_tail_set_attrs(const char **where)
 #define SETATTR(fn) do { const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fn), hipFuncAttributeMaxDynamicSharedMemorySize, 100 << 10); \
                          if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(" #fn ", MaxDynamicSharedMemorySize)"; return (int)e_; } } while (0)
 	SETATTR(k_phase<PH_L1>); SETATTR(k_phase<PH_L2>); SETATTR(k_phase<PH_L3>); SETATTR(k_phase<PH_C5>);
-	{ const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_l2_recon), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(H * (H + 2) * sizeof(int16_t) + 288));
-	  if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(k_l2_recon, MaxDynamicSharedMemorySize)"; return (int)e_; } }
+	for (const void *fn : { reinterpret_cast<const void *>(&k_l2_recon<false>), reinterpret_cast<const void *>(&k_l2_recon<true>) }) {
+		const hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(H * (H + 2) * sizeof(int16_t) + 288));
+		if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(k_l2_recon, MaxDynamicSharedMemorySize)"; return (int)e_; }
+	}
 #undef SETATTR
 	return 0;
 }
