@@ -50,7 +50,7 @@ int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes)
  * form 1's part; form 3: the staged kernels for form 0's part; form 4: form 3 stopped behind the synthesis; form 5: the staged synthesis alone. */
 int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream);
 
-/* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip) */
+/* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip, sized by dec_bytes there) */
 void nhw_dec_debug_stop_after(nhw_dec *d, int stage);
 int  nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size_t bytes);
 /* decoder: the colour matrix of write_image_bmp (nhw_decoder_cli.c:133-283) for quality q on n (Y, U, V) byte triples in device memory (n a

@@ -21,12 +21,10 @@
  * Everything is int16/uint8 arithmetic; the only floating point is the colour matrix (compiled with
  * -ffp-contract=off like the rest of the library).  No stage falls back to the host.
  */
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <climits>
+#include <assert.h>
 
-#include "nhw_host.h"
+#include "nhw_dec.h"
+#include "nhw_dwt.h"
 
 #define DW 512
 #define DH 256
@@ -41,11 +39,26 @@ enum {
 	D_META, D_LL, D_SPARE, D_P1, D_P3, D_P5, D_P6, D_MARKS, D_A, D_B, D_CA, D_CB, D_CU, D_SEG, D_NZG, D_COUNT
 };
 enum { P16_CAP = 65536 + 64, P6_CAP = 131072 + 64, PK_WORDS = 98304 /* sanity bound on the packet words of a file (the encoder's buffer holds 80000) */ };
-const size_t k_dec_bytes[D_COUNT] = {
-	/* META */ 512, /* LL */ 24832, /* SPARE */ 1024, /* P1 */ P16_CAP * 2, /* P3 */ P16_CAP * 2, /* P5 */ P16_CAP * 2, /* P6 */ (size_t)P6_CAP * 4,
-	/* MARKS */ 2 * DQ, /* A */ 8 * DQ + 8192, /* B: luma value list */ 16 * DQ + 8192, /* CA */ 2 * (2 * DQ + 4096), /* CB: chroma value list */ 8 * DQ + 8192, /* CU */ 2 * DQ,
-	/* SEG */ 5120, /* NZG: which 16-byte groups of plane A's rows are in memory (k_dec_expand), a 64-bit word a row */ 4096
-};
+/* bytes of buffer b per image: the one size list of host and device (an index that is no D_* is refused where the value is a constant, and asserts) */
+constexpr __host__ __device__ size_t dec_bytes(int b)
+{
+	switch (b) {
+	case D_META: return 512;
+	case D_LL: return 24832;
+	case D_SPARE: return 1024;
+	case D_P1: case D_P3: case D_P5: return P16_CAP * 2;
+	case D_P6: return (size_t)P6_CAP * 4;
+	case D_MARKS: return 2 * DQ;
+	case D_A: return 8 * DQ + 8192;
+	case D_B: return 16 * DQ + 8192;                              /* luma value list */
+	case D_CA: return 2 * (2 * DQ + 4096);
+	case D_CB: return 8 * DQ + 8192;                              /* chroma value list */
+	case D_CU: return 2 * DQ;
+	case D_SEG: return 5120;
+	case D_NZG: return 4096;                                      /* which 16-byte groups of plane A's rows are in memory (k_dec_expand), a 64-bit word a row */
+	}
+	assert(!"dec_bytes: not a D_* index"); return 0;
+}
 
 struct DecMeta {
 	int status, q, res_high;
@@ -68,16 +81,7 @@ struct DecWs {
 	const uint64_t *blob_off;  /* n offsets into it */
 	const uint32_t *blob_len;  /* n lengths */
 	int dense;                 /* a stage check is going to read plane A: every group of it is written (production leaves out the all-zero groups of the level-1 detail bands) */
-	template <typename T> __host__ __device__ T *buf(int b, int img) const { return (T *)(base + off[b] + (size_t)img * k_dec_bytes_dev(b)); }
-	__host__ __device__ static size_t k_dec_bytes_dev(int b)
-	{
-		switch (b) {
-		case D_META: return 512; case D_LL: return 24832; case D_SPARE: return 1024;
-		case D_P1: case D_P3: case D_P5: return P16_CAP * 2; case D_P6: return (size_t)P6_CAP * 4;
-		case D_MARKS: return 2 * DQ; case D_A: return 8 * DQ + 8192; case D_B: return 16 * DQ + 8192;
-		case D_CA: return 2 * (2 * DQ + 4096); case D_CB: return 8 * DQ + 8192; case D_SEG: return 5120; case D_NZG: return 4096; default: return 2 * DQ;
-		}
-	}
+	template <typename T> __host__ __device__ T *buf(int b, int img) const { return (T *)(base + off[b] + (size_t)img * dec_bytes(b)); }
 };
 
 /* plane A starts 4096 bytes into its buffer (the reference writes one cell in front of a plane in a corner case) */
@@ -102,6 +106,17 @@ DEV int16_t *plane_ca(const DecWs &ws, int img, int comp) { return ws.buf<int16_
 DEV int iabs(int v) { return v < 0 ? -v : v; }
 DEV int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 DEV int bit_of(const uint8_t *bytes, int nbytes, int k) { return (k >> 3) < nbytes ? (bytes[k >> 3] >> (7 - (k & 7))) & 1 : 0; }
+
+/* Exception samples (nhw_decoder.c:656-668, :943-981, :1231-1267): one byte string holds the luma plane's list, U's and V's behind one another, a list a run of
+ * triples (row, column | 128 where the value is positive, magnitude) and, behind all but the last, two zero bytes.  Bytes behind the end read 0.
+ * ex_triple: the triple at byte i, decoded; false where it begins with two zero bytes, a list's end.  ex_skip: the first byte behind the list that starts at i. */
+DEV bool ex_triple(const uint8_t *x, int n, int i, int &row, int &col, int &val)
+{
+	const int b0 = i < n ? x[i] : 0, b1 = i + 1 < n ? x[i + 1] : 0, mag = i + 2 < n ? x[i + 2] : 0;
+	row = b0; col = b1 & 127; val = b1 >= 128 ? mag + 255 : -mag;   /* (decoded either way: the last list has no end mark, its zero pairs are samples) */
+	return b0 || b1;
+}
+DEV int ex_skip(const uint8_t *x, int n, int i) { for (int row, col, val; i < n && ex_triple(x, n, i, row, col, val);) i += 3; return i + 2; }
 
 /* Wave-wide scans on the DPP network (an instruction each step; the shuffle forms go through the LDS crossbar: address arithmetic, a
  * ds_bpermute and its latency per step, and these scans sit on the serial path of every 64-byte step of the entropy kernels).
@@ -1354,17 +1369,10 @@ __global__ __launch_bounds__(256) void k_dec_expand(DecWs ws)
 		}
 		wave_sync();
 	}
-	if (!lane) {
-		/* exception samples of the luma plane (:656-668); U and V follow on the same cursor (k_dec_chroma) */
+	if (!lane) {                                                   /* exception samples of the luma plane (:656-668) */
 		const uint8_t *x = f + m->o_exw;
 		const int n = m->exw_len;
-#define XB(k) ((k) < n ? (int)x[k] : 0)
-		for (int i = 0; i < n; i += 3) {
-			if (!XB(i) && !XB(i + 1)) break;
-			const int hi = XB(i + 1) >= 128, lo = XB(i + 1) & 127;
-			a[(XB(i) << 9) + lo] = (int16_t)(hi ? XB(i + 2) + 255 : -XB(i + 2));
-		}
-#undef XB
+		for (int i = 0, row, col, val; i < n && ex_triple(x, n, i, row, col, val); i += 3) a[(row << 9) + col] = (int16_t)val;
 	}
 }
 
@@ -1390,23 +1398,67 @@ DEV void add_i16_at(int16_t *base, int idx, int delta)
  * it before it writes it), then along the columns, and column c of the result is row c of the plane -- the transposed orientation the
  * reference's transposes leave behind and everything downstream expects.  The plane in between never travels.  The block kernels below
  * (k_dec_luma_l2, k_dec_chroma) fill a CU's LDS with one 1024-thread workgroup, which therefore works through several blocks. */
-DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }   /* orders LDS traffic only: global loads stay in flight across it */
-template <int S>
-DEV void synth_pair(const int16_t *x, int st, int k, bool norm, int &ev, int &od)
+/* (lds_barrier, syn_pair, syn_taps: nhw_dwt.h, the encoder's own.)  The two in-place passes of a block at `pitch` shorts a row, a wavefront's share of them: */
+template <int S, int ROWS, int UNROLL> DEV void syn_rows_inplace(int16_t *x0, int pitch, int lane)        /* ROWS rows from x0 on, along the row, un-normalised: sample pair k goes back as dword k; UNROLL: of the loop over the rows */
 {
-	constexpr int M = S / 2;
-	const int16_t *lo = x, *hi = x + M * st;
-	const int l0 = lo[k * st], ln = k + 1 < M ? lo[(k + 1) * st] : l0;
-	const int h0 = hi[k * st], hp = k > 0 ? hi[(k - 1) * st] : h0, hn = k + 1 < M ? hi[(k + 1) * st] : h0;
-	ev = (int16_t)((int16_t)(l0 << 3) - ((h0 + hp) << 1));
-	od = (int16_t)((int16_t)((l0 + ln) << 2) + (6 * h0 - hp - hn));
-	if (norm) { if (ev > 0) ev = (int16_t)(ev + 32); ev >>= 6; if (od > 0) od = (int16_t)(od + 32); od >>= 6; }
+	constexpr int PPL = S / 128;
+#pragma unroll UNROLL
+	for (int i = 0; i < ROWS; i++) {
+		int16_t *x = x0 + i * pitch;
+		int e[PPL], o[PPL];
+#pragma unroll
+		for (int u = 0; u < PPL; u++) syn_pair<S>(x, 1, lane + 64 * u, false, &e[u], &o[u]);
+#pragma unroll
+		for (int u = 0; u < PPL; u++) reinterpret_cast<uint32_t *>(x)[lane + 64 * u] = (uint32_t)(uint16_t)e[u] | ((uint32_t)(uint16_t)o[u] << 16);
+	}
 }
+template <int S, int COLS> DEV void syn_cols_inplace(int16_t *x0, int pitch, int lane)        /* COLS columns from x0 on, down the column, normalised: samples 2k, 2k + 1 of the column */
+{
+	constexpr int PPL = S / 128;
+#pragma unroll 1
+	for (int i = 0; i < COLS; i++) {
+		int16_t *x = x0 + i;
+		int e[PPL], o[PPL];
+#pragma unroll
+		for (int u = 0; u < PPL; u++) syn_pair<S>(x, pitch, lane + 64 * u, true, &e[u], &o[u]);
+#pragma unroll
+		for (int u = 0; u < PPL; u++) { const int k = lane + 64 * u; x[(2 * k) * pitch] = (int16_t)e[u]; x[(2 * k + 1) * pitch] = (int16_t)o[u]; }
+	}
+}
+
+/* The residual lists of level 2 (nhw_decoder.c:731-787), which both level-2 kernels add onto the level-1 LL: list r = 0, 1, 2 (res5, res1, res3) is open from a
+ * quality on (cnt = 0 below it) and holds cnt positions (row << 8 | column, D_P5 / D_P1 / D_P3) with a byte string that says what each adds. */
+struct ResList { const uint16_t *pos; const uint8_t *bits; int cnt, nbytes /* of `bits`; bytes behind them read 0 */, per_byte /* log2 of the entries a byte describes */, amp; };
+DEV ResList res_list(int r, const DecWs &ws, int img, const DecMeta *m)
+{
+	const uint8_t *f = ws.blob + ws.blob_off[img];
+	const int q = m->q;
+	if (r == 0) return { ws.buf<uint16_t>(D_P5, img), f + m->o_res5_word, q >= 21 ? (m->res5_bits - 1) * 8 : 0, m->res5_bits, 3, 3 };
+	if (r == 1) return { ws.buf<uint16_t>(D_P1, img), f + m->o_res1_word, q > 12 ? (m->res1_bits - 1) * 8 : 0, m->res1_bits, 3, q >= 18 ? 5 : q >= 15 ? 7 : 9 };
+	return { ws.buf<uint16_t>(D_P3, img), f + m->o_res3_word, q >= 19 ? (m->res3_bits * 2 - 2) * 4 : 0, 1 << 30, 2, 0 };
+}
+DEV int res_byte(const ResList &L, int k) { const int bi = k >> L.per_byte; return bi < L.nbytes ? L.bits[bi] : 0; }   /* the byte that describes entry k */
+/* entry k of a list (ps: its position, byte: res_byte) -> acc(row, column, delta) for every cell it steps.  res5 and res1: a sign bit an entry, the amplitude by
+ * quality.  res3: two bits an entry pick one of four columns of steps for the cell and the one or two below it; rows 254 / 255 reach below the level-1 LL -- in the
+ * reference those cells are scratch that the next pass overwrites, here they are the level-1 detail bands, so those adds are dropped. */
+template <class Acc> DEV void res_apply(const ResList &L, int k, int ps, int byte, Acc &&acc)
+{
+	const int row = ps >> 8, col = ps & 255;
+	if (L.per_byte == 3) { acc(row, col, ((byte >> (7 - (k & 7))) & 1) ? -L.amp : L.amp); return; }
+	const int sel = (byte >> (6 - 2 * (k & 3))) & 3;
+	const int d0 = sel == 1 ? -4 : sel == 0 ? 4 : sel == 2 ? 2 : -2, d1 = sel == 1 ? -3 : sel == 0 ? 3 : sel == 2 ? 2 : -2, d2 = sel == 2 ? 2 : sel == 3 ? -2 : 0;
+	acc(row, col, d0);
+	if (row + 1 < DH) acc(row + 1, col, d1);
+	if (d2 && row + 2 < DH) acc(row + 2, col, d2);
+}
+
 /* ---------------------------------------------------------------------------------------------- level 2 of the luma (:670-787)
  * Three passes of the reference on one LDS residency of the 256 x 256 block (plane A's top-left quarter), one launch:
- *   shrink    isolated level-2 coefficients shrink by one (:670-721): a stencil on the values as they were -- a cell that shrinks cannot
- *             have a neighbour that does, but its new value would read differently to that neighbour, so all decisions are taken (a
- *             thread slides a 3 x 3 window down 64 rows of a column, a bit per row) before any is applied;
+ *   shrink    isolated level-2 coefficients shrink by one (:670-721).  THE 3 x 3 RULE: a cell of rows 1 .. 254 and columns 1 .. 254 outside the LL2
+ *             quadrant whose |v| > 8 moves one towards zero unless a neighbour is loud -- |v| > 8 for the four beside, above and below it, |v| > diag (16
+ *             up to quality 16, else 8) for the four diagonal ones.  It is a stencil on the values as they were: a cell that shrinks cannot have a
+ *             neighbour that does, but its new value would read differently to that neighbour, so all decisions are taken before any is applied.
+ *             Both kernels make "loud" one compare per cell into bit masks and the rule mask algebra; they differ in who holds which mask;
  *   synthesis both directions, in place (see k_dec_synth2d): afterwards LDS holds sample (row c, column j) of the level-1 LL, in the
  *             transposed orientation the plane keeps, at [j][c];
  *   residuals the three residual lists onto it (:731-787): positions repeat, the steps commute: compare-and-swap adds on the LDS words;
@@ -1442,9 +1494,9 @@ __global__ __launch_bounds__(1024) void k_dec_luma_l2(DecWs ws, int items, int u
 			for (int u = 0; u < NPRE; u++) { const int v = t + u * NT_; pre[u] = *reinterpret_cast<const uint4 *>(src + (size_t)(v / (S / 8)) * DW + 8 * (v % (S / 8))); }
 		}
 		{
-			/* shrink: a wavefront takes 16 rows, its lanes the columns (lane + 64k).  "Loud" (|v| > 8, > diag) is one compare per cell into a
-			 * row mask; the 3 x 3 rule is then mask algebra on the three rows around a cell (the scalar unit's work, 256 columns at a time), and
-			 * a lane only keeps its own 4 x 16 verdicts, as bits, until every wavefront has taken its decisions. */
+			/* shrink (the 3 x 3 rule above): a wavefront takes 16 rows, its lanes the columns (lane + 64k).  A row's loud masks come from ballots, the
+			 * rule runs on the three rows around a cell (the scalar unit's work, 256 columns at a time), and a lane only keeps its own 4 x 16
+			 * verdicts, as bits, until every wavefront has taken its decisions. */
 			const int diag = q <= 16 ? 16 : 8, i_first = 16 * wv;
 			auto loud = [&](int r, Mask4 &m8, Mask4 &md) {
 #pragma unroll
@@ -1495,53 +1547,16 @@ __global__ __launch_bounds__(1024) void k_dec_luma_l2(DecWs ws, int items, int u
 			lds_barrier();
 			continue;
 		}
-		for (int i = 0; i < 16; i++) {                               /* along the rows, un-normalised */
-			int16_t *x = smem + (wv * 16 + i) * LS;
-			int e[PPL], o[PPL];
-#pragma unroll
-			for (int u = 0; u < PPL; u++) synth_pair<S>(x, 1, lane + 64 * u, false, e[u], o[u]);
-#pragma unroll
-			for (int u = 0; u < PPL; u++) reinterpret_cast<uint32_t *>(x)[lane + 64 * u] = (uint32_t)(uint16_t)e[u] | ((uint32_t)(uint16_t)o[u] << 16);
-		}
+		syn_rows_inplace<S, 16, 16>(smem + wv * 16 * LS, LS, lane);          /* (unrolled, as this loop has always compiled; k_dec_chroma asks for its loops rolled) */
 		lds_barrier();
-		for (int i = 0; i < 16; i++) {                               /* along the columns, normalised, in place: sample 2k, 2k+1 of column c */
-			int16_t *x = smem + wv * 16 + i;
-			int e[PPL], o[PPL];
-#pragma unroll
-			for (int u = 0; u < PPL; u++) synth_pair<S>(x, LS, lane + 64 * u, true, e[u], o[u]);
-#pragma unroll
-			for (int u = 0; u < PPL; u++) { const int k = lane + 64 * u; x[(2 * k) * LS] = (int16_t)e[u]; x[(2 * k + 1) * LS] = (int16_t)o[u]; }
-		}
+		syn_cols_inplace<S, 16>(smem + wv * 16, LS, lane);           /* sample 2k, 2k+1 of column c */
 		lds_barrier();
 		if (upto >= 3 && !skip) {                                    /* residual lists: plane cell (row, col) sits at [col][row] */
-			const uint8_t *f = ws.blob + ws.blob_off[img];
-#define ACC(row, col, d) add_i16_at(smem, (col) * LS + (row), (d))
-			if (q >= 21) {
-				const uint16_t *p5 = ws.buf<uint16_t>(D_P5, img);
-				const int cnt = (m->res5_bits - 1) * 8;
-				for (int k = t; k < cnt; k += NT_) { const int p = p5[k]; ACC(p >> 8, p & 255, bit_of(f + m->o_res5_word, m->res5_bits, k) ? -3 : 3); }
+#pragma unroll
+			for (int r = 0; r < 3; r++) {
+				const ResList L = res_list(r, ws, img, m);
+				for (int k = t; k < L.cnt; k += NT_) res_apply(L, k, L.pos[k], res_byte(L, k), [&](int row, int col, int d) { add_i16_at(smem, col * LS + row, d); });
 			}
-			if (q > 12) {
-				const uint16_t *p1 = ws.buf<uint16_t>(D_P1, img);
-				const int amp = q >= 18 ? 5 : q >= 15 ? 7 : 9, cnt = (m->res1_bits - 1) * 8;
-				for (int k = t; k < cnt; k += NT_) { const int p = p1[k]; ACC(p >> 8, p & 255, bit_of(f + m->o_res1_word, m->res1_bits, k) ? -amp : amp); }
-			}
-			if (q >= 19) {
-				const uint16_t *p3 = ws.buf<uint16_t>(D_P3, img);
-				const uint8_t *w = f + m->o_res3_word;
-				const int cnt = (m->res3_bits * 2 - 2) * 4;
-				for (int k = t; k < cnt; k += NT_) {
-					const int p = p3[k], row = p >> 8, col = p & 255;
-					const int sel = (w[k >> 2] >> (6 - 2 * (k & 3))) & 3;
-					/* rows 254/255 reach below the level-1 LL: in the reference those cells are scratch that the next pass overwrites; here they are
-					 * the level-1 detail bands, so those adds are dropped */
-					const int d0 = sel == 1 ? -4 : sel == 0 ? 4 : sel == 2 ? 2 : -2, d1 = sel == 1 ? -3 : sel == 0 ? 3 : sel == 2 ? 2 : -2, d2 = sel == 2 ? 2 : sel == 3 ? -2 : 0;
-					ACC(row, col, d0);
-					if (row + 1 < DH) ACC(row + 1, col, d1);
-					if (d2 && row + 2 < DH) ACC(row + 2, col, d2);
-				}
-			}
-#undef ACC
 		}
 		lds_barrier();
 		if (!skip)
@@ -1596,10 +1611,10 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int s
 	}
 	lds_barrier();
 	{
-		/* shrink (:670-721): a lane a ROW (row 64 wv + lane; the tile's pitch of 37 dwords puts 64 rows on different banks): it sorts its row's 72 cells
-		 * into "loud" masks (|v| > 8, > diag; a bit a cell of either window), takes the masks of the rows above and below from its neighbour lanes
-		 * (the wavefront's first and last row: from the next wavefront, through LDS), and the 3 x 3 rule is mask algebra in registers.  All masks are
-		 * made from the values as they were: nothing is applied before every wavefront has read its rows. */
+		/* shrink (the 3 x 3 rule above k_dec_luma_l2): a lane a ROW (row 64 wv + lane; the tile's pitch of 37 dwords puts 64 rows on different banks): it sorts
+		 * its row's 72 cells into loud masks (a bit a cell of either window), takes the masks of the rows above and below from its neighbour lanes (the
+		 * wavefront's first and last row: from the next wavefront, through LDS), and the rule runs in registers.  Nothing is applied before every
+		 * wavefront has read its rows. */
 		__shared__ uint64_t s_edge[4][2][4];                           /* a wavefront's first / last row: m8[0], m8[1], md[0], md[1] */
 		const int diag = q <= 16 ? 16 : 8, r = 64 * wv + lane;
 		uint64_t ok[2], ll[2];                                       /* per window: cells with both neighbours in it and a block column 1 .. 254; cells of the LL2 quadrant's columns */
@@ -1656,57 +1671,40 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int s
 			int16_t *x = T + (it * 8 + wv * 2 + rsub) * LQ_LS;
 			const int l0 = x[kk + 2], ln = k + 1 < HLF ? x[kk + 3] : l0;
 			const int h0 = x[36 + kk + 2], hp = k > 0 ? x[36 + kk + 1] : h0, hn = k + 1 < HLF ? x[36 + kk + 3] : h0;
-			const int ev = (int16_t)((int16_t)(l0 << 3) - ((h0 + hp) << 1));
-			const int od = (int16_t)((int16_t)((l0 + ln) << 2) + (6 * h0 - hp - hn));
+			int ev, od;
+			syn_taps(l0, ln, h0, hp, hn, false, &ev, &od);
 			__builtin_amdgcn_wave_barrier();                          /* every lane of the row has read its taps */
 			reinterpret_cast<uint32_t *>(x)[kk] = (uint32_t)(uint16_t)ev | ((uint32_t)(uint16_t)od << 16);
 		}
 	}
 	lds_barrier();
+#pragma unroll 1                                                    /* (rolled, as it has always compiled: left alone, the compiler now unrolls all 16 columns, a quarter more code for the kernel) */
 	for (int i = 0; i < 16; i++) {                                   /* along the columns, normalised, in place: sample 2k, 2k+1 of column j */
 		int16_t *x = T + wv * 16 + i;
 		int e[2], o[2];
 #pragma unroll
-		for (int u = 0; u < 2; u++) synth_pair<S>(x, LQ_LS, lane + 64 * u, true, e[u], o[u]);
+		for (int u = 0; u < 2; u++) syn_pair<S>(x, LQ_LS, lane + 64 * u, true, &e[u], &o[u]);
 		__builtin_amdgcn_wave_barrier();
 #pragma unroll
 		for (int u = 0; u < 2; u++) { const int k = lane + 64 * u; x[(2 * k) * LQ_LS] = (int16_t)e[u]; x[(2 * k + 1) * LQ_LS] = (int16_t)o[u]; }
 	}
 	lds_barrier();
 	{                                                                /* residual lists (:731-787): plane cell (row, col) sits at [col][row - 64 p]; a quarter takes the cells of its own plane rows */
-		const uint8_t *f = ws.blob + ws.blob_off[img];
-#define ACC(row, col, d) do { const int r_ = (row); if ((r_ >> 6) == p) add_i16_at(T, (col) * LQ_LS + (r_ & 63), (d)); } while (0)
-		/* a thread's entries of a list eight at a time: their loads (the entry, the byte its sign bits sit in) go out together, then the adds */
-		auto scan = [&](const uint16_t *pp, int cnt, const uint8_t *bits, int nbytes, int per_byte_shift, auto &&apply) {
-			for (int k0 = t; k0 < cnt; k0 += 256 * 8) {
+		/* a thread's entries of a list eight at a time: their loads (the entry, the byte that describes it) go out together, then the adds */
+#pragma unroll
+		for (int r = 0; r < 3; r++) {
+			const ResList L = res_list(r, ws, img, m);
+			for (int k0 = t; k0 < L.cnt; k0 += 256 * 8) {
 				int e[8], by[8];
 #pragma unroll
-				for (int j = 0; j < 8; j++) {
-					const int k = k0 + 256 * j, kc = k < cnt ? k : cnt - 1, bi = kc >> per_byte_shift;
-					e[j] = pp[kc]; by[j] = bi < nbytes ? bits[bi] : 0;
-				}
+				for (int j = 0; j < 8; j++) { const int k = k0 + 256 * j, kc = k < L.cnt ? k : L.cnt - 1; e[j] = L.pos[kc]; by[j] = res_byte(L, kc); }
 #pragma unroll
-				for (int j = 0; j < 8; j++) { const int k = k0 + 256 * j; if (k < cnt) apply(k, e[j], by[j]); }
+				for (int j = 0; j < 8; j++) {
+					const int k = k0 + 256 * j;
+					if (k < L.cnt) res_apply(L, k, e[j], by[j], [&](int row, int col, int d) { if ((row >> 6) == p) add_i16_at(T, col * LQ_LS + (row & 63), d); });
+				}
 			}
-		};
-		if (q >= 21) scan(ws.buf<uint16_t>(D_P5, img), (m->res5_bits - 1) * 8, f + m->o_res5_word, m->res5_bits, 3,
-		                  [&](int k, int ps, int byte) { ACC(ps >> 8, ps & 255, ((byte >> (7 - (k & 7))) & 1) ? -3 : 3); });
-		if (q > 12) {
-			const int amp = q >= 18 ? 5 : q >= 15 ? 7 : 9;
-			scan(ws.buf<uint16_t>(D_P1, img), (m->res1_bits - 1) * 8, f + m->o_res1_word, m->res1_bits, 3,
-			     [&](int k, int ps, int byte) { ACC(ps >> 8, ps & 255, ((byte >> (7 - (k & 7))) & 1) ? -amp : amp); });
 		}
-		if (q >= 19)
-			scan(ws.buf<uint16_t>(D_P3, img), (m->res3_bits * 2 - 2) * 4, f + m->o_res3_word, 1 << 30, 2,
-			     [&](int k, int ps, int byte) {
-				const int row = ps >> 8, col = ps & 255;
-				const int sel = (byte >> (6 - 2 * (k & 3))) & 3;
-				const int d0 = sel == 1 ? -4 : sel == 0 ? 4 : sel == 2 ? 2 : -2, d1 = sel == 1 ? -3 : sel == 0 ? 3 : sel == 2 ? 2 : -2, d2 = sel == 2 ? 2 : sel == 3 ? -2 : 0;
-				ACC(row, col, d0);
-				if (row + 1 < DH) ACC(row + 1, col, d1);                /* (rows 254 / 255 reach below the level-1 LL: dropped, see k_dec_luma_l2) */
-				if (d2 && row + 2 < DH) ACC(row + 2, col, d2);
-			     });
-#undef ACC
 	}
 	lds_barrier();
 	int16_t *l1 = plane_l1(ws, img);
@@ -1763,20 +1761,12 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 			for (int k = t; k < DQ / 16; k += NT_) smem[(k >> 6) * LS + (k & 63)] = (int16_t)(l[k] + (q > 15 ? 0 : 1));
 		}
 		lds_barrier();
-		if (!t) {                                                    /* exception samples: luma, then U, then V share one cursor */
+		if (!t) {                                                    /* exception samples: behind the luma list, and for V behind U's */
 			const uint8_t *x = f + m->o_exw;
 			const int n = m->exw_len;
-#define XB(k) ((k) < n ? (int)x[k] : 0)
-			int i = 0;
-			for (; i < n; i += 3) if (!XB(i) && !XB(i + 1)) break;
-			i += 2;
-			if (comp) { for (; i < n; i += 3) if (!XB(i) && !XB(i + 1)) break; i += 2; }
-			for (; i < n; i += 3) {
-				if (!comp && !XB(i) && !XB(i + 1)) break;
-				const int hi = XB(i + 1) >= 128, lo = XB(i + 1) & 127;
-				smem[XB(i) * LS + lo] = (int16_t)(hi ? XB(i + 2) + 255 : -XB(i + 2));
-			}
-#undef XB
+			int i = ex_skip(x, n, 0), row, col, val;
+			if (comp) i = ex_skip(x, n, i);
+			for (; i < n && (ex_triple(x, n, i, row, col, val) || comp); i += 3) smem[row * LS + col] = (int16_t)val;   /* V's list is the last: it runs to the end of the bytes */
 		}
 		lds_barrier();
 		/* the block back to the plane for the debug stop; llt: the 128 x 128 corner sits transposed in LDS */
@@ -1788,21 +1778,9 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 			}
 		};
 		if (upto == 1) { store_block(false); lds_barrier(); continue; }
-#pragma unroll 1
-		for (int i = 0; i < 8; i++) {                                /* level 2, along the rows of the corner (un-normalised) */
-			int16_t *x = smem + (wv * 8 + i) * LS;
-			int e, o;
-			synth_pair<HLF>(x, 1, lane, false, e, o);
-			reinterpret_cast<uint32_t *>(x)[lane] = (uint32_t)(uint16_t)e | ((uint32_t)(uint16_t)o << 16);
-		}
+		syn_rows_inplace<HLF, 8, 1>(smem + wv * 8 * LS, LS, lane);      /* level 2 on the corner */
 		lds_barrier();
-#pragma unroll 1
-		for (int i = 0; i < 8; i++) {                                /* along its columns, normalised, in place */
-			int16_t *x = smem + wv * 8 + i;
-			int e, o;
-			synth_pair<HLF>(x, LS, lane, true, e, o);
-			x[(2 * lane) * LS] = (int16_t)e; x[(2 * lane + 1) * LS] = (int16_t)o;
-		}
+		syn_cols_inplace<HLF, 8>(smem + wv * 8, LS, lane);
 		lds_barrier();
 		if (upto == 2) { store_block(true); lds_barrier(); continue; }
 		{                                                            /* the corrections: a symbol 5003..5006 in a detail band steps the level-1 LL cell(s) it sits over.  Such a symbol can only
@@ -1827,15 +1805,7 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 		}
 		lds_barrier();
 		if (upto == 3) { store_block(true); lds_barrier(); continue; }
-#pragma unroll 1
-		for (int i = 0; i < 16; i++) {                               /* level 1, along the rows */
-			int16_t *x = smem + (wv * 16 + i) * LS;
-			int e[2], o[2];
-#pragma unroll
-			for (int u = 0; u < 2; u++) synth_pair<S>(x, 1, lane + 64 * u, false, e[u], o[u]);
-#pragma unroll
-			for (int u = 0; u < 2; u++) reinterpret_cast<uint32_t *>(x)[lane + 64 * u] = (uint32_t)(uint16_t)e[u] | ((uint32_t)(uint16_t)o[u] << 16);
-		}
+		syn_rows_inplace<S, 16, 1>(smem + wv * 16 * LS, LS, lane);      /* level 1 */
 		lds_barrier();
 #pragma unroll 1
 		for (int i = 0; i < 16; i++) {                               /* along the columns, normalised: column c is row c of the plane */
@@ -1844,7 +1814,7 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 #pragma unroll
 			for (int u = 0; u < 2; u++) {
 				int e, o;
-				synth_pair<S>(smem + c, LS, lane + 64 * u, true, e, o);
+				syn_pair<S>(smem + c, LS, lane + 64 * u, true, &e, &o);
 				dst[lane + 64 * u] = (uint32_t)(uint16_t)e | ((uint32_t)(uint16_t)o << 16);
 			}
 		}
@@ -2293,7 +2263,6 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 	 * arithmetic: the reference's values are int16 with wrap-around at every step, which is what the packed instructions compute; at the two
 	 * ends of a line the missing neighbour is the sample itself (that is what the end rules of filters.c:143-194 amount to). */
 	for (int lp = 1; lp <= FR / 2; lp++) {                                       /* local rows 2 lp, 2 lp + 1 <-> r0 + 2 (lp - 1), + 1 */
-		typedef short s16x2 __attribute__((ext_vector_type(2)));
 		const int j = tid, M = DH;
 #define TW(k) (*reinterpret_cast<const uint32_t *>(T + (k) * FBP + 2 * lp))
 		const uint32_t lo0 = TW(j), h0 = TW(M + j);
@@ -2386,52 +2355,34 @@ __global__ __launch_bounds__(256) void k_dec_status(DecWs ws, int32_t *status, i
 } /* namespace */
 
 /* ---------------------------------------------------------------------------------------------- host side */
-static thread_local std::string g_derr;
-#define NHW_ERR g_derr
-extern "C" const char *nhw_dec_last_error(void) { return g_derr.c_str(); }
+thread_local std::string nhw_dec_err;
+extern "C" const char *nhw_dec_last_error(void) { return nhw_dec_err.c_str(); }
 
-struct nhw_dec {
-	int device, max_batch;
-	DecWs ws;
-	hipStream_t own_stream;
-	hipStream_t chroma_stream;   /* the chroma sequence runs here, next to the luma one (NHW_CHROMA_FORK=0: behind it, on the caller's stream) */
-	hipEvent_t fork_ev, join_ev;
-	uint16_t *vlc_table;         /* the prefix code's two-level lookup table (k_dec_vlc_table), 2.5 KB */
-	int chroma_fork;
-	int stop_after;
-	bool l1_moved;               /* the last batch ran level 2 of the luma whole: the level-1 LL is in plane_l1 (D_B), not plane A (nhw_dec_debug_read) */
-	int slice_order;             /* debug: the forced slice order of the kernels that split a file (nhw_host.h; 0 = production) */
-	hipEvent_t ev[4];         /* start, after the entropy stages, around the final reconstruction kernel (= end) */
-	bool timed;
-	/* host convenience path: the files (grow-only) and, for max_batch files, their offsets and lengths, the pictures, status and quality */
-	GrowBuf blob;
-	uint64_t *d_off; uint32_t *d_len; uint8_t *d_out; int32_t *d_status; int32_t *d_quality;
-	/* nhw_dec_pictures, nhw_dec_regions*: the cropped pictures or regions, their descriptor table and the per-tile offsets, lengths and status, grow-only */
-	GrowBuf pic_px, pic_desc, pic_tiles;
-	uint64_t reg_tiles, reg_bytes;   /* the last region call: tiles handed to the decoder, tile-file bytes uploaded (nhw_dec_last_region_stats) */
-};
-
-static DevSet host_set(nhw_dec *d)
+/* the workspace of a handle: max_batch images behind `base`, every buffer's share 256-byte aligned; *total: its bytes */
+static DecWs dec_ws(uint8_t *base, int max_batch, size_t *total = nullptr)
 {
-	const size_t mb = (size_t)d->max_batch;
-	return { dev_buf(d->d_off, mb + 1), dev_buf(d->d_len, mb + 1), dev_buf(d->d_out, mb * NHW_IMG_BYTES), dev_buf(d->d_status, mb), dev_buf(d->d_quality, mb) };
+	DecWs ws = { base };
+	size_t at = 0;
+	for (int b = 0; b < D_COUNT; b++) { ws.off[b] = at; at = (at + dec_bytes(b) * (size_t)max_batch + 255) & ~(size_t)255; }
+	if (total) *total = at;
+	return ws;
 }
 
 extern "C" int nhw_dec_create(int device, int max_batch, nhw_dec **out)
 {
-	if (!out || max_batch < 1) { g_derr = "bad argument"; return NHW_E_ARG; }
+	if (!out || max_batch < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(device));
 	nhw_dec *d = new nhw_dec();
 	memset(d, 0, sizeof *d);
 	d->device = device; d->max_batch = max_batch;
-	size_t at = 0;
-	for (int b = 0; b < D_COUNT; b++) { d->ws.off[b] = at; at += k_dec_bytes[b] * (size_t)max_batch; at = (at + 255) & ~(size_t)255; }
+	size_t at = 0;                                                 /* the workspace's bytes */
+	dec_ws(nullptr, max_batch, &at);
 	const int rc = [&]() -> int {                                  /* a failure half-way leaves nothing behind: the handle is destroyed below */
 		size_t free_b = 0, total_b = 0;
 		HIPCHK(hipMemGetInfo(&free_b, &total_b));
-		if (at > free_b) { char b[160]; snprintf(b, sizeof b, "decoder workspace for max_batch %d needs %zu MiB, %zu MiB of HBM are free", max_batch, at >> 20, free_b >> 20); g_derr = b; return NHW_E_ARG; }
-		HIPCHK(hipMalloc(&d->ws.base, at));
-		HIPCHK(hipMemset(d->ws.base, 0, at));
+		if (at > free_b) { char b[160]; snprintf(b, sizeof b, "decoder workspace for max_batch %d needs %zu MiB, %zu MiB of HBM are free", max_batch, at >> 20, free_b >> 20); nhw_dec_err = b; return NHW_E_ARG; }
+		HIPCHK(hipMalloc(&d->ws_base, at));
+		HIPCHK(hipMemset(d->ws_base, 0, at));
 		HIPCHK(hipStreamCreateWithFlags(&d->own_stream, hipStreamNonBlocking));
 		HIPCHK(hipStreamCreateWithFlags(&d->chroma_stream, hipStreamNonBlocking));
 		HIPCHK(hipEventCreateWithFlags(&d->fork_ev, hipEventDisableTiming));
@@ -2440,7 +2391,7 @@ extern "C" int nhw_dec_create(int device, int max_batch, nhw_dec **out)
 		HIPCHK(hipMalloc(&d->vlc_table, (256 + 16 * 64) * sizeof(uint16_t)));
 		k_dec_vlc_table<<<1, 64, 0, d->own_stream>>>(d->vlc_table);
 		HIPCHK(hipStreamSynchronize(d->own_stream));
-		if (synth2d_attrs() != NHW_OK) { g_derr = "hipFuncSetAttribute(129 KB of LDS for the block kernels) failed"; return NHW_E_HIP; }
+		if (synth2d_attrs() != NHW_OK) { nhw_dec_err = "hipFuncSetAttribute(129 KB of LDS for the block kernels) failed"; return NHW_E_HIP; }
 		return NHW_OK;
 	}();
 	if (rc != NHW_OK) { nhw_dec_destroy(d); return rc; }
@@ -2455,7 +2406,7 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 {
 	if (!d) return;
 	(void)hipSetDevice(d->device);
-	if (d->ws.base) (void)hipFree(d->ws.base);
+	if (d->ws_base) (void)hipFree(d->ws_base);
 	dev_free(host_set(d));
 	for (GrowBuf *g : { &d->blob, &d->pic_px, &d->pic_desc, &d->pic_tiles }) nhw_grow_free(*g);
 	if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
@@ -2476,23 +2427,24 @@ void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_afte
 	*device = d->device; *max_batch = d->max_batch; *stop_after = d->stop_after;
 }
 
-/* debug: copy a workspace buffer of one image to the host (what = D_* index) */
 extern "C" int nhw_dec_debug_colour(int quality, const void *d_yuv, void *d_rgb, int n)
 {
 	if (!d_yuv || !d_rgb || n < 8 || (n & 7) || quality < 1 || quality > 23) return NHW_E_ARG;
 	k_dec_colour_probe<<<(n / 8 + 255) / 256, 256>>>((const uint8_t *)d_yuv, (uint8_t *)d_rgb, n / 8, quality);
 	return hipGetLastError() == hipSuccess ? NHW_OK : NHW_E_HIP;
 }
+/* debug: copy a workspace buffer of one image to the host (what = D_* index) */
 extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size_t bytes)
 {
-	if (!d || what < 0 || what >= D_COUNT || img < 0 || img >= d->max_batch || bytes > k_dec_bytes[what]) { g_derr = "bad argument"; return NHW_E_ARG; }
+	if (!d || what < 0 || what >= D_COUNT || img < 0 || img >= d->max_batch || bytes > dec_bytes(what)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const DecWs ws = dec_ws(d->ws_base, d->max_batch);
 	HIPCHK(hipSetDevice(d->device));
 	HIPCHK(hipDeviceSynchronize());
-	HIPCHK(hipMemcpy(dst, d->ws.base + d->ws.off[what] + (size_t)img * k_dec_bytes[what], bytes, hipMemcpyDeviceToHost));
+	HIPCHK(hipMemcpy(dst, ws.buf<uint8_t>(what, img), bytes, hipMemcpyDeviceToHost));
 	if (what == D_A && d->l1_moved)                                 /* plane A as the stage checks know it: with the level-1 LL where the reference keeps it */
 		for (int r = 0; r < DH && 4096 + (size_t)r * DW * 2 < bytes; r++) {
 			const size_t at = 4096 + (size_t)r * DW * 2, len = bytes - at < (size_t)DH * 2 ? bytes - at : (size_t)DH * 2;
-			HIPCHK(hipMemcpy((uint8_t *)dst + at, d->ws.base + d->ws.off[D_B] + (size_t)img * k_dec_bytes[D_B] + at, len, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy((uint8_t *)dst + at, ws.buf<uint8_t>(D_B, img) + at, len, hipMemcpyDeviceToHost));
 		}
 	return NHW_OK;
 }
@@ -2500,11 +2452,11 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, void *d_bgr, int32_t *d_status,
                                     int32_t *d_quality, void *stream)
 {
-	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { g_derr = "bad argument"; return NHW_E_ARG; }
+	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(d->device));                              /* the handle's device, whatever the calling thread had current */
 	hipStream_t s = stream ? (hipStream_t)stream : d->own_stream;
 	const NhwSliceScope slices(d->slice_order);
-	DecWs ws = d->ws;
+	DecWs ws = dec_ws(d->ws_base, d->max_batch);
 	ws.n = n; ws.blob = (const uint8_t *)d_nhw; ws.blob_off = d_off; ws.blob_len = d_len; ws.dense = d->stop_after != 0;
 	int stage = 0;
 	d->timed = false;
@@ -2595,254 +2547,4 @@ extern "C" int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t)
 	HIPCHK(hipEventElapsedTime(&t->entropy_ms, d->ev[0], d->ev[1]));
 	HIPCHK(hipEventElapsedTime(&t->recon_ms, d->ev[2], d->ev[3]));
 	return NHW_OK;
-}
-
-/* the host paths' buffers: the blob (grow-only, room for `total` bytes of files) and, on the first call, the per-file arrays and the
- * decoded pictures of max_batch files */
-static int host_buffers(nhw_dec *d, size_t total)
-{
-	if (total + 64 > d->blob.cap) HIPCHK(nhw_grow(d->blob, total + (total >> 2) + (1u << 20)));   /* 64 spare bytes at least; a quarter and 1 MiB more when it grows, so that batches of a similar size do not reallocate */
-	return d->d_off ? NHW_OK : dev_alloc(host_set(d), nullptr, d->max_batch, g_derr);   /* all five or none: a half-made set would hand null pointers to the next call */
-}
-
-/* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1]. */
-extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality)
-{
-	if (!d || !nhw || !off || !bgr || !status || n < 1 || n > d->max_batch) { g_derr = "bad argument"; return NHW_E_ARG; }
-	HIPCHK(hipSetDevice(d->device));
-	const size_t total = (size_t)(off[n] - off[0]);
-	{ const int rc = host_buffers(d, total); if (rc) return rc; }
-	uint64_t *rel = (uint64_t *)malloc(((size_t)n + 1) * 12);
-	if (!rel) return NHW_E_ARG;
-	uint32_t *len = (uint32_t *)(rel + n + 1);
-	for (int i = 0; i < n; i++) {
-		rel[i] = off[i] - off[0];
-		const uint64_t l = off[i + 1] - off[i];
-		len[i] = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
-	}
-	hipError_t e1 = hipMemcpyAsync(d->blob.p, nhw + off[0], total, hipMemcpyHostToDevice, d->own_stream);
-	hipError_t e2 = hipMemcpyAsync(d->d_off, rel, (size_t)n * 8, hipMemcpyHostToDevice, d->own_stream);
-	hipError_t e4 = hipMemcpyAsync(d->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, d->own_stream);
-	hipError_t e3 = hipStreamSynchronize(d->own_stream);
-	free(rel);
-	HIPCHK(e1); HIPCHK(e2); HIPCHK(e4); HIPCHK(e3);
-	const int rc = nhw_dec_batch_device(d, d->blob.p, d->d_off, d->d_len, n, d->d_out, d->d_status, d->d_quality, d->own_stream);
-	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(bgr, d->d_out, (size_t)n * NHW_IMG_BYTES, hipMemcpyDeviceToHost, d->own_stream));
-	HIPCHK(hipMemcpyAsync(status, d->d_status, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
-	if (quality) HIPCHK(hipMemcpyAsync(quality, d->d_quality, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
-	HIPCHK(hipStreamSynchronize(d->own_stream));
-	return NHW_OK;
-}
-
-/* ---------------------------------------------------------------------------------------------- pictures of any size (DESIGN.md sections 11, 13) */
-/* What nhw_dec_pictures and the region calls share: a container's directory, the chunked decode of a list of tile files, the status
- * gather and the download of the results. */
-static uint32_t dir_len(const uint8_t *dir, int k)                /* length of tile file k in a container's directory */
-{
-	return (uint32_t)dir[4 * k] | ((uint32_t)dir[4 * k + 1] << 8) | ((uint32_t)dir[4 * k + 2] << 16) | ((uint32_t)dir[4 * k + 3] << 24);
-}
-
-static const size_t MAX_CALL_TILES = (size_t)(INT_MAX / 16);       /* the tiles one host call takes */
-
-/* The tile files of a call, in the handle's blob (already on its way there on the handle's stream): offsets and lengths go up, the tiles are
- * decoded in chunks of max_batch into the host path's picture slots, each chunk followed by crop(t0, m) -- the launch that takes the
- * decoded tiles [t0, t0 + m) out of d->d_out --, and the per-tile status comes back.  Synchronises the stream. */
-template <class Crop>
-static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const std::vector<uint32_t> &tlen, std::vector<int32_t> &tst, Crop &&crop)
-{
-	const int tiles = (int)toff.size();
-	HIPCHK(nhw_grow(d->pic_tiles, (size_t)tiles * 16));
-	uint64_t *d_toff = d->pic_tiles.as<uint64_t>();
-	uint32_t *d_tlen = (uint32_t *)(d_toff + tiles);
-	int32_t *d_tst = (int32_t *)(d_tlen + tiles);
-	hipStream_t s = d->own_stream;
-	HIPCHK(hipMemcpyAsync(d_toff, toff.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(d_tlen, tlen.data(), (size_t)tiles * 4, hipMemcpyHostToDevice, s));
-	for (int t0 = 0; t0 < tiles; t0 += d->max_batch) {
-		const int m = tiles - t0 < d->max_batch ? tiles - t0 : d->max_batch;
-		const int rc = nhw_dec_batch_device(d, d->blob.p, d_toff + t0, d_tlen + t0, m, d->d_out, d_tst + t0, nullptr, s);
-		if (rc) return rc;
-		HIPCHK(crop(t0, m));
-	}
-	tst.resize((size_t)tiles);
-	HIPCHK(hipMemcpyAsync(tst.data(), d_tst, (size_t)tiles * 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipStreamSynchronize(s));
-	return NHW_OK;
-}
-
-static int32_t tiles_status(const std::vector<int32_t> &tst, int t0, int t1)   /* NHW_OK if the tiles [t0, t1) all decoded */
-{
-	for (int t = t0; t < t1; t++) if (tst[t] != NHW_OK) return NHW_E_FORMAT;
-	return NHW_OK;
-}
-
-/* results that decoded, device -> host: neighbours that are contiguous on both sides go as one copy */
-struct Span { uint64_t dev, host, len; };
-static int download_spans(uint8_t *bgr, const std::vector<Span> &sp)
-{
-	for (size_t k = 0; k < sp.size();) {
-		uint64_t len = sp[k].len;
-		size_t j = k + 1;
-		while (j < sp.size() && sp[j].dev == sp[k].dev + len && sp[j].host == sp[k].host + len) len += sp[j++].len;
-		HIPCHK(hipMemcpy(bgr + sp[k].host, (const void *)(uintptr_t)sp[k].dev, len, hipMemcpyDeviceToHost));
-		k = j;
-	}
-	return NHW_OK;
-}
-
-/* Parse every container on the host; upload the blob once (a container's tile files lie back to back, so the decoder's offsets and lengths
- * come from its directory); decode the tiles in chunks of max_batch into the host path's picture slots and crop each chunk into the
- * picture buffer (k_untile_crop); then bring back the pictures whose tiles all decoded. */
-extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
-{
-	if (!d || !blob || !off || !bgr || !out_off || !status || n < 1) { g_derr = "bad argument"; return NHW_E_ARG; }
-	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { g_derr = "nhw_dec_pictures: off[] must not decrease"; return NHW_E_ARG; }
-	std::vector<nhw_picture> desc;
-	std::vector<int> which;                                      /* desc[k] is container which[k] */
-	std::vector<uint64_t> toff;
-	std::vector<uint32_t> tlen;
-	uint64_t bytes = 0;
-	for (int i = 0; i < n; i++) {
-		uint32_t w = 0, h = 0;
-		int t = 0;
-		const uint8_t *dir = nullptr;
-		status[i] = NHW_E_FORMAT;
-		if (nhw_container_parse(blob + off[i], (size_t)(off[i + 1] - off[i]), &w, &h, &t, &dir) != NHW_OK) continue;
-		if (toff.size() + (size_t)t > MAX_CALL_TILES) { g_derr = "nhw_dec_pictures: too many tiles in one call"; return NHW_E_ARG; }
-		status[i] = NHW_OK;
-		desc.push_back({ bytes, 3ull * w, w, h, (uint32_t)toff.size(), 0 });
-		which.push_back(i);
-		uint64_t fo = off[i] - off[0] + 16 + 4 * (uint64_t)t;
-		for (int k = 0; k < t; k++) { toff.push_back(fo); tlen.push_back(dir_len(dir, k)); fo += tlen.back(); }
-		bytes += 3ull * w * h;
-	}
-	if (desc.empty()) return NHW_OK;
-	const int tiles = (int)toff.size(), np = (int)desc.size();
-	HIPCHK(hipSetDevice(d->device));
-	{ const int rc = host_buffers(d, (size_t)(off[n] - off[0])); if (rc) return rc; }
-	HIPCHK(nhw_grow(d->pic_px, bytes));
-	HIPCHK(nhw_grow(d->pic_desc, (size_t)np * sizeof(nhw_picture)));
-	for (nhw_picture &p : desc) p.addr += (uint64_t)(uintptr_t)d->pic_px.p;
-	const nhw_picture *d_desc = d->pic_desc.as<nhw_picture>();
-	hipStream_t s = d->own_stream;
-	HIPCHK(hipMemcpyAsync(d->blob.p, blob + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
-	std::vector<int32_t> tst;
-	{ const int rc = decode_tile_list(d, toff, tlen, tst, [&](int t0, int m) { return nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, s); }); if (rc) return rc; }
-	std::vector<Span> sp;
-	for (int k = 0; k < np; k++) {
-		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < np ? (int)desc[k + 1].first_tile : tiles);
-		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
-	}
-	return download_spans(bgr, sp);
-}
-
-/* ---------------------------------------------------------------------------------------------- regions of pictures */
-/* a container as the region calls see it: parsed once, when the first rect names it; start[k] = byte offset of tile file k in it */
-struct RegionSource {
-	int state;                                                   /* 0 not looked at, 1 well-formed, -1 malformed */
-	uint32_t w, h;
-	int t;
-	const uint8_t *dir;
-	std::vector<uint64_t> start;                                 /* t + 1 entries */
-};
-
-/* Both region calls: bgr / out_off (the regions packed in a device buffer of the handle, then downloaded) or dst_addr / dst_pitch (cropped
- * straight into the caller's device memory).  The selected tile files are gathered on the host -- a selection row tx0 .. tx1 is one
- * contiguous byte run of its container -- and go up as one blob; the decoder gets their offsets and lengths as it does for whole pictures,
- * and every chunk is followed by k_untile_region. */
-static int dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, uint8_t *bgr, const uint64_t *out_off,
-                       const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who)
-{
-	const bool to_device = dst_addr != nullptr;
-	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (to_device ? !dst_pitch : (!bgr || !out_off))) { g_derr = "bad argument"; return NHW_E_ARG; }
-	for (int i = 0; i < nc; i++) if (off[i + 1] < off[i]) { g_derr = std::string(who) + ": off[] must not decrease"; return NHW_E_ARG; }
-	if (to_device) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_pitch[i] < 3ull * rects[i].width) { g_derr = std::string(who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
-	d->reg_tiles = d->reg_bytes = 0;
-	std::vector<RegionSource> src((size_t)nc);
-	std::vector<nhw_region> desc;
-	std::vector<int> which;                                      /* desc[k] is rect which[k] */
-	std::vector<uint64_t> toff;
-	std::vector<uint32_t> tlen;
-	std::vector<uint8_t> files;                                  /* the selected tile files, back to back */
-	uint64_t bytes = 0;
-	for (int i = 0; i < nr; i++) {
-		const nhw_rect &r = rects[i];
-		status[i] = NHW_E_ARG;
-		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
-		RegionSource &c = src[r.container];
-		const uint8_t *base = blob + off[r.container];
-		if (c.state == 0) {
-			c.state = nhw_container_parse(base, (size_t)(off[r.container + 1] - off[r.container]), &c.w, &c.h, &c.t, &c.dir) == NHW_OK ? 1 : -1;
-			if (c.state == 1) {
-				c.start.resize((size_t)c.t + 1);
-				c.start[0] = 16 + 4 * (uint64_t)c.t;
-				for (int k = 0; k < c.t; k++) c.start[k + 1] = c.start[k] + dir_len(c.dir, k);
-			}
-		}
-		if (c.state < 0) { status[i] = NHW_E_FORMAT; continue; }
-		const int nt = nhw_region_tiles(c.w, c.h, r.x, r.y, r.width, r.height);
-		if (nt < 1) continue;
-		if (toff.size() + (size_t)nt > MAX_CALL_TILES) { g_derr = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
-		status[i] = NHW_OK;
-		desc.push_back({ to_device ? dst_addr[i] : bytes, to_device ? dst_pitch[i] : 3ull * r.width, r.x, r.y, r.width, r.height, c.w, c.h, (uint32_t)toff.size(), 0 });
-		which.push_back(i);
-		bytes += 3ull * r.width * r.height;
-		const uint32_t nx = (c.w + 511) / 512, tx0 = r.x / 512, tx1 = (r.x + r.width - 1) / 512;
-		for (uint32_t ty = r.y / 512; ty <= (r.y + r.height - 1) / 512; ty++) {
-			const uint32_t k0 = ty * nx + tx0, k1 = ty * nx + tx1;
-			for (uint32_t k = k0; k <= k1; k++) { toff.push_back(files.size() + (c.start[k] - c.start[k0])); tlen.push_back(dir_len(c.dir, (int)k)); }
-			files.insert(files.end(), base + c.start[k0], base + c.start[k1 + 1]);
-		}
-	}
-	if (desc.empty()) return NHW_OK;
-	const int tiles = (int)toff.size(), ng = (int)desc.size();
-	HIPCHK(hipSetDevice(d->device));
-	{ const int rc = host_buffers(d, files.size()); if (rc) return rc; }
-	HIPCHK(nhw_grow(d->pic_desc, (size_t)ng * sizeof(nhw_region)));
-	if (!to_device) {
-		HIPCHK(nhw_grow(d->pic_px, bytes));
-		for (nhw_region &g : desc) g.addr += (uint64_t)(uintptr_t)d->pic_px.p;
-	}
-	const nhw_region *d_desc = d->pic_desc.as<nhw_region>();
-	hipStream_t s = d->own_stream;
-	HIPCHK(hipMemcpyAsync(d->blob.p, files.data(), files.size(), hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)ng * sizeof(nhw_region), hipMemcpyHostToDevice, s));
-	d->reg_tiles = (uint64_t)tiles; d->reg_bytes = files.size();
-	std::vector<int32_t> tst;
-	{ const int rc = decode_tile_list(d, toff, tlen, tst, [&](int t0, int m) { return nhw_launch_untile_region(d->d_out, d_desc, ng, t0, m, s); }); if (rc) return rc; }
-	std::vector<Span> sp;
-	for (int k = 0; k < ng; k++) {
-		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < ng ? (int)desc[k + 1].first_tile : tiles);
-		if (!to_device && status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
-	}
-	return download_spans(bgr, sp);
-}
-
-extern "C" int nhw_dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
-                               uint8_t *bgr, const uint64_t *out_off, int32_t *status)
-{
-	return dec_regions(d, blob, off, n_containers, rects, n_rects, bgr, out_off, nullptr, nullptr, status, "nhw_dec_regions");
-}
-
-extern "C" int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
-                                         const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status)
-{
-	if (!dst_addr) { g_derr = "bad argument"; return NHW_E_ARG; }
-	return dec_regions(d, blob, off, n_containers, rects, n_rects, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_regions_to_device");
-}
-
-extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)
-{
-	if (!d || !tiles_decoded || !bytes_uploaded) { g_derr = "bad argument"; return NHW_E_ARG; }
-	*tiles_decoded = d->reg_tiles; *bytes_uploaded = d->reg_bytes;
-	return NHW_OK;
-}
-
-/* the 54-byte header nhw-dec writes in front of the pixels (nhw_decoder_cli.c:61-65, :293-312) */
-extern "C" void nhw_dec_bmp_header(uint8_t h[54])
-{
-	static const uint8_t base[54] = { 66,77,54,0,12,0,0,0,0,0, 54,0,0,0,40,0,0,0,0,2, 0,0,0,2,0,0,1,0,24,0, 0,0,0,0,0,0,12,0,0,0 };
-	memcpy(h, base, 54);
 }

@@ -1,0 +1,253 @@
+/* nhw_dec_hostpath.hip -- the decoder's host conveniences: files in host memory in, pictures out (nhw_dec_batch), pictures of any size and regions of them out of
+ * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
+#include "nhw_dec.h"
+
+/* the host paths' buffers: the blob (grow-only, room for `total` bytes of files) and, on the first call, the per-file arrays and the
+ * decoded pictures of max_batch files */
+static int host_buffers(nhw_dec *d, size_t total)
+{
+	if (total + 64 > d->blob.cap) HIPCHK(nhw_grow(d->blob, total + (total >> 2) + (1u << 20)));   /* 64 spare bytes at least; a quarter and 1 MiB more when it grows, so that batches of a similar size do not reallocate */
+	return d->d_off ? NHW_OK : dev_alloc(host_set(d), nullptr, d->max_batch, nhw_dec_err);   /* all five or none: a half-made set would hand null pointers to the next call */
+}
+
+/* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1]. */
+extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality)
+{
+	if (!d || !nhw || !off || !bgr || !status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	HIPCHK(hipSetDevice(d->device));
+	const size_t total = (size_t)(off[n] - off[0]);
+	{ const int rc = host_buffers(d, total); if (rc) return rc; }
+	uint64_t *rel = (uint64_t *)malloc(((size_t)n + 1) * 12);
+	if (!rel) return NHW_E_ARG;
+	uint32_t *len = (uint32_t *)(rel + n + 1);
+	for (int i = 0; i < n; i++) {
+		rel[i] = off[i] - off[0];
+		const uint64_t l = off[i + 1] - off[i];
+		len[i] = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
+	}
+	hipError_t e1 = hipMemcpyAsync(d->blob.p, nhw + off[0], total, hipMemcpyHostToDevice, d->own_stream);
+	hipError_t e2 = hipMemcpyAsync(d->d_off, rel, (size_t)n * 8, hipMemcpyHostToDevice, d->own_stream);
+	hipError_t e4 = hipMemcpyAsync(d->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, d->own_stream);
+	hipError_t e3 = hipStreamSynchronize(d->own_stream);
+	free(rel);
+	HIPCHK(e1); HIPCHK(e2); HIPCHK(e4); HIPCHK(e3);
+	const int rc = nhw_dec_batch_device(d, d->blob.p, d->d_off, d->d_len, n, d->d_out, d->d_status, d->d_quality, d->own_stream);
+	if (rc) return rc;
+	HIPCHK(hipMemcpyAsync(bgr, d->d_out, (size_t)n * NHW_IMG_BYTES, hipMemcpyDeviceToHost, d->own_stream));
+	HIPCHK(hipMemcpyAsync(status, d->d_status, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
+	if (quality) HIPCHK(hipMemcpyAsync(quality, d->d_quality, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
+	HIPCHK(hipStreamSynchronize(d->own_stream));
+	return NHW_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------- pictures of any size (DESIGN.md sections 11, 13) */
+/* What nhw_dec_pictures and the region calls share: a container's directory, the chunked decode of a list of tile files, the status
+ * gather and the download of the results. */
+static uint32_t dir_len(const uint8_t *dir, int k)                /* length of tile file k in a container's directory */
+{
+	return (uint32_t)dir[4 * k] | ((uint32_t)dir[4 * k + 1] << 8) | ((uint32_t)dir[4 * k + 2] << 16) | ((uint32_t)dir[4 * k + 3] << 24);
+}
+
+static const size_t MAX_CALL_TILES = (size_t)(INT_MAX / 16);       /* the tiles one host call takes */
+
+/* The tile files of a call, in the handle's blob (already on its way there on the handle's stream): offsets and lengths go up, the tiles are
+ * decoded in chunks of max_batch into the host path's picture slots, each chunk followed by crop(t0, m) -- the launch that takes the
+ * decoded tiles [t0, t0 + m) out of d->d_out --, and the per-tile status comes back.  Synchronises the stream. */
+template <class Crop>
+static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const std::vector<uint32_t> &tlen, std::vector<int32_t> &tst, Crop &&crop)
+{
+	const int tiles = (int)toff.size();
+	HIPCHK(nhw_grow(d->pic_tiles, (size_t)tiles * 16));
+	uint64_t *d_toff = d->pic_tiles.as<uint64_t>();
+	uint32_t *d_tlen = (uint32_t *)(d_toff + tiles);
+	int32_t *d_tst = (int32_t *)(d_tlen + tiles);
+	hipStream_t s = d->own_stream;
+	HIPCHK(hipMemcpyAsync(d_toff, toff.data(), (size_t)tiles * 8, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d_tlen, tlen.data(), (size_t)tiles * 4, hipMemcpyHostToDevice, s));
+	for (int t0 = 0; t0 < tiles; t0 += d->max_batch) {
+		const int m = tiles - t0 < d->max_batch ? tiles - t0 : d->max_batch;
+		const int rc = nhw_dec_batch_device(d, d->blob.p, d_toff + t0, d_tlen + t0, m, d->d_out, d_tst + t0, nullptr, s);
+		if (rc) return rc;
+		HIPCHK(crop(t0, m));
+	}
+	tst.resize((size_t)tiles);
+	HIPCHK(hipMemcpyAsync(tst.data(), d_tst, (size_t)tiles * 4, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return NHW_OK;
+}
+
+static int32_t tiles_status(const std::vector<int32_t> &tst, int t0, int t1)   /* NHW_OK if the tiles [t0, t1) all decoded */
+{
+	for (int t = t0; t < t1; t++) if (tst[t] != NHW_OK) return NHW_E_FORMAT;
+	return NHW_OK;
+}
+
+/* results that decoded, device -> host: neighbours that are contiguous on both sides go as one copy */
+struct Span { uint64_t dev, host, len; };
+static int download_spans(uint8_t *bgr, const std::vector<Span> &sp)
+{
+	for (size_t k = 0; k < sp.size();) {
+		uint64_t len = sp[k].len;
+		size_t j = k + 1;
+		while (j < sp.size() && sp[j].dev == sp[k].dev + len && sp[j].host == sp[k].host + len) len += sp[j++].len;
+		HIPCHK(hipMemcpy(bgr + sp[k].host, (const void *)(uintptr_t)sp[k].dev, len, hipMemcpyDeviceToHost));
+		k = j;
+	}
+	return NHW_OK;
+}
+
+/* Parse every container on the host; upload the blob once (a container's tile files lie back to back, so the decoder's offsets and lengths
+ * come from its directory); decode the tiles in chunks of max_batch into the host path's picture slots and crop each chunk into the
+ * picture buffer (k_untile_crop); then bring back the pictures whose tiles all decoded. */
+extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+{
+	if (!d || !blob || !off || !bgr || !out_off || !status || n < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { nhw_dec_err = "nhw_dec_pictures: off[] must not decrease"; return NHW_E_ARG; }
+	std::vector<nhw_picture> desc;
+	std::vector<int> which;                                      /* desc[k] is container which[k] */
+	std::vector<uint64_t> toff;
+	std::vector<uint32_t> tlen;
+	uint64_t bytes = 0;
+	for (int i = 0; i < n; i++) {
+		uint32_t w = 0, h = 0;
+		int t = 0;
+		const uint8_t *dir = nullptr;
+		status[i] = NHW_E_FORMAT;
+		if (nhw_container_parse(blob + off[i], (size_t)(off[i + 1] - off[i]), &w, &h, &t, &dir) != NHW_OK) continue;
+		if (toff.size() + (size_t)t > MAX_CALL_TILES) { nhw_dec_err = "nhw_dec_pictures: too many tiles in one call"; return NHW_E_ARG; }
+		status[i] = NHW_OK;
+		desc.push_back({ bytes, 3ull * w, w, h, (uint32_t)toff.size(), 0 });
+		which.push_back(i);
+		uint64_t fo = off[i] - off[0] + 16 + 4 * (uint64_t)t;
+		for (int k = 0; k < t; k++) { toff.push_back(fo); tlen.push_back(dir_len(dir, k)); fo += tlen.back(); }
+		bytes += 3ull * w * h;
+	}
+	if (desc.empty()) return NHW_OK;
+	const int tiles = (int)toff.size(), np = (int)desc.size();
+	HIPCHK(hipSetDevice(d->device));
+	{ const int rc = host_buffers(d, (size_t)(off[n] - off[0])); if (rc) return rc; }
+	HIPCHK(nhw_grow(d->pic_px, bytes));
+	HIPCHK(nhw_grow(d->pic_desc, (size_t)np * sizeof(nhw_picture)));
+	for (nhw_picture &p : desc) p.addr += (uint64_t)(uintptr_t)d->pic_px.p;
+	const nhw_picture *d_desc = d->pic_desc.as<nhw_picture>();
+	hipStream_t s = d->own_stream;
+	HIPCHK(hipMemcpyAsync(d->blob.p, blob + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
+	std::vector<int32_t> tst;
+	{ const int rc = decode_tile_list(d, toff, tlen, tst, [&](int t0, int m) { return nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, s); }); if (rc) return rc; }
+	std::vector<Span> sp;
+	for (int k = 0; k < np; k++) {
+		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < np ? (int)desc[k + 1].first_tile : tiles);
+		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
+	}
+	return download_spans(bgr, sp);
+}
+
+/* ---------------------------------------------------------------------------------------------- regions of pictures */
+/* a container as the region calls see it: parsed once, when the first rect names it; start[k] = byte offset of tile file k in it */
+struct RegionSource {
+	int state;                                                   /* 0 not looked at, 1 well-formed, -1 malformed */
+	uint32_t w, h;
+	int t;
+	const uint8_t *dir;
+	std::vector<uint64_t> start;                                 /* t + 1 entries */
+};
+
+/* Both region calls: bgr / out_off (the regions packed in a device buffer of the handle, then downloaded) or dst_addr / dst_pitch (cropped
+ * straight into the caller's device memory).  The selected tile files are gathered on the host -- a selection row tx0 .. tx1 is one
+ * contiguous byte run of its container -- and go up as one blob; the decoder gets their offsets and lengths as it does for whole pictures,
+ * and every chunk is followed by k_untile_region. */
+static int dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, uint8_t *bgr, const uint64_t *out_off,
+                       const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who)
+{
+	const bool to_device = dst_addr != nullptr;
+	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (to_device ? !dst_pitch : (!bgr || !out_off))) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	for (int i = 0; i < nc; i++) if (off[i + 1] < off[i]) { nhw_dec_err = std::string(who) + ": off[] must not decrease"; return NHW_E_ARG; }
+	if (to_device) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_pitch[i] < 3ull * rects[i].width) { nhw_dec_err = std::string(who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
+	d->reg_tiles = d->reg_bytes = 0;
+	std::vector<RegionSource> src((size_t)nc);
+	std::vector<nhw_region> desc;
+	std::vector<int> which;                                      /* desc[k] is rect which[k] */
+	std::vector<uint64_t> toff;
+	std::vector<uint32_t> tlen;
+	std::vector<uint8_t> files;                                  /* the selected tile files, back to back */
+	uint64_t bytes = 0;
+	for (int i = 0; i < nr; i++) {
+		const nhw_rect &r = rects[i];
+		status[i] = NHW_E_ARG;
+		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
+		RegionSource &c = src[r.container];
+		const uint8_t *base = blob + off[r.container];
+		if (c.state == 0) {
+			c.state = nhw_container_parse(base, (size_t)(off[r.container + 1] - off[r.container]), &c.w, &c.h, &c.t, &c.dir) == NHW_OK ? 1 : -1;
+			if (c.state == 1) {
+				c.start.resize((size_t)c.t + 1);
+				c.start[0] = 16 + 4 * (uint64_t)c.t;
+				for (int k = 0; k < c.t; k++) c.start[k + 1] = c.start[k] + dir_len(c.dir, k);
+			}
+		}
+		if (c.state < 0) { status[i] = NHW_E_FORMAT; continue; }
+		const int nt = nhw_region_tiles(c.w, c.h, r.x, r.y, r.width, r.height);
+		if (nt < 1) continue;
+		if (toff.size() + (size_t)nt > MAX_CALL_TILES) { nhw_dec_err = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
+		status[i] = NHW_OK;
+		desc.push_back({ to_device ? dst_addr[i] : bytes, to_device ? dst_pitch[i] : 3ull * r.width, r.x, r.y, r.width, r.height, c.w, c.h, (uint32_t)toff.size(), 0 });
+		which.push_back(i);
+		bytes += 3ull * r.width * r.height;
+		const uint32_t nx = (c.w + 511) / 512, tx0 = r.x / 512, tx1 = (r.x + r.width - 1) / 512;
+		for (uint32_t ty = r.y / 512; ty <= (r.y + r.height - 1) / 512; ty++) {
+			const uint32_t k0 = ty * nx + tx0, k1 = ty * nx + tx1;
+			for (uint32_t k = k0; k <= k1; k++) { toff.push_back(files.size() + (c.start[k] - c.start[k0])); tlen.push_back(dir_len(c.dir, (int)k)); }
+			files.insert(files.end(), base + c.start[k0], base + c.start[k1 + 1]);
+		}
+	}
+	if (desc.empty()) return NHW_OK;
+	const int tiles = (int)toff.size(), ng = (int)desc.size();
+	HIPCHK(hipSetDevice(d->device));
+	{ const int rc = host_buffers(d, files.size()); if (rc) return rc; }
+	HIPCHK(nhw_grow(d->pic_desc, (size_t)ng * sizeof(nhw_region)));
+	if (!to_device) {
+		HIPCHK(nhw_grow(d->pic_px, bytes));
+		for (nhw_region &g : desc) g.addr += (uint64_t)(uintptr_t)d->pic_px.p;
+	}
+	const nhw_region *d_desc = d->pic_desc.as<nhw_region>();
+	hipStream_t s = d->own_stream;
+	HIPCHK(hipMemcpyAsync(d->blob.p, files.data(), files.size(), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)ng * sizeof(nhw_region), hipMemcpyHostToDevice, s));
+	d->reg_tiles = (uint64_t)tiles; d->reg_bytes = files.size();
+	std::vector<int32_t> tst;
+	{ const int rc = decode_tile_list(d, toff, tlen, tst, [&](int t0, int m) { return nhw_launch_untile_region(d->d_out, d_desc, ng, t0, m, s); }); if (rc) return rc; }
+	std::vector<Span> sp;
+	for (int k = 0; k < ng; k++) {
+		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < ng ? (int)desc[k + 1].first_tile : tiles);
+		if (!to_device && status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
+	}
+	return download_spans(bgr, sp);
+}
+
+extern "C" int nhw_dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
+                               uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+{
+	return dec_regions(d, blob, off, n_containers, rects, n_rects, bgr, out_off, nullptr, nullptr, status, "nhw_dec_regions");
+}
+
+extern "C" int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
+                                         const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status)
+{
+	if (!dst_addr) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	return dec_regions(d, blob, off, n_containers, rects, n_rects, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_regions_to_device");
+}
+
+extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)
+{
+	if (!d || !tiles_decoded || !bytes_uploaded) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	*tiles_decoded = d->reg_tiles; *bytes_uploaded = d->reg_bytes;
+	return NHW_OK;
+}
+
+/* the 54-byte header nhw-dec writes in front of the pixels (nhw_decoder_cli.c:61-65, :293-312) */
+extern "C" void nhw_dec_bmp_header(uint8_t h[54])
+{
+	static const uint8_t base[54] = { 66,77,54,0,12,0,0,0,0,0, 54,0,0,0,40,0,0,0,0,2, 0,0,0,2,0,0,1,0,24,0, 0,0,0,0,0,0,12,0,0,0 };
+	memcpy(h, base, 54);
+}

@@ -9,15 +9,10 @@
 /* workgroup barrier that orders LDS traffic only: global loads stay in flight across it */
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-/* one output pair of the 5/3 synthesis (wavelet_filterbank.c:305-496; upfilter53I / III / VI, filters.c:521-572): x holds the low band in cells 0 .. S/2-1 and the
- * high band behind it, st apart; the second direction normalises */
-template <int S>
-__device__ __forceinline__ void syn_pair(const int16_t *x, int st, int k, bool normalise, int *e_out, int *o_out)
+/* the 5/3 synthesis on five loaded taps (upfilter53I / III / VI, filters.c:521-572): l0 and ln are low-band cell k and the one behind it, h0, hp and hn high-band
+ * cell k, the one before and the one behind it; e / o: samples 2k and 2k + 1, un-normalised in 16 bits as the reference keeps them; the second direction normalises */
+__device__ __forceinline__ void syn_taps(int16_t l0, int16_t ln, int16_t h0, int16_t hp, int16_t hn, bool normalise, int *e_out, int *o_out)
 {
-	constexpr int M = S / 2;
-	const int16_t *lo = x, *hi = x + M * st;
-	const int l0 = lo[k * st], ln = (k + 1 < M) ? lo[(k + 1) * st] : l0;
-	const int h0 = hi[k * st], hp = k > 0 ? hi[(k - 1) * st] : hi[0], hn = (k + 1 < M) ? hi[(k + 1) * st] : h0;
 	int16_t e = (int16_t)(l0 << 3);
 	int16_t o = (int16_t)((l0 + ln) << 2);
 	e = (int16_t)(e - ((h0 + hp) << 1));
@@ -29,6 +24,17 @@ __device__ __forceinline__ void syn_pair(const int16_t *x, int st, int k, bool n
 		o >>= 6;
 	}
 	*e_out = e; *o_out = o;
+}
+/* one output pair of the synthesis (wavelet_filterbank.c:305-496): x holds the low band in cells 0 .. S/2-1 and the high band behind it, st apart; a line's
+ * ends repeat their own cell */
+template <int S>
+__device__ __forceinline__ void syn_pair(const int16_t *x, int st, int k, bool normalise, int *e_out, int *o_out)
+{
+	constexpr int M = S / 2;
+	const int16_t *lo = x, *hi = x + M * st;
+	const int l0 = lo[k * st], ln = (k + 1 < M) ? lo[(k + 1) * st] : l0;
+	const int h0 = hi[k * st], hp = k > 0 ? hi[(k - 1) * st] : hi[0], hn = (k + 1 < M) ? hi[(k + 1) * st] : h0;
+	syn_taps(l0, ln, h0, hp, hn, normalise, e_out, o_out);
 }
 
 /* rounding of the analysis' second direction (filters.c:88-287) */
