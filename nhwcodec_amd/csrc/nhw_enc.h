@@ -99,9 +99,6 @@ inline DevSet fit_sse_set(nhw_enc *e)
 	         dev_buf(e->fit_sse.sse_out, mb), dev_buf(e->fit_sse.dstatus, mb) };
 }
 
-static inline int16_t *plane16(const NhwWs &ws, int b) { return (int16_t *)(ws.base + ws.off[b]); }
-static inline uint8_t *plane8(const NhwWs &ws, int b) { return ws.base + ws.off[b]; }
-
 /* nhw_enc.hip: buffers of the host path for up to n images; on a failed allocation nothing dangles and the capacity stays what really exists */
 int host_buffers(nhw_enc *e, int n);
 /* nhw_enc_hostpath.hip */

@@ -36,8 +36,8 @@ extern "C" int nhw_enc_set_compat(nhw_enc *e, int mode)
 	if (e->ws.compat != mode && mode == NHW_COMPAT_CANONICAL) {      /* the compatibility mode writes behind ll1 and the level-2 copy: give the guards their zeros back */
 		HIPCHK(hipSetDevice(e->device));
 		HIPCHK(hipDeviceSynchronize());
-		HIPCHK(hipMemset2D(e->ws.base + e->ws.off[B_LL1] + 2 * Q, e->ws.stride[B_LL1], 0, 1024, (size_t)e->max_batch));
-		HIPCHK(hipMemset2D(e->ws.base + e->ws.off[B_L2SAVE] + 2 * Q, e->ws.stride[B_L2SAVE], 0, 256, (size_t)e->max_batch));
+		HIPCHK(hipMemset2D(e->ws.plane<uint8_t>(B_LL1).p + 2 * Q, e->ws.plane<uint8_t>(B_LL1).bytes(), 0, 1024, (size_t)e->max_batch));
+		HIPCHK(hipMemset2D(e->ws.plane<uint8_t>(B_L2SAVE).p + 2 * Q, e->ws.plane<uint8_t>(B_L2SAVE).bytes(), 0, 256, (size_t)e->max_batch));
 	}
 	e->ws.compat = mode;
 	return NHW_OK;
@@ -138,7 +138,6 @@ int host_buffers(nhw_enc *e, int n)
 	return rc;
 }
 
-
 /* a chroma component's launches up to the second dequantiser simulation, on stream cs (run_batch; nhw_stage_chroma_loops).  1 = carry on;
  * NHW_OK: the debug stop fell in here */
 #define STAGE_DONE() do { if (e->stop_after && ++stage == e->stop_after) { HIPCHK(hipGetLastError()); return NHW_OK; } } while (0)
@@ -146,38 +145,40 @@ static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hi
 {
 	const int q = ws.q;
 	const bool low = q <= 16;
-	const size_t cps = ws.stride[B_CJPEG] / 2;
-	uint8_t *out = nullptr; uint32_t *d_sizes = nullptr; int32_t *d_status = nullptr;   /* (the chroma phases write none of them) */
 	const bool vp = comp && ws.split_chroma;
-	int16_t *cjpeg = plane16(ws, vp ? B_CJPEG_V : B_CJPEG), *cproc = plane16(ws, vp ? B_CPROC_V : B_CPROC);
-	int16_t *cll1 = plane16(ws, vp ? B_CLL1_V : B_CLL1), *cl2save = plane16(ws, vp ? B_CL2SAVE_V : B_CL2SAVE);
+	const Plane<int16_t> cjpeg = ws.plane<int16_t>(vp ? B_CJPEG_V : B_CJPEG), cproc = ws.plane<int16_t>(vp ? B_CPROC_V : B_CPROC);
+	const Plane<int16_t> cll1 = ws.plane<int16_t>(vp ? B_CLL1_V : B_CLL1), cl2save = ws.plane<int16_t>(vp ? B_CL2SAVE_V : B_CL2SAVE);
+	const Plane<const uint8_t> bytes = ws.plane<const uint8_t>(comp ? B_PV : B_PU);
 	const bool widen_in_analysis = q > 14 && !ws.dbg;              /* the analysis reads the byte plane itself (the stage checks keep the copy as a stage of its own) */
-	if (q <= 14) nhw_launch_low_prefilter_chroma(comp ? plane8(ws, B_PV) : plane8(ws, B_PU), ws.stride[B_PU], cjpeg, cps, q, n, cs);   /* :2263 / :2579 */
-	else if (!widen_in_analysis) nhw_launch_phase(PH_C0, ws, comp, out, d_sizes, d_status, cs);
+	if (q <= 14) nhw_launch_low_prefilter_chroma(bytes, cjpeg, q, n, cs);   /* :2263 / :2579 */
+	else if (!widen_in_analysis) nhw_launch_phase(PH_C0, ws, comp, cs);
 	STAGE_DONE();
-	nhw_launch_analysis(cjpeg, cproc, n, cps, H, H, 0, cs, cll1, ws.stride[B_CLL1] / 2, H / 2, 2,   /* + the copy of LL1 */
-	                    widen_in_analysis ? (comp ? plane8(ws, B_PV) : plane8(ws, B_PU)) : nullptr, ws.stride[B_PU], ws.dbg ? 0 : 2);   /* 2: nor the LL quadrant back into the work plane -- the level-2 analysis below reads its copy */
-	if (low) nhw_launch_low_chroma_thin(cproc, cps, n, cs);      /* :2277-2308 / :2590-2621 */
+	NhwAnalysis l1 = NhwAnalysis{ cjpeg, cproc, n, H, H, 0 }.saving(cll1, H / 2, ANA_SAVE_LL);   /* + the copy of LL1 */
+	l1.store = ws.dbg ? ANA_STORE_ALL : ANA_STORE_NO_T_LL_SAVED;   /* production: nor the LL quadrant back into the work plane -- the level-2 analysis reads its copy */
+	if (widen_in_analysis) l1.src8 = bytes;
+	nhw_launch_analysis(l1, cs);
+	if (low) nhw_launch_low_chroma_thin(cproc, n, cs);           /* :2277-2308 / :2590-2621 */
 	STAGE_DONE();
 	STAGE_DONE();
 	if (!ws.dbg) {   /* both closed loops on one residency of the level-2 block, from the copy of LL1 (k_chroma_loops); the stage checks take the seven kernels */
-		nhw_launch_chroma_loops(cproc, cps, cll1, ws.stride[B_CLL1] / 2, cl2save, ws.stride[B_CL2SAVE] / 2, plane8(ws, B_PU), ws.stride[B_PU], q, comp, ws.compat, n, cs);
+		nhw_launch_chroma_loops(cproc, cll1, cl2save, ws.plane<const uint8_t>(B_PU), q, comp, ws.compat, n, cs);
 		return 1;
 	}
-	nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs);
+	const NhwAnalysis l2{ cjpeg, cproc, n, H, H / 2, 1 };
+	nhw_launch_analysis(l2, cs);
 	STAGE_DONE();
-	nhw_launch_phase(PH_C2, ws, comp, out, d_sizes, d_status, cs);
+	nhw_launch_phase(PH_C2, ws, comp, cs);
 	STAGE_DONE();
-	nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, cs);
+	nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, cs);
 	STAGE_DONE();
-	nhw_launch_phase(PH_C3, ws, comp, out, d_sizes, d_status, cs);
+	nhw_launch_phase(PH_C3, ws, comp, cs);
 	STAGE_DONE();
-	nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, cs, cl2save, ws.stride[B_CL2SAVE] / 2, H / 2, 1);   /* + the copy of the level-2 block */
+	nhw_launch_analysis(l2.saving(cl2save, H / 2, ANA_SAVE_BLOCK), cs);   /* + the copy of the level-2 block */
 	STAGE_DONE();
 	STAGE_DONE();
-	nhw_launch_phase(PH_C4, ws, comp, out, d_sizes, d_status, cs);
+	nhw_launch_phase(PH_C4, ws, comp, cs);
 	STAGE_DONE();
-	nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, cs);
+	nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, cs);
 	STAGE_DONE();
 	return 1;
 }
@@ -187,27 +188,24 @@ static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hi
 static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage)
 {
 	const int q = ws.q;
-	int16_t *jpeg = plane16(ws, B_JPEG), *proc = plane16(ws, B_PROC);
-	const size_t ps = ws.stride[B_JPEG] / 2;
-	uint8_t *out = nullptr; uint32_t *d_sizes = nullptr; int32_t *d_status = nullptr;   /* (these phases write none of them) */
-	/* Y4: level-2 analysis (:139) */
-	/* the LL rows come from ll1 (the front's copy of them in natural orientation, res256): the front does not write them into the work plane as well
-	 * outside the stage checks, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane) */
-	nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, H);
+	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC), ll1 = ws.plane<int16_t>(B_LL1), l2save = ws.plane<int16_t>(B_L2SAVE);
+	const NhwAnalysis l2{ jpeg, proc, n, W, H, 1 };
+	/* Y4: level-2 analysis (:139).  The LL rows come from ll1 (the front's copy of them in natural orientation, res256): outside the stage checks the front
+	 * does not write them into the work plane as well, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane) */
+	nhw_launch_analysis(l2.from(ll1, H), s);
 	STAGE_DONE();
 	if (q > 6) {                                                     /* first closed loop (:141-283) */
-	nhw_launch_phase(PH_L1, ws, 0, out, d_sizes, d_status, s);
+	nhw_launch_phase(PH_L1, ws, 0, s);
 	nhw_launch_wave(WV_DQ1, ws, s);          /* every quality (1..16: rationed low bits, no marking passes) */
 	STAGE_DONE();
 	if (ws.dbg) {
-	nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s);
+	nhw_launch_synthesis(jpeg, proc, n, W, H, 0, s);
 	STAGE_DONE();
-	nhw_launch_phase(PH_L2, ws, 0, out, d_sizes, d_status, s);
+	nhw_launch_phase(PH_L2, ws, 0, s);
 	STAGE_DONE();
-	} else nhw_launch_l2_recon(jpeg, proc, ps, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, n, s,   /* synthesis + Y8 + Y9 on one residency of the block; the stage checks take the three kernels */
-	                           q > 12 ? plane16(ws, B_L2SAVE) : nullptr, ws.stride[B_L2SAVE] / 2);   /* q > 12: + the second analysis and Y13 (:623-631), still on that residency */
-	if (q <= 12) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);   /* (Y11 / Y12 follow, and Y13's copy behind them) */
-	else if (ws.dbg) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, plane16(ws, B_L2SAVE), ws.stride[B_L2SAVE] / 2, H, 1);   /* + Y13: copy of the coefficient block */
+	} else nhw_launch_l2_recon(jpeg, proc, ll1, q > 12 ? l2save : Plane<int16_t>{}, n, s);   /* synthesis + Y8 + Y9 on one residency of the block (the stage checks take the three kernels); q > 12: + the second analysis and Y13 (:623-631), still on that residency */
+	if (q <= 12) nhw_launch_analysis(l2, s);                         /* (Y11 / Y12 follow, and Y13's copy behind them) */
+	else if (ws.dbg) nhw_launch_analysis(l2.saving(l2save, H, ANA_SAVE_BLOCK), s);   /* + Y13: copy of the coefficient block */
 	STAGE_DONE();
 	}
 	return 1;
@@ -221,45 +219,42 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	NhwWs ws = ws_in;
 	const int q = quality;
 	const bool low = q <= 16;      /* integer colour, the rationed pre-filter of image_processing.c:838-2423 and the other quality 1..16 forms (nhw_low.hip) */
-	int16_t *jpeg = plane16(ws, B_JPEG), *proc = plane16(ws, B_PROC);
-	int16_t *cjpeg = plane16(ws, B_CJPEG), *cproc = plane16(ws, B_CPROC);
-	const size_t ps = ws.stride[B_JPEG] / 2, cps = ws.stride[B_CJPEG] / 2;
-	uint8_t *out = (uint8_t *)d_out;
+	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC);
+	const Plane<uint8_t> pu = ws.plane<uint8_t>(B_PU), pv = ws.plane<uint8_t>(B_PV);
 
 	e->low_parts_used = 1;         /* until the pre-filter below runs in sub-batches: the chroma fork never waits on an event of an earlier batch */
 	int stage = 0;
-	(void)n;
 	if (what & 1) {
 	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_START], s));
 	/* a1 + a2 + Y2 + Y3: colour + 4:2:0, pre-filter (q<=21, nhw_encoder.c:116-119), level-1 analysis (:125), LL1 copy (:127-135): ONE kernel
 	 * for quality 17..23 (k_front_image with the pre-filter, k_front_plain without: a workgroup walks an image top to bottom).  The luma plane
 	 * never reaches HBM.  Quality 1..16: colour kernel -> luma plane, the rationed pre-filter (nhw_low.hip) -> k_front_plain's input plane. */
-	int16_t *yin = plane16(ws, B_KMAP);
-	const size_t yin_stride = ws.stride[B_KMAP];
+	const Plane<int16_t> yin = ws.plane<int16_t>(B_KMAP);
+	NhwFront f;
+	f.q = q; f.n = n; f.y = yin /* quality 17..23, developer builds only: a plane for a dump */; f.st = ws.plane<uint8_t>(B_ROWSTATE);
+	f.proc = proc; f.jpeg = jpeg; f.ll1 = ws.plane<int16_t>(B_LL1); f.switches = ws.dbg ? 2 : 0;
 	if (low) {
-		nhw_launch_color((const uint8_t *)d_bgr, n, q, jpeg, ws.stride[B_JPEG], plane8(ws, B_PU), plane8(ws, B_PV), ws.stride[B_PU], s);
+		nhw_launch_color((const uint8_t *)d_bgr, n, q, jpeg, pu, pv, s);
 		HIPCHK(hipEventRecord(e->ev[EV_COLOR], s));                      /* with the front group, whoever brackets it: nhw_timing.color_dwt_ms / prefilter_ms */
 		STAGE_DONE();
 		{ const int lparts = (timed == 1 && what == 3 && !e->stop_after && n >= 1024) ? e->low_parts : 1;   /* (the stage checks and small batches: in line) */
 		  e->low_parts_used = lparts;
-		  HIPCHK((hipError_t)nhw_launch_low_prefilter(jpeg, ws.stride[B_JPEG] / 2, yin, yin_stride / 2, proc, ps, plane8(ws, B_SCAN), ws.stride[B_SCAN], plane8(ws, B_KEEP), ws.stride[B_KEEP], (uint16_t *)plane8(ws, B_LOWTAB), ws.stride[B_LOWTAB], q, n, s, (e->front_fallback & 1) ? 32 : 0,
+		  HIPCHK((hipError_t)nhw_launch_low_prefilter(jpeg, yin, proc, ws.plane<uint8_t>(B_SCAN), ws.plane<uint8_t>(B_KEEP), ws.plane<uint8_t>(B_LOWTAB), q, n, s, (e->front_fallback & 1) ? 32 : 0,
 		                                              lparts, e->low_stream, e->low_ev)); }   /* contrast map -> proc plane, flags -> scan buffer: both free until the band kernel / the quantiser; the pair machine's answers -> the q >= 22 plane */
 		HIPCHK(hipEventRecord(e->ev[EV_PREFILTER], s));
 		STAGE_DONE();
-		if (ws.compat) nhw_launch_low_stale(proc, ps, plane16(ws, B_STALE), ws.stride[B_STALE], n, s);   /* compatibility mode only: the map cells the stock binary's heap re-uses */
-		nhw_launch_front_fused(nullptr, q, nullptr, nullptr, 0, yin, yin_stride, 0, plane8(ws, B_ROWSTATE), ws.stride[B_ROWSTATE],
-		                       proc, jpeg, ps, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, nullptr, 0, n, s, ws.dbg ? 2 : 0);
+		if (ws.compat) nhw_launch_low_stale(proc, ws.plane<uint8_t>(B_STALE), n, s);   /* compatibility mode only: the map cells the stock binary's heap re-uses */
 	} else {
 		HIPCHK(hipEventRecord(e->ev[EV_COLOR], s)); HIPCHK(hipEventRecord(e->ev[EV_PREFILTER], s));   /* no kernels of their own for colour and pre-filter: both times 0 */
 		STAGE_DONE();
 		if (q < 22) STAGE_DONE();
-		nhw_launch_front_fused((const uint8_t *)d_bgr, q, plane8(ws, B_PU), plane8(ws, B_PV), ws.stride[B_PU], yin, yin_stride /* developer builds only: a plane for a dump */, q < 22,
-		                       plane8(ws, B_ROWSTATE), ws.stride[B_ROWSTATE], proc, jpeg, ps, plane16(ws, B_LL1), ws.stride[B_LL1] / 2,
-		                       q > 21 ? plane16(ws, B_KEEP) : nullptr, ws.stride[B_KEEP] / 2, n, s, (e->front_fallback & 1) | (ws.dbg ? 2 : 0));
-		if (ws.compat && q < 22) {   /* compatibility mode only: the kernel-map cells the stock binary's heap re-uses are replayed from a luma plane */
-			nhw_launch_color((const uint8_t *)d_bgr, n, q, yin, yin_stride, plane8(ws, B_PU), plane8(ws, B_PV), ws.stride[B_PU], s);
-			nhw_launch_front_stale(yin, yin_stride, plane8(ws, B_ROWSTATE), ws.stride[B_ROWSTATE], plane16(ws, B_STALE), ws.stride[B_STALE], n, s);
-		}
+		f.bgr = (const uint8_t *)d_bgr; f.pu = pu; f.pv = pv; f.with_prefilter = q < 22; f.switches |= e->front_fallback & 1;
+		if (q > 21) f.keep = ws.plane<int16_t>(B_KEEP);
+	}
+	nhw_launch_front_fused(f, s);
+	if (!low && ws.compat && q < 22) {   /* compatibility mode only: the kernel-map cells the stock binary's heap re-uses are replayed from a luma plane */
+		nhw_launch_color((const uint8_t *)d_bgr, n, q, yin, pu, pv, s);
+		nhw_launch_front_stale(yin, f.st, ws.plane<uint8_t>(B_STALE), n, s);
 	}
 	STAGE_DONE();
 	STAGE_DONE();
@@ -277,7 +272,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	ws.split_chroma = fork;                                          /* (the stage checks and the in-line order keep the reference's one set of planes) */
 	auto chroma_head = [&](int comp) -> int { return chroma_head_launches(e, ws, comp, n, cs, stage); };   /* everything up to the second dequantiser simulation */
 	auto chroma_tail = [&](int comp) -> int {                        /* marks, LL2 emission (appends to the exception list), quantiser, stream bytes */
-		nhw_launch_phase(PH_C5, ws, comp, out, d_sizes, d_status, cs);
+		nhw_launch_phase(PH_C5, ws, comp, cs);
 		STAGE_DONE();
 		return 1;
 	};
@@ -289,8 +284,8 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	}
 	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12) */
 	if (q <= 12) {                                                   /* Y11 (q <= 11), Y12, then Y13 */
-		nhw_launch_low_ll2(proc, ps, q, n, s);
-		nhw_launch_copy_block(proc, ps, W, plane16(ws, B_L2SAVE), ws.stride[B_L2SAVE] / 2, H, H, H, n, s);
+		nhw_launch_low_ll2(proc, q, n, s);
+		nhw_launch_copy_block(proc, W, ws.plane<int16_t>(B_L2SAVE), H, H, H, n, s);
 	}
 	STAGE_DONE();
 	nhw_launch_wave(WV_EMIT, ws, s);                                 /* Y14, Y15 */
@@ -301,11 +296,11 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	if (fork_ll) {
 		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_FORK], s));
 		HIPCHK(hipStreamWaitEvent(e->ll_stream, e->ll_ev[LL_EV_FORK], 0));
-		nhw_launch_phase(PH_L3, ws, 0, out, d_sizes, d_status, e->ll_stream);
+		nhw_launch_phase(PH_L3, ws, 0, e->ll_stream);
 		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_DONE], e->ll_stream));
 		HIPCHK(hipEventRecord(e->part_ev[PE_LUMA_LIST], e->ll_stream));   /* exception list of the luma plane complete, and the coder through with the bytes behind the luma samples: the chroma emission writes its own there */
 	} else {
-	nhw_launch_phase(PH_L3, ws, 0, out, d_sizes, d_status, s);
+	nhw_launch_phase(PH_L3, ws, 0, s);
 	if (fork) HIPCHK(hipEventRecord(e->part_ev[PE_LUMA_LIST], s));              /* exception list of the luma plane complete */
 	}
 	if (q > 12) {                                                    /* second closed loop (:759-779) */
@@ -313,12 +308,13 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	STAGE_DONE();
 	if (fork_ll) {
 		HIPCHK(hipStreamWaitEvent(s, e->ll_ev[LL_EV_DONE], 0));               /* (the coder is long done: the simulation takes twice its time) */
-		nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s, q <= 21 && !ws.dbg, ws.buf<uint16_t>(B_LLMEM, 0), ws.stride[B_LLMEM], &ws.buf<NhwMeta>(B_META, 0)->ll_mem_len, ws.stride[B_META]);
+		const Plane<const uint8_t> meta = ws.plane<const uint8_t>(B_META), len{ meta.p + offsetof(NhwMeta, ll_mem_len), meta.pitch };
+		nhw_launch_synthesis(jpeg, proc, n, W, H, q <= 21 && !ws.dbg, ws.plane<const uint8_t>(B_LLMEM), len, s);
 	} else
-	nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s, q <= 21 && !ws.dbg);   /* its copy in natural orientation is only read by Y19 (q > 21, :766-777) */
+	nhw_launch_synthesis(jpeg, proc, n, W, H, q <= 21 && !ws.dbg, s);   /* its copy in natural orientation is only read by Y19 (q > 21, :766-777) */
 	STAGE_DONE();
 	}
-	nhw_launch_phase(PH_L4A, ws, 0, out, d_sizes, d_status, s);      /* Y19-Y23 */
+	nhw_launch_phase(PH_L4A, ws, 0, s);      /* Y19-Y23 */
 	/* Y24, Y25: the position lists are read by nothing before the packetiser, and what the pass leaves in the residual-code plane by nobody
 	 * at all; below q21 it shares no scratch with the passes behind it either (from q21 on its third list and Y27's snapshot both live in
 	 * the hs plane, and Y29 needs Y24), so there it runs beside them on a stream of its own */
@@ -326,17 +322,17 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	if (fork_lists) {
 		HIPCHK(hipEventRecord(e->part_ev[PE_LISTS_FORK], s));
 		HIPCHK(hipStreamWaitEvent(e->part_stream[1], e->part_ev[PE_LISTS_FORK], 0));
-		nhw_launch_phase(PH_L4B, ws, 0, out, d_sizes, d_status, e->part_stream[1]);
+		nhw_launch_phase(PH_L4B, ws, 0, e->part_stream[1]);
 		HIPCHK(hipEventRecord(e->part_ev[PE_LISTS], e->part_stream[1]));
 	} else if (q > 12)
-		nhw_launch_phase(PH_L4B, ws, 0, out, d_sizes, d_status, s);  /* Y24, Y25 (:1498) */
-	nhw_launch_phase(PH_L4C, ws, 0, out, d_sizes, d_status, s);      /* Y26, Y27 */
+		nhw_launch_phase(PH_L4B, ws, 0, s);  /* Y24, Y25 (:1498) */
+	nhw_launch_phase(PH_L4C, ws, 0, s);      /* Y26, Y27 */
 	const bool early_join = fork && e->quant_join;
 	auto chroma_rest = [&]() -> int {
 		HIPCHK(hipStreamWaitEvent(cs, e->part_ev[PE_LUMA_LIST], 0));
 		CHROMA(chroma_tail(0));
 		CHROMA(chroma_tail(1));
-		nhw_launch_phase(PH_LLC, ws, 0, out, d_sizes, d_status, cs);   /* Z1: the chroma LL2 coder appends to the luma one's output (Y16, long done) */
+		nhw_launch_phase(PH_LLC, ws, 0, cs);   /* Z1: the chroma LL2 coder appends to the luma one's output (Y16, long done) */
 		HIPCHK(hipEventRecord(e->part_ev[PE_CHROMA], cs));
 		return 1;
 	};
@@ -350,9 +346,9 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_CHROMA], 0));
 	}
 	nhw_launch_wave(WV_QUANT, ws, s);                                /* Y28 (+ Y30: the symbols leave in stream order), every quality */
-	if (q > 21) nhw_launch_phase(PH_L4C2, ws, 0, out, d_sizes, d_status, s);   /* Y29 */
+	if (q > 21) nhw_launch_phase(PH_L4C2, ws, 0, s);   /* Y29 */
 	if (fork && !early_join) CHROMA(chroma_rest());                  /* queued here so that the wait finds its event recorded */
-	nhw_launch_phase(PH_L4D, ws, 0, out, d_sizes, d_status, s);      /* Y31 (Y30, the stream order, is the quantisers' output order) */
+	nhw_launch_phase(PH_L4D, ws, 0, s);      /* Y31 (Y30, the stream order, is the quantisers' output order) */
 	STAGE_DONE();
 	if (timed) HIPCHK(hipEventRecord(e->ev[EV_LUMA], s));
 
@@ -365,8 +361,8 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		}
 #undef CHROMA
 	if (timed) HIPCHK(hipEventRecord(e->ev[EV_CHROMA], s));
-	if (!fork) nhw_launch_phase(PH_LLC, ws, 0, out, d_sizes, d_status, s);     /* Z1 */
-	nhw_launch_phase(PH_FINAL, ws, 0, out, d_sizes, d_status, s);   /* Z2, container */
+	if (!fork) nhw_launch_phase(PH_LLC, ws, 0, s);     /* Z1 */
+	nhw_launch_final(ws, (uint8_t *)d_out, d_sizes, d_status, s);   /* Z2, container */
 	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_END], s));
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
@@ -447,7 +443,7 @@ extern "C" int nhw_stage_color(nhw_enc *e, const void *d_bgr, int n, int quality
 	if (!e || n < 1) return NHW_E_ARG;
 	if (quality < 1 || quality > 23) return NHW_E_QUALITY;          /* this stage covers every quality (the whole encoder: 17..23) */
 	HIPCHK(hipSetDevice(e->device));
-	nhw_launch_color((const uint8_t *)d_bgr, n, quality, (int16_t *)d_y, 8 * Q, (uint8_t *)d_u, (uint8_t *)d_v, Q, stream ? (hipStream_t)stream : e->own_stream);
+	nhw_launch_color((const uint8_t *)d_bgr, n, quality, Plane<int16_t>{ (int16_t *)d_y, 4 * Q }, Plane<uint8_t>{ (uint8_t *)d_u, Q }, Plane<uint8_t>{ (uint8_t *)d_v, Q }, stream ? (hipStream_t)stream : e->own_stream);
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
 }
@@ -462,8 +458,9 @@ extern "C" int nhw_stage_prefilter(nhw_enc *e, void *d_y, int n, int quality, vo
 	const NhwWs &ws = e->ws;
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
 	/* in place for the caller: filter into the workspace plane the encoder uses, copy back */
-	HIPCHK((hipError_t)nhw_launch_low_prefilter((const int16_t *)d_y, 4 * Q, plane16(ws, B_KMAP), ws.stride[B_KMAP] / 2, plane16(ws, B_PROC), ws.stride[B_PROC] / 2, plane8(ws, B_SCAN), ws.stride[B_SCAN], plane8(ws, B_KEEP), ws.stride[B_KEEP], (uint16_t *)plane8(ws, B_LOWTAB), ws.stride[B_LOWTAB], quality, n, s));
-	HIPCHK(hipMemcpy2DAsync(d_y, 8 * Q, plane16(ws, B_KMAP), ws.stride[B_KMAP], 8 * Q, (size_t)n, hipMemcpyDeviceToDevice, s));
+	const Plane<int16_t> filtered = ws.plane<int16_t>(B_KMAP);
+	HIPCHK((hipError_t)nhw_launch_low_prefilter(Plane<const int16_t>{ (const int16_t *)d_y, 4 * Q }, filtered, ws.plane<int16_t>(B_PROC), ws.plane<uint8_t>(B_SCAN), ws.plane<uint8_t>(B_KEEP), ws.plane<uint8_t>(B_LOWTAB), quality, n, s, 0, 1 /* in line */, e->low_stream, e->low_ev));
+	HIPCHK(hipMemcpy2DAsync(d_y, 8 * Q, filtered.p, filtered.bytes(), 8 * Q, (size_t)n, hipMemcpyDeviceToDevice, s));
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
 }
@@ -503,7 +500,7 @@ extern "C" int nhw_stage_analysis(nhw_enc *e, void *d_jpeg, void *d_proc, int n_
 		}
 		const NhwWs &ws = e->ws;
 		{                                                          /* the domain check: U = largest sample (or 0), L = -smallest (or 0); 104 U + 40 L and 104 L + 40 U at most NHW_ANA512_BOUND */
-			int *d_mm = reinterpret_cast<int *>(plane8(ws, B_ROWSTATE)), mm[2] = { 32767, -32768 };   /* (the front kernel's row-state bytes: free until it runs) */
+			int *d_mm = reinterpret_cast<int *>(ws.plane<uint8_t>(B_ROWSTATE).p), mm[2] = { 32767, -32768 };   /* (the front kernel's row-state bytes: free until it runs) */
 			HIPCHK(hipMemcpyAsync(d_mm, mm, sizeof mm, hipMemcpyHostToDevice, s));
 			k_plane_range<<<dim3(32, n_img), 256, 0, s>>>((const int16_t *)d_jpeg, plane_stride, d_mm);
 			HIPCHK(hipMemcpyAsync(mm, d_mm, sizeof mm, hipMemcpyDeviceToHost, s));
@@ -515,11 +512,14 @@ extern "C" int nhw_stage_analysis(nhw_enc *e, void *d_jpeg, void *d_proc, int n_
 			}
 		}
 		/* the level-1 kernel's input is a plane of its own (the caller's jpeg plane receives the LL rows) */
-		HIPCHK(hipMemcpy2DAsync(plane16(ws, B_KMAP), ws.stride[B_KMAP], d_jpeg, plane_stride * 2, 8 * Q, (size_t)n_img, hipMemcpyDeviceToDevice, s));
-		nhw_launch_front_fused(nullptr, 20, nullptr, nullptr, 0, plane16(ws, B_KMAP), ws.stride[B_KMAP], 0, plane8(ws, B_ROWSTATE), ws.stride[B_ROWSTATE],
-		                       (int16_t *)d_proc, (int16_t *)d_jpeg, plane_stride, plane16(ws, B_LL1), ws.stride[B_LL1] / 2, nullptr, 0, n_img, s, 2);
+		const Plane<int16_t> in = ws.plane<int16_t>(B_KMAP);
+		HIPCHK(hipMemcpy2DAsync(in.p, in.bytes(), d_jpeg, plane_stride * 2, 8 * Q, (size_t)n_img, hipMemcpyDeviceToDevice, s));
+		NhwFront f;
+		f.q = 20; f.n = n_img; f.y = in; f.st = ws.plane<uint8_t>(B_ROWSTATE);
+		f.proc = { (int16_t *)d_proc, plane_stride }; f.jpeg = { (int16_t *)d_jpeg, plane_stride }; f.ll1 = ws.plane<int16_t>(B_LL1); f.switches = 2;
+		nhw_launch_front_fused(f, s);
 	} else if (size == 256 || size == 128)
-		nhw_launch_analysis((int16_t *)d_jpeg, (int16_t *)d_proc, n_img, plane_stride, stride, size, final_level, s);
+		nhw_launch_analysis(NhwAnalysis{ { (int16_t *)d_jpeg, plane_stride }, { (int16_t *)d_proc, plane_stride }, n_img, stride, size, final_level }, s);
 	else { nhw_enc_err = "transform size must be 512, 256 or 128"; return NHW_E_ARG; }
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
@@ -539,9 +539,9 @@ extern "C" int nhw_stage_chroma_l1(nhw_enc *e, int n, void *stream)
 	const NhwWs &ws = e->ws;
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
 	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));                     /* behind that batch, whatever stream it ran on: its chroma sequence (a stream of the handle) works in the planes written here */
-	for (int comp = 0; comp < 2; comp++)
-		nhw_launch_analysis(plane16(ws, B_CJPEG), plane16(ws, B_CPROC), n, ws.stride[B_CJPEG] / 2, H, H, 0, s, plane16(ws, B_CLL1), ws.stride[B_CLL1] / 2, H / 2, 2,
-		                    comp ? plane8(ws, B_PV) : plane8(ws, B_PU), ws.stride[B_PU], 2);
+	NhwAnalysis l1 = NhwAnalysis{ ws.plane<int16_t>(B_CJPEG), ws.plane<int16_t>(B_CPROC), n, H, H, 0 }.saving(ws.plane<int16_t>(B_CLL1), H / 2, ANA_SAVE_LL);
+	l1.store = ANA_STORE_NO_T_LL_SAVED;
+	for (int comp = 0; comp < 2; comp++) { l1.src8 = ws.plane<const uint8_t>(comp ? B_PV : B_PU); nhw_launch_analysis(l1, s); }
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
 }
@@ -567,23 +567,23 @@ extern "C" int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, voi
 	ws.n = n; ws.q = e->last_q; ws.dbg = 0; ws.split_chroma = false;
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
 	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
-	int16_t *cjpeg = plane16(ws, B_CJPEG), *cproc = plane16(ws, B_CPROC), *cll1 = plane16(ws, B_CLL1), *cl2save = plane16(ws, B_CL2SAVE);
-	const size_t cps = ws.stride[B_CJPEG] / 2;
+	const Plane<int16_t> cjpeg = ws.plane<int16_t>(B_CJPEG), cproc = ws.plane<int16_t>(B_CPROC), cll1 = ws.plane<int16_t>(B_CLL1), cl2save = ws.plane<int16_t>(B_CL2SAVE);
 	if (form == 0) {
 		int stage = 0;
 		const int rc = chroma_head_launches(e, ws, comp, n, s, stage);
 		if (rc != 1) return rc;
 	} else if (form == 1)
-		nhw_launch_chroma_loops(cproc, cps, cll1, ws.stride[B_CLL1] / 2, cl2save, ws.stride[B_CL2SAVE] / 2, plane8(ws, B_PU), ws.stride[B_PU], ws.q, comp, ws.compat, n, s);
+		nhw_launch_chroma_loops(cproc, cll1, cl2save, ws.plane<const uint8_t>(B_PU), ws.q, comp, ws.compat, n, s);
 	else {
 		const int k = form - 1;
-		nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, cll1, ws.stride[B_CLL1] / 2, H / 2);
-		if (k > 1) nhw_launch_phase(PH_C2, ws, comp, nullptr, nullptr, nullptr, s);
-		if (k > 2) nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, s);
-		if (k > 3) nhw_launch_phase(PH_C3, ws, comp, nullptr, nullptr, nullptr, s);
-		if (k > 4) nhw_launch_analysis(cjpeg, cproc, n, cps, H, H / 2, 1, s, cl2save, ws.stride[B_CL2SAVE] / 2, H / 2, 1);
-		if (k > 5) nhw_launch_phase(PH_C4, ws, comp, nullptr, nullptr, nullptr, s);
-		if (k > 6) nhw_launch_synthesis(cjpeg, cproc, n, cps, H, H / 2, s);
+		const NhwAnalysis l2{ cjpeg, cproc, n, H, H / 2, 1 };
+		nhw_launch_analysis(l2.from(cll1, H / 2), s);
+		if (k > 1) nhw_launch_phase(PH_C2, ws, comp, s);
+		if (k > 2) nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, s);
+		if (k > 3) nhw_launch_phase(PH_C3, ws, comp, s);
+		if (k > 4) nhw_launch_analysis(l2.saving(cl2save, H / 2, ANA_SAVE_BLOCK), s);
+		if (k > 5) nhw_launch_phase(PH_C4, ws, comp, s);
+		if (k > 6) nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, s);
 	}
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
@@ -608,27 +608,26 @@ extern "C" int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream)
 	ws.n = n; ws.q = e->last_q; ws.dbg = 0;
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
 	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
-	int16_t *jpeg = plane16(ws, B_JPEG), *proc = plane16(ws, B_PROC), *ll1 = plane16(ws, B_LL1), *l2save = plane16(ws, B_L2SAVE);
-	const size_t ps = ws.stride[B_JPEG] / 2;
+	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC), ll1 = ws.plane<int16_t>(B_LL1), l2save = ws.plane<int16_t>(B_L2SAVE);
+	const NhwAnalysis l2{ jpeg, proc, n, W, H, 1 };
 	const bool save = ws.q > 12;
 	if (form == 0) {
 		int stage = 0;
 		const int rc = luma_loop_launches(e, ws, n, s, stage);
 		if (rc != 1) return rc;
 	} else if (form == 1) {
-		nhw_launch_l2_recon(jpeg, proc, ps, ll1, ws.stride[B_LL1] / 2, n, s, save ? l2save : nullptr, ws.stride[B_L2SAVE] / 2);
-		if (!save) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);
+		nhw_launch_l2_recon(jpeg, proc, ll1, save ? l2save : Plane<int16_t>{}, n, s);
+		if (!save) nhw_launch_analysis(l2, s);
 	} else {
 		if (form == 3 || form == 4) {
-			nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, nullptr, 0, 0, 0, nullptr, 0, 0, ll1, ws.stride[B_LL1] / 2, H);
-			nhw_launch_phase(PH_L1, ws, 0, nullptr, nullptr, nullptr, s);
+			nhw_launch_analysis(l2.from(ll1, H), s);
+			nhw_launch_phase(PH_L1, ws, 0, s);
 			nhw_launch_wave(WV_DQ1, ws, s);
 		}
-		nhw_launch_synthesis(jpeg, proc, n, ps, W, H, s);
+		nhw_launch_synthesis(jpeg, proc, n, W, H, 0, s);
 		if (form < 4) {
-			nhw_launch_phase(PH_L2, ws, 0, nullptr, nullptr, nullptr, s);
-			if (save) nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s, l2save, ws.stride[B_L2SAVE] / 2, H, 1);
-			else nhw_launch_analysis(jpeg, proc, n, ps, W, H, 1, s);
+			nhw_launch_phase(PH_L2, ws, 0, s);
+			nhw_launch_analysis(save ? l2.saving(l2save, H, ANA_SAVE_BLOCK) : l2, s);
 		}
 	}
 	HIPCHK(hipGetLastError());
@@ -640,7 +639,7 @@ extern "C" int nhw_stage_synthesis(nhw_enc *e, void *d_jpeg, void *d_proc, int n
 	if (!e || n_img < 1) return NHW_E_ARG;
 	if (size != 256 && size != 128) { nhw_enc_err = "synthesis: transform size must be 256 or 128 (the encoder has no synthesis of size 512)"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(e->device));
-	nhw_launch_synthesis((int16_t *)d_jpeg, (int16_t *)d_proc, n_img, plane_stride, stride, size, stream ? (hipStream_t)stream : e->own_stream);
+	nhw_launch_synthesis({ (int16_t *)d_jpeg, plane_stride }, { (int16_t *)d_proc, plane_stride }, n_img, stride, size, 0, stream ? (hipStream_t)stream : e->own_stream);
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
 }

@@ -263,19 +263,24 @@ __global__ void k_synth(uint8_t *__restrict__ bgr, int n, uint32_t seed_base)
 /* ------------------------------------------------------------------------------------------------ launchers */
 using namespace nhw;
 
-static float color_yq(int q, int *family);
-void nhw_launch_color(const uint8_t *bgr, int n, int q, int16_t *y, size_t y_stride, uint8_t *u, uint8_t *v, size_t c_stride, hipStream_t s)
+static float color_yq(int q, int *family)
+{
+	static const int k_qtz[17] = { 0, 15900, 16500, 17100, 18000, 18820, 19670, 20640, 21540, 23540, 25570, 27522, 27830, 27607, 28786, 31262, 32375 };
+	if (q >= 20) { *family = 0; return 0.f; }
+	if (q >= 18) { *family = 1; return q == 19 ? 0.975f : 0.93f; }
+	if (q == 17) { *family = 2; return 0.f; }
+	*family = 3;
+	return __builtin_bit_cast(float, k_qtz[q < 1 ? 1 : q]);
+}
+void nhw_launch_color(const uint8_t *bgr, int n, int q, Plane<int16_t> y, Plane<uint8_t> u, Plane<uint8_t> v, hipStream_t s)
 {
 	const dim3 grid(H / 4, n);
+	assert(u.pitch == v.pitch);
 	int fam = 0;
 	const float yq = color_yq(q, &fam);
-	if (fam == 0) k_color<0><<<grid, 256, 0, s>>>(bgr, y, y_stride, u, v, c_stride, yq);
-	else if (fam == 1) k_color<1><<<grid, 256, 0, s>>>(bgr, y, y_stride, u, v, c_stride, yq);
-	else if (fam == 2) k_color<2><<<grid, 256, 0, s>>>(bgr, y, y_stride, u, v, c_stride, yq);
-	else k_color<3><<<grid, 256, 0, s>>>(bgr, y, y_stride, u, v, c_stride, yq);         /* quality table of colorspace.c:174-189 (format constants) */
+	(fam == 0 ? k_color<0> : fam == 1 ? k_color<1> : fam == 2 ? k_color<2> : k_color<3>)<<<grid, 256, 0, s>>>(bgr, y.p, y.bytes(), u.p, v.p, u.pitch, yq);   /* quality table of colorspace.c:174-189 (format constants) */
 }
 
-/* keep != nullptr: copy of the first 256 rows x 512 of the transposed pass-1 plane (q>=22, level 0) */
 /* ------------------------------------------------------------------------------------------------
  * Whole-block filterbank kernels for the 256- and 128-sized levels: one workgroup keeps the S x S block in
  * LDS (row stride S + 2 shorts: column walks hit 64 different banks), runs both directions there and writes
@@ -573,83 +578,71 @@ int nhw_front_set_attrs(const char **where)
 	return 0;
 }
 
-/* save (optional): a second destination for the block the reference copies right after the transform -- the S x S coefficient block
- * (save_kind 1) or the LL quadrant in natural orientation (save_kind 2) -- written by the fused kernels, by a block copy otherwise */
-void nhw_launch_analysis(int16_t *jpeg, int16_t *proc, int n, size_t plane_stride, int stride, int size, int final_level,
-                         hipStream_t s, int16_t *save, size_t save_plane, int save_row, int save_kind, const uint8_t *src8, size_t src8_plane, int drop_t,
-                         const int16_t *alt, size_t alt_plane, int alt_stride)
+/* src8 means the encoder's chroma level 1 from the 4:2:0 byte plane and nothing else: k_chroma_l1q, a quarter of the block to a workgroup
+ * (NHW_CHROMA_L1Q=0, a developer switch: k_dwt_ana<256>, which widens the bytes as well and always copies the LL quadrant back) */
+void nhw_launch_analysis(const NhwAnalysis &a, hipStream_t s)
 {
-	if (!save) save_kind = 0;
-	static const int quarters = getenv("NHW_CHROMA_L1Q") ? atoi(getenv("NHW_CHROMA_L1Q")) : 1;
-	if (size == 256 && src8 && !final_level && drop_t && save_kind != 1 && !alt && stride == 256 && quarters)   /* the encoder's chroma level 1 from the byte plane */
-		nhw_slices(4, [&](int sl) {
-			k_chroma_l1q<<<sl < 0 ? 4 * ((n + 7) & ~7) : n, 256, 0, s>>>(src8, src8_plane, proc, jpeg, plane_stride, save_kind == 2 ? save : nullptr, save_plane, save_row, n, !(drop_t == 2 && save_kind == 2), sl);
-		});
-	else if (size == 256) k_dwt_ana<256><<<n < DWT_WGS ? n : DWT_WGS, 1024, 256 * 258 * sizeof(int16_t), s>>>(jpeg, proc, plane_stride, stride, final_level, save, save_plane, save_row, save_kind, n, src8, src8_plane, drop_t, alt, alt_plane, alt_stride);
-	else if (size == 128) k_dwt_ana<128><<<n, 512, 128 * 130 * sizeof(int16_t), s>>>(jpeg, proc, plane_stride, stride, final_level, save, save_plane, save_row, save_kind, n, nullptr, 0, drop_t, alt, alt_plane, alt_stride);
-	else {   /* size 512 is the front kernels' (nhw_launch_front_fused); a caller with any other size would get stale planes: stop loudly */
-		fprintf(stderr, "nhw_launch_analysis: no kernel for transform size %d (256 and 128 only; 512 is nhw_launch_front_fused)\n", size);
-		abort();
+	const bool ll = a.save_kind == ANA_SAVE_LL && !a.final_level;   /* (the final level copies no LL quadrant) */
+	if ((a.size != 256 && a.size != 128) || (a.save.p != nullptr) != (a.save_kind != ANA_SAVE_NONE) || (a.save_kind == ANA_SAVE_LL) != ll || (a.store == ANA_STORE_NO_T_LL_SAVED && !ll)
+	    || (a.src8.p && (a.size != 256 || a.stride != 256 || a.final_level || a.alt.p || a.store == ANA_STORE_ALL || a.save_kind == ANA_SAVE_BLOCK))) {   /* a caller would get stale planes: stop loudly */
+		fprintf(stderr, "nhw_launch_analysis: no kernel for size %d (256, 128; 512 is nhw_launch_front_fused), final %d, save %d, store %d, bytes %d, alt %d\n", a.size, a.final_level, (int)a.save_kind, (int)a.store, !!a.src8.p, !!a.alt.p); abort();
 	}
+	assert(a.jpeg.pitch == a.proc.pitch);
+	static const int quarters = getenv("NHW_CHROMA_L1Q") ? atoi(getenv("NHW_CHROMA_L1Q")) : 1;
+	if (a.src8.p && quarters)
+		nhw_slices(4, [&](int sl) {
+			k_chroma_l1q<<<sl < 0 ? 4 * ((a.n + 7) & ~7) : a.n, 256, 0, s>>>(a.src8.p, a.src8.pitch, a.proc.p, a.jpeg.p, a.jpeg.pitch, a.save.p, a.save.pitch, a.save_row, a.n, a.store != ANA_STORE_NO_T_LL_SAVED, sl);
+		});
+	else if (a.size == 256) k_dwt_ana<256><<<a.n < DWT_WGS ? a.n : DWT_WGS, 1024, 256 * 258 * sizeof(int16_t), s>>>(a.jpeg.p, a.proc.p, a.jpeg.pitch, a.stride, a.final_level, a.save.p, a.save.pitch, a.save_row, (int)a.save_kind, a.n, a.src8.p, a.src8.pitch, (int)a.store, a.alt.p, a.alt.pitch, a.alt_stride);
+	else k_dwt_ana<128><<<a.n, 512, 128 * 130 * sizeof(int16_t), s>>>(a.jpeg.p, a.proc.p, a.jpeg.pitch, a.stride, a.final_level, a.save.p, a.save.pitch, a.save_row, (int)a.save_kind, a.n, nullptr, 0, (int)a.store, a.alt.p, a.alt.pitch, a.alt_stride);
 }
 
-void nhw_launch_synthesis(int16_t *jpeg, int16_t *proc, int n, size_t plane_stride, int stride, int size, hipStream_t s, int drop_nat,
-                          const uint16_t *verb_list, size_t verb_list_stride, const int *verb_len, size_t verb_len_stride)
+void nhw_launch_synthesis(Plane<int16_t> jpeg, Plane<int16_t> proc, int n, int stride, int size, int drop_nat, Plane<const uint8_t> verb_list, Plane<const uint8_t> verb_len, hipStream_t s)
 {
-	if (size == 256) k_dwt_syn<256><<<n < DWT_WGS ? n : DWT_WGS, 1024, 256 * 258 * sizeof(int16_t), s>>>(jpeg, proc, plane_stride, stride, n, drop_nat, verb_list, verb_list_stride, verb_len, verb_len_stride);
-	else if (size == 128) k_dwt_syn<128><<<n, 512, 128 * 130 * sizeof(int16_t), s>>>(jpeg, proc, plane_stride, stride, n, drop_nat, nullptr, 0, nullptr, 0);
-	else {
-		fprintf(stderr, "nhw_launch_synthesis: no kernel for transform size %d (256 and 128 only)\n", size);
-		abort();
-	}
+	assert(jpeg.pitch == proc.pitch && (size == 256 || !verb_list.p));
+	if (size == 256) k_dwt_syn<256><<<n < DWT_WGS ? n : DWT_WGS, 1024, 256 * 258 * sizeof(int16_t), s>>>(jpeg.p, proc.p, jpeg.pitch, stride, n, drop_nat,
+		reinterpret_cast<const uint16_t *>(verb_list.p), verb_list.bytes(), reinterpret_cast<const int *>(verb_len.p), verb_len.bytes());
+	else if (size == 128) k_dwt_syn<128><<<n, 512, 128 * 130 * sizeof(int16_t), s>>>(jpeg.p, proc.p, jpeg.pitch, stride, n, drop_nat, nullptr, 0, nullptr, 0);
+	else { fprintf(stderr, "nhw_launch_synthesis: no kernel for transform size %d (256 and 128 only)\n", size); abort(); }
 }
 
 /* the front launch group = ONE kernel.
  * bgr != nullptr: quality 17..23, everything from the BGR bytes (colour, 4:2:0 planes pu / pv, pre-filter for q <= 21, level-1 analysis): k_front_image
  *                 with the pre-filter, k_front_plain without;
  * bgr == nullptr: the luma plane y is the input (quality 1..16 behind their own pre-filter; the analysis stage entry point): k_front_plain.
- * st (optional): the carry at the start of every image row, for the compatibility mode's replay of a few rows (k_front_stale).
+ * st (optional): the carry at the start of every image row, for the compatibility mode's replay of a few rows (k_front_stale); keep (optional, q >= 22).
  * switches bit 0: every carry segment takes its exact replay (tests); bit 1: a stage check is going to read every plane (nothing is left out). */
-static float color_yq(int q, int *family)
+void nhw_launch_front_fused(const NhwFront &f, hipStream_t s)
 {
-	static const int k_qtz[17] = { 0, 15900, 16500, 17100, 18000, 18820, 19670, 20640, 21540, 23540, 25570, 27522, 27830, 27607, 28786, 31262, 32375 };
-	if (q >= 20) { *family = 0; return 0.f; }
-	if (q >= 18) { *family = 1; return q == 19 ? 0.975f : 0.93f; }
-	if (q == 17) { *family = 2; return 0.f; }
-	*family = 3;
-	return __builtin_bit_cast(float, k_qtz[q < 1 ? 1 : q]);
-}
-void nhw_launch_front_fused(const uint8_t *bgr, int q, uint8_t *pu, uint8_t *pv, size_t c_stride, const int16_t *y, size_t y_stride, int with_prefilter,
-                            uint8_t *st, size_t s_stride, int16_t *proc, int16_t *jpeg, size_t plane_stride, int16_t *ll1, size_t ll1_stride,
-                            int16_t *keep, size_t keep_stride, int n, hipStream_t s, int switches)
-{
+	assert(f.pu.pitch == f.pv.pitch && f.proc.pitch == f.jpeg.pitch);
+	Plane<int16_t> keep = f.keep;
 	int fam = 0;
-	const float yq = bgr ? color_yq(q, &fam) : 0.f;
-	int fl = (switches & 1) | ((switches & 2) ? 0x100000 : 0);
+	const float yq = f.bgr ? color_yq(f.q, &fam) : 0.f;
+	int fl = (f.switches & 1) | ((f.switches & 2) ? 0x100000 : 0);
 #ifdef NHW_DEV
 	{ const char *e = getenv("NHW_BAND_STOP"); if (e) fl |= atoi(e) << 8; }
 	if (getenv("NHW_FRONT_PROF")) fl |= 0x10000;
 	{ const char *e = getenv("NHW_FRONT_SKIP"); if (e) fl |= atoi(e) & 12; }     /* 4: no stores of the level-1 plane, 8: none of the LL rows (timing experiments) */
-	if (getenv("NHW_FRONT_DUMP") && y && bgr && with_prefilter) { fl |= 2 | (atoi(getenv("NHW_FRONT_DUMP")) << 4); keep = const_cast<int16_t *>(y); keep_stride = y_stride / 2; }
+	if (getenv("NHW_FRONT_DUMP") && f.y.p && f.bgr && f.with_prefilter) { fl |= 2 | (atoi(getenv("NHW_FRONT_DUMP")) << 4); keep = { const_cast<int16_t *>(f.y.p), f.y.pitch }; }
 #endif
-#define FI_ARGS(srcp, sstride) srcp, sstride, yq, pu, pv, c_stride, st, s_stride, proc, jpeg, plane_stride, ll1, ll1_stride, keep, keep_stride, fl
-#define FP_ARGS(srcp, sstride) srcp, sstride, yq, pu, pv, c_stride, proc, jpeg, plane_stride, ll1, ll1_stride, keep, keep_stride, fl
-	if (!bgr) k_front_plain<0, 0><<<n, FI_NT, FP_LDS_BYTES, s>>>(FP_ARGS((const void *)y, y_stride));
-	else if (!with_prefilter) k_front_plain<1, 0><<<n, FI_NT, FP_LDS_BYTES, s>>>(FP_ARGS((const void *)bgr, (size_t)0));
-	else if (fam == 0) k_front_image<1, 1, 0><<<n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)bgr, (size_t)0));
-	else if (fam == 1) k_front_image<1, 1, 1><<<n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)bgr, (size_t)0));
-	else k_front_image<1, 1, 2><<<n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)bgr, (size_t)0));
+#define FI_ARGS(srcp, sstride) srcp, sstride, yq, f.pu.p, f.pv.p, f.pu.pitch, f.st.p, f.st.bytes(), f.proc.p, f.jpeg.p, f.jpeg.pitch, f.ll1.p, f.ll1.pitch, keep.p, keep.pitch, fl
+#define FP_ARGS(srcp, sstride) srcp, sstride, yq, f.pu.p, f.pv.p, f.pu.pitch, f.proc.p, f.jpeg.p, f.jpeg.pitch, f.ll1.p, f.ll1.pitch, keep.p, keep.pitch, fl
+	if (!f.bgr) k_front_plain<0, 0><<<f.n, FI_NT, FP_LDS_BYTES, s>>>(FP_ARGS((const void *)f.y.p, f.y.bytes()));
+	else if (!f.with_prefilter) k_front_plain<1, 0><<<f.n, FI_NT, FP_LDS_BYTES, s>>>(FP_ARGS((const void *)f.bgr, (size_t)0));
+	else if (fam == 0) k_front_image<1, 1, 0><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));
+	else if (fam == 1) k_front_image<1, 1, 1><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));
+	else k_front_image<1, 1, 2><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));
 #undef FP_ARGS
 #undef FI_ARGS
 #ifdef NHW_DEV
-	if (getenv("NHW_FRONT_PROF") && bgr && with_prefilter) {
+	if (getenv("NHW_FRONT_PROF") && f.bgr && f.with_prefilter) {
 		unsigned long long h[16];
 		hipStreamSynchronize(s);
 		hipMemcpyFromSymbol(h, HIP_SYMBOL(nhw::g_fi_prof), sizeof h);
 		static const char *nm[16] = { "loop top (hold rows, last barrier)", "barrier after phase 0 (+ prefetch issue)", "chroma vertical + barrier", "contrast + barrier", "entry states + barrier(s)", "replay + barrier", "pair rules + barrier", "horizontal + barrier", "vertical + barrier", "phase 0 work (wait for rows, colour, LDS stores)", "vertical: keep stores", "vertical: row copies + column loads", "vertical: arithmetic", "vertical: stores issued" };
 		unsigned long long tot = 0; for (int i = 0; i < 14; i++) tot += h[i];
-		fprintf(stderr, "k_front_image q%d: thread-0 clock ticks per image (sum over bands), %d images\n", q, n);
-		for (int i = 0; i < 14; i++) fprintf(stderr, "  %-52s %10.0f  %5.1f %%\n", nm[i], (double)h[i] / n, 100.0 * h[i] / (tot ? tot : 1));
+		fprintf(stderr, "k_front_image q%d: thread-0 clock ticks per image (sum over bands), %d images\n", f.q, f.n);
+		for (int i = 0; i < 14; i++) fprintf(stderr, "  %-52s %10.0f  %5.1f %%\n", nm[i], (double)h[i] / f.n, 100.0 * h[i] / (tot ? tot : 1));
 		memset(h, 0, sizeof h); hipMemcpyToSymbol(HIP_SYMBOL(nhw::g_fi_prof), h, sizeof h);
 	}
 #endif
@@ -686,9 +679,9 @@ __global__ void k_front_stale(const int16_t *__restrict__ yb, size_t y_stride, c
 		dst[c] = (int16_t)k;
 	}
 }
-void nhw_launch_front_stale(const int16_t *y, size_t y_stride, const uint8_t *st, size_t s_stride, int16_t *stale, size_t stale_stride, int n, hipStream_t s)
+void nhw_launch_front_stale(Plane<const int16_t> y, Plane<const uint8_t> st, Plane<uint8_t> stale, int n, hipStream_t s)
 {
-	k_front_stale<<<n, 64, 0, s>>>(y, y_stride, st, s_stride, stale, stale_stride);
+	k_front_stale<<<n, 64, 0, s>>>(y.p, y.bytes(), st.p, st.bytes(), reinterpret_cast<int16_t *>(stale.p), stale.bytes());
 }
 
 

@@ -2,7 +2,11 @@
  * nhw_host.h -- everything of libnhwhip.so's host side that crosses a file, declared once: the launchers of the kernel files, the
  * forced slice order, and the helpers both handles (nhw_enc, nhw_dec) use for errors and device buffers (nhw_host.hip).  Private: the
  * public interface is include/nhw_hip.h.  Every file that defines one of these symbols includes this header, so a signature that
- * drifts does not compile; default arguments live here only.
+ * drifts does not compile.  No launcher has a default argument: a call says everything it passes.
+ *
+ * A per-image buffer crosses this header as a Plane<T>: image i starts at p + i * pitch, the pitch in ELEMENTS OF T.  A plane a kernel
+ * addresses in bytes is a Plane<uint8_t>, whatever the kernel's pointer type.  The launcher converts to what its kernel takes (pitch, or
+ * bytes()) at the <<< >>> and asserts that planes the kernel takes with one stride have one pitch; an absent optional plane is Plane{}.
  */
 #ifndef NHW_HOST_H
 #define NHW_HOST_H
@@ -14,7 +18,14 @@
 
 #include "../../include/nhw_hip.h"
 
-struct NhwWs;                               /* nhw_ws.h: the encoder's workspace view */
+struct NhwWs;                               /* nhw_ws.h: the encoder's workspace view; ws.plane<T>(B_x) makes the Plane of one of its buffers */
+
+template <class T> struct Plane {
+	T *p = nullptr; size_t pitch = 0;
+	Plane at(size_t i) const { return { p + i * pitch, pitch }; }   /* the view that starts at image i */
+	size_t bytes() const { return pitch * sizeof(T); }
+	operator Plane<const T>() const { return { p, pitch }; }
+};
 
 /* ------------------------------------------------------------------------------------------------ the forced slice order of the tests
  * (nhw_debug_slice_order, nhw_dec_debug_slice_order in include/nhw_hip_debug.h)
@@ -47,38 +58,52 @@ template <typename F> inline void nhw_slices(int nslices, F &&launch)
 
 /* ------------------------------------------------------------------------------------------------ launchers */
 /* nhw_front.hip */
-void nhw_launch_color(const uint8_t *bgr, int n, int q, int16_t *y, size_t y_stride, uint8_t *u, uint8_t *v, size_t c_stride, hipStream_t s);
-void nhw_launch_analysis(int16_t *jpeg, int16_t *proc, int n, size_t plane_stride, int stride, int size, int final_level, hipStream_t s,
-                         int16_t *save = nullptr, size_t save_plane = 0, int save_row = 0, int save_kind = 0, const uint8_t *src8 = nullptr, size_t src8_plane = 0, int drop_t = 0,
-                         const int16_t *alt = nullptr, size_t alt_plane = 0, int alt_stride = 0);
-void nhw_launch_synthesis(int16_t *jpeg, int16_t *proc, int n, size_t plane_stride, int stride, int size, hipStream_t s, int drop_nat = 0,
-                          const uint16_t *verb_list = nullptr, size_t verb_list_stride = 0, const int *verb_len = nullptr, size_t verb_len_stride = 0);
+void nhw_launch_color(const uint8_t *bgr, int n, int q, Plane<int16_t> y, Plane<uint8_t> u, Plane<uint8_t> v, hipStream_t s);
+/* One whole-block analysis level (size 256 or 128) of n images: NhwAnalysis{ jpeg, proc, n, row stride, size, final_level }, the optionals by name.
+ * save: a second destination for what the reference copies right behind the transform; src8: the block comes as bytes (a 4:2:0 plane);
+ * alt: it is read from another int16 plane.  NO_T: the transposed first-direction plane is not stored; NO_T_LL_SAVED: nor need the LL
+ * quadrant reach more than `save` (the byte-plane kernel then leaves it out of the work plane) */
+enum NhwAnaSave { ANA_SAVE_NONE, ANA_SAVE_BLOCK /* the coefficient block */, ANA_SAVE_LL /* the LL quadrant in natural orientation */ };
+enum NhwAnaStore { ANA_STORE_ALL, ANA_STORE_NO_T, ANA_STORE_NO_T_LL_SAVED };
+struct NhwAnalysis {
+	Plane<int16_t> jpeg, proc; int n, stride, size, final_level;
+	Plane<int16_t> save = {}; int save_row = 0; NhwAnaSave save_kind = ANA_SAVE_NONE; NhwAnaStore store = ANA_STORE_ALL;
+	Plane<const uint8_t> src8 = {}; Plane<const int16_t> alt = {}; int alt_stride = 0;
+	NhwAnalysis from(Plane<const int16_t> p, int row) const { NhwAnalysis a = *this; a.alt = p; a.alt_stride = row; return a; }
+	NhwAnalysis saving(Plane<int16_t> p, int row, NhwAnaSave kind) const { NhwAnalysis a = *this; a.save = p; a.save_row = row; a.save_kind = kind; return a; }
+};
+void nhw_launch_analysis(const NhwAnalysis &a, hipStream_t s);
+/* verb_list, verb_len (size 256): + puts back the samples the LL2 coder sent verbatim -- a list of uint16_t an image and the int that holds its length */
+void nhw_launch_synthesis(Plane<int16_t> jpeg, Plane<int16_t> proc, int n, int stride, int size, int drop_nat, Plane<const uint8_t> verb_list, Plane<const uint8_t> verb_len, hipStream_t s);
+inline void nhw_launch_synthesis(Plane<int16_t> jpeg, Plane<int16_t> proc, int n, int stride, int size, int drop_nat, hipStream_t s) { nhw_launch_synthesis(jpeg, proc, n, stride, size, drop_nat, {}, {}, s); }
 void nhw_launch_synth(uint8_t *bgr, int n, uint32_t seed_base, hipStream_t s);
-void nhw_launch_front_fused(const uint8_t *bgr, int q, uint8_t *pu, uint8_t *pv, size_t c_stride, const int16_t *y, size_t y_stride, int with_prefilter,
-                            uint8_t *st, size_t s_stride, int16_t *proc, int16_t *jpeg, size_t plane_stride, int16_t *ll1, size_t ll1_stride,
-                            int16_t *keep, size_t keep_stride, int n, hipStream_t s, int switches);
-void nhw_launch_front_stale(const int16_t *y, size_t y_stride, const uint8_t *st, size_t s_stride, int16_t *stale, size_t stale_stride, int n, hipStream_t s);
+struct NhwFront {                           /* the front launch group of n images: the forms and the members are described at nhw_launch_front_fused */
+	const uint8_t *bgr = nullptr; Plane<uint8_t> pu = {}, pv = {}, st = {}; Plane<const int16_t> y = {};
+	Plane<int16_t> proc = {}, jpeg = {}, ll1 = {}, keep = {}; int q = 0, with_prefilter = 0, n = 0, switches = 0;
+};
+void nhw_launch_front_fused(const NhwFront &f, hipStream_t s);
+void nhw_launch_front_stale(Plane<const int16_t> y, Plane<const uint8_t> st, Plane<uint8_t> stale, int n, hipStream_t s);
 int nhw_front_set_attrs(const char **where);   /* nhw_front.hip, nhw_tail.hip: dynamic-LDS opt-ins of the device the handle lives on */
 /* nhw_tail.hip */
-enum { PH_L1, PH_L2, PH_L3, PH_L4A, PH_C0, PH_C2, PH_C3, PH_C4, PH_C5, PH_FINAL, PH_L4B, PH_L4C, PH_L4D, PH_LLC, PH_L4C2 };
+enum { PH_L1, PH_L2, PH_L3, PH_L4A, PH_C0, PH_C2, PH_C3, PH_C4, PH_C5, PH_L4B = 10, PH_L4C, PH_L4D, PH_LLC, PH_L4C2 };   /* the numbers name k_phase's instances in recorded profiles (9 was the final phase: k_final) */
 enum { WV_DQ1, WV_DQ0, WV_EMIT, WV_QUANT };
-void nhw_launch_phase(int ph, const NhwWs &ws, int comp, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s);
+void nhw_launch_phase(int ph, const NhwWs &ws, int comp, hipStream_t s);
+void nhw_launch_final(const NhwWs &ws, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s);   /* Z2 + the container */
 void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s);
-void nhw_launch_l2_recon(int16_t *jpeg, int16_t *proc, size_t plane_stride, int16_t *ll1, size_t ll1_stride, int n, hipStream_t s, int16_t *l2save = nullptr, size_t save_stride = 0);
-void nhw_launch_chroma_loops(int16_t *cproc, size_t plane_stride, int16_t *cll1, size_t ll1_stride, int16_t *cl2save, size_t save_stride,
-                             const uint8_t *pu, size_t pu_stride, int q, int comp, int compat, int n, hipStream_t s);   /* both chroma closed loops of one component, from cll1 */
-void nhw_launch_copy_block(const int16_t *src, size_t src_plane, int src_row, int16_t *dst, size_t dst_plane, int dst_row, int rows, int cols, int n, hipStream_t s);
+void nhw_launch_l2_recon(Plane<int16_t> jpeg, Plane<int16_t> proc, Plane<int16_t> ll1, Plane<int16_t> l2save /* or empty */, int n, hipStream_t s);
+void nhw_launch_chroma_loops(Plane<int16_t> cproc, Plane<int16_t> cll1, Plane<int16_t> cl2save, Plane<const uint8_t> pu, int q, int comp, int compat, int n, hipStream_t s);   /* both chroma closed loops of one component, from cll1 */
+void nhw_launch_copy_block(Plane<const int16_t> src, int src_row, Plane<int16_t> dst, int dst_row, int rows, int cols, int n, hipStream_t s);
 int nhw_tail_set_attrs(const char **where);
 /* nhw_low.hip: quality 1..16 only.  The pre-filter's sub-batches (parts > 1) record into ev[LOW_EV_COUNT]: */
 enum { LOW_EV_START = 0, LOW_EV_COUNT = 13 };                       /* the fork; then a pair of events a sub-batch: */
 inline int low_ev_pass_a(int p) { return 1 + p; }                   /* sub-batch p is through its pass A */
 inline int low_ev_done(int parts, int p) { return 1 + parts + p; }  /* ... and through the whole pre-filter */
-int nhw_launch_low_prefilter(const int16_t *src, size_t src_stride, int16_t *y, size_t y_stride, int16_t *km, size_t km_stride, uint8_t *so, size_t so_stride, uint8_t *chain, size_t chain_stride,
-                             uint16_t *tab, size_t tab_stride, int q, int n, hipStream_t s, int force = 0, int parts = 1, hipStream_t *aux = nullptr, hipEvent_t *ev = nullptr);
-void nhw_launch_low_prefilter_chroma(const uint8_t *src, size_t src_stride, int16_t *dst, size_t dst_stride, int q, int n, hipStream_t s);
-void nhw_launch_low_chroma_thin(int16_t *plane, size_t plane_stride, int n, hipStream_t s);
-void nhw_launch_low_ll2(int16_t *proc, size_t plane_stride, int q, int n, hipStream_t s);
-void nhw_launch_low_stale(const int16_t *km, size_t km_stride, int16_t *stale, size_t stale_stride, int n, hipStream_t s);
+int nhw_launch_low_prefilter(Plane<const int16_t> src, Plane<int16_t> y, Plane<int16_t> km, Plane<uint8_t> so, Plane<uint8_t> chain, Plane<uint8_t> tab,
+                             int q, int n, hipStream_t s, int force, int parts, hipStream_t *aux, hipEvent_t *ev);
+void nhw_launch_low_prefilter_chroma(Plane<const uint8_t> src, Plane<int16_t> dst, int q, int n, hipStream_t s);
+void nhw_launch_low_chroma_thin(Plane<int16_t> plane, int n, hipStream_t s);
+void nhw_launch_low_ll2(Plane<int16_t> proc, int q, int n, hipStream_t s);
+void nhw_launch_low_stale(Plane<const int16_t> km, Plane<uint8_t> stale, int n, hipStream_t s);
 /* nhw_fit.hip, nhw_metric.hip: the quality searches */
 void nhw_launch_fit_gather(const uint8_t *d_bgr, const int *idx, int m, uint8_t *staging, hipStream_t s);
 void nhw_launch_fit_select(const int *idx, int m, const uint8_t *st_out, const uint32_t *st_sizes, const int32_t *st_status, const void *limit,

@@ -1528,59 +1528,54 @@ __global__ __launch_bounds__(256) void k_low_chroma_thin(int16_t *__restrict__ p
 	}
 	*reinterpret_cast<uint4 *>(p + r * H + c0) = make_uint4(ww[0], ww[1], ww[2], ww[3]);
 }
-void nhw_launch_low_chroma_thin(int16_t *plane, size_t plane_stride, int n, hipStream_t s)
+void nhw_launch_low_chroma_thin(Plane<int16_t> plane, int n, hipStream_t s)
 {
-	k_low_chroma_thin<<<dim3(Q / 8 / 256, n), 256, 0, s>>>(plane, plane_stride);
+	k_low_chroma_thin<<<dim3(Q / 8 / 256, n), 256, 0, s>>>(plane.p, plane.pitch);
 }
 
-void nhw_launch_low_ll2(int16_t *proc, size_t plane_stride, int q, int n, hipStream_t s)
+void nhw_launch_low_ll2(Plane<int16_t> proc, int q, int n, hipStream_t s)
 {
 	const int maps = (q <= 7) ? 4 : 3;                               /* k_ll2_thr[q][4] == 36 up to quality 7 */
-	k_low_ll2<<<n, LL2_NT, (size_t)(128 * 132 + 8) * 2 + (size_t)maps * (128 * 128 / 32) * 4, s>>>(proc, plane_stride, q);   /* 128 rows at the kernel's pitch LP + the hit maps */
+	k_low_ll2<<<n, LL2_NT, (size_t)(128 * 132 + 8) * 2 + (size_t)maps * (128 * 128 / 32) * 4, s>>>(proc.p, proc.pitch, q);   /* 128 rows at the kernel's pitch LP + the hit maps */
 }
 /* The pre-filter of a batch.  parts > 1: the batch is cut into sub-batches whose sequences run on streams of their own (aux), the next one's
  * pass A starting when the one before has finished its own -- the chain (k_low_chain) is two wavefronts a picture that live on the scalar
  * unit and on look-ups, and leaves the vector units and the memory system to the streaming kernels of the sub-batches before and behind it
  * (pass A, the answers' application, passes C and D).  ev: the LOW_EV_COUNT events of nhw_host.h.  Returns a hipError_t. */
-int nhw_launch_low_prefilter(const int16_t *src, size_t src_stride, int16_t *y, size_t y_stride, int16_t *km, size_t km_stride, uint8_t *so, size_t so_stride,
-                             uint8_t *chain /* CH_BYTES an image: the machine's answers */, size_t chain_stride,
-                             uint16_t *tab /* MASK_ROW * W bytes an image: pass A's candidate masks */, size_t tab_stride, int q, int n, hipStream_t s, int force /* 32: the bands of pass A go back three rows for their entry state (tests) */,
+int nhw_launch_low_prefilter(Plane<const int16_t> src, Plane<int16_t> y, Plane<int16_t> km, Plane<uint8_t> so, Plane<uint8_t> chain /* CH_BYTES an image: the machine's answers */,
+                             Plane<uint8_t> tab /* MASK_ROW * W bytes an image: pass A's candidate masks */, int q, int n, hipStream_t s, int force /* 32: the bands of pass A go back three rows for their entry state (tests) */,
                              int parts, hipStream_t *aux, hipEvent_t *ev)
 {
 	static int dbg = 0;
 #ifdef NHW_DEV   /* developer builds: bits that switch passes of the pre-filter off for timing */
 	{ const char *e = getenv("NHW_LOW_DBG"); dbg = e ? atoi(e) : 0; }
 #endif
-	auto head = [&](int i0, int m, hipStream_t st) {                    /* pass A of images i0 .. i0 + m - 1 */
-		nhw_slices(PRE_NB, [&](int sl) {
-			k_low_pre<<<dim3(sl < 0 ? PRE_NB : 1, m), 64, 0, st>>>(src + (size_t)i0 * src_stride, src_stride, km + (size_t)i0 * km_stride, km_stride, reinterpret_cast<uint8_t *>(tab) + (size_t)i0 * tab_stride, tab_stride, q, dbg | force, sl);
-		});
-		k_low_mapfix<<<m, 64, 0, st>>>(km + (size_t)i0 * km_stride, km_stride, reinterpret_cast<const uint8_t *>(tab) + (size_t)i0 * tab_stride, tab_stride, so + (size_t)i0 * so_stride, so_stride, q, dbg);
-	};
-	auto machine = [&](int i0, int m, hipStream_t st) {                 /* pass B's machine */
-		k_low_chain<<<m, 128, 0, st>>>(km + (size_t)i0 * km_stride, km_stride, chain + (size_t)i0 * chain_stride, chain_stride, q, dbg);
-	};
-	auto rest = [&](int i0, int m, hipStream_t st) {                    /* pass B's picture side, passes C and D */
-		nhw_slices(PRE_NB, [&](int sl) {
-			k_low_apply<<<dim3(sl < 0 ? PRE_NB : 1, m), 64, 0, st>>>(src + (size_t)i0 * src_stride, src_stride, y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride,
-			                                                          chain + (size_t)i0 * chain_stride, chain_stride, q, dbg, sl);
-		});
-		k_low_markrows<<<m, 64, 0, st>>>(y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride, q);
-		nhw_slices(MK_NW, [&](int sl) {
-			k_low_marks<<<dim3(sl < 0 ? MK_NW : 1, m), MK_R, 0, st>>>(y + (size_t)i0 * y_stride, y_stride, km + (size_t)i0 * km_stride, km_stride, so + (size_t)i0 * so_stride, so_stride, q, dbg, sl);
-		});
-	};
-	if (parts <= 1 || !aux || !ev) { head(0, n, s); machine(0, n, s); rest(0, n, s); return (int)hipGetLastError(); }
 #define LOWCHK(x) do { const hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
+	auto run = [&](int i0, int m, hipStream_t st, hipEvent_t pass_a /* or null */) -> hipError_t {   /* images i0 .. i0 + m - 1 */
+		const Plane<const int16_t> sr = src.at(i0); const Plane<int16_t> yy = y.at(i0), k = km.at(i0);
+		const Plane<uint8_t> o = so.at(i0), ch = chain.at(i0), tb = tab.at(i0);
+		nhw_slices(PRE_NB, [&](int sl) {                                /* pass A */
+			k_low_pre<<<dim3(sl < 0 ? PRE_NB : 1, m), 64, 0, st>>>(sr.p, sr.pitch, k.p, k.pitch, tb.p, tb.pitch, q, dbg | force, sl);
+		});
+		k_low_mapfix<<<m, 64, 0, st>>>(k.p, k.pitch, tb.p, tb.pitch, o.p, o.pitch, q, dbg);
+		if (pass_a) { const hipError_t e_ = hipEventRecord(pass_a, st); if (e_ != hipSuccess) return e_; }
+		k_low_chain<<<m, 128, 0, st>>>(k.p, k.pitch, ch.p, ch.pitch, q, dbg);   /* pass B's machine */
+		nhw_slices(PRE_NB, [&](int sl) {                                /* pass B's picture side, passes C and D */
+			k_low_apply<<<dim3(sl < 0 ? PRE_NB : 1, m), 64, 0, st>>>(sr.p, sr.pitch, yy.p, yy.pitch, k.p, k.pitch, o.p, o.pitch, ch.p, ch.pitch, q, dbg, sl);
+		});
+		k_low_markrows<<<m, 64, 0, st>>>(yy.p, yy.pitch, k.p, k.pitch, o.p, o.pitch, q);
+		nhw_slices(MK_NW, [&](int sl) {
+			k_low_marks<<<dim3(sl < 0 ? MK_NW : 1, m), MK_R, 0, st>>>(yy.p, yy.pitch, k.p, k.pitch, o.p, o.pitch, q, dbg, sl);
+		});
+		return hipSuccess;
+	};
+	if (parts <= 1 || !aux || !ev) { LOWCHK(run(0, n, s, nullptr)); return (int)hipGetLastError(); }
 	LOWCHK(hipEventRecord(ev[LOW_EV_START], s));
 	for (int p = 0; p < parts; p++) {
 		const int i0 = (int)((long long)n * p / parts), i1 = (int)((long long)n * (p + 1) / parts);
 		LOWCHK(hipStreamWaitEvent(aux[p], ev[LOW_EV_START], 0));
 		if (p) LOWCHK(hipStreamWaitEvent(aux[p], ev[low_ev_pass_a(p - 1)], 0));              /* the sub-batch before is through its pass A */
-		head(i0, i1 - i0, aux[p]);
-		LOWCHK(hipEventRecord(ev[low_ev_pass_a(p)], aux[p]));
-		machine(i0, i1 - i0, aux[p]);
-		rest(i0, i1 - i0, aux[p]);
+		LOWCHK(run(i0, i1 - i0, aux[p], ev[low_ev_pass_a(p)]));
 		LOWCHK(hipEventRecord(ev[low_ev_done(parts, p)], aux[p]));
 	}
 	for (int p = 0; p < parts; p++) LOWCHK(hipStreamWaitEvent(s, ev[low_ev_done(parts, p)], 0));
@@ -1599,11 +1594,11 @@ __global__ void k_low_stale(const int16_t *__restrict__ kmb, size_t km_stride, i
 	for (int i = t; i < 9 * W / 4; i += 256) reinterpret_cast<uint2 *>(out + 4)[i] = reinterpret_cast<const uint2 *>(km + (size_t)272 * W)[i];
 	if (t < 4) { out[t] = km[(size_t)128 * W + t]; out[4 + 9 * W + t] = km[(size_t)256 * W + 8 + t]; }
 }
-void nhw_launch_low_stale(const int16_t *km, size_t km_stride, int16_t *stale, size_t stale_stride, int n, hipStream_t s)
+void nhw_launch_low_stale(Plane<const int16_t> km, Plane<uint8_t> stale, int n, hipStream_t s)
 {
-	k_low_stale<<<n, 256, 0, s>>>(km, km_stride, stale, stale_stride);
+	k_low_stale<<<n, 256, 0, s>>>(km.p, km.pitch, reinterpret_cast<int16_t *>(stale.p), stale.bytes());
 }
-void nhw_launch_low_prefilter_chroma(const uint8_t *src, size_t src_stride, int16_t *dst, size_t dst_stride, int q, int n, hipStream_t s)
+void nhw_launch_low_prefilter_chroma(Plane<const uint8_t> src, Plane<int16_t> dst, int q, int n, hipStream_t s)
 {
-	k_low_prefilter_chroma<<<dim3(Q / 4 / 256, n), 256, 0, s>>>(src, src_stride, dst, dst_stride, q);
+	k_low_prefilter_chroma<<<dim3(Q / 4 / 256, n), 256, 0, s>>>(src.p, src.pitch, dst.p, dst.pitch, q);
 }

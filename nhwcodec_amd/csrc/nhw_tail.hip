@@ -13,7 +13,7 @@ using namespace nhw;
 #endif
 
 template <int PH>
-__global__ __launch_bounds__(256) void k_phase(NhwWs ws, int comp, uint8_t *out, uint32_t *sizes, int32_t *status)
+__global__ __launch_bounds__(256) void k_phase(NhwWs ws, int comp)
 {
 	__shared__ int sh_counts[2];
 	__shared__ int sh_pos[2 * NT + 2];
@@ -102,12 +102,7 @@ __global__ __launch_bounds__(256) void k_wave(NhwWs ws)
 void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s)
 {
 	const dim3 g((ws.n + 3) / 4), b(256);
-	switch (ph) {
-	case WV_DQ1: k_wave<WV_DQ1><<<g, b, 0, s>>>(ws); break;
-	case WV_DQ0: k_wave<WV_DQ0><<<g, b, 0, s>>>(ws); break;
-	case WV_EMIT: k_wave<WV_EMIT><<<g, b, 0, s>>>(ws); break;
-	case WV_QUANT: k_wave<WV_QUANT><<<g, b, 0, s>>>(ws); break;
-	}
+	(ph == WV_DQ1 ? k_wave<WV_DQ1> : ph == WV_DQ0 ? k_wave<WV_DQ0> : ph == WV_EMIT ? k_wave<WV_EMIT> : k_wave<WV_QUANT>)<<<g, b, 0, s>>>(ws);
 }
 
 /* The middle of the first closed loop on one LDS residency of the 256 x 256 block: level-2 synthesis (wavelet_filterbank.c:305-496), Y8 (the
@@ -296,11 +291,10 @@ __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, 
 		lds_barrier();                                             /* the block is done with before the next one moves in */
 	}
 }
-void nhw_launch_l2_recon(int16_t *jpeg, int16_t *proc, size_t plane_stride, int16_t *ll1, size_t ll1_stride, int n, hipStream_t s,
-                         int16_t *l2save /* non-null: + the level-2 analysis of the pre-compensated block and its copy (rows of H cells) */, size_t save_stride)
+void nhw_launch_l2_recon(Plane<int16_t> jpeg, Plane<int16_t> proc, Plane<int16_t> ll1, Plane<int16_t> l2save /* not empty: + the level-2 analysis of the pre-compensated block and its copy (rows of H cells) */, int n, hipStream_t s)
 {
-	if (l2save) k_l2_recon<true><<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg, proc, plane_stride, ll1, ll1_stride, n, l2save, save_stride);
-	else k_l2_recon<false><<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg, proc, plane_stride, ll1, ll1_stride, n, nullptr, 0);
+	assert(jpeg.pitch == proc.pitch);
+	(l2save.p ? k_l2_recon<true> : k_l2_recon<false>)<<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg.p, proc.p, jpeg.pitch, ll1.p, ll1.pitch, n, l2save.p, l2save.pitch);
 }
 
 /* Both closed loops of a chroma component on one LDS residency of its 128 x 128 level-2 block (nhw_encoder.c:2310-2370 for U, :2623-2680 for V):
@@ -435,10 +429,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 		reinterpret_cast<uint32_t *>(p + (size_t)(r0 + i) * H)[lane] = (uint32_t)(uint16_t)e | ((uint32_t)(uint16_t)od << 16);
 	}
 }
-void nhw_launch_chroma_loops(int16_t *cproc, size_t plane_stride, int16_t *cll1, size_t ll1_stride, int16_t *cl2save, size_t save_stride,
-                             const uint8_t *pu, size_t pu_stride, int q, int comp, int compat, int n, hipStream_t s)
+void nhw_launch_chroma_loops(Plane<int16_t> cproc, Plane<int16_t> cll1, Plane<int16_t> cl2save, Plane<const uint8_t> pu, int q, int comp, int compat, int n, hipStream_t s)
 {
-	k_chroma_loops<<<n, 512, 0, s>>>(cproc, plane_stride, cll1, ll1_stride, cl2save, save_stride, pu, pu_stride, q, comp, compat);
+	k_chroma_loops<<<n, 512, 0, s>>>(cproc.p, cproc.pitch, cll1.p, cll1.pitch, cl2save.p, cl2save.pitch, pu.p, pu.pitch, q, comp, compat);
 }
 
 /* rows x cols block of shorts between two strided planes, every image of the batch: a workgroup an image, 16 bytes a thread and turn, four
@@ -467,7 +460,6 @@ static size_t phase_lds(int ph)
 	case PH_L2: return 3 * 32 * 33 + 32;                          /* the three 32 x 32 blocks of steps of Y8 (Y9 works on the plane itself) */
 	case PH_L3: return LL_LDS_BYTES;
 	case PH_LLC: return LLC_LDS_BYTES;
-	case PH_FINAL: return PK_LDS_BYTES;
 	case PH_L4A: return RF_LDS_BYTES > (NT + 2) * TLS * sizeof(int16_t) ? RF_LDS_BYTES : (size_t)(NT + 2) * TLS * sizeof(int16_t);
 	case PH_L4B: return (size_t)(NT + 2) * TLS * sizeof(int16_t);
 	case PH_L4C: return 0;                                         /* Y26 is pointwise, Y27 a wavefront per row straight on the plane */
@@ -491,32 +483,27 @@ int nhw_tail_set_attrs(const char **where)
 	return 0;
 }
 
-void nhw_launch_phase(int ph, const NhwWs &ws, int comp, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s)
+void nhw_launch_phase(int ph, const NhwWs &ws, int comp, hipStream_t s)
 {
 	const dim3 g(ws.n), b(256);
 	const size_t lds = phase_lds(ph);
+#define PHASE(P) case P: k_phase<P><<<g, b, lds, s>>>(ws, comp); break
 	switch (ph) {
-	case PH_L1: k_phase<PH_L1><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L2: k_phase<PH_L2><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L3: k_phase<PH_L3><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L4A: if (ws.q >= 17) k_l4a<<<g, b, lds, s>>>(ws); else k_phase<PH_L4A><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L4B: k_phase<PH_L4B><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L4C: k_phase<PH_L4C><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L4D: if (NHW_DENSE_STREAM || ws.dbg) k_phase<PH_L4D><<<g, b, lds, s>>>(ws, comp, out, sizes, status); else k_y31<<<g, 512, lds, s>>>(ws); break;
-	case PH_LLC: k_phase<PH_LLC><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_L4C2: k_phase<PH_L4C2><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_C0: k_phase<PH_C0><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_C2: k_phase<PH_C2><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_C3: k_phase<PH_C3><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_C4: k_phase<PH_C4><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_C5: k_phase<PH_C5><<<g, b, lds, s>>>(ws, comp, out, sizes, status); break;
-	case PH_FINAL: k_final<<<g, b, lds, s>>>(ws, out, sizes, status); break;
+	PHASE(PH_L1); PHASE(PH_L2); PHASE(PH_L3);
+	case PH_L4A: if (ws.q >= 17) k_l4a<<<g, b, lds, s>>>(ws); else k_phase<PH_L4A><<<g, b, lds, s>>>(ws, comp); break;
+	PHASE(PH_L4B); PHASE(PH_L4C);
+	case PH_L4D: if (NHW_DENSE_STREAM || ws.dbg) k_phase<PH_L4D><<<g, b, lds, s>>>(ws, comp); else k_y31<<<g, 512, lds, s>>>(ws); break;
+	PHASE(PH_LLC); PHASE(PH_L4C2); PHASE(PH_C0); PHASE(PH_C2); PHASE(PH_C3); PHASE(PH_C4); PHASE(PH_C5);
 	}
+#undef PHASE
+}
+void nhw_launch_final(const NhwWs &ws, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s)
+{
+	k_final<<<ws.n, 256, PK_LDS_BYTES, s>>>(ws, out, sizes, status);
 }
 
-void nhw_launch_copy_block(const int16_t *src, size_t src_plane, int src_row, int16_t *dst, size_t dst_plane, int dst_row,
-                           int rows, int cols, int n, hipStream_t s)
+void nhw_launch_copy_block(Plane<const int16_t> src, int src_row, Plane<int16_t> dst, int dst_row, int rows, int cols, int n, hipStream_t s)
 {
-	if ((cols | src_row | dst_row) & 7 || (src_plane | dst_plane) & 7 || ((uintptr_t)src | (uintptr_t)dst) & 15) { fprintf(stderr, "nhw_launch_copy_block: block not 16-byte aligned\n"); abort(); }
-	k_copy_block<<<n, 256, 0, s>>>(src, src_plane, src_row, dst, dst_plane, dst_row, rows, cols);
+	if ((cols | src_row | dst_row) & 7 || (src.pitch | dst.pitch) & 7 || ((uintptr_t)src.p | (uintptr_t)dst.p) & 15) { fprintf(stderr, "nhw_launch_copy_block: block not 16-byte aligned\n"); abort(); }
+	k_copy_block<<<n, 256, 0, s>>>(src.p, src.pitch, src_row, dst.p, dst.pitch, dst_row, rows, cols);
 }

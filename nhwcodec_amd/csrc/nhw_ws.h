@@ -3,6 +3,7 @@
 #define NHW_WS_H
 
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <stdint.h>
 
 #define W  512      /* luma row stride  (reference 2*IM_DIM) */
@@ -42,6 +43,7 @@ struct NhwMeta {
 	int pad;
 };
 
+template <class T> struct Plane;   /* nhw_host.h: how the host's launch layer passes one buffer of every image */
 struct NhwWs {
 	uint8_t *base;
 	size_t off[B_COUNT];
@@ -53,6 +55,7 @@ struct NhwWs {
 	int defer_verbatim;   /* the LL2 coder (Y16) runs beside the second dequantiser simulation: the samples it sent verbatim are put back by the synthesis behind both (k_dwt_syn) */
 	int compat;   /* 0: canonical (out-of-bounds reads see zeros); 1: the heap neighbours of the stock one-image-per-process binary (nhw_hip.h) */
 	template <typename T> __host__ __device__ T *buf(int b, int img) const { return (T *)(base + off[b] + (size_t)img * stride[b]); }
+	template <typename T> Plane<T> plane(int b) const { assert(stride[b] % sizeof(T) == 0); return { (T *)(base + off[b]), stride[b] / sizeof(T) }; }   /* host: buffer b of this view's images */
 };
 
 

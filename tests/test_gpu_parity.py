@@ -96,8 +96,8 @@ def test_colour_exhaustive_all_2_24_triples(enc, oracle, q):
 @pytest.mark.gpu
 @pytest.mark.parametrize("q", [1, 6, 7, 8, 9, 10, 14, 16])
 def test_prefilter_matches_oracle(enc, oracle, q):
-    """The pre-filter is a stage of its own for quality 1..16 (k_low_machine + k_low_marks + the chroma pass, the kernels the encoder runs,
-    behind nhw_stage_prefilter); for 17..21 it lives inside the fused front kernel k_front_image (test_fused_front_matches_oracle)."""
+    """The pre-filter is a stage of its own for quality 1..16 (k_low_pre, k_low_mapfix, k_low_chain, k_low_apply, k_low_markrows and k_low_marks,
+    the kernels the encoder runs, behind nhw_stage_prefilter); for 17..21 it lives inside the fused front kernel k_front_image (test_fused_front_matches_oracle)."""
     import torch
     imgs = [oracle.synth(3), class_image("noise", 1), class_image("blocks", 2), class_image("flat")]
     ys = np.stack([oracle.color(im, q)[0] for im in imgs])
