@@ -304,6 +304,29 @@ int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *o
 /* the last region call on the handle: the selected tiles that were handed to the decoder (those of the NHW_OK rects and of the rects that
  * failed on a refused tile) and the tile-file bytes uploaded for them */
 int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded);
+/* ---- decode at half or quarter scale straight from the wavelet pyramid ----
+ * scale 1, 2 or 4; the tile side is T = 512 / scale and a file decodes to 3 T T bytes, in the byte order of the full decode.  Scale 1 is the
+ * full decode.  Scale 2: Y = the level-1 low band of the luma (after its residual lists), U and V = the sharpened 4:2:0 planes, an exact 4:4:4
+ * picture with no resampling; scale 4: Y = the level-2 low band, U and V = the chroma planes' level-1 low band after their corrections; both
+ * through the file's own colour matrix, neither with the smoothing at the marks or the q > 21 level-1 corrections.  Scale 2 runs neither the
+ * level-1 synthesis of the luma nor the mark search, scale 4 in addition none of level 2 of the luma, level 1 of the chroma and the sharpening.
+ * nhw_dec_batch_device_scaled: the arguments of nhw_dec_batch_device plus scale; d_out holds n * 3 T T bytes, file after file, 8-byte aligned;
+ * d_status and d_quality are exactly those of the full decode, and a refused file's bytes are left untouched.  NHW_E_ARG for any other scale
+ * and for a scale of 2 or 4 on a handle with a debug stop set.  Asynchronous on `stream`; nhw_dec_last_timing describes it, recon_ms = the
+ * kernel that writes the scaled pictures.  One handle serves full and scaled batches in any order. */
+int nhw_dec_batch_device_scaled(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_out,
+                                int32_t *d_status, int32_t *d_quality, void *stream);
+/* host convenience, synchronous: as nhw_dec_batch, for any n >= 1 (decoded in chunks of max_batch); file i lands at out + i * 3 T T */
+int nhw_dec_batch_scaled(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality);
+/* A W x H picture at scale s is ceil(W / s) x ceil(H / s): output pixel (r, c) is pixel (r % T, c % T) of the scaled decode of tile
+ * (r / T, c / T).  The tile count does not change (ceil(ceil(W / s) / T) = ceil(W / 512)); where W or H is no multiple of s the last column or
+ * row comes from the edge-replicated padding.  NHW_E_ARG for a side outside 1..65535 or a scale other than 1, 2, 4. */
+int nhw_picture_scaled_size(uint32_t width, uint32_t height, int scale, uint32_t *scaled_width, uint32_t *scaled_height);
+/* nhw_untile_pictures_device for the tiles of a scaled decode: tile t at d_tiles + (t - tile0) * 3 T T, and the table describes the
+ * DESTINATION: the scaled width, height and pitch of every picture.  Same rules otherwise; NHW_E_ARG also for a scale other than 1, 2, 4. */
+int nhw_untile_pictures_scaled_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int n_tiles, int scale, void *stream);
+/* nhw_dec_pictures at a scale: picture i (ceil(W / scale) x ceil(H / scale) x 3 bytes, packed) lands at out + out_off[i] */
+int nhw_dec_pictures_scaled(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, int scale, uint8_t *out, const uint64_t *out_off, int32_t *status);
 /* hipEvent timings of the last nhw_dec_batch_device call (events on its launch stream): the whole sequence, the entropy stages
  * (parse, prefix-code walk, un-zig-zag), the two level-1 luma synthesis passes and the colour kernel -- the last three are the kernels
  * SURVEY.md 8(d) prices against the HBM roofline for the decode path */

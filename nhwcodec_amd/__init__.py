@@ -87,6 +87,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_dec_regions.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, P, P, P]
     L.nhw_dec_regions_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, P, P, P]
     L.nhw_dec_last_region_stats.argtypes = [P, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    L.nhw_dec_batch_device_scaled.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, P, P, P, P]
+    L.nhw_dec_batch_scaled.argtypes = [P, P, P, ctypes.c_int, ctypes.c_int, P, P, P]
+    L.nhw_picture_scaled_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    L.nhw_untile_pictures_scaled_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_dec_pictures_scaled.argtypes = [P, P, P, ctypes.c_int, ctypes.c_int, P, P, P]
     return L
 
 
@@ -145,6 +150,26 @@ def picture_tiles(width: int, height: int) -> int:
     return ((width + 511) // 512) * ((height + 511) // 512)
 
 
+# ---------------------------------------------------------------- half and quarter scale
+SCALES = (1, 2, 4)
+
+
+def _scale(scale, what):
+    if isinstance(scale, bool) or not isinstance(scale, numbers.Integral) or scale not in SCALES:
+        raise NhwError(f"{what}: the scale must be 1, 2 or 4, got {scale!r}")
+    return int(scale)
+
+
+def scaled_size(width: int, height: int, scale: int) -> tuple:
+    """(ceil(width / scale), ceil(height / scale)): the size of a width x height picture (sides 1..65535) decoded at scale 1, 2 or 4.  Its tiles
+    have the side 512 // scale and are as many as the whole picture's."""
+    scale = _scale(scale, "scaled_size")
+    if not (isinstance(width, numbers.Integral) and isinstance(height, numbers.Integral)):
+        raise NhwError(f"a picture's sides must be integers, got {width!r} x {height!r}")
+    picture_tiles(int(width), int(height))
+    return -(-int(width) // scale), -(-int(height) // scale)
+
+
 # ---------------------------------------------------------------- a rectangle of a picture from the tiles it touches (DESIGN.md section 13)
 REGION_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("x", "<u4"), ("y", "<u4"), ("width", "<u4"), ("height", "<u4"), ("pic_width", "<u4"),
                 ("pic_height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_region
@@ -160,9 +185,9 @@ def region_tiles(pic_width: int, pic_height: int, x: int, y: int, width: int, he
     return ((x + width - 1) // 512 - x // 512 + 1) * ((y + height - 1) // 512 - y // 512 + 1)
 
 
-def _picture_table(pictures, what):
+def _picture_table(pictures, what, side=512):
     """the checked nhw_picture table of a list of uint8 CUDA tensors [H, W, 3] with strides (pitch, 3, 1), on one device -> (table as an
-    int64 CUDA tensor, total tiles, device)"""
+    int64 CUDA tensor, total tiles, device).  side: the tile side (512; 256 or 128 for the pictures of a scaled decode)"""
     import numpy as np
     import torch
     if not isinstance(pictures, (list, tuple)) or not pictures:
@@ -176,7 +201,7 @@ def _picture_table(pictures, what):
         if x.device != dev:
             raise NhwError(f"{what}: picture {i} is on {x.device}, picture 0 on {dev}")
         h, w = int(x.shape[0]), int(x.shape[1])
-        t = picture_tiles(w, h)
+        t = picture_tiles(w, h) if side == 512 else (-(-w // side)) * (-(-h // side))
         if x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w):
             raise NhwError(f"{what}: picture {i} must have strides (pitch >= 3 W, 3, 1), got {tuple(x.stride())}")
         table[i] = (x.data_ptr(), x.stride(0) if h > 1 else 3 * w, w, h, tiles, 0)
@@ -217,6 +242,29 @@ def untile_pictures_device(tiles, pictures):
     L = _library()
     with torch.cuda.device(dev):
         rc = L.nhw_untile_pictures_device(tiles.data_ptr(), table.data_ptr(), len(pictures), 0, n_tiles, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+
+
+def untile_scaled_pictures_device(tiles, pictures, scale):
+    """untile_pictures_device for the tiles of a scaled decode (nhw_untile_pictures_scaled_device): tiles uint8 [T, S, S, 3] with S = 512 // scale
+    (e.g. Decoder.decode_scaled_device's pixels) into the preallocated pictures, given as for untile_pictures_device but at their SCALED sizes
+    (scaled_size); picture k takes ceil(W' / S) * ceil(H' / S) tiles.  Only the pictures' own bytes are written.  Ordered on torch's current stream."""
+    import torch
+    what = "untile_scaled_pictures_device"
+    scale = _scale(scale, what)
+    side = 512 // scale
+    if isinstance(pictures, (list, tuple)):
+        for i, x in enumerate(pictures):
+            if isinstance(x, torch.Tensor) and x.dim() == 3 and not (1 <= x.shape[0] <= -(-65535 // scale) and 1 <= x.shape[1] <= -(-65535 // scale)):
+                raise NhwError(f"{what}: picture {i} is {x.shape[1]} x {x.shape[0]}, beyond a 65535 x 65535 picture at scale {scale}")
+    table, n_tiles, dev = _picture_table(pictures, what, side)
+    if not (isinstance(tiles, torch.Tensor) and tiles.is_cuda and tiles.device == dev and tiles.dtype == torch.uint8 and tiles.is_contiguous()
+            and tiles.numel() == n_tiles * 3 * side * side):
+        raise NhwError(f"{what}: `tiles` must be a contiguous uint8 tensor [{n_tiles}, {side}, {side}, 3] on {dev}")
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_untile_pictures_scaled_device(tiles.data_ptr(), table.data_ptr(), len(pictures), 0, n_tiles, scale, torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
 
@@ -756,6 +804,78 @@ class Decoder:
             self._chk(self.lib.nhw_dec_batch_device(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, out.data_ptr(), status.data_ptr(),
                                                     quality.data_ptr(), st))
         return out, status, quality
+
+    def decode_scaled_device(self, arena, offsets, lengths, scale, out=None):
+        """decode_device at scale 1, 2 or 4 (nhw_dec_batch_device_scaled): the half-scale (256 x 256, exact 4:4:4) or
+        quarter-scale (128 x 128) picture every file holds, without the level-1 synthesis.  Arguments as for decode_device; out: a contiguous
+        uint8 tensor of at least n * 3 * S * S bytes, S = 512 // scale.  Returns (pixels[n, S, S, 3], status[n], quality[n]) on the device;
+        status and quality are those of the full decode.  Scale 1 is decode_device."""
+        t = self.torch
+        scale = _scale(scale, "decode_scaled_device")
+        side = 512 // scale
+        dev = f"cuda:{self.device}"
+        for name, x, dt in (("arena", arena, t.uint8), ("offsets", offsets, t.int64), ("lengths", lengths, t.int32)):
+            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous()):
+                raise NhwError(f"decode_scaled_device: `{name}` must be a contiguous {dt} tensor on cuda:{self.device}")
+        n = offsets.numel()
+        if lengths.numel() != n or n < 1:
+            raise NhwError("decode_scaled_device: offsets and lengths must have one entry per file")
+        if n > self.max_batch:
+            raise NhwError(f"decode_scaled_device: {n} files for a decoder of max_batch {self.max_batch}")
+        if out is None:
+            out = t.empty((n, side, side, 3), dtype=t.uint8, device=dev)
+        elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == t.uint8 and out.is_contiguous()
+                  and out.numel() >= n * 3 * side * side and out.data_ptr() % 8 == 0):
+            raise NhwError(f"decode_scaled_device: `out` must be a contiguous, 8-byte aligned uint8 tensor of n*{3 * side * side} bytes on this decoder's device")
+        status = t.empty(n, dtype=t.int32, device=dev)
+        quality = t.empty(n, dtype=t.int32, device=dev)
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_dec_batch_device_scaled(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, out.data_ptr(),
+                                                           status.data_ptr(), quality.data_ptr(), st))
+        px = out if out.dim() == 4 and tuple(out.shape) == (n, side, side, 3) else out.reshape(-1)[:n * 3 * side * side].view(n, side, side, 3)
+        return px, status, quality
+
+    def decode_scaled(self, files, scale):
+        """decode at scale 1, 2 or 4 (nhw_dec_batch_scaled): files, a list of .nhw byte strings of any length (decoded in chunks of max_batch) ->
+        (uint8 [n, S, S, 3] with S = 512 // scale, quality list).  Raises on a file the decoder refuses."""
+        import numpy as np
+        scale = _scale(scale, "decode_scaled")
+        side = 512 // scale
+        if not isinstance(files, (list, tuple)) or not files or not all(isinstance(f, (bytes, bytearray, memoryview)) for f in files):
+            raise NhwError("decode_scaled wants a non-empty list of .nhw byte strings")
+        n = len(files)
+        offs = np.zeros(n + 1, np.uint64)
+        offs[1:] = np.cumsum([len(f) for f in files])
+        blob = np.frombuffer(b"".join(bytes(f) for f in files) + b"\0", np.uint8)
+        out = np.empty((n, side, side, 3), np.uint8)
+        status = np.empty(n, np.int32)
+        quality = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_dec_batch_scaled(self.h, blob.ctypes.data, offs.ctypes.data, n, scale, out.ctypes.data, status.ctypes.data, quality.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-file status {status.tolist()}")
+        return out, quality.tolist()
+
+    def decode_pictures_scaled(self, containers, scale):
+        """decode_pictures at scale 1, 2 or 4 (nhw_dec_pictures_scaled): a list of .nhwp containers (bytes) -> a list of numpy uint8
+        [ceil(H / scale), ceil(W / scale), 3], each assembled on the device from the scaled decode of its tiles: the overview of a large picture
+        without the level-1 synthesis of a single tile.  Raises on a malformed container or a tile the decoder refuses."""
+        import numpy as np
+        scale = _scale(scale, "decode_pictures_scaled")
+        if not isinstance(containers, (list, tuple)) or len(containers) < 1:
+            raise NhwError("decode_pictures_scaled wants a non-empty list of containers")
+        n = len(containers)
+        shapes = [scaled_size(*picture_info(c), scale) for c in containers]
+        offs = np.zeros(n + 1, np.uint64)
+        offs[1:] = np.cumsum([len(c) for c in containers])
+        blob = np.frombuffer(b"".join(bytes(c) for c in containers), np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        out_off[1:] = np.cumsum([3 * w * h for w, h in shapes])
+        out = np.empty(int(out_off[n]), np.uint8)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_dec_pictures_scaled(self.h, blob.ctypes.data, offs.ctypes.data, n, scale, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-container status {status.tolist()}")
+        return [out[int(out_off[i]):int(out_off[i + 1])].reshape(h, w, 3) for i, (w, h) in enumerate(shapes)]
 
     def decode_pictures(self, containers):
         """containers: a list of .nhwp containers (bytes) -> a list of numpy uint8 [H, W, 3]: the tiles decoded in chunks of max_batch and

@@ -1727,7 +1727,8 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int s
  * c of the result leaves as row c of the plane.  Before: five kernels and four round trips of the plane.  After the in-place level 2 the
  * corner holds sample (row r, column c) of the level-1 LL at [c][r] -- which is how level 1 wants it (its row pass reads line c of the
  * transposed LL) and where the corrections, given in plane coordinates, are added.  `upto`: the debug stop (1: the block as built, 2: after
- * level 2, 3: after the corrections -- written back in the plane's layout; 4: everything). */
+ * level 2, 3: after the corrections -- written back in the plane's layout; 4: everything).  5 is no debug stop: the quarter-scale decode
+ * (k_dec_scaled<4>) ends a plane behind the corrections and takes its level-1 LL, 128 rows of 128 in the plane's orientation, from the head of the plane. */
 __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int upto)
 {
 	extern __shared__ __attribute__((aligned(16))) int16_t smem[];
@@ -1805,6 +1806,16 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 		}
 		lds_barrier();
 		if (upto == 3) { store_block(true); lds_barrier(); continue; }
+		if (upto == 5) {                                             /* the quarter-scale decode's exit: the corrected level-1 LL alone, turned back, its 128 rows packed at the head of the plane */
+			uint32_t *dst = reinterpret_cast<uint32_t *>(pl);
+#pragma unroll 2
+			for (int k = t; k < HLF * HLF / 2; k += NT_) {
+				const int r = k >> 6, c = 2 * (k & 63);
+				dst[k] = (uint32_t)(uint16_t)smem[c * LS + r] | ((uint32_t)(uint16_t)smem[(c + 1) * LS + r] << 16);
+			}
+			lds_barrier();
+			continue;
+		}
 		syn_rows_inplace<S, 16, 1>(smem + wv * 16 * LS, LS, lane);      /* level 1 */
 		lds_barrier();
 #pragma unroll 1
@@ -2343,6 +2354,73 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 	}
 }
 
+/* ---------------------------------------------------------------------------------------------- half and quarter scale
+ * The small pictures a file holds anyway, through the colour matrix of k_dec_final: no level-1 synthesis of the luma, no marks, no x2 of the chroma.
+ *   S = 2: Y = the level-1 LL as k_dec_luma_l2q leaves it (plane_l1), U, V = the sharpened bytes of k_dec_sharpen -- an exact 4:4:4 picture of 256 x 256;
+ *   S = 4: Y = the level-2 LL quadrant of plane A as k_dec_expand leaves it, which is the picture transposed (the level-2 synthesis is what would turn
+ *          it), U, V = the level-1 LL of the chroma planes behind the corrections (k_dec_chroma, upto 5) -- 128 x 128.
+ * A workgroup takes SC_ROWS output rows of one file and depends on no other; a thread takes eight pixels of a row: 16 bytes of int16 or 8 bytes of
+ * samples a plane in, three 8-byte stores out, consecutive lanes on consecutive 24-byte pieces.  The quarter scale's luma goes through LDS to be turned:
+ * of line c of plane A the band needs the SC_ROWS samples from r0 on, 64 contiguous bytes, four lanes a line. */
+#define SC_ROWS 32
+DEV uint32_t clip8x4(uint32_t a, uint32_t b)                      /* four int16 in two dwords -> four bytes, clipped */
+{
+	return (uint32_t)clip8((int16_t)(a & 0xFFFFu)) | ((uint32_t)clip8((int16_t)(a >> 16)) << 8) | ((uint32_t)clip8((int16_t)(b & 0xFFFFu)) << 16) | ((uint32_t)clip8((int16_t)(b >> 16)) << 24);
+}
+DEV uint2 clip8x8(const uint4 &v) { return make_uint2(clip8x4(v.x, v.y), clip8x4(v.z, v.w)); }
+template <int S> __global__ __launch_bounds__(256) void k_dec_scaled(DecWs ws, uint8_t *out)
+{
+	static_assert(S == 2 || S == 4, "half or quarter scale");
+	constexpr int T = DW / S, NB = T / SC_ROWS, TPR = T / 8, YP = T + 4;   /* tile side, bands a file, threads a row; LDS pitch of a luma row (S = 4): a band's four pieces of a line on different banks */
+	__shared__ __attribute__((aligned(16))) uint8_t ybuf[S == 4 ? SC_ROWS * YP : 16];
+	const int tid = threadIdx.x, img = blockIdx.x / NB, r0 = (blockIdx.x % NB) * SC_ROWS;
+	const DecMeta *m = ws.buf<DecMeta>(D_META, img);
+	if (m->status) return;
+	const int q = m->q;
+	if (S == 4) {
+		const int16_t *A = plane_a(ws, img);
+		const int g = tid & 3;
+#pragma unroll
+		for (int pass = 0; pass < T / 64; pass++) {
+			const int c = (tid >> 2) + 64 * pass;
+			const uint2 y8 = clip8x8(*reinterpret_cast<const uint4 *>(A + (size_t)c * DW + r0 + 8 * g));
+#pragma unroll
+			for (int e = 0; e < 8; e++) ybuf[(8 * g + e) * YP + c] = (uint8_t)((e < 4 ? y8.x : y8.y) >> (8 * (e & 3)));
+		}
+		__syncthreads();
+	}
+	for (int it = 0; it < SC_ROWS * TPR / 256; it++) {
+		const int i = tid + 256 * it, lr = i / TPR, c8 = i % TPR, r = r0 + lr;
+		uint2 y8, u8, v8;
+		if (S == 2) {
+			y8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_l1(ws, img) + (size_t)r * DW + 8 * c8));
+			const uint8_t *cu = ws.buf<uint8_t>(D_CU, img) + (size_t)r * DH + 8 * c8;
+			u8 = *reinterpret_cast<const uint2 *>(cu); v8 = *reinterpret_cast<const uint2 *>(cu + DQ);
+		} else {
+			const uint32_t *yw = reinterpret_cast<const uint32_t *>(ybuf + lr * YP + 8 * c8);
+			y8 = make_uint2(yw[0], yw[1]);
+			u8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_ca(ws, img, 0) + r * T + 8 * c8));
+			v8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_ca(ws, img, 1) + r * T + 8 * c8));
+		}
+		uint32_t w[6];
+		if (q >= 20) colour8_q20(y8, u8, v8, w);
+		else {
+#pragma unroll
+			for (int e = 0; e < 6; e++) w[e] = 0;
+#pragma unroll
+			for (int px = 0; px < 8; px++) {
+				const uint32_t yw = px < 4 ? y8.x : y8.y, uw = px < 4 ? u8.x : u8.y, vw = px < 4 ? v8.x : v8.y;
+				int R, G, B;
+				yuv_to_bytes(q, (int)((yw >> (8 * (px & 3))) & 255u), (int)((uw >> (8 * (px & 3))) & 255u), (int)((vw >> (8 * (px & 3))) & 255u), R, G, B);
+				const int b0 = 3 * px;
+				w[b0 >> 2] |= (uint32_t)R << (8 * (b0 & 3)); w[(b0 + 1) >> 2] |= (uint32_t)G << (8 * ((b0 + 1) & 3)); w[(b0 + 2) >> 2] |= (uint32_t)B << (8 * ((b0 + 2) & 3));
+			}
+		}
+		uint2 *o = reinterpret_cast<uint2 *>(out + (size_t)img * (3 * T * T) + (size_t)r * (3 * T) + 24 * c8);
+		o[0] = make_uint2(w[0], w[1]); o[1] = make_uint2(w[2], w[3]); o[2] = make_uint2(w[4], w[5]);
+	}
+}
+
 __global__ __launch_bounds__(256) void k_dec_status(DecWs ws, int32_t *status, int32_t *quality)
 {
 	const int img = blockIdx.x * 256 + threadIdx.x;
@@ -2449,10 +2527,14 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 	return NHW_OK;
 }
 
-extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, void *d_bgr, int32_t *d_status,
-                                    int32_t *d_quality, void *stream)
+/* one batch at scale 1 (the whole decode), 2 or 4: what the two entry points below share */
+static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_bgr, int32_t *d_status,
+                     int32_t *d_quality, void *stream)
 {
 	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	if (scale != 1 && d->stop_after) { nhw_dec_err = "a scaled decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
+	if (scale != 1 && ((uintptr_t)d_bgr & 7)) { nhw_dec_err = "a scaled decode's output must be 8-byte aligned"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(d->device));                              /* the handle's device, whatever the calling thread had current */
 	hipStream_t s = stream ? (hipStream_t)stream : d->own_stream;
 	const NhwSliceScope slices(d->slice_order);
@@ -2461,7 +2543,7 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 	int stage = 0;
 	d->timed = false;
 	d->l1_moved = false;
-	const bool fork = (d->chroma_fork & 2) && !d->stop_after;          /* the chroma sequence beside the luma one */
+	const bool fork = (d->chroma_fork & 2) && !d->stop_after && scale == 1;   /* the chroma sequence beside the luma one (a scaled decode keeps it in line) */
 	const bool fork_e = (d->chroma_fork & 1) && !d->stop_after;        /* the two entropy branches side by side */
 	hipStream_t cs = fork ? d->chroma_stream : s;
 	hipStream_t es = fork_e ? d->chroma_stream : s;
@@ -2484,6 +2566,14 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 	 * stop it stays in line. */
 #define CHROMA(UPTO, STREAM) k_dec_chroma<<<2 * n < SYNTH_WGS ? 2 * n : SYNTH_WGS, 1024, 256 * 258 * sizeof(int16_t), STREAM>>>(ws, 2 * n, UPTO)
 	k_dec_expand<<<(n + 3) / 4, 256, 0, s>>>(ws);
+	if (scale == 4) {                                                             /* quarter scale: the level-2 LL is in plane A already; the chroma planes up to their corrections */
+		CHROMA(5, s);
+		EV(2);
+		k_dec_scaled<4><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		EV(3);
+		d->timed = true;
+		goto done;
+	}
 	if (fork) {
 		CHROMA(4, cs);
 		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, cs>>>(ws);
@@ -2502,6 +2592,15 @@ extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_
 	STAGE_END();                                                                  /* 4 (the block as the shrink leaves it) */
 	STAGE_END();                                                                  /* 5 (after the synthesis) */
 	STAGE_END();                                                                  /* 6 */
+	if (scale == 2) {                                                             /* half scale: the level-1 LL and the whole chroma sequence, in line; no marks, no level 1 of the luma */
+		CHROMA(4, s);
+		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, s>>>(ws);
+		EV(2);
+		k_dec_scaled<2><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		EV(3);
+		d->timed = true;
+		goto done;
+	}
 	if (fork_late) {
 		HIPCHK(hipEventRecord(d->fork_ev, s)); HIPCHK(hipStreamWaitEvent(d->chroma_stream, d->fork_ev, 0));
 		CHROMA(4, d->chroma_stream);
@@ -2537,6 +2636,18 @@ done:
 #undef STAGE_END
 #undef EV
 #undef CHROMA
+}
+
+extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, void *d_bgr, int32_t *d_status,
+                                    int32_t *d_quality, void *stream)
+{
+	return dec_batch(d, d_nhw, d_off, d_len, n, 1, d_bgr, d_status, d_quality, stream);
+}
+
+extern "C" int nhw_dec_batch_device_scaled(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_out,
+                                           int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
 }
 
 extern "C" int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t)

@@ -40,7 +40,41 @@ extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off
 	return NHW_OK;
 }
 
-/* ---------------------------------------------------------------------------------------------- pictures of any size (DESIGN.md sections 11, 13) */
+/* the same at scale 1, 2 or 4, for any n >= 1: the files go up once and are decoded in chunks of max_batch; file i's
+ * 3 T T bytes (T = 512 / scale) land at out + i * 3 T T */
+extern "C" int nhw_dec_batch_scaled(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality)
+{
+	if (!d || !nhw || !off || !out || !status || n < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { nhw_dec_err = "nhw_dec_batch_scaled: off[] must not decrease"; return NHW_E_ARG; }
+	HIPCHK(hipSetDevice(d->device));
+	const size_t total = (size_t)(off[n] - off[0]), per = (size_t)NHW_IMG_BYTES / (size_t)(scale * scale);
+	{ const int rc = host_buffers(d, total); if (rc) return rc; }
+	hipStream_t s = d->own_stream;
+	HIPCHK(hipMemcpyAsync(d->blob.p, nhw + off[0], total, hipMemcpyHostToDevice, s));
+	std::vector<uint64_t> rel((size_t)d->max_batch);
+	std::vector<uint32_t> len((size_t)d->max_batch);
+	for (int i0 = 0; i0 < n; i0 += d->max_batch) {
+		const int m = n - i0 < d->max_batch ? n - i0 : d->max_batch;
+		for (int i = 0; i < m; i++) {
+			rel[i] = off[i0 + i] - off[0];
+			const uint64_t l = off[i0 + i + 1] - off[i0 + i];
+			len[i] = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
+		}
+		HIPCHK(hipMemcpyAsync(d->d_off, rel.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(d->d_len, len.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
+		HIPCHK(hipStreamSynchronize(s));                              /* rel and len are filled again for the next chunk */
+		const int rc = nhw_dec_batch_device_scaled(d, d->blob.p, d->d_off, d->d_len, m, scale, d->d_out, d->d_status, d->d_quality, s);
+		if (rc) return rc;
+		HIPCHK(hipMemcpyAsync(out + (size_t)i0 * per, d->d_out, (size_t)m * per, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(status + i0, d->d_status, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+		if (quality) HIPCHK(hipMemcpyAsync(quality + i0, d->d_quality, (size_t)m * 4, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+	}
+	return NHW_OK;
+}
+
+/* ---------------------------------------------------------------------------------------------- pictures of any size (DESIGN.md sections 11, 13, 14) */
 /* What nhw_dec_pictures and the region calls share: a container's directory, the chunked decode of a list of tile files, the status
  * gather and the download of the results. */
 static uint32_t dir_len(const uint8_t *dir, int k)                /* length of tile file k in a container's directory */
@@ -51,10 +85,10 @@ static uint32_t dir_len(const uint8_t *dir, int k)                /* length of t
 static const size_t MAX_CALL_TILES = (size_t)(INT_MAX / 16);       /* the tiles one host call takes */
 
 /* The tile files of a call, in the handle's blob (already on its way there on the handle's stream): offsets and lengths go up, the tiles are
- * decoded in chunks of max_batch into the host path's picture slots, each chunk followed by crop(t0, m) -- the launch that takes the
+ * decoded at `scale` in chunks of max_batch into the host path's picture slots, each chunk followed by crop(t0, m) -- the launch that takes the
  * decoded tiles [t0, t0 + m) out of d->d_out --, and the per-tile status comes back.  Synchronises the stream. */
 template <class Crop>
-static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const std::vector<uint32_t> &tlen, std::vector<int32_t> &tst, Crop &&crop)
+static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const std::vector<uint32_t> &tlen, int scale, std::vector<int32_t> &tst, Crop &&crop)
 {
 	const int tiles = (int)toff.size();
 	HIPCHK(nhw_grow(d->pic_tiles, (size_t)tiles * 16));
@@ -66,7 +100,7 @@ static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const
 	HIPCHK(hipMemcpyAsync(d_tlen, tlen.data(), (size_t)tiles * 4, hipMemcpyHostToDevice, s));
 	for (int t0 = 0; t0 < tiles; t0 += d->max_batch) {
 		const int m = tiles - t0 < d->max_batch ? tiles - t0 : d->max_batch;
-		const int rc = nhw_dec_batch_device(d, d->blob.p, d_toff + t0, d_tlen + t0, m, d->d_out, d_tst + t0, nullptr, s);
+		const int rc = nhw_dec_batch_device_scaled(d, d->blob.p, d_toff + t0, d_tlen + t0, m, scale, d->d_out, d_tst + t0, nullptr, s);
 		if (rc) return rc;
 		HIPCHK(crop(t0, m));
 	}
@@ -99,9 +133,10 @@ static int download_spans(uint8_t *bgr, const std::vector<Span> &sp)
 /* Parse every container on the host; upload the blob once (a container's tile files lie back to back, so the decoder's offsets and lengths
  * come from its directory); decode the tiles in chunks of max_batch into the host path's picture slots and crop each chunk into the
  * picture buffer (k_untile_crop); then bring back the pictures whose tiles all decoded. */
-extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+static int dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, int scale, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
 {
 	if (!d || !blob || !off || !bgr || !out_off || !status || n < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
 	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { nhw_dec_err = "nhw_dec_pictures: off[] must not decrease"; return NHW_E_ARG; }
 	std::vector<nhw_picture> desc;
 	std::vector<int> which;                                      /* desc[k] is container which[k] */
@@ -116,6 +151,7 @@ extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t 
 		if (nhw_container_parse(blob + off[i], (size_t)(off[i + 1] - off[i]), &w, &h, &t, &dir) != NHW_OK) continue;
 		if (toff.size() + (size_t)t > MAX_CALL_TILES) { nhw_dec_err = "nhw_dec_pictures: too many tiles in one call"; return NHW_E_ARG; }
 		status[i] = NHW_OK;
+		nhw_picture_scaled_size(w, h, scale, &w, &h);                 /* the table describes the destination; the tile count is that of the whole picture */
 		desc.push_back({ bytes, 3ull * w, w, h, (uint32_t)toff.size(), 0 });
 		which.push_back(i);
 		uint64_t fo = off[i] - off[0] + 16 + 4 * (uint64_t)t;
@@ -134,13 +170,24 @@ extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t 
 	HIPCHK(hipMemcpyAsync(d->blob.p, blob + off[0], (size_t)(off[n] - off[0]), hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
 	std::vector<int32_t> tst;
-	{ const int rc = decode_tile_list(d, toff, tlen, tst, [&](int t0, int m) { return nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, s); }); if (rc) return rc; }
+	{ const int rc = decode_tile_list(d, toff, tlen, scale, tst, [&](int t0, int m) { return nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, scale, s); }); if (rc) return rc; }
 	std::vector<Span> sp;
 	for (int k = 0; k < np; k++) {
 		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < np ? (int)desc[k + 1].first_tile : tiles);
 		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
 	}
 	return download_spans(bgr, sp);
+}
+
+extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+{
+	return dec_pictures(d, blob, off, n, 1, bgr, out_off, status);
+}
+
+/* the same at scale 2 or 4 (1: nhw_dec_pictures): picture i is ceil(W / scale) x ceil(H / scale), made from the half- or quarter-scale decode of its tiles */
+extern "C" int nhw_dec_pictures_scaled(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, int scale, uint8_t *out, const uint64_t *out_off, int32_t *status)
+{
+	return dec_pictures(d, blob, off, n, scale, out, out_off, status);
 }
 
 /* ---------------------------------------------------------------------------------------------- regions of pictures */
@@ -216,7 +263,7 @@ static int dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)ng * sizeof(nhw_region), hipMemcpyHostToDevice, s));
 	d->reg_tiles = (uint64_t)tiles; d->reg_bytes = files.size();
 	std::vector<int32_t> tst;
-	{ const int rc = decode_tile_list(d, toff, tlen, tst, [&](int t0, int m) { return nhw_launch_untile_region(d->d_out, d_desc, ng, t0, m, s); }); if (rc) return rc; }
+	{ const int rc = decode_tile_list(d, toff, tlen, 1, tst, [&](int t0, int m) { return nhw_launch_untile_region(d->d_out, d_desc, ng, t0, m, s); }); if (rc) return rc; }
 	std::vector<Span> sp;
 	for (int k = 0; k < ng; k++) {
 		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < ng ? (int)desc[k + 1].first_tile : tiles);

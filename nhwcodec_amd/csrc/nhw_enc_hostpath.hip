@@ -103,7 +103,16 @@ extern "C" int nhw_tile_pictures_device(const nhw_picture *d_pics, int n_pics, i
 extern "C" int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, void *stream)
 {
 	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_untile_pictures_device")) return rc;
-	HIPCHK(nhw_launch_untile_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, m, (hipStream_t)stream));
+	HIPCHK(nhw_launch_untile_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, m, 1, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* the crop of a scaled decode: tiles of side 512 / scale, 3 T T bytes each, into the scaled pictures of the table */
+extern "C" int nhw_untile_pictures_scaled_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int n_tiles, int scale, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, n_tiles, d_tiles, "nhw_untile_pictures_scaled_device")) return rc;
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = "nhw_untile_pictures_scaled_device: the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_untile_crop((const uint8_t *)d_tiles, d_pics, n_pics, tile0, n_tiles, scale, (hipStream_t)stream));
 	return NHW_OK;
 }
 

@@ -1,6 +1,6 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11, 12, 13): the padding kernel k_tile_pad, its inverse
- * k_untile_crop, the rectangle-of-a-picture crop k_untile_region, the picture-cropped error k_sse_crop, and the .nhwp container that
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11, 12, 13, 14): the padding kernel k_tile_pad, its inverse
+ * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crop k_untile_region, the picture-cropped error k_sse_crop, and the .nhwp container that
  * holds a picture's width, height and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
@@ -61,14 +61,16 @@ struct TileRef {
 	int k;                                  /* the picture's index in the table */
 };
 
-/* the workgroup's tile (tile0 + blockIdx.x / TP_BANDS) and its picture; false for a tile no picture of the table holds */
+/* the workgroup's tile (tile0 + blockIdx.x / bands of a tile) and its picture; false for a tile no picture of the table holds.  T: the tile's
+ * side, 512 or, for the tiles of a scaled decode, 256 or 128 -- the table then holds the scaled pictures */
+template <int T = 512>
 __device__ __forceinline__ bool tile_of(const nhw_picture *pics, int n, int tile0, TileRef &r)
 {
-	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
+	const uint32_t t = (uint32_t)tile0 + blockIdx.x / (T / TP_ROWS);
 	r.k = find_picture(pics, n, t);
 	r.p = pics[r.k];
 	if (!r.p.width || !r.p.height || t < r.p.first_tile) return false;
-	const uint32_t nx = (r.p.width + 511) / 512, ny = (r.p.height + 511) / 512, in = t - r.p.first_tile;
+	const uint32_t nx = (r.p.width + T - 1) / T, ny = (r.p.height + T - 1) / T, in = t - r.p.first_tile;
 	if (in >= nx * ny) return false;
 	r.ty = in / nx; r.tx = in % nx;
 	return true;
@@ -145,26 +147,29 @@ __device__ __forceinline__ void store_part(uint8_t *A, uint4 v, int j, int e)
 	}
 }
 
-/* the inverse: tile row rr (a picture row r = 512 ty + rr < H) holds picture bytes [1536 tx, min(1536 tx + 1536, 3W)) of row r.  They go
- * out as the 16-byte-aligned destination words that cover them (at most 97 a row): whole words as dwordx4, the ragged head and tail with
- * store_part.  The source side reads the tile row through fetch, only the bytes it stores. */
+/* the inverse: tile row rr (a picture row r = T ty + rr < H) holds picture bytes [3T tx, min(3T tx + 3T, 3W)) of row r (T = 512: 1536).  They go
+ * out as the 16-byte-aligned destination words that cover them (at most 3T / 16 + 1 a row: 97), whole words as dwordx4, the ragged head and tail with
+ * store_part.  The source side reads the tile row through fetch, only the bytes it stores.  T = 256, 128: the tiles of a scaled decode, 3 T T
+ * bytes each, into the scaled pictures of the table. */
+template <int T>
 __global__ __launch_bounds__(TP_THREADS) void k_untile_crop(const uint8_t *__restrict__ tiles, const nhw_picture *__restrict__ pics, int n_pics, int tile0)
 {
+	constexpr int BANDS = T / TP_ROWS, ROW = 3 * T;
 	TileRef r;
-	if (!tile_of(pics, n_pics, tile0, r)) return;
-	const int band = blockIdx.x % TP_BANDS;
-	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES);
-	const int rb = 3 * (int)r.p.width, s0 = 1536 * (int)r.tx, seg = rb - s0 < 1536 ? rb - s0 : 1536;
-	constexpr int SLOTS = TP_WORDS + 1;
+	if (!tile_of<T>(pics, n_pics, tile0, r)) return;
+	const int band = blockIdx.x % BANDS;
+	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / BANDS) * (size_t)(ROW * T));
+	const int rb = 3 * (int)r.p.width, s0 = ROW * (int)r.tx, seg = rb - s0 < ROW ? rb - s0 : ROW;
+	constexpr int SLOTS = ROW / 16 + 1;
 	for (int i = threadIdx.x; i < TP_ROWS * SLOTS; i += TP_THREADS) {
 		const int rr = band * TP_ROWS + i / SLOTS, k = i % SLOTS;
-		const uint32_t row = 512 * r.ty + rr;
+		const uint32_t row = T * r.ty + rr;
 		if (row >= r.p.height) break;                                 /* (rows only grow with i) */
 		const uintptr_t D0 = (uintptr_t)(r.p.addr + (uint64_t)row * r.p.pitch) + s0, D1 = D0 + seg;
 		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
 		if (A >= D1) continue;
 		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
-		const uint4 v = fetch(src + (uintptr_t)rr * 1536 + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
+		const uint4 v = fetch(src + (uintptr_t)rr * ROW + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
 		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
 		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
 	}
@@ -309,9 +314,12 @@ hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0,
 	return hipGetLastError();
 }
 
-hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, hipStream_t s)
+hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, int scale, hipStream_t s)
 {
-	k_untile_crop<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	if (scale == 1) k_untile_crop<512><<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	else if (scale == 2) k_untile_crop<256><<<m * (256 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	else if (scale == 4) k_untile_crop<128><<<m * (128 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }
 
@@ -335,6 +343,15 @@ extern "C" int nhw_picture_tiles(uint32_t width, uint32_t height)
 {
 	if (width < 1 || width > 65535 || height < 1 || height > 65535) return NHW_E_ARG;
 	return (int)(((width + 511) / 512) * ((height + 511) / 512));
+}
+
+/* a W x H picture decoded at scale s is ceil(W / s) x ceil(H / s); its tile count does not change */
+extern "C" int nhw_picture_scaled_size(uint32_t width, uint32_t height, int scale, uint32_t *scaled_width, uint32_t *scaled_height)
+{
+	if (nhw_picture_tiles(width, height) < 1 || (scale != 1 && scale != 2 && scale != 4) || !scaled_width || !scaled_height) return NHW_E_ARG;
+	*scaled_width = (width + (uint32_t)scale - 1) / (uint32_t)scale;
+	*scaled_height = (height + (uint32_t)scale - 1) / (uint32_t)scale;
+	return NHW_OK;
 }
 
 /* the tiles a region x, y, w, h of a W x H picture selects: columns x / 512 .. (x + w - 1) / 512 times rows y / 512 .. (y + h - 1) / 512 */

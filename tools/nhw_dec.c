@@ -8,7 +8,9 @@
  * carries on into undefined behaviour), 3 not an .nhw file (reference: "Not an .nhw file", exit(-1)).
  * Extension: --batch <dir> decodes every *.nhw of a directory to <name>.bmp in one GPU batch; --picture <in.nhwp> <out.bmp> decodes a
  * container of nhw-enc --picture to a bottom-up 24-bit BMP of the picture's own size; with --region X,Y,W,H behind it, only that rectangle
- * (X, Y from the left and the top of the picture as a viewer shows it), decoded from the tiles it touches.
+ * (X, Y from the left and the top of the picture as a viewer shows it), decoded from the tiles it touches.  --scale 2|4 (1: the same as
+ * without it), anywhere on the line of a single file, --batch or --picture: the half- or quarter-scale picture straight from the wavelet
+ * pyramid, under a header that carries the scaled size.
  */
 #include <dirent.h>
 #include <stdint.h>
@@ -32,7 +34,8 @@ static void show_usage(void)
 	"  tiles:   nhw-dec --tiles <rows> <columns> <stem> <image.bmp>   (joins <stem>_y<r>_x<c>.nhw, as written by nhw-enc --tiles)\n"
 	"  tar:     nhw-dec --tar <in.tar> <out.tar>   (every x.nhw member of a ustar archive -> member x.bmp, in order)\n"
 	"  picture: nhw-dec --picture <in.nhwp> <image.bmp>   (a container of nhw-enc --picture, any size)\n"
-	"  region:  nhw-dec --picture <in.nhwp> <image.bmp> --region X,Y,W,H   (that rectangle only, X,Y from the top left; decodes the tiles it touches)\n",
+	"  region:  nhw-dec --picture <in.nhwp> <image.bmp> --region X,Y,W,H   (that rectangle only, X,Y from the top left; decodes the tiles it touches)\n"
+	"  scale:   --scale 1|2|4 with a single file, --batch or --picture   (2, 4: the half- or quarter-scale picture, without the full reconstruction)\n",
 	PROGRAM);
 }
 
@@ -49,14 +52,28 @@ static int read_file(const char *path, uint8_t **buf, size_t *len)
 	return 0;
 }
 
+static int g_scale = 1;                                               /* --scale */
+
+/* the reference's 54 bytes with the size fields of a width x height picture of `bytes` pixel bytes (rows padded to 4) */
+static void bmp_header_sized(uint8_t hdr[54], uint32_t width, uint32_t height, uint32_t bytes)
+{
+	nhw_dec_bmp_header(hdr);
+	hdr[2] = (uint8_t)(bytes + 54); hdr[3] = (uint8_t)((bytes + 54) >> 8); hdr[4] = (uint8_t)((bytes + 54) >> 16); hdr[5] = (uint8_t)((bytes + 54) >> 24);
+	hdr[18] = (uint8_t)width; hdr[19] = (uint8_t)(width >> 8); hdr[20] = (uint8_t)(width >> 16); hdr[21] = (uint8_t)(width >> 24);
+	hdr[22] = (uint8_t)height; hdr[23] = (uint8_t)(height >> 8); hdr[24] = (uint8_t)(height >> 16); hdr[25] = (uint8_t)(height >> 24);
+	hdr[34] = (uint8_t)bytes; hdr[35] = (uint8_t)(bytes >> 8); hdr[36] = (uint8_t)(bytes >> 16); hdr[37] = (uint8_t)(bytes >> 24);
+}
+
 static int write_bmp(const char *path, const uint8_t *pixels)
 {
 	uint8_t hdr[54];
+	const uint32_t side = 512u / (uint32_t)g_scale;
 	FILE *f = fopen(path, "wb");
 	if (!f) { printf("Failed to open output decompressed .bmp file %s\n", path); return 1; }
-	nhw_dec_bmp_header(hdr);
+	if (g_scale == 1) nhw_dec_bmp_header(hdr);
+	else bmp_header_sized(hdr, side, side, 3u * side * side);
 	fwrite(hdr, 54, 1, f);
-	fwrite(pixels, NHW_IMG_BYTES, 1, f);
+	fwrite(pixels, (size_t)3 * side * side, 1, f);
 	fclose(f);
 	return 0;
 }
@@ -78,13 +95,14 @@ static int decode_files(char **in, char **out, int n)
 	}
 	off[n] = total;
 	pix = (uint8_t *)malloc((size_t)n * NHW_IMG_BYTES);
-	if (nhw_dec_create(0, n, &d) || nhw_dec_batch(d, blob, off, n, pix, status, NULL)) {
+	if (nhw_dec_create(0, n, &d) ||
+	    (g_scale == 1 ? nhw_dec_batch(d, blob, off, n, pix, status, NULL) : nhw_dec_batch_scaled(d, blob, off, n, g_scale, pix, status, NULL))) {
 		fprintf(stderr, "%s: GPU decoder unavailable: %s\n", PROGRAM, nhw_dec_last_error());
 		return 2;
 	}
 	for (i = 0; i < n; i++) {
 		if (status[i]) { printf("\nNot an .nhw file"); if (n > 1) printf(": %s", in[i]); printf("\n"); rc = 3; continue; }
-		if (write_bmp(out[i], pix + (size_t)i * NHW_IMG_BYTES)) rc = rc ? rc : 1;
+		if (write_bmp(out[i], pix + (size_t)i * (NHW_IMG_BYTES / (size_t)(g_scale * g_scale)))) rc = rc ? rc : 1;
 	}
 	nhw_dec_destroy(d);
 	free(blob); free(pix); free(off); free(status);
@@ -126,11 +144,7 @@ static int decode_tiles(int ny, int nx, const char *stem, const char *out_path)
 		return 2;
 	}
 	for (t = 0; t < n; t++) if (status[t]) { printf("\nNot an .nhw file: %s_y%d_x%d.nhw\n", stem, t / nx, t % nx); return 3; }
-	nhw_dec_bmp_header(hdr);                                          /* the reference's 54 bytes, with the size fields of the whole picture */
-	hdr[2] = (uint8_t)(bytes + 54); hdr[3] = (uint8_t)((bytes + 54) >> 8); hdr[4] = (uint8_t)((bytes + 54) >> 16); hdr[5] = (uint8_t)((bytes + 54) >> 24);
-	hdr[18] = (uint8_t)width; hdr[19] = (uint8_t)(width >> 8); hdr[20] = (uint8_t)(width >> 16); hdr[21] = (uint8_t)(width >> 24);
-	hdr[22] = (uint8_t)height; hdr[23] = (uint8_t)(height >> 8); hdr[24] = (uint8_t)(height >> 16); hdr[25] = (uint8_t)(height >> 24);
-	hdr[34] = (uint8_t)bytes; hdr[35] = (uint8_t)(bytes >> 8); hdr[36] = (uint8_t)(bytes >> 16); hdr[37] = (uint8_t)(bytes >> 24);
+	bmp_header_sized(hdr, width, height, bytes);                      /* the reference's 54 bytes, with the size fields of the whole picture */
 	f = fopen(out_path, "wb");
 	if (!f) { printf("Failed to open output decompressed .bmp file %s\n", out_path); return 1; }
 	fwrite(hdr, 54, 1, f);
@@ -190,7 +204,10 @@ static int decode_picture(const char *in_path, const char *out_path, const uint3
 		}
 		width = rect.width; height = rect.height;
 	}
-	else t = nhw_picture_tiles(width, height);
+	else {
+		t = nhw_picture_tiles(width, height);
+		if (g_scale != 1) nhw_picture_scaled_size(width, height, g_scale, &width, &height);   /* the tile count stays; the BMP has the scaled size */
+	}
 	row = width * 3; stride = (row + 3) & ~3u;
 	if ((uint64_t)stride * height + 54u > 0xFFFFFFFFull) {           /* the BMP header's 32-bit size fields */
 		fprintf(stderr, "%s: a %u x %u picture does not fit a BMP file (4 GiB)\n", PROGRAM, (unsigned)width, (unsigned)height);
@@ -201,18 +218,15 @@ static int decode_picture(const char *in_path, const char *out_path, const uint3
 	pix = (uint8_t *)malloc((size_t)row * height);
 	off[0] = 0; off[1] = len;
 	if (!pix || nhw_dec_create(0, t < 1024 ? t : 1024, &d) ||
-	    (region ? nhw_dec_regions(d, blob, off, 1, &rect, 1, pix, out_off, &status) : nhw_dec_pictures(d, blob, off, 1, pix, out_off, &status))) {
+	    (region ? nhw_dec_regions(d, blob, off, 1, &rect, 1, pix, out_off, &status) :
+	     g_scale != 1 ? nhw_dec_pictures_scaled(d, blob, off, 1, g_scale, pix, out_off, &status) : nhw_dec_pictures(d, blob, off, 1, pix, out_off, &status))) {
 		fprintf(stderr, "%s: GPU decoder unavailable: %s\n", PROGRAM, nhw_dec_last_error());
 		return 2;
 	}
 	nhw_dec_destroy(d);
 	free(blob);
 	if (status) { printf("\nNot an .nhwp file\n"); free(pix); return 3; }
-	nhw_dec_bmp_header(hdr);                                          /* the reference's 54 bytes, with the size fields of the picture */
-	hdr[2] = (uint8_t)(bytes + 54); hdr[3] = (uint8_t)((bytes + 54) >> 8); hdr[4] = (uint8_t)((bytes + 54) >> 16); hdr[5] = (uint8_t)((bytes + 54) >> 24);
-	hdr[18] = (uint8_t)width; hdr[19] = (uint8_t)(width >> 8); hdr[20] = (uint8_t)(width >> 16); hdr[21] = (uint8_t)(width >> 24);
-	hdr[22] = (uint8_t)height; hdr[23] = (uint8_t)(height >> 8); hdr[24] = (uint8_t)(height >> 16); hdr[25] = (uint8_t)(height >> 24);
-	hdr[34] = (uint8_t)bytes; hdr[35] = (uint8_t)(bytes >> 8); hdr[36] = (uint8_t)(bytes >> 16); hdr[37] = (uint8_t)(bytes >> 24);
+	bmp_header_sized(hdr, width, height, bytes);                      /* the reference's 54 bytes, with the size fields of the picture */
 	f = fopen(out_path, "wb");
 	if (!f) { printf("Failed to open output decompressed .bmp file %s\n", out_path); free(pix); return 1; }
 	fwrite(hdr, 54, 1, f);
@@ -324,6 +338,17 @@ static int decode_tar(const char *in_path, const char *out_path)
 int main(int argc, char **argv)
 {
 	int a;
+	for (a = 1; a < argc; a++)                                        /* --scale 1|2|4: anywhere; checked before any file is touched, then taken off the line */
+		if (!strncmp(argv[a], "--scale", 7)) {
+			int b;
+			if (strcmp(argv[a], "--scale") || a + 1 >= argc || strlen(argv[a + 1]) != 1 || !strchr("124", argv[a + 1][0])) { fprintf(stderr, "%s: --scale wants 1, 2 or 4\n", PROGRAM); return 1; }
+			g_scale = argv[a + 1][0] - '0';
+			for (b = 1; b < argc; b++) if (!strncmp(argv[b], "--region", 8)) { fprintf(stderr, "%s: --scale and --region do not go together\n", PROGRAM); return 1; }
+			if (argc > 3 && (!strcmp(argv[1], "--tar") || !strcmp(argv[1], "--tiles"))) { fprintf(stderr, "%s: --scale goes with a single file, --batch or --picture\n", PROGRAM); return 1; }
+			for (b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
+			argc -= 2;
+			break;
+		}
 	for (a = 1; a < argc; a++)                                        /* --region: behind --picture <in> <out> only, checked before any file is touched */
 		if (!strncmp(argv[a], "--region", 8)) {
 			uint32_t reg[4];
