@@ -709,7 +709,9 @@ DEV int vlc_parse_chunk(const uint8_t *g, int nwords, int c, int &start0, bool z
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 	__builtin_amdgcn_wave_barrier();
 	const int total_bits = (nwords - c * VCH_WORDS) * 32;           /* bits of the stream from the start of this chunk */
-	const int lo = 64 * lane, hi = min(64 * (lane + 1), total_bits);
+	/* THE OVERRUN RULE: a symbol is taken while it starts below bit (nwords + 2) * 32 of its stream -- the bits behind
+	 * the stream's end read 0 -- and a walk that needs one more than those is refused */
+	const int lo = 64 * lane, hi = min(64 * (lane + 1), total_bits + 64);
 	int start = lane ? lo : start0, exitp = 0, cnt = 0;
 	for (;;) {
 		int pos = start, n = 0, rk;
@@ -848,7 +850,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__rest
 	const int16_t *lv = level;
 	const uint8_t *g = f + (part ? m->o_packet2 : m->o_packet1);
 	const int nwords = part ? m->data2 - m->data1 : m->data1;
-	const int nchunks = (nwords + VCH_WORDS - 1) / VCH_WORDS + 1;       /* one more: zero bits behind the stream decode as words too, as in the reference */
+	const int nchunks = (nwords + VCH_WORDS - 1) / VCH_WORDS + 1;       /* one more: the 64 zero bits behind the stream that still decode (the overrun rule, vlc_parse_chunk) may lie in it */
 	int bad = 0, start0 = 0;
 	if (!part) {
 		/* The symbols leave as a list of (position in the stream, value) in stream order -- a q20 file has a few thousand values for its
@@ -864,7 +866,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__rest
 		int e = 0, t1 = 0, t2 = 0;
 		unsigned carry = (0u) | (3u << 9);                            /* nothing before the start: mem 0, no 254-run yet, e = 0, history zero */
 		bool done = false;
-		for (int c = 0; c < nchunks + 64 && !done; c++) {
+		for (int c = 0; c < nchunks && !done; c++) {
 			const int nsym = vlc_parse_chunk(g, nwords, c, start0, zoned, lut, lut2, cw, syms, lane, bad);
 			for (int base = 0; base < nsym && !done; base += 64) {
 				const bool have = base + lane < nsym;
@@ -918,7 +920,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__rest
 				}
 				if (e >= limit) done = true;
 			}
-			if (c >= nchunks - 1 && !done && (c + 1) * VCH_WORDS > nwords + 8) { bad = 1; break; }   /* ran out of stream before the last cell */
+			if (c == nchunks - 1 && !done) bad = 1;                       /* the overrun rule: no symbol left and the last cell not reached */
 		}
 		segment_index(ent, nE, 11, 128, ws.buf<uint32_t>(D_SEG, img), lane);   /* the strips of the luma stream: k_dec_expand follows each with a cursor */
 	} else {
@@ -927,7 +929,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__rest
 		const int limit = 2 * DQ - 2;
 		int e = 0;
 		bool done = false;
-		for (int c = 0; c < nchunks + 64 && !done; c++) {
+		for (int c = 0; c < nchunks && !done; c++) {
 			const int nsym = vlc_parse_chunk(g, nwords, c, start0, false, lut, lut2, cw, syms, lane, bad);
 			for (int base = 0; base < nsym && !done; base += 64) {
 				const bool have = base + lane < nsym;
@@ -949,7 +951,7 @@ __global__ __launch_bounds__(64) void k_dec_vlc(DecWs ws, const uint16_t *__rest
 				if (lm) { const int last = 63 - __builtin_clzll(lm); e += __builtin_amdgcn_readlane(pe, last); nE += __builtin_amdgcn_readlane(pw, last); }
 				if (e >= limit) done = true;
 			}
-			if (c >= nchunks - 1 && !done && (c + 1) * VCH_WORDS > nwords + 8) { bad = 1; break; }
+			if (c == nchunks - 1 && !done) bad = 1;
 		}
 		if (!lane) ws.buf<uint32_t>(D_SEG, img)[SEG_CHROMA + 128] = (uint32_t)nE;     /* k_dec_chroma takes its component's entries from the whole list */
 	}

@@ -122,7 +122,7 @@ static int ll_expand(const nhw_file *f, uint8_t *code, uint8_t *ll)
 	while (j < Q / 4) {
 		const int b = code[i];
 		if (b >= 128) {                                        /* verbatim sample, preceded by its fine byte when q>15 */
-			if (q > 15) PUSH(f->ll_word[a++]);
+			if (q > 15) { PUSH(a < f->ll_word_len ? f->ll_word[a] : 0); a++; }   /* behind its end the string reads 0 (the canonical model), not the section behind it */
 			PUSH((b - 128) << 1);
 		}
 		else if (mode == 0 || mode == 3) {                     /* :1665-1789 (3 never occurs; the reference would land here) */
