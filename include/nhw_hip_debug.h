@@ -49,6 +49,11 @@ int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes)
  * alone (synthesis, Y8, Y9 and, for q > 12 on the same LDS residency, the second analysis with Y13's copy); form 2: the staged kernels for
  * form 1's part; form 3: the staged kernels for form 0's part; form 4: form 3 stopped behind the synthesis; form 5: the staged synthesis alone. */
 int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream);
+/* The LL2 bump walk of the luma plane's second closed loop for the first n images of the handle's last whole batch, at that batch's quality
+ * (13 .. 23), on B_PROC, B_JPEG and B_L2SAVE as they stand: the LL2 emission, the LL coder and the second dequantiser simulation on one stream.
+ * form 0: the forked order's kernels (the emission makes the walk for both, the simulation skips it); form 1: the in-line order's (each makes
+ * it); forms 2, 3: the same two with the verbatim samples put back by the level-2 synthesis, which then follows. */
+int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream);
 
 /* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip, sized by dec_bytes there) */
 void nhw_dec_debug_stop_after(nhw_dec *d, int stage);

@@ -23,8 +23,9 @@ enum { EV_START, EV_FRONT, EV_LUMA, EV_CHROMA, EV_END, EV_COLOR, EV_PREFILTER, E
  * chroma stream is through, the position lists' fork and their end, the front group's end in front of the sub-batches.  With sub-batches
  * (NHW_PARTS > 1) the forks are off and slot k < 4 is sub-batch k's end instead. */
 enum { PE_LUMA_LIST, PE_CHROMA, PE_LISTS_FORK, PE_LISTS, PE_FRONT, PE_COUNT };
-/* ll_ev[]: the LL2 coder's fork beside the second dequantiser simulation, and its end */
-enum { LL_EV_FORK, LL_EV_DONE, LL_EV_COUNT };
+/* ll_ev[]: the LL2 coder's fork beside the second dequantiser simulation, and its end; Y5's fork onto the same stream beside the first
+ * simulation, and its end */
+enum { LL_EV_FORK, LL_EV_DONE, LL_EV_Y5_FORK, LL_EV_Y5_DONE, LL_EV_COUNT };
 
 struct nhw_enc {
 	int device, max_batch;
@@ -37,10 +38,12 @@ struct nhw_enc {
 	int low_parts;                /* how many (NHW_LOW_PARTS; 1 = the whole batch in line) */
 	int low_parts_used;           /* ... in the batch that is being queued */
 	int low_chroma;               /* quality 1..16: where the chroma sequence starts (NHW_LOW_CHROMA: 0 behind the front group, 1 behind the colour kernel, 2 behind the last sub-batch's pass A) */
-	hipStream_t ll_stream;        /* the LL2 coder (Y16) beside the second dequantiser simulation */
+	hipStream_t ll_stream;        /* the LL2 coder (Y16) beside the second dequantiser simulation; before that, Y5 beside the first */
 	hipEvent_t ll_ev[LL_EV_COUNT];
 	int ll_fork;
 	int quant_join;               /* the side streams join in front of the luma quantiser (q <= 21) */
+	int y5_fork;                  /* Y5 on ll_stream beside the first dequantiser simulation (NHW_Y5_FORK=0: in front of it on the luma stream) */
+	int ll2_once;                 /* q > 12: the LL2 bump walk in the emission only (NHW_LL2_ONCE=0: again in the second simulation) */
 	int parts;
 	hipEvent_t ev[EV_COUNT];
 	bool timed;

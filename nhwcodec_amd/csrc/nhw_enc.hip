@@ -99,6 +99,8 @@ extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_
 	e->lists_fork = env("NHW_LISTS_FORK", 1) != 0;
 	e->ll_fork = env("NHW_LL_FORK", 1) != 0;
 	e->quant_join = env("NHW_QUANT_JOIN", 1) != 0;
+	e->y5_fork = env("NHW_Y5_FORK", 1) != 0;
+	e->ll2_once = env("NHW_LL2_ONCE", 1) != 0;
 	*out = e;
 	return NHW_OK;
 }
@@ -185,7 +187,7 @@ static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hi
 
 /* the luma plane's launches from the first level-2 analysis to the second, on stream s (run_batch; nhw_stage_luma_loop).  1 = carry on;
  * NHW_OK: the debug stop fell in here */
-static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage)
+static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage, bool y5_beside = false /* run_batch's forked order */)
 {
 	const int q = ws.q;
 	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC), ll1 = ws.plane<int16_t>(B_LL1), l2save = ws.plane<int16_t>(B_L2SAVE);
@@ -195,8 +197,21 @@ static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s,
 	nhw_launch_analysis(l2.from(ll1, H), s);
 	STAGE_DONE();
 	if (q > 6) {                                                     /* first closed loop (:141-283) */
+	/* Y5 and the first dequantiser simulation need nothing of each other, and the first kernel that needs both is k_l2_recon (Y8 reads Y5's
+	 * tags, the synthesis the simulation's plane).  Y5 (luma_p1_par, tag_l2_details_par) reads proc and read-modify-writes ll1 (compatibility
+	 * mode: and clears the 512 cells behind ll1); it never touches jpeg.  The simulation (wave_dequant_sim_luma, part 1) reads proc and
+	 * writes jpeg; it never touches ll1, and it writes proc only with keep_p, which is ws.dbg: the stage checks, which do not come here
+	 * (the forked order has no debug stop).  So in the forked order Y5 runs on the LL coder's stream, idle until Y16, beside the simulation. */
+	if (y5_beside) {
+		assert(!ws.dbg);
+		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_Y5_FORK], s));
+		HIPCHK(hipStreamWaitEvent(e->ll_stream, e->ll_ev[LL_EV_Y5_FORK], 0));
+		nhw_launch_phase(PH_L1, ws, 0, e->ll_stream);
+		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_Y5_DONE], e->ll_stream));
+	} else
 	nhw_launch_phase(PH_L1, ws, 0, s);
 	nhw_launch_wave(WV_DQ1, ws, s);          /* every quality (1..16: rationed low bits, no marking passes) */
+	if (y5_beside) HIPCHK(hipStreamWaitEvent(s, e->ll_ev[LL_EV_Y5_DONE], 0));   /* (Y16's later fork onto that stream is behind Y5 by stream order) */
 	STAGE_DONE();
 	if (ws.dbg) {
 	nhw_launch_synthesis(jpeg, proc, n, W, H, 0, s);
@@ -282,13 +297,14 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		CHROMA(chroma_head(0));
 		CHROMA(chroma_head(1));                                      /* V's head in planes of its own, right behind U's: U's quantiser waits for the luma tail, and this stream stood idle until then (2 ms of a q20 step).  (Measured and not taken: V's head on a stream of its own beside U's, +0.3 ms; V's head held back until the second dequantiser simulation is through, +0.4 ms.) */
 	}
-	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12) */
+	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage, fork && e->y5_fork); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12) */
 	if (q <= 12) {                                                   /* Y11 (q <= 11), Y12, then Y13 */
 		nhw_launch_low_ll2(proc, q, n, s);
 		nhw_launch_copy_block(proc, W, ws.plane<int16_t>(B_L2SAVE), H, H, H, n, s);
 	}
 	STAGE_DONE();
-	nhw_launch_wave(WV_EMIT, ws, s);                                 /* Y14, Y15 */
+	const bool one_walk = fork && q > 12 && e->ll2_once;             /* the LL2 bump walk once, in the emission: the second simulation finds its cells made (wave_emit_ll2) */
+	nhw_launch_wave(WV_EMIT, ws, s, one_walk);                       /* Y14, Y15 */
 	/* Y16, the LL2 coder, is a latency-bound parse (0.6 ms at 0.3 TB/s) in front of the vector-bound dequantiser simulation, which only wants its
 	 * list of verbatim samples -- at its very end, to put them back into the block.  Production: the coder runs beside the simulation on a
 	 * stream of its own and the synthesis behind both does the putting back (ws.defer_verbatim).  Not in the compatibility mode and not
@@ -304,7 +320,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	if (fork) HIPCHK(hipEventRecord(e->part_ev[PE_LUMA_LIST], s));              /* exception list of the luma plane complete */
 	}
 	if (q > 12) {                                                    /* second closed loop (:759-779) */
-	nhw_launch_wave(WV_DQ0, ws, s);
+	nhw_launch_wave(WV_DQ0, ws, s, one_walk);
 	STAGE_DONE();
 	if (fork_ll) {
 		HIPCHK(hipStreamWaitEvent(s, e->ll_ev[LL_EV_DONE], 0));               /* (the coder is long done: the simulation takes twice its time) */
@@ -629,6 +645,36 @@ extern "C" int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream)
 			nhw_launch_phase(PH_L2, ws, 0, s);
 			nhw_launch_analysis(save ? l2.saving(l2save, H, ANA_SAVE_BLOCK) : l2, s);
 		}
+	}
+	HIPCHK(hipGetLastError());
+	return NHW_OK;
+}
+
+/* A test hook for the LL2 bump walk of the second closed loop, on B_PROC, B_JPEG and B_L2SAVE as they stand (a test writes them), for the first n
+ * images of the handle's last whole batch at that batch's quality (13 .. 23), on one stream: the emission (Y14, Y15), the LL coder (Y16) and the
+ * second dequantiser simulation.
+ *   form 0: the forked order's kernels -- the emission makes the walk and leaves the simulation's LL2 cells, the simulation skips it;
+ *   form 1: the in-line order's -- the emission leaves zeros, the simulation makes the walk again;
+ *   forms 2, 3: forms 0, 1 with the put-back of verbatim samples left to the level-2 synthesis, which follows (ws.defer_verbatim). */
+extern "C" int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream)
+{
+	if (!e || n < 1 || n > e->max_batch || form < 0 || form > 3) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after || e->last_q < 13) {
+		nhw_enc_err = "nhw_stage_ll2_walk: needs a completed whole batch of >= n images at quality >= 13 and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = 0; ws.defer_verbatim = form >= 2;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	const bool one_walk = !(form & 1);
+	nhw_launch_wave(WV_EMIT, ws, s, one_walk);
+	nhw_launch_phase(PH_L3, ws, 0, s);
+	nhw_launch_wave(WV_DQ0, ws, s, one_walk);
+	if (ws.defer_verbatim) {
+		const Plane<const uint8_t> meta = ws.plane<const uint8_t>(B_META), len{ meta.p + offsetof(NhwMeta, ll_mem_len), meta.pitch };
+		nhw_launch_synthesis(ws.plane<int16_t>(B_JPEG), ws.plane<int16_t>(B_PROC), n, W, H, ws.q <= 21, ws.plane<const uint8_t>(B_LLMEM), len, s);
 	}
 	HIPCHK(hipGetLastError());
 	return NHW_OK;

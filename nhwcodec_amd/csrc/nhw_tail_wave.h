@@ -143,6 +143,19 @@ DEV void ll2_load_row(const int16_t *p, int r, int lane, int *v, M4 *tag, int q,
 	*tag = t;
 }
 
+/* samples the LL coder sent verbatim keep their exact value (:2728-2735): behind the walk of the second loop, from the work plane's unrounded
+ * values.  Production: the synthesis behind the simulation does it (k_dwt_syn, ws.defer_verbatim), the coder runs beside that kernel. */
+DEV void wave_ll2_verbatim(Ctx *c, int lane)
+{
+	if (c->defer_verbatim) return;
+	__threadfence_block();
+	const int nm = c->m->ll_mem_len;
+	for (int i = lane; i < nm; i += 64) {
+		const int idx = c->ll_mem[i], pos = ((idx >> 7) << 9) + (idx & 127);
+		c->jpeg[pos] = c->proc[pos];
+	}
+}
+
 DEV void wave_ll2(Ctx *c, int part, int lane, bool keep_p, const int16_t *src, int ss /* where the rows are read: the work plane (pitch W), or -- second closed loop, production -- the level-2 block's copy l2save (pitch H): Y17 (nhw_encoder.c:749-755) restored the block into the work plane for this reader alone */)
 {
 	int16_t *p = c->proc, *jp = c->jpeg;
@@ -184,23 +197,32 @@ DEV void wave_ll2(Ctx *c, int part, int lane, bool keep_p, const int16_t *src, i
 		for (int k = 0; k < 3; k++) { v0[k] = v1[k]; v1[k] = v2[k]; v2[k] = v3[k]; v3[k] = vn[k]; }
 		t0 = t1; t1 = t2; t2 = t3; t3 = tn;
 	}
-	if (!part && !c->defer_verbatim) {                             /* samples the LL coder sent verbatim keep their exact value (:2728-2735); production: the synthesis behind this pass does it (k_dwt_syn), the coder runs beside this kernel */
-		__threadfence_block();
-		const int nm = c->m->ll_mem_len;
-		for (int i = lane; i < nm; i += 64) {
-			const int idx = c->ll_mem[i], pos = ((idx >> 7) << 9) + (idx & 127);
-			jp[pos] = p[pos];
-		}
-	}
+	if (!part) wave_ll2_verbatim(c, lane);
 	__threadfence_block();
 }
 
 /* Y14 + Y15 (nhw_encoder.c:640-741): tag the runs of four odd LL2 samples (their first columns go to the res4 list),
  * the same bump walk as above, and the emission of the samples as bytes: a sample outside 0..255 goes to the
- * exception list and repeats the byte before it in the stream.  The band is left zero. */
-DEV void wave_emit_ll2(Ctx *c, int lane)
+ * exception list and repeats the byte before it in the stream.  The band is left zero.
+ *
+ * sim (the forked order of quality 13 and up, run_batch): the walk of the second dequantiser simulation, wave_ll2(part 0), is this walk once
+ * more -- the same 128 x 128 samples (k_l2_recon<true> stores one register to the work plane, read here, and to l2save, read there), the same
+ * tags (ll2_load_row, part 0), ballots, alt_runs and increments in the same order (bumped into v0, vf into v1), so v0 at the row's end is the
+ * value that walk stores.  This pass then leaves what that one leaves, cell for cell: the work plane gets v0 where it got 0, the
+ * reconstruction plane gets tagged ? v0 : ll2_round(v0), and k_wave<WV_DQ0> skips its walk (wave_dequant_sim_luma).
+ *   * Nothing between this kernel and the simulation touches the LL2 quadrant of either plane.  On the luma stream and the coder's side
+ *     stream there is only Y16, luma_p3_par: it reads ll_bytes, ll_full, l2save and the stale-heap bytes and writes ll_bytes' tail, the coder's
+ *     output, the meta words and (compatibility mode) the cells behind ll1 and l2save; its copy of l2save into the work plane (Y17) is made for
+ *     quality <= 12 and the stage checks only.  That holds where Y16 runs in line on the luma stream as well -- quality 13, the compatibility
+ *     mode and NHW_LL_FORK=0 with the fork on: sim is on there too, and the put-back of verbatim samples that k_wave<WV_DQ0> then makes
+ *     itself (wave_ll2_verbatim) reads this kernel's v0 from the work plane.  The chroma stream's kernels run beside the simulation's own stores to these cells today, in
+ *     either order, and work in the chroma planes.
+ *   * The zeros have no reader once the simulation follows: its part 0 overwrites every one of them with v0 before anything else looks (the
+ *     readers of the quadrant -- the in-kernel put-back of verbatim samples, k_dwt_syn, wave_shrink's column 127 -- come behind that store and
+ *     find the same v0 here).  Quality <= 12 has no second simulation; there the zeros are what Y19 onwards reads and sim stays false. */
+DEV void wave_emit_ll2(Ctx *c, int lane, bool sim)
 {
-	int16_t *p = c->proc;
+	int16_t *p = c->proc, *jp = c->jpeg;
 	const int q = c->q;
 	int v0[3], v1[3], v2[3], v3[3];
 	M4 t0, t1, t2, t3, s0, s1, s2, s3;
@@ -255,7 +277,8 @@ DEV void wave_emit_ll2(Ctx *c, int lane)
 				ex[0] = (uint8_t)r; ex[1] = (uint8_t)(col + (s > 255 ? 128 : 0)); ex[2] = (uint8_t)(mag > 255 ? 255 : mag);
 				c->ll_bytes[a] = (uint8_t)prev; c->ll_full[a] = (uint8_t)prev;
 			} else { c->ll_full[a] = (uint8_t)byte[k]; c->ll_bytes[a] = (uint8_t)(byte[k] & 254); }
-			p[r * W + col] = 0;
+			p[r * W + col] = (int16_t)(sim ? v0[k] : 0);
+			if (sim) jp[r * W + col] = (int16_t)(TB(t0, k) ? v0[k] : ll2_round(v0[k]));
 		}
 		e += 3 * (__popcll(x[0]) + __popcll(x[1]));
 		if (g[1]) carry = __shfl(byte[1], 63 - __builtin_clzll(g[1])) & 254;
@@ -942,12 +965,15 @@ DEV void wave_quantise_luma(Ctx *c, int lane, uint8_t *park /* 16 x QROW bytes o
 /* keep_p: the marked coefficients go back into the work plane as the reference's in-place pass leaves them.  Nothing reads them there -- the
  * synthesis that follows reads the dequantised plane, and the next analysis (first loop) or that synthesis (second loop) rewrites the whole
  * block -- so production leaves these 128 KB per image and loop out; the stage checks compare the plane and keep them. */
-DEV void wave_dequant_sim_luma(Ctx *c, int part, int lane, const uint32_t *lut, bool from_save, bool keep_p)
+/* ll2_done (second loop, the forked order): the emission in front of this kernel has left the LL2 cells of both planes (wave_emit_ll2, sim);
+ * only the put-back of verbatim samples is left of the walk, where the synthesis behind this kernel does not make it */
+DEV void wave_dequant_sim_luma(Ctx *c, int part, int lane, const uint32_t *lut, bool from_save, bool keep_p, bool ll2_done = false)
 {
 	PROF_BEGIN();
 	const int16_t *src = from_save ? c->l2save : c->proc;
 	const int ss = from_save ? H : W;
-	wave_ll2(c, part, lane, keep_p, src, ss);
+	if (ll2_done) wave_ll2_verbatim(c, lane);
+	else wave_ll2(c, part, lane, keep_p, src, ss);
 	wave_dequant_details(c, part, lane, lut, keep_p, src, ss);
 	if (!part) wave_shrink(c, lane);
 	if (!lane) PROF(c, part ? 1 : 7);
