@@ -22,7 +22,7 @@ struct nhw_dec {
 	uint16_t *vlc_table;         /* the prefix code's two-level lookup table (k_dec_vlc_table), 2.5 KB */
 	int chroma_fork;
 	int stop_after;
-	bool l1_moved;               /* the last batch ran level 2 of the luma whole: the level-1 LL is in plane_l1 (D_B), not plane A (nhw_dec_debug_read) */
+	bool l1_moved;               /* the last batch ran k_dec_luma_l2q (any stage of it): what it made of plane A's block is in plane_l1 (D_B) (nhw_dec_debug_read) */
 	int slice_order;             /* debug: the forced slice order of the kernels that split a file (nhw_host.h; 0 = production) */
 	hipEvent_t ev[4];         /* start, after the entropy stages, around the final reconstruction kernel (= end) */
 	bool timed;

@@ -12,7 +12,7 @@
  *                  short-state chain for the placement rules; it leaves lists of (position, value), stream order
  *   k_dec_expand   pattern symbols -> coefficients, the +-1 nudge of the HH band, LL2 samples, odd-LL tags,
  *                  exception samples: one wavefront per image, the rows streaming through LDS in order
- *   k_dec_luma_l2  level 2 of the luma on one LDS residency of the block: shrink, synthesis both ways, residual lists
+ *   k_dec_luma_l2q level 2 of the luma on one LDS residency of a quarter of the block: shrink, synthesis both ways, residual lists
  *   k_dec_chroma   a chroma plane on one LDS residency: built from the value list, LL2 + exception samples, level 2, pair
  *                  corrections, level 1
  *   k_dec_marks, k_dec_sharpen
@@ -1398,13 +1398,13 @@ DEV void add_i16_at(int16_t *base, int idx, int delta)
  */
 /* Both directions of a level run on one LDS residency of the block: filtered along the rows in place (a wavefront owns a row: it has read
  * it before it writes it), then along the columns, and column c of the result is row c of the plane -- the transposed orientation the
- * reference's transposes leave behind and everything downstream expects.  The plane in between never travels.  The block kernels below
- * (k_dec_luma_l2, k_dec_chroma) fill a CU's LDS with one 1024-thread workgroup, which therefore works through several blocks. */
+ * reference's transposes leave behind and everything downstream expects.  The plane in between never travels.  The block kernel below
+ * (k_dec_chroma) fills a CU's LDS with one 1024-thread workgroup, which therefore works through several blocks. */
 /* (lds_barrier, syn_pair, syn_taps: nhw_dwt.h, the encoder's own.)  The two in-place passes of a block at `pitch` shorts a row, a wavefront's share of them: */
-template <int S, int ROWS, int UNROLL> DEV void syn_rows_inplace(int16_t *x0, int pitch, int lane)        /* ROWS rows from x0 on, along the row, un-normalised: sample pair k goes back as dword k; UNROLL: of the loop over the rows */
+template <int S, int ROWS> DEV void syn_rows_inplace(int16_t *x0, int pitch, int lane)        /* ROWS rows from x0 on, along the row, un-normalised: sample pair k goes back as dword k (k_dec_chroma wants the loop over the rows rolled) */
 {
 	constexpr int PPL = S / 128;
-#pragma unroll UNROLL
+#pragma unroll 1
 	for (int i = 0; i < ROWS; i++) {
 		int16_t *x = x0 + i * pitch;
 		int e[PPL], o[PPL];
@@ -1428,7 +1428,7 @@ template <int S, int COLS> DEV void syn_cols_inplace(int16_t *x0, int pitch, int
 	}
 }
 
-/* The residual lists of level 2 (nhw_decoder.c:731-787), which both level-2 kernels add onto the level-1 LL: list r = 0, 1, 2 (res5, res1, res3) is open from a
+/* The residual lists of level 2 (nhw_decoder.c:731-787), which k_dec_luma_l2q adds onto the level-1 LL: list r = 0, 1, 2 (res5, res1, res3) is open from a
  * quality on (cnt = 0 below it) and holds cnt positions (row << 8 | column, D_P5 / D_P1 / D_P3) with a byte string that says what each adds. */
 struct ResList { const uint16_t *pos; const uint8_t *bits; int cnt, nbytes /* of `bits`; bytes behind them read 0 */, per_byte /* log2 of the entries a byte describes */, amp; };
 DEV ResList res_list(int r, const DecWs &ws, int img, const DecMeta *m)
@@ -1460,130 +1460,23 @@ template <class Acc> DEV void res_apply(const ResList &L, int k, int ps, int byt
  *             quadrant whose |v| > 8 moves one towards zero unless a neighbour is loud -- |v| > 8 for the four beside, above and below it, |v| > diag (16
  *             up to quality 16, else 8) for the four diagonal ones.  It is a stencil on the values as they were: a cell that shrinks cannot have a
  *             neighbour that does, but its new value would read differently to that neighbour, so all decisions are taken before any is applied.
- *             Both kernels make "loud" one compare per cell into bit masks and the rule mask algebra; they differ in who holds which mask;
- *   synthesis both directions, in place (see k_dec_synth2d): afterwards LDS holds sample (row c, column j) of the level-1 LL, in the
- *             transposed orientation the plane keeps, at [j][c];
+ *             "Loud" is one compare per cell into bit masks, and the rule is mask algebra;
+ *   synthesis both directions, in place: afterwards LDS holds sample (row c, column j) of the level-1 LL, in the transposed orientation the
+ *             plane keeps, at [j][c];
  *   residuals the three residual lists onto it (:731-787): positions repeat, the steps commute: compare-and-swap adds on the LDS words;
- * then column c of the LDS block leaves as row c of the plane.  Before: three kernels, each a round trip of the block (and the residual
- * kernel read every list eight times, once per band of rows).  `upto`: the debug stop (1: write the block back after the shrink, 2: after
- * the synthesis; 3: everything). */
-__global__ __launch_bounds__(1024) void k_dec_luma_l2(DecWs ws, int items, int upto)
-{
-	extern __shared__ __attribute__((aligned(16))) int16_t smem[];
-	constexpr int S = DH, LS = S + 2, HLF = S / 2, PPL = HLF / 64, NT_ = 1024, NPRE = S * (S / 8) / NT_;
-	const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-	uint4 pre[NPRE];
-	if ((int)blockIdx.x < items) {
-		const int16_t *src = plane_a(ws, blockIdx.x);
-#pragma unroll
-		for (int u = 0; u < NPRE; u++) { const int v = t + u * NT_; pre[u] = *reinterpret_cast<const uint4 *>(src + (size_t)(v / (S / 8)) * DW + 8 * (v % (S / 8))); }
-	}
-	for (int img = blockIdx.x; img < items; img += gridDim.x) {
-		int16_t *pl = plane_a(ws, img);
-		const DecMeta *m = ws.buf<DecMeta>(D_META, img);
-		const bool skip = m->status != 0;
-		const int q = m->q;
-#pragma unroll
-		for (int u = 0; u < NPRE; u++) {
-			const int v = t + u * NT_, row = v / (S / 8), o = v % (S / 8);
-			uint32_t *d = reinterpret_cast<uint32_t *>(smem + row * LS + 8 * o);
-			d[0] = pre[u].x; d[1] = pre[u].y; d[2] = pre[u].z; d[3] = pre[u].w;
-		}
-		lds_barrier();
-		if (img + (int)gridDim.x < items) {
-			const int16_t *src = plane_a(ws, img + gridDim.x);
-#pragma unroll
-			for (int u = 0; u < NPRE; u++) { const int v = t + u * NT_; pre[u] = *reinterpret_cast<const uint4 *>(src + (size_t)(v / (S / 8)) * DW + 8 * (v % (S / 8))); }
-		}
-		{
-			/* shrink (the 3 x 3 rule above): a wavefront takes 16 rows, its lanes the columns (lane + 64k).  A row's loud masks come from ballots, the
-			 * rule runs on the three rows around a cell (the scalar unit's work, 256 columns at a time), and a lane only keeps its own 4 x 16
-			 * verdicts, as bits, until every wavefront has taken its decisions. */
-			const int diag = q <= 16 ? 16 : 8, i_first = 16 * wv;
-			auto loud = [&](int r, Mask4 &m8, Mask4 &md) {
-#pragma unroll
-				for (int k = 0; k < 4; k++) {
-					const int a = r >= 0 && r < S ? iabs((int)smem[r * LS + lane + 64 * k]) : 0;
-					m8.w[k] = __ballot(a > 8); md.w[k] = __ballot(a > diag);
-				}
-			};
-			Mask4 p8, pd, c8, cd, n8, nd;
-			loud(i_first - 1, p8, pd); loud(i_first, c8, cd);
-			unsigned hb0 = 0, hb1 = 0;                               /* rows 0..7, 8..15 of mine: four bits a row */
-#pragma unroll 1
-			for (int t = 0; t < 16; t++) {
-				const int i = i_first + t;
-				loud(i + 1, n8, nd);
-				Mask4 h;
-				const Mask4 c8l = m4_prev(c8), c8r = m4_next(c8), pdl = m4_prev(pd), pdr = m4_next(pd), ndl = m4_prev(nd), ndr = m4_next(nd);
-#pragma unroll
-				for (int k = 0; k < 4; k++) h.w[k] = c8.w[k] & ~(c8l.w[k] | c8r.w[k] | p8.w[k] | n8.w[k] | pdl.w[k] | pdr.w[k] | ndl.w[k] | ndr.w[k]);
-				h.w[0] &= ~1ull; h.w[3] &= ~(1ull << 63);                 /* columns 1 .. 254 */
-				if (i < HLF) { h.w[0] = 0; h.w[1] = 0; }                  /* not the LL2 quadrant */
-				if (i < 1 || i > S - 2) { h.w[0] = h.w[1] = h.w[2] = h.w[3] = 0; }
-				unsigned nib = 0;
-#pragma unroll
-				for (int k = 0; k < 4; k++) nib |= (unsigned)m4_bit(h, k, lane) << k;
-				if (t < 8) hb0 |= nib << (4 * t); else hb1 |= nib << (4 * t - 32);
-				p8 = c8; pd = cd; c8 = n8; cd = nd;
-			}
-			lds_barrier();
-			for (int half = 0; half < 2; half++) {
-				unsigned hb = half ? hb1 : hb0;
-				while (hb) {
-					const int b = __builtin_ctz(hb);
-					hb &= hb - 1;
-					int16_t *cell = smem + (i_first + 8 * half + (b >> 2)) * LS + lane + 64 * (b & 3);
-					*cell = (int16_t)(*cell > 0 ? *cell - 1 : *cell + 1);
-				}
-			}
-			lds_barrier();
-		}
-		if (upto == 1) {
-			if (!skip)
-				for (int v = t; v < S * (S / 8); v += NT_) {
-					const int row = v / (S / 8), o = v % (S / 8);
-					const uint32_t *d = reinterpret_cast<const uint32_t *>(smem + row * LS + 8 * o);
-					*reinterpret_cast<uint4 *>(pl + (size_t)row * DW + 8 * o) = make_uint4(d[0], d[1], d[2], d[3]);
-				}
-			lds_barrier();
-			continue;
-		}
-		syn_rows_inplace<S, 16, 16>(smem + wv * 16 * LS, LS, lane);          /* (unrolled, as this loop has always compiled; k_dec_chroma asks for its loops rolled) */
-		lds_barrier();
-		syn_cols_inplace<S, 16>(smem + wv * 16, LS, lane);           /* sample 2k, 2k+1 of column c */
-		lds_barrier();
-		if (upto >= 3 && !skip) {                                    /* residual lists: plane cell (row, col) sits at [col][row] */
-#pragma unroll
-			for (int r = 0; r < 3; r++) {
-				const ResList L = res_list(r, ws, img, m);
-				for (int k = t; k < L.cnt; k += NT_) res_apply(L, k, L.pos[k], res_byte(L, k), [&](int row, int col, int d) { add_i16_at(smem, col * LS + row, d); });
-			}
-		}
-		lds_barrier();
-		if (!skip)
-		for (int i = 0; i < 16; i++) {                               /* column c of the block is row c of the plane (the whole pass: of plane_l1) */
-			const int c = wv * 16 + i;
-			uint32_t *dst = reinterpret_cast<uint32_t *>((upto >= 3 ? plane_l1(ws, img) : pl) + (size_t)c * DW);
-#pragma unroll
-			for (int u = 0; u < PPL; u++) {
-				const int k = lane + 64 * u;
-				dst[k] = (uint32_t)(uint16_t)smem[(2 * k) * LS + c] | ((uint32_t)(uint16_t)smem[(2 * k + 1) * LS + c] << 16);
-			}
-		}
-		lds_barrier();                                               /* the block is done with before the next one moves in */
-	}
-}
-
-/* The same three passes, a QUARTER of the block to a 256-thread workgroup (production; the debug stops keep k_dec_luma_l2): quarter p owns the
- * 64 columns 64 p .. 64 p + 63 of the row pass's result = rows 64 p .. of the plane.  Its row pass reads, of every row, the low-band cells
- * 32 p .. 32 p + 32 and the high-band cells 32 p - 1 .. 32 p + 32; the shrink before it looks one cell further: two windows of 36 cells a row
- * (dword-aligned: block columns 32 p - 2 .. and 126 + 32 p ..), 38 KB of LDS, four workgroups a CU -- whose load, filter and store phases
- * overlap where the 1024-thread block kernel's follow one another (0.71 ms for 1.3 GB).  Each quarter takes the shrink's decisions for the cells
- * it reads (from the values as they were, all before any is applied), filters in place, adds the residuals whose plane row is its own and
- * writes 64 whole rows of the plane.  Block b -> file ((b >> 5) << 3) | (b & 7), quarter (b >> 3) & 3 (a file's quarters on one XCD). */
+ * then column c of the LDS tile leaves as row c of the plane.  Before: three kernels, each a round trip of the block (and the residual
+ * kernel read every list eight times, once per band of rows).
+ * A QUARTER of the block to a 256-thread workgroup: quarter p owns the 64 columns 64 p .. 64 p + 63 of the row pass's result = rows 64 p ..
+ * of the plane.  Its row pass reads, of every row, the low-band cells 32 p .. 32 p + 32 and the high-band cells 32 p - 1 .. 32 p + 32; the
+ * shrink before it looks one cell further: two windows of 36 cells a row (dword-aligned: block columns 32 p - 2 .. and 126 + 32 p ..), 38 KB
+ * of LDS, four workgroups a CU, whose load, filter and store phases overlap.  Each quarter takes the shrink's decisions for the cells it
+ * reads (from the values as they were, all before any is applied), filters in place, adds the residuals whose plane row is its own and
+ * writes 64 whole rows of the plane.  Block b -> file ((b >> 5) << 3) | (b & 7), quarter (b >> 3) & 3 (a file's quarters on one XCD).
+ * UPTO: 3 is production; 1 and 2 are the debug stops (1: the block as the shrink leaves it, 2: after the synthesis).  Every one of them
+ * writes to plane_l1, never to plane A, which another quarter of the file may still be loading its windows from (nhw_dec_debug_read shows
+ * the block in its place). */
 #define LQ_LS 74                      /* pitch of a row of the tile in shorts (37 dwords: column walks on 32 banks) */
-__global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int slice /* -1: production; else the quarter (nhw_host.h) */)
+template <int UPTO> __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int slice /* -1: production; else the quarter (nhw_host.h) */)
 {
 	__shared__ __attribute__((aligned(16))) int16_t T[DH * LQ_LS];
 	constexpr int S = DH, HLF = S / 2;
@@ -1613,7 +1506,7 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int s
 	}
 	lds_barrier();
 	{
-		/* shrink (the 3 x 3 rule above k_dec_luma_l2): a lane a ROW (row 64 wv + lane; the tile's pitch of 37 dwords puts 64 rows on different banks): it sorts
+		/* shrink (the 3 x 3 rule above): a lane a ROW (row 64 wv + lane; the tile's pitch of 37 dwords puts 64 rows on different banks): it sorts
 		 * its row's 72 cells into loud masks (a bit a cell of either window), takes the masks of the rows above and below from its neighbour lanes (the
 		 * wavefront's first and last row: from the next wavefront, through LDS), and the rule runs in registers.  Nothing is applied before every
 		 * wavefront has read its rows. */
@@ -1666,6 +1559,14 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int s
 		}
 		lds_barrier();
 	}
+	if constexpr (UPTO == 1) {                                       /* the cells the quarter owns, x = 2 .. 33 of either window (dwords 1 .. 16): block columns 32 p .. and 128 + 32 p .., all rows */
+		int16_t *l1 = plane_l1(ws, img);
+		for (int idx = t; idx < S * 32; idx += 256) {
+			const int row = idx >> 5, w = (idx >> 4) & 1, d = 1 + (idx & 15);
+			*reinterpret_cast<uint32_t *>(l1 + (size_t)row * DW + (w ? a_hi : a_lo) + 2 * d) = reinterpret_cast<const uint32_t *>(T)[row * (LQ_LS / 2) + 18 * w + d];
+		}
+		return;
+	}
 	{                                                                /* along the rows, un-normalised: half a wavefront a row, a lane the outputs 2 k, 2 k + 1 of k = 32 p + (lane & 31) */
 		const int rsub = lane >> 5, kk = lane & 31, k = 32 * p + kk;
 #pragma unroll 2
@@ -1691,7 +1592,7 @@ __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs ws, int items, int s
 		for (int u = 0; u < 2; u++) { const int k = lane + 64 * u; x[(2 * k) * LQ_LS] = (int16_t)e[u]; x[(2 * k + 1) * LQ_LS] = (int16_t)o[u]; }
 	}
 	lds_barrier();
-	{                                                                /* residual lists (:731-787): plane cell (row, col) sits at [col][row - 64 p]; a quarter takes the cells of its own plane rows */
+	if constexpr (UPTO == 3) {                                       /* residual lists (:731-787): plane cell (row, col) sits at [col][row - 64 p]; a quarter takes the cells of its own plane rows */
 		/* a thread's entries of a list eight at a time: their loads (the entry, the byte that describes it) go out together, then the adds */
 #pragma unroll
 		for (int r = 0; r < 3; r++) {
@@ -1781,7 +1682,7 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 			}
 		};
 		if (upto == 1) { store_block(false); lds_barrier(); continue; }
-		syn_rows_inplace<HLF, 8, 1>(smem + wv * 8 * LS, LS, lane);      /* level 2 on the corner */
+		syn_rows_inplace<HLF, 8>(smem + wv * 8 * LS, LS, lane);      /* level 2 on the corner */
 		lds_barrier();
 		syn_cols_inplace<HLF, 8>(smem + wv * 8, LS, lane);
 		lds_barrier();
@@ -1818,7 +1719,7 @@ __global__ __launch_bounds__(1024) void k_dec_chroma(DecWs ws, int items, int up
 			lds_barrier();
 			continue;
 		}
-		syn_rows_inplace<S, 16, 1>(smem + wv * 16 * LS, LS, lane);      /* level 1 */
+		syn_rows_inplace<S, 16>(smem + wv * 16 * LS, LS, lane);      /* level 1 */
 		lds_barrier();
 #pragma unroll 1
 		for (int i = 0; i < 16; i++) {                               /* along the columns, normalised: column c is row c of the plane */
@@ -1840,8 +1741,7 @@ static int synth2d_attrs()
 {
 	int rc = NHW_OK;                                               /* per device: every handle sets it for its own */
 	const int big = 256 * 258 * (int)sizeof(int16_t);
-	if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_chroma), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
-	    hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_luma_l2), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess) rc = NHW_E_HIP;
+	if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_chroma), hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess) rc = NHW_E_HIP;
 	return rc;
 }
 
@@ -2521,7 +2421,7 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 	HIPCHK(hipSetDevice(d->device));
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipMemcpy(dst, ws.buf<uint8_t>(what, img), bytes, hipMemcpyDeviceToHost));
-	if (what == D_A && d->l1_moved)                                 /* plane A as the stage checks know it: with the level-1 LL where the reference keeps it */
+	if (what == D_A && d->l1_moved)                                 /* plane A as the stage checks know it: with the level-2 kernel's block where the reference keeps it */
 		for (int r = 0; r < DH && 4096 + (size_t)r * DW * 2 < bytes; r++) {
 			const size_t at = 4096 + (size_t)r * DW * 2, len = bytes - at < (size_t)DH * 2 ? bytes - at : (size_t)DH * 2;
 			HIPCHK(hipMemcpy((uint8_t *)dst + at, ws.buf<uint8_t>(D_B, img) + at, len, hipMemcpyDeviceToHost));
@@ -2584,12 +2484,10 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 	else if (d->stop_after == 3) CHROMA(1, s);                                    /* the chroma planes as the expansion leaves them */
 	STAGE_END();                                                                  /* 3 */
 	{
-		/* level 2 of the luma: shrink, synthesis, residual lists on A's top-left 256 x 256 -> the level-1 LL in the same place */
-		const int upto = d->stop_after == 4 ? 1 : d->stop_after == 5 ? 2 : 3;
-		static const int quarters = getenv("NHW_DEC_L2Q") ? atoi(getenv("NHW_DEC_L2Q")) : 1;
-		if (upto == 3 && quarters) nhw_slices(4, [&](int sl) { k_dec_luma_l2q<<<sl < 0 ? 4 * ((n + 7) & ~7) : n, 256, 0, s>>>(ws, n, sl); });
-		else k_dec_luma_l2<<<n < SYNTH_WGS ? n : SYNTH_WGS, 1024, 256 * 258 * sizeof(int16_t), s>>>(ws, n, upto);
-		d->l1_moved = upto == 3;
+		/* level 2 of the luma: shrink, synthesis, residual lists on A's top-left 256 x 256 -> the level-1 LL in plane_l1; the debug stops 4 and 5 end it earlier */
+		const auto l2q = d->stop_after == 4 ? k_dec_luma_l2q<1> : d->stop_after == 5 ? k_dec_luma_l2q<2> : k_dec_luma_l2q<3>;
+		nhw_slices(4, [&](int sl) { l2q<<<sl < 0 ? 4 * ((n + 7) & ~7) : n, 256, 0, s>>>(ws, n, sl); });
+		d->l1_moved = true;
 	}
 	STAGE_END();                                                                  /* 4 (the block as the shrink leaves it) */
 	STAGE_END();                                                                  /* 5 (after the synthesis) */

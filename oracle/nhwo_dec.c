@@ -23,7 +23,7 @@
 
 static inline int iabs(int v) { return v < 0 ? -v : v; }
 
-/* checkpoint probe (tools/dev/gpu_dec_debug.py): copy one intermediate buffer out of the next decode */
+/* checkpoint probe (tests/test_decode_stages.py): copy one intermediate buffer out of the next decode */
 static struct { int id; void *dst; size_t cap, got; } g_probe;
 void nhwo_dec_probe(int id, void *dst, size_t cap) { g_probe.id = id; g_probe.dst = dst; g_probe.cap = cap; g_probe.got = 0; }
 size_t nhwo_dec_probe_len(void) { return g_probe.got; }
@@ -589,11 +589,13 @@ static int decode_luma(dctx *d, uint8_t *ybytes)
 		for (k = 0; k < cnt; k++) if (bit_of(f->res5_word, f->res5_bits, k)) b[AT(p5[k])] -= 3;
 		for (k = 0; k < cnt; k++) if (!bit_of(f->res5_word, f->res5_bits, k)) b[AT(p5[k])] += 3;
 	}
+	probe(50, b, 4 * Q * 2);                                      /* (between the lists: what each of them changed) */
 	if (q > 12) {
 		const int amp = q >= 18 ? 5 : q >= 15 ? 7 : 9, cnt = (f->res1_bits - 1) * 8;
 		for (k = 0; k < cnt; k++) if (bit_of(f->res1_word, f->res1_bits, k)) b[AT(p1[k])] = (int16_t)(b[AT(p1[k])] - amp);
 		for (k = 0; k < cnt; k++) if (!bit_of(f->res1_word, f->res1_bits, k)) b[AT(p1[k])] = (int16_t)(b[AT(p1[k])] + amp);
 	}
+	probe(51, b, 4 * Q * 2);
 	if (q >= 19) {
 		const int cnt = (f->res3_bits * 2 - 2) * 4;
 		int pass;
