@@ -139,9 +139,11 @@ template <int PPL, int HLF, bool IN_RANGE = false /* the caller vouches for the 
 __device__ __forceinline__ void ana_col_pair(const uint32_t (&Ew)[PPL], const uint32_t (&Ow)[PPL], bool left, int lane, int (&lo)[PPL][2], int (&hi)[PPL][2])
 {
 	/* Two columns side by side in packed 16-bit arithmetic wherever nothing can leave 16 bits: with every cell of the wavefront's two columns in
-	 * -1300 .. 3000 the un-normalised sums stay inside (10 x 3000 + 2 x 1300 < 32768) -- which is every block of a real picture (the level-2
-	 * input is LL1, the level-1 chroma input a byte plane).  A block outside that range takes the 32-bit form below, which follows the
-	 * reference's int arithmetic where it wraps. */
+	 * -1300 .. 3000 the un-normalised sums stay inside (10 x 3000 + 2 x 1300 < 32768) -- which is every block of the suite's images (below
+	 * about 2200; the level-2 input is LL1, the level-1 chroma input a byte plane), not of every picture: hard edges in the filters' own sign
+	 * pattern reach about 3480 in luma and 3095 in chroma ("The 16-bit gate of the second direction";
+	 * tests/test_filterbank_gate.py).  A pair outside that range takes the 32-bit form below, which follows the reference's int arithmetic
+	 * where it wraps. */
 	bool wide = false;
 	if (!IN_RANGE)
 #pragma unroll
