@@ -173,7 +173,9 @@ int nhw_picture_tiles(uint32_t width, uint32_t height);
 /* The global tiles [tile0, tile0 + m) of the pictures d_pics[0 .. n_pics) (a table in device memory, the caller's responsibility), tile t
  * padded into d_tiles + (t - tile0) * NHW_IMG_BYTES (16-byte aligned); untile: the inverse, from decoded tiles it writes exactly the
  * pictures' bytes (not the bytes between rows, nothing outside the pictures).  No handle: the current device; stream NULL is the null
- * stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_pics < 1, m < 1, tile0 < 0, an unaligned d_tiles. */
+ * stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_pics < 1, m < 1, tile0 < 0, an unaligned d_tiles.
+ * A tile of the range that no picture of the table holds -- one below the table's first tile, one past its last, or one of an entry with a
+ * zero side (which may share its successor's first_tile) -- is passed over: nothing is written for it, and nhw_sse_pictures_device adds nothing. */
 int nhw_tile_pictures_device(const nhw_picture *d_pics, int n_pics, int tile0, int m, void *d_tiles, void *stream);
 int nhw_untile_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, void *stream);
 /* The .nhwp container (version 1, little-endian): "NHWP", version 1, 3 zero bytes, W (4 bytes), H (4), T = nx ny tile lengths (4 each,
