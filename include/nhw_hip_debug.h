@@ -54,6 +54,14 @@ int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream);
  * form 0: the forked order's kernels (the emission makes the walk for both, the simulation skips it); form 1: the in-line order's (each makes
  * it); forms 2, 3: the same two with the verbatim samples put back by the level-2 synthesis, which then follows. */
 int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream);
+/* The stream stage (the Y31 symbol rewrites, then the RLE + VLC packetiser and the container) for the first n images of the handle's last whole
+ * batch, at that batch's quality, on the workspace as it stands.  form 0: k_y31 and k_final, from the symbol lists as the quantisers leave
+ * them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS); form 1: k_final alone, on B_NZS / B_VOFF / B_VALS as they stand;
+ * form 2: k_y31 alone, which leaves its lists to be read (k_final puts the chroma part's map into B_NZS / B_VOFF) and reports nothing.
+ * The files go to the handle's own output arena, the per-image status and file size to `status` and `sizes` (n entries each, host memory;
+ * sizes may be null); the packet words, the code books, the sign words and the scalars are read from the workspace behind the call
+ * (B_PACKET, B_BOOK1/2, B_SEL1/2, B_META). */
+int nhw_stage_stream(nhw_enc *e, int n, int form, int32_t *status, uint32_t *sizes, void *stream);
 
 /* decoder: the same two hooks (stage order: decode_image, decoder/nhw_decoder.c:54-1476; `what`: an index of the D_* list in nhw_dec.hip, sized by dec_bytes there) */
 void nhw_dec_debug_stop_after(nhw_dec *d, int stage);

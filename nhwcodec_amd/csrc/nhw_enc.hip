@@ -680,6 +680,38 @@ extern "C" int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream)
 	return NHW_OK;
 }
 
+/* A test hook for the stream stage -- the Y31 symbol rewrites and the RLE + VLC packetiser, a pure function of the symbol stream -- for the first n
+ * images of the handle's last whole batch at that batch's quality, on the workspace as it stands (a test writes the lists: nhw_debug_write).
+ *   form 0: k_y31, then k_final: from the lists as the quantisers leave them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS);
+ *   form 1: k_final alone, on B_NZS / B_VOFF / B_VALS as they stand (and the chroma lists, which it puts into stream order itself);
+ *   form 2: k_y31 alone: B_NZS / B_VOFF / B_VALS behind it are Y31's (k_final puts the chroma part's map into B_NZS / B_VOFF); nothing is
+ *           reported.
+ * k_final writes the files into the handle's own output arena; what a test compares lies in the workspace behind the call (B_PACKET, B_BOOK1/2,
+ * B_SEL1/2, B_META).  status, sizes (may be null): n entries each of the caller's, host memory -- what k_final reports for every image; the call
+ * returns when they are there. */
+extern "C" int nhw_stage_stream(nhw_enc *e, int n, int form, int32_t *status, uint32_t *sizes, void *stream)
+{
+	if (!e || (!status && form != 2) || n < 1 || n > e->max_batch || form < 0 || form > 2) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after) {
+		nhw_enc_err = "nhw_stage_stream: needs a completed whole batch of >= n images and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, n); if (rc != NHW_OK) return rc; }
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = 0;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	if (form != 1) nhw_launch_phase(PH_L4D, ws, 0, s);
+	if (form == 2) { HIPCHK(hipGetLastError()); HIPCHK(hipStreamSynchronize(s)); return NHW_OK; }
+	nhw_launch_final(ws, e->d_out, e->d_sizes, e->d_status, s);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(status, e->d_status, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+	if (sizes) HIPCHK(hipMemcpyAsync(sizes, e->d_sizes, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipStreamSynchronize(s));
+	return NHW_OK;
+}
+
 extern "C" int nhw_stage_synthesis(nhw_enc *e, void *d_jpeg, void *d_proc, int n_img, size_t plane_stride, int stride, int size, void *stream)
 {
 	if (!e || n_img < 1) return NHW_E_ARG;

@@ -2958,6 +2958,11 @@ DEV void pack_part_par(Ctx *c, int part, PackShared *sh, int tid, int word0, uin
 	BARRIER();
 	if (sh->rc) return;
 	uint16_t *rank_sym = reinterpret_cast<uint16_t *>(lw), *rank_run = rank_sym + 256;
+	/* A walked symbol that enters no book is looked up all the same: the reference writes the ranks over the counts of the book's symbols
+	 * only (:261-266) and finds such a symbol's COUNT where a rank would be.  One symbol can do this: the 201 whose 132 .. 135 code stood in
+	 * the stream's first four symbols, which Y31 clears (no picture puts a +-8 there; the stream stage's tests do). */
+	rank_sym[tid] = (uint16_t)(sh->hist[tid] < 0xFFFF ? sh->hist[tid] : 0xFFFF);
+	BARRIER();
 	{                                                            /* stable descending rank == the reference's bubble sort (:238-252) */
 		const int k = sh->k;
 		for (int e = tid; e < k; e += NT) {

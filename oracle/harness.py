@@ -106,6 +106,26 @@ class RefEncoder:
         return (data, tr) if trace else data
 
 
+    def stream_packet(self, stream, select1: int, select2: int):
+        """nhwref_stream_packet: the unmodified wavlts2packet on a 393216-symbol stream (the luma part behind the rewrites, then the chroma
+        part) -> (status, dict of the packet words, both books, both sign-word arrays and the scalars).  Not for streams of more than
+        80000 packet words: the reference has no bound."""
+        stream = np.ascontiguousarray(stream, np.uint8)
+        assert stream.size == 6 * 65536 and 0 <= select1 < 65536 and 0 <= select2 < 65536
+        pk = np.zeros(80000, np.uint32); b1 = np.zeros(708, np.uint8); b2 = np.zeros(708, np.uint8)
+        s1 = np.zeros(32768 + 8, np.uint8); s2 = np.zeros_like(s1)
+        info = np.zeros(8, np.int32)
+        fn = self.lib.nhwref_stream_packet
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
+        rc = fn(stream.ctypes.data, select1, select2, pk.ctypes.data, b1.ctypes.data, b2.ctypes.data, s1.ctypes.data, s2.ctypes.data, info.ctypes.data)
+        if rc != 0:
+            return rc, None
+        d1, d2, t1, t2, te, n1, n2, wt = (int(v) for v in info)
+        return 0, dict(size_data1=d1, size_data2=d2, size_book1=t1, size_book2=t2, tree_end=te, select1=n1, select2=n2, wavelet_type=wt,
+                       packet=pk[:d2], book1=b1[:t1], book2=b2[:t2], sel_word1=s1[:n1], sel_word2=s2[:n2])
+
+
 REF_DEC_SO = os.path.join(HERE, "_ref", "libnhwref_dec.so")
 STOCK_ENC = os.path.join(HERE, "_ref", "nhw-enc")      # the reference encoder exactly as its README builds it (gcc *.c -O3), no shim
 

@@ -78,6 +78,23 @@ void nhwo_analysis(int16_t *jpeg, int16_t *proc, int stride, int n, int final_le
 /* a7: wavelet_filterbank.c:305-496. */
 void nhwo_synthesis(int16_t *jpeg, int16_t *proc, int stride, int n);
 
+/* The stream stage: the symbol rewrites of encode_image (nhw_encoder.c:2134-2252) and wavlts2packet (compress_pixel.c:53-469) on a symbol
+ * stream the caller made -- luma: 4 * NHWO_QSIZE symbols as the serpentine gather leaves them, chroma: 2 * NHWO_QSIZE as the chroma quantisers
+ * leave them.  luma_out: the luma part behind the three rewrites.  select1_pre / select2_pre: the counts the second rewrite leaves
+ * (nhw_select1 / nhw_select2 before packing); select1 / select2: the bytes of sel_word1 / sel_word2 (4 * NHWO_QSIZE / 8 + 8 bytes each).
+ * The packet is made in a scratch of the worst case's size: `words` is what the stream takes, however many (the encoder's block holds
+ * 80000), and `packet` receives the first min(words, packet_cap).  book1 / book2: 708 bytes each.  Returns the status (also in info). */
+typedef struct {
+	int status;
+	int select1_pre, select2_pre, select1, select2;
+	int size_data1, size_data2, size_book1, size_book2, tree_end, wavelet_type;
+	int words;
+} nhwo_stream_info;
+int nhwo_stream_stage(const uint8_t *luma, const uint8_t *chroma, uint8_t *luma_out, uint8_t *sel_word1, uint8_t *sel_word2,
+                      uint32_t *packet, size_t packet_cap, uint8_t *book1, uint8_t *book2, nhwo_stream_info *info);
+/* which byte codes can enter a code book (compress_pixel.c:131-160) */
+int nhwo_book_symbol_ok(int v);
+
 /* ---- decoder (BASELINE config 5; nhwo_dec.c) ---- */
 /* .nhw bytes -> 786432 bytes in the order the reference's nhw-dec writes them behind its 54-byte BMP header */
 int nhwo_decode(const uint8_t *nhw, size_t len, uint8_t *bgr, int *quality);

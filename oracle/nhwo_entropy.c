@@ -499,3 +499,52 @@ int nhwo_packetise(nhwo_ctx *c)
 	c->scan[6 * Q - 1] = c->scan[6 * Q - 2];                   /* :465 */
 	return pack_part(c, 1, &bs);
 }
+
+/* ------------------------------------------------------------------------------------------
+ * the stream stage as an entry point: the rewrites in the middle of encode_image (nhw_encoder.c:2134-2252) and wavlts2packet on a stream
+ * the caller made.  luma: 4 Q symbols as the serpentine gather leaves them; chroma: 2 Q symbols as the chroma quantisers leave them (U and V
+ * interleaved).  The rewrites run while the chroma part still reads zero, as in the reference, whose im_nhw is calloc'ed and whose chroma
+ * sequences come later.  The packet goes to a scratch sized for the worst case (6 Q tokens of 20 bits: put_bits has no bound, the
+ * encoder's block holds 80000 words) and info->words says how many it took; `packet` receives min(words, packet_cap) of them.
+ * sel_word1 / sel_word2: 4 Q / 8 + 8 bytes each; book1 / book2: 708 bytes each.
+ * ------------------------------------------------------------------------------------------ */
+int nhwo_book_symbol_ok(int v) { return v >= 0 && v < 256 && book_symbol_ok(v); }
+
+int nhwo_stream_stage(const uint8_t *luma, const uint8_t *chroma, uint8_t *luma_out, uint8_t *sel_word1, uint8_t *sel_word2,
+                      uint32_t *packet, size_t packet_cap, uint8_t *book1, uint8_t *book2, nhwo_stream_info *info)
+{
+	nhwo_ctx ctx, *c = &ctx;
+	const size_t worst = (size_t)6 * Q * 20 / 32 + 16;
+	int rc;
+	memset(c, 0, sizeof *c);
+	memset(info, 0, sizeof *info);
+	c->arena.cap = 4u << 20;
+	c->arena.base = (uint8_t *)calloc(c->arena.cap, 1);
+	if (!c->arena.base) return NHWO_E_ALLOC;
+	c->scan = (uint8_t *)arena_get(&c->arena, 6 * Q);
+	c->packet = (uint32_t *)arena_get(&c->arena, worst * sizeof(uint32_t));
+	c->book1 = (uint8_t *)arena_get(&c->arena, 354 * 2); c->book2 = (uint8_t *)arena_get(&c->arena, 354 * 2);
+	if (!c->scan || !c->packet || !c->book1 || !c->book2) { free(c->arena.base); return NHWO_E_ALLOC; }
+
+	memcpy(c->scan, luma, 4 * Q);
+	nhwo_rewrite_stream(c);
+	memcpy(luma_out, c->scan, 4 * Q);
+	info->select1_pre = c->select1; info->select2_pre = c->select2;
+	memcpy(c->scan + 4 * Q, chroma, 2 * Q);
+	rc = nhwo_packetise(c);
+	info->status = rc;
+	if (!rc) {
+		size_t n;
+		info->select1 = c->select1; info->select2 = c->select2;
+		info->size_data1 = c->size_data1; info->size_data2 = c->size_data2;
+		info->size_book1 = c->size_book1; info->size_book2 = c->size_book2;
+		info->tree_end = c->tree_end; info->wavelet_type = c->wavelet_type;
+		info->words = c->size_data2;
+		memcpy(sel_word1, c->sel_word1, (size_t)c->select1); memcpy(sel_word2, c->sel_word2, (size_t)c->select2);
+		memcpy(book1, c->book1, (size_t)c->size_book1); memcpy(book2, c->book2, (size_t)c->size_book2);
+		n = (size_t)c->size_data2 < packet_cap ? (size_t)c->size_data2 : packet_cap;
+		memcpy(packet, c->packet, n * sizeof(uint32_t));
+	}
+	free(c->arena.base);
+	return rc;
+}

@@ -99,6 +99,7 @@ void nhwo_quantise_chroma(nhwo_ctx *c);                         /* offsetUV */
 void nhwo_ll_code_luma(nhwo_ctx *c);                            /* Y_highres_compression */
 void nhwo_ll_code_chroma(nhwo_ctx *c);                          /* highres_compression */
 int  nhwo_packetise(nhwo_ctx *c);                               /* wavlts2packet */
+void nhwo_rewrite_stream(nhwo_ctx *c);                          /* the symbol rewrites in the middle of encode_image */
 void nhwo_band_recons(nhwo_ctx *c);                             /* im_recons_wavelet_band */
 void nhwo_hq_settings(nhwo_ctx *c);                             /* wavelet_synthesis_high_quality_settings */
 void nhwo_poslist_finish(nhwo_ctx *c, nhwo_poslist *pl, uint8_t *raw, int raw_len, const uint8_t *payload,

@@ -474,13 +474,12 @@ static void clean_details(nhwo_ctx *c)
 		}
 }
 
-/* Y30 + Y31: serpentine gather into the symbol stream, then the symbol rewrites (:2108-2252) */
-static void scan_and_rewrite(nhwo_ctx *c)
+/* Y30: serpentine gather into the symbol stream (:2108-2132) */
+static void scan_gather(nhwo_ctx *c)
 {
 	const int16_t *p = c->proc;
 	uint8_t *s = c->scan;
-	const int n = 4 * Q;
-	int strip, r, t, i, run;
+	int strip, r, t;
 
 	for (strip = 0, t = 0; strip < W / 4; strip++)        /* 128 strips of 4 columns */
 		for (r = 0; r < W; r++) {
@@ -489,6 +488,15 @@ static void scan_and_rewrite(nhwo_ctx *c)
 			else { s[t] = (uint8_t)row[3]; s[t + 1] = (uint8_t)row[2]; s[t + 2] = (uint8_t)row[1]; s[t + 3] = (uint8_t)row[0]; }
 			t += 4;
 		}
+}
+
+/* Y31: the three symbol rewrites of the luma part of the stream (:2134-2252).  A function of the stream alone (nhwo_stream_stage); the third
+ * rewrite reads up to four bytes behind the luma part, which the chroma sequences have not written yet (im_nhw is calloc'ed: zeros) */
+void nhwo_rewrite_stream(nhwo_ctx *c)
+{
+	uint8_t *s = c->scan;
+	const int n = 4 * Q;
+	int t, i, run;
 
 	for (i = 0; i < n - 4; i++) {                         /* :2136-2161 (+-8, 0,0,0, +-8) */
 		if (s[i] != 128 && s[i + 1] == 128) {
@@ -840,6 +848,7 @@ int nhwo_luma(nhwo_ctx *c)
 	nhwo_quantise_luma(c);                                                                                      /* Y28 :2100 */
 	trace_planes(c, "offsetY", NULL, 0, c->proc, 8 * Q);
 	if (q > 21) { nhwo_band_recons(c); trace_planes(c, "im_recons_wavelet_band", c->band, 2 * Q, NULL, 0); nhwo_hq_settings(c); }                                                   /* Y29 :2102-2106 */
-	scan_and_rewrite(c);
+	scan_gather(c);
+	nhwo_rewrite_stream(c);
 	return NHWO_OK;
 }

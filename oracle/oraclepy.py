@@ -13,6 +13,11 @@ class _Trace(ctypes.Structure):
     _fields_ = [("buf", P), ("cap", ctypes.c_size_t), ("len", ctypes.c_size_t), ("count", ctypes.c_int)]
 
 
+class _StreamInfo(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int) for k in ("status", "select1_pre", "select2_pre", "select1", "select2", "size_data1", "size_data2",
+                                            "size_book1", "size_book2", "tree_end", "wavelet_type", "words")]
+
+
 class Oracle:
     def __init__(self, so_path: str = SO):
         L = self.lib = ctypes.CDLL(so_path)
@@ -92,6 +97,31 @@ class Oracle:
         proc = np.zeros_like(jpeg)
         self.lib.nhwo_synthesis(jpeg.ctypes.data, proc.ctypes.data, stride, n)
         return jpeg, proc
+
+    def stream_stage(self, luma, chroma, packet_cap: int = 80000) -> dict:
+        """nhwo_stream_stage: the symbol rewrites and the packetiser on a stream of the caller's (luma: uint8[262144] as the gather leaves
+        it, chroma: uint8[131072] as the chroma quantisers leave it).  -> the rewritten luma part, the packet words (the first
+        min(words, packet_cap)), both books, both sign-word arrays and every scalar of nhwo_stream_info."""
+        luma = np.ascontiguousarray(luma, np.uint8); chroma = np.ascontiguousarray(chroma, np.uint8)
+        assert luma.size == 4 * 65536 and chroma.size == 2 * 65536
+        out = np.empty(4 * 65536, np.uint8)
+        s1 = np.zeros(4 * 65536 // 8 + 8, np.uint8); s2 = np.zeros_like(s1)
+        pk = np.zeros(packet_cap, np.uint32)
+        b1 = np.zeros(708, np.uint8); b2 = np.zeros(708, np.uint8)
+        info = _StreamInfo()
+        fn = self.lib.nhwo_stream_stage
+        fn.restype = ctypes.c_int
+        fn.argtypes = [P, P, P, P, P, P, ctypes.c_size_t, P, P, ctypes.POINTER(_StreamInfo)]
+        rc = fn(luma.ctypes.data, chroma.ctypes.data, out.ctypes.data, s1.ctypes.data, s2.ctypes.data, pk.ctypes.data, packet_cap,
+                b1.ctypes.data, b2.ctypes.data, ctypes.byref(info))
+        r = {k: getattr(info, k) for k, _ in _StreamInfo._fields_}
+        assert rc == r["status"]
+        r.update(luma=out, packet=pk[:min(r["words"], packet_cap)], book1=b1[:r["size_book1"]], book2=b2[:r["size_book2"]],
+                 sel_word1=s1[:r["select1"]], sel_word2=s2[:r["select2"]])
+        return r
+
+    def book_symbol_ok(self, v: int) -> bool:
+        return bool(self.lib.nhwo_book_symbol_ok(int(v)))
 
     def supported(self, q: int) -> bool:
         return bool(self.lib.nhwo_quality_supported(q))

@@ -316,3 +316,46 @@ int nhwref_encode_file(const char *bmp_path, const char *nhw_path, int quality)
 	release_leftovers();
 	return rc;
 }
+
+/* wavlts2packet (compress_pixel.c:53) alone, on a symbol stream the caller made: 6 * IM_SIZE bytes, the luma part behind the rewrites of
+ * encode_image and the chroma part, with the counts those rewrites leave in nhw_select1 / nhw_select2 (they size two scratch lists).  The
+ * same allocator and the same zeroed stack as inside an encode.  The caller keeps streams that take more than the 80000 words of
+ * enc->encode away from here: the function has no bound.
+ * info: size_data1, size_data2, size_tree1, size_tree2, tree_end, nhw_select1, nhw_select2, wavelet_type.  sel1 / sel2: IM_SIZE / 2 + 8
+ * bytes each; book1 / book2: 708 bytes each; packet: 80000 words.  Returns 0, or what the reference handed to exit(). */
+int nhwref_stream_packet(const uint8_t *stream, int select1, int select2, uint32_t *packet, uint8_t *book1, uint8_t *book2,
+                         uint8_t *sel1, uint8_t *sel2, int32_t *info)
+{
+	image_buffer im;
+	encode_state enc;
+	codec_setup setup;
+	int rc;
+	memset(&im, 0, sizeof im);
+	memset(&enc, 0, sizeof enc);
+	memset(&setup, 0, sizeof setup);
+	g_track = 1; g_in_call = 1;
+	rc = setjmp(g_jmp);
+	if (rc == 0) {
+		im.setup = &setup;
+		setup.quality_setting = 20;
+		setup.colorspace = YUV;
+		setup.wavelet_type = WVLTS_53;
+		setup.RES_HIGH = 0;
+		setup.RES_LOW = 3;
+		setup.wvlts_order = 2;
+		im.im_nhw = (unsigned char *)calloc(6 * IM_SIZE, sizeof(char));
+		memcpy(im.im_nhw, stream, 6 * IM_SIZE);
+		enc.nhw_select1 = (unsigned short)select1;
+		enc.nhw_select2 = (unsigned short)select2;
+		scrub_stack_below();
+		__real_wavlts2packet(&im, &enc);
+		info[0] = enc.size_data1; info[1] = enc.size_data2; info[2] = enc.size_tree1; info[3] = enc.size_tree2;
+		info[4] = enc.tree_end; info[5] = enc.nhw_select1; info[6] = enc.nhw_select2; info[7] = setup.wavelet_type;
+		memcpy(packet, enc.encode, (size_t)enc.size_data2 * 4);
+		memcpy(book1, enc.tree1, enc.size_tree1); memcpy(book2, enc.tree2, enc.size_tree2);
+		memcpy(sel1, enc.nhw_select_word1, enc.nhw_select1); memcpy(sel2, enc.nhw_select_word2, enc.nhw_select2);
+	}
+	g_in_call = 0; g_track = 0;
+	release_leftovers();
+	return rc;
+}
