@@ -54,6 +54,11 @@ int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream);
  * form 0: the forked order's kernels (the emission makes the walk for both, the simulation skips it); form 1: the in-line order's (each makes
  * it); forms 2, 3: the same two with the verbatim samples put back by the level-2 synthesis, which then follows. */
 int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream);
+/* The luma quantiser for the first n images of the handle's last whole batch, at that batch's quality (17 .. 23), on B_L2SAVE, B_PROC and the other
+ * planes as they stand.  form 0: the second dequantiser simulation, which leaves the level-2 details behind the quantiser's loops 2 and 3 in
+ * B_KMAP, then the quantiser reading them (production); form 1: the quantiser alone with its own loops.  Both leave the symbol list to be read:
+ * B_NZQ (the non-zero map, 4096 words, with the fbase table of 33 words behind it) and B_VALS. */
+int nhw_stage_quant(nhw_enc *e, int n, int form, void *stream);
 /* The stream stage (the Y31 symbol rewrites, then the RLE + VLC packetiser and the container) for the first n images of the handle's last whole
  * batch, at that batch's quality, on the workspace as it stands.  form 0: k_y31 and k_final, from the symbol lists as the quantisers leave
  * them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS); form 1: k_final alone, on B_NZS / B_VOFF / B_VALS as they stand;

@@ -44,6 +44,7 @@ struct nhw_enc {
 	int quant_join;               /* the side streams join in front of the luma quantiser (q <= 21) */
 	int y5_fork;                  /* Y5 on ll_stream beside the first dequantiser simulation (NHW_Y5_FORK=0: in front of it on the luma stream) */
 	int ll2_once;                 /* q > 12: the LL2 bump walk in the emission only (NHW_LL2_ONCE=0: again in the second simulation) */
+	int quant_marks;              /* q > 16: the second simulation hands its marks to the quantiser, which skips its loops 2 and 3 (NHW_QUANT_MARKS=0: the quantiser runs them itself) */
 	int parts;
 	hipEvent_t ev[EV_COUNT];
 	bool timed;

@@ -101,6 +101,7 @@ extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_
 	e->quant_join = env("NHW_QUANT_JOIN", 1) != 0;
 	e->y5_fork = env("NHW_Y5_FORK", 1) != 0;
 	e->ll2_once = env("NHW_LL2_ONCE", 1) != 0;
+	e->quant_marks = env("NHW_QUANT_MARKS", 1) != 0;
 	*out = e;
 	return NHW_OK;
 }
@@ -304,6 +305,11 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	}
 	STAGE_DONE();
 	const bool one_walk = fork && q > 12 && e->ll2_once;             /* the LL2 bump walk once, in the emission: the second simulation finds its cells made (wave_emit_ll2) */
+	/* The second simulation's two marking blocks are the quantiser's loops 2 and 3 on the same cells (wave_dequant_details): it leaves their outcome
+	 * in B_KMAP and the quantiser takes the level-2 details from there.  On wherever the simulation of this very call runs in front of the quantiser
+	 * on these planes -- every order of this function above quality 16 (forked, in line, a sub-batch's view: both kernels are launched below on s, and
+	 * the fit paths come through here) -- and off under a debug stop, whose stage checks read the quantiser's own work plane. */
+	const bool marks = q > 16 && !e->stop_after && !ws.dbg && e->quant_marks;
 	nhw_launch_wave(WV_EMIT, ws, s, one_walk);                       /* Y14, Y15 */
 	/* Y16, the LL2 coder, is a latency-bound parse (0.6 ms at 0.3 TB/s) in front of the vector-bound dequantiser simulation, which only wants its
 	 * list of verbatim samples -- at its very end, to put them back into the block.  Production: the coder runs beside the simulation on a
@@ -320,7 +326,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	if (fork) HIPCHK(hipEventRecord(e->part_ev[PE_LUMA_LIST], s));              /* exception list of the luma plane complete */
 	}
 	if (q > 12) {                                                    /* second closed loop (:759-779) */
-	nhw_launch_wave(WV_DQ0, ws, s, one_walk);
+	nhw_launch_wave(WV_DQ0, ws, s, one_walk, marks);
 	STAGE_DONE();
 	if (fork_ll) {
 		HIPCHK(hipStreamWaitEvent(s, e->ll_ev[LL_EV_DONE], 0));               /* (the coder is long done: the simulation takes twice its time) */
@@ -352,7 +358,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		HIPCHK(hipEventRecord(e->part_ev[PE_CHROMA], cs));
 		return 1;
 	};
-	/* The quantiser is a wavefront an image at 115 registers: four wavefronts fill a SIMD's register file, and it is as fast as its slowest
+	/* The quantiser is a wavefront an image at 119 registers: four wavefronts fill a SIMD's register file, and it is as fast as its slowest
 	 * wavefront is late.  A side stream's workgroup that sits on a CU when it starts keeps four of its images waiting for a second round (the
 	 * kernel took 3.0 ms beside the chroma sequence, 1.9 alone).  So the side streams are let finish first (they have had the
 	 * multi-round kernels Y19-Y27 to hide behind), and Y31 and the packetiser then run alone as well. */
@@ -361,7 +367,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		if (fork_lists) HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_LISTS], 0));
 		HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_CHROMA], 0));
 	}
-	nhw_launch_wave(WV_QUANT, ws, s);                                /* Y28 (+ Y30: the symbols leave in stream order), every quality */
+	nhw_launch_wave(WV_QUANT, ws, s, false, marks);                  /* Y28 (+ Y30: the symbols leave in stream order), every quality */
 	if (q > 21) nhw_launch_phase(PH_L4C2, ws, 0, s);   /* Y29 */
 	if (fork && !early_join) CHROMA(chroma_rest());                  /* queued here so that the wait finds its event recorded */
 	nhw_launch_phase(PH_L4D, ws, 0, s);      /* Y31 (Y30, the stream order, is the quantisers' output order) */
@@ -676,6 +682,30 @@ extern "C" int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream)
 		const Plane<const uint8_t> meta = ws.plane<const uint8_t>(B_META), len{ meta.p + offsetof(NhwMeta, ll_mem_len), meta.pitch };
 		nhw_launch_synthesis(ws.plane<int16_t>(B_JPEG), ws.plane<int16_t>(B_PROC), n, W, H, ws.q <= 21, ws.plane<const uint8_t>(B_LLMEM), len, s);
 	}
+	HIPCHK(hipGetLastError());
+	return NHW_OK;
+}
+
+/* A test hook for the hand-over of the second dequantiser simulation's marks to the luma quantiser, on B_L2SAVE, B_PROC and the other planes as they
+ * stand (a test writes them), for the first n images of the handle's last whole batch at that batch's quality (17 .. 23), on one stream.
+ *   form 0: the second simulation with the hand-over (its LL2 walk and the put-back of verbatim samples left out: neither plane the quantiser
+ *           reads is written), then the quantiser reading it;
+ *   form 1: the quantiser alone, with its own loops 2 and 3.
+ * Both leave B_NZQ (with its fbase table) and B_VALS; above quality 21 the quantiser has then coded the work plane in place. */
+extern "C" int nhw_stage_quant(nhw_enc *e, int n, int form, void *stream)
+{
+	if (!e || n < 1 || n > e->max_batch || form < 0 || form > 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after || e->last_q < 17) {
+		nhw_enc_err = "nhw_stage_quant: needs a completed whole batch of >= n images at quality >= 17 and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = 0; ws.defer_verbatim = 1;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	if (form == 0) nhw_launch_wave(WV_DQ0, ws, s, true, true);
+	nhw_launch_wave(WV_QUANT, ws, s, false, form == 0);
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
 }

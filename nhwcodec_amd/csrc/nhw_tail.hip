@@ -79,8 +79,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NHW_L4A_WAV
 
 /* passes that run one wavefront per image (nhw_tail_wave.h): four images per workgroup, no workgroup barriers */
 template <int PH>
-__global__ __launch_bounds__(256) void k_wave(NhwWs ws, int one_walk /* WV_EMIT, WV_DQ0: the LL2 bump walk is made once, by the emission (wave_emit_ll2) */)
+__global__ __launch_bounds__(256) void k_wave(NhwWs ws, int flags /* bit 0, WV_EMIT and WV_DQ0: the LL2 bump walk is made once, by the emission (wave_emit_ll2); bit 1, WV_DQ0 and WV_QUANT: the simulation leaves the level-2 details behind the quantiser's loops 2 and 3 in B_KMAP, the quantiser takes them from there (wave_dequant_details) */)
 {
+	const int one_walk = flags & 1, marks = flags & 2;
 	const int img = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	__shared__ uint32_t dq_lut[(PH == WV_DQ1 || PH == WV_DQ0) ? DQ_WORDS : 1];
 	if (PH == WV_DQ1 || PH == WV_DQ0) {                            /* the one workgroup barrier of these kernels: the table of the dequantiser walk */
@@ -91,19 +92,20 @@ __global__ __launch_bounds__(256) void k_wave(NhwWs ws, int one_walk /* WV_EMIT,
 	Ctx c;
 	ctx_load(&c, ws, img);
 	if (PH == WV_DQ1) wave_dequant_sim_luma(&c, 1, lane, dq_lut, false, ws.dbg != 0);
-	else if (PH == WV_DQ0) wave_dequant_sim_luma(&c, 0, lane, dq_lut, !ws.dbg, ws.dbg != 0, one_walk != 0);   /* production: the level-2 block straight from l2save (Y17's restore of the work plane is not made: luma_p3_par) */
+	else if (PH == WV_DQ0) wave_dequant_sim_luma(&c, 0, lane, dq_lut, !ws.dbg, ws.dbg != 0, one_walk != 0, marks ? ws.buf<int16_t>(B_KMAP, img) : nullptr);   /* production: the level-2 block straight from l2save (Y17's restore of the work plane is not made: luma_p3_par) */
 	else if (PH == WV_QUANT) {
 		__shared__ __attribute__((aligned(16))) uint8_t park[4][16 * QROW];
 		__shared__ uint32_t lut[4][QLUT + 3];
-		PROF_BEGIN(); wave_quantise_luma(&c, lane, park[threadIdx.x >> 6], lut[threadIdx.x >> 6], ws.q > 21 || ws.dbg, NHW_DENSE_STREAM || ws.dbg, !(ws.q > 21 || ws.dbg)); if (!lane) PROF(&c, 15);
+		PROF_BEGIN(); wave_quantise_luma(&c, lane, park[threadIdx.x >> 6], lut[threadIdx.x >> 6], ws.q > 21 || ws.dbg, NHW_DENSE_STREAM || ws.dbg, !(ws.q > 21 || ws.dbg), marks ? ws.buf<int16_t>(B_KMAP, img) : nullptr); if (!lane) PROF(&c, 15);
 	}
 	else if (PH == WV_EMIT) { PROF_BEGIN(); wave_emit_ll2(&c, lane, one_walk != 0); if (!lane) PROF(&c, 4); }
 }
-void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s, bool one_walk)
+void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s, bool one_walk, bool marks)
 {
 	const dim3 g((ws.n + 3) / 4), b(256);
 	assert(!one_walk || ((ph == WV_EMIT || ph == WV_DQ0) && ws.q > 12 && !ws.dbg));
-	(ph == WV_DQ1 ? k_wave<WV_DQ1> : ph == WV_DQ0 ? k_wave<WV_DQ0> : ph == WV_EMIT ? k_wave<WV_EMIT> : k_wave<WV_QUANT>)<<<g, b, 0, s>>>(ws, one_walk ? 1 : 0);
+	assert(!marks || ((ph == WV_DQ0 || ph == WV_QUANT) && ws.q > 16 && !ws.dbg));
+	(ph == WV_DQ1 ? k_wave<WV_DQ1> : ph == WV_DQ0 ? k_wave<WV_DQ0> : ph == WV_EMIT ? k_wave<WV_EMIT> : k_wave<WV_QUANT>)<<<g, b, 0, s>>>(ws, (one_walk ? 1 : 0) | (marks ? 2 : 0));
 }
 
 /* The middle of the first closed loop on one LDS residency of the 256 x 256 block: level-2 synthesis (wavelet_filterbank.c:305-496), Y8 (the

@@ -359,7 +359,22 @@ DEV unsigned dq_entry(int i)
 	if (x < -12 && ((-x) & 7) == 6) e |= DQ_AC;
 	return e;
 }
-DEV void wave_dequant_details(Ctx *c, int part, int lane, const uint32_t *lut /* DQ_WORDS, filled by the workgroup */, bool keep_p, const int16_t *src, int ss /* see wave_ll2 */)
+/* HAND (the second simulation; the first keeps the plain form, whose code is what it was): `hand`, when set -- production above quality 16 --,
+ * takes a second value per detail cell of this pass (columns 128..255 of rows 0..127, whole rows 128..255; rows of H cells): what loops 2 and 3
+ * of the quantiser (wave_quantise_luma, image_processing.c:241-309) leave there, which then does not run them.  The two marking blocks below are those loops on the same cells of the same plane: the same
+ * predicates, column ranges and skip walk, a vertical pair's marks into the next row alike; only the values written differ, and every one of
+ * either alphabet lies outside +-4..7, so a later row and the equal-sign block see the same of a marked cell.
+ *   mark                                   here             quantiser
+ *   triple centre                          0                12700 / 12900
+ *   left of a triple                       15300 / 15400    10100
+ *   left of a vertical pair                15500 / 15600    12100 / 12200
+ *   vertical pair: centre, the two below   -, 15500/600, 0  10100
+ *   equal-sign pair, by sign               15700 / 15800    10300 / 10204
+ * The value is taken behind the equal-sign block and in front of the walk (whose +-8 rewrites are not the quantiser's).  Row 255: the marking
+ * block stops at row 254 here, the quantiser's loop 2 includes row 255 (it looks down into HL1), so that row goes over with row 254's vertical
+ * marks alone and the quantiser runs both loops on it. */
+template <bool HAND>
+DEV void wave_dequant_details(Ctx *c, int part, int lane, const uint32_t *lut /* DQ_WORDS, filled by the workgroup */, bool keep_p, const int16_t *src, int ss /* see wave_ll2 */, int16_t *hand = nullptr)
 {
 	int16_t *p = c->proc, *jp = c->jpeg;
 	const bool hq = c->q > 16;                                     /* quality 1..16: no triple / pair marking, and negative magnitudes keep their low bits on a ration (:2938-2989) */
@@ -382,6 +397,11 @@ DEV void wave_dequant_details(Ctx *c, int part, int lane, const uint32_t *lut /*
 		const int col0 = top ? H / 2 : 0;
 		int jv[4] = { pend_v[0], pend_v[1], pend_v[2], pend_v[3] };
 		unsigned je = pend;
+		int hv[HAND ? 4 : 1];                                        /* HAND: the row in the quantiser's alphabet */
+		if constexpr (HAND) {
+			const unsigned above = pend | DN(pend);                    /* the two cells under a vertical pair of the row above */
+			for (int k = K0; k < 4; k++) hv[k] = BIT(above, k) ? 10100 : cur[k];
+		}
 		pend = 0;
 		if (hq && r < H - 1) {                                     /* :2759-2853 (quality 17 and up) */
 			unsigned P, N, PN, NN;
@@ -412,6 +432,11 @@ DEV void wave_dequant_details(Ctx *c, int part, int lane, const uint32_t *lut /*
 					if (BIT(ftn, k)) jv[k] = -6;
 					if (BIT(fvn, k) || BIT(ftn_r, k)) jv[k] = -5;
 					pend_v[k] = BIT(fvp, k) ? 5 : -5;
+					if constexpr (HAND) {
+						if (BIT(ftp, k)) hv[k] = 12700; if (BIT(ftn, k)) hv[k] = 12900;
+						if (BIT(ftp_l | ftn_l | fv, k)) hv[k] = 10100;
+						if (BIT(fvp_l, k)) hv[k] = 12100; if (BIT(fvn_l, k)) hv[k] = 12200;
+					}
 				}
 				je |= fired | ftp_r | ftn_r;
 				pend = fv;
@@ -425,8 +450,14 @@ DEV void wave_dequant_details(Ctx *c, int part, int lane, const uint32_t *lut /*
 				const unsigned fired = bs_from4(alt_runs(bs_ballot4(cand)));
 				const unsigned fa = fired & A, fb = fired & B;
 				for (int k = K0; k < 4; k++) { if (BIT(fa, k)) cur[k] = 15700; if (BIT(fb, k)) cur[k] = 15800; }
+				if constexpr (HAND) if (r < H - 1) for (int k = K0; k < 4; k++) { if (BIT(fa, k)) hv[k] = 10300; if (BIT(fb, k)) hv[k] = 10204; }
 			}
 		}
+		/* B_KMAP, the plane `hand` points into, between this store and the quantiser's load: written by the front launch group alone (quality 1..16:
+		 * the rationed pre-filter's output, k_low_prefilter; compatibility mode below quality 22: the luma plane of the stale-cell replay,
+		 * nhw_launch_color; developer builds: the front kernel's dump) and by the stage hooks nhw_stage_prefilter and nhw_stage_analysis, read by the
+		 * front kernels and those hooks -- all of them in front of this kernel in a batch's launch order, or in another call on the handle. */
+		if constexpr (HAND) if (hand) for (int k = K0; k < 4; k++) hand[r * H + lane + 64 * k] = (int16_t)hv[k];
 		{                                                          /* :2909-3124 */
 			unsigned code = 0, k1 = 0, k2 = 0, pr_p = 0, pr_n = 0, wr = 0;
 			unsigned e8 = 0, e7 = 0, em7 = 0, dc = 0, ac = 0;
@@ -644,8 +675,18 @@ DEV int right_of_dpp(const int *v, int k, int nk, int lane, int edge)
 /* ll: the level-2 block (rows and columns below 256) comes from its copy l2save instead of the work plane -- Y26 (nhw_encoder.c:1893-1910) put
  * it back there with the tags of its LL2 quarter cleared (everything up to 8000 in rows and columns below 128 becomes 0), for this reader
  * alone: 256 KB of copy per image that this load does itself */
-DEV void quant_load_row(const int16_t *p, int r, int lane, int *v, const int16_t *ll = nullptr)
+/* hand: the detail cells of the level-2 block come from the plane the second dequantiser simulation of this batch left (wave_dequant_details): the
+ * row behind loops 2 and 3 (row 255: in front of them).  It holds no LL2 quadrant, which comes from where it came before, by the same rule. */
+DEV void quant_load_row(const int16_t *p, int r, int lane, int *v, const int16_t *ll = nullptr, const int16_t *hand = nullptr)
 {
+	if (hand && r < H) {
+		for (int k = 0; k < 4; k++) {
+			if (r < H / 2 && k < 2) { const int x = ll ? ll[r * H + lane + 64 * k] : p[r * W + lane + 64 * k]; v[k] = (ll && x <= 8000) ? 0 : x; }
+			else v[k] = hand[r * H + lane + 64 * k];
+		}
+		for (int k = 4; k < 8; k++) v[k] = p[r * W + lane + 64 * k];
+		return;
+	}
 	if (ll && r < H) {
 		for (int k = 0; k < 4; k++) { const int x = ll[r * H + lane + 64 * k]; v[k] = (r < H / 2 && k < 2 && x <= 8000) ? 0 : x; }
 		for (int k = 4; k < 8; k++) v[k] = p[r * W + lane + 64 * k];
@@ -695,7 +736,8 @@ DEV unsigned quant_entry(int x)
  * strip (a wave prefix sum of the popcounts), inside a slice in stream order.  fbase[f] is where flush f starts in `vals`.  Zero-run lengths
  * are gaps between set bits; Y31 (scan_rewrite_list_par) turns the map into stream order for the packetiser.  `dense`: the byte stream as
  * well (stage checks). */
-DEV void wave_quantise_luma(Ctx *c, int lane, uint8_t *park /* 16 x QROW bytes of this wavefront */, uint32_t *lut /* QLUT words of this wavefront */, bool write_plane, bool dense, bool ll_from_save)
+DEV void wave_quantise_luma(Ctx *c, int lane, uint8_t *park /* 16 x QROW bytes of this wavefront */, uint32_t *lut /* QLUT words of this wavefront */, bool write_plane, bool dense, bool ll_from_save,
+                            const int16_t *hand = nullptr /* quality 17 and up: rows 0..254 arrive behind loops 2 and 3, row 255 with row 254's vertical marks (quant_load_row) */)
 {
 	const int16_t *const llsrc = ll_from_save ? c->l2save : nullptr;
 	uint64_t *const nzq = c->nzq;
@@ -707,16 +749,16 @@ DEV void wave_quantise_luma(Ctx *c, int lane, uint8_t *park /* 16 x QROW bytes o
 	uint8_t *stream = c->scan;
 	int prev[8], cur[8], nxt[8];
 	int q0[8];                                                     /* row r+2 in flight (and r+3: `far`; a row's step is 3.5 us, a memory round trip shorter) */
-	quant_load_row(p, 0, lane, cur, llsrc);
-	quant_load_row(p, 1, lane, nxt, llsrc);
-	quant_load_row(p, 2, lane, q0, llsrc);
+	quant_load_row(p, 0, lane, cur, llsrc, hand);
+	quant_load_row(p, 1, lane, nxt, llsrc, hand);
+	quant_load_row(p, 2, lane, q0, llsrc, hand);
 	for (int k = 0; k < 8; k++) prev[k] = 0;
 	const bool low = c->q <= 16;                                   /* quality 1..16 (image_processing.c:357-410, :427-510): no loops 2 and 3; rationed low bits; the `quant4` pushes */
 	int q4_turn = 0, q4_carry = 0;                                 /* quant4: its every-third-pair counter runs through the whole plane; a push out of column 511 lands in the next row's first cell */
 	unsigned last_le0 = 0;                                         /* the last cell of the row above is <= 0 (loop 1 looks at it from column 0) */
 	for (int r = 0; r <= W; r++) {                                 /* step r: loops 1-3 on row r, loop 4 on row r - 1 */
 		int far[8];
-		quant_load_row(p, r + 3, lane, far, llsrc);
+		quant_load_row(p, r + 3, lane, far, llsrc, hand);
 		if (r < W) {
 			if (r < H) {                                           /* loop 1, upper half: only columns 256..511 (words 4..7) take part */
 				/* both rules start from two neighbours on multiples of 8 (from 8 up): a row without such a pair -- most rows -- is done after that test */
@@ -752,7 +794,7 @@ DEV void wave_quantise_luma(Ctx *c, int lane, uint8_t *park /* 16 x QROW bytes o
 					for (int k = 0; k < 8; k++) cur[k] -= (dec >> k) & 1;
 				}
 			}
-			if (r < H && !low) {
+			if (r < H && !low && !(hand && r < H - 1)) {           /* (with `hand` only row 255 is left to them) */
 				{                                                  /* loop 2 */
 					unsigned P, N, PN, NN;
 					BS_PRED(P, cur, 4, (unsigned)(x - 4) < 4u); BS_PRED(N, cur, 4, (unsigned)(x + 7) < 4u);
@@ -967,14 +1009,15 @@ DEV void wave_quantise_luma(Ctx *c, int lane, uint8_t *park /* 16 x QROW bytes o
  * block -- so production leaves these 128 KB per image and loop out; the stage checks compare the plane and keep them. */
 /* ll2_done (second loop, the forked order): the emission in front of this kernel has left the LL2 cells of both planes (wave_emit_ll2, sim);
  * only the put-back of verbatim samples is left of the walk, where the synthesis behind this kernel does not make it */
-DEV void wave_dequant_sim_luma(Ctx *c, int part, int lane, const uint32_t *lut, bool from_save, bool keep_p, bool ll2_done = false)
+DEV void wave_dequant_sim_luma(Ctx *c, int part, int lane, const uint32_t *lut, bool from_save, bool keep_p, bool ll2_done = false, int16_t *hand = nullptr /* see wave_dequant_details */)
 {
 	PROF_BEGIN();
 	const int16_t *src = from_save ? c->l2save : c->proc;
 	const int ss = from_save ? H : W;
 	if (ll2_done) wave_ll2_verbatim(c, lane);
 	else wave_ll2(c, part, lane, keep_p, src, ss);
-	wave_dequant_details(c, part, lane, lut, keep_p, src, ss);
+	if (part) wave_dequant_details<false>(c, part, lane, lut, keep_p, src, ss);   /* (`part` is a constant of either caller: k_wave<WV_DQ1> holds this form alone) */
+	else wave_dequant_details<true>(c, part, lane, lut, keep_p, src, ss, hand);
 	if (!part) wave_shrink(c, lane);
 	if (!lane) PROF(c, part ? 1 : 7);
 }
