@@ -304,7 +304,8 @@ int nhw_dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_
 int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
                               const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status);
 /* the last region call on the handle: the selected tiles that were handed to the decoder (those of the NHW_OK rects and of the rects that
- * failed on a refused tile) and the tile-file bytes uploaded for them */
+ * failed on a refused tile) and the tile-file bytes uploaded for them.  After a window call (below): the UNIQUE tiles and the bytes of
+ * exactly those files */
 int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded);
 /* ---- decode at half or quarter scale straight from the wavelet pyramid ----
  * scale 1, 2 or 4; the tile side is T = 512 / scale and a file decodes to 3 T T bytes, in the byte order of the full decode.  Scale 1 is the
@@ -329,6 +330,39 @@ int nhw_picture_scaled_size(uint32_t width, uint32_t height, int scale, uint32_t
 int nhw_untile_pictures_scaled_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int n_tiles, int scale, void *stream);
 /* nhw_dec_pictures at a scale: picture i (ceil(W / scale) x ceil(H / scale) x 3 bytes, packed) lands at out + out_off[i] */
 int nhw_dec_pictures_scaled(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, int scale, uint8_t *out, const uint64_t *out_off, int32_t *status);
+/* ---- windows: rectangles of .nhwp pictures at scale 1, 2 or 4, every tile decoded once ----
+ * A window of a W x H picture at scale s is a rectangle x, y, width, height (width, height >= 1, x + width <= W', y + height <= H') in the
+ * coordinates of the scaled picture W' x H' = ceil(W / s) x ceil(H / s), the array nhw_dec_pictures_scaled returns at that scale (scale 1:
+ * nhw_dec_pictures); its result is that array's rows y .. y + height - 1, columns x .. x + width - 1, byte for byte.  With T = 512 / s it
+ * selects tile columns x / T .. (x + width - 1) / T times tile rows y / T .. (y + height - 1) / T of the picture's ordinary tile grid.
+ * nhw_window_tiles: the FULL picture's sides and a window in scaled coordinates -> the window's own tile count, or NHW_E_ARG for a side
+ * outside 1..65535, a scale other than 1, 2, 4, an empty rectangle or one not inside the scaled picture.  At scale 1 it is nhw_region_tiles. */
+int nhw_window_tiles(uint32_t pic_width, uint32_t pic_height, int scale, uint32_t x, uint32_t y, uint32_t width, uint32_t height);
+/* A use: tile (ty, tx) of the picture's grid, decoded into slot `slot` of the call's unique tiles, feeds window `region` of the table. */
+typedef struct { uint32_t region, slot, tx, ty; } nhw_window_use;   /* 16 bytes */
+/* The crop alone.  d_tiles holds the decoded tiles of the slots [tile0, tile0 + m), 3 T T bytes each (T = 512 / scale), 16-byte aligned;
+ * d_regs[0 .. n_regs) are nhw_region descriptors with x, y, width, height in scaled coordinates and pic_width, pic_height the SCALED
+ * picture's sides (first_tile is not read); d_uses[0 .. n_uses) the (window, tile) pairs, in any order.  Of a use, tile row rr is
+ * scaled-picture row T ty + rr; if y <= T ty + rr < y + height, its columns [max(T tx, x), min(T tx + T, x + width)) go to destination byte
+ * 3 (col - x) of row T ty + rr - y.  Writes exactly those bytes: never a byte outside [addr + r pitch, addr + r pitch + 3 width) of a window
+ * row r, never a read-modify-write.  A use is passed over, nothing stored, when its region is >= n_regs, its slot outside [tile0, tile0 + m),
+ * its (tx, ty) outside the window's selection, or its descriptor no window of a picture (a zero side, a scaled side above ceil(65535 / scale),
+ * x + width or y + height beyond the side).  Several uses may share a slot, and a table may hold the uses of other chunks.  No handle: the
+ * current device; stream NULL is the null stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_regs < 1,
+ * n_uses < 1, m < 1, tile0 < 0, an unaligned d_tiles, a scale other than 1, 2, 4. */
+int nhw_untile_windows_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
+                              int tile0, int m, int scale, void *stream);
+/* Host conveniences, synchronous: nhw_dec_regions / nhw_dec_regions_to_device for windows, all of one call at one scale.  The tiles of a call
+ * are the UNION of its windows' selections: a tile of a container is uploaded and decoded once, however many windows select it, and no other
+ * tile file is uploaded, decoded or looked at (but for the well-formedness check of the container).  Containers, rects, bgr / out_off,
+ * dst_addr / dst_pitch, the per-rect statuses and the call-level NHW_E_ARG cases are those of the region calls, with the rectangle checked
+ * against the scaled picture; NHW_E_ARG also for a scale other than 1, 2, 4, and at scales 2 and 4 for a handle with a debug stop set.  A
+ * window's status depends on its selected tiles alone: a tile the decoder refuses fails exactly the windows that select it (NHW_E_FORMAT).
+ * After a window call nhw_dec_last_region_stats reports the UNIQUE tiles handed to the decoder and the bytes of exactly those files. */
+int nhw_dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                    uint8_t *bgr, const uint64_t *out_off, int32_t *status);
+int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                              const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status);
 /* hipEvent timings of the last nhw_dec_batch_device call (events on its launch stream): the whole sequence, the entropy stages
  * (parse, prefix-code walk, un-zig-zag), the two level-1 luma synthesis passes and the colour kernel -- the last three are the kernels
  * SURVEY.md 8(d) prices against the HBM roofline for the decode path */

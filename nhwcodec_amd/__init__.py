@@ -95,6 +95,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_picture_scaled_size.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.nhw_untile_pictures_scaled_device.argtypes = [P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
     L.nhw_dec_pictures_scaled.argtypes = [P, P, P, ctypes.c_int, ctypes.c_int, P, P, P]
+    L.nhw_window_tiles.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int] + [ctypes.c_uint32] * 4
+    L.nhw_untile_windows_device.argtypes = [P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_dec_windows.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, P, P, P]
+    L.nhw_dec_windows_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, P, P, P]
     return L
 
 
@@ -186,6 +190,21 @@ def region_tiles(pic_width: int, pic_height: int, x: int, y: int, width: int, he
     if not (width >= 1 and height >= 1 and x >= 0 and y >= 0 and x + width <= pic_width and y + height <= pic_height):
         raise NhwError(f"the region {x}, {y}, {width} x {height} is empty or not inside the {pic_width} x {pic_height} picture")
     return ((x + width - 1) // 512 - x // 512 + 1) * ((y + height - 1) // 512 - y // 512 + 1)
+
+
+WINDOW_USE_DTYPE = [("region", "<u4"), ("slot", "<u4"), ("tx", "<u4"), ("ty", "<u4")]   # nhw_window_use
+
+
+def window_tiles(pic_width: int, pic_height: int, scale: int, x: int, y: int, width: int, height: int) -> int:
+    """the tiles the window x, y, width, height of a pic_width x pic_height picture at scale 1, 2 or 4 selects (nhw_window_tiles, DESIGN.md
+    section 15): the rectangle is in the coordinates of the scaled picture (scaled_size), whose tiles have the side T = 512 // scale: columns
+    x // T .. (x + width - 1) // T times rows y // T .. (y + height - 1) // T.  At scale 1 it is region_tiles."""
+    scale = _scale(scale, "window_tiles")
+    sw, sh = scaled_size(pic_width, pic_height, scale)
+    if not (width >= 1 and height >= 1 and x >= 0 and y >= 0 and x + width <= sw and y + height <= sh):
+        raise NhwError(f"the window {x}, {y}, {width} x {height} is empty or not inside the {sw} x {sh} picture ({pic_width} x {pic_height} at scale {scale})")
+    side = 512 // scale
+    return ((x + width - 1) // side - x // side + 1) * ((y + height - 1) // side - y // side + 1)
 
 
 def _picture_table(pictures, what, side=512):
@@ -919,52 +938,75 @@ class Decoder:
         if (status != 0).any():
             raise NhwError(f"per-region status {status.tolist()}")
 
-    def decode_regions(self, containers, rects):
-        """Rectangles of .nhwp pictures from only the tiles they touch (nhw_dec_regions): containers a list of containers (bytes), rects a
-        sequence of (container index, x, y, w, h) in the coordinates of decode_pictures' arrays -> a list of numpy uint8 [h, w, 3], region i
-        equal to decode_pictures(containers)[container][y:y + h, x:x + w].  Raises on any status that is not NHW_OK."""
+    def _regions_host(self, containers, rects, what, call):
+        """the host form of a region or window call: call(blob, offsets, n containers, rect table, n, out, out_off, status) -> rc"""
         import numpy as np
-        blob, offs, table = self._region_args(containers, rects, "decode_regions")
+        blob, offs, table = self._region_args(containers, rects, what)
         n = len(table)
         out_off = np.zeros(n + 1, np.uint64)
         out_off[1:] = np.cumsum(3 * table["width"].astype(np.uint64) * table["height"].astype(np.uint64))
         out = np.empty(max(int(out_off[n]), 1), np.uint8)
         status = np.empty(n, np.int32)
-        self._chk(self.lib.nhw_dec_regions(self.h, blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, out.ctypes.data,
-                                           out_off.ctypes.data, status.ctypes.data))
+        self._chk(call(blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
         self._region_raise(status)
         return [out[int(out_off[i]):int(out_off[i + 1])].reshape(int(r["height"]), int(r["width"]), 3) for i, r in enumerate(table)]
 
-    def decode_regions_device(self, containers, rects, out=None):
-        """decode_regions with the pixels left on the device (nhw_dec_regions_to_device): -> a list of uint8 CUDA tensors [h, w, 3] on this
-        decoder's device.  out: a list of preallocated tensors, one a rect, with strides (pitch >= 3 w, 3, 1) -- views into an [n, h, w, 3]
-        batch tensor work --, which are filled and returned.  The work is ordered after torch's current stream and complete on return."""
+    def _regions_device(self, containers, rects, out, what, call):
+        """the device form: call(blob, offsets, n containers, rect table, n, addresses, pitches, status) -> rc"""
         import numpy as np
         t = self.torch
-        blob, offs, table = self._region_args(containers, rects, "decode_regions_device")
+        blob, offs, table = self._region_args(containers, rects, what)
         n = len(table)
         dev = t.device("cuda", self.device)
         if out is None:
             out = [t.empty((int(r["height"]), int(r["width"]), 3), dtype=t.uint8, device=dev) for r in table]
         elif not isinstance(out, (list, tuple)) or len(out) != n:
-            raise NhwError(f"decode_regions_device: `out` must be a list of {n} tensors")
+            raise NhwError(f"{what}: `out` must be a list of {n} tensors")
         addr, pitch = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         for i, (x, r) in enumerate(zip(out, table)):
             h, w = int(r["height"]), int(r["width"])
             if not (isinstance(x, t.Tensor) and x.is_cuda and x.device == dev and x.dtype == t.uint8 and tuple(x.shape) == (h, w, 3)):
-                raise NhwError(f"decode_regions_device: out[{i}] is not a uint8 tensor [{h}, {w}, 3] on {dev}")
+                raise NhwError(f"{what}: out[{i}] is not a uint8 tensor [{h}, {w}, 3] on {dev}")
             if x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w):
-                raise NhwError(f"decode_regions_device: out[{i}] must have strides (pitch >= 3 w, 3, 1), got {tuple(x.stride())}")
+                raise NhwError(f"{what}: out[{i}] must have strides (pitch >= 3 w, 3, 1), got {tuple(x.stride())}")
             addr[i], pitch[i] = x.data_ptr(), x.stride(0) if h > 1 else 3 * w
         status = np.empty(n, np.int32)
         t.cuda.current_stream(dev).synchronize()                     # the call runs on the handle's own stream and waits for it
-        self._chk(self.lib.nhw_dec_regions_to_device(self.h, blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, addr.ctypes.data,
-                                                     pitch.ctypes.data, status.ctypes.data))
+        self._chk(call(blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, addr.ctypes.data, pitch.ctypes.data, status.ctypes.data))
         self._region_raise(status)
         return list(out)
 
+    def decode_regions(self, containers, rects):
+        """Rectangles of .nhwp pictures from only the tiles they touch (nhw_dec_regions): containers a list of containers (bytes), rects a
+        sequence of (container index, x, y, w, h) in the coordinates of decode_pictures' arrays -> a list of numpy uint8 [h, w, 3], region i
+        equal to decode_pictures(containers)[container][y:y + h, x:x + w].  Raises on any status that is not NHW_OK."""
+        return self._regions_host(containers, rects, "decode_regions", lambda *a: self.lib.nhw_dec_regions(self.h, *a))
+
+    def decode_regions_device(self, containers, rects, out=None):
+        """decode_regions with the pixels left on the device (nhw_dec_regions_to_device): -> a list of uint8 CUDA tensors [h, w, 3] on this
+        decoder's device.  out: a list of preallocated tensors, one a rect, with strides (pitch >= 3 w, 3, 1) -- views into an [n, h, w, 3]
+        batch tensor work --, which are filled and returned.  The work is ordered after torch's current stream and complete on return."""
+        return self._regions_device(containers, rects, out, "decode_regions_device", lambda *a: self.lib.nhw_dec_regions_to_device(self.h, *a))
+
+    def decode_windows(self, containers, rects, scale=1):
+        """Rectangles of .nhwp pictures at scale 1, 2 or 4, every tile decoded once (nhw_dec_windows): containers and
+        rects as for decode_regions, the rectangles in the coordinates of decode_pictures_scaled's arrays at that scale -> a list of numpy uint8
+        [h, w, 3], window i equal to decode_pictures_scaled(containers, scale)[container][y:y + h, x:x + w].  The tiles of the call are the union
+        of the windows' selections: a tile that several windows select is uploaded and decoded once (region_stats).  Raises on any status that
+        is not NHW_OK."""
+        scale = _scale(scale, "decode_windows")
+        return self._regions_host(containers, rects, "decode_windows", lambda *a: self.lib.nhw_dec_windows(self.h, *a[:5], scale, *a[5:]))
+
+    def decode_windows_device(self, containers, rects, scale=1, out=None):
+        """decode_windows with the pixels left on the device (nhw_dec_windows_to_device); out and the stream ordering as for
+        decode_regions_device."""
+        scale = _scale(scale, "decode_windows_device")
+        return self._regions_device(containers, rects, out, "decode_windows_device",
+                                    lambda *a: self.lib.nhw_dec_windows_to_device(self.h, *a[:5], scale, *a[5:]))
+
     def region_stats(self):
-        """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region call (nhw_dec_last_region_stats)"""
+        """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region or window call (nhw_dec_last_region_stats);
+        after a window call the tiles are the unique ones"""
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         self._chk(self.lib.nhw_dec_last_region_stats(self.h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value

@@ -1,5 +1,5 @@
 /* nhw_dec_hostpath.hip -- the decoder's host conveniences: files in host memory in, pictures out (nhw_dec_batch), pictures of any size and regions of them out of
- * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
+ * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
 #include "nhw_dec.h"
 
 /* the host paths' buffers: the blob (grow-only, room for `total` bytes of files) and, on the first call, the per-file arrays and the
@@ -200,6 +200,17 @@ struct RegionSource {
 	std::vector<uint64_t> start;                                 /* t + 1 entries */
 };
 
+static void source_look(RegionSource &c, const uint8_t *base, size_t len)   /* the first look at a container */
+{
+	if (c.state != 0) return;
+	c.state = nhw_container_parse(base, len, &c.w, &c.h, &c.t, &c.dir) == NHW_OK ? 1 : -1;
+	if (c.state == 1) {
+		c.start.resize((size_t)c.t + 1);
+		c.start[0] = 16 + 4 * (uint64_t)c.t;
+		for (int k = 0; k < c.t; k++) c.start[k + 1] = c.start[k] + dir_len(c.dir, k);
+	}
+}
+
 /* Both region calls: bgr / out_off (the regions packed in a device buffer of the handle, then downloaded) or dst_addr / dst_pitch (cropped
  * straight into the caller's device memory).  The selected tile files are gathered on the host -- a selection row tx0 .. tx1 is one
  * contiguous byte run of its container -- and go up as one blob; the decoder gets their offsets and lengths as it does for whole pictures,
@@ -225,14 +236,7 @@ static int dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
 		RegionSource &c = src[r.container];
 		const uint8_t *base = blob + off[r.container];
-		if (c.state == 0) {
-			c.state = nhw_container_parse(base, (size_t)(off[r.container + 1] - off[r.container]), &c.w, &c.h, &c.t, &c.dir) == NHW_OK ? 1 : -1;
-			if (c.state == 1) {
-				c.start.resize((size_t)c.t + 1);
-				c.start[0] = 16 + 4 * (uint64_t)c.t;
-				for (int k = 0; k < c.t; k++) c.start[k + 1] = c.start[k] + dir_len(c.dir, k);
-			}
-		}
+		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
 		if (c.state < 0) { status[i] = NHW_E_FORMAT; continue; }
 		const int nt = nhw_region_tiles(c.w, c.h, r.x, r.y, r.width, r.height);
 		if (nt < 1) continue;
@@ -283,6 +287,114 @@ extern "C" int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const 
 {
 	if (!dst_addr) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	return dec_regions(d, blob, off, n_containers, rects, n_rects, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_regions_to_device");
+}
+
+/* ---------------------------------------------------------------------------------------------- windows */
+/* Both window calls, as dec_regions serves both region calls: the same arguments plus the scale, the same statuses.  What differs: the
+ * tiles of the call are the union of the windows' selections.  A tile gets a slot when the first window selects it (slot_of, per
+ * container); only the files of those tiles are gathered, slot after slot, and decoded; every (window, tile) pair is a use, and the uses
+ * sorted by slot make the chunk [t0, t0 + m) of decoded tiles the owner of the contiguous range [first_use[t0], first_use[t0 + m)), which
+ * k_untile_window crops behind the chunk.  A window's status is the worst of its own tiles'. */
+static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
+                       const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who)
+{
+	const bool to_device = dst_addr != nullptr;
+	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (to_device ? !dst_pitch : (!bgr || !out_off))) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	if (scale != 1 && d->stop_after) { nhw_dec_err = "a scaled decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
+	for (int i = 0; i < nc; i++) if (off[i + 1] < off[i]) { nhw_dec_err = std::string(who) + ": off[] must not decrease"; return NHW_E_ARG; }
+	if (to_device) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_pitch[i] < 3ull * rects[i].width) { nhw_dec_err = std::string(who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
+	d->reg_tiles = d->reg_bytes = 0;
+	const uint32_t T = 512u / (uint32_t)scale;
+	std::vector<RegionSource> src((size_t)nc);
+	std::vector<std::vector<int32_t>> slot_of((size_t)nc);        /* per container: a tile's slot, -1 while no window has selected it */
+	std::vector<nhw_region> desc;
+	std::vector<int> which;                                      /* desc[k] is rect which[k] */
+	std::vector<nhw_window_use> uses;
+	std::vector<uint64_t> toff;
+	std::vector<uint32_t> tlen;
+	std::vector<uint8_t> files;                                  /* the unique tile files, slot after slot */
+	uint64_t bytes = 0;
+	for (int i = 0; i < nr; i++) {
+		const nhw_rect &r = rects[i];
+		status[i] = NHW_E_ARG;
+		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
+		RegionSource &c = src[r.container];
+		const uint8_t *base = blob + off[r.container];
+		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
+		if (c.state < 0) { status[i] = NHW_E_FORMAT; continue; }
+		const int nt = nhw_window_tiles(c.w, c.h, scale, r.x, r.y, r.width, r.height);
+		if (nt < 1) continue;
+		if (uses.size() + (size_t)nt > MAX_CALL_TILES) { nhw_dec_err = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
+		status[i] = NHW_OK;
+		uint32_t sw = 0, sh = 0;
+		nhw_picture_scaled_size(c.w, c.h, scale, &sw, &sh);           /* the table describes the destination */
+		desc.push_back({ to_device ? dst_addr[i] : bytes, to_device ? dst_pitch[i] : 3ull * r.width, r.x, r.y, r.width, r.height, sw, sh, 0, 0 });
+		which.push_back(i);
+		bytes += 3ull * r.width * r.height;
+		std::vector<int32_t> &slot = slot_of[r.container];
+		if (slot.empty()) slot.assign((size_t)c.t, -1);
+		const uint32_t nx = (c.w + 511) / 512;                        /* the grid does not change with the scale */
+		for (uint32_t ty = r.y / T; ty <= (r.y + r.height - 1) / T; ty++)
+			for (uint32_t tx = r.x / T; tx <= (r.x + r.width - 1) / T; tx++) {
+				const uint32_t k = ty * nx + tx;
+				if (slot[k] < 0) {
+					slot[k] = (int32_t)toff.size();
+					toff.push_back(files.size());
+					tlen.push_back(dir_len(c.dir, (int)k));
+					files.insert(files.end(), base + c.start[k], base + c.start[k + 1]);
+				}
+				uses.push_back({ (uint32_t)desc.size() - 1, (uint32_t)slot[k], tx, ty });
+			}
+	}
+	if (desc.empty()) return NHW_OK;
+	const int tiles = (int)toff.size(), ng = (int)desc.size(), nu = (int)uses.size();
+	std::vector<int> first_use((size_t)tiles + 1, 0);             /* sorted by slot (a counting sort): uses [first_use[t], first_use[t + 1]) are those of slot t */
+	for (const nhw_window_use &u : uses) first_use[u.slot + 1]++;
+	for (int t = 0; t < tiles; t++) first_use[t + 1] += first_use[t];
+	{
+		std::vector<nhw_window_use> sorted((size_t)nu);
+		std::vector<int> at(first_use.begin(), first_use.end() - 1);
+		for (const nhw_window_use &u : uses) sorted[(size_t)at[u.slot]++] = u;
+		uses.swap(sorted);
+	}
+	HIPCHK(hipSetDevice(d->device));
+	{ const int rc = host_buffers(d, files.size()); if (rc) return rc; }
+	const size_t desc_bytes = (size_t)ng * sizeof(nhw_region);     /* (a multiple of 16: the use table behind it is aligned) */
+	HIPCHK(nhw_grow(d->pic_desc, desc_bytes + (size_t)nu * sizeof(nhw_window_use)));
+	if (!to_device) {
+		HIPCHK(nhw_grow(d->pic_px, bytes));
+		for (nhw_region &g : desc) g.addr += (uint64_t)(uintptr_t)d->pic_px.p;
+	}
+	const nhw_region *d_desc = d->pic_desc.as<nhw_region>();
+	const nhw_window_use *d_uses = (const nhw_window_use *)(d->pic_desc.as<uint8_t>() + desc_bytes);
+	hipStream_t s = d->own_stream;
+	HIPCHK(hipMemcpyAsync(d->blob.p, files.data(), files.size(), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), desc_bytes, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync((void *)d_uses, uses.data(), (size_t)nu * sizeof(nhw_window_use), hipMemcpyHostToDevice, s));
+	d->reg_tiles = (uint64_t)tiles; d->reg_bytes = files.size();
+	std::vector<int32_t> tst;
+	{ const int rc = decode_tile_list(d, toff, tlen, scale, tst, [&](int t0, int m) {
+		return nhw_launch_untile_window(d->d_out, d_desc, ng, d_uses + first_use[t0], first_use[t0 + m] - first_use[t0], t0, m, scale, s); }); if (rc) return rc; }
+	for (const nhw_window_use &u : uses)
+		if (tiles_status(tst, (int)u.slot, (int)u.slot + 1) != NHW_OK) status[which[u.region]] = NHW_E_FORMAT;
+	std::vector<Span> sp;
+	if (!to_device) for (int k = 0; k < ng; k++)
+		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
+	return download_spans(bgr, sp);
+}
+
+extern "C" int nhw_dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                               uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+{
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, bgr, out_off, nullptr, nullptr, status, "nhw_dec_windows");
+}
+
+extern "C" int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                         const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status)
+{
+	if (!dst_addr) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_windows_to_device");
 }
 
 extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)

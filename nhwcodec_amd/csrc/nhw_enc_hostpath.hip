@@ -123,6 +123,17 @@ extern "C" int nhw_untile_regions_device(const void *d_tiles, const nhw_region *
 	return NHW_OK;
 }
 
+/* the crop of a window call: a table of (window, tile) uses over the decoded tiles of the slots [tile0, tile0 + m) */
+extern "C" int nhw_untile_windows_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
+                                         int tile0, int m, int scale, void *stream)
+{
+	if (const int rc = picture_args(d_regs, n_regs, tile0, m, d_tiles, "nhw_untile_windows_device")) return rc;
+	if (!d_uses || n_uses < 1 || n_uses > INT_MAX / 16) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = "nhw_untile_windows_device: the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_untile_window((const uint8_t *)d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 extern "C" int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, void *stream)
 {
 	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_sse_pictures_device")) return rc;

@@ -1,6 +1,6 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11, 12, 13, 14): the padding kernel k_tile_pad, its inverse
- * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crop k_untile_region, the picture-cropped error k_sse_crop, and the .nhwp container that
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 15): the padding kernel k_tile_pad, its inverse
+ * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, and the .nhwp container that
  * holds a picture's width, height and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
@@ -250,6 +250,28 @@ __global__ __launch_bounds__(TP_THREADS) void k_sse_crop(const uint8_t *__restri
 	}
 }
 
+/* The copy of the region and window kernels: `rows` rows of seg bytes (3 .. ROW), row q from src + q ROW (anywhere inside a tile row of ROW
+ * bytes) to dst + q pitch (any alignment, any pitch).  The 16-byte-aligned destination words that cover a row's bytes, whole ones as dwordx4,
+ * the ragged head and tail with store_part, the tile side through fetch; the two sides have independent phases, and the words a row needs
+ * (at most seg / 16 + 2) depend on seg: the rows x that many slots are dealt out flat over the threads (slot -> row by a multiply-high
+ * with the reciprocal, exact for the 32 x 97 slots a band can have), so that a 224-pixel crop does not walk 97 slots a row. */
+template <int ROW>
+__device__ __forceinline__ void copy_rows(uintptr_t src, uintptr_t dst, uint64_t pitch, int seg, uint32_t rows)
+{
+	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = rows * slots;   /* 2 .. 97 words cover seg bytes at any phase */
+	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots */
+	for (uint32_t i = threadIdx.x; i < total; i += TP_THREADS) {
+		const uint32_t q = __umulhi(i, rcp), k = i - q * slots;            /* row q of the band's wanted rows, word k of it */
+		const uintptr_t D0 = dst + (uint64_t)q * pitch, D1 = D0 + seg;
+		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
+		if (A >= D1) continue;
+		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
+		const uint4 v = fetch(src + (uintptr_t)q * ROW + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
+		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
+		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
+	}
+}
+
 /* ---- a rectangle of a picture from the tiles it touches ----
  * the region holding tile t of the call's running selection: the last descriptor with first_tile <= t (find_picture's search on the
  * 48-byte descriptors) */
@@ -269,11 +291,7 @@ __device__ __forceinline__ int find_region(const nhw_region *regs, int n, uint32
 
 /* Selected tile (ty, tx) of a region x, y, w, h: tile row rr is picture row 512 ty + rr, wanted if y <= row < y + h; of it the picture
  * columns [c0, c1) = [max(512 tx, x), min(512 tx + 512, x + w)) go from tile byte 3 (c0 - 512 tx) of the row to destination byte
- * 3 (c0 - x) of destination row (row - y).  The same copy as k_untile_crop -- the 16-byte-aligned destination words that cover the
- * bytes, whole ones as dwordx4, the ragged head and tail with store_part, the tile side through fetch -- but the source starts anywhere
- * inside a tile row, so the two sides have independent phases, and the words a row needs (at most seg / 16 + 2) depend on the region:
- * the band's wanted rows x that many slots are dealt out flat over the threads (slot -> row by a multiply-high with the reciprocal,
- * exact for the 32 x 97 slots a band can have), so that a 224-pixel crop does not walk 97 slots a row. */
+ * 3 (c0 - x) of destination row (row - y).  The same copy as k_untile_crop, but the source starts anywhere inside a tile row: copy_rows. */
 __global__ __launch_bounds__(TP_THREADS) void k_untile_region(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs, int tile0)
 {
 	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
@@ -292,18 +310,36 @@ __global__ __launch_bounds__(TP_THREADS) void k_untile_region(const uint8_t *__r
 	const int seg = 3 * (int)(c1 - c0);                                  /* 3 .. 1536 bytes a row */
 	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES) + (uintptr_t)(lo - 512 * ty) * 1536 + 3 * (c0 - 512 * tx);
 	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
-	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = (hi - lo) * slots;   /* 2 .. 97 words cover seg bytes at any phase */
-	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots */
-	for (uint32_t i = threadIdx.x; i < total; i += TP_THREADS) {
-		const uint32_t q = __umulhi(i, rcp), k = i - q * slots;            /* row q of the band's wanted rows, word k of it */
-		const uintptr_t D0 = dst + (uint64_t)q * g.pitch, D1 = D0 + seg;
-		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
-		if (A >= D1) continue;
-		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
-		const uint4 v = fetch(src + (uintptr_t)q * 1536 + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
-		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
-		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
-	}
+	copy_rows<1536>(src, dst, g.pitch, seg, hi - lo);
+}
+
+/* ---- windows: rectangles of pictures at scale 1, 2 or 4, every tile decoded once ----
+ * One workgroup per 32-row band of a USE, a (window, tile) pair of the table: tile (ty, tx) of the picture's grid, decoded into slot
+ * u.slot of the call's unique tiles, feeds window regs[u.region].  The descriptor is section 13's, in the coordinates of the scaled
+ * picture (pic_width x pic_height: the scaled sides; first_tile is not read); tile row rr is scaled-picture row T ty + rr, a row of tile
+ * bytes 3 T.  A use that names no region of the table, a slot outside the buffer's [tile0, tile0 + m), a tile outside the window's
+ * selection or a descriptor that is no window of a picture stores nothing.  The copy is k_untile_region's (copy_rows). */
+template <int T>
+__global__ __launch_bounds__(TP_THREADS) void k_untile_window(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs,
+                                                               const nhw_window_use *__restrict__ uses, int tile0, int m)
+{
+	constexpr int BANDS = T / TP_ROWS, ROW = 3 * T;
+	constexpr uint32_t SIDE_MAX = (65535 + 512 / T - 1) / (512 / T);     /* the largest scaled side: 65535, 32768, 16384 */
+	const nhw_window_use u = uses[blockIdx.x / BANDS];
+	if (u.region >= (uint32_t)n_regs || u.slot < (uint32_t)tile0 || u.slot - (uint32_t)tile0 >= (uint32_t)m) return;
+	const nhw_region g = regs[u.region];
+	if (!g.width || !g.height) return;
+	if (g.pic_width > SIDE_MAX || g.pic_height > SIDE_MAX || (uint64_t)g.x + g.width > g.pic_width || (uint64_t)g.y + g.height > g.pic_height) return;   /* not a window of a picture */
+	if (u.tx < g.x / T || u.tx > (g.x + g.width - 1) / T || u.ty < g.y / T || u.ty > (g.y + g.height - 1) / T) return;   /* not a tile of the window's selection */
+	/* the band's rows inside the window: scaled-picture rows [lo, hi) */
+	const uint32_t top = T * u.ty + (blockIdx.x % BANDS) * TP_ROWS;
+	const uint32_t lo = top > g.y ? top : g.y, hi = top + TP_ROWS < g.y + g.height ? top + TP_ROWS : g.y + g.height;
+	if (lo >= hi) return;
+	const uint32_t c0 = T * u.tx > g.x ? T * u.tx : g.x, c1 = T * u.tx + T < g.x + g.width ? T * u.tx + T : g.x + g.width;
+	const int seg = 3 * (int)(c1 - c0);                                  /* 3 .. 3 T bytes a row */
+	const uintptr_t src = (uintptr_t)(tiles + (size_t)(u.slot - (uint32_t)tile0) * (size_t)(ROW * T)) + (uintptr_t)(lo - T * u.ty) * ROW + 3 * (c0 - T * u.tx);
+	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
+	copy_rows<ROW>(src, dst, g.pitch, seg, hi - lo);
 }
 
 } /* namespace */
@@ -326,6 +362,15 @@ hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_p
 hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, hipStream_t s)
 {
 	k_untile_region<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, tile0);
+	return hipGetLastError();
+}
+
+hipError_t nhw_launch_untile_window(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses, int tile0, int m, int scale, hipStream_t s)
+{
+	if (scale == 1) k_untile_window<512><<<n_uses * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
+	else if (scale == 2) k_untile_window<256><<<n_uses * (256 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
+	else if (scale == 4) k_untile_window<128><<<n_uses * (128 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
+	else return hipErrorInvalidValue;
 	return hipGetLastError();
 }
 
@@ -360,6 +405,17 @@ extern "C" int nhw_region_tiles(uint32_t pic_width, uint32_t pic_height, uint32_
 	if (nhw_picture_tiles(pic_width, pic_height) < 1 || width < 1 || height < 1) return NHW_E_ARG;
 	if ((uint64_t)x + width > pic_width || (uint64_t)y + height > pic_height) return NHW_E_ARG;
 	return (int)(((x + width - 1) / 512 - x / 512 + 1) * ((y + height - 1) / 512 - y / 512 + 1));
+}
+
+/* the tiles a window x, y, w, h of the picture at scale s selects: the rectangle is in the coordinates of the scaled
+ * picture ceil(W / s) x ceil(H / s), whose tiles have the side T = 512 / s; at scale 1 it is nhw_region_tiles */
+extern "C" int nhw_window_tiles(uint32_t pic_width, uint32_t pic_height, int scale, uint32_t x, uint32_t y, uint32_t width, uint32_t height)
+{
+	uint32_t sw = 0, sh = 0;
+	if (nhw_picture_scaled_size(pic_width, pic_height, scale, &sw, &sh) != NHW_OK || width < 1 || height < 1) return NHW_E_ARG;
+	if ((uint64_t)x + width > sw || (uint64_t)y + height > sh) return NHW_E_ARG;
+	const uint32_t T = 512u / (uint32_t)scale;
+	return (int)(((x + width - 1) / T - x / T + 1) * ((y + height - 1) / T - y / T + 1));
 }
 
 /* A well-formed container: magic, version 1, zero reserved bytes, W and H in 1..65535, T = nhw_picture_tiles(W, H) lengths of 1 ..

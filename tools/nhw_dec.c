@@ -10,7 +10,8 @@
  * container of nhw-enc --picture to a bottom-up 24-bit BMP of the picture's own size; with --region X,Y,W,H behind it, only that rectangle
  * (X, Y from the left and the top of the picture as a viewer shows it), decoded from the tiles it touches.  --scale 2|4 (1: the same as
  * without it), anywhere on the line of a single file, --batch or --picture: the half- or quarter-scale picture straight from the wavelet
- * pyramid, under a header that carries the scaled size.
+ * pyramid, under a header that carries the scaled size.  --window S,X,Y,W,H behind --picture <in> <out>: that rectangle
+ * of the picture at scale S (1, 2 or 4), in the coordinates of the scaled picture, from the tiles it touches.
  */
 #include <dirent.h>
 #include <stdint.h>
@@ -35,6 +36,7 @@ static void show_usage(void)
 	"  tar:     nhw-dec --tar <in.tar> <out.tar>   (every x.nhw member of a ustar archive -> member x.bmp, in order)\n"
 	"  picture: nhw-dec --picture <in.nhwp> <image.bmp>   (a container of nhw-enc --picture, any size)\n"
 	"  region:  nhw-dec --picture <in.nhwp> <image.bmp> --region X,Y,W,H   (that rectangle only, X,Y from the top left; decodes the tiles it touches)\n"
+	"  window:  nhw-dec --picture <in.nhwp> <image.bmp> --window S,X,Y,W,H   (that rectangle of the picture at scale S = 1, 2 or 4, X,Y from the top left of the scaled picture)\n"
 	"  scale:   --scale 1|2|4 with a single file, --batch or --picture   (2, 4: the half- or quarter-scale picture, without the full reconstruction)\n",
 	PROGRAM);
 }
@@ -158,26 +160,36 @@ static int decode_tiles(int ny, int nx, const char *stem, const char *out_path)
 	return 0;
 }
 
-/* --region X,Y,W,H: four decimal numbers, nothing else; 0 if the argument is one */
-static int parse_region(const char *arg, uint32_t reg[4])
+/* n decimal numbers with commas between them, nothing else; 0 if the argument is that */
+static int parse_numbers(const char *arg, uint32_t *out, int n)
 {
 	int i;
-	for (i = 0; i < 4; i++) {
+	for (i = 0; i < n; i++) {
 		unsigned long v = 0;
 		int digits = 0;
 		for (; *arg >= '0' && *arg <= '9'; arg++, digits++) { v = v * 10 + (unsigned long)(*arg - '0'); if (v > 0xFFFFFFFFul) return 1; }
-		if (!digits || *arg != (i < 3 ? ',' : '\0')) return 1;
+		if (!digits || *arg != (i < n - 1 ? ',' : '\0')) return 1;
 		arg++;
-		reg[i] = (uint32_t)v;
+		out[i] = (uint32_t)v;
 	}
 	return 0;
+}
+
+/* --region X,Y,W,H: four decimal numbers, nothing else; 0 if the argument is one */
+static int parse_region(const char *arg, uint32_t reg[4]) { return parse_numbers(arg, reg, 4); }
+
+/* --window S,X,Y,W,H: five decimal numbers, nothing else, S = 1, 2 or 4; 0 if the argument is one */
+static int parse_window(const char *arg, uint32_t win[5])
+{
+	return parse_numbers(arg, win, 5) || (win[0] != 1 && win[0] != 2 && win[0] != 4);
 }
 
 /* --picture: the inverse of nhw-enc --picture.  The container's tiles are decoded and cropped by the library (nhw_dec_pictures); the
  * rows go out under the reference's 54-byte header with the size fields of the picture, each padded to 4 bytes.  With a region (X, Y from
  * the top left as a viewer shows the BMP, W, H; NULL: the whole picture) only the tiles it touches are decoded (nhw_dec_regions): the files
- * are bottom-up, so it is the library's rows H - Y - Hr .. H - Y - 1, and the BMP is that rectangle of the whole picture's BMP. */
-static int decode_picture(const char *in_path, const char *out_path, const uint32_t *region)
+ * are bottom-up, so it is the library's rows H - Y - Hr .. H - Y - 1, and the BMP is that rectangle of the whole picture's BMP.  With a
+ * window (S, X, Y, W, H; NULL: none) the same of the picture at scale S, in the scaled picture's coordinates (nhw_dec_windows). */
+static int decode_picture(const char *in_path, const char *out_path, const uint32_t *region, const uint32_t *window)
 {
 	uint8_t *blob = NULL, *pix, hdr[54], pad[3] = { 0, 0, 0 };
 	size_t len = 0;
@@ -190,7 +202,24 @@ static int decode_picture(const char *in_path, const char *out_path, const uint3
 	FILE *f;
 	if (read_file(in_path, &blob, &len)) return 1;
 	if (nhw_picture_info(blob, len, &width, &height) != NHW_OK) { printf("\nNot an .nhwp file\n"); free(blob); return 3; }
-	if (region) {
+	if (window) {
+		uint32_t sw = 0, sh = 0;
+		t = NHW_E_ARG;
+		nhw_picture_scaled_size(width, height, (int)window[0], &sw, &sh);
+		if (window[4] >= 1 && (uint64_t)window[2] + window[4] <= sh) {
+			rect.container = 0; rect.x = window[1]; rect.y = sh - window[2] - window[4]; rect.width = window[3]; rect.height = window[4];
+			t = nhw_window_tiles(width, height, (int)window[0], rect.x, rect.y, rect.width, rect.height);
+		}
+		if (t < 1) {
+			fprintf(stderr, "%s: --window %u,%u,%u,%u,%u is empty or not inside the %u x %u picture (%u x %u at scale %u)\n", PROGRAM, (unsigned)window[0],
+			        (unsigned)window[1], (unsigned)window[2], (unsigned)window[3], (unsigned)window[4], (unsigned)sw, (unsigned)sh, (unsigned)width,
+			        (unsigned)height, (unsigned)window[0]);
+			free(blob);
+			return 1;
+		}
+		width = rect.width; height = rect.height;
+	}
+	else if (region) {
 		t = NHW_E_ARG;
 		if (region[3] >= 1 && (uint64_t)region[1] + region[3] <= height) {
 			rect.container = 0; rect.x = region[0]; rect.y = height - region[1] - region[3]; rect.width = region[2]; rect.height = region[3];
@@ -218,7 +247,8 @@ static int decode_picture(const char *in_path, const char *out_path, const uint3
 	pix = (uint8_t *)malloc((size_t)row * height);
 	off[0] = 0; off[1] = len;
 	if (!pix || nhw_dec_create(0, t < 1024 ? t : 1024, &d) ||
-	    (region ? nhw_dec_regions(d, blob, off, 1, &rect, 1, pix, out_off, &status) :
+	    (window ? nhw_dec_windows(d, blob, off, 1, &rect, 1, (int)window[0], pix, out_off, &status) :
+	     region ? nhw_dec_regions(d, blob, off, 1, &rect, 1, pix, out_off, &status) :
 	     g_scale != 1 ? nhw_dec_pictures_scaled(d, blob, off, 1, g_scale, pix, out_off, &status) : nhw_dec_pictures(d, blob, off, 1, pix, out_off, &status))) {
 		fprintf(stderr, "%s: GPU decoder unavailable: %s\n", PROGRAM, nhw_dec_last_error());
 		return 2;
@@ -236,7 +266,7 @@ static int decode_picture(const char *in_path, const char *out_path, const uint3
 	}
 	fclose(f);
 	free(pix);
-	printf(region ? "%u x %u region\n" : "%u x %u picture\n", (unsigned)width, (unsigned)height);
+	printf(window ? "%u x %u window\n" : region ? "%u x %u region\n" : "%u x %u picture\n", (unsigned)width, (unsigned)height);
 	return 0;
 }
 
@@ -338,12 +368,21 @@ static int decode_tar(const char *in_path, const char *out_path)
 int main(int argc, char **argv)
 {
 	int a;
+	for (a = 1; a < argc; a++)                                        /* --window: behind --picture <in> <out> only, without --scale or --region; checked before any file is touched */
+		if (!strncmp(argv[a], "--window", 8)) {
+			uint32_t win[5];
+			int b;
+			for (b = 1; b < argc; b++) if (!strncmp(argv[b], "--scale", 7) || !strncmp(argv[b], "--region", 8)) { fprintf(stderr, "%s: --window carries its own scale and rectangle: not with --scale or --region\n", PROGRAM); return 1; }
+			if (strcmp(argv[a], "--window") || strcmp(argv[1], "--picture") || a != 4) { fprintf(stderr, "%s: --window S,X,Y,W,H goes behind --picture <in.nhwp> <image.bmp>\n", PROGRAM); return 1; }
+			if (argc != 6 || parse_window(argv[5], win)) { fprintf(stderr, "%s: --window wants S,X,Y,W,H: five decimal numbers, S = 1, 2 or 4\n", PROGRAM); return 1; }
+			return decode_picture(argv[2], argv[3], NULL, win);
+		}
 	for (a = 1; a < argc; a++)                                        /* --scale 1|2|4: anywhere; checked before any file is touched, then taken off the line */
 		if (!strncmp(argv[a], "--scale", 7)) {
 			int b;
 			if (strcmp(argv[a], "--scale") || a + 1 >= argc || strlen(argv[a + 1]) != 1 || !strchr("124", argv[a + 1][0])) { fprintf(stderr, "%s: --scale wants 1, 2 or 4\n", PROGRAM); return 1; }
 			g_scale = argv[a + 1][0] - '0';
-			for (b = 1; b < argc; b++) if (!strncmp(argv[b], "--region", 8)) { fprintf(stderr, "%s: --scale and --region do not go together\n", PROGRAM); return 1; }
+			for (b = 1; b < argc; b++) if (!strncmp(argv[b], "--region", 8)) { fprintf(stderr, "%s: --scale and --region do not go together (a rectangle at a scale: --window S,X,Y,W,H)\n", PROGRAM); return 1; }
 			if (argc > 3 && (!strcmp(argv[1], "--tar") || !strcmp(argv[1], "--tiles"))) { fprintf(stderr, "%s: --scale goes with a single file, --batch or --picture\n", PROGRAM); return 1; }
 			for (b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
 			argc -= 2;
@@ -354,7 +393,7 @@ int main(int argc, char **argv)
 			uint32_t reg[4];
 			if (strcmp(argv[a], "--region") || strcmp(argv[1], "--picture") || a != 4) { fprintf(stderr, "%s: --region X,Y,W,H goes behind --picture <in.nhwp> <image.bmp>\n", PROGRAM); return 1; }
 			if (argc != 6 || parse_region(argv[5], reg)) { fprintf(stderr, "%s: --region wants X,Y,W,H: four decimal numbers\n", PROGRAM); return 1; }
-			return decode_picture(argv[2], argv[3], reg);
+			return decode_picture(argv[2], argv[3], reg, NULL);
 		}
 	if (argc < 3) { show_usage(); return 0; }
 	if (!strcmp(argv[1], "--tar")) {
@@ -363,7 +402,7 @@ int main(int argc, char **argv)
 	}
 	if (!strcmp(argv[1], "--picture")) {
 		if (argc < 4) { show_usage(); return 1; }
-		return decode_picture(argv[2], argv[3], NULL);
+		return decode_picture(argv[2], argv[3], NULL, NULL);
 	}
 	if (!strcmp(argv[1], "--tiles")) {
 		int ny, nx;
