@@ -363,6 +363,44 @@ int nhw_dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_
                     uint8_t *bgr, const uint64_t *out_off, int32_t *status);
 int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                               const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status);
+/* ---- decode straight into training tensors ----
+ * The form the pixels leave the decoder in.  The byte entry points above write uint8 [S][S][3], B, G, R a pixel, rows in BMP file order; a
+ * tensor format names another element type, plane layout, channel order and row direction, and a scale and a bias per output channel.
+ *   dtype     NHW_T_U8, NHW_T_F16 (IEEE binary16), NHW_T_BF16 (bfloat16) or NHW_T_F32
+ *   layout    NHW_T_HWC: [S][S][3], as the byte path; NHW_T_CHW: [3][S][S]
+ *   channels  NHW_T_BGR: output channel 0 is the byte path's byte 0 of a pixel (blue in a BMP file), as the byte path; NHW_T_RGB: channels 0
+ *             and 2 change places
+ *   rows      NHW_T_ROWS_FILE: as the byte path; NHW_T_ROWS_REVERSED: output row r is row S - 1 - r of the byte path's output.
+ *             nhw_dec_bmp_header writes a POSITIVE height (512), and a BMP file with a positive height holds its rows bottom-up: the byte
+ *             path's row 0 is the picture's bottom row.  NHW_T_ROWS_REVERSED is therefore the top-down picture, row 0 = its top row, which
+ *             is what an image tensor usually is; NHW_T_ROWS_FILE is the bottom-up one.
+ *   scale[3], bias[3]   indexed by OUTPUT channel position (with NHW_T_RGB, index 0 belongs to R)
+ *   reserved  must be 0
+ * The value rule: for NHW_T_F16, NHW_T_BF16 and NHW_T_F32 the element for byte b of output channel c is fmaf((float) b, scale[c], bias[c])
+ * in single precision, rounded ONCE, to nearest even, to the output type.  For NHW_T_U8 scale must be 1 and bias 0, and the bytes go out
+ * unchanged.
+ * A format is refused with NHW_E_ARG, before anything is launched, for an unknown enum value, a non-zero reserved word, a scale or bias that is
+ * not finite, or NHW_T_U8 with another scale or bias. */
+enum { NHW_T_U8 = 0, NHW_T_F16 = 1, NHW_T_BF16 = 2, NHW_T_F32 = 3 };
+enum { NHW_T_HWC = 0, NHW_T_CHW = 1 };
+enum { NHW_T_BGR = 0, NHW_T_RGB = 1 };
+enum { NHW_T_ROWS_FILE = 0, NHW_T_ROWS_REVERSED = 1 };
+typedef struct { int32_t dtype, layout, channels, rows; float scale[3], bias[3]; uint32_t reserved; } nhw_tensor_format;   /* 44 bytes */
+/* nhw_dec_batch_device_scaled with a format: scale 1, 2 or 4 as there (S = 512 / scale), file i's tensor at d_out + i * 3 * S * S *
+ * sizeof(dtype); d_status and d_quality are those of the full decode, and a refused file leaves its slot untouched.  The entropy stages and
+ * every kernel up to the last are the byte path's, launched as there; the last kernel (k_dec_final, k_dec_scaled<S>) stores the format
+ * straight from the registers that hold R, G and B.  The format NHW_T_U8 / NHW_T_HWC / NHW_T_BGR / NHW_T_ROWS_FILE is the byte path itself.
+ * NHW_E_ARG, before anything is launched: a refused format, a d_out that is not 16-byte aligned, a handle with a debug stop set, and the
+ * cases of nhw_dec_batch_device_scaled.  Asynchronous on `stream`; one handle serves byte and tensor calls in any order. */
+int nhw_dec_batch_device_tensor(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream);
+/* The same formats for what is already bytes (the outputs of the picture, region and window calls): picture k of the table d_pics[0 ..
+ * n_pics) (as for nhw_tile_pictures_device: any W x H, pitch and alignment; first_tile is not read) goes, under the same rule, to a tensor of
+ * its own size -- [H][W][3] or [3][H][W] elements, packed -- at the device address d_out_addr[k] (a device array of n_pics addresses, each a
+ * multiple of the element size).  Reads exactly the pictures' bytes, never those between rows or beyond a picture.  An entry with a zero
+ * side, a side above 65535 or a misaligned address is passed over: nothing is written for it.  No handle: the current device; stream NULL is
+ * the null stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_pics outside 1 .. 2^24 and a refused format. */
+int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics, const nhw_tensor_format *fmt, const uint64_t *d_out_addr, void *stream);
 /* hipEvent timings of the last nhw_dec_batch_device call (events on its launch stream): the whole sequence, the entropy stages
  * (parse, prefix-code walk, un-zig-zag), the two level-1 luma synthesis passes and the colour kernel -- the last three are the kernels
  * SURVEY.md 8(d) prices against the HBM roofline for the decode path */

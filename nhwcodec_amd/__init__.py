@@ -35,6 +35,11 @@ class NhwError(RuntimeError):
     pass
 
 
+class CTensorFormat(ctypes.Structure):
+    """nhw_tensor_format (include/nhw_hip.h)"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("dtype", "layout", "channels", "rows")] + [("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3), ("reserved", ctypes.c_uint32)]
+
+
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise NhwError(f"{path} not built: run `python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc); there is no CPU fallback")
@@ -99,6 +104,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_untile_windows_device.argtypes = [P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
     L.nhw_dec_windows.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, P, P, P]
     L.nhw_dec_windows_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, P, P, P]
+    L.nhw_dec_batch_device_tensor.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P, P, P]
+    L.nhw_bytes_to_tensor_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
     return L
 
 
@@ -207,6 +214,88 @@ def window_tiles(pic_width: int, pic_height: int, scale: int, x: int, y: int, wi
     return ((x + width - 1) // side - x // side + 1) * ((y + height - 1) // side - y // side + 1)
 
 
+# ---------------------------------------------------------------- decode straight into training tensors
+NHW_T_U8, NHW_T_F16, NHW_T_BF16, NHW_T_F32 = 0, 1, 2, 3
+TENSOR_DTYPES = {"uint8": NHW_T_U8, "float16": NHW_T_F16, "bfloat16": NHW_T_BF16, "float32": NHW_T_F32}
+TENSOR_LAYOUTS = {"HWC": 0, "CHW": 1}             # NHW_T_HWC, NHW_T_CHW
+TENSOR_CHANNELS = {"BGR": 0, "RGB": 1}            # NHW_T_BGR, NHW_T_RGB
+TENSOR_ROWS = {"file": 0, "reversed": 1}          # NHW_T_ROWS_FILE, NHW_T_ROWS_REVERSED
+
+
+class TensorFormat:
+    """The form decoded pixels leave in (nhw_tensor_format): dtype torch.uint8 / float16 / bfloat16 / float32 (or its name), layout "CHW"
+    ([3, S, S]) or "HWC" ([S, S, 3], as the byte path), channels "RGB" or "BGR" (as the byte path), rows "file" (BMP file order, bottom-up,
+    as the byte path) or "reversed" (top-down: row 0 is the picture's top row), and per OUTPUT channel a scale and a bias: the element for
+    byte b of channel c is fmaf(float32(b), scale[c], bias[c]) in single precision, rounded once to dtype.  uint8 passes the bytes on and
+    takes scale 1, bias 0 only.  Either scale / bias (three numbers each, or one for all; default 1 and 0) or mean / std in units of 0..1
+    pixels, which give, in float32 arithmetic, scale = 1 / (255 * std) and bias = -mean / std (so that the element is (b / 255 - mean) / std
+    up to rounding).  The attributes scale and bias are the float32 constants the kernels get, as tuples of Python floats."""
+
+    def __init__(self, dtype="float32", layout="CHW", channels="RGB", rows="reversed", scale=None, bias=None, mean=None, std=None):
+        import numpy as np
+        name = dtype if isinstance(dtype, str) else str(dtype).replace("torch.", "")
+        if name not in TENSOR_DTYPES:
+            raise NhwError(f"TensorFormat: dtype must be uint8, float16, bfloat16 or float32, got {dtype!r}")
+        for what, v, table in (("layout", layout, TENSOR_LAYOUTS), ("channels", channels, TENSOR_CHANNELS), ("rows", rows, TENSOR_ROWS)):
+            if not isinstance(v, str) or v not in table:
+                raise NhwError(f"TensorFormat: {what} must be one of {sorted(table)}, got {v!r}")
+        if (mean is not None or std is not None) and (scale is not None or bias is not None):
+            raise NhwError("TensorFormat: give scale / bias or mean / std, not both")
+
+        def three(v, default, what):
+            if v is None:
+                v = default
+            try:
+                with np.errstate(over="ignore"):
+                    a = np.asarray(v, dtype=np.float64).astype(np.float32)
+            except (TypeError, ValueError):
+                raise NhwError(f"TensorFormat: {what} must be one number or three, got {v!r}") from None
+            if a.ndim == 0:
+                a = np.repeat(a, 3)
+            if a.shape != (3,):
+                raise NhwError(f"TensorFormat: {what} must be one number or three, got {v!r}")
+            if not np.all(np.isfinite(a)):
+                raise NhwError(f"TensorFormat: {what} must be finite in float32, got {v!r}")
+            return a
+
+        if mean is not None or std is not None:
+            m, sd = three(mean, 0.0, "mean"), three(std, 1.0, "std")
+            with np.errstate(all="ignore"):
+                sc = np.float32(1) / (np.float32(255) * sd)
+                bi = -m / sd
+            if not (np.all(np.isfinite(sc)) and np.all(np.isfinite(bi))):
+                raise NhwError(f"TensorFormat: mean {mean!r} / std {std!r} give no finite float32 scale and bias")
+        else:
+            sc, bi = three(scale, 1.0, "scale"), three(bias, 0.0, "bias")
+        if name == "uint8" and not (np.all(sc == 1) and np.all(bi == 0)):
+            raise NhwError("TensorFormat: uint8 passes the bytes on: scale must be 1 and bias 0")
+        self.dtype_name, self.layout, self.channels, self.rows = name, layout, channels, rows
+        self.scale = tuple(float(x) for x in sc)
+        self.bias = tuple(float(x) for x in bi)
+
+    @property
+    def dtype(self):
+        import torch
+        return getattr(torch, self.dtype_name)
+
+    def shape(self, height, width):
+        """the shape of one picture's tensor"""
+        return (3, height, width) if self.layout == "CHW" else (height, width, 3)
+
+    def c_struct(self) -> CTensorFormat:
+        return CTensorFormat(TENSOR_DTYPES[self.dtype_name], TENSOR_LAYOUTS[self.layout], TENSOR_CHANNELS[self.channels], TENSOR_ROWS[self.rows],
+                             (ctypes.c_float * 3)(*self.scale), (ctypes.c_float * 3)(*self.bias), 0)
+
+    def __repr__(self):
+        return f"TensorFormat({self.dtype_name}, {self.layout}, {self.channels}, rows={self.rows}, scale={self.scale}, bias={self.bias})"
+
+
+def _tensor_format(fmt, what):
+    if not isinstance(fmt, TensorFormat):
+        raise NhwError(f"{what}: `fmt` must be a TensorFormat, got {type(fmt).__name__}")
+    return fmt
+
+
 def _picture_table(pictures, what, side=512):
     """the checked nhw_picture table of a list of uint8 CUDA tensors [H, W, 3] with strides (pitch, 3, 1), on one device -> (table as an
     int64 CUDA tensor, total tiles, device).  side: the tile side (512; 256 or 128 for the pictures of a scaled decode)"""
@@ -289,6 +378,27 @@ def untile_scaled_pictures_device(tiles, pictures, scale):
         rc = L.nhw_untile_pictures_scaled_device(tiles.data_ptr(), table.data_ptr(), len(pictures), 0, n_tiles, scale, torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+
+
+def pictures_to_tensor_device(pictures, fmt):
+    """What is already bytes, to a tensor format in one pass (k_bytes_to_tensor, nhw_bytes_to_tensor_device): a list of uint8 CUDA tensors
+    [H, W, 3] as for tile_pictures_device (any size, any pitch: the outputs of decode_pictures*, of the region and window calls, crop views)
+    -> a list of new tensors of fmt.dtype, [3, H, W] or [H, W, 3] each, under TensorFormat's value rule.  Reads only the pictures' own bytes.
+    Ordered on torch's current stream."""
+    import numpy as np
+    import torch
+    what = "pictures_to_tensor_device"
+    fmt = _tensor_format(fmt, what)
+    table, _, dev = _picture_table(pictures, what)
+    outs = [torch.empty(fmt.shape(int(x.shape[0]), int(x.shape[1])), dtype=fmt.dtype, device=dev) for x in pictures]
+    addr = torch.from_numpy(np.array([o.data_ptr() for o in outs], dtype=np.uint64).view(np.int64)).to(dev)
+    L = _library()
+    c = fmt.c_struct()
+    with torch.cuda.device(dev):
+        rc = L.nhw_bytes_to_tensor_device(table.data_ptr(), len(pictures), ctypes.byref(c), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return outs
 
 
 def sse_pictures_device(tiles, pictures):
@@ -855,6 +965,41 @@ class Decoder:
             self._chk(self.lib.nhw_dec_batch_device_scaled(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, out.data_ptr(),
                                                            status.data_ptr(), quality.data_ptr(), st))
         px = out if out.dim() == 4 and tuple(out.shape) == (n, side, side, 3) else out.reshape(-1)[:n * 3 * side * side].view(n, side, side, 3)
+        return px, status, quality
+
+    def decode_tensor_device(self, arena, offsets, lengths, fmt, scale=1, out=None):
+        """decode_scaled_device straight into a tensor format (nhw_dec_batch_device_tensor): the last kernel stores
+        fmt's element type, layout, channel order and row direction from the registers that hold the pixel, with no pass over the bytes.
+        Arguments as for decode_scaled_device; fmt: a TensorFormat; out: a contiguous, 16-byte aligned tensor of fmt.dtype with at least
+        n * 3 * S * S elements, S = 512 // scale.  Returns (tensor [n, 3, S, S] or [n, S, S, 3], status[n], quality[n]) on the device; a
+        refused file's slot is left untouched."""
+        t = self.torch
+        what = "decode_tensor_device"
+        fmt = _tensor_format(fmt, what)
+        scale = _scale(scale, what)
+        side = 512 // scale
+        dev = f"cuda:{self.device}"
+        for name, x, dt in (("arena", arena, t.uint8), ("offsets", offsets, t.int64), ("lengths", lengths, t.int32)):
+            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous()):
+                raise NhwError(f"{what}: `{name}` must be a contiguous {dt} tensor on cuda:{self.device}")
+        n = offsets.numel()
+        if lengths.numel() != n or n < 1:
+            raise NhwError(f"{what}: offsets and lengths must have one entry per file")
+        if n > self.max_batch:
+            raise NhwError(f"{what}: {n} files for a decoder of max_batch {self.max_batch}")
+        shape = (n,) + fmt.shape(side, side)
+        if out is None:
+            out = t.empty(shape, dtype=fmt.dtype, device=dev)
+        elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == fmt.dtype and out.is_contiguous()
+                  and out.numel() >= n * 3 * side * side and out.data_ptr() % 16 == 0):
+            raise NhwError(f"{what}: `out` must be a contiguous, 16-byte aligned {fmt.dtype} tensor of n*{3 * side * side} elements on this decoder's device")
+        status = t.empty(n, dtype=t.int32, device=dev)
+        quality = t.empty(n, dtype=t.int32, device=dev)
+        c = fmt.c_struct()
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_dec_batch_device_tensor(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, ctypes.byref(c),
+                                                           out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
+        px = out if tuple(out.shape) == shape else out.reshape(-1)[:n * 3 * side * side].view(shape)
         return px, status, quality
 
     def decode_scaled(self, files, scale):

@@ -16,15 +16,17 @@
  *   k_dec_chroma   a chroma plane on one LDS residency: built from the value list, LL2 + exception samples, level 2, pair
  *                  corrections, level 1
  *   k_dec_marks, k_dec_sharpen
- *   k_dec_final    level 1 of the luma both ways, corrections, smoothing, chroma up-sampling, colour matrix -> BGR24
+ *   k_dec_final    level 1 of the luma both ways, corrections, smoothing, chroma up-sampling, colour matrix -> BGR24,
+ *                  or a tensor format (the store policies: DESIGN.md section 16)
  *
- * Everything is int16/uint8 arithmetic; the only floating point is the colour matrix (compiled with
- * -ffp-contract=off like the rest of the library).  No stage falls back to the host.
+ * Everything is int16/uint8 arithmetic; the only floating point is the colour matrix and a tensor format's scale and
+ * bias (compiled with -ffp-contract=off like the rest of the library).  No stage falls back to the host.
  */
 #include <assert.h>
 
 #include "nhw_dec.h"
 #include "nhw_dwt.h"
+#include "nhw_tensor.h"
 
 #define DW 512
 #define DH 256
@@ -2024,6 +2026,14 @@ __global__ void k_dec_colour_probe(const uint8_t *__restrict__ yuv, uint8_t *__r
 	for (int e = 0; e < 6; e++) reinterpret_cast<uint32_t *>(rgb + (size_t)i * 24)[e] = w[e];
 }
 
+/* ---------------------------------------------------------------------------------------------- store policies
+ * Where the last kernels' pixels go, in which order and as which type is a property of the store: k_dec_final and k_dec_scaled take it as a template
+ * parameter.  NhwStoreTensor<dtype, layout> (nhw_tensor.h) writes a tensor format: its put<S, N> takes N = 8 or 4 pixels of one row -- columns N c ..
+ * of row r of file img, an S x S picture -- as the 3 N bytes the byte path stores (B, G, R a pixel), and its constants are kernel arguments.
+ * StoreBytes is the byte path and only a tag: its stores stay spelled out in the kernels, and it adds no kernel argument, so that instantiation is
+ * the code it was before there were formats, instruction for instruction. */
+struct StoreBytes { static constexpr bool bytes = true; };
+
 /* ---------------------------------------------------------------------------------------------- final reconstruction, one kernel
  * Level-1 synthesis in both directions (decoder/wavelet_filterbank.c:52-357 as driven by nhw_decoder.c), the q > 21 corrections on the
  * plane between them (wavelet_filterbank.c:301-347), the 5-tap smoothing at the marked samples (nhw_decoder.c:859-876), the doubling of
@@ -2044,9 +2054,11 @@ __global__ void k_dec_colour_probe(const uint8_t *__restrict__ yuv, uint8_t *__r
 #define FM (FR / 2 + 1)              /* values of m a band computes: r0/2 - 1 .. r0/2 + FR/2 - 1 */
 #define F_T_BYTES (2 * DH * FBP * 2)
 #define F_LDS_BYTES (F_T_BYTES + FR * DW + 2 * (FR / 2 + 1) * DH)   /* T, the luma bytes, the chroma rows: 31 KB, five bands to a CU */
+template <class ST /* the store policy of the colour phase */, class... Fmt /* its kernel arguments: none for StoreBytes, NhwTensorArgs for a tensor format */>
 __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int dev_stop /* developer builds: end every band after phase dev_stop (0: run it all) */,
-                                                  int slice /* -1: production; else the band (nhw_host.h) */)
+                                                  int slice /* -1: production; else the band (nhw_host.h) */, Fmt... fmt)
 {
+	const ST st{ fmt... };
 #ifdef NHW_DEV
 #define F_STOP(i) do { if (dev_stop == (i)) return; } while (0)
 #else
@@ -2218,8 +2230,11 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 			}
 			uint32_t w[6];
 			colour8_q20(y8, c8[0], c8[1], w);
-			uint2 *o = reinterpret_cast<uint2 *>(out + (size_t)img * NHW_IMG_BYTES + (size_t)r * DW * 3 + 24 * t8);   /* consecutive lanes, consecutive 24-byte pieces */
-			o[0] = make_uint2(w[0], w[1]); o[1] = make_uint2(w[2], w[3]); o[2] = make_uint2(w[4], w[5]);
+			if constexpr (ST::bytes) {
+				uint2 *o = reinterpret_cast<uint2 *>(out + (size_t)img * NHW_IMG_BYTES + (size_t)r * DW * 3 + 24 * t8);   /* consecutive lanes, consecutive 24-byte pieces */
+				o[0] = make_uint2(w[0], w[1]); o[1] = make_uint2(w[2], w[3]); o[2] = make_uint2(w[4], w[5]);
+			}
+			else st.template put<DW, 8>(out, img, r, t8, w);
 		}
 	} else {
 		const int t = tid & 127;
@@ -2251,7 +2266,8 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 				w[(b0 + 2) >> 2] |= (uint32_t)B << (8 * ((b0 + 2) & 3));
 			}
 			/* consecutive lanes, consecutive 12-byte pieces: one store instruction writes 768 contiguous bytes of the row */
-			*reinterpret_cast<uint3 *>(out + (size_t)img * NHW_IMG_BYTES + (size_t)r * DW * 3 + 12 * t) = make_uint3(w[0], w[1], w[2]);
+			if constexpr (ST::bytes) *reinterpret_cast<uint3 *>(out + (size_t)img * NHW_IMG_BYTES + (size_t)r * DW * 3 + 12 * t) = make_uint3(w[0], w[1], w[2]);
+			else st.template put<DW, 4>(out, img, r, t, w);
 		}
 	}
 }
@@ -2270,8 +2286,9 @@ DEV uint32_t clip8x4(uint32_t a, uint32_t b)                      /* four int16 
 	return (uint32_t)clip8((int16_t)(a & 0xFFFFu)) | ((uint32_t)clip8((int16_t)(a >> 16)) << 8) | ((uint32_t)clip8((int16_t)(b & 0xFFFFu)) << 16) | ((uint32_t)clip8((int16_t)(b >> 16)) << 24);
 }
 DEV uint2 clip8x8(const uint4 &v) { return make_uint2(clip8x4(v.x, v.y), clip8x4(v.z, v.w)); }
-template <int S> __global__ __launch_bounds__(256) void k_dec_scaled(DecWs ws, uint8_t *out)
+template <int S, class ST = StoreBytes, class... Fmt /* as for k_dec_final */> __global__ __launch_bounds__(256) void k_dec_scaled(DecWs ws, uint8_t *out, Fmt... fmt)
 {
+	const ST st{ fmt... };
 	static_assert(S == 2 || S == 4, "half or quarter scale");
 	constexpr int T = DW / S, NB = T / SC_ROWS, TPR = T / 8, YP = T + 4;   /* tile side, bands a file, threads a row; LDS pitch of a luma row (S = 4): a band's four pieces of a line on different banks */
 	__shared__ __attribute__((aligned(16))) uint8_t ybuf[S == 4 ? SC_ROWS * YP : 16];
@@ -2318,8 +2335,11 @@ template <int S> __global__ __launch_bounds__(256) void k_dec_scaled(DecWs ws, u
 				w[b0 >> 2] |= (uint32_t)R << (8 * (b0 & 3)); w[(b0 + 1) >> 2] |= (uint32_t)G << (8 * ((b0 + 1) & 3)); w[(b0 + 2) >> 2] |= (uint32_t)B << (8 * ((b0 + 2) & 3));
 			}
 		}
-		uint2 *o = reinterpret_cast<uint2 *>(out + (size_t)img * (3 * T * T) + (size_t)r * (3 * T) + 24 * c8);
-		o[0] = make_uint2(w[0], w[1]); o[1] = make_uint2(w[2], w[3]); o[2] = make_uint2(w[4], w[5]);
+		if constexpr (ST::bytes) {
+			uint2 *o = reinterpret_cast<uint2 *>(out + (size_t)img * (3 * T * T) + (size_t)r * (3 * T) + 24 * c8);
+			o[0] = make_uint2(w[0], w[1]); o[1] = make_uint2(w[2], w[3]); o[2] = make_uint2(w[4], w[5]);
+		}
+		else st.template put<T, 8>(out, img, r, c8, w);
 	}
 }
 
@@ -2430,8 +2450,9 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 }
 
 /* one batch at scale 1 (the whole decode), 2 or 4: what the two entry points below share */
+struct TensorStore { int dtype, layout; NhwTensorArgs a; };         /* a checked format other than the byte path's */
 static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_bgr, int32_t *d_status,
-                     int32_t *d_quality, void *stream)
+                     int32_t *d_quality, void *stream, const TensorStore *tensor = nullptr /* the last kernel stores this format */)
 {
 	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
@@ -2471,7 +2492,8 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 	if (scale == 4) {                                                             /* quarter scale: the level-2 LL is in plane A already; the chroma planes up to their corrections */
 		CHROMA(5, s);
 		EV(2);
-		k_dec_scaled<4><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		if (!tensor) k_dec_scaled<4><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) { k_dec_scaled<4, decltype(st)><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr, st.a); });
 		EV(3);
 		d->timed = true;
 		goto done;
@@ -2496,7 +2518,8 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 		CHROMA(4, s);
 		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, s>>>(ws);
 		EV(2);
-		k_dec_scaled<2><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		if (!tensor) k_dec_scaled<2><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) { k_dec_scaled<2, decltype(st)><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr, st.a); });
 		EV(3);
 		d->timed = true;
 		goto done;
@@ -2525,7 +2548,10 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 #ifdef NHW_DEV
 		if (const char *e = getenv("NHW_FINAL_STOP")) dev_stop = atoi(e);
 #endif
-		nhw_slices(DW / FR, [&](int sl) { k_dec_final<<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl); });
+		if (!tensor) nhw_slices(DW / FR, [&](int sl) { k_dec_final<StoreBytes><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl); });
+		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) {     /* the same launch plan, the same LDS */
+			nhw_slices(DW / FR, [&](int sl) { k_dec_final<decltype(st)><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl, st.a); });
+		});
 	}
 	EV(3);
 	d->timed = true;
@@ -2548,6 +2574,19 @@ extern "C" int nhw_dec_batch_device_scaled(nhw_dec *d, const void *d_nhw, const 
                                            int32_t *d_status, int32_t *d_quality, void *stream)
 {
 	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
+}
+
+/* a batch into a tensor format: the byte path's launches, the last kernel with the format's store */
+extern "C" int nhw_dec_batch_device_tensor(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                           const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	TensorStore t;
+	if (const int rc = nhw_tensor_format_check(fmt, &t.a, nhw_dec_err)) return rc;
+	if ((uintptr_t)d_out & 15) { nhw_dec_err = "a tensor decode's output must be 16-byte aligned"; return NHW_E_ARG; }
+	if (d && d->stop_after) { nhw_dec_err = "a tensor decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
+	if (nhw_tensor_format_is_bytes(fmt)) return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
+	t.dtype = fmt->dtype; t.layout = fmt->layout;
+	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, &t);
 }
 
 extern "C" int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t)

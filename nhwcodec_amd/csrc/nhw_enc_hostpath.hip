@@ -4,6 +4,7 @@
  * of the picture kernels and the SSE.
  */
 #include "nhw_enc.h"
+#include "nhw_tensor.h"
 
 /* ------------------------------------------------------------------------------------------------ host path */
 __global__ void k_offsets(const uint32_t *sizes, uint64_t *offs, int n)
@@ -131,6 +132,16 @@ extern "C" int nhw_untile_windows_device(const void *d_tiles, const nhw_region *
 	if (!d_uses || n_uses < 1 || n_uses > INT_MAX / 16) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
 	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = "nhw_untile_windows_device: the scale must be 1, 2 or 4"; return NHW_E_ARG; }
 	HIPCHK(nhw_launch_untile_window((const uint8_t *)d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* the pictures of a table to tensors of a format, one pointwise pass */
+extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics, const nhw_tensor_format *fmt, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_out_addr || n_pics < 1 || n_pics > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	NhwTensorArgs a;
+	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
+	HIPCHK(nhw_launch_bytes_to_tensor(d_pics, n_pics, fmt->dtype, fmt->layout, a, d_out_addr, (hipStream_t)stream));
 	return NHW_OK;
 }
 

@@ -1,6 +1,6 @@
 /*
  * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 15): the padding kernel k_tile_pad, its inverse
- * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, and the .nhwp container that
+ * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16), and the .nhwp container that
  * holds a picture's width, height and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
@@ -13,9 +13,11 @@
  * k_untile_crop, of the tile rows it reads), and no store touches a byte outside a picture row.
  */
 #include <string.h>
+#include <type_traits>
 
 #include "nhw_host.h"
 #include "nhw_sse.h"
+#include "nhw_tensor.h"
 
 namespace {
 
@@ -342,7 +344,46 @@ __global__ __launch_bounds__(TP_THREADS) void k_untile_window(const uint8_t *__r
 	copy_rows<ROW>(src, dst, g.pitch, seg, hi - lo);
 }
 
+/* What is already bytes, to a tensor format: picture k of the table to [H][W][3] or [3][H][W] elements at out_addr[k], under the
+ * value rule of nhw_tensor.h.  The host knows no picture's size (the table lives in device memory), so a picture gets `per` workgroups whatever its
+ * size and workgroup `part` walks rows part, part + per, ...; a thread takes a pixel of the row at a time: three byte loads (any alignment and pitch:
+ * consecutive lanes on consecutive 3-byte pieces, never a byte outside the row) and three element stores -- in CHW consecutive lanes on consecutive
+ * elements of a plane, in HWC 3 elements apart.  Pictures and tensors have no alignment to build wider stores on (W is any number). */
+template <int DT, int CHW>
+__global__ __launch_bounds__(TP_THREADS) void k_bytes_to_tensor(const nhw_picture *__restrict__ pics, int per, NhwTensorArgs a, const uint64_t *__restrict__ out_addr)
+{
+	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+	const int k = blockIdx.x / per, part = blockIdx.x % per;
+	const nhw_picture p = pics[k];
+	const uint64_t oa = out_addr[k];
+	if (!p.width || !p.height || p.width > 65535u || p.height > 65535u || !oa || (oa & (sizeof(E) - 1))) return;
+	E *out = reinterpret_cast<E *>(oa);
+	const size_t W = p.width, H = p.height;
+	for (uint32_t r = part; r < p.height; r += per) {
+		const uint8_t *src = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)r * p.pitch);
+		const size_t rr = a.flip ? H - 1 - r : r;
+		for (uint32_t c = threadIdx.x; c < p.width; c += TP_THREADS) {
+			const uint32_t b0 = src[3 * c], b1 = src[3 * c + 1], b2 = src[3 * c + 2];
+			const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b2 : b0, a.scale[0], a.bias[0]);
+			const E e1 = (E)nhw_tensor_elem<DT>(b1, a.scale[1], a.bias[1]);
+			const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b0 : b2, a.scale[2], a.bias[2]);
+			if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
+			else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
+		}
+	}
+}
+
 } /* namespace */
+
+hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s)
+{
+	const int per = n_pics >= 256 ? 16 : n_pics >= 4 ? 4096 / n_pics : 1024;   /* workgroups a picture: some 4096 in all, 16 .. 1024 each */
+	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
+		k_bytes_to_tensor<DT, CHW><<<n_pics * per, TP_THREADS, 0, s>>>(d_pics, per, a, d_out_addr);
+	});
+	return hipGetLastError();
+}
 
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
 {

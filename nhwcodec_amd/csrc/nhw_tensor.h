@@ -1,0 +1,148 @@
+/*
+ * nhw_tensor.h -- the tensor formats of a decode (nhw_tensor_format in include/nhw_hip.h): the one value rule, the check
+ * of a format, and the store shapes the decoder's last kernels (nhw_dec.hip) and the pointwise kernel (nhw_picture.hip) share.
+ *
+ * Value rule: the element for byte b of output channel c is fmaf((float)b, scale[c], bias[c]) in single precision, rounded once, to nearest
+ * even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).
+ */
+#ifndef NHW_TENSOR_H
+#define NHW_TENSOR_H
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string>
+
+#include "../../include/nhw_hip.h"
+
+/* what a kernel gets of a format: dtype and layout are template parameters, the rest are kernel arguments (six floats and two flags, uniform) */
+struct NhwTensorArgs { float scale[3], bias[3]; int rgb, flip; };
+
+/* NHW_OK and the kernel's view of the format, or NHW_E_ARG with the reason in err */
+inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a, std::string &err)
+{
+	if (!f) { err = "bad argument"; return NHW_E_ARG; }
+	if (f->dtype < NHW_T_U8 || f->dtype > NHW_T_F32 || (f->layout != NHW_T_HWC && f->layout != NHW_T_CHW) || (f->channels != NHW_T_BGR && f->channels != NHW_T_RGB) ||
+	    (f->rows != NHW_T_ROWS_FILE && f->rows != NHW_T_ROWS_REVERSED)) { err = "tensor format: unknown dtype, layout, channels or rows value"; return NHW_E_ARG; }
+	if (f->reserved) { err = "tensor format: the reserved word must be 0"; return NHW_E_ARG; }
+	for (int c = 0; c < 3; c++) {
+		if (!isfinite(f->scale[c]) || !isfinite(f->bias[c])) { err = "tensor format: scale and bias must be finite"; return NHW_E_ARG; }
+		if (f->dtype == NHW_T_U8 && (f->scale[c] != 1.0f || f->bias[c] != 0.0f)) { err = "tensor format: NHW_T_U8 takes scale 1 and bias 0 only"; return NHW_E_ARG; }
+		a->scale[c] = f->scale[c]; a->bias[c] = f->bias[c];
+	}
+	a->rgb = f->channels == NHW_T_RGB; a->flip = f->rows == NHW_T_ROWS_REVERSED;
+	return NHW_OK;
+}
+inline bool nhw_tensor_format_is_bytes(const nhw_tensor_format *f)    /* what the byte entry points write */
+{
+	return f->dtype == NHW_T_U8 && f->layout == NHW_T_HWC && f->channels == NHW_T_BGR && f->rows == NHW_T_ROWS_FILE;
+}
+
+template <int DT> struct NhwElem { static constexpr int bytes = DT == NHW_T_U8 ? 1 : DT == NHW_T_F32 ? 4 : 2; };
+
+/* the element of byte b, in the low bits of a dword */
+template <int DT> __device__ __forceinline__ uint32_t nhw_tensor_elem(uint32_t b, float scale, float bias)
+{
+	if (DT == NHW_T_U8) return b;
+	const float x = __fmaf_rn((float)b, scale, bias);
+	if (DT == NHW_T_F32) return __float_as_uint(x);
+	if (DT == NHW_T_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);              /* v_cvt_f16_f32: to nearest even, f16 denormals kept */
+	/* bfloat16: the float's upper half, rounded to nearest even on the lower.  x is finite or an infinity the fma overflowed to (b, scale, bias are
+	 * finite), never a NaN, and an infinity's lower half is 0: the integer form is exact for every value that occurs */
+	const uint32_t u = __float_as_uint(x);
+	return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+/* K dwords to p in vectors of V dwords (p aligned to 4 V bytes; 12-byte vectors to 4): plain vector stores.  The 16- and 8-byte ones are native
+ * vector types, one store instruction each as written here: as structs of dwords the compiler takes them apart and groups the dwords anew. */
+typedef uint32_t nhw_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t nhw_u32x2 __attribute__((ext_vector_type(2)));
+template <int K, int V> __device__ __forceinline__ void nhw_store_words(uint8_t *p, const uint32_t *w)
+{
+	static_assert(K % V == 0 && V >= 1 && V <= 4, "whole vectors");
+#pragma unroll
+	for (int k = 0; k < K; k += V) {
+		if (V == 4) *reinterpret_cast<nhw_u32x4 *>(p + 4 * k) = (nhw_u32x4){ w[k], w[k + 1], w[k + 2], w[k + 3] };
+		else if (V == 3) *reinterpret_cast<uint3 *>(p + 4 * k) = make_uint3(w[k], w[k + 1], w[k + 2]);
+		else if (V == 2) *reinterpret_cast<nhw_u32x2 *>(p + 4 * k) = (nhw_u32x2){ w[k], w[k + 1] };
+		else *reinterpret_cast<uint32_t *>(p + 4 * k) = w[k];
+	}
+}
+
+/* N elements (in the low bits of e[]) packed into N * bytes / 4 dwords */
+template <int DT, int N> __device__ __forceinline__ void nhw_pack_elems(const uint32_t *e, uint32_t *w)
+{
+	constexpr int PER = 4 / NhwElem<DT>::bytes;
+	static_assert(N % PER == 0, "whole dwords");
+#pragma unroll
+	for (int k = 0; k < N / PER; k++) {
+		uint32_t v = 0;
+#pragma unroll
+		for (int j = 0; j < PER; j++) v |= e[PER * k + j] << (8 * NhwElem<DT>::bytes * j);
+		w[k] = v;
+	}
+}
+
+/* The store of N = 8 or 4 pixels of one row of an S x S picture, columns N c .. N c + N - 1 of byte-path row r of file img: `w` holds their 3 N bytes
+ * as the byte path stores them (B, G, R a pixel).  The thread owns
+ *   CHW: N consecutive elements in each of the three planes -- N * bytes each: 32 (two 16-byte stores), 16 (one), 8 or 4 bytes;
+ *   HWC: 3 N consecutive elements -- 96, 48 (16-byte stores), 24 (8-byte stores) or 12 bytes (one store).
+ * Consecutive lanes take consecutive pieces either way.  Every address is a multiple of its store's size when `out` is 16-byte aligned (12-byte
+ * stores: of 4). */
+template <int DT, int CHW> struct NhwStoreTensor {
+	static constexpr int dtype = DT, layout = CHW;
+	static constexpr bool bytes = false;
+	NhwTensorArgs a;
+	template <int S, int N> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
+	{
+		constexpr int EB = NhwElem<DT>::bytes;
+		const int rr = a.flip ? S - 1 - r : r;
+		uint32_t e[3][N];                                                   /* [output channel][pixel] */
+#pragma unroll
+		for (int px = 0; px < N; px++) {
+			uint32_t b[3];
+#pragma unroll
+			for (int ch = 0; ch < 3; ch++) b[ch] = (w[(3 * px + ch) >> 2] >> (8 * ((3 * px + ch) & 3))) & 0xFFu;
+			e[0][px] = nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
+			e[1][px] = nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
+			e[2][px] = nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
+		}
+		uint8_t *base = out + (size_t)img * (3 * S * S * EB);
+		if (CHW) {
+			constexpr int K = N * EB / 4;                                   /* dwords a plane: 8, 4, 2 or 1 */
+#pragma unroll
+			for (int oc = 0; oc < 3; oc++) {
+				uint32_t v[K];
+				nhw_pack_elems<DT, N>(e[oc], v);
+				nhw_store_words<K, (K > 4 ? 4 : K)>(base + ((size_t)oc * S * S + (size_t)rr * S + N * c) * EB, v);
+			}
+		} else {
+			constexpr int K = 3 * N * EB / 4;                               /* 24, 12, 6 or 3 dwords */
+			uint32_t il[3 * N], v[K];
+#pragma unroll
+			for (int px = 0; px < N; px++) { il[3 * px] = e[0][px]; il[3 * px + 1] = e[1][px]; il[3 * px + 2] = e[2][px]; }
+			nhw_pack_elems<DT, 3 * N>(il, v);
+			nhw_store_words<K, (K % 4 == 0 ? 4 : K == 6 ? 2 : 3)>(base + ((size_t)rr * S + N * c) * (3 * EB), v);
+		}
+	}
+};
+
+/* f(NhwStoreTensor<dtype, layout>{ a }) for a checked format */
+template <class F> inline void nhw_with_tensor_store(int dtype, int layout, const NhwTensorArgs &a, F &&f)
+{
+	switch (2 * dtype + layout) {
+	case 2 * NHW_T_U8 + NHW_T_HWC: f(NhwStoreTensor<NHW_T_U8, NHW_T_HWC>{ a }); break;
+	case 2 * NHW_T_U8 + NHW_T_CHW: f(NhwStoreTensor<NHW_T_U8, NHW_T_CHW>{ a }); break;
+	case 2 * NHW_T_F16 + NHW_T_HWC: f(NhwStoreTensor<NHW_T_F16, NHW_T_HWC>{ a }); break;
+	case 2 * NHW_T_F16 + NHW_T_CHW: f(NhwStoreTensor<NHW_T_F16, NHW_T_CHW>{ a }); break;
+	case 2 * NHW_T_BF16 + NHW_T_HWC: f(NhwStoreTensor<NHW_T_BF16, NHW_T_HWC>{ a }); break;
+	case 2 * NHW_T_BF16 + NHW_T_CHW: f(NhwStoreTensor<NHW_T_BF16, NHW_T_CHW>{ a }); break;
+	case 2 * NHW_T_F32 + NHW_T_HWC: f(NhwStoreTensor<NHW_T_F32, NHW_T_HWC>{ a }); break;
+	default: f(NhwStoreTensor<NHW_T_F32, NHW_T_CHW>{ a }); break;
+	}
+}
+
+/* nhw_picture.hip: every picture of the table to a tensor of its own size, one pass */
+hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s);
+
+#endif
