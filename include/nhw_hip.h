@@ -401,6 +401,49 @@ int nhw_dec_batch_device_tensor(nhw_dec *d, const void *d_nhw, const uint64_t *d
  * side, a side above 65535 or a misaligned address is passed over: nothing is written for it.  No handle: the current device; stream NULL is
  * the null stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_pics outside 1 .. 2^24 and a refused format. */
 int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics, const nhw_tensor_format *fmt, const uint64_t *d_out_addr, void *stream);
+
+/* ---- encode straight from training tensors ----
+ * The mirror of the section above: the encoder reads its pictures under an nhw_tensor_format -- the same struct, the same enums.  For this
+ * direction the format says how the INPUT tensor is laid out, and scale[c], bias[c] are indexed by the TENSOR's channel c.
+ *
+ * The value rule (the whole specification).  For element x of tensor channel c:
+ *   1. x is widened exactly to float32: NHW_T_F16 as IEEE binary16 with its denormals, NHW_T_BF16 as bits << 16, NHW_T_U8 as the integer;
+ *   2. y = fmaf(x, scale[c], bias[c]) in single precision, ONE rounding, denormals honoured;
+ *   3. the byte is 0 if y is a NaN; otherwise rint(y), ties to even, clamped to 0 .. 255 -- the clamp in float, before the conversion to an
+ *      integer: -inf and every negative give 0, +inf and everything from 255.5 on give 255;
+ *   4. NHW_T_U8 takes scale 1 and bias 0 only and passes the byte on: a pure permutation.
+ * Channels and rows: with NHW_T_RGB tensor channel 0 is R and goes to byte 2 of the pixel; with NHW_T_ROWS_REVERSED tensor row r is row
+ * H - 1 - r of the byte picture (S - 1 - r in a batch of 512 x 512 pictures).
+ * Everything downstream is defined through those bytes: nhw_enc_batch_device_tensor is nhw_enc_batch_device of them, byte for byte (files,
+ * sizes, status), and nhw_tile_tensors_device is nhw_tile_pictures_device of those byte pictures, so the edge replication acts on the
+ * converted picture.  A format is refused with NHW_E_ARG, before anything is launched or allocated, for the reasons given above
+ * nhw_tensor_format. */
+
+/* n contiguous 512 x 512 pictures, [n][3][512][512] or [n][512][512][3] elements at d_in, to n * NHW_IMG_BYTES bytes at d_bgr as the byte entry
+ * points take them.  Both pointers 16-byte aligned.  No handle: the current device; stream NULL is the null stream.  Asynchronous, and may be
+ * captured in a graph.  NHW_E_ARG for NULL or misaligned pointers, n outside 1 .. 2^22 and a refused format.  (The byte format U8 / HWC / BGR /
+ * ROWS_FILE is a plain copy.) */
+int nhw_tensor_to_bytes_device(const void *d_in, int n, const nhw_tensor_format *fmt, void *d_bgr, void *stream);
+/* nhw_enc_batch_device with a format in front of it: d_in as for nhw_tensor_to_bytes_device (16-byte aligned), the other arguments as for
+ * nhw_enc_batch_device.  The bytes go to a scratch of max_batch * NHW_IMG_BYTES bytes that the handle owns: the FIRST tensor call on a
+ * handle allocates it (so make that call before any graph capture) and nhw_enc_destroy frees it.  The conversion and the encode are ordered on
+ * `stream`; byte and tensor calls on one handle work in any order.  The format U8 / HWC / BGR / ROWS_FILE routes to nhw_enc_batch_device itself,
+ * with no copy and no scratch.  NHW_E_ARG, before anything is launched or allocated: a refused format, a misaligned d_in, and the cases of
+ * nhw_enc_batch_device (NULL pointers, n outside 1 .. max_batch); NHW_E_QUALITY as there. */
+int nhw_enc_batch_device_tensor(nhw_enc *e, const void *d_in, int n, const nhw_tensor_format *fmt, int quality,
+                                void *d_out, int32_t *d_sizes, int32_t *d_status, void *stream);
+/* Tensor pictures of any size (sides 1 .. 65535): addr = the device address of element (channel 0, row 0, column 0), pitch = bytes between rows,
+ * plane = bytes between channel planes (read for NHW_T_CHW only; an NHW_T_HWC pixel is 3 consecutive elements and consecutive pixels of a row
+ * follow each other), first_tile as in nhw_picture.  Crop views therefore work without a copy: x[:, y0:y1, x0:x1] of a larger CHW tensor,
+ * x[y0:y1, x0:x1, :] of an HWC one. */
+typedef struct { uint64_t addr, pitch, plane; uint32_t width, height, first_tile, reserved; } nhw_tensor_picture;   /* 40 bytes */
+/* nhw_tile_pictures_device for tensor pictures: the tiles [tile0, tile0 + m) of the byte pictures the value rule makes of d_pics[0 .. n_pics)
+ * (a device table, first_tile ascending) to d_tiles (m * NHW_IMG_BYTES bytes, 16-byte aligned).  Reads only elements of the pictures, never
+ * between rows or beyond a view.  An entry with a zero side, a side above 65535, or an address, pitch or (CHW) plane that is no multiple of the
+ * element size is passed over: its tiles are not written.  No handle: the current device; stream NULL is the null stream.  Asynchronous, and may
+ * be captured in a graph.  NHW_E_ARG as for nhw_tile_pictures_device, and for a refused format. */
+int nhw_tile_tensors_device(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m,
+                            const nhw_tensor_format *fmt, void *d_tiles, void *stream);
 /* hipEvent timings of the last nhw_dec_batch_device call (events on its launch stream): the whole sequence, the entropy stages
  * (parse, prefix-code walk, un-zig-zag), the two level-1 luma synthesis passes and the colour kernel -- the last three are the kernels
  * SURVEY.md 8(d) prices against the HBM roofline for the decode path */

@@ -106,6 +106,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_dec_windows_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, P, P, P]
     L.nhw_dec_batch_device_tensor.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P, P, P]
     L.nhw_bytes_to_tensor_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
+    L.nhw_tensor_to_bytes_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
+    L.nhw_enc_batch_device_tensor.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(CTensorFormat), ctypes.c_int, P, P, P, P]
+    L.nhw_tile_tensors_device.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
     return L
 
 
@@ -286,6 +289,20 @@ class TensorFormat:
         return CTensorFormat(TENSOR_DTYPES[self.dtype_name], TENSOR_LAYOUTS[self.layout], TENSOR_CHANNELS[self.channels], TENSOR_ROWS[self.rows],
                              (ctypes.c_float * 3)(*self.scale), (ctypes.c_float * 3)(*self.bias), 0)
 
+    def inverted(self):
+        """The format that ENCODES what a decode under this one produced: the same dtype, layout, channels and rows, and in float32 arithmetic
+        scale' = 1 / scale and bias' = -bias / scale, so that fmaf(fmaf(b, scale, bias), scale', bias') lies near b.  NhwError if a scale is 0 or
+        a result is not finite in float32."""
+        import numpy as np
+        sc, bi = np.array(self.scale, np.float32), np.array(self.bias, np.float32)
+        if np.any(sc == 0):
+            raise NhwError(f"TensorFormat.inverted: a scale of 0 has no inverse: {self.scale}")
+        with np.errstate(all="ignore"):
+            isc, ibi = np.float32(1) / sc, -bi / sc
+        if not (np.all(np.isfinite(isc)) and np.all(np.isfinite(ibi))):
+            raise NhwError(f"TensorFormat.inverted: scale {self.scale} / bias {self.bias} give no finite float32 inverse")
+        return TensorFormat(self.dtype_name, self.layout, self.channels, self.rows, scale=tuple(float(x) for x in isc), bias=tuple(float(x) + 0.0 for x in ibi))
+
     def __repr__(self):
         return f"TensorFormat({self.dtype_name}, {self.layout}, {self.channels}, rows={self.rows}, scale={self.scale}, bias={self.bias})"
 
@@ -399,6 +416,96 @@ def pictures_to_tensor_device(pictures, fmt):
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return outs
+
+
+TENSOR_PICTURE_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("plane", "<u8"), ("width", "<u4"), ("height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_tensor_picture
+
+
+def _tensor_batch(x, fmt, what, device=None):
+    """x: a contiguous, 16-byte aligned CUDA tensor [n, 3, 512, 512] or [n, 512, 512, 3] of fmt.dtype (on cuda:device, if given) -> n"""
+    import torch
+    shape = fmt.shape(512, 512)
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and tuple(x.shape[1:]) == shape and x.shape[0] >= 1):
+        raise NhwError(f"{what} wants a tensor of shape [n, {', '.join(map(str, shape))}] for {fmt.layout}, got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if x.dtype != fmt.dtype:
+        raise NhwError(f"{what}: the batch is {x.dtype}, the format {fmt.dtype}")
+    if not x.is_cuda or (device is not None and x.device.index != device):
+        raise NhwError(f"{what}: the batch is on {x.device}, not on " + ("a GPU" if device is None else f"cuda:{device}"))
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        raise NhwError(f"{what}: the batch must be contiguous and 16-byte aligned")
+    return int(x.shape[0])
+
+
+def tensor_to_bytes_device(x, fmt):
+    """The pictures the encoder makes of a tensor batch (k_tensor_to_bytes, nhw_tensor_to_bytes_device): x, a contiguous
+    CUDA tensor [n, 3, 512, 512] (fmt.layout "CHW") or [n, 512, 512, 3] of fmt.dtype, read under fmt -> uint8 [n, 512, 512, 3] as encode_device
+    and the fit searches take them.  The byte of element x of tensor channel c is rint(fmaf(float32(x), scale[c], bias[c])), ties to even,
+    clamped to 0 .. 255, 0 for a NaN; uint8 passes the bytes on.  Ordered on torch's current stream."""
+    import torch
+    what = "tensor_to_bytes_device"
+    fmt = _tensor_format(fmt, what)
+    n = _tensor_batch(x, fmt, what)
+    out = torch.empty((n, 512, 512, 3), dtype=torch.uint8, device=x.device)
+    L = _library()
+    c = fmt.c_struct()
+    with torch.cuda.device(x.device):
+        rc = L.nhw_tensor_to_bytes_device(x.data_ptr(), n, ctypes.byref(c), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
+
+
+def _tensor_picture_table(tensors, fmt, what):
+    """the checked nhw_tensor_picture table of a list of CUDA tensors [3, H, W] (strides (plane, pitch, 1)) or [H, W, 3] (strides (pitch, 3, 1))
+    of fmt.dtype on one device -> (table as an int64 CUDA tensor, total tiles, device)"""
+    import numpy as np
+    import torch
+    chw = fmt.layout == "CHW"
+    form = "[3, H, W]" if chw else "[H, W, 3]"
+    if not isinstance(tensors, (list, tuple)) or not tensors:
+        raise NhwError(f"{what} wants a non-empty list of {fmt.dtype_name} CUDA tensors {form}")
+    dev = tensors[0].device if isinstance(tensors[0], torch.Tensor) else None
+    table = np.zeros(len(tensors), TENSOR_PICTURE_DTYPE)
+    es = fmt.dtype.itemsize
+    tiles = 0
+    for i, x in enumerate(tensors):
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == fmt.dtype and x.dim() == 3 and x.shape[0 if chw else 2] == 3):
+            raise NhwError(f"{what}: picture {i} is not a {fmt.dtype_name} CUDA tensor {form}")
+        if x.device != dev:
+            raise NhwError(f"{what}: picture {i} is on {x.device}, picture 0 on {dev}")
+        h, w = (int(x.shape[1]), int(x.shape[2])) if chw else (int(x.shape[0]), int(x.shape[1]))
+        t = picture_tiles(w, h)
+        if chw:
+            ok = (w == 1 or x.stride(2) == 1) and (h == 1 or x.stride(1) >= w) and x.stride(0) >= 0
+            pitch, plane = (x.stride(1) if h > 1 else w) * es, x.stride(0) * es
+        else:
+            ok = x.stride(2) == 1 and (w == 1 or x.stride(1) == 3) and (h == 1 or x.stride(0) >= 3 * w)
+            pitch, plane = (x.stride(0) if h > 1 else 3 * w) * es, 0
+        if not ok:
+            raise NhwError(f"{what}: picture {i} must have strides " + ("(plane, pitch >= W, 1)" if chw else "(pitch >= 3 W, 3, 1)") + f", got {tuple(x.stride())}")
+        table[i] = (x.data_ptr(), pitch, plane, w, h, tiles, 0)
+        tiles += t
+    return torch.from_numpy(table.view(np.int64).copy()).to(dev), tiles, dev
+
+
+def tile_tensors_device(tensors, fmt):
+    """tile_pictures_device for tensor pictures (k_tile_pad_tensor, nhw_tile_tensors_device): a list of CUDA tensors of
+    fmt.dtype on one device, [3, H, W] with element stride 1 along W (any row and plane stride: x[:, y0:y1, x0:x1] of a larger tensor works
+    without a copy) or [H, W, 3] with strides (pitch, 3, 1), any H and W up to 65535 -> tiles uint8 [T, 512, 512, 3] of the byte pictures
+    tensor_to_bytes_device's rule makes of them, padded by edge replication, picture after picture.  Reads only the pictures' own elements.
+    Ordered on torch's current stream; feeds Encoder.encode_device and encode_fit_device."""
+    import torch
+    what = "tile_tensors_device"
+    fmt = _tensor_format(fmt, what)
+    table, tiles, dev = _tensor_picture_table(tensors, fmt, what)
+    out = torch.empty((tiles, 512, 512, 3), dtype=torch.uint8, device=dev)
+    L = _library()
+    c = fmt.c_struct()
+    with torch.cuda.device(dev):
+        rc = L.nhw_tile_tensors_device(table.data_ptr(), len(tensors), 0, tiles, ctypes.byref(c), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
 
 
 def sse_pictures_device(tiles, pictures):
@@ -532,6 +639,21 @@ class Encoder:
         o, sizes, status = self._device_outputs("encode_device", n, out)
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_enc_batch_device(self.h, bgr.data_ptr(), n, quality, o.data_ptr(), sizes.data_ptr(), status.data_ptr(), st))
+        return o, sizes, status
+
+    def encode_tensor_device(self, x, fmt, quality: int = QUALITY_DEFAULT, out=None):
+        """encode_device straight from a tensor batch (nhw_enc_batch_device_tensor): x as for tensor_to_bytes_device, on
+        this encoder's device.  The files, sizes and status are those of encode_device(tensor_to_bytes_device(x, fmt)), byte for byte; the bytes
+        go through a scratch the handle allocates on its first tensor call.  Returns (out[n,OUT_STRIDE], sizes[n], status[n]) on device."""
+        what = "encode_tensor_device"
+        fmt = _tensor_format(fmt, what)
+        n = _tensor_batch(x, fmt, what, self.device)
+        if n > self.max_batch:
+            raise NhwError(f"{what}: {n} pictures for an encoder of max_batch {self.max_batch}")
+        o, sizes, status = self._device_outputs(what, n, out)
+        c = fmt.c_struct()
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_enc_batch_device_tensor(self.h, x.data_ptr(), n, ctypes.byref(c), quality, o.data_ptr(), sizes.data_ptr(), status.data_ptr(), st))
         return o, sizes, status
 
     def encode(self, images, quality: int = QUALITY_DEFAULT):

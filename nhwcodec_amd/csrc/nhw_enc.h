@@ -53,6 +53,7 @@ struct nhw_enc {
 	uint8_t *d_in, *d_out, *d_compact;
 	uint32_t *d_sizes; int32_t *d_status; uint64_t *d_offs;
 	int conv_cap;
+	uint8_t *d_tensor_bytes;      /* nhw_enc_batch_device_tensor: the converted pictures of a batch, max_batch of them; allocated by the first tensor call */
 	int chroma_fork;  /* the chroma sequence on a stream of its own next to the luma tail (NHW_CHROMA_FORK=0 turns it off) */
 	int lists_fork;   /* the position lists (Y24/Y25) on a third stream (NHW_LISTS_FORK=0 turns it off: +0.75 ms per q20 batch) */
 	int front_fallback; /* debug: every row / segment of the pre-filter carry takes its exact fallback path (tests) */

@@ -115,6 +115,7 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	(void)hipDeviceSynchronize();
 	if (e->ws.base) (void)hipFree(e->ws.base);
 	dev_free(host_set(e, 0));
+	dev_free({ dev_buf(e->d_tensor_bytes, 0) });
 	dev_free(fit_set(e));
 	dev_free(fit_sse_set(e));
 	for (GrowBuf *g : { &e->pic_px, &e->pic_desc, &e->pfit_px, &e->pfit_aux }) nhw_grow_free(*g);

@@ -145,6 +145,51 @@ extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics,
 	return NHW_OK;
 }
 
+/* ------------------------------------------------------------------------------------------------ encode from tensors */
+static int tensor_in_args(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
+{
+	if (const int rc = nhw_tensor_format_check(fmt, a, nhw_enc_err)) return rc;
+	if (!d_in || ((uintptr_t)d_in & 15)) { nhw_enc_err = std::string(who) + ": d_in must be a 16-byte aligned device pointer"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+extern "C" int nhw_tensor_to_bytes_device(const void *d_in, int n, const nhw_tensor_format *fmt, void *d_bgr, void *stream)
+{
+	NhwTensorArgs a;
+	if (const int rc = tensor_in_args(d_in, fmt, &a, "nhw_tensor_to_bytes_device")) return rc;
+	if (!d_bgr || ((uintptr_t)d_bgr & 15)) { nhw_enc_err = "nhw_tensor_to_bytes_device: d_bgr must be a 16-byte aligned device pointer"; return NHW_E_ARG; }
+	if (n < 1 || n > (1 << 22)) { nhw_enc_err = "nhw_tensor_to_bytes_device: n outside 1 .. 2^22"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_tensor_to_bytes(d_in, n, fmt->dtype, fmt->layout, a, (uint8_t *)d_bgr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_enc_batch_device_tensor(nhw_enc *e, const void *d_in, int n, const nhw_tensor_format *fmt, int quality,
+                                           void *d_out, int32_t *d_sizes, int32_t *d_status, void *stream)
+{
+	if (!e || !d_out || !d_sizes || !d_status || n < 1 || n > e->max_batch) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	NhwTensorArgs a;
+	if (const int rc = tensor_in_args(d_in, fmt, &a, "nhw_enc_batch_device_tensor")) return rc;
+	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	if (nhw_tensor_format_is_bytes(fmt)) return nhw_enc_batch_device(e, d_in, n, quality, d_out, (uint32_t *)d_sizes, d_status, stream);
+	HIPCHK(hipSetDevice(e->device));
+	if (!e->d_tensor_bytes) {                                          /* the first tensor call on the handle */
+		const int rc = dev_alloc({ dev_buf(e->d_tensor_bytes, (size_t)e->max_batch * NHW_IMG_BYTES) }, "tensor encode scratch", e->max_batch, nhw_enc_err);
+		if (rc) return rc;
+	}
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;      /* as nhw_enc_batch_device reads it: the conversion goes in front of the encode */
+	HIPCHK(nhw_launch_tensor_to_bytes(d_in, n, fmt->dtype, fmt->layout, a, e->d_tensor_bytes, s));
+	return nhw_enc_batch_device(e, e->d_tensor_bytes, n, quality, d_out, (uint32_t *)d_sizes, d_status, s);
+}
+
+extern "C" int nhw_tile_tensors_device(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, const nhw_tensor_format *fmt, void *d_tiles, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_tile_tensors_device")) return rc;
+	NhwTensorArgs a;
+	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
+	HIPCHK(nhw_launch_tile_pad_tensor(d_pics, n_pics, tile0, m, fmt->dtype, fmt->layout, a, (uint8_t *)d_tiles, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 extern "C" int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, void *stream)
 {
 	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_sse_pictures_device")) return rc;

@@ -1,6 +1,7 @@
 /*
  * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 15): the padding kernel k_tile_pad, its inverse
- * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16), and the .nhwp container that
+ * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16), its mirrors k_tensor_to_bytes and k_tile_pad_tensor
+ * (section 17), and the .nhwp container that
  * holds a picture's width, height and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
@@ -42,8 +43,9 @@ __device__ __forceinline__ uint4 fetch(uintptr_t p, int j, int e)
 }
 
 /* the picture holding global tile t: the last descriptor with first_tile <= t.  A wave probes 64 evenly spaced entries at a time, so a
- * table of 65535 pictures takes three rounds of loads; the answer is the same in every lane. */
-__device__ __forceinline__ int find_picture(const nhw_picture *pics, int n, uint32_t t)
+ * table of 65535 pictures takes three rounds of loads; the answer is the same in every lane.  P: nhw_picture or nhw_tensor_picture */
+template <class P>
+__device__ __forceinline__ int find_picture(const P *pics, int n, uint32_t t)
 {
 	int lo = 0, hi = n;
 	const int lane = threadIdx.x & 63;
@@ -57,16 +59,17 @@ __device__ __forceinline__ int find_picture(const nhw_picture *pics, int n, uint
 	return __builtin_amdgcn_readfirstlane(lo);
 }
 
-struct TileRef {
-	nhw_picture p;
+template <class P> struct TileRefOf {
+	P p;
 	uint32_t ty, tx;
 	int k;                                  /* the picture's index in the table */
 };
+using TileRef = TileRefOf<nhw_picture>;
 
 /* the workgroup's tile (tile0 + blockIdx.x / bands of a tile) and its picture; false for a tile no picture of the table holds.  T: the tile's
  * side, 512 or, for the tiles of a scaled decode, 256 or 128 -- the table then holds the scaled pictures */
-template <int T = 512>
-__device__ __forceinline__ bool tile_of(const nhw_picture *pics, int n, int tile0, TileRef &r)
+template <int T = 512, class P>
+__device__ __forceinline__ bool tile_of(const P *pics, int n, int tile0, TileRefOf<P> &r)
 {
 	const uint32_t t = (uint32_t)tile0 + blockIdx.x / (T / TP_ROWS);
 	r.k = find_picture(pics, n, t);
@@ -373,7 +376,114 @@ __global__ __launch_bounds__(TP_THREADS) void k_bytes_to_tensor(const nhw_pictur
 	}
 }
 
+/* ------------------------------------------------------------------------------------------------ tensors to bytes */
+/* N = 4 pixels' elements by tensor channel from a run of a tensor row: CHW three runs of N elements, `plane` bytes apart, HWC one run of 3 N.
+ * ALIGN > 0: p is a multiple of it (the batch kernel); 0: looked at when running (the picture kernel's crop views) */
+template <int DT, int CHW, int ALIGN>
+__device__ __forceinline__ void load_quad(const uint8_t *p, uint64_t plane, uint32_t (*e)[4])
+{
+	constexpr int EB = NhwElem<DT>::bytes;
+	if (CHW) {
+#pragma unroll
+		for (int c = 0; c < 3; c++) {
+			uint32_t d[EB];                                                 /* 4 EB bytes */
+			if constexpr (ALIGN != 0) nhw_load_words<4 * EB, (ALIGN < 4 * EB ? ALIGN : 4 * EB)>(p + c * plane, d); else nhw_load_words_any<4 * EB, EB>(p + c * plane, d);
+#pragma unroll
+			for (int px = 0; px < 4; px++) e[c][px] = nhw_unpack_elem<DT>(d, px);
+		}
+	} else {
+		uint32_t d[3 * EB];                                                 /* 12 EB bytes */
+		if constexpr (ALIGN != 0) nhw_load_words<12 * EB, ALIGN>(p, d); else nhw_load_words_any<12 * EB, EB>(p, d);
+#pragma unroll
+		for (int px = 0; px < 4; px++)
+#pragma unroll
+			for (int c = 0; c < 3; c++) e[c][px] = nhw_unpack_elem<DT>(d, 3 * px + c);
+	}
+}
+
+/* n contiguous 512 x 512 tensors to the byte path's pictures.  A thread takes 4 pixels of a row -- columns 4 q .. 4 q + 3 of byte-path row r -- so a
+ * row is 128 threads and a workgroup two rows: CHW one load a plane of 16 (f32), 8 (f16, bf16) or 4 bytes (u8), HWC 48 (three 16-byte loads), 24
+ * (three 8-byte loads) or 12 contiguous bytes (one 12-byte load), then one 12-byte store.  Consecutive lanes are on consecutive pieces in every load
+ * and in the store; every address is a multiple of its access's size (12-byte ones: of 4) because both pointers are 16-byte aligned. */
+constexpr int TB_THREADS = 256, TB_QUADS = 512 * 512 / 4;                 /* threads a picture: 65536 */
+template <int DT, int CHW>
+__global__ __launch_bounds__(TB_THREADS) void k_tensor_to_bytes(const uint8_t *__restrict__ in, NhwTensorArgs a, uint8_t *__restrict__ bgr)
+{
+	constexpr int EB = NhwElem<DT>::bytes;
+	const size_t img = blockIdx.x / (TB_QUADS / TB_THREADS);
+	const int i = (blockIdx.x % (TB_QUADS / TB_THREADS)) * TB_THREADS + threadIdx.x, r = i >> 7, q = i & 127;
+	const int rr = a.flip ? 511 - r : r;
+	const uint8_t *base = in + img * (size_t)(3 * 512 * 512 * EB);
+	uint32_t e[3][4], w[3];
+	if (CHW) load_quad<DT, 1, 4 * EB>(base + ((size_t)rr * 512 + 4 * q) * EB, (uint64_t)(512 * 512 * EB), e);
+	else load_quad<DT, 0, (EB == 4 ? 16 : EB == 2 ? 8 : 4)>(base + ((size_t)rr * 512 + 4 * q) * (3 * EB), 0, e);
+	nhw_pixels_to_bytes<DT, 4>(e, a, w);
+	nhw_store_words<3, 3>(bgr + img * NHW_IMG_BYTES + ((size_t)r * 512 + 4 * q) * 3, w);
+}
+
+/* k_tile_pad for tensor pictures: the same grid (tiles x bands of TP_ROWS rows), a thread 4 pixels of a tile row at a time and one 12-byte store,
+ * contiguous across the wavefront.  Tile pixel (rr, cc) of tile (ty, tx) is byte-picture pixel (min(512 ty + rr, H - 1), min(512 tx + cc, W - 1));
+ * the row flip comes after the clamp of the row, so the replication acts in byte-picture coordinates.  EDGE false (an interior tile column: all
+ * 512 columns lie inside the picture): every quad is a run of the tensor row, load_quad with the address's alignment looked at when running (16, 8
+ * or 4 bytes wide; 2 or 1 where an f16 / u8 view starts there).  EDGE true: a quad that crosses or lies beyond column W loads its elements one at a
+ * time from the clamped columns.  No load touches anything but an element of the picture. */
+template <int DT, int CHW, bool EDGE>
+__device__ __forceinline__ void pad_band_tensor(const TileRefOf<nhw_tensor_picture> &r, const NhwTensorArgs &a, uint8_t *__restrict__ dst, int band)
+{
+	constexpr int EB = NhwElem<DT>::bytes, QUADS = TP_ROWS * 128;
+	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+	const uint32_t W = r.p.width, H = r.p.height;
+	const uint64_t px_step = CHW ? EB : 3 * EB, ch_step = CHW ? r.p.plane : EB;
+	for (int i = threadIdx.x; i < QUADS; i += TP_THREADS) {
+		const int rr = band * TP_ROWS + (i >> 7), q = i & 127;
+		const uint32_t R = 512 * r.ty + rr < H ? 512 * r.ty + rr : H - 1, row = a.flip ? H - 1 - R : R, c0 = 512 * r.tx + 4 * q;
+		const uint8_t *rowp = reinterpret_cast<const uint8_t *>(r.p.addr + (uint64_t)row * r.p.pitch);
+		uint32_t e[3][4], w[3];
+		if (!EDGE || c0 + 4 <= W) load_quad<DT, CHW, 0>(rowp + c0 * px_step, r.p.plane, e);
+		else {
+#pragma unroll
+			for (int px = 0; px < 4; px++) {
+				const uint32_t col = c0 + px < W ? c0 + px : W - 1;
+#pragma unroll
+				for (int c = 0; c < 3; c++) e[c][px] = *reinterpret_cast<const E *>(rowp + col * px_step + c * ch_step);
+			}
+		}
+		nhw_pixels_to_bytes<DT, 4>(e, a, w);
+		nhw_store_words<3, 3>(dst + ((size_t)rr * 512 + 4 * q) * 3, w);
+	}
+}
+
+template <int DT, int CHW>
+__global__ __launch_bounds__(TP_THREADS) void k_tile_pad_tensor(const nhw_tensor_picture *__restrict__ pics, int n_pics, int tile0, NhwTensorArgs a, uint8_t *__restrict__ tiles)
+{
+	constexpr uint64_t EB = NhwElem<DT>::bytes;
+	TileRefOf<nhw_tensor_picture> r;
+	if (!tile_of(pics, n_pics, tile0, r)) return;
+	if (r.p.width > 65535u || r.p.height > 65535u || !r.p.addr || ((r.p.addr | r.p.pitch | (CHW ? r.p.plane : 0)) & (EB - 1))) return;
+	uint8_t *dst = tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES;
+	if (512 * (r.tx + 1) <= r.p.width) pad_band_tensor<DT, CHW, false>(r, a, dst, blockIdx.x % TP_BANDS);
+	else pad_band_tensor<DT, CHW, true>(r, a, dst, blockIdx.x % TP_BANDS);
+}
+
 } /* namespace */
+
+hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s)
+{
+	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
+		k_tensor_to_bytes<DT, CHW><<<n * (TB_QUADS / TB_THREADS), TB_THREADS, 0, s>>>((const uint8_t *)d_in, a, d_bgr);
+	});
+	return hipGetLastError();
+}
+
+hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s)
+{
+	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
+		k_tile_pad_tensor<DT, CHW><<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_pics, n_pics, tile0, a, d_tiles);
+	});
+	return hipGetLastError();
+}
 
 hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s)
 {

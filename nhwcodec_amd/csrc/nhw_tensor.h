@@ -1,9 +1,12 @@
 /*
- * nhw_tensor.h -- the tensor formats of a decode (nhw_tensor_format in include/nhw_hip.h): the one value rule, the check
- * of a format, and the store shapes the decoder's last kernels (nhw_dec.hip) and the pointwise kernel (nhw_picture.hip) share.
+ * nhw_tensor.h -- the tensor formats of a decode and of an encode (section 17; nhw_tensor_format in include/nhw_hip.h):
+ * the value rule of each direction, the check of a format, the store shapes the decoder's last kernels (nhw_dec.hip) and the pointwise
+ * kernel (nhw_picture.hip) share, and the load shapes of the encoder's conversion kernels (nhw_picture.hip) that mirror them.
  *
- * Value rule: the element for byte b of output channel c is fmaf((float)b, scale[c], bias[c]) in single precision, rounded once, to nearest
- * even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).
+ * Value rule of a decode: the element for byte b of output channel c is fmaf((float)b, scale[c], bias[c]) in single precision, rounded once, to
+ * nearest even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).
+ * Value rule of an encode: element x of tensor channel c, widened exactly to float, gives y = fmaf(x, scale[c], bias[c]); the byte is 0 for a
+ * NaN, else rint(y), ties to even, clamped to 0 .. 255 (the clamp in float, before the conversion); NHW_T_U8 passes the byte on.
  */
 #ifndef NHW_TENSOR_H
 #define NHW_TENSOR_H
@@ -127,6 +130,79 @@ template <int DT, int CHW> struct NhwStoreTensor {
 	}
 };
 
+/* ------------------------------------------------------------------------------------------------ the other direction */
+/* the element whose bits are the low bits of e, widened exactly to float: IEEE half with its denormals (v_cvt_f32_f16), bfloat16 as bits << 16 */
+template <int DT> __device__ __forceinline__ float nhw_tensor_widen(uint32_t e)
+{
+	if (DT == NHW_T_F32) return __uint_as_float(e);
+	if (DT == NHW_T_F16) return (float)__builtin_bit_cast(_Float16, (uint16_t)e);
+	if (DT == NHW_T_BF16) return __uint_as_float(e << 16);
+	return (float)(e & 0xFFu);
+}
+/* the byte of element e: one fma, the clamp in float (a NaN fails the first comparison and gives 0), then the rounding to nearest even; what
+ * reaches rintf lies in [0, 255] */
+template <int DT> __device__ __forceinline__ uint32_t nhw_tensor_byte(uint32_t e, float scale, float bias)
+{
+	if (DT == NHW_T_U8) return e & 0xFFu;
+	const float y = __fmaf_rn(nhw_tensor_widen<DT>(e), scale, bias);
+	const float c = y > 0.0f ? (y < 255.0f ? y : 255.0f) : 0.0f;
+	return (uint32_t)rintf(c);
+}
+
+/* BYTES (a multiple of 4) from address p to d[], p a multiple of ALIGN (a power of two, 1 .. 16, known when compiling): the widest vector
+ * loads that BYTES and ALIGN both allow (12 bytes on a 4-byte alignment: one 12-byte load), as native vector types; below 4 bytes of alignment, shorts or bytes put together.  Reads [p, p + BYTES)
+ * and nothing else. */
+template <int BYTES, int ALIGN> __device__ __forceinline__ void nhw_load_words(const uint8_t *p, uint32_t *d)
+{
+	static_assert(BYTES % 4 == 0, "whole dwords");
+	constexpr int V = ALIGN >= 16 && BYTES % 16 == 0 ? 4 : ALIGN >= 8 && BYTES % 8 == 0 ? 2 : ALIGN >= 4 && BYTES == 12 ? 3 : 1;
+#pragma unroll
+	for (int k = 0; k < BYTES / 4; k += V) {
+		if (ALIGN >= 4) {
+			if (V == 3) { const uint3 v = *reinterpret_cast<const uint3 *>(p); d[0] = v.x; d[1] = v.y; d[2] = v.z; }
+			else if (V == 4) { const nhw_u32x4 v = *reinterpret_cast<const nhw_u32x4 *>(p + 4 * k); d[k] = v.x; d[k + 1] = v.y; d[k + 2] = v.z; d[k + 3] = v.w; }
+			else if (V == 2) { const nhw_u32x2 v = *reinterpret_cast<const nhw_u32x2 *>(p + 4 * k); d[k] = v.x; d[k + 1] = v.y; }
+			else d[k] = *reinterpret_cast<const uint32_t *>(p + 4 * k);
+		} else if (ALIGN == 2) {
+			const uint16_t *h = reinterpret_cast<const uint16_t *>(p + 4 * k);
+			d[k] = (uint32_t)h[0] | (uint32_t)h[1] << 16;
+		} else {
+			const uint8_t *b = reinterpret_cast<const uint8_t *>(p + 4 * k);
+			d[k] = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24;
+		}
+	}
+}
+/* the same with the alignment looked at when running (p a multiple of the element size EB at least): the crop views of the picture kernel */
+template <int BYTES, int EB> __device__ __forceinline__ void nhw_load_words_any(const uint8_t *q, uint32_t *d)
+{
+	const uintptr_t p = (uintptr_t)q;
+	if (BYTES % 16 == 0 && !(p & 15)) nhw_load_words<BYTES, 16>(q, d);
+	else if (BYTES % 8 == 0 && !(p & 7)) nhw_load_words<BYTES, 8>(q, d);
+	else if (EB == 4 || !(p & 3)) nhw_load_words<BYTES, 4>(q, d);
+	else if (EB == 2 || !(p & 1)) nhw_load_words<BYTES, 2>(q, d);
+	else nhw_load_words<BYTES, 1>(q, d);
+}
+/* element i of the elements packed in d[] */
+template <int DT> __device__ __forceinline__ uint32_t nhw_unpack_elem(const uint32_t *d, int i)
+{
+	constexpr int EB = NhwElem<DT>::bytes, PER = 4 / EB;
+	return EB == 4 ? d[i] : (d[i / PER] >> (8 * EB * (i % PER))) & (EB == 2 ? 0xFFFFu : 0xFFu);
+}
+/* e[c][px]: the elements of N pixels by TENSOR channel -> their 3 N bytes as the byte path holds them (B, G, R a pixel), 3 N / 4 dwords */
+template <int DT, int N> __device__ __forceinline__ void nhw_pixels_to_bytes(const uint32_t (*e)[N], const NhwTensorArgs &a, uint32_t *w)
+{
+	static_assert(N % 4 == 0, "whole dwords");
+	uint32_t b[3 * N];
+#pragma unroll
+	for (int px = 0; px < N; px++) {
+		const uint32_t t0 = nhw_tensor_byte<DT>(e[0][px], a.scale[0], a.bias[0]), t1 = nhw_tensor_byte<DT>(e[1][px], a.scale[1], a.bias[1]),
+		               t2 = nhw_tensor_byte<DT>(e[2][px], a.scale[2], a.bias[2]);
+		b[3 * px] = a.rgb ? t2 : t0; b[3 * px + 1] = t1; b[3 * px + 2] = a.rgb ? t0 : t2;
+	}
+#pragma unroll
+	for (int k = 0; k < 3 * N / 4; k++) w[k] = b[4 * k] | b[4 * k + 1] << 8 | b[4 * k + 2] << 16 | b[4 * k + 3] << 24;
+}
+
 /* f(NhwStoreTensor<dtype, layout>{ a }) for a checked format */
 template <class F> inline void nhw_with_tensor_store(int dtype, int layout, const NhwTensorArgs &a, F &&f)
 {
@@ -144,5 +220,8 @@ template <class F> inline void nhw_with_tensor_store(int dtype, int layout, cons
 
 /* nhw_picture.hip: every picture of the table to a tensor of its own size, one pass */
 hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s);
+/* ... and the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
+hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
+hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
 
 #endif
