@@ -401,6 +401,43 @@ int nhw_dec_batch_device_tensor(nhw_dec *d, const void *d_nhw, const uint64_t *d
  * side, a side above 65535 or a misaligned address is passed over: nothing is written for it.  No handle: the current device; stream NULL is
  * the null stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG for NULL pointers, n_pics outside 1 .. 2^24 and a refused format. */
 int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics, const nhw_tensor_format *fmt, const uint64_t *d_out_addr, void *stream);
+/* ---- crops resized into tensors of one size: crop, resize, flip ----
+ * A crop at scale s (1, 2 or 4) is a window of that scale (above) plus an output size out_width x out_height (1 .. 4096 each, one size for all
+ * crops of a call) and a flag byte whose bit 0 means "mirror left-right".  With P the window's bytes -- uint8 [h][w][3], B, G, R a pixel, rows
+ * in file order -- the result is defined from P alone, in integers:
+ *   position of output index o along an axis of source length n and output length m, in 64-bit integers:
+ *     t = max((2 o + 1) n - m, 0),  X = min(floor(128 t / m), 256 (n - 1)),  i0 = X >> 8,  f = X & 255,  i1 = min(i0 + 1, n - 1)
+ *     (the centre-aligned (o + 1/2) n / m - 1/2, clamped to the axis, in 1/256 pixel);
+ *   byte of output pixel (oy, ox), channel c, with (y0, y1, fy) from (oy, h, out_height) and (x0, x1, fx) from (ox, w, out_width):
+ *     ((256 - fx)(256 - fy) P[y0][x0][c] + fx (256 - fy) P[y0][x1][c] + (256 - fx) fy P[y1][x0][c] + fx fy P[y1][x1][c] + 32768) >> 16;
+ *   the picture R of these bytes, uint8 [out_height][out_width][3], is mirrored left-right (R[oy][out_width - 1 - ox]) when the flag is set;
+ *   the tensor is what nhw_bytes_to_tensor_device makes of R under the format: its value rule, channel order, row direction and layout.
+ * The filter has two taps a direction: it is meant for reductions below 2, which nhw_crop_scale arranges whenever the crop is at least as
+ * large as the output; larger reductions alias as bilinear interpolation does.
+ * nhw_crop_scale: the scale to decode a width x height crop at -- the largest s of 4, 2, 1 with s out_width <= width and s out_height <=
+ * height, 1 if there is none; NHW_E_ARG for a zero side or an output side above 4096.  A crop x, y, w, h in FULL-resolution coordinates,
+ * inside a W x H picture, becomes the window at scale s
+ *     x' = floor(x / s),  y' = floor(y / s),  w' = ceil((x + w) / s) - x',  h' = ceil((y + h) / s) - y',
+ * the smallest scaled window that covers it; it lies inside ceil(W / s) x ceil(H / s). */
+int nhw_crop_scale(uint32_t width, uint32_t height, uint32_t out_width, uint32_t out_height);   /* 1, 2 or 4; NHW_E_ARG on a zero or an output side above 4096 */
+/* The resize alone, the counterpart of nhw_bytes_to_tensor_device: picture k of the table d_pics[0 .. n) (addr, pitch, width and height are
+ * read; any alignment and pitch; bytes outside a row's 3 width are never read) goes, under the rule above with P the picture, to the
+ * [out_height][out_width][3] or [3][out_height][out_width] elements at d_out_addr[k]; d_flags: n flag bytes in device memory, or NULL for
+ * none.  Writes exactly those 3 out_width out_height elements, element by element.  An entry with a zero side, a side above 65535, a zero
+ * address or an address that is no multiple of the element size is passed over: nothing is written for it.  No handle: the current device;
+ * stream NULL is the null stream.  Asynchronous, and may be captured in a graph.  NHW_E_ARG, before anything is launched, for NULL d_pics or
+ * d_out_addr, n outside 1 .. 2^24, an output side outside 1 .. 4096 and a refused format. */
+int nhw_resize_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream);
+/* nhw_dec_windows_to_device with the resize behind it, synchronous: rects are windows at `scale`, flags (host memory, n_rects bytes, or NULL)
+ * their flag bytes, dst_addr[i] the device address of crop i's tensor (e.g. slot i of an [n][3][out_height][out_width] batch).  Everything
+ * nhw_dec_windows_to_device says holds: the union of tiles, each uploaded and decoded once; the per-rect statuses; nhw_dec_last_region_stats;
+ * the call-level NHW_E_ARG cases, among them scale 2 or 4 on a handle with a debug stop -- with, in place of the pitch's, a dst_addr that is 0
+ * or no multiple of the element size, an output side outside 1 .. 4096, a refused format and n_rects above 2^24.  The windows are cropped into
+ * a staging buffer of the handle and resized from there by one launch behind the last chunk of tiles; nothing is downloaded.  A crop whose
+ * status is not NHW_OK leaves its destination untouched. */
+int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status);
 
 /* ---- encode straight from training tensors ----
  * The mirror of the section above: the encoder reads its pictures under an nhw_tensor_format -- the same struct, the same enums.  For this

@@ -107,6 +107,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_dec_batch_device_tensor.argtypes = [P, P, P, P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P, P, P]
     L.nhw_bytes_to_tensor_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
     L.nhw_tensor_to_bytes_device.argtypes = [P, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
+    L.nhw_crop_scale.argtypes = [ctypes.c_uint32] * 4
+    L.nhw_resize_to_tensor_device.argtypes = [P, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CTensorFormat), P, P, P]
+    L.nhw_dec_crops_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CTensorFormat), P, P, P]
     L.nhw_enc_batch_device_tensor.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(CTensorFormat), ctypes.c_int, P, P, P, P]
     L.nhw_tile_tensors_device.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
     return L
@@ -416,6 +419,82 @@ def pictures_to_tensor_device(pictures, fmt):
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return outs
+
+
+# ---------------------------------------------------------------- crops resized into tensors of one size
+CROP_SIDE_MAX = 4096
+
+
+def _crop_size(size, what):
+    """the checked (out_h, out_w) of a crop call"""
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in size)
+            and all(1 <= v <= CROP_SIDE_MAX for v in size)):
+        raise NhwError(f"{what}: `size` must be (out_h, out_w), integers of 1 .. {CROP_SIDE_MAX}, got {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def _crop_flips(flips, n, what):
+    """the flag bytes of n crops (bit 0: mirror left-right) as a numpy uint8 array, or None"""
+    import numpy as np
+    if flips is None:
+        return None
+    try:
+        f = np.asarray(flips)
+    except Exception:
+        f = None
+    if f is None or f.shape != (n,) or f.dtype.kind not in "biu":
+        raise NhwError(f"{what}: `flips` must be {n} booleans or flag bytes, one a crop, got {flips!r}")
+    return np.ascontiguousarray(f.astype(bool).astype(np.uint8) if f.dtype.kind == "b" else (f & 1).astype(np.uint8))
+
+
+def crop_scale(w: int, h: int, out_w: int, out_h: int) -> int:
+    """the scale to decode a w x h crop at that goes to out_w x out_h (nhw_crop_scale): the largest s of 4, 2, 1 with s * out_w <= w and
+    s * out_h <= h, which leaves the two-tap resize a reduction below 2; 1 if there is none (the crop is enlarged)"""
+    if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (w, h, out_w, out_h)):
+        raise NhwError(f"crop_scale wants integers, got {(w, h, out_w, out_h)!r}")
+    if not (1 <= w <= 0xFFFFFFFF and 1 <= h <= 0xFFFFFFFF and 1 <= out_w <= CROP_SIDE_MAX and 1 <= out_h <= CROP_SIDE_MAX):
+        raise NhwError(f"crop_scale: a {w} x {h} crop to {out_w} x {out_h}: the sides must be at least 1, the output's {CROP_SIDE_MAX} at the most")
+    for s in (4, 2):
+        if s * out_w <= w and s * out_h <= h:
+            return s
+    return 1
+
+
+def crop_window(x: int, y: int, w: int, h: int, scale: int) -> tuple:
+    """the smallest window at `scale` that covers the full-resolution crop x, y, w, h -> (x', y', w', h') with x' = x // s, y' = y // s,
+    w' = ceil((x + w) / s) - x', h' = ceil((y + h) / s) - y'.  A crop inside a W x H picture gives a window inside scaled_size(W, H, scale)."""
+    scale = _scale(scale, "crop_window")
+    if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (x, y, w, h)) or x < 0 or y < 0 or w < 1 or h < 1:
+        raise NhwError(f"crop_window: the crop {x!r}, {y!r}, {w!r} x {h!r} is empty or no rectangle of integers")
+    x, y, w, h = int(x), int(y), int(w), int(h)
+    return x // scale, y // scale, -(-(x + w) // scale) - x // scale, -(-(y + h) // scale) - y // scale
+
+
+def resize_to_tensor_device(pictures, size, fmt, flips=None):
+    """Pictures of any sizes to one batch tensor of one size (k_resize_to_tensor, nhw_resize_to_tensor_device): a list of uint8 CUDA tensors
+    [H, W, 3] as for pictures_to_tensor_device, size = (out_h, out_w) of 1 .. 4096 each, flips: None or one boolean a picture ("mirror
+    left-right") -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Picture k is resampled under the integer rule
+    of DESIGN.md section 18 (centre-aligned, two taps a direction, weights in 1/256), mirrored, and converted under TensorFormat's value
+    rule.  Reads only the pictures' own bytes.  Ordered on torch's current stream."""
+    import torch
+    what = "resize_to_tensor_device"
+    fmt = _tensor_format(fmt, what)
+    out_h, out_w = _crop_size(size, what)
+    table, _, dev = _picture_table(pictures, what)
+    n = len(pictures)
+    flags = _crop_flips(flips, n, what)
+    out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
+    addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (3 * out_h * out_w * out.element_size())
+    addr = addr.to(dev)
+    d_flags = torch.from_numpy(flags).to(dev) if flags is not None else None
+    L = _library()
+    c = fmt.c_struct()
+    with torch.cuda.device(dev):
+        rc = L.nhw_resize_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                                           addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
 
 
 TENSOR_PICTURE_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("plane", "<u8"), ("width", "<u4"), ("height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_tensor_picture
@@ -1270,6 +1349,56 @@ class Decoder:
         scale = _scale(scale, "decode_windows_device")
         return self._regions_device(containers, rects, out, "decode_windows_device",
                                     lambda *a: self.lib.nhw_dec_windows_to_device(self.h, *a[:5], scale, *a[5:]))
+
+    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None):
+        """RandomResizedCrop's decode (nhw_dec_crops_to_device): crops, a sequence of (container index, x, y, w, h), each
+        resampled to size = (out_h, out_w), mirrored left-right where flips[i] is true, and stored under fmt -> (tensor [n, 3, out_h, out_w]
+        or [n, out_h, out_w, 3] of fmt.dtype on this decoder's device, the list of the scales used).  With a scale (1, 2 or 4) the crops
+        are windows at that scale, as for decode_windows, and go down in one call.  With scale=None they are rectangles of the full-resolution
+        pictures: crop i is decoded at crop_scale(w, h, out_w, out_h), as the window crop_window(x, y, w, h, that scale), and the crops of
+        one scale go down together -- three calls at the most, each decoding the union of its windows' tiles once.  out: a contiguous tensor of
+        fmt.dtype with at least n * 3 * out_h * out_w elements on this device, which is filled.  Raises on any status that is not NHW_OK.  The
+        work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls."""
+        import numpy as np
+        t = self.torch
+        what = "decode_crops_device"
+        fmt = _tensor_format(fmt, what)
+        out_h, out_w = _crop_size(size, what)
+        if scale is not None:
+            scale = _scale(scale, what)
+        blob, offs, table = self._region_args(containers, crops, what)
+        n = len(table)
+        flags = _crop_flips(flips, n, what)
+        if scale is None:
+            x, y, w, h = (table[k].astype(np.int64) for k in ("x", "y", "width", "height"))
+            if not (w.all() and h.all()):
+                raise NhwError(f"{what}: crop {int(np.flatnonzero((w == 0) | (h == 0))[0])} is empty")
+            sc = np.where((4 * out_w <= w) & (4 * out_h <= h), 4, np.where((2 * out_w <= w) & (2 * out_h <= h), 2, 1))   # crop_scale and crop_window, on arrays
+            table["x"], table["y"] = x // sc, y // sc
+            table["width"], table["height"] = -(-(x + w) // sc) - x // sc, -(-(y + h) // sc) - y // sc
+            scales = sc.tolist()
+        else:
+            scales = [scale] * n
+        dev = t.device("cuda", self.device)
+        shape = (n,) + fmt.shape(out_h, out_w)
+        per = 3 * out_h * out_w
+        if out is None:
+            out = t.empty(shape, dtype=fmt.dtype, device=dev)
+        elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device == dev and out.dtype == fmt.dtype and out.is_contiguous() and out.numel() >= n * per):
+            raise NhwError(f"{what}: `out` must be a contiguous {fmt.dtype} tensor of at least {n}*{per} elements on {dev}")
+        addr = np.uint64(out.data_ptr()) + np.arange(n, dtype=np.uint64) * np.uint64(per * out.element_size())
+        status = np.zeros(n, np.int32)
+        c = fmt.c_struct()
+        t.cuda.current_stream(dev).synchronize()                     # the calls run on the handle's own stream and wait for it
+        for s in sorted(set(scales)):
+            idx = np.flatnonzero(np.array(scales) == s)
+            sub, a, st = np.ascontiguousarray(table[idx]), np.ascontiguousarray(addr[idx]), np.empty(len(idx), np.int32)
+            f = np.ascontiguousarray(flags[idx]) if flags is not None else None
+            self._chk(self.lib.nhw_dec_crops_to_device(self.h, blob.ctypes.data, offs.ctypes.data, len(containers), sub.ctypes.data, len(idx), s, out_w, out_h,
+                                                       ctypes.byref(c), f.ctypes.data if f is not None else None, a.ctypes.data, st.ctypes.data))
+            status[idx] = st
+        self._region_raise(status)
+        return (out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)), scales
 
     def region_stats(self):
         """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region or window call (nhw_dec_last_region_stats);

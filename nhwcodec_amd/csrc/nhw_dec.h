@@ -31,6 +31,7 @@ struct nhw_dec {
 	uint64_t *d_off; uint32_t *d_len; uint8_t *d_out; int32_t *d_status; int32_t *d_quality;
 	/* nhw_dec_pictures, nhw_dec_regions*: the cropped pictures or regions, their descriptor table and the per-tile offsets, lengths and status, grow-only */
 	GrowBuf pic_px, pic_desc, pic_tiles;
+	GrowBuf crop_tab;            /* nhw_dec_crops_to_device: the staged windows as pictures, the tensors' addresses and the flags, grow-only */
 	uint64_t reg_tiles, reg_bytes;   /* the last region call: tiles handed to the decoder, tile-file bytes uploaded (nhw_dec_last_region_stats) */
 };
 

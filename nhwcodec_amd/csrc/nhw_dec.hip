@@ -2408,7 +2408,7 @@ extern "C" void nhw_dec_destroy(nhw_dec *d)
 	(void)hipSetDevice(d->device);
 	if (d->ws_base) (void)hipFree(d->ws_base);
 	dev_free(host_set(d));
-	for (GrowBuf *g : { &d->blob, &d->pic_px, &d->pic_desc, &d->pic_tiles }) nhw_grow_free(*g);
+	for (GrowBuf *g : { &d->blob, &d->pic_px, &d->pic_desc, &d->pic_tiles, &d->crop_tab }) nhw_grow_free(*g);
 	if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
 	if (d->chroma_stream) (void)hipStreamDestroy(d->chroma_stream);
 	if (d->vlc_table) (void)hipFree(d->vlc_table);

@@ -1,6 +1,7 @@
 /* nhw_dec_hostpath.hip -- the decoder's host conveniences: files in host memory in, pictures out (nhw_dec_batch), pictures of any size and regions of them out of
- * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
+ * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
 #include "nhw_dec.h"
+#include "nhw_tensor.h"
 
 /* the host paths' buffers: the blob (grow-only, room for `total` bytes of files) and, on the first call, the per-file arrays and the
  * decoded pictures of max_batch files */
@@ -294,16 +295,22 @@ extern "C" int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const 
  * tiles of the call are the union of the windows' selections.  A tile gets a slot when the first window selects it (slot_of, per
  * container); only the files of those tiles are gathered, slot after slot, and decoded; every (window, tile) pair is a use, and the uses
  * sorted by slot make the chunk [t0, t0 + m) of decoded tiles the owner of the contiguous range [first_use[t0], first_use[t0 + m)), which
- * k_untile_window crops behind the chunk.  A window's status is the worst of its own tiles'. */
+ * k_untile_window crops behind the chunk.  A window's status is the worst of its own tiles'.
+ * The crop call is the third form: `crop` set, dst_addr the tensors' addresses.  The windows are cropped into the handle's
+ * staging as for the host form and stay there; behind the last chunk one k_resize_to_tensor takes every window whose tiles all decoded to its
+ * tensor -- the others get the address 0, which the kernel passes over. */
+struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; };
+
 static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
-                       const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who)
+                       const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, const CropSpec *crop = nullptr)
 {
-	const bool to_device = dst_addr != nullptr;
-	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (to_device ? !dst_pitch : (!bgr || !out_off))) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const bool to_device = dst_addr != nullptr && !crop;
+	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (crop ? !dst_addr : to_device ? !dst_pitch : (!bgr || !out_off))) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
 	if (scale != 1 && d->stop_after) { nhw_dec_err = "a scaled decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
 	for (int i = 0; i < nc; i++) if (off[i + 1] < off[i]) { nhw_dec_err = std::string(who) + ": off[] must not decrease"; return NHW_E_ARG; }
 	if (to_device) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_pitch[i] < 3ull * rects[i].width) { nhw_dec_err = std::string(who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
+	if (crop) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_addr[i] % (crop->dtype == NHW_T_U8 ? 1u : crop->dtype == NHW_T_F32 ? 4u : 2u)) { nhw_dec_err = std::string(who) + ": a destination needs an address that is a multiple of the element size"; return NHW_E_ARG; }
 	d->reg_tiles = d->reg_bytes = 0;
 	const uint32_t T = 512u / (uint32_t)scale;
 	std::vector<RegionSource> src((size_t)nc);
@@ -378,6 +385,24 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		return nhw_launch_untile_window(d->d_out, d_desc, ng, d_uses + first_use[t0], first_use[t0 + m] - first_use[t0], t0, m, scale, s); }); if (rc) return rc; }
 	for (const nhw_window_use &u : uses)
 		if (tiles_status(tst, (int)u.slot, (int)u.slot + 1) != NHW_OK) status[which[u.region]] = NHW_E_FORMAT;
+	if (crop) {                                                   /* one table entry a rect: a rect that has no window keeps a zero picture and a zero address */
+		std::vector<nhw_picture> pics((size_t)nr, nhw_picture{ 0, 0, 0, 0, 0, 0 });
+		std::vector<uint64_t> oaddr((size_t)nr, 0);
+		for (int k = 0; k < ng; k++) {
+			pics[(size_t)which[k]] = { desc[k].addr, desc[k].pitch, desc[k].width, desc[k].height, 0, 0 };
+			if (status[which[k]] == NHW_OK) oaddr[(size_t)which[k]] = dst_addr[which[k]];
+		}
+		const size_t pics_bytes = (size_t)nr * sizeof(nhw_picture), addr_bytes = (size_t)nr * 8;
+		HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + (size_t)nr));
+		uint8_t *tab = d->crop_tab.as<uint8_t>();
+		HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
+		if (crop->flags) HIPCHK(hipMemcpyAsync(tab + pics_bytes + addr_bytes, crop->flags, (size_t)nr, hipMemcpyHostToDevice, s));
+		HIPCHK(nhw_launch_resize_to_tensor((const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
+		                                   crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
+		HIPCHK(hipStreamSynchronize(s));
+		return NHW_OK;
+	}
 	std::vector<Span> sp;
 	if (!to_device) for (int k = 0; k < ng; k++)
 		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
@@ -395,6 +420,19 @@ extern "C" int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const 
 {
 	if (!dst_addr) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_windows_to_device");
+}
+
+/* nhw_dec_windows_to_device with a resize behind it: window i, resampled to out_width x out_height and mirrored where bit 0 of
+ * flags[i] is set, to the tensor at dst_addr[i] */
+extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status)
+{
+	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_crops_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	CropSpec c = { out_width, out_height, 0, 0, {}, flags };
+	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
+	c.dtype = fmt->dtype; c.layout = fmt->layout;
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", &c);
 }
 
 extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)

@@ -145,6 +145,18 @@ extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics,
 	return NHW_OK;
 }
 
+/* ... and resampled to one size on the way: the pictures of a table to out_width x out_height tensors, one pass */
+extern "C" int nhw_resize_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                           const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = "nhw_resize_to_tensor_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	NhwTensorArgs a;
+	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
+	HIPCHK(nhw_launch_resize_to_tensor(d_pics, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_flags, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
 static int tensor_in_args(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
 {

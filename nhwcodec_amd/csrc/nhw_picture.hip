@@ -1,6 +1,6 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 15): the padding kernel k_tile_pad, its inverse
- * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16), its mirrors k_tensor_to_bytes and k_tile_pad_tensor
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 18): the padding kernel k_tile_pad, its inverse
+ * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16) and its resampling form k_resize_to_tensor (section 18), its mirrors k_tensor_to_bytes and k_tile_pad_tensor
  * (section 17), and the .nhwp container that
  * holds a picture's width, height and tile files.
  *
@@ -376,6 +376,68 @@ __global__ __launch_bounds__(TP_THREADS) void k_bytes_to_tensor(const nhw_pictur
 	}
 }
 
+/* ---- crops resized into tensors of one size ----
+ * The position of output index o along an axis of source length n (1 .. 65535) and output length m (1 .. 4096): X = min(floor(128 t / m),
+ * 256 (n - 1)) with t = max((2 o + 1) n - m, 0), the centre-aligned (o + 1/2) n / m - 1/2 clamped to the axis, in 1/256 pixel.  t is below
+ * 2^30, so with t = q m + r the quotient is 128 q + floor(128 r / m) in 32-bit arithmetic (128 r < 2^19).  Packed as X (i0 = X >> 8 in bits
+ * 8 .. 23, f = X & 255) with i1 - i0 (0 or 1) in bit 24. */
+__device__ __forceinline__ uint32_t resize_pos(uint32_t o, uint32_t n, uint32_t m)
+{
+	const uint32_t s = (2 * o + 1) * n, t = s > m ? s - m : 0, q = t / m, r = t - q * m;
+	uint32_t X = 128 * q + 128 * r / m;
+	if (X > 256 * (n - 1)) X = 256 * (n - 1);
+	return X | ((X >> 8) + 1 < n ? 1u << 24 : 0u);
+}
+
+/* Picture k of the table, resampled to out_w x out_h under the rule of section 18 (two taps a direction, weights in 1/256, one rounding), mirrored
+ * left-right where bit 0 of flags[k] says so, to [out_h][out_w][3] or [3][out_h][out_w] elements at out_addr[k] under the value rule of
+ * nhw_tensor.h.  The host knows no picture's size, so the grid is crops x bands of `rows` output rows.  A workgroup puts the positions of all
+ * out_w columns and of its band's rows into LDS -- the only divisions of the kernel --, and after the one barrier walks the band 256 >> lg
+ * rows at a time, 1 << lg lanes a row (the power of two that holds out_w, 256 at the most: wider rows in steps).  A thread takes one output pixel
+ * at a time: twelve byte loads (any alignment and pitch; consecutive lanes on neighbouring source pixels; never a byte outside a row's 3 W),
+ * the blend, and three element stores as in k_bytes_to_tensor.  An entry with a zero or oversize side, a zero address or one that is no
+ * multiple of the element size stores nothing. */
+constexpr int RS_MAX = 4096, RS_ROWS = 64;      /* the largest output side; the most rows a band has */
+template <int DT, int CHW>
+__global__ __launch_bounds__(TP_THREADS) void k_resize_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
+                                                                  NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
+{
+	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+	__shared__ uint32_t col_pos[RS_MAX], row_pos[RS_ROWS];
+	const int k = blockIdx.x / bands;
+	const uint32_t r0 = (uint32_t)(blockIdx.x % bands) * (uint32_t)rows;     /* the band: output rows [r0, r0 + nr) */
+	const nhw_picture p = pics[k];
+	const uint64_t oa = out_addr[k];
+	if (!p.width || !p.height || p.width > 65535u || p.height > 65535u || !oa || (oa & (sizeof(E) - 1))) return;
+	if (out_w > (uint32_t)RS_MAX || rows > RS_ROWS || r0 >= out_h) return;     /* (the launcher sends neither) */
+	const uint32_t nr = out_h - r0 < (uint32_t)rows ? out_h - r0 : (uint32_t)rows;
+	const bool mirror = flags && (flags[k] & 1);
+	for (uint32_t o = threadIdx.x; o < out_w; o += TP_THREADS) col_pos[o] = resize_pos(o, p.width, out_w);
+	if (threadIdx.x < nr) row_pos[threadIdx.x] = resize_pos(r0 + threadIdx.x, p.height, out_h);
+	__syncthreads();
+	E *out = reinterpret_cast<E *>(oa);
+	const size_t W = out_w, H = out_h;
+	for (uint32_t r = threadIdx.x >> lg; r < nr; r += TP_THREADS >> lg) {
+		const uint32_t py = row_pos[r], fy = py & 255u;
+		const uint8_t *s0 = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)((py >> 8) & 0xFFFFu) * p.pitch);
+		const uint8_t *s1 = s0 + (uint64_t)(py >> 24) * p.pitch;
+		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
+		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
+			const uint32_t px = col_pos[mirror ? out_w - 1 - c : c], fx = px & 255u, x0 = 3 * ((px >> 8) & 0xFFFFu), x1 = x0 + 3 * (px >> 24);
+			const uint32_t w00 = (256 - fx) * (256 - fy), w01 = fx * (256 - fy), w10 = (256 - fx) * fy, w11 = fx * fy;
+			uint32_t b[3];
+#pragma unroll
+			for (int ch = 0; ch < 3; ch++)
+				b[ch] = (w00 * s0[x0 + ch] + w01 * s0[x1 + ch] + w10 * s1[x0 + ch] + w11 * s1[x1 + ch] + 32768u) >> 16;
+			const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
+			const E e1 = (E)nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
+			const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
+			if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
+			else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
+		}
+	}
+}
+
 /* ------------------------------------------------------------------------------------------------ tensors to bytes */
 /* N = 4 pixels' elements by tensor channel from a run of a tensor row: CHW three runs of N elements, `plane` bytes apart, HWC one run of 3 N.
  * ALIGN > 0: p is a multiple of it (the batch kernel); 0: looked at when running (the picture kernel's crop views) */
@@ -495,6 +557,26 @@ hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int
 	return hipGetLastError();
 }
 
+/* Bands: some 8192 workgroups in all where the crops are few, one band a crop where they are many; a band has at most RS_ROWS rows and, where
+ * the output is narrow, at least the rows of one pass (256 >> lg), so that a pass has work for every lane. */
+hipError_t nhw_launch_resize_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                       const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return hipErrorInvalidValue;
+	int lg = 0;
+	while (lg < 8 && (1u << lg) < out_w) lg++;
+	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
+	uint32_t rows = (out_h + want - 1) / want;
+	if (rows < (uint32_t)(TP_THREADS >> lg)) rows = TP_THREADS >> lg;
+	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
+	const int bands = (int)((out_h + rows - 1) / rows);                 /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
+	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
+		k_resize_to_tensor<DT, CHW><<<n * bands, TP_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+	});
+	return hipGetLastError();
+}
+
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
 {
 	k_tile_pad<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_pics, n_pics, tile0, d_tiles);
@@ -567,6 +649,16 @@ extern "C" int nhw_window_tiles(uint32_t pic_width, uint32_t pic_height, int sca
 	if ((uint64_t)x + width > sw || (uint64_t)y + height > sh) return NHW_E_ARG;
 	const uint32_t T = 512u / (uint32_t)scale;
 	return (int)(((x + width - 1) / T - x / T + 1) * ((y + height - 1) / T - y / T + 1));
+}
+
+/* the scale to decode a width x height crop at that goes to out_width x out_height: the largest s of 4, 2, 1 with
+ * s out_width <= width and s out_height <= height, so that what is left to the two-tap resize is a reduction below 2; 1 if there is none */
+extern "C" int nhw_crop_scale(uint32_t width, uint32_t height, uint32_t out_width, uint32_t out_height)
+{
+	if (!width || !height || !out_width || !out_height || out_width > 4096u || out_height > 4096u) return NHW_E_ARG;
+	for (uint32_t s = 4; s > 1; s >>= 1)
+		if (s * out_width <= width && s * out_height <= height) return (int)s;
+	return 1;
 }
 
 /* A well-formed container: magic, version 1, zero reserved bytes, W and H in 1..65535, T = nhw_picture_tiles(W, H) lengths of 1 ..

@@ -1,7 +1,7 @@
 /*
  * nhw_tensor.h -- the tensor formats of a decode and of an encode (section 17; nhw_tensor_format in include/nhw_hip.h):
  * the value rule of each direction, the check of a format, the store shapes the decoder's last kernels (nhw_dec.hip) and the pointwise
- * kernel (nhw_picture.hip) share, and the load shapes of the encoder's conversion kernels (nhw_picture.hip) that mirror them.
+ * kernels (nhw_picture.hip; the resampling one of section 18 among them) share, and the load shapes of the encoder's conversion kernels (nhw_picture.hip) that mirror them.
  *
  * Value rule of a decode: the element for byte b of output channel c is fmaf((float)b, scale[c], bias[c]) in single precision, rounded once, to
  * nearest even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).
@@ -220,6 +220,9 @@ template <class F> inline void nhw_with_tensor_store(int dtype, int layout, cons
 
 /* nhw_picture.hip: every picture of the table to a tensor of its own size, one pass */
 hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s);
+/* ... and every picture resampled to out_w x out_h (1 .. 4096 each), mirrored where bit 0 of d_flags[k] is set (d_flags may be null) */
+hipError_t nhw_launch_resize_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                       const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
 /* ... and the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
