@@ -277,7 +277,7 @@ void nhw_dec_destroy(nhw_dec *d);
 const char *nhw_dec_last_error(void);
 int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, void *d_bgr, int32_t *d_status,
                          int32_t *d_quality, void *stream);
-/* host convenience: H2D of the files (nhw[off[i]..off[i+1])), decode, D2H.  Synchronous. */
+/* host convenience: H2D of the files (nhw[off[i]..off[i+1])), decode, D2H.  Synchronous.  NHW_E_ARG for n > max_batch and for an off[] that decreases. */
 int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality);
 void nhw_dec_bmp_header(uint8_t h[54]);
 /* host convenience for .nhwp containers, synchronous: container i is blob[off[i] .. off[i + 1]) (off: n + 1 entries); its tiles are

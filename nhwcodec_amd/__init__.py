@@ -1115,24 +1115,43 @@ class Decoder:
         self._chk(self.lib.nhw_dec_last_timing(self.h, ctypes.byref(t)))
         return t
 
+    def _device_files(self, arena, offsets, lengths, what, limit=True):
+        """the checked files of a decode_*_device call: arena uint8, offsets int64 [n], lengths int32 [n], contiguous, on this decoder's device
+        -> n (limit: at most max_batch)"""
+        t = self.torch
+        for name, x, dt in (("arena", arena, t.uint8), ("offsets", offsets, t.int64), ("lengths", lengths, t.int32)):
+            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous()):
+                raise NhwError(f"{what}: `{name}` must be a contiguous {dt} tensor on cuda:{self.device}")
+        n = offsets.numel()
+        if lengths.numel() != n or n < 1:
+            raise NhwError(f"{what}: offsets and lengths must have one entry per file")
+        if limit and n > self.max_batch:
+            raise NhwError(f"{what}: {n} files for a decoder of max_batch {self.max_batch}")
+        return n
+
+    def _device_out(self, out, what, dtype, shape, align, wants):
+        """the checked `out` of a decode_*_device call (None: a new tensor of `shape`): contiguous, of dtype, on this decoder's device, at least
+        prod(shape) elements at an address that is a multiple of align; wants: the error's words for that -> (out, its first prod(shape)
+        elements as `shape`, new status [n] and quality [n])"""
+        t = self.torch
+        dev = f"cuda:{self.device}"
+        count = 1
+        for v in shape:
+            count *= v
+        if out is None:
+            out = t.empty(shape, dtype=dtype, device=dev)
+        elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == dtype and out.is_contiguous()
+                  and out.numel() >= count and out.data_ptr() % align == 0):
+            raise NhwError(f"{what}: `out` must be a {wants} on this decoder's device")
+        px = out if tuple(out.shape) == tuple(shape) else out.reshape(-1)[:count].view(shape)
+        return out, px, t.empty(shape[0], dtype=t.int32, device=dev), t.empty(shape[0], dtype=t.int32, device=dev)
+
     def decode_device(self, arena, offsets, lengths, out=None):
         """arena: uint8 CUDA tensor holding the files; offsets: int64 CUDA tensor [n]; lengths: int32 CUDA tensor [n]
         (the encoder's output arena with offsets i*OUT_STRIDE and its sizes tensor fits as is).
         Returns (pixels[n,512,512,3], status[n], quality[n]) on the device."""
-        t = self.torch
-        n = offsets.numel()
-        dev = f"cuda:{self.device}"
-        for name, x, dt in (("arena", arena, t.uint8), ("offsets", offsets, t.int64), ("lengths", lengths, t.int32)):
-            if not (x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous()):
-                raise NhwError(f"decode_device: `{name}` must be a contiguous {dt} tensor on cuda:{self.device}")
-        if lengths.numel() != n or n < 1:
-            raise NhwError("decode_device: offsets and lengths must have one entry per file")
-        if out is None:
-            out = t.empty((n, 512, 512, 3), dtype=t.uint8, device=dev)
-        elif not (out.is_cuda and out.device.index == self.device and out.dtype == t.uint8 and out.is_contiguous() and out.numel() >= n * IMG_BYTES):
-            raise NhwError("decode_device: `out` must be a contiguous uint8 tensor of n*786432 bytes on this decoder's device")
-        status = t.empty(n, dtype=t.int32, device=dev)
-        quality = t.empty(n, dtype=t.int32, device=dev)
+        n = self._device_files(arena, offsets, lengths, "decode_device", limit=False)
+        out, _, status, quality = self._device_out(out, "decode_device", self.torch.uint8, (n, 512, 512, 3), 1, "contiguous uint8 tensor of n*786432 bytes")
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_dec_batch_device(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, out.data_ptr(), status.data_ptr(),
                                                     quality.data_ptr(), st))
@@ -1143,29 +1162,15 @@ class Decoder:
         quarter-scale (128 x 128) picture every file holds, without the level-1 synthesis.  Arguments as for decode_device; out: a contiguous
         uint8 tensor of at least n * 3 * S * S bytes, S = 512 // scale.  Returns (pixels[n, S, S, 3], status[n], quality[n]) on the device;
         status and quality are those of the full decode.  Scale 1 is decode_device."""
-        t = self.torch
-        scale = _scale(scale, "decode_scaled_device")
+        what = "decode_scaled_device"
+        scale = _scale(scale, what)
         side = 512 // scale
-        dev = f"cuda:{self.device}"
-        for name, x, dt in (("arena", arena, t.uint8), ("offsets", offsets, t.int64), ("lengths", lengths, t.int32)):
-            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous()):
-                raise NhwError(f"decode_scaled_device: `{name}` must be a contiguous {dt} tensor on cuda:{self.device}")
-        n = offsets.numel()
-        if lengths.numel() != n or n < 1:
-            raise NhwError("decode_scaled_device: offsets and lengths must have one entry per file")
-        if n > self.max_batch:
-            raise NhwError(f"decode_scaled_device: {n} files for a decoder of max_batch {self.max_batch}")
-        if out is None:
-            out = t.empty((n, side, side, 3), dtype=t.uint8, device=dev)
-        elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == t.uint8 and out.is_contiguous()
-                  and out.numel() >= n * 3 * side * side and out.data_ptr() % 8 == 0):
-            raise NhwError(f"decode_scaled_device: `out` must be a contiguous, 8-byte aligned uint8 tensor of n*{3 * side * side} bytes on this decoder's device")
-        status = t.empty(n, dtype=t.int32, device=dev)
-        quality = t.empty(n, dtype=t.int32, device=dev)
+        n = self._device_files(arena, offsets, lengths, what)
+        out, px, status, quality = self._device_out(out, what, self.torch.uint8, (n, side, side, 3), 8,
+                                                    f"contiguous, 8-byte aligned uint8 tensor of n*{3 * side * side} bytes")
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_dec_batch_device_scaled(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, out.data_ptr(),
                                                            status.data_ptr(), quality.data_ptr(), st))
-        px = out if out.dim() == 4 and tuple(out.shape) == (n, side, side, 3) else out.reshape(-1)[:n * 3 * side * side].view(n, side, side, 3)
         return px, status, quality
 
     def decode_tensor_device(self, arena, offsets, lengths, fmt, scale=1, out=None):
@@ -1174,33 +1179,17 @@ class Decoder:
         Arguments as for decode_scaled_device; fmt: a TensorFormat; out: a contiguous, 16-byte aligned tensor of fmt.dtype with at least
         n * 3 * S * S elements, S = 512 // scale.  Returns (tensor [n, 3, S, S] or [n, S, S, 3], status[n], quality[n]) on the device; a
         refused file's slot is left untouched."""
-        t = self.torch
         what = "decode_tensor_device"
         fmt = _tensor_format(fmt, what)
         scale = _scale(scale, what)
         side = 512 // scale
-        dev = f"cuda:{self.device}"
-        for name, x, dt in (("arena", arena, t.uint8), ("offsets", offsets, t.int64), ("lengths", lengths, t.int32)):
-            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device.index == self.device and x.dtype == dt and x.is_contiguous()):
-                raise NhwError(f"{what}: `{name}` must be a contiguous {dt} tensor on cuda:{self.device}")
-        n = offsets.numel()
-        if lengths.numel() != n or n < 1:
-            raise NhwError(f"{what}: offsets and lengths must have one entry per file")
-        if n > self.max_batch:
-            raise NhwError(f"{what}: {n} files for a decoder of max_batch {self.max_batch}")
-        shape = (n,) + fmt.shape(side, side)
-        if out is None:
-            out = t.empty(shape, dtype=fmt.dtype, device=dev)
-        elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == fmt.dtype and out.is_contiguous()
-                  and out.numel() >= n * 3 * side * side and out.data_ptr() % 16 == 0):
-            raise NhwError(f"{what}: `out` must be a contiguous, 16-byte aligned {fmt.dtype} tensor of n*{3 * side * side} elements on this decoder's device")
-        status = t.empty(n, dtype=t.int32, device=dev)
-        quality = t.empty(n, dtype=t.int32, device=dev)
+        n = self._device_files(arena, offsets, lengths, what)
+        out, px, status, quality = self._device_out(out, what, fmt.dtype, (n,) + fmt.shape(side, side), 16,
+                                                    f"contiguous, 16-byte aligned {fmt.dtype} tensor of n*{3 * side * side} elements")
         c = fmt.c_struct()
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_dec_batch_device_tensor(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, ctypes.byref(c),
                                                            out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
-        px = out if tuple(out.shape) == shape else out.reshape(-1)[:n * 3 * side * side].view(shape)
         return px, status, quality
 
     def decode_scaled(self, files, scale):
@@ -1223,14 +1212,9 @@ class Decoder:
             raise NhwError(f"per-file status {status.tolist()}")
         return out, quality.tolist()
 
-    def decode_pictures_scaled(self, containers, scale):
-        """decode_pictures at scale 1, 2 or 4 (nhw_dec_pictures_scaled): a list of .nhwp containers (bytes) -> a list of numpy uint8
-        [ceil(H / scale), ceil(W / scale), 3], each assembled on the device from the scaled decode of its tiles: the overview of a large picture
-        without the level-1 synthesis of a single tile.  Raises on a malformed container or a tile the decoder refuses."""
+    def _pictures_host(self, containers, scale, call):
+        """decode_pictures and decode_pictures_scaled: call(blob, offsets, n, out, out_off, status) -> rc"""
         import numpy as np
-        scale = _scale(scale, "decode_pictures_scaled")
-        if not isinstance(containers, (list, tuple)) or len(containers) < 1:
-            raise NhwError("decode_pictures_scaled wants a non-empty list of containers")
         n = len(containers)
         shapes = [scaled_size(*picture_info(c), scale) for c in containers]
         offs = np.zeros(n + 1, np.uint64)
@@ -1240,30 +1224,26 @@ class Decoder:
         out_off[1:] = np.cumsum([3 * w * h for w, h in shapes])
         out = np.empty(int(out_off[n]), np.uint8)
         status = np.empty(n, np.int32)
-        self._chk(self.lib.nhw_dec_pictures_scaled(self.h, blob.ctypes.data, offs.ctypes.data, n, scale, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
+        self._chk(call(blob.ctypes.data, offs.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
         if (status != 0).any():
             raise NhwError(f"per-container status {status.tolist()}")
         return [out[int(out_off[i]):int(out_off[i + 1])].reshape(h, w, 3) for i, (w, h) in enumerate(shapes)]
 
+    def decode_pictures_scaled(self, containers, scale):
+        """decode_pictures at scale 1, 2 or 4 (nhw_dec_pictures_scaled): a list of .nhwp containers (bytes) -> a list of numpy uint8
+        [ceil(H / scale), ceil(W / scale), 3], each assembled on the device from the scaled decode of its tiles: the overview of a large picture
+        without the level-1 synthesis of a single tile.  Raises on a malformed container or a tile the decoder refuses."""
+        scale = _scale(scale, "decode_pictures_scaled")
+        if not isinstance(containers, (list, tuple)) or len(containers) < 1:
+            raise NhwError("decode_pictures_scaled wants a non-empty list of containers")
+        return self._pictures_host(containers, scale, lambda *a: self.lib.nhw_dec_pictures_scaled(self.h, *a[:3], scale, *a[3:]))
+
     def decode_pictures(self, containers):
         """containers: a list of .nhwp containers (bytes) -> a list of numpy uint8 [H, W, 3]: the tiles decoded in chunks of max_batch and
         cropped on the device (nhw_dec_pictures).  Raises on a malformed container or a tile the decoder refuses."""
-        import numpy as np
-        n = len(containers)
-        if n < 1:
+        if len(containers) < 1:
             raise NhwError("decode_pictures wants a non-empty list of containers")
-        shapes = [picture_info(c) for c in containers]
-        offs = np.zeros(n + 1, np.uint64)
-        offs[1:] = np.cumsum([len(c) for c in containers])
-        blob = np.frombuffer(b"".join(bytes(c) for c in containers), np.uint8)
-        out_off = np.zeros(n + 1, np.uint64)
-        out_off[1:] = np.cumsum([3 * w * h for w, h in shapes])
-        out = np.empty(int(out_off[n]), np.uint8)
-        status = np.empty(n, np.int32)
-        self._chk(self.lib.nhw_dec_pictures(self.h, blob.ctypes.data, offs.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
-        if (status != 0).any():
-            raise NhwError(f"per-container status {status.tolist()}")
-        return [out[int(out_off[i]):int(out_off[i + 1])].reshape(h, w, 3) for i, (w, h) in enumerate(shapes)]
+        return self._pictures_host(containers, 1, lambda *a: self.lib.nhw_dec_pictures(self.h, *a))
 
     def _region_args(self, containers, rects, what):
         """the packed containers and the checked nhw_rect table of a region call -> (blob, offsets, rect table)"""

@@ -11,43 +11,26 @@ static int host_buffers(nhw_dec *d, size_t total)
 	return d->d_off ? NHW_OK : dev_alloc(host_set(d), nullptr, d->max_batch, nhw_dec_err);   /* all five or none: a half-made set would hand null pointers to the next call */
 }
 
-/* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1]. */
-extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality)
+/* what every host call checks of its scale and of its offsets off[0 .. n] */
+static bool scale_ok(int scale)
 {
-	if (!d || !nhw || !off || !bgr || !status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	HIPCHK(hipSetDevice(d->device));
-	const size_t total = (size_t)(off[n] - off[0]);
-	{ const int rc = host_buffers(d, total); if (rc) return rc; }
-	uint64_t *rel = (uint64_t *)malloc(((size_t)n + 1) * 12);
-	if (!rel) return NHW_E_ARG;
-	uint32_t *len = (uint32_t *)(rel + n + 1);
-	for (int i = 0; i < n; i++) {
-		rel[i] = off[i] - off[0];
-		const uint64_t l = off[i + 1] - off[i];
-		len[i] = l > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l;
-	}
-	hipError_t e1 = hipMemcpyAsync(d->blob.p, nhw + off[0], total, hipMemcpyHostToDevice, d->own_stream);
-	hipError_t e2 = hipMemcpyAsync(d->d_off, rel, (size_t)n * 8, hipMemcpyHostToDevice, d->own_stream);
-	hipError_t e4 = hipMemcpyAsync(d->d_len, len, (size_t)n * 4, hipMemcpyHostToDevice, d->own_stream);
-	hipError_t e3 = hipStreamSynchronize(d->own_stream);
-	free(rel);
-	HIPCHK(e1); HIPCHK(e2); HIPCHK(e4); HIPCHK(e3);
-	const int rc = nhw_dec_batch_device(d, d->blob.p, d->d_off, d->d_len, n, d->d_out, d->d_status, d->d_quality, d->own_stream);
-	if (rc) return rc;
-	HIPCHK(hipMemcpyAsync(bgr, d->d_out, (size_t)n * NHW_IMG_BYTES, hipMemcpyDeviceToHost, d->own_stream));
-	HIPCHK(hipMemcpyAsync(status, d->d_status, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
-	if (quality) HIPCHK(hipMemcpyAsync(quality, d->d_quality, (size_t)n * 4, hipMemcpyDeviceToHost, d->own_stream));
-	HIPCHK(hipStreamSynchronize(d->own_stream));
-	return NHW_OK;
+	if (scale == 1 || scale == 2 || scale == 4) return true;
+	nhw_dec_err = "the scale must be 1, 2 or 4";
+	return false;
 }
 
-/* the same at scale 1, 2 or 4, for any n >= 1: the files go up once and are decoded in chunks of max_batch; file i's
- * 3 T T bytes (T = 512 / scale) land at out + i * 3 T T */
-extern "C" int nhw_dec_batch_scaled(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality)
+static bool offsets_ok(const uint64_t *off, int n, const char *who)
+{
+	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { nhw_dec_err = std::string(who) + ": off[] must not decrease"; return false; }
+	return true;
+}
+
+/* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1].  At scale 1, 2 or 4 (DESIGN.md section
+ * 14), for any n >= 1: the files go up once and are decoded in chunks of max_batch; file i's 3 T T bytes (T = 512 / scale) land at out + i * 3 T T */
+static int dec_batch_host(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality, const char *who)
 {
 	if (!d || !nhw || !off || !out || !status || n < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
-	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { nhw_dec_err = "nhw_dec_batch_scaled: off[] must not decrease"; return NHW_E_ARG; }
+	if (!scale_ok(scale) || !offsets_ok(off, n, who)) return NHW_E_ARG;
 	HIPCHK(hipSetDevice(d->device));
 	const size_t total = (size_t)(off[n] - off[0]), per = (size_t)NHW_IMG_BYTES / (size_t)(scale * scale);
 	{ const int rc = host_buffers(d, total); if (rc) return rc; }
@@ -73,6 +56,18 @@ extern "C" int nhw_dec_batch_scaled(nhw_dec *d, const uint8_t *nhw, const uint64
 		HIPCHK(hipStreamSynchronize(s));
 	}
 	return NHW_OK;
+}
+
+/* the full-size call takes one chunk: n <= max_batch */
+extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, uint8_t *bgr, int32_t *status, int32_t *quality)
+{
+	if (d && n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	return dec_batch_host(d, nhw, off, n, 1, bgr, status, quality, "nhw_dec_batch");
+}
+
+extern "C" int nhw_dec_batch_scaled(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality)
+{
+	return dec_batch_host(d, nhw, off, n, scale, out, status, quality, "nhw_dec_batch_scaled");
 }
 
 /* ---------------------------------------------------------------------------------------------- pictures of any size (DESIGN.md sections 11, 13, 14) */
@@ -117,10 +112,15 @@ static int32_t tiles_status(const std::vector<int32_t> &tst, int t0, int t1)   /
 	return NHW_OK;
 }
 
-/* results that decoded, device -> host: neighbours that are contiguous on both sides go as one copy */
-struct Span { uint64_t dev, host, len; };
-static int download_spans(uint8_t *bgr, const std::vector<Span> &sp)
+/* the results whose status is NHW_OK, device -> host: desc[k] (a picture or a region: 3 width height bytes at addr) is entry which[k] of the
+ * call and goes to bgr + out_off[which[k]]; neighbours that are contiguous on both sides go as one copy */
+template <class D>
+static int download_decoded(uint8_t *bgr, const uint64_t *out_off, const std::vector<D> &desc, const std::vector<int> &which, const int32_t *status)
 {
+	struct Span { uint64_t dev, host, len; };
+	std::vector<Span> sp;
+	for (size_t k = 0; k < desc.size(); k++)
+		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
 	for (size_t k = 0; k < sp.size();) {
 		uint64_t len = sp[k].len;
 		size_t j = k + 1;
@@ -137,8 +137,7 @@ static int download_spans(uint8_t *bgr, const std::vector<Span> &sp)
 static int dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, int scale, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
 {
 	if (!d || !blob || !off || !bgr || !out_off || !status || n < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
-	for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { nhw_dec_err = "nhw_dec_pictures: off[] must not decrease"; return NHW_E_ARG; }
+	if (!scale_ok(scale) || !offsets_ok(off, n, "nhw_dec_pictures")) return NHW_E_ARG;
 	std::vector<nhw_picture> desc;
 	std::vector<int> which;                                      /* desc[k] is container which[k] */
 	std::vector<uint64_t> toff;
@@ -172,12 +171,8 @@ static int dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, in
 	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)np * sizeof(nhw_picture), hipMemcpyHostToDevice, s));
 	std::vector<int32_t> tst;
 	{ const int rc = decode_tile_list(d, toff, tlen, scale, tst, [&](int t0, int m) { return nhw_launch_untile_crop(d->d_out, d_desc, np, t0, m, scale, s); }); if (rc) return rc; }
-	std::vector<Span> sp;
-	for (int k = 0; k < np; k++) {
-		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < np ? (int)desc[k + 1].first_tile : tiles);
-		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
-	}
-	return download_spans(bgr, sp);
+	for (int k = 0; k < np; k++) status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < np ? (int)desc[k + 1].first_tile : tiles);
+	return download_decoded(bgr, out_off, desc, which, status);
 }
 
 extern "C" int nhw_dec_pictures(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, uint8_t *bgr, const uint64_t *out_off, int32_t *status)
@@ -191,8 +186,7 @@ extern "C" int nhw_dec_pictures_scaled(nhw_dec *d, const uint8_t *blob, const ui
 	return dec_pictures(d, blob, off, n, scale, out, out_off, status);
 }
 
-/* ---------------------------------------------------------------------------------------------- regions of pictures */
-/* a container as the region calls see it: parsed once, when the first rect names it; start[k] = byte offset of tile file k in it */
+/* a container as the region and window calls see it: parsed once, when the first rect names it; start[k] = byte offset of tile file k in it */
 struct RegionSource {
 	int state;                                                   /* 0 not looked at, 1 well-formed, -1 malformed */
 	uint32_t w, h;
@@ -212,115 +206,43 @@ static void source_look(RegionSource &c, const uint8_t *base, size_t len)   /* t
 	}
 }
 
-/* Both region calls: bgr / out_off (the regions packed in a device buffer of the handle, then downloaded) or dst_addr / dst_pitch (cropped
- * straight into the caller's device memory).  The selected tile files are gathered on the host -- a selection row tx0 .. tx1 is one
- * contiguous byte run of its container -- and go up as one blob; the decoder gets their offsets and lengths as it does for whole pictures,
- * and every chunk is followed by k_untile_region. */
-static int dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, uint8_t *bgr, const uint64_t *out_off,
-                       const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who)
-{
-	const bool to_device = dst_addr != nullptr;
-	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (to_device ? !dst_pitch : (!bgr || !out_off))) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	for (int i = 0; i < nc; i++) if (off[i + 1] < off[i]) { nhw_dec_err = std::string(who) + ": off[] must not decrease"; return NHW_E_ARG; }
-	if (to_device) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_pitch[i] < 3ull * rects[i].width) { nhw_dec_err = std::string(who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
-	d->reg_tiles = d->reg_bytes = 0;
-	std::vector<RegionSource> src((size_t)nc);
-	std::vector<nhw_region> desc;
-	std::vector<int> which;                                      /* desc[k] is rect which[k] */
-	std::vector<uint64_t> toff;
-	std::vector<uint32_t> tlen;
-	std::vector<uint8_t> files;                                  /* the selected tile files, back to back */
-	uint64_t bytes = 0;
-	for (int i = 0; i < nr; i++) {
-		const nhw_rect &r = rects[i];
-		status[i] = NHW_E_ARG;
-		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
-		RegionSource &c = src[r.container];
-		const uint8_t *base = blob + off[r.container];
-		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
-		if (c.state < 0) { status[i] = NHW_E_FORMAT; continue; }
-		const int nt = nhw_region_tiles(c.w, c.h, r.x, r.y, r.width, r.height);
-		if (nt < 1) continue;
-		if (toff.size() + (size_t)nt > MAX_CALL_TILES) { nhw_dec_err = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
-		status[i] = NHW_OK;
-		desc.push_back({ to_device ? dst_addr[i] : bytes, to_device ? dst_pitch[i] : 3ull * r.width, r.x, r.y, r.width, r.height, c.w, c.h, (uint32_t)toff.size(), 0 });
-		which.push_back(i);
-		bytes += 3ull * r.width * r.height;
-		const uint32_t nx = (c.w + 511) / 512, tx0 = r.x / 512, tx1 = (r.x + r.width - 1) / 512;
-		for (uint32_t ty = r.y / 512; ty <= (r.y + r.height - 1) / 512; ty++) {
-			const uint32_t k0 = ty * nx + tx0, k1 = ty * nx + tx1;
-			for (uint32_t k = k0; k <= k1; k++) { toff.push_back(files.size() + (c.start[k] - c.start[k0])); tlen.push_back(dir_len(c.dir, (int)k)); }
-			files.insert(files.end(), base + c.start[k0], base + c.start[k1 + 1]);
-		}
-	}
-	if (desc.empty()) return NHW_OK;
-	const int tiles = (int)toff.size(), ng = (int)desc.size();
-	HIPCHK(hipSetDevice(d->device));
-	{ const int rc = host_buffers(d, files.size()); if (rc) return rc; }
-	HIPCHK(nhw_grow(d->pic_desc, (size_t)ng * sizeof(nhw_region)));
-	if (!to_device) {
-		HIPCHK(nhw_grow(d->pic_px, bytes));
-		for (nhw_region &g : desc) g.addr += (uint64_t)(uintptr_t)d->pic_px.p;
-	}
-	const nhw_region *d_desc = d->pic_desc.as<nhw_region>();
-	hipStream_t s = d->own_stream;
-	HIPCHK(hipMemcpyAsync(d->blob.p, files.data(), files.size(), hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(d->pic_desc.p, desc.data(), (size_t)ng * sizeof(nhw_region), hipMemcpyHostToDevice, s));
-	d->reg_tiles = (uint64_t)tiles; d->reg_bytes = files.size();
-	std::vector<int32_t> tst;
-	{ const int rc = decode_tile_list(d, toff, tlen, 1, tst, [&](int t0, int m) { return nhw_launch_untile_region(d->d_out, d_desc, ng, t0, m, s); }); if (rc) return rc; }
-	std::vector<Span> sp;
-	for (int k = 0; k < ng; k++) {
-		status[which[k]] = tiles_status(tst, (int)desc[k].first_tile, k + 1 < ng ? (int)desc[k + 1].first_tile : tiles);
-		if (!to_device && status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
-	}
-	return download_spans(bgr, sp);
-}
-
-extern "C" int nhw_dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
-                               uint8_t *bgr, const uint64_t *out_off, int32_t *status)
-{
-	return dec_regions(d, blob, off, n_containers, rects, n_rects, bgr, out_off, nullptr, nullptr, status, "nhw_dec_regions");
-}
-
-extern "C" int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
-                                         const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status)
-{
-	if (!dst_addr) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	return dec_regions(d, blob, off, n_containers, rects, n_rects, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_regions_to_device");
-}
-
-/* ---------------------------------------------------------------------------------------------- windows */
-/* Both window calls, as dec_regions serves both region calls: the same arguments plus the scale, the same statuses.  What differs: the
- * tiles of the call are the union of the windows' selections.  A tile gets a slot when the first window selects it (slot_of, per
- * container); only the files of those tiles are gathered, slot after slot, and decoded; every (window, tile) pair is a use, and the uses
- * sorted by slot make the chunk [t0, t0 + m) of decoded tiles the owner of the contiguous range [first_use[t0], first_use[t0 + m)), which
- * k_untile_window crops behind the chunk.  A window's status is the worst of its own tiles'.
+/* ---------------------------------------------------------------------------------------------- regions and windows (DESIGN.md sections 13, 15) */
+/* The region and window calls: bgr / out_off (the rectangles packed in a device buffer of the handle, then downloaded) or dst_addr / dst_pitch
+ * (cropped straight into the caller's device memory).  The tiles of a window call are the union of the windows' selections: a tile gets a
+ * slot when the first window selects it (slot_of, per container).  A region call is a window call at scale 1 with `merge` off: every selected
+ * tile of every rect gets a slot and a copy of its file of its own (section 13's contract: nhw_dec_last_region_stats counts them).  Only the
+ * files of the slots are gathered on the host, slot after slot, go up as one blob and are decoded as the tiles of whole pictures are; every
+ * (window, tile) pair is a use, and the uses sorted by slot (without merging: the order they were made in) make the chunk [t0, t0 + m) of
+ * decoded tiles the owner of the contiguous range [first_use[t0], first_use[t0 + m)), which k_untile_window crops behind the chunk.  A
+ * window's status is the worst of its own tiles'.
  * The crop call is the third form: `crop` set, dst_addr the tensors' addresses.  The windows are cropped into the handle's
  * staging as for the host form and stay there; behind the last chunk one k_resize_to_tensor takes every window whose tiles all decoded to its
  * tensor -- the others get the address 0, which the kernel passes over. */
 struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; };
 
 static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
-                       const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, const CropSpec *crop = nullptr)
+                       const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, bool merge = true,
+                       const CropSpec *crop = nullptr)
 {
 	const bool to_device = dst_addr != nullptr && !crop;
 	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || (crop ? !dst_addr : to_device ? !dst_pitch : (!bgr || !out_off))) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	if (!scale_ok(scale)) return NHW_E_ARG;
 	if (scale != 1 && d->stop_after) { nhw_dec_err = "a scaled decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
-	for (int i = 0; i < nc; i++) if (off[i + 1] < off[i]) { nhw_dec_err = std::string(who) + ": off[] must not decrease"; return NHW_E_ARG; }
+	if (!offsets_ok(off, nc, who)) return NHW_E_ARG;
 	if (to_device) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_pitch[i] < 3ull * rects[i].width) { nhw_dec_err = std::string(who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
 	if (crop) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_addr[i] % (crop->dtype == NHW_T_U8 ? 1u : crop->dtype == NHW_T_F32 ? 4u : 2u)) { nhw_dec_err = std::string(who) + ": a destination needs an address that is a multiple of the element size"; return NHW_E_ARG; }
 	d->reg_tiles = d->reg_bytes = 0;
 	const uint32_t T = 512u / (uint32_t)scale;
 	std::vector<RegionSource> src((size_t)nc);
-	std::vector<std::vector<int32_t>> slot_of((size_t)nc);        /* per container: a tile's slot, -1 while no window has selected it */
+	std::vector<std::vector<int32_t>> slot_of((size_t)nc);        /* per container: a tile's (latest) slot, -1 while no window has selected it */
 	std::vector<nhw_region> desc;
 	std::vector<int> which;                                      /* desc[k] is rect which[k] */
 	std::vector<nhw_window_use> uses;
 	std::vector<uint64_t> toff;
 	std::vector<uint32_t> tlen;
-	std::vector<uint8_t> files;                                  /* the unique tile files, slot after slot */
+	std::vector<uint8_t> files;                                  /* the slots' tile files, slot after slot */
+	const uint8_t *run = nullptr, *run_end = nullptr;            /* ... but for the latest slots' files, which lie back to back in their container: a row of a
+	                                                              * selection goes in as one run (one append a tile measured a quarter more for the gather) */
 	uint64_t bytes = 0;
 	for (int i = 0; i < nr; i++) {
 		const nhw_rect &r = rects[i];
@@ -345,15 +267,20 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		for (uint32_t ty = r.y / T; ty <= (r.y + r.height - 1) / T; ty++)
 			for (uint32_t tx = r.x / T; tx <= (r.x + r.width - 1) / T; tx++) {
 				const uint32_t k = ty * nx + tx;
-				if (slot[k] < 0) {
+				if (!merge || slot[k] < 0) {
 					slot[k] = (int32_t)toff.size();
-					toff.push_back(files.size());
+					if (run_end != base + c.start[k]) {                     /* not the file behind the last one: the run so far goes in */
+						files.insert(files.end(), run, run_end);
+						run = base + c.start[k];
+					}
+					toff.push_back(files.size() + (uint64_t)(base + c.start[k] - run));
 					tlen.push_back(dir_len(c.dir, (int)k));
-					files.insert(files.end(), base + c.start[k], base + c.start[k + 1]);
+					run_end = base + c.start[k + 1];
 				}
 				uses.push_back({ (uint32_t)desc.size() - 1, (uint32_t)slot[k], tx, ty });
 			}
 	}
+	files.insert(files.end(), run, run_end);
 	if (desc.empty()) return NHW_OK;
 	const int tiles = (int)toff.size(), ng = (int)desc.size(), nu = (int)uses.size();
 	std::vector<int> first_use((size_t)tiles + 1, 0);             /* sorted by slot (a counting sort): uses [first_use[t], first_use[t + 1]) are those of slot t */
@@ -403,10 +330,20 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		HIPCHK(hipStreamSynchronize(s));
 		return NHW_OK;
 	}
-	std::vector<Span> sp;
-	if (!to_device) for (int k = 0; k < ng; k++)
-		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
-	return download_spans(bgr, sp);
+	return to_device ? NHW_OK : download_decoded(bgr, out_off, desc, which, status);
+}
+
+extern "C" int nhw_dec_regions(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
+                               uint8_t *bgr, const uint64_t *out_off, int32_t *status)
+{
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, 1, bgr, out_off, nullptr, nullptr, status, "nhw_dec_regions", false);
+}
+
+extern "C" int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects,
+                                         const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status)
+{
+	if (!dst_addr) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, 1, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_regions_to_device", false);
 }
 
 extern "C" int nhw_dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
@@ -432,7 +369,7 @@ extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const ui
 	CropSpec c = { out_width, out_height, 0, 0, {}, flags };
 	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
 	c.dtype = fmt->dtype; c.layout = fmt->layout;
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", &c);
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", true, &c);
 }
 
 extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)

@@ -1,17 +1,20 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 18): the padding kernel k_tile_pad, its inverse
- * k_untile_crop (also for the 256 and 128 tiles of a scaled decode), the rectangle-of-a-picture crops k_untile_region and k_untile_window, the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16) and its resampling form k_resize_to_tensor (section 18), its mirrors k_tensor_to_bytes and k_tile_pad_tensor
- * (section 17), and the .nhwp container that
- * holds a picture's width, height and tile files.
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 18): the padding kernel k_tile_pad; the crops, which
+ * share one body (crop_band over copy_rows) and differ in how a workgroup learns its tile and its rectangle -- k_untile_crop (k_tile_pad's
+ * inverse: the whole picture, also from the 256 and 128 tiles of a scaled decode), k_untile_region (first_tile search) and k_untile_window (use
+ * table) --; the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16) and its resampling form k_resize_to_tensor
+ * (section 18), its mirrors k_tensor_to_bytes and k_tile_pad_tensor (section 17), and the .nhwp container that holds a picture's width, height
+ * and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
  * ny = ceil(H / 512), by edge replication: padded pixel (r, c) = picture pixel (min(r, H - 1), min(c, W - 1)).  Tile (ty, tx) is padded
  * rows 512 ty .. and columns 512 tx .., index ty nx + tx; a picture's tiles are numbered from its descriptor's first_tile on.
  *
- * The first two kernels are copies: a workgroup moves one band of TP_ROWS rows of one tile (k_sse_crop reads one the same way).  The picture side may have any alignment and any
- * pitch, so its bytes are reached through the naturally aligned dwords that hold them, funnelled together with v_alignbyte_b32 (fetch);
- * the tile side is 16-byte aligned and moves in dwordx4.  No load touches a word that holds no byte of a picture row (or, for
- * k_untile_crop, of the tile rows it reads), and no store touches a byte outside a picture row.
+ * k_tile_pad and the crops are copies: a workgroup moves one band of TP_ROWS rows of one tile (k_sse_crop reads one the same way).  The
+ * picture side may have any alignment and any pitch.  k_tile_pad reaches its bytes through the naturally aligned dwords that hold them,
+ * funnelled together with v_alignbyte_b32 (fetch), and stores the 16-byte-aligned tile side in dwordx4; the crops store the 16-byte-aligned
+ * words of the picture side and fetch the tile side at whatever phase that leaves.  No load touches a word that holds no byte of a picture
+ * row (or, for the crops, of the tile bytes they store), and no store touches a byte outside a picture row.
  */
 #include <string.h>
 #include <type_traits>
@@ -152,32 +155,94 @@ __device__ __forceinline__ void store_part(uint8_t *A, uint4 v, int j, int e)
 	}
 }
 
-/* the inverse: tile row rr (a picture row r = T ty + rr < H) holds picture bytes [3T tx, min(3T tx + 3T, 3W)) of row r (T = 512: 1536).  They go
- * out as the 16-byte-aligned destination words that cover them (at most 3T / 16 + 1 a row: 97), whole words as dwordx4, the ragged head and tail with
- * store_part.  The source side reads the tile row through fetch, only the bytes it stores.  T = 256, 128: the tiles of a scaled decode, 3 T T
- * bytes each, into the scaled pictures of the table. */
-template <int T>
-__global__ __launch_bounds__(TP_THREADS) void k_untile_crop(const uint8_t *__restrict__ tiles, const nhw_picture *__restrict__ pics, int n_pics, int tile0)
+/* ---- the crops: what a tile and a rectangle of its picture have in common, from the tile to the rectangle's destination ----
+ * The copy: `rows` rows of seg bytes (3 .. ROW), row q from src + q ROW (anywhere inside a tile row of ROW bytes) to dst + q pitch (any
+ * alignment, any pitch).  The 16-byte-aligned destination words that cover a row's bytes, whole ones as dwordx4, the ragged head and tail
+ * with store_part, the tile side through fetch, only the bytes it stores; the two sides have independent phases, and the words a row needs
+ * (at most seg / 16 + 2; a whole row of a 512 tile: 97) depend on seg: the rows x that many slots are dealt out flat over the threads (slot
+ * -> row by a multiply-high with the reciprocal, exact for the 32 x 97 slots a band can have), so that a 224-pixel crop does not walk 97
+ * slots a row. */
+template <int ROW>
+__device__ __forceinline__ void copy_rows(uintptr_t src, uintptr_t dst, uint64_t pitch, int seg, uint32_t rows)
 {
-	constexpr int BANDS = T / TP_ROWS, ROW = 3 * T;
-	TileRef r;
-	if (!tile_of<T>(pics, n_pics, tile0, r)) return;
-	const int band = blockIdx.x % BANDS;
-	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / BANDS) * (size_t)(ROW * T));
-	const int rb = 3 * (int)r.p.width, s0 = ROW * (int)r.tx, seg = rb - s0 < ROW ? rb - s0 : ROW;
-	constexpr int SLOTS = ROW / 16 + 1;
-	for (int i = threadIdx.x; i < TP_ROWS * SLOTS; i += TP_THREADS) {
-		const int rr = band * TP_ROWS + i / SLOTS, k = i % SLOTS;
-		const uint32_t row = T * r.ty + rr;
-		if (row >= r.p.height) break;                                 /* (rows only grow with i) */
-		const uintptr_t D0 = (uintptr_t)(r.p.addr + (uint64_t)row * r.p.pitch) + s0, D1 = D0 + seg;
+	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = rows * slots;   /* 2 .. 97 words cover seg bytes at any phase */
+	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots */
+	for (uint32_t i = threadIdx.x; i < total; i += TP_THREADS) {
+		const uint32_t q = __umulhi(i, rcp), k = i - q * slots;            /* row q of the band's wanted rows, word k of it */
+		const uintptr_t D0 = dst + (uint64_t)q * pitch, D1 = D0 + seg;
 		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
 		if (A >= D1) continue;
 		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
-		const uint4 v = fetch(src + (uintptr_t)rr * ROW + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
+		const uint4 v = fetch(src + (uintptr_t)q * ROW + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
 		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
 		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
 	}
+}
+
+/* The workgroup's band of TP_ROWS rows of the tile (ty, tx) of side T at `tile` (3 T bytes a row; T = 512, or 256 or 128: the tiles of a
+ * scaled decode), into the rectangle x, y, width, height of g: tile row rr is picture row T ty + rr, wanted if
+ * y <= row < y + height; of it the picture columns [c0, c1) = [max(T tx, x), min(T tx + T, x + width)) go from tile byte 3 (c0 - T tx) of
+ * the row to byte 3 (c0 - x) of destination row (row - y).  A band or a tile that shares nothing with the rectangle stores nothing. */
+template <int T>
+__device__ __forceinline__ void crop_band(const uint8_t *tile, uint32_t ty, uint32_t tx, const nhw_region &g)
+{
+	constexpr int ROW = 3 * T;
+	const uint32_t top = T * ty + (blockIdx.x % (T / TP_ROWS)) * TP_ROWS;   /* picture row of the band's first row */
+	const uint32_t lo = top > g.y ? top : g.y, hi = top + TP_ROWS < g.y + g.height ? top + TP_ROWS : g.y + g.height;
+	const uint32_t c0 = T * tx > g.x ? T * tx : g.x, c1 = T * tx + T < g.x + g.width ? T * tx + T : g.x + g.width;
+	if (lo >= hi || c0 >= c1) return;
+	const uintptr_t src = (uintptr_t)tile + (uintptr_t)(lo - T * ty) * ROW + 3 * (c0 - T * tx);
+	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
+	copy_rows<ROW>(src, dst, g.pitch, 3 * (int)(c1 - c0), hi - lo);      /* 3 .. 3 T bytes a row */
+}
+
+/* a rectangle of a picture whose tiles have the side T: not empty, the picture's sides at most the largest scaled ones (65535, 32768, 16384),
+ * the rectangle inside them */
+template <int T>
+__device__ __forceinline__ bool rect_of_picture(const nhw_region &g)
+{
+	constexpr uint32_t SIDE_MAX = (65535 + 512 / T - 1) / (512 / T);
+	return g.width && g.height && g.pic_width <= SIDE_MAX && g.pic_height <= SIDE_MAX && (uint64_t)g.x + g.width <= g.pic_width && (uint64_t)g.y + g.height <= g.pic_height;
+}
+
+/* k_tile_pad's inverse: global tile tile0 + blockIdx.x / bands of a tile, into the picture that holds it -- the rectangle
+ * that is all of the picture.  T = 256, 128: the tiles of a scaled decode, into the scaled pictures of the table. */
+template <int T>
+__global__ __launch_bounds__(TP_THREADS) void k_untile_crop(const uint8_t *__restrict__ tiles, const nhw_picture *__restrict__ pics, int n_pics, int tile0)
+{
+	TileRef r;
+	if (!tile_of<T>(pics, n_pics, tile0, r)) return;
+	crop_band<T>(tiles + (size_t)(blockIdx.x / (T / TP_ROWS)) * (size_t)(3 * T * T), r.ty, r.tx, { r.p.addr, r.p.pitch, 0, 0, r.p.width, r.p.height, r.p.width, r.p.height, 0, 0 });
+}
+
+/* A rectangle of a picture from the tiles it touches: tile t = tile0 + blockIdx.x / TP_BANDS of the call's running
+ * selection belongs to the last descriptor with first_tile <= t and is tile t - first_tile of that region's selection, row by row. */
+__global__ __launch_bounds__(TP_THREADS) void k_untile_region(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs, int tile0)
+{
+	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
+	const nhw_region g = regs[find_picture(regs, n_regs, t)];
+	if (t < g.first_tile || !rect_of_picture<512>(g)) return;
+	const uint32_t tx0 = g.x / 512, ty0 = g.y / 512, nx = (g.x + g.width - 1) / 512 - tx0 + 1, ny = (g.y + g.height - 1) / 512 - ty0 + 1;
+	const uint32_t in = t - g.first_tile;
+	if (in >= nx * ny) return;
+	crop_band<512>(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES, ty0 + in / nx, tx0 + in % nx, g);
+}
+
+/* Windows: rectangles of pictures at scale 1, 2 or 4, every tile decoded once.  One workgroup per band of a USE, a
+ * (window, tile) pair of the table: tile (ty, tx) of the picture's grid, decoded into slot u.slot of the call's tiles, feeds window
+ * regs[u.region].  The descriptor is section 13's, in the coordinates of the scaled picture (pic_width x pic_height: the scaled sides;
+ * first_tile is not read).  A use that names no region of the table, a slot outside the buffer's [tile0, tile0 + m), a tile outside the
+ * window's selection or a descriptor that is no window of a picture stores nothing. */
+template <int T>
+__global__ __launch_bounds__(TP_THREADS) void k_untile_window(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs,
+                                                               const nhw_window_use *__restrict__ uses, int tile0, int m)
+{
+	const nhw_window_use u = uses[blockIdx.x / (T / TP_ROWS)];
+	if (u.region >= (uint32_t)n_regs || u.slot < (uint32_t)tile0 || u.slot - (uint32_t)tile0 >= (uint32_t)m) return;
+	const nhw_region g = regs[u.region];
+	if (!rect_of_picture<T>(g)) return;
+	if (u.tx < g.x / T || u.tx > (g.x + g.width - 1) / T || u.ty < g.y / T || u.ty > (g.y + g.height - 1) / T) return;   /* not a tile of the window's selection */
+	crop_band<T>(tiles + (size_t)(u.slot - (uint32_t)tile0) * (size_t)(3 * T * T), u.ty, u.tx, g);
 }
 
 /* The SSE of decoded tiles against the pictures' own bytes: tile row rr of tile (ty, tx) against picture row 512 ty + rr < H, bytes
@@ -253,98 +318,6 @@ __global__ __launch_bounds__(TP_THREADS) void k_sse_crop(const uint8_t *__restri
 		for (int w = 0; w < TP_THREADS / 64; w++) s += wsum[w];
 		atomicAdd(sse + r.k, s);
 	}
-}
-
-/* The copy of the region and window kernels: `rows` rows of seg bytes (3 .. ROW), row q from src + q ROW (anywhere inside a tile row of ROW
- * bytes) to dst + q pitch (any alignment, any pitch).  The 16-byte-aligned destination words that cover a row's bytes, whole ones as dwordx4,
- * the ragged head and tail with store_part, the tile side through fetch; the two sides have independent phases, and the words a row needs
- * (at most seg / 16 + 2) depend on seg: the rows x that many slots are dealt out flat over the threads (slot -> row by a multiply-high
- * with the reciprocal, exact for the 32 x 97 slots a band can have), so that a 224-pixel crop does not walk 97 slots a row. */
-template <int ROW>
-__device__ __forceinline__ void copy_rows(uintptr_t src, uintptr_t dst, uint64_t pitch, int seg, uint32_t rows)
-{
-	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = rows * slots;   /* 2 .. 97 words cover seg bytes at any phase */
-	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots */
-	for (uint32_t i = threadIdx.x; i < total; i += TP_THREADS) {
-		const uint32_t q = __umulhi(i, rcp), k = i - q * slots;            /* row q of the band's wanted rows, word k of it */
-		const uintptr_t D0 = dst + (uint64_t)q * pitch, D1 = D0 + seg;
-		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
-		if (A >= D1) continue;
-		const int j = A < D0 ? (int)(D0 - A) : 0, e = A + 16 > D1 ? (int)(D1 - A) : 16;
-		const uint4 v = fetch(src + (uintptr_t)q * ROW + (A - D0), j, e);   /* (A - D0 wraps below 0 for the head word: fetch reads from byte j on) */
-		if (j == 0 && e == 16) *reinterpret_cast<uint4 *>(A) = v;
-		else store_part(reinterpret_cast<uint8_t *>(A), v, j, e);
-	}
-}
-
-/* ---- a rectangle of a picture from the tiles it touches ----
- * the region holding tile t of the call's running selection: the last descriptor with first_tile <= t (find_picture's search on the
- * 48-byte descriptors) */
-__device__ __forceinline__ int find_region(const nhw_region *regs, int n, uint32_t t)
-{
-	int lo = 0, hi = n;
-	const int lane = threadIdx.x & 63;
-	while (hi - lo > 1) {
-		const int step = (hi - lo + 63) / 64, idx = lo + lane * step;
-		const bool le = idx < hi && regs[idx].first_tile <= t;
-		const int c = __popcll(__ballot(le));
-		lo += (c > 0 ? c - 1 : 0) * step;
-		hi = lo + step < hi ? lo + step : hi;
-	}
-	return __builtin_amdgcn_readfirstlane(lo);
-}
-
-/* Selected tile (ty, tx) of a region x, y, w, h: tile row rr is picture row 512 ty + rr, wanted if y <= row < y + h; of it the picture
- * columns [c0, c1) = [max(512 tx, x), min(512 tx + 512, x + w)) go from tile byte 3 (c0 - 512 tx) of the row to destination byte
- * 3 (c0 - x) of destination row (row - y).  The same copy as k_untile_crop, but the source starts anywhere inside a tile row: copy_rows. */
-__global__ __launch_bounds__(TP_THREADS) void k_untile_region(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs, int tile0)
-{
-	const uint32_t t = (uint32_t)tile0 + blockIdx.x / TP_BANDS;
-	const nhw_region g = regs[find_region(regs, n_regs, t)];
-	if (!g.width || !g.height || t < g.first_tile) return;
-	if (g.pic_width > 65535 || g.pic_height > 65535 || (uint64_t)g.x + g.width > g.pic_width || (uint64_t)g.y + g.height > g.pic_height) return;   /* not a region of a picture */
-	const uint32_t tx0 = g.x / 512, ty0 = g.y / 512, nx = (g.x + g.width - 1) / 512 - tx0 + 1, ny = (g.y + g.height - 1) / 512 - ty0 + 1;
-	const uint32_t in = t - g.first_tile;
-	if (in >= nx * ny) return;
-	const uint32_t ty = ty0 + in / nx, tx = tx0 + in % nx;
-	/* the band's rows inside the region: tile rows [r0, r1) */
-	const uint32_t top = 512 * ty + (blockIdx.x % TP_BANDS) * TP_ROWS;   /* picture row of the band's first row */
-	const uint32_t lo = top > g.y ? top : g.y, hi = top + TP_ROWS < g.y + g.height ? top + TP_ROWS : g.y + g.height;
-	if (lo >= hi) return;                                                /* a band with no row inside the region */
-	const uint32_t c0 = 512 * tx > g.x ? 512 * tx : g.x, c1 = 512 * tx + 512 < g.x + g.width ? 512 * tx + 512 : g.x + g.width;
-	const int seg = 3 * (int)(c1 - c0);                                  /* 3 .. 1536 bytes a row */
-	const uintptr_t src = (uintptr_t)(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES) + (uintptr_t)(lo - 512 * ty) * 1536 + 3 * (c0 - 512 * tx);
-	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
-	copy_rows<1536>(src, dst, g.pitch, seg, hi - lo);
-}
-
-/* ---- windows: rectangles of pictures at scale 1, 2 or 4, every tile decoded once ----
- * One workgroup per 32-row band of a USE, a (window, tile) pair of the table: tile (ty, tx) of the picture's grid, decoded into slot
- * u.slot of the call's unique tiles, feeds window regs[u.region].  The descriptor is section 13's, in the coordinates of the scaled
- * picture (pic_width x pic_height: the scaled sides; first_tile is not read); tile row rr is scaled-picture row T ty + rr, a row of tile
- * bytes 3 T.  A use that names no region of the table, a slot outside the buffer's [tile0, tile0 + m), a tile outside the window's
- * selection or a descriptor that is no window of a picture stores nothing.  The copy is k_untile_region's (copy_rows). */
-template <int T>
-__global__ __launch_bounds__(TP_THREADS) void k_untile_window(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs,
-                                                               const nhw_window_use *__restrict__ uses, int tile0, int m)
-{
-	constexpr int BANDS = T / TP_ROWS, ROW = 3 * T;
-	constexpr uint32_t SIDE_MAX = (65535 + 512 / T - 1) / (512 / T);     /* the largest scaled side: 65535, 32768, 16384 */
-	const nhw_window_use u = uses[blockIdx.x / BANDS];
-	if (u.region >= (uint32_t)n_regs || u.slot < (uint32_t)tile0 || u.slot - (uint32_t)tile0 >= (uint32_t)m) return;
-	const nhw_region g = regs[u.region];
-	if (!g.width || !g.height) return;
-	if (g.pic_width > SIDE_MAX || g.pic_height > SIDE_MAX || (uint64_t)g.x + g.width > g.pic_width || (uint64_t)g.y + g.height > g.pic_height) return;   /* not a window of a picture */
-	if (u.tx < g.x / T || u.tx > (g.x + g.width - 1) / T || u.ty < g.y / T || u.ty > (g.y + g.height - 1) / T) return;   /* not a tile of the window's selection */
-	/* the band's rows inside the window: scaled-picture rows [lo, hi) */
-	const uint32_t top = T * u.ty + (blockIdx.x % BANDS) * TP_ROWS;
-	const uint32_t lo = top > g.y ? top : g.y, hi = top + TP_ROWS < g.y + g.height ? top + TP_ROWS : g.y + g.height;
-	if (lo >= hi) return;
-	const uint32_t c0 = T * u.tx > g.x ? T * u.tx : g.x, c1 = T * u.tx + T < g.x + g.width ? T * u.tx + T : g.x + g.width;
-	const int seg = 3 * (int)(c1 - c0);                                  /* 3 .. 3 T bytes a row */
-	const uintptr_t src = (uintptr_t)(tiles + (size_t)(u.slot - (uint32_t)tile0) * (size_t)(ROW * T)) + (uintptr_t)(lo - T * u.ty) * ROW + 3 * (c0 - T * u.tx);
-	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
-	copy_rows<ROW>(src, dst, g.pitch, seg, hi - lo);
 }
 
 /* What is already bytes, to a tensor format: picture k of the table to [H][W][3] or [3][H][W] elements at out_addr[k], under the
@@ -583,13 +556,24 @@ hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0,
 	return hipGetLastError();
 }
 
+/* f(the tile side 512 / scale as a std::integral_constant) for a scale of 1, 2 or 4, and the launch's error; any other scale is refused */
+template <class F> static hipError_t with_tile_side(int scale, F &&f)
+{
+	switch (scale) {
+	case 1: f(std::integral_constant<int, 512>{}); break;
+	case 2: f(std::integral_constant<int, 256>{}); break;
+	case 4: f(std::integral_constant<int, 128>{}); break;
+	default: return hipErrorInvalidValue;
+	}
+	return hipGetLastError();
+}
+
 hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, int scale, hipStream_t s)
 {
-	if (scale == 1) k_untile_crop<512><<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
-	else if (scale == 2) k_untile_crop<256><<<m * (256 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
-	else if (scale == 4) k_untile_crop<128><<<m * (128 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
-	else return hipErrorInvalidValue;
-	return hipGetLastError();
+	return with_tile_side(scale, [&](auto side) {
+		constexpr int T = decltype(side)::value;
+		k_untile_crop<T><<<m * (T / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_pics, n_pics, tile0);
+	});
 }
 
 hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, hipStream_t s)
@@ -600,11 +584,10 @@ hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_
 
 hipError_t nhw_launch_untile_window(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses, int tile0, int m, int scale, hipStream_t s)
 {
-	if (scale == 1) k_untile_window<512><<<n_uses * TP_BANDS, TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
-	else if (scale == 2) k_untile_window<256><<<n_uses * (256 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
-	else if (scale == 4) k_untile_window<128><<<n_uses * (128 / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
-	else return hipErrorInvalidValue;
-	return hipGetLastError();
+	return with_tile_side(scale, [&](auto side) {
+		constexpr int T = decltype(side)::value;
+		k_untile_window<T><<<n_uses * (T / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
+	});
 }
 
 hipError_t nhw_launch_sse_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, hipStream_t s)

@@ -378,6 +378,48 @@ def test_decode_regions_device_writes_only_the_regions(world):
         world.dec.decode_regions_device(world.containers, crops[:1], out=[batch[0].transpose(0, 1)])
 
 
+@pytest.mark.gpu
+def test_regions_whose_repeated_tiles_straddle_chunks(world):
+    """a 700 x 600 picture (a 2 x 2 grid) on a decoder of max_batch 2: tile (1, 1) alone, all four tiles, tile (1, 1) again -- unmerged
+    1 + 4 + 1 = 6 slots, so that chunks of 2 cut the four-tile rect's slots 1 .. 4 across three chunks and tile (1, 1) is decoded in three of
+    them; the same rects as windows at scale 1 decode the four tiles once"""
+    import nhwcodec_amd as na
+    import torch
+    e = na.Encoder(0, max_batch=4)
+    container = e.encode_pictures([np.ascontiguousarray(world.pics[3][:600, :700])], 20)[0]
+    e.close()
+    W, H, files = parse_container(container)
+    assert (W, H, len(files)) == (700, 600, 4)
+    rects = [(0, 520, 515, 50, 40), (0, 100, 100, 500, 450), (0, 520, 515, 50, 40)]
+    assert [selected(W, *r[1:]) for r in rects] == [[3], [0, 1, 2, 3], [3]]
+    unmerged = (6, 2 * len(files[3]) + sum(len(f) for f in files))
+    assert expected_stats([container], rects) == unmerged
+    dec = na.Decoder(0, max_batch=2)
+    full = dec.decode_pictures([container])[0]
+    assert full.shape == (600, 700, 3)
+    want = [full[y:y + h, x:x + w] for _, x, y, w, h in rects]
+
+    def check(got):
+        assert len(got) == len(want)
+        for g, f in zip(got, want):
+            assert np.array_equal(g.cpu().numpy() if isinstance(g, torch.Tensor) else g, f)
+
+    check(dec.decode_regions([container], rects))
+    assert dec.region_stats() == unmerged
+    buf, views = _dest_views([(w, h) for _, _, _, w, h in rects])
+    check(dec.decode_regions_device([container], rects, out=views))
+    assert dec.region_stats() == unmerged
+    assert bool((buf[~_mask(buf, views)] == CANARY).all()), "a byte outside the regions was written"
+    merged = (4, sum(len(f) for f in files))
+    check(dec.decode_windows([container], rects, 1))
+    assert dec.region_stats() == merged
+    buf2, views2 = _dest_views([(w, h) for _, _, _, w, h in rects])
+    check(dec.decode_windows_device([container], rects, 1, out=views2))
+    assert dec.region_stats() == merged
+    assert torch.equal(buf, buf2)                                    # the same bytes, canaries included
+    dec.close()
+
+
 def _call_regions(dec, containers, rects, canary_host=None, dst=None):
     """nhw_dec_regions (or, with dst = (addresses, pitches), nhw_dec_regions_to_device) by ctypes: the wrappers raise on a status
     -> (rc, status, the host buffer, its offsets)"""

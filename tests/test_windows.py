@@ -359,6 +359,67 @@ def _pitch(v):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("scale", SCALES)
+def test_whole_picture_windows_write_what_the_picture_crop_writes(scale):
+    """the crop kernels against each other, no decode: random bytes as the tiles of four scaled pictures -- 1 x 1, 5 x 3, a 2 x 1 grid with a
+    one-pixel last column, a 3 x 2 grid -- written by nhw_untile_pictures_scaled_device, by nhw_untile_windows_device (window = the whole
+    picture, uses in slot order) and, at T = 512, by nhw_untile_regions_device, each into its own canary-filled buffer at the same
+    misalignments and pitches: the buffers are equal byte for byte and hold the numpy crop of the tiles"""
+    import nhwcodec_amd as na
+    import torch
+    T = 512 // scale
+    sizes = [(1, 1), (5, 3), (T + 1, T // 2 + 1), (2 * T + 1, T + 1)]   # W, H
+    grids = [(-(-w // T), -(-h // T)) for w, h in sizes]
+    assert grids == [(1, 1), (1, 1), (2, 1), (3, 2)]
+    first = np.concatenate([[0], np.cumsum([nx * ny for nx, ny in grids])])
+    n_tiles = int(first[-1])
+    tiles_h = np.random.default_rng(90 + scale).integers(0, 256, (n_tiles, T, T, 3), dtype=np.uint8)
+    tiles = torch.from_numpy(tiles_h).cuda()
+    want = [np.concatenate([np.concatenate(list(tiles_h[f + r * nx:f + (r + 1) * nx]), axis=1) for r in range(ny)], axis=0)[:h, :w]
+            for (w, h), (nx, ny), f in zip(sizes, grids, first)]
+    lib = na._library()
+    keep = []                                                        # the tables, until the launches have run
+
+    def filled(launch):
+        """launch(views) writes the pictures; -> the whole buffer, checked against the numpy crop"""
+        buf, views = _dest_views(sizes)
+        assert launch(views) == 0
+        torch.cuda.synchronize()
+        for v, w in zip(views, want):
+            assert np.array_equal(v.cpu().numpy(), w)
+        assert bool((buf[~_mask(buf, views)] == CANARY).all()), "a byte outside the pictures was written"
+        return buf
+
+    def regions(views, numbered):
+        table = (Region * len(sizes))(*[Region(v.data_ptr(), _pitch(v), 0, 0, w, h, w, h, int(f) if numbered else 0xDEAD, 0)
+                                        for v, (w, h), f in zip(views, sizes, first)])
+        keep.append(torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()).cuda())
+        return keep[-1]
+
+    def by_pictures(views):
+        table = np.zeros(len(sizes), na.PICTURE_DTYPE)
+        for k, (v, (w, h)) in enumerate(zip(views, sizes)):
+            table[k] = (v.data_ptr(), _pitch(v), w, h, first[k], 0)
+        keep.append(torch.from_numpy(table.view(np.uint8).copy()).cuda())
+        return lib.nhw_untile_pictures_scaled_device(tiles.data_ptr(), keep[-1].data_ptr(), len(sizes), 0, n_tiles, scale, None)
+
+    def by_windows(views):
+        uses = [Use(k, int(first[k]) + ty * nx + tx, tx, ty) for k, (nx, ny) in enumerate(grids) for ty in range(ny) for tx in range(nx)]
+        assert [u.slot for u in uses] == list(range(n_tiles))
+        d_uses = torch.from_numpy(np.frombuffer(bytes((Use * len(uses))(*uses)), np.uint8).copy()).cuda()
+        keep.append(d_uses)
+        return lib.nhw_untile_windows_device(tiles.data_ptr(), regions(views, False).data_ptr(), len(sizes), d_uses.data_ptr(), len(uses), 0, n_tiles, scale, None)
+
+    def by_regions(views):
+        return lib.nhw_untile_regions_device(tiles.data_ptr(), regions(views, True).data_ptr(), len(sizes), 0, n_tiles, None)
+
+    a, b = filled(by_pictures), filled(by_windows)
+    assert torch.equal(a, b)
+    if scale == 1:
+        assert torch.equal(a, filled(by_regions))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scale", SCALES)
 def test_untile_windows_device_writes_only_the_windows(scale):
     """the kernel on its own, no decode: six tiles of random bytes as the 2 x 3 grid of a picture with odd sides, destinations at every
     misalignment, the launch split into two chunks that both see the whole use table, and uses that must store nothing"""
