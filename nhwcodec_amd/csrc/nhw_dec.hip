@@ -102,6 +102,8 @@ DEV int16_t *plane_l1(const DecWs &ws, int img) { return ws.buf<int16_t>(D_B, im
 #define ENT_MAKE(pos, v) (((uint32_t)(v) << 18) | (uint32_t)(pos))
 DEV uint16_t *mark_rows(const DecWs &ws, int img) { return ws.buf<uint16_t>(D_SPARE, img) + 8; }   /* behind the verdict words */
 /* the prefix-code walk's verdict on a file: a word per stream (each written by that stream's workgroup only), 0 = fine */
+DEV int *l1_far_flag(const DecWs &ws, int img) { return ws.buf<int>(D_SPARE, img) + 2; }   /* between the verdict words and mark_rows */
+DEV bool l1_far(const DecWs &ws, int img) { return *l1_far_flag(ws, img) != 0; }
 DEV int walk_verdict(const DecWs &ws, int img) { const int *v = ws.buf<int>(D_SPARE, img); return v[0] ? v[0] : v[1]; }
 DEV int16_t *plane_ca(const DecWs &ws, int img, int comp) { return ws.buf<int16_t>(D_CA, img) + 1024 + (size_t)comp * (DQ + 2048); }
 
@@ -1007,6 +1009,7 @@ __global__ __launch_bounds__(256) void k_dec_verdict(DecWs ws)
 	const int img = blockIdx.x * 256 + threadIdx.x;
 	if (img >= ws.n) return;
 	const int v = walk_verdict(ws, img);
+	*l1_far_flag(ws, img) = 0;
 	DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (v && !m->status) m->status = v;
 }
@@ -1613,15 +1616,20 @@ template <int UPTO> __global__ __launch_bounds__(256) void k_dec_luma_l2q(DecWs 
 	}
 	lds_barrier();
 	int16_t *l1 = plane_l1(ws, img);
+	typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+	u16x2 reach = (u16x2)(0);                                        /* max of (cell + 5999) as unsigned 16 bits: above 15999 <=> the cell lies outside -5999 .. 10000 */
 	for (int i = 0; i < 16; i++) {                                   /* column j of the tile is row 64 p + j of the level-1 LL (plane_l1: plane A is what the other quarters read) */
 		const int j = wv * 16 + i;
 		uint32_t *dst = reinterpret_cast<uint32_t *>(l1 + (size_t)(64 * p + j) * DW);
 #pragma unroll
 		for (int u = 0; u < 2; u++) {
 			const int k = lane + 64 * u;
-			dst[k] = (uint32_t)(uint16_t)T[(2 * k) * LQ_LS + j] | ((uint32_t)(uint16_t)T[(2 * k + 1) * LQ_LS + j] << 16);
+			const uint32_t w = (uint32_t)(uint16_t)T[(2 * k) * LQ_LS + j] | ((uint32_t)(uint16_t)T[(2 * k + 1) * LQ_LS + j] << 16);
+			dst[k] = w;
+			if constexpr (UPTO == 3) reach = __builtin_elementwise_max(reach, __builtin_bit_cast(u16x2, w) + (u16x2)(5999));
 		}
 	}
+	if constexpr (UPTO == 3) if (reach.x > 15999 || reach.y > 15999) atomicOr(l1_far_flag(ws, img), 1);   /* (k_dec_marks_far) */
 }
 
 /* ---------------------------------------------------------------------------------------------- a chroma plane up to its level-1 synthesis
@@ -1759,13 +1767,18 @@ DEV void pair_decide(int r0, int r1, int &m0, int &m1)
 	m0 = (r0 > 41 && r0 < 108 && r1 < 16) || (r0 < -41 && r0 > -108 && r1 > -16);
 	m1 = !m0 && ((r1 > 41 && r1 < 108 && r0 < 16) || (r1 < -41 && r1 > -108 && r0 > -16));
 }
-__global__ __launch_bounds__(256) void k_dec_marks(DecWs ws)
+/* A level-1 LL cell outside -5999 .. 10000 -- only a residual list that names one cell hundreds of times gets there, no encoder does -- meets the
+ * reference's test of the VALUE in its mark list (:838-848): a mark is 16000 added into a short, and the list takes every cell that then stands above
+ * 10000.  k_dec_luma_l2q flags such a file (a word of D_SPARE, cleared by k_dec_verdict); k_dec_marks, the walk with FAR false, leaves it to
+ * k_dec_marks_far, the same walk with that test, the 16-bit wrap of a mark's 16000 and the write-back of what they change.  Inside -5999 .. 10000 a
+ * marked cell stands at 10001 .. 26000, so the list is the Laplacian's verdict and no cell changes: FAR false is the kernel as it was. */
+template <bool FAR> DEV void marks_walk(const DecWs &ws)
 {
 	const int img = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
 	if (img >= ws.n) return;
 	DecMeta *m = ws.buf<DecMeta>(D_META, img);
-	if (m->status) return;
-	const int16_t *c = plane_l1(ws, img);
+	if (m->status || l1_far(ws, img) != FAR) return;
+	int16_t *c = plane_l1(ws, img);
 	uint16_t *marks = ws.buf<uint16_t>(D_MARKS, img);
 	uint16_t *rowstart = mark_rows(ws, img);                        /* [257]: index of the first mark of row i (the list is in row order) */
 	int total = 0;
@@ -1780,6 +1793,8 @@ __global__ __launch_bounds__(256) void k_dec_marks(DecWs ws)
 #pragma unroll
 		for (int e = 0; e < 3; e++) { v[2 * e] = (int16_t)(r.w[e] & 0xFFFFu); v[2 * e + 1] = (int16_t)(r.w[e] >> 16); }
 	};
+	/* what a mark adds to its cell as the later Laplacians see it: 16000 stored into a short, so a cell from 16768 on wraps */
+	auto raised = [](int v) { return v >= 32768 - 16000 ? 16000 - 65536 : 16000; };
 #define MK_AHEAD 4
 	int up[6], mid[6], dn[6];
 	{ const Row8 r0 = ld(0), r1 = ld(1); cells(r0, up); cells(r1, mid); }
@@ -1796,20 +1811,40 @@ __global__ __launch_bounds__(256) void k_dec_marks(DecWs ws)
 		for (int x = 0; x < 6; x++) cs[x] = up[x] + mid[x] + dn[x];
 #pragma unroll
 		for (int k = 0; k < 4; k++) base[k] = (lane < 63 || k < 2) ? 9 * mid[k + 1] - (cs[k] + cs[k + 1] + cs[k + 2]) : 0;
+		int rup[6], cur[5];                                          /* FAR: the row above and this row's cells 4l .. 4l+4, kept past the roll */
+		if constexpr (FAR) {
+#pragma unroll
+			for (int x = 0; x < 6; x++) rup[x] = up[x];
+#pragma unroll
+			for (int x = 0; x < 5; x++) cur[x] = mid[x];
+		}
 #pragma unroll
 		for (int x = 0; x < 6; x++) { up[x] = mid[x]; mid[x] = dn[x]; }
 		/* marks above cells 4l .. 4l+5 as bits 0..5 */
 		const unsigned fromL = (unsigned)from_left((int)above, 0), fromR = (unsigned)__builtin_amdgcn_update_dpp(0, (int)above, 0x130 /* wave_shl:1 */, 0xF, 0xF, false);
 		const unsigned ab = (lane ? (fromL >> 3) & 1u : 0u) | (above << 1) | (lane < 63 ? (fromR & 1u) << 5 : 0u);
-		int cont[4];
+		int cont[4];                                                 /* what the marks above add to the three cells over a cell: their number, FAR: their sum */
+		if constexpr (!FAR) {
 #pragma unroll
-		for (int k = 0; k < 4; k++) cont[k] = (int)((ab >> k) & 1u) + (int)((ab >> (k + 1)) & 1u) + (int)((ab >> (k + 2)) & 1u);
+			for (int k = 0; k < 4; k++) cont[k] = (int)((ab >> k) & 1u) + (int)((ab >> (k + 1)) & 1u) + (int)((ab >> (k + 2)) & 1u);
+		} else {
+			int dl[6];
+#pragma unroll
+			for (int x = 0; x < 6; x++) dl[x] = ((ab >> x) & 1u) ? raised(rup[x]) : 0;
+#pragma unroll
+			for (int k = 0; k < 4; k++) cont[k] = dl[k] + dl[k + 1] + dl[k + 2];
+		}
 		int res[2][4];                                               /* [left cell marked][m0A, m1A, m0B, m1B] */
 #pragma unroll
 		for (int ml = 0; ml < 2; ml++) {
 			int a0, a1, b0, b1;
-			pair_decide(base[0] - 16000 * (cont[0] + ml), base[1] - 16000 * cont[1], a0, a1);
-			pair_decide(base[2] - 16000 * (cont[2] + a1), base[3] - 16000 * cont[3], b0, b1);
+			if constexpr (!FAR) {
+				pair_decide(base[0] - 16000 * (cont[0] + ml), base[1] - 16000 * cont[1], a0, a1);
+				pair_decide(base[2] - 16000 * (cont[2] + a1), base[3] - 16000 * cont[3], b0, b1);
+			} else {
+				pair_decide(base[0] - (cont[0] + ml * raised(cur[0])), base[1] - cont[1], a0, a1);
+				pair_decide(base[2] - (cont[2] + a1 * raised(cur[2])), base[3] - cont[3], b0, b1);
+			}
 			if (lane == 63) { b0 = 0; b1 = 0; }                       /* pair 127 (cells 255, 256) does not exist */
 			res[ml][0] = a0; res[ml][1] = a1; res[ml][2] = b0; res[ml][3] = b1;
 		}
@@ -1820,20 +1855,43 @@ __global__ __launch_bounds__(256) void k_dec_marks(DecWs ws)
 		const unsigned mine0 = (unsigned)res[0][0] | ((unsigned)res[0][1] << 1) | ((unsigned)res[0][2] << 2) | ((unsigned)res[0][3] << 3);
 		const unsigned mine1 = (unsigned)res[1][0] | ((unsigned)res[1][1] << 1) | ((unsigned)res[1][2] << 2) | ((unsigned)res[1][3] << 3);
 		const unsigned mine = ml ? mine1 : mine0;                       /* (indexing res[] with ml put the array in scratch memory) */
-		/* ordered output */
-		const int cnt = __popc(mine);
-		int pre = cnt;
-		pre = wscan_add(pre);
-		int at = total + pre - cnt;
+		if constexpr (!FAR) {
+			/* ordered output */
+			const int cnt = __popc(mine);
+			int pre = cnt;
+			pre = wscan_add(pre);
+			int at = total + pre - cnt;
 #pragma unroll
-		for (int k = 0; k < 4; k++) if ((mine >> k) & 1u) marks[at++] = (uint16_t)(i * DH + 4 * lane + 1 + k);
-		total += last_lane(pre);
+			for (int k = 0; k < 4; k++) if ((mine >> k) & 1u) marks[at++] = (uint16_t)(i * DH + 4 * lane + 1 + k);
+			total += last_lane(pre);
+		} else {
+			/* The list is a test of the value: every cell of the row that stands above 10000 once the marked ones are 16000 higher goes onto it and
+			 * comes down by 16000 -- a cell a residual list drove above 10000 as well (columns 0 and 255 included), while a marked cell from 16768 on
+			 * (the sum wrapped) or at or below -6000 stays off it and keeps what the mark made of it.  Bit 0: column 0 (lane 0), bits 1 .. 4: my cells. */
+			unsigned listed = 0;
+#pragma unroll
+			for (int x = 0; x < 5; x++) {
+				const bool valid = x ? (lane < 63 || x < 4) : lane == 0, lap = x && ((mine >> (x - 1)) & 1u);
+				const int v = cur[x], t = lap ? (int)(int16_t)(v + 16000) : v, nv = t > 10000 ? t - 16000 : t;
+				if (valid && t > 10000) listed |= 1u << x;
+				if (valid && nv != v) c[(size_t)i * DW + 4 * lane + x] = (int16_t)nv;      /* (every lane has had this row in registers for MK_AHEAD rows) */
+			}
+			const int cnt = __popc(listed);
+			int pre = cnt;
+			pre = wscan_add(pre);
+			int at = total + pre - cnt;
+#pragma unroll
+			for (int x = 0; x < 5; x++) if ((listed >> x) & 1u) marks[at++] = (uint16_t)(i * DH + 4 * lane + x);
+			total += last_lane(pre);
+		}
 		above = mine;
 		if (!lane) rowstart[i + 1] = (uint16_t)total;
 	}
 	if (!lane) { m->nmarks = total; rowstart[DH] = (uint16_t)total; }
 #undef MK_AHEAD
 }
+__global__ __launch_bounds__(256) void k_dec_marks(DecWs ws) { marks_walk<false>(ws); }
+__global__ __launch_bounds__(256) void k_dec_marks_far(DecWs ws) { marks_walk<true>(ws); }
 
 /* ---------------------------------------------------------------------------------------------- chroma
  */
@@ -2047,7 +2105,8 @@ struct StoreBytes { static constexpr bool bytes = true; };
  * line; the four bands that share a 64-byte sector run next to each other on one XCD (same workgroup order as the encoder's front
  * kernel), so the sector is fetched from HBM once.  Only T (18 KB), the band's luma bytes and nine rows of either chroma plane live in LDS.
  * The smoothing reads the rows above and below a mark; marks sit in even rows only (k_dec_marks), and the rows next to them are never
- * marked, so a band needs one extra row (r0 - 1) and sees it as the corrections left it.  The list is in row order and k_dec_marks
+ * marked, so a band needs one extra row (r0 - 1) -- and for a mark in column 0, whose left neighbours are the last line's cells a row up, row r0 - 2 --
+ * and sees them as the corrections left them.  The list is in row order and k_dec_marks
  * leaves the index of every row's first mark, so a band knows its share. */
 #define FR 16                        /* output rows per workgroup */
 #define FBP (FR + 2)                 /* LDS pitch (shorts) of a line of T: local index l <-> row r0 - 2 + l (l = 0 unused); 9 dwords: no bank conflicts across lines */
@@ -2143,7 +2202,7 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 		const uint8_t *f = ws.blob + ws.blob_off[img];
 		const uint32_t *p6 = ws.buf<uint32_t>(D_P6, img);
 		const int cnt = (m->res6_bits - 1) * 8;
-#define F_ADD(at, delta) do { const int rr_ = (int)((at) & (DW - 1)) - (r0 - 2); if (rr_ >= 1 && rr_ <= FR + 1) add_i16_at(T, (int)((at) >> 9) * FBP + rr_, (delta)); } while (0)
+#define F_ADD(at, delta) do { const int rr_ = (int)((at) & (DW - 1)) - (r0 - 2); if (rr_ >= 0 && rr_ <= FR + 1) add_i16_at(T, (int)((at) >> 9) * FBP + rr_, (delta)); } while (0)
 		for (int k = tid; k < cnt; k += 256) if (p6[k] < 4u * DQ) F_ADD(p6[k], bit_of(f + m->o_res6_word, m->res6_bits, k) ? -32 : 32);
 		const uint8_t *cr = f + m->o_char;
 		for (int k = tid; k < m->char_res1_len; k += 256) {
@@ -2170,10 +2229,19 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 		const uint16_t *rows = mark_rows(ws, img);
 		const int k_lo = rows[r0 / 2], k_hi = rows[r0 / 2 + FR / 2];
 		for (int k = k_lo + tid; k < k_hi; k += 256) {
-			if (k > 0 && marks[k - 1] + 1 == marks[k]) continue;
-			for (int t = k; t < nmarks && (t == k || marks[t - 1] + 1 == marks[t]); t++) {
+			/* a run: marks next to each other in one row (a mark in column 0 -- only a value above 10000 puts one there -- starts a run of its own) */
+			if (k > 0 && marks[k - 1] + 1 == marks[k] && (marks[k] & 255)) continue;
+			for (int t = k; t < nmarks && (t == k || (marks[t - 1] + 1 == marks[t] && (marks[t] & 255))); t++) {
 				const int l = ((marks[t] >> 8) << 1) - (r0 - 2), col = marks[t] & 255;   /* cell (row, col) of the transposed plane = T[col][row] */
 #define TP(dr, dc) ((int)T[(col + (dc)) * FBP + l + (dr)])
+				if (col == 0) {                                        /* left of column 0 the reference's plane has the last cell of the row above: T[511][row - 1] */
+#define TL(dr) ((int)T[(2 * DH - 1) * FBP + l + (dr) - 1])
+					const int ctr = TP(0, 0);
+					const int lap = (ctr << 3) - TL(0) - TP(0, 1) - TP(-1, 0) - TP(1, 0) - TL(-1) - TL(1) - TP(-1, 1) - TP(1, 1);
+					if (iabs(lap) < 116) T[l] = (int16_t)(((ctr << 2) + TL(0) + TP(0, 1) + TP(-1, 0) + TP(1, 0) + 4) >> 3);
+#undef TL
+					continue;
+				}
 				const int ctr = TP(0, 0);
 				const int lap = (ctr << 3) - TP(0, -1) - TP(0, 1) - TP(-1, 0) - TP(1, 0) - TP(-1, -1) - TP(1, -1) - TP(-1, 1) - TP(1, 1);
 				if (iabs(lap) < 116) T[col * FBP + l] = (int16_t)(((ctr << 2) + TP(0, -1) + TP(0, 1) + TP(-1, 0) + TP(1, 0) + 4) >> 3);
@@ -2531,6 +2599,7 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 		HIPCHK(hipEventRecord(d->join_ev, d->chroma_stream));
 	}
 	k_dec_marks<<<(n + 3) / 4, 256, 0, s>>>(ws);
+	k_dec_marks_far<<<(n + 3) / 4, 256, 0, s>>>(ws);                              /* (ends at once for every file but one whose level-1 LL leaves -5999 .. 10000) */
 	STAGE_END();                                                                  /* 7 */
 	if (fork || fork_late) HIPCHK(hipStreamWaitEvent(s, d->join_ev, 0));
 	else {

@@ -1,7 +1,8 @@
 """The decoder stage by stage against the oracle's checkpoints (pytest -m gpu).
 
 nhw_dec_debug_stop_after ends a batch behind one stage, nhw_dec_debug_read copies a workspace buffer out, and the oracle's decode_probe
-gives the same buffer at the same point of decode_image: STAGES below is the table stop -> buffer -> probe id, every row bit for bit.
+gives the same buffer at the same point of decode_image: STAGES (tests/dec_stages.py, shared with tests/test_decode_values.py) is the table
+stop -> buffer -> probe id, every row bit for bit.
 Stops 4, 5 and 6 are the three instantiations of k_dec_luma_l2q (the block as the shrink leaves it, after the synthesis, production);
 they and the whole decode run again under both forced slice orders (nhw_dec_debug_slice_order), the quarters of a file one per launch,
 ascending and descending, where a quarter that wrote what another one reads would show.
@@ -18,49 +19,9 @@ take a path: it caps what the test can miss, it is no tolerance, and it fails th
 import numpy as np
 import pytest
 
+from tests.dec_stages import PROBES, STAGES, run_to as _run
+
 FILES = [(q, seed) for q, seeds in ((10, (0, 1)), (13, (0, 1)), (16, (0, 1)), (17, (0, 1)), (20, (67, 222, 277)), (23, (0, 1))) for seed in seeds]
-D = dict(MARKS=7, A=8, CA=10, CU=12)                                  # nhw_dec_debug_read's buffer indices
-PROBES = (3, 4, 5, 50, 51, 6, 7, 30, 31, 40, 41, 42, 43, 44, 45, 46, 47)
-
-
-def _rd(dec, what, img, nbytes, dtype):
-    buf = np.empty(nbytes, np.uint8)
-    assert dec.lib.nhw_dec_debug_read(dec.h, D[what], img, buf.ctypes.data, nbytes) == 0
-    return buf.view(dtype)
-
-
-def _luma(dec, img):
-    return _rd(dec, "A", img, 8 * 65536 + 8192, np.int16)[2048:2048 + 262144].reshape(512, 512)
-
-
-def _chroma(dec, img, comp):
-    o = 1024 + comp * (65536 + 2048)
-    return _rd(dec, "CA", img, 2 * (2 * 65536 + 4096), np.int16)[o:o + 65536].reshape(256, 256)
-
-
-def _sharp(dec, img, comp):
-    return _rd(dec, "CU", img, 131072, np.uint8)[65536 * comp:65536 * (comp + 1)].reshape(256, 256)
-
-
-# stop -> [(what, GPU side (dec, file index, probe), oracle side (probe))]; probe(id) is the oracle's buffer as int16
-STAGES = {
-    # (the luma plane does not exist before the expansion: the walk leaves a list of values that k_dec_expand turns into rows)
-    3: [("A after the expansion", lambda d, i, pr: _luma(d, i), lambda pr: pr(3).reshape(512, 512)),
-        ("U after the expansion", lambda d, i, pr: _chroma(d, i, 0), lambda pr: pr(30).reshape(256, 256)),
-        ("V after the expansion", lambda d, i, pr: _chroma(d, i, 1), lambda pr: pr(31).reshape(256, 256))],
-    4: [("A after the shrink", lambda d, i, pr: _luma(d, i), lambda pr: pr(4).reshape(512, 512))],
-    5: [("level-1 LL after the synthesis", lambda d, i, pr: _luma(d, i)[:256, :256], lambda pr: pr(5).reshape(512, 512)[:256, :256])],
-    6: [("level-1 LL after the residuals", lambda d, i, pr: _luma(d, i)[:256, :256], lambda pr: pr(6).reshape(512, 512)[:256, :256])],
-    7: [("marks", lambda d, i, pr: _rd(d, "MARKS", i, 2 * 65536, np.uint16)[:len(pr(7))], lambda pr: pr(7).view(np.uint16))],
-    8: [("U after level 2", lambda d, i, pr: _chroma(d, i, 0)[:128, :128], lambda pr: pr(40).reshape(256, 256)[:128, :128]),
-        ("V after level 2", lambda d, i, pr: _chroma(d, i, 1)[:128, :128], lambda pr: pr(41).reshape(256, 256)[:128, :128])],
-    9: [("U after the corrections", lambda d, i, pr: _chroma(d, i, 0)[:128, :128], lambda pr: pr(42).reshape(256, 256)[:128, :128]),
-        ("V after the corrections", lambda d, i, pr: _chroma(d, i, 1)[:128, :128], lambda pr: pr(43).reshape(256, 256)[:128, :128])],
-    10: [("U before the sharpening", lambda d, i, pr: _chroma(d, i, 0), lambda pr: pr(44).reshape(256, 256)),
-         ("V before the sharpening", lambda d, i, pr: _chroma(d, i, 1), lambda pr: pr(45).reshape(256, 256))],
-    11: [("U sharpened", lambda d, i, pr: _sharp(d, i, 0), lambda pr: pr(46).reshape(256, 256).astype(np.uint8)),
-         ("V sharpened", lambda d, i, pr: _sharp(d, i, 1), lambda pr: pr(47).reshape(256, 256).astype(np.uint8))],
-}
 
 
 def reach(files, probes):
@@ -124,16 +85,6 @@ def dec():
     d = nhwcodec_amd.Decoder(0, max_batch=len(FILES))
     yield d
     d.close()
-
-
-def _run(dec, files, stop, mode):
-    assert dec.lib.nhw_dec_debug_slice_order(dec.h, mode) == 0
-    dec.lib.nhw_dec_debug_stop_after(dec.h, stop)
-    try:
-        return dec.decode(files)
-    finally:
-        dec.lib.nhw_dec_debug_stop_after(dec.h, 0)
-        assert dec.lib.nhw_dec_debug_slice_order(dec.h, 0) == 0
 
 
 def test_files_reach_every_rule(batch):

@@ -1,0 +1,510 @@
+"""The decoder on well-formed files whose coefficient VALUES sit at the edges of what a file can carry: every detail cell
+at +-275, signs that maximise both filter taps, LL2 samples and exception samples at their extremes, pictures far outside 0 .. 255 on either
+side, corrections repeated on one cell, lone groups of the detail bands, and the smallest contents that make each stage's 16-bit arithmetic
+wrap.  tests/nhw_values.py builds the fixed list of cases; the oracle, built with AddressSanitizer and UBSan, says for each whether it is
+defined (and what its pixels are), refused, or undefined (no expectation: left out of the GPU lists).
+
+CPU (-m "not gpu"): the builder writes the planes asked for, the classification and its two conditions, tests/golden/dec/values.json reproduced,
+the reference decoder (where oracle/_ref holds it) against the oracle, and reach(): the list reaches the bounds, both sides of every clip,
+every lone-group pattern and a wrap in every stage section 7.1b says can wrap.
+GPU (-m gpu): every defined case bit for bit -- the whole decode, every stage against the oracle's probe, under both forced slice orders, at
+half and quarter scale, as float tensors, on a handle that has just decoded dense files and the other way round, and as tiles of a container.
+"""
+import os
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import nhw_surgery as S
+from tests import nhw_values as V
+from tests.dec_stages import PROBES, STAGES, run_to
+
+NHW_E_FORMAT = -6
+CANARY = 0xA5
+REACH_PROBES = tuple(sorted(set(PROBES) | {8, 9}))
+sha = V.sha
+
+
+@pytest.fixture(scope="module")
+def record():
+    return V.load_record()
+
+
+@pytest.fixture(scope="module")
+def cases(oracle):
+    return V.cases(oracle)
+
+
+@pytest.fixture(scope="module")
+def probed(oracle, cases, record):
+    """the defined cases with what the oracle says of each, computed once and read only:
+    [(name, family, quality, bytes, {probe id: int16 array}, planes uint8 [3, 512, 512], pixels uint8 [512, 512, 3])]"""
+    out = []
+    for name, fam, q, data in cases:
+        if record[name]["class"] != "defined":
+            continue
+        pr = {i: np.frombuffer(oracle.decode_probe(data, i), np.int16) for i in REACH_PROBES}
+        planes = oracle.decode(data, planes=True)[0]
+        px = oracle.decode(data)[0]
+        for a in list(pr.values()) + [planes, px]:
+            a.setflags(write=False)
+        out.append((name, fam, q, data, pr, planes, px))
+    return out
+
+
+# ---------------------------------------------------------------- the filters in numpy, with and without the 16-bit wrap
+def _w16(a):
+    return ((a + 32768) & 65535) - 32768
+
+
+def synth_rows(x, normalise, wrap):
+    """oracle synth_rows on int64 [rows, n], a row = [low half | high half]; wrap: every store goes through int16, as in the oracle (and the
+    reference); without it the same steps in exact integers"""
+    w = _w16 if wrap else (lambda a: a)
+    m = x.shape[1] // 2
+    lo, hi = x[:, :m], x[:, m:]
+    nxt = np.concatenate([lo[:, 1:], lo[:, -1:]], 1)
+    hm = np.concatenate([hi[:, :1], hi[:, :-1]], 1)                 # at either end the missing neighbour is the sample itself
+    hp = np.concatenate([hi[:, 1:], hi[:, -1:]], 1)
+    ev = w(w(lo << 3) - ((hi + hm) << 1))
+    od = w(w((nxt + lo) << 2) + 6 * hi - hp - hm)
+    if normalise:
+        ev = np.where(ev > 0, w(ev + 32), ev) >> 6
+        od = np.where(od > 0, w(od + 32), od) >> 6
+    out = np.empty_like(x)
+    out[:, 0::2], out[:, 1::2] = ev, od
+    return out
+
+
+def level(x, wrap):
+    """a whole level on a square block: along the rows, transposed, along the rows normalised"""
+    return synth_rows(np.ascontiguousarray(synth_rows(x, False, wrap).T), True, wrap)
+
+
+def stage_models(q, pr, planes):
+    """every filter stage of a file, from the oracle's probe in front of it: {stage: (the oracle's result, the model with the 16-bit wrap, the
+    model in exact integers)}; for the second direction of the luma the three are compared behind the clip to a byte, which is all that leaves it"""
+    g = lambda i, n: pr[i].astype(np.int64).reshape(n, n)
+    out = {}
+    a4 = g(4, 512)
+    out["luma level 2"] = (g(5, 512)[:256, :256],) + tuple(level(a4[:256, :256], w) for w in (True, False))
+    # between probe 6 and the first direction the mark list works on the level-1 LL (nhwo_dec.c:620-633): a listed cell above 10000 comes down by
+    # 16000, an unlisted one of rows 1 .. 254 from 16768 on was marked and keeps its wrapped sum; a cell at or below -6000 may have been marked and kept
+    # its 16000 -- the one thing probe 7 does not tell, so where the result shows 8 x (cell + 16000) the model takes it
+    ll = g(6, 512)[:256, :256].copy()
+    listed = np.zeros(65536, bool); listed[pr[7].view(np.uint16)] = True
+    listed = listed.reshape(256, 256)
+    inner = np.zeros((256, 256), bool); inner[1:255] = True
+    ll[listed & (ll > 10000)] -= 16000
+    ll[inner & ~listed & (ll >= 16768)] -= 65536 - 16000
+    low = inner & (ll <= -6000) & (g(8, 512)[:256, 0:512:2].T == _w16(8 * (ll + 16000))) & ~a4[:256, 256:].any()
+    ll[low] += 16000
+    first = a4.copy(); first[:256, :256] = ll.T
+    out["luma level 1, first direction"] = (g(8, 512),) + tuple(synth_rows(first, False, w) for w in (True, False))
+    clip = lambda a: np.clip(a, 0, 255)
+    out["luma level 1, second direction"] = (planes[0].astype(np.int64),) + tuple(clip(synth_rows(g(9, 512), True, w)) for w in (True, False))
+    for c, tag in enumerate("UV"):
+        a = g(30 + c, 256)
+        out[f"{tag} level 2"] = (g(40 + c, 256)[:128, :128],) + tuple(level(a[:128, :128], w) for w in (True, False))
+        b = a.copy()
+        b[(b >= 5003) & (b <= 5006)] = 0                            # (the correction symbols of the level-1 bands are taken out as they are applied)
+        b[:128, :128] = g(42 + c, 256)[:128, :128].T
+        out[f"{tag} level 1"] = (g(44 + c, 256),) + tuple(level(b, w) for w in (True, False))
+    return out
+
+
+WRAPS = ("luma level 2", "luma level 1, first direction", "luma level 1, second direction", "U level 2", "V level 2", "U level 1", "V level 1")
+
+
+def group_rows(p3):
+    """the non-zero groups of eight cells of the detail bands, row by row, from probe 3: {row: (groups, set of (group, cell))}.  Rows below 256: groups
+    32 .. 63 (the level-1 LL quadrant is always in memory); from 256 on: all 64"""
+    a = p3.reshape(512, 512)
+    out = {}
+    for k in range(512):
+        g0 = 32 if k < 256 else 0
+        nz = np.flatnonzero(a[k, 8 * g0:]) + 8 * g0
+        if len(nz):
+            out[k] = (sorted({int(c) >> 3 for c in nz}), {(int(c) >> 3, int(c) & 7) for c in nz})
+    return out
+
+
+def reach(items):
+    """What the list must exercise, from the oracle's probes alone -> the conditions it misses (empty: none).  items: `probed`."""
+    missed = []
+    hi3 = {k: -10 ** 9 for k in ("ll2", "l2", "l1", "cll2", "cdet")}
+    lo3 = {k: 10 ** 9 for k in hi3}
+    sides = {p: [False, False] for p in (5, 6, 42, 43, 44, 45)}
+    pats, wrapped, model_bad, at_plus32 = set(), set(), [], False
+    mk = set()                                                      # what the value test of the mark list (nhwo_dec.c:630) has met
+    corr = set()                                                    # what the q > 21 corrections have met
+    for name, fam, q, data, pr, planes, px in items:
+        a = pr[3].astype(np.int64).reshape(512, 512)
+        l2 = a[:256, :256].copy(); l2[:128, :128] = 0
+        l1 = a.copy(); l1[:256, :256] = 0
+        parts = {"ll2": a[:128, :128], "l2": l2, "l1": l1}
+        for c in (30, 31):
+            b = pr[c].astype(np.int64).reshape(256, 256)
+            parts[("cll2", c)] = b[:64, :64]
+            d = b.copy(); d[:64, :64] = 0
+            parts[("cdet", c)] = d
+        for k, v in parts.items():
+            k = k[0] if isinstance(k, tuple) else k
+            hi3[k], lo3[k] = max(hi3[k], int(v.max())), min(lo3[k], int(v.min()))
+        for p in sides:
+            n = 512 if p < 10 else 256
+            b = pr[p].reshape(n, n)[:256, :256] if p < 10 else pr[p].reshape(n, n)[:128, :128] if p < 44 else pr[p].reshape(n, n)
+            sides[p][0] |= bool((b < 0).any()); sides[p][1] |= bool((b > 255).any())
+        for k, (groups, cells) in group_rows(pr[3]).items():
+            half = int(k >= 256)
+            ends = all((g, 0) in cells and (g, 7) in cells for g in groups)
+            if not ends:
+                continue
+            if len(groups) == 1:
+                g = groups[0]
+                pats.add((half, "g0" if g == 0 else "g63" if g == 63 else "g31" if g == 31 else "g32" if g == 32 else "interior"))
+            elif len(groups) == 2 and groups[1] == groups[0] + 1:
+                pats.add((half, "pair"))
+        pre = synth_rows(pr[9].astype(np.int64).reshape(512, 512), False, True)        # the second direction in front of its + 32
+        at_plus32 |= bool((pre > 32767 - 32).any())
+        p6, listed = pr[6].astype(np.int64).reshape(512, 512)[:256, :256], np.zeros(65536, bool)
+        listed[pr[7].view(np.uint16)] = True
+        listed = listed.reshape(256, 256)
+        t8 = pr[8].astype(np.int64).reshape(512, 512)
+        if not pr[4].reshape(512, 512)[:256, 256:].any():           # no detail beside the level-1 LL: line c of the first direction shows 8 x the cell (r, c) at 2 r
+            kept = t8[:256, 0:512:2].T                              # [r, c]
+            high, low = (p6 >= 16768) & ~listed, (p6 < -6000)
+            high[[0, 255]] = False
+            if (high & (kept == _w16(8 * (p6 + 16000 - 65536)))).any(): mk.add("a marked cell from 16768 on keeps its wrapped sum and stays off the list")
+            if (low & (kept == _w16(8 * (p6 + 16000)))).any(): mk.add("a marked cell below -6000 keeps its 16000 and stays off the list")
+            # the edges of the test, each in a file where no other cell could have sent it the long way
+            inner6 = p6[1:255]
+            edge = (inner6 == -6000) & ~listed[1:255] & (kept[1:255] == _w16(8 * 10000))
+            if edge.any() and p6.min() == -6000 and p6.max() <= 10000: mk.add("a marked cell at exactly -6000, the lowest of its file, keeps 10000 and stays off the list")
+            if ((inner6 == 10000) & ~listed[1:255] & (kept[1:255] == _w16(8 * 10000))).any(): mk.add("an unmarked cell at exactly 10000 stays as it is")
+            if ((inner6 == 10001) & listed[1:255]).any() and p6.max() == 10001 and p6.min() > -6000: mk.add("a cell at 10001, the only one of its file outside -5999 .. 10000, is on the list")
+        for r, c in np.argwhere(p6 > 10000):
+            where = "row 0" if r == 0 else "row 255" if r == 255 else "column 0" if c == 0 else "inside"
+            if r in (0, 255):
+                if not listed[r, c]: mk.add(f"a cell above 10000 in {where} is left alone")
+            elif listed[r, c]:
+                mk.add(f"a cell above 10000 {'in ' if c == 0 else ''}{where} is on the list")
+                if c < 253 and p6[r, c + 1] > 10000 and listed[r, c + 1]: mk.add("two such cells side by side")
+        h = S.read(data).h
+        corrected = any(h.get(k, 0) for k in ("res6_bits", "char_res1_len", "qs3_len"))       # probe 8 lies behind the q > 21 corrections
+        models = stage_models(q, pr, planes)
+        if corrected and not h.get("res6_bits", 0) and fam != "encoded":
+            # the corrections of a built file, from its own qs3 and char_res1 words, summed in exact integers onto the first direction's result
+            f = S.read(data)
+            add = np.zeros(512 * 512, np.int64)
+            for w in np.frombuffer(f.s.get("qs3", b""), "<u4").astype(np.int64):
+                add[w >> 1] += -56 if w & 1 else 56
+            for v in np.frombuffer(f.s["char"], "<u2").astype(np.int64):
+                add[((v - (v & 3)) << 1) + (254 if (v & 3) < 2 else 255)] += -32 if v & 1 else 32
+            add = add.reshape(512, 512)
+            exact = models["luma level 1, first direction"][1] + add
+            if np.array_equal(_w16(exact), t8):
+                if not np.array_equal(exact, t8): corr.add("a cell wraps")
+                cols = set(np.argwhere(add)[:, 1].tolist())
+                for c, what in ((0, "column 0"), (511, "column 511")):
+                    if c in cols: corr.add(what)
+                if any(c % 16 == 15 for c in cols): corr.add("the last row of a band, the row above the next")
+                if any(c % 16 == 0 for c in cols): corr.add("the first row of a band")
+            else:
+                model_bad.append(f"{name}: the corrections summed from the file's words are not the oracle's")
+        for st, (want, m16, m32) in models.items():
+            if corrected and st == "luma level 1, first direction":
+                continue
+            if not np.array_equal(want, m16):
+                model_bad.append(f"{name}: the 16-bit model of '{st}' is not the oracle's")
+            if not np.array_equal(want, m32):
+                wrapped.add(st)
+    want_hi = dict(ll2=V.EX_MAX, l2=V.EX_MAX, l1=V.LUMA_TAG_MAX, cll2=V.EX_MAX, cdet=V.CHROMA_TAG_MAX)
+    want_lo = dict(ll2=V.EX_MIN, l2=V.LEVEL_MIN, l1=V.LEVEL_MIN, cll2=V.EX_MIN, cdet=V.LEVEL_MIN)
+    for k in hi3:
+        if (hi3[k], lo3[k]) != (want_hi[k], want_lo[k]):
+            missed.append(f"probe 3 / 30 / 31, {k}: {lo3[k]} .. {hi3[k]}, the bounds are {want_lo[k]} .. {want_hi[k]}")
+    for p, (neg, big) in sides.items():
+        if not neg: missed.append(f"probe {p}: no cell below 0")
+        if not big: missed.append(f"probe {p}: no cell above 255")
+    for pat in [(1, "g0"), (1, "g63"), (0, "g63"), (1, "interior"), (0, "interior"), (1, "pair"), (0, "pair"), (1, "g31"), (1, "g32"), (0, "g32")]:
+        if pat not in pats:
+            missed.append(f"no row of half {pat[0]} whose only groups are '{pat[1]}' with cells 0 and 7 set")
+    for st in WRAPS:
+        if st not in wrapped:
+            missed.append(f"no file makes '{st}' wrap: the exact evaluation equals the oracle's everywhere")
+    for what in ("a marked cell from 16768 on keeps its wrapped sum and stays off the list", "a marked cell below -6000 keeps its 16000 and stays off the list",
+                 "a marked cell at exactly -6000, the lowest of its file, keeps 10000 and stays off the list", "an unmarked cell at exactly 10000 stays as it is",
+                 "a cell at 10001, the only one of its file outside -5999 .. 10000, is on the list",
+                 "a cell above 10000 in row 0 is left alone", "a cell above 10000 in row 255 is left alone", "a cell above 10000 in column 0 is on the list",
+                 "a cell above 10000 inside is on the list", "two such cells side by side"):
+        if what not in mk:
+            missed.append(f"the mark list's value test: no file where {what}")
+    for what in ("a cell wraps", "column 0", "column 511", "the last row of a band, the row above the next", "the first row of a band"):
+        if what not in corr:
+            missed.append(f"the q > 21 corrections: no built file reaches '{what}'")
+    if not at_plus32:
+        missed.append("no file brings a sample of the second direction within 32 of 32767: its + 32 never wraps")
+    return missed + model_bad
+
+
+# ---------------------------------------------------------------- CPU
+def test_alphabets_are_the_oracles(oracle):
+    """the builder's value -> word tables against the oracle's own walk: a file of one literal per word decodes to the values the tables say"""
+    for words, lo in ((V.LUMA_WORD, V.LEVEL_MIN), (V.CHROMA_WORD, V.LEVEL_MIN)):
+        assert min(words) == lo
+    vals = sorted(V.LUMA_WORD)
+    plane = np.zeros((512, 512), np.int64)
+    for i, val in enumerate(vals):                                  # (probe 2: the plane as the strips leave it, in front of every pass)
+        plane[300 + 2 * (i // 120), 2 * (i % 120)] = val
+    cv = sorted(V.CHROMA_WORD)
+    u = np.zeros((256, 256), np.int64); u[200, :len(cv)] = cv
+    data = V.build(23, plane, u, u[::-1].copy(), *V._flat(23))
+    got = np.frombuffer(oracle.decode_probe(data, 2), np.int16).reshape(512, 512)
+    assert np.array_equal(got, plane)
+    gu = np.frombuffer(oracle.decode_probe(data, 30), np.int16).reshape(256, 256)
+    assert np.array_equal(gu[200], u[200]) and not gu[64:200].any()
+
+
+def test_builder_writes_the_planes_asked_for(oracle, cases):
+    by = {n: d for n, _, _, d in cases}
+    for q in (10, 20):
+        for name, c in ((f"q{q}_lone_groups", V._lone_groups(q)), (f"q{q}_one_sided", V._one_sided(q))):
+            luma = np.array(c["luma"]); luma[:128, :128] = 0; luma[511, 508] = 0      # (the stream's last cell is never read)
+            got = np.frombuffer(oracle.decode_probe(by[name], 2), np.int16).reshape(512, 512)
+            assert np.array_equal(got, luma), name
+            a3 = np.frombuffer(oracle.decode_probe(by[name], 3), np.int16).reshape(512, 512)
+            ex = {(r, col): v for r, col, v in (c.get("ex") or ((), (), ()))[0]}
+            ll = np.array(c["ll"]).reshape(128, 128).copy()
+            for (r, col), v in ex.items():
+                if r < 128: ll[r, col] = v
+            assert np.array_equal(a3[:128, :128], ll), name
+            for comp, key, lk in ((0, "u", "llu"), (1, "v", "llv")):
+                g = np.frombuffer(oracle.decode_probe(by[name], 30 + comp), np.int16).reshape(256, 256)
+                w = np.array(c[key]); w[:64, :64] = np.array(c[lk]).reshape(64, 64) + (0 if q > 15 else 1)
+                w[255, 248] = 0                                    # (the stream's last cell of either component is never read)
+                for r, col, v in (c.get("ex") or ((), (), ()))[1 + comp]:
+                    w[r, col] = v
+                assert np.array_equal(g, w), (name, key)
+    for q in V.QUALITIES:                                           # LL2 by verbatim tokens: the fine bytes at odd values (q > 15)
+        a3 = np.frombuffer(oracle.decode_probe(by[f"q{q}_ll_alt_verbatim_ex"], 3), np.int16).reshape(512, 512)[:128, :128]
+        assert a3.max() == V.EX_MAX and a3.min() == V.EX_MIN and ((a3 == 255).any() and (a3 == 1).any()) == (q > 15)
+
+
+def test_cases_reproduce_the_record(record, cases):
+    assert {n for n, *_ in cases} == set(record) and len(cases) == len(record) <= 68
+    for name, fam, q, data in cases:
+        r = record[name]
+        assert (r["family"], r["quality"], r["bytes"], r["nhw_sha256"]) == (fam, q, len(data), sha(data)), name
+        assert data[1] == q and len(data) < S.OUT_STRIDE
+    assert not V.conditions(cases, [record[n]["class"] for n, *_ in cases])
+
+
+def test_oracle_classifies_every_case_under_the_sanitizers(record, cases, oracle, tmp_path):
+    exe = S.build_asan()
+    if exe is None:
+        # (as tests/test_decode_surgery.py does.  The two conditions on the classification do not go unchecked then: test_cases_reproduce_the_record
+        # holds the committed record to them and never skips)
+        pytest.skip("this machine's compiler cannot build oracle/_asan/nhwo_dec_asan (-fsanitize=address,undefined)")
+    res = V.classify_all(exe, str(tmp_path), cases)
+    missed = V.conditions(cases, [r[0] for r in res])
+    assert not missed, "\n  ".join(missed)
+    for (name, fam, q, data), (cls, gq, px) in zip(cases, res):
+        r = record[name]
+        assert r["class"] == cls, f"{name}: recorded {r['class']}, now {cls}: {px if cls == 'undefined' else ''}"
+        if cls == "defined":
+            assert (q, r["pixels_sha256"]) == (gq, sha(px)), name
+            got, oq = oracle.decode(data)                          # the plain build agrees with the sanitizer build
+            assert oq == q and sha(got.tobytes()) == r["pixels_sha256"], name
+
+
+_REF_CHILD = r"""
+import sys, ctypes, hashlib, numpy as np
+lib = ctypes.CDLL(sys.argv[1])
+lib.nhwref_decode_planes.argtypes = [ctypes.c_char_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int)]
+for path in sys.argv[2:]:
+    out = np.zeros(3 * 262144, np.uint8); q = ctypes.c_int(0)
+    rc = lib.nhwref_decode_planes(path.encode(), out.ctypes.data, ctypes.byref(q))
+    print(rc, q.value, hashlib.sha256(out.tobytes()).hexdigest(), flush=True)
+"""
+
+
+def test_reference_decoder_agrees_with_the_oracle(probed, tmp_path):
+    """where oracle/_ref holds the reference decoder: its Y, U, V planes of every defined case are the oracle's (a difference is an oracle bug).  The
+    reference runs in a child process: a file it cannot take must not end the test run"""
+    so = os.path.join(S.ROOT, "oracle", "_ref", "libnhwref_dec.so")
+    if not os.path.exists(so):
+        pytest.skip("oracle/_ref/libnhwref_dec.so is not built here")
+    paths = []
+    for name, _, _, data, *_ in probed:
+        paths.append(str(tmp_path / f"{name}.nhw"))
+        with open(paths[-1], "wb") as fp:
+            fp.write(data)
+    p = subprocess.run([sys.executable, "-c", _REF_CHILD, so] + paths, capture_output=True, text=True, timeout=600)
+    lines = p.stdout.split("\n")
+    bad = []
+    for k, (name, _, q, _, _, planes, _) in enumerate(probed):
+        got = lines[k].split() if k < len(lines) else []
+        if got != ["0", str(q), sha(planes.tobytes())]:
+            bad.append((name, got[:2]))
+    assert not bad and p.returncode == 0, f"the reference decodes differently from the oracle: {bad[:10]} {p.stderr[-300:]}"
+
+
+def test_cases_reach_the_bounds_the_clips_the_groups_and_the_wraps(probed):
+    missed = reach(probed)
+    assert not missed, "the case list no longer reaches what it is there for:\n  " + "\n  ".join(missed)
+
+
+# ---------------------------------------------------------------- GPU
+@pytest.fixture(scope="module")
+def dec():
+    import nhwcodec_amd
+    d = nhwcodec_amd.Decoder(0, max_batch=72)
+    yield d
+    d.close()
+
+
+@pytest.fixture(scope="module")
+def batch(oracle, cases, record, probed):
+    """the batch of every GPU test: every defined and every refused case in the list's order, a golden file in front and one in the middle, which
+    must stay exact -> [(name, bytes, class, {probe: array} or None, pixels or None)]"""
+    by = {name: (pr, px) for name, _, _, _, pr, _, px in probed}
+    items = []
+    for k, (name, fam, q, data) in enumerate(cases):
+        if k in (0, len(cases) // 2):
+            g = S.golden(V.NEIGHBOURS[0 if k == 0 else 1])
+            items.append((V.NEIGHBOURS[0 if k == 0 else 1], g, "defined", {i: np.frombuffer(oracle.decode_probe(g, i), np.int16) for i in PROBES}, oracle.decode(g)[0]))
+        cls = record[name]["class"]
+        if cls == "defined":
+            items.append((name, data, cls) + by[name])
+        elif cls == "refused":
+            items.append((name, data, cls, None, None))
+    assert len(items) <= 72 and sum(c == "defined" for _, _, c, _, _ in items) >= 50
+    return items
+
+
+def _whole(dec, batch, what):
+    from tests.test_decode_surgery import _dec_batch
+    px, st, qq = _dec_batch(dec, [d for _, d, *_ in batch])
+    bad = []
+    for i, (name, data, cls, _, want) in enumerate(batch):
+        if cls == "refused":
+            ok = st[i] == NHW_E_FORMAT
+        else:
+            ok = st[i] == 0 and qq[i] == data[1] and np.array_equal(px[i], want)
+        if not ok:
+            bad.append((name, int(st[i]), int((px[i] != want).sum()) if want is not None else None))
+    assert not bad, f"{what}: (file, status, differing bytes) {bad[:12]} of {len(batch)}"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", [0, 1, 2])
+def test_gpu_whole_decode(dec, batch, mode):
+    """bit for bit against the oracle's pixels, NHW_E_FORMAT for a refused file, the golden files exact; 1 and 2: the forced slice orders"""
+    assert dec.lib.nhw_dec_debug_slice_order(dec.h, mode) == 0
+    try:
+        _whole(dec, batch, f"nhw_dec_batch, slice order {mode}")
+    finally:
+        assert dec.lib.nhw_dec_debug_slice_order(dec.h, 0) == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("stop", sorted(STAGES))
+def test_gpu_stage_matches_oracle(dec, batch, stop):
+    """every stop of tests/dec_stages.py against the oracle's probe, for every defined case: a mismatch names its kernel"""
+    live = [it for it in batch if it[2] == "defined"]
+    run_to(dec, [d for _, d, *_ in live], stop, 0)
+    bad = []
+    for i, (name, data, _, probes, _) in enumerate(live):
+        if stop == 7:
+            # the table compares as many marks as the oracle has; the length of the GPU's list is the last word of its row index (D_SPARE, behind 8 shorts)
+            spare = np.empty(1024, np.uint8)
+            assert dec.lib.nhw_dec_debug_read(dec.h, 2, i, spare.ctypes.data, 1024) == 0
+            n_gpu, n_oracle = int(spare.view(np.uint16)[8 + 256]), len(probes[7])
+            if n_gpu != n_oracle:
+                bad.append(f"{name}, marks: the GPU lists {n_gpu}, the oracle {n_oracle}")
+        for tag, gpu, want in STAGES[stop]:
+            pr = probes.__getitem__
+            g, o = gpu(dec, i, pr), want(pr)
+            if g.shape != o.shape:
+                bad.append(f"{name}, {tag}: shape {g.shape}, the oracle's {o.shape}")
+            elif not np.array_equal(g, o):
+                at = np.argwhere(g != o)
+                bad.append(f"{name}, {tag}: {len(at)} cells differ, first {at[0].tolist()} (GPU {g[tuple(at[0])]}, oracle {o[tuple(at[0])]}), "
+                           f"spanning {at.min(0).tolist()} .. {at.max(0).tolist()}")
+    assert not bad, f"stop {stop}:\n  " + "\n  ".join(bad[:40])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scale", [2, 4])
+def test_gpu_scaled_decode(dec, oracle, batch, scale):
+    """half and quarter scale against tests/test_scaled_decode.py's definition, built from the oracle's probes: the clips of k_dec_scaled on planes that
+    leave 0 .. 255 on both sides"""
+    from tests.test_scaled_decode import _decode_scaled, expected
+    live = [it for it in batch if it[2] == "defined"]
+    px, st, qq = _decode_scaled(dec, [d for _, d, *_ in live], scale)
+    bad = [(name, int(st[i]), int((px[i] != expected(oracle, data, scale)).sum())) for i, (name, data, *_) in enumerate(live)
+           if st[i] != 0 or qq[i] != data[1] or not np.array_equal(px[i], expected(oracle, data, scale))]
+    assert not bad, f"scale {scale}: (file, status, differing bytes) {bad[:12]}"
+
+
+TENSOR_FORMATS = [("float16", "CHW", "RGB", "file", "imagenet"), ("bfloat16", "HWC", "BGR", "reversed", "unit"), ("float32", "CHW", "BGR", "file", "negative")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scale", [1, 2, 4])
+@pytest.mark.parametrize("fmt", TENSOR_FORMATS, ids=lambda f: "-".join(f))
+def test_gpu_tensor_formats(dec, oracle, batch, fmt, scale):
+    """decode_tensor_device: the bit patterns of tests/test_tensor_decode.py's CPU form of the oracle's picture"""
+    from tests.test_tensor_decode import _assert_tensor, _decode_tensor, _fmt
+    f = _fmt(*fmt)
+    live = [d for _, d, cls, *_ in batch if cls == "defined"]
+    bits, st, qq = _decode_tensor(dec, live, f, scale)
+    assert not st.any() and qq.tolist() == [d[1] for d in live]
+    _assert_tensor(oracle, bits, live, st, f, scale, "values batch")
+
+
+@pytest.mark.gpu
+def test_gpu_handle_reuse_with_dense_golden_batches(oracle, batch):
+    """one handle: the 34 golden files (dense natural content), the values batch, the golden files again, the values batch again -- neither may pick up
+    what the other left in the workspace"""
+    import json
+    import nhwcodec_amd
+    from tests.test_decode_surgery import _dec_batch
+    with open(os.path.join(S.GOLD, "manifest.json")) as fp:
+        man = json.load(fp)
+    names = sorted(man)
+    gold = [S.golden(n) for n in names]
+    d = nhwcodec_amd.Decoder(0, max_batch=72)
+    try:
+        hdr = d.bmp_header()
+        for turn in range(2):
+            px, st, qq = _dec_batch(d, gold)
+            bad = [n for i, n in enumerate(names) if st[i] or qq[i] != man[n]["quality"] or sha(hdr + px[i].tobytes()) != man[n]["bmp_sha256"]]
+            assert not bad, f"turn {turn}: golden files differ {'behind the values batch' if turn else ''}: {bad}"
+            _whole(d, batch, f"turn {turn}: the values batch behind the golden files")
+    finally:
+        d.close()
+
+
+@pytest.mark.gpu
+def test_gpu_cases_as_tiles_of_a_container(dec, oracle, batch):
+    """a 2048 x 512 .nhwp picture of four tiles (lone groups, a golden file, one-sided clipping, the all-maximal details): the whole picture, a region
+    and a half-scale window across the borders of the lone-group tile"""
+    from tests.test_scaled_decode import expected
+    by = {name: (data, px) for name, data, _, _, px in batch}
+    tiles = [by[n] for n in ("q20_lone_groups", V.NEIGHBOURS[0], "q10_one_sided", "q23_all_minus")]
+    fs = [t[0] for t in tiles]
+    con = b"NHWP\x01\0\0\0" + struct.pack("<II", 512 * len(fs), 512) + struct.pack(f"<{len(fs)}I", *[len(f) for f in fs]) + b"".join(fs)
+    want = np.concatenate([t[1] for t in tiles], 1)
+    assert np.array_equal(dec.decode_pictures([con])[0], want)
+    rects = [(0, 380, 100, 300, 200), (0, 0, 0, 513, 512), (0, 1000, 500, 600, 12)]
+    for r, got in zip(rects, dec.decode_regions([con], rects)):
+        assert np.array_equal(got, want[r[2]:r[2] + r[4], r[1]:r[1] + r[3]]), r
+    half = np.concatenate([expected(oracle, f, 2) for f in fs], 1)
+    wins = [(0, 200, 40, 120, 100), (0, 250, 0, 300, 256)]
+    for r, got in zip(wins, dec.decode_windows([con], wins, scale=2)):
+        assert np.array_equal(got, half[r[2]:r[2] + r[4], r[1]:r[1] + r[3]]), r
