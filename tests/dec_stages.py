@@ -1,7 +1,10 @@
 """The table behind the decoder's stage checks, shared by tests/test_decode_stages.py and tests/test_decode_values.py: nhw_dec_debug_stop_after ends a
 batch behind one stage, nhw_dec_debug_read copies a workspace buffer out, and the oracle's decode_probe gives the same buffer at the same point of
-decode_image.  STAGES is the table stop -> buffer -> probe id, every row bit for bit."""
+decode_image.  STAGES is the table stop -> buffer -> probe id, every row bit for bit.  dec_batch is the whole decode by the C call, for
+tests/test_decode_surgery.py and tests/test_decode_values.py."""
 import numpy as np
+
+from tests.support import CANARY
 
 D = dict(MARKS=7, A=8, CA=10, CU=12)                                  # nhw_dec_debug_read's buffer indices
 PROBES = (3, 4, 5, 50, 51, 6, 7, 30, 31, 40, 41, 42, 43, 44, 45, 46, 47)
@@ -55,3 +58,16 @@ def run_to(dec, files, stop, mode):
     finally:
         dec.lib.nhw_dec_debug_stop_after(dec.h, 0)
         assert dec.lib.nhw_dec_debug_slice_order(dec.h, 0) == 0
+
+
+def dec_batch(dec, files):
+    """nhw_dec_batch, max_batch files a call (the call takes no more), every output slot filled with the canary first"""
+    n, mb = len(files), dec.max_batch
+    out = np.full((n, 512, 512, 3), CANARY, np.uint8); status = np.full(n, 77, np.int32); quality = np.full(n, 77, np.int32)
+    for i0 in range(0, n, mb):
+        part = files[i0:i0 + mb]
+        offs = np.zeros(len(part) + 1, np.uint64); offs[1:] = np.cumsum([len(f) for f in part])
+        blob = np.frombuffer(b"".join(part), np.uint8)
+        assert dec.lib.nhw_dec_batch(dec.h, blob.ctypes.data, offs.ctypes.data, len(part), out[i0:].ctypes.data, status[i0:].ctypes.data,
+                                     quality[i0:].ctypes.data) == 0
+    return out, status, quality

@@ -613,7 +613,7 @@ def main():
     import tempfile
     from tests.conftest import ROOT as _  # noqa: F401  (the repository root on sys.path)
     from oracle.oraclepy import Oracle
-    from tests.test_scaled_decode import expected
+    from tests.tensor_cases import expected
     exe = build_asan()
     assert exe, "no sanitizer build"
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])

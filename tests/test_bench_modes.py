@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
 FULL_ONLY = ("sweep", "config4_per_gpu_shape", "host_path", "decode", "cpu_baseline")
 
 

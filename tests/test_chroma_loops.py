@@ -12,47 +12,19 @@ import ctypes
 import os
 import subprocess
 import sys
-from concurrent.futures import ProcessPoolExecutor
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-Q = 65536
+from tests.enc_stages import B_CL2SAVE, B_CLL1, B_CPROC, N_IMAGES, Q, chroma_images, oracle_files, ws_index
+from tests.support import ROOT
+
 QUALITIES = (1, 10, 14, 15, 16, 17, 18, 20, 22, 23)   # the q <= 15 branch of the first simulation, both res_uv settings, the q >= 22 path
-N_IMAGES = 64
-
-
-def _ws_index(name):
-    import re
-    txt = open(os.path.join(ROOT, "nhwcodec_amd", "csrc", "nhw_ws.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", txt[txt.index("enum {"):txt.index("B_COUNT")], flags=re.S)
-    return re.findall(r"B_[A-Z0-9_]+", body).index("B_" + name)
-
-
-B_CPROC, B_CLL1, B_CL2SAVE = _ws_index("CPROC"), _ws_index("CLL1"), _ws_index("CL2SAVE")
 
 
 def _luma_stages(q):
     """the stage count behind Y31 (fewer stages where a closed loop is missing); a chroma sequence has 12, the second synthesis is its 11th"""
     return 12 if q >= 22 else 13 if q > 12 else 11 if q > 6 else 7
-
-
-def _want(args):
-    from oracle.oraclepy import Oracle
-    q, compat, imgs = args
-    o = Oracle()
-    o.set_oob_mode(bool(compat))
-    try:
-        return [o.encode(im, q) for im in imgs]
-    finally:
-        o.set_oob_mode(False)
-
-
-def oracle_files(imgs, q, compat=False):
-    step = 4
-    with ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as ex:
-        return [f for part in ex.map(_want, [(q, compat, imgs[i:i + step]) for i in range(0, len(imgs), step)]) for f in part]
 
 
 def threshold_planes(n, seed):
@@ -95,7 +67,7 @@ def check_threshold_planes(q, n=32):
         return [(rd(B_CPROC, i, 2 * Q).reshape(256, 256), rd(B_CL2SAVE, i, Q // 2).reshape(128, 128), rd(B_CLL1, i, Q // 2 + 2)) for i in range(n)]
 
     try:
-        e.encode(synthetic_images(q, n), q)                         # the hook works at the quality of the handle's last whole batch
+        e.encode(chroma_images(q, n), q)                         # the hook works at the quality of the handle's last whole batch
         for comp in (0, 1):
             recon1 = np.stack([p[0][:128, :128] for p in run(comp, 4)]).astype(np.int32)   # behind the first synthesis
             staged = run(comp, 8)
@@ -145,7 +117,7 @@ def check_case(imgs, q, compat=False):
             e.set_compat(True)
         files = e.encode(imgs, q)                                   # the production path
         prod_save = {0: [rd(B_CL2SAVE, i, Q // 2) for i in range(n)] if fork_on else None,   # (in line, V's block has gone over U's in the one plane set)
-                     1: [rd(_ws_index("CL2SAVE_V") if fork_on else B_CL2SAVE, i, Q // 2) for i in range(n)]}
+                     1: [rd(ws_index("CL2SAVE_V") if fork_on else B_CL2SAVE, i, Q // 2) for i in range(n)]}
         fused = {}
         for comp in (0, 1):
             assert e.lib.nhw_stage_chroma_loops(e.h, n, comp, 0, None) == 0, "nhw_stage_chroma_loops"
@@ -174,22 +146,16 @@ def check_case(imgs, q, compat=False):
     return n
 
 
-def synthetic_images(q, n=N_IMAGES):
-    from oracle.oraclepy import Oracle
-    o = Oracle()
-    return np.stack([o.synth(52000 + 97 * q + i) for i in range(n)])
-
-
 def run_all_qualities():
     for q in QUALITIES:
-        assert check_case(synthetic_images(q), q) == N_IMAGES
+        assert check_case(chroma_images(q), q) == N_IMAGES
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("q", QUALITIES)
 def test_fused_chroma_loops_equal_the_staged_kernels(q):
     """64 generator images a quality, chroma fork on (V in its own plane set in the production batch)."""
-    assert check_case(synthetic_images(q), q) == N_IMAGES
+    assert check_case(chroma_images(q), q) == N_IMAGES
 
 
 @pytest.mark.gpu

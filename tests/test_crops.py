@@ -1,6 +1,6 @@
 """Crops resized into tensors of one size: the rule, the kernel k_resize_to_tensor (nhw_resize_to_tensor_device), the
 host call nhw_dec_crops_to_device and the Python wrappers crop_scale, crop_window, resize_to_tensor_device and Decoder.decode_crops_device.
-The rule is stated here in numpy, in 64-bit integers, from the window's bytes alone; the elements come from test_tensor_decode's
+The rule is stated here in numpy, in 64-bit integers, from the window's bytes alone; the elements come from tensor_cases.py's
 expected_tensor.  Every comparison is exact: bytes for uint8, bit patterns for the float types."""
 import ctypes
 import os
@@ -9,10 +9,10 @@ import re
 import numpy as np
 import pytest
 
-from tests.test_tensor_decode import expected_tensor
-from tests.test_windows import SIZES, Rect, expected_stats, make_container, parse_container, selected
+from tests.picture_cases import SIZES, Rect, World, expected_stats, make_container, parse_container, selected
+from tests.support import CANARY, ROOT, load_lib
+from tests.tensor_cases import ALL_FORMATS, expected_tensor, tensor_bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ("nhw_crop_scale", "nhw_resize_to_tensor_device", "nhw_dec_crops_to_device")
 PROTOTYPES = """
 int nhw_crop_scale(uint32_t width, uint32_t height, uint32_t out_width, uint32_t out_height);
@@ -22,7 +22,6 @@ int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off
                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status);
 """
 NHW_E_ARG, NHW_E_FORMAT = -4, -6
-CANARY = 0xA5
 GUARD = 4096                                                        # canary bytes kept in front of and behind a batch
 SCALES = (1, 2, 4)
 QUALITY = 20
@@ -30,8 +29,6 @@ BIG = 2                                                             # 1023 x 102
 
 IMAGENET = dict(mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
 NEGATIVE = dict(scale=(-1 / 255, -0.5, -2.0), bias=(1.0, 127.5, 3.25))
-DTYPES = ("uint8", "float16", "bfloat16", "float32")
-ALL_FORMATS = [(d, l, c, r) for d in DTYPES for l in ("HWC", "CHW") for c in ("BGR", "RGB") for r in ("file", "reversed")]   # 32
 
 
 def _fmt(dtype, layout, channels, rows, k=0):
@@ -68,20 +65,9 @@ def rule(P, out_w, out_h, flip=False):
     return np.ascontiguousarray(R[:, ::-1]) if flip else R
 
 
-def _bits(t):
-    """a tensor's bit patterns on the host, as unsigned integers"""
-    import torch
-    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()]
-    return t.contiguous().view(view).cpu().numpy().view({1: np.uint8, 2: np.uint16, 4: np.uint32}[t.element_size()])
-
-
 @pytest.fixture(scope="module")
 def lib():
-    import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return nhwcodec_amd.load_library()                               # (behind torch: a process must have one HIP runtime, and the GPU tests of this file follow)
+    return load_lib()
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -268,7 +254,7 @@ def test_gpu_resize_kernel_on_random_bytes(sources, out_w, out_h):
     fmt = _fmt("float16", "CHW", "RGB", "reversed")
     got = na.resize_to_tensor_device(sources.views, (out_h, out_w), fmt, flips=[bool(f) for f in FLAGS])
     assert got.dtype == fmt.dtype and tuple(got.shape) == (n, 3, out_h, out_w)
-    bits = _bits(got)
+    bits = tensor_bits(got)
     for i in range(n):
         assert np.array_equal(bits[i], expected_tensor(sources.rule(i, out_w, out_h, FLAGS[i]), fmt))
     plain = na.resize_to_tensor_device(sources.views, (out_h, out_w), _fmt("uint8", "HWC", "BGR", "file"))
@@ -341,13 +327,9 @@ def test_gpu_resize_many_crops_take_bands_of_64_rows(sources):
 
 
 # ---------------------------------------------------------------- on the MI355X: the host path
-class World:
-    pass
-
-
 @pytest.fixture(scope="module")
 def world():
-    """test_windows.py's pictures (1 x 700, 500 x 375, 1023 x 1025: crops of one seeded scene of generated images) as containers at q20, and a
+    """the windows' pictures (SIZES: 1 x 700, 500 x 375, 1023 x 1025, crops of one seeded scene of generated images) as containers at q20, and a
     decoder of 4 tiles a chunk: the six tiles of the large picture span two chunks"""
     import nhwcodec_amd as na
     w = World()
@@ -398,7 +380,7 @@ def test_gpu_crops_of_their_own_size_are_the_windows(world, scale):
         want = torch.stack(na.pictures_to_tensor_device(wins, fmt))
         got, scales = world.dec.decode_crops_device(world.containers, rects, (h, w), fmt, scale=scale)
         assert scales == [scale] * len(rects) and got.dtype == fmt.dtype and tuple(got.shape) == (len(rects),) + fmt.shape(h, w)
-        assert np.array_equal(_bits(got), _bits(want)), (scale, fmt)
+        assert np.array_equal(tensor_bits(got), tensor_bits(want)), (scale, fmt)
 
 
 @pytest.mark.gpu
@@ -418,9 +400,9 @@ def test_gpu_crops_equal_the_rule_on_decode_windows(world, scale, out_w, out_h, 
     stats = world.dec.region_stats()
     got, scales = world.dec.decode_crops_device(world.containers, rects, (out_h, out_w), fmt, flips=flips, scale=scale)
     assert scales == [scale] * len(rects) and tuple(got.shape) == (len(rects),) + fmt.shape(out_h, out_w)
-    assert world.dec.region_stats() == stats == expected_stats(world.containers, rects, scale)
+    assert world.dec.region_stats() == stats == expected_stats(world.containers, rects, scale, unique=True)
     assert 8 <= stats[0] <= 9 < sum(len(k) for k in slots(rects, scale))                            # (nearly) every tile there is, each once
-    bits = _bits(got)
+    bits = tensor_bits(got)
     for i, (r, P, f) in enumerate(zip(rects, wins, flips)):
         assert P.shape == (r[4], r[3], 3)
         assert np.array_equal(bits[i], expected_tensor(rule(P, out_w, out_h, f), fmt)), (scale, r, f)
@@ -428,11 +410,11 @@ def test_gpu_crops_equal_the_rule_on_decode_windows(world, scale, out_w, out_h, 
     perm = rng.permutation(len(rects))
     per = 3 * out_w * out_h
     mine = torch.full((len(rects) * per + 64,), 1, dtype=fmt.dtype, device="cuda")
-    before = _bits(mine[len(rects) * per:]).copy()
+    before = tensor_bits(mine[len(rects) * per:]).copy()
     again, _ = world.dec.decode_crops_device(world.containers, [rects[i] for i in perm], (out_h, out_w), fmt, flips=[flips[i] for i in perm], scale=scale, out=mine)
     assert again.data_ptr() == mine.data_ptr() and world.dec.region_stats() == stats
-    assert np.array_equal(_bits(again), bits[perm])
-    assert np.array_equal(_bits(mine[len(rects) * per:]), before)
+    assert np.array_equal(tensor_bits(again), bits[perm])
+    assert np.array_equal(tensor_bits(mine[len(rects) * per:]), before)
 
 
 @pytest.mark.gpu
@@ -452,7 +434,7 @@ def test_gpu_crops_choose_their_scale(world):
     got, scales = world.dec.decode_crops_device(world.containers, crops, (out_h, out_w), fmt, flips=flips)
     assert scales == [crop_scale_rule(w, h, out_w, out_h) for _, _, _, w, h in crops] == [na.crop_scale(w, h, out_w, out_h) for _, _, _, w, h in crops]
     assert scales[:7] == [4, 4, 2, 2, 1, 1, 1] and all(scales.count(s) >= 5 for s in SCALES)
-    bits = _bits(got)
+    bits = tensor_bits(got)
     for s in SCALES:
         idx = [i for i, v in enumerate(scales) if v == s]
         rects = [(crops[i][0], *na.crop_window(*crops[i][1:], s)) for i in idx]
@@ -503,7 +485,7 @@ def test_gpu_a_refused_tile_fails_exactly_the_crops_that_select_it(world, scale)
     rc, status = _call_crops(world.dec, [broken], rects, scale, out_w, out_h, fmt.c_struct(), flips, addrs)
     torch.cuda.synchronize()
     assert rc == 0 and status.tolist() == [NHW_E_FORMAT if h else 0 for h in hit]
-    assert world.dec.region_stats() == expected_stats([broken], rects, scale)
+    assert world.dec.region_stats() == expected_stats([broken], rects, scale, unique=True)
     host = buf.cpu().numpy()
     ok = [r for r, h in zip(rects, hit) if not h]
     wins = iter(world.dec.decode_windows([broken], ok, scale))
@@ -612,9 +594,9 @@ def test_gpu_one_handle_serves_files_pictures_windows_and_crops(world):
     steps = [("files", lambda d: d.decode(files[:4])[0]), ("pictures", lambda d: d.decode_pictures(cs))]
     for s in SCALES:
         steps += [(f"windows {s}", lambda d, s=s: d.decode_windows(cs, rects[s], s)),
-                  (f"crops {s}", lambda d, s=s: [_bits(d.decode_crops_device(cs, rects[s], (24, 40), fmt, flips=[True, False, False, True], scale=s)[0])]),
+                  (f"crops {s}", lambda d, s=s: [tensor_bits(d.decode_crops_device(cs, rects[s], (24, 40), fmt, flips=[True, False, False, True], scale=s)[0])]),
                   (f"windows again {s}", lambda d, s=s: d.decode_windows(cs, rects[s], s))]
-    steps.append(("crops any", lambda d: [_bits(d.decode_crops_device(cs, rects[1], (24, 40), fmt)[0])]))
+    steps.append(("crops any", lambda d: [tensor_bits(d.decode_crops_device(cs, rects[1], (24, 40), fmt)[0])]))
     fresh = []
     for name, step in steps:                                         # every step on a handle of its own
         d = na.Decoder(0, max_batch=4)

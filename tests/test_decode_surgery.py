@@ -16,9 +16,10 @@ import numpy as np
 import pytest
 
 from tests import nhw_surgery as S
+from tests.dec_stages import dec_batch
+from tests.support import CANARY, device_arena
 
 NHW_E_FORMAT = -6
-CANARY = 0xA5
 NEIGHBOURS = S.NEIGHBOURS
 sha = lambda b: hashlib.sha256(b).hexdigest()
 
@@ -155,19 +156,6 @@ def _batches(record):
     return out
 
 
-def _dec_batch(dec, files):
-    """nhw_dec_batch, max_batch files a call (the call takes no more), every output slot filled with the canary first"""
-    n, mb = len(files), dec.max_batch
-    out = np.full((n, 512, 512, 3), CANARY, np.uint8); status = np.full(n, 77, np.int32); quality = np.full(n, 77, np.int32)
-    for i0 in range(0, n, mb):
-        part = files[i0:i0 + mb]
-        offs = np.zeros(len(part) + 1, np.uint64); offs[1:] = np.cumsum([len(f) for f in part])
-        blob = np.frombuffer(b"".join(part), np.uint8)
-        assert dec.lib.nhw_dec_batch(dec.h, blob.ctypes.data, offs.ctypes.data, len(part), out[i0:].ctypes.data, status[i0:].ctypes.data,
-                                     quality[i0:].ctypes.data) == 0
-    return out, status, quality
-
-
 def _check(items, px, status, quality, dec_manifest, hdr, what):
     bad = []
     for i, (name, data, r) in enumerate(items):
@@ -195,7 +183,7 @@ def test_gpu_defined_cases_one_mixed_batch(dec, record, dec_manifest, mode):
     hdr = dec.bmp_header()
     _mode(dec, mode)
     try:
-        px, st, qq = _dec_batch(dec, files)
+        px, st, qq = dec_batch(dec, files)
         _check(items, px, st, qq, dec_manifest, hdr, f"nhw_dec_batch, slice order {mode}")
         if mode == 0:
             px2, q2 = dec.decode(files)
@@ -214,7 +202,7 @@ def test_gpu_refused_cases_one_mixed_batch(dec, record, dec_manifest, mode):
     assert 60 < len(files) <= dec.max_batch
     _mode(dec, mode)
     try:
-        px, st, qq = _dec_batch(dec, files)
+        px, st, qq = dec_batch(dec, files)
         _check(items, px, st, qq, dec_manifest, dec.bmp_header(), f"nhw_dec_batch, slice order {mode}")
         if mode == 0:
             import nhwcodec_amd
@@ -247,7 +235,7 @@ def test_gpu_both_batches_on_a_handle_that_just_decoded_dense_files(record, dec_
         assert int(st[ok].abs().sum()) == 0
         hdr = d.bmp_header()
         for items, what in zip(_batches(record), ("defined", "refused")):
-            px, st, qq = _dec_batch(d, [x for _, x, _ in items])
+            px, st, qq = dec_batch(d, [x for _, x, _ in items])
             _check(items, px, st, qq, dec_manifest, hdr, f"{what} cases after a dense batch")
     finally:
         d.close()
@@ -257,15 +245,14 @@ def test_gpu_both_batches_on_a_handle_that_just_decoded_dense_files(record, dec_
 @pytest.mark.parametrize("scale", [2, 4])
 def test_gpu_scaled_decode_of_every_case(dec, record, neighbours, scale):
     """decode_scaled_device: status and quality as the full decode's; a defined case equals the scaled definition of DESIGN.md section 14 (the
-    digest surgery.json keeps was computed by tests/test_scaled_decode.py's `expected`); a refused file's bytes are left untouched, as
+    digest surgery.json keeps was computed by tests/tensor_cases.py's `expected`); a refused file's bytes are left untouched, as
     include/nhw_hip.h promises for the scaled calls"""
     import torch
-    from tests.test_scaled_decode import _arena
     t = 512 // scale
     for items in _batches(record):
         files = [d for _, d, _ in items]
         buf = torch.full((len(files) * 3 * t * t + 4096,), CANARY, dtype=torch.uint8, device="cuda")
-        px, st, qq = dec.decode_scaled_device(*_arena(files), scale, out=buf)
+        px, st, qq = dec.decode_scaled_device(*device_arena(files), scale, out=buf)
         torch.cuda.synchronize()
         assert bool((buf[len(files) * 3 * t * t:] == CANARY).all())
         px, st, qq = px.cpu().numpy(), st.cpu().numpy(), qq.cpu().numpy()

@@ -20,10 +20,10 @@ import pytest
 
 from tests import nhw_surgery as S
 from tests import nhw_values as V
-from tests.dec_stages import PROBES, STAGES, run_to
+from tests.dec_stages import PROBES, STAGES, dec_batch, run_to
+from tests.tensor_cases import assert_tensor, decode_scaled, decode_tensor, expected, tensor_format
 
 NHW_E_FORMAT = -6
-CANARY = 0xA5
 REACH_PROBES = tuple(sorted(set(PROBES) | {8, 9}))
 sha = V.sha
 
@@ -387,8 +387,7 @@ def batch(oracle, cases, record, probed):
 
 
 def _whole(dec, batch, what):
-    from tests.test_decode_surgery import _dec_batch
-    px, st, qq = _dec_batch(dec, [d for _, d, *_ in batch])
+    px, st, qq = dec_batch(dec, [d for _, d, *_ in batch])
     bad = []
     for i, (name, data, cls, _, want) in enumerate(batch):
         if cls == "refused":
@@ -441,11 +440,10 @@ def test_gpu_stage_matches_oracle(dec, batch, stop):
 @pytest.mark.gpu
 @pytest.mark.parametrize("scale", [2, 4])
 def test_gpu_scaled_decode(dec, oracle, batch, scale):
-    """half and quarter scale against tests/test_scaled_decode.py's definition, built from the oracle's probes: the clips of k_dec_scaled on planes that
+    """half and quarter scale against tests/tensor_cases.py's definition, built from the oracle's probes: the clips of k_dec_scaled on planes that
     leave 0 .. 255 on both sides"""
-    from tests.test_scaled_decode import _decode_scaled, expected
     live = [it for it in batch if it[2] == "defined"]
-    px, st, qq = _decode_scaled(dec, [d for _, d, *_ in live], scale)
+    px, st, qq = decode_scaled(dec, [d for _, d, *_ in live], scale)
     bad = [(name, int(st[i]), int((px[i] != expected(oracle, data, scale)).sum())) for i, (name, data, *_) in enumerate(live)
            if st[i] != 0 or qq[i] != data[1] or not np.array_equal(px[i], expected(oracle, data, scale))]
     assert not bad, f"scale {scale}: (file, status, differing bytes) {bad[:12]}"
@@ -458,13 +456,12 @@ TENSOR_FORMATS = [("float16", "CHW", "RGB", "file", "imagenet"), ("bfloat16", "H
 @pytest.mark.parametrize("scale", [1, 2, 4])
 @pytest.mark.parametrize("fmt", TENSOR_FORMATS, ids=lambda f: "-".join(f))
 def test_gpu_tensor_formats(dec, oracle, batch, fmt, scale):
-    """decode_tensor_device: the bit patterns of tests/test_tensor_decode.py's CPU form of the oracle's picture"""
-    from tests.test_tensor_decode import _assert_tensor, _decode_tensor, _fmt
-    f = _fmt(*fmt)
+    """decode_tensor_device: the bit patterns of tests/tensor_cases.py's CPU form of the oracle's picture"""
+    f = tensor_format(*fmt)
     live = [d for _, d, cls, *_ in batch if cls == "defined"]
-    bits, st, qq = _decode_tensor(dec, live, f, scale)
+    bits, st, qq = decode_tensor(dec, live, f, scale)
     assert not st.any() and qq.tolist() == [d[1] for d in live]
-    _assert_tensor(oracle, bits, live, st, f, scale, "values batch")
+    assert_tensor(oracle, bits, live, st, f, scale, "values batch")
 
 
 @pytest.mark.gpu
@@ -473,7 +470,6 @@ def test_gpu_handle_reuse_with_dense_golden_batches(oracle, batch):
     what the other left in the workspace"""
     import json
     import nhwcodec_amd
-    from tests.test_decode_surgery import _dec_batch
     with open(os.path.join(S.GOLD, "manifest.json")) as fp:
         man = json.load(fp)
     names = sorted(man)
@@ -482,7 +478,7 @@ def test_gpu_handle_reuse_with_dense_golden_batches(oracle, batch):
     try:
         hdr = d.bmp_header()
         for turn in range(2):
-            px, st, qq = _dec_batch(d, gold)
+            px, st, qq = dec_batch(d, gold)
             bad = [n for i, n in enumerate(names) if st[i] or qq[i] != man[n]["quality"] or sha(hdr + px[i].tobytes()) != man[n]["bmp_sha256"]]
             assert not bad, f"turn {turn}: golden files differ {'behind the values batch' if turn else ''}: {bad}"
             _whole(d, batch, f"turn {turn}: the values batch behind the golden files")
@@ -494,7 +490,6 @@ def test_gpu_handle_reuse_with_dense_golden_batches(oracle, batch):
 def test_gpu_cases_as_tiles_of_a_container(dec, oracle, batch):
     """a 2048 x 512 .nhwp picture of four tiles (lone groups, a golden file, one-sided clipping, the all-maximal details): the whole picture, a region
     and a half-scale window across the borders of the lone-group tile"""
-    from tests.test_scaled_decode import expected
     by = {name: (data, px) for name, data, _, _, px in batch}
     tiles = [by[n] for n in ("q20_lone_groups", V.NEIGHBOURS[0], "q10_one_sided", "q23_all_minus")]
     fs = [t[0] for t in tiles]

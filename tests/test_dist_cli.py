@@ -6,7 +6,7 @@ import sys
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT, built_cli, run
 
 
 def test_shard_ranges_partition_the_batch():
@@ -86,20 +86,12 @@ def test_bench_strong_split_is_baseline_config_4():
 
 
 # ---------------------------------------------------------------- CLI contract (no GPU needed for argument handling)
-CLI = os.path.join(ROOT, "tools", "nhw-enc")
 REF_CLI = os.path.join(ROOT, "oracle", "_ref", "nhw-enc")
-
-
-def _run(exe, *a):
-    p = subprocess.run([exe, *a], capture_output=True, text=True)
-    return p.returncode, p.stdout, p.stderr
 
 
 @pytest.fixture(scope="module")
 def cli():
-    if not os.path.exists(CLI):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return CLI
+    return built_cli("nhw-enc")
 
 
 # what the stock reference binaries (oracle/_ref/nhw-enc, nhw-dec) answered to these command lines and files: recorded in
@@ -117,14 +109,14 @@ def cli_record(ref_record):
 
 @pytest.mark.parametrize("args", ENC_ARGS)
 def test_cli_argument_handling_matches_reference_binary(cli, cli_record, args):
-    rc, out, err = _run(cli, *args)
+    rc, out, err = run(cli, *args)
     want = cli_record["enc_args"][" ".join(args)]
     assert rc == want["rc"]
     assert out.splitlines()[:1] == want["stdout_lines"][:1] and err == want["stderr"]
 
 
 def test_cli_rejects_unimplemented_quality_loudly(cli):
-    rc, out, err = _run(cli, "-q0", "a.bmp", "b.nhw")       # accepted by the reference's argument loop, but it has no tables for it
+    rc, out, err = run(cli, "-q0", "a.bmp", "b.nhw")       # accepted by the reference's argument loop, but it has no tables for it
     assert rc == 3 and "not implemented" in err
 
 
@@ -133,7 +125,7 @@ def test_cli_rejects_unimplemented_quality_loudly(cli):
                                       (["--chunk", "x"], "--chunk wants"), (["--chunk", "0"], "--chunk wants"), (["--chunk", "99999"], "--chunk wants")])
 def test_cli_rejects_malformed_device_lists_and_chunks(cli, tmp_path, args, msg):
     """A malformed --devices / --chunk is an error with a message and exit code 1 (before any GPU work), not a silent `device 0` / clamp."""
-    rc, out, err = _run(cli, *args, "--synthetic", "1", "--outdir", str(tmp_path))
+    rc, out, err = run(cli, *args, "--synthetic", "1", "--outdir", str(tmp_path))
     assert rc == 1 and msg in err, (rc, err)
     assert not list(tmp_path.iterdir())
 
@@ -142,7 +134,7 @@ def test_cli_bad_bmp_exit_codes_match_reference(cli, cli_record, tmp_path):
     for name, data in BAD_BMPS.items():
         p = tmp_path / name
         p.write_bytes(data)
-        rc, out, _ = _run(cli, str(p), str(tmp_path / "o.nhw"))
+        rc, out, _ = run(cli, str(p), str(tmp_path / "o.nhw"))
         want = cli_record["bad_bmp"][name]
         assert (rc, out) == (want["rc"], want["stdout"]), name
 
@@ -154,33 +146,33 @@ def test_cli_end_to_end_files(cli, oracle, tmp_path):
     from oracle.harness import bmp_bytes
     img = oracle.synth(21)
     (tmp_path / "a.bmp").write_bytes(bmp_bytes(img))
-    assert _run(cli, "-q20", str(tmp_path / "a.bmp"), str(tmp_path / "a.nhw"))[0] == 0
+    assert run(cli, "-q20", str(tmp_path / "a.bmp"), str(tmp_path / "a.nhw"))[0] == 0
     assert (tmp_path / "a.nhw").read_bytes() == oracle.encode(img, 20)
     # negative height: rows stored top-down -> the reader flips them
     hdr = struct.pack("<2sIHHIIiiHHIIiiII", b"BM", 54 + img.size, 0, 0, 54, 40, 512, -512, 1, 24, 0, img.size, 0, 0, 0, 0)
     (tmp_path / "b.bmp").write_bytes(hdr + img.tobytes())
-    assert _run(cli, "-q23", str(tmp_path / "b.bmp"), str(tmp_path / "b.nhw"))[0] == 0
+    assert run(cli, "-q23", str(tmp_path / "b.bmp"), str(tmp_path / "b.nhw"))[0] == 0
     assert (tmp_path / "b.nhw").read_bytes() == oracle.encode(img[::-1], 23)
     # V4 header (108 bytes) with a larger data offset, truncated pixel data (short read -> zero tail)
     off = 14 + 108 + 20
     hdr = struct.pack("<2sIHHI", b"BM", off + img.size, 0, 0, off) + struct.pack("<IiiHHI", 108, 512, 512, 1, 24, 0) + bytes(108 - 20) + bytes(20)
     cut = img.copy(); cut.reshape(-1)[-30000:] = 0
     (tmp_path / "c.bmp").write_bytes(hdr + img.tobytes()[:-30000])
-    assert _run(cli, str(tmp_path / "c.bmp"), str(tmp_path / "c.nhw"))[0] == 0
+    assert run(cli, str(tmp_path / "c.bmp"), str(tmp_path / "c.nhw"))[0] == 0
     assert (tmp_path / "c.nhw").read_bytes() == oracle.encode(cut, 20)
     # batch directory mode
     d = tmp_path / "dir"; d.mkdir()
     for s in (1, 2, 3):
         (d / f"i{s}.bmp").write_bytes(bmp_bytes(oracle.synth(s)))
-    assert _run(cli, "-q21", "--batch", str(d))[0] == 0
+    assert run(cli, "-q21", "--batch", str(d))[0] == 0
     for s in (1, 2, 3):
         assert (d / f"i{s}.nhw").read_bytes() == oracle.encode(oracle.synth(s), 21)
     # synthetic mode: SURVEY 8d images generated on the device, one file per seed; --gpus 1 = one worker thread on device 0
     o = tmp_path / "syn"; o.mkdir()
-    assert _run(cli, "-q10", "--gpus", "1", "--synthetic", "5", "--seed", "40", "--outdir", str(o))[0] == 0
+    assert run(cli, "-q10", "--gpus", "1", "--synthetic", "5", "--seed", "40", "--outdir", str(o))[0] == 0
     for s in range(40, 45):
         assert (o / f"synth_{s}.nhw").read_bytes() == oracle.encode(oracle.synth(s), 10)
-    rc, _, err = _run(cli, "--gpus", "99", "--synthetic", "2", "--outdir", str(o))
+    rc, _, err = run(cli, "--gpus", "99", "--synthetic", "2", "--outdir", str(o))
     assert rc == 1 and "device(s) visible" in err
 
 
@@ -191,33 +183,30 @@ def test_cli_two_workers_on_one_device_share_the_queue(cli, oracle, tmp_path):
     quality and at the headline one, so that both front kernels and their per-handle attributes run twice in one process."""
     for q, n in ((20, 40), (10, 24)):
         one = tmp_path / f"one{q}"; two = tmp_path / f"two{q}"; one.mkdir(); two.mkdir()
-        assert _run(cli, f"-q{q}", "--gpus", "1", "--chunk", "7", "--synthetic", str(n), "--seed", "900", "--outdir", str(one))[0] == 0
-        rc, out, err = _run(cli, f"-q{q}", "--devices", "0,0", "--chunk", "7", "--synthetic", str(n), "--seed", "900", "--outdir", str(two))
+        assert run(cli, f"-q{q}", "--gpus", "1", "--chunk", "7", "--synthetic", str(n), "--seed", "900", "--outdir", str(one))[0] == 0
+        rc, out, err = run(cli, f"-q{q}", "--devices", "0,0", "--chunk", "7", "--synthetic", str(n), "--seed", "900", "--outdir", str(two))
         assert rc == 0, err
         for s in range(900, 900 + n):
             a, b = (one / f"synth_{s}.nhw").read_bytes(), (two / f"synth_{s}.nhw").read_bytes()
             assert a == b, f"q{q} seed {s}: the two-worker run differs from the one-worker run"
         for s in (900, 900 + n // 2, 900 + n - 1):
             assert (two / f"synth_{s}.nhw").read_bytes() == oracle.encode(oracle.synth(s), q)
-    rc, _, err = _run(cli, "--devices", "0,7", "--synthetic", "2", "--outdir", str(tmp_path))
+    rc, _, err = run(cli, "--devices", "0,7", "--synthetic", "2", "--outdir", str(tmp_path))
     assert rc == 1 and "device(s) visible" in err
 
 
 # ---------------------------------------------------------------- nhw-dec
-DEC_CLI = os.path.join(ROOT, "tools", "nhw-dec")
 REF_DEC_CLI = os.path.join(ROOT, "oracle", "_ref", "nhw-dec")
 
 
 @pytest.fixture(scope="module")
 def dec_cli():
-    if not os.path.exists(DEC_CLI):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return DEC_CLI
+    return built_cli("nhw-dec")
 
 
 def test_dec_cli_usage_matches_reference_binary(dec_cli, cli_record):
     for args in DEC_ARGS:
-        rc, out, err = _run(dec_cli, *args)
+        rc, out, err = run(dec_cli, *args)
         want = cli_record["dec_args"][" ".join(args)]
         assert rc == want["rc"] == 0
         assert out.splitlines()[:5] == want["stdout_lines"][:5] and err == want["stderr"]
@@ -233,17 +222,17 @@ def test_dec_cli_end_to_end_files(dec_cli, oracle, tmp_path):
     man = json.load(open(os.path.join(gold, "manifest.json")))
     for name in ("q20_0.nhw", "q07_0.nhw", "q23_0.nhw"):
         shutil.copy(os.path.join(gold, name), tmp_path / name)
-        assert _run(dec_cli, str(tmp_path / name), str(tmp_path / (name + ".bmp")))[0] == 0
+        assert run(dec_cli, str(tmp_path / name), str(tmp_path / (name + ".bmp")))[0] == 0
         assert hashlib.sha256((tmp_path / (name + ".bmp")).read_bytes()).hexdigest() == man[name]["bmp_sha256"]
     d = tmp_path / "dir"; d.mkdir()
     names = ["q01_0.nhw", "q10_0.nhw", "q16_4.nhw", "q20_blocks.nhw"]
     for n in names:
         shutil.copy(os.path.join(gold, n), d / n)
-    assert _run(dec_cli, "--batch", str(d))[0] == 0
+    assert run(dec_cli, "--batch", str(d))[0] == 0
     for n in names:
         assert hashlib.sha256((d / (n[:-4] + ".bmp")).read_bytes()).hexdigest() == man[n]["bmp_sha256"]
     (tmp_path / "junk.nhw").write_bytes(b"BM" + bytes(500))
-    rc, out, _ = _run(dec_cli, str(tmp_path / "junk.nhw"), str(tmp_path / "junk.bmp"))
+    rc, out, _ = run(dec_cli, str(tmp_path / "junk.nhw"), str(tmp_path / "junk.bmp"))
     assert rc == 3 and "Not an .nhw file" in out and not (tmp_path / "junk.bmp").exists()
 
 
@@ -270,7 +259,7 @@ def test_tile_helpers_round_trip_and_reject_odd_sizes():
 def test_cli_tiles_rejects_sizes_that_are_not_multiples_of_512(cli, tmp_path):
     """the size check comes before any GPU work: same "invalid image file." line and exit code as a wrong-size BMP in the one-tile path"""
     (tmp_path / "odd.bmp").write_bytes(_big_bmp(np.zeros((512, 600, 3), np.uint8)))
-    rc, out, err = _run(cli, "--tiles", str(tmp_path / "odd.bmp"), str(tmp_path / "odd"))
+    rc, out, err = run(cli, "--tiles", str(tmp_path / "odd.bmp"), str(tmp_path / "odd"))
     assert rc == (-16) % 256 and "invalid image file." in out and "multiples of 512" in err
 
 
@@ -281,7 +270,7 @@ def test_cli_tiles_encode_and_join(cli, dec_cli, oracle, tmp_path):
     import nhwcodec_amd as na
     big = na.untile_images(np.stack([oracle.synth(700 + t) for t in range(6)]), 2, 3)
     (tmp_path / "big.bmp").write_bytes(_big_bmp(big))
-    rc, out, _ = _run(cli, "-q20", "--tiles", str(tmp_path / "big.bmp"), str(tmp_path / "t"))
+    rc, out, _ = run(cli, "-q20", "--tiles", str(tmp_path / "big.bmp"), str(tmp_path / "t"))
     assert rc == 0 and "2 x 3 tiles" in out
     files = []
     for r in range(2):
@@ -289,14 +278,14 @@ def test_cli_tiles_encode_and_join(cli, dec_cli, oracle, tmp_path):
             f = (tmp_path / f"t_y{r}_x{c}.nhw").read_bytes()
             assert f == oracle.encode(big[512 * r:512 * r + 512, 512 * c:512 * c + 512], 20), (r, c)
             files.append(f)
-    assert _run(dec_cli, "--tiles", "2", "3", str(tmp_path / "t"), str(tmp_path / "joined.bmp"))[0] == 0
+    assert run(dec_cli, "--tiles", "2", "3", str(tmp_path / "t"), str(tmp_path / "joined.bmp"))[0] == 0
     joined = (tmp_path / "joined.bmp").read_bytes()
     want = na.untile_images(np.stack([oracle.decode(f)[0] for f in files]), 2, 3)
     assert len(joined) == 54 + want.size and joined[54:] == want.tobytes()
     assert int.from_bytes(joined[18:22], "little") == 1536 and int.from_bytes(joined[22:26], "little") == 1024
     # top-down file
     (tmp_path / "neg.bmp").write_bytes(_big_bmp(big, negative_height=True))
-    assert _run(cli, "-q23", "--tiles", str(tmp_path / "neg.bmp"), str(tmp_path / "n"))[0] == 0
+    assert run(cli, "-q23", "--tiles", str(tmp_path / "neg.bmp"), str(tmp_path / "n"))[0] == 0
     assert (tmp_path / "n_y0_x2.nhw").read_bytes() == oracle.encode(big[::-1][:512, 1024:], 23)
     # python
     e = na.Encoder(0, 6)
@@ -309,9 +298,9 @@ def test_cli_tiles_encode_and_join(cli, dec_cli, oracle, tmp_path):
 
 # ---------------------------------------------------------------- a tar archive as the batch container
 def test_cli_tar_missing_archive_fails_before_any_gpu_work(cli, dec_cli, tmp_path):
-    rc, out, _ = _run(cli, "--tar", str(tmp_path / "none.tar"), str(tmp_path / "o.tar"))
+    rc, out, _ = run(cli, "--tar", str(tmp_path / "none.tar"), str(tmp_path / "o.tar"))
     assert rc == 255 and "Could not open file" in out
-    assert _run(dec_cli, "--tar", str(tmp_path / "none.tar"), str(tmp_path / "o.tar"))[0] == 1
+    assert run(dec_cli, "--tar", str(tmp_path / "none.tar"), str(tmp_path / "o.tar"))[0] == 1
 
 
 @pytest.mark.gpu
@@ -329,7 +318,7 @@ def test_cli_tar_round_trip(cli, dec_cli, oracle, tmp_path):
         for name, im in imgs.items():
             add(name, bmp_bytes(im))
         add("broken.bmp", b"BM" + bytes(100))
-    rc, out, err = _run(cli, "-q21", "--tar", str(src), str(tmp_path / "out.tar"))
+    rc, out, err = run(cli, "-q21", "--tar", str(src), str(tmp_path / "out.tar"))
     assert rc == 1 and "5 image(s) encoded" in out and "broken.bmp" in err          # the broken member makes the exit code 1, the others are there
     with tarfile.open(tmp_path / "out.tar") as tf:
         members = tf.getmembers()
@@ -337,7 +326,7 @@ def test_cli_tar_round_trip(cli, dec_cli, oracle, tmp_path):
         files = [tf.extractfile(m).read() for m in members]
     for f, im in zip(files, imgs.values()):
         assert f == oracle.encode(im, 21)
-    assert _run(dec_cli, "--tar", str(tmp_path / "out.tar"), str(tmp_path / "back.tar"))[0] == 0
+    assert run(dec_cli, "--tar", str(tmp_path / "out.tar"), str(tmp_path / "back.tar"))[0] == 0
     with tarfile.open(tmp_path / "back.tar") as tf:
         members = tf.getmembers()
         assert [m.name for m in members] == list(imgs)

@@ -16,9 +16,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_luma_loop import Hook, compare, _ws_index, synthetic_images
+from tests.enc_stages import B_CL2SAVE, B_CLL1, B_CPROC, Q, Hook, chroma_images, compare, synthetic_images, ws_index
 
-Q = 65536
 GATE_LO, GATE_HI = -1300, 3000
 SGN = np.array([1, 1, -1, 1])       # the sign of the low-pass taps around an output at 2k, from 2k on, period 4
 STAGED = [(512, 256, 1), (256, 256, 0), (256, 128, 1), (512, 256, 0)]
@@ -323,7 +322,7 @@ def test_staged_analysis_at_the_gate(enc, oracle, stride, size, final):
 
 
 # ---------------------------------------------------------------------------------------------- 3. GPU: the fused kernels, through the hooks
-B_CPROC, B_CLL1, B_CL2SAVE, B_CJPEG, B_PV = (_ws_index(n) for n in ("CPROC", "CLL1", "CL2SAVE", "CJPEG", "PV"))
+B_CJPEG, B_PV = ws_index("CJPEG"), ws_index("PV")
 
 
 @pytest.mark.gpu
@@ -333,7 +332,6 @@ def test_chroma_loops_at_the_gate(oracle, q):
     staged kernels (form 8) on every plane; and its second analysis against the oracle's of the pre-compensated block, which form 5 leaves in
     cjpeg -- that block must itself have wide pairs beside packed ones.  q15 / q20: both forms of the first simulation."""
     import torch
-    from tests.test_chroma_loops import synthetic_images as chroma_images
     fam = families(128)
     want = refs(oracle, 256, 128, 1)
     n = len(fam)

@@ -1,37 +1,24 @@
 """Encode to a byte budget (nhw_enc_fit_batch_device / nhw_enc_fit_batch, Encoder.encode_fit*, nhw-enc --max-bytes): for every image the
 file of the first ladder rung whose encode succeeds within the image's budget, identical to the fixed-quality encode at that quality."""
-import ctypes
 import os
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "tools", "nhw-enc")
+from tests.support import CLI, ROOT, built_cli, load_lib, run, same_files
+
 LADDERS = {"default": None, "every4": [20, 16, 12, 8, 4], "q20": [20]}
-
-
-def _run(*a):
-    import subprocess
-    p = subprocess.run([CLI, *a], capture_output=True, text=True, timeout=120)
-    return p.returncode, p.stdout, p.stderr
 
 
 @pytest.fixture(scope="module")
 def cli():
-    import subprocess
-    if not os.path.exists(CLI):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return CLI
+    return built_cli("nhw-enc")
 
 
 # ---------------------------------------------------------------- without a GPU
 def test_library_exports_the_fit_entry_points():
     import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(nhwcodec_amd.LIB_PATH)
+    lib = load_lib()
     for name in ("nhw_enc_fit_batch_device", "nhw_enc_fit_batch", "nhw_enc_last_fit_stats"):
         assert hasattr(lib, name)
     assert nhwcodec_amd.NHW_E_BUDGET == -7
@@ -50,9 +37,9 @@ def test_library_exports_the_fit_entry_points():
 ])
 def test_cli_budget_arguments_fail_before_any_gpu_work(cli, tmp_path, args, msg):
     """(a.bmp does not exist: a run that got as far as reading it would say "Could not open file" and exit 255)"""
-    rc, out, err = _run(*[str(tmp_path / a) if a.endswith((".bmp", ".nhw", ".tar")) else a for a in args])
+    rc, out, err = run(CLI, *[str(tmp_path / a) if a.endswith((".bmp", ".nhw", ".tar")) else a for a in args])
     assert rc == 1 and msg in err and "Could not open" not in out
-    assert "--max-bytes" in _run("-h")[1]
+    assert "--max-bytes" in run(CLI, "-h")[1]
 
 
 # ---------------------------------------------------------------- on the MI355X
@@ -205,12 +192,6 @@ def _fit_on_device_reference(enc, bgr, budget, ladder):
     return e_out, e_sz, e_st, e_q
 
 
-def _same_files(a, b, sizes):
-    import torch
-    mask = torch.arange(a.shape[1], device="cuda")[None, :] < sizes.long()[:, None]
-    return not bool(((a != b) & mask).any())
-
-
 @pytest.mark.gpu
 def test_fit_at_scale_on_a_device_only_handle():
     """1024 images made on the device, n == max_batch, per-image budgets around the q20 sizes (some below every rung), on torch's default
@@ -235,10 +216,10 @@ def test_fit_at_scale_on_a_device_only_handle():
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         assert torch.equal(sz, want[1]) and torch.equal(st, want[2]) and torch.equal(q, want[3])
-        assert _same_files(o, want[0], sz)
+        assert same_files(o, want[0], sz)
     o, s, st = enc.encode_device(bgr, 20)
     torch.cuda.synchronize()
-    assert torch.equal(s, s20) and torch.equal(st, st20) and _same_files(o, o20, s20)
+    assert torch.equal(s, s20) and torch.equal(st, st20) and same_files(o, o20, s20)
     enc.close()
 
 
@@ -261,7 +242,7 @@ def test_cli_batch_to_a_byte_budget(cli, oracle, tmp_path):
     budget = int(least[order[-2]])
     for k, im in enumerate(imgs):
         (tmp_path / f"img{k}.bmp").write_bytes(bmp_bytes(im))
-    rc, out, err = _run("-q20", "--max-bytes", str(budget), "--batch", str(tmp_path))
+    rc, out, err = run(CLI, "-q20", "--max-bytes", str(budget), "--batch", str(tmp_path))
     assert rc == 1
     assert f"img5.nhw: no quality in q20..q1 fits {budget} bytes (q1: " in err
     assert not (tmp_path / "img5.nhw").exists()

@@ -8,25 +8,16 @@ import os
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "tools", "nhw-enc")
+from tests.support import CLI, ROOT, built_cli, load_lib, run, same_files
+
 PEAK = 65025 * 786432
 UINT64_MAX = 2**64 - 1
 LADDERS = {"default": None, "q17_23": list(range(17, 24)), "descending": [23, 20, 17], "q20": [20]}
 
 
-def _run(*a):
-    import subprocess
-    p = subprocess.run([CLI, *a], capture_output=True, text=True, timeout=300)
-    return p.returncode, p.stdout, p.stderr
-
-
 @pytest.fixture(scope="module")
 def cli():
-    import subprocess
-    if not os.path.exists(CLI):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return CLI
+    return built_cli("nhw-enc")
 
 
 def _np_sse(a, b):
@@ -37,11 +28,7 @@ def _np_sse(a, b):
 
 # ---------------------------------------------------------------- without a GPU
 def test_library_exports_the_psnr_entry_points():
-    import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(nhwcodec_amd.LIB_PATH)
+    lib = load_lib()
     for name in ("nhw_sse_batch_device", "nhw_enc_fit_sse_batch_device", "nhw_enc_fit_sse_batch"):
         assert hasattr(lib, name)
     hdr = open(os.path.join(ROOT, "include", "nhw_hip.h")).read()
@@ -81,9 +68,9 @@ def test_psnr_to_max_sse_formula_and_refusals():
 ])
 def test_cli_psnr_arguments_fail_before_any_gpu_work(cli, tmp_path, args, msg):
     """(a.bmp does not exist: a run that got as far as reading it would say "Could not open file" and exit 255)"""
-    rc, out, err = _run(*[str(tmp_path / a) if a.endswith((".bmp", ".nhw", ".tar")) else a for a in args])
+    rc, out, err = run(CLI, *[str(tmp_path / a) if a.endswith((".bmp", ".nhw", ".tar")) else a for a in args])
     assert rc == 1 and msg in err and "Could not open" not in out
-    assert "PSNR (MI355X build): " in _run("-h")[1]
+    assert "PSNR (MI355X build): " in run(CLI, "-h")[1]
 
 
 # ---------------------------------------------------------------- on the MI355X
@@ -407,12 +394,6 @@ def _fit_psnr_on_device_reference(enc, dec, bgr, target, ladder):
     return e_out, e_sz, e_st, e_q, e_sse
 
 
-def _same_files(a, b, sizes):
-    import torch
-    mask = torch.arange(a.shape[1], device="cuda")[None, :] < sizes.long()[:, None]
-    return not bool(((a != b) & mask).any())
-
-
 @pytest.mark.gpu
 def test_fit_psnr_at_scale_on_a_device_only_handle():
     """1024 images made on the device, n == max_batch on both handles, per-image targets spread around the q18 SSE, on torch's default
@@ -443,11 +424,11 @@ def test_fit_psnr_at_scale_on_a_device_only_handle():
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         assert torch.equal(sz, want[1]) and torch.equal(st, want[2]) and torch.equal(q, want[3]) and torch.equal(sse, want[4])
-        assert _same_files(o, want[0], sz)
+        assert same_files(o, want[0], sz)
     o, s, st = enc.encode_device(bgr, 18)
     px, dst, _ = dec.decode_device(o, offs, s)
     torch.cuda.synchronize()
-    assert torch.equal(s, s18) and torch.equal(st, st18) and _same_files(o, o18, s18)
+    assert torch.equal(s, s18) and torch.equal(st, st18) and same_files(o, o18, s18)
     assert torch.equal(dst, dst18) and torch.equal(px, px18)
     dec.close()
     enc.close()
@@ -480,7 +461,7 @@ def test_cli_batch_to_a_psnr_target(cli, oracle, tmp_path):
     assert best[order[-2]] <= bound < best[worst]
     for k, im in enumerate(imgs):
         (tmp_path / f"img{k}.bmp").write_bytes(bmp_bytes(im))
-    rc, out, err = _run("-q20", "--min-psnr", str(db), "--batch", str(tmp_path))
+    rc, out, err = run(CLI, "-q20", "--min-psnr", str(db), "--batch", str(tmp_path))
     assert rc == 1
     assert f"img{worst}.nhw: no quality in q1..q20 reaches" in err
     assert not (tmp_path / f"img{worst}.nhw").exists()

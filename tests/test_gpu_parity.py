@@ -10,18 +10,15 @@ import numpy as np
 import pytest
 
 from oracle.harness import class_image
+from tests.enc_stages import ws_index
+from tests.support import ROOT, load_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 
 # ---------------------------------------------------------------- CPU-side checks of the boundary
 def test_c_abi_exports_every_declared_symbol():
-    import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(nhwcodec_amd.LIB_PATH)      # loading needs no GPU
+    lib = load_lib()                              # loading needs no GPU
     for header, must in (("nhw_hip.h", {"nhw_enc_create", "nhw_enc_batch", "nhw_enc_batch_device", "nhw_enc_destroy"}),
                          ("nhw_hip_debug.h", {"nhw_debug_stop_after", "nhw_debug_read", "nhw_dec_debug_read"})):   # the boundary, and the hooks the tests call
         hdr = open(os.path.join(ROOT, "include", header)).read()
@@ -640,15 +637,6 @@ def _read_ws(e, buf, img, nbytes):
     return out
 
 
-def _ws_index(name):
-    """index of a workspace buffer (nhwcodec_amd/csrc/nhw_ws.h, the B_* list) for nhw_debug_read"""
-    import re
-    txt = open(os.path.join(ROOT, "nhwcodec_amd", "csrc", "nhw_ws.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", txt[txt.index("enum {"):txt.index("B_COUNT")], flags=re.S)
-    names = re.findall(r"B_[A-Z0-9_]+", body)
-    return names.index("B_" + name)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("q", [1, 10, 16, 17, 20, 23])
 def test_symbol_list_equals_the_byte_stream(oracle, q):
@@ -664,7 +652,7 @@ def test_symbol_list_equals_the_byte_stream(oracle, q):
     imgs = np.stack([oracle.synth(7000 + 31 * q + i) for i in range(6)] + [class_image(k, q) for k in ("noise", "blocks", "flat", "gradient", "tiles")])
     e = nhwcodec_amd.Encoder(0, max_batch=len(imgs))
     d_in = torch.from_numpy(imgs).cuda()
-    rd = lambda name, i, nbytes, dt: np.frombuffer(bytes(_read_ws(e, _ws_index(name), i, nbytes)), dt)
+    rd = lambda name, i, nbytes, dt: np.frombuffer(bytes(_read_ws(e, ws_index(name), i, nbytes)), dt)
     luma_stage = 12 if q >= 22 else 13 if q > 12 else 11 if q > 6 else 7       # the stage count behind Y31 (fewer stages where a closed loop is missing)
     try:
         e.lib.nhw_debug_stop_after(e.h, luma_stage)

@@ -6,15 +6,12 @@ one slice per launch, slices ascending (mode 1) or descending (mode 2): a slice 
 (mode 2) writes then sees the written values.  Every check here is against the CPU oracle, byte for byte.  The kernels in the mode and
 the ones that cannot have the hazard: DESIGN.md, "Kernels that split an item".
 """
-import os
 
 import numpy as np
 import pytest
 
 from oracle.harness import class_image
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden", "dec")
+from tests.support import golden, golden_names
 
 # k_low_apply used to re-read the last row of the band above for its entry tail-rules flag, a row that band rewrites in the same launch.
 # In mode 1 that read sees the rewritten row; it changes the flag only where the pair machine's answer for pair 254 of that row rewrites
@@ -117,8 +114,8 @@ def test_encoder_forced_order_matches_oracle(enc, imgs, want, q, mode):
 @pytest.mark.parametrize("mode", MODES)
 def test_decoder_forced_order_goldens(dec, oracle, mode):
     """the committed reference-encoder files, every quality, in one batch (not a multiple of 8)"""
-    names = sorted(f for f in os.listdir(GOLD) if f.endswith(".nhw"))
-    files = [open(os.path.join(GOLD, f), "rb").read() for f in names]
+    names = golden_names()
+    files = [golden(f) for f in names]
     assert len({int(f[1:3]) for f in names}) == 23
     px, qs = _decode(dec, files, mode)
     for i, f in enumerate(files):

@@ -7,7 +7,7 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
 SRC = os.path.join(ROOT, "tests", "low_machine")
 
 

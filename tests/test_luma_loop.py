@@ -10,29 +10,13 @@ before each form (nhw_debug_write):
     (threshold_planes); form 0 against form 3 on low-amplitude LL1 blocks whose level-2 details sit at 2 .. 4 along the block's borders;
   * the files of whole production batches with the oracle's.
 The CPU part walks ana_row_quad's lane arrangement (four cells a lane) against the line filter it stands for."""
-import ctypes
-import os
-import re
-from concurrent.futures import ProcessPoolExecutor
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-Q = 65536
+from tests.enc_stages import B_LL1, N_IMAGES, Q, Hook, compare, oracle_files, synthetic_images
+
 QUALITIES = (7, 10, 12, 13, 14, 16, 17, 18, 20, 21, 22, 23)
-N_IMAGES = 64
 PATTERN = (-4, -3, 4, 3)    # a row of these differences hands a change of the incoming step on from cell to cell to its end (asserted below)
-
-
-def _ws_index(name):
-    txt = open(os.path.join(ROOT, "nhwcodec_amd", "csrc", "nhw_ws.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", txt[txt.index("enum {"):txt.index("B_COUNT")], flags=re.S)
-    return re.findall(r"B_[A-Z0-9_]+", body).index("B_" + name)
-
-
-B_JPEG, B_PROC, B_LL1, B_L2SAVE = (_ws_index(n) for n in ("JPEG", "PROC", "LL1", "L2SAVE"))
-PLANES = (("jpeg", B_JPEG, 8 * Q), ("proc", B_PROC, 8 * Q), ("ll1 + the cell behind", B_LL1, 2 * Q + 2), ("l2save", B_L2SAVE, 2 * Q))
 
 
 # ---------------------------------------------------------------------------------------------- the rules, as the reference states them
@@ -157,66 +141,7 @@ def test_pattern_row_hands_a_step_on_to_its_end():
     assert lane_rounds(d[0], 0, 0) > 32                          # (handed 3, every lane's guess is right at once)
 
 
-# ---------------------------------------------------------------------------------------------- GPU part
-def _want(args):
-    from oracle.oraclepy import Oracle
-    q, compat, imgs = args
-    o = Oracle()
-    o.set_oob_mode(bool(compat))
-    try:
-        return [o.encode(im, q) for im in imgs]
-    finally:
-        o.set_oob_mode(False)
-
-
-def oracle_files(imgs, q, compat=False):
-    step = 4
-    with ProcessPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as ex:
-        return [f for part in ex.map(_want, [(q, compat, imgs[i:i + step]) for i in range(0, len(imgs), step)]) for f in part]
-
-
-def synthetic_images(q, n=N_IMAGES):
-    from oracle.oraclepy import Oracle
-    o = Oracle()
-    return np.stack([o.synth(61000 + 89 * q + i) for i in range(n)])
-
-
-class Hook:
-    def __init__(self, n):
-        import nhwcodec_amd
-        self.n = n
-        self.e = nhwcodec_amd.Encoder(0, max_batch=n)
-
-    def read(self, buf, i, nbytes):
-        out = np.empty(nbytes, np.uint8)
-        assert self.e.lib.nhw_debug_read(self.e.h, buf, i, ctypes.c_void_p(out.ctypes.data), ctypes.c_size_t(nbytes)) == 0
-        return out.view(np.int16)
-
-    def write(self, buf, i, a):
-        a = np.ascontiguousarray(a)
-        assert self.e.lib.nhw_debug_write(self.e.h, buf, i, ctypes.c_void_p(a.ctypes.data), ctypes.c_size_t(a.nbytes)) == 0
-
-    def planes(self):
-        return [[self.read(buf, i, nbytes) for _, buf, nbytes in PLANES] for i in range(self.n)]
-
-    def run(self, form, inputs):
-        """inputs: per image (jpeg, proc, ll1, l2save) as int16 arrays, written before the launches"""
-        import torch
-        for i, planes in enumerate(inputs):
-            for (_, buf, nbytes), a in zip(PLANES, planes):
-                self.write(buf, i, a.ravel()[:min(a.size, nbytes // 2 if buf != B_LL1 else Q)])   # (the cell behind ll1 is left as it stands)
-        assert self.e.lib.nhw_stage_luma_loop(self.e.h, self.n, form, None) == 0, "nhw_stage_luma_loop"
-        torch.cuda.synchronize()
-        return self.planes()
-
-
-def compare(tag, got, want):
-    for i, (g, w) in enumerate(zip(got, want)):
-        for (name, _, _), a, b in zip(PLANES, g, w):
-            bad = np.flatnonzero(a != b)
-            assert bad.size == 0, f"{tag} image {i} {name}: {bad.size} cells differ, first {bad[:8].tolist()}"
-
-
+# ---------------------------------------------------------------------------------------------- GPU part (the hook: tests/enc_stages.py)
 def check_case(imgs, q, compat=False):
     n = len(imgs)
     h = Hook(n)

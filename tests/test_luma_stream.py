@@ -19,12 +19,12 @@ import sys
 import numpy as np
 import pytest
 
-from tests.test_luma_loop import B_JPEG, B_L2SAVE, B_PROC, Q, Hook, _ws_index, oracle_files
+from tests.enc_stages import B_JPEG, B_L2SAVE, B_PROC, Q, Hook, oracle_files, ws_index
+from tests.support import ROOT
 
-B_LLMEM, B_META = _ws_index("LLMEM"), _ws_index("META")
+B_LLMEM, B_META = ws_index("LLMEM"), ws_index("META")
 META_LL_MEM_LEN = 18                               # NhwMeta::ll_mem_len as an int index (nhw_ws.h: two lengths, four NhwPosLens, four more lengths in front of it)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QUALITIES = (7, 12, 13, 14, 17, 18, 20, 21, 23)    # Y5 from 7, k_l2_recon<true> from 13, Y16's fork from 14, the bump walk from 18, the lists fork up to 20, Y29 from 22
 BATCHES = (1, 5, 64)                               # 5: a partly filled four-image workgroup of the wavefront-per-image kernels
 WALK_QUALITIES = (13, 18, 20, 23)

@@ -9,9 +9,9 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_pictures import _views, pad_reference, parse_container
+from tests.picture_cases import np_picture_sse, pad_reference, padding_mask, parse_container, picture_views
+from tests.support import ROOT, load_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UINT64_MAX = 2**64 - 1
 NEW_SYMBOLS = ("nhw_sse_pictures_device", "nhw_enc_fit_pictures", "nhw_enc_fit_sse_pictures")
 DEFAULT_BYTES = list(range(23, 0, -1))
@@ -22,10 +22,7 @@ LADDERS = {"default": None, "short": [20, 15, 10, 5], "one": [17], "non_monotone
 # ---------------------------------------------------------------- without a GPU
 def test_picture_fit_symbols_and_prototypes():
     import nhwcodec_amd as na
-    if not os.path.exists(na.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(na.LIB_PATH)
+    lib = load_lib()
     for name in NEW_SYMBOLS:
         assert hasattr(lib, name), name
     hdr = " ".join(open(os.path.join(ROOT, "include", "nhw_hip.h")).read().split())
@@ -76,30 +73,12 @@ SSE_SPECS = ([(1, 1, 0, 0), (1, 700, 0, 1), (700, 1, 5, 3), (511, 513, 0, 2), (5
              + [(149 + 11 * r, 3 + r, 9 if r % 2 else 0, r % 4) for r in range(16)])          # 3W mod 16 takes every residue, every alignment
 
 
-def _np_picture_sse(tiles, pic):
-    """the SSE of a picture's decoded tiles [T, 512, 512, 3], joined and cropped, against the picture"""
-    h, w = pic.shape[:2]
-    ny, nx = -(-h // 512), -(-w // 512)
-    full = tiles.reshape(ny, nx, 512, 512, 3).transpose(0, 2, 1, 3, 4).reshape(512 * ny, 512 * nx, 3)[:h, :w]
-    d = full.astype(np.int64) - pic.astype(np.int64)
-    return int((d * d).sum())
-
-
-def _padding_mask(pic_shape):
-    """True on the padded bytes of a picture's tiles [T, 512, 512, 3]"""
-    h, w = pic_shape[:2]
-    ny, nx = -(-h // 512), -(-w // 512)
-    m = np.ones((512 * ny, 512 * nx, 3), bool)
-    m[:h, :w] = False
-    return np.ascontiguousarray(m.reshape(ny, 512, nx, 512, 3).transpose(0, 2, 1, 3, 4)).reshape(ny * nx, 512, 512, 3)
-
-
 @pytest.mark.gpu
 def test_sse_pictures_device_matches_numpy():
     import nhwcodec_amd as na
     import torch
     assert sorted({(3 * w) % 16 for w, *_ in SSE_SPECS}) == list(range(16))
-    buf, views = _views(SSE_SPECS, seed=5)
+    buf, views = picture_views(SSE_SPECS, seed=5)
     pics = [v.cpu().numpy() for v in views]
     counts = [na.picture_tiles(p.shape[1], p.shape[0]) for p in pics]
     bounds = np.concatenate([[0], np.cumsum(counts)])
@@ -108,7 +87,7 @@ def test_sse_pictures_device_matches_numpy():
     padded = na.tile_pictures_device(views).cpu().numpy()
     noisy = padded.copy()
     for k, p in enumerate(pics):
-        m = _padding_mask(p.shape)
+        m = padding_mask(p.shape)
         part = noisy[bounds[k]:bounds[k + 1]]
         part[m] = rng.integers(0, 256, int(m.sum()), dtype=np.uint8)
     assert (noisy != padded).any()
@@ -117,7 +96,7 @@ def test_sse_pictures_device_matches_numpy():
     assert got.dtype == torch.int64 and got.cpu().tolist() == [0] * len(views)
     # random tiles: the numpy SSE over each crop
     rand = rng.integers(0, 256, padded.shape, dtype=np.uint8)
-    want = [_np_picture_sse(rand[bounds[k]:bounds[k + 1]], p) for k, p in enumerate(pics)]
+    want = [np_picture_sse(rand[bounds[k]:bounds[k + 1]], p) for k, p in enumerate(pics)]
     assert max(want) > 2**32                                          # beyond 32 bits: the 64-bit sums are needed
     d_rand = torch.from_numpy(rand).cuda()
     got = na.sse_pictures_device(d_rand, views)

@@ -15,9 +15,8 @@ import bisect
 import numpy as np
 import pytest
 
-from tests.test_picture_fit import _np_picture_sse, _padding_mask
-from tests.test_pictures import SPECS, _views, pad_reference, parse_container
-from tests.test_regions import CANARY, _dest_views, selected
+from tests.picture_cases import SPECS, dest_views, np_picture_sse, pad_reference, padding_mask, parse_container, picture_views, selected
+from tests.support import CANARY
 
 FILL = 7
 PERIOD = 11                                                          # global tile t is given the bytes of random tile t % PERIOD
@@ -114,7 +113,7 @@ def region_rects(n):
 
 
 def _region_counts(rects):
-    return np.array([len(selected(1024, *r)) for r in rects], np.int64)
+    return np.array([len(selected(1024, 1, *r)) for r in rects], np.int64)
 
 
 def _check_model(first, counts, reached):
@@ -210,13 +209,13 @@ def pool():
     """the 32 source pictures on the device, their numpy copies, their padded tiles by pad_reference (host and device) and padding masks"""
     import torch
     p = Pool()
-    p.buf, p.views = _views(POOL, seed=21)
+    p.buf, p.views = picture_views(POOL, seed=21)
     p.pics = [v.cpu().numpy() for v in p.views]
     ref = [pad_reference(a) for a in p.pics]
     p.first = _first([len(r) for r in ref])
     p.ref = np.concatenate(ref)
     p.ref_dev = torch.from_numpy(p.ref).cuda()
-    p.padding = np.concatenate([_padding_mask(a.shape) for a in p.pics])
+    p.padding = np.concatenate([padding_mask(a.shape) for a in p.pics])
     assert len({a.tobytes() for a in p.pics}) == 32
     return p
 
@@ -283,7 +282,7 @@ def test_untile_crop_finds_its_picture_in_a_big_table(side):
     counts = np.array([_tiles(w, h, side) for w, h in shapes], np.int64)
     first = _first(counts)
     fl, total = first.tolist(), int(first[-1] + counts[-1])
-    buf, views = _dest_views(shapes)
+    buf, views = dest_views(shapes)
     d_table = _upload(_picture_table(views, first))
     rand, d_rand = _random_tiles(side, 3)
     exp = np.full(buf.numel(), CANARY, np.uint8)
@@ -357,7 +356,7 @@ def _launch_regions(lib, d_table, n, rects, fl, total, views, buf, exp, d_pic_ti
             sel.append(3 - u % 2)                                    # nobody's tile: any bytes
             continue
         x, y, w, h = rects[k]
-        tile = selected(1024, x, y, w, h)[u - fl[k]]
+        tile = selected(1024, 1, x, y, w, h, coords=False)[u - fl[k]]
         sel.append(tile)
         ty, tx = divmod(tile, 2)
         r0, r1, c0, c1 = max(512 * ty, y), min(512 * ty + 512, y + h), max(512 * tx, x), min(512 * tx + 512, x + w)
@@ -377,7 +376,7 @@ def test_untile_region_finds_its_region_in_a_big_table(n):
     counts = _region_counts(rects)
     first = _first(counts)
     fl, total = first.tolist(), int(first[-1] + counts[-1])
-    buf, views = _dest_views([(w, h) for _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, w, h in rects])
     d_table = _upload(_region_table(rects, views, first))
     pic_tiles = np.random.default_rng(5).integers(0, 256, (4, 512, 512, 3), dtype=np.uint8)
     d_pic_tiles = torch.from_numpy(pic_tiles).cuda()
@@ -523,7 +522,7 @@ def test_tile_pad_and_sse_crop_leave_the_tiles_nobody_owns():
     import nhwcodec_amd as na
     import torch
     lib = na._library()
-    _, views = _views(RANGE_SPECS, seed=8)
+    _, views = picture_views(RANGE_SPECS, seed=8)
     pics = [v.cpu().numpy() for v in views]
     ref = [pad_reference(p) for p in pics]
     counts = [len(r) for r in ref]
@@ -542,7 +541,7 @@ def test_tile_pad_and_sse_crop_leave_the_tiles_nobody_owns():
     assert lib.nhw_sse_pictures_device(d_rand.data_ptr(), d_table.data_ptr(), 3, 0, tiles + 5, acc[0].data_ptr(), None) == 0
     assert lib.nhw_sse_pictures_device(d_rand.data_ptr() + 3 * na.IMG_BYTES, d_table.data_ptr(), 3, 3, tiles, acc[1].data_ptr(), None) == 0
     bounds = 3 + np.concatenate([[0], np.cumsum(counts)])
-    want = [_np_picture_sse(rand[bounds[k]:bounds[k + 1]], p) for k, p in enumerate(pics)]
+    want = [np_picture_sse(rand[bounds[k]:bounds[k + 1]], p) for k, p in enumerate(pics)]
     assert acc.cpu().tolist() == [want, want]
 
 
@@ -552,7 +551,7 @@ def test_untile_crop_leaves_the_tiles_nobody_owns(side):
     import nhwcodec_amd as na
     import torch
     lib = na._library()
-    buf, views = _views(RANGE_SPECS, seed=10)
+    buf, views = picture_views(RANGE_SPECS, seed=10)
     buf.fill_(CANARY)
     counts = [_tiles(w, h, side) for w, h, *_ in RANGE_SPECS]
     tiles = sum(counts)
@@ -578,7 +577,7 @@ def test_untile_region_leaves_the_tiles_nobody_owns():
     assert counts.tolist() == [4, 1, 2, 1]
     first = 3 + _first(counts)
     fl, total = first.tolist(), int(first[-1] + counts[-1])
-    buf, views = _dest_views([(w, h) for _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, w, h in rects])
     d_table = _upload(_region_table(rects, views, first))
     pic_tiles = np.random.default_rng(12).integers(0, 256, (4, 512, 512, 3), dtype=np.uint8)
     d_pic_tiles = torch.from_numpy(pic_tiles).cuda()
@@ -603,7 +602,7 @@ def test_an_empty_picture_entry_is_passed_over(zero):
     import torch
     lib = na._library()
     first = [0, 1, 1, 2]
-    _, src = _views(EMPTY_SPECS, seed=13)
+    _, src = picture_views(EMPTY_SPECS, seed=13)
     table = _picture_table(src, first)
     table[zero][1] = 0
     d_table = _upload(table)
@@ -617,11 +616,11 @@ def test_an_empty_picture_entry_is_passed_over(zero):
     d_rand = torch.from_numpy(rand).cuda()
     acc = torch.zeros(4, dtype=torch.int64, device="cuda")
     assert lib.nhw_sse_pictures_device(d_rand.data_ptr(), d_table.data_ptr(), 4, 0, 4, acc.data_ptr(), None) == 0
-    want = [_np_picture_sse(rand[0:1], src[0].cpu().numpy()), 0, _np_picture_sse(rand[1:2], src[2].cpu().numpy()),
-            _np_picture_sse(rand[2:4], src[3].cpu().numpy())]
+    want = [np_picture_sse(rand[0:1], src[0].cpu().numpy()), 0, np_picture_sse(rand[1:2], src[2].cpu().numpy()),
+            np_picture_sse(rand[2:4], src[3].cpu().numpy())]
     assert acc.cpu().tolist() == want and min(want[0], want[2], want[3]) > 0
     # the inverse, the empty entry's address inside the canary
-    buf, dst = _views(EMPTY_SPECS, seed=15)
+    buf, dst = picture_views(EMPTY_SPECS, seed=15)
     buf.fill_(CANARY)
     table = _picture_table(dst, first)
     table[zero][1] = 0
@@ -641,7 +640,7 @@ def test_an_empty_region_entry_is_passed_over():
     lib = na._library()
     rects = [(5, 7, 8, 8), (100, 100, 6, 3), (100, 100, 6, 3), (511, 100, 2, 3)]
     first = [0, 1, 1, 2]
-    buf, views = _dest_views([(w, h) for _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, w, h in rects])
     table = _region_table(rects, views, first)
     table["width"][1] = 0
     d_table = _upload(table)
@@ -667,7 +666,7 @@ def test_sides_of_65535(spec):
     import torch
     w, h = spec[:2]
     rng = np.random.default_rng(17)
-    _, (src,) = _views([spec], seed=18)
+    _, (src,) = picture_views([spec], seed=18)
     pic = src.cpu().numpy()
     tiles = na.tile_pictures_device([src])
     want = torch.from_numpy(pad_reference(pic)).cuda()
@@ -675,7 +674,7 @@ def test_sides_of_65535(spec):
     assert torch.equal(tiles, want), [t for t in range(128) if not torch.equal(tiles[t], want[t])]
     del want
     # back into a canary copy of the layout
-    buf, (dst,) = _views([spec], seed=19)
+    buf, (dst,) = picture_views([spec], seed=19)
     buf.fill_(CANARY)
     na.untile_pictures_device(tiles, [dst])
     exp = np.full(buf.numel(), CANARY, np.uint8)
@@ -686,7 +685,7 @@ def test_sides_of_65535(spec):
     low = rng.integers(0, 32, pic.shape, dtype=np.uint8)
     src.copy_(torch.from_numpy(low).cuda())
     rand = rng.integers(200, 256, (128, 512, 512, 3), dtype=np.uint8)
-    sse = _np_picture_sse(rand, low)
+    sse = np_picture_sse(rand, low)
     assert sse > 2**32
     assert na.sse_pictures_device(torch.from_numpy(rand).cuda(), [src]).cpu().tolist() == [sse]
     del rand
@@ -695,7 +694,7 @@ def test_sides_of_65535(spec):
         side = 512 // scale
         ws, hs = na.scaled_size(w, h, scale)
         assert _tiles(ws, hs, side) == 128
-        buf, (dst,) = _views([(ws, hs, spec[2], spec[3])], seed=20)
+        buf, (dst,) = picture_views([(ws, hs, spec[2], spec[3])], seed=20)
         buf.fill_(CANARY)
         rand = rng.integers(0, 256, (128, side, side, 3), dtype=np.uint8)
         na.untile_scaled_pictures_device(torch.from_numpy(rand).cuda(), [dst], scale)
@@ -736,7 +735,7 @@ def test_row_offsets_past_4_gib():
     d_rand = torch.from_numpy(rand).cuda()
     acc = torch.zeros(1, dtype=torch.int64, device="cuda")
     assert lib.nhw_sse_pictures_device(d_rand.data_ptr(), d_table.data_ptr(), 1, 0, 1, acc.data_ptr(), None) == 0
-    assert acc.cpu().tolist() == [_np_picture_sse(rand, pic)]
+    assert acc.cpu().tolist() == [np_picture_sse(rand, pic)]
     # untile: the picture's rows, and the 16 bytes on either side of each as they were
     around = rng.integers(0, 256, (h, 3 * w + 32), dtype=np.uint8)
     around[:, 16:16 + 3 * w] = CANARY

@@ -5,64 +5,26 @@ the padded tile."""
 import ctypes
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "tools", "nhw-enc")
-DEC_CLI = os.path.join(ROOT, "tools", "nhw-dec")
+from tests.picture_cases import SPECS, make_container, pad_reference, parse_container, picture_views
+from tests.support import DEC_CLI, ROOT, built_cli, load_lib, run
+
 NEW_SYMBOLS = ("nhw_picture_tiles", "nhw_tile_pictures_device", "nhw_untile_pictures_device", "nhw_picture_info", "nhw_enc_pictures",
                "nhw_dec_pictures")
 
 
-def pad_reference(pic):
-    """the padding rule in numpy: edge replication to whole tiles, then tile_images' cut -> [ny * nx, 512, 512, 3]"""
-    h, w = pic.shape[:2]
-    ny, nx = -(-h // 512), -(-w // 512)
-    big = np.pad(pic, ((0, 512 * ny - h), (0, 512 * nx - w), (0, 0)), mode="edge")
-    return np.ascontiguousarray(big.reshape(ny, 512, nx, 512, 3).transpose(0, 2, 1, 3, 4)).reshape(ny * nx, 512, 512, 3)
-
-
-def parse_container(c):
-    """the test's own reading of a .nhwp container -> (W, H, [tile files])"""
-    assert c[:8] == b"NHWP\x01\x00\x00\x00"
-    w, h = struct.unpack_from("<II", c, 8)
-    t = (-(-w // 512)) * (-(-h // 512))
-    lens = struct.unpack_from(f"<{t}I", c, 16)
-    files, at = [], 16 + 4 * t
-    for n in lens:
-        files.append(bytes(c[at:at + n]))
-        at += n
-    assert at == len(c)
-    return w, h, files
-
-
-def make_container(w, h, files, version=1, reserved=b"\0\0\0", magic=b"NHWP", lens=None):
-    lens = [len(f) for f in files] if lens is None else lens
-    return magic + bytes([version]) + reserved + struct.pack("<II", w, h) + struct.pack(f"<{len(lens)}I", *lens) + b"".join(files)
-
-
-def _run(exe, *a):
-    p = subprocess.run([exe, *a], capture_output=True, text=True, timeout=300)
-    return p.returncode, p.stdout, p.stderr
-
-
 @pytest.fixture(scope="module")
 def lib():
-    import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return ctypes.CDLL(nhwcodec_amd.LIB_PATH)
+    return load_lib()
 
 
 @pytest.fixture(scope="module")
 def cli():
-    if not (os.path.exists(CLI) and os.path.exists(DEC_CLI)):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return CLI
+    built_cli("nhw-dec")
+    return built_cli("nhw-enc")
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -143,43 +105,24 @@ def test_padding_reference_equals_tile_images_for_multiples_of_512():
                                   ["--tar"], ["--tiles"], ["--batch", "somedir"]])
 def test_cli_picture_refuses_other_modes_before_any_gpu_work(cli, tmp_path, args):
     """(a.bmp does not exist: a run that got as far as reading it would say "Could not open file" and exit 255)"""
-    rc, out, err = _run(cli, "--picture", *args, str(tmp_path / "a.bmp"), str(tmp_path / "b.nhwp"))
+    rc, out, err = run(cli, "--picture", *args, str(tmp_path / "a.bmp"), str(tmp_path / "b.nhwp"))
     assert rc == 1 and "--picture works alone" in err and "Could not open" not in out
-    assert "--picture" in _run(cli, "-h")[1] and "--picture" in _run(DEC_CLI)[1]
+    assert "--picture" in run(cli, "-h")[1] and "--picture" in run(DEC_CLI)[1]
 
 
 def test_cli_dec_picture_refuses_a_file_that_is_no_container(cli, tmp_path):
     (tmp_path / "x.nhwp").write_bytes(MALFORMED["over-long"])
-    rc, out, _ = _run(DEC_CLI, "--picture", str(tmp_path / "x.nhwp"), str(tmp_path / "x.bmp"))
+    rc, out, _ = run(DEC_CLI, "--picture", str(tmp_path / "x.nhwp"), str(tmp_path / "x.bmp"))
     assert rc == 3 and "Not an .nhwp file" in out and not (tmp_path / "x.bmp").exists()
 
 
 # ---------------------------------------------------------------- on the MI355X
-def _views(specs, seed=0):
-    """pictures as uint8 CUDA views [H, W, 3] into one byte buffer: spec (W, H, pitch extra, byte misalignment of addr)"""
-    import torch
-    rng = np.random.default_rng(seed)
-    at, offs = 256, []
-    for w, h, extra, mis in specs:
-        at = (at + 255) // 256 * 256 + mis
-        offs.append(at)
-        at += (3 * w + extra) * h + 64
-    buf = torch.from_numpy(rng.integers(0, 256, at + 256, dtype=np.uint8)).cuda()
-    views = [buf.as_strided((h, w, 3), (3 * w + extra, 3, 1), o) for (w, h, extra, _), o in zip(specs, offs)]
-    return buf, views
-
-
-SPECS = ([(1, 1, 0, 0), (1, 700, 0, 1), (700, 1, 5, 3), (511, 513, 0, 2), (513, 511, 16, 1), (512, 512, 0, 0), (1023, 1025, 7, 0),
-          (1920, 1080, 0, 1)]
-         + [(149 + 11 * r, 3 + r, 9 if r % 2 else 0, r % 4) for r in range(16)])          # 3W mod 16 takes every residue
-
-
 @pytest.mark.gpu
 def test_tile_pad_matches_the_padding_rule():
     import nhwcodec_amd as na
     import torch
     assert sorted({(3 * w) % 16 for w, *_ in SPECS}) == list(range(16))
-    buf, views = _views(SPECS)
+    buf, views = picture_views(SPECS)
     want = np.concatenate([pad_reference(v.cpu().numpy()) for v in views])
     got = na.tile_pictures_device(views)                            # every picture of mixed sizes in one call
     torch.cuda.synchronize()
@@ -209,9 +152,9 @@ def test_tile_pad_matches_the_padding_rule():
 def test_untile_inverts_tile_and_writes_only_the_pictures():
     import nhwcodec_amd as na
     import torch
-    src_buf, src = _views(SPECS, seed=1)
+    src_buf, src = picture_views(SPECS, seed=1)
     tiles = na.tile_pictures_device(src)
-    dst_buf, dst = _views(SPECS, seed=2)                            # same layout: pitch gaps and slack between pictures
+    dst_buf, dst = picture_views(SPECS, seed=2)                    # same layout: pitch gaps and slack between pictures
     dst_buf.fill_(0xA5)
     na.untile_pictures_device(tiles, dst)
     torch.cuda.synchronize()
@@ -321,11 +264,11 @@ def test_cli_picture_round_trip(cli, oracle, tmp_path):
     want = np.concatenate([oracle.decode(f)[0] for f in files], axis=1)[:301, :517]
     for top_down in (False, True):
         (tmp_path / "p.bmp").write_bytes(_bmp(pic, top_down))
-        rc, out, err = _run(cli, "-q20", "--picture", str(tmp_path / "p.bmp"), str(tmp_path / "p.nhwp"))
+        rc, out, err = run(cli, "-q20", "--picture", str(tmp_path / "p.bmp"), str(tmp_path / "p.nhwp"))
         assert rc == 0 and "517 x 301" in out, err
         c = (tmp_path / "p.nhwp").read_bytes()
         assert parse_container(c) == (517, 301, files)
-        rc, out, err = _run(DEC_CLI, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "o.bmp"))
+        rc, out, err = run(DEC_CLI, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "o.bmp"))
         assert rc == 0, err
         b = (tmp_path / "o.bmp").read_bytes()
         stride = (3 * 517 + 3) & ~3

@@ -18,9 +18,9 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_luma_loop import B_L2SAVE, B_PROC, Q, _ws_index, oracle_files
+from tests.enc_stages import B_L2SAVE, B_PROC, Q, oracle_files, ws_index
 
-B_KMAP, B_NZQ, B_VALS = _ws_index("KMAP"), _ws_index("NZQ"), _ws_index("VALS")
+B_KMAP, B_NZQ, B_VALS = ws_index("KMAP"), ws_index("NZQ"), ws_index("VALS")
 HOOK_QUALITIES = (17, 20, 23)
 FILE_QUALITIES = (17, 18, 20, 21, 22, 23)
 N_FILES, N_DENSE = 64, 16

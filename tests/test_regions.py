@@ -6,13 +6,14 @@ import ctypes
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEC_CLI = os.path.join(ROOT, "tools", "nhw-dec")
+from tests.picture_cases import (SPECS, Rect, Region, World, check_host_result, dest_views, expected_stats, fixed_rects, make_container,
+                                 parse_container, picture_views, random_rects, selected, views_mask)
+from tests.support import CANARY, ROOT, built_cli, load_lib, run
+
 NEW_SYMBOLS = ("nhw_region_tiles", "nhw_untile_regions_device", "nhw_dec_regions", "nhw_dec_regions_to_device", "nhw_dec_last_region_stats")
 PROTOTYPES = """
 typedef struct { uint64_t addr, pitch; uint32_t x, y, width, height, pic_width, pic_height, first_tile, reserved; } nhw_region;
@@ -26,61 +27,16 @@ int nhw_dec_regions_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *o
 int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded);
 """
 NHW_E_ARG, NHW_E_FORMAT = -4, -6
-CANARY = 0xA5
-
-
-class Region(ctypes.Structure):                                   # the tests' own mirror of nhw_region
-    _fields_ = [("addr", ctypes.c_uint64), ("pitch", ctypes.c_uint64)] + [(n, ctypes.c_uint32) for n in
-                ("x", "y", "width", "height", "pic_width", "pic_height", "first_tile", "reserved")]
-
-
-class Rect(ctypes.Structure):                                     # ... and of nhw_rect
-    _fields_ = [(n, ctypes.c_uint32) for n in ("container", "x", "y", "width", "height")]
-
-
-def _run(exe, *a):
-    p = subprocess.run([exe, *a], capture_output=True, text=True, timeout=300)
-    return p.returncode, p.stdout, p.stderr
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return ctypes.CDLL(nhwcodec_amd.LIB_PATH)
+    return load_lib()
 
 
 @pytest.fixture(scope="module")
 def cli():
-    if not os.path.exists(DEC_CLI):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return DEC_CLI
-
-
-def parse_container(c):
-    """the test's own reading of a .nhwp container -> (W, H, [tile files])"""
-    assert c[:8] == b"NHWP\x01\x00\x00\x00"
-    w, h = struct.unpack_from("<II", c, 8)
-    t = (-(-w // 512)) * (-(-h // 512))
-    lens = struct.unpack_from(f"<{t}I", c, 16)
-    files, at = [], 16 + 4 * t
-    for n in lens:
-        files.append(bytes(c[at:at + n]))
-        at += n
-    assert at == len(c)
-    return w, h, files
-
-
-def make_container(w, h, files):
-    return b"NHWP\x01\0\0\0" + struct.pack("<II", w, h) + struct.pack(f"<{len(files)}I", *[len(f) for f in files]) + b"".join(files)
-
-
-def selected(w, x, y, rw, rh):
-    """the tiles a region selects, row-major: the rule of section 13 in the test's own words"""
-    nx = -(-w // 512)
-    return [ty * nx + tx for ty in range(y // 512, (y + rh - 1) // 512 + 1) for tx in range(x // 512, (x + rw - 1) // 512 + 1)]
+    return built_cli("nhw-dec")
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -126,7 +82,7 @@ def test_region_tiles_counts(lib, args, want):
     lib.nhw_region_tiles.argtypes = [ctypes.c_uint32] * 6
     assert lib.nhw_region_tiles(*args) == want
     if want > 0:
-        assert na.region_tiles(*args) == want == len(selected(args[0], *args[2:]))
+        assert na.region_tiles(*args) == want == len(selected(args[0], 1, *args[2:]))
         if args[2:] == (0, 0) + args[:2]:
             assert want == na.picture_tiles(*args[:2])
     else:
@@ -138,7 +94,7 @@ def test_region_tiles_counts(lib, args, want):
                                   ["--region", "1,2,3,4,5"], ["--region", "1,2,3,4 "], ["--region", "1,,3,4"], ["--region", "1,2,3,4", "more"]])
 def test_cli_region_refuses_a_malformed_argument(cli, tmp_path, tail):
     """(a does not exist: a run that got as far as reading it would say "Could not open file")"""
-    rc, out, err = _run(cli, "--picture", str(tmp_path / "a"), str(tmp_path / "b"), *tail)
+    rc, out, err = run(cli, "--picture", str(tmp_path / "a"), str(tmp_path / "b"), *tail)
     assert rc == 1 and "--region" in err and len(err.strip().splitlines()) == 1 and "Could not open" not in out
     assert not (tmp_path / "b").exists()
 
@@ -146,16 +102,16 @@ def test_cli_region_refuses_a_malformed_argument(cli, tmp_path, tail):
 def test_cli_region_needs_picture(cli, tmp_path):
     for args in (["a.nhw", "b.bmp", "--region", "0,0,1,1"], ["--region", "0,0,1,1", "a.nhw", "b.bmp"], ["--batch", "dir", "--region", "0,0,1,1"],
                  ["--region", "0,0,1,1"]):
-        rc, out, err = _run(cli, *[str(tmp_path / a) if not a.startswith("-") and "," not in a else a for a in args])
+        rc, out, err = run(cli, *[str(tmp_path / a) if not a.startswith("-") and "," not in a else a for a in args])
         assert rc == 1 and "--picture" in err and "Could not open" not in out, args
-    assert "--region" in _run(cli)[1]                                # the usage text names it
+    assert "--region" in run(cli)[1]                                # the usage text names it
 
 
 def test_cli_region_outside_the_picture_is_refused_before_any_gpu_work(cli, tmp_path):
     """a well-formed container of two files that are no .nhw files: a run that reached the decoder would not exit 1"""
     (tmp_path / "p.nhwp").write_bytes(make_container(700, 300, [b"\x02abc", b"\x03de"]))
     for reg in ("0,0,701,1", "700,0,1,1", "0,300,1,1", "0,299,1,2", "0,0,0,1", "0,0,1,0", "4294967295,0,2,1"):
-        rc, out, err = _run(cli, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "o.bmp"), "--region", reg)
+        rc, out, err = run(cli, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "o.bmp"), "--region", reg)
         assert rc == 1 and "--region" in err and len(err.strip().splitlines()) == 1, reg
         assert not (tmp_path / "o.bmp").exists()
 
@@ -163,10 +119,6 @@ def test_cli_region_outside_the_picture_is_refused_before_any_gpu_work(cli, tmp_
 # ---------------------------------------------------------------- on the MI355X
 SIZES = [(1, 700), (500, 375), (1023, 1025), (1920, 1080), (2600, 1600)]          # W, H
 QUALITIES = (10, 20)                                                                # one <= 16, one >= 17
-
-
-class World:
-    pass
 
 
 @pytest.fixture(scope="module")
@@ -188,48 +140,6 @@ def world():
     w.dec.close()
 
 
-def fixed_rects(W, H):
-    """the whole picture; each corner pixel; a rect inside one tile; x = 511, w = 2; 2 x 2 on a four-tile corner; exactly one tile; one
-    full-width row; one full-height column -- those of them the picture is large enough for"""
-    r = [(0, 0, W, H), (0, 0, 1, 1), (W - 1, 0, 1, 1), (0, H - 1, 1, 1), (W - 1, H - 1, 1, 1),
-         (min(3, W - 1), min(5, H - 1), min(W - min(3, W - 1), 200), min(H - min(5, H - 1), 100)), (0, H // 2, W, 1), (W // 2, 0, 1, H)]
-    if W >= 513:
-        r.append((511, min(9, H - 1), 2, min(7, H - min(9, H - 1))))
-    if W >= 513 and H >= 513:
-        r.append((511, 511, 2, 2))
-    if W >= 512 and H >= 512:
-        r.append((0, 0, 512, 512))
-    if W >= 1024 and H >= 1024:
-        r.append((512, 512, 512, 512))
-    return r
-
-
-def random_rects(W, H, n, rng):
-    """n rects of mixed shapes: mostly wide and low, every tenth narrow and tall, so that the call's pixels stay small"""
-    out = []
-    for i in range(n):
-        if i % 10 == 9:
-            w, h = int(rng.integers(1, min(W, 48) + 1)), int(rng.integers(1, min(H, 1100) + 1))
-        else:
-            w, h = int(rng.integers(1, min(W, 700) + 1)), int(rng.integers(1, min(H, 40) + 1))
-        out.append((int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1)), w, h))
-    return out
-
-
-def expected_stats(containers, rects):
-    """(the tiles the rects select, the bytes of exactly those tile files), the container read by the test's own parser"""
-    parsed = {}
-    tiles = size = 0
-    for ci, x, y, w, h in rects:
-        if ci not in parsed:
-            parsed[ci] = parse_container(containers[ci])
-        W, H, files = parsed[ci]
-        sel = selected(W, x, y, w, h)
-        tiles += len(sel)
-        size += sum(len(files[k]) for k in sel)
-    return tiles, size
-
-
 @pytest.mark.gpu
 def test_regions_equal_the_slices_of_decode_pictures(world, oracle):
     import nhwcodec_amd as na
@@ -237,13 +147,13 @@ def test_regions_equal_the_slices_of_decode_pictures(world, oracle):
     rects = []
     for ci, f in enumerate(world.full):
         H, W = f.shape[:2]
-        mine = fixed_rects(W, H) + random_rects(W, H, 200, rng)
+        mine = fixed_rects(W, H, 512, residues=False) + random_rects(W, H, 200, rng, 700, 40)
         if W >= 64:                                                  # both phases take every residue, picture by picture
             assert sorted({3 * x % 16 for x, _, w, _ in mine}) == list(range(16)) == sorted({3 * w % 16 for x, _, w, _ in mine}), (W, H)
         rects += [(ci, *r) for r in mine]
     assert len(rects) > 2000
     got = world.dec.decode_regions(world.containers, rects)        # one call; max_batch 8: thousands of tiles in chunks of 8
-    want_tiles, want_bytes = expected_stats(world.containers, rects)
+    want_tiles, want_bytes = expected_stats(world.containers, rects, 1, unique=False)
     assert sum(na.region_tiles(world.full[ci].shape[1], world.full[ci].shape[0], x, y, w, h) for ci, x, y, w, h in rects) == want_tiles
     assert world.dec.region_stats() == (want_tiles, want_bytes)
     for (ci, x, y, w, h), g in zip(rects, got):
@@ -263,38 +173,8 @@ def test_regions_equal_the_slices_of_decode_pictures(world, oracle):
         assert n > 200
 
 
-def _dest_views(shapes):
-    """destinations as uint8 CUDA views [h, w, 3] into one canary-filled byte buffer: misalignments 0 .. 15 in turn, pitch gaps of
-    1, 5, 16, 7, 3 or 0 bytes, 64 bytes of slack behind a region -- except that every seventh one is packed (pitch 3 w) and its successor
-    starts on the very next byte, so that the two share a dword"""
-    import torch
-    gaps = (0, 1, 5, 16, 7, 3)
-    at, offs, extras, packed = 256, [], [], False
-    for i, (w, h) in enumerate(shapes):
-        extra = 0 if i % 7 == 0 else gaps[i % len(gaps)]
-        if not packed:
-            at = (at + 15) // 16 * 16 + i % 16
-        offs.append(at)
-        extras.append(extra)
-        at += (3 * w + extra) * (h - 1) + 3 * w
-        packed = i % 7 == 0
-        if not packed:
-            at += 64
-    buf = torch.full((at + 256,), CANARY, dtype=torch.uint8, device="cuda")
-    views = [buf.as_strided((h, w, 3), (3 * w + e, 3, 1), o) for (w, h), e, o in zip(shapes, extras, offs)]
-    return buf, views
-
-
-def _mask(buf, views):
-    import torch
-    mask = torch.zeros_like(buf, dtype=torch.bool)
-    for v in views:
-        mask.as_strided(v.shape, v.stride(), v.storage_offset()).fill_(True)
-    return mask
-
-
 def _own_bytes_rects(W, H, rng):
-    rects = fixed_rects(W, H) + random_rects(W, H, 40, rng)
+    rects = fixed_rects(W, H, 512, residues=False) + random_rects(W, H, 40, rng, 700, 40)
     return [r for r in rects if r[2] * r[3] < 600000]
 
 
@@ -313,12 +193,12 @@ def test_untile_regions_device_writes_only_the_regions(world):
                                      torch.tensor(lens, dtype=torch.int32).cuda())
     assert int(status.abs().sum()) == 0
     rects = _own_bytes_rects(W, H, np.random.default_rng(5))
-    buf, views = _dest_views([(w, h) for _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, w, h in rects])
     table = (Region * len(rects))()
     order = []
     for i, ((x, y, w, h), v) in enumerate(zip(rects, views)):
         table[i] = Region(v.data_ptr(), v.stride(0) if h > 1 else 3 * w, x, y, w, h, W, H, len(order), 0)
-        order += selected(W, x, y, w, h)
+        order += selected(W, 1, x, y, w, h, coords=False)
     assert {v.data_ptr() % 16 for v in views} == set(range(16))
     tiles = px[torch.tensor(order, device="cuda")].contiguous()
     d_table = torch.from_numpy(np.frombuffer(bytes(table), np.uint8).copy()).cuda()
@@ -330,7 +210,7 @@ def test_untile_regions_device_writes_only_the_regions(world):
     full = torch.from_numpy(world.full[ci]).cuda()
     for (x, y, w, h), v in zip(rects, views):
         assert torch.equal(v, full[y:y + h, x:x + w]), (x, y, w, h)
-    mask = _mask(buf, views)
+    mask = views_mask(buf, views)
     assert int(mask.sum()) == sum(3 * w * h for _, _, w, h in rects)
     assert bool((buf[~mask] == CANARY).all()), "a byte outside the regions was written"
     # what the host can check is refused
@@ -351,12 +231,12 @@ def test_decode_regions_device_writes_only_the_regions(world):
     for ci in (0, 1, 5 + 2, 5 + 3, 4):
         H, W = world.full[ci].shape[:2]
         rects += [(ci, *r) for r in _own_bytes_rects(W, H, rng)]
-    buf, views = _dest_views([(w, h) for _, _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, _, w, h in rects])
     got = world.dec.decode_regions_device(world.containers, rects, out=views)
-    assert world.dec.region_stats() == expected_stats(world.containers, rects)
+    assert world.dec.region_stats() == expected_stats(world.containers, rects, 1, unique=False)
     for (ci, x, y, w, h), v, g in zip(rects, views, got):
         assert g is v and np.array_equal(v.cpu().numpy(), world.full[ci][y:y + h, x:x + w]), (ci, x, y, w, h)
-    mask = _mask(buf, views)
+    mask = views_mask(buf, views)
     assert bool((buf[~mask] == CANARY).all()), "a byte outside the regions was written"
     # without `out`: fresh tensors on the decoder's device; crops straight into the slots of a batch tensor
     crops = [(5 + 3, x, y, 224, 224) for x, y in ((0, 0), (400, 300), (1696, 856), (511, 511))]
@@ -366,7 +246,7 @@ def test_decode_regions_device_writes_only_the_regions(world):
     for i, (ci, x, y, w, h) in enumerate(crops):
         assert fresh[i].is_cuda and fresh[i].dtype == torch.uint8 and tuple(fresh[i].shape) == (224, 224, 3)
         assert np.array_equal(fresh[i].cpu().numpy(), world.full[ci][y:y + h, x:x + w]) and torch.equal(fresh[i], batch[i])
-    assert world.dec.region_stats() == expected_stats(world.containers, crops) and world.dec.region_stats()[0] == 1 + 4 + 2 + 4
+    assert world.dec.region_stats() == expected_stats(world.containers, crops, 1, unique=False) and world.dec.region_stats()[0] == 1 + 4 + 2 + 4
     # destinations the wrapper refuses
     with pytest.raises(na.NhwError):
         world.dec.decode_regions_device(world.containers, crops, out=[batch[i] for i in range(3)])
@@ -391,9 +271,9 @@ def test_regions_whose_repeated_tiles_straddle_chunks(world):
     W, H, files = parse_container(container)
     assert (W, H, len(files)) == (700, 600, 4)
     rects = [(0, 520, 515, 50, 40), (0, 100, 100, 500, 450), (0, 520, 515, 50, 40)]
-    assert [selected(W, *r[1:]) for r in rects] == [[3], [0, 1, 2, 3], [3]]
+    assert [selected(W, 1, *r[1:], coords=False) for r in rects] == [[3], [0, 1, 2, 3], [3]]
     unmerged = (6, 2 * len(files[3]) + sum(len(f) for f in files))
-    assert expected_stats([container], rects) == unmerged
+    assert expected_stats([container], rects, 1, unique=False) == unmerged
     dec = na.Decoder(0, max_batch=2)
     full = dec.decode_pictures([container])[0]
     assert full.shape == (600, 700, 3)
@@ -406,14 +286,14 @@ def test_regions_whose_repeated_tiles_straddle_chunks(world):
 
     check(dec.decode_regions([container], rects))
     assert dec.region_stats() == unmerged
-    buf, views = _dest_views([(w, h) for _, _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, _, w, h in rects])
     check(dec.decode_regions_device([container], rects, out=views))
     assert dec.region_stats() == unmerged
-    assert bool((buf[~_mask(buf, views)] == CANARY).all()), "a byte outside the regions was written"
+    assert bool((buf[~views_mask(buf, views)] == CANARY).all()), "a byte outside the regions was written"
     merged = (4, sum(len(f) for f in files))
     check(dec.decode_windows([container], rects, 1))
     assert dec.region_stats() == merged
-    buf2, views2 = _dest_views([(w, h) for _, _, _, w, h in rects])
+    buf2, views2 = dest_views([(w, h) for _, _, _, w, h in rects])
     check(dec.decode_windows_device([container], rects, 1, out=views2))
     assert dec.region_stats() == merged
     assert torch.equal(buf, buf2)                                    # the same bytes, canaries included
@@ -441,17 +321,6 @@ def _call_regions(dec, containers, rects, canary_host=None, dst=None):
     return rc, status, out, out_off
 
 
-def _check_host_result(rects, status, out, out_off, full_of):
-    """OK rects hold their slice, every other byte of the buffer is still the canary"""
-    clean = np.ones(out.size, bool)
-    for i, (ci, x, y, w, h) in enumerate(rects):
-        if status[i] == 0:
-            a = int(out_off[i])
-            assert np.array_equal(out[a:a + 3 * w * h].reshape(h, w, 3), full_of(ci)[y:y + h, x:x + w]), rects[i]
-            clean[a:a + 3 * w * h] = False
-    assert (out[clean] == CANARY).all()
-
-
 @pytest.mark.gpu
 def test_a_refused_tile_fails_exactly_the_regions_that_select_it(world):
     import nhwcodec_amd as na
@@ -463,21 +332,21 @@ def test_a_refused_tile_fails_exactly_the_regions_that_select_it(world):
     broken = make_container(W, H, bad)
     assert na.picture_info(broken) == (W, H)                         # the directory is consistent: the container is well-formed
     rng = np.random.default_rng(9)
-    rects = [(0, *r) for r in fixed_rects(W, H) + random_rects(W, H, 60, rng)]
-    hit = [k in selected(W, *r[1:]) for r in rects]
+    rects = [(0, *r) for r in fixed_rects(W, H, 512, residues=False) + random_rects(W, H, 60, rng, 700, 40)]
+    hit = [k in selected(W, 1, *r[1:], coords=False) for r in rects]
     assert 10 < sum(hit) < len(rects) - 10
     full = world.full[ci]
     rc, status, out, out_off = _call_regions(world.dec, [broken], rects)
     assert rc == 0 and status.tolist() == [NHW_E_FORMAT if h else 0 for h in hit]
-    _check_host_result(rects, status, out, out_off, lambda c: full)
-    assert world.dec.region_stats() == expected_stats([broken], rects)   # every rect was handed to the decoder
+    check_host_result(rects, status, out, out_off, lambda c: full)
+    assert world.dec.region_stats() == expected_stats([broken], rects, 1, unique=False)   # every rect was handed to the decoder
     with pytest.raises(na.NhwError):
         world.dec.decode_regions([broken], rects)
     ok = [r for r, h in zip(rects, hit) if not h]
     for (c, x, y, w, h), g in zip(ok, world.dec.decode_regions([broken], ok)):
         assert np.array_equal(g, full[y:y + h, x:x + w])
     # on the device: a failed rect may have bytes of its own rows written, nothing else is touched
-    buf, views = _dest_views([(w, h) for _, _, _, w, h in rects])
+    buf, views = dest_views([(w, h) for _, _, _, w, h in rects])
     dst = ([v.data_ptr() for v in views], [v.stride(0) if v.shape[0] > 1 else 3 * v.shape[1] for v in views])
     rc, status, _, _ = _call_regions(world.dec, [broken], rects, dst=dst)
     torch.cuda.synchronize()
@@ -485,7 +354,7 @@ def test_a_refused_tile_fails_exactly_the_regions_that_select_it(world):
     for (c, x, y, w, h), v, h_ in zip(rects, views, hit):
         if not h_:
             assert np.array_equal(v.cpu().numpy(), full[y:y + h, x:x + w])
-    assert bool((buf[~_mask(buf, views)] == CANARY).all())
+    assert bool((buf[~views_mask(buf, views)] == CANARY).all())
 
 
 @pytest.mark.gpu
@@ -508,13 +377,13 @@ def test_statuses_are_per_rect(world):
     full = {0: world.full[1], 2: world.full[3]}
     rc, status, out, out_off = _call_regions(world.dec, containers, rects)
     assert rc == 0 and status.tolist() == want
-    _check_host_result(rects, status, out, out_off, lambda c: full[c])
+    check_host_result(rects, status, out, out_off, lambda c: full[c])
     good = [r for r, s in zip(rects, want) if s == 0]
-    assert world.dec.region_stats() == expected_stats(containers, good)      # only the good rects reached the decoder
+    assert world.dec.region_stats() == expected_stats(containers, good, 1, unique=False)      # only the good rects reached the decoder
     with pytest.raises(na.NhwError):
         world.dec.decode_regions(containers, rects)
     # the same on the device: the rects that are not NHW_OK leave their destinations untouched
-    buf, views = _dest_views([(max(w, 1), max(h, 1)) for _, _, _, w, h in rects])
+    buf, views = dest_views([(max(w, 1), max(h, 1)) for _, _, _, w, h in rects])
     dst = ([v.data_ptr() for v in views], [v.stride(0) if v.shape[0] > 1 else 3 * v.shape[1] for v in views])
     rc, status, _, _ = _call_regions(world.dec, containers, rects, dst=dst)
     torch.cuda.synchronize()
@@ -522,7 +391,7 @@ def test_statuses_are_per_rect(world):
     for (ci, x, y, w, h), v, st in zip(rects, views, want):
         if st == 0:
             assert np.array_equal(v.cpu().numpy(), full[ci][y:y + h, x:x + w])
-    assert bool((buf[~_mask(buf, [v for v, st in zip(views, want) if st == 0])] == CANARY).all())
+    assert bool((buf[~views_mask(buf, [v for v, st in zip(views, want) if st == 0])] == CANARY).all())
     # the call as a whole fails only for what no rect can answer for
     before = buf.clone()
     assert _call_regions(world.dec, containers, rects[:1], dst=([views[0].data_ptr()], [3 * 100 - 1]))[0] == na.NHW_E_ARG
@@ -544,33 +413,14 @@ def test_statuses_are_per_rect(world):
     assert L.nhw_dec_regions_to_device(h, blob.ctypes.data, off.ctypes.data, 1, a, 1, None, oo.ctypes.data, st.ctypes.data) == na.NHW_E_ARG
 
 
-def _views(specs, seed=0):
-    """pictures as uint8 CUDA views [H, W, 3] into one byte buffer: spec (W, H, pitch extra, byte misalignment of addr)"""
-    import torch
-    rng = np.random.default_rng(seed)
-    at, offs = 256, []
-    for w, h, extra, mis in specs:
-        at = (at + 255) // 256 * 256 + mis
-        offs.append(at)
-        at += (3 * w + extra) * h + 64
-    buf = torch.from_numpy(rng.integers(0, 256, at + 256, dtype=np.uint8)).cuda()
-    views = [buf.as_strided((h, w, 3), (3 * w + extra, 3, 1), o) for (w, h, extra, _), o in zip(specs, offs)]
-    return buf, views
-
-
-SPECS = ([(1, 1, 0, 0), (1, 700, 0, 1), (700, 1, 5, 3), (511, 513, 0, 2), (513, 511, 16, 1), (512, 512, 0, 0), (1023, 1025, 7, 0),
-          (1920, 1080, 0, 1)]
-         + [(149 + 11 * r, 3 + r, 9 if r % 2 else 0, r % 4) for r in range(16)])          # 3W mod 16 takes every residue
-
-
 @pytest.mark.gpu
 def test_whole_picture_regions_write_what_untile_pictures_writes():
     import nhwcodec_amd as na
     import torch
-    _, src = _views(SPECS, seed=1)
+    _, src = picture_views(SPECS, seed=1)
     tiles = na.tile_pictures_device(src)
-    old_buf, old = _views(SPECS, seed=2)
-    new_buf, new = _views(SPECS, seed=2)                             # the same layout and the same bytes underneath
+    old_buf, old = picture_views(SPECS, seed=2)
+    new_buf, new = picture_views(SPECS, seed=2)                             # the same layout and the same bytes underneath
     old_buf.fill_(CANARY)
     new_buf.fill_(CANARY)
     na.untile_pictures_device(tiles, old)
@@ -610,7 +460,7 @@ def test_one_handle_serves_pictures_regions_and_files_in_turn(world):
         if first is None:
             first = px.copy()
         assert np.array_equal(px, first)
-        assert d.region_stats() == expected_stats(cs, rects)
+        assert d.region_stats() == expected_stats(cs, rects, 1, unique=False)
     d.close()
 
 
@@ -620,14 +470,14 @@ def test_cli_region_equals_the_rectangle_of_the_whole_bmp(cli, world, tmp_path):
     ci = 5 + 2
     W, H = 1023, 1025
     (tmp_path / "p.nhwp").write_bytes(world.containers[ci])
-    rc, out, err = _run(cli, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "full.bmp"))
+    rc, out, err = run(cli, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "full.bmp"))
     assert rc == 0, err
     whole = (tmp_path / "full.bmp").read_bytes()
     stride = (3 * W + 3) & ~3
     rows = np.frombuffer(whole[54:], np.uint8).reshape(H, stride)
     assert np.array_equal(rows[:, :3 * W].reshape(H, W, 3), world.full[ci])
     for x, y, w, h in ((0, 0, 1023, 3), (500, 1000, 30, 25), (510, 300, 5, 400), (1022, 1024, 1, 1)):   # the top row; the bottom row; ...
-        rc, out, err = _run(cli, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "r.bmp"), "--region", f"{x},{y},{w},{h}")
+        rc, out, err = run(cli, "--picture", str(tmp_path / "p.nhwp"), str(tmp_path / "r.bmp"), "--region", f"{x},{y},{w},{h}")
         assert rc == 0 and f"{w} x {h}" in out, err
         b = (tmp_path / "r.bmp").read_bytes()
         rs = (3 * w + 3) & ~3

@@ -6,7 +6,7 @@ Y23's (cell, coefficient) for every residual x coefficient x coefficient-before 
 import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.support import ROOT
 
 
 def test_tables_equal_the_chains(tmp_path):

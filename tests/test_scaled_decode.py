@@ -6,22 +6,21 @@ The reference has no such mode; the expected pictures are built here from the or
 oracle/nhwo_dec.c) and the oracle's own colour matrix (nhwo_dec_color of liboracle.so):
   scale 2: Y = clip8(probe 6, the level-1 LL after the residual lists), U, V = probes 46, 47 (the sharpened, clipped 4:2:0 planes);
   scale 4: Y = clip8(probe 4's level-2 LL quadrant, TRANSPOSED), U, V = clip8(probes 42, 43's quadrant: level 2 + corrections).
-Every output byte of the GPU must equal them."""
+Every output byte of the GPU must equal them.  The construction itself is tests/tensor_cases.py's expected(): other modules hold their
+scaled decodes against it too."""
 import ctypes
-import hashlib
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle.harness import class_image
+from tests.picture_cases import parse_container
+from tests.support import CANARY, ROOT, built_cli, device_arena, golden, golden_names, load_lib, psnr, run
+from tests.tensor_cases import decode_scaled, expected, expected_planes
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden", "dec")
-DEC_CLI = os.path.join(ROOT, "tools", "nhw-dec")
 NEW_SYMBOLS = ("nhw_dec_batch_device_scaled", "nhw_dec_batch_scaled", "nhw_picture_scaled_size", "nhw_untile_pictures_scaled_device",
                "nhw_dec_pictures_scaled")
 PROTOTYPES = """
@@ -33,103 +32,16 @@ int nhw_untile_pictures_scaled_device(const void *d_tiles, const nhw_picture *d_
 int nhw_dec_pictures_scaled(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n, int scale, uint8_t *out, const uint64_t *out_off, int32_t *status);
 """
 NHW_E_ARG, NHW_E_FORMAT = -4, -6
-CANARY = 0xA5
-Q = 65536
-
-
-def _golden(name):
-    with open(os.path.join(GOLD, name), "rb") as f:
-        return f.read()
-
-
-def _golden_names():
-    return sorted(n for n in os.listdir(GOLD) if n.endswith(".nhw"))
-
-
-def _run(exe, *a):
-    p = subprocess.run([exe, *a], capture_output=True, text=True, timeout=300)
-    return p.returncode, p.stdout, p.stderr
-
-
-def _psnr(a, b):
-    d = a.astype(np.float64) - b.astype(np.float64)
-    return 10 * np.log10(255.0 ** 2 / max(np.mean(d * d), 1e-9))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import nhwcodec_amd
-    if not os.path.exists(nhwcodec_amd.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    return nhwcodec_amd.load_library()                          # (after torch: a process has one HIP runtime, and the GPU tests below share this one)
+    return load_lib()
 
 
 @pytest.fixture(scope="module")
 def cli():
-    if not os.path.exists(DEC_CLI):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tools")])
-    return DEC_CLI
-
-
-# ---------------------------------------------------------------- the expected pictures: probes -> planes -> nhwo_dec_color
-def _probe16(oracle, nhw, pid, stride):
-    return np.frombuffer(oracle.decode_probe(nhw, pid), np.int16).reshape(-1, stride)
-
-
-def expected_planes(oracle, nhw, scale):
-    """(Y, U, V) uint8 [T, T] of section 14's definition, and the file's quality"""
-    clip = lambda a: np.clip(a, 0, 255).astype(np.uint8)
-    q = oracle.decode(nhw)[1]
-    if scale == 2:
-        y = clip(_probe16(oracle, nhw, 6, 512)[:256, :256])
-        u, v = (clip(_probe16(oracle, nhw, 46 + c, 256)[:256, :256]) for c in (0, 1))
-    else:
-        y = clip(_probe16(oracle, nhw, 4, 512)[:128, :128].T)
-        u, v = (clip(_probe16(oracle, nhw, 42 + c, 256)[:128, :128]) for c in (0, 1))
-    return np.ascontiguousarray(y), np.ascontiguousarray(u), np.ascontiguousarray(v), q
-
-
-def oracle_colour(oracle, y, u, v, q):
-    """the file's own quality branch of nhwo_dec_color on small planes: the function walks 262144 pixels, so the planes sit at the front of
-    zero-padded arrays and the first T * T pixels come back"""
-    t = y.shape[0]
-    fn = oracle.lib.nhwo_dec_color
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-    fn.restype = None
-    pad = [np.zeros(4 * Q, np.uint8) for _ in range(3)]
-    for p, a in zip(pad, (y, u, v)):
-        p[:t * t] = a.reshape(-1)
-    out = np.empty(12 * Q, np.uint8)
-    fn(pad[0].ctypes.data, pad[1].ctypes.data, pad[2].ctypes.data, q, out.ctypes.data)
-    return out[:3 * t * t].reshape(t, t, 3).copy()
-
-
-_EXPECTED = {}
-
-
-def expected(oracle, nhw, scale):
-    """the expected scaled picture of a file, uint8 [T, T, 3]; computed once a (file, scale) and never written to"""
-    key = (hashlib.sha1(nhw).digest(), scale)
-    if key not in _EXPECTED:
-        y, u, v, q = expected_planes(oracle, nhw, scale)
-        px = oracle_colour(oracle, y, u, v, q)
-        px.setflags(write=False)
-        _EXPECTED[key] = px
-    return _EXPECTED[key]
-
-
-def parse_container(c):
-    assert c[:8] == b"NHWP\x01\x00\x00\x00"
-    w, h = struct.unpack_from("<II", c, 8)
-    t = (-(-w // 512)) * (-(-h // 512))
-    lens = struct.unpack_from(f"<{t}I", c, 16)
-    files, at = [], 16 + 4 * t
-    for n in lens:
-        files.append(bytes(c[at:at + n]))
-        at += n
-    assert at == len(c)
-    return w, h, files
+    return built_cli("nhw-dec")
 
 
 def expected_picture(oracle, container, scale):
@@ -157,8 +69,8 @@ def test_definition_orientation_tripwire(oracle, q):
     assert qq == q
     y2, u2, v2, _ = expected_planes(oracle, nhw, 2)
     y4, u4, v4, _ = expected_planes(oracle, nhw, 4)
-    figures = {"Y2": _psnr(y2, _box(planes[0], 2)), "Y4": _psnr(y4, _box(planes[0], 4)), "U4": _psnr(u4, _box(planes[1], 4)), "V4": _psnr(v4, _box(planes[2], 4))}
-    wrong = {"Y2": _psnr(y2.T, _box(planes[0], 2)), "Y4": _psnr(y4.T, _box(planes[0], 4))}
+    figures = {"Y2": psnr(y2, _box(planes[0], 2)), "Y4": psnr(y4, _box(planes[0], 4)), "U4": psnr(u4, _box(planes[1], 4)), "V4": psnr(v4, _box(planes[2], 4))}
+    wrong = {"Y2": psnr(y2.T, _box(planes[0], 2)), "Y4": psnr(y4.T, _box(planes[0], 4))}
     print(f"q{q}: " + ", ".join(f"{k} {v:.1f} dB" for k, v in figures.items()) + " | transposed: " + ", ".join(f"{k} {v:.1f} dB" for k, v in wrong.items()))
     assert figures["Y2"] >= 35.0, figures
     assert min(figures["Y4"], figures["U4"], figures["V4"]) >= 30.0, figures
@@ -221,7 +133,7 @@ def test_scaled_symbols_and_prototypes(lib):
 def test_cli_refuses_a_bad_scale_before_any_gpu_work(cli, tmp_path, args):
     """refused like a malformed --region: exit 1 with a message on stderr, no file read, none written, the GPU never opened (this runs without one)"""
     args = tuple(str(tmp_path / a) if a.endswith((".nhw", ".nhwp", ".bmp")) else a for a in args)
-    rc, out, err = _run(cli, *args)
+    rc, out, err = run(cli, *args)
     assert rc == 1 and "--scale" in err and out == "", (rc, out, err)
     assert not os.listdir(tmp_path)
 
@@ -233,28 +145,6 @@ def dec():
     d = nhwcodec_amd.Decoder(0, max_batch=64)
     yield d
     d.close()
-
-
-def _arena(files):
-    """files -> (arena, offsets, lengths) on the device, as decode_device takes them"""
-    import torch
-    offs = np.zeros(len(files), np.int64)
-    offs[1:] = np.cumsum([len(f) for f in files])[:-1]
-    blob = np.frombuffer(b"".join(files) + bytes(64), np.uint8).copy()
-    return (torch.from_numpy(blob).cuda(), torch.from_numpy(offs).cuda(), torch.from_numpy(np.array([len(f) for f in files], np.int32)).cuda())
-
-
-def _decode_scaled(dec, files, scale):
-    """one decode_scaled_device call into a canary-backed buffer -> (pixels, status, quality) on the host; the canary is checked"""
-    import torch
-    n, t = len(files), 512 // scale
-    room = n * 3 * t * t
-    buf = torch.full((room + 4096,), CANARY, dtype=torch.uint8, device="cuda")
-    px, st, qq = dec.decode_scaled_device(*_arena(files), scale, out=buf)
-    torch.cuda.synchronize()
-    assert tuple(px.shape) == (n, t, t, 3) and px.data_ptr() == buf.data_ptr()
-    assert bool((buf[room:] == CANARY).all()), "bytes behind n * 3 T T were written"
-    return px.cpu().numpy(), st.cpu().numpy(), qq.cpu().numpy()
 
 
 def _assert_pictures(oracle, got, files, scale, names=None, only=None):
@@ -272,10 +162,10 @@ def _assert_pictures(oracle, got, files, scale, names=None, only=None):
 @pytest.mark.parametrize("scale", [2, 4])
 def test_gpu_scaled_every_quality_one_mixed_batch(dec, oracle, scale):
     """the 34 committed files (q1 .. 23, every colour branch, every residual list) in one call: every output byte"""
-    names = _golden_names()
+    names = golden_names()
     assert len(names) == 34
-    files = [_golden(n) for n in names]
-    px, st, qq = _decode_scaled(dec, files, scale)
+    files = [golden(n) for n in names]
+    px, st, qq = decode_scaled(dec, files, scale)
     assert not st.any()
     assert qq.tolist() == [int(n[1:3]) for n in names]
     _assert_pictures(oracle, px, files, scale, names)
@@ -285,8 +175,8 @@ def test_gpu_scaled_every_quality_one_mixed_batch(dec, oracle, scale):
 @pytest.mark.parametrize("scale", [2, 4])
 @pytest.mark.parametrize("name", ["q20_0.nhw", "q10_0.nhw"])
 def test_gpu_scaled_single_file(dec, oracle, scale, name):
-    f = _golden(name)
-    px, st, qq = _decode_scaled(dec, [f], scale)
+    f = golden(name)
+    px, st, qq = decode_scaled(dec, [f], scale)
     assert st.tolist() == [0] and qq.tolist() == [int(name[1:3])]
     _assert_pictures(oracle, px, [f], scale, [name])
 
@@ -294,8 +184,8 @@ def test_gpu_scaled_single_file(dec, oracle, scale, name):
 @pytest.mark.gpu
 def test_gpu_scale_1_is_the_full_decode(dec):
     import torch
-    files = [_golden(n) for n in _golden_names()]
-    a = _arena(files)
+    files = [golden(n) for n in golden_names()]
+    a = device_arena(files)
     px1, st1, q1 = dec.decode_scaled_device(*a, 1)
     px, st, q = dec.decode_device(*a)
     torch.cuda.synchronize()
@@ -309,12 +199,12 @@ def test_gpu_scaled_refused_files_and_good_neighbours(dec, oracle, scale):
     """a truncated, a zero-filled and a foreign file among good ones: status and quality as the full decode reports them, a refused file's bytes
     untouched, every good neighbour byte-exact"""
     import torch
-    good, other = _golden("q20_0.nhw"), _golden("q10_0.nhw")
-    files = [good, good[:40], other, bytes(3000), bytes([9, 20]) + good[2:], good[: len(good) // 2], _golden("q23_0.nhw"), good]
-    a = _arena(files)
+    good, other = golden("q20_0.nhw"), golden("q10_0.nhw")
+    files = [good, good[:40], other, bytes(3000), bytes([9, 20]) + good[2:], good[: len(good) // 2], golden("q23_0.nhw"), good]
+    a = device_arena(files)
     _, st_full, q_full = dec.decode_device(*a)
     torch.cuda.synchronize()
-    px, st, qq = _decode_scaled(dec, files, scale)
+    px, st, qq = decode_scaled(dec, files, scale)
     assert st.tolist() == st_full.cpu().tolist() == [0, NHW_E_FORMAT, 0, NHW_E_FORMAT, NHW_E_FORMAT, NHW_E_FORMAT, 0, 0]
     assert qq.tolist() == q_full.cpu().tolist()
     _assert_pictures(oracle, px, files, scale, only={0, 2, 6, 7})
@@ -344,7 +234,7 @@ def test_gpu_one_handle_full_and_scaled_in_any_order(oracle):
     plan = [("dense", 1), ("sparse", 4), ("dense", 2), ("dense", 1), ("sparse", 2), ("dense", 4)]
 
     def run(d, key, scale):
-        px, st, qq = d.decode_scaled_device(*_arena(batches[key]), scale)
+        px, st, qq = d.decode_scaled_device(*device_arena(batches[key]), scale)
         torch.cuda.synchronize()
         assert not bool(st.any())
         return px.cpu().numpy()
@@ -370,7 +260,7 @@ def test_gpu_scaled_host_path_is_chunked(oracle, scale):
     """decode_scaled of 5 files on a handle of max_batch 2: three chunks"""
     import nhwcodec_amd as na
     names = ["q20_0.nhw", "q10_gradient.nhw", "q23_tiles.nhw", "q01_0.nhw", "q17_0.nhw"]
-    files = [_golden(n) for n in names]
+    files = [golden(n) for n in names]
     d = na.Decoder(0, max_batch=2)
     try:
         px, qs = d.decode_scaled(files, scale)
@@ -444,7 +334,7 @@ def test_gpu_untile_scaled_writes_only_the_pictures_bytes(oracle, containers, sc
     t = 512 // scale
     files = [f for c in containers for f in parse_container(c)[2]]
     d = na.Decoder(0, max_batch=len(files))
-    tiles, st, _ = d.decode_scaled_device(*_arena(files), scale)
+    tiles, st, _ = d.decode_scaled_device(*device_arena(files), scale)
     torch.cuda.synchronize()
     d.close()
     assert not bool(st.any()) and tuple(tiles.shape) == (len(files), t, t, 3)
@@ -477,12 +367,12 @@ def test_gpu_scaled_call_with_a_debug_stop_is_refused(oracle):
     try:
         d.lib.nhw_dec_debug_stop_after(d.h, 4)
         with pytest.raises(na.NhwError):
-            d.decode_scaled_device(*_arena([_golden("q20_0.nhw")]), 2)
+            d.decode_scaled_device(*device_arena([golden("q20_0.nhw")]), 2)
         d.lib.nhw_dec_debug_stop_after(d.h, 0)
-        px, st, _ = d.decode_scaled_device(*_arena([_golden("q20_0.nhw")]), 2)
-        assert np.array_equal(px[0].cpu().numpy(), expected(oracle, _golden("q20_0.nhw"), 2))
+        px, st, _ = d.decode_scaled_device(*device_arena([golden("q20_0.nhw")]), 2)
+        assert np.array_equal(px[0].cpu().numpy(), expected(oracle, golden("q20_0.nhw"), 2))
         with pytest.raises(na.NhwError):
-            d.decode_scaled_device(*_arena([_golden("q20_0.nhw")] * 3), 2)      # more files than max_batch
+            d.decode_scaled_device(*device_arena([golden("q20_0.nhw")] * 3), 2)      # more files than max_batch
     finally:
         d.close()
 
@@ -501,25 +391,25 @@ def _bmp_header(dec, w, h):
 def test_gpu_cli_scale(dec, oracle, cli, containers, tmp_path):
     """nhw-dec --scale 2 on one file: the header of a 256 x 256 BMP and the expected bytes; --scale 1 is the plain call; --batch --scale 4;
     --picture --scale 4 on the 513 x 511 container"""
-    f = _golden("q20_0.nhw")
+    f = golden("q20_0.nhw")
     src = tmp_path / "a.nhw"
     src.write_bytes(f)
-    rc, out, err = _run(cli, "--scale", "2", str(src), str(tmp_path / "a2.bmp"))
+    rc, out, err = run(cli, "--scale", "2", str(src), str(tmp_path / "a2.bmp"))
     assert rc == 0, (out, err)
     assert (tmp_path / "a2.bmp").read_bytes() == _bmp_header(dec, 256, 256) + expected(oracle, f, 2).tobytes()
-    assert _run(cli, str(src), str(tmp_path / "a1.bmp"), "--scale", "1")[0] == 0 and _run(cli, str(src), str(tmp_path / "a0.bmp"))[0] == 0
+    assert run(cli, str(src), str(tmp_path / "a1.bmp"), "--scale", "1")[0] == 0 and run(cli, str(src), str(tmp_path / "a0.bmp"))[0] == 0
     assert (tmp_path / "a1.bmp").read_bytes() == (tmp_path / "a0.bmp").read_bytes() == dec.bmp_header() + oracle.decode(f)[0].tobytes()
     bdir = tmp_path / "batch"
     bdir.mkdir()
     for n in ("q10_0.nhw", "q23_0.nhw"):
-        (bdir / n).write_bytes(_golden(n))
-    rc, out, err = _run(cli, "--batch", str(bdir), "--scale", "4")
+        (bdir / n).write_bytes(golden(n))
+    rc, out, err = run(cli, "--batch", str(bdir), "--scale", "4")
     assert rc == 0 and "2 file(s) decoded" in out, (out, err)
     for n in ("q10_0", "q23_0"):
-        assert (bdir / (n + ".bmp")).read_bytes() == _bmp_header(dec, 128, 128) + expected(oracle, _golden(n + ".nhw"), 4).tobytes()
+        assert (bdir / (n + ".bmp")).read_bytes() == _bmp_header(dec, 128, 128) + expected(oracle, golden(n + ".nhw"), 4).tobytes()
     c = containers[2]
     (tmp_path / "p.nhwp").write_bytes(c)
-    rc, out, err = _run(cli, "--picture", "--scale", "4", str(tmp_path / "p.nhwp"), str(tmp_path / "p4.bmp"))
+    rc, out, err = run(cli, "--picture", "--scale", "4", str(tmp_path / "p.nhwp"), str(tmp_path / "p4.bmp"))
     assert rc == 0 and "129 x 128 picture" in out, (out, err)
     want = expected_picture(oracle, c, 4)
     rows = b"".join(want[r].tobytes() + bytes(-3 * 129 % 4) for r in range(128))

@@ -32,20 +32,15 @@ import numpy as np
 import pytest
 
 from tests import stream_cases as sc
+from tests.enc_stages import ws_index
+from tests.support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 Q = sc.Q
 E_CODEBOOK, E_SPACE = -2, -3
 
 
 def _ws_text():
     return open(os.path.join(ROOT, "nhwcodec_amd", "csrc", "nhw_ws.h")).read()
-
-
-def _ws_index(name):
-    txt = _ws_text()
-    body = re.sub(r"/\*.*?\*/", "", txt[txt.index("enum {"):txt.index("B_COUNT")], flags=re.S)
-    return re.findall(r"B_[A-Z0-9_]+", body).index("B_" + name)
 
 
 def _meta_index():
@@ -62,7 +57,7 @@ def _meta_index():
 
 
 META, META_INTS = _meta_index()
-B = {k: _ws_index(k) for k in ("SCAN", "NZQ", "NZS", "VOFF", "VALS", "CNZQ", "CVALS", "PACKET", "BOOK1", "BOOK2", "SEL1", "SEL2", "META")}
+B = {k: ws_index(k) for k in ("SCAN", "NZQ", "NZS", "VOFF", "VALS", "CNZQ", "CVALS", "PACKET", "BOOK1", "BOOK2", "SEL1", "SEL2", "META")}
 SCALARS = ("select1", "select2", "size_data1", "size_data2", "size_book1", "size_book2", "tree_end", "wavelet_type")
 
 

@@ -2,11 +2,11 @@
 and k_dec_scaled<2> / <4>), nhw_bytes_to_tensor_device (k_bytes_to_tensor) and their Python faces.
 
 The expected values come from the specification, not from the code under test.  The expected BYTES of a file are the oracle decoder's (scale 1)
-or section 14's pictures as tests/test_scaled_decode.py builds them (scales 2, 4).  The expected TENSOR is made on the CPU:
+or section 14's pictures as tests/tensor_cases.py builds them (scales 2, 4).  The expected TENSOR is made on the CPU:
 b.astype(float64) * float64(scale32[c]) + float64(bias32[c]), .astype(float32), then the target type's own rounding from float32 (numpy for
 float16, torch on the CPU for bfloat16), then indexed and flipped by the format.  That equals fmaf(float32(b), scale, bias) EXACTLY when
 |exponent(scale) - exponent(bias)| <= 20 (or bias = 0): the product of an 8-bit and a 24-bit significand is exact in float64, under the condition
-so is the sum, and one rounding to float32 remains.  _check_constants asserts the condition on every constant this file uses, so a later edit
+so is the sum, and one rounding to float32 remains.  check_constants asserts the condition on every constant this file uses, so a later edit
 cannot quietly turn exact equality into double rounding.  Bit patterns are compared as integers.
 
 Batches (committed files of tests/golden/dec, the smallest shapes that take every path): THREE = q20_0 (eight pixels a thread), q10_0 (four) and
@@ -14,7 +14,6 @@ a file truncated to 40 bytes (a refused slot), under all 32 formats; TWO = q23_0
 count at scale 4 is 36, no multiple of eight; at scale 2 it is 72), the last two under four formats in which every enum value appears.  Every
 batch runs at scales 1, 2 and 4 into a sentinel-filled buffer: a refused slot and everything past n * 3 * S * S elements must stay as they were."""
 import ctypes
-import itertools
 import os
 import re
 
@@ -22,97 +21,25 @@ import numpy as np
 import pytest
 
 from oracle.harness import class_image
-from tests.test_scaled_decode import _arena, _golden, _golden_names, expected as expected_scaled
+from tests.support import ROOT, device_arena, golden, golden_names
+from tests.tensor_cases import (ALL_FORMATS, CONSTANTS, DTYPES, IMAGENET_MEAN, IMAGENET_STD, SENTINEL, assert_tensor, check_constants, decode_tensor,
+                                expected_bytes, expected_tensor, tensor_bits, tensor_format)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NHW_E_ARG, NHW_E_FORMAT = -4, -6
-SENTINEL = 0xA5
-TAIL = 4096                                     # sentinel bytes kept behind every output
-
-IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 # the float32 constants TensorFormat(mean=IMAGENET_MEAN, std=IMAGENET_STD) must arrive at: 1 / (255 std) and -mean / std in float32 arithmetic
 IMAGENET_SCALE32 = (0.017124753445386887, 0.017507001757621765, 0.01742919348180294)
 IMAGENET_BIAS32 = (-2.1179039478302, -2.0357141494750977, -1.804444432258606)
-CONSTANTS = {                                   # name -> TensorFormat keywords
-    "imagenet": dict(mean=IMAGENET_MEAN, std=IMAGENET_STD),
-    "unit": dict(scale=1 / 255, bias=0),
-    "negative": dict(scale=(-1 / 255, -0.5, -2.0), bias=(1.0, 127.5, 3.25)),
-    "identity": dict(scale=1, bias=0),
-}
-DTYPES = ("uint8", "float16", "bfloat16", "float32")
-ALL_FORMATS = list(itertools.product(DTYPES, ("HWC", "CHW"), ("BGR", "RGB"), ("file", "reversed")))      # 32
 FOUR_FORMATS = [("uint8", "CHW", "RGB", "reversed"), ("float16", "HWC", "BGR", "file"), ("bfloat16", "CHW", "BGR", "reversed"), ("float32", "HWC", "RGB", "file")]
-
-
-def _fmt(dtype, layout, channels, rows, constants=None):
-    """the TensorFormat of a parameter tuple; the float types walk through CONSTANTS so that every set meets every dtype"""
-    import nhwcodec_amd as na
-    if dtype == "uint8":
-        return na.TensorFormat(dtype, layout, channels, rows)
-    if constants is None:
-        constants = list(CONSTANTS)[ALL_FORMATS.index((dtype, layout, channels, rows)) % len(CONSTANTS)]
-    return na.TensorFormat(dtype, layout, channels, rows, **CONSTANTS[constants])
-
-
-def _check_constants(fmt):
-    """the condition under which the float64 form below IS the single-precision fma"""
-    for s, b in zip(fmt.scale, fmt.bias):
-        assert np.float32(s) == s and np.float32(b) == b and np.isfinite(s) and np.isfinite(b) and s != 0
-        assert b == 0 or abs(int(np.frexp(s)[1]) - int(np.frexp(b)[1])) <= 20, (s, b)
-
-
-def expected_tensor(px, fmt):
-    """the specification on the CPU: px uint8 [H, W, 3] as the byte path writes it -> the bit patterns of the tensor, [H, W, 3] or [3, H, W]"""
-    import torch
-    _check_constants(fmt)
-    b = px[..., ::-1] if fmt.channels == "RGB" else px
-    if fmt.dtype_name == "uint8":
-        bits = b.copy()
-    else:
-        sc, bi = np.array(fmt.scale, np.float32), np.array(fmt.bias, np.float32)
-        x = (b.astype(np.float64) * sc.astype(np.float64) + bi.astype(np.float64)).astype(np.float32)
-        if fmt.dtype_name == "float32":
-            bits = x.view(np.uint32)
-        elif fmt.dtype_name == "float16":
-            bits = x.astype(np.float16).view(np.uint16)
-        else:
-            bits = torch.from_numpy(np.ascontiguousarray(x)).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
-    if fmt.rows == "reversed":
-        bits = bits[::-1]
-    if fmt.layout == "CHW":
-        bits = bits.transpose(2, 0, 1)
-    return np.ascontiguousarray(bits)
-
-
-def _bits(t):
-    """a tensor's bit patterns on the host, as unsigned integers"""
-    import torch
-    view = {1: torch.uint8, 2: torch.int16, 4: torch.int32}[t.element_size()]
-    return t.contiguous().view(view).cpu().numpy().view({1: np.uint8, 2: np.uint16, 4: np.uint32}[t.element_size()])
-
-
-_BYTES = {}
-
-
-def expected_bytes(oracle, nhw, scale):
-    """the byte path's picture of a file, uint8 [S, S, 3]: the oracle decoder's at scale 1, section 14's at 2 and 4; computed once, never written to"""
-    if scale != 1:
-        return expected_scaled(oracle, nhw, scale)
-    if nhw not in _BYTES:
-        px = np.array(oracle.decode(nhw)[0], np.uint8).reshape(512, 512, 3)
-        px.setflags(write=False)
-        _BYTES[nhw] = px
-    return _BYTES[nhw]
 
 
 def _batch(name):
     if name == "three":
-        return [_golden("q20_0.nhw"), _golden("q10_0.nhw"), _golden("q20_0.nhw")[:40]], [0, 0, NHW_E_FORMAT]
+        return [golden("q20_0.nhw"), golden("q10_0.nhw"), golden("q20_0.nhw")[:40]], [0, 0, NHW_E_FORMAT]
     if name == "two":
-        return [_golden("q23_0.nhw"), _golden("q01_0.nhw")], [0, 0]
-    names = _golden_names()[::4]
+        return [golden("q23_0.nhw"), golden("q01_0.nhw")], [0, 0]
+    names = golden_names()[::4]
     assert len(names) == 9
-    return [_golden(n) for n in names], [0] * 9
+    return [golden(n) for n in names], [0] * 9
 
 
 # ---------------------------------------------------------------- without a GPU
@@ -159,7 +86,7 @@ def test_tensor_format_mean_std_arithmetic():
     assert (d.dtype_name, d.layout, d.channels, d.rows, d.scale, d.bias) == ("float32", "CHW", "RGB", "reversed", (1.0,) * 3, (0.0,) * 3)
     assert na.TensorFormat("uint8").scale == (1.0, 1.0, 1.0)
     for name in CONSTANTS:
-        _check_constants(_fmt("float32", "CHW", "RGB", "file", name))
+        check_constants(tensor_format("float32", "CHW", "RGB", "file", name))
 
 
 @pytest.mark.parametrize("kw", [
@@ -183,42 +110,16 @@ def dec():
     d.close()
 
 
-def _decode_tensor(dec, files, fmt, scale):
-    """one decode_tensor_device call into a sentinel-filled buffer -> (the tensor's bit patterns, status, quality) on the host; what lies behind
-    n * 3 * S * S elements is checked"""
-    import torch
-    n, s = len(files), 512 // scale
-    room = n * 3 * s * s * fmt.dtype.itemsize
-    buf = torch.full((room + TAIL,), SENTINEL, dtype=torch.uint8, device="cuda")
-    out = buf[:room].view(fmt.dtype)
-    t, st, qq = dec.decode_tensor_device(*_arena(files), fmt, scale=scale, out=out)
-    torch.cuda.synchronize()
-    assert t.dtype == fmt.dtype and tuple(t.shape) == (n,) + fmt.shape(s, s) and t.data_ptr() == buf.data_ptr()
-    assert bool((buf[room:] == SENTINEL).all()), "elements behind n * 3 * S * S were written"
-    return _bits(t), st.cpu().numpy(), qq.cpu().numpy()
-
-
-def _assert_tensor(oracle, bits, files, status, fmt, scale, what=""):
-    for i, f in enumerate(files):
-        if status[i]:
-            assert (bits[i].view(np.uint8) == SENTINEL).all(), f"{what}: refused file {i}: its slot was written"
-            continue
-        want = expected_tensor(expected_bytes(oracle, f, scale), fmt)
-        assert bits[i].dtype == want.dtype and bits[i].shape == want.shape
-        bad = bits[i] != want
-        assert not bad.any(), f"{what} {fmt} scale {scale} file {i}: {int(bad.sum())} of {bad.size} elements differ, first at {tuple(np.argwhere(bad)[0])}"
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("scale", [1, 2, 4])
 @pytest.mark.parametrize("dtype,layout,channels,rows", ALL_FORMATS)
 def test_gpu_tensor_three_files_every_format(dec, oracle, dtype, layout, channels, rows, scale):
     """both colour branches and a refused slot, under all 32 formats, bit for bit"""
     files, status = _batch("three")
-    fmt = _fmt(dtype, layout, channels, rows)
-    bits, st, qq = _decode_tensor(dec, files, fmt, scale)
+    fmt = tensor_format(dtype, layout, channels, rows)
+    bits, st, qq = decode_tensor(dec, files, fmt, scale)
     assert st.tolist() == status and qq.tolist()[:2] == [20, 10]
-    _assert_tensor(oracle, bits, files, status, fmt, scale, "three")
+    assert_tensor(oracle, bits, files, status, fmt, scale, "three")
 
 
 def test_the_four_formats_hold_every_enum_value():
@@ -234,10 +135,10 @@ def test_the_four_formats_hold_every_enum_value():
 def test_gpu_tensor_other_batches(dec, oracle, batch, k, scale):
     """q23 (the level-1 corrections) and q1 (the low colour matrix); nine files, whose workgroups at scale 4 are no multiple of eight"""
     files, status = _batch(batch)
-    fmt = _fmt(*FOUR_FORMATS[k], constants=list(CONSTANTS)[k])
-    bits, st, _ = _decode_tensor(dec, files, fmt, scale)
+    fmt = tensor_format(*FOUR_FORMATS[k], constants=list(CONSTANTS)[k])
+    bits, st, _ = decode_tensor(dec, files, fmt, scale)
     assert st.tolist() == status
-    _assert_tensor(oracle, bits, files, status, fmt, scale, batch)
+    assert_tensor(oracle, bits, files, status, fmt, scale, batch)
 
 
 @pytest.mark.gpu
@@ -248,9 +149,9 @@ def test_gpu_byte_format_is_the_byte_path_and_u8_chw_its_permutation(dec, scale)
     files, status = _batch("three")
     s = 512 // scale
     ref = torch.full((3, s, s, 3), SENTINEL, dtype=torch.uint8, device="cuda")
-    px, st0, q0 = dec.decode_scaled_device(*_arena(files), scale, out=ref)
-    same, st1, q1 = _decode_tensor(dec, files, na.TensorFormat("uint8", "HWC", "BGR", "file"), scale)
-    perm, st2, q2 = _decode_tensor(dec, files, na.TensorFormat("uint8", "CHW", "RGB", "reversed"), scale)
+    px, st0, q0 = dec.decode_scaled_device(*device_arena(files), scale, out=ref)
+    same, st1, q1 = decode_tensor(dec, files, na.TensorFormat("uint8", "HWC", "BGR", "file"), scale)
+    perm, st2, q2 = decode_tensor(dec, files, na.TensorFormat("uint8", "CHW", "RGB", "reversed"), scale)
     torch.cuda.synchronize()
     assert st0.cpu().tolist() == status == st1.tolist() == st2.tolist() and q0.cpu().tolist() == q1.tolist() == q2.tolist()
     px = px.cpu().numpy()
@@ -275,18 +176,18 @@ def test_gpu_one_handle_bytes_and_tensors_in_any_order(oracle):
         assert len(ok) >= 2, (key, status.tolist())
         batches[key] = [out[i, : int(sizes[i])].cpu().numpy().tobytes() for i in ok]
     enc.close()
-    f16 = _fmt("float16", "CHW", "RGB", "reversed", "imagenet")
-    f32 = _fmt("float32", "HWC", "BGR", "file", "negative")
+    f16 = tensor_format("float16", "CHW", "RGB", "reversed", "imagenet")
+    f32 = tensor_format("float32", "HWC", "BGR", "file", "negative")
     plan = [("dense", 1, None), ("sparse", 2, f16), ("dense", 4, None), ("dense", 1, f32), ("sparse", 1, None), ("dense", 2, f16), ("sparse", 4, f32)]
 
     def run(d, key, scale, fmt):
         if fmt is None:
-            px, st, _ = d.decode_scaled_device(*_arena(batches[key]), scale)
+            px, st, _ = d.decode_scaled_device(*device_arena(batches[key]), scale)
         else:
-            px, st, _ = d.decode_tensor_device(*_arena(batches[key]), fmt, scale=scale)
+            px, st, _ = d.decode_tensor_device(*device_arena(batches[key]), fmt, scale=scale)
         torch.cuda.synchronize()
         assert not bool(st.any())
-        return _bits(px)
+        return tensor_bits(px)
 
     one = na.Decoder(0, 4)
     got = [run(one, *step) for step in plan]
@@ -307,16 +208,16 @@ def test_gpu_tensor_under_forced_slice_orders(dec, oracle, mode):
     """the bands of k_dec_final one per launch, ascending and descending (the orders nhw_dec_debug_slice_order offers): the same tensors"""
     files, status = _batch("three")
     for k, four in enumerate(FOUR_FORMATS):
-        fmt = _fmt(*four, constants=list(CONSTANTS)[k])
-        want, st_w, _ = _decode_tensor(dec, files, fmt, 1)
+        fmt = tensor_format(*four, constants=list(CONSTANTS)[k])
+        want, st_w, _ = decode_tensor(dec, files, fmt, 1)
         assert dec.lib.nhw_dec_debug_slice_order(dec.h, mode) == 0
         try:
-            got, st, _ = _decode_tensor(dec, files, fmt, 1)
+            got, st, _ = decode_tensor(dec, files, fmt, 1)
         finally:
             assert dec.lib.nhw_dec_debug_slice_order(dec.h, 0) == 0
         assert st.tolist() == st_w.tolist() == status
         assert np.array_equal(got, want)
-        _assert_tensor(oracle, got, files, status, fmt, 1, f"slice order {mode}")
+        assert_tensor(oracle, got, files, status, fmt, 1, f"slice order {mode}")
 
 
 # ---------------------------------------------------------------- what is already bytes
@@ -362,15 +263,15 @@ def test_gpu_pictures_to_tensor(arrangement):
     other, own2 = _picture_views(arrangement, 2)
     assert all(np.array_equal(a, b) for a, b in zip(own, own2))
     for four in ALL_FORMATS:
-        fmt = _fmt(*four)
+        fmt = tensor_format(*four)
         got = na.pictures_to_tensor_device(views, fmt)
         again = na.pictures_to_tensor_device(other, fmt)
         torch.cuda.synchronize()
         for (w, h), px, g, g2 in zip(PICTURE_SIZES, own, got, again):
             assert g.dtype == fmt.dtype and tuple(g.shape) == fmt.shape(h, w)
-            bits, want = _bits(g), expected_tensor(px, fmt)
+            bits, want = tensor_bits(g), expected_tensor(px, fmt)
             assert np.array_equal(bits, want), f"{fmt} {w} x {h}: {int((bits != want).sum())} elements differ"
-            assert np.array_equal(_bits(g2), want)
+            assert np.array_equal(tensor_bits(g2), want)
 
 
 @pytest.mark.gpu
@@ -382,7 +283,7 @@ def test_gpu_bytes_to_tensor_writes_only_the_tensors(dec):
     views, own = _picture_views("pitch", 3)
     table, _, dev = na._picture_table(views, "test")
     for four in FOUR_FORMATS:
-        fmt = _fmt(*four)
+        fmt = tensor_format(*four)
         es = fmt.dtype.itemsize
         sizes = [3 * w * h * es for w, h in PICTURE_SIZES]
         offs, at = [], 64
@@ -429,7 +330,7 @@ def test_gpu_refusals_launch_nothing(dec):
     stay at their sentinel"""
     import torch
     files, _ = _batch("two")
-    arena, offs, lens = _arena(files)
+    arena, offs, lens = device_arena(files)
     out = torch.full((2 * 3 * 512 * 512 * 4 + 64,), SENTINEL, dtype=torch.uint8, device="cuda")
     st = torch.full((2,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
     qq = torch.full((2,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
@@ -485,7 +386,7 @@ def test_gpu_python_argument_errors(dec):
     import torch
     import nhwcodec_amd as na
     files, _ = _batch("two")
-    a = _arena(files)
+    a = device_arena(files)
     fmt = na.TensorFormat("float32", "CHW", "RGB", "reversed")
     room = 2 * 3 * 512 * 512
     buf = torch.full((room + 8,), 7.0, dtype=torch.float32, device="cuda")

@@ -18,10 +18,9 @@ import numpy as np
 import pytest
 
 from oracle.harness import class_image
-from tests.test_scaled_decode import _arena, _golden
-from tests.test_tensor_decode import ALL_FORMATS, CONSTANTS, DTYPES, SENTINEL, expected_tensor
+from tests.support import ROOT, device_arena, golden, load_lib
+from tests.tensor_cases import ALL_FORMATS, CONSTANTS, DTYPES, SENTINEL, expected_tensor
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NHW_E_ARG, NHW_E_QUALITY = -4, -1
 IMG = 786432
 GUARD = 4096
@@ -191,7 +190,7 @@ def test_header_declares_the_entry_points_and_the_picture_struct():
     assert "typedef struct { uint64_t addr, pitch, plane; uint32_t width, height, first_tile, reserved; } nhw_tensor_picture;" in hdr
     assert np.dtype(na.TENSOR_PICTURE_DTYPE).itemsize == 40
     assert [n for n, _ in na.TENSOR_PICTURE_DTYPE] == ["addr", "pitch", "plane", "width", "height", "first_tile", "reserved"]
-    lib = ctypes.CDLL(na.LIB_PATH)
+    lib = load_lib()
     for name in ("nhw_tensor_to_bytes_device", "nhw_enc_batch_device_tensor", "nhw_tile_tensors_device"):
         assert hasattr(lib, name), name
 
@@ -247,8 +246,7 @@ def test_python_argument_errors_without_a_device():
 # ---------------------------------------------------------------- GPU
 @pytest.fixture(scope="module")
 def lib():
-    import nhwcodec_amd as na
-    return na.load_library()
+    return load_lib()
 
 
 def _guarded(nbytes):
@@ -391,7 +389,7 @@ def _class_pictures():
 
 
 def _decoded_form(px, fmt):
-    """what a decode under fmt stores for the byte pictures px [n, 512, 512, 3]: bit patterns in fmt's layout (tests/test_tensor_decode.py)"""
+    """what a decode under fmt stores for the byte pictures px [n, 512, 512, 3]: bit patterns in fmt's layout (tests/tensor_cases.py)"""
     return np.stack([expected_tensor(p, fmt) for p in px])
 
 
@@ -438,12 +436,12 @@ def test_gpu_round_trip(enc, dtype, constants):
     """decode_tensor_device(fmt) of three committed files, then encode_tensor_device(fmt.inverted()): the files of decode_device + encode_device"""
     import torch
     import nhwcodec_amd as na
-    files = [_golden("q20_0.nhw"), _golden("q10_0.nhw"), _golden("q23_0.nhw")]
+    files = [golden("q20_0.nhw"), golden("q10_0.nhw"), golden("q23_0.nhw")]
     fmt = na.TensorFormat(dtype, "CHW", "RGB", "reversed", **CONSTANTS[constants])
     dec = na.Decoder(0, max_batch=3)
     try:
-        t, st, _ = dec.decode_tensor_device(*_arena(files), fmt)
-        px, st2, _ = dec.decode_device(*_arena(files))
+        t, st, _ = dec.decode_tensor_device(*device_arena(files), fmt)
+        px, st2, _ = dec.decode_device(*device_arena(files))
         torch.cuda.synchronize()
         assert not bool(st.any()) and not bool(st2.any())
         got = _encode(enc, enc.encode_tensor_device, t, fmt.inverted(), 20)
