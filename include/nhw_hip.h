@@ -438,6 +438,42 @@ int nhw_resize_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_w
  * status is not NHW_OK leaves its destination untouched. */
 int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status);
+/* ---- the area filter: shrink without aliasing ----
+ * The two-tap rule above is right for reductions below 2.  The area rule is the same definition with other taps: P, the output size, the flag,
+ * the mirror, the format and the layout are those of the section above, and each axis -- source length n (1 .. 65535), output length m
+ * (1 .. 4096) -- gives output index o a list of taps (i, weight) and an axis total A, in integers:
+ *   an axis that does not shrink (m >= n): the two taps above, (i0, 256 - f) and (i1, f), A = 256;
+ *   an axis that shrinks (m < n): in units of 1 / m source pixel, source pixel i covers [i m, (i + 1) m) and output o covers [o n, (o + 1) n);
+ *     the taps are i = floor(o n / m) .. ceil((o + 1) n / m) - 1 with weight min((i + 1) m, (o + 1) n) - max(i m, o n) -- every weight is 1 .. m,
+ *     they sum to n, and A = n.  (o + 1) n <= 4096 x 65535 < 2^28;
+ *   byte of output pixel (oy, ox), channel c: S = sum over y taps, x taps of wy wx P[y][x][c], D = Ay Ax, byte = floor((2 S + D) / (2 D)) -- the
+ *     weighted mean rounded to nearest, halves up.  A row's sum of wx P is at most 255 x 65535 < 2^24; S <= 255 D < 2^40 and D < 2^32, so the sum
+ *     over rows and the division are 64 bits wide;
+ *   the reduction limit: n <= NHW_AREA_MAX_REDUCTION m on each axis (at most 129 taps an axis; a 65535-pixel side still reaches 512).
+ * With out_width >= w and out_height >= h this is the two-tap rule bit for bit (D = 65536); with w = k out_width and h = k out_height it is the
+ * k x k box mean floor((2 sum + k k) / (2 k k)).
+ * nhw_area_to_tensor_device: nhw_resize_to_tensor_device under the area rule -- the same arguments, reads, writes, passed-over entries and
+ * NHW_E_ARG cases, stream-ordered and capturable; an entry beyond the reduction limit on either axis is passed over as well: nothing is written
+ * for it.
+ * nhw_dec_crops_to_device_filter: nhw_dec_crops_to_device with the filter named.  NHW_FILTER_TWO_TAP is that call itself (the same path, bytes
+ * and statistics); NHW_FILTER_AREA resizes the windows under the area rule; any other value is a call-level NHW_E_ARG.  With the area filter a
+ * rect whose window is beyond the reduction limit for the call's output size gets status NHW_E_ARG: it selects no tile, its destination is not
+ * written, and the other rects go on.
+ * nhw_enc_pictures_resized: nhw_enc_pictures with the area rule in front -- n packed pictures of any sizes (as there) to n .nhwp containers of
+ * out_width x out_height (1 .. 4096 each); container i is byte for byte what nhw_enc_pictures writes for the rule's picture of picture i (no
+ * mirror) at that quality.  The pictures are uploaded, resized by one launch into a buffer of the handle, and tiled and encoded from there.
+ * NHW_E_ARG, before anything is uploaded: the cases of nhw_enc_pictures, an output side outside 1 .. 4096 and a picture beyond the reduction
+ * limit; NHW_E_QUALITY as there. */
+#define NHW_FILTER_TWO_TAP 0
+#define NHW_FILTER_AREA 1
+#define NHW_AREA_MAX_REDUCTION 128
+int nhw_area_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                              const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream);
+int nhw_dec_crops_to_device_filter(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                   uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status,
+                                   int filter);
+int nhw_enc_pictures_resized(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                             uint32_t out_width, uint32_t out_height, int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status);
 
 /* ---- encode straight from training tensors ----
  * The mirror of the section above: the encoder reads its pictures under an nhw_tensor_format -- the same struct, the same enums.  For this

@@ -112,6 +112,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_dec_crops_to_device.argtypes = [P, P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(CTensorFormat), P, P, P]
     L.nhw_enc_batch_device_tensor.argtypes = [P, P, ctypes.c_int, ctypes.POINTER(CTensorFormat), ctypes.c_int, P, P, P, P]
     L.nhw_tile_tensors_device.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
+    L.nhw_area_to_tensor_device.argtypes = L.nhw_resize_to_tensor_device.argtypes
+    L.nhw_dec_crops_to_device_filter.argtypes = L.nhw_dec_crops_to_device.argtypes + [ctypes.c_int]
+    L.nhw_enc_pictures_resized.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, P, ctypes.c_size_t, P, P]
     return L
 
 
@@ -470,18 +473,40 @@ def crop_window(x: int, y: int, w: int, h: int, scale: int) -> tuple:
     return x // scale, y // scale, -(-(x + w) // scale) - x // scale, -(-(y + h) // scale) - y // scale
 
 
-def resize_to_tensor_device(pictures, size, fmt, flips=None):
+FILTERS = {"two_tap": 0, "area": 1}                # NHW_FILTER_TWO_TAP, NHW_FILTER_AREA
+AREA_MAX_REDUCTION = 128                           # NHW_AREA_MAX_REDUCTION: the area filter takes a side down to 1 / 128 at the most
+
+
+def _filter(filter, what):
+    """the checked NHW_FILTER_* value of a filter name"""
+    if not isinstance(filter, str) or filter not in FILTERS:
+        raise NhwError(f"{what}: `filter` must be one of {', '.join(repr(k) for k in FILTERS)}, got {filter!r}")
+    return FILTERS[filter]
+
+
+def _area_limit(w, h, out_w, out_h, what, which):
+    if w > AREA_MAX_REDUCTION * out_w or h > AREA_MAX_REDUCTION * out_h:
+        raise NhwError(f"{what}: {which} is {w} x {h}, more than {AREA_MAX_REDUCTION} times the output's {out_w} x {out_h} along a side: beyond the area filter's limit")
+
+
+def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     """Pictures of any sizes to one batch tensor of one size (k_resize_to_tensor, nhw_resize_to_tensor_device): a list of uint8 CUDA tensors
     [H, W, 3] as for pictures_to_tensor_device, size = (out_h, out_w) of 1 .. 4096 each, flips: None or one boolean a picture ("mirror
     left-right") -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Picture k is resampled under the integer rule
     of DESIGN.md section 18 (centre-aligned, two taps a direction, weights in 1/256), mirrored, and converted under TensorFormat's value
-    rule.  Reads only the pictures' own bytes.  Ordered on torch's current stream."""
+    rule.  filter="area" (k_area_to_tensor, nhw_area_to_tensor_device): an axis that shrinks takes the exact box mean
+    instead, which does not alias; a picture more than AREA_MAX_REDUCTION times the output along a side is refused.  Reads only the
+    pictures' own bytes.  Ordered on torch's current stream."""
     import torch
     what = "resize_to_tensor_device"
+    filter = _filter(filter, what)
     fmt = _tensor_format(fmt, what)
     out_h, out_w = _crop_size(size, what)
     table, _, dev = _picture_table(pictures, what)
     n = len(pictures)
+    if filter == FILTERS["area"]:
+        for i, x in enumerate(pictures):
+            _area_limit(int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
     flags = _crop_flips(flips, n, what)
     out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
     addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (3 * out_h * out_w * out.element_size())
@@ -490,8 +515,9 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None):
     L = _library()
     c = fmt.c_struct()
     with torch.cuda.device(dev):
-        rc = L.nhw_resize_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                                           addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        call = L.nhw_area_to_tensor_device if filter == FILTERS["area"] else L.nhw_resize_to_tensor_device
+        rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                  addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -922,6 +948,40 @@ class Encoder:
             raise NhwError(f"per-picture status {status.tolist()}")
         return _split(arena, offs)
 
+    def encode_pictures_resized(self, pictures, size, quality: int = QUALITY_DEFAULT):
+        """encode_pictures with the area filter in front (nhw_enc_pictures_resized): pictures as there, size = (out_h,
+        out_w) of 1 .. 4096 each -> a list of .nhwp containers of out_w x out_h pictures: thumbnails, a fixed-resolution set.  Picture i is
+        resized on the device under the area rule (no mirror) and container i is encode_pictures' for that picture, byte for byte.  A picture
+        more than AREA_MAX_REDUCTION times the output along a side is refused.  Raises on a per-picture failure."""
+        import numpy as np
+        what = "encode_pictures_resized"
+        out_h, out_w = _crop_size(size, what)
+        n, blob, in_off, width, height, _, _ = self._host_pictures(pictures, what)
+        for i in range(n):
+            _area_limit(int(width[i]), int(height[i]), out_w, out_h, what, f"picture {i}")
+        arena = np.empty(n * (16 + picture_tiles(out_w, out_h) * (4 + OUT_STRIDE)), np.uint8)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_enc_pictures_resized(self.h, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n, out_w, out_h, quality,
+                                                    arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-picture status {status.tolist()}")
+        return _split(arena, offs)
+
+    def encode_resized_device(self, pictures, quality: int = QUALITY_DEFAULT, out=None):
+        """Any photo to one .nhw file: pictures, a list of at most max_batch uint8 CUDA tensors [H, W, 3] as for tile_pictures_device (crop views
+        work), each resized to one 512 x 512 picture under the area rule (resize_to_tensor_device with filter="area")
+        and encoded by encode_device -> (out[n,OUT_STRIDE], sizes[n], status[n]) on device, the files of encode_device on the rule's
+        pictures, byte for byte."""
+        what = "encode_resized_device"
+        if not isinstance(pictures, (list, tuple)) or not 1 <= len(pictures) <= self.max_batch:
+            raise NhwError(f"{what} wants a list of 1 .. max_batch = {self.max_batch} uint8 CUDA tensors [H, W, 3]")
+        dev = getattr(pictures[0], "device", None)                   # (the resize checks that all pictures are on one device)
+        if dev is not None and dev.type == "cuda" and dev.index != self.device:
+            raise NhwError(f"the pictures are on cuda:{dev.index}, this encoder on cuda:{self.device}")
+        bgr = resize_to_tensor_device(pictures, (512, 512), TensorFormat("uint8", "HWC", "BGR", "file"), filter="area")
+        return self.encode_device(bgr, quality, out)
+
     def encode_pictures_fit(self, pictures, max_bytes, ladder=None):
         """The best .nhwp within a byte budget (nhw_enc_fit_pictures): pictures as for encode_pictures; max_bytes: an int or one per picture,
         the budget for the whole container -> (containers, qualities, status), lists of n.  Picture i gets the container of the first quality
@@ -1330,18 +1390,21 @@ class Decoder:
         return self._regions_device(containers, rects, out, "decode_windows_device",
                                     lambda *a: self.lib.nhw_dec_windows_to_device(self.h, *a[:5], scale, *a[5:]))
 
-    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None):
+    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap"):
         """RandomResizedCrop's decode (nhw_dec_crops_to_device): crops, a sequence of (container index, x, y, w, h), each
         resampled to size = (out_h, out_w), mirrored left-right where flips[i] is true, and stored under fmt -> (tensor [n, 3, out_h, out_w]
         or [n, out_h, out_w, 3] of fmt.dtype on this decoder's device, the list of the scales used).  With a scale (1, 2 or 4) the crops
         are windows at that scale, as for decode_windows, and go down in one call.  With scale=None they are rectangles of the full-resolution
         pictures: crop i is decoded at crop_scale(w, h, out_w, out_h), as the window crop_window(x, y, w, h, that scale), and the crops of
         one scale go down together -- three calls at the most, each decoding the union of its windows' tiles once.  out: a contiguous tensor of
-        fmt.dtype with at least n * 3 * out_h * out_w elements on this device, which is filled.  Raises on any status that is not NHW_OK.  The
+        fmt.dtype with at least n * 3 * out_h * out_w elements on this device, which is filled.  filter="area" resizes the windows under the area
+        rule (nhw_dec_crops_to_device_filter): the scales and windows are chosen as before, and a window more than
+        AREA_MAX_REDUCTION times the output along a side is refused before any call.  Raises on any status that is not NHW_OK.  The
         work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls."""
         import numpy as np
-        t = self.torch
         what = "decode_crops_device"
+        filter = _filter(filter, what)
+        t = self.torch
         fmt = _tensor_format(fmt, what)
         out_h, out_w = _crop_size(size, what)
         if scale is not None:
@@ -1359,6 +1422,9 @@ class Decoder:
             scales = sc.tolist()
         else:
             scales = [scale] * n
+        if filter == FILTERS["area"]:
+            for i, r in enumerate(table):
+                _area_limit(int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
         dev = t.device("cuda", self.device)
         shape = (n,) + fmt.shape(out_h, out_w)
         per = 3 * out_h * out_w
@@ -1374,8 +1440,9 @@ class Decoder:
             idx = np.flatnonzero(np.array(scales) == s)
             sub, a, st = np.ascontiguousarray(table[idx]), np.ascontiguousarray(addr[idx]), np.empty(len(idx), np.int32)
             f = np.ascontiguousarray(flags[idx]) if flags is not None else None
-            self._chk(self.lib.nhw_dec_crops_to_device(self.h, blob.ctypes.data, offs.ctypes.data, len(containers), sub.ctypes.data, len(idx), s, out_w, out_h,
-                                                       ctypes.byref(c), f.ctypes.data if f is not None else None, a.ctypes.data, st.ctypes.data))
+            args = (self.h, blob.ctypes.data, offs.ctypes.data, len(containers), sub.ctypes.data, len(idx), s, out_w, out_h,
+                    ctypes.byref(c), f.ctypes.data if f is not None else None, a.ctypes.data, st.ctypes.data)
+            self._chk(self.lib.nhw_dec_crops_to_device_filter(*args, filter) if filter else self.lib.nhw_dec_crops_to_device(*args))
             status[idx] = st
         self._region_raise(status)
         return (out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)), scales

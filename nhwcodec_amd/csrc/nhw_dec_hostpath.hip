@@ -1,5 +1,5 @@
 /* nhw_dec_hostpath.hip -- the decoder's host conveniences: files in host memory in, pictures out (nhw_dec_batch), pictures of any size and regions of them out of
- * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
+ * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
 #include "nhw_dec.h"
 #include "nhw_tensor.h"
 
@@ -217,8 +217,9 @@ static void source_look(RegionSource &c, const uint8_t *base, size_t len)   /* t
  * window's status is the worst of its own tiles'.
  * The crop call is the third form: `crop` set, dst_addr the tensors' addresses.  The windows are cropped into the handle's
  * staging as for the host form and stay there; behind the last chunk one k_resize_to_tensor takes every window whose tiles all decoded to its
- * tensor -- the others get the address 0, which the kernel passes over. */
-struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; };
+ * tensor -- the others get the address 0, which the kernel passes over.  With the area filter that launch is
+ * k_area_to_tensor, and a rect whose window is beyond the reduction limit for the output size is NHW_E_ARG before it selects a tile. */
+struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter; };
 
 static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
                        const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, bool merge = true,
@@ -248,6 +249,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		const nhw_rect &r = rects[i];
 		status[i] = NHW_E_ARG;
 		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
+		if (crop && crop->filter == NHW_FILTER_AREA && (r.width > NHW_AREA_MAX_REDUCTION * crop->out_w || r.height > NHW_AREA_MAX_REDUCTION * crop->out_h)) continue;
 		RegionSource &c = src[r.container];
 		const uint8_t *base = blob + off[r.container];
 		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
@@ -325,8 +327,9 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 		HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
 		if (crop->flags) HIPCHK(hipMemcpyAsync(tab + pics_bytes + addr_bytes, crop->flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		HIPCHK(nhw_launch_resize_to_tensor((const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
-		                                   crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
+		const auto launch = crop->filter == NHW_FILTER_AREA ? nhw_launch_area_to_tensor : nhw_launch_resize_to_tensor;
+		HIPCHK(launch((const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
+		              crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
 		HIPCHK(hipStreamSynchronize(s));
 		return NHW_OK;
 	}
@@ -361,15 +364,23 @@ extern "C" int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const 
 
 /* nhw_dec_windows_to_device with a resize behind it: window i, resampled to out_width x out_height and mirrored where bit 0 of
  * flags[i] is set, to the tensor at dst_addr[i] */
-extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status)
+extern "C" int nhw_dec_crops_to_device_filter(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status,
+                                              int filter)
 {
 	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (filter != NHW_FILTER_TWO_TAP && filter != NHW_FILTER_AREA) { nhw_dec_err = "nhw_dec_crops_to_device: the filter must be NHW_FILTER_TWO_TAP or NHW_FILTER_AREA"; return NHW_E_ARG; }
 	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_crops_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	CropSpec c = { out_width, out_height, 0, 0, {}, flags };
+	CropSpec c = { out_width, out_height, 0, 0, {}, flags, filter };
 	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
 	c.dtype = fmt->dtype; c.layout = fmt->layout;
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", true, &c);
+}
+
+extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status)
+{
+	return nhw_dec_crops_to_device_filter(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, status, NHW_FILTER_TWO_TAP);
 }
 
 extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)

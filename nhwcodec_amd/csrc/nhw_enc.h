@@ -81,8 +81,9 @@ struct nhw_enc {
 	nhw_fit_stats fit_stats;
 	bool fit_done;
 	/* grow-only.  nhw_enc_pictures and the picture searches: the uploaded pictures and their descriptor table; nhw_enc_fit_sse_pictures: a
-	 * chunk's decoded tiles; the decoder's offsets (a chunk), the open pictures' SSE, the decoder's status (a chunk) */
-	GrowBuf pic_px, pic_desc, pfit_px, pfit_aux;
+	 * chunk's decoded tiles; the decoder's offsets (a chunk), the open pictures' SSE, the decoder's status (a chunk);
+	 * nhw_enc_pictures_resized: the resized pictures, their descriptor table and the resize's address table */
+	GrowBuf pic_px, pic_desc, pfit_px, pfit_aux, pic_resized;
 };
 
 inline DevSet host_set(nhw_enc *e, size_t n)   /* input slot, output slot, compacted output, sizes, status, offsets: the host path for n images */

@@ -118,7 +118,7 @@ extern "C" void nhw_enc_destroy(nhw_enc *e)
 	dev_free({ dev_buf(e->d_tensor_bytes, 0) });
 	dev_free(fit_set(e));
 	dev_free(fit_sse_set(e));
-	for (GrowBuf *g : { &e->pic_px, &e->pic_desc, &e->pfit_px, &e->pfit_aux }) nhw_grow_free(*g);
+	for (GrowBuf *g : { &e->pic_px, &e->pic_desc, &e->pfit_px, &e->pfit_aux, &e->pic_resized }) nhw_grow_free(*g);
 	if (e->h_fit_count) (void)hipHostFree(e->h_fit_count);
 	for (int i = 0; i < 2; i++) if (e->fit_ev[i]) (void)hipEventDestroy(e->fit_ev[i]);
 	for (int i = 0; i < EV_COUNT; i++) if (e->ev[i]) (void)hipEventDestroy(e->ev[i]);

@@ -145,16 +145,29 @@ extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics,
 	return NHW_OK;
 }
 
-/* ... and resampled to one size on the way: the pictures of a table to out_width x out_height tensors, one pass */
+/* ... and resampled to one size on the way: the pictures of a table to out_width x out_height tensors, one pass of `launch` -- the two-tap
+ * kernel or the area kernel (section 19) */
+static int resize_entry(const char *who, decltype(nhw_launch_resize_to_tensor) *launch, const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height,
+                        const nhw_tensor_format *fmt, const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = std::string(who) + ": an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	NhwTensorArgs a;
+	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
+	HIPCHK(launch(d_pics, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_flags, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 extern "C" int nhw_resize_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                            const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
 {
-	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = "nhw_resize_to_tensor_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	NhwTensorArgs a;
-	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
-	HIPCHK(nhw_launch_resize_to_tensor(d_pics, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_flags, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
+	return resize_entry("nhw_resize_to_tensor_device", nhw_launch_resize_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+}
+
+extern "C" int nhw_area_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                         const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
+{
+	return resize_entry("nhw_area_to_tensor_device", nhw_launch_area_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
 }
 
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
@@ -318,24 +331,15 @@ static int put_container(uint8_t *out_arena, size_t arena_cap, uint64_t *at, uin
 	return NHW_OK;
 }
 
-/* Upload the pictures, pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch
- * its files; then one container per picture. */
-extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
-                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+/* The tiles of a table encoded (encode_tiles), then one container per picture: picture i's status is its first tile's that is not NHW_OK, and
+ * only a picture whose tiles all encoded gets a container. */
+static int encode_containers(nhw_enc *e, const nhw_picture *d_desc, const PicCall &pc, int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
 {
-	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
-	PicCall pc;
-	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures", pc); if (rc) return rc; }
-	const int tiles = pc.tiles;
-	HIPCHK(hipSetDevice(e->device));
-	{ const int rc = host_buffers(e, tiles < e->max_batch ? tiles : e->max_batch); if (rc) return rc; }
-	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
-	HIPCHK(hipMemcpyAsync(e->pic_desc.p, pc.desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, e->own_stream));
+	const int n = (int)pc.desc.size(), tiles = pc.tiles;
 	std::vector<uint8_t> files;
 	std::vector<uint32_t> lens((size_t)tiles);
 	std::vector<int32_t> tst((size_t)tiles);
-	{ const int rc = encode_tiles(e, e->pic_desc.as<nhw_picture>(), n, tiles, quality, nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
+	{ const int rc = encode_tiles(e, d_desc, n, tiles, quality, nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
 	const int *first = pc.first.data();
 	uint64_t at = 0, fpos = 0;
 	for (int i = 0; i < n; i++) {
@@ -345,13 +349,69 @@ extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *
 		out_off[i] = at;
 		status[i] = st;
 		if (st == NHW_OK) {
-			const int rc = put_container(out_arena, arena_cap, &at, width[i], height[i], lens.data() + first[i], first[i + 1] - first[i], files.data() + fpos);
+			const int rc = put_container(out_arena, arena_cap, &at, pc.desc[i].width, pc.desc[i].height, lens.data() + first[i], first[i + 1] - first[i], files.data() + fpos);
 			if (rc) return rc;
 		}
 		fpos += sum;
 	}
 	out_off[n] = at;
 	return NHW_OK;
+}
+
+/* Upload the pictures, pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch
+ * its files; then one container per picture. */
+extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	PicCall pc;
+	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures", pc); if (rc) return rc; }
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, pc.tiles < e->max_batch ? pc.tiles : e->max_batch); if (rc) return rc; }
+	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
+	HIPCHK(hipMemcpyAsync(e->pic_desc.p, pc.desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, e->own_stream));
+	return encode_containers(e, e->pic_desc.as<nhw_picture>(), pc, quality, out_arena, arena_cap, out_off, status);
+}
+
+/* nhw_enc_pictures with the area filter in front: the pictures go up as there; one k_area_to_tensor (uint8, HWC, BGR, file
+ * rows, no flags) resizes them into the handle's second picture buffer, packed out_width x out_height pictures one behind the other with their
+ * descriptor table and the launch's address table behind them; the tiles are padded and encoded from that table. */
+extern "C" int nhw_enc_pictures_resized(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                        uint32_t out_width, uint32_t out_height, int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = "nhw_enc_pictures_resized: an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	PicCall src, pc;
+	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures_resized", src); if (rc) return rc; }
+	for (int i = 0; i < n; i++)
+		if (width[i] > NHW_AREA_MAX_REDUCTION * out_width || height[i] > NHW_AREA_MAX_REDUCTION * out_height) {
+			nhw_enc_err = "nhw_enc_pictures_resized: a picture more than " + std::to_string(NHW_AREA_MAX_REDUCTION) + " times the output size along a side";
+			return NHW_E_ARG;
+		}
+	{
+		const std::vector<uint32_t> ow((size_t)n, out_width), oh((size_t)n, out_height);
+		const int rc = pictures_check(ow.data(), oh.data(), n, "nhw_enc_pictures_resized", pc);
+		if (rc) return rc;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, pc.tiles < e->max_batch ? pc.tiles : e->max_batch); if (rc) return rc; }
+	{ const int rc = pictures_upload(e, bgr, in_off, src); if (rc) return rc; }
+	const size_t per = 3 * (size_t)out_width * out_height, px_bytes = ((size_t)n * per + 15) & ~(size_t)15, desc_bytes = (size_t)n * sizeof(nhw_picture);
+	HIPCHK(nhw_grow(e->pic_resized, px_bytes + desc_bytes + (size_t)n * 8));
+	uint8_t *px = e->pic_resized.as<uint8_t>();
+	std::vector<uint64_t> addr((size_t)n);
+	for (int i = 0; i < n; i++) pc.desc[i].addr = addr[i] = (uint64_t)(uintptr_t)(px + (size_t)i * per);
+	const nhw_picture *d_desc = (const nhw_picture *)(px + px_bytes);
+	const uint64_t *d_addr = (const uint64_t *)(px + px_bytes + desc_bytes);
+	hipStream_t s = e->own_stream;
+	HIPCHK(hipMemcpyAsync(e->pic_desc.p, src.desc.data(), desc_bytes, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync((void *)d_desc, pc.desc.data(), desc_bytes, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync((void *)d_addr, addr.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+	const NhwTensorArgs bytes = { { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f }, 0, 0 };
+	HIPCHK(nhw_launch_area_to_tensor(e->pic_desc.as<nhw_picture>(), n, out_width, out_height, NHW_T_U8, NHW_T_HWC, bytes, nullptr, d_addr, s));
+	return encode_containers(e, d_desc, pc, quality, out_arena, arena_cap, out_off, status);
 }
 
 /* ------------------------------------------------------------------------------------------------ distortion */

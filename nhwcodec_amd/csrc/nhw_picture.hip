@@ -3,7 +3,7 @@
  * share one body (crop_band over copy_rows) and differ in how a workgroup learns its tile and its rectangle -- k_untile_crop (k_tile_pad's
  * inverse: the whole picture, also from the 256 and 128 tiles of a scaled decode), k_untile_region (first_tile search) and k_untile_window (use
  * table) --; the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16) and its resampling form k_resize_to_tensor
- * (section 18), its mirrors k_tensor_to_bytes and k_tile_pad_tensor (section 17), and the .nhwp container that holds a picture's width, height
+ * (section 18) with its area-filter form k_area_to_tensor (section 19), its mirrors k_tensor_to_bytes and k_tile_pad_tensor (section 17), and the .nhwp container that holds a picture's width, height
  * and tile files.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
@@ -411,6 +411,107 @@ __global__ __launch_bounds__(TP_THREADS) void k_resize_to_tensor(const nhw_pictu
 	}
 }
 
+/* ---- the area filter: k_resize_to_tensor's rule where an axis does not shrink, the exact box mean where it does ----
+ * The taps of output index o along an axis of source length n and output length m, as a run: source pixels first .. first + count - 1, the
+ * first with weight wf, the last (count > 1) with wl, those between with m.  m >= n: section 18's two taps, 256 - f and f (one tap of 256
+ * where i1 = i0; the axis total is 256).  m < n: in units of 1 / m pixel output o covers [o n, (o + 1) n) and source pixel i [i m, (i + 1) m):
+ * first = floor(o n / m), the last pixel ceil((o + 1) n / m) - 1, each weight the overlap (the total is n).  n <= 128 m (the caller's check)
+ * makes count at most 129 and (o + 1) n at most 4096 x 65535 < 2^28.  Packed as first | count << 16 and wf | wl << 16 (both at most 4096). */
+__device__ __forceinline__ uint2 area_taps(uint32_t o, uint32_t n, uint32_t m)
+{
+	if (m >= n) {
+		const uint32_t p = resize_pos(o, n, m), f = p & 255u, two = p >> 24;
+		return make_uint2(((p >> 8) & 0xFFFFu) | (1u + two) << 16, (two ? 256u - f : 256u) | f << 16);
+	}
+	const uint32_t lo = o * n, hi = lo + n, first = lo / m, last = (hi + m - 1) / m - 1;
+	const uint32_t wf = ((first + 1) * m < hi ? (first + 1) * m : hi) - lo;
+	return make_uint2(first | (last - first + 1) << 16, wf | (hi - last * m) << 16);
+}
+
+/* sum of weight x byte over the run of x taps t (area_taps) of the row at s, a channel at a time: wf first + m (those between) + wl last;
+ * at most 255 x the axis total, below 2^24 */
+__device__ __forceinline__ void area_row(const uint8_t *__restrict__ s, uint2 t, uint32_t m, uint32_t *r)
+{
+	const uint32_t cnt = t.x >> 16, wf = t.y & 0xFFFFu, wl = t.y >> 16;
+	const uint8_t *q = s + 3 * (t.x & 0xFFFFu);
+	uint32_t mid[3] = { 0, 0, 0 };
+	for (uint32_t i = 1; i + 1 < cnt; i++) { mid[0] += q[3 * i]; mid[1] += q[3 * i + 1]; mid[2] += q[3 * i + 2]; }
+#pragma unroll
+	for (int ch = 0; ch < 3; ch++) r[ch] = wf * q[ch] + m * mid[ch];
+	if (cnt > 1) {
+#pragma unroll
+		for (int ch = 0; ch < 3; ch++) r[ch] += wl * q[3 * (cnt - 1) + ch];
+	}
+}
+
+/* floor((2 S + D) / (2 D)) for S <= 255 D, D < 2^32: the quotient is at most 255, so the float estimate (three roundings of 2^-24 each on a
+ * value below 256) is off by less than 1 and one 64-bit multiply-and-compare each way makes it exact */
+__device__ __forceinline__ uint32_t area_mean(uint64_t S, uint64_t D)
+{
+	const uint64_t N = 2 * S + D, D2 = 2 * D;
+	uint32_t q = (uint32_t)((float)N / (float)D2);
+	if ((uint64_t)q * D2 > N) q--;
+	else if ((uint64_t)(q + 1) * D2 <= N) q++;
+	return q;
+}
+
+/* k_resize_to_tensor with the taps of area_taps: the same table, formats, flags, grid (entries x bands of `rows` output rows) and walk -- a
+ * thread one output pixel at a time, 1 << lg lanes a row.  The tap runs of all out_w columns and of the band's rows go into LDS (out_w + rows
+ * entries of 8 bytes, sized by the launch) before the one barrier; they hold the kernel's only integer divisions.  A pixel then reads its
+ * rows x columns source bytes once (byte loads, any alignment and pitch, never a byte outside a row's 3 W; neighbouring lanes on neighbouring
+ * runs): every row gives three 32-bit sums (area_row), the rows between the first and the last add up in 32 bits as well (127 x 2^24 < 2^31),
+ * and only the three products with the row weights and the division are 64 bits wide.  The loops run `count` times, at most 129: an entry
+ * beyond the reduction limit on either axis stores nothing, like one with a zero or oversize side, a zero address or one that is no multiple
+ * of the element size. */
+template <int DT, int CHW>
+__global__ __launch_bounds__(TP_THREADS) void k_area_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
+                                                                NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
+{
+	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+	extern __shared__ uint2 area_tab[];                                    /* [out_w] columns, then [rows] rows */
+	const int k = blockIdx.x / bands;
+	const uint32_t r0 = (uint32_t)(blockIdx.x % bands) * (uint32_t)rows;     /* the band: output rows [r0, r0 + nr) */
+	const nhw_picture p = pics[k];
+	const uint64_t oa = out_addr[k];
+	if (!p.width || !p.height || p.width > 65535u || p.height > 65535u || !oa || (oa & (sizeof(E) - 1))) return;
+	if (out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX || rows > RS_ROWS || r0 >= out_h) return;   /* (the launcher sends neither) */
+	if (p.width > NHW_AREA_MAX_REDUCTION * out_w || p.height > NHW_AREA_MAX_REDUCTION * out_h) return;
+	const uint32_t nr = out_h - r0 < (uint32_t)rows ? out_h - r0 : (uint32_t)rows;
+	const bool mirror = flags && (flags[k] & 1);
+	uint2 *col_tap = area_tab, *row_tap = area_tab + out_w;
+	for (uint32_t o = threadIdx.x; o < out_w; o += TP_THREADS) col_tap[o] = area_taps(o, p.width, out_w);
+	if (threadIdx.x < nr) row_tap[threadIdx.x] = area_taps(r0 + threadIdx.x, p.height, out_h);
+	__syncthreads();
+	E *out = reinterpret_cast<E *>(oa);
+	const size_t W = out_w, H = out_h;
+	const uint64_t D = (uint64_t)(out_w >= p.width ? 256u : p.width) * (out_h >= p.height ? 256u : p.height);
+	for (uint32_t r = threadIdx.x >> lg; r < nr; r += TP_THREADS >> lg) {
+		const uint2 ty = row_tap[r];
+		const uint32_t cy = ty.x >> 16;
+		const uint8_t *s = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)(ty.x & 0xFFFFu) * p.pitch);
+		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
+		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
+			const uint2 tx = col_tap[mirror ? out_w - 1 - c : c];
+			uint32_t first[3], last[3] = { 0, 0, 0 }, mid[3] = { 0, 0, 0 }, b[3];
+			area_row(s, tx, out_w, first);
+			for (uint32_t i = 1; i + 1 < cy; i++) {
+				uint32_t v[3];
+				area_row(s + (uint64_t)i * p.pitch, tx, out_w, v);
+				mid[0] += v[0]; mid[1] += v[1]; mid[2] += v[2];
+			}
+			if (cy > 1) area_row(s + (uint64_t)(cy - 1) * p.pitch, tx, out_w, last);
+#pragma unroll
+			for (int ch = 0; ch < 3; ch++)
+				b[ch] = area_mean((uint64_t)(ty.y & 0xFFFFu) * first[ch] + (uint64_t)out_h * mid[ch] + (uint64_t)(ty.y >> 16) * last[ch], D);
+			const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
+			const E e1 = (E)nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
+			const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
+			if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
+			else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
+		}
+	}
+}
+
 /* ------------------------------------------------------------------------------------------------ tensors to bytes */
 /* N = 4 pixels' elements by tensor channel from a run of a tensor row: CHW three runs of N elements, `plane` bytes apart, HWC one run of 3 N.
  * ALIGN > 0: p is a multiple of it (the batch kernel); 0: looked at when running (the picture kernel's crop views) */
@@ -546,6 +647,27 @@ hipError_t nhw_launch_resize_to_tensor(const nhw_picture *d_pics, int n, uint32_
 	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
 		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
 		k_resize_to_tensor<DT, CHW><<<n * bands, TP_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+	});
+	return hipGetLastError();
+}
+
+/* The area filter: the bands of nhw_launch_resize_to_tensor (the same rule, so that both kernels meet the same launch shapes), and the LDS the
+ * band's tap runs take: 8 (out_w + rows) bytes, 33 280 at the most. */
+hipError_t nhw_launch_area_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                     const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return hipErrorInvalidValue;
+	int lg = 0;
+	while (lg < 8 && (1u << lg) < out_w) lg++;
+	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
+	uint32_t rows = (out_h + want - 1) / want;
+	if (rows < (uint32_t)(TP_THREADS >> lg)) rows = TP_THREADS >> lg;
+	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
+	const int bands = (int)((out_h + rows - 1) / rows);                 /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
+	const size_t lds = sizeof(uint2) * ((size_t)out_w + rows);
+	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
+		k_area_to_tensor<DT, CHW><<<n * bands, TP_THREADS, lds, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
 	});
 	return hipGetLastError();
 }

@@ -19,6 +19,8 @@
  *                    and not written
  *   --picture <in.bmp> <out.nhwp>   any 24-bit BMP (W, H >= 1): padded to whole 512 x 512 tiles on the device, one .nhwp container
  *                    (nhw_enc_pictures); alone, not with --max-bytes, --min-psnr, --synthetic, --tar, --tiles or --batch
+ *   --resize <W>x<H>   (with --picture, anywhere on the line) the picture is first shrunk or enlarged to W x H (1 .. 4096 each) on the device
+ *                    under the area rule (nhw_enc_pictures_resized); a picture more than NHW_AREA_MAX_REDUCTION times W or H is refused
  * --gpus G: images are independent (encoder/nhw_encoder_cli.c:175-183 is a per-image sequence), so the job is a queue of chunks of up
  * to 1024 images; one host thread per GPU, each with its own encoder handle, takes the next chunk until the queue is empty.  The work
  * descriptor {first image, count, quality, seed} lives in this process; between processes (one per GPU under torchrun) it travels by
@@ -59,8 +61,9 @@ static void usage(void)
 	        "Tar   (MI355X build): %s [-q#] --tar <in.tar> <out.tar>    (every x.bmp member of a ustar archive -> member x.nhw, in order)\n"
 	        "Budget (MI355X build): %s [-q#] --max-bytes <n> [--min-quality <m>] ...   (single file, --batch, --tiles: the highest quality from -q# down to m whose file fits n bytes)\n"
 	        "PSNR (MI355X build): %s [-q#] --min-psnr <dB> [--min-quality <m>] ...   (single file, --batch, --tiles: the lowest quality from m up to -q# whose decoded picture reaches dB)\n"
-	        "Picture (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp>   (any size: padded 512x512 tiles and the real size in one container)\n",
-	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
+	        "Picture (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp>   (any size: padded 512x512 tiles and the real size in one container)\n"
+	        "Resize (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp> --resize <W>x<H>   (the picture resized to W x H, 1..4096 each, by the area filter first)\n",
+	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
 }
 
 static void version(void)
@@ -206,21 +209,29 @@ static uint8_t *load_bmp_picture(const char *path, uint32_t *w, uint32_t *h)
 	return px;
 }
 
-static int encode_picture(const char *in_path, const char *out_path, int quality, int stock_compat)
+/* out_w, out_h: the size of --resize, 0 without it */
+static int encode_picture(const char *in_path, const char *out_path, int quality, int stock_compat, uint32_t out_w, uint32_t out_h)
 {
 	uint32_t w = 0, h = 0;
 	uint8_t *px = load_bmp_picture(in_path, &w, &h), *arena;
-	const int t = nhw_picture_tiles(w, h);
+	const int t = out_w ? nhw_picture_tiles(out_w, out_h) : nhw_picture_tiles(w, h);
 	const size_t cap = 16 + (size_t)t * (4 + NHW_OUT_STRIDE);
 	uint64_t in_off[2] = { 0, 3ull * w * h }, off[2];
 	int32_t st = 0;
 	nhw_enc *enc = NULL;
 	int rc;
+	if (out_w && (w > NHW_AREA_MAX_REDUCTION * out_w || h > NHW_AREA_MAX_REDUCTION * out_h)) {   /* before any GPU work */
+		fprintf(stderr, "%s: --resize: the %ux%u picture is more than %d times %ux%u along a side\n", PROGRAM, (unsigned)w, (unsigned)h, NHW_AREA_MAX_REDUCTION, (unsigned)out_w, (unsigned)out_h);
+		return 1;
+	}
 	if ((rc = nhw_enc_create(0, t < 1024 ? t : 1024, &enc))) die_lib("nhw_enc_create", rc);   /* (the batch modes' chunk) */
 	if (stock_compat) nhw_enc_set_compat(enc, NHW_COMPAT_GLIBC_ONESHOT);
 	arena = (uint8_t *)malloc(cap);
 	if (!arena) { fprintf(stderr, "%s: out of memory\n", PROGRAM); exit(-1); }
-	if ((rc = nhw_enc_pictures(enc, px, in_off, &w, &h, 1, quality, arena, cap, off, &st))) die_lib("nhw_enc_pictures", rc);
+	if (out_w) {
+		if ((rc = nhw_enc_pictures_resized(enc, px, in_off, &w, &h, 1, out_w, out_h, quality, arena, cap, off, &st))) die_lib("nhw_enc_pictures_resized", rc);
+		w = out_w; h = out_h;
+	} else if ((rc = nhw_enc_pictures(enc, px, in_off, &w, &h, 1, quality, arena, cap, off, &st))) die_lib("nhw_enc_pictures", rc);
 	nhw_enc_destroy(enc);
 	free(px);
 	if (st) { fprintf(stderr, "%s: %s: encoder status %d (code book overflow)\n", PROGRAM, in_path, st); free(arena); return 1; }
@@ -511,10 +522,21 @@ int main(int argc, char **argv)
 	int stock_compat = 0;   /* --stock-compat: NHW_COMPAT_GLIBC_ONESHOT, the stock binary's out-of-bounds reads (include/nhw_hip.h) */
 	const char *max_bytes_arg = NULL, *min_quality_arg = NULL;   /* --max-bytes, --min-quality, --min-psnr: checked once the flags are read */
 	const char *min_psnr_arg = NULL;
+	const char *resize_arg = NULL;                               /* --resize: may stand behind the file names, so it is taken off the line first */
+	uint32_t resize_w = 0, resize_h = 0;
 	nhw_dec *dec = NULL;
 	nhw_enc *enc = NULL;
 	int rc;
 
+	for (i = 1; i < argc; i++)
+		if (!strcmp(argv[i], "--resize")) {
+			int k;
+			const int took = i + 1 < argc ? 2 : 1;
+			resize_arg = took == 2 ? argv[i + 1] : "";
+			for (k = i; k + took < argc; k++) argv[k] = argv[k + took];
+			argc -= took;
+			break;
+		}
 	while (argc > 1 && argv[1][0] == '-') {
 		if (!strcmp(argv[1], "--batch") && argc > 2) { batch_dir = argv[2]; argc -= 2; argv += 2; continue; }
 		if (!strcmp(argv[1], "--synthetic") && argc > 2) { synthetic = atoi(argv[2]); argc -= 2; argv += 2; continue; }
@@ -574,6 +596,19 @@ int main(int argc, char **argv)
 	if (picture && (max_bytes_arg || min_psnr_arg || min_quality_arg || synthetic > 0 || tar || tiles || batch_dir)) {   /* before any GPU work */
 		fprintf(stderr, "%s: --picture works alone, not with --max-bytes, --min-psnr, --min-quality, --synthetic, --tar, --tiles or --batch\n", PROGRAM);
 		return 1;
+	}
+	if (resize_arg) {                                                /* before any GPU work */
+		char *end, *end2 = NULL;
+		long rw, rh;
+		if (!picture) { fprintf(stderr, "%s: --resize works with --picture only\n", PROGRAM); return 1; }
+		rw = strtol(resize_arg, &end, 10);
+		rh = *end == 'x' ? strtol(end + 1, &end2, 10) : 0;
+		if (end == resize_arg || *end != 'x' || end2 == end + 1 || *end2 || resize_arg[0] == '-' || resize_arg[0] == '+' || end[1] == '-' || end[1] == '+') {
+			fprintf(stderr, "%s: --resize wants <W>x<H>, got '%s'\n", PROGRAM, resize_arg);
+			return 1;
+		}
+		if (rw < 1 || rw > 4096 || rh < 1 || rh > 4096) { fprintf(stderr, "%s: --resize: the sides must be 1..4096, got '%s'\n", PROGRAM, resize_arg); return 1; }
+		resize_w = (uint32_t)rw; resize_h = (uint32_t)rh;
 	}
 	if (max_bytes_arg || min_quality_arg || min_psnr_arg) {          /* before any GPU work */
 		char *end;
@@ -647,7 +682,7 @@ int main(int argc, char **argv)
 
 	if (argc < 3) { printf("Not enough arguments. Check help.\n"); usage(); return 0; }
 	if (tar) return encode_tar(argv[1], argv[2], quality, stock_compat);
-	if (picture) return encode_picture(argv[1], argv[2], quality, stock_compat);
+	if (picture) return encode_picture(argv[1], argv[2], quality, stock_compat, resize_w, resize_h);
 	if (tiles) {
 		int ny = 0, nx = 0, n, bad, t;
 		uint8_t *imgs = load_bmp_tiles(argv[1], &ny, &nx);
