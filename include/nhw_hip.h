@@ -474,6 +474,38 @@ int nhw_dec_crops_to_device_filter(nhw_dec *d, const uint8_t *blob, const uint64
                                    int filter);
 int nhw_enc_pictures_resized(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
                              uint32_t out_width, uint32_t out_height, int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status);
+/* ---- the cubic filter: a kernel with lobes ----
+ * The Keys cubic with a = -1/2 (PIL's BICUBIC, torch's bicubic with antialias), its support widened with the reduction, as one integer rule.
+ * P, the output size, the flag, the mirror, the format and the layout are those of the two sections above.  The rule is separable; each axis
+ * has source length n (1 .. 65535), output length m (1 .. 4096) and D = max(n, m).  Every division is a floor division, also of a negative
+ * numerator; every shift is arithmetic.
+ *   the reduction limit: n <= NHW_CUBIC_MAX_REDUCTION m on each axis (at most 129 taps an axis);
+ *   distance of source pixel i from output index o: N = (2 i + 1) m - (2 o + 1) n (2 m times the distance of the centres, in source pixels),
+ *     U = floor((1024 |N| + D) / (2 D)), in 1/1024 of the kernel's unit: a source pixel when enlarging, n / m source pixels when shrinking;
+ *   the taps of o: the i in 0 .. n - 1 with U < 2048, one contiguous run, cut at the picture's edges (not replicated);
+ *   raw weight (the cubic times 2^31, exact in 64 bits): r = 3 U^3 - 5120 U^2 + 2^31 for U <= 1024, else r = -U^3 + 5120 U^2 - 8 x 2^20 U + 2^32
+ *     (r(0) = 2^31, r(1024) = r(2048) = 0, negative between);
+ *   quantised weight: R = sum of r over the run (positive), q_i = floor((2^15 r_i + R) / (2 R)), then 2^14 - sum q is added to the tap with the
+ *     largest q, the lowest index among equals: a run's weights sum to exactly 16384;
+ *   horizontal pass, source row y, output column ox: H[y][ox][c] = (sum_x qx P[y][x][c] + 128) >> 8 (units of 1/64; it can be negative);
+ *   vertical pass and the byte: V = sum_y qy H[y][ox][c], byte = clamp((V + 2^19) >> 20, 0, 255);
+ *   widths: sum |q| of a run stays below 2^15 (20 484 at the most on the axes the tests walk), so |sum qx P| < 2^23, |H| < 2^15, |V| < 2^30.
+ * With n = m a run is one tap of 16384 (beside two of 0): the picture comes back byte for byte.
+ * nhw_resample_to_tensor_device: nhw_resize_to_tensor_device with the filter named -- NHW_FILTER_TWO_TAP and NHW_FILTER_AREA are the two calls
+ * above themselves, NHW_FILTER_CUBIC resamples under this rule: the same arguments, reads, writes, passed-over entries and NHW_E_ARG cases,
+ * stream-ordered and capturable; an entry beyond the filter's reduction limit on either axis is passed over as well.  Any other filter is
+ * NHW_E_ARG and nothing is launched.
+ * nhw_dec_crops_to_device_resample: nhw_dec_crops_to_device_filter for the filters 0 .. 2.  Filters 0 and 1 are that call itself (the same
+ * path, bytes, statuses and statistics); NHW_FILTER_CUBIC resizes the windows under this rule, and a rect whose window is beyond 32 times the
+ * call's output size on a side gets status NHW_E_ARG: it selects no tile, its destination is not written, and the other rects go on.  Any
+ * other filter is a call-level NHW_E_ARG.  (nhw_dec_crops_to_device_filter itself keeps refusing everything but 0 and 1.) */
+#define NHW_FILTER_CUBIC 2
+#define NHW_CUBIC_MAX_REDUCTION 32
+int nhw_resample_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                  const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream);
+int nhw_dec_crops_to_device_resample(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                     uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
+                                     int *status, int filter);
 
 /* ---- encode straight from training tensors ----
  * The mirror of the section above: the encoder reads its pictures under an nhw_tensor_format -- the same struct, the same enums.  For this

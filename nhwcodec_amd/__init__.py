@@ -114,6 +114,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_tile_tensors_device.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CTensorFormat), P, P]
     L.nhw_area_to_tensor_device.argtypes = L.nhw_resize_to_tensor_device.argtypes
     L.nhw_dec_crops_to_device_filter.argtypes = L.nhw_dec_crops_to_device.argtypes + [ctypes.c_int]
+    a = L.nhw_resize_to_tensor_device.argtypes
+    L.nhw_resample_to_tensor_device.argtypes = a[:4] + [ctypes.c_int] + a[4:]
+    L.nhw_dec_crops_to_device_resample.argtypes = L.nhw_dec_crops_to_device_filter.argtypes
     L.nhw_enc_pictures_resized.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, P, ctypes.c_size_t, P, P]
     return L
 
@@ -475,18 +478,28 @@ def crop_window(x: int, y: int, w: int, h: int, scale: int) -> tuple:
 
 FILTERS = {"two_tap": 0, "area": 1}                # NHW_FILTER_TWO_TAP, NHW_FILTER_AREA
 AREA_MAX_REDUCTION = 128                           # NHW_AREA_MAX_REDUCTION: the area filter takes a side down to 1 / 128 at the most
+RESAMPLERS = {"two_tap": 0, "area": 1, "cubic": 2}  # FILTERS and NHW_FILTER_CUBIC: what the `filter` arguments take
+CUBIC_MAX_REDUCTION = 32                           # NHW_CUBIC_MAX_REDUCTION: the cubic filter takes a side down to 1 / 32 at the most
 
 
 def _filter(filter, what):
     """the checked NHW_FILTER_* value of a filter name"""
-    if not isinstance(filter, str) or filter not in FILTERS:
-        raise NhwError(f"{what}: `filter` must be one of {', '.join(repr(k) for k in FILTERS)}, got {filter!r}")
-    return FILTERS[filter]
+    if not isinstance(filter, str) or filter not in RESAMPLERS:
+        raise NhwError(f"{what}: `filter` must be one of {', '.join(repr(k) for k in RESAMPLERS)}, got {filter!r}")
+    return RESAMPLERS[filter]
 
 
 def _area_limit(w, h, out_w, out_h, what, which):
     if w > AREA_MAX_REDUCTION * out_w or h > AREA_MAX_REDUCTION * out_h:
         raise NhwError(f"{what}: {which} is {w} x {h}, more than {AREA_MAX_REDUCTION} times the output's {out_w} x {out_h} along a side: beyond the area filter's limit")
+
+
+def _filter_limit(filter, w, h, out_w, out_h, what, which):
+    """raises for a picture or window beyond the reduction limit of the (checked) filter"""
+    if filter == RESAMPLERS["area"]:
+        _area_limit(w, h, out_w, out_h, what, which)
+    elif filter == RESAMPLERS["cubic"] and (w > CUBIC_MAX_REDUCTION * out_w or h > CUBIC_MAX_REDUCTION * out_h):
+        raise NhwError(f"{what}: {which} is {w} x {h}, more than {CUBIC_MAX_REDUCTION} times the output's {out_w} x {out_h} along a side: beyond the cubic filter's limit")
 
 
 def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
@@ -495,13 +508,19 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     left-right") -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Picture k is resampled under the integer rule
     of DESIGN.md section 18 (centre-aligned, two taps a direction, weights in 1/256), mirrored, and converted under TensorFormat's value
     rule.  filter="area" (k_area_to_tensor, nhw_area_to_tensor_device): an axis that shrinks takes the exact box mean
-    instead, which does not alias; a picture more than AREA_MAX_REDUCTION times the output along a side is refused.  Reads only the
+    instead, which does not alias; a picture more than AREA_MAX_REDUCTION times the output along a side is refused.  filter="cubic"
+    (k_cubic_to_tensor, nhw_resample_to_tensor_device): the Keys cubic with a = -1/2, widened with the reduction, what
+    PIL's BICUBIC and torch's antialiased bicubic compute, as an integer rule; the limit is CUBIC_MAX_REDUCTION.  Reads only the
     pictures' own bytes.  Ordered on torch's current stream."""
     import torch
     what = "resize_to_tensor_device"
     filter = _filter(filter, what)
     fmt = _tensor_format(fmt, what)
     out_h, out_w = _crop_size(size, what)
+    if filter == RESAMPLERS["cubic"] and isinstance(pictures, (list, tuple)):   # from the shapes alone, before a device is looked at
+        for i, x in enumerate(pictures):
+            if len(getattr(x, "shape", ())) == 3:
+                _filter_limit(filter, int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
     table, _, dev = _picture_table(pictures, what)
     n = len(pictures)
     if filter == FILTERS["area"]:
@@ -515,9 +534,12 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     L = _library()
     c = fmt.c_struct()
     with torch.cuda.device(dev):
-        call = L.nhw_area_to_tensor_device if filter == FILTERS["area"] else L.nhw_resize_to_tensor_device
-        rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                  addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        rest = (ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None, addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if filter == RESAMPLERS["cubic"]:
+            rc = L.nhw_resample_to_tensor_device(table.data_ptr(), n, out_w, out_h, filter, *rest)
+        else:
+            call = L.nhw_area_to_tensor_device if filter == FILTERS["area"] else L.nhw_resize_to_tensor_device
+            rc = call(table.data_ptr(), n, out_w, out_h, *rest)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -968,18 +990,19 @@ class Encoder:
             raise NhwError(f"per-picture status {status.tolist()}")
         return _split(arena, offs)
 
-    def encode_resized_device(self, pictures, quality: int = QUALITY_DEFAULT, out=None):
+    def encode_resized_device(self, pictures, quality: int = QUALITY_DEFAULT, out=None, filter="area"):
         """Any photo to one .nhw file: pictures, a list of at most max_batch uint8 CUDA tensors [H, W, 3] as for tile_pictures_device (crop views
         work), each resized to one 512 x 512 picture under the area rule (resize_to_tensor_device with filter="area")
         and encoded by encode_device -> (out[n,OUT_STRIDE], sizes[n], status[n]) on device, the files of encode_device on the rule's
-        pictures, byte for byte."""
+        pictures, byte for byte.  filter: "area", or "cubic" for the cubic rule, passed on to the resize."""
         what = "encode_resized_device"
+        _filter(filter, what)
         if not isinstance(pictures, (list, tuple)) or not 1 <= len(pictures) <= self.max_batch:
             raise NhwError(f"{what} wants a list of 1 .. max_batch = {self.max_batch} uint8 CUDA tensors [H, W, 3]")
         dev = getattr(pictures[0], "device", None)                   # (the resize checks that all pictures are on one device)
         if dev is not None and dev.type == "cuda" and dev.index != self.device:
             raise NhwError(f"the pictures are on cuda:{dev.index}, this encoder on cuda:{self.device}")
-        bgr = resize_to_tensor_device(pictures, (512, 512), TensorFormat("uint8", "HWC", "BGR", "file"), filter="area")
+        bgr = resize_to_tensor_device(pictures, (512, 512), TensorFormat("uint8", "HWC", "BGR", "file"), filter=filter)
         return self.encode_device(bgr, quality, out)
 
     def encode_pictures_fit(self, pictures, max_bytes, ladder=None):
@@ -1399,7 +1422,8 @@ class Decoder:
         one scale go down together -- three calls at the most, each decoding the union of its windows' tiles once.  out: a contiguous tensor of
         fmt.dtype with at least n * 3 * out_h * out_w elements on this device, which is filled.  filter="area" resizes the windows under the area
         rule (nhw_dec_crops_to_device_filter): the scales and windows are chosen as before, and a window more than
-        AREA_MAX_REDUCTION times the output along a side is refused before any call.  Raises on any status that is not NHW_OK.  The
+        AREA_MAX_REDUCTION times the output along a side is refused before any call; filter="cubic" resizes them under the cubic rule
+        (nhw_dec_crops_to_device_resample, section 20) with the limit CUBIC_MAX_REDUCTION.  Raises on any status that is not NHW_OK.  The
         work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls."""
         import numpy as np
         what = "decode_crops_device"
@@ -1422,9 +1446,9 @@ class Decoder:
             scales = sc.tolist()
         else:
             scales = [scale] * n
-        if filter == FILTERS["area"]:
+        if filter:
             for i, r in enumerate(table):
-                _area_limit(int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
+                _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
         dev = t.device("cuda", self.device)
         shape = (n,) + fmt.shape(out_h, out_w)
         per = 3 * out_h * out_w
@@ -1442,7 +1466,8 @@ class Decoder:
             f = np.ascontiguousarray(flags[idx]) if flags is not None else None
             args = (self.h, blob.ctypes.data, offs.ctypes.data, len(containers), sub.ctypes.data, len(idx), s, out_w, out_h,
                     ctypes.byref(c), f.ctypes.data if f is not None else None, a.ctypes.data, st.ctypes.data)
-            self._chk(self.lib.nhw_dec_crops_to_device_filter(*args, filter) if filter else self.lib.nhw_dec_crops_to_device(*args))
+            self._chk(self.lib.nhw_dec_crops_to_device_resample(*args, filter) if filter == RESAMPLERS["cubic"] else
+                      self.lib.nhw_dec_crops_to_device_filter(*args, filter) if filter else self.lib.nhw_dec_crops_to_device(*args))
             status[idx] = st
         self._region_raise(status)
         return (out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)), scales

@@ -218,8 +218,19 @@ static void source_look(RegionSource &c, const uint8_t *base, size_t len)   /* t
  * The crop call is the third form: `crop` set, dst_addr the tensors' addresses.  The windows are cropped into the handle's
  * staging as for the host form and stay there; behind the last chunk one k_resize_to_tensor takes every window whose tiles all decoded to its
  * tensor -- the others get the address 0, which the kernel passes over.  With the area filter that launch is
- * k_area_to_tensor, and a rect whose window is beyond the reduction limit for the output size is NHW_E_ARG before it selects a tile. */
-struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter; };
+ * k_area_to_tensor, with the cubic filter (section 20) k_cubic_to_tensor, and a rect whose window is beyond the filter's reduction limit for
+ * the output size is NHW_E_ARG before it selects a tile. */
+struct CropSpec {
+	uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter;
+	uint32_t limit;                                              /* the filter's reduction limit, 0 for none */
+	decltype(nhw_launch_resize_to_tensor) *launch;               /* ... and its kernel */
+};
+static void crop_filter(CropSpec &c, int filter)
+{
+	c.filter = filter;
+	c.limit = filter == NHW_FILTER_CUBIC ? NHW_CUBIC_MAX_REDUCTION : filter == NHW_FILTER_AREA ? NHW_AREA_MAX_REDUCTION : 0;
+	c.launch = filter == NHW_FILTER_CUBIC ? nhw_launch_cubic_to_tensor : filter == NHW_FILTER_AREA ? nhw_launch_area_to_tensor : nhw_launch_resize_to_tensor;
+}
 
 static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
                        const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, bool merge = true,
@@ -249,7 +260,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		const nhw_rect &r = rects[i];
 		status[i] = NHW_E_ARG;
 		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
-		if (crop && crop->filter == NHW_FILTER_AREA && (r.width > NHW_AREA_MAX_REDUCTION * crop->out_w || r.height > NHW_AREA_MAX_REDUCTION * crop->out_h)) continue;
+		if (crop && crop->limit && (r.width > (uint64_t)crop->limit * crop->out_w || r.height > (uint64_t)crop->limit * crop->out_h)) continue;
 		RegionSource &c = src[r.container];
 		const uint8_t *base = blob + off[r.container];
 		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
@@ -327,8 +338,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 		HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
 		if (crop->flags) HIPCHK(hipMemcpyAsync(tab + pics_bytes + addr_bytes, crop->flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		const auto launch = crop->filter == NHW_FILTER_AREA ? nhw_launch_area_to_tensor : nhw_launch_resize_to_tensor;
-		HIPCHK(launch((const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
+		HIPCHK(crop->launch((const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
 		              crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
 		HIPCHK(hipStreamSynchronize(s));
 		return NHW_OK;
@@ -364,17 +374,37 @@ extern "C" int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const 
 
 /* nhw_dec_windows_to_device with a resize behind it: window i, resampled to out_width x out_height and mirrored where bit 0 of
  * flags[i] is set, to the tensor at dst_addr[i] */
+static int dec_crops(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale, uint32_t out_width,
+                     uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status, int filter)
+{
+	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_crops_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	CropSpec c = { out_width, out_height, 0, 0, {}, flags, 0, 0, nullptr };
+	crop_filter(c, filter);
+	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
+	c.dtype = fmt->dtype; c.layout = fmt->layout;
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", true, &c);
+}
+
 extern "C" int nhw_dec_crops_to_device_filter(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                                               uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status,
                                               int filter)
 {
 	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (filter != NHW_FILTER_TWO_TAP && filter != NHW_FILTER_AREA) { nhw_dec_err = "nhw_dec_crops_to_device: the filter must be NHW_FILTER_TWO_TAP or NHW_FILTER_AREA"; return NHW_E_ARG; }
-	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_crops_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	CropSpec c = { out_width, out_height, 0, 0, {}, flags, filter };
-	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
-	c.dtype = fmt->dtype; c.layout = fmt->layout;
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", true, &c);
+	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, status, filter);
+}
+
+/* ... for the filters 0 .. 2: 0 and 1 are the call above, 2 puts k_cubic_to_tensor behind the windows */
+extern "C" int nhw_dec_crops_to_device_resample(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                                uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
+                                                int *status, int filter)
+{
+	static_assert(sizeof(int) == sizeof(int32_t), "the statuses are 32 bits wide");
+	if (filter == NHW_FILTER_TWO_TAP || filter == NHW_FILTER_AREA)
+		return nhw_dec_crops_to_device_filter(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, (int32_t *)status, filter);
+	if (filter != NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_to_device_resample: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, (int32_t *)status, filter);
 }
 
 extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,

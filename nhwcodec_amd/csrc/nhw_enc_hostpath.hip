@@ -170,6 +170,16 @@ extern "C" int nhw_area_to_tensor_device(const nhw_picture *d_pics, int n, uint3
 	return resize_entry("nhw_area_to_tensor_device", nhw_launch_area_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
 }
 
+/* ... and with the filter named: 0 and 1 are the two entries above, 2 the cubic kernel */
+extern "C" int nhw_resample_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                             const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
+{
+	if (filter == NHW_FILTER_TWO_TAP) return nhw_resize_to_tensor_device(d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+	if (filter == NHW_FILTER_AREA) return nhw_area_to_tensor_device(d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+	if (filter != NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	return resize_entry("nhw_resample_to_tensor_device", nhw_launch_cubic_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+}
+
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
 static int tensor_in_args(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
 {

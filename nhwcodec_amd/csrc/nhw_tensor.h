@@ -227,6 +227,10 @@ hipError_t nhw_launch_resize_to_tensor(const nhw_picture *d_pics, int n, uint32_
  * entry whose width exceeds NHW_AREA_MAX_REDUCTION out_w, or its height that many out_h, stores nothing */
 hipError_t nhw_launch_area_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
                                      const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
+/* ... the same with the cubic filter: the Keys cubic, a = -1/2, widened with the reduction; an entry whose width exceeds
+ * NHW_CUBIC_MAX_REDUCTION out_w, or its height that many out_h, stores nothing */
+hipError_t nhw_launch_cubic_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                      const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
 /* ... and the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
