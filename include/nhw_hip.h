@@ -377,8 +377,11 @@ int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *o
  *   scale[3], bias[3]   indexed by OUTPUT channel position (with NHW_T_RGB, index 0 belongs to R)
  *   reserved  must be 0
  * The value rule: for NHW_T_F16, NHW_T_BF16 and NHW_T_F32 the element for byte b of output channel c is fmaf((float) b, scale[c], bias[c])
- * in single precision, rounded ONCE, to nearest even, to the output type.  For NHW_T_U8 scale must be 1 and bias 0, and the bytes go out
- * unchanged.
+ * in single precision, rounded ONCE, to nearest even, to the output type.  That rounding follows the fma's own, of the exact sum to float32:
+ * two roundings in all, and the two-step value is the rule.  Subnormals are kept and what lies beyond the range is an infinity, in float32
+ * and in the output type.  A value that is not zero keeps its sign where it rounds to zero; an exact sum of zero is +0, except that a zero
+ * product of negative sign (b = 0 or a scale of 0, under a scale below zero or -0) plus a bias of -0 is -0.  For NHW_T_U8 scale must be 1 and
+ * bias 0, and the bytes go out unchanged.
  * A format is refused with NHW_E_ARG, before anything is launched, for an unknown enum value, a non-zero reserved word, a scale or bias that is
  * not finite, or NHW_T_U8 with another scale or bias. */
 enum { NHW_T_U8 = 0, NHW_T_F16 = 1, NHW_T_BF16 = 2, NHW_T_F32 = 3 };

@@ -239,7 +239,10 @@ class TensorFormat:
     ([3, S, S]) or "HWC" ([S, S, 3], as the byte path), channels "RGB" or "BGR" (as the byte path), rows "file" (BMP file order, bottom-up,
     as the byte path) or "reversed" (top-down: row 0 is the picture's top row), and per OUTPUT channel a scale and a bias: the element for
     byte b of channel c is fmaf(float32(b), scale[c], bias[c]) in single precision, rounded once to dtype.  uint8 passes the bytes on and
-    takes scale 1, bias 0 only.  Either scale / bias (three numbers each, or one for all; default 1 and 0) or mean / std in units of 0..1
+    takes scale 1, bias 0 only.  The rounding to dtype comes after the fma's own rounding to float32: two roundings in all, both to nearest
+    even, and that two-step result is the rule (on rare values it is not the exact b * scale + bias rounded once to dtype).  Subnormals
+    are kept and overflow gives an infinity, in float32 and in dtype.  Zero's sign is the fma's: a nonzero value that rounds to zero keeps
+    its sign; an exact zero is +0, except -0 for a zero product of negative sign (byte 0 under a scale below zero) plus a bias of -0.0.  Either scale / bias (three numbers each, or one for all; default 1 and 0) or mean / std in units of 0..1
     pixels, which give, in float32 arithmetic, scale = 1 / (255 * std) and bias = -mean / std (so that the element is (b / 255 - mean) / std
     up to rounding).  The attributes scale and bias are the float32 constants the kernels get, as tuples of Python floats."""
 

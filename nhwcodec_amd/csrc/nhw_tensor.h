@@ -4,7 +4,11 @@
  * kernels (nhw_picture.hip; the resampling one of section 18 among them) share, and the load shapes of the encoder's conversion kernels (nhw_picture.hip) that mirror them.
  *
  * Value rule of a decode: the element for byte b of output channel c is fmaf((float)b, scale[c], bias[c]) in single precision, rounded once, to
- * nearest even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).
+ * nearest even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).  That rounding
+ * comes after the fma's own, of the exact b * scale + bias to float32: two roundings in all, both to nearest even, and the two-step result is
+ * normative (it is not always the exact sum rounded once to the type).  Subnormals of float32 and of the output type are kept, what lies beyond
+ * the type's range is an infinity.  Zero's sign is the fma's: a nonzero value that rounds to zero keeps its sign at either rounding; an exact
+ * sum of zero is +0, unless the product (b = 0 or scale 0, with a scale below zero or -0) and the bias are both -0, which is -0.
  * Value rule of an encode: element x of tensor channel c, widened exactly to float, gives y = fmaf(x, scale[c], bias[c]); the byte is 0 for a
  * NaN, else rint(y), ties to even, clamped to 0 .. 255 (the clamp in float, before the conversion); NHW_T_U8 passes the byte on.
  */
@@ -49,7 +53,14 @@ template <int DT> __device__ __forceinline__ uint32_t nhw_tensor_elem(uint32_t b
 	if (DT == NHW_T_U8) return b;
 	const float x = __fmaf_rn((float)b, scale, bias);
 	if (DT == NHW_T_F32) return __float_as_uint(x);
-	if (DT == NHW_T_F16) return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);              /* v_cvt_f16_f32: to nearest even, f16 denormals kept */
+	if (DT == NHW_T_F16) {
+		/* the fma's float32 result has to exist before it is converted: left to itself the compiler folds fma and conversion into
+		 * v_fma_mixlo_f16, which rounds the exact sum ONCE, to float16 -- not the rule (scale 1 + 2^-11, bias 2^-40, b = 1 would give
+		 * 0x3C01 for 0x3C00).  The empty asm takes x in a vector register and hands it back; it emits nothing */
+		float y = x;
+		asm("" : "+v"(y));
+		return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)y);                                /* v_cvt_f16_f32: to nearest even, f16 denormals kept */
+	}
 	/* bfloat16: the float's upper half, rounded to nearest even on the lower.  x is finite or an infinity the fma overflowed to (b, scale, bias are
 	 * finite), never a NaN, and an infinity's lower half is 0: the integer form is exact for every value that occurs */
 	const uint32_t u = __float_as_uint(x);

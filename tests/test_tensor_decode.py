@@ -2,12 +2,12 @@
 and k_dec_scaled<2> / <4>), nhw_bytes_to_tensor_device (k_bytes_to_tensor) and their Python faces.
 
 The expected values come from the specification, not from the code under test.  The expected BYTES of a file are the oracle decoder's (scale 1)
-or section 14's pictures as tests/tensor_cases.py builds them (scales 2, 4).  The expected TENSOR is made on the CPU:
-b.astype(float64) * float64(scale32[c]) + float64(bias32[c]), .astype(float32), then the target type's own rounding from float32 (numpy for
-float16, torch on the CPU for bfloat16), then indexed and flipped by the format.  That equals fmaf(float32(b), scale, bias) EXACTLY when
-|exponent(scale) - exponent(bias)| <= 20 (or bias = 0): the product of an 8-bit and a 24-bit significand is exact in float64, under the condition
-so is the sum, and one rounding to float32 remains.  check_constants asserts the condition on every constant this file uses, so a later edit
-cannot quietly turn exact equality into double rounding.  Bit patterns are compared as integers.
+or section 14's pictures as tests/tensor_cases.py builds them (scales 2, 4).  The expected TENSOR is made on the CPU by
+tests/tensor_cases.py's exact_elements: the exact b * scale + bias in rationals, rounded once to float32 as the fma rounds it and once more to the
+target type, a table of 256 bit patterns per output channel that expected_tensor indexes with the bytes, flips and permutes by the format.  On
+the constants of this file that equals the float64 form these tests used before (product and sum in double, astype(float32), numpy's and
+torch's rounding to the type), which test_tensor_values.py asserts bit for bit; check_constants states the condition under which that form
+is the fma.  Bit patterns are compared as integers.
 
 Batches (committed files of tests/golden/dec, the smallest shapes that take every path): THREE = q20_0 (eight pixels a thread), q10_0 (four) and
 a file truncated to 40 bytes (a refused slot), under all 32 formats; TWO = q23_0, q01_0; NINE = nine files of mixed qualities (its workgroup

@@ -11,6 +11,7 @@ Shapes: a 512 x 512 picture is the codec's unit, so n = 3 is the small batch.  A
 channel order and row direction only permute it."""
 import ctypes
 import fractions
+import math
 import os
 import re
 
@@ -19,7 +20,7 @@ import pytest
 
 from oracle.harness import class_image
 from tests.support import ROOT, device_arena, golden, load_lib
-from tests.tensor_cases import ALL_FORMATS, CONSTANTS, DTYPES, SENTINEL, expected_tensor
+from tests.tensor_cases import ALL_FORMATS, CONSTANTS, DTYPES, SENTINEL, binade, expected_tensor, round_to_binary
 
 NHW_E_ARG, NHW_E_QUALITY = -4, -1
 IMG = 786432
@@ -36,13 +37,10 @@ def _round_to_f32(q):
     """a rational, rounded once to float32 (normal range), half-even -> the rational that float32 holds"""
     if q == 0:
         return q
-    e = 0
-    while abs(q) * fractions.Fraction(2) ** (23 - e) >= 1 << 24:
-        e += 1
-    while abs(q) * fractions.Fraction(2) ** (23 - e) < 1 << 23:
-        e -= 1
-    assert e >= -126
-    return round(q * fractions.Fraction(2) ** (23 - e)) * fractions.Fraction(2) ** (e - 23)
+    assert binade(abs(q)) >= -126
+    r = round_to_binary(abs(q), "float32")       # tensor_cases' rounder, which also knows the subnormals and the overflow
+    assert r != math.inf
+    return r if q > 0 else -r
 
 
 def _exact_byte(x, scale, bias):
