@@ -59,6 +59,14 @@ int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream);
  * B_KMAP, then the quantiser reading them (production); form 1: the quantiser alone with its own loops.  Both leave the symbol list to be read:
  * B_NZQ (the non-zero map, 4096 words, with the fbase table of 33 words behind it) and B_VALS. */
 int nhw_stage_quant(nhw_enc *e, int n, int form, void *stream);
+/* The luma residual passes Y19 .. Y27 (between the second level-2 synthesis and the quantiser) for the first n images of the handle's last whole
+ * batch, at that batch's quality, on B_JPEG (its LL quadrant: the first-order samples Y19 copies above quality 21), B_PROC, B_LL1, B_L2SAVE and
+ * B_FIRST as they stand, on one stream.  form 0: the kernels of Y19 .. Y23, of Y24 and Y25 (quality > 12) and of Y26 and Y27 as a production batch
+ * launches them -- up to quality 21 without Y26's copy of the level-2 block, HL1's first row looking up into B_L2SAVE; form 1: the same
+ * launches as a debug stop makes them, with the copy at every quality; form 2: Y24 and Y25 alone on the code plane B_LL1 as it stands
+ * (quality > 12); form 3: Y26 and Y27 alone, as production.  Behind the call: B_PROC's level-1 bands, its level-2 block where the form copies it
+ * (quality > 21 or form 1), B_FIRST above quality 21, the position lists B_R1 / R3 / R5 (LIST, BITS, WORD) with their lengths in B_META. */
+int nhw_stage_residuals(nhw_enc *e, int n, int form, void *stream);
 /* The stream stage (the Y31 symbol rewrites, then the RLE + VLC packetiser and the container) for the first n images of the handle's last whole
  * batch, at that batch's quality, on the workspace as it stands.  form 0: k_y31 and k_final, from the symbol lists as the quantisers leave
  * them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS); form 1: k_final alone, on B_NZS / B_VOFF / B_VALS as they stand;

@@ -75,6 +75,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_stage_luma_loop.argtypes = [P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_ll2_walk.argtypes = [P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_quant.argtypes = [P, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_stage_residuals.argtypes = [P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_stream.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, P]
     L.nhw_debug_write.argtypes = [P, ctypes.c_int, ctypes.c_int, P, ctypes.c_size_t]
     L.nhw_stage_analysis.argtypes = [P, P, P, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]

@@ -711,6 +711,32 @@ extern "C" int nhw_stage_quant(nhw_enc *e, int n, int form, void *stream)
 	return NHW_OK;
 }
 
+/* A test hook for the luma residual passes Y19 .. Y27, on B_JPEG, B_PROC, B_LL1, B_L2SAVE and B_FIRST as they stand (a test writes them), for the first
+ * n images of the handle's last whole batch at that batch's quality, on one stream.
+ *   form 0: k_l4a / k_phase<PH_L4A> (Y19 .. Y23), k_phase<PH_L4B> (Y24, Y25; q > 12) and k_phase<PH_L4C> (Y26, Y27) as production launches them:
+ *           up to quality 21 Y26 is left out and HL1's first row looks up into l2save;
+ *   form 1: the same launches as a debug stop makes them (ws.dbg = 1): Y26 puts the level-2 block back at every quality;
+ *   form 2: k_phase<PH_L4B> alone, on the code plane B_LL1 (and B_FIRST) as it stands (q > 12);
+ *   form 3: k_phase<PH_L4C> alone, as production launches it. */
+extern "C" int nhw_stage_residuals(nhw_enc *e, int n, int form, void *stream)
+{
+	if (!e || n < 1 || n > e->max_batch || form < 0 || form > 3) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after || (form == 2 && e->last_q <= 12)) {
+		nhw_enc_err = "nhw_stage_residuals: needs a completed whole batch of >= n images (form 2: at quality >= 13) and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = form == 1;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	if (form < 2) nhw_launch_phase(PH_L4A, ws, 0, s);
+	if (form < 3 && ws.q > 12) nhw_launch_phase(PH_L4B, ws, 0, s);
+	if (form != 2) nhw_launch_phase(PH_L4C, ws, 0, s);
+	HIPCHK(hipGetLastError());
+	return NHW_OK;
+}
+
 /* A test hook for the stream stage -- the Y31 symbol rewrites and the RLE + VLC packetiser, a pure function of the symbol stream -- for the first n
  * images of the handle's last whole batch at that batch's quality, on the workspace as it stands (a test writes the lists: nhw_debug_write).
  *   form 0: k_y31, then k_final: from the lists as the quantisers leave them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS);

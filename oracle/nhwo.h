@@ -92,6 +92,35 @@ typedef struct {
 } nhwo_stream_info;
 int nhwo_stream_stage(const uint8_t *luma, const uint8_t *chroma, uint8_t *luma_out, uint8_t *sel_word1, uint8_t *sel_word2,
                       uint32_t *packet, size_t packet_cap, uint8_t *book1, uint8_t *book2, nhwo_stream_info *info);
+/* The residual stage: the luma passes between the second level-2 synthesis and the quantiser (nhw_encoder.c:766-2098, Y19 .. Y27 of SURVEY.md
+ * Appendix A) on planes the caller made -- the very function nhwo_luma runs.  The passes come in three parts: 0: Y19 .. Y23 (the copy to the
+ * first-order plane, the level-1 thresholds, the +-5..7 runs, the residual classification and codes), 1: Y24 and Y25 (the feedback into the
+ * first-order plane, the three position lists), 2: Y26 and Y27 (the detail clean-ups); the call runs parts first .. last.  jpeg, proc: 4 *
+ * NHWO_QSIZE shorts each; ll1, l2save, first_order: NHWO_QSIZE each; all in and out.  Inside they live in the guarded arena, so reads past ll1
+ * and l2save see zeros.  out: the three position lists (res1, res3, res5) with their lengths and the raw entry count of each pass before pruning
+ * (row markers included), and the arm counters of this call. */
+#define NHWO_ARM_MAX 128
+typedef struct {
+	int list_len, bits_len, word_len, raw_count;
+	uint8_t list[NHWO_QSIZE + 64], bits[NHWO_QSIZE / 8 + 64], word[NHWO_QSIZE / 4 + 64];
+} nhwo_residual_list;
+typedef struct {
+	nhwo_residual_list pl[3];
+	uint32_t arm[NHWO_ARM_MAX];
+} nhwo_residual_out;
+int nhwo_residual_stage(int quality, int first, int last, int16_t *jpeg, int16_t *proc, int16_t *ll1, const int16_t *l2save,
+                        int16_t *first_order, nhwo_residual_out *out);
+/* the arm counters: how many there are, a counter's name, whether the arm can be taken at a quality.  The counters themselves are plain
+ * increments in the passes, on in every build; nhwo_residual_stage reports what its own call added. */
+int nhwo_arm_count(void);
+const char *nhwo_arm_name(int arm);
+int nhwo_arm_live(int arm, int quality);
+/* oracle-only tap: when set (null by default), nhwo_luma copies the five planes in front of the residual passes into `in`, and the planes and
+ * lists behind them into `out` and `lists`.  The checkpoint trace does not change. */
+typedef struct { int16_t jpeg[4 * NHWO_QSIZE], proc[4 * NHWO_QSIZE], ll1[NHWO_QSIZE], l2save[NHWO_QSIZE], first_order[NHWO_QSIZE]; } nhwo_residual_planes;
+typedef struct { nhwo_residual_planes in, out; nhwo_residual_out lists; } nhwo_residual_tap;
+extern nhwo_residual_tap *nhwo_residual_tap_ptr;
+
 /* which byte codes can enter a code book (compress_pixel.c:131-160) */
 int nhwo_book_symbol_ok(int v);
 

@@ -77,7 +77,56 @@ typedef struct {
 	int size_book1, size_book2, tree_end;
 	uint8_t book_tmp[600];          /* wavlts2packet's `codebook` scratch, shared by both parts */
 	int res1_count, res3_count, res5_count; /* running nhw_resN_word_len counters of Y22/Y23 */
+	int raw_count[3];               /* Y25: entries of each pass's list before pruning, row markers included (reference buffer: 96*H+1 bytes) */
 } nhwo_ctx;
+
+/* The arm counters of the residual passes (nhwo.h, nhwo_residual_stage): X(name, first quality, last quality at which the arm can be taken).
+ * Arms the reference has and no input reaches are not here: its (-7, -6/-7) and (7, 7) branches of Y21 (nhwo_luma.c, tag_small_runs: 5 .. 7 and
+ * -7 .. -5 are consumed by the two tests in front of them), and the ripple's "8 beside -7" (ripple: an 8 is 0 modulo 8 and at least 8, so the chain's
+ * first test takes it). */
+#define NHWO_ARMS(X) \
+	/* Y20, 16 <= q <= 19 */ \
+	X(Y20H_HL, 16, 19) X(Y20H_HH, 16, 19) \
+	/* Y20, q 14 and 15 */ \
+	X(Y20M_HL_ZERO, 14, 15) X(Y20M_HH_LOUD, 14, 15) X(Y20M_HH_ZERO, 14, 15) \
+	/* Y20, q <= 13: the loud count's four levels (q <= 12), then by band: thin_by_parent's three arms, the isolated and the small cell */ \
+	X(Y20L_LOUD3, 1, 12) X(Y20L_LOUD2, 1, 12) X(Y20L_LOUD1, 1, 12) X(Y20L_LOUD0, 1, 12) \
+	X(Y20L_LH_PARENT, 1, 13) X(Y20L_LH_PAIRL, 1, 13) X(Y20L_LH_PAIRR, 1, 13) X(Y20L_LH_ISO, 1, 13) \
+	X(Y20L_HL_PARENT, 1, 13) X(Y20L_HL_PAIRL, 1, 13) X(Y20L_HL_PAIRR, 1, 13) X(Y20L_HL_ISO, 1, 13) X(Y20L_HL_SMALL, 1, 13) \
+	X(Y20L_HH_PARENT, 1, 13) X(Y20L_HH_PAIRL, 1, 13) X(Y20L_HH_PAIRR, 1, 13) X(Y20L_HH_ISO, 1, 13) X(Y20L_HH_SMALL, 1, 13) \
+	X(Y20L_KEEP_P7, 11, 13) X(Y20L_KEEP_N7, 11, 13) X(Y20L_KEEP_0, 1, 13) \
+	/* Y21 */ \
+	X(Y21_LH_POS, 17, 23) X(Y21_LH_NEG, 17, 23) X(Y21_LH_P8_TEN, 17, 23) X(Y21_LH_P8_PAIR, 17, 23) X(Y21_LH_N8_NINE, 17, 23) X(Y21_LH_N8_PAIR, 17, 23) \
+	X(Y21_HL_POS, 17, 23) X(Y21_HL_NEG, 17, 23) X(Y21_HL_P8_TEN, 20, 23) X(Y21_HL_N8_NINE, 20, 23) /* (up to quality 19 Y20 has made HL1's +-8 a +-7) */ \
+	/* Y22: the chain's arms in its order */ \
+	X(Y22_MARK_22, 13, 23) X(Y22_MARK_23, 13, 23) X(Y22_MARK_33, 13, 23) X(Y22_SNAP_33, 19, 23) \
+	X(Y22_INC_AM4, 13, 23) X(Y22_MARK_AM4, 13, 23) X(Y22_MARK_ABOVE_P, 13, 23) \
+	X(Y22_SNAP_125, 13, 23) X(Y22_SNAP_121, 19, 23) X(Y22_Q18P_BELOW_A5, 18, 18) X(Y22_Q18P_CELL, 18, 18) X(Y22_Q18P_BELOW_R3, 18, 18) \
+	X(Y22_MARK_NB_P, 13, 23) \
+	X(Y22_DEC_A4, 13, 23) X(Y22_MARK_A4, 13, 23) \
+	X(Y22_SNAP_126, 13, 23) X(Y22_SNAP_122, 19, 23) X(Y22_Q18N_BELOW_A5, 18, 18) X(Y22_Q18N_CELL, 18, 18) X(Y22_Q18N_BELOW_R3, 18, 18) \
+	X(Y22_MARK_NEG_D2, 13, 23) X(Y22_CODE_145, 21, 23) X(Y22_MARK_NB_N, 13, 23) X(Y22_SITE_M2_A, 13, 23) X(Y22_SITE_M3_A, 13, 20) \
+	X(Y22_MARK_ABOVE_N, 13, 23) X(Y22_MARK_M1_D3, 13, 23) X(Y22_SITE_UP_A, 13, 23) X(Y22_MARK_M4, 13, 23) X(Y22_SITE_LARGE_A, 13, 23) \
+	X(Y22_SITE_UP_B, 13, 23) X(Y22_SITE_M2_B, 13, 23) X(Y22_SITE_M3_B, 13, 23) X(Y22_SITE_LARGE_B, 13, 23) \
+	/* the nudges of the LH1 partner */ \
+	X(NUDGE_UP_7, 13, 23) X(NUDGE_UP_8, 13, 23) X(NUDGE_M2_NEG, 13, 23) X(NUDGE_M2_POS, 13, 23) \
+	X(NUDGE_M3_145, 21, 23) X(NUDGE_M3_NEG, 13, 20) X(NUDGE_M3_TEN, 13, 20) X(NUDGE_M3_BIG, 13, 20) \
+	X(LARGE_M4, 13, 23) X(LARGE_149, 21, 23) X(LARGE_NEG, 13, 23) X(LARGE_POS, 13, 23) \
+	/* Y23 */ \
+	X(Y23_R01, 13, 23) X(Y23_R2_DEC, 13, 23) X(Y23_R2_M78, 13, 23) X(Y23_R2_M6, 13, 23) \
+	X(Y23_R3_144, 21, 23) X(Y23_R3_DEC, 13, 20) X(Y23_R3_M10, 13, 20) \
+	X(Y23_141, 13, 23) X(Y23_R4, 20, 23) X(Y23_148, 21, 23) X(Y23_R7_DEC, 13, 23) X(Y23_R7_M9, 13, 23) \
+	/* Y24 */ \
+	X(Y24_141, 22, 23) X(Y24_140, 22, 23) X(Y24_144, 22, 23) X(Y24_145, 22, 23) X(Y24_121, 22, 23) X(Y24_122, 22, 23) \
+	X(Y24_123, 22, 23) X(Y24_124, 22, 23) X(Y24_126, 22, 23) X(Y24_125, 22, 23) X(Y24_148, 22, 23) X(Y24_149, 22, 23) \
+	/* Y27: the ripple, then the three bands (LH1's and HL1's pull to +-7 needs |v| in 6 .. lim2 - 1, and lim2 is 4 at quality 23) */ \
+	X(RIPPLE_DEC, 1, 23) X(RIPPLE_M7_8, 1, 23) X(RIPPLE_NEG_7, 1, 23) X(RIPPLE_NEG_AHEAD, 1, 23) \
+	X(Y27_LH_TO_M7, 1, 22) X(Y27_LH_TO_7, 1, 22) X(Y27_LH_ZERO, 1, 23) X(Y27_HL_TO_7, 1, 22) X(Y27_HL_ZERO, 1, 23) \
+	X(Y27_HH_TO_7, 1, 23) X(Y27_HH_ZERO, 1, 23)
+#define NHWO_ARM_ENUM(name, lo, hi) ARM_##name,
+enum { NHWO_ARMS(NHWO_ARM_ENUM) ARM_COUNT };
+extern uint32_t nhwo_arm[NHWO_ARM_MAX];
+#define ARM(name) (nhwo_arm[ARM_##name]++)
 
 /* trace */
 void nhwo_trace_put(nhwo_trace *t, const char *name, int nblobs, const void **blobs, const uint32_t *lens);

@@ -165,15 +165,15 @@ static void tag_small_runs(nhwo_ctx *c)
 	for (r = 1; r < H - 1; r++)
 		for (j = H + 1; j < W - 1; j++) {
 			int16_t *v = p + r * W + j;
-			if (v[0] > 4 && v[0] < 8) { if (in_4_7(v[-1]) && in_4_7(v[1])) { v[0] = 12700; v[-1] = 10100; v[1] = 10100; } }
-			else if (v[0] < -4 && v[0] > -8) { if (in_m7_m4(v[-1]) && in_m7_m4(v[1])) { v[0] = 12900; v[-1] = 10100; v[1] = 10100; } }
+			if (v[0] > 4 && v[0] < 8) { if (in_4_7(v[-1]) && in_4_7(v[1])) { ARM(Y21_LH_POS); v[0] = 12700; v[-1] = 10100; v[1] = 10100; } }
+			else if (v[0] < -4 && v[0] > -8) { if (in_m7_m4(v[-1]) && in_m7_m4(v[1])) { ARM(Y21_LH_NEG); v[0] = 12900; v[-1] = 10100; v[1] = 10100; } }
 			else if (v[0] == 8) {
-				if ((v[-1] & 0xFFFE) == 6 || (v[1] & 0xFFFE) == 6) v[0] = 10;
-				else if (v[1] == 8) { v[0] = 9; v[1] = 9; }
+				if ((v[-1] & 0xFFFE) == 6 || (v[1] & 0xFFFE) == 6) { ARM(Y21_LH_P8_TEN); v[0] = 10; }
+				else if (v[1] == 8) { ARM(Y21_LH_P8_PAIR); v[0] = 9; v[1] = 9; }
 			}
 			else if (v[0] == -8) {
-				if (((-v[-1]) & 0xFFFE) == 6 || ((-v[1]) & 0xFFFE) == 6) v[0] = -9;
-				else if (v[1] == -8) { v[0] = -9; v[1] = -9; }
+				if (((-v[-1]) & 0xFFFE) == 6 || ((-v[1]) & 0xFFFE) == 6) { ARM(Y21_LH_N8_NINE); v[0] = -9; }
+				else if (v[1] == -8) { ARM(Y21_LH_N8_PAIR); v[0] = -9; v[1] = -9; }
 			}
 			/* the reference's (-7,-6/-7) and (7,7) branches (:995-1002) are unreachable: 5..7 and
 			 * -7..-5 are consumed by the two tests above */
@@ -181,10 +181,10 @@ static void tag_small_runs(nhwo_ctx *c)
 	for (r = H + 1; r < W - 1; r++)
 		for (j = 1; j < H - 1; j++) {
 			int16_t *v = p + r * W + j;
-			if (v[0] > 4 && v[0] < 8) { if (in_4_7(v[-1]) && in_4_7(v[1])) { v[0] = 12700; v[-1] = 10100; v[1] = 10100; } }
-			else if (v[0] < -4 && v[0] > -8) { if (in_m7_m4(v[-1]) && in_m7_m4(v[1])) { v[0] = 12900; v[-1] = 10100; v[1] = 10100; } }
-			else if (v[0] == 8) { if ((v[-1] & 0xFFFE) == 6 || (v[1] & 0xFFFE) == 6) v[0] = 10; }
-			else if (v[0] == -8) { if (((-v[-1]) & 0xFFFE) == 6 || ((-v[1]) & 0xFFFE) == 6) v[0] = -9; }
+			if (v[0] > 4 && v[0] < 8) { if (in_4_7(v[-1]) && in_4_7(v[1])) { ARM(Y21_HL_POS); v[0] = 12700; v[-1] = 10100; v[1] = 10100; } }
+			else if (v[0] < -4 && v[0] > -8) { if (in_m7_m4(v[-1]) && in_m7_m4(v[1])) { ARM(Y21_HL_NEG); v[0] = 12900; v[-1] = 10100; v[1] = 10100; } }
+			else if (v[0] == 8) { if ((v[-1] & 0xFFFE) == 6 || (v[1] & 0xFFFE) == 6) { ARM(Y21_HL_P8_TEN); v[0] = 10; } }
+			else if (v[0] == -8) { if (((-v[-1]) & 0xFFFE) == 6 || ((-v[1]) & 0xFFFE) == 6) { ARM(Y21_HL_N8_NINE); v[0] = -9; } }
 			/* :1040-1064 (-6/-7 and 7 with a vertical partner) unreachable for the same reason */
 		}
 }
@@ -192,29 +192,29 @@ static void tag_small_runs(nhwo_ctx *c)
 /* Y22/Y23 nudges of the LH1 coefficient paired with an LL1 sample */
 static void nudge_up_small(int16_t *v)                       /* L_W1 (:1251-1262) */
 {
-	if (v[0] == 7) { if (v[-1] >= 0 && v[-1] < 8) v[0] += 2; }
-	else if (v[0] == 8) { if (v[-1] >= -2 && v[-1] < 8) v[0] += 2; }
+	if (v[0] == 7) { if (v[-1] >= 0 && v[-1] < 8) { ARM(NUDGE_UP_7); v[0] += 2; } }
+	else if (v[0] == 8) { if (v[-1] >= -2 && v[-1] < 8) { ARM(NUDGE_UP_8); v[0] += 2; } }
 }
 static void nudge_m2(int16_t *v)                             /* L_W2 (:1264-1275) */
 {
-	if (v[0] < -14) { if (mult8_or_7(-v[0])) v[0]++; }
-	else if (v[0] == 7 || (v[0] & 0xFFFE) == 8) { if (v[-1] >= -2) v[0] += 3; }
+	if (v[0] < -14) { if (mult8_or_7(-v[0])) { ARM(NUDGE_M2_NEG); v[0]++; } }
+	else if (v[0] == 7 || (v[0] & 0xFFFE) == 8) { if (v[-1] >= -2) { ARM(NUDGE_M2_POS); v[0] += 3; } }
 }
 static void nudge_m3(nhwo_ctx *c, int16_t *v, int16_t *cell)  /* L_W3 (:1277-1294) */
 {
-	if (c->q >= 21) *cell = 14500;
-	else if (v[0] < -14) { if (mult8_or_7(-v[0])) v[0]++; }
-	else if (v[0] >= 0 && ((v[0] + 2) & 0xFFFC) == 8) { if (v[-1] >= -2) v[0] = 10; }
-	else if (v[0] > 14 && (v[0] & 7) == 7) v[0]++;
+	if (c->q >= 21) { ARM(NUDGE_M3_145); *cell = 14500; }
+	else if (v[0] < -14) { if (mult8_or_7(-v[0])) { ARM(NUDGE_M3_NEG); v[0]++; } }
+	else if (v[0] >= 0 && ((v[0] + 2) & 0xFFFC) == 8) { if (v[-1] >= -2) { ARM(NUDGE_M3_TEN); v[0] = 10; } }
+	else if (v[0] > 14 && (v[0] & 7) == 7) { ARM(NUDGE_M3_BIG); v[0]++; }
 }
 static void mark_m_large(nhwo_ctx *c, int16_t *v, int16_t *cell, int res) /* L_W5 (:1296-1325) */
 {
 	*cell = 14000;
-	if (res == -4) { if (v[0] == -7 || v[0] == -8) { if (v[-1] < 2 && v[-1] > -8) v[0] = -9; } }
+	if (res == -4) { if (v[0] == -7 || v[0] == -8) { if (v[-1] < 2 && v[-1] > -8) { ARM(LARGE_M4); v[0] = -9; } } }
 	else if (res < -6) {
-		if (res < -7 && c->q >= 21) *cell = 14900;
-		else if (v[0] < -14) { if (mult8_or_7(-v[0])) v[0]++; }
-		else if (v[0] == 7 || v[0] == 8) { if (v[-1] >= -1 && v[-1] < 8) v[0] += 3; }
+		if (res < -7 && c->q >= 21) { ARM(LARGE_149); *cell = 14900; }
+		else if (v[0] < -14) { if (mult8_or_7(-v[0])) { ARM(LARGE_NEG); v[0]++; } }
+		else if (v[0] == 7 || v[0] == 8) { if (v[-1] >= -1 && v[-1] < 8) { ARM(LARGE_POS); v[0] += 3; } }
 	}
 }
 
@@ -231,70 +231,70 @@ static void classify_residuals(nhwo_ctx *c, int res_setting)
 			int16_t *lh = p + j * W + H + r;            /* (j<<9)+(i>>9)+IM_DIM */
 			const int res = p[s] - o[k], a = p[s + W] - o[k + H];
 			const int d2 = p[s + 2 * W] - o[k + 2 * H];  /* two rows down: reads past ll1 on the last rows */
-#define MARK(code, step) do { *cell = (code); p[s + W] += (step); p[s + 2 * W] += (step); } while (0)
-#define SNAP(code) do { *cell = (code); p[s + W] = o[k + H]; } while (0)
-			if (res == 2 && a == 2 && d2 >= 2) { if (d2 < 5 || d2 > 6) MARK(12400, -2); }
-			else if (((res == 2 && a == 3) || (res == 3 && a == 2)) && d2 > 1 && d2 < 6) MARK(12400, -2);
+#define MARK(arm, code, step) do { ARM(arm); *cell = (code); p[s + W] += (step); p[s + 2 * W] += (step); } while (0)
+#define SNAP(arm, code) do { ARM(arm); *cell = (code); p[s + W] = o[k + H]; } while (0)
+			if (res == 2 && a == 2 && d2 >= 2) { if (d2 < 5 || d2 > 6) MARK(Y22_MARK_22, 12400, -2); }
+			else if (((res == 2 && a == 3) || (res == 3 && a == 2)) && d2 > 1 && d2 < 6) MARK(Y22_MARK_23, 12400, -2);
 			else if (res == 3 && a == 3) {
-				if (d2 > 0 && d2 < 6) MARK(12400, -2);
-				else if (q >= 19) SNAP(12100);
+				if (d2 > 0 && d2 < 6) MARK(Y22_MARK_33, 12400, -2);
+				else if (q >= 19) SNAP(Y22_SNAP_33, 12100);
 			}
 			else if (a == -4 && (res == 2 || res == 3) && (d2 == 2 || d2 == 3)) {
-				if (res == 2 && d2 == 2) p[s + W]++; else MARK(12400, -2);
+				if (res == 2 && d2 == 2) { ARM(Y22_INC_AM4); p[s + W]++; } else MARK(Y22_MARK_AM4, 12400, -2);
 			}
 			else if (res == 1 && a == 3 && d2 == 2) {
-				if (r > 0 && (p[s - W] - o[k - H]) >= 0) MARK(12400, -2);
+				if (r > 0 && (p[s - W] - o[k - H]) >= 0) MARK(Y22_MARK_ABOVE_P, 12400, -2);
 			}
 			else if ((res == 3 || res == 4 || res == 5 || res > 6) && (a == 3 || (a & 0xFFFE) == 4)) {
-				if (res > 6) SNAP(12500);
-				else if (q >= 19) SNAP(12100);
+				if (res > 6) SNAP(Y22_SNAP_125, 12500);
+				else if (q >= 19) SNAP(Y22_SNAP_121, 12100);
 				else if (q == 18) {
-					if (res < 5 && a == 5) o[k + H] = 14100;
-					else if (res >= 5) *cell = 14100;
-					else if (res == 3 && a >= 4) o[k + H] = 14100;
+					if (res < 5 && a == 5) { ARM(Y22_Q18P_BELOW_A5); o[k + H] = 14100; }
+					else if (res >= 5) { ARM(Y22_Q18P_CELL); *cell = 14100; }
+					else if (res == 3 && a >= 4) { ARM(Y22_Q18P_BELOW_R3); o[k + H] = 14100; }
 					p[s + W] = o[k + H];
 				}
 			}
 			else if ((res == 2 || res == 3) && (a == 2 || a == 3)) {
 				if (d2 == 0 || d2 == 1) {
 					const int x0 = p[s + 1] - o[k + 1], x1 = p[s + W + 1] - o[k + H + 1];
-					if ((x0 == 2 || x0 == 3) && (x1 == 2 || x1 == 3) && (p[s + 2 * W + 1] - o[k + 2 * H + 1]) > 0) MARK(12400, -2);
+					if ((x0 == 2 || x0 == 3) && (x1 == 2 || x1 == 3) && (p[s + 2 * W + 1] - o[k + 2 * H + 1]) > 0) MARK(Y22_MARK_NB_P, 12400, -2);
 				}
 			}
 			else if (a == 4 && (res == -2 || res == -3) && (d2 == -2 || d2 == -3)) {
-				if (res == -2 && d2 == -2) p[s + W]--; else MARK(12300, 2);
+				if (res == -2 && d2 == -2) { ARM(Y22_DEC_A4); p[s + W]--; } else MARK(Y22_MARK_A4, 12300, 2);
 			}
 			else if ((res == -3 || res == -4 || res == -5 || res < -7) && (a == -3 || a == -4 || a == -5)) {
-				if (res < -7) SNAP(12600);
-				else if (q >= 19) SNAP(12200);
+				if (res < -7) SNAP(Y22_SNAP_126, 12600);
+				else if (q >= 19) SNAP(Y22_SNAP_122, 12200);
 				else if (q == 18) {
-					if (res > -5 && a == -5) o[k + H] = 14000;
-					else if (res <= -5) *cell = 14000;
-					else if (res == -3 && a <= -4) o[k + H] = 14000;
+					if (res > -5 && a == -5) { ARM(Y22_Q18N_BELOW_A5); o[k + H] = 14000; }
+					else if (res <= -5) { ARM(Y22_Q18N_CELL); *cell = 14000; }
+					else if (res == -3 && a <= -4) { ARM(Y22_Q18N_BELOW_R3); o[k + H] = 14000; }
 					p[s + W] = o[k + H];
 				}
 			}
 			else if (a == -2 || a == -3) {
 				if (res == -2 || res == -3) {
-					if (d2 < 0) MARK(12300, 2);
-					else if (res == -3 && q >= 21) *cell = 14500;
+					if (d2 < 0) MARK(Y22_MARK_NEG_D2, 12300, 2);
+					else if (res == -3 && q >= 21) { ARM(Y22_CODE_145); *cell = 14500; }
 					else if (d2 == 0) {
 						const int x0 = p[s + 1] - o[k + 1], x1 = p[s + W + 1] - o[k + H + 1];
-						if ((x0 == -2 || x0 == -3) && (x1 == -2 || x1 == -3) && (p[s + 2 * W + 1] - o[k + 2 * H + 1]) < 0) MARK(12300, 2);
+						if ((x0 == -2 || x0 == -3) && (x1 == -2 || x1 == -3) && (p[s + 2 * W + 1] - o[k + 2 * H + 1]) < 0) MARK(Y22_MARK_NB_N, 12300, 2);
 					}
-					else if (res == -2) nudge_m2(lh);
-					else nudge_m3(c, lh, cell);
+					else if (res == -2) { ARM(Y22_SITE_M2_A); nudge_m2(lh); }
+					else { ARM(Y22_SITE_M3_A); nudge_m3(c, lh, cell); }
 				}
 				else if (res == -1 && a == -3 && d2 == -2) {
-					if (r > 0 && (p[s - W] - o[k - H]) <= 0) MARK(12300, 2);
+					if (r > 0 && (p[s - W] - o[k - H]) <= 0) MARK(Y22_MARK_ABOVE_N, 12300, 2);
 				}
-				else if (res == -1) { if (d2 == -3) MARK(12300, 2); else nudge_up_small(lh); }
-				else if (res == -4) { if (d2 < -1 && d2 > -4) MARK(12300, 2); else mark_m_large(c, lh, cell, res); }
+				else if (res == -1) { if (d2 == -3) MARK(Y22_MARK_M1_D3, 12300, 2); else { ARM(Y22_SITE_UP_A); nudge_up_small(lh); } }
+				else if (res == -4) { if (d2 < -1 && d2 > -4) MARK(Y22_MARK_M4, 12300, 2); else { ARM(Y22_SITE_LARGE_A); mark_m_large(c, lh, cell, res); } }
 			}
-			else if (!res || res == -1) nudge_up_small(lh);
-			else if (res == -2) nudge_m2(lh);
-			else if (res == -3) nudge_m3(c, lh, cell);
-			else if (res < -res_setting) mark_m_large(c, lh, cell, res);
+			else if (!res || res == -1) { ARM(Y22_SITE_UP_B); nudge_up_small(lh); }
+			else if (res == -2) { ARM(Y22_SITE_M2_B); nudge_m2(lh); }
+			else if (res == -3) { ARM(Y22_SITE_M3_B); nudge_m3(c, lh, cell); }
+			else if (res < -res_setting) { ARM(Y22_SITE_LARGE_B); mark_m_large(c, lh, cell, res); }
 #undef MARK
 #undef SNAP
 		}
@@ -313,24 +313,25 @@ static void code_residuals(nhwo_ctx *c, int res_setting)
 			if (*cell < 12000) {
 				const int res = p[r * W + j] - *cell;
 				*cell = 0;
-				if (!res || res == 1) { if (v[0] == -7 || v[0] == -8) { if (v[-1] < 2 && v[-1] > -8) v[0] = -9; } }
+				if (!res || res == 1) { if (v[0] == -7 || v[0] == -8) { if (v[-1] < 2 && v[-1] > -8) { ARM(Y23_R01); v[0] = -9; } } }
 				else if (res == 2) {
-					if (v[0] > 15 && !(v[0] & 7)) v[0]--;
-					else if (v[0] == -7 || v[0] == -8) { if (v[-1] <= 1) v[0] = -9; }
-					else if (v[0] == -6) { if (v[-1] <= -1 && v[-1] > -8) v[0] = -9; }
+					if (v[0] > 15 && !(v[0] & 7)) { ARM(Y23_R2_DEC); v[0]--; }
+					else if (v[0] == -7 || v[0] == -8) { if (v[-1] <= 1) { ARM(Y23_R2_M78); v[0] = -9; } }
+					else if (v[0] == -6) { if (v[-1] <= -1 && v[-1] > -8) { ARM(Y23_R2_M6); v[0] = -9; } }
 				}
 				else if (res == 3) {
-					if (q >= 21) *cell = 144;
-					else if (v[0] > 15 && !(v[0] & 7)) v[0]--;
-					else if (v[0] <= 0 && (((-v[0]) + 2) & 0xFFFC) == 8) { if (v[-1] <= 2) v[0] = -10; }
+					if (q >= 21) { ARM(Y23_R3_144); *cell = 144; }
+					else if (v[0] > 15 && !(v[0] & 7)) { ARM(Y23_R3_DEC); v[0]--; }
+					else if (v[0] <= 0 && (((-v[0]) + 2) & 0xFFFC) == 8) { if (v[-1] <= 2) { ARM(Y23_R3_M10); v[0] = -10; } }
 				}
 				else if (res > res_setting) {
+					ARM(Y23_141);
 					*cell = 141;
-					if (res == 4) { if (v[0] == 7 || (v[0] & 0xFFFE) == 8) { if (v[-1] >= 0 && v[-1] < 8) v[0] += 2; } }
+					if (res == 4) { if (v[0] == 7 || (v[0] & 0xFFFE) == 8) { if (v[-1] >= 0 && v[-1] < 8) { ARM(Y23_R4); v[0] += 2; } } }
 					else if (res > 6) {
-						if (res > 7 && q >= 21) *cell = 148;
-						else if (v[0] > 15 && !(v[0] & 7)) v[0]--;
-						else if (v[0] == -6 || v[0] == -7 || v[0] == -8) { if (v[-1] < 0 && v[-1] > -8) v[0] = -9; }
+						if (res > 7 && q >= 21) { ARM(Y23_148); *cell = 148; }
+						else if (v[0] > 15 && !(v[0] & 7)) { ARM(Y23_R7_DEC); v[0]--; }
+						else if (v[0] == -6 || v[0] == -7 || v[0] == -8) { if (v[-1] < 0 && v[-1] > -8) { ARM(Y23_R7_M9); v[0] = -9; } }
 					}
 				}
 			} else {
@@ -356,13 +357,13 @@ static void adjust_first_order(nhwo_ctx *c)
 			const int code = c->ll1[r * H + j];
 			int16_t *t = f + j * H + r;
 			switch (code) {
-			case 141: t[0] -= 5; break;           case 140: t[0] += 5; break;
-			case 144: t[0] -= 3; break;           case 145: t[0] += 3; break;
-			case 121: t[0] -= 4; t[1] -= 3; break; case 122: t[0] += 4; t[1] += 3; break;
-			case 123: t[0] += 2; t[1] += 2; t[2] += 2; break;
-			case 124: t[0] -= 2; t[1] -= 2; t[2] -= 2; break;
-			case 126: t[0] += 9; t[1] += 3; break; case 125: t[0] -= 9; t[1] -= 3; break;
-			case 148: t[0] -= 8; break;           case 149: t[0] += 8; break;
+			case 141: ARM(Y24_141); t[0] -= 5; break;           case 140: ARM(Y24_140); t[0] += 5; break;
+			case 144: ARM(Y24_144); t[0] -= 3; break;           case 145: ARM(Y24_145); t[0] += 3; break;
+			case 121: ARM(Y24_121); t[0] -= 4; t[1] -= 3; break; case 122: ARM(Y24_122); t[0] += 4; t[1] += 3; break;
+			case 123: ARM(Y24_123); t[0] += 2; t[1] += 2; t[2] += 2; break;
+			case 124: ARM(Y24_124); t[0] -= 2; t[1] -= 2; t[2] -= 2; break;
+			case 126: ARM(Y24_126); t[0] += 9; t[1] += 3; break; case 125: ARM(Y24_125); t[0] -= 9; t[1] -= 3; break;
+			case 148: ARM(Y24_148); t[0] -= 8; break;           case 149: ARM(Y24_149); t[0] += 8; break;
 			default: break;
 			}
 		}
@@ -406,6 +407,7 @@ static void build_poslists(nhwo_ctx *c)
 					else if (*cell == 145) { raw[n++] = (uint8_t)j; *cell = 0; pay[e++] = 0; }
 				}
 			}
+		c->raw_count[pass] = n;
 		nhwo_poslist_finish(c, pass == 0 ? &c->res1 : pass == 1 ? &c->res3 : &c->res5, raw, n, pay, e, pass == 1 ? 2 : 1);
 	}
 	free(pay); free(raw);
@@ -416,13 +418,13 @@ static inline void ripple(int16_t *v, int may_look_two_ahead)
 {
 	const int e = v[0];
 	if (iabs(e) <= 6) return;
-	if (e >= 8 && (e & 7) < 2) { if (v[1] > 7 && v[1] < 10000) v[1]--; }
-	else if (e == -7 && v[1] == 8) v[0] = -8;
-	else if (e == 8 && v[1] == -7) v[1] = -8;
+	if (e >= 8 && (e & 7) < 2) { if (v[1] > 7 && v[1] < 10000) { ARM(RIPPLE_DEC); v[1]--; } }
+	else if (e == -7 && v[1] == 8) { ARM(RIPPLE_M7_8); v[0] = -8; }
+	else if (e == 8 && v[1] == -7) v[1] = -8;      /* (never taken: the first test has every 8) */
 	else if (e < -7 && ((-e) & 7) < 2) {
 		if (v[1] < -14) {
-			if (((-v[1]) & 7) == 7) v[1]++;
-			else if (((-v[1]) & 7) < 2 && may_look_two_ahead && v[2] <= 0) v[1]++;
+			if (((-v[1]) & 7) == 7) { ARM(RIPPLE_NEG_7); v[1]++; }
+			else if (((-v[1]) & 7) < 2 && may_look_two_ahead && v[2] <= 0) { ARM(RIPPLE_NEG_AHEAD); v[1]++; }
 		}
 	}
 }
@@ -444,9 +446,9 @@ static void clean_details(nhwo_ctx *c)
 			int16_t *v = p + r * W + j;
 			if (iabs(v[0]) >= DEADZONE - 2) {
 				if (iabs(v[0]) < lim2) {
-					if (loud_neighbours(v) < 3 && v[0] < lim && v[0] > -lim) { if (v[0] < -6) v[0] = -7; else if (v[0] > 6) v[0] = 7; }
+					if (loud_neighbours(v) < 3 && v[0] < lim && v[0] > -lim) { if (v[0] < -6) { ARM(Y27_LH_TO_M7); v[0] = -7; } else if (v[0] > 6) { ARM(Y27_LH_TO_7); v[0] = 7; } }
 				}
-			} else v[0] = 0;
+			} else { if (v[0]) ARM(Y27_LH_ZERO); v[0] = 0; }
 			ripple(v, j < W - 2);
 		}
 
@@ -457,9 +459,9 @@ static void clean_details(nhwo_ctx *c)
 			if (iabs(v[0]) >= DEADZONE - 2) {
 				if (iabs(v[0]) < lim2) {
 					const int n = loud_neighbours(v);
-					if ((n < 3 && v[0] < lim && v[0] > -lim) || !n) v[0] = (int16_t)(v[0] < 0 ? -7 : 7);
+					if ((n < 3 && v[0] < lim && v[0] > -lim) || !n) { ARM(Y27_HL_TO_7); v[0] = (int16_t)(v[0] < 0 ? -7 : 7); }
 				}
-			} else v[0] = 0;
+			} else { if (v[0]) ARM(Y27_HL_ZERO); v[0] = 0; }
 			ripple(v, j < H - 2);
 		}
 
@@ -468,8 +470,8 @@ static void clean_details(nhwo_ctx *c)
 		for (j = H + 1; j < W - 1; j++) {
 			int16_t *v = p + r * W + j;
 			if (iabs(v[0]) >= DEADZONE - 1) {
-				if (iabs(v[0]) < lim) { if (loud_neighbours(v) < 3) v[0] = (int16_t)(v[0] < 0 ? -7 : 7); }
-			} else v[0] = 0;
+				if (iabs(v[0]) < lim) { if (loud_neighbours(v) < 3) { ARM(Y27_HH_TO_7); v[0] = (int16_t)(v[0] < 0 ? -7 : 7); } }
+			} else { if (v[0]) ARM(Y27_HH_ZERO); v[0] = 0; }
 			ripple(v, j < W - 2);
 		}
 }
@@ -667,14 +669,15 @@ static void smooth_ll2(nhwo_ctx *c)
 
 /* zeroing rule shared by the three bands of Y20 at q<=13: a small coefficient goes when its level-2 parent is small,
  * or together with a neighbour when the pair nearly cancels (:875-886 etc.) */
-static inline void thin_by_parent(int16_t *v, int parent, int lim_parent, int lim_pair)
+static inline void thin_by_parent(int16_t *v, int parent, int lim_parent, int lim_pair, int arm /* the band's first counter */)
 {
-	if (iabs(parent) < lim_parent) v[0] = 0;
-	else if (iabs(v[0] + v[-1]) < lim_pair && iabs(v[1]) < lim_pair) { v[0] = 0; v[-1] = 0; }
-	else if (iabs(v[0] + v[1]) < lim_pair && iabs(v[-1]) < lim_pair) { v[0] = 0; v[1] = 0; }
+	if (iabs(parent) < lim_parent) { nhwo_arm[arm]++; v[0] = 0; }
+	else if (iabs(v[0] + v[-1]) < lim_pair && iabs(v[1]) < lim_pair) { nhwo_arm[arm + 1]++; v[0] = 0; v[-1] = 0; }
+	else if (iabs(v[0] + v[1]) < lim_pair && iabs(v[-1]) < lim_pair) { nhwo_arm[arm + 2]++; v[0] = 0; v[1] = 0; }
 }
 static inline int16_t keep_loud(int v, int q) /* :947-953 */
 {
+	if (q > 10 && v >= 16) ARM(Y20L_KEEP_P7); else if (q > 10 && v <= -16) ARM(Y20L_KEEP_N7); else ARM(Y20L_KEEP_0);
 	if (q > 10) return (int16_t)(v >= 16 ? 7 : v <= -16 ? -7 : 0);
 	return 0;
 }
@@ -690,10 +693,10 @@ static void thin_l1_low(nhwo_ctx *c)
 	if (q >= 14) {                                               /* :804-832 */
 		t1 = 11; t2 = (q == 15) ? 19 : 20;
 		for (r = H; r < W; r++) {
-			for (j = 0; j < H; j++) { int16_t *v = p + r * W + j; if (iabs(*v) >= DEADZONE && iabs(*v) < t1) *v = 0; }
+			for (j = 0; j < H; j++) { int16_t *v = p + r * W + j; if (iabs(*v) >= DEADZONE && iabs(*v) < t1) { ARM(Y20M_HL_ZERO); *v = 0; } }
 			for (j = H; j < W; j++) {
 				int16_t *v = p + r * W + j;
-				if (iabs(*v) >= DEADZONE && iabs(*v) < t2) *v = (int16_t)(*v >= 14 ? 7 : *v <= -14 ? -7 : 0);
+				if (iabs(*v) >= DEADZONE && iabs(*v) < t2) { if (iabs(*v) >= 14) ARM(Y20M_HH_LOUD); else ARM(Y20M_HH_ZERO); *v = (int16_t)(*v >= 14 ? 7 : *v <= -14 ? -7 : 0); }
 			}
 		}
 		return;
@@ -703,9 +706,10 @@ static void thin_l1_low(nhwo_ctx *c)
 		int loud = 0, i;
 		t1 = 16; t2 = 28; t3 = 11; t4 = 8; t5 = 5;
 		for (i = 2 * Q; i < 4 * Q; i++) if (iabs(p[i]) >= 12) loud++;
-		if (loud > 12500) { t1 = 19; t2 = 31; t3 = 13; t4 = 9; t5 = 6; }
-		else if (loud > 10000) { t1 = 18; t2 = 30; t3 = 12; t4 = 8; t5 = 6; }
-		else if (loud >= 7000) { t1 = 17; t2 = 29; t3 = 11; t4 = 8; t5 = 5; }
+		if (loud > 12500) { ARM(Y20L_LOUD3); t1 = 19; t2 = 31; t3 = 13; t4 = 9; t5 = 6; }
+		else if (loud > 10000) { ARM(Y20L_LOUD2); t1 = 18; t2 = 30; t3 = 12; t4 = 8; t5 = 6; }
+		else if (loud >= 7000) { ARM(Y20L_LOUD1); t1 = 17; t2 = 29; t3 = 11; t4 = 8; t5 = 5; }
+		else ARM(Y20L_LOUD0);
 		if (q == 11) { if (loud > 12500) { t1++; t2++; t3++; t4++; t5++; } else t1++; }
 		else if (q <= 10) {
 			if (loud > 12500) { t1 += 3; t2 += 3; t3 += 2; t4 += 3; t5 += 3; }
@@ -716,34 +720,152 @@ static void thin_l1_low(nhwo_ctx *c)
 	for (r = 0; r < H; r++)                                      /* rows 0..255, columns 256..511 (:871-896) */
 		for (j = H; j < W; j++) {
 			int16_t *v = p + r * W + j;
-			if (iabs(*v) >= DEADZONE && iabs(*v) < t3 + 2) thin_by_parent(v, par[((r * H + (j - H)) >> 1) + H / 2], t4, t5);
-			if (iabs(*v) >= DEADZONE && iabs(*v) < t3) { if (iabs(v[-1]) < DEADZONE && iabs(v[1]) < DEADZONE) *v = 0; }
+			if (iabs(*v) >= DEADZONE && iabs(*v) < t3 + 2) thin_by_parent(v, par[((r * H + (j - H)) >> 1) + H / 2], t4, t5, ARM_Y20L_LH_PARENT);
+			if (iabs(*v) >= DEADZONE && iabs(*v) < t3) { if (iabs(v[-1]) < DEADZONE && iabs(v[1]) < DEADZONE) { ARM(Y20L_LH_ISO); *v = 0; } }
 		}
 	for (r = H; r < W; r++) {                                    /* rows 256..511 (:898-967) */
 		for (j = 0; j < H; j++) {
 			int16_t *v = p + r * W + j;
-			if (iabs(*v) >= DEADZONE && iabs(*v) < t1 + 2) thin_by_parent(v, par[(((r - H) * H + j) >> 1) + Q / 2], t4, t5);
+			if (iabs(*v) >= DEADZONE && iabs(*v) < t1 + 2) thin_by_parent(v, par[(((r - H) * H + j) >> 1) + Q / 2], t4, t5, ARM_Y20L_HL_PARENT);
 			if (iabs(*v) >= DEADZONE && iabs(*v) < t1) {
-				if (iabs(v[-1]) < DEADZONE && iabs(v[1]) < DEADZONE) *v = 0;
-				else if (iabs(*v) < t1 - 4) *v = 0;
+				if (iabs(v[-1]) < DEADZONE && iabs(v[1]) < DEADZONE) { ARM(Y20L_HL_ISO); *v = 0; }
+				else if (iabs(*v) < t1 - 4) { ARM(Y20L_HL_SMALL); *v = 0; }
 			}
 		}
 		for (j = H; j < W - 1; j++) {
 			int16_t *v = p + r * W + j;
 			if (iabs(*v) >= DEADZONE && iabs(*v) < t2 + 1)
-				thin_by_parent(v, par[(((r - H) * H + (j - H)) >> 1) + Q / 2 + H / 2], t4 + 1, t5);
+				thin_by_parent(v, par[(((r - H) * H + (j - H)) >> 1) + Q / 2 + H / 2], t4 + 1, t5, ARM_Y20L_HH_PARENT);
 			if (iabs(*v) >= DEADZONE && iabs(*v) < t2) {
-				if (iabs(v[-1]) < DEADZONE && iabs(v[1]) < DEADZONE) *v = keep_loud(*v, q);
-				else if (iabs(*v) < t2 - 5) *v = keep_loud(*v, q);
+				if (iabs(v[-1]) < DEADZONE && iabs(v[1]) < DEADZONE) { ARM(Y20L_HH_ISO); *v = keep_loud(*v, q); }
+				else if (iabs(*v) < t2 - 5) { ARM(Y20L_HH_SMALL); *v = keep_loud(*v, q); }
 			}
 		}
 	}
 }
 
-int nhwo_luma(nhwo_ctx *c)
+/* Y19 .. Y27: what encode_image does between the second level-2 synthesis and the quantiser (:766-2098), in three parts -- 0: Y19 .. Y23,
+ * 1: Y24 and Y25, 2: Y26 and Y27.  nhwo_luma runs all of them; nhwo_residual_stage runs parts first .. last on planes of its caller's. */
+static void residual_passes(nhwo_ctx *c, int first, int last)
 {
 	const int q = c->q;
 	int r, j, res_setting;
+
+	if (first <= 0 && last >= 0) {
+	if (q > 21) for (r = 0; r < H; r++) memcpy(c->first_order + r * H, c->jpeg + r * W, sizeof(int16_t) * H);   /* Y19 :766-777 */
+
+	if (nhwo_oob_mode && q <= 13) {
+		/* the same heap once more: Y20 reads its level-2 parents up to 128 entries behind resIII, which is followed by 8 bytes of stale
+		 * kernel map (row 256, columns 8..11), the size word of the next chunk (0x6011) and that chunk, tree1 (SURVEY App. D) */
+		extern int16_t nhwo_kernel_row256[4];
+		int16_t *tail = c->l2save + Q;
+		int k;
+		for (k = 0; k < 4; k++) tail[k] = nhwo_kernel_row256[k];
+		tail[4] = 0x6011; tail[5] = 0; tail[6] = 0; tail[7] = 0;
+		for (k = 0; k < 120; k++) tail[8 + k] = (int16_t)(c->ll_bytes[2 * k] | c->ll_bytes[2 * k + 1] << 8);
+	}
+	if (q <= 15) thin_l1_low(c);                                                                                /* Y20, q<=15 (:804-968) */
+	else if (q < 20) {                                                                                               /* Y20, 16<=q<=19 (:783-801) */
+		int16_t *p = c->proc;
+		for (r = H; r < W; r++) {
+			for (j = 0; j < H; j++) { int16_t *v = p + r * W + j; if (iabs(*v) >= DEADZONE && iabs(*v) < 9) { ARM(Y20H_HL); *v = (int16_t)(*v > 0 ? 7 : -7); } }
+			for (j = H; j < W; j++) { int16_t *v = p + r * W + j; if (iabs(*v) >= DEADZONE && iabs(*v) <= 14) { ARM(Y20H_HH); *v = (int16_t)(*v > 0 ? 7 : -7); } }
+		}
+	}
+	if (q > 16) tag_small_runs(c);                                                                              /* Y21 (:970) */
+
+	res_setting = q >= 20 ? 3 : q >= 18 ? 4 : q >= 15 ? 6 : 8;                                                  /* :1075-1079 */
+	if (q > 12) {                                                                                               /* :1081, :1498 */
+	classify_residuals(c, res_setting);                                                                         /* Y22 */
+	code_residuals(c, res_setting);                                                                             /* Y23 */
+	}
+	}
+	if (first <= 1 && last >= 1 && q > 12) {
+	if (q > 21) adjust_first_order(c);                                                                          /* Y24 */
+	build_poslists(c);                                                                                          /* Y25 */
+	}
+
+	if (first <= 2 && last >= 2) {
+	{                                                                                                           /* Y26 :1893-1910 */
+		int16_t *p = c->proc;
+		for (r = 0; r < H; r++)
+			for (j = 0; j < H; j++) {
+				const int16_t v = c->l2save[r * H + j];
+				p[r * W + j] = (r < H / 2 && j < H / 2 && v <= 8000) ? 0 : v;
+			}
+	}
+	clean_details(c);                                                                                           /* Y27 */
+	}
+}
+
+/* ---------------------------------------------------------------- the residual stage and its tap (nhwo.h) */
+uint32_t nhwo_arm[NHWO_ARM_MAX];
+nhwo_residual_tap *nhwo_residual_tap_ptr;
+#define NHWO_ARM_NAME(name, lo, hi) #name,
+#define NHWO_ARM_LO(name, lo, hi) lo,
+#define NHWO_ARM_HI(name, lo, hi) hi,
+static const char *const arm_names[] = { NHWO_ARMS(NHWO_ARM_NAME) };
+static const uint8_t arm_lo[] = { NHWO_ARMS(NHWO_ARM_LO) }, arm_hi[] = { NHWO_ARMS(NHWO_ARM_HI) };
+typedef char arm_table_fits[ARM_COUNT <= NHWO_ARM_MAX ? 1 : -1];
+int nhwo_arm_count(void) { return ARM_COUNT; }
+const char *nhwo_arm_name(int arm) { return arm >= 0 && arm < ARM_COUNT ? arm_names[arm] : NULL; }
+int nhwo_arm_live(int arm, int quality) { return arm >= 0 && arm < ARM_COUNT && quality >= arm_lo[arm] && quality <= arm_hi[arm]; }
+
+static void tap_planes(const nhwo_ctx *c, nhwo_residual_planes *t)
+{
+	memcpy(t->jpeg, c->jpeg, sizeof t->jpeg); memcpy(t->proc, c->proc, sizeof t->proc);
+	memcpy(t->ll1, c->ll1, sizeof t->ll1); memcpy(t->l2save, c->l2save, sizeof t->l2save);
+	memcpy(t->first_order, c->first_order, sizeof t->first_order);
+}
+/* the three lists as Y25 left them (a list the quality does not make: all lengths 0); arm0: the counters before the passes (NULL: not reported) */
+static void report_lists(const nhwo_ctx *c, nhwo_residual_out *out, const uint32_t *arm0)
+{
+	const nhwo_poslist *pl[3] = { &c->res1, &c->res3, &c->res5 };
+	int k;
+	memset(out, 0, sizeof *out);
+	for (k = 0; k < 3; k++) {
+		nhwo_residual_list *d = &out->pl[k];
+		if (!pl[k]->list) continue;
+		d->list_len = pl[k]->list_len; d->bits_len = pl[k]->bits_len; d->word_len = pl[k]->word_len; d->raw_count = c->raw_count[k];
+		memcpy(d->list, pl[k]->list, (size_t)d->list_len); memcpy(d->bits, pl[k]->bits, (size_t)d->bits_len);
+		memcpy(d->word, pl[k]->word, (size_t)d->word_len);
+	}
+	if (arm0) for (k = 0; k < ARM_COUNT; k++) out->arm[k] = nhwo_arm[k] - arm0[k];
+}
+
+int nhwo_residual_stage(int quality, int first, int last, int16_t *jpeg, int16_t *proc, int16_t *ll1, const int16_t *l2save,
+                        int16_t *first_order, nhwo_residual_out *out)
+{
+	nhwo_ctx ctx, *c = &ctx;
+	uint32_t arm0[NHWO_ARM_MAX];
+	if (!nhwo_quality_supported(quality) || first < 0 || last > 2 || first > last) return NHWO_E_QUALITY;
+	memset(c, 0, sizeof *c);
+	c->q = quality;
+	c->arena.cap = 8u << 20;
+	c->arena.base = (uint8_t *)calloc(c->arena.cap, 1);
+	if (!c->arena.base) return NHWO_E_ALLOC;
+#define GET(T, n) ((T *)arena_get(&c->arena, sizeof(T) * (size_t)(n)))
+	c->jpeg = GET(int16_t, 4 * Q); c->proc = GET(int16_t, 4 * Q);
+	c->ll1 = GET(int16_t, Q); c->l2save = GET(int16_t, Q + 256); c->first_order = GET(int16_t, Q);   /* (as nhwo_encode carves them) */
+	c->ll_bytes = GET(uint8_t, 96 * H + 1);
+#undef GET
+	if (!c->ll_bytes) { free(c->arena.base); return NHWO_E_ALLOC; }
+	memcpy(c->jpeg, jpeg, sizeof(int16_t) * 4 * Q); memcpy(c->proc, proc, sizeof(int16_t) * 4 * Q);
+	memcpy(c->ll1, ll1, sizeof(int16_t) * Q); memcpy(c->l2save, l2save, sizeof(int16_t) * Q);
+	memcpy(c->first_order, first_order, sizeof(int16_t) * Q);
+	memcpy(arm0, nhwo_arm, sizeof arm0);
+	residual_passes(c, first, last);
+	report_lists(c, out, arm0);
+	memcpy(jpeg, c->jpeg, sizeof(int16_t) * 4 * Q); memcpy(proc, c->proc, sizeof(int16_t) * 4 * Q);
+	memcpy(ll1, c->ll1, sizeof(int16_t) * Q); memcpy(first_order, c->first_order, sizeof(int16_t) * Q);
+	free(c->arena.base);
+	return NHWO_OK;
+}
+
+int nhwo_luma(nhwo_ctx *c)
+{
+	const int q = c->q;
+	int r;
 
 	if (q < 22) { nhwo_prefilter(c->jpeg, q); trace_planes(c, "pre_processing", c->jpeg, 8 * Q, NULL, 0); }   /* :116-119 */
 
@@ -804,46 +926,10 @@ int nhwo_luma(nhwo_ctx *c)
 	trace_planes(c, "offsetY_recons256_p0", c->jpeg, 8 * Q, c->proc, 8 * Q);
 	nhwo_synthesis(c->jpeg, c->proc, W, H);
 	trace_planes(c, "wavelet_synthesis_256", c->jpeg, 8 * Q, c->proc, 8 * Q);
-	if (q > 21) for (r = 0; r < H; r++) memcpy(c->first_order + r * H, c->jpeg + r * W, sizeof(int16_t) * H);   /* Y19 :766-777 */
 	}
-
-	if (nhwo_oob_mode && q <= 13) {
-		/* the same heap once more: Y20 reads its level-2 parents up to 128 entries behind resIII, which is followed by 8 bytes of stale
-		 * kernel map (row 256, columns 8..11), the size word of the next chunk (0x6011) and that chunk, tree1 (SURVEY App. D) */
-		extern int16_t nhwo_kernel_row256[4];
-		int16_t *tail = c->l2save + Q;
-		int k;
-		for (k = 0; k < 4; k++) tail[k] = nhwo_kernel_row256[k];
-		tail[4] = 0x6011; tail[5] = 0; tail[6] = 0; tail[7] = 0;
-		for (k = 0; k < 120; k++) tail[8 + k] = (int16_t)(c->ll_bytes[2 * k] | c->ll_bytes[2 * k + 1] << 8);
-	}
-	if (q <= 15) thin_l1_low(c);                                                                                /* Y20, q<=15 (:804-968) */
-	else if (q < 20) {                                                                                               /* Y20, 16<=q<=19 (:783-801) */
-		int16_t *p = c->proc;
-		for (r = H; r < W; r++) {
-			for (j = 0; j < H; j++) { int16_t *v = p + r * W + j; if (iabs(*v) >= DEADZONE && iabs(*v) < 9) *v = (int16_t)(*v > 0 ? 7 : -7); }
-			for (j = H; j < W; j++) { int16_t *v = p + r * W + j; if (iabs(*v) >= DEADZONE && iabs(*v) <= 14) *v = (int16_t)(*v > 0 ? 7 : -7); }
-		}
-	}
-	if (q > 16) tag_small_runs(c);                                                                              /* Y21 (:970) */
-
-	res_setting = q >= 20 ? 3 : q >= 18 ? 4 : q >= 15 ? 6 : 8;                                                  /* :1075-1079 */
-	if (q > 12) {                                                                                               /* :1081, :1498 */
-	classify_residuals(c, res_setting);                                                                         /* Y22 */
-	code_residuals(c, res_setting);                                                                             /* Y23 */
-	if (q > 21) adjust_first_order(c);                                                                          /* Y24 */
-	build_poslists(c);                                                                                          /* Y25 */
-	}
-
-	{                                                                                                           /* Y26 :1893-1910 */
-		int16_t *p = c->proc;
-		for (r = 0; r < H; r++)
-			for (j = 0; j < H; j++) {
-				const int16_t v = c->l2save[r * H + j];
-				p[r * W + j] = (r < H / 2 && j < H / 2 && v <= 8000) ? 0 : v;
-			}
-	}
-	clean_details(c);                                                                                           /* Y27 */
+	if (nhwo_residual_tap_ptr) tap_planes(c, &nhwo_residual_tap_ptr->in);
+	residual_passes(c, 0, 2);                                                                                   /* Y19 .. Y27 */
+	if (nhwo_residual_tap_ptr) { tap_planes(c, &nhwo_residual_tap_ptr->out); report_lists(c, &nhwo_residual_tap_ptr->lists, NULL); }
 	trace_planes(c, "pre_offsetY", NULL, 0, c->proc, 8 * Q);
 	nhwo_quantise_luma(c);                                                                                      /* Y28 :2100 */
 	trace_planes(c, "offsetY", NULL, 0, c->proc, 8 * Q);

@@ -18,6 +18,44 @@ class _StreamInfo(ctypes.Structure):
                                             "size_book1", "size_book2", "tree_end", "wavelet_type", "words")]
 
 
+Q = 65536
+ARM_MAX = 128
+
+
+class _ResidualList(ctypes.Structure):
+    _fields_ = [("list_len", ctypes.c_int), ("bits_len", ctypes.c_int), ("word_len", ctypes.c_int), ("raw_count", ctypes.c_int),
+                ("list", ctypes.c_uint8 * (Q + 64)), ("bits", ctypes.c_uint8 * (Q // 8 + 64)), ("word", ctypes.c_uint8 * (Q // 4 + 64))]
+
+
+class _ResidualOut(ctypes.Structure):
+    _fields_ = [("pl", _ResidualList * 3), ("arm", ctypes.c_uint32 * ARM_MAX)]
+
+
+class _ResidualPlanes(ctypes.Structure):
+    _fields_ = [("jpeg", ctypes.c_int16 * (4 * Q)), ("proc", ctypes.c_int16 * (4 * Q)), ("ll1", ctypes.c_int16 * Q),
+                ("l2save", ctypes.c_int16 * Q), ("first_order", ctypes.c_int16 * Q)]
+
+
+class _ResidualTap(ctypes.Structure):
+    _fields_ = [("inp", _ResidualPlanes), ("out", _ResidualPlanes), ("lists", _ResidualOut)]
+
+
+RESIDUAL_PLANES = ("jpeg", "proc", "ll1", "l2save", "first_order")
+
+
+def _planes_dict(p):
+    return {k: np.frombuffer(getattr(p, k), np.int16).copy() for k in RESIDUAL_PLANES}
+
+
+def _lists_dict(out, arm_names=None):
+    """nhwo_residual_out -> {"lists": three dicts (list, bits, word as bytes; raw_count), "arms": {name: count}}"""
+    r = {"lists": [{"list": bytes(l.list[:l.list_len]), "bits": bytes(l.bits[:l.bits_len]), "word": bytes(l.word[:l.word_len]),
+                    "raw_count": l.raw_count} for l in out.pl]}
+    if arm_names is not None:
+        r["arms"] = {n: int(out.arm[i]) for i, n in enumerate(arm_names)}
+    return r
+
+
 class Oracle:
     def __init__(self, so_path: str = SO):
         L = self.lib = ctypes.CDLL(so_path)
@@ -119,6 +157,45 @@ class Oracle:
         r.update(luma=out, packet=pk[:min(r["words"], packet_cap)], book1=b1[:r["size_book1"]], book2=b2[:r["size_book2"]],
                  sel_word1=s1[:r["select1"]], sel_word2=s2[:r["select2"]])
         return r
+
+    def arm_names(self):
+        L = self.lib
+        L.nhwo_arm_name.restype = ctypes.c_char_p
+        return [L.nhwo_arm_name(i).decode() for i in range(L.nhwo_arm_count())]
+
+    def live_arms(self, q: int):
+        """the arm counters (by name) whose arm can be taken at quality q"""
+        return [n for i, n in enumerate(self.arm_names()) if self.lib.nhwo_arm_live(i, int(q))]
+
+    def residual_stage(self, q, jpeg, proc, ll1, l2save, first_order=None, first=0, last=2) -> dict:
+        """nhwo_residual_stage: parts first .. last (0: Y19 .. Y23, 1: Y24 and Y25, 2: Y26 and Y27) of the residual passes on planes of the
+        caller's (int16; jpeg, proc: 512 x 512; ll1, l2save, first_order: 256 x 256).  -> the five planes behind the passes (flat), "lists"
+        (res1, res3, res5: list, bits and word bytes, the raw entry count) and "arms" (the arm counters of this call by name)."""
+        a = [np.ascontiguousarray(x, np.int16).ravel().copy() for x in
+             (jpeg, proc, ll1, l2save, np.zeros(Q, np.int16) if first_order is None else first_order)]
+        assert [x.size for x in a] == [4 * Q, 4 * Q, Q, Q, Q]
+        out = _ResidualOut()
+        fn = self.lib.nhwo_residual_stage
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P, P, P, P, ctypes.POINTER(_ResidualOut)]
+        rc = fn(int(q), int(first), int(last), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, a[4].ctypes.data,
+                ctypes.byref(out))
+        if rc != 0:
+            raise RuntimeError(f"oracle residual stage failed rc={rc}")
+        r = dict(zip(RESIDUAL_PLANES, a))
+        r.update(_lists_dict(out, self.arm_names()))
+        return r
+
+    def encode_tapped(self, img, q):
+        """the whole encode with the residual tap set -> (file bytes, planes in front of Y19 .. Y27, planes behind them, the three lists)"""
+        tap = _ResidualTap()
+        ptr = ctypes.c_void_p.in_dll(self.lib, "nhwo_residual_tap_ptr")
+        ptr.value = ctypes.addressof(tap)
+        try:
+            data = self.encode(img, q)
+        finally:
+            ptr.value = None
+        return data, _planes_dict(tap.inp), _planes_dict(tap.out), _lists_dict(tap.lists)["lists"]
 
     def book_symbol_ok(self, v: int) -> bool:
         return bool(self.lib.nhwo_book_symbol_ok(int(v)))
