@@ -480,30 +480,24 @@ def crop_window(x: int, y: int, w: int, h: int, scale: int) -> tuple:
     return x // scale, y // scale, -(-(x + w) // scale) - x // scale, -(-(y + h) // scale) - y // scale
 
 
-FILTERS = {"two_tap": 0, "area": 1}                # NHW_FILTER_TWO_TAP, NHW_FILTER_AREA
+RESAMPLERS = {"two_tap": 0, "area": 1, "cubic": 2}  # NHW_FILTER_TWO_TAP, NHW_FILTER_AREA, NHW_FILTER_CUBIC: what the `filter` arguments take
+FILTERS = {k: v for k, v in RESAMPLERS.items() if k != "cubic"}   # ... without the cubic filter: what nhw_dec_crops_to_device_filter takes
 AREA_MAX_REDUCTION = 128                           # NHW_AREA_MAX_REDUCTION: the area filter takes a side down to 1 / 128 at the most
-RESAMPLERS = {"two_tap": 0, "area": 1, "cubic": 2}  # FILTERS and NHW_FILTER_CUBIC: what the `filter` arguments take
 CUBIC_MAX_REDUCTION = 32                           # NHW_CUBIC_MAX_REDUCTION: the cubic filter takes a side down to 1 / 32 at the most
+_LIMITS = {"area": AREA_MAX_REDUCTION, "cubic": CUBIC_MAX_REDUCTION}   # the reduction limit by filter name; the two taps have none
 
 
 def _filter(filter, what):
-    """the checked NHW_FILTER_* value of a filter name"""
+    """raises unless `filter` is a filter's name, a key of RESAMPLERS"""
     if not isinstance(filter, str) or filter not in RESAMPLERS:
         raise NhwError(f"{what}: `filter` must be one of {', '.join(repr(k) for k in RESAMPLERS)}, got {filter!r}")
-    return RESAMPLERS[filter]
-
-
-def _area_limit(w, h, out_w, out_h, what, which):
-    if w > AREA_MAX_REDUCTION * out_w or h > AREA_MAX_REDUCTION * out_h:
-        raise NhwError(f"{what}: {which} is {w} x {h}, more than {AREA_MAX_REDUCTION} times the output's {out_w} x {out_h} along a side: beyond the area filter's limit")
 
 
 def _filter_limit(filter, w, h, out_w, out_h, what, which):
-    """raises for a picture or window beyond the reduction limit of the (checked) filter"""
-    if filter == RESAMPLERS["area"]:
-        _area_limit(w, h, out_w, out_h, what, which)
-    elif filter == RESAMPLERS["cubic"] and (w > CUBIC_MAX_REDUCTION * out_w or h > CUBIC_MAX_REDUCTION * out_h):
-        raise NhwError(f"{what}: {which} is {w} x {h}, more than {CUBIC_MAX_REDUCTION} times the output's {out_w} x {out_h} along a side: beyond the cubic filter's limit")
+    """raises for a picture or window beyond the reduction limit of the filter (a checked name)"""
+    limit = _LIMITS.get(filter)
+    if limit and (w > limit * out_w or h > limit * out_h):
+        raise NhwError(f"{what}: {which} is {w} x {h}, more than {limit} times the output's {out_w} x {out_h} along a side: beyond the {filter} filter's limit")
 
 
 def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
@@ -518,18 +512,15 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     pictures' own bytes.  Ordered on torch's current stream."""
     import torch
     what = "resize_to_tensor_device"
-    filter = _filter(filter, what)
+    _filter(filter, what)
     fmt = _tensor_format(fmt, what)
     out_h, out_w = _crop_size(size, what)
-    if filter == RESAMPLERS["cubic"] and isinstance(pictures, (list, tuple)):   # from the shapes alone, before a device is looked at
+    if isinstance(pictures, (list, tuple)):                          # the limit from the shapes alone, before a device is looked at
         for i, x in enumerate(pictures):
             if len(getattr(x, "shape", ())) == 3:
                 _filter_limit(filter, int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
     table, _, dev = _picture_table(pictures, what)
     n = len(pictures)
-    if filter == FILTERS["area"]:
-        for i, x in enumerate(pictures):
-            _area_limit(int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
     flags = _crop_flips(flips, n, what)
     out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
     addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (3 * out_h * out_w * out.element_size())
@@ -538,12 +529,8 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     L = _library()
     c = fmt.c_struct()
     with torch.cuda.device(dev):
-        rest = (ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None, addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        if filter == RESAMPLERS["cubic"]:
-            rc = L.nhw_resample_to_tensor_device(table.data_ptr(), n, out_w, out_h, filter, *rest)
-        else:
-            call = L.nhw_area_to_tensor_device if filter == FILTERS["area"] else L.nhw_resize_to_tensor_device
-            rc = call(table.data_ptr(), n, out_w, out_h, *rest)
+        rc = L.nhw_resample_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                                             addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -984,7 +971,7 @@ class Encoder:
         out_h, out_w = _crop_size(size, what)
         n, blob, in_off, width, height, _, _ = self._host_pictures(pictures, what)
         for i in range(n):
-            _area_limit(int(width[i]), int(height[i]), out_w, out_h, what, f"picture {i}")
+            _filter_limit("area", int(width[i]), int(height[i]), out_w, out_h, what, f"picture {i}")
         arena = np.empty(n * (16 + picture_tiles(out_w, out_h) * (4 + OUT_STRIDE)), np.uint8)
         offs = np.empty(n + 1, np.uint64)
         status = np.empty(n, np.int32)
@@ -1431,7 +1418,7 @@ class Decoder:
         work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls."""
         import numpy as np
         what = "decode_crops_device"
-        filter = _filter(filter, what)
+        _filter(filter, what)
         t = self.torch
         fmt = _tensor_format(fmt, what)
         out_h, out_w = _crop_size(size, what)
@@ -1450,7 +1437,7 @@ class Decoder:
             scales = sc.tolist()
         else:
             scales = [scale] * n
-        if filter:
+        if filter in _LIMITS:
             for i, r in enumerate(table):
                 _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
         dev = t.device("cuda", self.device)
@@ -1470,8 +1457,7 @@ class Decoder:
             f = np.ascontiguousarray(flags[idx]) if flags is not None else None
             args = (self.h, blob.ctypes.data, offs.ctypes.data, len(containers), sub.ctypes.data, len(idx), s, out_w, out_h,
                     ctypes.byref(c), f.ctypes.data if f is not None else None, a.ctypes.data, st.ctypes.data)
-            self._chk(self.lib.nhw_dec_crops_to_device_resample(*args, filter) if filter == RESAMPLERS["cubic"] else
-                      self.lib.nhw_dec_crops_to_device_filter(*args, filter) if filter else self.lib.nhw_dec_crops_to_device(*args))
+            self._chk(self.lib.nhw_dec_crops_to_device_resample(*args, RESAMPLERS[filter]))
             status[idx] = st
         self._region_raise(status)
         return (out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)), scales

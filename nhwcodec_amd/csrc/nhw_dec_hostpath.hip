@@ -1,5 +1,5 @@
 /* nhw_dec_hostpath.hip -- the decoder's host conveniences: files in host memory in, pictures out (nhw_dec_batch), pictures of any size and regions of them out of
- * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip) and nhw_picture.hip. */
+ * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip), nhw_picture.hip and nhw_resample.hip. */
 #include "nhw_dec.h"
 #include "nhw_tensor.h"
 
@@ -220,17 +220,7 @@ static void source_look(RegionSource &c, const uint8_t *base, size_t len)   /* t
  * tensor -- the others get the address 0, which the kernel passes over.  With the area filter that launch is
  * k_area_to_tensor, with the cubic filter (section 20) k_cubic_to_tensor, and a rect whose window is beyond the filter's reduction limit for
  * the output size is NHW_E_ARG before it selects a tile. */
-struct CropSpec {
-	uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter;
-	uint32_t limit;                                              /* the filter's reduction limit, 0 for none */
-	decltype(nhw_launch_resize_to_tensor) *launch;               /* ... and its kernel */
-};
-static void crop_filter(CropSpec &c, int filter)
-{
-	c.filter = filter;
-	c.limit = filter == NHW_FILTER_CUBIC ? NHW_CUBIC_MAX_REDUCTION : filter == NHW_FILTER_AREA ? NHW_AREA_MAX_REDUCTION : 0;
-	c.launch = filter == NHW_FILTER_CUBIC ? nhw_launch_cubic_to_tensor : filter == NHW_FILTER_AREA ? nhw_launch_area_to_tensor : nhw_launch_resize_to_tensor;
-}
+struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter; };
 
 static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
                        const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, bool merge = true,
@@ -245,6 +235,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 	if (crop) for (int i = 0; i < nr; i++) if (!dst_addr[i] || dst_addr[i] % (crop->dtype == NHW_T_U8 ? 1u : crop->dtype == NHW_T_F32 ? 4u : 2u)) { nhw_dec_err = std::string(who) + ": a destination needs an address that is a multiple of the element size"; return NHW_E_ARG; }
 	d->reg_tiles = d->reg_bytes = 0;
 	const uint32_t T = 512u / (uint32_t)scale;
+	const uint64_t limit = crop ? nhw_filter_limit(crop->filter) : 0;   /* the filter's reduction limit, 0 for none */
 	std::vector<RegionSource> src((size_t)nc);
 	std::vector<std::vector<int32_t>> slot_of((size_t)nc);        /* per container: a tile's (latest) slot, -1 while no window has selected it */
 	std::vector<nhw_region> desc;
@@ -260,7 +251,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		const nhw_rect &r = rects[i];
 		status[i] = NHW_E_ARG;
 		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
-		if (crop && crop->limit && (r.width > (uint64_t)crop->limit * crop->out_w || r.height > (uint64_t)crop->limit * crop->out_h)) continue;
+		if (limit && (r.width > limit * crop->out_w || r.height > limit * crop->out_h)) continue;
 		RegionSource &c = src[r.container];
 		const uint8_t *base = blob + off[r.container];
 		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
@@ -338,8 +329,8 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 		HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
 		if (crop->flags) HIPCHK(hipMemcpyAsync(tab + pics_bytes + addr_bytes, crop->flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		HIPCHK(crop->launch((const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
-		              crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
+		HIPCHK(nhw_launch_resample(crop->filter, (const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
+		                           crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
 		HIPCHK(hipStreamSynchronize(s));
 		return NHW_OK;
 	}
@@ -372,45 +363,48 @@ extern "C" int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const 
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, dst_pitch, status, "nhw_dec_windows_to_device");
 }
 
-/* nhw_dec_windows_to_device with a resize behind it: window i, resampled to out_width x out_height and mirrored where bit 0 of
- * flags[i] is set, to the tensor at dst_addr[i] */
+/* nhw_dec_windows_to_device with a resize behind it (DESIGN.md sections 18 to 20): window i, resampled to out_width x out_height under `filter` and
+ * mirrored where bit 0 of flags[i] is set, to the tensor at dst_addr[i].  The three entries are this body and differ in `accept`, the filters an
+ * entry takes, a bit each: the two older ones take 0 and 1 (nhw_dec_crops_to_device_filter keeps refusing the cubic filter), the newest all
+ * three.  A filter an entry does not take is refused in that entry's words and at that entry's place among the checks, which callers can tell
+ * apart by the message they get for two mistakes at once: the newest entry looks at the filter first, the older ones at dst_addr and n_rects. */
+constexpr unsigned CROPS_TWO = 1u << NHW_FILTER_TWO_TAP | 1u << NHW_FILTER_AREA, CROPS_ALL = CROPS_TWO | 1u << NHW_FILTER_CUBIC;
 static int dec_crops(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale, uint32_t out_width,
-                     uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status, int filter)
+                     uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status, int filter, unsigned accept)
 {
-	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const bool taken = filter >= NHW_FILTER_TWO_TAP && filter <= NHW_FILTER_CUBIC && (accept >> filter & 1), args = dst_addr && n_rects <= (1 << 24);
+	if (!taken && (accept == CROPS_ALL || args)) {
+		nhw_dec_err = accept == CROPS_ALL ? "nhw_dec_crops_to_device_resample: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"
+		                                  : "nhw_dec_crops_to_device: the filter must be NHW_FILTER_TWO_TAP or NHW_FILTER_AREA";
+		return NHW_E_ARG;
+	}
+	if (!args) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_crops_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	CropSpec c = { out_width, out_height, 0, 0, {}, flags, 0, 0, nullptr };
-	crop_filter(c, filter);
+	CropSpec c = { out_width, out_height, 0, 0, {}, flags, filter };
 	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
 	c.dtype = fmt->dtype; c.layout = fmt->layout;
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", true, &c);
+}
+
+extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status)
+{
+	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, status, NHW_FILTER_TWO_TAP, CROPS_TWO);
 }
 
 extern "C" int nhw_dec_crops_to_device_filter(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                                               uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status,
                                               int filter)
 {
-	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	if (filter != NHW_FILTER_TWO_TAP && filter != NHW_FILTER_AREA) { nhw_dec_err = "nhw_dec_crops_to_device: the filter must be NHW_FILTER_TWO_TAP or NHW_FILTER_AREA"; return NHW_E_ARG; }
-	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, status, filter);
+	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, status, filter, CROPS_TWO);
 }
 
-/* ... for the filters 0 .. 2: 0 and 1 are the call above, 2 puts k_cubic_to_tensor behind the windows */
 extern "C" int nhw_dec_crops_to_device_resample(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                                                 uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
                                                 int *status, int filter)
 {
 	static_assert(sizeof(int) == sizeof(int32_t), "the statuses are 32 bits wide");
-	if (filter == NHW_FILTER_TWO_TAP || filter == NHW_FILTER_AREA)
-		return nhw_dec_crops_to_device_filter(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, (int32_t *)status, filter);
-	if (filter != NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_to_device_resample: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, (int32_t *)status, filter);
-}
-
-extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status)
-{
-	return nhw_dec_crops_to_device_filter(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, status, NHW_FILTER_TWO_TAP);
+	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, (int32_t *)status, filter, CROPS_ALL);
 }
 
 extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)

@@ -145,39 +145,38 @@ extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics,
 	return NHW_OK;
 }
 
-/* ... and resampled to one size on the way: the pictures of a table to out_width x out_height tensors, one pass of `launch` -- the two-tap
- * kernel or the area kernel (section 19) */
-static int resize_entry(const char *who, decltype(nhw_launch_resize_to_tensor) *launch, const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height,
-                        const nhw_tensor_format *fmt, const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
+/* ... and resampled to one size on the way: the pictures of a table to out_width x out_height tensors, one pass of the filter's kernel (DESIGN.md
+ * sections 18 to 20).  The three entries are this body; only nhw_resample_to_tensor_device can name a filter that does not exist.  A message
+ * names the entry that brought its filter in: through the newest entry the filters 0 and 1 are the older calls themselves, texts included. */
+static int resize_entry(int filter, const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *d_flags,
+                        const uint64_t *d_out_addr, void *stream)
 {
+	static const char *const entry[] = { "nhw_resize_to_tensor_device", "nhw_area_to_tensor_device", "nhw_resample_to_tensor_device" };
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
 	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = std::string(who) + ": an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = std::string(entry[filter]) + ": an output side outside 1 .. 4096"; return NHW_E_ARG; }
 	NhwTensorArgs a;
 	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
-	HIPCHK(launch(d_pics, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_flags, d_out_addr, (hipStream_t)stream));
+	HIPCHK(nhw_launch_resample(filter, d_pics, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_flags, d_out_addr, (hipStream_t)stream));
 	return NHW_OK;
 }
 
 extern "C" int nhw_resize_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                            const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
 {
-	return resize_entry("nhw_resize_to_tensor_device", nhw_launch_resize_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+	return resize_entry(NHW_FILTER_TWO_TAP, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
 }
 
 extern "C" int nhw_area_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                          const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
 {
-	return resize_entry("nhw_area_to_tensor_device", nhw_launch_area_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+	return resize_entry(NHW_FILTER_AREA, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
 }
 
-/* ... and with the filter named: 0 and 1 are the two entries above, 2 the cubic kernel */
 extern "C" int nhw_resample_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
                                              const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
 {
-	if (filter == NHW_FILTER_TWO_TAP) return nhw_resize_to_tensor_device(d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
-	if (filter == NHW_FILTER_AREA) return nhw_area_to_tensor_device(d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
-	if (filter != NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	return resize_entry("nhw_resample_to_tensor_device", nhw_launch_cubic_to_tensor, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
+	return resize_entry(filter, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
 }
 
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
@@ -395,9 +394,10 @@ extern "C" int nhw_enc_pictures_resized(nhw_enc *e, const uint8_t *bgr, const ui
 	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = "nhw_enc_pictures_resized: an output side outside 1 .. 4096"; return NHW_E_ARG; }
 	PicCall src, pc;
 	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures_resized", src); if (rc) return rc; }
+	const uint32_t limit = nhw_filter_limit(NHW_FILTER_AREA);
 	for (int i = 0; i < n; i++)
-		if (width[i] > NHW_AREA_MAX_REDUCTION * out_width || height[i] > NHW_AREA_MAX_REDUCTION * out_height) {
-			nhw_enc_err = "nhw_enc_pictures_resized: a picture more than " + std::to_string(NHW_AREA_MAX_REDUCTION) + " times the output size along a side";
+		if (width[i] > limit * out_width || height[i] > limit * out_height) {
+			nhw_enc_err = "nhw_enc_pictures_resized: a picture more than " + std::to_string(limit) + " times the output size along a side";
 			return NHW_E_ARG;
 		}
 	{
@@ -420,7 +420,7 @@ extern "C" int nhw_enc_pictures_resized(nhw_enc *e, const uint8_t *bgr, const ui
 	HIPCHK(hipMemcpyAsync((void *)d_desc, pc.desc.data(), desc_bytes, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync((void *)d_addr, addr.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
 	const NhwTensorArgs bytes = { { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f }, 0, 0 };
-	HIPCHK(nhw_launch_area_to_tensor(e->pic_desc.as<nhw_picture>(), n, out_width, out_height, NHW_T_U8, NHW_T_HWC, bytes, nullptr, d_addr, s));
+	HIPCHK(nhw_launch_resample(NHW_FILTER_AREA, e->pic_desc.as<nhw_picture>(), n, out_width, out_height, NHW_T_U8, NHW_T_HWC, bytes, nullptr, d_addr, s));
 	return encode_containers(e, d_desc, pc, quality, out_arena, arena_cap, out_off, status);
 }
 

@@ -1,10 +1,10 @@
 /*
- * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 18): the padding kernel k_tile_pad; the crops, which
+ * nhw_picture.hip -- pictures of any size as 512 x 512 tiles (DESIGN.md sections 11 to 17): the padding kernel k_tile_pad; the crops, which
  * share one body (crop_band over copy_rows) and differ in how a workgroup learns its tile and its rectangle -- k_untile_crop (k_tile_pad's
  * inverse: the whole picture, also from the 256 and 128 tiles of a scaled decode), k_untile_region (first_tile search) and k_untile_window (use
- * table) --; the picture-cropped error k_sse_crop, the pointwise k_bytes_to_tensor (section 16) and its resampling form k_resize_to_tensor
- * (section 18) with its area-filter form k_area_to_tensor (section 19), its mirrors k_tensor_to_bytes and k_tile_pad_tensor (section 17), and the .nhwp container that holds a picture's width, height
- * and tile files.
+ * table) --; the picture-cropped error k_sse_crop; the conversions between bytes and tensor formats, k_bytes_to_tensor (section 16) and its
+ * mirrors k_tensor_to_bytes and k_tile_pad_tensor (section 17); and on the host the geometry of tiles, regions, windows and crop scales and
+ * the .nhwp container that holds a picture's width, height and tile files.  The resamplers (sections 18 to 20) are in nhw_resample.hip.
  *
  * Padding rule: a W x H picture (B, G, R bytes, rows in BMP file order) is padded to 512 nx x 512 ny, nx = ceil(W / 512),
  * ny = ceil(H / 512), by edge replication: padded pixel (r, c) = picture pixel (min(r, H - 1), min(c, W - 1)).  Tile (ty, tx) is padded
@@ -323,12 +323,13 @@ __global__ __launch_bounds__(TP_THREADS) void k_sse_crop(const uint8_t *__restri
 /* What is already bytes, to a tensor format: picture k of the table to [H][W][3] or [3][H][W] elements at out_addr[k], under the
  * value rule of nhw_tensor.h.  The host knows no picture's size (the table lives in device memory), so a picture gets `per` workgroups whatever its
  * size and workgroup `part` walks rows part, part + per, ...; a thread takes a pixel of the row at a time: three byte loads (any alignment and pitch:
- * consecutive lanes on consecutive 3-byte pieces, never a byte outside the row) and three element stores -- in CHW consecutive lanes on consecutive
- * elements of a plane, in HWC 3 elements apart.  Pictures and tensors have no alignment to build wider stores on (W is any number). */
+ * consecutive lanes on consecutive 3-byte pieces, never a byte outside the row) and the pixel's three element stores (nhw_store_pixel) -- in CHW
+ * consecutive lanes on consecutive elements of a plane, in HWC 3 elements apart.  Pictures and tensors have no alignment to build wider stores on
+ * (W is any number).  The resampling forms of this kernel are in nhw_resample.hip. */
 template <int DT, int CHW>
 __global__ __launch_bounds__(TP_THREADS) void k_bytes_to_tensor(const nhw_picture *__restrict__ pics, int per, NhwTensorArgs a, const uint64_t *__restrict__ out_addr)
 {
-	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+	using E = typename NhwElem<DT>::type;
 	const int k = blockIdx.x / per, part = blockIdx.x % per;
 	const nhw_picture p = pics[k];
 	const uint64_t oa = out_addr[k];
@@ -339,345 +340,8 @@ __global__ __launch_bounds__(TP_THREADS) void k_bytes_to_tensor(const nhw_pictur
 		const uint8_t *src = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)r * p.pitch);
 		const size_t rr = a.flip ? H - 1 - r : r;
 		for (uint32_t c = threadIdx.x; c < p.width; c += TP_THREADS) {
-			const uint32_t b0 = src[3 * c], b1 = src[3 * c + 1], b2 = src[3 * c + 2];
-			const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b2 : b0, a.scale[0], a.bias[0]);
-			const E e1 = (E)nhw_tensor_elem<DT>(b1, a.scale[1], a.bias[1]);
-			const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b0 : b2, a.scale[2], a.bias[2]);
-			if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
-			else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
-		}
-	}
-}
-
-/* ---- crops resized into tensors of one size ----
- * The position of output index o along an axis of source length n (1 .. 65535) and output length m (1 .. 4096): X = min(floor(128 t / m),
- * 256 (n - 1)) with t = max((2 o + 1) n - m, 0), the centre-aligned (o + 1/2) n / m - 1/2 clamped to the axis, in 1/256 pixel.  t is below
- * 2^30, so with t = q m + r the quotient is 128 q + floor(128 r / m) in 32-bit arithmetic (128 r < 2^19).  Packed as X (i0 = X >> 8 in bits
- * 8 .. 23, f = X & 255) with i1 - i0 (0 or 1) in bit 24. */
-__device__ __forceinline__ uint32_t resize_pos(uint32_t o, uint32_t n, uint32_t m)
-{
-	const uint32_t s = (2 * o + 1) * n, t = s > m ? s - m : 0, q = t / m, r = t - q * m;
-	uint32_t X = 128 * q + 128 * r / m;
-	if (X > 256 * (n - 1)) X = 256 * (n - 1);
-	return X | ((X >> 8) + 1 < n ? 1u << 24 : 0u);
-}
-
-/* Picture k of the table, resampled to out_w x out_h under the rule of section 18 (two taps a direction, weights in 1/256, one rounding), mirrored
- * left-right where bit 0 of flags[k] says so, to [out_h][out_w][3] or [3][out_h][out_w] elements at out_addr[k] under the value rule of
- * nhw_tensor.h.  The host knows no picture's size, so the grid is crops x bands of `rows` output rows.  A workgroup puts the positions of all
- * out_w columns and of its band's rows into LDS -- the only divisions of the kernel --, and after the one barrier walks the band 256 >> lg
- * rows at a time, 1 << lg lanes a row (the power of two that holds out_w, 256 at the most: wider rows in steps).  A thread takes one output pixel
- * at a time: twelve byte loads (any alignment and pitch; consecutive lanes on neighbouring source pixels; never a byte outside a row's 3 W),
- * the blend, and three element stores as in k_bytes_to_tensor.  An entry with a zero or oversize side, a zero address or one that is no
- * multiple of the element size stores nothing. */
-constexpr int RS_MAX = 4096, RS_ROWS = 64;      /* the largest output side; the most rows a band has */
-template <int DT, int CHW>
-__global__ __launch_bounds__(TP_THREADS) void k_resize_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
-                                                                  NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
-{
-	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
-	__shared__ uint32_t col_pos[RS_MAX], row_pos[RS_ROWS];
-	const int k = blockIdx.x / bands;
-	const uint32_t r0 = (uint32_t)(blockIdx.x % bands) * (uint32_t)rows;     /* the band: output rows [r0, r0 + nr) */
-	const nhw_picture p = pics[k];
-	const uint64_t oa = out_addr[k];
-	if (!p.width || !p.height || p.width > 65535u || p.height > 65535u || !oa || (oa & (sizeof(E) - 1))) return;
-	if (out_w > (uint32_t)RS_MAX || rows > RS_ROWS || r0 >= out_h) return;     /* (the launcher sends neither) */
-	const uint32_t nr = out_h - r0 < (uint32_t)rows ? out_h - r0 : (uint32_t)rows;
-	const bool mirror = flags && (flags[k] & 1);
-	for (uint32_t o = threadIdx.x; o < out_w; o += TP_THREADS) col_pos[o] = resize_pos(o, p.width, out_w);
-	if (threadIdx.x < nr) row_pos[threadIdx.x] = resize_pos(r0 + threadIdx.x, p.height, out_h);
-	__syncthreads();
-	E *out = reinterpret_cast<E *>(oa);
-	const size_t W = out_w, H = out_h;
-	for (uint32_t r = threadIdx.x >> lg; r < nr; r += TP_THREADS >> lg) {
-		const uint32_t py = row_pos[r], fy = py & 255u;
-		const uint8_t *s0 = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)((py >> 8) & 0xFFFFu) * p.pitch);
-		const uint8_t *s1 = s0 + (uint64_t)(py >> 24) * p.pitch;
-		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
-		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
-			const uint32_t px = col_pos[mirror ? out_w - 1 - c : c], fx = px & 255u, x0 = 3 * ((px >> 8) & 0xFFFFu), x1 = x0 + 3 * (px >> 24);
-			const uint32_t w00 = (256 - fx) * (256 - fy), w01 = fx * (256 - fy), w10 = (256 - fx) * fy, w11 = fx * fy;
-			uint32_t b[3];
-#pragma unroll
-			for (int ch = 0; ch < 3; ch++)
-				b[ch] = (w00 * s0[x0 + ch] + w01 * s0[x1 + ch] + w10 * s1[x0 + ch] + w11 * s1[x1 + ch] + 32768u) >> 16;
-			const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
-			const E e1 = (E)nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
-			const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
-			if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
-			else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
-		}
-	}
-}
-
-/* ---- the area filter: k_resize_to_tensor's rule where an axis does not shrink, the exact box mean where it does ----
- * The taps of output index o along an axis of source length n and output length m, as a run: source pixels first .. first + count - 1, the
- * first with weight wf, the last (count > 1) with wl, those between with m.  m >= n: section 18's two taps, 256 - f and f (one tap of 256
- * where i1 = i0; the axis total is 256).  m < n: in units of 1 / m pixel output o covers [o n, (o + 1) n) and source pixel i [i m, (i + 1) m):
- * first = floor(o n / m), the last pixel ceil((o + 1) n / m) - 1, each weight the overlap (the total is n).  n <= 128 m (the caller's check)
- * makes count at most 129 and (o + 1) n at most 4096 x 65535 < 2^28.  Packed as first | count << 16 and wf | wl << 16 (both at most 4096). */
-__device__ __forceinline__ uint2 area_taps(uint32_t o, uint32_t n, uint32_t m)
-{
-	if (m >= n) {
-		const uint32_t p = resize_pos(o, n, m), f = p & 255u, two = p >> 24;
-		return make_uint2(((p >> 8) & 0xFFFFu) | (1u + two) << 16, (two ? 256u - f : 256u) | f << 16);
-	}
-	const uint32_t lo = o * n, hi = lo + n, first = lo / m, last = (hi + m - 1) / m - 1;
-	const uint32_t wf = ((first + 1) * m < hi ? (first + 1) * m : hi) - lo;
-	return make_uint2(first | (last - first + 1) << 16, wf | (hi - last * m) << 16);
-}
-
-/* sum of weight x byte over the run of x taps t (area_taps) of the row at s, a channel at a time: wf first + m (those between) + wl last;
- * at most 255 x the axis total, below 2^24 */
-__device__ __forceinline__ void area_row(const uint8_t *__restrict__ s, uint2 t, uint32_t m, uint32_t *r)
-{
-	const uint32_t cnt = t.x >> 16, wf = t.y & 0xFFFFu, wl = t.y >> 16;
-	const uint8_t *q = s + 3 * (t.x & 0xFFFFu);
-	uint32_t mid[3] = { 0, 0, 0 };
-	for (uint32_t i = 1; i + 1 < cnt; i++) { mid[0] += q[3 * i]; mid[1] += q[3 * i + 1]; mid[2] += q[3 * i + 2]; }
-#pragma unroll
-	for (int ch = 0; ch < 3; ch++) r[ch] = wf * q[ch] + m * mid[ch];
-	if (cnt > 1) {
-#pragma unroll
-		for (int ch = 0; ch < 3; ch++) r[ch] += wl * q[3 * (cnt - 1) + ch];
-	}
-}
-
-/* floor((2 S + D) / (2 D)) for S <= 255 D, D < 2^32: the quotient is at most 255, so the float estimate (three roundings of 2^-24 each on a
- * value below 256) is off by less than 1 and one 64-bit multiply-and-compare each way makes it exact */
-__device__ __forceinline__ uint32_t area_mean(uint64_t S, uint64_t D)
-{
-	const uint64_t N = 2 * S + D, D2 = 2 * D;
-	uint32_t q = (uint32_t)((float)N / (float)D2);
-	if ((uint64_t)q * D2 > N) q--;
-	else if ((uint64_t)(q + 1) * D2 <= N) q++;
-	return q;
-}
-
-/* k_resize_to_tensor with the taps of area_taps: the same table, formats, flags, grid (entries x bands of `rows` output rows) and walk -- a
- * thread one output pixel at a time, 1 << lg lanes a row.  The tap runs of all out_w columns and of the band's rows go into LDS (out_w + rows
- * entries of 8 bytes, sized by the launch) before the one barrier; they hold the kernel's only integer divisions.  A pixel then reads its
- * rows x columns source bytes once (byte loads, any alignment and pitch, never a byte outside a row's 3 W; neighbouring lanes on neighbouring
- * runs): every row gives three 32-bit sums (area_row), the rows between the first and the last add up in 32 bits as well (127 x 2^24 < 2^31),
- * and only the three products with the row weights and the division are 64 bits wide.  The loops run `count` times, at most 129: an entry
- * beyond the reduction limit on either axis stores nothing, like one with a zero or oversize side, a zero address or one that is no multiple
- * of the element size. */
-template <int DT, int CHW>
-__global__ __launch_bounds__(TP_THREADS) void k_area_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
-                                                                NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
-{
-	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
-	extern __shared__ uint2 area_tab[];                                    /* [out_w] columns, then [rows] rows */
-	const int k = blockIdx.x / bands;
-	const uint32_t r0 = (uint32_t)(blockIdx.x % bands) * (uint32_t)rows;     /* the band: output rows [r0, r0 + nr) */
-	const nhw_picture p = pics[k];
-	const uint64_t oa = out_addr[k];
-	if (!p.width || !p.height || p.width > 65535u || p.height > 65535u || !oa || (oa & (sizeof(E) - 1))) return;
-	if (out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX || rows > RS_ROWS || r0 >= out_h) return;   /* (the launcher sends neither) */
-	if (p.width > NHW_AREA_MAX_REDUCTION * out_w || p.height > NHW_AREA_MAX_REDUCTION * out_h) return;
-	const uint32_t nr = out_h - r0 < (uint32_t)rows ? out_h - r0 : (uint32_t)rows;
-	const bool mirror = flags && (flags[k] & 1);
-	uint2 *col_tap = area_tab, *row_tap = area_tab + out_w;
-	for (uint32_t o = threadIdx.x; o < out_w; o += TP_THREADS) col_tap[o] = area_taps(o, p.width, out_w);
-	if (threadIdx.x < nr) row_tap[threadIdx.x] = area_taps(r0 + threadIdx.x, p.height, out_h);
-	__syncthreads();
-	E *out = reinterpret_cast<E *>(oa);
-	const size_t W = out_w, H = out_h;
-	const uint64_t D = (uint64_t)(out_w >= p.width ? 256u : p.width) * (out_h >= p.height ? 256u : p.height);
-	for (uint32_t r = threadIdx.x >> lg; r < nr; r += TP_THREADS >> lg) {
-		const uint2 ty = row_tap[r];
-		const uint32_t cy = ty.x >> 16;
-		const uint8_t *s = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)(ty.x & 0xFFFFu) * p.pitch);
-		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
-		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
-			const uint2 tx = col_tap[mirror ? out_w - 1 - c : c];
-			uint32_t first[3], last[3] = { 0, 0, 0 }, mid[3] = { 0, 0, 0 }, b[3];
-			area_row(s, tx, out_w, first);
-			for (uint32_t i = 1; i + 1 < cy; i++) {
-				uint32_t v[3];
-				area_row(s + (uint64_t)i * p.pitch, tx, out_w, v);
-				mid[0] += v[0]; mid[1] += v[1]; mid[2] += v[2];
-			}
-			if (cy > 1) area_row(s + (uint64_t)(cy - 1) * p.pitch, tx, out_w, last);
-#pragma unroll
-			for (int ch = 0; ch < 3; ch++)
-				b[ch] = area_mean((uint64_t)(ty.y & 0xFFFFu) * first[ch] + (uint64_t)out_h * mid[ch] + (uint64_t)(ty.y >> 16) * last[ch], D);
-			const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
-			const E e1 = (E)nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
-			const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
-			if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
-			else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
-		}
-	}
-}
-
-/* ---- the cubic filter: the Keys cubic with a = -1/2, its support widened with the reduction, in integers ----
- * An axis of source length n (1 .. 65535) and output length m (1 .. 4096), n <= 32 m, D = max(n, m).  Source pixel i is at N = (2 i + 1) m -
- * (2 o + 1) n from output index o (2 m times the distance of the centres) and at U = floor((1024 |N| + D) / (2 D)) in 1/1024 of the kernel's
- * unit; the taps of o are the i in 0 .. n - 1 with U < 2048, which is |N| <= L = floor((4095 D - 1) / 1024): one run, from ceil((c - L - m) /
- * 2 m) to floor((c + L - m) / 2 m) with c = (2 o + 1) n, cut at the axis' ends.  c < 2^30 and L < 2^18, so all of it is 32-bit; L >= 3 D >= m
- * keeps the upper numerator positive, and the pixel nearest the output's centre has |N| <= m <= L: no run is empty.  The N of a run are 2 m
- * apart inside an interval shorter than 8 D: at most floor(4 D / m) + 1 taps, 129 under the limit.  Packed as first | count << 16. */
-constexpr int CB_HP = 4096;                     /* pixels of the horizontal pass a workgroup holds (three int16 each) */
-constexpr int CB_W = 2048;                      /* weights of a chunk of columns; of a chunk of rows */
-constexpr int CB_COLS = 256;                    /* the most columns a chunk has: a thread each when their weights are made */
-constexpr int CB_RUNS = 4;                      /* the source rows of a pass hold this many of the longest runs at least */
-__device__ __forceinline__ uint32_t cubic_reach(uint32_t D) { return (4095u * D - 1u) >> 10; }
-__device__ __forceinline__ uint32_t cubic_run(uint32_t o, uint32_t n, uint32_t m, uint32_t L)
-{
-	const int32_t c = (int32_t)((2 * o + 1) * n), a = c + (int32_t)m - 1 - (int32_t)L;
-	const uint32_t lo = a > 0 ? (uint32_t)a / (2 * m) : 0u;
-	uint32_t hi = (uint32_t)(c + (int32_t)L - (int32_t)m) / (2 * m);
-	if (hi > n - 1) hi = n - 1;
-	return lo | (hi >= lo ? hi - lo + 1 : 0u) << 16;
-}
-
-/* the Keys cubic times 2^31 at U < 2048, exact: 2^31 at 0, 0 at 1024, negative beyond */
-__device__ __forceinline__ int64_t cubic_raw(uint32_t U)
-{
-	const int64_t u = (int64_t)U;
-	if (U <= 1024u) return 3 * u * u * u - 5120 * u * u + (1ll << 31);
-	return -u * u * u + 5120 * u * u - (8ll << 20) * u + (1ll << 32);
-}
-__device__ __forceinline__ int64_t cubic_tap(uint32_t i, int32_t c, uint32_t m, uint32_t D)
-{
-	const int32_t N = (int32_t)((2 * i + 1) * m) - c;
-	return cubic_raw((1024u * (uint32_t)(N < 0 ? -N : N) + D) / (2 * D));     /* 1024 |N| + D < 4 x 1024 D + D < 2^29 */
-}
-
-/* The weights of the run `run` of output index o into w[0 .. count): q = floor((2^15 r + R) / (2 R)) with R the run's sum of r (positive), then
- * 2^14 - sum q onto the largest q (the first of equals).  The quotient lies inside +-2^15 (the tests bound sum |q|), so the float estimate --
- * three roundings of 2^-24 each -- is off by less than 1 and one 64-bit multiply-and-compare each way makes it the floor, also below zero.
- * `cap` is the room of w: count never exceeds it (above), and nothing is written beyond it. */
-__device__ __forceinline__ void cubic_weights(int16_t *w, uint32_t o, uint32_t run, uint32_t n, uint32_t m, uint32_t D, uint32_t cap)
-{
-	const uint32_t first = run & 0xFFFFu, count = (run >> 16) < cap ? run >> 16 : cap;
-	const int32_t c = (int32_t)((2 * o + 1) * n);
-	int64_t R = 0;
-	for (uint32_t k = 0; k < count; k++) R += cubic_tap(first + k, c, m, D);
-	if (R <= 0) { for (uint32_t k = 0; k < count; k++) w[k] = 0; return; }   /* (no run of the rule) */
-	const int64_t den = 2 * R;
-	int32_t sum = 0, best = -65536;
-	uint32_t at = 0;
-	for (uint32_t k = 0; k < count; k++) {
-		const int64_t num = cubic_tap(first + k, c, m, D) * 32768 + R;
-		int32_t q = (int32_t)floorf((float)num / (float)den);
-		if ((int64_t)q * den > num) q--;
-		else if ((int64_t)(q + 1) * den <= num) q++;
-		w[k] = (int16_t)q;
-		sum += q;
-		if (q > best) { best = q; at = k; }
-	}
-	if (count) w[at] = (int16_t)(w[at] + (16384 - sum));
-}
-
-/* k_resize_to_tensor under the cubic rule: the same table, formats, flags and grid (entries x bands of `rows` output rows).  The rule is
- * separable and fixes the rounding between the passes, so the kernel is: H[y][ox] = (sum_x qx P[y][x] + 128) >> 8 for the source rows a group
- * of output rows needs, as int16 in LDS, then byte = clamp((sum_y qy H[y][ox] + 2^19) >> 20) from there -- Tx + Ty multiply-adds a pixel where
- * the direct form has Tx Ty.  The host knows no source size, so the LDS is fixed: CB_HP pixels of H (24 576 bytes), CB_W int16 weights for a
- * chunk of columns and as many for a chunk of rows (8192), the runs of a chunk's columns and of the band's rows (1280): 34 048 bytes, four
- * workgroups a CU.  The workgroup cuts its band itself, uniformly, from sizes it has checked: tb = floor(4 D / m) + 1 bounds an axis' runs;
- * the weights of wc = min(out_w, CB_COLS, CB_W / tbx) columns are held at a time (all of them for a 224-wide output below a reduction of 2);
- * a pass takes cc = min(wc, CB_HP / (CB_RUNS tby)) of them, so that CB_HP / cc source rows (CB_RUNS runs at least) fit; a chunk of rows grows
- * while its weights fit (CB_W / tby rows) and its source rows -- first run's first to last run's end; firsts and ends do not decrease with
- * o -- fit.  Per chunk of columns: runs and weights (a thread a column); in it per chunk of rows: its weights (a thread a row), barrier; in
- * it per pass: H (a thread a source row and column at a time, byte loads, any alignment and pitch, never a byte outside a row's 3 W),
- * barrier, the vertical pass and the element stores, barrier.  Every loop bound is one of these sizes or a count clamped to its table's
- * room.  An entry beyond the reduction limit on either axis stores nothing, like one with a zero or oversize side, a zero address or one
- * that is no multiple of the element size. */
-template <int DT, int CHW>
-__global__ __launch_bounds__(TP_THREADS) void k_cubic_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows,
-                                                                 NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
-{
-	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
-	__shared__ int16_t cb_h[3 * CB_HP], cb_wx[CB_W], cb_wy[CB_W];
-	__shared__ uint32_t cb_col[CB_COLS], cb_row[RS_ROWS];
-	static_assert(CB_COLS <= TP_THREADS && RS_ROWS <= TP_THREADS, "a thread a run");
-	const int k = blockIdx.x / bands;
-	const uint32_t r0 = (uint32_t)(blockIdx.x % bands) * (uint32_t)rows;     /* the band: output rows [r0, r0 + nr) */
-	const nhw_picture p = pics[k];
-	const uint64_t oa = out_addr[k];
-	if (!p.width || !p.height || p.width > 65535u || p.height > 65535u || !oa || (oa & (sizeof(E) - 1))) return;
-	if (!out_w || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX || rows < 1 || rows > RS_ROWS || r0 >= out_h) return;   /* (the launcher sends neither) */
-	if (p.width > NHW_CUBIC_MAX_REDUCTION * out_w || p.height > NHW_CUBIC_MAX_REDUCTION * out_h) return;
-	const uint32_t nr = out_h - r0 < (uint32_t)rows ? out_h - r0 : (uint32_t)rows;
-	const bool mirror = flags && (flags[k] & 1);
-	const uint32_t Dx = p.width > out_w ? p.width : out_w, Dy = p.height > out_h ? p.height : out_h;
-	const uint32_t tbx = 4 * Dx / out_w + 1, tby = 4 * Dy / out_h + 1;          /* 5 .. 129 */
-	uint32_t wc = out_w < (uint32_t)CB_COLS ? out_w : (uint32_t)CB_COLS;        /* columns whose weights are held at a time */
-	if (wc > CB_W / tbx) wc = CB_W / tbx;
-	uint32_t cc = wc;                                                        /* ... and columns of a pass: 7 at the least, or out_w */
-	if (cc > (uint32_t)CB_HP / (CB_RUNS * tby)) cc = (uint32_t)CB_HP / (CB_RUNS * tby);
-	const uint32_t smax = CB_HP / cc, rcmax = CB_W / tby;
-	uint32_t lanes = 1;
-	while (lanes < cc) lanes <<= 1;                                          /* lanes a row of a pass: 1 .. 256 */
-	if (threadIdx.x < nr) cb_row[threadIdx.x] = cubic_run(r0 + threadIdx.x, p.height, out_h, cubic_reach(Dy));
-	__syncthreads();
-	E *out = reinterpret_cast<E *>(oa);
-	const size_t W = out_w, H = out_h;
-	for (uint32_t ws = 0; ws < out_w; ws += wc) {
-		const uint32_t nw = out_w - ws < wc ? out_w - ws : wc;
-		if (threadIdx.x < nw) {
-			const uint32_t run = cubic_run(ws + threadIdx.x, p.width, out_w, cubic_reach(Dx));
-			cb_col[threadIdx.x] = run;
-			cubic_weights(cb_wx + threadIdx.x * tbx, ws + threadIdx.x, run, p.width, out_w, Dx, tbx);
-		}
-		for (uint32_t rs = 0; rs < nr;) {
-			const uint32_t ylo = cb_row[rs] & 0xFFFFu;
-			uint32_t re = rs + 1;
-			while (re < nr && re - rs < rcmax && (cb_row[re] & 0xFFFFu) + (cb_row[re] >> 16) - ylo <= smax) re++;
-			const uint32_t span = (cb_row[re - 1] & 0xFFFFu) + (cb_row[re - 1] >> 16) - ylo;
-			if (span > smax || ylo + span > p.height) return;                /* (no run of the rule: smax holds CB_RUNS of the longest) */
-			if (threadIdx.x < re - rs) cubic_weights(cb_wy + threadIdx.x * tby, r0 + rs + threadIdx.x, cb_row[rs + threadIdx.x], p.height, out_h, Dy, tby);
-			__syncthreads();                                                 /* the weights of the columns and of these rows are there */
-			for (uint32_t cs = 0; cs < nw; cs += cc) {
-				const uint32_t ncol = nw - cs < cc ? nw - cs : cc;
-				for (uint32_t s = threadIdx.x / lanes; s < span; s += TP_THREADS / lanes) {
-					const uint8_t *src = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)(ylo + s) * p.pitch);
-					for (uint32_t j = threadIdx.x & (lanes - 1); j < ncol; j += lanes) {
-						const uint32_t run = cb_col[cs + j], cnt = (run >> 16) < tbx ? run >> 16 : tbx;
-						const uint8_t *q = src + 3 * (run & 0xFFFFu);
-						const int16_t *wt = cb_wx + (cs + j) * tbx;
-						int32_t acc[3] = { 0, 0, 0 };
-						for (uint32_t i = 0; i < cnt; i++) {
-							const int32_t wi = wt[i];
-							acc[0] += wi * (int32_t)q[3 * i]; acc[1] += wi * (int32_t)q[3 * i + 1]; acc[2] += wi * (int32_t)q[3 * i + 2];
-						}
-						int16_t *hp = cb_h + 3 * (s * ncol + j);
-#pragma unroll
-						for (int ch = 0; ch < 3; ch++) hp[ch] = (int16_t)((acc[ch] + 128) >> 8);
-					}
-				}
-				__syncthreads();
-				for (uint32_t r = threadIdx.x / lanes; r < re - rs; r += TP_THREADS / lanes) {
-					const uint32_t run = cb_row[rs + r], s0 = (run & 0xFFFFu) - ylo, cnt = (run >> 16) < tby ? run >> 16 : tby;
-					const int16_t *wt = cb_wy + r * tby;
-					const size_t rr = a.flip ? H - 1 - (r0 + rs + r) : r0 + rs + r;
-					for (uint32_t j = threadIdx.x & (lanes - 1); j < ncol; j += lanes) {
-						int32_t v[3] = { 0, 0, 0 };
-						uint32_t b[3];
-						for (uint32_t i = 0; i < cnt; i++) {
-							const int32_t wi = wt[i];
-							const int16_t *hp = cb_h + 3 * ((s0 + i) * ncol + j);
-							v[0] += wi * hp[0]; v[1] += wi * hp[1]; v[2] += wi * hp[2];
-						}
-#pragma unroll
-						for (int ch = 0; ch < 3; ch++) {
-							const int32_t y = (v[ch] + (1 << 19)) >> 20;
-							b[ch] = (uint32_t)(y < 0 ? 0 : y > 255 ? 255 : y);
-						}
-						const size_t c = mirror ? out_w - 1 - (ws + cs + j) : ws + cs + j;
-						const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
-						const E e1 = (E)nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
-						const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
-						if (CHW) { E *o = out + rr * W + c; o[0] = e0; o[H * W] = e1; o[2 * H * W] = e2; }
-						else { E *o = out + (rr * W + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
-					}
-				}
-				__syncthreads();                                             /* before H, these rows' weights or the columns' are written again */
-			}
-			rs = re;
+			const uint32_t b[3] = { src[3 * c], src[3 * c + 1], src[3 * c + 2] };
+			nhw_store_pixel<DT, CHW>(out, H, W, rr, c, b, a);
 		}
 	}
 }
@@ -737,7 +401,7 @@ template <int DT, int CHW, bool EDGE>
 __device__ __forceinline__ void pad_band_tensor(const TileRefOf<nhw_tensor_picture> &r, const NhwTensorArgs &a, uint8_t *__restrict__ dst, int band)
 {
 	constexpr int EB = NhwElem<DT>::bytes, QUADS = TP_ROWS * 128;
-	using E = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+	using E = typename NhwElem<DT>::type;
 	const uint32_t W = r.p.width, H = r.p.height;
 	const uint64_t px_step = CHW ? EB : 3 * EB, ch_step = CHW ? r.p.plane : EB;
 	for (int i = threadIdx.x; i < QUADS; i += TP_THREADS) {
@@ -797,66 +461,6 @@ hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int
 	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
 		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
 		k_bytes_to_tensor<DT, CHW><<<n_pics * per, TP_THREADS, 0, s>>>(d_pics, per, a, d_out_addr);
-	});
-	return hipGetLastError();
-}
-
-/* Bands: some 8192 workgroups in all where the crops are few, one band a crop where they are many; a band has at most RS_ROWS rows and, where
- * the output is narrow, at least the rows of one pass (256 >> lg), so that a pass has work for every lane. */
-hipError_t nhw_launch_resize_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                       const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return hipErrorInvalidValue;
-	int lg = 0;
-	while (lg < 8 && (1u << lg) < out_w) lg++;
-	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
-	uint32_t rows = (out_h + want - 1) / want;
-	if (rows < (uint32_t)(TP_THREADS >> lg)) rows = TP_THREADS >> lg;
-	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
-	const int bands = (int)((out_h + rows - 1) / rows);                 /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
-	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
-		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
-		k_resize_to_tensor<DT, CHW><<<n * bands, TP_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
-	});
-	return hipGetLastError();
-}
-
-/* The area filter: the bands of nhw_launch_resize_to_tensor (the same rule, so that both kernels meet the same launch shapes), and the LDS the
- * band's tap runs take: 8 (out_w + rows) bytes, 33 280 at the most. */
-hipError_t nhw_launch_area_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                     const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return hipErrorInvalidValue;
-	int lg = 0;
-	while (lg < 8 && (1u << lg) < out_w) lg++;
-	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
-	uint32_t rows = (out_h + want - 1) / want;
-	if (rows < (uint32_t)(TP_THREADS >> lg)) rows = TP_THREADS >> lg;
-	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
-	const int bands = (int)((out_h + rows - 1) / rows);                 /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
-	const size_t lds = sizeof(uint2) * ((size_t)out_w + rows);
-	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
-		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
-		k_area_to_tensor<DT, CHW><<<n * bands, TP_THREADS, lds, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
-	});
-	return hipGetLastError();
-}
-
-/* The cubic filter: the bands of nhw_launch_resize_to_tensor again; the kernel's LDS is static and it cuts its band itself */
-hipError_t nhw_launch_cubic_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                      const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return hipErrorInvalidValue;
-	int lg = 0;
-	while (lg < 8 && (1u << lg) < out_w) lg++;
-	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
-	uint32_t rows = (out_h + want - 1) / want;
-	if (rows < (uint32_t)(TP_THREADS >> lg)) rows = TP_THREADS >> lg;
-	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
-	const int bands = (int)((out_h + rows - 1) / rows);                 /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
-	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
-		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
-		k_cubic_to_tensor<DT, CHW><<<n * bands, TP_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr);
 	});
 	return hipGetLastError();
 }

@@ -1,7 +1,7 @@
 /*
  * nhw_tensor.h -- the tensor formats of a decode and of an encode (section 17; nhw_tensor_format in include/nhw_hip.h):
- * the value rule of each direction, the check of a format, the store shapes the decoder's last kernels (nhw_dec.hip) and the pointwise
- * kernels (nhw_picture.hip; the resampling one of section 18 among them) share, and the load shapes of the encoder's conversion kernels (nhw_picture.hip) that mirror them.
+ * the value rule of each direction, the check of a format, the store shapes of the decoder's last kernels (nhw_dec.hip), the pixel store
+ * of the pointwise kernel (nhw_picture.hip) and the resamplers (nhw_resample.hip), and the load shapes of the encoder's conversion kernels (nhw_picture.hip).
  *
  * Value rule of a decode: the element for byte b of output channel c is fmaf((float)b, scale[c], bias[c]) in single precision, rounded once, to
  * nearest even, to the output type; NHW_T_U8 passes the byte on.  The fma is explicit (the library builds with -ffp-contract=off).  That rounding
@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/nhw_hip.h"
 
@@ -45,7 +46,11 @@ inline bool nhw_tensor_format_is_bytes(const nhw_tensor_format *f)    /* what th
 	return f->dtype == NHW_T_U8 && f->layout == NHW_T_HWC && f->channels == NHW_T_BGR && f->rows == NHW_T_ROWS_FILE;
 }
 
-template <int DT> struct NhwElem { static constexpr int bytes = DT == NHW_T_U8 ? 1 : DT == NHW_T_F32 ? 4 : 2; };
+/* an element of a dtype: its size, and the unsigned integer that holds its bits */
+template <int DT> struct NhwElem {
+	static constexpr int bytes = DT == NHW_T_U8 ? 1 : DT == NHW_T_F32 ? 4 : 2;
+	using type = typename std::conditional<DT == NHW_T_U8, uint8_t, typename std::conditional<DT == NHW_T_F32, uint32_t, uint16_t>::type>::type;
+};
 
 /* the element of byte b, in the low bits of a dword */
 template <int DT> __device__ __forceinline__ uint32_t nhw_tensor_elem(uint32_t b, float scale, float bias)
@@ -65,6 +70,20 @@ template <int DT> __device__ __forceinline__ uint32_t nhw_tensor_elem(uint32_t b
 	 * finite), never a NaN, and an infinity's lower half is 0: the integer form is exact for every value that occurs */
 	const uint32_t u = __float_as_uint(x);
 	return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+/* One pixel, its bytes b[0 .. 2] as the byte path holds them (B, G, R), to row rr, column c of the h x w tensor at out: the channel order, the
+ * value rule and three element stores -- in CHW a plane apart, in HWC side by side.  What the kernels that make a pixel at a time share (the
+ * pointwise k_bytes_to_tensor, the resamplers of nhw_resample.hip); the caller has turned the row (a.flip) and, where it mirrors, the column. */
+template <int DT, int CHW>
+__device__ __forceinline__ void nhw_store_pixel(typename NhwElem<DT>::type *out, size_t h, size_t w, size_t rr, size_t c, const uint32_t *b, const NhwTensorArgs &a)
+{
+	using E = typename NhwElem<DT>::type;
+	const E e0 = (E)nhw_tensor_elem<DT>(a.rgb ? b[2] : b[0], a.scale[0], a.bias[0]);
+	const E e1 = (E)nhw_tensor_elem<DT>(b[1], a.scale[1], a.bias[1]);
+	const E e2 = (E)nhw_tensor_elem<DT>(a.rgb ? b[0] : b[2], a.scale[2], a.bias[2]);
+	if (CHW) { E *o = out + rr * w + c; o[0] = e0; o[h * w] = e1; o[2 * h * w] = e2; }
+	else { E *o = out + (rr * w + c) * 3; o[0] = e0; o[1] = e1; o[2] = e2; }
 }
 
 /* K dwords to p in vectors of V dwords (p aligned to 4 V bytes; 12-byte vectors to 4): plain vector stores.  The 16- and 8-byte ones are native
@@ -231,18 +250,14 @@ template <class F> inline void nhw_with_tensor_store(int dtype, int layout, cons
 
 /* nhw_picture.hip: every picture of the table to a tensor of its own size, one pass */
 hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s);
-/* ... and every picture resampled to out_w x out_h (1 .. 4096 each), mirrored where bit 0 of d_flags[k] is set (d_flags may be null) */
-hipError_t nhw_launch_resize_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                       const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
-/* ... the same with the area filter: the exact box mean along an axis that shrinks, section 18's two taps along one that does not; an
- * entry whose width exceeds NHW_AREA_MAX_REDUCTION out_w, or its height that many out_h, stores nothing */
-hipError_t nhw_launch_area_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                     const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
-/* ... the same with the cubic filter: the Keys cubic, a = -1/2, widened with the reduction; an entry whose width exceeds
- * NHW_CUBIC_MAX_REDUCTION out_w, or its height that many out_h, stores nothing */
-hipError_t nhw_launch_cubic_to_tensor(const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                      const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
-/* ... and the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
+/* nhw_resample.hip: every picture resampled to out_w x out_h (1 .. 4096 each), mirrored where bit 0 of d_flags[k] is set (d_flags may be null), under
+ * the filter NHW_FILTER_TWO_TAP, NHW_FILTER_AREA (section 19: the exact box mean along an axis that shrinks, the two taps along
+ * one that does not) or NHW_FILTER_CUBIC (section 20: the Keys cubic, a = -1/2, widened with the reduction).  An entry whose width exceeds
+ * nhw_filter_limit(filter) out_w, or its height that many out_h, stores nothing (0: the two taps have no limit) */
+inline uint32_t nhw_filter_limit(int filter) { return filter == NHW_FILTER_CUBIC ? NHW_CUBIC_MAX_REDUCTION : filter == NHW_FILTER_AREA ? NHW_AREA_MAX_REDUCTION : 0; }
+hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                               const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
+/* nhw_picture.hip again, the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
 

@@ -217,7 +217,7 @@ def test_unknown_filter_raises_before_any_device():
 
 # ---------------------------------------------------------------- on the MI355X: the kernel alone
 SRC_SIZES = [(1, 1), (2, 2), (3, 1), (5, 3), (7, 1), (33, 17), (128, 128), (256, 255), (300, 200)]      # W, H
-OUT_SIZES = [(1, 1), (2, 1), (3, 2), (16, 16), (100, 75), (100, 299), (224, 224), (299, 299)]           # W, H
+OUT_SIZES = [(1, 1), (2, 1), (3, 2), (16, 16), (100, 75), (100, 299), (224, 224), (299, 299), (4096, 1)]   # W, H
 ALL_32 = (100, 75)                                                  # the output size that meets all 32 formats
 FLAGS = [0, 1, 0, 1, 1, 0, 1, 1, 0]
 
@@ -303,7 +303,7 @@ def test_gpu_area_kernel_on_random_bytes(sources, out_w, out_h):
     the two formats of section 18's tests for the others; the batch between guards; then the wrapper"""
     import nhwcodec_amd as na
     ks = [k for k, s in enumerate(SRC_SIZES) if within(s, (out_w, out_h))]
-    assert len(ks) >= 7 and (len(ks) < len(SRC_SIZES)) == (out_w < 3)
+    assert len(ks) >= 7 and (len(ks) < len(SRC_SIZES)) == (out_w < 3 or out_h < 2)
     flags = [FLAGS[k] for k in ks]
     formats = [_fmt(*four, k=i // 2) for i, four in enumerate(ALL_FORMATS)] if (out_w, out_h) == ALL_32 else [_fmt(*BYTES), _fmt(*HALF)]
     for i, fmt in enumerate(formats):
