@@ -558,6 +558,55 @@ int nhw_tile_tensors_device(const nhw_tensor_picture *d_pics, int n_pics, int ti
 typedef struct { float total_ms, entropy_ms, recon_ms; } nhw_dec_timing;   /* recon_ms: the final reconstruction kernel (level-1 synthesis both ways + colour) */
 int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t);
 
+/* ---- affine warps into tensors of one size: rotate, shear, translate ----
+ * The resamplers above sample along an axis-aligned grid; a warp samples along a tilted one.  The source P is uint8 [h][w][3], B, G, R a pixel,
+ * rows in file order, sides 1 .. 65535 (what an nhw_picture describes); the output is out_width x out_height, 1 .. 4096 each; an entry
+ * carries one nhw_warp, declared below.  All arithmetic is signed 64-bit; every shift is arithmetic and floors.  For output pixel (ox, oy), numbered
+ * before the format's row reversal exactly as the resamplers number theirs:
+ *   position, in 1/65536 pixel on a grid where source pixel i has its centre at 65536 i:
+ *     SX = ((a (2 ox + 1) + b (2 oy + 1)) >> 1) + c,   SY = ((d (2 ox + 1) + e (2 oy + 1)) >> 1) + f
+ *     (the host folds the -1/2 of the centre convention into c and f); under the limits |SX|, |SY| < 2^41;
+ *   X8 = (SX + 128) >> 8, ix = X8 >> 8, fx = X8 & 255, and iy, fy from SY alike (1/256 pixel; ix and iy fit 32 bits);
+ *   the four taps (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1) with the weights (256 - fx)(256 - fy), fx (256 - fy), (256 - fx) fy,
+ *     fx fy.  A tap with x outside 0 .. w - 1 or y outside 0 .. h - 1 takes `fill`; with NHW_WARP_REPLICATE it takes the pixel at the
+ *     clamped index instead.  A tap is judged outside even where its weight is 0;
+ *   byte = (sum of weight x tap + 32768) >> 16, a channel: section 18's blend, which cannot leave 0 .. 255;
+ *   the tensor is what nhw_bytes_to_tensor_device makes of these bytes under the format: its value rule, channel order, row direction and
+ *     layout.  There is no mirror flag: a mirror is a matrix.
+ * The limits: each of |a|, |b|, |d|, |e| <= NHW_WARP_MAX_STEP x 65536 = 2^22, |c|, |f| <= 2^40.  An entry beyond them stores nothing, and so
+ * do the entries the resamplers pass over: a zero or oversize side, a zero address, an address that is no multiple of the element size.
+ * From a matrix [[A, B, C], [D, E, F]] that takes the centre (ox + 1/2, oy + 1/2) of an output pixel to continuous source coordinates, in
+ * which pixel i covers [i, i + 1): a = rint(65536 A), b, d, e alike, c = rint(65536 (C - 1/2)), f = rint(65536 (F - 1/2)).  The matrix
+ * [[1, 0, 0], [0, 1, 0]] (a = e = 65536, b = d = 0, c = f = -32768) returns the picture byte for byte, [[-1, 0, w], [0, 1, 0]] its mirror,
+ * [[0, 1, 0], [-1, 0, h]] to an h x w output its quarter turn, [[1, 0, 5], [0, 1, -3]] the picture moved with `fill` in the uncovered
+ * band: where the entries are multiples of 1/2 nothing is rounded. */
+typedef struct nhw_warp {     /* 40 bytes, 8-byte aligned */
+	int64_t  c, f;            /* offsets, 1/65536 source pixel; |c|, |f| <= 2^40 */
+	int32_t  a, b, d, e;      /* steps, 1/65536 source pixel an output pixel; each |.| <= 2^22 (NHW_WARP_MAX_STEP 64 pixels) */
+	uint8_t  fill[3];         /* B, G, R of the border colour */
+	uint8_t  flags;           /* bit 0: NHW_WARP_REPLICATE, taps outside take the nearest edge pixel instead of `fill`; other bits are not read */
+	uint32_t reserved;        /* 0 */
+} nhw_warp;
+#define NHW_WARP_REPLICATE 1
+#define NHW_WARP_MAX_STEP 64
+/* The warp alone, beside nhw_resample_to_tensor_device: picture k of the table d_pics[0 .. n) (addr, pitch, width and height are read; any
+ * alignment and pitch; bytes outside a row's 3 width are never read) goes, under the rule above with the warp d_warps[k] (a device table
+ * of n entries, 8-byte aligned as nhw_warp is: every device allocation is), to the [out_height][out_width][3] or [3][out_height][out_width]
+ * elements at d_out_addr[k].  Writes exactly those elements,
+ * element by element, or nothing for an entry that stores nothing.  No handle: the current device; stream NULL is the null stream.
+ * Asynchronous, and may be captured in a graph.  NHW_E_ARG, before anything is launched: the cases of nhw_resample_to_tensor_device (NULL
+ * d_pics or d_out_addr, n outside 1 .. 2^24, an output side outside 1 .. 4096, a refused format) and a NULL d_warps. */
+int nhw_warp_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                              const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream);
+/* nhw_dec_crops_to_device with the warp behind the windows in place of a resize, synchronous: rects are windows at `scale`, warps (host
+ * memory, one entry a rect, never NULL: a call-level NHW_E_ARG) are expressed in the coordinates of their rect's window -- window pixel
+ * (0, 0) is source pixel (0, 0) --, dst_addr[i] is the device address of warp i's tensor.  A rect whose warp is beyond the limits gets status
+ * NHW_E_ARG before it selects a tile: its destination is not written, and the other rects go on.  Everything else is the crop call's: the
+ * union of tiles, each uploaded and decoded once, the per-rect statuses, nhw_dec_last_region_stats and the call-level NHW_E_ARG cases. */
+int nhw_dec_warps_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
+                            int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

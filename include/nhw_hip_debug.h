@@ -82,6 +82,10 @@ int  nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size_t bytes);
 /* decoder: the colour matrix of write_image_bmp (nhw_decoder_cli.c:133-283) for quality q on n (Y, U, V) byte triples in device memory (n a
  * multiple of 8) -> n x 3 bytes in the order the reference writes them, through the functions k_dec_final runs: the exhaustive 2^24 test */
 int  nhw_dec_debug_colour(int quality, const void *d_yuv, void *d_rgb, int n);
+/* the warp kernel's choice of walk, for measurements and tests: every later nhw_warp_to_tensor_device and
+ * nhw_dec_warps_to_device of the process walks an entry by rows where |d| <= limit and by 8 x 8 blocks elsewhere (-1: blocks for every entry;
+ * 4194304: rows for every entry); a limit below -1 puts the rule's own 16384 back.  The bytes do not depend on the walk. */
+void nhw_debug_warp_row_limit(int limit);
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@ used only as plumbing: device buffers, streams, torch.distributed.  There is no 
 library is missing or no GPU is visible, construction fails.
 """
 import ctypes
+import math
 import numbers
 import os
 
@@ -119,6 +120,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_resample_to_tensor_device.argtypes = a[:4] + [ctypes.c_int] + a[4:]
     L.nhw_dec_crops_to_device_resample.argtypes = L.nhw_dec_crops_to_device_filter.argtypes
     L.nhw_enc_pictures_resized.argtypes = [P, P, P, P, P, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, P, ctypes.c_size_t, P, P]
+    L.nhw_warp_to_tensor_device.argtypes = L.nhw_resize_to_tensor_device.argtypes          # the table of warps where the flags are
+    L.nhw_dec_warps_to_device.argtypes = L.nhw_dec_crops_to_device.argtypes
+    L.nhw_debug_warp_row_limit.argtypes, L.nhw_debug_warp_row_limit.restype = [ctypes.c_int], None
     return L
 
 
@@ -531,6 +535,175 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     with torch.cuda.device(dev):
         rc = L.nhw_resample_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
                                              addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
+
+
+# ---------------------------------------------------------------- affine warps into tensors of one size
+WARP_DTYPE = [("c", "<i8"), ("f", "<i8"), ("a", "<i4"), ("b", "<i4"), ("d", "<i4"), ("e", "<i4"), ("fill", "u1", (3,)), ("flags", "u1"), ("reserved", "<u4")]   # nhw_warp
+WARP_MAX_STEP = 64                                 # NHW_WARP_MAX_STEP: a step of the grid is 64 source pixels an output pixel at the most
+WARP_BORDERS = {"fill": 0, "replicate": 1}         # bit 0 of nhw_warp.flags: NHW_WARP_REPLICATE
+_WARP_STEP, _WARP_OFFSET = WARP_MAX_STEP << 16, 1 << 40
+
+
+def _warp_matrix(matrix, what):
+    """`matrix` as a float64 array [2, 3] of finite numbers, or raises"""
+    import numpy as np
+    try:
+        m = np.asarray(matrix)
+        m = m.astype(np.float64) if m.dtype.kind in "iuf" else None
+    except (TypeError, ValueError):
+        m = None
+    if m is None or m.shape != (2, 3):
+        raise NhwError(f"{what}: a warp is a 2 x 3 matrix [[A, B, C], [D, E, F]] of numbers, got {matrix!r}")
+    if not np.isfinite(m).all():
+        raise NhwError(f"{what}: a warp's entries must be finite, got {m.tolist()!r}")
+    return m
+
+
+def _warp_within(six, what):
+    """the six integers (a, b, c, d, e, f) of a warp inside nhw_warp's limits, or raises"""
+    a, b, c, d, e, f = six
+    if any(abs(v) > _WARP_STEP for v in (a, b, d, e)) or any(abs(v) > _WARP_OFFSET for v in (c, f)):
+        raise NhwError(f"{what}: the warp {tuple(six)!r} is beyond the limits: steps of {WARP_MAX_STEP} source pixels an output pixel (2^22), offsets of 2^24 pixels (2^40)")
+    return tuple(int(v) for v in six)
+
+
+def warp_fixed(matrix):
+    """A warp in nhw_warp's fixed point.  matrix: 2 x 3 floats [[A, B, C], [D, E, F]] that map the centre (ox + 1/2, oy + 1/2) of output pixel
+    (ox, oy) to continuous source coordinates in which pixel i covers [i, i + 1): sx = A (ox + 1/2) + B (oy + 1/2) + C, sy alike -> the six
+    integers (a, b, c, d, e, f) of DESIGN.md section 21: a = rint(65536 A), b, d, e alike, c = rint(65536 (C - 1/2)), f = rint(65536 (F - 1/2)),
+    in float64, ties to even (the -1/2 moves to the grid on which pixel i has its centre at i).  Raises NhwError for an entry that is not
+    finite or beyond the limits: |a|, |b|, |d|, |e| <= 2^22 (WARP_MAX_STEP pixels), |c|, |f| <= 2^40."""
+    import numpy as np
+    m = _warp_matrix(matrix, "warp_fixed")
+    v = np.rint(np.array([m[0, 0], m[0, 1], m[0, 2] - 0.5, m[1, 0], m[1, 1], m[1, 2] - 0.5]) * 65536.0)
+    if not (np.isfinite(v).all() and (np.abs(v[[0, 1, 3, 4]]) <= _WARP_STEP).all() and (np.abs(v[[2, 5]]) <= _WARP_OFFSET).all()):
+        raise NhwError(f"warp_fixed: the warp {m.tolist()!r} is beyond the limits: steps of {WARP_MAX_STEP} source pixels an output pixel, offsets of 2^24 pixels")
+    return tuple(int(x) for x in v)
+
+
+def warp_scale(matrix) -> int:
+    """the scale to decode at for a warp in full-resolution coordinates: the largest s of 4, 2 with min(hypot(A, D), hypot(B, E)) >= s, else
+    1 -- the lengths of the steps along the two output axes, so that at that scale the two taps see a reduction below 2 along both (where
+    the steps are below 8 pixels; beyond that the filter aliases as section 18's does)"""
+    m = _warp_matrix(matrix, "warp_scale")
+    n = min(math.hypot(m[0, 0], m[1, 0]), math.hypot(m[0, 1], m[1, 1]))
+    return 4 if n >= 4 else 2 if n >= 2 else 1
+
+
+def _warp_index(six, ox, oy):
+    """(ix, iy) of output pixel (ox, oy) under section 21's rule, in Python's integers (>> floors)"""
+    a, b, c, d, e, f = six
+    sx, sy = ((a * (2 * ox + 1) + b * (2 * oy + 1)) >> 1) + c, ((d * (2 * ox + 1) + e * (2 * oy + 1)) >> 1) + f
+    return (sx + 128) >> 16, (sy + 128) >> 16
+
+
+def warp_window(matrix, size, pic_w: int, pic_h: int, scale: int) -> tuple:
+    """The window of a pic_w x pic_h picture at `scale` that a warp needs, and the warp in that window's coordinates.  matrix: as for
+    warp_fixed, in full-resolution coordinates; size = (out_h, out_w) -> ((x0, y0, w0, h0), fixed').  With m = warp_fixed(matrix / scale) the
+    rule's own ix, iy at the four corner output pixels are the extremes (the position is monotone along either output axis); the window is
+    min ix .. max ix + 1 by min iy .. max iy + 1, each bound clamped into the scaled picture (scaled_size), so it is never empty, holds every
+    tap that lies in the picture and the clamp of every tap that does not; fixed' is m with c - 65536 x0 and f - 65536 y0, an exact
+    translation, which never takes a warp out of the limits: x0 is above 0 only where some position is -- then c is above -2^36, the
+    reach of 4096 steps of 64 pixels --, and it is below 2^16, so c - 65536 x0 lies between -2^36 - 2^32 and c.  The warp of the window under fixed' is therefore, byte for byte, the warp of the whole scaled picture under m, with
+    either border."""
+    what = "warp_window"
+    scale = _scale(scale, what)
+    out_h, out_w = _crop_size(size, what)
+    sw, sh = scaled_size(pic_w, pic_h, scale)
+    m = warp_fixed(_warp_matrix(matrix, what) / scale)
+    at = [_warp_index(m, ox, oy) for ox in (0, out_w - 1) for oy in (0, out_h - 1)]
+    clamp = lambda v, n: min(max(v, 0), n - 1)
+    x0, x1 = clamp(min(p[0] for p in at), sw), clamp(max(p[0] for p in at) + 1, sw)
+    y0, y1 = clamp(min(p[1] for p in at), sh), clamp(max(p[1] for p in at) + 1, sh)
+    fixed = _warp_within((m[0], m[1], m[2] - 65536 * x0, m[3], m[4], m[5] - 65536 * y0), what)
+    return (x0, y0, x1 - x0 + 1, y1 - y0 + 1), fixed
+
+
+def crop_warp(x, y, w, h, size, angle=0.0, flip=False):
+    """RandomResizedCrop + RandomRotation as one warp: the 2 x 3 matrix (numpy float64, as warp_fixed takes it) that lays the out_w x out_h
+    output, size = (out_h, out_w), over the w x h rectangle at (x, y) of the source -- numbers, in the continuous coordinates of warp_fixed --,
+    turned by `angle` radians about the rectangle's centre and mirrored left-right with `flip`.  With u = ((ox + 1/2) / out_w - 1/2) w (its
+    sign changed by `flip`) and v = ((oy + 1/2) / out_h - 1/2) h, the source position is (x + w / 2 + u cos - v sin, y + h / 2 + u sin + v
+    cos): angle 0 is the crop resized with two taps, a positive angle turns the sampling grid from the +x axis towards the +y axis of the
+    source.  Coordinates and the sense of rotation are those of the STORED rows (row 0 is the first row of the byte picture): under
+    rows="reversed" on a bottom-up file, where the tensor shows the picture upright, a positive angle appears to turn the other way."""
+    import numpy as np
+    what = "crop_warp"
+    out_h, out_w = _crop_size(size, what)
+    try:
+        x, y, w, h, angle = (float(v) for v in (x, y, w, h, angle))
+    except (TypeError, ValueError):
+        raise NhwError(f"{what}: x, y, w, h and angle must be numbers") from None
+    if not all(math.isfinite(v) for v in (x, y, w, h, angle)) or w <= 0 or h <= 0:
+        raise NhwError(f"{what}: the rectangle {x!r}, {y!r}, {w!r} x {h!r} is empty or not finite, or the angle {angle!r} is not finite")
+    cs, sn = math.cos(angle), math.sin(angle)
+    ux, vy = (-w if flip else w) / out_w, h / out_h                      # u = ux (ox + 1/2) - (ux out_w) / 2, v = vy (oy + 1/2) - h / 2
+    u0, v0 = -ux * out_w / 2, -h / 2
+    return np.array([[cs * ux, -sn * vy, x + w / 2 + cs * u0 - sn * v0], [sn * ux, cs * vy, y + h / 2 + sn * u0 + cs * v0]], dtype=np.float64)
+
+
+def _warp_border(fill, border, what):
+    """the checked (fill bytes B, G, R; flag byte) of a warp call"""
+    if not isinstance(border, str) or border not in WARP_BORDERS:
+        raise NhwError(f"{what}: `border` must be one of {', '.join(repr(k) for k in WARP_BORDERS)}, got {border!r}")
+    if not (isinstance(fill, (tuple, list)) and len(fill) == 3 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and 0 <= v <= 255 for v in fill)):
+        raise NhwError(f"{what}: `fill` must be three bytes (B, G, R), got {fill!r}")
+    return tuple(int(v) for v in fill), WARP_BORDERS[border]
+
+
+def _warp_entry(matrix, what):
+    """one entry of `matrices`: the six integers (a, b, c, d, e, f) as they are -- a flat sequence of six integers, or an array of an integer
+    dtype, [6] or [2, 3] -- or a 2 x 3 matrix of floats, which goes through warp_fixed"""
+    import numpy as np
+    try:
+        m = np.asarray(matrix)
+    except Exception:
+        m = None
+    if m is not None and m.dtype.kind in "iu" and (m.shape == (6,) or (m.shape == (2, 3) and isinstance(matrix, np.ndarray))):
+        return _warp_within([int(v) for v in m.reshape(6)], what)
+    if m is None or m.shape != (2, 3) or m.dtype.kind not in "iuf":
+        raise NhwError(f"{what}: a warp is a 2 x 3 matrix of floats or the six integers (a, b, c, d, e, f), got {matrix!r}")
+    return warp_fixed(m)
+
+
+def _warp_table(fixed, fill, flags):
+    """the nhw_warp table of a list of six-integer warps, a numpy array of WARP_DTYPE"""
+    import numpy as np
+    t = np.zeros(len(fixed), WARP_DTYPE)
+    for i, (a, b, c, d, e, f) in enumerate(fixed):
+        t[i] = (c, f, a, b, d, e, fill, flags, 0)
+    return t
+
+
+def warp_to_tensor_device(pictures, matrices, size, fmt, fill=(0, 0, 0), border="fill"):
+    """Pictures sampled along tilted grids into one batch tensor of one size (k_warp_to_tensor, nhw_warp_to_tensor_device, DESIGN.md section
+    21): pictures as for resize_to_tensor_device, matrices one warp a picture -- a 2 x 3 matrix of floats as warp_fixed takes it, in the
+    picture's own coordinates, or the six integers (a, b, c, d, e, f) as warp_fixed returns them (a flat sequence of six integers, or an array
+    of an integer dtype) --, size = (out_h, out_w) -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Two taps a
+    direction at the position the warp gives, in integers; a tap outside the picture takes fill = (B, G, R), or with border="replicate" the
+    nearest edge pixel.  Reads only the pictures' own bytes.  Ordered on torch's current stream."""
+    import numpy as np
+    import torch
+    what = "warp_to_tensor_device"
+    fmt = _tensor_format(fmt, what)
+    out_h, out_w = _crop_size(size, what)
+    fill, flags = _warp_border(fill, border, what)
+    if not isinstance(pictures, (list, tuple)) or not isinstance(matrices, (list, tuple, np.ndarray)) or len(matrices) != len(pictures):
+        raise NhwError(f"{what}: `pictures` and `matrices` must be lists of the same length, one warp a picture")
+    warps = _warp_table([_warp_entry(m, f"{what}: matrix {i}") for i, m in enumerate(matrices)], fill, flags)
+    table, _, dev = _picture_table(pictures, what)
+    n = len(pictures)
+    out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
+    addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (3 * out_h * out_w * out.element_size())
+    addr = addr.to(dev)
+    d_warps = torch.from_numpy(warps.view(np.int64).copy()).to(dev)
+    L = _library()
+    c = fmt.c_struct()
+    with torch.cuda.device(dev):
+        rc = L.nhw_warp_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -1440,6 +1613,16 @@ class Decoder:
         if filter in _LIMITS:
             for i, r in enumerate(table):
                 _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
+        return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
+                                    lambda *args: self.lib.nhw_dec_crops_to_device_resample(*args, RESAMPLERS[filter])), scales
+
+    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call):
+        """the device side of decode_crops_device and decode_warps_device: the checked batch tensor (`out`, or a new one), and per scale one
+        call(handle, blob, offsets, n containers, the scale's rects, their count, scale, out_w, out_h, format, the scale's rows of `extra` --
+        the flag bytes or the nhw_warp table, or None --, the tensors' addresses, statuses) -> rc.  Raises on any status that is not NHW_OK"""
+        import numpy as np
+        t = self.torch
+        n = len(table)
         dev = t.device("cuda", self.device)
         shape = (n,) + fmt.shape(out_h, out_w)
         per = 3 * out_h * out_w
@@ -1454,13 +1637,51 @@ class Decoder:
         for s in sorted(set(scales)):
             idx = np.flatnonzero(np.array(scales) == s)
             sub, a, st = np.ascontiguousarray(table[idx]), np.ascontiguousarray(addr[idx]), np.empty(len(idx), np.int32)
-            f = np.ascontiguousarray(flags[idx]) if flags is not None else None
-            args = (self.h, blob.ctypes.data, offs.ctypes.data, len(containers), sub.ctypes.data, len(idx), s, out_w, out_h,
-                    ctypes.byref(c), f.ctypes.data if f is not None else None, a.ctypes.data, st.ctypes.data)
-            self._chk(self.lib.nhw_dec_crops_to_device_resample(*args, RESAMPLERS[filter]))
+            x = np.ascontiguousarray(extra[idx]) if extra is not None else None
+            self._chk(call(self.h, blob.ctypes.data, offs.ctypes.data, n_containers, sub.ctypes.data, len(idx), s, out_w, out_h,
+                           ctypes.byref(c), x.ctypes.data if x is not None else None, a.ctypes.data, st.ctypes.data))
             status[idx] = st
         self._region_raise(status)
-        return (out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)), scales
+        return out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)
+
+    def decode_warps_device(self, containers, which, matrices, size, fmt, fill=(0, 0, 0), border="fill", scale=None, out=None):
+        """RandomAffine's / RandomRotation's decode (nhw_dec_warps_to_device): warp i samples the picture of container
+        which[i] along the grid of matrices[i] -- a 2 x 3 matrix of floats as warp_fixed takes it, in FULL-resolution picture coordinates
+        (crop_warp makes one from a rectangle, an angle and a flip) -- into size = (out_h, out_w), and is stored under fmt -> (tensor [n, 3,
+        out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype on this decoder's device, the list of the scales used).  With scale=None warp i is
+        decoded at warp_scale(matrices[i]) and the warps of one scale go down together, three calls at the most; with a scale (1, 2 or 4),
+        one call at that scale.  Each warp's window is warp_window's -- only the tiles it touches are uploaded and decoded, each once a call
+        -- and the result is, byte for byte, the warp of the whole picture decoded at that scale under warp_fixed(matrix / scale).  A tap
+        outside the picture takes fill = (B, G, R), or with border="replicate" the nearest edge pixel.  out: as for decode_crops_device.
+        Raises on any status that is not NHW_OK.  The work is ordered after torch's current stream and complete on return; region_stats
+        speaks of the last of the calls."""
+        import numpy as np
+        what = "decode_warps_device"
+        fmt = _tensor_format(fmt, what)
+        out_h, out_w = _crop_size(size, what)
+        fill, flags = _warp_border(fill, border, what)
+        if scale is not None:
+            scale = _scale(scale, what)
+        if not isinstance(containers, (list, tuple)) or len(containers) < 1:
+            raise NhwError(f"{what} wants a non-empty list of containers")
+        if not isinstance(which, (list, tuple, np.ndarray)) or not isinstance(matrices, (list, tuple, np.ndarray)) or len(which) < 1 or len(which) != len(matrices):
+            raise NhwError(f"{what}: `which` and `matrices` must be non-empty and of the same length: one container index and one matrix a warp")
+        n = len(which)
+        for i, ci in enumerate(which):
+            if isinstance(ci, bool) or not isinstance(ci, numbers.Integral) or not 0 <= ci < len(containers):
+                raise NhwError(f"{what}: which[{i}] must be a container index of 0 .. {len(containers) - 1}, got {ci!r}")
+        mats = [_warp_matrix(m, f"{what}: matrix {i}") for i, m in enumerate(matrices)]
+        scales = [warp_scale(m) for m in mats] if scale is None else [scale] * n
+        sizes, rects, fixed = {}, [], []
+        for i, (ci, m, s) in enumerate(zip(which, mats, scales)):
+            if ci not in sizes:
+                sizes[ci] = picture_info(containers[ci])
+            win, fx = warp_window(m, (out_h, out_w), *sizes[ci], s)
+            rects.append((int(ci),) + win)
+            fixed.append(fx)
+        blob, offs, table = self._region_args(containers, rects, what)
+        return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
+                                    self.lib.nhw_dec_warps_to_device), scales
 
     def region_stats(self):
         """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region or window call (nhw_dec_last_region_stats);

@@ -219,8 +219,10 @@ static void source_look(RegionSource &c, const uint8_t *base, size_t len)   /* t
  * staging as for the host form and stay there; behind the last chunk one k_resize_to_tensor takes every window whose tiles all decoded to its
  * tensor -- the others get the address 0, which the kernel passes over.  With the area filter that launch is
  * k_area_to_tensor, with the cubic filter (section 20) k_cubic_to_tensor, and a rect whose window is beyond the filter's reduction limit for
- * the output size is NHW_E_ARG before it selects a tile. */
-struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter; };
+ * the output size is NHW_E_ARG before it selects a tile.  With `warps` set the launch is k_warp_to_tensor instead: warps[i]
+ * samples window i along its tilted grid, the table of warps goes up behind the addresses where the flags would, and a rect whose warp is
+ * beyond the limits is NHW_E_ARG before it selects a tile. */
+struct CropSpec { uint32_t out_w, out_h; int dtype, layout; NhwTensorArgs a; const uint8_t *flags; int filter; const nhw_warp *warps; };
 
 static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int nc, const nhw_rect *rects, int nr, int scale, uint8_t *bgr,
                        const uint64_t *out_off, const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status, const char *who, bool merge = true,
@@ -252,6 +254,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 		status[i] = NHW_E_ARG;
 		if (!r.width || !r.height || r.container >= (uint32_t)nc) continue;
 		if (limit && (r.width > limit * crop->out_w || r.height > limit * crop->out_h)) continue;
+		if (crop && crop->warps && !nhw_warp_within(crop->warps[i])) continue;
 		RegionSource &c = src[r.container];
 		const uint8_t *base = blob + off[r.container];
 		source_look(c, base, (size_t)(off[r.container + 1] - off[r.container]));
@@ -324,10 +327,17 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 			if (status[which[k]] == NHW_OK) oaddr[(size_t)which[k]] = dst_addr[which[k]];
 		}
 		const size_t pics_bytes = (size_t)nr * sizeof(nhw_picture), addr_bytes = (size_t)nr * 8;
-		HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + (size_t)nr));
+		HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + (size_t)nr * (crop->warps ? sizeof(nhw_warp) : 1)));
 		uint8_t *tab = d->crop_tab.as<uint8_t>();
 		HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 		HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
+		if (crop->warps) {                                            /* (32 + 8 bytes an entry in front: the warps are 8-byte aligned) */
+			HIPCHK(hipMemcpyAsync(tab + pics_bytes + addr_bytes, crop->warps, (size_t)nr * sizeof(nhw_warp), hipMemcpyHostToDevice, s));
+			HIPCHK(nhw_launch_warp((const nhw_picture *)tab, (const nhw_warp *)(tab + pics_bytes + addr_bytes), nr, crop->out_w, crop->out_h, crop->dtype, crop->layout,
+			                       crop->a, (const uint64_t *)(tab + pics_bytes), s));
+			HIPCHK(hipStreamSynchronize(s));
+			return NHW_OK;
+		}
 		if (crop->flags) HIPCHK(hipMemcpyAsync(tab + pics_bytes + addr_bytes, crop->flags, (size_t)nr, hipMemcpyHostToDevice, s));
 		HIPCHK(nhw_launch_resample(crop->filter, (const nhw_picture *)tab, nr, crop->out_w, crop->out_h, crop->dtype, crop->layout, crop->a,
 		                           crop->flags ? tab + pics_bytes + addr_bytes : nullptr, (const uint64_t *)(tab + pics_bytes), s));
@@ -380,7 +390,7 @@ static int dec_crops(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n
 	}
 	if (!args) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_crops_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	CropSpec c = { out_width, out_height, 0, 0, {}, flags, filter };
+	CropSpec c = { out_width, out_height, 0, 0, {}, flags, filter, nullptr };
 	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
 	c.dtype = fmt->dtype; c.layout = fmt->layout;
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_crops_to_device", true, &c);
@@ -405,6 +415,20 @@ extern "C" int nhw_dec_crops_to_device_resample(nhw_dec *d, const uint8_t *blob,
 {
 	static_assert(sizeof(int) == sizeof(int32_t), "the statuses are 32 bits wide");
 	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, flags, dst_addr, (int32_t *)status, filter, CROPS_ALL);
+}
+
+/* the windows sampled along tilted grids: the crop call with a warp a rect in place of filter and flags */
+extern "C" int nhw_dec_warps_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
+                                       int32_t *status)
+{
+	static_assert(sizeof(nhw_warp) == 40 && sizeof(nhw_picture) == 32, "the crop table's layout");
+	if (!warps || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_dec_err = "nhw_dec_warps_to_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	CropSpec c = { out_width, out_height, 0, 0, {}, nullptr, NHW_FILTER_TWO_TAP, warps };
+	if (const int rc = nhw_tensor_format_check(fmt, &c.a, nhw_dec_err)) return rc;
+	c.dtype = fmt->dtype; c.layout = fmt->layout;
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, nullptr, nullptr, dst_addr, nullptr, status, "nhw_dec_warps_to_device", true, &c);
 }
 
 extern "C" int nhw_dec_last_region_stats(nhw_dec *d, uint64_t *tiles_decoded, uint64_t *bytes_uploaded)

@@ -179,6 +179,18 @@ extern "C" int nhw_resample_to_tensor_device(const nhw_picture *d_pics, int n, u
 	return resize_entry(filter, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
 }
 
+/* ... or sampled along a tilted grid: the same table and checks, a device table of warps in place of the flags */
+extern "C" int nhw_warp_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                         const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_warps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = "nhw_warp_to_tensor_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	NhwTensorArgs a;
+	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
+	HIPCHK(nhw_launch_warp(d_pics, d_warps, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
 static int tensor_in_args(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
 {

@@ -1,6 +1,7 @@
 /*
  * nhw_resample.hip -- pictures resampled into tensors of one size (DESIGN.md sections 18 to 20): the two-tap kernel k_resize_to_tensor, the
- * area filter k_area_to_tensor and the cubic filter k_cubic_to_tensor, the axis helpers of each, and their one launcher nhw_launch_resample.
+ * area filter k_area_to_tensor and the cubic filter k_cubic_to_tensor, the axis helpers of each, and their one launcher nhw_launch_resample;
+ * and pictures sampled along a tilted grid (section 21): the affine warp k_warp_to_tensor and its launcher nhw_launch_warp, under the same band rule.
  *
  * The three kernels have one shape.  The table (nhw_picture entries, addr, pitch, width and height read), the flags and the tensors'
  * addresses live in device memory, so the host knows no picture's size: the grid is entries x bands of `rows` output rows, cut by the one
@@ -10,6 +11,7 @@
  * alignment and pitch and tensors any width: the loads are byte loads that never touch a byte outside a row's 3 W, the stores single elements.
  */
 #include "nhw_tensor.h"
+#include "../../include/nhw_hip_debug.h"
 
 namespace {
 
@@ -23,12 +25,12 @@ constexpr int RS_MAX = 4096, RS_ROWS = 64;      /* the largest output side; the 
  * nhw_launch_resample refuses before it launches -- an output side of 0 or above RS_MAX, a band of no rows or of more than RS_ROWS, a band
  * below the output -- so that no kernel depends on its launcher for the room of its tables. */
 template <int DT>
-__device__ __forceinline__ bool resample_entry(const nhw_picture *__restrict__ pics, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, uint32_t out_w,
-                                               uint32_t out_h, int bands, int rows, uint32_t limit, nhw_picture &p, typename NhwElem<DT>::type *&out, uint32_t &r0, uint32_t &nr,
-                                               bool &mirror)
+__device__ __forceinline__ bool resample_entry_at(const nhw_picture *__restrict__ pics, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, uint32_t out_w,
+                                                  uint32_t out_h, int bands, int rows, uint32_t limit, nhw_picture &p, typename NhwElem<DT>::type *&out, uint32_t &r0, uint32_t &nr,
+                                                  bool &mirror, int &k)
 {
 	using E = typename NhwElem<DT>::type;
-	const int k = blockIdx.x / bands;
+	k = blockIdx.x / bands;
 	const uint32_t first = (uint32_t)(blockIdx.x % bands) * (uint32_t)rows;
 	const nhw_picture q = pics[k];
 	const uint64_t oa = out_addr[k];
@@ -41,6 +43,15 @@ __device__ __forceinline__ bool resample_entry(const nhw_picture *__restrict__ p
 	mirror = flags && (flags[k] & 1);
 	out = reinterpret_cast<E *>(oa);
 	return true;
+}
+/* ... as the three resamplers call it; resample_entry_at hands the entry's index back as well, for a kernel with a table of its own (the warp) */
+template <int DT>
+__device__ __forceinline__ bool resample_entry(const nhw_picture *__restrict__ pics, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, uint32_t out_w,
+                                               uint32_t out_h, int bands, int rows, uint32_t limit, nhw_picture &p, typename NhwElem<DT>::type *&out, uint32_t &r0, uint32_t &nr,
+                                               bool &mirror)
+{
+	int k;
+	return resample_entry_at<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, limit, p, out, r0, nr, mirror, k);
 }
 
 /* ---- the two taps ----
@@ -337,24 +348,133 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
 	}
 }
 
+/* ---- the affine warp: two taps a direction along a tilted grid ----
+ * k_resize_to_tensor with the positions of an nhw_warp in place of an axis' table: the same picture table, formats, grid and band, no flags (a
+ * mirror is a matrix), no LDS and no division beyond resample_entry's own.  The entry's limits are checked here (nhw_warp_within), so that every width below holds
+ * whatever the table says: a (2 ox + 1) + b (2 oy + 1) is below 2^36, SX and SY below 2^41, X8 below 2^33 and ix, iy below 2^25 in magnitude.
+ * warp_pixel makes one output pixel: the four taps are loaded from the indices clamped to the picture -- inside it for every position, since
+ * resample_entry has seen the sides -- and a tap judged outside then gives way to the border colour unless the entry replicates: twelve byte
+ * loads, the blend of section 18; the caller stores the pixel.  The row's part of the position (bx, ey) is the caller's; a pixel adds its
+ * own with one 32 x 32 -> 64-bit multiply an axis.  iy x pitch is 64 bits wide.
+ * Two walks over the band, chosen by the entry (uniformly for the workgroup).  Where the grid's rows are nearly the source's -- d, the source
+ * rows a step along an output row crosses, is at most WARP_ROW_LANES / 65536 = 1/4: a wavefront's 64 columns stay within 16 source rows -- the
+ * walk is k_resize_to_tensor's, 1 << lg lanes an output row: stores of consecutive lanes are consecutive elements, and the loads follow the
+ * source's rows.  Elsewhere a wavefront takes an 8 x 8 block of output pixels at a time, which keeps its taps within a compact patch of the
+ * source at any angle and cuts its stores into runs of 8 elements.  Measured (section 21), 4096 entries of 256 x 256 -> 224 x 224: rows 1.7,
+ * 4.4 and 7.6 ms at 0, 30 and 90 degrees, blocks 2.6, 2.9 and 2.8 ms; the two meet at 15 degrees, d = 19 385, and the limit is the power of two below. */
+constexpr int32_t WARP_ROW_LANES = 16384;
+int32_t warp_row_limit = WARP_ROW_LANES;          /* host: what the launches pass as row_limit; nhw_debug_warp_row_limit (include/nhw_hip_debug.h) moves it */
+__device__ __forceinline__ void warp_pixel(const nhw_warp &m, const nhw_picture &p, bool fill, int64_t bx, int64_t ey, uint32_t c, uint32_t *b)
+{
+	const int32_t xl = (int32_t)p.width - 1, yl = (int32_t)p.height - 1;     /* 0 .. 65534 */
+	const uint8_t *src = reinterpret_cast<const uint8_t *>(p.addr);
+	const int32_t tx = (int32_t)(2 * c + 1);
+	const int64_t X8 = ((((int64_t)m.a * tx + bx) >> 1) + m.c + 128) >> 8, Y8 = ((((int64_t)m.d * tx + ey) >> 1) + m.f + 128) >> 8;
+	const int32_t ix = (int32_t)(X8 >> 8), iy = (int32_t)(Y8 >> 8);
+	const uint32_t fx = (uint32_t)X8 & 255u, fy = (uint32_t)Y8 & 255u;
+	const int32_t x0 = ix < 0 ? 0 : ix > xl ? xl : ix, x1 = ix + 1 < 0 ? 0 : ix + 1 > xl ? xl : ix + 1;
+	const int32_t y0 = iy < 0 ? 0 : iy > yl ? yl : iy, y1 = iy + 1 < 0 ? 0 : iy + 1 > yl ? yl : iy + 1;
+	const bool ox0 = fill && x0 != ix, ox1 = fill && x1 != ix + 1, oy0 = fill && y0 != iy, oy1 = fill && y1 != iy + 1;
+	const uint8_t *s0 = src + (uint64_t)(uint32_t)y0 * p.pitch, *s1 = src + (uint64_t)(uint32_t)y1 * p.pitch;
+	const uint32_t w00 = (256 - fx) * (256 - fy), w01 = fx * (256 - fy), w10 = (256 - fx) * fy, w11 = fx * fy;
+#pragma unroll
+	for (int ch = 0; ch < 3; ch++) {
+		uint32_t t00 = s0[3 * x0 + ch], t01 = s0[3 * x1 + ch], t10 = s1[3 * x0 + ch], t11 = s1[3 * x1 + ch];
+		if (oy0 || ox0) t00 = m.fill[ch];
+		if (oy0 || ox1) t01 = m.fill[ch];
+		if (oy1 || ox0) t10 = m.fill[ch];
+		if (oy1 || ox1) t11 = m.fill[ch];
+		b[ch] = (w00 * t00 + w01 * t01 + w10 * t10 + w11 * t11 + 32768u) >> 16;
+	}
+}
+
+template <int DT, int CHW>
+__global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture *__restrict__ pics, const nhw_warp *__restrict__ warps, uint32_t out_w, uint32_t out_h,
+                                                                int bands, int rows, int lg, int32_t row_limit, NhwTensorArgs a, const uint64_t *__restrict__ out_addr)
+{
+	nhw_picture p;
+	typename NhwElem<DT>::type *out;
+	uint32_t r0, nr;
+	bool mirror;                                                             /* (never set: there is no flag table) */
+	int k;
+	if (!resample_entry_at<DT>(pics, nullptr, out_addr, out_w, out_h, bands, rows, 0, p, out, r0, nr, mirror, k)) return;
+	const nhw_warp m = warps[k];
+	if (!nhw_warp_within(m)) return;
+	const bool fill = !(m.flags & NHW_WARP_REPLICATE);
+	const size_t W = out_w, H = out_h;
+	if ((m.d < 0 ? -m.d : m.d) > row_limit) {                                /* a wavefront an 8 x 8 block of output pixels (|d| <= 2^22: checked) */
+		const uint32_t tiles_x = (out_w + 7) >> 3, tiles_y = (nr + 7) >> 3, lane = threadIdx.x & 63u;
+		uint32_t tc = threadIdx.x >> 6, tr = 0;
+		for (;;) {
+			while (tc >= tiles_x) { tc -= tiles_x; tr++; }
+			if (tr >= tiles_y) break;
+			const uint32_t r = 8 * tr + (lane >> 3), c = 8 * tc + (lane & 7u);
+			if (r < nr && c < out_w) {
+				const int32_t ty = (int32_t)(2 * (r0 + r) + 1);
+				uint32_t b[3];
+				warp_pixel(m, p, fill, (int64_t)m.b * ty, (int64_t)m.e * ty, c, b);
+				nhw_store_pixel<DT, CHW>(out, H, W, a.flip ? H - 1 - (r0 + r) : r0 + r, c, b, a);
+			}
+			tc += RS_THREADS >> 6;
+		}
+		return;
+	}
+	for (uint32_t r = threadIdx.x >> lg; r < nr; r += RS_THREADS >> lg) {
+		const int32_t ty = (int32_t)(2 * (r0 + r) + 1);
+		const int64_t bx = (int64_t)m.b * ty, ey = (int64_t)m.e * ty;
+		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
+		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
+			uint32_t b[3];
+			warp_pixel(m, p, fill, bx, ey, c, b);
+			nhw_store_pixel<DT, CHW>(out, H, W, rr, c, b, a);
+		}
+	}
+}
+
 } /* namespace */
 
 /* The band rule: some 8192 workgroups in all where the entries are few, one band an entry where they are many; a band has at most RS_ROWS rows
- * and, where the output is narrow, at least the rows of one pass (256 >> lg), so that a pass has work for every lane.  All three kernels meet
- * the same launch shapes.  The area kernel's LDS is sized here: the tap runs of the columns and of a band's rows, 8 (out_w + rows) bytes,
- * 33 280 at the most; the other two have static LDS, and the cubic kernel cuts its band itself (it takes no lg). */
+ * and, where the output is narrow, at least the rows of one pass (256 >> lg), so that a pass has work for every lane.  All four kernels meet
+ * the same launch shapes, those of resample_bands: false for what no kernel is launched for.  The area kernel's LDS is sized by its launch: the
+ * tap runs of the columns and of a band's rows, 8 (out_w + rows) bytes, 33 280 at the most; the cubic and the two-tap kernel have static LDS,
+ * the warp has none, and the cubic kernel cuts its band itself (it takes no lg). */
+static bool resample_bands(int n, uint32_t out_w, uint32_t out_h, int &lg, uint32_t &rows, int &bands)
+{
+	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return false;
+	lg = 0;
+	while (lg < 8 && (1u << lg) < out_w) lg++;
+	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
+	rows = (out_h + want - 1) / want;
+	if (rows < (uint32_t)(RS_THREADS >> lg)) rows = RS_THREADS >> lg;
+	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
+	bands = (int)((out_h + rows - 1) / rows);                           /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
+	return true;
+}
+
+hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                           const uint64_t *d_out_addr, hipStream_t s)
+{
+	int lg, bands;
+	uint32_t rows;
+	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
+	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
+		k_warp_to_tensor<DT, CHW><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr);
+	});
+	return hipGetLastError();
+}
+
+/* the developer's hook for measurements and tests: every later launch of the process walks by rows where |d| <= limit (-1: blocks for every
+ * entry; 2^22: rows for every entry); a limit below -1 puts the rule's own back.  The results are the same bytes whatever the walk. */
+extern "C" void nhw_debug_warp_row_limit(int limit) { warp_row_limit = limit < -1 ? WARP_ROW_LANES : limit; }
+
 hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
                                const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
 {
 	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) return hipErrorInvalidValue;
-	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return hipErrorInvalidValue;
-	int lg = 0;
-	while (lg < 8 && (1u << lg) < out_w) lg++;
-	const uint32_t want = (8192u + (uint32_t)n - 1) / (uint32_t)n < out_h ? (8192u + (uint32_t)n - 1) / (uint32_t)n : out_h;   /* bands wanted: 1 .. out_h */
-	uint32_t rows = (out_h + want - 1) / want;
-	if (rows < (uint32_t)(RS_THREADS >> lg)) rows = RS_THREADS >> lg;
-	if (rows > (uint32_t)RS_ROWS) rows = RS_ROWS;
-	const int bands = (int)((out_h + rows - 1) / rows);                 /* 1 .. 4096; with n above 8192, 64 at the most: n * bands is below 2^31 */
+	int lg, bands;
+	uint32_t rows;
+	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
 	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
 		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
 		switch (filter) {

@@ -257,6 +257,17 @@ hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int
 inline uint32_t nhw_filter_limit(int filter) { return filter == NHW_FILTER_CUBIC ? NHW_CUBIC_MAX_REDUCTION : filter == NHW_FILTER_AREA ? NHW_AREA_MAX_REDUCTION : 0; }
 hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
                                const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
+/* nhw_resample.hip as well: every picture sampled along the tilted grid of its nhw_warp, under the band rule of
+ * nhw_launch_resample.  An entry whose warp is not nhw_warp_within stores nothing: the kernel checks it, and the host paths that know a
+ * warp refuse it with the same words before they launch. */
+__host__ __device__ inline bool nhw_warp_within(const nhw_warp &m)
+{
+	constexpr int32_t S = NHW_WARP_MAX_STEP << 16;
+	constexpr int64_t O = 1ll << 40;
+	return m.a >= -S && m.a <= S && m.b >= -S && m.b <= S && m.d >= -S && m.d <= S && m.e >= -S && m.e <= S && m.c >= -O && m.c <= O && m.f >= -O && m.f <= O;
+}
+hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                           const uint64_t *d_out_addr, hipStream_t s);
 /* nhw_picture.hip again, the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
