@@ -154,10 +154,9 @@ static int resize_entry(int filter, const nhw_picture *d_pics, int n, uint32_t o
 	static const char *const entry[] = { "nhw_resize_to_tensor_device", "nhw_area_to_tensor_device", "nhw_resample_to_tensor_device" };
 	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
 	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = std::string(entry[filter]) + ": an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	NhwTensorArgs a;
-	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
-	HIPCHK(nhw_launch_resample(filter, d_pics, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_flags, d_out_addr, (hipStream_t)stream));
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check(entry[filter], out_width, out_height, fmt, &o, nhw_enc_err)) return rc;
+	HIPCHK(nhw_launch_resample(filter, d_pics, n, o.w, o.h, o.dtype, o.layout, o.a, d_flags, d_out_addr, (hipStream_t)stream));
 	return NHW_OK;
 }
 
@@ -184,10 +183,9 @@ extern "C" int nhw_warp_to_tensor_device(const nhw_picture *d_pics, int n, uint3
                                          const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream)
 {
 	if (!d_pics || !d_warps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { nhw_enc_err = "nhw_warp_to_tensor_device: an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	NhwTensorArgs a;
-	if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_enc_err)) return rc;
-	HIPCHK(nhw_launch_warp(d_pics, d_warps, n, out_width, out_height, fmt->dtype, fmt->layout, a, d_out_addr, (hipStream_t)stream));
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_warp_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err)) return rc;
+	HIPCHK(nhw_launch_warp(d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_out_addr, (hipStream_t)stream));
 	return NHW_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/nhw_hip.h"
+#include "nhw_container.h"                  /* the .nhwp container's parser and writer (nhw_container_parse, nhw_container_head) and the tile geometry: inline, HIP-free */
 
 struct NhwWs;                               /* nhw_ws.h: the encoder's workspace view; ws.plane<T>(B_x) makes the Plane of one of its buffers */
 
@@ -118,8 +119,6 @@ hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_p
 hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, hipStream_t s);
 hipError_t nhw_launch_untile_window(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses /* the launch's own range of the use table */, int n_uses, int tile0, int m, int scale, hipStream_t s);
 hipError_t nhw_launch_sse_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, hipStream_t s);
-size_t nhw_container_head(uint8_t *dst, uint32_t width, uint32_t height, const uint32_t *lens, int t);
-int nhw_container_parse(const uint8_t *c, size_t len, uint32_t *width, uint32_t *height, int *tiles, const uint8_t **dir);
 /* nhw_dec.hip: what a caller needs to know about a decoder handle before it hands it work (the distortion searches) */
 void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after);
 

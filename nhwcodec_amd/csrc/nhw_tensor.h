@@ -41,6 +41,16 @@ inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a,
 	a->rgb = f->channels == NHW_T_RGB; a->flip = f->rows == NHW_T_ROWS_REVERSED;
 	return NHW_OK;
 }
+/* the tensors of one size that a resampling or warping call makes, as its launcher takes them */
+struct NhwTensorOut { uint32_t w, h; int dtype, layout; NhwTensorArgs a; };
+/* ... and what every such entry checks of them, in this order: the sides, 1 .. 4096 each (the message names the entry), then the format */
+inline int nhw_tensor_out_check(const char *who, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *f, NhwTensorOut *o, std::string &err)
+{
+	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { err = std::string(who) + ": an output side outside 1 .. 4096"; return NHW_E_ARG; }
+	if (const int rc = nhw_tensor_format_check(f, &o->a, err)) return rc;
+	o->w = out_width; o->h = out_height; o->dtype = f->dtype; o->layout = f->layout;
+	return NHW_OK;
+}
 inline bool nhw_tensor_format_is_bytes(const nhw_tensor_format *f)    /* what the byte entry points write */
 {
 	return f->dtype == NHW_T_U8 && f->layout == NHW_T_HWC && f->channels == NHW_T_BGR && f->rows == NHW_T_ROWS_FILE;

@@ -537,9 +537,8 @@ def cases():
 
 
 # ---------------------------------------------------------------------------------------------- classification
-def build_asan():
-    """the sanitizer build of the oracle's decoder; None where this machine's compiler cannot link a sanitized program at all (a one-line
-    program says so); any other failure of the build is an error"""
+def can_sanitize():
+    """whether this machine's compiler can link and run a sanitized program at all: a one-line program says so"""
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         src = os.path.join(tmp, "probe.c")
@@ -550,7 +549,12 @@ def build_asan():
             can = probe.returncode == 0 and subprocess.run([os.path.join(tmp, "probe")], capture_output=True).returncode == 0
         except OSError:
             can = False
-    if not can:
+    return can
+
+
+def build_asan():
+    """the sanitizer build of the oracle's decoder; None where can_sanitize() says no; any other failure of the build is an error"""
+    if not can_sanitize():
         return None
     p = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "asan"], capture_output=True, text=True)
     if p.returncode != 0 or not os.path.exists(ASAN_EXE):
