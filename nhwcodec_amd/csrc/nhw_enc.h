@@ -24,8 +24,8 @@ enum { EV_START, EV_FRONT, EV_LUMA, EV_CHROMA, EV_END, EV_COLOR, EV_PREFILTER, E
  * (NHW_PARTS > 1) the forks are off and slot k < 4 is sub-batch k's end instead. */
 enum { PE_LUMA_LIST, PE_CHROMA, PE_LISTS_FORK, PE_LISTS, PE_FRONT, PE_COUNT };
 /* ll_ev[]: the LL2 coder's fork beside the second dequantiser simulation, and its end; Y5's fork onto the same stream beside the first
- * simulation, and its end */
-enum { LL_EV_FORK, LL_EV_DONE, LL_EV_Y5_FORK, LL_EV_Y5_DONE, LL_EV_COUNT };
+ * simulation, and its end; the chroma packetiser's fork onto it beside Z1 (NHW_PACK_FORK=2), and its end */
+enum { LL_EV_FORK, LL_EV_DONE, LL_EV_Y5_FORK, LL_EV_Y5_DONE, LL_EV_PACK_FORK, LL_EV_PACK_DONE, LL_EV_COUNT };
 
 struct nhw_enc {
 	int device, max_batch;
@@ -45,6 +45,7 @@ struct nhw_enc {
 	int y5_fork;                  /* Y5 on ll_stream beside the first dequantiser simulation (NHW_Y5_FORK=0: in front of it on the luma stream) */
 	int ll2_once;                 /* q > 12: the LL2 bump walk in the emission only (NHW_LL2_ONCE=0: again in the second simulation) */
 	int quant_marks;              /* q > 16: the second simulation hands its marks to the quantiser, which skips its loops 2 and 3 (NHW_QUANT_MARKS=0: the quantiser runs them itself) */
+	int pack_fork;                /* forked order: Z2's chroma part (k_pack_chroma) on ll_stream beside Z1 (2, the default), on the chroma stream behind Z1 (1); NHW_PACK_FORK=0: directly in front of k_final, as in every other order */
 	int parts;
 	hipEvent_t ev[EV_COUNT];
 	bool timed;

@@ -23,7 +23,8 @@ static const size_t k_buf_bytes[B_COUNT] = {
 	/* NZQ (32 x 128 words of 64 bits + 33 flush bases) */ Q / 2 + 256, /* NZS */ Q / 2, /* VOFF */ Q / 4, /* VALS (every symbol non-zero: 4 Q) */ 4 * Q,
 	/* CNZQ (16 flushes x 64 lanes x 2 words of 64 bits + 17 flush bases) */ Q / 4 + 256, /* CVALS */ 2 * Q,
 	/* CJPEG_V */ 2 * Q, /* CPROC_V */ 2 * Q, /* CLL1_V */ Q / 2, /* CL2SAVE_V */ Q / 2, /* UBYTES */ Q,
-	/* LOWTAB (quality 1..16: pass A's five candidate masks, 64 bytes each, for every row) */ 320 * 512
+	/* LOWTAB (quality 1..16: pass A's five candidate masks, 64 bytes each, for every row) */ 320 * 512,
+	/* CPACK */ sizeof(NhwChromaPack), /* CPACKET (80000 words, like PACKET) */ 320000
 };
 
 static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -63,7 +64,7 @@ extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_
 		size_t free_b = 0, total_b = 0;
 		HIPCHK(hipMemGetInfo(&free_b, &total_b));
 		const size_t need = total + (host_staging ? HOST_PATH_BYTES * (size_t)max_batch : 0);
-		if (need > free_b) {                                       /* 7.0 MB of workspace (+ 1.8 MB of host-path staging) per image: say so instead of failing inside hipMalloc */
+		if (need > free_b) {                                       /* 7.4 MB of workspace (+ 1.8 MB of host-path staging) per image: say so instead of failing inside hipMalloc */
 			char b[200];
 			snprintf(b, sizeof b, "encoder workspace for max_batch %d needs %zu MiB (%.1f MiB per image), %zu MiB of HBM are free", max_batch, need >> 20, (double)need / max_batch / 1048576.0, free_b >> 20);
 			nhw_enc_err = b;
@@ -102,6 +103,7 @@ extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_
 	e->y5_fork = env("NHW_Y5_FORK", 1) != 0;
 	e->ll2_once = env("NHW_LL2_ONCE", 1) != 0;
 	e->quant_marks = env("NHW_QUANT_MARKS", 1) != 0;
+	e->pack_fork = within(env("NHW_PACK_FORK", 2), 0, 2, 2);
 	*out = e;
 	return NHW_OK;
 }
@@ -351,11 +353,25 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		nhw_launch_phase(PH_L4B, ws, 0, s);  /* Y24, Y25 (:1498) */
 	nhw_launch_phase(PH_L4C, ws, 0, s);      /* Y26, Y27 */
 	const bool early_join = fork && e->quant_join;
+	const int pack_fork = fork ? e->pack_fork : 0;                   /* every other order: directly in front of k_final (nhw_launch_final) */
 	auto chroma_rest = [&]() -> int {
 		HIPCHK(hipStreamWaitEvent(cs, e->part_ev[PE_LUMA_LIST], 0));
 		CHROMA(chroma_tail(0));
 		CHROMA(chroma_tail(1));
+		/* Z2's chroma part needs V's quantiser and nothing else, and writes only memory of its own (k_pack_chroma): it runs here, while the luma
+		 * stream ends its residual passes, instead of inside the packetiser at the very end, where nothing can run beside it.  Beside Z1 on
+		 * the LL coder's stream, idle since Y16 (NHW_PACK_FORK=2, the default: the join moves back by 0.24 ms, k_final loses 0.35), or behind
+		 * Z1 on this stream (NHW_PACK_FORK=1: the join moves back by the kernel's whole 0.32 ms, as much as k_final loses); either way it is
+		 * through before the join.  NHW_PACK_FORK=0: in front of k_final, as in every other order. */
+		if (pack_fork == 2) {
+			HIPCHK(hipEventRecord(e->ll_ev[LL_EV_PACK_FORK], cs));
+			HIPCHK(hipStreamWaitEvent(e->ll_stream, e->ll_ev[LL_EV_PACK_FORK], 0));
+			nhw_launch_pack_chroma(ws, e->ll_stream);
+			HIPCHK(hipEventRecord(e->ll_ev[LL_EV_PACK_DONE], e->ll_stream));
+		}
 		nhw_launch_phase(PH_LLC, ws, 0, cs);   /* Z1: the chroma LL2 coder appends to the luma one's output (Y16, long done) */
+		if (pack_fork == 1) nhw_launch_pack_chroma(ws, cs);
+		if (pack_fork == 2) HIPCHK(hipStreamWaitEvent(cs, e->ll_ev[LL_EV_PACK_DONE], 0));
 		HIPCHK(hipEventRecord(e->part_ev[PE_CHROMA], cs));
 		return 1;
 	};
@@ -385,7 +401,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 #undef CHROMA
 	if (timed) HIPCHK(hipEventRecord(e->ev[EV_CHROMA], s));
 	if (!fork) nhw_launch_phase(PH_LLC, ws, 0, s);     /* Z1 */
-	nhw_launch_final(ws, (uint8_t *)d_out, d_sizes, d_status, s);   /* Z2, container */
+	nhw_launch_final(ws, (uint8_t *)d_out, d_sizes, d_status, s, pack_fork != 0);   /* Z2, container */
 	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_END], s));
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
@@ -739,12 +755,13 @@ extern "C" int nhw_stage_residuals(nhw_enc *e, int n, int form, void *stream)
 
 /* A test hook for the stream stage -- the Y31 symbol rewrites and the RLE + VLC packetiser, a pure function of the symbol stream -- for the first n
  * images of the handle's last whole batch at that batch's quality, on the workspace as it stands (a test writes the lists: nhw_debug_write).
- *   form 0: k_y31, then k_final: from the lists as the quantisers leave them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS);
- *   form 1: k_final alone, on B_NZS / B_VOFF / B_VALS as they stand (and the chroma lists, which it puts into stream order itself);
- *   form 2: k_y31 alone: B_NZS / B_VOFF / B_VALS behind it are Y31's (k_final puts the chroma part's map into B_NZS / B_VOFF); nothing is
- *           reported.
- * k_final writes the files into the handle's own output arena; what a test compares lies in the workspace behind the call (B_PACKET, B_BOOK1/2,
- * B_SEL1/2, B_META).  status, sizes (may be null): n entries each of the caller's, host memory -- what k_final reports for every image; the call
+ *   form 0: k_y31, k_pack_chroma, k_final: from the lists as the quantisers leave them (B_NZQ with its fbase table, B_VALS; B_CNZQ with cfbase, B_CVALS);
+ *   form 1: k_pack_chroma, k_final, on B_NZS / B_VOFF / B_VALS as they stand (and the chroma lists: k_pack_chroma puts them into stream order
+ *           itself, in B_CPACK);
+ *   form 2: k_y31 alone: B_NZS / B_VOFF / B_VALS behind it are Y31's; nothing is reported.
+ * The chroma packetiser runs on the same stream directly in front of k_final, as in every order of run_batch but the forked one.
+ * k_final writes the files into the handle's own output arena; what a test compares lies in the workspace behind the call (B_PACKET -- both
+ * parts' words, the chroma part's copied behind the luma part's --, B_BOOK1/2, B_SEL1/2, B_META).  status, sizes (may be null): n entries each of the caller's, host memory -- what k_final reports for every image; the call
  * returns when they are there. */
 extern "C" int nhw_stage_stream(nhw_enc *e, int n, int form, int32_t *status, uint32_t *sizes, void *stream)
 {

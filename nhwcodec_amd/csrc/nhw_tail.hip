@@ -38,17 +38,43 @@ __global__ __launch_bounds__(256) void k_phase(NhwWs ws, int comp)
 	else if (PH == PH_C5) chroma_p5_par(&c, comp, tid, dyn_lds, sh_counts, ws.dbg != 0);
 }
 
-/* Z2 + the container as a kernel of its own: exactly four wavefronts a SIMD.  Its two parts are two inlined copies of the same walks since the
- * chroma part became a list too, and left alone the register allocator took 158 registers for them (three wavefronts a SIMD: +0.35 ms); held
- * to 128 it spills 21 dwords in the code-book construction, off the walks. */
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_final(NhwWs ws, uint8_t *out, uint32_t *sizes, int32_t *status)
+/* Z2 + the container as two kernels, each with one copy of the walks (pack_words_par).
+ * k_pack_chroma packs the chroma part's words and ranks its book: its inputs are complete behind V's quantiser, before the luma part's,
+ * and everything it writes is its own (B_CPACK, B_CPACKET), so the forked order runs it beside Z1 in front of the join (nhw_enc.hip,
+ * run_batch); every other order launches it directly in front of k_final.  k_final packs the luma part, makes both books (book 2 reads on
+ * into book 1's bytes: the one thing the chroma part needs of the luma part), puts the chroma part's words behind the luma part's and
+ * writes the container.
+ * Registers (gfx950 code objects).  While one kernel held both parts as two inlined copies of the walks the register allocator took 158
+ * (three wavefronts a SIMD: +0.35 ms); held to 128 (four) it spilled 20 dwords, 84 bytes of scratch a lane.  With one copy k_final takes
+ * 107 and k_pack_chroma 93 without scratch, and both fit the bound their LDS (22.9 KB a workgroup) allows: six workgroups a CU, 80
+ * registers -- the 16 images a CU gets of a 4096-image batch in three rounds instead of four.  At 80 k_final spills 77 dwords (104 bytes
+ * of scratch) and k_pack_chroma 23 (48 bytes), all in the code-book construction, off the walks.  Alone on the chip, 4096 images, q20:
+ * k_final 1.222 ms at four wavefronts a SIMD, 1.228 at five (96 registers, 21 spilled), 1.171 at six; k_pack_chroma 0.321 / 0.300 / 0.312. */
+#ifndef NHW_FINAL_WAVES
+#define NHW_FINAL_WAVES 6
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NHW_FINAL_WAVES, NHW_FINAL_WAVES))) void k_final(NhwWs ws, uint8_t *out, uint32_t *sizes, int32_t *status)
 {
 	extern __shared__ __attribute__((aligned(16))) int16_t dyn_lds[];
 	__shared__ PackShared sh_pack;
 	const int img = blockIdx.x, tid = threadIdx.x;
 	Ctx c;
 	ctx_load(&c, ws, img);
-	final_phase_par(&c, out + (size_t)img * (512u << 10), 512u << 10, &sizes[img], &status[img], &sh_pack, tid, reinterpret_cast<uint32_t *>(dyn_lds));
+	final_phase_par(&c, ws.buf<NhwChromaPack>(B_CPACK, img), ws.buf<uint32_t>(B_CPACKET, img), out + (size_t)img * (512u << 10), 512u << 10, &sizes[img], &status[img], &sh_pack, tid,
+	                reinterpret_cast<uint32_t *>(dyn_lds));
+}
+
+#ifndef NHW_PACKC_WAVES
+#define NHW_PACKC_WAVES 6
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NHW_PACKC_WAVES, NHW_PACKC_WAVES))) void k_pack_chroma(NhwWs ws)
+{
+	extern __shared__ __attribute__((aligned(16))) int16_t dyn_lds[];
+	__shared__ PackShared sh_pack;
+	const int img = blockIdx.x;
+	Ctx c;
+	ctx_load(&c, ws, img);
+	pack_chroma_par(&c, ws.buf<NhwChromaPack>(B_CPACK, img), ws.buf<uint32_t>(B_CPACKET, img), &sh_pack, threadIdx.x, reinterpret_cast<uint32_t *>(dyn_lds));
 }
 
 /* Y31 on the symbol list as a kernel of 512 threads (production; the stage checks run k_phase<L4D>, which has the dense form behind it) */
@@ -500,8 +526,13 @@ void nhw_launch_phase(int ph, const NhwWs &ws, int comp, hipStream_t s)
 	}
 #undef PHASE
 }
-void nhw_launch_final(const NhwWs &ws, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s)
+void nhw_launch_pack_chroma(const NhwWs &ws, hipStream_t s)
 {
+	k_pack_chroma<<<ws.n, 256, PK_LDS_BYTES, s>>>(ws);
+}
+void nhw_launch_final(const NhwWs &ws, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s, bool chroma_packed)
+{
+	if (!chroma_packed) nhw_launch_pack_chroma(ws, s);
 	k_final<<<ws.n, 256, PK_LDS_BYTES, s>>>(ws, out, sizes, status);
 }
 

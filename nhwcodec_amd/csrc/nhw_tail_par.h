@@ -2759,8 +2759,8 @@ DEV void pack_walk_list(uint64_t nz, int skip, const uint8_t *vb, int N, int lo,
 		if (rest & 1) {
 			const int px = vb[vi++];
 			if (MODE == 0) { atomicAdd(&sh->hist[px], 1); i++; rest >>= 1; continue; }
-			if (px == 153 || px == 155) { if (MODE == 2 && i1 + n1 < S_CAP) s1[i1 + n1] = (uint8_t)(px == 155); if (MODE == 1 && px == 155) s1m |= 1ull << n1; n1++; i++; rest >>= 1; continue; }
-			if (px == 157 || px == 159) { if (MODE == 2 && i2 + n2 < S_CAP) s2[i2 + n2] = (uint8_t)(px == 159); if (MODE == 1 && px == 159) s2m |= 1ull << n2; n2++; i++; rest >>= 1; continue; }
+			if (px == 153 || px == 155) { if (MODE == 2 && s1 && i1 + n1 < S_CAP) s1[i1 + n1] = (uint8_t)(px == 155); if (MODE == 1 && px == 155) s1m |= 1ull << n1; n1++; i++; rest >>= 1; continue; }
+			if (px == 157 || px == 159) { if (MODE == 2 && s2 && i2 + n2 < S_CAP) s2[i2 + n2] = (uint8_t)(px == 159); if (MODE == 1 && px == 159) s2m |= 1ull << n2; n2++; i++; rest >>= 1; continue; }
 			EMIT(sh->code_sym[px]);
 			if (px > 131 && px < 136) { vi += __builtin_popcount((unsigned)rest & 0x1Eu); i += 5; rest >>= 5; } else { i++; rest >>= 1; }
 			continue;
@@ -2810,8 +2810,8 @@ DEV void pack_walk_list(uint64_t nz, int skip, const uint8_t *vb, int N, int lo,
  * lanes of a wavefront read adjacent cache lines (a thread-per-kilobyte split makes every lane stream its own
  * line and thrashes L1: measured 5 us per symbol). */
 /* The chroma part's list as the chroma quantiser leaves it (quantise_chroma_par: [flush][lane][2 slices], a wavefront's values in a region of
- * its own) -> the form the walks read: map and value offset per slice in STREAM order, in the luma part's arrays (c->nzs, c->voff: the luma
- * part is through with them).  A thread takes eight consecutive slices of a flush (sixteen threads a flush): popcounts, a 16-lane prefix
+ * its own) -> the form the walks read: map and value offset per slice in STREAM order, in c->nzs, c->voff -- which k_pack_chroma points at
+ * arrays of the chroma part's own (B_CPACK): Y31 may not have filled the luma part's yet.  A thread takes eight consecutive slices of a flush (sixteen threads a flush): popcounts, a 16-lane prefix
  * sum on top of the flush's base.  Slice (flush F = 4 wavefront + turn, lane, half) holds rows 64 wv + 16 turn + 8 (lane & 1) + 4 half .. + 3 of
  * strip lane >> 1, U and V interleaved: stream slice 64 strip + rows / 4.  The last symbol of the stream is a copy of the one before it
  * (compress_pixel.c:464-465): only whether it is the zero symbol can matter (it is never walked, a run can end in it). */
@@ -2836,9 +2836,16 @@ DEV void pack_chroma_order(Ctx *c, int tid)
 }
 
 /* A part of the stream comes as a symbol list: the luma part from Y31 (c->nzs, c->voff, c->vals), the chroma part from the chroma quantiser
- * (c->cnzq / c->cvals, put into stream order here) -- the dense byte stream is only ever written for the stage checks. */
-DEV void pack_part_par(Ctx *c, int part, PackShared *sh, int tid, int word0, uint32_t *lw /* PK_LDS_BYTES */)
+ * (c->cnzq / c->cvals, put into stream order here) -- the dense byte stream is only ever written for the stage checks.
+ * pack_words_par is a part up to and including the write sweep: the luma part in k_final, the chroma part in k_pack_chroma (one copy of the
+ * walks in each kernel).  What it touches besides its inputs: c->nzs / c->voff (the chroma part writes them), c->raw (its gaps), c->packet
+ * (its words, from word 0) -- k_pack_chroma points all four at memory of its own -- and, the luma part only, c->s1 / c->s2, the sign words
+ * and its scalars in c->m.  The chroma part's sign symbols are counted and skipped like the luma part's, and stored nowhere: nobody reads them
+ * (sel_word1/2 are the luma part's), and the two parts run in either order.  It leaves sh->k, sh->sorted and the totals for the book. */
+template <int PART>
+DEV void pack_words_par(Ctx *c, PackShared *sh, int tid, uint32_t *lw /* PK_LDS_BYTES */)
 {
+	constexpr int part = PART;
 	const uint8_t *vals = part ? c->cvals : c->vals;
 	const int N = part ? 2 * Q : 4 * Q;
 	if (part) { pack_chroma_order(c, tid); __threadfence_block(); BARRIER(); }
@@ -2996,7 +3003,8 @@ DEV void pack_part_par(Ctx *c, int part, PackShared *sh, int tid, int word0, uin
 	/* bit counts and bits in one sweep: while a chunk is in LDS every slice is walked twice -- once to count its code bits
 	 * and sign symbols, and, after a workgroup prefix sum on top of the running totals, once to drop its bits at their
 	 * offset.  The words a chunk will touch are zeroed just ahead of it (the chunk before may share its first word). */
-	uint32_t *words = c->packet + word0;
+	uint32_t *words = c->packet;
+	uint8_t *const s1 = part ? nullptr : c->s1, *const s2 = part ? nullptr : c->s2;
 	unsigned base_bits = 0, base_n1 = 0, base_n2 = 0;
 	int zeroed = 0;                                              /* words [0, zeroed) are cleared or already carry bits */
 	PackPreL prel;
@@ -3015,8 +3023,10 @@ DEV void pack_part_par(Ctx *c, int part, PackShared *sh, int tid, int word0, uin
 		const unsigned on = block_exscan(x1 | (x2 << 16), tid, sh->bits, &tn);
 		const int last = tb ? (int)((base_bits + tb - 1) >> 5) : zeroed - 1;
 		/* the packet holds 80000 words per image, like the reference's calloc(80000) (compress_pixel.c:64), which never checks: a
-		 * stream that would not fit ends THIS image with a status instead of running into its neighbours' words */
-		if (word0 + last >= 80000) { if (tid == 0) sh->rc = NHW_E_SPACE; BARRIER(); return; }
+		 * stream that would not fit ends THIS image with a status instead of running into its neighbours' words.  (A part's words start at
+		 * word 0 of its own block, which holds 80000 as well; the chroma part's go behind the luma part's in the file, and `last` only grows
+		 * from chunk to chunk: k_final applies the rule to word0 + last once, from the chroma part's total -- final_phase_par.) */
+		if (last >= 80000) { if (tid == 0) sh->rc = NHW_E_SPACE; BARRIER(); return; }
 		for (int w = zeroed + tid; w <= last; w += NT) words[w] = 0;
 		BARRIER();
 		if (lo < S) {
@@ -3028,27 +3038,21 @@ DEV void pack_part_par(Ctx *c, int part, PackShared *sh, int tid, int word0, uin
 #pragma unroll
 				for (int k = 0; k < 5; k++) if (k < nw && v[k]) atomicOr(&words[w0 + k], v[k]);
 				const unsigned a1 = base_n1 + (on & 0xFFFF), a2 = base_n2 + (on >> 16);
-				for (unsigned z = 0; z < x1; z++) if (a1 + z < S_CAP) c->s1[a1 + z] = (uint8_t)((rec.s1m >> z) & 1);
-				for (unsigned z = 0; z < x2; z++) if (a2 + z < S_CAP) c->s2[a2 + z] = (uint8_t)((rec.s2m >> z) & 1);
+				if (!part) {
+					for (unsigned z = 0; z < x1; z++) if (a1 + z < S_CAP) s1[a1 + z] = (uint8_t)((rec.s1m >> z) & 1);
+					for (unsigned z = 0; z < x2; z++) if (a2 + z < S_CAP) s2[a2 + z] = (uint8_t)((rec.s2m >> z) & 1);
+				}
 			}
-			else pack_walk_list<2>(my_nz, my_skip, dl, N, lo, hi, sh, words, base_bits + ob, c->s1, base_n1 + (on & 0xFFFF), c->s2, base_n2 + (on >> 16), nullptr, nullptr, nullptr, my_prev, my_next);
+			else pack_walk_list<2>(my_nz, my_skip, dl, N, lo, hi, sh, words, base_bits + ob, s1, base_n1 + (on & 0xFFFF), s2, base_n2 + (on >> 16), nullptr, nullptr, nullptr, my_prev, my_next);
 		}
 		base_bits += tb; base_n1 += tn & 0xFFFF; base_n2 += tn >> 16;
 		if (last + 1 > zeroed) zeroed = last + 1;
 	}
 	if (tid == 0) { if (!zeroed) words[0] = 0; sh->total_bits = base_bits; sh->total_n1 = base_n1; sh->total_n2 = base_n2; }
 	BARRIER();
-	const int nwords = sh->total_bits ? (int)((sh->total_bits - 1) >> 5) + 1 : 1;
 	if (!tid) PROF(c, 26);
-
-	/* the code book (:400-459): the ranked entries as bytes (a run entry takes two), de-interleaved (even positions, then odd ones), runs of
-	 * the marker byte (3 in book 1, 128 in book 2) collapsed into (marker, count).  Until round 3 one thread walked this -- 0.1 of the
-	 * packetiser's 0.58 ms per image with 255 threads waiting; now three prefix sums.  Book 2's collapse reads on behind its table into what
-	 * book 1 left in the reference's one scratch array (c->cc) when the table ends in a run of 128s. */
-	const uint16_t *sorted = sh->sorted;
-	uint8_t *book = reinterpret_cast<uint8_t *>(lw), *tmp_book = book + 1024;
-	int *book_len = reinterpret_cast<int *>(book + 2048);
 	if (part == 0) {
+		const int nwords = sh->total_bits ? (int)((sh->total_bits - 1) >> 5) + 1 : 1;
 		const int n1 = (int)sh->total_n1, n2 = (int)sh->total_n2;
 		const int b1 = (n1 >> 3) + 1, b2 = (n2 >> 3) + 1;        /* sign bits, 8 per byte (:370-398) */
 		for (int t = tid; t < b1; t += NT) { int v = 0; for (int u = 0; u < 8; u++) v = (v << 1) | ((8 * t + u < n1 && 8 * t + u < S_CAP ? c->s1[8 * t + u] : 0) & 1); c->sel_word1[t] = (uint8_t)v; }
@@ -3058,7 +3062,22 @@ DEV void pack_part_par(Ctx *c, int part, PackShared *sh, int tid, int word0, uin
 			c->m->wavelet_type = (sh->select > 4 || !sh->top_is_zero) ? 4 : 0;       /* :367-368 */
 			c->m->select1 = b1; c->m->select2 = b2;
 		}
-	} else if (tid == 0) c->m->size_data2 = word0 + nwords;
+	}
+}
+
+/* A part's code book from its ranked entries (sh->sorted, sh->k): the luma part's behind its words, the chroma part's from what k_pack_chroma
+ * left (final_phase_par).  Book 2 must come second: see the stale bytes below, the one true dependency of the chroma part on the luma part. */
+template <int PART>
+DEV void pack_book_par(Ctx *c, PackShared *sh, int tid, uint32_t *lw /* PK_LDS_BYTES */)
+{
+	constexpr int part = PART;
+	/* the code book (:400-459): the ranked entries as bytes (a run entry takes two), de-interleaved (even positions, then odd ones), runs of
+	 * the marker byte (3 in book 1, 128 in book 2) collapsed into (marker, count).  Until round 3 one thread walked this -- 0.1 of the
+	 * packetiser's 0.58 ms per image with 255 threads waiting; now three prefix sums.  Book 2's collapse reads on behind its table into what
+	 * book 1 left in the reference's one scratch array (c->cc) when the table ends in a run of 128s. */
+	const uint16_t *sorted = sh->sorted;
+	uint8_t *book = reinterpret_cast<uint8_t *>(lw), *tmp_book = book + 1024;
+	int *book_len = reinterpret_cast<int *>(book + 2048);
 	{
 		const int k = sh->k, marker = part ? 128 : 3;
 		unsigned *scr = sh->bits;                                  /* scan scratch (the write sweep is done with it) */
@@ -3160,17 +3179,43 @@ DEV size_t container_par(Ctx *c, uint8_t *out, size_t cap, int tid)
 	return s.n <= cap ? s.n : 0;
 }
 
-/* Z1, Z2 and the container */
-DEV void final_phase_par(Ctx *c, uint8_t *out, size_t cap, uint32_t *size, int32_t *status, PackShared *sh, int tid, uint32_t *lw)
+/* Z2's chroma part up to and including its words (k_pack_chroma): on the chroma lists alone -- complete behind V's quantiser -- and into memory
+ * of its own (cp, words), so that it runs beside or in front of the luma tail.  Every field k_final reads is written on every path. */
+DEV void pack_chroma_par(Ctx *c, NhwChromaPack *cp, uint32_t *words, PackShared *sh, int tid, uint32_t *lw)
+{
+	c->nzs = cp->nzs; c->voff = cp->voff; c->raw = reinterpret_cast<uint8_t *>(cp->gaps); c->packet = words;
+	if (tid == 0) { sh->k = 0; sh->total_bits = 0; }
+	pack_words_par<1>(c, sh, tid, lw);
+	BARRIER();
+	const int rc = sh->rc, k = rc ? 0 : sh->k;
+	for (int e = tid; e < k; e += NT) cp->sorted[e] = sh->sorted[e];
+	if (tid == 0) {
+		const unsigned bits = rc ? 0u : sh->total_bits;
+		cp->rc = rc; cp->k = k;
+		cp->nwords = bits ? (int)((bits - 1) >> 5) + 1 : 1;
+		cp->last = bits ? (int)((bits - 1) >> 5) : -1;
+	}
+}
+
+/* Z2's luma part, both books and the container (k_final).  The chroma part's words and ranked book entries are k_pack_chroma's. */
+DEV void final_phase_par(Ctx *c, const NhwChromaPack *cp, const uint32_t *cwords, uint8_t *out, size_t cap, uint32_t *size, int32_t *status, PackShared *sh, int tid, uint32_t *lw)
 {
 	PROF_BEGIN();
 	/* (the reference's sentinel behind the luma part, compress_pixel.c:66, and its copy of the last chroma symbol, :464-465, were writes into the
 	 * byte stream; both parts come as lists now: the walks never reach the sentinel, the copy is made on the chroma part's map) */
-	pack_part_par(c, 0, sh, tid, 0, lw);
+	pack_words_par<0>(c, sh, tid, lw);
 	if (sh->rc) { if (tid == 0) { *size = 0; *status = sh->rc; } return; }
+	pack_book_par<0>(c, sh, tid, lw);
+	/* the status is the first of: the luma part's, the chroma part's, the capacity rule's (the chroma part's words go behind the luma part's:
+	 * word0 + last >= 80000, as when one workgroup packed both), the container's */
+	const int word0 = c->m->size_data1, crc = cp->rc, nwords = cp->nwords;
+	if (crc || word0 + cp->last >= 80000) { if (tid == 0) { *size = 0; *status = crc ? crc : NHW_E_SPACE; } return; }
+	for (int w = tid; w < nwords; w += NT) c->packet[word0 + w] = cwords[w];
+	const int ck = cp->k;
+	for (int e = tid; e < ck; e += NT) sh->sorted[e] = cp->sorted[e];
+	if (tid == 0) { sh->k = ck; c->m->size_data2 = word0 + nwords; }
 	BARRIER();
-	pack_part_par(c, 1, sh, tid, c->m->size_data1, lw);
-	if (sh->rc) { if (tid == 0) { *size = 0; *status = sh->rc; } return; }
+	pack_book_par<1>(c, sh, tid, lw);
 	if (!tid) PROF(c, 19);
 	const size_t n = container_par(c, out, cap, tid);
 	if (tid == 0) { *size = (uint32_t)n; *status = n ? NHW_OK : -3; }

@@ -26,7 +26,18 @@ enum {
 	B_NZQ, B_NZS, B_VOFF, B_VALS, B_CNZQ, B_CVALS,   /* the luma symbol stream as a list (nhw_tail_wave.h, wave_quantise_luma): non-zero map as the quantiser writes it, the map and the value offsets in stream order (Y31), the values; CNZQ / CVALS: the chroma part's map and values as the chroma quantiser leaves them */
 	B_CJPEG_V, B_CPROC_V, B_CLL1_V, B_CL2SAVE_V, B_UBYTES,   /* the V plane's own copies of the four chroma work planes (production: NhwWs::split_chroma); UBYTES: where the chroma quantiser parks U's symbols until V's come (it used the band plane, and above q21 waited for Y29 to be through with it) */
 	B_LOWTAB,   /* quality 1..16: the candidate masks pass A of the pre-filter leaves for its order-dependent cells (nhw_low.hip, k_low_pre -> k_low_mapfix): 320 bytes a row */
+	B_CPACK, B_CPACKET,   /* the chroma packetiser's own (k_pack_chroma, NhwChromaPack below): its map and value offsets in stream order, its scratch and what it leaves for k_final; its packet words from word 0 on (a chroma part alone may hold 80000 words) */
 	B_COUNT
+};
+
+/* B_CPACK of an image.  k_pack_chroma runs while the luma tail still owns B_NZS / B_VOFF (Y31) and B_RAW (Y25): everything it writes lies here
+ * and in B_CPACKET.  k_final reads the four scalars and the ranked entries. */
+struct NhwChromaPack {
+	uint64_t nzs[2048];          /* the chroma part's map in stream order (pack_chroma_order) */
+	uint32_t voff[2048];
+	int gaps[2 * (2048 + 8)];    /* last non-zero symbol before / first at-or-after a slice (pack_words_par) */
+	uint16_t sorted[360];        /* book 2's entries by rank */
+	int k, rc, nwords, last;     /* entries; the part's status; its packet words; its last word that carries bits (-1: none): the capacity rule's `last` */
 };
 
 /* scalar per-image state (reference encode_state / codec_setup scalars), one struct per image in B_META */
