@@ -386,7 +386,7 @@ int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *o
  * not finite, or NHW_T_U8 with another scale or bias. */
 enum { NHW_T_U8 = 0, NHW_T_F16 = 1, NHW_T_BF16 = 2, NHW_T_F32 = 3 };
 enum { NHW_T_HWC = 0, NHW_T_CHW = 1 };
-enum { NHW_T_BGR = 0, NHW_T_RGB = 1 };
+enum { NHW_T_BGR = 0, NHW_T_RGB = 1, NHW_T_GREY = 2 };   /* NHW_T_GREY: one channel; taken by the grey decode alone (below) */
 enum { NHW_T_ROWS_FILE = 0, NHW_T_ROWS_REVERSED = 1 };
 typedef struct { int32_t dtype, layout, channels, rows; float scale[3], bias[3]; uint32_t reserved; } nhw_tensor_format;   /* 44 bytes */
 /* nhw_dec_batch_device_scaled with a format: scale 1, 2 or 4 as there (S = 512 / scale), file i's tensor at d_out + i * 3 * S * S *
@@ -606,6 +606,29 @@ int nhw_warp_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_wid
 int nhw_dec_warps_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
                             int32_t *status);
+
+/* ---- decode grey: the luma alone into one-channel bytes and tensors ----
+ * The grey byte of a pixel is what the file's own colour matrix gives for the pixel's luma byte Y at neutral chroma, U = V = 128.  There the
+ * matrix gives R = G = B for every quality and every Y, so grey is a table of 256 bytes a quality, G_q[Y]: the identity for quality 20 .. 23,
+ * a monotone gain curve below (quality 19: 16 -> 16, 128 -> 131, 235 -> 241).  Y at scale 1 is the decoder's luma plane in front of the colour
+ * matrix; at scale 2 and 4 it is the luma of the scaled decode above (the level-1 low band clipped; the level-2 low band turned and clipped).
+ * The chroma of the file is not decoded: the chroma planes' kernels are not launched, and the last kernel stores 1 byte a pixel, not 3.
+ * nhw_grey_table: G_quality into table[0 .. 256).  Host only: no handle, no GPU call.  NHW_E_ARG for a quality outside 1 .. 23 or a NULL table. */
+int nhw_grey_table(int quality, uint8_t table[256]);
+/* nhw_dec_batch_device_scaled as grey: scale 1, 2 or 4, S = 512 / scale.  fmt NULL: file i's S S grey bytes at d_out + i * S S, uint8 [S][S],
+ * rows in file order (the byte path's).  Otherwise fmt->channels must be NHW_T_GREY, and file i's tensor, S S elements, lies at d_out + i * S *
+ * S * sizeof(dtype): dtype, rows, scale[0] and bias[0] are read, under the value rule of the tensor formats; with one channel NHW_T_HWC
+ * ([S][S][1]) and NHW_T_CHW ([1][S][S]) are the same memory, and both are accepted; entries 1 and 2 of scale and bias are checked as ever (finite;
+ * scale 1 and bias 0 for NHW_T_U8) and not used.  d_status and d_quality are exactly those of the colour decode -- the prefix-code walk of the
+ * chroma packet still runs, so a file whose chroma packet alone is damaged is refused here too --, and a refused file leaves its slot untouched.
+ * NHW_E_ARG, before anything is launched: a format with NHW_T_BGR or NHW_T_RGB, an otherwise refused format, a d_out that is not 16-byte
+ * aligned, a handle with a debug stop set, and the cases of nhw_dec_batch_device_scaled.  Asynchronous on `stream`; nhw_dec_last_timing
+ * describes it, recon_ms = the kernel that writes the grey pictures.  One handle serves colour and grey batches in any order.  Every other
+ * entry point refuses NHW_T_GREY. */
+int nhw_dec_batch_device_grey(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                              const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream);
+/* host convenience, synchronous: as nhw_dec_batch_scaled, for any n >= 1; file i's S S grey bytes land at out + i * S S */
+int nhw_dec_batch_grey(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality);
 
 #ifdef __cplusplus
 }

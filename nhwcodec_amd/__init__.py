@@ -123,6 +123,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_warp_to_tensor_device.argtypes = L.nhw_resize_to_tensor_device.argtypes          # the table of warps where the flags are
     L.nhw_dec_warps_to_device.argtypes = L.nhw_dec_crops_to_device.argtypes
     L.nhw_debug_warp_row_limit.argtypes, L.nhw_debug_warp_row_limit.restype = [ctypes.c_int], None
+    L.nhw_grey_table.argtypes = [ctypes.c_int, P]
+    L.nhw_dec_batch_device_grey.argtypes = L.nhw_dec_batch_device_tensor.argtypes
+    L.nhw_dec_batch_grey.argtypes = L.nhw_dec_batch_scaled.argtypes
     return L
 
 
@@ -236,6 +239,7 @@ NHW_T_U8, NHW_T_F16, NHW_T_BF16, NHW_T_F32 = 0, 1, 2, 3
 TENSOR_DTYPES = {"uint8": NHW_T_U8, "float16": NHW_T_F16, "bfloat16": NHW_T_BF16, "float32": NHW_T_F32}
 TENSOR_LAYOUTS = {"HWC": 0, "CHW": 1}             # NHW_T_HWC, NHW_T_CHW
 TENSOR_CHANNELS = {"BGR": 0, "RGB": 1}            # NHW_T_BGR, NHW_T_RGB
+TENSOR_GREY = 2                                   # NHW_T_GREY: channels "GREY", which the grey decode alone takes
 TENSOR_ROWS = {"file": 0, "reversed": 1}          # NHW_T_ROWS_FILE, NHW_T_ROWS_REVERSED
 
 
@@ -249,14 +253,17 @@ class TensorFormat:
     are kept and overflow gives an infinity, in float32 and in dtype.  Zero's sign is the fma's: a nonzero value that rounds to zero keeps
     its sign; an exact zero is +0, except -0 for a zero product of negative sign (byte 0 under a scale below zero) plus a bias of -0.0.  Either scale / bias (three numbers each, or one for all; default 1 and 0) or mean / std in units of 0..1
     pixels, which give, in float32 arithmetic, scale = 1 / (255 * std) and bias = -mean / std (so that the element is (b / 255 - mean) / std
-    up to rounding).  The attributes scale and bias are the float32 constants the kernels get, as tuples of Python floats."""
+    up to rounding).  The attributes scale and bias are the float32 constants the kernels get, as tuples of Python floats.
+    channels "GREY" is the one-channel format of Decoder.decode_grey_device and of nothing else: scale / bias / mean /
+    std take ONE number (three are refused), the tensor is [1, S, S] or [S, S, 1], and there is no inverse, for encoding from grey is not
+    built."""
 
     def __init__(self, dtype="float32", layout="CHW", channels="RGB", rows="reversed", scale=None, bias=None, mean=None, std=None):
         import numpy as np
         name = dtype if isinstance(dtype, str) else str(dtype).replace("torch.", "")
         if name not in TENSOR_DTYPES:
             raise NhwError(f"TensorFormat: dtype must be uint8, float16, bfloat16 or float32, got {dtype!r}")
-        for what, v, table in (("layout", layout, TENSOR_LAYOUTS), ("channels", channels, TENSOR_CHANNELS), ("rows", rows, TENSOR_ROWS)):
+        for what, v, table in (("layout", layout, TENSOR_LAYOUTS), ("channels", channels, dict(TENSOR_CHANNELS, GREY=TENSOR_GREY)), ("rows", rows, TENSOR_ROWS)):
             if not isinstance(v, str) or v not in table:
                 raise NhwError(f"TensorFormat: {what} must be one of {sorted(table)}, got {v!r}")
         if (mean is not None or std is not None) and (scale is not None or bias is not None):
@@ -270,6 +277,8 @@ class TensorFormat:
                     a = np.asarray(v, dtype=np.float64).astype(np.float32)
             except (TypeError, ValueError):
                 raise NhwError(f"TensorFormat: {what} must be one number or three, got {v!r}") from None
+            if channels == "GREY" and a.ndim != 0:
+                raise NhwError(f"TensorFormat: with channels \"GREY\" {what} must be one number, got {v!r}")
             if a.ndim == 0:
                 a = np.repeat(a, 3)
             if a.shape != (3,):
@@ -300,10 +309,11 @@ class TensorFormat:
 
     def shape(self, height, width):
         """the shape of one picture's tensor"""
-        return (3, height, width) if self.layout == "CHW" else (height, width, 3)
+        c = 1 if self.channels == "GREY" else 3
+        return (c, height, width) if self.layout == "CHW" else (height, width, c)
 
     def c_struct(self) -> CTensorFormat:
-        return CTensorFormat(TENSOR_DTYPES[self.dtype_name], TENSOR_LAYOUTS[self.layout], TENSOR_CHANNELS[self.channels], TENSOR_ROWS[self.rows],
+        return CTensorFormat(TENSOR_DTYPES[self.dtype_name], TENSOR_LAYOUTS[self.layout], TENSOR_GREY if self.channels == "GREY" else TENSOR_CHANNELS[self.channels], TENSOR_ROWS[self.rows],
                              (ctypes.c_float * 3)(*self.scale), (ctypes.c_float * 3)(*self.bias), 0)
 
     def inverted(self):
@@ -311,6 +321,8 @@ class TensorFormat:
         scale' = 1 / scale and bias' = -bias / scale, so that fmaf(fmaf(b, scale, bias), scale', bias') lies near b.  NhwError if a scale is 0 or
         a result is not finite in float32."""
         import numpy as np
+        if self.channels == "GREY":
+            raise NhwError("TensorFormat.inverted: a grey format has no inverse: encoding from grey is not built")
         sc, bi = np.array(self.scale, np.float32), np.array(self.bias, np.float32)
         if np.any(sc == 0):
             raise NhwError(f"TensorFormat.inverted: a scale of 0 has no inverse: {self.scale}")
@@ -322,6 +334,18 @@ class TensorFormat:
 
     def __repr__(self):
         return f"TensorFormat({self.dtype_name}, {self.layout}, {self.channels}, rows={self.rows}, scale={self.scale}, bias={self.bias})"
+
+
+def grey_table(quality: int):
+    """G_quality (nhw_grey_table): numpy uint8 [256], the grey byte of every luma byte under the colour matrix of that
+    quality at neutral chroma -- the identity for quality 20 .. 23, a gain curve below.  Needs no GPU."""
+    import numpy as np
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 23:
+        raise NhwError(f"grey_table: quality must be an integer 1 .. 23, got {quality!r}")
+    t = np.empty(256, np.uint8)
+    if _library().nhw_grey_table(quality, t.ctypes.data) != 0:
+        raise NhwError(f"grey_table: {_library().nhw_dec_last_error().decode()}")
+    return t
 
 
 def _tensor_format(fmt, what):
@@ -1439,25 +1463,54 @@ class Decoder:
                                                            out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
         return px, status, quality
 
-    def decode_scaled(self, files, scale):
-        """decode at scale 1, 2 or 4 (nhw_dec_batch_scaled): files, a list of .nhw byte strings of any length (decoded in chunks of max_batch) ->
-        (uint8 [n, S, S, 3] with S = 512 // scale, quality list).  Raises on a file the decoder refuses."""
+    def decode_grey_device(self, arena, offsets, lengths, scale=1, fmt=None, out=None):
+        """decode_scaled_device as grey (nhw_dec_batch_device_grey): the luma alone, through the grey table of the
+        file's quality (grey_table), one channel; the chroma planes are not decoded.  Arguments as for decode_scaled_device.  Without fmt:
+        (uint8 pixels [n, S, S], rows in file order, status[n], quality[n]), S = 512 // scale.  With fmt, a TensorFormat of channels "GREY":
+        (tensor [n, 1, S, S] or [n, S, S, 1] of fmt.dtype, status, quality).  out: a contiguous, 16-byte aligned tensor of that dtype with at
+        least n * S * S elements.  Status and quality are those of the colour decode; a refused file's slot is left untouched."""
+        what = "decode_grey_device"
+        if fmt is not None and _tensor_format(fmt, what).channels != "GREY":
+            raise NhwError(f"{what}: `fmt` must have channels \"GREY\", got {fmt.channels!r}")
+        scale = _scale(scale, what)
+        side = 512 // scale
+        n = self._device_files(arena, offsets, lengths, what)
+        dtype = self.torch.uint8 if fmt is None else fmt.dtype
+        out, px, status, quality = self._device_out(out, what, dtype, (n, side, side) if fmt is None else (n,) + fmt.shape(side, side), 16,
+                                                    f"contiguous, 16-byte aligned {dtype} tensor of n*{side * side} elements")
+        c = None if fmt is None else fmt.c_struct()
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_dec_batch_device_grey(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale,
+                                                         None if c is None else ctypes.byref(c), out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
+        return px, status, quality
+
+    def _scaled_host(self, files, scale, what, call, channels):
+        """decode_scaled and decode_grey: call = the C entry -> (uint8 [n, S, S] + channels, quality list)"""
         import numpy as np
-        scale = _scale(scale, "decode_scaled")
+        scale = _scale(scale, what)
         side = 512 // scale
         if not isinstance(files, (list, tuple)) or not files or not all(isinstance(f, (bytes, bytearray, memoryview)) for f in files):
-            raise NhwError("decode_scaled wants a non-empty list of .nhw byte strings")
+            raise NhwError(f"{what} wants a non-empty list of .nhw byte strings")
         n = len(files)
         offs = np.zeros(n + 1, np.uint64)
         offs[1:] = np.cumsum([len(f) for f in files])
         blob = np.frombuffer(b"".join(bytes(f) for f in files) + b"\0", np.uint8)
-        out = np.empty((n, side, side, 3), np.uint8)
+        out = np.empty((n, side, side) + channels, np.uint8)
         status = np.empty(n, np.int32)
         quality = np.empty(n, np.int32)
-        self._chk(self.lib.nhw_dec_batch_scaled(self.h, blob.ctypes.data, offs.ctypes.data, n, scale, out.ctypes.data, status.ctypes.data, quality.ctypes.data))
+        self._chk(call(self.h, blob.ctypes.data, offs.ctypes.data, n, scale, out.ctypes.data, status.ctypes.data, quality.ctypes.data))
         if (status != 0).any():
             raise NhwError(f"per-file status {status.tolist()}")
         return out, quality.tolist()
+
+    def decode_scaled(self, files, scale):
+        """decode at scale 1, 2 or 4 (nhw_dec_batch_scaled): files, a list of .nhw byte strings of any length (decoded in chunks of max_batch) ->
+        (uint8 [n, S, S, 3] with S = 512 // scale, quality list).  Raises on a file the decoder refuses."""
+        return self._scaled_host(files, scale, "decode_scaled", self.lib.nhw_dec_batch_scaled, (3,))
+
+    def decode_grey(self, files, scale=1):
+        """decode_scaled as grey (nhw_dec_batch_grey) -> (uint8 [n, S, S], rows in file order, quality list)."""
+        return self._scaled_host(files, scale, "decode_grey", self.lib.nhw_dec_batch_grey, ())
 
     def _pictures_host(self, containers, scale, call):
         """decode_pictures and decode_pictures_scaled: call(blob, offsets, n, out, out_off, status) -> rc"""

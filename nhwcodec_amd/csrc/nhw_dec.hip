@@ -17,7 +17,8 @@
  *                  corrections, level 1
  *   k_dec_marks, k_dec_sharpen
  *   k_dec_final    level 1 of the luma both ways, corrections, smoothing, chroma up-sampling, colour matrix -> BGR24,
- *                  or a tensor format (the store policies: DESIGN.md section 16)
+ *                  or a tensor format (the store policies: DESIGN.md section 16); its grey form: the luma phases, then the grey table
+ *                  (nhw_grey.h) and one channel out, nothing of the chroma (section 22)
  *
  * Everything is int16/uint8 arithmetic; the only floating point is the colour matrix and a tensor format's scale and
  * bias (compiled with -ffp-contract=off like the rest of the library).  No stage falls back to the host.
@@ -26,6 +27,7 @@
 
 #include "nhw_dec.h"
 #include "nhw_dwt.h"
+#include "nhw_grey.h"
 #include "nhw_tensor.h"
 
 #define DW 512
@@ -2090,7 +2092,17 @@ __global__ void k_dec_colour_probe(const uint8_t *__restrict__ yuv, uint8_t *__r
  * of row r of file img, an S x S picture -- as the 3 N bytes the byte path stores (B, G, R a pixel), and its constants are kernel arguments.
  * StoreBytes is the byte path and only a tag: its stores stay spelled out in the kernels, and it adds no kernel argument, so that instantiation is
  * the code it was before there were formats, instruction for instruction. */
-struct StoreBytes { static constexpr bool bytes = true; };
+struct StoreBytes { static constexpr bool bytes = true, grey = false; };
+/* NhwStoreGrey<dtype> (nhw_tensor.h) makes either kernel its grey form: the luma phases as they are, nothing of the chroma
+ * loaded or computed, the luma bytes through the grey table of the file's quality (nhw_grey.h; the identity from quality 20 on, where the table is
+ * not even built) and one channel stored.  The 256 threads of a workgroup make the 256 entries in LDS, one each. */
+DEV void grey_table_fill(uint8_t *tab, int q, int tid) { if (q < 20) tab[tid] = (uint8_t)nhw_grey_value(q, tid); }
+/* four luma bytes -> their grey bytes */
+DEV uint32_t grey4(const uint8_t *tab, int q, uint32_t y4)
+{
+	if (q >= 20) return y4;
+	return (uint32_t)tab[y4 & 255u] | ((uint32_t)tab[(y4 >> 8) & 255u] << 8) | ((uint32_t)tab[(y4 >> 16) & 255u] << 16) | ((uint32_t)tab[y4 >> 24] << 24);
+}
 
 /* ---------------------------------------------------------------------------------------------- final reconstruction, one kernel
  * Level-1 synthesis in both directions (decoder/wavelet_filterbank.c:52-357 as driven by nhw_decoder.c), the q > 21 corrections on the
@@ -2113,6 +2125,7 @@ struct StoreBytes { static constexpr bool bytes = true; };
 #define FM (FR / 2 + 1)              /* values of m a band computes: r0/2 - 1 .. r0/2 + FR/2 - 1 */
 #define F_T_BYTES (2 * DH * FBP * 2)
 #define F_LDS_BYTES (F_T_BYTES + FR * DW + 2 * (FR / 2 + 1) * DH)   /* T, the luma bytes, the chroma rows: 31 KB, five bands to a CU */
+#define F_GREY_LDS_BYTES (F_T_BYTES + FR * DW + 256)                /* the grey form: T, the luma bytes, the grey table: 26.25 KB, six bands to a CU */
 template <class ST /* the store policy of the colour phase */, class... Fmt /* its kernel arguments: none for StoreBytes, NhwTensorArgs for a tensor format */>
 __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int dev_stop /* developer builds: end every band after phase dev_stop (0: run it all) */,
                                                   int slice /* -1: production; else the band (nhw_host.h) */, Fmt... fmt)
@@ -2126,7 +2139,7 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 	extern __shared__ __attribute__((aligned(16))) uint8_t fl[];
 	int16_t *T = reinterpret_cast<int16_t *>(fl);                               /* [512][FBP] */
 	uint8_t *ybuf = fl + F_T_BYTES;                                             /* [FR][512] */
-	uint8_t *crow = ybuf + FR * DW;                                             /* [2][FR / 2 + 1][256] */
+	uint8_t *crow = ybuf + FR * DW;                                             /* [2][FR / 2 + 1][256]; the grey form: its table, [256] */
 	const int tid = threadIdx.x;
 	int band, img;
 	{
@@ -2140,7 +2153,8 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 	const int q = m->q, r0 = FR * band, m0 = r0 / 2 - 1;                       /* m0: first m of the band (-1 in band 0: skipped) */
 	const int16_t *A = plane_a(ws, img), *L1 = plane_l1(ws, img);              /* the detail bands; the level-1 LL */
 
-	for (int k = tid; k < 2 * (FR / 2 + 1) * (DH / 16); k += 256) {
+	if constexpr (ST::grey) grey_table_fill(crow, q, tid);                      /* (read behind the barriers of the luma phases) */
+	else for (int k = tid; k < 2 * (FR / 2 + 1) * (DH / 16); k += 256) {
 		const int pl = k / ((FR / 2 + 1) * (DH / 16)), rem = k % ((FR / 2 + 1) * (DH / 16)), rr = rem / (DH / 16), o = rem % (DH / 16);
 		const int src = r0 / 2 + rr < DH ? r0 / 2 + rr : DH - 1;
 		reinterpret_cast<uint4 *>(crow + (pl * (FR / 2 + 1) + rr) * DH)[o] = reinterpret_cast<const uint4 *>(ws.buf<uint8_t>(D_CU, img) + (size_t)pl * DQ + (size_t)src * DH)[o];
@@ -2277,8 +2291,18 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 	F_STOP(4);
 
 	/* colour (nhw_decoder_cli.c:133-283).  Quality >= 20: a thread = EIGHT pixels of one row, four rows a step; the chroma is doubled four bytes
-	 * at a time (byte-wise means: v_lerp_u8), the matrix runs in packed single precision (colour8_q20). */
-	if (q >= 20) {
+	 * at a time (byte-wise means: v_lerp_u8), the matrix runs in packed single precision (colour8_q20).
+	 * The grey form has no colour phase: a thread = SIXTEEN pixels of one row, eight rows a step, through the table, one piece stored. */
+	if constexpr (ST::grey) {
+		const int t16 = tid & 31;
+		for (int it = 0; it < FR / 8; it++) {
+			const int lr = 8 * it + (tid >> 5), r = r0 + lr;
+			const uint4 y16 = *reinterpret_cast<const uint4 *>(ybuf + lr * DW + 16 * t16);
+			const uint32_t w[4] = { grey4(crow, q, y16.x), grey4(crow, q, y16.y), grey4(crow, q, y16.z), grey4(crow, q, y16.w) };
+			st.template put<DW, 16>(out, img, r, t16, w);
+		}
+	}
+	else if (q >= 20) {
 		const int t8 = tid & 63;
 		const uint8_t *cU = crow, *cV = crow + (FR / 2 + 1) * DH;
 		for (int it = 0; it < FR / 4; it++) {
@@ -2359,11 +2383,16 @@ template <int S, class ST = StoreBytes, class... Fmt /* as for k_dec_final */> _
 	const ST st{ fmt... };
 	static_assert(S == 2 || S == 4, "half or quarter scale");
 	constexpr int T = DW / S, NB = T / SC_ROWS, TPR = T / 8, YP = T + 4;   /* tile side, bands a file, threads a row; LDS pitch of a luma row (S = 4): a band's four pieces of a line on different banks */
-	__shared__ __attribute__((aligned(16))) uint8_t ybuf[S == 4 ? SC_ROWS * YP : 16];
-	const int tid = threadIdx.x, img = blockIdx.x / NB, r0 = (blockIdx.x % NB) * SC_ROWS;
+	constexpr int YB = S == 4 ? SC_ROWS * YP : 16;
+	__shared__ __attribute__((aligned(16))) uint8_t ybuf[YB + (ST::grey ? 256 : 0)];
+	uint8_t *gtab = ybuf + YB;                                           /* the grey form: its table, [256] */
+	const int tid = threadIdx.x;
+	int img = blockIdx.x / NB, r0 = (blockIdx.x % NB) * SC_ROWS;
+	if constexpr (ST::grey) if (st.a.slice >= 0) { img = blockIdx.x; r0 = st.a.slice * SC_ROWS; }   /* a forced slice order (nhw_host.h): every file's band `slice` */
 	const DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (m->status) return;
 	const int q = m->q;
+	if constexpr (ST::grey) { grey_table_fill(gtab, q, tid); if (S != 4) __syncthreads(); }   /* (S = 4: the barrier behind the turn) */
 	if (S == 4) {
 		const int16_t *A = plane_a(ws, img);
 		const int g = tid & 3;
@@ -2379,13 +2408,20 @@ template <int S, class ST = StoreBytes, class... Fmt /* as for k_dec_final */> _
 	for (int it = 0; it < SC_ROWS * TPR / 256; it++) {
 		const int i = tid + 256 * it, lr = i / TPR, c8 = i % TPR, r = r0 + lr;
 		uint2 y8, u8, v8;
+		if (S == 2) y8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_l1(ws, img) + (size_t)r * DW + 8 * c8));
+		else {
+			const uint32_t *yw = reinterpret_cast<const uint32_t *>(ybuf + lr * YP + 8 * c8);
+			y8 = make_uint2(yw[0], yw[1]);
+		}
+		if constexpr (ST::grey) {                                      /* no chroma: the luma through the table, one channel out */
+			const uint32_t g[2] = { grey4(gtab, q, y8.x), grey4(gtab, q, y8.y) };
+			st.template put<T, 8>(out, img, r, c8, g);
+			continue;
+		}
 		if (S == 2) {
-			y8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_l1(ws, img) + (size_t)r * DW + 8 * c8));
 			const uint8_t *cu = ws.buf<uint8_t>(D_CU, img) + (size_t)r * DH + 8 * c8;
 			u8 = *reinterpret_cast<const uint2 *>(cu); v8 = *reinterpret_cast<const uint2 *>(cu + DQ);
 		} else {
-			const uint32_t *yw = reinterpret_cast<const uint32_t *>(ybuf + lr * YP + 8 * c8);
-			y8 = make_uint2(yw[0], yw[1]);
 			u8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_ca(ws, img, 0) + r * T + 8 * c8));
 			v8 = clip8x8(*reinterpret_cast<const uint4 *>(plane_ca(ws, img, 1) + r * T + 8 * c8));
 		}
@@ -2519,8 +2555,22 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 
 /* one batch at scale 1 (the whole decode), 2 or 4: what the two entry points below share */
 struct TensorStore { int dtype, layout; NhwTensorArgs a; };         /* a checked format other than the byte path's */
+struct GreyStore { int dtype; NhwGreyArgs a; };                      /* a checked grey format */
+/* the grey forms of the scaled kernel: the file's T / SC_ROWS bands side by side, or a band a launch under a forced slice order */
+template <int S> static void launch_scaled_grey(const DecWs &ws, int n, const GreyStore &g, uint8_t *out, hipStream_t s)
+{
+	constexpr int NB = DW / S / SC_ROWS;
+	nhw_slices(NB, [&](int sl) {
+		NhwGreyArgs a = g.a;
+		a.slice = sl;
+		nhw_with_grey_store(g.dtype, a, [&](auto st) { k_dec_scaled<S, decltype(st)><<<sl < 0 ? NB * n : n, 256, 0, s>>>(ws, out, st.a); });
+	});
+}
+/* With `grey` the plan is the grey one: the entropy stages, the expansion, the luma's kernels and the grey form of the last kernel -- no k_dec_chroma,
+ * no k_dec_sharpen, no chroma stream; behind the prefix-code walk nothing reads the chroma value list, and nothing reads or writes D_CA or D_CU. */
 static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_bgr, int32_t *d_status,
-                     int32_t *d_quality, void *stream, const TensorStore *tensor = nullptr /* the last kernel stores this format */)
+                     int32_t *d_quality, void *stream, const TensorStore *tensor = nullptr /* the last kernel stores this format */,
+                     const GreyStore *grey = nullptr)
 {
 	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
@@ -2534,11 +2584,11 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 	int stage = 0;
 	d->timed = false;
 	d->l1_moved = false;
-	const bool fork = (d->chroma_fork & 2) && !d->stop_after && scale == 1;   /* the chroma sequence beside the luma one (a scaled decode keeps it in line) */
+	const bool fork = (d->chroma_fork & 2) && !d->stop_after && scale == 1 && !grey;   /* the chroma sequence beside the luma one (a scaled decode keeps it in line) */
 	const bool fork_e = (d->chroma_fork & 1) && !d->stop_after;        /* the two entropy branches side by side */
 	hipStream_t cs = fork ? d->chroma_stream : s;
 	hipStream_t es = fork_e ? d->chroma_stream : s;
-	const bool fork_late = (d->chroma_fork & 4) && !fork && !d->stop_after;   /* the chroma sequence beside the smooth-edge marks only: behind the luma's level 2 */
+	const bool fork_late = (d->chroma_fork & 4) && !fork && !d->stop_after && !grey;   /* the chroma sequence beside the smooth-edge marks only: behind the luma's level 2 */
 #define STAGE_END() do { if (d->stop_after && ++stage >= d->stop_after) goto done; } while (0)
 #define EV(i) HIPCHK(hipEventRecord(d->ev[i], s))
 	EV(0);
@@ -2558,9 +2608,10 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 #define CHROMA(UPTO, STREAM) k_dec_chroma<<<2 * n < SYNTH_WGS ? 2 * n : SYNTH_WGS, 1024, 256 * 258 * sizeof(int16_t), STREAM>>>(ws, 2 * n, UPTO)
 	k_dec_expand<<<(n + 3) / 4, 256, 0, s>>>(ws);
 	if (scale == 4) {                                                             /* quarter scale: the level-2 LL is in plane A already; the chroma planes up to their corrections */
-		CHROMA(5, s);
+		if (!grey) CHROMA(5, s);
 		EV(2);
-		if (!tensor) k_dec_scaled<4><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		if (grey) launch_scaled_grey<4>(ws, n, *grey, (uint8_t *)d_bgr, s);
+		else if (!tensor) k_dec_scaled<4><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
 		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) { k_dec_scaled<4, decltype(st)><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr, st.a); });
 		EV(3);
 		d->timed = true;
@@ -2583,10 +2634,13 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 	STAGE_END();                                                                  /* 5 (after the synthesis) */
 	STAGE_END();                                                                  /* 6 */
 	if (scale == 2) {                                                             /* half scale: the level-1 LL and the whole chroma sequence, in line; no marks, no level 1 of the luma */
-		CHROMA(4, s);
-		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, s>>>(ws);
+		if (!grey) {
+			CHROMA(4, s);
+			k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, s>>>(ws);
+		}
 		EV(2);
-		if (!tensor) k_dec_scaled<2><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
+		if (grey) launch_scaled_grey<2>(ws, n, *grey, (uint8_t *)d_bgr, s);
+		else if (!tensor) k_dec_scaled<2><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
 		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) { k_dec_scaled<2, decltype(st)><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr, st.a); });
 		EV(3);
 		d->timed = true;
@@ -2602,7 +2656,7 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 	k_dec_marks_far<<<(n + 3) / 4, 256, 0, s>>>(ws);                              /* (ends at once for every file but one whose level-1 LL leaves -5999 .. 10000) */
 	STAGE_END();                                                                  /* 7 */
 	if (fork || fork_late) HIPCHK(hipStreamWaitEvent(s, d->join_ev, 0));
-	else {
+	else if (!grey) {
 		CHROMA(d->stop_after == 8 ? 2 : d->stop_after == 9 ? 3 : 4, s);
 		STAGE_END();                                                              /* 8 (after level 2) */
 		STAGE_END();                                                              /* 9 (after the corrections) */
@@ -2617,7 +2671,10 @@ static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const
 #ifdef NHW_DEV
 		if (const char *e = getenv("NHW_FINAL_STOP")) dev_stop = atoi(e);
 #endif
-		if (!tensor) nhw_slices(DW / FR, [&](int sl) { k_dec_final<StoreBytes><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl); });
+		if (grey) nhw_with_grey_store(grey->dtype, grey->a, [&](auto st) {                    /* the same launch plan, the grey form's LDS */
+			nhw_slices(DW / FR, [&](int sl) { k_dec_final<decltype(st)><<<sl < 0 ? (DW / FR) * n : n, 256, F_GREY_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl, st.a); });
+		});
+		else if (!tensor) nhw_slices(DW / FR, [&](int sl) { k_dec_final<StoreBytes><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl); });
 		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) {     /* the same launch plan, the same LDS */
 			nhw_slices(DW / FR, [&](int sl) { k_dec_final<decltype(st)><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl, st.a); });
 		});
@@ -2656,6 +2713,29 @@ extern "C" int nhw_dec_batch_device_tensor(nhw_dec *d, const void *d_nhw, const 
 	if (nhw_tensor_format_is_bytes(fmt)) return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
 	t.dtype = fmt->dtype; t.layout = fmt->layout;
 	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, &t);
+}
+
+/* a batch as grey: the grey plan of dec_batch; without a format, bytes in file order */
+extern "C" int nhw_dec_batch_device_grey(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                         const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	GreyStore g = { NHW_T_U8, { 1.0f, 0.0f, 0, -1 } };
+	if (fmt) {
+		NhwTensorArgs a;
+		if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_dec_err, true)) return rc;
+		g.dtype = fmt->dtype; g.a.scale = a.scale[0]; g.a.bias = a.bias[0]; g.a.flip = a.flip;
+	}
+	if ((uintptr_t)d_out & 15) { nhw_dec_err = "a grey decode's output must be 16-byte aligned"; return NHW_E_ARG; }
+	if (d && d->stop_after) { nhw_dec_err = "a grey decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
+	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, nullptr, &g);
+}
+
+/* host only: no handle, no GPU call */
+extern "C" int nhw_grey_table(int quality, uint8_t table[256])
+{
+	if (!table || quality < 1 || quality > 23) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	for (int y = 0; y < 256; y++) table[y] = (uint8_t)nhw_grey_value(quality, y);
+	return NHW_OK;
 }
 
 extern "C" int nhw_dec_last_timing(nhw_dec *d, nhw_dec_timing *t)

@@ -27,13 +27,14 @@ static bool offsets_ok(const uint64_t *off, int n, const char *who)
 }
 
 /* host convenience: H2D of the files, decode, D2H of the pixels.  nhw: the files back to back, off[n+1].  At scale 1, 2 or 4 (DESIGN.md section
- * 14), for any n >= 1: the files go up once and are decoded in chunks of max_batch; file i's 3 T T bytes (T = 512 / scale) land at out + i * 3 T T */
-static int dec_batch_host(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality, const char *who)
+ * 14), for any n >= 1: the files go up once and are decoded in chunks of max_batch; file i's 3 T T bytes (T = 512 / scale) land at out + i * 3 T T;
+ * as grey its T T bytes at out + i * T T */
+static int dec_batch_host(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality, const char *who, bool grey = false)
 {
 	if (!d || !nhw || !off || !out || !status || n < 1) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (!scale_ok(scale) || !offsets_ok(off, n, who)) return NHW_E_ARG;
 	HIPCHK(hipSetDevice(d->device));
-	const size_t total = (size_t)(off[n] - off[0]), per = (size_t)NHW_IMG_BYTES / (size_t)(scale * scale);
+	const size_t total = (size_t)(off[n] - off[0]), per = (size_t)NHW_IMG_BYTES / (size_t)(scale * scale) / (grey ? 3 : 1);
 	{ const int rc = host_buffers(d, total); if (rc) return rc; }
 	hipStream_t s = d->own_stream;
 	HIPCHK(hipMemcpyAsync(d->blob.p, nhw + off[0], total, hipMemcpyHostToDevice, s));
@@ -49,7 +50,8 @@ static int dec_batch_host(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, i
 		HIPCHK(hipMemcpyAsync(d->d_off, rel.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
 		HIPCHK(hipMemcpyAsync(d->d_len, len.data(), (size_t)m * 4, hipMemcpyHostToDevice, s));
 		HIPCHK(hipStreamSynchronize(s));                              /* rel and len are filled again for the next chunk */
-		const int rc = nhw_dec_batch_device_scaled(d, d->blob.p, d->d_off, d->d_len, m, scale, d->d_out, d->d_status, d->d_quality, s);
+		const int rc = grey ? nhw_dec_batch_device_grey(d, d->blob.p, d->d_off, d->d_len, m, scale, nullptr, d->d_out, d->d_status, d->d_quality, s)
+		                    : nhw_dec_batch_device_scaled(d, d->blob.p, d->d_off, d->d_len, m, scale, d->d_out, d->d_status, d->d_quality, s);
 		if (rc) return rc;
 		HIPCHK(hipMemcpyAsync(out + (size_t)i0 * per, d->d_out, (size_t)m * per, hipMemcpyDeviceToHost, s));
 		HIPCHK(hipMemcpyAsync(status + i0, d->d_status, (size_t)m * 4, hipMemcpyDeviceToHost, s));
@@ -69,6 +71,12 @@ extern "C" int nhw_dec_batch(nhw_dec *d, const uint8_t *nhw, const uint64_t *off
 extern "C" int nhw_dec_batch_scaled(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality)
 {
 	return dec_batch_host(d, nhw, off, n, scale, out, status, quality, "nhw_dec_batch_scaled");
+}
+
+/* the same as grey bytes: file i's T T bytes at out + i * T T, rows in file order */
+extern "C" int nhw_dec_batch_grey(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality)
+{
+	return dec_batch_host(d, nhw, off, n, scale, out, status, quality, "nhw_dec_batch_grey", true);
 }
 
 /* ---------------------------------------------------------------------------------------------- pictures of any size (DESIGN.md sections 11, 13, 14) */

@@ -26,11 +26,13 @@
 /* what a kernel gets of a format: dtype and layout are template parameters, the rest are kernel arguments (six floats and two flags, uniform) */
 struct NhwTensorArgs { float scale[3], bias[3]; int rgb, flip; };
 
-/* NHW_OK and the kernel's view of the format, or NHW_E_ARG with the reason in err */
-inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a, std::string &err)
+/* NHW_OK and the kernel's view of the format, or NHW_E_ARG with the reason in err.  grey: the caller is the grey decode, which
+ * takes NHW_T_GREY and nothing else; every other caller takes BGR and RGB and nothing else */
+inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a, std::string &err, bool grey = false)
 {
 	if (!f) { err = "bad argument"; return NHW_E_ARG; }
-	if (f->dtype < NHW_T_U8 || f->dtype > NHW_T_F32 || (f->layout != NHW_T_HWC && f->layout != NHW_T_CHW) || (f->channels != NHW_T_BGR && f->channels != NHW_T_RGB) ||
+	if (grey && (f->channels == NHW_T_BGR || f->channels == NHW_T_RGB)) { err = "tensor format: a grey decode takes NHW_T_GREY, not NHW_T_BGR or NHW_T_RGB"; return NHW_E_ARG; }
+	if (f->dtype < NHW_T_U8 || f->dtype > NHW_T_F32 || (f->layout != NHW_T_HWC && f->layout != NHW_T_CHW) || (grey ? f->channels != NHW_T_GREY : f->channels != NHW_T_BGR && f->channels != NHW_T_RGB) ||
 	    (f->rows != NHW_T_ROWS_FILE && f->rows != NHW_T_ROWS_REVERSED)) { err = "tensor format: unknown dtype, layout, channels or rows value"; return NHW_E_ARG; }
 	if (f->reserved) { err = "tensor format: the reserved word must be 0"; return NHW_E_ARG; }
 	for (int c = 0; c < 3; c++) {
@@ -134,7 +136,7 @@ template <int DT, int N> __device__ __forceinline__ void nhw_pack_elems(const ui
  * stores: of 4). */
 template <int DT, int CHW> struct NhwStoreTensor {
 	static constexpr int dtype = DT, layout = CHW;
-	static constexpr bool bytes = false;
+	static constexpr bool bytes = false, grey = false;
 	NhwTensorArgs a;
 	template <int S, int N> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
 	{
@@ -169,6 +171,38 @@ template <int DT, int CHW> struct NhwStoreTensor {
 		}
 	}
 };
+
+/* The one-channel store: N = 16 or 8 grey bytes of one row of an S x S picture, columns N c .. N c + N - 1 of byte-path row r of
+ * file img, N / 4 dwords in `w`, under the value rule with scale[0] and bias[0].  With one channel HWC and CHW are the same memory, so the layout is
+ * no parameter.  The thread owns N consecutive elements, N * bytes: 64 (four 16-byte stores), 32, 16 (one) or 8 bytes; consecutive lanes take
+ * consecutive pieces, and every address is a multiple of its store's size when `out` is 16-byte aligned.  `slice` is no part of the format: the
+ * slice of the launch (nhw_host.h) for a kernel that has no argument of its own for it, -1 in production. */
+struct NhwGreyArgs { float scale, bias; int flip, slice; };
+template <int DT> struct NhwStoreGrey {
+	static constexpr int dtype = DT;
+	static constexpr bool bytes = false, grey = true;
+	NhwGreyArgs a;
+	template <int S, int N> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
+	{
+		constexpr int EB = NhwElem<DT>::bytes, K = N * EB / 4;              /* dwords: 16, 8, 4 or 2 */
+		const int rr = a.flip ? S - 1 - r : r;
+		uint32_t e[N], v[K];
+#pragma unroll
+		for (int px = 0; px < N; px++) e[px] = nhw_tensor_elem<DT>((w[px >> 2] >> (8 * (px & 3))) & 0xFFu, a.scale, a.bias);
+		nhw_pack_elems<DT, N>(e, v);
+		nhw_store_words<K, (K > 4 ? 4 : K)>(out + ((size_t)img * S * S + (size_t)rr * S + N * c) * EB, v);
+	}
+};
+/* f(NhwStoreGrey<dtype>{ a }) for a checked format */
+template <class F> inline void nhw_with_grey_store(int dtype, const NhwGreyArgs &a, F &&f)
+{
+	switch (dtype) {
+	case NHW_T_U8: f(NhwStoreGrey<NHW_T_U8>{ a }); break;
+	case NHW_T_F16: f(NhwStoreGrey<NHW_T_F16>{ a }); break;
+	case NHW_T_BF16: f(NhwStoreGrey<NHW_T_BF16>{ a }); break;
+	default: f(NhwStoreGrey<NHW_T_F32>{ a }); break;
+	}
+}
 
 /* ------------------------------------------------------------------------------------------------ the other direction */
 /* the element whose bits are the low bits of e, widened exactly to float: IEEE half with its denormals (v_cvt_f32_f16), bfloat16 as bits << 16 */

@@ -12,6 +12,8 @@
  * without it), anywhere on the line of a single file, --batch or --picture: the half- or quarter-scale picture straight from the wavelet
  * pyramid, under a header that carries the scaled size.  --window S,X,Y,W,H behind --picture <in> <out>: that rectangle
  * of the picture at scale S (1, 2 or 4), in the coordinates of the scaled picture, from the tiles it touches.
+ * --grey <in.nhw> <out.pgm>, with or without --scale: the luma alone through the grey table of the file's quality, as a
+ * binary PGM (P5) with its rows top-down; not with --batch, --tar, --tiles or --picture.
  */
 #include <dirent.h>
 #include <stdint.h>
@@ -55,6 +57,7 @@ static int read_file(const char *path, uint8_t **buf, size_t *len)
 }
 
 static int g_scale = 1;                                               /* --scale */
+static int g_grey = 0;                                                /* --grey */
 
 /* the reference's 54 bytes with the size fields of a width x height picture of `bytes` pixel bytes (rows padded to 4) */
 static void bmp_header_sized(uint8_t hdr[54], uint32_t width, uint32_t height, uint32_t bytes)
@@ -80,6 +83,19 @@ static int write_bmp(const char *path, const uint8_t *pixels)
 	return 0;
 }
 
+/* --grey: "P5", the side twice, 255, then the rows top-down: the byte path's row 0 is the picture's bottom row, so PGM row r is row side - 1 - r */
+static int write_pgm(const char *path, const uint8_t *grey)
+{
+	const uint32_t side = 512u / (uint32_t)g_scale;
+	uint32_t r;
+	FILE *f = fopen(path, "wb");
+	if (!f) { printf("Failed to open output decompressed .pgm file %s\n", path); return 1; }
+	fprintf(f, "P5\n%u %u\n255\n", (unsigned)side, (unsigned)side);
+	for (r = 0; r < side; r++) fwrite(grey + (size_t)(side - 1 - r) * side, side, 1, f);
+	fclose(f);
+	return 0;
+}
+
 static int decode_files(char **in, char **out, int n)
 {
 	nhw_dec *d = NULL;
@@ -98,13 +114,15 @@ static int decode_files(char **in, char **out, int n)
 	off[n] = total;
 	pix = (uint8_t *)malloc((size_t)n * NHW_IMG_BYTES);
 	if (nhw_dec_create(0, n, &d) ||
-	    (g_scale == 1 ? nhw_dec_batch(d, blob, off, n, pix, status, NULL) : nhw_dec_batch_scaled(d, blob, off, n, g_scale, pix, status, NULL))) {
+	    (g_grey ? nhw_dec_batch_grey(d, blob, off, n, g_scale, pix, status, NULL) :
+	     g_scale == 1 ? nhw_dec_batch(d, blob, off, n, pix, status, NULL) : nhw_dec_batch_scaled(d, blob, off, n, g_scale, pix, status, NULL))) {
 		fprintf(stderr, "%s: GPU decoder unavailable: %s\n", PROGRAM, nhw_dec_last_error());
 		return 2;
 	}
 	for (i = 0; i < n; i++) {
 		if (status[i]) { printf("\nNot an .nhw file"); if (n > 1) printf(": %s", in[i]); printf("\n"); rc = 3; continue; }
-		if (write_bmp(out[i], pix + (size_t)i * (NHW_IMG_BYTES / (size_t)(g_scale * g_scale)))) rc = rc ? rc : 1;
+		if (g_grey ? write_pgm(out[i], pix + (size_t)i * (NHW_IMG_BYTES / 3 / (size_t)(g_scale * g_scale)))
+		           : write_bmp(out[i], pix + (size_t)i * (NHW_IMG_BYTES / (size_t)(g_scale * g_scale)))) rc = rc ? rc : 1;
 	}
 	nhw_dec_destroy(d);
 	free(blob); free(pix); free(off); free(status);
@@ -368,6 +386,21 @@ static int decode_tar(const char *in_path, const char *out_path)
 int main(int argc, char **argv)
 {
 	int a;
+	for (a = 1; a < argc; a++)                                        /* --grey: with a single file only (and --scale); checked before any file is touched, then taken off the line */
+		if (!strncmp(argv[a], "--grey", 6)) {
+			int b;
+			if (strcmp(argv[a], "--grey")) { fprintf(stderr, "%s: --grey takes no value: --grey <in.nhw> <out.pgm>\n", PROGRAM); return 1; }
+			for (b = 1; b < argc; b++)
+				if (!strcmp(argv[b], "--batch") || !strcmp(argv[b], "--tar") || !strcmp(argv[b], "--tiles") || !strcmp(argv[b], "--picture") ||
+				    !strncmp(argv[b], "--region", 8) || !strncmp(argv[b], "--window", 8)) {
+					fprintf(stderr, "%s: --grey goes with a single file (and --scale): not with %s\n", PROGRAM, argv[b]);
+					return 1;
+				}
+			g_grey = 1;
+			for (b = a; b + 1 < argc; b++) argv[b] = argv[b + 1];
+			argc -= 1;
+			break;
+		}
 	for (a = 1; a < argc; a++)                                        /* --window: behind --picture <in> <out> only, without --scale or --region; checked before any file is touched */
 		if (!strncmp(argv[a], "--window", 8)) {
 			uint32_t win[5];
@@ -395,6 +428,7 @@ int main(int argc, char **argv)
 			if (argc != 6 || parse_region(argv[5], reg)) { fprintf(stderr, "%s: --region wants X,Y,W,H: four decimal numbers\n", PROGRAM); return 1; }
 			return decode_picture(argv[2], argv[3], reg, NULL);
 		}
+	if (g_grey && argc != 3) { fprintf(stderr, "%s: --grey wants <in.nhw> <out.pgm>\n", PROGRAM); return 1; }
 	if (argc < 3) { show_usage(); return 0; }
 	if (!strcmp(argv[1], "--tar")) {
 		if (argc < 4) { show_usage(); return 1; }
