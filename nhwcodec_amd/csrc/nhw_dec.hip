@@ -26,6 +26,7 @@
 #include <assert.h>
 
 #include "nhw_dec.h"
+#include "nhw_dec_plan.h"
 #include "nhw_dwt.h"
 #include "nhw_grey.h"
 #include "nhw_tensor.h"
@@ -2553,181 +2554,153 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
 	return NHW_OK;
 }
 
-/* one batch at scale 1 (the whole decode), 2 or 4: what the two entry points below share */
-struct TensorStore { int dtype, layout; NhwTensorArgs a; };         /* a checked format other than the byte path's */
-struct GreyStore { int dtype; NhwGreyArgs a; };                      /* a checked grey format */
-/* the grey forms of the scaled kernel: the file's T / SC_ROWS bands side by side, or a band a launch under a forced slice order */
-template <int S> static void launch_scaled_grey(const DecWs &ws, int n, const GreyStore &g, uint8_t *out, hipStream_t s)
+/* ---------------------------------------------------------------------------------------------- one batch: check, plan, run
+ * What the last kernel stores: the byte path's pixels, a checked tensor format other than those, or a checked grey
+ * format (section 22) -- the kind and that kind's arguments. */
+enum { STORE_BYTES, STORE_TENSOR, STORE_GREY };
+struct DecStore { int kind, dtype, layout; NhwTensorArgs t; NhwGreyArgs g; };
+/* f(the store policy object): StoreBytes{}, NhwStoreTensor<...>{ t } or NhwStoreGrey<...>{ g with `slice` } */
+template <class F> static void dec_with_store(const DecStore &o, int slice, F &&f)
+{
+	if (o.kind == STORE_GREY) { NhwGreyArgs a = o.g; a.slice = slice; nhw_with_grey_store(o.dtype, a, f); }
+	else if (o.kind == STORE_TENSOR) nhw_with_tensor_store(o.dtype, o.layout, o.t, f);
+	else f(StoreBytes{});
+}
+/* the scaled kernel: unsliced for the colour forms; the grey form has the file's T / SC_ROWS bands side by side, or a band a launch under a forced
+ * slice order, the band in its store's arguments */
+template <int S> static void launch_scaled(const DecWs &ws, int n, const DecStore &o, uint8_t *out, hipStream_t s)
 {
 	constexpr int NB = DW / S / SC_ROWS;
-	nhw_slices(NB, [&](int sl) {
-		NhwGreyArgs a = g.a;
-		a.slice = sl;
-		nhw_with_grey_store(g.dtype, a, [&](auto st) { k_dec_scaled<S, decltype(st)><<<sl < 0 ? NB * n : n, 256, 0, s>>>(ws, out, st.a); });
+	auto launch = [&](int sl) {
+		dec_with_store(o, sl, [&](auto st) {
+			using ST = decltype(st);
+			if constexpr (ST::bytes) k_dec_scaled<S><<<NB * n, 256, 0, s>>>(ws, out);
+			else k_dec_scaled<S, ST><<<sl < 0 ? NB * n : n, 256, 0, s>>>(ws, out, st.a);
+		});
+	};
+	if (o.kind == STORE_GREY) nhw_slices(NB, launch); else launch(-1);
+}
+/* the last kernel of a batch at `scale` with the call's store.  Scale 1: level-1 synthesis both ways + corrections + smoothing + colour, one kernel,
+ * one band of FR output rows per workgroup -- every store under the same launch plan, the grey form with its own LDS */
+static void launch_last(const DecWs &ws, int n, int scale, const DecStore &o, uint8_t *out, hipStream_t s)
+{
+	if (scale == 2) return launch_scaled<2>(ws, n, o, out, s);
+	if (scale == 4) return launch_scaled<4>(ws, n, o, out, s);
+	int dev_stop = 0;
+#ifdef NHW_DEV
+	if (const char *e = getenv("NHW_FINAL_STOP")) dev_stop = atoi(e);
+#endif
+	nhw_slices(DW / FR, [&](int sl) {
+		dec_with_store(o, -1, [&](auto st) {
+			using ST = decltype(st);
+			const int grid = sl < 0 ? (DW / FR) * n : n;
+			if constexpr (ST::bytes) k_dec_final<ST><<<grid, 256, F_LDS_BYTES, s>>>(ws, out, dev_stop, sl);
+			else k_dec_final<ST><<<grid, 256, ST::grey ? F_GREY_LDS_BYTES : F_LDS_BYTES, s>>>(ws, out, dev_stop, sl, st.a);
+		});
 	});
 }
-/* With `grey` the plan is the grey one: the entropy stages, the expansion, the luma's kernels and the grey form of the last kernel -- no k_dec_chroma,
- * no k_dec_sharpen, no chroma stream; behind the prefix-code walk nothing reads the chroma value list, and nothing reads or writes D_CA or D_CU. */
-static int dec_batch(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_bgr, int32_t *d_status,
-                     int32_t *d_quality, void *stream, const TensorStore *tensor = nullptr /* the last kernel stores this format */,
-                     const GreyStore *grey = nullptr)
+
+/* What the four entries refuse, in the order they always have, and the store of a call that passes.  A format's entry checks the format, then the
+ * 16-byte alignment its stores need, then that the handle has no debug stop, and only then what every entry checks: the arguments, the scale, and
+ * for a scaled decode the debug stop and the 8-byte alignment. */
+enum { ENTRY_BYTES, ENTRY_TENSOR, ENTRY_GREY };
+static int dec_check(int entry, const nhw_tensor_format *fmt, const nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                     const void *d_out, const int32_t *d_status, DecStore *o)
 {
-	if (!d || !d_nhw || !d_off || !d_len || !d_bgr || !d_status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	*o = { STORE_BYTES, NHW_T_U8, NHW_T_HWC, {}, { 1.0f, 0.0f, 0, -1 } };
+	if (entry == ENTRY_TENSOR) {
+		if (const int rc = nhw_tensor_format_check(fmt, &o->t, nhw_dec_err)) return rc;
+		if (!nhw_tensor_format_is_bytes(fmt)) { o->kind = STORE_TENSOR; o->dtype = fmt->dtype; o->layout = fmt->layout; }
+	}
+	if (entry == ENTRY_GREY) {                                      /* without a format: bytes in file order */
+		o->kind = STORE_GREY;
+		if (fmt) {
+			NhwTensorArgs a;
+			if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_dec_err, true)) return rc;
+			o->dtype = fmt->dtype; o->g.scale = a.scale[0]; o->g.bias = a.bias[0]; o->g.flip = a.flip;
+		}
+	}
+	if (entry != ENTRY_BYTES) {
+		const std::string who = entry == ENTRY_TENSOR ? "a tensor decode" : "a grey decode";
+		if ((uintptr_t)d_out & 15) { nhw_dec_err = who + "'s output must be 16-byte aligned"; return NHW_E_ARG; }
+		if (d && d->stop_after) { nhw_dec_err = who + " has no debug stops: the handle has one set"; return NHW_E_ARG; }
+	}
+	if (!d || !d_nhw || !d_off || !d_len || !d_out || !d_status || n < 1 || n > d->max_batch) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (scale != 1 && scale != 2 && scale != 4) { nhw_dec_err = "the scale must be 1, 2 or 4"; return NHW_E_ARG; }
 	if (scale != 1 && d->stop_after) { nhw_dec_err = "a scaled decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
-	if (scale != 1 && ((uintptr_t)d_bgr & 7)) { nhw_dec_err = "a scaled decode's output must be 8-byte aligned"; return NHW_E_ARG; }
+	if (scale != 1 && ((uintptr_t)d_out & 7)) { nhw_dec_err = "a scaled decode's output must be 8-byte aligned"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+/* one batch at scale 1 (the whole decode), 2 or 4: the steps of its plan (nhw_dec_plan.h), one after the other */
+static int dec_batch(int entry, const nhw_tensor_format *fmt, nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                     void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	DecStore o;
+	if (const int rc = dec_check(entry, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, &o)) return rc;
+	const DecPlan plan = dec_plan(scale, o.kind == STORE_GREY, d->stop_after, d->chroma_fork);
+	if (!plan.n) { nhw_dec_err = "the debug stop set on the handle is none of 0 .. 11"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(d->device));                              /* the handle's device, whatever the calling thread had current */
-	hipStream_t s = stream ? (hipStream_t)stream : d->own_stream;
+	const hipStream_t s = stream ? (hipStream_t)stream : d->own_stream;
 	const NhwSliceScope slices(d->slice_order);
 	DecWs ws = dec_ws(d->ws_base, d->max_batch);
 	ws.n = n; ws.blob = (const uint8_t *)d_nhw; ws.blob_off = d_off; ws.blob_len = d_len; ws.dense = d->stop_after != 0;
-	int stage = 0;
 	d->timed = false;
 	d->l1_moved = false;
-	const bool fork = (d->chroma_fork & 2) && !d->stop_after && scale == 1 && !grey;   /* the chroma sequence beside the luma one (a scaled decode keeps it in line) */
-	const bool fork_e = (d->chroma_fork & 1) && !d->stop_after;        /* the two entropy branches side by side */
-	hipStream_t cs = fork ? d->chroma_stream : s;
-	hipStream_t es = fork_e ? d->chroma_stream : s;
-	const bool fork_late = (d->chroma_fork & 4) && !fork && !d->stop_after && !grey;   /* the chroma sequence beside the smooth-edge marks only: behind the luma's level 2 */
-#define STAGE_END() do { if (d->stop_after && ++stage >= d->stop_after) goto done; } while (0)
-#define EV(i) HIPCHK(hipEventRecord(d->ev[i], s))
-	EV(0);
-	/* Two entropy branches that only meet at the expansion: the side streams (LL2 DPCM, position lists; latency-bound scans) on the caller's
-	 * stream, the prefix-code walk and the un-zig-zag on the second one. */
-	if (fork_e) { HIPCHK(hipEventRecord(d->fork_ev, s)); HIPCHK(hipStreamWaitEvent(es, d->fork_ev, 0)); }
-	nhw_slices(4, [&](int sl) { k_dec_parse<<<sl < 0 ? 4 * n : n, 64, 0, s>>>(ws, sl); });
-	STAGE_END();                                                                  /* 1 */
-	nhw_slices(2, [&](int sl) { k_dec_vlc<<<sl < 0 ? 2 * n : n, 64, 0, es>>>(ws, d->vlc_table, sl); });
-	if (fork_e) { HIPCHK(hipEventRecord(d->join_ev, es)); HIPCHK(hipStreamWaitEvent(s, d->join_ev, 0)); }
-	if (fork) { HIPCHK(hipEventRecord(d->fork_ev, s)); HIPCHK(hipStreamWaitEvent(cs, d->fork_ev, 0)); }   /* chroma goes on once both branches are in */
-	k_dec_verdict<<<(n + 255) / 256, 256, 0, s>>>(ws);
-	EV(1);
-	STAGE_END();                                                                  /* 2 */
-	/* From here the luma and the chroma sequences share nothing until the colour kernel: chroma goes to a stream of its own.  With the debug
-	 * stop it stays in line. */
-#define CHROMA(UPTO, STREAM) k_dec_chroma<<<2 * n < SYNTH_WGS ? 2 * n : SYNTH_WGS, 1024, 256 * 258 * sizeof(int16_t), STREAM>>>(ws, 2 * n, UPTO)
-	k_dec_expand<<<(n + 3) / 4, 256, 0, s>>>(ws);
-	if (scale == 4) {                                                             /* quarter scale: the level-2 LL is in plane A already; the chroma planes up to their corrections */
-		if (!grey) CHROMA(5, s);
-		EV(2);
-		if (grey) launch_scaled_grey<4>(ws, n, *grey, (uint8_t *)d_bgr, s);
-		else if (!tensor) k_dec_scaled<4><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
-		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) { k_dec_scaled<4, decltype(st)><<<(DW / 4 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr, st.a); });
-		EV(3);
-		d->timed = true;
-		goto done;
-	}
-	if (fork) {
-		CHROMA(4, cs);
-		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, cs>>>(ws);
-		HIPCHK(hipEventRecord(d->join_ev, cs));
-	}
-	else if (d->stop_after == 3) CHROMA(1, s);                                    /* the chroma planes as the expansion leaves them */
-	STAGE_END();                                                                  /* 3 */
-	{
-		/* level 2 of the luma: shrink, synthesis, residual lists on A's top-left 256 x 256 -> the level-1 LL in plane_l1; the debug stops 4 and 5 end it earlier */
-		const auto l2q = d->stop_after == 4 ? k_dec_luma_l2q<1> : d->stop_after == 5 ? k_dec_luma_l2q<2> : k_dec_luma_l2q<3>;
-		nhw_slices(4, [&](int sl) { l2q<<<sl < 0 ? 4 * ((n + 7) & ~7) : n, 256, 0, s>>>(ws, n, sl); });
-		d->l1_moved = true;
-	}
-	STAGE_END();                                                                  /* 4 (the block as the shrink leaves it) */
-	STAGE_END();                                                                  /* 5 (after the synthesis) */
-	STAGE_END();                                                                  /* 6 */
-	if (scale == 2) {                                                             /* half scale: the level-1 LL and the whole chroma sequence, in line; no marks, no level 1 of the luma */
-		if (!grey) {
-			CHROMA(4, s);
-			k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, s>>>(ws);
+	for (int i = 0; i < plan.n; i++) {
+		const DecStep &st = plan.step[i];
+		const hipStream_t q = st.side ? d->chroma_stream : s;
+		switch (st.op) {
+		case DEC_STAMP: HIPCHK(hipEventRecord(d->ev[st.arg], q)); break;
+		case DEC_FORK: HIPCHK(hipEventRecord(d->fork_ev, q)); HIPCHK(hipStreamWaitEvent(d->chroma_stream, d->fork_ev, 0)); break;
+		case DEC_JOIN_RECORD: HIPCHK(hipEventRecord(d->join_ev, q)); break;
+		case DEC_JOIN_WAIT: HIPCHK(hipStreamWaitEvent(q, d->join_ev, 0)); break;
+		case DEC_PARSE: nhw_slices(4, [&](int sl) { k_dec_parse<<<sl < 0 ? 4 * n : n, 64, 0, q>>>(ws, sl); }); break;
+		case DEC_VLC: nhw_slices(2, [&](int sl) { k_dec_vlc<<<sl < 0 ? 2 * n : n, 64, 0, q>>>(ws, d->vlc_table, sl); }); break;
+		case DEC_VERDICT: k_dec_verdict<<<(n + 255) / 256, 256, 0, q>>>(ws); break;
+		case DEC_EXPAND: k_dec_expand<<<(n + 3) / 4, 256, 0, q>>>(ws); break;
+		case DEC_CHROMA: k_dec_chroma<<<2 * n < SYNTH_WGS ? 2 * n : SYNTH_WGS, 1024, 256 * 258 * sizeof(int16_t), q>>>(ws, 2 * n, st.arg); break;
+		case DEC_SHARPEN: k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, q>>>(ws); break;
+		case DEC_L2Q: {                                              /* shrink, synthesis, residual lists on A's top-left 256 x 256 -> the level-1 LL in plane_l1 */
+			const auto l2q = st.arg == 1 ? k_dec_luma_l2q<1> : st.arg == 2 ? k_dec_luma_l2q<2> : k_dec_luma_l2q<3>;
+			nhw_slices(4, [&](int sl) { l2q<<<sl < 0 ? 4 * ((n + 7) & ~7) : n, 256, 0, q>>>(ws, n, sl); });
+			break;
 		}
-		EV(2);
-		if (grey) launch_scaled_grey<2>(ws, n, *grey, (uint8_t *)d_bgr, s);
-		else if (!tensor) k_dec_scaled<2><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr);
-		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) { k_dec_scaled<2, decltype(st)><<<(DW / 2 / SC_ROWS) * n, 256, 0, s>>>(ws, (uint8_t *)d_bgr, st.a); });
-		EV(3);
-		d->timed = true;
-		goto done;
+		case DEC_MARKS: k_dec_marks<<<(n + 3) / 4, 256, 0, q>>>(ws); break;
+		case DEC_MARKS_FAR: k_dec_marks_far<<<(n + 3) / 4, 256, 0, q>>>(ws); break;
+		case DEC_LAST: launch_last(ws, n, st.arg, o, (uint8_t *)d_out, q); break;
+		case DEC_STATUS: k_dec_status<<<(n + 255) / 256, 256, 0, q>>>(ws, d_status, d_quality); HIPCHK(hipGetLastError()); break;
+		}
 	}
-	if (fork_late) {
-		HIPCHK(hipEventRecord(d->fork_ev, s)); HIPCHK(hipStreamWaitEvent(d->chroma_stream, d->fork_ev, 0));
-		CHROMA(4, d->chroma_stream);
-		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, d->chroma_stream>>>(ws);
-		HIPCHK(hipEventRecord(d->join_ev, d->chroma_stream));
-	}
-	k_dec_marks<<<(n + 3) / 4, 256, 0, s>>>(ws);
-	k_dec_marks_far<<<(n + 3) / 4, 256, 0, s>>>(ws);                              /* (ends at once for every file but one whose level-1 LL leaves -5999 .. 10000) */
-	STAGE_END();                                                                  /* 7 */
-	if (fork || fork_late) HIPCHK(hipStreamWaitEvent(s, d->join_ev, 0));
-	else if (!grey) {
-		CHROMA(d->stop_after == 8 ? 2 : d->stop_after == 9 ? 3 : 4, s);
-		STAGE_END();                                                              /* 8 (after level 2) */
-		STAGE_END();                                                              /* 9 (after the corrections) */
-		STAGE_END();                                                              /* 10 */
-		k_dec_sharpen<<<(2 * n + 3) / 4, 256, 0, s>>>(ws);
-		STAGE_END();                                                              /* 11 */
-	}
-	/* level-1 synthesis both ways + corrections + smoothing + colour: one kernel, one band of FR output rows per workgroup */
-	EV(2);
-	{
-		int dev_stop = 0;
-#ifdef NHW_DEV
-		if (const char *e = getenv("NHW_FINAL_STOP")) dev_stop = atoi(e);
-#endif
-		if (grey) nhw_with_grey_store(grey->dtype, grey->a, [&](auto st) {                    /* the same launch plan, the grey form's LDS */
-			nhw_slices(DW / FR, [&](int sl) { k_dec_final<decltype(st)><<<sl < 0 ? (DW / FR) * n : n, 256, F_GREY_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl, st.a); });
-		});
-		else if (!tensor) nhw_slices(DW / FR, [&](int sl) { k_dec_final<StoreBytes><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl); });
-		else nhw_with_tensor_store(tensor->dtype, tensor->layout, tensor->a, [&](auto st) {     /* the same launch plan, the same LDS */
-			nhw_slices(DW / FR, [&](int sl) { k_dec_final<decltype(st)><<<sl < 0 ? (DW / FR) * n : n, 256, F_LDS_BYTES, s>>>(ws, (uint8_t *)d_bgr, dev_stop, sl, st.a); });
-		});
-	}
-	EV(3);
-	d->timed = true;
-done:
-	k_dec_status<<<(n + 255) / 256, 256, 0, s>>>(ws, d_status, d_quality);
-	HIPCHK(hipGetLastError());
+	d->timed = plan.timed;
+	d->l1_moved = plan.l1_moved;
 	return NHW_OK;
-#undef STAGE_END
-#undef EV
-#undef CHROMA
 }
 
 extern "C" int nhw_dec_batch_device(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, void *d_bgr, int32_t *d_status,
                                     int32_t *d_quality, void *stream)
 {
-	return dec_batch(d, d_nhw, d_off, d_len, n, 1, d_bgr, d_status, d_quality, stream);
+	return dec_batch(ENTRY_BYTES, nullptr, d, d_nhw, d_off, d_len, n, 1, d_bgr, d_status, d_quality, stream);
 }
 
 extern "C" int nhw_dec_batch_device_scaled(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale, void *d_out,
                                            int32_t *d_status, int32_t *d_quality, void *stream)
 {
-	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
+	return dec_batch(ENTRY_BYTES, nullptr, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
 }
 
 /* a batch into a tensor format: the byte path's launches, the last kernel with the format's store */
 extern "C" int nhw_dec_batch_device_tensor(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
                                            const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
 {
-	TensorStore t;
-	if (const int rc = nhw_tensor_format_check(fmt, &t.a, nhw_dec_err)) return rc;
-	if ((uintptr_t)d_out & 15) { nhw_dec_err = "a tensor decode's output must be 16-byte aligned"; return NHW_E_ARG; }
-	if (d && d->stop_after) { nhw_dec_err = "a tensor decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
-	if (nhw_tensor_format_is_bytes(fmt)) return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
-	t.dtype = fmt->dtype; t.layout = fmt->layout;
-	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, &t);
+	return dec_batch(ENTRY_TENSOR, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
 }
 
-/* a batch as grey: the grey plan of dec_batch; without a format, bytes in file order */
+/* a batch as grey: the grey plan; without a format, bytes in file order */
 extern "C" int nhw_dec_batch_device_grey(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
                                          const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
 {
-	GreyStore g = { NHW_T_U8, { 1.0f, 0.0f, 0, -1 } };
-	if (fmt) {
-		NhwTensorArgs a;
-		if (const int rc = nhw_tensor_format_check(fmt, &a, nhw_dec_err, true)) return rc;
-		g.dtype = fmt->dtype; g.a.scale = a.scale[0]; g.a.bias = a.bias[0]; g.a.flip = a.flip;
-	}
-	if ((uintptr_t)d_out & 15) { nhw_dec_err = "a grey decode's output must be 16-byte aligned"; return NHW_E_ARG; }
-	if (d && d->stop_after) { nhw_dec_err = "a grey decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
-	return dec_batch(d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, nullptr, &g);
+	return dec_batch(ENTRY_GREY, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
 }
 
 /* host only: no handle, no GPU call */
