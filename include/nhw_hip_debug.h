@@ -45,14 +45,20 @@ int nhw_dec_debug_slice_order(nhw_dec *d, int mode);
 int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, void *stream);
 int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes);
 /* The luma plane's first closed loop for the first n images of the handle's last whole batch, at that batch's quality (7 .. 23), on B_JPEG, B_PROC,
- * B_LL1 and B_L2SAVE as they stand.  form 0: the production launches from the first level-2 analysis to the second; form 1: their last part
+ * B_LL1 and B_L2SAVE as they stand.  form 0: the production kernels from the first level-2 analysis to the second; form 1: their last part
  * alone (synthesis, Y8, Y9 and, for q > 12 on the same LDS residency, the second analysis with Y13's copy); form 2: the staged kernels for
- * form 1's part; form 3: the staged kernels for form 0's part; form 4: form 3 stopped behind the synthesis; form 5: the staged synthesis alone. */
+ * form 1's part; form 3: the staged kernels for form 0's part; form 4: form 3 stopped behind the synthesis; form 5: the staged synthesis alone.
+ * Forms 0 and 1 are the production kernels with every plane stored, so that they can be compared with the staged ones cell by cell.  A batch
+ * (outside the compatibility mode and without a debug stop) leaves out the stores of the level-2 block that nothing behind them reads, listed in
+ * the transposed first-direction plane of both analyses in B_JPEG, and rows 128 .. 255 of the second analysis' block in B_PROC.
+ * forms 6, 7: forms 0, 1 as a batch launches them, without those stores (not in the compatibility mode): the cells keep what stood there. */
 int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream);
 /* The LL2 bump walk of the luma plane's second closed loop for the first n images of the handle's last whole batch, at that batch's quality
  * (13 .. 23), on B_PROC, B_JPEG and B_L2SAVE as they stand: the LL2 emission, the LL coder and the second dequantiser simulation on one stream.
  * form 0: the forked order's kernels (the emission makes the walk for both, the simulation skips it); form 1: the in-line order's (each makes
- * it); forms 2, 3: the same two with the verbatim samples put back by the level-2 synthesis, which then follows. */
+ * it); forms 2, 3: the same two with the verbatim samples put back by the level-2 synthesis, which then follows.  These are the kernels of a
+ * batch as they are: between them they write every cell of the level-2 block of B_JPEG (which is why a batch does not store the block in front
+ * of them, see nhw_stage_luma_loop), and they read of B_PROC only rows 0 .. 127 of the block. */
 int nhw_stage_ll2_walk(nhw_enc *e, int n, int form, void *stream);
 /* The luma quantiser for the first n images of the handle's last whole batch, at that batch's quality (17 .. 23), on B_L2SAVE, B_PROC and the other
  * planes as they stand.  form 0: the second dequantiser simulation, which leaves the level-2 details behind the quantiser's loops 2 and 3 in

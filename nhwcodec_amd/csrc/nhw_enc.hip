@@ -191,14 +191,21 @@ static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hi
 
 /* the luma plane's launches from the first level-2 analysis to the second, on stream s (run_batch; nhw_stage_luma_loop).  1 = carry on;
  * NHW_OK: the debug stop fell in here */
-static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage, bool y5_beside = false /* run_batch's forked order */)
+static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage, bool y5_beside = false /* run_batch's forked order */,
+                              bool lean = false /* run_batch without a debug stop, outside the compatibility mode: the stores of the level-2 block that nothing reads are left out (below; k_l2_recon) */)
 {
 	const int q = ws.q;
 	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC), ll1 = ws.plane<int16_t>(B_LL1), l2save = ws.plane<int16_t>(B_L2SAVE);
 	const NhwAnalysis l2{ jpeg, proc, n, W, H, 1 };
+	assert(!lean || (!ws.dbg && !ws.compat));
 	/* Y4: level-2 analysis (:139).  The LL rows come from ll1 (the front's copy of them in natural orientation, res256): outside the stage checks the front
-	 * does not write them into the work plane as well, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane) */
-	nhw_launch_analysis(l2.from(ll1, H), s);
+	 * does not write them into the work plane as well, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane).
+	 * lean, q > 6: the transposed first-direction plane is not stored.  The first dequantiser simulation, the next kernel that touches the block of
+	 * jpeg, writes every cell of it (wave_ll2 the LL2 quadrant, wave_dequant_details the rest: the case list there) in front of its one reader,
+	 * k_l2_recon; Y5 reads proc and ll1.  (Below q7 there is no simulation and the plane stays.) */
+	NhwAnalysis first = l2.from(ll1, H);
+	if (lean && q > 6) first.store = ANA_STORE_NO_T;
+	nhw_launch_analysis(first, s);
 	STAGE_DONE();
 	if (q > 6) {                                                     /* first closed loop (:141-283) */
 	/* Y5 and the first dequantiser simulation need nothing of each other, and the first kernel that needs both is k_l2_recon (Y8 reads Y5's
@@ -222,7 +229,7 @@ static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s,
 	STAGE_DONE();
 	nhw_launch_phase(PH_L2, ws, 0, s);
 	STAGE_DONE();
-	} else nhw_launch_l2_recon(jpeg, proc, ll1, q > 12 ? l2save : Plane<int16_t>{}, n, s);   /* synthesis + Y8 + Y9 on one residency of the block (the stage checks take the three kernels); q > 12: + the second analysis and Y13 (:623-631), still on that residency */
+	} else nhw_launch_l2_recon(jpeg, proc, ll1, q > 12 ? l2save : Plane<int16_t>{}, n, s, lean && q > 12);   /* synthesis + Y8 + Y9 on one residency of the block (the stage checks take the three kernels); q > 12: + the second analysis and Y13 (:623-631), still on that residency */
 	if (q <= 12) nhw_launch_analysis(l2, s);                         /* (Y11 / Y12 follow, and Y13's copy behind them) */
 	else if (ws.dbg) nhw_launch_analysis(l2.saving(l2save, H, ANA_SAVE_BLOCK), s);   /* + Y13: copy of the coefficient block */
 	STAGE_DONE();
@@ -301,7 +308,7 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 		CHROMA(chroma_head(0));
 		CHROMA(chroma_head(1));                                      /* V's head in planes of its own, right behind U's: U's quantiser waits for the luma tail, and this stream stood idle until then (2 ms of a q20 step).  (Measured and not taken: V's head on a stream of its own beside U's, +0.3 ms; V's head held back until the second dequantiser simulation is through, +0.4 ms.) */
 	}
-	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage, fork && e->y5_fork); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12) */
+	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage, fork && e->y5_fork, !ws.dbg && !ws.compat); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12), every order of this function: forked, in line, a sub-batch's view */
 	if (q <= 12) {                                                   /* Y11 (q <= 11), Y12, then Y13 */
 		nhw_launch_low_ll2(proc, q, n, s);
 		nhw_launch_copy_block(proc, W, ws.plane<int16_t>(B_L2SAVE), H, H, H, n, s);
@@ -630,14 +637,17 @@ extern "C" int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, voi
 
 /* A test hook for the luma plane's first closed loop, on B_JPEG, B_PROC, B_LL1 and B_L2SAVE as they stand (a test writes them: nhw_debug_write), for
  * the first n images of the handle's last whole batch at that batch's quality (7 .. 23: below it there is no first closed loop).
- *   form 0: the production launches from the first level-2 analysis to the second (luma_loop_launches);
- *   form 1: their last part alone, from the synthesis on: k_l2_recon<true> for q > 12, k_l2_recon<false> and the analysis below it;
+ *   form 0: the production kernels from the first level-2 analysis to the second (luma_loop_launches), every plane stored;
+ *   form 1: their last part alone, from the synthesis on: k_l2_recon<true> for q > 12, k_l2_recon<false> and the analysis below it, every plane stored;
+ *   forms 6, 7: forms 0, 1 as run_batch launches them outside the compatibility mode, without the stores of the level-2 block that nothing in a
+ *           batch reads: the first analysis' transposed plane, and for q > 12 the fused kernel's transposed plane and rows 128 .. 255 of
+ *           its block of the work plane.  What those cells hold behind these forms is what stood there (form 6: the first simulation's plane in B_JPEG);
  *   form 2: the staged kernels for form 1's part (synthesis, Y8 + Y9, analysis + Y13's copy), every plane stored;
  *   form 3: the staged kernels for form 0's part; form 4: the same, stopped behind the synthesis (proc = the reconstruction before Y8's nudges,
  *           B_LL1 with Y5's tags); form 5: the staged synthesis alone. */
 extern "C" int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream)
 {
-	if (!e || n < 1 || n > e->max_batch || form < 0 || form > 5) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e || n < 1 || n > e->max_batch || form < 0 || form > 7) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
 	if (!e->timed || n > e->last_n || e->stop_after || e->last_q < 7) {
 		nhw_enc_err = "nhw_stage_luma_loop: needs a completed whole batch of >= n images at quality >= 7 and no debug stop";
 		return NHW_E_ARG;
@@ -650,12 +660,14 @@ extern "C" int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream)
 	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC), ll1 = ws.plane<int16_t>(B_LL1), l2save = ws.plane<int16_t>(B_L2SAVE);
 	const NhwAnalysis l2{ jpeg, proc, n, W, H, 1 };
 	const bool save = ws.q > 12;
-	if (form == 0) {
+	const bool lean = form >= 6;
+	if (lean && ws.compat) { nhw_enc_err = "nhw_stage_luma_loop: forms 6 and 7 are not launched in the compatibility mode"; return NHW_E_ARG; }
+	if (form == 0 || form == 6) {
 		int stage = 0;
-		const int rc = luma_loop_launches(e, ws, n, s, stage);
+		const int rc = luma_loop_launches(e, ws, n, s, stage, false, lean);
 		if (rc != 1) return rc;
-	} else if (form == 1) {
-		nhw_launch_l2_recon(jpeg, proc, ll1, save ? l2save : Plane<int16_t>{}, n, s);
+	} else if (form == 1 || form == 7) {
+		nhw_launch_l2_recon(jpeg, proc, ll1, save ? l2save : Plane<int16_t>{}, n, s, lean && save);
 		if (!save) nhw_launch_analysis(l2, s);
 	} else {
 		if (form == 3 || form == 4) {

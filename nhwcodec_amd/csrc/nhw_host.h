@@ -93,7 +93,7 @@ void nhw_launch_pack_chroma(const NhwWs &ws, hipStream_t s);   /* Z2, the chroma
 void nhw_launch_final(const NhwWs &ws, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s, bool chroma_packed = false);   /* Z2 + the container; chroma_packed: nhw_launch_pack_chroma has run on these images (otherwise it is launched here, in front) */
 void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s, bool one_walk = false /* WV_EMIT and WV_DQ0 of one batch alike, quality > 12, production: the emission leaves the LL2 cells of the second simulation, which skips its walk (wave_emit_ll2) */,
                      bool marks = false /* WV_DQ0 and WV_QUANT of one batch alike, quality > 16, production: the simulation hands the quantiser the level-2 details behind its loops 2 and 3 (wave_dequant_details) */);
-void nhw_launch_l2_recon(Plane<int16_t> jpeg, Plane<int16_t> proc, Plane<int16_t> ll1, Plane<int16_t> l2save /* or empty */, int n, hipStream_t s);
+void nhw_launch_l2_recon(Plane<int16_t> jpeg, Plane<int16_t> proc, Plane<int16_t> ll1, Plane<int16_t> l2save /* or empty */, int n, hipStream_t s, bool lean = false /* production, with l2save: without the stores nothing reads (k_l2_recon) */);
 void nhw_launch_chroma_loops(Plane<int16_t> cproc, Plane<int16_t> cll1, Plane<int16_t> cl2save, Plane<const uint8_t> pu, int q, int comp, int compat, int n, hipStream_t s);   /* both chroma closed loops of one component, from cll1 */
 void nhw_launch_copy_block(Plane<const int16_t> src, int src_row, Plane<int16_t> dst, int dst_row, int rows, int cols, int n, hipStream_t s);
 int nhw_tail_set_attrs(const char **where);

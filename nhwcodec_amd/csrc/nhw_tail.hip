@@ -157,9 +157,14 @@ void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s, bool one_walk, bool
  *     (jpeg[i * stride + j]: k_dwt_ana gathers it): a straight row copy.  The second direction runs along rows of A, and output row c is row
  *     c of proc and of l2save.  A wavefront takes its own 16 rows through all three steps (copy, filter in place, copy), two rows at a
  *     time: no further barrier, and every global store is 16 bytes a lane on whole 512-byte rows;
- *   * the block of the work plane is still stored: wave_dequant_sim_luma writes only some cells of it.
+ *   * LEAN (run_batch outside the compatibility mode; the stage hooks keep every store) leaves out what nothing reads.  The transposed
+ *     first-direction plane in the block of jpeg: the next kernels that touch the block are the LL2 emission and the second dequantiser
+ *     simulation, which between them write every cell of it before wave_shrink and k_dwt_syn read it (the case list at wave_dequant_details).
+ *     Rows 128 .. 255 of the block of the work plane: the LL2 emission (wave_emit_ll2: ll2_load_row takes rows 0 .. 127, columns 0 .. 191) is
+ *     the one reader of the block -- the second simulation, k_phase<PH_L4C> and the quantiser take it from l2save, the put-backs of verbatim
+ *     samples read LL2 cells the emission or the simulation's walk has just written -- and k_dwt_syn behind the simulation rewrites all of it.
  * The arithmetic is ana_row_taps' and ana_col_pair's (nhw_dwt.h), as in k_dwt_ana. */
-template <bool ANA>
+template <bool ANA, bool LEAN = false>
 __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, int16_t *__restrict__ procb, size_t plane_stride, int16_t *__restrict__ ll1b, size_t ll1_stride, int n,
                                                    int16_t *__restrict__ saveb, size_t save_stride)
 {
@@ -295,7 +300,7 @@ __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, 
 			for (int i = 0; i < 8; i++) {                          /* my rows c, c + 1 = two columns of the first-direction plane (filters.c:88-287) */
 				const int c = r0 + 2 * i;
 				const uint32_t *g = reinterpret_cast<const uint32_t *>(A + (c + rr) * LS + 8 * c8);
-				*reinterpret_cast<uint4 *>(jp + (size_t)(c + rr) * W + 8 * c8) = make_uint4(g[0], g[1], g[2], g[3]);
+				if (!LEAN) *reinterpret_cast<uint4 *>(jp + (size_t)(c + rr) * W + 8 * c8) = make_uint4(g[0], g[1], g[2], g[3]);
 				uint32_t Ew[PPL], Ow[PPL];
 				int lo[PPL][2], hi[PPL][2];
 #pragma unroll
@@ -313,17 +318,18 @@ __global__ __launch_bounds__(1024) void k_l2_recon(int16_t *__restrict__ jpegb, 
 				}
 				asm volatile("" ::: "memory");
 				const uint4 w = make_uint4(g[0], g[1], g[2], g[3]);   /* rows c, c + 1 of the coefficient block (written by this wavefront: LDS operations of a wavefront keep their order) */
-				*reinterpret_cast<uint4 *>(p + (size_t)(c + rr) * W + 8 * c8) = w;
+				if (!LEAN || c < HLF) *reinterpret_cast<uint4 *>(p + (size_t)(c + rr) * W + 8 * c8) = w;   /* (LEAN: the rows the LL2 emission reads; c is the wavefront's) */
 				*reinterpret_cast<uint4 *>(save + (size_t)(c + rr) * H + 8 * c8) = w;   /* Y13 (:623-631) */
 			}
 		}
 		lds_barrier();                                             /* the block is done with before the next one moves in */
 	}
 }
-void nhw_launch_l2_recon(Plane<int16_t> jpeg, Plane<int16_t> proc, Plane<int16_t> ll1, Plane<int16_t> l2save /* not empty: + the level-2 analysis of the pre-compensated block and its copy (rows of H cells) */, int n, hipStream_t s)
+void nhw_launch_l2_recon(Plane<int16_t> jpeg, Plane<int16_t> proc, Plane<int16_t> ll1, Plane<int16_t> l2save /* not empty: + the level-2 analysis of the pre-compensated block and its copy (rows of H cells) */, int n, hipStream_t s,
+                         bool lean /* with l2save: the stores nothing reads behind a production batch's kernel are left out (k_l2_recon, LEAN) */)
 {
-	assert(jpeg.pitch == proc.pitch);
-	(l2save.p ? k_l2_recon<true> : k_l2_recon<false>)<<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg.p, proc.p, jpeg.pitch, ll1.p, ll1.pitch, n, l2save.p, l2save.pitch);
+	assert(jpeg.pitch == proc.pitch && (!lean || l2save.p));
+	(!l2save.p ? k_l2_recon<false> : lean ? k_l2_recon<true, true> : k_l2_recon<true>)<<<n < 256 ? n : 256, 1024, H * (H + 2) * sizeof(int16_t) + 288, s>>>(jpeg.p, proc.p, jpeg.pitch, ll1.p, ll1.pitch, n, l2save.p, l2save.pitch);
 }
 
 /* Both closed loops of a chroma component on one LDS residency of its 128 x 128 level-2 block (nhw_encoder.c:2310-2370 for U, :2623-2680 for V):
@@ -504,7 +510,7 @@ int nhw_tail_set_attrs(const char **where)
 #define SETATTR(fn) do { const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fn), hipFuncAttributeMaxDynamicSharedMemorySize, 100 << 10); \
                          if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(" #fn ", MaxDynamicSharedMemorySize)"; return (int)e_; } } while (0)
 	SETATTR(k_phase<PH_L1>); SETATTR(k_phase<PH_L2>); SETATTR(k_phase<PH_L3>); SETATTR(k_phase<PH_C5>);
-	for (const void *fn : { reinterpret_cast<const void *>(&k_l2_recon<false>), reinterpret_cast<const void *>(&k_l2_recon<true>) }) {
+	for (const void *fn : { reinterpret_cast<const void *>(&k_l2_recon<false>), reinterpret_cast<const void *>(&k_l2_recon<true>), reinterpret_cast<const void *>(&k_l2_recon<true, true>) }) {
 		const hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(H * (H + 2) * sizeof(int16_t) + 288));
 		if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(k_l2_recon, MaxDynamicSharedMemorySize)"; return (int)e_; }
 	}

@@ -372,7 +372,27 @@ DEV unsigned dq_entry(int i)
  *   equal-sign pair, by sign               15700 / 15800    10300 / 10204
  * The value is taken behind the equal-sign block and in front of the walk (whose +-8 rewrites are not the quantiser's).  Row 255: the marking
  * block stops at row 254 here, the quantiser's loop 2 includes row 255 (it looks down into HL1), so that row goes over with row 254's vertical
- * marks alone and the quantiser runs both loops on it. */
+ * marks alone and the quantiser runs both loops on it.
+ *
+ * EVERY CELL OF THE PASS IS STORED (jp; with the LL2 walk in front -- wave_ll2, or wave_emit_ll2(sim) for the second loop, both of which store
+ * their 128 x 128 cells unconditionally -- a simulation writes the whole level-2 block of the reconstruction plane).  Production relies on it: the
+ * kernels in front of either simulation do not store that block (luma_loop_launches, k_l2_recon LEAN).  A cell is stored when its bit of je is
+ * set, and je collects pend | fired | ftp_r | ftn_r | part_p | part_n | (vis & ~wr):
+ *   * vis & ~wr: every cell the walk visits.  wr is empty: a value above 15000 that is none of the six marks is never produced -- the planes read
+ *     here (the work plane behind the first analysis, l2save behind the second) hold coefficients, Y5's tags go into ll1 -- and it exists only in
+ *     the comparison form (the table form sends such a value there).  Below quality 17 there are no marks and vis is the whole row;
+ *   * the cells the walk steps over are the one behind a visited 15500 .. 15800 and the two behind a visited 15300 / 15400 (sk: pattern 2 or 6
+ *     from the mark's own bit; a mark that is itself stepped over adds nothing, so the cell behind it is visited).  Where a mark in cur comes from:
+ *       15300 / 15400 at j: this row's marking block alone (ftp_l / ftn_l), so j + 1 is the firing centre (fired) and j + 2 the triple's right
+ *         cell (ftp_r / ftn_r) -- both in je;
+ *       15500 / 15600 at j from this row's marking block (fvp_l / fvn_l): j + 1 is the firing cell of the vertical pair (fired);
+ *       15500 / 15600 at j from the row above (written into nxt there; nothing rewrites it here -- a mark is no P or N, so j neither fires nor
+ *         lies left of a firing cell, and the equal-sign block wants 5 .. 7): j + 1 fired in the row above as a vertical pair, which is pend;
+ *       15700 / 15800 at j (the equal-sign block, second loop only; its candidates stop at column 254): j + 1 is the partner, part_p / part_n
+ *         when j is visited -- and visited itself when j is stepped over.
+ *     The cells are looked at by the mark's VALUE at the walk, so an order of the assignments above that lets one mark overwrite another (a cell
+ *     left of two firing cells) changes which case applies, not that one does.
+ * tests/test_l2_dead_stores.py fills the block in front of either simulation and finds no cell of the fill behind it, on pictures made of marks. */
 template <bool HAND>
 DEV void wave_dequant_details(Ctx *c, int part, int lane, const uint32_t *lut /* DQ_WORDS, filled by the workgroup */, bool keep_p, const int16_t *src, int ss /* see wave_ll2 */, int16_t *hand = nullptr)
 {

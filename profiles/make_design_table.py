@@ -1,24 +1,24 @@
 """Regenerates the kernel table of DESIGN.md (between the KERNEL_TABLE markers) from the committed profile summaries, so that the numbers
 cannot drift from the files they cite.   usage: python profiles/make_design_table.py [--check]
-inputs: profiles/round7_kernel_stats_1stream.txt (rocprofv3 --kernel-trace --stats, one stream), profiles/round7_pmc.json (FETCH_SIZE and
+inputs: profiles/l2_dead_stores_kernel_stats_1stream_after.txt (rocprofv3 --kernel-trace --stats, one stream), profiles/l2_dead_stores_pmc_after.json (FETCH_SIZE and
 WRITE_SIZE per kernel from separate --pmc passes; KiB; FETCH_SIZE doubled for gfx950 as MI355X_MICROARCH.md prescribes)."""
 import json, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STATS = os.path.join(ROOT, "profiles", "round7_kernel_stats_1stream.txt")
-PMC = os.path.join(ROOT, "profiles", "round7_pmc.json")
+STATS = os.path.join(ROOT, "profiles", "l2_dead_stores_kernel_stats_1stream_after.txt")
+PMC = os.path.join(ROOT, "profiles", "l2_dead_stores_pmc_after.json")
 BATCHES = 7.0            # bench.py --steps 5 --warmup 2 in profiles/collect.sh
 PH = ["L1", "L2", "L3", "L4A", "C0", "C2", "C3", "C4", "C5", "FINAL", "L4B", "L4C", "L4D", "LLC", "L4C2"]
 WV = ["DQ1", "DQ0", "EMIT", "QUANT"]
 WHAT = {
     "k_front_image": "a1 + a2 + Y2 + Y3 fused: BGR24 -> Y, 4:2:0 chroma planes out, pre-filter (carry chained in the kernel), both directions of the level-1 analysis, LL copy; a workgroup walks an image (32 rows a band, 512 threads, 78 KB LDS)",
     "k_front_plain": "the same without the pre-filter (q >= 22; q <= 16 and the analysis stage from a luma plane): horizontal pass from registers, 64 rows a band",
-    "k_dwt_ana<256>": "level-2 luma analysis of both closed loops (whole block in LDS, persistent workgroups); level-1 chroma analysis only for q <= 14 and the stage checks",
+    "k_dwt_ana<256>": "level-2 luma analysis of the first closed loop, from ll1, without its transposed plane (whole block in LDS, persistent workgroups); the second loop's only for q <= 12 and the stage checks, level-1 chroma analysis only for q <= 14 and the stage checks",
     "k_chroma_l1q": "level-1 chroma analysis from the 4:2:0 byte plane, a quarter of the 256 x 256 block to a workgroup (four a CU); its coefficients are part of SURVEY's 6 B/pixel",
     "k_dwt_ana<128>": "level-2 chroma analysis (only the tests' stage checks run it)",
     "k_chroma_loops": "both chroma closed loops of a component on one LDS residency of its level-2 block: analysis, simulation 1, synthesis, pre-compensation, analysis (+ cl2save), simulation 2, synthesis (four workgroups a CU)",
     "k_dwt_syn<256>": "level-2 luma synthesis of the second closed loop",
     "k_dwt_syn<128>": "level-2 chroma synthesis (only the tests' stage checks run it)",
-    "k_l2_recon": "first closed loop: level-2 synthesis + Y8 (tags -> reconstruction) + Y9 (LL1 pre-compensation) on one LDS residency of the block",
+    "k_l2_recon": "first closed loop: level-2 synthesis + Y8 (tags -> reconstruction) + Y9 (LL1 pre-compensation) + the second level-2 analysis with Y13's copy on one LDS residency of the block; a batch's form stores l2save and rows 0 .. 127 of the work plane's block",
     "L1": "Y5 tag level-2 details", "L2": "Y8, Y9 as a kernel of their own (only the tests' stage checks run it)", "L3": "Y16 LL2 coder (parse), on a stream of its own beside the second dequantiser simulation",
     "L4A": "Y19-Y23: small runs (wavefront per row), residual classification (one table-driven step for every kind) and coding (column walks on LDS tiles)",
     "L4B": "Y24, Y25 position lists + list packing", "L4C": "Y27 detail clean-up (a wavefront takes 64 consecutive rows, neighbours in registers; Y26 only for q >= 22)", "L4D": "Y31 rewrites, on the symbol LIST (non-zero map + values); leaves map and offsets in stream order",
@@ -27,7 +27,8 @@ WHAT = {
     "C5": "chroma: marks (running-index fixed point), LL2 emission, quantiser (wavefront per row); V leaves the merged chroma stream as a list", "LLC": "Z1 chroma LL2 coder", "FINAL": "Z2 packetiser + container",
     "k_l4a": "Y19-Y23 of q >= 17: Y21 small runs (wavefront per row, rows in which nothing fires skipped), Y22 + Y23 as ONE column sweep on registers and class tables (eight workgroups a CU)",
     "k_y31": "Y31 rewrites on the symbol LIST (non-zero map + values), 512 threads an image; leaves map and offsets in stream order",
-    "k_final": "Z2 packetiser (both parts from the symbol lists) + container; a kernel of its own at four wavefronts a SIMD",
+    "k_final": "Z2 packetiser (the luma part from its symbol list, both books) + container; a kernel of its own at six wavefronts a SIMD",
+    "k_pack_chroma": "Z2's chroma part: words and ranked book entries from the chroma symbol list (on the chroma stream in the forked order)",
     "DQ1": "a8 dequantiser simulation, first closed loop (wavefront per image)", "DQ0": "a8 dequantiser simulation, second closed loop",
     "EMIT": "Y14/Y15 LL2 emission", "QUANT": "Y28 luma quantiser + Y30: the symbols leave as a list in stream order (wavefront per image); reads the level-2 block from l2save (Y26)",
 }
