@@ -386,7 +386,7 @@ int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *o
  * not finite, or NHW_T_U8 with another scale or bias. */
 enum { NHW_T_U8 = 0, NHW_T_F16 = 1, NHW_T_BF16 = 2, NHW_T_F32 = 3 };
 enum { NHW_T_HWC = 0, NHW_T_CHW = 1 };
-enum { NHW_T_BGR = 0, NHW_T_RGB = 1, NHW_T_GREY = 2 };   /* NHW_T_GREY: one channel; taken by the grey decode alone (below) */
+enum { NHW_T_BGR = 0, NHW_T_RGB = 1, NHW_T_GREY = 2 };   /* NHW_T_GREY: one channel; taken by the grey decode and the grey calls alone (DESIGN.md sections 22 and 23, below) */
 enum { NHW_T_ROWS_FILE = 0, NHW_T_ROWS_REVERSED = 1 };
 typedef struct { int32_t dtype, layout, channels, rows; float scale[3], bias[3]; uint32_t reserved; } nhw_tensor_format;   /* 44 bytes */
 /* nhw_dec_batch_device_scaled with a format: scale 1, 2 or 4 as there (S = 512 / scale), file i's tensor at d_out + i * 3 * S * S *
@@ -624,11 +624,48 @@ int nhw_grey_table(int quality, uint8_t table[256]);
  * NHW_E_ARG, before anything is launched: a format with NHW_T_BGR or NHW_T_RGB, an otherwise refused format, a d_out that is not 16-byte
  * aligned, a handle with a debug stop set, and the cases of nhw_dec_batch_device_scaled.  Asynchronous on `stream`; nhw_dec_last_timing
  * describes it, recon_ms = the kernel that writes the grey pictures.  One handle serves colour and grey batches in any order.  Every other
- * entry point refuses NHW_T_GREY. */
+ * entry point refuses NHW_T_GREY, but for the grey calls of section 23 below. */
 int nhw_dec_batch_device_grey(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
                               const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream);
 /* host convenience, synchronous: as nhw_dec_batch_scaled, for any n >= 1; file i's S S grey bytes land at out + i * S S */
 int nhw_dec_batch_grey(nhw_dec *d, const uint8_t *nhw, const uint64_t *off, int n, int scale, uint8_t *out, int32_t *status, int32_t *quality);
+
+/* ---- grey windows, crops, resamplers and warps at one byte a pixel ----
+ * The grey picture of a container at scale s is its tile files' grey decodes at that scale (above), laid on the tile grid and cut to
+ * ceil(W / s) x ceil(H / s): uint8 [H'][W'], rows in file order.  A grey window is a rectangle of it, a grey crop or warp a grey window resampled
+ * or warped.  The seven calls below are the colour calls named beside them with one byte where those have three and one element where those have
+ * three: the same arguments, checks, per-rect statuses (the tiles a call selects, uploads and decodes are the colour call's, and so are the
+ * decoder's verdicts on them), statistics and passed-over entries.  What differs:
+ *   a picture of a table (nhw_picture) and a packed window have 1 byte a pixel, and a pitch is at least the width;
+ *   a tensor format must name NHW_T_GREY: NHW_T_BGR and NHW_T_RGB are refused as nhw_dec_batch_device_grey refuses them.  dtype, rows, scale[0]
+ *     and bias[0] are read; NHW_T_HWC and NHW_T_CHW are the same memory, out_height x out_width elements, element (r, c) at index r out_width + c;
+ *     entries 1 and 2 of scale and bias are checked as ever and not used;
+ *   the rules of the resamplers (sections 18 to 20) and of the warp (section 21) apply to the one channel as they stand: positions, taps, weights,
+ *     roundings, reduction limits, the mirror flag; a warp's border byte is fill[0], and fill[1] and fill[2] are not read;
+ *   the host calls refuse a handle with a debug stop set at every scale, as the grey decode does.
+ * There is no grey nhw_dec_pictures and no grey region call: a whole picture is the window (0, 0, ceil(W / s), ceil(H / s)), a region a window at
+ * scale 1.  The colour entry points go on refusing NHW_T_GREY. */
+/* nhw_untile_windows_device over the slots of a grey decode, T T bytes each: columns go to destination byte (col - x) of their row */
+int nhw_untile_windows_grey_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
+                                   int tile0, int m, int scale, void *stream);
+/* nhw_resample_to_tensor_device and nhw_warp_to_tensor_device for one-byte pictures and one-channel tensors */
+int nhw_resample_grey_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                       const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream);
+int nhw_warp_grey_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                   const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream);
+/* nhw_dec_windows: window i's width x height grey bytes, packed, land at out + out_off[i] */
+int nhw_dec_windows_grey(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                         uint8_t *out, const uint64_t *out_off, int32_t *status);
+/* nhw_dec_windows_to_device: dst_pitch[i] >= width */
+int nhw_dec_windows_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                   const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status);
+/* nhw_dec_crops_to_device_resample (filter 0 .. 2) and nhw_dec_warps_to_device */
+int nhw_dec_crops_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                 uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
+                                 int32_t *status, int filter);
+int nhw_dec_warps_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                 uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
+                                 int32_t *status);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_grey_table.argtypes = [ctypes.c_int, P]
     L.nhw_dec_batch_device_grey.argtypes = L.nhw_dec_batch_device_tensor.argtypes
     L.nhw_dec_batch_grey.argtypes = L.nhw_dec_batch_scaled.argtypes
+    L.nhw_untile_windows_grey_device.argtypes = L.nhw_untile_windows_device.argtypes       # the grey calls: their colour calls' arguments
+    L.nhw_resample_grey_to_tensor_device.argtypes = L.nhw_resample_to_tensor_device.argtypes
+    L.nhw_warp_grey_to_tensor_device.argtypes = L.nhw_warp_to_tensor_device.argtypes
+    L.nhw_dec_windows_grey.argtypes = L.nhw_dec_windows.argtypes
+    L.nhw_dec_windows_grey_to_device.argtypes = L.nhw_dec_windows_to_device.argtypes
+    L.nhw_dec_crops_grey_to_device.argtypes = L.nhw_dec_crops_to_device_resample.argtypes
+    L.nhw_dec_warps_grey_to_device.argtypes = L.nhw_dec_warps_to_device.argtypes
     return L
 
 
@@ -239,7 +246,7 @@ NHW_T_U8, NHW_T_F16, NHW_T_BF16, NHW_T_F32 = 0, 1, 2, 3
 TENSOR_DTYPES = {"uint8": NHW_T_U8, "float16": NHW_T_F16, "bfloat16": NHW_T_BF16, "float32": NHW_T_F32}
 TENSOR_LAYOUTS = {"HWC": 0, "CHW": 1}             # NHW_T_HWC, NHW_T_CHW
 TENSOR_CHANNELS = {"BGR": 0, "RGB": 1}            # NHW_T_BGR, NHW_T_RGB
-TENSOR_GREY = 2                                   # NHW_T_GREY: channels "GREY", which the grey decode alone takes
+TENSOR_GREY = 2                                   # NHW_T_GREY: channels "GREY", which the grey decode and the grey calls alone take (DESIGN.md sections 22, 23)
 TENSOR_ROWS = {"file": 0, "reversed": 1}          # NHW_T_ROWS_FILE, NHW_T_ROWS_REVERSED
 
 
@@ -254,7 +261,8 @@ class TensorFormat:
     its sign; an exact zero is +0, except -0 for a zero product of negative sign (byte 0 under a scale below zero) plus a bias of -0.0.  Either scale / bias (three numbers each, or one for all; default 1 and 0) or mean / std in units of 0..1
     pixels, which give, in float32 arithmetic, scale = 1 / (255 * std) and bias = -mean / std (so that the element is (b / 255 - mean) / std
     up to rounding).  The attributes scale and bias are the float32 constants the kernels get, as tuples of Python floats.
-    channels "GREY" is the one-channel format of Decoder.decode_grey_device and of nothing else: scale / bias / mean /
+    channels "GREY" is the one-channel format of Decoder.decode_grey_device and of the calls with `grey` in their names
+    (section 23), and of nothing else: scale / bias / mean /
     std take ONE number (three are refused), the tensor is [1, S, S] or [S, S, 1], and there is no inverse, for encoding from grey is not
     built."""
 
@@ -348,32 +356,43 @@ def grey_table(quality: int):
     return t
 
 
-def _tensor_format(fmt, what):
+def _tensor_format(fmt, what, grey=False):
+    """the checked format of a call: a TensorFormat, of channels "GREY" for a grey call (grey=True) and of no such for a colour call (False);
+    None: either"""
     if not isinstance(fmt, TensorFormat):
         raise NhwError(f"{what}: `fmt` must be a TensorFormat, got {type(fmt).__name__}")
+    if grey is True and fmt.channels != "GREY":
+        raise NhwError(f"{what}: `fmt` must have channels \"GREY\", got {fmt.channels!r}")
+    if grey is False and fmt.channels == "GREY":
+        raise NhwError(f"{what}: `fmt` has channels \"GREY\", which the grey calls alone take")
     return fmt
 
 
-def _picture_table(pictures, what, side=512):
+def _picture_table(pictures, what, side=512, channels=3):
     """the checked nhw_picture table of a list of uint8 CUDA tensors [H, W, 3] with strides (pitch, 3, 1), on one device -> (table as an
-    int64 CUDA tensor, total tiles, device).  side: the tile side (512; 256 or 128 for the pictures of a scaled decode)"""
+    int64 CUDA tensor, total tiles, device).  side: the tile side (512; 256 or 128 for the pictures of a scaled decode).  channels=1: the
+    one-byte pictures of the grey calls, [H, W] with strides (pitch >= W, 1)"""
     import numpy as np
     import torch
+    C = channels
+    form = "[H, W, 3]" if C == 3 else "[H, W]"
     if not isinstance(pictures, (list, tuple)) or not pictures:
-        raise NhwError(f"{what} wants a non-empty list of uint8 CUDA tensors [H, W, 3]")
+        raise NhwError(f"{what} wants a non-empty list of uint8 CUDA tensors {form}")
     dev = pictures[0].device if isinstance(pictures[0], torch.Tensor) else None
     table = np.zeros(len(pictures), PICTURE_DTYPE)
     tiles = 0
     for i, x in enumerate(pictures):
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and x.dim() == 3 and x.shape[2] == 3):
-            raise NhwError(f"{what}: picture {i} is not a uint8 CUDA tensor [H, W, 3]")
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8 and (x.dim() == 3 and x.shape[2] == 3 if C == 3 else x.dim() == 2)):
+            raise NhwError(f"{what}: picture {i} is not a uint8 CUDA tensor {form}")
         if x.device != dev:
             raise NhwError(f"{what}: picture {i} is on {x.device}, picture 0 on {dev}")
         h, w = int(x.shape[0]), int(x.shape[1])
         t = picture_tiles(w, h) if side == 512 else (-(-w // side)) * (-(-h // side))
-        if x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w):
+        if C == 1 and ((w > 1 and x.stride(1) != 1) or (h > 1 and x.stride(0) < w)):
+            raise NhwError(f"{what}: picture {i} must have strides (pitch >= W, 1), got {tuple(x.stride())}")
+        if C == 3 and (x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w)):
             raise NhwError(f"{what}: picture {i} must have strides (pitch >= 3 W, 3, 1), got {tuple(x.stride())}")
-        table[i] = (x.data_ptr(), x.stride(0) if h > 1 else 3 * w, w, h, tiles, 0)
+        table[i] = (x.data_ptr(), x.stride(0) if h > 1 else C * w, w, h, tiles, 0)
         tiles += t
     return torch.from_numpy(table.view(np.int64).copy()).to(dev), tiles, dev
 
@@ -538,27 +557,39 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     (k_cubic_to_tensor, nhw_resample_to_tensor_device): the Keys cubic with a = -1/2, widened with the reduction, what
     PIL's BICUBIC and torch's antialiased bicubic compute, as an integer rule; the limit is CUBIC_MAX_REDUCTION.  Reads only the
     pictures' own bytes.  Ordered on torch's current stream."""
+    return _resize_to_tensor("resize_to_tensor_device", 3, pictures, size, fmt, flips, filter)
+
+
+def resize_grey_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
+    """resize_to_tensor_device for one-channel pictures (nhw_resample_grey_to_tensor_device): a list of uint8 CUDA
+    tensors [H, W] with strides (pitch >= W, 1), fmt a TensorFormat of channels "GREY" -> a new tensor [n, 1, out_h, out_w] or [n, out_h,
+    out_w, 1] of fmt.dtype.  The rules of the three filters on the one channel; the value rule with the format's one scale and bias."""
+    return _resize_to_tensor("resize_grey_to_tensor_device", 1, pictures, size, fmt, flips, filter)
+
+
+def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter):
+    """resize_to_tensor_device (channels=3) and resize_grey_to_tensor_device (1)"""
     import torch
-    what = "resize_to_tensor_device"
     _filter(filter, what)
-    fmt = _tensor_format(fmt, what)
+    fmt = _tensor_format(fmt, what, grey=channels == 1)
     out_h, out_w = _crop_size(size, what)
     if isinstance(pictures, (list, tuple)):                          # the limit from the shapes alone, before a device is looked at
         for i, x in enumerate(pictures):
-            if len(getattr(x, "shape", ())) == 3:
+            if len(getattr(x, "shape", ())) == (3 if channels == 3 else 2):
                 _filter_limit(filter, int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
-    table, _, dev = _picture_table(pictures, what)
+    table, _, dev = _picture_table(pictures, what, channels=channels)
     n = len(pictures)
     flags = _crop_flips(flips, n, what)
     out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
-    addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (3 * out_h * out_w * out.element_size())
+    addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (channels * out_h * out_w * out.element_size())
     addr = addr.to(dev)
     d_flags = torch.from_numpy(flags).to(dev) if flags is not None else None
     L = _library()
     c = fmt.c_struct()
+    call = L.nhw_resample_to_tensor_device if channels == 3 else L.nhw_resample_grey_to_tensor_device
     with torch.cuda.device(dev):
-        rc = L.nhw_resample_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                                             addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        rc = call(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                  addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -669,10 +700,14 @@ def crop_warp(x, y, w, h, size, angle=0.0, flip=False):
     return np.array([[cs * ux, -sn * vy, x + w / 2 + cs * u0 - sn * v0], [sn * ux, cs * vy, y + h / 2 + sn * u0 + cs * v0]], dtype=np.float64)
 
 
-def _warp_border(fill, border, what):
-    """the checked (fill bytes B, G, R; flag byte) of a warp call"""
+def _warp_border(fill, border, what, channels=3):
+    """the checked (fill bytes B, G, R; flag byte) of a warp call; channels=1: fill is one byte, which goes into the first place"""
     if not isinstance(border, str) or border not in WARP_BORDERS:
         raise NhwError(f"{what}: `border` must be one of {', '.join(repr(k) for k in WARP_BORDERS)}, got {border!r}")
+    if channels == 1:
+        if isinstance(fill, bool) or not isinstance(fill, numbers.Integral) or not 0 <= fill <= 255:
+            raise NhwError(f"{what}: `fill` must be one byte, an integer of 0 .. 255, got {fill!r}")
+        return (int(fill), 0, 0), WARP_BORDERS[border]
     if not (isinstance(fill, (tuple, list)) and len(fill) == 3 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and 0 <= v <= 255 for v in fill)):
         raise NhwError(f"{what}: `fill` must be three bytes (B, G, R), got {fill!r}")
     return tuple(int(v) for v in fill), WARP_BORDERS[border]
@@ -709,25 +744,36 @@ def warp_to_tensor_device(pictures, matrices, size, fmt, fill=(0, 0, 0), border=
     of an integer dtype) --, size = (out_h, out_w) -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Two taps a
     direction at the position the warp gives, in integers; a tap outside the picture takes fill = (B, G, R), or with border="replicate" the
     nearest edge pixel.  Reads only the pictures' own bytes.  Ordered on torch's current stream."""
+    return _warp_to_tensor("warp_to_tensor_device", 3, pictures, matrices, size, fmt, fill, border)
+
+
+def warp_grey_to_tensor_device(pictures, matrices, size, fmt, fill=0, border="fill"):
+    """warp_to_tensor_device for one-channel pictures (nhw_warp_grey_to_tensor_device): pictures and fmt as for
+    resize_grey_to_tensor_device, fill one byte -> a new tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype."""
+    return _warp_to_tensor("warp_grey_to_tensor_device", 1, pictures, matrices, size, fmt, fill, border)
+
+
+def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border):
+    """warp_to_tensor_device (channels=3) and warp_grey_to_tensor_device (1)"""
     import numpy as np
     import torch
-    what = "warp_to_tensor_device"
-    fmt = _tensor_format(fmt, what)
+    fmt = _tensor_format(fmt, what, grey=channels == 1)
     out_h, out_w = _crop_size(size, what)
-    fill, flags = _warp_border(fill, border, what)
+    fill, flags = _warp_border(fill, border, what, channels)
     if not isinstance(pictures, (list, tuple)) or not isinstance(matrices, (list, tuple, np.ndarray)) or len(matrices) != len(pictures):
         raise NhwError(f"{what}: `pictures` and `matrices` must be lists of the same length, one warp a picture")
     warps = _warp_table([_warp_entry(m, f"{what}: matrix {i}") for i, m in enumerate(matrices)], fill, flags)
-    table, _, dev = _picture_table(pictures, what)
+    table, _, dev = _picture_table(pictures, what, channels=channels)
     n = len(pictures)
     out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
-    addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (3 * out_h * out_w * out.element_size())
+    addr = out.data_ptr() + torch.arange(n, dtype=torch.int64) * (channels * out_h * out_w * out.element_size())
     addr = addr.to(dev)
     d_warps = torch.from_numpy(warps.view(np.int64).copy()).to(dev)
     L = _library()
     c = fmt.c_struct()
+    call = L.nhw_warp_to_tensor_device if channels == 3 else L.nhw_warp_grey_to_tensor_device
     with torch.cuda.device(dev):
-        rc = L.nhw_warp_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -1470,8 +1516,8 @@ class Decoder:
         (tensor [n, 1, S, S] or [n, S, S, 1] of fmt.dtype, status, quality).  out: a contiguous, 16-byte aligned tensor of that dtype with at
         least n * S * S elements.  Status and quality are those of the colour decode; a refused file's slot is left untouched."""
         what = "decode_grey_device"
-        if fmt is not None and _tensor_format(fmt, what).channels != "GREY":
-            raise NhwError(f"{what}: `fmt` must have channels \"GREY\", got {fmt.channels!r}")
+        if fmt is not None:
+            _tensor_format(fmt, what, grey=True)
         scale = _scale(scale, what)
         side = 512 // scale
         n = self._device_files(arena, offsets, lengths, what)
@@ -1564,38 +1610,44 @@ class Decoder:
         if (status != 0).any():
             raise NhwError(f"per-region status {status.tolist()}")
 
-    def _regions_host(self, containers, rects, what, call):
-        """the host form of a region or window call: call(blob, offsets, n containers, rect table, n, out, out_off, status) -> rc"""
+    def _regions_host(self, containers, rects, what, call, channels=3):
+        """the host form of a region or window call: call(blob, offsets, n containers, rect table, n, out, out_off, status) -> rc;
+        channels=1: a grey call's [h, w] arrays"""
         import numpy as np
         blob, offs, table = self._region_args(containers, rects, what)
         n = len(table)
         out_off = np.zeros(n + 1, np.uint64)
-        out_off[1:] = np.cumsum(3 * table["width"].astype(np.uint64) * table["height"].astype(np.uint64))
+        out_off[1:] = np.cumsum(channels * table["width"].astype(np.uint64) * table["height"].astype(np.uint64))
         out = np.empty(max(int(out_off[n]), 1), np.uint8)
         status = np.empty(n, np.int32)
         self._chk(call(blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, out.ctypes.data, out_off.ctypes.data, status.ctypes.data))
         self._region_raise(status)
-        return [out[int(out_off[i]):int(out_off[i + 1])].reshape(int(r["height"]), int(r["width"]), 3) for i, r in enumerate(table)]
+        return [out[int(out_off[i]):int(out_off[i + 1])].reshape((int(r["height"]), int(r["width"])) + ((3,) if channels == 3 else ())) for i, r in enumerate(table)]
 
-    def _regions_device(self, containers, rects, out, what, call):
-        """the device form: call(blob, offsets, n containers, rect table, n, addresses, pitches, status) -> rc"""
+    def _regions_device(self, containers, rects, out, what, call, channels=3):
+        """the device form: call(blob, offsets, n containers, rect table, n, addresses, pitches, status) -> rc; channels=1: a grey call's
+        [h, w] tensors with strides (pitch >= w, 1)"""
         import numpy as np
         t = self.torch
         blob, offs, table = self._region_args(containers, rects, what)
         n = len(table)
         dev = t.device("cuda", self.device)
+        C = channels
+        last = (3,) if C == 3 else ()
         if out is None:
-            out = [t.empty((int(r["height"]), int(r["width"]), 3), dtype=t.uint8, device=dev) for r in table]
+            out = [t.empty((int(r["height"]), int(r["width"])) + last, dtype=t.uint8, device=dev) for r in table]
         elif not isinstance(out, (list, tuple)) or len(out) != n:
             raise NhwError(f"{what}: `out` must be a list of {n} tensors")
         addr, pitch = np.zeros(n, np.uint64), np.zeros(n, np.uint64)
         for i, (x, r) in enumerate(zip(out, table)):
             h, w = int(r["height"]), int(r["width"])
-            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device == dev and x.dtype == t.uint8 and tuple(x.shape) == (h, w, 3)):
-                raise NhwError(f"{what}: out[{i}] is not a uint8 tensor [{h}, {w}, 3] on {dev}")
-            if x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w):
+            if not (isinstance(x, t.Tensor) and x.is_cuda and x.device == dev and x.dtype == t.uint8 and tuple(x.shape) == (h, w) + last):
+                raise NhwError(f"{what}: out[{i}] is not a uint8 tensor {list((h, w) + last)} on {dev}")
+            if C == 1 and ((w > 1 and x.stride(1) != 1) or (h > 1 and x.stride(0) < w)):
+                raise NhwError(f"{what}: out[{i}] must have strides (pitch >= w, 1), got {tuple(x.stride())}")
+            if C == 3 and (x.stride(2) != 1 or (w > 1 and x.stride(1) != 3) or (h > 1 and x.stride(0) < 3 * w)):
                 raise NhwError(f"{what}: out[{i}] must have strides (pitch >= 3 w, 3, 1), got {tuple(x.stride())}")
-            addr[i], pitch[i] = x.data_ptr(), x.stride(0) if h > 1 else 3 * w
+            addr[i], pitch[i] = x.data_ptr(), x.stride(0) if h > 1 else C * w
         status = np.empty(n, np.int32)
         t.cuda.current_stream(dev).synchronize()                     # the call runs on the handle's own stream and waits for it
         self._chk(call(blob.ctypes.data, offs.ctypes.data, len(containers), table.ctypes.data, n, addr.ctypes.data, pitch.ctypes.data, status.ctypes.data))
@@ -1630,6 +1682,34 @@ class Decoder:
         return self._regions_device(containers, rects, out, "decode_windows_device",
                                     lambda *a: self.lib.nhw_dec_windows_to_device(self.h, *a[:5], scale, *a[5:]))
 
+    def decode_windows_grey(self, containers, rects, scale=1):
+        """decode_windows as grey (nhw_dec_windows_grey): the luma alone through the grey table of each tile file's
+        quality, one byte a pixel -> a list of numpy uint8 [h, w], window i equal to decode_pictures_grey(containers, scale)[container][y:y + h,
+        x:x + w].  The tiles, statuses and region_stats are decode_windows' own."""
+        scale = _scale(scale, "decode_windows_grey")
+        return self._regions_host(containers, rects, "decode_windows_grey", lambda *a: self.lib.nhw_dec_windows_grey(self.h, *a[:5], scale, *a[5:]), channels=1)
+
+    def decode_windows_grey_device(self, containers, rects, scale=1, out=None):
+        """decode_windows_grey with the pixels left on the device (nhw_dec_windows_grey_to_device): -> a list of uint8 CUDA tensors [h, w];
+        out: preallocated tensors with strides (pitch >= w, 1).  The stream ordering is decode_regions_device's."""
+        scale = _scale(scale, "decode_windows_grey_device")
+        return self._regions_device(containers, rects, out, "decode_windows_grey_device",
+                                    lambda *a: self.lib.nhw_dec_windows_grey_to_device(self.h, *a[:5], scale, *a[5:]), channels=1)
+
+    def decode_pictures_grey(self, containers, scale=1):
+        """Whole .nhwp pictures as grey at scale 1, 2 or 4 -> a list of numpy uint8 [ceil(H / scale), ceil(W / scale)]: decode_windows_grey
+        with the window that is all of each picture."""
+        scale = _scale(scale, "decode_pictures_grey")
+        if not isinstance(containers, (list, tuple)) or len(containers) < 1:
+            raise NhwError("decode_pictures_grey wants a non-empty list of containers")
+        return self.decode_windows_grey(containers, [(i, 0, 0) + scaled_size(*picture_info(c), scale) for i, c in enumerate(containers)], scale)
+
+    def decode_crops_grey_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap"):
+        """decode_crops_device as grey (nhw_dec_crops_grey_to_device): fmt a TensorFormat of channels "GREY" -> (tensor
+        [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype, the list of the scales used).  The scales and windows are chosen as there,
+        the filters and their limits are the same, and so are the tiles and the statuses; out: at least n * out_h * out_w elements."""
+        return self._crops_to_batch("decode_crops_grey_device", 1, containers, crops, size, fmt, flips, scale, out, filter)
+
     def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap"):
         """RandomResizedCrop's decode (nhw_dec_crops_to_device): crops, a sequence of (container index, x, y, w, h), each
         resampled to size = (out_h, out_w), mirrored left-right where flips[i] is true, and stored under fmt -> (tensor [n, 3, out_h, out_w]
@@ -1642,11 +1722,13 @@ class Decoder:
         AREA_MAX_REDUCTION times the output along a side is refused before any call; filter="cubic" resizes them under the cubic rule
         (nhw_dec_crops_to_device_resample, section 20) with the limit CUBIC_MAX_REDUCTION.  Raises on any status that is not NHW_OK.  The
         work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls."""
+        return self._crops_to_batch("decode_crops_device", 3, containers, crops, size, fmt, flips, scale, out, filter)
+
+    def _crops_to_batch(self, what, channels, containers, crops, size, fmt, flips, scale, out, filter):
+        """decode_crops_device (channels=3) and decode_crops_grey_device (1)"""
         import numpy as np
-        what = "decode_crops_device"
         _filter(filter, what)
-        t = self.torch
-        fmt = _tensor_format(fmt, what)
+        fmt = _tensor_format(fmt, what, grey=channels == 1)
         out_h, out_w = _crop_size(size, what)
         if scale is not None:
             scale = _scale(scale, what)
@@ -1666,10 +1748,11 @@ class Decoder:
         if filter in _LIMITS:
             for i, r in enumerate(table):
                 _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
+        call = self.lib.nhw_dec_crops_to_device_resample if channels == 3 else self.lib.nhw_dec_crops_grey_to_device
         return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
-                                    lambda *args: self.lib.nhw_dec_crops_to_device_resample(*args, RESAMPLERS[filter])), scales
+                                    lambda *args: call(*args, RESAMPLERS[filter]), channels), scales
 
-    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call):
+    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3):
         """the device side of decode_crops_device and decode_warps_device: the checked batch tensor (`out`, or a new one), and per scale one
         call(handle, blob, offsets, n containers, the scale's rects, their count, scale, out_w, out_h, format, the scale's rows of `extra` --
         the flag bytes or the nhw_warp table, or None --, the tensors' addresses, statuses) -> rc.  Raises on any status that is not NHW_OK"""
@@ -1678,7 +1761,7 @@ class Decoder:
         n = len(table)
         dev = t.device("cuda", self.device)
         shape = (n,) + fmt.shape(out_h, out_w)
-        per = 3 * out_h * out_w
+        per = channels * out_h * out_w
         if out is None:
             out = t.empty(shape, dtype=fmt.dtype, device=dev)
         elif not (isinstance(out, t.Tensor) and out.is_cuda and out.device == dev and out.dtype == fmt.dtype and out.is_contiguous() and out.numel() >= n * per):
@@ -1697,6 +1780,12 @@ class Decoder:
         self._region_raise(status)
         return out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)
 
+    def decode_warps_grey_device(self, containers, which, matrices, size, fmt, fill=0, border="fill", scale=None, out=None):
+        """decode_warps_device as grey (nhw_dec_warps_grey_to_device): fmt a TensorFormat of channels "GREY", fill one
+        byte -> (tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype, the list of the scales used).  The scales and windows are
+        chosen as there."""
+        return self._warps_to_batch("decode_warps_grey_device", 1, containers, which, matrices, size, fmt, fill, border, scale, out)
+
     def decode_warps_device(self, containers, which, matrices, size, fmt, fill=(0, 0, 0), border="fill", scale=None, out=None):
         """RandomAffine's / RandomRotation's decode (nhw_dec_warps_to_device): warp i samples the picture of container
         which[i] along the grid of matrices[i] -- a 2 x 3 matrix of floats as warp_fixed takes it, in FULL-resolution picture coordinates
@@ -1708,11 +1797,14 @@ class Decoder:
         outside the picture takes fill = (B, G, R), or with border="replicate" the nearest edge pixel.  out: as for decode_crops_device.
         Raises on any status that is not NHW_OK.  The work is ordered after torch's current stream and complete on return; region_stats
         speaks of the last of the calls."""
+        return self._warps_to_batch("decode_warps_device", 3, containers, which, matrices, size, fmt, fill, border, scale, out)
+
+    def _warps_to_batch(self, what, channels, containers, which, matrices, size, fmt, fill, border, scale, out):
+        """decode_warps_device (channels=3) and decode_warps_grey_device (1)"""
         import numpy as np
-        what = "decode_warps_device"
-        fmt = _tensor_format(fmt, what)
+        fmt = _tensor_format(fmt, what, grey=channels == 1)
         out_h, out_w = _crop_size(size, what)
-        fill, flags = _warp_border(fill, border, what)
+        fill, flags = _warp_border(fill, border, what, channels)
         if scale is not None:
             scale = _scale(scale, what)
         if not isinstance(containers, (list, tuple)) or len(containers) < 1:
@@ -1734,7 +1826,7 @@ class Decoder:
             fixed.append(fx)
         blob, offs, table = self._region_args(containers, rects, what)
         return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
-                                    self.lib.nhw_dec_warps_to_device), scales
+                                    self.lib.nhw_dec_warps_to_device if channels == 3 else self.lib.nhw_dec_warps_grey_to_device, channels), scales
 
     def region_stats(self):
         """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region or window call (nhw_dec_last_region_stats);

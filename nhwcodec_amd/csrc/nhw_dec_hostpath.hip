@@ -1,5 +1,5 @@
 /* nhw_dec_hostpath.hip -- the decoder's host conveniences: files in host memory in, pictures out (nhw_dec_batch), pictures of any size and regions of them out of
- * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip), nhw_picture.hip and nhw_resample.hip. */
+ * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device*, and the window, crop and warp calls as grey, nhw_dec_*_grey*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip), nhw_picture.hip and nhw_resample.hip. */
 #include "nhw_dec.h"
 #include "nhw_tensor.h"
 #include "nhw_tile_plan.h"
@@ -86,9 +86,10 @@ static const size_t MAX_CALL_TILES = (size_t)(INT_MAX / 16);       /* the tiles 
 
 /* The tile files of a call, in the handle's blob (already on its way there on the handle's stream): offsets and lengths go up, the tiles are
  * decoded at `scale` in chunks of max_batch into the host path's picture slots, each chunk followed by crop(t0, m) -- the launch that takes the
- * decoded tiles [t0, t0 + m) out of d->d_out --, and the per-tile status comes back.  Synchronises the stream. */
+ * decoded tiles [t0, t0 + m) out of d->d_out --, and the per-tile status comes back.  Synchronises the stream.  grey: the grey batch decode
+ *  without a format, T T bytes a slot where the colour decode leaves 3 T T. */
 template <class Crop>
-static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const std::vector<uint32_t> &tlen, int scale, std::vector<int32_t> &tst, Crop &&crop)
+static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const std::vector<uint32_t> &tlen, int scale, std::vector<int32_t> &tst, Crop &&crop, bool grey = false)
 {
 	const int tiles = (int)toff.size();
 	HIPCHK(nhw_grow(d->pic_tiles, (size_t)tiles * 16));
@@ -100,7 +101,8 @@ static int decode_tile_list(nhw_dec *d, const std::vector<uint64_t> &toff, const
 	HIPCHK(hipMemcpyAsync(d_tlen, tlen.data(), (size_t)tiles * 4, hipMemcpyHostToDevice, s));
 	for (int t0 = 0; t0 < tiles; t0 += d->max_batch) {
 		const int m = tiles - t0 < d->max_batch ? tiles - t0 : d->max_batch;
-		const int rc = nhw_dec_batch_device_scaled(d, d->blob.p, d_toff + t0, d_tlen + t0, m, scale, d->d_out, d_tst + t0, nullptr, s);
+		const int rc = grey ? nhw_dec_batch_device_grey(d, d->blob.p, d_toff + t0, d_tlen + t0, m, scale, nullptr, d->d_out, d_tst + t0, nullptr, s)
+		                    : nhw_dec_batch_device_scaled(d, d->blob.p, d_toff + t0, d_tlen + t0, m, scale, d->d_out, d_tst + t0, nullptr, s);
 		if (rc) return rc;
 		HIPCHK(crop(t0, m));
 	}
@@ -116,15 +118,15 @@ static int32_t tiles_status(const std::vector<int32_t> &tst, int t0, int t1)   /
 	return NHW_OK;
 }
 
-/* the results whose status is NHW_OK, device -> host: desc[k] (a picture or a region: 3 width height bytes at addr) is entry which[k] of the
- * call and goes to bgr + out_off[which[k]]; neighbours that are contiguous on both sides go as one copy */
+/* the results whose status is NHW_OK, device -> host: desc[k] (a picture or a region: px width height bytes at addr, px bytes a pixel) is
+ * entry which[k] of the call and goes to bgr + out_off[which[k]]; neighbours that are contiguous on both sides go as one copy */
 template <class D>
-static int download_decoded(uint8_t *bgr, const uint64_t *out_off, const std::vector<D> &desc, const std::vector<int> &which, const int32_t *status)
+static int download_decoded(uint8_t *bgr, const uint64_t *out_off, const std::vector<D> &desc, const std::vector<int> &which, const int32_t *status, uint64_t px = 3)
 {
 	struct Span { uint64_t dev, host, len; };
 	std::vector<Span> sp;
 	for (size_t k = 0; k < desc.size(); k++)
-		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], 3ull * desc[k].width * desc[k].height });
+		if (status[which[k]] == NHW_OK) sp.push_back({ desc[k].addr, out_off[which[k]], px * desc[k].width * desc[k].height });
 	for (size_t k = 0; k < sp.size();) {
 		uint64_t len = sp[k].len;
 		size_t j = k + 1;
@@ -174,7 +176,9 @@ extern "C" int nhw_dec_pictures_scaled(nhw_dec *d, const uint8_t *blob, const ui
 /* ---------------------------------------------------------------------------------------------- regions and windows (DESIGN.md sections 13, 15) */
 /* The region, window, crop and warp calls are one function, dec_windows: checks, the plan of the call's tiles (plan_windows in
  * nhw_tile_plan.h: a window call takes the union of its windows' selections; a region call is a window call at scale 1 with `merge` off),
- * upload, the chunked decode with k_untile_window behind each chunk, the statuses, and one of three finishes. */
+ * upload, the chunked decode with k_untile_window behind each chunk, the statuses, and one of three finishes.  A grey call (DESIGN.md
+ * section 23) is the same function at one byte a pixel: the grey decode underneath, k_untile_window_grey behind each chunk, the one-channel
+ * resamplers and warp at the end; the plan's tiles, and with them the statuses, are the colour call's. */
 enum WindowsMode {
 	WIN_TO_HOST,                                                 /* bgr / out_off: the rectangles packed in a device buffer of the handle, then downloaded (download_decoded) */
 	WIN_TO_DEVICE,                                               /* dst_addr / dst_pitch: cropped straight into the caller's device memory; nothing is left to do */
@@ -186,6 +190,7 @@ struct WindowsCall {
 	uint8_t *bgr = nullptr; const uint64_t *out_off = nullptr, *dst_addr = nullptr, *dst_pitch = nullptr;
 	const CropSpec *crop = nullptr;
 	bool merge = true;
+	bool grey = false;
 	const char *who = "";
 };
 
@@ -194,9 +199,10 @@ static int windows_check(const nhw_dec *d, const uint8_t *blob, const uint64_t *
 	const bool dst = c.mode == WIN_TO_HOST ? c.bgr && c.out_off : c.mode == WIN_TO_DEVICE ? c.dst_addr && c.dst_pitch : c.dst_addr && c.crop;
 	if (!d || !blob || !off || !rects || !status || nc < 1 || nr < 1 || !dst) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
 	if (!scale_ok(scale)) return NHW_E_ARG;
+	if (c.grey && d->stop_after) { nhw_dec_err = "a grey decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
 	if (scale != 1 && d->stop_after) { nhw_dec_err = "a scaled decode has no debug stops: the handle has one set"; return NHW_E_ARG; }
 	if (!offsets_ok(off, nc, c.who)) return NHW_E_ARG;
-	if (c.mode == WIN_TO_DEVICE) for (int i = 0; i < nr; i++) if (!c.dst_addr[i] || c.dst_pitch[i] < 3ull * rects[i].width) { nhw_dec_err = std::string(c.who) + ": a destination needs an address and a pitch of at least 3 x width"; return NHW_E_ARG; }
+	if (c.mode == WIN_TO_DEVICE) for (int i = 0; i < nr; i++) if (!c.dst_addr[i] || c.dst_pitch[i] < (c.grey ? 1ull : 3ull) * rects[i].width) { nhw_dec_err = std::string(c.who) + (c.grey ? ": a destination needs an address and a pitch of at least the width" : ": a destination needs an address and a pitch of at least 3 x width"); return NHW_E_ARG; }
 	if (c.mode == WIN_TO_TENSORS) for (int i = 0; i < nr; i++) if (!c.dst_addr[i] || c.dst_addr[i] % (c.crop->out.dtype == NHW_T_U8 ? 1u : c.crop->out.dtype == NHW_T_F32 ? 4u : 2u)) { nhw_dec_err = std::string(c.who) + ": a destination needs an address that is a multiple of the element size"; return NHW_E_ARG; }
 	return NHW_OK;
 }
@@ -238,7 +244,7 @@ static int upload_plan(nhw_dec *d, TilePlan &p, bool staged)
  * that has no window keeps a zero picture), nr tensor addresses (0 for a rect without a window or with a tile that failed, which the kernel
  * passes over), and behind them either the nr flag bytes -- k_resize_to_tensor, k_area_to_tensor or k_cubic_to_tensor by the filter -- or
  * the nr warps (32 + 8 bytes an entry in front: they are 8-byte aligned) -- k_warp_to_tensor, warps[i] sampling window i along its tilted grid. */
-static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, const uint64_t *dst_addr, int nr, const int32_t *status)
+static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, const uint64_t *dst_addr, int nr, const int32_t *status, bool grey)
 {
 	static_assert(sizeof(nhw_warp) == 40 && sizeof(nhw_picture) == 32, "the crop table's layout");
 	std::vector<nhw_picture> pics((size_t)nr, nhw_picture{ 0, 0, 0, 0, 0, 0 });
@@ -259,10 +265,12 @@ static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, con
 	HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
 	if (crop.warps) {
 		HIPCHK(hipMemcpyAsync(last, crop.warps, (size_t)nr * sizeof(nhw_warp), hipMemcpyHostToDevice, s));
-		HIPCHK(nhw_launch_warp(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_addr, s));
+		HIPCHK(grey ? nhw_launch_warp_grey(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.a, d_addr, s)
+		            : nhw_launch_warp(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_addr, s));
 	} else {
 		if (crop.flags) HIPCHK(hipMemcpyAsync(last, crop.flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		HIPCHK(nhw_launch_resample(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_addr, s));
+		HIPCHK(grey ? nhw_launch_resample_grey(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.a, crop.flags ? last : nullptr, d_addr, s)
+		            : nhw_launch_resample(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_addr, s));
 	}
 	HIPCHK(hipStreamSynchronize(s));
 	return NHW_OK;
@@ -277,7 +285,7 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 	const bool to_device = c.mode == WIN_TO_DEVICE;
 	TilePlan p;
 	if (const int rc = plan_windows({ blob, off, nc, rects, nr, scale, c.merge, c.crop ? refused.data() : nullptr, to_device ? c.dst_addr : nullptr, to_device ? c.dst_pitch : nullptr,
-	                                  c.who, MAX_CALL_TILES }, p, status, nhw_dec_err)) return rc;
+	                                  c.who, MAX_CALL_TILES, c.grey ? 1u : 3u }, p, status, nhw_dec_err)) return rc;
 	if (p.desc.empty()) return NHW_OK;
 	if (const int rc = upload_plan(d, p, !to_device)) return rc;
 	const int ng = (int)p.desc.size();
@@ -285,12 +293,13 @@ static int dec_windows(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int
 	const nhw_window_use *d_uses = (const nhw_window_use *)(d_desc + ng);
 	std::vector<int32_t> tst;
 	if (const int rc = decode_tile_list(d, p.toff, p.tlen, scale, tst, [&](int t0, int m) {
-		return nhw_launch_untile_window(d->d_out, d_desc, ng, d_uses + p.first_use[t0], p.first_use[t0 + m] - p.first_use[t0], t0, m, scale, d->own_stream); })) return rc;
+		const auto launch = c.grey ? nhw_launch_untile_window_grey : nhw_launch_untile_window;
+		return launch(d->d_out, d_desc, ng, d_uses + p.first_use[t0], p.first_use[t0 + m] - p.first_use[t0], t0, m, scale, d->own_stream); }, c.grey)) return rc;
 	for (const nhw_window_use &u : p.uses)
 		if (tst[u.slot] != NHW_OK) status[p.which[u.region]] = NHW_E_FORMAT;
 	switch (c.mode) {
-	case WIN_TO_HOST: return download_decoded(c.bgr, c.out_off, p.desc, p.which, status);
-	case WIN_TO_TENSORS: return crops_finish(d, p, *c.crop, c.dst_addr, nr, status);
+	case WIN_TO_HOST: return download_decoded(c.bgr, c.out_off, p.desc, p.which, status, c.grey ? 1 : 3);
+	case WIN_TO_TENSORS: return crops_finish(d, p, *c.crop, c.dst_addr, nr, status, c.grey);
 	default: return NHW_OK;
 	}
 }
@@ -377,6 +386,49 @@ extern "C" int nhw_dec_warps_to_device(nhw_dec *d, const uint8_t *blob, const ui
 	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err)) return rc;
 	WindowsCall c;
 	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.who = "nhw_dec_warps_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+/* ---------------------------------------------------------------------------------------------- the same calls at one byte a pixel */
+extern "C" int nhw_dec_windows_grey(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                    uint8_t *out, const uint64_t *out_off, int32_t *status)
+{
+	WindowsCall c;
+	c.mode = WIN_TO_HOST; c.bgr = out; c.out_off = out_off; c.grey = true; c.who = "nhw_dec_windows_grey";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+extern "C" int nhw_dec_windows_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                              const uint64_t *dst_addr, const uint64_t *dst_pitch, int32_t *status)
+{
+	WindowsCall c;
+	c.mode = WIN_TO_DEVICE; c.dst_addr = dst_addr; c.dst_pitch = dst_pitch; c.grey = true; c.who = "nhw_dec_windows_grey_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+/* nhw_dec_crops_to_device_resample's checks in its order -- the filter, then dst_addr and n_rects, then the sides and the format, which must be a grey one */
+extern "C" int nhw_dec_crops_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
+                                            int32_t *status, int filter)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_grey_to_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	CropSpec crop = { {}, flags, filter, nullptr };
+	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_grey_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, true)) return rc;
+	WindowsCall c;
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = true; c.who = "nhw_dec_crops_grey_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+extern "C" int nhw_dec_warps_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
+                                            int32_t *status)
+{
+	if (!warps || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps };
+	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_grey_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, true)) return rc;
+	WindowsCall c;
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = true; c.who = "nhw_dec_warps_grey_to_device";
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
 }
 

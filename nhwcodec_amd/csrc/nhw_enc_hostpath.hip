@@ -135,6 +135,17 @@ extern "C" int nhw_untile_windows_device(const void *d_tiles, const nhw_region *
 	return NHW_OK;
 }
 
+/* ... and of a grey window call: the same table and uses over slots of T T bytes, one byte a pixel */
+extern "C" int nhw_untile_windows_grey_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
+                                              int tile0, int m, int scale, void *stream)
+{
+	if (const int rc = picture_args(d_regs, n_regs, tile0, m, d_tiles, "nhw_untile_windows_grey_device")) return rc;
+	if (!d_uses || n_uses < 1 || n_uses > INT_MAX / 16) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = "nhw_untile_windows_grey_device: the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_untile_window_grey((const uint8_t *)d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 /* the pictures of a table to tensors of a format, one pointwise pass */
 extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics, const nhw_tensor_format *fmt, const uint64_t *d_out_addr, void *stream)
 {
@@ -186,6 +197,28 @@ extern "C" int nhw_warp_to_tensor_device(const nhw_picture *d_pics, int n, uint3
 	NhwTensorOut o;
 	if (const int rc = nhw_tensor_out_check("nhw_warp_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err)) return rc;
 	HIPCHK(nhw_launch_warp(d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* the one-channel forms of both: pictures of 1 byte a pixel, a grey format, the same checks in the same order */
+extern "C" int nhw_resample_grey_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                                  const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_grey_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_resample_grey_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, true)) return rc;
+	HIPCHK(nhw_launch_resample_grey(filter, d_pics, n, o.w, o.h, o.dtype, o.a, d_flags, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_warp_grey_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                              const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_warps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_warp_grey_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, true)) return rc;
+	HIPCHK(nhw_launch_warp_grey(d_pics, d_warps, n, o.w, o.h, o.dtype, o.a, d_out_addr, (hipStream_t)stream));
 	return NHW_OK;
 }
 

@@ -119,6 +119,7 @@ hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0,
 hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, int scale /* 1, 2, 4: tiles of side 512 / scale, the table holds the scaled pictures */, hipStream_t s);
 hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, hipStream_t s);
 hipError_t nhw_launch_untile_window(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses /* the launch's own range of the use table */, int n_uses, int tile0, int m, int scale, hipStream_t s);
+hipError_t nhw_launch_untile_window_grey(const uint8_t *d_tiles /* slots of T T bytes: a grey decode's */, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses, int tile0, int m, int scale, hipStream_t s);
 hipError_t nhw_launch_sse_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, uint64_t *d_sse, hipStream_t s);
 /* nhw_dec.hip: what a caller needs to know about a decoder handle before it hands it work (the distortion searches) */
 void nhw_dec_props(const nhw_dec *d, int *device, int *max_batch, int *stop_after);

@@ -161,14 +161,15 @@ __device__ __forceinline__ void store_part(uint8_t *A, uint4 v, int j, int e)
  * with store_part, the tile side through fetch, only the bytes it stores; the two sides have independent phases, and the words a row needs
  * (at most seg / 16 + 2; a whole row of a 512 tile: 97) depend on seg: the rows x that many slots are dealt out flat over the threads (slot
  * -> row by a multiply-high with the reciprocal, exact for the 32 x 97 slots a band can have), so that a 224-pixel crop does not walk 97
- * slots a row. */
-template <int ROW>
+ * slots a row.  ONE: seg may be below 3 (the one-byte pixels of DESIGN.md section 23), down to 1, which has one slot a row: the reciprocal
+ * of 1 is 2^32 and wraps to 0 in 32 bits, so the quotient is taken as the index itself there. */
+template <int ROW, bool ONE = false>
 __device__ __forceinline__ void copy_rows(uintptr_t src, uintptr_t dst, uint64_t pitch, int seg, uint32_t rows)
 {
-	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = rows * slots;   /* 2 .. 97 words cover seg bytes at any phase */
-	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots */
+	const uint32_t slots = (uint32_t)(seg + 30) / 16, total = rows * slots;   /* 2 .. 97 words cover seg bytes at any phase (ONE: 1 .. 33) */
+	const uint32_t rcp = 0xFFFFFFFFu / slots + 1;                         /* i / slots = umulhi(i, rcp) for i < 2^32 / slots, slots >= 2 */
 	for (uint32_t i = threadIdx.x; i < total; i += TP_THREADS) {
-		const uint32_t q = __umulhi(i, rcp), k = i - q * slots;            /* row q of the band's wanted rows, word k of it */
+		const uint32_t q = ONE && slots == 1 ? i : __umulhi(i, rcp), k = i - q * slots;   /* row q of the band's wanted rows, word k of it */
 		const uintptr_t D0 = dst + (uint64_t)q * pitch, D1 = D0 + seg;
 		const uintptr_t A = (D0 & ~(uintptr_t)15) + 16 * (uintptr_t)k;
 		if (A >= D1) continue;
@@ -179,21 +180,25 @@ __device__ __forceinline__ void copy_rows(uintptr_t src, uintptr_t dst, uint64_t
 	}
 }
 
-/* The workgroup's band of TP_ROWS rows of the tile (ty, tx) of side T at `tile` (3 T bytes a row; T = 512, or 256 or 128: the tiles of a
- * scaled decode), into the rectangle x, y, width, height of g: tile row rr is picture row T ty + rr, wanted if
- * y <= row < y + height; of it the picture columns [c0, c1) = [max(T tx, x), min(T tx + T, x + width)) go from tile byte 3 (c0 - T tx) of
- * the row to byte 3 (c0 - x) of destination row (row - y).  A band or a tile that shares nothing with the rectangle stores nothing. */
-template <int T>
+/* The workgroup's band of TP_ROWS rows of the tile (ty, tx) of side T at `tile` (C T bytes a row, C bytes a pixel: 3, or 1 for the grey tiles of
+ * DESIGN.md section 23; T = 512, or 256 or 128: the tiles of a scaled decode, section 14), into the rectangle x, y, width, height of g: tile row rr
+ * is picture row T ty + rr, wanted if y <= row < y + height; of it the picture columns [c0, c1) = [max(T tx, x), min(T tx + T, x + width)) go
+ * from tile byte C (c0 - T tx) of the row to byte C (c0 - x) of destination row (row - y).  A band or a tile that shares nothing with the rectangle
+ * stores nothing.  With C = 1 a segment has 1 .. T bytes where the colour form has 3 .. 3 T, and copy_rows is told so (ONE): a run of seg bytes
+ * at phase ph touches the words 0 .. (ph + seg - 1) / 16, at most (seg + 30) / 16 of them (ph = 15), so its slot count is right for the short
+ * segments too -- 1 for seg = 1, 2 for seg = 2 -- and a slot whose word starts at or behind the run's end is passed over by A >= D1; its
+ * reciprocal is exact for 2 slots (2^31: a shift) but not for 1, where 2^32 does not fit, and there the quotient is the index itself. */
+template <int T, int C = 3>
 __device__ __forceinline__ void crop_band(const uint8_t *tile, uint32_t ty, uint32_t tx, const nhw_region &g)
 {
-	constexpr int ROW = 3 * T;
+	constexpr int ROW = C * T;
 	const uint32_t top = T * ty + (blockIdx.x % (T / TP_ROWS)) * TP_ROWS;   /* picture row of the band's first row */
 	const uint32_t lo = top > g.y ? top : g.y, hi = top + TP_ROWS < g.y + g.height ? top + TP_ROWS : g.y + g.height;
 	const uint32_t c0 = T * tx > g.x ? T * tx : g.x, c1 = T * tx + T < g.x + g.width ? T * tx + T : g.x + g.width;
 	if (lo >= hi || c0 >= c1) return;
-	const uintptr_t src = (uintptr_t)tile + (uintptr_t)(lo - T * ty) * ROW + 3 * (c0 - T * tx);
-	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + 3 * (c0 - g.x);
-	copy_rows<ROW>(src, dst, g.pitch, 3 * (int)(c1 - c0), hi - lo);      /* 3 .. 3 T bytes a row */
+	const uintptr_t src = (uintptr_t)tile + (uintptr_t)(lo - T * ty) * ROW + C * (c0 - T * tx);
+	const uintptr_t dst = (uintptr_t)(g.addr + (uint64_t)(lo - g.y) * g.pitch) + C * (c0 - g.x);
+	copy_rows<ROW, C == 1>(src, dst, g.pitch, C * (int)(c1 - c0), hi - lo);   /* C .. C T bytes a row */
 }
 
 /* a rectangle of a picture whose tiles have the side T: not empty, the picture's sides at most the largest scaled ones (65535, 32768, 16384),
@@ -232,17 +237,29 @@ __global__ __launch_bounds__(TP_THREADS) void k_untile_region(const uint8_t *__r
  * (window, tile) pair of the table: tile (ty, tx) of the picture's grid, decoded into slot u.slot of the call's tiles, feeds window
  * regs[u.region].  The descriptor is section 13's, in the coordinates of the scaled picture (pic_width x pic_height: the scaled sides;
  * first_tile is not read).  A use that names no region of the table, a slot outside the buffer's [tile0, tile0 + m), a tile outside the
- * window's selection or a descriptor that is no window of a picture stores nothing. */
-template <int T>
-__global__ __launch_bounds__(TP_THREADS) void k_untile_window(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs,
-                                                               const nhw_window_use *__restrict__ uses, int tile0, int m)
+ * window's selection or a descriptor that is no window of a picture stores nothing.  k_untile_window_grey is the same over the one-byte
+ * pixels of a grey decode: slots of T T bytes, descriptors as they are with a pitch of at least the width. */
+template <int T, int C>
+__device__ __forceinline__ void window_band(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs, const nhw_window_use *__restrict__ uses, int tile0, int m)
 {
 	const nhw_window_use u = uses[blockIdx.x / (T / TP_ROWS)];
 	if (u.region >= (uint32_t)n_regs || u.slot < (uint32_t)tile0 || u.slot - (uint32_t)tile0 >= (uint32_t)m) return;
 	const nhw_region g = regs[u.region];
 	if (!rect_of_picture<T>(g)) return;
 	if (u.tx < g.x / T || u.tx > (g.x + g.width - 1) / T || u.ty < g.y / T || u.ty > (g.y + g.height - 1) / T) return;   /* not a tile of the window's selection */
-	crop_band<T>(tiles + (size_t)(u.slot - (uint32_t)tile0) * (size_t)(3 * T * T), u.ty, u.tx, g);
+	crop_band<T, C>(tiles + (size_t)(u.slot - (uint32_t)tile0) * (size_t)(C * T * T), u.ty, u.tx, g);
+}
+template <int T>
+__global__ __launch_bounds__(TP_THREADS) void k_untile_window(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs,
+                                                               const nhw_window_use *__restrict__ uses, int tile0, int m)
+{
+	window_band<T, 3>(tiles, regs, n_regs, uses, tile0, m);
+}
+template <int T>
+__global__ __launch_bounds__(TP_THREADS) void k_untile_window_grey(const uint8_t *__restrict__ tiles, const nhw_region *__restrict__ regs, int n_regs,
+                                                                    const nhw_window_use *__restrict__ uses, int tile0, int m)
+{
+	window_band<T, 1>(tiles, regs, n_regs, uses, tile0, m);
 }
 
 /* The SSE of decoded tiles against the pictures' own bytes: tile row rr of tile (ty, tx) against picture row 512 ty + rr < H, bytes
@@ -502,6 +519,14 @@ hipError_t nhw_launch_untile_window(const uint8_t *d_tiles, const nhw_region *d_
 	return with_tile_side(scale, [&](auto side) {
 		constexpr int T = decltype(side)::value;
 		k_untile_window<T><<<n_uses * (T / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
+	});
+}
+
+hipError_t nhw_launch_untile_window_grey(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses, int tile0, int m, int scale, hipStream_t s)
+{
+	return with_tile_side(scale, [&](auto side) {
+		constexpr int T = decltype(side)::value;
+		k_untile_window_grey<T><<<n_uses * (T / TP_ROWS), TP_THREADS, 0, s>>>(d_tiles, d_regs, n_regs, d_uses, tile0, m);
 	});
 }
 

@@ -9,6 +9,11 @@
  * it puts what the axes need into LDS (the kernel's only integer divisions), and a thread then makes one output pixel at a time as three
  * bytes B, G, R, which nhw_store_pixel (nhw_tensor.h) stores under the format's value rule, channel order and layout.  Pictures have any
  * alignment and pitch and tensors any width: the loads are byte loads that never touch a byte outside a row's 3 W, the stores single elements.
+ *
+ * Each kernel has the bytes a pixel, C, as its last template parameter.  C = 3 is the colour form described here, and
+ * what a kernel's name means without it.  C = 1 is the one-channel form, k_*_to_tensor<DT, 0, 1>: pictures of 1 byte a pixel (pitch >= W), the
+ * same positions, taps, weights, roundings, limits and mirror on the one channel, one element a pixel under scale[0] and bias[0]; the layout
+ * parameter means nothing there and is 0.
  */
 #include "nhw_tensor.h"
 #include "../../include/nhw_hip_debug.h"
@@ -54,6 +59,16 @@ __device__ __forceinline__ bool resample_entry(const nhw_picture *__restrict__ p
 	return resample_entry_at<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, limit, p, out, r0, nr, mirror, k);
 }
 
+/* The pixel's store.  C, the bytes a source pixel has and the elements an output pixel gets, is 3 (B, G, R: nhw_store_pixel) or 1 (the one-channel
+ * forms of DESIGN.md section 23: one element at out[rr w + c], the value rule with scale[0] and bias[0]; with one channel CHW and HWC are the
+ * same memory, and the grey kernels have no layout). */
+template <int DT, int CHW, int C>
+__device__ __forceinline__ void resample_store(typename NhwElem<DT>::type *out, size_t h, size_t w, size_t rr, size_t c, const uint32_t *b, const NhwTensorArgs &a)
+{
+	if constexpr (C == 3) nhw_store_pixel<DT, CHW>(out, h, w, rr, c, b, a);
+	else out[rr * w + c] = (typename NhwElem<DT>::type)nhw_tensor_elem<DT>(b[0], a.scale[0], a.bias[0]);
+}
+
 /* ---- the two taps ----
  * The position of output index o along an axis of source length n (1 .. 65535) and output length m (1 .. 4096): X = min(floor(128 t / m),
  * 256 (n - 1)) with t = max((2 o + 1) n - m, 0), the centre-aligned (o + 1/2) n / m - 1/2 clamped to the axis, in 1/256 pixel.  t is below
@@ -72,7 +87,7 @@ __device__ __forceinline__ uint32_t resize_pos(uint32_t o, uint32_t n, uint32_t 
  * nhw_tensor.h.  A workgroup puts the positions of all out_w columns and of its band's rows into LDS, and after the one barrier walks the band
  * 256 >> lg rows at a time, 1 << lg lanes a row (the power of two that holds out_w, 256 at the most: wider rows in steps).  A thread takes
  * one output pixel at a time: twelve byte loads (consecutive lanes on neighbouring source pixels), the blend, and the pixel's store. */
-template <int DT, int CHW>
+template <int DT, int CHW, int C = 3>
 __global__ __launch_bounds__(RS_THREADS) void k_resize_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
                                                                   NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
 {
@@ -92,13 +107,13 @@ __global__ __launch_bounds__(RS_THREADS) void k_resize_to_tensor(const nhw_pictu
 		const uint8_t *s1 = s0 + (uint64_t)(py >> 24) * p.pitch;
 		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
 		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
-			const uint32_t px = col_pos[mirror ? out_w - 1 - c : c], fx = px & 255u, x0 = 3 * ((px >> 8) & 0xFFFFu), x1 = x0 + 3 * (px >> 24);
+			const uint32_t px = col_pos[mirror ? out_w - 1 - c : c], fx = px & 255u, x0 = C * ((px >> 8) & 0xFFFFu), x1 = x0 + C * (px >> 24);
 			const uint32_t w00 = (256 - fx) * (256 - fy), w01 = fx * (256 - fy), w10 = (256 - fx) * fy, w11 = fx * fy;
-			uint32_t b[3];
+			uint32_t b[C];
 #pragma unroll
-			for (int ch = 0; ch < 3; ch++)
+			for (int ch = 0; ch < C; ch++)
 				b[ch] = (w00 * s0[x0 + ch] + w01 * s0[x1 + ch] + w10 * s1[x0 + ch] + w11 * s1[x1 + ch] + 32768u) >> 16;
-			nhw_store_pixel<DT, CHW>(out, H, W, rr, c, b, a);
+			resample_store<DT, CHW, C>(out, H, W, rr, c, b, a);
 		}
 	}
 }
@@ -122,17 +137,21 @@ __device__ __forceinline__ uint2 area_taps(uint32_t o, uint32_t n, uint32_t m)
 
 /* sum of weight x byte over the run of x taps t (area_taps) of the row at s, a channel at a time: wf first + m (those between) + wl last;
  * at most 255 x the axis total, below 2^24 */
+template <int C>
 __device__ __forceinline__ void area_row(const uint8_t *__restrict__ s, uint2 t, uint32_t m, uint32_t *r)
 {
 	const uint32_t cnt = t.x >> 16, wf = t.y & 0xFFFFu, wl = t.y >> 16;
-	const uint8_t *q = s + 3 * (t.x & 0xFFFFu);
-	uint32_t mid[3] = { 0, 0, 0 };
-	for (uint32_t i = 1; i + 1 < cnt; i++) { mid[0] += q[3 * i]; mid[1] += q[3 * i + 1]; mid[2] += q[3 * i + 2]; }
+	const uint8_t *q = s + C * (t.x & 0xFFFFu);
+	uint32_t mid[C] = {};
+	for (uint32_t i = 1; i + 1 < cnt; i++) {
 #pragma unroll
-	for (int ch = 0; ch < 3; ch++) r[ch] = wf * q[ch] + m * mid[ch];
+		for (int ch = 0; ch < C; ch++) mid[ch] += q[C * i + ch];
+	}
+#pragma unroll
+	for (int ch = 0; ch < C; ch++) r[ch] = wf * q[ch] + m * mid[ch];
 	if (cnt > 1) {
 #pragma unroll
-		for (int ch = 0; ch < 3; ch++) r[ch] += wl * q[3 * (cnt - 1) + ch];
+		for (int ch = 0; ch < C; ch++) r[ch] += wl * q[C * (cnt - 1) + ch];
 	}
 }
 
@@ -152,7 +171,7 @@ __device__ __forceinline__ uint32_t area_mean(uint64_t S, uint64_t D)
  * before the one barrier.  A pixel then reads its rows x columns source bytes once (neighbouring lanes on neighbouring runs): every row gives
  * three 32-bit sums (area_row), the rows between the first and the last add up in 32 bits as well (127 x 2^24 < 2^31), and only the three
  * products with the row weights and the division are 64 bits wide.  The loops run `count` times, at most 129 under the reduction limit. */
-template <int DT, int CHW>
+template <int DT, int CHW, int C = 3>
 __global__ __launch_bounds__(RS_THREADS) void k_area_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
                                                                 NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
 {
@@ -175,18 +194,18 @@ __global__ __launch_bounds__(RS_THREADS) void k_area_to_tensor(const nhw_picture
 		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
 		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
 			const uint2 tx = col_tap[mirror ? out_w - 1 - c : c];
-			uint32_t first[3], last[3] = { 0, 0, 0 }, mid[3] = { 0, 0, 0 }, b[3];
-			area_row(s, tx, out_w, first);
+			uint32_t first[C], last[C] = {}, mid[C] = {}, b[C];
+			area_row<C>(s, tx, out_w, first);
 			for (uint32_t i = 1; i + 1 < cy; i++) {
-				uint32_t v[3];
-				area_row(s + (uint64_t)i * p.pitch, tx, out_w, v);
-				mid[0] += v[0]; mid[1] += v[1]; mid[2] += v[2];
+				uint32_t v[C];
+				area_row<C>(s + (uint64_t)i * p.pitch, tx, out_w, v);
+				if constexpr (C == 3) { mid[0] += v[0]; mid[1] += v[1]; mid[2] += v[2]; } else mid[0] += v[0];   /* (spelled out: as a loop over the channels the colour form compiles to other instructions than it always had) */
 			}
-			if (cy > 1) area_row(s + (uint64_t)(cy - 1) * p.pitch, tx, out_w, last);
+			if (cy > 1) area_row<C>(s + (uint64_t)(cy - 1) * p.pitch, tx, out_w, last);
 #pragma unroll
-			for (int ch = 0; ch < 3; ch++)
+			for (int ch = 0; ch < C; ch++)
 				b[ch] = area_mean((uint64_t)(ty.y & 0xFFFFu) * first[ch] + (uint64_t)out_h * mid[ch] + (uint64_t)(ty.y >> 16) * last[ch], D);
-			nhw_store_pixel<DT, CHW>(out, H, W, rr, c, b, a);
+			resample_store<DT, CHW, C>(out, H, W, rr, c, b, a);
 		}
 	}
 }
@@ -263,11 +282,11 @@ __device__ __forceinline__ void cubic_weights(int16_t *w, uint32_t o, uint32_t r
  * runs and weights (a thread a column); in it per chunk of rows: its weights (a thread a row), barrier; in it per pass: H (a thread a source
  * row and column at a time), barrier, the vertical pass and the pixels' stores, barrier.  Every loop bound is one of these sizes or a count
  * clamped to its table's room. */
-template <int DT, int CHW>
+template <int DT, int CHW, int C = 3>
 __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows,
                                                                  NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
 {
-	__shared__ int16_t cb_h[3 * CB_HP], cb_wx[CB_W], cb_wy[CB_W];
+	__shared__ int16_t cb_h[C * CB_HP], cb_wx[CB_W], cb_wy[CB_W];
 	__shared__ uint32_t cb_col[CB_COLS], cb_row[RS_ROWS];
 	static_assert(CB_COLS <= RS_THREADS && RS_ROWS <= RS_THREADS, "a thread a run");
 	nhw_picture p;
@@ -308,16 +327,17 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
 					const uint8_t *src = reinterpret_cast<const uint8_t *>(p.addr + (uint64_t)(ylo + s) * p.pitch);
 					for (uint32_t j = threadIdx.x & (lanes - 1); j < ncol; j += lanes) {
 						const uint32_t run = cb_col[cs + j], cnt = (run >> 16) < tbx ? run >> 16 : tbx;
-						const uint8_t *q = src + 3 * (run & 0xFFFFu);
+						const uint8_t *q = src + C * (run & 0xFFFFu);
 						const int16_t *wt = cb_wx + (cs + j) * tbx;
-						int32_t acc[3] = { 0, 0, 0 };
+						int32_t acc[C] = {};
 						for (uint32_t i = 0; i < cnt; i++) {
 							const int32_t wi = wt[i];
-							acc[0] += wi * (int32_t)q[3 * i]; acc[1] += wi * (int32_t)q[3 * i + 1]; acc[2] += wi * (int32_t)q[3 * i + 2];
-						}
-						int16_t *hp = cb_h + 3 * (s * ncol + j);
 #pragma unroll
-						for (int ch = 0; ch < 3; ch++) hp[ch] = (int16_t)((acc[ch] + 128) >> 8);
+							for (int ch = 0; ch < C; ch++) acc[ch] += wi * (int32_t)q[C * i + ch];
+						}
+						int16_t *hp = cb_h + C * (s * ncol + j);
+#pragma unroll
+						for (int ch = 0; ch < C; ch++) hp[ch] = (int16_t)((acc[ch] + 128) >> 8);
 					}
 				}
 				__syncthreads();
@@ -326,19 +346,20 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
 					const int16_t *wt = cb_wy + r * tby;
 					const size_t rr = a.flip ? H - 1 - (r0 + rs + r) : r0 + rs + r;
 					for (uint32_t j = threadIdx.x & (lanes - 1); j < ncol; j += lanes) {
-						int32_t v[3] = { 0, 0, 0 };
-						uint32_t b[3];
+						int32_t v[C] = {};
+						uint32_t b[C];
 						for (uint32_t i = 0; i < cnt; i++) {
 							const int32_t wi = wt[i];
-							const int16_t *hp = cb_h + 3 * ((s0 + i) * ncol + j);
-							v[0] += wi * hp[0]; v[1] += wi * hp[1]; v[2] += wi * hp[2];
+							const int16_t *hp = cb_h + C * ((s0 + i) * ncol + j);
+#pragma unroll
+							for (int ch = 0; ch < C; ch++) v[ch] += wi * hp[ch];
 						}
 #pragma unroll
-						for (int ch = 0; ch < 3; ch++) {
+						for (int ch = 0; ch < C; ch++) {
 							const int32_t y = (v[ch] + (1 << 19)) >> 20;
 							b[ch] = (uint32_t)(y < 0 ? 0 : y > 255 ? 255 : y);
 						}
-						nhw_store_pixel<DT, CHW>(out, H, W, rr, mirror ? out_w - 1 - (ws + cs + j) : ws + cs + j, b, a);
+						resample_store<DT, CHW, C>(out, H, W, rr, mirror ? out_w - 1 - (ws + cs + j) : ws + cs + j, b, a);
 					}
 				}
 				__syncthreads();                                             /* before H, these rows' weights or the columns' are written again */
@@ -364,6 +385,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
  * 4.4 and 7.6 ms at 0, 30 and 90 degrees, blocks 2.6, 2.9 and 2.8 ms; the two meet at 15 degrees, d = 19 385, and the limit is the power of two below. */
 constexpr int32_t WARP_ROW_LANES = 16384;
 int32_t warp_row_limit = WARP_ROW_LANES;          /* host: what the launches pass as row_limit; nhw_debug_warp_row_limit (include/nhw_hip_debug.h) moves it */
+template <int C>
 __device__ __forceinline__ void warp_pixel(const nhw_warp &m, const nhw_picture &p, bool fill, int64_t bx, int64_t ey, uint32_t c, uint32_t *b)
 {
 	const int32_t xl = (int32_t)p.width - 1, yl = (int32_t)p.height - 1;     /* 0 .. 65534 */
@@ -378,8 +400,8 @@ __device__ __forceinline__ void warp_pixel(const nhw_warp &m, const nhw_picture 
 	const uint8_t *s0 = src + (uint64_t)(uint32_t)y0 * p.pitch, *s1 = src + (uint64_t)(uint32_t)y1 * p.pitch;
 	const uint32_t w00 = (256 - fx) * (256 - fy), w01 = fx * (256 - fy), w10 = (256 - fx) * fy, w11 = fx * fy;
 #pragma unroll
-	for (int ch = 0; ch < 3; ch++) {
-		uint32_t t00 = s0[3 * x0 + ch], t01 = s0[3 * x1 + ch], t10 = s1[3 * x0 + ch], t11 = s1[3 * x1 + ch];
+	for (int ch = 0; ch < C; ch++) {
+		uint32_t t00 = s0[C * x0 + ch], t01 = s0[C * x1 + ch], t10 = s1[C * x0 + ch], t11 = s1[C * x1 + ch];
 		if (oy0 || ox0) t00 = m.fill[ch];
 		if (oy0 || ox1) t01 = m.fill[ch];
 		if (oy1 || ox0) t10 = m.fill[ch];
@@ -388,7 +410,7 @@ __device__ __forceinline__ void warp_pixel(const nhw_warp &m, const nhw_picture 
 	}
 }
 
-template <int DT, int CHW>
+template <int DT, int CHW, int C = 3>
 __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture *__restrict__ pics, const nhw_warp *__restrict__ warps, uint32_t out_w, uint32_t out_h,
                                                                 int bands, int rows, int lg, int32_t row_limit, NhwTensorArgs a, const uint64_t *__restrict__ out_addr)
 {
@@ -411,9 +433,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
 			const uint32_t r = 8 * tr + (lane >> 3), c = 8 * tc + (lane & 7u);
 			if (r < nr && c < out_w) {
 				const int32_t ty = (int32_t)(2 * (r0 + r) + 1);
-				uint32_t b[3];
-				warp_pixel(m, p, fill, (int64_t)m.b * ty, (int64_t)m.e * ty, c, b);
-				nhw_store_pixel<DT, CHW>(out, H, W, a.flip ? H - 1 - (r0 + r) : r0 + r, c, b, a);
+				uint32_t b[C];
+				warp_pixel<C>(m, p, fill, (int64_t)m.b * ty, (int64_t)m.e * ty, c, b);
+				resample_store<DT, CHW, C>(out, H, W, a.flip ? H - 1 - (r0 + r) : r0 + r, c, b, a);
 			}
 			tc += RS_THREADS >> 6;
 		}
@@ -424,9 +446,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
 		const int64_t bx = (int64_t)m.b * ty, ey = (int64_t)m.e * ty;
 		const size_t rr = a.flip ? H - 1 - (r0 + r) : r0 + r;
 		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
-			uint32_t b[3];
-			warp_pixel(m, p, fill, bx, ey, c, b);
-			nhw_store_pixel<DT, CHW>(out, H, W, rr, c, b, a);
+			uint32_t b[C];
+			warp_pixel<C>(m, p, fill, bx, ey, c, b);
+			resample_store<DT, CHW, C>(out, H, W, rr, c, b, a);
 		}
 	}
 }
@@ -464,6 +486,29 @@ hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, i
 	return hipGetLastError();
 }
 
+/* f(the dtype as a std::integral_constant) for a checked format: what the one-channel launches are told apart by */
+template <class F> static void with_dtype(int dtype, F &&f)
+{
+	switch (dtype) {
+	case NHW_T_U8: f(std::integral_constant<int, NHW_T_U8>{}); break;
+	case NHW_T_F16: f(std::integral_constant<int, NHW_T_F16>{}); break;
+	case NHW_T_BF16: f(std::integral_constant<int, NHW_T_BF16>{}); break;
+	default: f(std::integral_constant<int, NHW_T_F32>{}); break;
+	}
+}
+
+hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                const uint64_t *d_out_addr, hipStream_t s)
+{
+	int lg, bands;
+	uint32_t rows;
+	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
+	with_dtype(dtype, [&](auto dt) {
+		k_warp_to_tensor<decltype(dt)::value, 0, 1><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr);
+	});
+	return hipGetLastError();
+}
+
 /* the developer's hook for measurements and tests: every later launch of the process walks by rows where |d| <= limit (-1: blocks for every
  * entry; 2^22: rows for every entry); a limit below -1 puts the rule's own back.  The results are the same bytes whatever the walk. */
 extern "C" void nhw_debug_warp_row_limit(int limit) { warp_row_limit = limit < -1 ? WARP_ROW_LANES : limit; }
@@ -486,6 +531,30 @@ hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uin
 			break;
 		default:
 			k_cubic_to_tensor<DT, CHW><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr);
+		}
+	});
+	return hipGetLastError();
+}
+
+/* the same launches for one-byte pixels and one-channel tensors: the same filters, band rule and LDS sizes */
+hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                    const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) return hipErrorInvalidValue;
+	int lg, bands;
+	uint32_t rows;
+	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
+	with_dtype(dtype, [&](auto dt) {
+		constexpr int DT = decltype(dt)::value;
+		switch (filter) {
+		case NHW_FILTER_TWO_TAP:
+			k_resize_to_tensor<DT, 0, 1><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+			break;
+		case NHW_FILTER_AREA:
+			k_area_to_tensor<DT, 0, 1><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+			break;
+		default:
+			k_cubic_to_tensor<DT, 0, 1><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr);
 		}
 	});
 	return hipGetLastError();

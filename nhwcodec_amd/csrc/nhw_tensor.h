@@ -26,7 +26,7 @@
 /* what a kernel gets of a format: dtype and layout are template parameters, the rest are kernel arguments (six floats and two flags, uniform) */
 struct NhwTensorArgs { float scale[3], bias[3]; int rgb, flip; };
 
-/* NHW_OK and the kernel's view of the format, or NHW_E_ARG with the reason in err.  grey: the caller is the grey decode, which
+/* NHW_OK and the kernel's view of the format, or NHW_E_ARG with the reason in err.  grey: the caller is the grey decode or a one-channel entry (section 23), which
  * takes NHW_T_GREY and nothing else; every other caller takes BGR and RGB and nothing else */
 inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a, std::string &err, bool grey = false)
 {
@@ -45,11 +45,12 @@ inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a,
 }
 /* the tensors of one size that a resampling or warping call makes, as its launcher takes them */
 struct NhwTensorOut { uint32_t w, h; int dtype, layout; NhwTensorArgs a; };
-/* ... and what every such entry checks of them, in this order: the sides, 1 .. 4096 each (the message names the entry), then the format */
-inline int nhw_tensor_out_check(const char *who, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *f, NhwTensorOut *o, std::string &err)
+/* ... and what every such entry checks of them, in this order: the sides, 1 .. 4096 each (the message names the entry), then the format -- as a
+ * one-channel entry where `grey` is set */
+inline int nhw_tensor_out_check(const char *who, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *f, NhwTensorOut *o, std::string &err, bool grey = false)
 {
 	if (out_width < 1 || out_height < 1 || out_width > 4096u || out_height > 4096u) { err = std::string(who) + ": an output side outside 1 .. 4096"; return NHW_E_ARG; }
-	if (const int rc = nhw_tensor_format_check(f, &o->a, err)) return rc;
+	if (const int rc = nhw_tensor_format_check(f, &o->a, err, grey)) return rc;
 	o->w = out_width; o->h = out_height; o->dtype = f->dtype; o->layout = f->layout;
 	return NHW_OK;
 }
@@ -312,6 +313,12 @@ __host__ __device__ inline bool nhw_warp_within(const nhw_warp &m)
 }
 hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
                            const uint64_t *d_out_addr, hipStream_t s);
+/* the one-channel forms of both: pictures of 1 byte a pixel to [out_h][out_w] elements under scale[0] and bias[0]; of a
+ * warp fill[0] alone is read */
+hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                    const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
+hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                const uint64_t *d_out_addr, hipStream_t s);
 /* nhw_picture.hip again, the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);

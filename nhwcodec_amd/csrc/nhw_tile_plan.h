@@ -45,7 +45,7 @@ struct TilePlan {
 	std::vector<uint64_t> toff;
 	std::vector<uint32_t> tlen;
 	std::vector<uint8_t> files;                                  /* the slots' tile files, slot after slot */
-	uint64_t bytes = 0;                                          /* 3 width height of every desc, summed: the packed pixels */
+	uint64_t bytes = 0;                                          /* px width height of every desc, summed: the packed pixels */
 };
 
 struct WindowsIn {
@@ -57,6 +57,7 @@ struct WindowsIn {
 	const uint64_t *dst_addr, *dst_pitch;                        /* both set: the descriptors' addresses and pitches; else running byte offsets and packed rows */
 	const char *who;                                             /* the entry point, for the message */
 	size_t max_tiles;                                            /* the uses one call takes */
+	uint32_t px = 3;                                             /* bytes a pixel of the packed rows and of `bytes`: 3, or 1 for a grey call */
 };
 
 /* Fills `p` and every status[i]: NHW_E_ARG for a rect that is empty, names no container, is refused or does not lie in the scaled picture,
@@ -87,9 +88,9 @@ inline int plan_windows(const WindowsIn &in, TilePlan &p, int32_t *status, std::
 		status[i] = NHW_OK;
 		uint32_t sw = 0, sh = 0;
 		nhw_rule_picture_scaled_size(c.w, c.h, in.scale, &sw, &sh);   /* the table describes the destination */
-		p.desc.push_back({ given ? in.dst_addr[i] : p.bytes, given ? in.dst_pitch[i] : 3ull * r.width, r.x, r.y, r.width, r.height, sw, sh, 0, 0 });
+		p.desc.push_back({ given ? in.dst_addr[i] : p.bytes, given ? in.dst_pitch[i] : (uint64_t)in.px * r.width, r.x, r.y, r.width, r.height, sw, sh, 0, 0 });
 		p.which.push_back(i);
-		p.bytes += 3ull * r.width * r.height;
+		p.bytes += (uint64_t)in.px * r.width * r.height;
 		std::vector<int32_t> &slot = slot_of[r.container];
 		if (slot.empty()) slot.assign((size_t)c.t, -1);
 		const uint32_t nx = (c.w + 511) / 512;                        /* the grid does not change with the scale */
