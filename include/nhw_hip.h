@@ -667,6 +667,49 @@ int nhw_dec_warps_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t
                                  uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
                                  int32_t *status);
 
+/* ---- a colour matrix a sample in the crop, resample and warp stores ----
+ * The photometric step that differs from sample to sample -- brightness, contrast about a fixed centre, saturation, a linear hue turn, a mix of
+ * the channels, an inversion, grey with some probability -- is one affine map of the pixel.  An entry of a mapped call carries one nhw_colour_map.
+ * The rule (the whole specification).  x = (x0, x1, x2) are the three bytes B, G, R that a resampler's (sections 18 to 20) or the warp's (section
+ * 21) blend has made for an output pixel; a warp's border colour went through that blend and is mapped like any other pixel.  All arithmetic is
+ * signed 32-bit:
+ *   t_i = m[i][0] x0 + m[i][1] x1 + m[i][2] x2 + o[i];   under the limits |t_i| <= 3 x 255 x 2^20 + 2^28 = 1 070 596 096, so t_i + 32768 fits;
+ *   y_i = min(max((t_i + 32768) >> 16, 0), 255);         the shift is arithmetic, floor((t_i + 32768) / 65536): halves go up, towards
+ *                                                        +infinity, at either sign.
+ * y then takes the place of the bytes in the pixel's store: the format's channel order, value rule, layout and row direction, and the mirror,
+ * are what they are without a map.  m = 65536 I, o = 0 is the identity on every byte ((65536 b + 32768) >> 16 = b).
+ * The one-channel form (section 23's pictures of one byte a pixel): y = clamp((m[0][0] x + o[0] + 32768) >> 16); the other ten numbers are not
+ * used for the value.
+ * A map is within the limits when each |m[i][j]| <= NHW_COLOUR_MAX_GAIN x 65536 = 2^20, each |o[i]| <= NHW_COLOUR_MAX_OFFSET x 65536 = 2^28 and
+ * the reserved words are 0 -- all twelve numbers, for both families.  An entry whose map is not stores nothing. */
+typedef struct nhw_colour_map {   /* 64 bytes, 4-byte aligned */
+	int32_t  m[3][3];     /* 1/65536; row i makes output byte i, column j reads input byte j, both in the byte path's order B, G, R; each |.| <= 2^20 */
+	int32_t  o[3];        /* 1/65536 of a grey level; each |.| <= 2^28 */
+	uint32_t reserved[4]; /* 0 */
+} nhw_colour_map;
+#define NHW_COLOUR_MAX_GAIN   16     /* 2^20 / 65536 */
+#define NHW_COLOUR_MAX_OFFSET 4096   /* 2^28 / 65536 */
+/* nhw_resample_to_tensor_device with a device table of n maps, d_maps[k] for picture k: the same arguments, reads, writes, passed-over entries,
+ * NHW_E_ARG cases in the same order, stream order and graph capture; a NULL d_maps is a call-level NHW_E_ARG before anything is launched.  The
+ * format names the family: with fmt->channels == NHW_T_GREY the call is nhw_resample_grey_to_tensor_device with maps -- pictures of 1 byte a
+ * pixel, one-channel tensors, the one-channel form of the rule --, with NHW_T_BGR or NHW_T_RGB the colour call. */
+int nhw_resample_mapped_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                         const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, void *stream);
+/* nhw_warp_to_tensor_device (nhw_warp_grey_to_tensor_device under a grey format) likewise */
+int nhw_warp_mapped_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                     const nhw_warp *d_warps, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, void *stream);
+/* nhw_dec_crops_to_device_resample (nhw_dec_crops_grey_to_device under a grey format) with one map a rect, host memory, never NULL: a
+ * call-level NHW_E_ARG beside dst_addr's.  A rect whose map is beyond the limits gets status NHW_E_ARG before it selects a tile, as a warp
+ * beyond its limits does: its destination is not written, and the other rects go on.  Everything else -- the tiles, the statuses, the
+ * statistics, the other refusals and their order -- is the unmapped call's; one handle serves mapped and unmapped calls in any order. */
+int nhw_dec_crops_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                   uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps,
+                                   const uint64_t *dst_addr, int32_t *status, int filter);
+/* nhw_dec_warps_to_device (nhw_dec_warps_grey_to_device under a grey format) likewise */
+int nhw_dec_warps_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                   uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
+                                   const uint64_t *dst_addr, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_dec_windows_grey_to_device.argtypes = L.nhw_dec_windows_to_device.argtypes
     L.nhw_dec_crops_grey_to_device.argtypes = L.nhw_dec_crops_to_device_resample.argtypes
     L.nhw_dec_warps_grey_to_device.argtypes = L.nhw_dec_warps_to_device.argtypes
+    a = L.nhw_resample_to_tensor_device.argtypes                                           # the mapped calls: the table of maps behind the flags or warps
+    L.nhw_resample_mapped_to_tensor_device.argtypes = a[:7] + [P] + a[7:]
+    a = L.nhw_warp_to_tensor_device.argtypes
+    L.nhw_warp_mapped_to_tensor_device.argtypes = a[:6] + [P] + a[6:]
+    a = L.nhw_dec_crops_to_device_resample.argtypes
+    L.nhw_dec_crops_mapped_to_device.argtypes = a[:11] + [P] + a[11:]
+    a = L.nhw_dec_warps_to_device.argtypes
+    L.nhw_dec_warps_mapped_to_device.argtypes = a[:11] + [P] + a[11:]
     return L
 
 
@@ -547,7 +555,7 @@ def _filter_limit(filter, w, h, out_w, out_h, what, which):
         raise NhwError(f"{what}: {which} is {w} x {h}, more than {limit} times the output's {out_w} x {out_h} along a side: beyond the {filter} filter's limit")
 
 
-def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
+def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None):
     """Pictures of any sizes to one batch tensor of one size (k_resize_to_tensor, nhw_resize_to_tensor_device): a list of uint8 CUDA tensors
     [H, W, 3] as for pictures_to_tensor_device, size = (out_h, out_w) of 1 .. 4096 each, flips: None or one boolean a picture ("mirror
     left-right") -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Picture k is resampled under the integer rule
@@ -556,18 +564,21 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
     instead, which does not alias; a picture more than AREA_MAX_REDUCTION times the output along a side is refused.  filter="cubic"
     (k_cubic_to_tensor, nhw_resample_to_tensor_device): the Keys cubic with a = -1/2, widened with the reduction, what
     PIL's BICUBIC and torch's antialiased bicubic compute, as an integer rule; the limit is CUBIC_MAX_REDUCTION.  Reads only the
-    pictures' own bytes.  Ordered on torch's current stream."""
-    return _resize_to_tensor("resize_to_tensor_device", 3, pictures, size, fmt, flips, filter)
+    pictures' own bytes.  Ordered on torch's current stream.  colours: None, or one colour map a picture (nhw_resample_mapped_to_tensor_device,
+    DESIGN.md section 24) -- a 3 x 4 matrix of floats on (R, G, B, 1) as colour_matrix makes it, or the twelve integers of colour_fixed --, applied
+    to the resampled bytes in front of the value rule: y = clamp((m x + o + 1/2) floored), in 1/65536."""
+    return _resize_to_tensor("resize_to_tensor_device", 3, pictures, size, fmt, flips, filter, colours)
 
 
-def resize_grey_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap"):
+def resize_grey_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None):
     """resize_to_tensor_device for one-channel pictures (nhw_resample_grey_to_tensor_device): a list of uint8 CUDA
     tensors [H, W] with strides (pitch >= W, 1), fmt a TensorFormat of channels "GREY" -> a new tensor [n, 1, out_h, out_w] or [n, out_h,
-    out_w, 1] of fmt.dtype.  The rules of the three filters on the one channel; the value rule with the format's one scale and bias."""
-    return _resize_to_tensor("resize_grey_to_tensor_device", 1, pictures, size, fmt, flips, filter)
+    out_w, 1] of fmt.dtype.  The rules of the three filters on the one channel; the value rule with the format's one scale and bias.  colours: None, or
+    one pair (gain, offset) a picture, the one-channel form of resize_to_tensor_device's maps."""
+    return _resize_to_tensor("resize_grey_to_tensor_device", 1, pictures, size, fmt, flips, filter, colours)
 
 
-def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter):
+def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter, colours=None):
     """resize_to_tensor_device (channels=3) and resize_grey_to_tensor_device (1)"""
     import torch
     _filter(filter, what)
@@ -577,6 +588,9 @@ def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter):
         for i, x in enumerate(pictures):
             if len(getattr(x, "shape", ())) == (3 if channels == 3 else 2):
                 _filter_limit(filter, int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
+        maps = _colour_table(colours, len(pictures), what, channels) if colours is not None else None   # (before a device is looked at, too)
+    elif colours is not None:
+        raise NhwError(f"{what}: `pictures` must be a list, one colour map a picture")
     table, _, dev = _picture_table(pictures, what, channels=channels)
     n = len(pictures)
     flags = _crop_flips(flips, n, what)
@@ -587,9 +601,14 @@ def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter):
     L = _library()
     c = fmt.c_struct()
     call = L.nhw_resample_to_tensor_device if channels == 3 else L.nhw_resample_grey_to_tensor_device
+    d_maps = _device_table(maps, dev) if colours is not None else None
     with torch.cuda.device(dev):
-        rc = call(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                  addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if colours is not None:
+            rc = L.nhw_resample_mapped_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                                                        d_maps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rc = call(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                      addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -737,23 +756,24 @@ def _warp_table(fixed, fill, flags):
     return t
 
 
-def warp_to_tensor_device(pictures, matrices, size, fmt, fill=(0, 0, 0), border="fill"):
+def warp_to_tensor_device(pictures, matrices, size, fmt, fill=(0, 0, 0), border="fill", colours=None):
     """Pictures sampled along tilted grids into one batch tensor of one size (k_warp_to_tensor, nhw_warp_to_tensor_device, DESIGN.md section
     21): pictures as for resize_to_tensor_device, matrices one warp a picture -- a 2 x 3 matrix of floats as warp_fixed takes it, in the
     picture's own coordinates, or the six integers (a, b, c, d, e, f) as warp_fixed returns them (a flat sequence of six integers, or an array
     of an integer dtype) --, size = (out_h, out_w) -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Two taps a
     direction at the position the warp gives, in integers; a tap outside the picture takes fill = (B, G, R), or with border="replicate" the
-    nearest edge pixel.  Reads only the pictures' own bytes.  Ordered on torch's current stream."""
-    return _warp_to_tensor("warp_to_tensor_device", 3, pictures, matrices, size, fmt, fill, border)
+    nearest edge pixel.  Reads only the pictures' own bytes.  Ordered on torch's current stream.  colours: as for resize_to_tensor_device
+    (nhw_warp_mapped_to_tensor_device); the border colour is mapped like any other pixel."""
+    return _warp_to_tensor("warp_to_tensor_device", 3, pictures, matrices, size, fmt, fill, border, colours)
 
 
-def warp_grey_to_tensor_device(pictures, matrices, size, fmt, fill=0, border="fill"):
+def warp_grey_to_tensor_device(pictures, matrices, size, fmt, fill=0, border="fill", colours=None):
     """warp_to_tensor_device for one-channel pictures (nhw_warp_grey_to_tensor_device): pictures and fmt as for
-    resize_grey_to_tensor_device, fill one byte -> a new tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype."""
-    return _warp_to_tensor("warp_grey_to_tensor_device", 1, pictures, matrices, size, fmt, fill, border)
+    resize_grey_to_tensor_device, fill one byte -> a new tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype; colours as there."""
+    return _warp_to_tensor("warp_grey_to_tensor_device", 1, pictures, matrices, size, fmt, fill, border, colours)
 
 
-def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border):
+def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border, colours=None):
     """warp_to_tensor_device (channels=3) and warp_grey_to_tensor_device (1)"""
     import numpy as np
     import torch
@@ -763,6 +783,7 @@ def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border)
     if not isinstance(pictures, (list, tuple)) or not isinstance(matrices, (list, tuple, np.ndarray)) or len(matrices) != len(pictures):
         raise NhwError(f"{what}: `pictures` and `matrices` must be lists of the same length, one warp a picture")
     warps = _warp_table([_warp_entry(m, f"{what}: matrix {i}") for i, m in enumerate(matrices)], fill, flags)
+    maps = _colour_table(colours, len(pictures), what, channels) if colours is not None else None
     table, _, dev = _picture_table(pictures, what, channels=channels)
     n = len(pictures)
     out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
@@ -772,11 +793,133 @@ def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border)
     L = _library()
     c = fmt.c_struct()
     call = L.nhw_warp_to_tensor_device if channels == 3 else L.nhw_warp_grey_to_tensor_device
+    d_maps = _device_table(maps, dev) if colours is not None else None
     with torch.cuda.device(dev):
-        rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        if colours is not None:
+            rc = L.nhw_warp_mapped_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), d_maps.data_ptr(), addr.data_ptr(),
+                                                    torch.cuda.current_stream(dev).cuda_stream)
+        else:
+            rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
+
+
+# ---------------------------------------------------------------- a colour matrix a sample
+COLOUR_DTYPE = [("m", "<i4", (3, 3)), ("o", "<i4", (3,)), ("reserved", "<u4", (4,))]   # nhw_colour_map, 64 bytes
+COLOUR_MAX_GAIN = 16                               # NHW_COLOUR_MAX_GAIN: a matrix entry is 16 in magnitude at the most (2^20 / 65536)
+COLOUR_MAX_OFFSET = 4096                           # NHW_COLOUR_MAX_OFFSET: an offset is 4096 grey levels in magnitude at the most (2^28 / 65536)
+_COLOUR_GAIN, _COLOUR_OFFSET = COLOUR_MAX_GAIN << 16, COLOUR_MAX_OFFSET << 16
+_YIQ = ((0.299, 0.587, 0.114), (0.596, -0.274, -0.322), (0.211, -0.523, 0.312))
+
+
+def _colour_affine(matrix, what):
+    """`matrix` as a float64 array [3, 4] of finite numbers, or raises"""
+    import numpy as np
+    try:
+        m = np.asarray(matrix)
+        m = m.astype(np.float64) if m.dtype.kind in "iuf" else None
+    except (TypeError, ValueError):
+        m = None
+    if m is None or m.shape != (3, 4):
+        raise NhwError(f"{what}: a colour map is a 3 x 4 matrix of numbers on (R, G, B, 1), got {matrix!r}")
+    if not np.isfinite(m).all():
+        raise NhwError(f"{what}: a colour map's entries must be finite, got {m.tolist()!r}")
+    return m
+
+
+def colour_compose(first, then):
+    """the affine map that applies `first` and then `then`, both float [3, 4] on (R, G, B, 1): then[:, :3] @ first, with then's offset added"""
+    import numpy as np
+    a, b = _colour_affine(first, "colour_compose"), _colour_affine(then, "colour_compose")
+    return np.concatenate([b[:, :3] @ a[:, :3], (b[:, :3] @ a[:, 3] + b[:, 3])[:, None]], axis=1)
+
+
+def colour_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, centre=128.0):
+    """ColorJitter as one affine map: a float64 [3, 4] matrix on (R, G, B, 1) in byte units (0 .. 255), the composition, applied in this order,
+    of brightness x -> b x; contrast x -> c x + (1 - c) centre; saturation x -> s x + (1 - s) L with L = 0.299 R + 0.587 G + 0.114 B; and hue,
+    a rotation by 2 pi hue of the I, Q plane of YIQ, inv(T) Rot T with T = [[0.299, 0.587, 0.114], [0.596, -0.274, -0.322], [0.211, -0.523,
+    0.312]] -- the linear form DALI and TensorFlow use, which keeps Y and keeps greys grey.  colour_fixed turns it into the integers the mapped
+    calls take; colour_compose chains it with other maps (a channel mix, an inversion, a grey).
+    This is not torchvision's chain, bit for bit or otherwise: there is no clamp to 0 .. 255 between the steps (only the one at the end of the
+    rule), contrast pivots on the given `centre`, not on the picture's own mean grey, and hue is the linear YIQ turn, not a shift of H through
+    HSV."""
+    import numpy as np
+    try:
+        b, c, s, h, z = (float(v) for v in (brightness, contrast, saturation, hue, centre))
+    except (TypeError, ValueError):
+        raise NhwError("colour_matrix: brightness, contrast, saturation, hue and centre must be numbers") from None
+    if not all(math.isfinite(v) for v in (b, c, s, h, z)):
+        raise NhwError(f"colour_matrix: the parameters must be finite, got {(brightness, contrast, saturation, hue, centre)!r}")
+    eye, zero = np.eye(3), np.zeros((3, 1))
+    luma = np.tile(np.array(_YIQ[0]), (3, 1))
+    t = np.array(_YIQ)
+    cs, sn = math.cos(2 * math.pi * h), math.sin(2 * math.pi * h)
+    rot = np.array([[1.0, 0.0, 0.0], [0.0, cs, -sn], [0.0, sn, cs]])
+    steps = [np.hstack([b * eye, zero]), np.hstack([c * eye, np.full((3, 1), (1 - c) * z)]), np.hstack([s * eye + (1 - s) * luma, zero]),
+             np.hstack([np.linalg.solve(t, rot @ t) if h else eye, zero])]     # (no turn is the identity exactly, not to the solver's last bit)
+    m = steps[0]
+    for step in steps[1:]:
+        m = colour_compose(m, step)
+    return m
+
+
+def colour_fixed(matrix):
+    """A colour map in nhw_colour_map's fixed point.  matrix: 3 x 4 floats on (R, G, B, 1) in byte units, as colour_matrix returns it -> the twelve
+    integers of the struct in its order B, G, R: m[0][0], m[0][1], .. m[2][2], then o[0], o[1], o[2], each rint(65536 value) in float64, ties to
+    even, with rows and columns 0 and 2 of the matrix exchanged (row 0 of the struct makes B, column 0 reads B).  Raises NhwError for an entry
+    that is not finite or beyond the limits: |m| <= 2^20 (COLOUR_MAX_GAIN), |o| <= 2^28 (COLOUR_MAX_OFFSET grey levels)."""
+    import numpy as np
+    a = _colour_affine(matrix, "colour_fixed")
+    v = np.rint(a[::-1] * 65536.0)
+    m, o = v[:, 2::-1], v[:, 3]
+    if not ((np.abs(m) <= _COLOUR_GAIN).all() and (np.abs(o) <= _COLOUR_OFFSET).all()):
+        raise NhwError(f"colour_fixed: the map {a.tolist()!r} is beyond the limits: matrix entries of {COLOUR_MAX_GAIN}, offsets of {COLOUR_MAX_OFFSET} grey levels")
+    return tuple(int(x) for x in m.reshape(9)) + tuple(int(x) for x in o)
+
+
+def _colour_table(colours, n, what, channels=3):
+    """the nhw_colour_map table of a call's `colours`, a numpy array of COLOUR_DTYPE: n entries, each a 3 x 4 matrix of floats (through
+    colour_fixed) or the twelve integers as colour_fixed returns them (an integer array [12]); channels=1: each a pair (gain, offset), which
+    goes to m[0][0] and o[0] as rint(65536 value).  Host only; raises for a wrong count or shape, a number that is not finite, a map beyond
+    the limits"""
+    import numpy as np
+    if not isinstance(colours, (list, tuple, np.ndarray)) or len(colours) != n:
+        raise NhwError(f"{what}: `colours` must be {n} colour maps, one a sample, got {len(colours) if hasattr(colours, '__len__') else colours!r}")
+    t = np.zeros(n, COLOUR_DTYPE)
+    for i, c in enumerate(colours):
+        who = f"{what}: colours[{i}]"
+        try:
+            a = np.asarray(c)
+        except Exception:
+            a = None
+        if channels == 1:
+            if a is None or a.shape != (2,) or a.dtype.kind not in "iuf":
+                raise NhwError(f"{who}: a grey call takes a pair (gain, offset) of numbers, got {c!r}")
+            a = a.astype(np.float64)
+            v = np.rint(a * 65536.0)
+            if not np.isfinite(a).all() or abs(v[0]) > _COLOUR_GAIN or abs(v[1]) > _COLOUR_OFFSET:
+                raise NhwError(f"{who}: the pair {a.tolist()!r} is not finite or beyond the limits: a gain of {COLOUR_MAX_GAIN}, an offset of {COLOUR_MAX_OFFSET} grey levels")
+            t[i]["m"][0, 0], t[i]["o"][0] = int(v[0]), int(v[1])
+            continue
+        if a is not None and a.dtype.kind in "iu" and a.shape == (12,):
+            twelve = [int(x) for x in a]
+            if any(abs(x) > _COLOUR_GAIN for x in twelve[:9]) or any(abs(x) > _COLOUR_OFFSET for x in twelve[9:]):
+                raise NhwError(f"{who}: the map {tuple(twelve)!r} is beyond the limits: matrix entries of 2^20, offsets of 2^28")
+        else:
+            try:
+                twelve = colour_fixed(_colour_affine(c, who))
+            except NhwError as e:
+                raise NhwError(f"{who}: {e}") from None
+        t[i]["m"], t[i]["o"] = np.array(twelve[:9]).reshape(3, 3), twelve[9:]
+    return t
+
+
+def _device_table(maps, dev):
+    """a table of COLOUR_DTYPE on the device, as 64-bit words"""
+    import numpy as np
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(maps).view(np.int64).copy()).to(dev)
 
 
 TENSOR_PICTURE_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("plane", "<u8"), ("width", "<u4"), ("height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_tensor_picture
@@ -1704,13 +1847,14 @@ class Decoder:
             raise NhwError("decode_pictures_grey wants a non-empty list of containers")
         return self.decode_windows_grey(containers, [(i, 0, 0) + scaled_size(*picture_info(c), scale) for i, c in enumerate(containers)], scale)
 
-    def decode_crops_grey_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap"):
+    def decode_crops_grey_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap", colours=None):
         """decode_crops_device as grey (nhw_dec_crops_grey_to_device): fmt a TensorFormat of channels "GREY" -> (tensor
         [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype, the list of the scales used).  The scales and windows are chosen as there,
-        the filters and their limits are the same, and so are the tiles and the statuses; out: at least n * out_h * out_w elements."""
-        return self._crops_to_batch("decode_crops_grey_device", 1, containers, crops, size, fmt, flips, scale, out, filter)
+        the filters and their limits are the same, and so are the tiles and the statuses; out: at least n * out_h * out_w elements.
+        colours: None, or one pair (gain, offset) a crop (nhw_dec_crops_mapped_to_device under a grey format)."""
+        return self._crops_to_batch("decode_crops_grey_device", 1, containers, crops, size, fmt, flips, scale, out, filter, colours)
 
-    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap"):
+    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap", colours=None):
         """RandomResizedCrop's decode (nhw_dec_crops_to_device): crops, a sequence of (container index, x, y, w, h), each
         resampled to size = (out_h, out_w), mirrored left-right where flips[i] is true, and stored under fmt -> (tensor [n, 3, out_h, out_w]
         or [n, out_h, out_w, 3] of fmt.dtype on this decoder's device, the list of the scales used).  With a scale (1, 2 or 4) the crops
@@ -1721,10 +1865,12 @@ class Decoder:
         rule (nhw_dec_crops_to_device_filter): the scales and windows are chosen as before, and a window more than
         AREA_MAX_REDUCTION times the output along a side is refused before any call; filter="cubic" resizes them under the cubic rule
         (nhw_dec_crops_to_device_resample, section 20) with the limit CUBIC_MAX_REDUCTION.  Raises on any status that is not NHW_OK.  The
-        work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls."""
-        return self._crops_to_batch("decode_crops_device", 3, containers, crops, size, fmt, flips, scale, out, filter)
+        work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls.  colours: None, or
+        one colour map a crop (nhw_dec_crops_mapped_to_device), as resize_to_tensor_device takes them: ColorJitter,
+        RandomGrayscale, a channel mix or an inversion of each sample in the resampler's store."""
+        return self._crops_to_batch("decode_crops_device", 3, containers, crops, size, fmt, flips, scale, out, filter, colours)
 
-    def _crops_to_batch(self, what, channels, containers, crops, size, fmt, flips, scale, out, filter):
+    def _crops_to_batch(self, what, channels, containers, crops, size, fmt, flips, scale, out, filter, colours=None):
         """decode_crops_device (channels=3) and decode_crops_grey_device (1)"""
         import numpy as np
         _filter(filter, what)
@@ -1732,6 +1878,10 @@ class Decoder:
         out_h, out_w = _crop_size(size, what)
         if scale is not None:
             scale = _scale(scale, what)
+        if colours is not None:
+            if not isinstance(crops, (list, tuple, np.ndarray)):
+                raise NhwError(f"{what}: `crops` must be a sequence, one colour map a crop")
+            maps = _colour_table(colours, len(crops), what, channels)
         blob, offs, table = self._region_args(containers, crops, what)
         n = len(table)
         flags = _crop_flips(flips, n, what)
@@ -1748,14 +1898,18 @@ class Decoder:
         if filter in _LIMITS:
             for i, r in enumerate(table):
                 _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
+        if colours is not None:
+            return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
+                                        lambda *args: self.lib.nhw_dec_crops_mapped_to_device(*args, RESAMPLERS[filter]), channels, maps), scales
         call = self.lib.nhw_dec_crops_to_device_resample if channels == 3 else self.lib.nhw_dec_crops_grey_to_device
         return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
                                     lambda *args: call(*args, RESAMPLERS[filter]), channels), scales
 
-    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3):
+    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3, maps=None):
         """the device side of decode_crops_device and decode_warps_device: the checked batch tensor (`out`, or a new one), and per scale one
         call(handle, blob, offsets, n containers, the scale's rects, their count, scale, out_w, out_h, format, the scale's rows of `extra` --
-        the flag bytes or the nhw_warp table, or None --, the tensors' addresses, statuses) -> rc.  Raises on any status that is not NHW_OK"""
+        the flag bytes or the nhw_warp table, or None --, the tensors' addresses, statuses) -> rc; with `maps`, the nhw_colour_map table of a mapped call, the
+        scale's rows of it go in front of the addresses.  Raises on any status that is not NHW_OK"""
         import numpy as np
         t = self.torch
         n = len(table)
@@ -1774,19 +1928,20 @@ class Decoder:
             idx = np.flatnonzero(np.array(scales) == s)
             sub, a, st = np.ascontiguousarray(table[idx]), np.ascontiguousarray(addr[idx]), np.empty(len(idx), np.int32)
             x = np.ascontiguousarray(extra[idx]) if extra is not None else None
+            mp = (np.ascontiguousarray(maps[idx]),) if maps is not None else ()
             self._chk(call(self.h, blob.ctypes.data, offs.ctypes.data, n_containers, sub.ctypes.data, len(idx), s, out_w, out_h,
-                           ctypes.byref(c), x.ctypes.data if x is not None else None, a.ctypes.data, st.ctypes.data))
+                           ctypes.byref(c), x.ctypes.data if x is not None else None, *(m.ctypes.data for m in mp), a.ctypes.data, st.ctypes.data))
             status[idx] = st
         self._region_raise(status)
         return out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)
 
-    def decode_warps_grey_device(self, containers, which, matrices, size, fmt, fill=0, border="fill", scale=None, out=None):
+    def decode_warps_grey_device(self, containers, which, matrices, size, fmt, fill=0, border="fill", scale=None, out=None, colours=None):
         """decode_warps_device as grey (nhw_dec_warps_grey_to_device): fmt a TensorFormat of channels "GREY", fill one
         byte -> (tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype, the list of the scales used).  The scales and windows are
-        chosen as there."""
-        return self._warps_to_batch("decode_warps_grey_device", 1, containers, which, matrices, size, fmt, fill, border, scale, out)
+        chosen as there.  colours: None, or one pair (gain, offset) a warp."""
+        return self._warps_to_batch("decode_warps_grey_device", 1, containers, which, matrices, size, fmt, fill, border, scale, out, colours)
 
-    def decode_warps_device(self, containers, which, matrices, size, fmt, fill=(0, 0, 0), border="fill", scale=None, out=None):
+    def decode_warps_device(self, containers, which, matrices, size, fmt, fill=(0, 0, 0), border="fill", scale=None, out=None, colours=None):
         """RandomAffine's / RandomRotation's decode (nhw_dec_warps_to_device): warp i samples the picture of container
         which[i] along the grid of matrices[i] -- a 2 x 3 matrix of floats as warp_fixed takes it, in FULL-resolution picture coordinates
         (crop_warp makes one from a rectangle, an angle and a flip) -- into size = (out_h, out_w), and is stored under fmt -> (tensor [n, 3,
@@ -1796,10 +1951,11 @@ class Decoder:
         -- and the result is, byte for byte, the warp of the whole picture decoded at that scale under warp_fixed(matrix / scale).  A tap
         outside the picture takes fill = (B, G, R), or with border="replicate" the nearest edge pixel.  out: as for decode_crops_device.
         Raises on any status that is not NHW_OK.  The work is ordered after torch's current stream and complete on return; region_stats
-        speaks of the last of the calls."""
-        return self._warps_to_batch("decode_warps_device", 3, containers, which, matrices, size, fmt, fill, border, scale, out)
+        speaks of the last of the calls.  colours: None, or one colour map a warp (nhw_dec_warps_mapped_to_device), as
+        decode_crops_device takes them; the border colour is mapped like any other pixel."""
+        return self._warps_to_batch("decode_warps_device", 3, containers, which, matrices, size, fmt, fill, border, scale, out, colours)
 
-    def _warps_to_batch(self, what, channels, containers, which, matrices, size, fmt, fill, border, scale, out):
+    def _warps_to_batch(self, what, channels, containers, which, matrices, size, fmt, fill, border, scale, out, colours=None):
         """decode_warps_device (channels=3) and decode_warps_grey_device (1)"""
         import numpy as np
         fmt = _tensor_format(fmt, what, grey=channels == 1)
@@ -1812,6 +1968,7 @@ class Decoder:
         if not isinstance(which, (list, tuple, np.ndarray)) or not isinstance(matrices, (list, tuple, np.ndarray)) or len(which) < 1 or len(which) != len(matrices):
             raise NhwError(f"{what}: `which` and `matrices` must be non-empty and of the same length: one container index and one matrix a warp")
         n = len(which)
+        maps = _colour_table(colours, n, what, channels) if colours is not None else None
         for i, ci in enumerate(which):
             if isinstance(ci, bool) or not isinstance(ci, numbers.Integral) or not 0 <= ci < len(containers):
                 raise NhwError(f"{what}: which[{i}] must be a container index of 0 .. {len(containers) - 1}, got {ci!r}")
@@ -1825,6 +1982,9 @@ class Decoder:
             rects.append((int(ci),) + win)
             fixed.append(fx)
         blob, offs, table = self._region_args(containers, rects, what)
+        if colours is not None:
+            return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
+                                        self.lib.nhw_dec_warps_mapped_to_device, channels, maps), scales
         return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
                                     self.lib.nhw_dec_warps_to_device if channels == 3 else self.lib.nhw_dec_warps_grey_to_device, channels), scales
 

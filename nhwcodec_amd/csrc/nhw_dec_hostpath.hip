@@ -2,6 +2,7 @@
  * .nhwp containers (nhw_dec_pictures, nhw_dec_regions*, nhw_dec_windows*, nhw_dec_crops_to_device*, and the window, crop and warp calls as grey, nhw_dec_*_grey*), the BMP header.  They reach the kernels only through nhw_dec_batch_device (nhw_dec.hip), nhw_picture.hip and nhw_resample.hip. */
 #include "nhw_dec.h"
 #include "nhw_tensor.h"
+#include "nhw_colour.h"
 #include "nhw_tile_plan.h"
 
 /* the host paths' buffers: the blob (grow-only, room for `total` bytes of files) and, on the first call, the per-file arrays and the
@@ -184,7 +185,7 @@ enum WindowsMode {
 	WIN_TO_DEVICE,                                               /* dst_addr / dst_pitch: cropped straight into the caller's device memory; nothing is left to do */
 	WIN_TO_TENSORS                                               /* crop, dst_addr the tensors' addresses: packed as for the host form, then resampled or warped (crops_finish) */
 };
-struct CropSpec { NhwTensorOut out; const uint8_t *flags; int filter; const nhw_warp *warps; };
+struct CropSpec { NhwTensorOut out; const uint8_t *flags; int filter; const nhw_warp *warps; const nhw_colour_map *maps = nullptr; /* one a rect, or none */ };
 struct WindowsCall {
 	WindowsMode mode = WIN_TO_HOST;
 	uint8_t *bgr = nullptr; const uint64_t *out_off = nullptr, *dst_addr = nullptr, *dst_pitch = nullptr;
@@ -209,13 +210,14 @@ static int windows_check(const nhw_dec *d, const uint8_t *blob, const uint64_t *
 
 /* The rects a crop or warp call refuses (NHW_E_ARG) before they select a tile: with the area filter or the cubic one
  * (section 20), a rect whose window is beyond the filter's reduction limit for the output size; with warps (section 21), one whose warp is
- * beyond the limits. */
+ * beyond the limits; with maps (section 24), one whose map is. */
 static std::vector<uint8_t> crop_refusals(const CropSpec &crop, const nhw_rect *rects, int nr)
 {
 	const uint64_t limit = nhw_filter_limit(crop.filter);               /* 0 for none */
 	std::vector<uint8_t> refused((size_t)nr);
 	for (int i = 0; i < nr; i++)
-		refused[(size_t)i] = (limit && (rects[i].width > limit * crop.out.w || rects[i].height > limit * crop.out.h)) || (crop.warps && !nhw_warp_within(crop.warps[i]));
+		refused[(size_t)i] = (limit && (rects[i].width > limit * crop.out.w || rects[i].height > limit * crop.out.h)) || (crop.warps && !nhw_warp_within(crop.warps[i])) ||
+		                     (crop.maps && !nhw_colour_within(crop.maps[i]));
 	return refused;
 }
 
@@ -243,7 +245,8 @@ static int upload_plan(nhw_dec *d, TilePlan &p, bool staged)
  * window whose tiles all decoded to its tensor.  crop_tab holds what the launch reads, one entry a rect: nr pictures (32 bytes each; a rect
  * that has no window keeps a zero picture), nr tensor addresses (0 for a rect without a window or with a tile that failed, which the kernel
  * passes over), and behind them either the nr flag bytes -- k_resize_to_tensor, k_area_to_tensor or k_cubic_to_tensor by the filter -- or
- * the nr warps (32 + 8 bytes an entry in front: they are 8-byte aligned) -- k_warp_to_tensor, warps[i] sampling window i along its tilted grid. */
+ * the nr warps (32 + 8 bytes an entry in front: they are 8-byte aligned) -- k_warp_to_tensor, warps[i] sampling window i along its tilted grid.
+ * A mapped call (section 24) has its nr colour maps behind that table, at the next multiple of 8, and launches the mapped forms of the same kernels. */
 static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, const uint64_t *dst_addr, int nr, const int32_t *status, bool grey)
 {
 	static_assert(sizeof(nhw_warp) == 40 && sizeof(nhw_picture) == 32, "the crop table's layout");
@@ -255,21 +258,26 @@ static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, con
 		if (status[i] == NHW_OK) oaddr[i] = dst_addr[i];
 	}
 	const size_t pics_bytes = (size_t)nr * sizeof(nhw_picture), addr_bytes = (size_t)nr * 8;
-	HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + (size_t)nr * (crop.warps ? sizeof(nhw_warp) : 1)));
+	const size_t last_bytes = ((size_t)nr * (crop.warps ? sizeof(nhw_warp) : 1) + 7) & ~(size_t)7, maps_bytes = crop.maps ? (size_t)nr * sizeof(nhw_colour_map) : 0;
+	HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + last_bytes + maps_bytes));
 	uint8_t *tab = d->crop_tab.as<uint8_t>(), *last = tab + pics_bytes + addr_bytes;
+	const nhw_colour_map *d_maps = (const nhw_colour_map *)(last + last_bytes);
 	const nhw_picture *d_pics = (const nhw_picture *)tab;
 	const uint64_t *d_addr = (const uint64_t *)(tab + pics_bytes);
 	const NhwTensorOut &o = crop.out;
 	hipStream_t s = d->own_stream;
 	HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
+	if (crop.maps) HIPCHK(hipMemcpyAsync(last + last_bytes, crop.maps, maps_bytes, hipMemcpyHostToDevice, s));
 	if (crop.warps) {
 		HIPCHK(hipMemcpyAsync(last, crop.warps, (size_t)nr * sizeof(nhw_warp), hipMemcpyHostToDevice, s));
-		HIPCHK(grey ? nhw_launch_warp_grey(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.a, d_addr, s)
+		if (crop.maps) HIPCHK(nhw_launch_warp_mapped(grey, d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_addr, s));
+		else HIPCHK(grey ? nhw_launch_warp_grey(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.a, d_addr, s)
 		            : nhw_launch_warp(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_addr, s));
 	} else {
 		if (crop.flags) HIPCHK(hipMemcpyAsync(last, crop.flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		HIPCHK(grey ? nhw_launch_resample_grey(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.a, crop.flags ? last : nullptr, d_addr, s)
+		if (crop.maps) HIPCHK(nhw_launch_resample_mapped(grey, crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_maps, d_addr, s));
+		else HIPCHK(grey ? nhw_launch_resample_grey(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.a, crop.flags ? last : nullptr, d_addr, s)
 		            : nhw_launch_resample(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_addr, s));
 	}
 	HIPCHK(hipStreamSynchronize(s));
@@ -429,6 +437,36 @@ extern "C" int nhw_dec_warps_grey_to_device(nhw_dec *d, const uint8_t *blob, con
 	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_grey_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, true)) return rc;
 	WindowsCall c;
 	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = true; c.who = "nhw_dec_warps_grey_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+/* ---------------------------------------------------------------------------------------------- the crop and warp calls with a colour map a rect */
+/* nhw_dec_crops_to_device_resample's and nhw_dec_warps_to_device's checks in their order, the NULL map table beside dst_addr; a format that names
+ * NHW_T_GREY makes the call the one-channel one */
+extern "C" int nhw_dec_crops_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps,
+                                              const uint64_t *dst_addr, int32_t *status, int filter)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_mapped_to_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!dst_addr || !maps || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = fmt && fmt->channels == NHW_T_GREY;
+	CropSpec crop = { {}, flags, filter, nullptr, maps };
+	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_mapped_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
+	WindowsCall c;
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_crops_mapped_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+extern "C" int nhw_dec_warps_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
+                                              const uint64_t *dst_addr, int32_t *status)
+{
+	if (!warps || !maps || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = fmt && fmt->channels == NHW_T_GREY;
+	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps, maps };
+	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_mapped_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
+	WindowsCall c;
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_warps_mapped_to_device";
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
 }
 

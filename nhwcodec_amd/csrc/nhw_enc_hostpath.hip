@@ -222,6 +222,33 @@ extern "C" int nhw_warp_grey_to_tensor_device(const nhw_picture *d_pics, int n, 
 	return NHW_OK;
 }
 
+/* ... and both with a colour map an entry: the unmapped entries' checks in their order, the NULL map table among the NULL
+ * pointers; a format that names NHW_T_GREY makes the call the one-channel one */
+static bool names_grey(const nhw_tensor_format *fmt) { return fmt && fmt->channels == NHW_T_GREY; }
+
+extern "C" int nhw_resample_mapped_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                                    const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, void *stream)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_mapped_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!d_pics || !d_maps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = names_grey(fmt);
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_resample_mapped_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
+	HIPCHK(nhw_launch_resample_mapped(grey, filter, d_pics, n, o.w, o.h, o.dtype, o.layout, o.a, d_flags, d_maps, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_warp_mapped_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                                const nhw_warp *d_warps, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_warps || !d_maps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = names_grey(fmt);
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_warp_mapped_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
+	HIPCHK(nhw_launch_warp_mapped(grey, d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
 static int tensor_in_args(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
 {

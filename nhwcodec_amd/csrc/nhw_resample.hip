@@ -14,8 +14,14 @@
  * what a kernel's name means without it.  C = 1 is the one-channel form, k_*_to_tensor<DT, 0, 1>: pictures of 1 byte a pixel (pitch >= W), the
  * same positions, taps, weights, roundings, limits and mirror on the one channel, one element a pixel under scale[0] and bias[0]; the layout
  * parameter means nothing there and is 0.
+ *
+ * Each kernel has a mapped form as well: its template parameters end in a pack M, empty in the forms above, and its
+ * arguments in `M... maps`, which is then nothing at all -- those forms have the arguments, registers and instructions they had before the pack.
+ * With M = const nhw_colour_map * the workgroup reads its entry's map once (EntryMap), stores nothing unless the map is within the limits, and puts
+ * every pixel's bytes through nhw_colour_apply (nhw_colour.h) between the blend and resample_store.
  */
 #include "nhw_tensor.h"
+#include "nhw_colour.h"
 #include "../../include/nhw_hip_debug.h"
 
 namespace {
@@ -69,6 +75,19 @@ __device__ __forceinline__ void resample_store(typename NhwElem<DT>::type *out, 
 	else out[rr * w + c] = (typename NhwElem<DT>::type)nhw_tensor_elem<DT>(b[0], a.scale[0], a.bias[0]);
 }
 
+/* The map of a workgroup's entry, by the kernel's pack M.  No table: nothing is held, read or done, and the kernel is what
+ * it is without this.  A table: maps[k], read once -- k is uniform, so are the twelve numbers --, `load` false for a map beyond the limits (the
+ * entry then stores nothing), `apply` the rule on a pixel's C bytes. */
+template <class... M> struct EntryMap {
+	__device__ __forceinline__ bool load(int, M...) { return true; }
+	template <int C> __device__ __forceinline__ void apply(uint32_t *) const {}
+};
+template <> struct EntryMap<const nhw_colour_map *> {
+	nhw_colour_map c;
+	__device__ __forceinline__ bool load(int k, const nhw_colour_map *maps) { c = maps[k]; return nhw_colour_within(c); }
+	template <int C> __device__ __forceinline__ void apply(uint32_t *b) const { nhw_colour_apply<C>(c, b); }
+};
+
 /* ---- the two taps ----
  * The position of output index o along an axis of source length n (1 .. 65535) and output length m (1 .. 4096): X = min(floor(128 t / m),
  * 256 (n - 1)) with t = max((2 o + 1) n - m, 0), the centre-aligned (o + 1/2) n / m - 1/2 clamped to the axis, in 1/256 pixel.  t is below
@@ -87,9 +106,9 @@ __device__ __forceinline__ uint32_t resize_pos(uint32_t o, uint32_t n, uint32_t 
  * nhw_tensor.h.  A workgroup puts the positions of all out_w columns and of its band's rows into LDS, and after the one barrier walks the band
  * 256 >> lg rows at a time, 1 << lg lanes a row (the power of two that holds out_w, 256 at the most: wider rows in steps).  A thread takes
  * one output pixel at a time: twelve byte loads (consecutive lanes on neighbouring source pixels), the blend, and the pixel's store. */
-template <int DT, int CHW, int C = 3>
+template <int DT, int CHW, int C = 3, class... M>
 __global__ __launch_bounds__(RS_THREADS) void k_resize_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
-                                                                  NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
+                                                                  NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, M... maps)
 {
 	__shared__ uint32_t col_pos[RS_MAX], row_pos[RS_ROWS];
 	nhw_picture p;
@@ -97,6 +116,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_resize_to_tensor(const nhw_pictu
 	uint32_t r0, nr;
 	bool mirror;
 	if (!resample_entry<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, 0, p, out, r0, nr, mirror)) return;
+	EntryMap<M...> cm;
+	if (!cm.load((int)(blockIdx.x / bands), maps...)) return;
 	for (uint32_t o = threadIdx.x; o < out_w; o += RS_THREADS) col_pos[o] = resize_pos(o, p.width, out_w);
 	if (threadIdx.x < nr) row_pos[threadIdx.x] = resize_pos(r0 + threadIdx.x, p.height, out_h);
 	__syncthreads();
@@ -113,6 +134,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_resize_to_tensor(const nhw_pictu
 #pragma unroll
 			for (int ch = 0; ch < C; ch++)
 				b[ch] = (w00 * s0[x0 + ch] + w01 * s0[x1 + ch] + w10 * s1[x0 + ch] + w11 * s1[x1 + ch] + 32768u) >> 16;
+			cm.template apply<C>(b);
 			resample_store<DT, CHW, C>(out, H, W, rr, c, b, a);
 		}
 	}
@@ -171,9 +193,9 @@ __device__ __forceinline__ uint32_t area_mean(uint64_t S, uint64_t D)
  * before the one barrier.  A pixel then reads its rows x columns source bytes once (neighbouring lanes on neighbouring runs): every row gives
  * three 32-bit sums (area_row), the rows between the first and the last add up in 32 bits as well (127 x 2^24 < 2^31), and only the three
  * products with the row weights and the division are 64 bits wide.  The loops run `count` times, at most 129 under the reduction limit. */
-template <int DT, int CHW, int C = 3>
+template <int DT, int CHW, int C = 3, class... M>
 __global__ __launch_bounds__(RS_THREADS) void k_area_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows, int lg,
-                                                                NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
+                                                                NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, M... maps)
 {
 	extern __shared__ uint2 area_tab[];                                    /* [out_w] columns, then [rows] rows */
 	nhw_picture p;
@@ -181,6 +203,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_area_to_tensor(const nhw_picture
 	uint32_t r0, nr;
 	bool mirror;
 	if (!resample_entry<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, NHW_AREA_MAX_REDUCTION, p, out, r0, nr, mirror)) return;
+	EntryMap<M...> cm;
+	if (!cm.load((int)(blockIdx.x / bands), maps...)) return;
 	uint2 *col_tap = area_tab, *row_tap = area_tab + out_w;
 	for (uint32_t o = threadIdx.x; o < out_w; o += RS_THREADS) col_tap[o] = area_taps(o, p.width, out_w);
 	if (threadIdx.x < nr) row_tap[threadIdx.x] = area_taps(r0 + threadIdx.x, p.height, out_h);
@@ -205,6 +229,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_area_to_tensor(const nhw_picture
 #pragma unroll
 			for (int ch = 0; ch < C; ch++)
 				b[ch] = area_mean((uint64_t)(ty.y & 0xFFFFu) * first[ch] + (uint64_t)out_h * mid[ch] + (uint64_t)(ty.y >> 16) * last[ch], D);
+			cm.template apply<C>(b);
 			resample_store<DT, CHW, C>(out, H, W, rr, c, b, a);
 		}
 	}
@@ -282,9 +307,9 @@ __device__ __forceinline__ void cubic_weights(int16_t *w, uint32_t o, uint32_t r
  * runs and weights (a thread a column); in it per chunk of rows: its weights (a thread a row), barrier; in it per pass: H (a thread a source
  * row and column at a time), barrier, the vertical pass and the pixels' stores, barrier.  Every loop bound is one of these sizes or a count
  * clamped to its table's room. */
-template <int DT, int CHW, int C = 3>
+template <int DT, int CHW, int C = 3, class... M>
 __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_picture *__restrict__ pics, uint32_t out_w, uint32_t out_h, int bands, int rows,
-                                                                 NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr)
+                                                                 NhwTensorArgs a, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, M... maps)
 {
 	__shared__ int16_t cb_h[C * CB_HP], cb_wx[CB_W], cb_wy[CB_W];
 	__shared__ uint32_t cb_col[CB_COLS], cb_row[RS_ROWS];
@@ -294,6 +319,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
 	uint32_t r0, nr;
 	bool mirror;
 	if (!resample_entry<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, NHW_CUBIC_MAX_REDUCTION, p, out, r0, nr, mirror)) return;
+	EntryMap<M...> cm;
+	if (!cm.load((int)(blockIdx.x / bands), maps...)) return;
 	const uint32_t Dx = p.width > out_w ? p.width : out_w, Dy = p.height > out_h ? p.height : out_h;
 	const uint32_t tbx = 4 * Dx / out_w + 1, tby = 4 * Dy / out_h + 1;          /* 5 .. 129 */
 	uint32_t wc = out_w < (uint32_t)CB_COLS ? out_w : (uint32_t)CB_COLS;        /* columns whose weights are held at a time */
@@ -359,6 +386,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
 							const int32_t y = (v[ch] + (1 << 19)) >> 20;
 							b[ch] = (uint32_t)(y < 0 ? 0 : y > 255 ? 255 : y);
 						}
+						cm.template apply<C>(b);
 						resample_store<DT, CHW, C>(out, H, W, rr, mirror ? out_w - 1 - (ws + cs + j) : ws + cs + j, b, a);
 					}
 				}
@@ -410,9 +438,9 @@ __device__ __forceinline__ void warp_pixel(const nhw_warp &m, const nhw_picture 
 	}
 }
 
-template <int DT, int CHW, int C = 3>
+template <int DT, int CHW, int C = 3, class... M>
 __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture *__restrict__ pics, const nhw_warp *__restrict__ warps, uint32_t out_w, uint32_t out_h,
-                                                                int bands, int rows, int lg, int32_t row_limit, NhwTensorArgs a, const uint64_t *__restrict__ out_addr)
+                                                                int bands, int rows, int lg, int32_t row_limit, NhwTensorArgs a, const uint64_t *__restrict__ out_addr, M... maps)
 {
 	nhw_picture p;
 	typename NhwElem<DT>::type *out;
@@ -422,6 +450,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
 	if (!resample_entry_at<DT>(pics, nullptr, out_addr, out_w, out_h, bands, rows, 0, p, out, r0, nr, mirror, k)) return;
 	const nhw_warp m = warps[k];
 	if (!nhw_warp_within(m)) return;
+	EntryMap<M...> cm;
+	if (!cm.load(k, maps...)) return;
 	const bool fill = !(m.flags & NHW_WARP_REPLICATE);
 	const size_t W = out_w, H = out_h;
 	if ((m.d < 0 ? -m.d : m.d) > row_limit) {                                /* a wavefront an 8 x 8 block of output pixels (|d| <= 2^22: checked) */
@@ -435,6 +465,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
 				const int32_t ty = (int32_t)(2 * (r0 + r) + 1);
 				uint32_t b[C];
 				warp_pixel<C>(m, p, fill, (int64_t)m.b * ty, (int64_t)m.e * ty, c, b);
+				cm.template apply<C>(b);
 				resample_store<DT, CHW, C>(out, H, W, a.flip ? H - 1 - (r0 + r) : r0 + r, c, b, a);
 			}
 			tc += RS_THREADS >> 6;
@@ -448,6 +479,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
 		for (uint32_t c = threadIdx.x & ((1u << lg) - 1); c < out_w; c += 1u << lg) {
 			uint32_t b[C];
 			warp_pixel<C>(m, p, fill, bx, ey, c, b);
+			cm.template apply<C>(b);
 			resample_store<DT, CHW, C>(out, H, W, rr, c, b, a);
 		}
 	}
@@ -473,15 +505,18 @@ static bool resample_bands(int n, uint32_t out_w, uint32_t out_h, int &lg, uint3
 	return true;
 }
 
-hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                           const uint64_t *d_out_addr, hipStream_t s)
+/* The four launches, each with the pack M of its kernels: empty for the calls that have no maps, const nhw_colour_map * and the
+ * device table of n maps for those that do. */
+template <class... M>
+static hipError_t launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                              const uint64_t *d_out_addr, hipStream_t s, M... maps)
 {
 	int lg, bands;
 	uint32_t rows;
 	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
 	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
 		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
-		k_warp_to_tensor<DT, CHW><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr);
+		k_warp_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr, maps...);
 	});
 	return hipGetLastError();
 }
@@ -497,14 +532,15 @@ template <class F> static void with_dtype(int dtype, F &&f)
 	}
 }
 
-hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                const uint64_t *d_out_addr, hipStream_t s)
+template <class... M>
+static hipError_t launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                   const uint64_t *d_out_addr, hipStream_t s, M... maps)
 {
 	int lg, bands;
 	uint32_t rows;
 	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
 	with_dtype(dtype, [&](auto dt) {
-		k_warp_to_tensor<decltype(dt)::value, 0, 1><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr);
+		k_warp_to_tensor<decltype(dt)::value, 0, 1, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr, maps...);
 	});
 	return hipGetLastError();
 }
@@ -513,8 +549,9 @@ hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_war
  * entry; 2^22: rows for every entry); a limit below -1 puts the rule's own back.  The results are the same bytes whatever the walk. */
 extern "C" void nhw_debug_warp_row_limit(int limit) { warp_row_limit = limit < -1 ? WARP_ROW_LANES : limit; }
 
-hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                               const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+template <class... M>
+static hipError_t launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                  const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s, M... maps)
 {
 	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) return hipErrorInvalidValue;
 	int lg, bands;
@@ -524,21 +561,22 @@ hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uin
 		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
 		switch (filter) {
 		case NHW_FILTER_TWO_TAP:
-			k_resize_to_tensor<DT, CHW><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+			k_resize_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
 			break;
 		case NHW_FILTER_AREA:
-			k_area_to_tensor<DT, CHW><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+			k_area_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
 			break;
 		default:
-			k_cubic_to_tensor<DT, CHW><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr);
+			k_cubic_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr, maps...);
 		}
 	});
 	return hipGetLastError();
 }
 
 /* the same launches for one-byte pixels and one-channel tensors: the same filters, band rule and LDS sizes */
-hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                    const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+template <class... M>
+static hipError_t launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                       const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s, M... maps)
 {
 	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) return hipErrorInvalidValue;
 	int lg, bands;
@@ -548,14 +586,50 @@ hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n
 		constexpr int DT = decltype(dt)::value;
 		switch (filter) {
 		case NHW_FILTER_TWO_TAP:
-			k_resize_to_tensor<DT, 0, 1><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+			k_resize_to_tensor<DT, 0, 1, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
 			break;
 		case NHW_FILTER_AREA:
-			k_area_to_tensor<DT, 0, 1><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr);
+			k_area_to_tensor<DT, 0, 1, M...><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
 			break;
 		default:
-			k_cubic_to_tensor<DT, 0, 1><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr);
+			k_cubic_to_tensor<DT, 0, 1, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr, maps...);
 		}
 	});
 	return hipGetLastError();
+}
+
+hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                               const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+{
+	return launch_resample(filter, d_pics, n, out_w, out_h, dtype, layout, a, d_flags, d_out_addr, s);
+}
+hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                    const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
+{
+	return launch_resample_grey(filter, d_pics, n, out_w, out_h, dtype, a, d_flags, d_out_addr, s);
+}
+hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                           const uint64_t *d_out_addr, hipStream_t s)
+{
+	return launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s);
+}
+hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
+                                const uint64_t *d_out_addr, hipStream_t s)
+{
+	return launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s);
+}
+/* ... and with a device table of n maps; `grey`: the one-channel kernels, which take no layout */
+hipError_t nhw_launch_resample_mapped(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                      const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (!d_maps) return hipErrorInvalidValue;
+	return grey ? launch_resample_grey(filter, d_pics, n, out_w, out_h, dtype, a, d_flags, d_out_addr, s, d_maps)
+	            : launch_resample(filter, d_pics, n, out_w, out_h, dtype, layout, a, d_flags, d_out_addr, s, d_maps);
+}
+hipError_t nhw_launch_warp_mapped(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
+                                  const NhwTensorArgs &a, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (!d_maps) return hipErrorInvalidValue;
+	return grey ? launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s, d_maps)
+	            : launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s, d_maps);
 }

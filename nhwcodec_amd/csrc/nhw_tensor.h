@@ -319,6 +319,13 @@ hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n
                                     const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
 hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
                                 const uint64_t *d_out_addr, hipStream_t s);
+/* the four launches above with a device table of n colour maps, d_maps[k] for entry k (the rule and nhw_colour_within are in
+ * nhw_colour.h): the mapped forms of the same kernels under the same band rule.  `grey`: the one-channel forms, which read no layout.  An entry
+ * whose map is not within the limits stores nothing: the kernel checks it, and the host paths that know a map refuse it before they launch. */
+hipError_t nhw_launch_resample_mapped(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                      const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s);
+hipError_t nhw_launch_warp_mapped(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
+                                  const NhwTensorArgs &a, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s);
 /* nhw_picture.hip again, the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
