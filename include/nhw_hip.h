@@ -710,6 +710,49 @@ int nhw_dec_warps_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64
                                    uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
                                    const uint64_t *dst_addr, int32_t *status);
 
+/* ---- a tone table a sample in the crop, resample and warp stores; histograms for equalize and autocontrast ----
+ * The pointwise operations that are no affine map -- posterize, solarize, gamma, a curve, equalize, autocontrast -- are one table of 256 bytes a
+ * channel.  An entry of a toned call carries one nhw_tone_table.
+ * The rule (the whole specification).  y = (y0, y1, y2) are the three bytes B, G, R that the blend, and then the colour map if the call has one
+ * (section 24), have made for an output pixel:  z_i = t[i][y_i].  z then takes the place of the bytes in the pixel's store.  The order is fixed:
+ * blend, map, table, value rule; a warp's border colour goes through all of it.  The one-channel form (section 23) reads t[0] alone: the other 512
+ * bytes are ignored, not checked.  Every table is valid: there is no predicate and no refusal for a table. */
+typedef struct nhw_tone_table { uint8_t t[3][256]; } nhw_tone_table;   /* 768 bytes, any alignment; rows in the byte path's order B, G, R */
+/* what nhw_tone_from_hist_device makes of a sample's histograms, one byte a sample; the rules are nhwcodec_amd/csrc/nhw_tone.h's, in 64-bit sums:
+ * equalize -- PIL's ImageOps.equalize, torchvision's _scale_channel: total = sum h, last = the count of the highest non-empty bin, step = (total -
+ *   last) / 255; step == 0: the identity; else row[0] = 0, row[x] = min((h[0] + .. + h[x - 1] + step / 2) / step, 255);
+ * autocontrast -- lo, hi the lowest and highest non-empty bin; lo >= hi or nothing counted: the identity; else row[x] = clamp(floor(255 (x - lo) /
+ *   (hi - lo)), 0, 255), exactly (torchvision computes it in float32 and may differ by one level where the quotient is an integer). */
+#define NHW_TONE_KEEP         0      /* the sample's table is left exactly as it is (so is it under any op not named here) */
+#define NHW_TONE_EQUALIZE     1
+#define NHW_TONE_AUTOCONTRAST 2
+/* nhw_resample_mapped_to_tensor_device with a device table of n tone tables, d_tones[k] for picture k.  d_maps may be NULL: no map, the table acts
+ * on the blend's bytes.  A NULL d_tones is a call-level NHW_E_ARG among the NULL-pointer checks, before anything is launched.  With a map, an
+ * entry whose map is beyond the limits stores nothing.  Every other check, message, order, stream and capture property is the mapped entry's; a
+ * format of NHW_T_GREY makes it the one-channel call. */
+int nhw_resample_toned_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                        const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, void *stream);
+/* nhw_warp_mapped_to_tensor_device likewise */
+int nhw_warp_toned_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                    const nhw_warp *d_warps, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, void *stream);
+/* nhw_dec_crops_mapped_to_device with one table a rect, host memory, never NULL; maps may be NULL.  Everything else is the mapped call's (without
+ * maps, the unmapped call's); one handle serves plain, mapped and toned calls in any order. */
+int nhw_dec_crops_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                  uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps,
+                                  const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status, int filter);
+/* nhw_dec_warps_mapped_to_device likewise */
+int nhw_dec_warps_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                  uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
+                                  const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status);
+/* The histograms of the n pictures of a device table, as the resamplers take it (any address, pitch and sides of 1 .. 65535; `channels` 3 or 1
+ * bytes a pixel): d_hist[k][c][v], uint32 [n][channels][256], is the number of pixels of picture k whose byte c is v.  The call overwrites d_hist
+ * (it zeroes it on the stream first); a picture with a zero address or a zero or oversize side gives zeroes.  Integer sums: the same words every
+ * run.  Reads only the pictures' own bytes.  Asynchronous on `stream`, capturable. */
+int nhw_hist_device(const nhw_picture *d_pics, int n, int channels, uint32_t *d_hist, void *stream);
+/* Rows of tone tables from histograms: for sample k and channel c, d_ops[k] (NHW_TONE_*) says what d_tones[k].t[c] becomes of d_hist[k][c]; with
+ * channels == 1 only t[0] is written.  The histograms need not come from a picture.  Asynchronous on `stream`, capturable. */
+int nhw_tone_from_hist_device(const uint32_t *d_hist, int n, int channels, const uint8_t *d_ops, nhw_tone_table *d_tones, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

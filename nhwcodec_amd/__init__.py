@@ -141,6 +141,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_dec_crops_mapped_to_device.argtypes = a[:11] + [P] + a[11:]
     a = L.nhw_dec_warps_to_device.argtypes
     L.nhw_dec_warps_mapped_to_device.argtypes = a[:11] + [P] + a[11:]
+    a = L.nhw_resample_mapped_to_tensor_device.argtypes                                    # the toned calls: the table of tone tables behind the maps
+    L.nhw_resample_toned_to_tensor_device.argtypes = a[:8] + [P] + a[8:]
+    a = L.nhw_warp_mapped_to_tensor_device.argtypes
+    L.nhw_warp_toned_to_tensor_device.argtypes = a[:7] + [P] + a[7:]
+    a = L.nhw_dec_crops_mapped_to_device.argtypes
+    L.nhw_dec_crops_toned_to_device.argtypes = a[:12] + [P] + a[12:]
+    a = L.nhw_dec_warps_mapped_to_device.argtypes
+    L.nhw_dec_warps_toned_to_device.argtypes = a[:12] + [P] + a[12:]
+    L.nhw_hist_device.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P]
+    L.nhw_tone_from_hist_device.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, P]
     return L
 
 
@@ -555,7 +565,7 @@ def _filter_limit(filter, w, h, out_w, out_h, what, which):
         raise NhwError(f"{what}: {which} is {w} x {h}, more than {limit} times the output's {out_w} x {out_h} along a side: beyond the {filter} filter's limit")
 
 
-def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None):
+def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None, tones=None):
     """Pictures of any sizes to one batch tensor of one size (k_resize_to_tensor, nhw_resize_to_tensor_device): a list of uint8 CUDA tensors
     [H, W, 3] as for pictures_to_tensor_device, size = (out_h, out_w) of 1 .. 4096 each, flips: None or one boolean a picture ("mirror
     left-right") -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Picture k is resampled under the integer rule
@@ -566,19 +576,23 @@ def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", c
     PIL's BICUBIC and torch's antialiased bicubic compute, as an integer rule; the limit is CUBIC_MAX_REDUCTION.  Reads only the
     pictures' own bytes.  Ordered on torch's current stream.  colours: None, or one colour map a picture (nhw_resample_mapped_to_tensor_device,
     DESIGN.md section 24) -- a 3 x 4 matrix of floats on (R, G, B, 1) as colour_matrix makes it, or the twelve integers of colour_fixed --, applied
-    to the resampled bytes in front of the value rule: y = clamp((m x + o + 1/2) floored), in 1/65536."""
-    return _resize_to_tensor("resize_to_tensor_device", 3, pictures, size, fmt, flips, filter, colours)
+    to the resampled bytes in front of the value rule: y = clamp((m x + o + 1/2) floored), in 1/65536.  tones: None, or one tone table a picture
+    (nhw_resample_toned_to_tensor_device) -- uint8 [3, 256] on R, G, B as the tone_* builders make it --, or a uint8 CUDA tensor
+    [n, 768] in the struct's own order, as tone_from_hist_device returns it; the table acts on the bytes behind the map: z = t[y].  colours and
+    tones combine."""
+    return _resize_to_tensor("resize_to_tensor_device", 3, pictures, size, fmt, flips, filter, colours, tones)
 
 
-def resize_grey_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None):
+def resize_grey_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None, tones=None):
     """resize_to_tensor_device for one-channel pictures (nhw_resample_grey_to_tensor_device): a list of uint8 CUDA
     tensors [H, W] with strides (pitch >= W, 1), fmt a TensorFormat of channels "GREY" -> a new tensor [n, 1, out_h, out_w] or [n, out_h,
     out_w, 1] of fmt.dtype.  The rules of the three filters on the one channel; the value rule with the format's one scale and bias.  colours: None, or
-    one pair (gain, offset) a picture, the one-channel form of resize_to_tensor_device's maps."""
-    return _resize_to_tensor("resize_grey_to_tensor_device", 1, pictures, size, fmt, flips, filter, colours)
+    one pair (gain, offset) a picture, the one-channel form of resize_to_tensor_device's maps.  tones: None, or one table uint8 [256] a picture (or
+    the CUDA tensor [n, 768], of which a sample's first 256 bytes are read)."""
+    return _resize_to_tensor("resize_grey_to_tensor_device", 1, pictures, size, fmt, flips, filter, colours, tones)
 
 
-def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter, colours=None):
+def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter, colours=None, tones=None):
     """resize_to_tensor_device (channels=3) and resize_grey_to_tensor_device (1)"""
     import torch
     _filter(filter, what)
@@ -589,8 +603,9 @@ def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter, colour
             if len(getattr(x, "shape", ())) == (3 if channels == 3 else 2):
                 _filter_limit(filter, int(x.shape[1]), int(x.shape[0]), out_w, out_h, what, f"picture {i}")
         maps = _colour_table(colours, len(pictures), what, channels) if colours is not None else None   # (before a device is looked at, too)
-    elif colours is not None:
-        raise NhwError(f"{what}: `pictures` must be a list, one colour map a picture")
+        tabs = _tone_arg(tones, len(pictures), what, channels) if tones is not None else None
+    elif colours is not None or tones is not None:
+        raise NhwError(f"{what}: `pictures` must be a list, one colour map or tone table a picture")
     table, _, dev = _picture_table(pictures, what, channels=channels)
     n = len(pictures)
     flags = _crop_flips(flips, n, what)
@@ -602,8 +617,13 @@ def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter, colour
     c = fmt.c_struct()
     call = L.nhw_resample_to_tensor_device if channels == 3 else L.nhw_resample_grey_to_tensor_device
     d_maps = _device_table(maps, dev) if colours is not None else None
+    d_tones = _device_tones(tabs, dev, what) if tones is not None else None
     with torch.cuda.device(dev):
-        if colours is not None:
+        if tones is not None:
+            rc = L.nhw_resample_toned_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                                                       d_maps.data_ptr() if d_maps is not None else None, d_tones.data_ptr(), addr.data_ptr(),
+                                                       torch.cuda.current_stream(dev).cuda_stream)
+        elif colours is not None:
             rc = L.nhw_resample_mapped_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
                                                         d_maps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
         else:
@@ -756,24 +776,25 @@ def _warp_table(fixed, fill, flags):
     return t
 
 
-def warp_to_tensor_device(pictures, matrices, size, fmt, fill=(0, 0, 0), border="fill", colours=None):
+def warp_to_tensor_device(pictures, matrices, size, fmt, fill=(0, 0, 0), border="fill", colours=None, tones=None):
     """Pictures sampled along tilted grids into one batch tensor of one size (k_warp_to_tensor, nhw_warp_to_tensor_device, DESIGN.md section
     21): pictures as for resize_to_tensor_device, matrices one warp a picture -- a 2 x 3 matrix of floats as warp_fixed takes it, in the
     picture's own coordinates, or the six integers (a, b, c, d, e, f) as warp_fixed returns them (a flat sequence of six integers, or an array
     of an integer dtype) --, size = (out_h, out_w) -> a new tensor [n, 3, out_h, out_w] or [n, out_h, out_w, 3] of fmt.dtype.  Two taps a
     direction at the position the warp gives, in integers; a tap outside the picture takes fill = (B, G, R), or with border="replicate" the
     nearest edge pixel.  Reads only the pictures' own bytes.  Ordered on torch's current stream.  colours: as for resize_to_tensor_device
-    (nhw_warp_mapped_to_tensor_device); the border colour is mapped like any other pixel."""
-    return _warp_to_tensor("warp_to_tensor_device", 3, pictures, matrices, size, fmt, fill, border, colours)
+    (nhw_warp_mapped_to_tensor_device); the border colour is mapped like any other pixel.  tones: as for resize_to_tensor_device
+    (nhw_warp_toned_to_tensor_device); the border colour goes through the table too."""
+    return _warp_to_tensor("warp_to_tensor_device", 3, pictures, matrices, size, fmt, fill, border, colours, tones)
 
 
-def warp_grey_to_tensor_device(pictures, matrices, size, fmt, fill=0, border="fill", colours=None):
+def warp_grey_to_tensor_device(pictures, matrices, size, fmt, fill=0, border="fill", colours=None, tones=None):
     """warp_to_tensor_device for one-channel pictures (nhw_warp_grey_to_tensor_device): pictures and fmt as for
-    resize_grey_to_tensor_device, fill one byte -> a new tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype; colours as there."""
-    return _warp_to_tensor("warp_grey_to_tensor_device", 1, pictures, matrices, size, fmt, fill, border, colours)
+    resize_grey_to_tensor_device, fill one byte -> a new tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype; colours and tones as there."""
+    return _warp_to_tensor("warp_grey_to_tensor_device", 1, pictures, matrices, size, fmt, fill, border, colours, tones)
 
 
-def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border, colours=None):
+def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border, colours=None, tones=None):
     """warp_to_tensor_device (channels=3) and warp_grey_to_tensor_device (1)"""
     import numpy as np
     import torch
@@ -784,6 +805,7 @@ def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border,
         raise NhwError(f"{what}: `pictures` and `matrices` must be lists of the same length, one warp a picture")
     warps = _warp_table([_warp_entry(m, f"{what}: matrix {i}") for i, m in enumerate(matrices)], fill, flags)
     maps = _colour_table(colours, len(pictures), what, channels) if colours is not None else None
+    tabs = _tone_arg(tones, len(pictures), what, channels) if tones is not None else None
     table, _, dev = _picture_table(pictures, what, channels=channels)
     n = len(pictures)
     out = torch.empty((n,) + fmt.shape(out_h, out_w), dtype=fmt.dtype, device=dev)
@@ -794,8 +816,12 @@ def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border,
     c = fmt.c_struct()
     call = L.nhw_warp_to_tensor_device if channels == 3 else L.nhw_warp_grey_to_tensor_device
     d_maps = _device_table(maps, dev) if colours is not None else None
+    d_tones = _device_tones(tabs, dev, what) if tones is not None else None
     with torch.cuda.device(dev):
-        if colours is not None:
+        if tones is not None:
+            rc = L.nhw_warp_toned_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), d_maps.data_ptr() if d_maps is not None else None,
+                                                   d_tones.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        elif colours is not None:
             rc = L.nhw_warp_mapped_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), d_maps.data_ptr(), addr.data_ptr(),
                                                     torch.cuda.current_stream(dev).cuda_stream)
         else:
@@ -920,6 +946,187 @@ def _device_table(maps, dev):
     import numpy as np
     import torch
     return torch.from_numpy(np.ascontiguousarray(maps).view(np.int64).copy()).to(dev)
+
+
+# ---------------------------------------------------------------- a tone table a sample; histograms
+TONE_OPS = {"keep": 0, "equalize": 1, "autocontrast": 2}     # NHW_TONE_KEEP, NHW_TONE_EQUALIZE, NHW_TONE_AUTOCONTRAST
+
+
+def _tone_values(v, what, name, lo, hi, integral=False):
+    """one number, or three for the channels R, G, B -> three floats (ints with `integral`) in lo .. hi, or raises"""
+    import numpy as np
+    vs = list(v) if isinstance(v, (list, tuple)) or (isinstance(v, np.ndarray) and v.ndim == 1) else [v] * 3
+    if len(vs) != 3:
+        raise NhwError(f"{what}: {name} is one value or three, one a channel, got {v!r}")
+    out = []
+    for x in vs:
+        ok = not isinstance(x, bool) and isinstance(x, numbers.Integral if integral else numbers.Real)
+        if ok and not integral:
+            ok = math.isfinite(x)
+        if not ok or not lo <= x <= hi:
+            raise NhwError(f"{what}: {name} must be {'an integer' if integral else 'a finite number'} of {lo} .. {hi}, got {x!r}")
+        out.append(int(x) if integral else float(x))
+    return out
+
+
+def _tone_check(table, what, channels=3):
+    """`table` as a uint8 array [3, 256] (channels=1: [256]) or raises: integers of 0 .. 255 in that shape"""
+    import numpy as np
+    try:
+        a = np.asarray(table)
+    except Exception:
+        a = None
+    shape = (3, 256) if channels == 3 else (256,)
+    if a is None or a.dtype.kind not in "iu" or a.shape != shape or (a < 0).any() or (a > 255).any():
+        raise NhwError(f"{what}: a tone table is {'3 x 256' if channels == 3 else '256'} integers of 0 .. 255, got {'an array of shape ' + str(a.shape) + ', ' + str(a.dtype) if a is not None and a.dtype.kind in 'iufb' else repr(table)}")
+    return a.astype(np.uint8)
+
+
+def tone_identity():
+    """the tone table that changes nothing: uint8 [3, 256], row c the bytes 0 .. 255.  A tone table is what a pointwise
+    operation on bytes is: row c (R, G, B) maps a byte of channel c; the toned calls apply it behind the blend and the colour map, in front of
+    the value rule."""
+    import numpy as np
+    return np.tile(np.arange(256, dtype=np.uint8), (3, 1))
+
+
+def tone_posterize(bits):
+    """Posterize: x & ~(2^(8 - bits) - 1), the top `bits` bits kept; bits 0 .. 8, one value or three (R, G, B) -> uint8 [3, 256]"""
+    import numpy as np
+    x = np.arange(256)
+    return np.stack([x & ~((1 << (8 - b)) - 1) & 255 for b in _tone_values(bits, "tone_posterize", "bits", 0, 8, integral=True)]).astype(np.uint8)
+
+
+def tone_solarize(threshold):
+    """Solarize: x where x < threshold, else 255 - x; threshold 0 .. 256 (0: the inversion, 256: the identity), one value or three -> uint8 [3, 256]"""
+    import numpy as np
+    x = np.arange(256)
+    return np.stack([np.where(x < t, x, 255 - x) for t in _tone_values(threshold, "tone_solarize", "threshold", 0, 256)]).astype(np.uint8)
+
+
+def tone_gamma(gamma, gain=1.0):
+    """Gamma: rint(255 min(1, gain (x / 255)^gamma)) in float64, ties to even; gamma and gain of 0 .. 1000, each one value or three -> uint8
+    [3, 256].  torchvision's adjust_gamma truncates where this rounds: its entries are this table's or one below."""
+    import numpy as np
+    x = np.arange(256) / 255.0
+    gs, ks = _tone_values(gamma, "tone_gamma", "gamma", 0, 1000), _tone_values(gain, "tone_gamma", "gain", 0, 1000)
+    return np.stack([np.rint(255.0 * np.minimum(1.0, k * x ** g)) for g, k in zip(gs, ks)]).astype(np.uint8)
+
+
+def tone_affine(gain, offset):
+    """The affine step a channel that must come AFTER a table, and so cannot be the colour matrix: clamp(floor(gain x + offset + 1/2), 0, 255),
+    halves up at either sign; gain and offset finite and of -65536 .. 65536, each one value or three -> uint8 [3, 256]"""
+    import numpy as np
+    x = np.arange(256, dtype=np.float64)
+    gs, os_ = _tone_values(gain, "tone_affine", "gain", -65536, 65536), _tone_values(offset, "tone_affine", "offset", -65536, 65536)
+    return np.stack([np.clip(np.floor(g * x + o + 0.5), 0, 255) for g, o in zip(gs, os_)]).astype(np.uint8)
+
+
+def tone_compose(first, then):
+    """the table that applies `first` and then `then`: row c is then[c][first[c][x]]"""
+    import numpy as np
+    a, b = _tone_check(first, "tone_compose"), _tone_check(then, "tone_compose")
+    return np.stack([b[c][a[c]] for c in range(3)])
+
+
+def tone_fixed(table):
+    """a tone table in nhw_tone_table's layout: uint8 [3, 256] on R, G, B -> the struct's 768 bytes, rows in its order B, G, R"""
+    import numpy as np
+    return np.ascontiguousarray(_tone_check(table, "tone_fixed")[::-1]).reshape(768)
+
+
+def _tone_arg(tones, n, what, channels=3):
+    """a call's `tones`: a uint8 CUDA tensor [n, 768] already in the struct's order (returned as it is), or n tables -- [3, 256] on R, G, B,
+    channels=1: [256], which goes to t[0] -- as a numpy uint8 array [n, 768].  No device is touched; raises for a wrong count, shape or value"""
+    import numpy as np
+    if hasattr(tones, "is_cuda"):
+        if not tones.is_cuda or str(tones.dtype) != "torch.uint8" or tuple(tones.shape) != (n, 768) or not tones.is_contiguous():
+            raise NhwError(f"{what}: `tones` as a tensor must be a contiguous uint8 CUDA tensor [{n}, 768], got {tuple(tones.shape)} {tones.dtype} on {tones.device}")
+        return tones
+    if not isinstance(tones, (list, tuple, np.ndarray)) or len(tones) != n:
+        raise NhwError(f"{what}: `tones` must be {n} tone tables, one a sample, got {len(tones) if hasattr(tones, '__len__') else tones!r}")
+    t = np.zeros((n, 768), np.uint8)
+    for i, x in enumerate(tones):
+        a = _tone_check(x, f"{what}: tones[{i}]", channels)
+        if channels == 3:
+            t[i] = a[::-1].reshape(768)
+        else:
+            t[i, :256] = a
+    return t
+
+
+def _host_tones(tones, n, what, channels=3):
+    """_tone_arg for the decoder's calls, whose tables are read from host memory: a tensor is no table here"""
+    if hasattr(tones, "is_cuda"):
+        raise NhwError(f"{what}: `tones` must be {n} tone tables in host memory, one a sample, not a tensor")
+    return _tone_arg(tones, n, what, channels)
+
+
+def _device_tones(tabs, dev, what):
+    """_tone_arg's result on the device `dev`"""
+    import torch
+    if isinstance(tabs, torch.Tensor):
+        if tabs.device != dev:
+            raise NhwError(f"{what}: `tones` is on {tabs.device}, the pictures on {dev}")
+        return tabs
+    return torch.from_numpy(tabs).to(dev)
+
+
+def hist_device(pictures):
+    """The byte histograms of pictures (k_hist_bytes, nhw_hist_device): a list of uint8 CUDA tensors, all [H, W, 3] as
+    resize_to_tensor_device takes them or all [H, W] as resize_grey_to_tensor_device does -> an int64 CUDA tensor [n, C, 256], C = 3 or 1:
+    entry [k, c, v] is the number of pixels of picture k whose byte c is v (c in the pictures' own order, B, G, R for the byte path's).  Reads
+    only the pictures' own bytes; integer sums, the same result every run.  Ordered on torch's current stream."""
+    import torch
+    what = "hist_device"
+    channels = 1 if isinstance(pictures, (list, tuple)) and pictures and len(getattr(pictures[0], "shape", ())) == 2 else 3
+    table, _, dev = _picture_table(pictures, what, channels=channels)
+    n = len(pictures)
+    hist = torch.empty((n, channels, 256), dtype=torch.int32, device=dev)
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_hist_device(table.data_ptr(), n, channels, hist.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return hist.to(torch.int64) & 0xFFFFFFFF
+
+
+def tone_from_hist_device(hist_u32, ops, tones=None):
+    """Tone tables from histograms on the device (k_tone_from_hist, nhw_tone_from_hist_device).  hist_u32: a CUDA tensor
+    [n, C, 256], C = 3 or 1, int64 as hist_device returns it (counts of 0 .. 2^32 - 1) or int32 holding the uint32 words; ops: one of "keep",
+    "equalize", "autocontrast" a sample; tones: the tables whose rows "keep" keeps -- as the toned calls take them, n tables [3, 256] (C = 1:
+    [256]) or a uint8 CUDA tensor [n, 768] --, the identity by default -> a new uint8 CUDA tensor [n, 768] in nhw_tone_table's order, row c made
+    from histogram c, which the toned calls take as `tones`.  "equalize" is PIL's ImageOps.equalize and torchvision's equalize; "autocontrast" is
+    torchvision's rule in exact integers (torchvision computes in float32 and may differ by one level).  With C = 1 only the first 256 bytes of
+    a table are written.  Ordered on torch's current stream.
+    The Equalize recipe, crops to an equalized training batch without leaving the device:
+      1. batch, _ = decoder.decode_crops_device(containers, crops, (224, 224), TensorFormat("uint8", "HWC", "BGR", "file"));
+      2. hist = hist_device(list(batch));                                  (the views batch[k], [224, 224, 3])
+      3. tables = tone_from_hist_device(hist, ["equalize"] * len(batch));
+      4. out = resize_to_tensor_device(list(batch), (224, 224), final_format, tones=tables)
+    -- the resample of a picture to its own size is the identity, so step 4 is the table and the value rule."""
+    import numpy as np
+    import torch
+    what = "tone_from_hist_device"
+    if not (isinstance(hist_u32, torch.Tensor) and hist_u32.is_cuda and hist_u32.dtype in (torch.int64, torch.int32) and hist_u32.dim() == 3
+            and hist_u32.shape[0] >= 1 and hist_u32.shape[1] in (1, 3) and hist_u32.shape[2] == 256):
+        raise NhwError(f"{what}: the histograms must be an int64 or int32 CUDA tensor [n, 3 or 1, 256]")
+    n, channels, dev = int(hist_u32.shape[0]), int(hist_u32.shape[1]), hist_u32.device
+    if not isinstance(ops, (list, tuple)) or len(ops) != n or any(not isinstance(o, str) or o not in TONE_OPS for o in ops):
+        raise NhwError(f"{what}: `ops` must be {n} of {sorted(TONE_OPS)}, one a sample")
+    tabs = _tone_arg(tones, n, what, channels) if tones is not None else np.tile(tone_fixed(tone_identity()), (n, 1))
+    d_tones = _device_tones(tabs, dev, what).clone()
+    h = hist_u32
+    if h.dtype == torch.int64:
+        h = torch.where(h >= 2 ** 31, h - 2 ** 32, h).to(torch.int32)
+    h = h.contiguous()
+    d_ops = torch.tensor([TONE_OPS[o] for o in ops], dtype=torch.uint8).to(dev)
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_tone_from_hist_device(h.data_ptr(), n, channels, d_ops.data_ptr(), d_tones.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return d_tones
 
 
 TENSOR_PICTURE_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("plane", "<u8"), ("width", "<u4"), ("height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_tensor_picture
@@ -1847,14 +2054,15 @@ class Decoder:
             raise NhwError("decode_pictures_grey wants a non-empty list of containers")
         return self.decode_windows_grey(containers, [(i, 0, 0) + scaled_size(*picture_info(c), scale) for i, c in enumerate(containers)], scale)
 
-    def decode_crops_grey_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap", colours=None):
+    def decode_crops_grey_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap", colours=None, tones=None):
         """decode_crops_device as grey (nhw_dec_crops_grey_to_device): fmt a TensorFormat of channels "GREY" -> (tensor
         [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype, the list of the scales used).  The scales and windows are chosen as there,
         the filters and their limits are the same, and so are the tiles and the statuses; out: at least n * out_h * out_w elements.
-        colours: None, or one pair (gain, offset) a crop (nhw_dec_crops_mapped_to_device under a grey format)."""
-        return self._crops_to_batch("decode_crops_grey_device", 1, containers, crops, size, fmt, flips, scale, out, filter, colours)
+        colours: None, or one pair (gain, offset) a crop (nhw_dec_crops_mapped_to_device under a grey format).
+        tones: None, or one tone table uint8 [256] a crop (nhw_dec_crops_toned_to_device, section 25)."""
+        return self._crops_to_batch("decode_crops_grey_device", 1, containers, crops, size, fmt, flips, scale, out, filter, colours, tones)
 
-    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap", colours=None):
+    def decode_crops_device(self, containers, crops, size, fmt, flips=None, scale=None, out=None, filter="two_tap", colours=None, tones=None):
         """RandomResizedCrop's decode (nhw_dec_crops_to_device): crops, a sequence of (container index, x, y, w, h), each
         resampled to size = (out_h, out_w), mirrored left-right where flips[i] is true, and stored under fmt -> (tensor [n, 3, out_h, out_w]
         or [n, out_h, out_w, 3] of fmt.dtype on this decoder's device, the list of the scales used).  With a scale (1, 2 or 4) the crops
@@ -1867,10 +2075,12 @@ class Decoder:
         (nhw_dec_crops_to_device_resample, section 20) with the limit CUBIC_MAX_REDUCTION.  Raises on any status that is not NHW_OK.  The
         work is ordered after torch's current stream and complete on return; region_stats speaks of the last of the calls.  colours: None, or
         one colour map a crop (nhw_dec_crops_mapped_to_device), as resize_to_tensor_device takes them: ColorJitter,
-        RandomGrayscale, a channel mix or an inversion of each sample in the resampler's store."""
-        return self._crops_to_batch("decode_crops_device", 3, containers, crops, size, fmt, flips, scale, out, filter, colours)
+        RandomGrayscale, a channel mix or an inversion of each sample in the resampler's store.  tones: None, or one tone table a crop, uint8
+        [3, 256] on R, G, B as the tone_* builders make it (nhw_dec_crops_toned_to_device, section 25): Posterize, Solarize, a gamma or any
+        curve of each sample, applied behind the map; colours and tones combine."""
+        return self._crops_to_batch("decode_crops_device", 3, containers, crops, size, fmt, flips, scale, out, filter, colours, tones)
 
-    def _crops_to_batch(self, what, channels, containers, crops, size, fmt, flips, scale, out, filter, colours=None):
+    def _crops_to_batch(self, what, channels, containers, crops, size, fmt, flips, scale, out, filter, colours=None, tones=None):
         """decode_crops_device (channels=3) and decode_crops_grey_device (1)"""
         import numpy as np
         _filter(filter, what)
@@ -1878,10 +2088,12 @@ class Decoder:
         out_h, out_w = _crop_size(size, what)
         if scale is not None:
             scale = _scale(scale, what)
-        if colours is not None:
+        maps = tabs = None
+        if colours is not None or tones is not None:
             if not isinstance(crops, (list, tuple, np.ndarray)):
-                raise NhwError(f"{what}: `crops` must be a sequence, one colour map a crop")
-            maps = _colour_table(colours, len(crops), what, channels)
+                raise NhwError(f"{what}: `crops` must be a sequence, one colour map{'' if tones is None else ' or tone table'} a crop")
+            maps = _colour_table(colours, len(crops), what, channels) if colours is not None else None
+            tabs = _host_tones(tones, len(crops), what, channels) if tones is not None else None
         blob, offs, table = self._region_args(containers, crops, what)
         n = len(table)
         flags = _crop_flips(flips, n, what)
@@ -1898,6 +2110,9 @@ class Decoder:
         if filter in _LIMITS:
             for i, r in enumerate(table):
                 _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
+        if tones is not None:
+            return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
+                                        lambda *args: self.lib.nhw_dec_crops_toned_to_device(*args, RESAMPLERS[filter]), channels, maps, tabs), scales
         if colours is not None:
             return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
                                         lambda *args: self.lib.nhw_dec_crops_mapped_to_device(*args, RESAMPLERS[filter]), channels, maps), scales
@@ -1905,11 +2120,12 @@ class Decoder:
         return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
                                     lambda *args: call(*args, RESAMPLERS[filter]), channels), scales
 
-    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3, maps=None):
+    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3, maps=None, tones=None):
         """the device side of decode_crops_device and decode_warps_device: the checked batch tensor (`out`, or a new one), and per scale one
         call(handle, blob, offsets, n containers, the scale's rects, their count, scale, out_w, out_h, format, the scale's rows of `extra` --
         the flag bytes or the nhw_warp table, or None --, the tensors' addresses, statuses) -> rc; with `maps`, the nhw_colour_map table of a mapped call, the
-        scale's rows of it go in front of the addresses.  Raises on any status that is not NHW_OK"""
+        scale's rows of it go in front of the addresses; with `tones`, the uint8 [n, 768] table of a toned call, the rows of the maps (or a null pointer)
+        and behind them the rows of the tables do.  Raises on any status that is not NHW_OK"""
         import numpy as np
         t = self.torch
         n = len(table)
@@ -1928,20 +2144,22 @@ class Decoder:
             idx = np.flatnonzero(np.array(scales) == s)
             sub, a, st = np.ascontiguousarray(table[idx]), np.ascontiguousarray(addr[idx]), np.empty(len(idx), np.int32)
             x = np.ascontiguousarray(extra[idx]) if extra is not None else None
-            mp = (np.ascontiguousarray(maps[idx]),) if maps is not None else ()
+            mp = (np.ascontiguousarray(maps[idx]),) if maps is not None else (None,) if tones is not None else ()
+            if tones is not None:
+                mp += (np.ascontiguousarray(tones[idx]),)
             self._chk(call(self.h, blob.ctypes.data, offs.ctypes.data, n_containers, sub.ctypes.data, len(idx), s, out_w, out_h,
-                           ctypes.byref(c), x.ctypes.data if x is not None else None, *(m.ctypes.data for m in mp), a.ctypes.data, st.ctypes.data))
+                           ctypes.byref(c), x.ctypes.data if x is not None else None, *(m.ctypes.data if m is not None else None for m in mp), a.ctypes.data, st.ctypes.data))
             status[idx] = st
         self._region_raise(status)
         return out if tuple(out.shape) == shape else out.reshape(-1)[:n * per].view(shape)
 
-    def decode_warps_grey_device(self, containers, which, matrices, size, fmt, fill=0, border="fill", scale=None, out=None, colours=None):
+    def decode_warps_grey_device(self, containers, which, matrices, size, fmt, fill=0, border="fill", scale=None, out=None, colours=None, tones=None):
         """decode_warps_device as grey (nhw_dec_warps_grey_to_device): fmt a TensorFormat of channels "GREY", fill one
         byte -> (tensor [n, 1, out_h, out_w] or [n, out_h, out_w, 1] of fmt.dtype, the list of the scales used).  The scales and windows are
-        chosen as there.  colours: None, or one pair (gain, offset) a warp."""
-        return self._warps_to_batch("decode_warps_grey_device", 1, containers, which, matrices, size, fmt, fill, border, scale, out, colours)
+        chosen as there.  colours: None, or one pair (gain, offset) a warp; tones: None, or one table uint8 [256] a warp."""
+        return self._warps_to_batch("decode_warps_grey_device", 1, containers, which, matrices, size, fmt, fill, border, scale, out, colours, tones)
 
-    def decode_warps_device(self, containers, which, matrices, size, fmt, fill=(0, 0, 0), border="fill", scale=None, out=None, colours=None):
+    def decode_warps_device(self, containers, which, matrices, size, fmt, fill=(0, 0, 0), border="fill", scale=None, out=None, colours=None, tones=None):
         """RandomAffine's / RandomRotation's decode (nhw_dec_warps_to_device): warp i samples the picture of container
         which[i] along the grid of matrices[i] -- a 2 x 3 matrix of floats as warp_fixed takes it, in FULL-resolution picture coordinates
         (crop_warp makes one from a rectangle, an angle and a flip) -- into size = (out_h, out_w), and is stored under fmt -> (tensor [n, 3,
@@ -1952,10 +2170,11 @@ class Decoder:
         outside the picture takes fill = (B, G, R), or with border="replicate" the nearest edge pixel.  out: as for decode_crops_device.
         Raises on any status that is not NHW_OK.  The work is ordered after torch's current stream and complete on return; region_stats
         speaks of the last of the calls.  colours: None, or one colour map a warp (nhw_dec_warps_mapped_to_device), as
-        decode_crops_device takes them; the border colour is mapped like any other pixel."""
-        return self._warps_to_batch("decode_warps_device", 3, containers, which, matrices, size, fmt, fill, border, scale, out, colours)
+        decode_crops_device takes them; the border colour is mapped like any other pixel.  tones: None, or one tone table a warp
+        (nhw_dec_warps_toned_to_device, section 25), as decode_crops_device takes them; the border colour goes through the table too."""
+        return self._warps_to_batch("decode_warps_device", 3, containers, which, matrices, size, fmt, fill, border, scale, out, colours, tones)
 
-    def _warps_to_batch(self, what, channels, containers, which, matrices, size, fmt, fill, border, scale, out, colours=None):
+    def _warps_to_batch(self, what, channels, containers, which, matrices, size, fmt, fill, border, scale, out, colours=None, tones=None):
         """decode_warps_device (channels=3) and decode_warps_grey_device (1)"""
         import numpy as np
         fmt = _tensor_format(fmt, what, grey=channels == 1)
@@ -1969,6 +2188,7 @@ class Decoder:
             raise NhwError(f"{what}: `which` and `matrices` must be non-empty and of the same length: one container index and one matrix a warp")
         n = len(which)
         maps = _colour_table(colours, n, what, channels) if colours is not None else None
+        tabs = _host_tones(tones, n, what, channels) if tones is not None else None
         for i, ci in enumerate(which):
             if isinstance(ci, bool) or not isinstance(ci, numbers.Integral) or not 0 <= ci < len(containers):
                 raise NhwError(f"{what}: which[{i}] must be a container index of 0 .. {len(containers) - 1}, got {ci!r}")
@@ -1982,6 +2202,9 @@ class Decoder:
             rects.append((int(ci),) + win)
             fixed.append(fx)
         blob, offs, table = self._region_args(containers, rects, what)
+        if tones is not None:
+            return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
+                                        self.lib.nhw_dec_warps_toned_to_device, channels, maps, tabs), scales
         if colours is not None:
             return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
                                         self.lib.nhw_dec_warps_mapped_to_device, channels, maps), scales

@@ -5,7 +5,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libnhwhip.so")
-SOURCES = ["nhw_front.hip", "nhw_tail.hip", "nhw_low.hip", "nhw_host.hip", "nhw_enc.hip", "nhw_enc_hostpath.hip", "nhw_enc_fit.hip", "nhw_dec.hip", "nhw_dec_hostpath.hip", "nhw_fit.hip", "nhw_metric.hip", "nhw_picture.hip", "nhw_resample.hip"]
+SOURCES = ["nhw_front.hip", "nhw_tail.hip", "nhw_low.hip", "nhw_host.hip", "nhw_enc.hip", "nhw_enc_hostpath.hip", "nhw_enc_fit.hip", "nhw_dec.hip", "nhw_dec_hostpath.hip", "nhw_fit.hip", "nhw_metric.hip", "nhw_picture.hip", "nhw_resample.hip", "nhw_tone.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-Wno-unused-value"]
 if os.environ.get("NHW_DEV"):
     FLAGS.append("-DNHW_DEV")       # phase stamps and pass switches of the front kernels (developer builds only)

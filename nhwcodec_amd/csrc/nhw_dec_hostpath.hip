@@ -185,7 +185,7 @@ enum WindowsMode {
 	WIN_TO_DEVICE,                                               /* dst_addr / dst_pitch: cropped straight into the caller's device memory; nothing is left to do */
 	WIN_TO_TENSORS                                               /* crop, dst_addr the tensors' addresses: packed as for the host form, then resampled or warped (crops_finish) */
 };
-struct CropSpec { NhwTensorOut out; const uint8_t *flags; int filter; const nhw_warp *warps; const nhw_colour_map *maps = nullptr; /* one a rect, or none */ };
+struct CropSpec { NhwTensorOut out; const uint8_t *flags; int filter; const nhw_warp *warps; const nhw_colour_map *maps = nullptr; /* one a rect, or none */ const nhw_tone_table *tones = nullptr; /* one a rect (section 25), or none */ };
 struct WindowsCall {
 	WindowsMode mode = WIN_TO_HOST;
 	uint8_t *bgr = nullptr; const uint64_t *out_off = nullptr, *dst_addr = nullptr, *dst_pitch = nullptr;
@@ -246,7 +246,9 @@ static int upload_plan(nhw_dec *d, TilePlan &p, bool staged)
  * that has no window keeps a zero picture), nr tensor addresses (0 for a rect without a window or with a tile that failed, which the kernel
  * passes over), and behind them either the nr flag bytes -- k_resize_to_tensor, k_area_to_tensor or k_cubic_to_tensor by the filter -- or
  * the nr warps (32 + 8 bytes an entry in front: they are 8-byte aligned) -- k_warp_to_tensor, warps[i] sampling window i along its tilted grid.
- * A mapped call (section 24) has its nr colour maps behind that table, at the next multiple of 8, and launches the mapped forms of the same kernels. */
+ * A mapped call (section 24) has its nr colour maps behind that table, at the next multiple of 8, and launches the mapped forms of the same kernels.
+ * A toned call (section 25) has its nr tone tables behind the maps (64 bytes each: a multiple of 8 again), or in their place where it has none,
+ * and launches the toned forms. */
 static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, const uint64_t *dst_addr, int nr, const int32_t *status, bool grey)
 {
 	static_assert(sizeof(nhw_warp) == 40 && sizeof(nhw_picture) == 32, "the crop table's layout");
@@ -259,9 +261,11 @@ static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, con
 	}
 	const size_t pics_bytes = (size_t)nr * sizeof(nhw_picture), addr_bytes = (size_t)nr * 8;
 	const size_t last_bytes = ((size_t)nr * (crop.warps ? sizeof(nhw_warp) : 1) + 7) & ~(size_t)7, maps_bytes = crop.maps ? (size_t)nr * sizeof(nhw_colour_map) : 0;
-	HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + last_bytes + maps_bytes));
+	const size_t tones_bytes = crop.tones ? (size_t)nr * sizeof(nhw_tone_table) : 0;
+	HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + last_bytes + maps_bytes + tones_bytes));
 	uint8_t *tab = d->crop_tab.as<uint8_t>(), *last = tab + pics_bytes + addr_bytes;
 	const nhw_colour_map *d_maps = (const nhw_colour_map *)(last + last_bytes);
+	const nhw_tone_table *d_tones = (const nhw_tone_table *)(last + last_bytes + maps_bytes);
 	const nhw_picture *d_pics = (const nhw_picture *)tab;
 	const uint64_t *d_addr = (const uint64_t *)(tab + pics_bytes);
 	const NhwTensorOut &o = crop.out;
@@ -269,14 +273,17 @@ static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, con
 	HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
 	if (crop.maps) HIPCHK(hipMemcpyAsync(last + last_bytes, crop.maps, maps_bytes, hipMemcpyHostToDevice, s));
+	if (crop.tones) HIPCHK(hipMemcpyAsync(last + last_bytes + maps_bytes, crop.tones, tones_bytes, hipMemcpyHostToDevice, s));
 	if (crop.warps) {
 		HIPCHK(hipMemcpyAsync(last, crop.warps, (size_t)nr * sizeof(nhw_warp), hipMemcpyHostToDevice, s));
-		if (crop.maps) HIPCHK(nhw_launch_warp_mapped(grey, d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_addr, s));
+		if (crop.tones) HIPCHK(nhw_launch_warp_toned(grey, d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.maps ? d_maps : nullptr, d_tones, d_addr, s));
+		else if (crop.maps) HIPCHK(nhw_launch_warp_mapped(grey, d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_addr, s));
 		else HIPCHK(grey ? nhw_launch_warp_grey(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.a, d_addr, s)
 		            : nhw_launch_warp(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_addr, s));
 	} else {
 		if (crop.flags) HIPCHK(hipMemcpyAsync(last, crop.flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		if (crop.maps) HIPCHK(nhw_launch_resample_mapped(grey, crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_maps, d_addr, s));
+		if (crop.tones) HIPCHK(nhw_launch_resample_toned(grey, crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, crop.maps ? d_maps : nullptr, d_tones, d_addr, s));
+		else if (crop.maps) HIPCHK(nhw_launch_resample_mapped(grey, crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_maps, d_addr, s));
 		else HIPCHK(grey ? nhw_launch_resample_grey(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.a, crop.flags ? last : nullptr, d_addr, s)
 		            : nhw_launch_resample(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_addr, s));
 	}
@@ -467,6 +474,35 @@ extern "C" int nhw_dec_warps_mapped_to_device(nhw_dec *d, const uint8_t *blob, c
 	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_mapped_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
 	WindowsCall c;
 	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_warps_mapped_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+/* ... and with a tone table a rect: the mapped calls' checks in their order, the NULL tone table where the NULL map table
+ * was; the maps may be NULL here */
+extern "C" int nhw_dec_crops_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps,
+                                             const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status, int filter)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_toned_to_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!dst_addr || !tones || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = fmt && fmt->channels == NHW_T_GREY;
+	CropSpec crop = { {}, flags, filter, nullptr, maps, tones };
+	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_toned_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
+	WindowsCall c;
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_crops_toned_to_device";
+	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
+}
+
+extern "C" int nhw_dec_warps_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
+                                             const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status)
+{
+	if (!warps || !tones || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = fmt && fmt->channels == NHW_T_GREY;
+	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps, maps, tones };
+	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_toned_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
+	WindowsCall c;
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_warps_toned_to_device";
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
 }
 

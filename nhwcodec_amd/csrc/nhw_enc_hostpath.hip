@@ -249,6 +249,48 @@ extern "C" int nhw_warp_mapped_to_tensor_device(const nhw_picture *d_pics, int n
 	return NHW_OK;
 }
 
+/* ... and with a tone table an entry: the mapped entries' checks in their order, the NULL tone table among the NULL pointers;
+ * the map table may be NULL here */
+extern "C" int nhw_resample_toned_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                                                   const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, void *stream)
+{
+	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_toned_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!d_pics || !d_tones || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = names_grey(fmt);
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_resample_toned_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
+	HIPCHK(nhw_launch_resample_toned(grey, filter, d_pics, n, o.w, o.h, o.dtype, o.layout, o.a, d_flags, d_maps, d_tones, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_warp_toned_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
+                                               const nhw_warp *d_warps, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, void *stream)
+{
+	if (!d_pics || !d_warps || !d_tones || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	const bool grey = names_grey(fmt);
+	NhwTensorOut o;
+	if (const int rc = nhw_tensor_out_check("nhw_warp_toned_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
+	HIPCHK(nhw_launch_warp_toned(grey, d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_tones, d_out_addr, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+/* the histograms of a table's pictures, and tone tables' rows from histograms (nhw_tone.hip) */
+extern "C" int nhw_hist_device(const nhw_picture *d_pics, int n, int channels, uint32_t *d_hist, void *stream)
+{
+	if (!d_pics || !d_hist || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (channels != 3 && channels != 1) { nhw_enc_err = "nhw_hist_device: channels must be 3 or 1"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_hist(d_pics, n, channels, d_hist, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_tone_from_hist_device(const uint32_t *d_hist, int n, int channels, const uint8_t *d_ops, nhw_tone_table *d_tones, void *stream)
+{
+	if (!d_hist || !d_ops || !d_tones || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (channels != 3 && channels != 1) { nhw_enc_err = "nhw_tone_from_hist_device: channels must be 3 or 1"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_tone_from_hist(d_hist, n, channels, d_ops, d_tones, (hipStream_t)stream));
+	return NHW_OK;
+}
+
 /* ------------------------------------------------------------------------------------------------ encode from tensors */
 static int tensor_in_args(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
 {

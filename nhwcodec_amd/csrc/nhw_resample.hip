@@ -19,9 +19,15 @@
  * arguments in `M... maps`, which is then nothing at all -- those forms have the arguments, registers and instructions they had before the pack.
  * With M = const nhw_colour_map * the workgroup reads its entry's map once (EntryMap), stores nothing unless the map is within the limits, and puts
  * every pixel's bytes through nhw_colour_apply (nhw_colour.h) between the blend and resample_store.
+ *
+ * ... and a toned form: M = const nhw_colour_map *, const nhw_tone_table *.  The map pointer may be null -- a kernel argument, so
+ * the branch is uniform -- and the workgroup then skips the map.  It copies its entry's table, 256 C bytes, into LDS (EntryMap::stage) once it has
+ * accepted the entry and the map, in front of the kernel's first barrier (the warp kernel, which has none otherwise, gains one: EntryMap::barrier), and
+ * a pixel's bytes take C byte reads from there behind the map.
  */
 #include "nhw_tensor.h"
 #include "nhw_colour.h"
+#include "nhw_tone.h"
 #include "../../include/nhw_hip_debug.h"
 
 namespace {
@@ -80,12 +86,49 @@ __device__ __forceinline__ void resample_store(typename NhwElem<DT>::type *out, 
  * entry then stores nothing), `apply` the rule on a pixel's C bytes. */
 template <class... M> struct EntryMap {
 	__device__ __forceinline__ bool load(int, M...) { return true; }
+	template <int C> __device__ __forceinline__ void stage() const {}
+	__device__ __forceinline__ void barrier() const {}
 	template <int C> __device__ __forceinline__ void apply(uint32_t *) const {}
 };
 template <> struct EntryMap<const nhw_colour_map *> {
 	nhw_colour_map c;
 	__device__ __forceinline__ bool load(int k, const nhw_colour_map *maps) { c = maps[k]; return nhw_colour_within(c); }
+	template <int C> __device__ __forceinline__ void stage() const {}
+	__device__ __forceinline__ void barrier() const {}
 	template <int C> __device__ __forceinline__ void apply(uint32_t *b) const { nhw_colour_apply<C>(c, b); }
+};
+/* ... and the toned pack: the map, where the call has one (`mapped`: uniform for the grid), and the entry's tone table.  `stage`
+ * copies the table's first 256 C bytes into LDS, a byte a thread at a time (a table has no alignment), for the whole workgroup: every thread
+ * calls it, before a barrier that every thread meets; `barrier` is that barrier for a kernel that has none of its own; `apply` is the map and
+ * then C byte reads from LDS. */
+template <int C> __device__ __forceinline__ uint8_t *tone_lds()
+{
+	__shared__ uint8_t tone[256 * C];
+	return tone;
+}
+template <> struct EntryMap<const nhw_colour_map *, const nhw_tone_table *> {
+	nhw_colour_map c;
+	bool mapped;
+	const uint8_t *table;
+	__device__ __forceinline__ bool load(int k, const nhw_colour_map *maps, const nhw_tone_table *tones)
+	{
+		mapped = maps != nullptr;
+		table = &tones[k].t[0][0];
+		if (!mapped) return true;
+		c = maps[k];
+		return nhw_colour_within(c);
+	}
+	template <int C> __device__ __forceinline__ void stage() const
+	{
+		uint8_t *t = tone_lds<C>();
+		for (uint32_t i = threadIdx.x; i < 256u * C; i += RS_THREADS) t[i] = table[i];
+	}
+	__device__ __forceinline__ void barrier() const { __syncthreads(); }
+	template <int C> __device__ __forceinline__ void apply(uint32_t *b) const
+	{
+		if (mapped) nhw_colour_apply<C>(c, b);
+		nhw_tone_apply<C>(tone_lds<C>(), b);
+	}
 };
 
 /* ---- the two taps ----
@@ -118,6 +161,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_resize_to_tensor(const nhw_pictu
 	if (!resample_entry<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, 0, p, out, r0, nr, mirror)) return;
 	EntryMap<M...> cm;
 	if (!cm.load((int)(blockIdx.x / bands), maps...)) return;
+	cm.template stage<C>();
 	for (uint32_t o = threadIdx.x; o < out_w; o += RS_THREADS) col_pos[o] = resize_pos(o, p.width, out_w);
 	if (threadIdx.x < nr) row_pos[threadIdx.x] = resize_pos(r0 + threadIdx.x, p.height, out_h);
 	__syncthreads();
@@ -205,6 +249,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_area_to_tensor(const nhw_picture
 	if (!resample_entry<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, NHW_AREA_MAX_REDUCTION, p, out, r0, nr, mirror)) return;
 	EntryMap<M...> cm;
 	if (!cm.load((int)(blockIdx.x / bands), maps...)) return;
+	cm.template stage<C>();
 	uint2 *col_tap = area_tab, *row_tap = area_tab + out_w;
 	for (uint32_t o = threadIdx.x; o < out_w; o += RS_THREADS) col_tap[o] = area_taps(o, p.width, out_w);
 	if (threadIdx.x < nr) row_tap[threadIdx.x] = area_taps(r0 + threadIdx.x, p.height, out_h);
@@ -321,6 +366,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_cubic_to_tensor(const nhw_pictur
 	if (!resample_entry<DT>(pics, flags, out_addr, out_w, out_h, bands, rows, NHW_CUBIC_MAX_REDUCTION, p, out, r0, nr, mirror)) return;
 	EntryMap<M...> cm;
 	if (!cm.load((int)(blockIdx.x / bands), maps...)) return;
+	cm.template stage<C>();
 	const uint32_t Dx = p.width > out_w ? p.width : out_w, Dy = p.height > out_h ? p.height : out_h;
 	const uint32_t tbx = 4 * Dx / out_w + 1, tby = 4 * Dy / out_h + 1;          /* 5 .. 129 */
 	uint32_t wc = out_w < (uint32_t)CB_COLS ? out_w : (uint32_t)CB_COLS;        /* columns whose weights are held at a time */
@@ -452,6 +498,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
 	if (!nhw_warp_within(m)) return;
 	EntryMap<M...> cm;
 	if (!cm.load(k, maps...)) return;
+	cm.template stage<C>();
+	cm.barrier();
 	const bool fill = !(m.flags & NHW_WARP_REPLICATE);
 	const size_t W = out_w, H = out_h;
 	if ((m.d < 0 ? -m.d : m.d) > row_limit) {                                /* a wavefront an 8 x 8 block of output pixels (|d| <= 2^22: checked) */
@@ -491,7 +539,8 @@ __global__ __launch_bounds__(RS_THREADS) void k_warp_to_tensor(const nhw_picture
  * and, where the output is narrow, at least the rows of one pass (256 >> lg), so that a pass has work for every lane.  All four kernels meet
  * the same launch shapes, those of resample_bands: false for what no kernel is launched for.  The area kernel's LDS is sized by its launch: the
  * tap runs of the columns and of a band's rows, 8 (out_w + rows) bytes, 33 280 at the most; the cubic and the two-tap kernel have static LDS,
- * the warp has none, and the cubic kernel cuts its band itself (it takes no lg). */
+ * the warp has none, and the cubic kernel cuts its band itself (it takes no lg).  A toned form has its table's 256 C bytes of static LDS on top
+ * (the area kernel's tap runs lie behind them). */
 static bool resample_bands(int n, uint32_t out_w, uint32_t out_h, int &lg, uint32_t &rows, int &bands)
 {
 	if (n < 1 || n > (1 << 24) || out_w < 1 || out_h < 1 || out_w > (uint32_t)RS_MAX || out_h > (uint32_t)RS_MAX) return false;
@@ -506,7 +555,8 @@ static bool resample_bands(int n, uint32_t out_w, uint32_t out_h, int &lg, uint3
 }
 
 /* The four launches, each with the pack M of its kernels: empty for the calls that have no maps, const nhw_colour_map * and the
- * device table of n maps for those that do. */
+ * device table of n maps for those that do; behind it const nhw_tone_table * and the table of n tone tables for the toned calls (section 25), whose
+ * map table may be null. */
 template <class... M>
 static hipError_t launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
                               const uint64_t *d_out_addr, hipStream_t s, M... maps)
@@ -632,4 +682,19 @@ hipError_t nhw_launch_warp_mapped(bool grey, const nhw_picture *d_pics, const nh
 	if (!d_maps) return hipErrorInvalidValue;
 	return grey ? launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s, d_maps)
 	            : launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s, d_maps);
+}
+/* ... and with a device table of n tone tables, the map table or null in front of it */
+hipError_t nhw_launch_resample_toned(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                     const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (!d_tones) return hipErrorInvalidValue;
+	return grey ? launch_resample_grey(filter, d_pics, n, out_w, out_h, dtype, a, d_flags, d_out_addr, s, d_maps, d_tones)
+	            : launch_resample(filter, d_pics, n, out_w, out_h, dtype, layout, a, d_flags, d_out_addr, s, d_maps, d_tones);
+}
+hipError_t nhw_launch_warp_toned(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
+                                 const NhwTensorArgs &a, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s)
+{
+	if (!d_tones) return hipErrorInvalidValue;
+	return grey ? launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s, d_maps, d_tones)
+	            : launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s, d_maps, d_tones);
 }

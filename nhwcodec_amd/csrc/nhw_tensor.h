@@ -326,6 +326,16 @@ hipError_t nhw_launch_resample_mapped(bool grey, int filter, const nhw_picture *
                                       const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s);
 hipError_t nhw_launch_warp_mapped(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
                                   const NhwTensorArgs &a, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s);
+/* ... and with a device table of n tone tables as well, d_tones[k] for entry k (the rule is in nhw_tone.h): the toned forms of
+ * the same kernels.  d_maps may be null here: no map.  Every table is valid. */
+hipError_t nhw_launch_resample_toned(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
+                                     const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s);
+hipError_t nhw_launch_warp_toned(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
+                                 const NhwTensorArgs &a, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s);
+/* nhw_tone.hip: the histograms of n pictures of `channels` (3 or 1) bytes a pixel, uint32 [n][channels][256], zeroed on the
+ * stream and then counted; and the rows of n tone tables from such histograms under one op byte a sample */
+hipError_t nhw_launch_hist(const nhw_picture *d_pics, int n, int channels, uint32_t *d_hist, hipStream_t s);
+hipError_t nhw_launch_tone_from_hist(const uint32_t *d_hist, int n, int channels, const uint8_t *d_ops, nhw_tone_table *d_tones, hipStream_t s);
 /* nhw_picture.hip again, the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
