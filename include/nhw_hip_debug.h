@@ -44,6 +44,14 @@ int nhw_dec_debug_slice_order(nhw_dec *d, int mode);
  * the counterpart of nhw_debug_read) and read them behind the call. */
 int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, void *stream);
 int nhw_debug_write(nhw_enc *e, int buf, int img, const void *src, size_t bytes);
+/* The chroma tail of component comp (the marks of quality 18 .. 23, the LL2 emission, the quantiser) for the first n images of the handle's last
+ * whole batch, at that batch's quality, on B_CPROC, B_CLL1 and B_CL2SAVE as they stand (V on a handle with the chroma fork: B_CPROC_V, B_CLL1_V,
+ * B_CL2SAVE_V) and the exception list (B_EXW, its length in B_META).  form 0: the production kernel, which reads each plane row once and
+ * does not write the work plane; form 1: the staged body with every plane written and the dense chroma stream in B_SCAN (from byte 4 * 65536
+ * on).  Both leave the symbol list (B_CNZQ with the cfbase table of 20 words behind its 2048 maps, B_CVALS: cfbase[F] is where the values of
+ * the sixteen plane rows 16 F .. 16 F + 15 start, wherever the kernel put them), U's parked bytes (B_UBYTES), the LL2 bytes, the exception
+ * list and the bit-1 bytes.  Run U before V: V merges U's parked bytes. */
+int nhw_stage_chroma_tail(nhw_enc *e, int n, int comp, int form, void *stream);
 /* The luma plane's first closed loop for the first n images of the handle's last whole batch, at that batch's quality (7 .. 23), on B_JPEG, B_PROC,
  * B_LL1 and B_L2SAVE as they stand.  form 0: the production kernels from the first level-2 analysis to the second; form 1: their last part
  * alone (synthesis, Y8, Y9 and, for q > 12 on the same LDS residency, the second analysis with Y13's copy); form 2: the staged kernels for

@@ -73,6 +73,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_stage_prefilter.argtypes = [P, P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_chroma_l1.argtypes = [P, ctypes.c_int, P]
     L.nhw_stage_chroma_loops.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
+    L.nhw_stage_chroma_tail.argtypes = [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_luma_loop.argtypes = [P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_ll2_walk.argtypes = [P, ctypes.c_int, ctypes.c_int, P]
     L.nhw_stage_quant.argtypes = [P, ctypes.c_int, ctypes.c_int, P]

@@ -44,6 +44,7 @@ struct nhw_enc {
 	int quant_join;               /* the side streams join in front of the luma quantiser (q <= 21) */
 	int y5_fork;                  /* Y5 on ll_stream beside the first dequantiser simulation (NHW_Y5_FORK=0: in front of it on the luma stream) */
 	int ll2_once;                 /* q > 12: the LL2 bump walk in the emission only (NHW_LL2_ONCE=0: again in the second simulation) */
+	int chroma_tail_once;         /* the chroma tail as one walk that reads each plane row once and does not write cproc (NHW_CHROMA_TAIL_ONCE=0: the staged body, as the stage checks run it) */
 	int quant_marks;              /* q > 16: the second simulation hands its marks to the quantiser, which skips its loops 2 and 3 (NHW_QUANT_MARKS=0: the quantiser runs them itself) */
 	int pack_fork;                /* forked order: Z2's chroma part (k_pack_chroma) on ll_stream beside Z1 (2, the default), on the chroma stream behind Z1 (1); NHW_PACK_FORK=0: directly in front of k_final, as in every other order */
 	int parts;

@@ -103,6 +103,7 @@ extern "C" int nhw_enc_create_ex(int device, int max_batch, unsigned flags, nhw_
 	e->y5_fork = env("NHW_Y5_FORK", 1) != 0;
 	e->ll2_once = env("NHW_LL2_ONCE", 1) != 0;
 	e->quant_marks = env("NHW_QUANT_MARKS", 1) != 0;
+	e->chroma_tail_once = env("NHW_CHROMA_TAIL_ONCE", 1) != 0;
 	e->pack_fork = within(env("NHW_PACK_FORK", 2), 0, 2, 2);
 	*out = e;
 	return NHW_OK;
@@ -296,9 +297,10 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	ws.defer_verbatim = fork_ll;
 	hipStream_t cs = fork ? e->part_stream[0] : s;
 	ws.split_chroma = fork;                                          /* (the stage checks and the in-line order keep the reference's one set of planes) */
+	const bool tail_once = e->chroma_tail_once && !e->stop_after && !ws.dbg;   /* every order of this function (forked, in line, a sub-batch's view; the fit paths come through here): nothing in a batch reads cproc behind the chroma tail.  Off under a debug stop, whose stage checks read the planes */
 	auto chroma_head = [&](int comp) -> int { return chroma_head_launches(e, ws, comp, n, cs, stage); };   /* everything up to the second dequantiser simulation */
 	auto chroma_tail = [&](int comp) -> int {                        /* marks, LL2 emission (appends to the exception list), quantiser, stream bytes */
-		nhw_launch_phase(PH_C5, ws, comp, cs);
+		nhw_launch_chroma_tail(ws, comp, tail_once, cs);
 		STAGE_DONE();
 		return 1;
 	};
@@ -631,6 +633,30 @@ extern "C" int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, voi
 		if (k > 5) nhw_launch_phase(PH_C4, ws, comp, s);
 		if (k > 6) nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, s);
 	}
+	HIPCHK(hipGetLastError());
+	return NHW_OK;
+}
+
+/* A test hook for the chroma tail (marks, LL2 emission, quantiser) of component comp, for the first n images of the handle's last whole batch at
+ * that batch's quality, on the planes as they stand (a test writes them: nhw_debug_write): B_CPROC, B_CLL1, B_CL2SAVE -- for V the planes the
+ * handle's order uses (B_CPROC_V, B_CLL1_V, B_CL2SAVE_V with the chroma fork, the same three without) -- and the exception list with its
+ * length in B_META, to which the emission appends.  U is run before V: V merges the bytes U parked in B_UBYTES.
+ *   form 0: the production form (k_chroma_tail): the symbol list in B_CNZQ / cfbase / B_CVALS; the work plane is not written;
+ *   form 1: the staged body as a debug stop runs it (k_phase<PH_C5> with ws.dbg): the same list, the dense stream behind the luma part in
+ *           B_SCAN as well, and every plane written. */
+extern "C" int nhw_stage_chroma_tail(nhw_enc *e, int n, int comp, int form, void *stream)
+{
+	if (!e || n < 1 || n > e->max_batch || comp < 0 || comp > 1 || form < 0 || form > 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!e->timed || n > e->last_n || e->stop_after) {
+		nhw_enc_err = "nhw_stage_chroma_tail: needs a completed whole batch of >= n images and no debug stop";
+		return NHW_E_ARG;
+	}
+	HIPCHK(hipSetDevice(e->device));
+	NhwWs ws = e->ws;
+	ws.n = n; ws.q = e->last_q; ws.dbg = form == 1; ws.split_chroma = e->chroma_fork;
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
+	nhw_launch_chroma_tail(ws, comp, form == 0, s);
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
 }

@@ -89,6 +89,7 @@ int nhw_front_set_attrs(const char **where);   /* nhw_front.hip, nhw_tail.hip: d
 enum { PH_L1, PH_L2, PH_L3, PH_L4A, PH_C0, PH_C2, PH_C3, PH_C4, PH_C5, PH_L4B = 10, PH_L4C, PH_L4D, PH_LLC, PH_L4C2 };   /* the numbers name k_phase's instances in recorded profiles (9 was the final phase: k_final) */
 enum { WV_DQ1, WV_DQ0, WV_EMIT, WV_QUANT };
 void nhw_launch_phase(int ph, const NhwWs &ws, int comp, hipStream_t s);
+void nhw_launch_chroma_tail(const NhwWs &ws, int comp, bool once, hipStream_t s);   /* marks, LL2 emission, chroma quantiser of a component.  once: k_chroma_tail, which reads each row of the work plane once and does not write it (a production batch); else, and always under ws.dbg, the staged body k_phase<PH_C5>, whose planes the stage checks read */
 void nhw_launch_pack_chroma(const NhwWs &ws, hipStream_t s);   /* Z2, the chroma part's words and ranked book entries: needs V's quantiser (k_phase<PH_C5>) and nothing of the luma tail */
 void nhw_launch_final(const NhwWs &ws, uint8_t *out, uint32_t *sizes, int32_t *status, hipStream_t s, bool chroma_packed = false);   /* Z2 + the container; chroma_packed: nhw_launch_pack_chroma has run on these images (otherwise it is launched here, in front) */
 void nhw_launch_wave(int ph, const NhwWs &ws, hipStream_t s, bool one_walk = false /* WV_EMIT and WV_DQ0 of one batch alike, quality > 12, production: the emission leaves the LL2 cells of the second simulation, which skips its walk (wave_emit_ll2) */,

@@ -103,6 +103,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NHW_L4A_WAV
 	luma_p4a_par(&c, threadIdx.x, dyn_lds);
 }
 
+/* the chroma tail of a production batch as a kernel of its own (chroma_tail_once_par: each plane row read once, cproc not written); the stage
+ * checks and NHW_CHROMA_TAIL_ONCE=0 run k_phase<PH_C5>, the staged form.  Its two sets of parked rows (35.6 KB of LDS) allow four workgroups
+ * a CU; the register allocator took 129, one over what four wavefronts a SIMD allow, and takes 128 without scratch when held to four. */
+#ifndef NHW_CTAIL_WAVES
+#define NHW_CTAIL_WAVES 4
+#endif
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NHW_CTAIL_WAVES, NHW_CTAIL_WAVES))) void k_chroma_tail(NhwWs ws, int comp)
+{
+	extern __shared__ __attribute__((aligned(16))) int16_t dyn_lds[];
+	Ctx c;
+	ctx_load(&c, ws, blockIdx.x, comp);
+	chroma_tail_once_par(&c, comp, threadIdx.x, dyn_lds);
+}
+
 /* passes that run one wavefront per image (nhw_tail_wave.h): four images per workgroup, no workgroup barriers */
 template <int PH>
 __global__ __launch_bounds__(256) void k_wave(NhwWs ws, int flags /* bit 0, WV_EMIT and WV_DQ0: the LL2 bump walk is made once, by the emission (wave_emit_ll2); bit 1, WV_DQ0 and WV_QUANT: the simulation leaves the level-2 details behind the quantiser's loops 2 and 3 in B_KMAP, the quantiser takes them from there (wave_dequant_details) */)
@@ -509,7 +523,7 @@ int nhw_tail_set_attrs(const char **where)
 {
 #define SETATTR(fn) do { const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void *>(&fn), hipFuncAttributeMaxDynamicSharedMemorySize, 100 << 10); \
                          if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(" #fn ", MaxDynamicSharedMemorySize)"; return (int)e_; } } while (0)
-	SETATTR(k_phase<PH_L1>); SETATTR(k_phase<PH_L2>); SETATTR(k_phase<PH_L3>); SETATTR(k_phase<PH_C5>);
+	SETATTR(k_phase<PH_L1>); SETATTR(k_phase<PH_L2>); SETATTR(k_phase<PH_L3>); SETATTR(k_phase<PH_C5>); SETATTR(k_chroma_tail);
 	for (const void *fn : { reinterpret_cast<const void *>(&k_l2_recon<false>), reinterpret_cast<const void *>(&k_l2_recon<true>), reinterpret_cast<const void *>(&k_l2_recon<true, true>) }) {
 		const hipError_t e_ = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(H * (H + 2) * sizeof(int16_t) + 288));
 		if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(k_l2_recon, MaxDynamicSharedMemorySize)"; return (int)e_; }
@@ -531,6 +545,11 @@ void nhw_launch_phase(int ph, const NhwWs &ws, int comp, hipStream_t s)
 	PHASE(PH_LLC); PHASE(PH_L4C2); PHASE(PH_C0); PHASE(PH_C2); PHASE(PH_C3); PHASE(PH_C4); PHASE(PH_C5);
 	}
 #undef PHASE
+}
+void nhw_launch_chroma_tail(const NhwWs &ws, int comp, bool once, hipStream_t s)
+{
+	if (once && !ws.dbg) k_chroma_tail<<<ws.n, 256, CT_LDS_BYTES, s>>>(ws, comp);
+	else nhw_launch_phase(PH_C5, ws, comp, s);
 }
 void nhw_launch_pack_chroma(const NhwWs &ws, hipStream_t s)
 {

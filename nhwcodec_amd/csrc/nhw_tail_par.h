@@ -863,12 +863,104 @@ DEV void clean_details_seq(Ctx *c, int tid, bool ll_in_plane /* Y26 has put the 
  * for 128 KB of coefficients and 64 KB of symbols.) */
 #define CQROW 264
 #define CQ_LDS_BYTES (4 * 16 * CQROW + 2 * (H + 2))
+/* The symbols of one row (both forms of the chroma tail): cur[k] = column lane + 64 k as it stands in front of the quantiser, first_next the
+ * cell the look from column 255 goes to. */
+DEV void cq_symbols(const int cur[4], int first_next, int lane, int sym[4])
+{
+	/* A row whose every cell lies in -6 .. 6 is all zero symbols, whatever its neighbours: such a cell is in the dead zone, it is neither half
+	 * of a -7 / -8 pair nor a 7 that could be raised, and the keep rule can only floor its magnitude to 0.  Chroma rows mostly are (five in
+	 * six of a q20 batch of the generator's pictures), and the kernel is bound by vector issue. */
+	if (!__any((unsigned)(cur[0] + 6) > 12u || (unsigned)(cur[1] + 6) > 12u || (unsigned)(cur[2] + 6) > 12u || (unsigned)(cur[3] + 6) > 12u)) {
+		for (int k = 0; k < 4; k++) sym[k] = 128;
+		return;
+	}
+	unsigned P, S, T;
+	BS_PRED(P, cur, 4, (unsigned)(x + 8) < 2u); BS_PRED(S, cur, 4, x > 6 && x <= 127 && (x & 7) >= 6); BS_PRED(T, cur, 4, x == 7);
+	const unsigned inrow = lane == 63 ? 0x7u : 0xFu;           /* columns 0..254: neither reaches across the row end */
+	const unsigned pc = P & bs_dn(P, lane) & inrow, bc = S & bs_dn(T, lane) & inrow;
+	const unsigned pf = __any(pc != 0) ? bs_from4(alt_runs(bs_ballot4(pc))) : 0u;
+	const unsigned bf = __any(bc != 0) ? bs_from4(alt_runs(bs_ballot4(bc))) : 0u;
+	const unsigned pair = pf | bs_up<4>(pf, lane), raised = bs_up<4>(bf, lane);
+	for (int k = 0; k < 4; k++) {
+		const int x = cur[k], nx = right_of_dpp(cur, k, 4, lane, first_next);
+		int a = (raised >> k) & 1 ? 8 : x;
+		const bool neg = a < 0;
+		int m = neg ? -a : a;
+		const bool keep = (nx < 0 && nx > -8) ? (m & 7) >= 6 : (m & 7) == 7;
+		m = (neg && !keep) ? (m & 504) : m;
+		a = neg ? -m : m;
+		int s = (unsigned)(a + DEADZONE - 1) < (unsigned)(2 * DEADZONE - 1) ? 128 : ((a + 128) & 248);
+		s = (pair >> k) & 1 ? 120 : s;
+		if (__ballot(x > 127 || x < -127)) {                     /* marks of the pass before and values beyond +-127: rare, whole words skip this */
+			if (x == 12400) s = 124; else if (x == 12600) s = 126; else if (x == 12900) s = 122; else if (x == 13000) s = 130;
+			else if (x > 127) s = big_code(x, k_big_pos);
+			else if (x < -127) s = big_code(-x, k_big_neg);
+		}
+		sym[k] = s;
+	}
+}
+/* Sixteen parked rows rb0 .. rb0 + 15 leave (both forms of the chroma tail): lane l takes rows 8 (l & 1) .. + 7 of strip l >> 1, 64 stream
+ * bytes.  The flush is F = rb0 / 16 whoever runs it: B_CNZQ and cfbase[0 .. 15] are laid out by F, and cfbase[F] is an absolute offset into
+ * B_CVALS -- pack_chroma_order derives the stream slices from F alone.  `region` is the caller's 32768 bytes of B_CVALS (four flushes fit
+ * it), vtotal its fill so far (wave-uniform); cfbase[16 + region] is the fill, which the packetiser's histogram reads. */
+DEV void cq_flush(Ctx *c, int comp, uint8_t *park, int rb0, int region, unsigned &vtotal, bool dense, int lane)
+{
+	uint8_t *ubytes = c->ubytes;                                    /* Q bytes of its own (until round 5: the band plane, which Y29 holds above q21) */
+	uint8_t *scan = c->scan + 4 * Q;
+	const int strip = lane >> 1, rb = rb0 + 8 * (lane & 1);
+	uint32_t w[16];
+	for (int j = 0; j < 8; j++) {
+		const uint2 x = *reinterpret_cast<const uint2 *>(park + (8 * (lane & 1) + j) * CQROW + 8 * strip);
+		if ((rb + j) & 1) { w[2 * j] = __builtin_bswap32(x.y); w[2 * j + 1] = __builtin_bswap32(x.x); } else { w[2 * j] = x.x; w[2 * j + 1] = x.y; }
+	}
+	const int pos = strip * (8 * H) + 8 * rb;
+	if (!comp) { for (int j = 0; j < 4; j++) reinterpret_cast<uint4 *>(ubytes + pos)[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]); return; }
+	uint32_t o[32];
+	for (int j = 0; j < 4; j++) {
+		const uint4 u4 = reinterpret_cast<const uint4 *>(ubytes + pos)[j];
+		const uint32_t uu[4] = { u4.x, u4.y, u4.z, u4.w };
+		for (int e = 0; e < 4; e++) {
+			const uint32_t u = uu[e], v = w[4 * j + e];
+			o[8 * j + 2 * e] = (u & 0xFF) | ((v & 0xFF) << 8) | ((u & 0xFF00) << 8) | ((v & 0xFF00) << 16);
+			o[8 * j + 2 * e + 1] = ((u >> 16) & 0xFF) | (((v >> 16) & 0xFF) << 8) | ((u >> 24) << 16) | ((v >> 24) << 24);
+		}
+	}
+	if (dense) for (int j = 0; j < 8; j++) reinterpret_cast<uint4 *>(scan + 2 * pos)[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+	/* the merged stream leaves as a list, like the luma part (wave_quantise_luma): the lane's 128 symbols are two slices of 64 -- a
+	 * non-zero map each, [flush][lane][2] -- and their symbols that are not 128 go behind those of the lanes before it (the wavefronts
+	 * of the workgroup run side by side: each appends to a region of its own, 32768 x wavefront, the size of all its symbols).  The
+	 * packetiser's chroma part puts the maps into stream order (pack_chroma_order). */
+	const int F = rb0 >> 4;
+	const uint64_t M0 = (uint64_t)ne_mask32(o, 0x80808080u) | (uint64_t)ne_mask32(o + 8, 0x80808080u) << 32;
+	const uint64_t M1 = (uint64_t)ne_mask32(o + 16, 0x80808080u) | (uint64_t)ne_mask32(o + 24, 0x80808080u) << 32;
+	*reinterpret_cast<uint4 *>(c->cnzq + (F * 64 + lane) * 2) = make_uint4((uint32_t)M0, (uint32_t)(M0 >> 32), (uint32_t)M1, (uint32_t)(M1 >> 32));
+	const unsigned cnt = (unsigned)(__builtin_popcountll(M0) + __builtin_popcountll(M1));
+	unsigned incl = cnt;
+	for (int o_ = 1; o_ < 64; o_ <<= 1) { const unsigned t_ = (unsigned)__shfl_up((int)incl, o_); if (lane >= o_) incl += t_; }
+	if (lane == 0) { c->cfbase[F] = 32768u * region + vtotal; c->cfbase[16 + region] = vtotal + (unsigned)__builtin_amdgcn_readlane((int)incl, 63); }   /* [16 + region]: the wavefront's values so far (its total behind the last flush) */
+	uint8_t *vp = c->cvals + 32768u * region + vtotal + incl - cnt;
+	vtotal += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
+	/* the symbols by position: a slice's sixteen dwords wait in the wavefront's parked rows -- every lane has read its own above, the
+	 * next sixteen rows have not begun -- word k of lane l at dword 64 k + l (no bank conflicts), and leave byte by byte for the set bits */
+	uint32_t *sw = reinterpret_cast<uint32_t *>(park);
+	static_assert(16 * CQROW >= 16 * 64 * 4, "a slice of every lane fits the parked rows");
+#pragma unroll
+	for (int hs = 0; hs < 2; hs++) {
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
+#pragma unroll
+		for (int k = 0; k < 16; k++) sw[64 * k + lane] = o[16 * hs + k];
+		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
+		const uint8_t *sb = reinterpret_cast<const uint8_t *>(sw) + 4 * lane;
+		for (uint64_t m = hs ? M1 : M0; m; m &= m - 1) {
+			const int bit = __builtin_ctzll(m);
+			*vp++ = sb[256 * (bit >> 2) + (bit & 3)];
+		}
+	}
+}
 DEV void quantise_chroma_par(Ctx *c, int comp, int tid, int16_t *lds, bool write_plane, bool dense /* the merged byte stream as well (stage checks) */)
 {
 	unsigned vtotal = 0;                                            /* V: values this wavefront has appended to the list (wave-uniform) */
 	int16_t *p = c->cproc;
-	uint8_t *ubytes = c->ubytes;                                    /* Q bytes of its own (until round 5: the band plane, which Y29 holds above q21) */
-	uint8_t *scan = c->scan + 4 * Q;
 	const int lane = tid & 63, wv = tid >> 6;
 	uint8_t *park = reinterpret_cast<uint8_t *>(lds) + wv * 16 * CQROW;
 	int16_t *nf = lds + 4 * 16 * CQROW / 2;                        /* nf[r]: cell (r, 0) as it was (r = 256: what lies behind the plane) */
@@ -880,85 +972,15 @@ DEV void quantise_chroma_par(Ctx *c, int comp, int tid, int16_t *lds, bool write
 	for (int i = 0; i < 64; i++) {
 		const int r = r0 + i;
 		if (i + 1 < 64) for (int k = 0; k < 4; k++) nxt[k] = p[(r + 1) * H + lane + 64 * k];
-		const int first_next = nf[r + 1];
-		unsigned P, S, T;
-		BS_PRED(P, cur, 4, (unsigned)(x + 8) < 2u); BS_PRED(S, cur, 4, x > 6 && x <= 127 && (x & 7) >= 6); BS_PRED(T, cur, 4, x == 7);
-		const unsigned inrow = lane == 63 ? 0x7u : 0xFu;           /* columns 0..254: neither reaches across the row end */
-		const unsigned pc = P & bs_dn(P, lane) & inrow, bc = S & bs_dn(T, lane) & inrow;
-		const unsigned pf = __any(pc != 0) ? bs_from4(alt_runs(bs_ballot4(pc))) : 0u;
-		const unsigned bf = __any(bc != 0) ? bs_from4(alt_runs(bs_ballot4(bc))) : 0u;
-		const unsigned pair = pf | bs_up<4>(pf, lane), raised = bs_up<4>(bf, lane);
+		int sym[4];
+		cq_symbols(cur, nf[r + 1], lane, sym);
 		for (int k = 0; k < 4; k++) {
-			const int x = cur[k], nx = right_of_dpp(cur, k, 4, lane, first_next);
-			int a = (raised >> k) & 1 ? 8 : x;
-			const bool neg = a < 0;
-			int m = neg ? -a : a;
-			const bool keep = (nx < 0 && nx > -8) ? (m & 7) >= 6 : (m & 7) == 7;
-			m = (neg && !keep) ? (m & 504) : m;
-			a = neg ? -m : m;
-			int sym = (unsigned)(a + DEADZONE - 1) < (unsigned)(2 * DEADZONE - 1) ? 128 : ((a + 128) & 248);
-			sym = (pair >> k) & 1 ? 120 : sym;
-			if (__ballot(x > 127 || x < -127)) {                     /* marks of the pass before and values beyond +-127: rare, whole words skip this */
-				if (x == 12400) sym = 124; else if (x == 12600) sym = 126; else if (x == 12900) sym = 122; else if (x == 13000) sym = 130;
-				else if (x > 127) sym = big_code(x, k_big_pos);
-				else if (x < -127) sym = big_code(-x, k_big_neg);
-			}
-			if (write_plane) p[r * H + lane + 64 * k] = (int16_t)sym;
-			park[(i & 15) * CQROW + lane + 64 * k] = (uint8_t)sym;
+			if (write_plane) p[r * H + lane + 64 * k] = (int16_t)sym[k];
+			park[(i & 15) * CQROW + lane + 64 * k] = (uint8_t)sym[k];
 		}
-		if ((i & 15) == 15) {                                      /* 16 rows complete: lane l takes rows 8 (l & 1) .. + 7 of strip l >> 1, 64 stream bytes */
+		if ((i & 15) == 15) {                                      /* 16 rows complete */
 			__threadfence_block();
-			const int strip = lane >> 1, rb = r - 15 + 8 * (lane & 1);
-			uint32_t w[16];
-			for (int j = 0; j < 8; j++) {
-				const uint2 x = *reinterpret_cast<const uint2 *>(park + (8 * (lane & 1) + j) * CQROW + 8 * strip);
-				if ((rb + j) & 1) { w[2 * j] = __builtin_bswap32(x.y); w[2 * j + 1] = __builtin_bswap32(x.x); } else { w[2 * j] = x.x; w[2 * j + 1] = x.y; }
-			}
-			const int pos = strip * (8 * H) + 8 * rb;
-			if (!comp) { for (int j = 0; j < 4; j++) reinterpret_cast<uint4 *>(ubytes + pos)[j] = make_uint4(w[4 * j], w[4 * j + 1], w[4 * j + 2], w[4 * j + 3]); }
-			else {
-				uint32_t o[32];
-				for (int j = 0; j < 4; j++) {
-					const uint4 u4 = reinterpret_cast<const uint4 *>(ubytes + pos)[j];
-					const uint32_t uu[4] = { u4.x, u4.y, u4.z, u4.w };
-					for (int e = 0; e < 4; e++) {
-						const uint32_t u = uu[e], v = w[4 * j + e];
-						o[8 * j + 2 * e] = (u & 0xFF) | ((v & 0xFF) << 8) | ((u & 0xFF00) << 8) | ((v & 0xFF00) << 16);
-						o[8 * j + 2 * e + 1] = ((u >> 16) & 0xFF) | (((v >> 16) & 0xFF) << 8) | ((u >> 24) << 16) | ((v >> 24) << 24);
-					}
-				}
-				if (dense) for (int j = 0; j < 8; j++) reinterpret_cast<uint4 *>(scan + 2 * pos)[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
-				/* the merged stream leaves as a list, like the luma part (wave_quantise_luma): the lane's 128 symbols are two slices of 64 -- a
-				 * non-zero map each, [flush][lane][2] -- and their symbols that are not 128 go behind those of the lanes before it (the wavefronts
-				 * of the workgroup run side by side: each appends to a region of its own, 32768 x wavefront, the size of all its symbols).  The
-				 * packetiser's chroma part puts the maps into stream order (pack_chroma_order). */
-				const int F = 4 * wv + (i >> 4);
-				const uint64_t M0 = (uint64_t)ne_mask32(o, 0x80808080u) | (uint64_t)ne_mask32(o + 8, 0x80808080u) << 32;
-				const uint64_t M1 = (uint64_t)ne_mask32(o + 16, 0x80808080u) | (uint64_t)ne_mask32(o + 24, 0x80808080u) << 32;
-				*reinterpret_cast<uint4 *>(c->cnzq + (F * 64 + lane) * 2) = make_uint4((uint32_t)M0, (uint32_t)(M0 >> 32), (uint32_t)M1, (uint32_t)(M1 >> 32));
-				const unsigned cnt = (unsigned)(__builtin_popcountll(M0) + __builtin_popcountll(M1));
-				unsigned incl = cnt;
-				for (int o_ = 1; o_ < 64; o_ <<= 1) { const unsigned t_ = (unsigned)__shfl_up((int)incl, o_); if (lane >= o_) incl += t_; }
-				if (lane == 0) { c->cfbase[F] = 32768u * wv + vtotal; c->cfbase[16 + wv] = vtotal + (unsigned)__builtin_amdgcn_readlane((int)incl, 63); }   /* [16 + wv]: the wavefront's values so far (its total behind the last flush) */
-				uint8_t *vp = c->cvals + 32768u * wv + vtotal + incl - cnt;
-				vtotal += (unsigned)__builtin_amdgcn_readlane((int)incl, 63);
-				/* the symbols by position: a slice's sixteen dwords wait in the wavefront's parked rows -- every lane has read its own above, the
-				 * next sixteen rows have not begun -- word k of lane l at dword 64 k + l (no bank conflicts), and leave byte by byte for the set bits */
-				uint32_t *sw = reinterpret_cast<uint32_t *>(park);
-				static_assert(16 * CQROW >= 16 * 64 * 4, "a slice of every lane fits the parked rows");
-#pragma unroll
-				for (int hs = 0; hs < 2; hs++) {
-					__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-#pragma unroll
-					for (int k = 0; k < 16; k++) sw[64 * k + lane] = o[16 * hs + k];
-					__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier();
-					const uint8_t *sb = reinterpret_cast<const uint8_t *>(sw) + 4 * lane;
-					for (uint64_t m = hs ? M1 : M0; m; m &= m - 1) {
-						const int bit = __builtin_ctzll(m);
-						*vp++ = sb[256 * (bit >> 2) + (bit & 3)];
-					}
-				}
-			}
+			cq_flush(c, comp, park, r - 15, wv, vtotal, dense, lane);
 			__threadfence_block();
 		}
 		for (int k = 0; k < 4; k++) cur[k] = nxt[k];
@@ -2494,26 +2516,74 @@ DEV void chroma_p3_par(Ctx *c, int comp, int tid)                     /* :2316-2
 		*reinterpret_cast<uint4 *>(jp + e0) = make_uint4(out[0], out[1], out[2], out[3]);
 	}
 }
-DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bool write_plane)
+/* The chroma marks (q >= 18), the rules of a cell: d, d1 are the cell's and its right neighbour's distance from cll1 at the row's shift; a mark
+ * goes into the first of the cell's HL1, LH1, HH1 details that is below 8 in magnitude.  Both forms of the tail take them from here, and so
+ * does the table of column 0's outcome (chroma_tail_once_par). */
+DEV bool uv_pair_pos(int d, int d1) { return d > 3 && d < 7 && d1 > 2 && d1 < 7; }
+DEV bool uv_pair_neg(int d, int d1) { return d < -3 && d > -7 && d1 < -2 && d1 > -8; }
+DEV bool uv_single(int d, int d1, int res_uv) { return iabs(d) > res_uv && (d > 0 || d != -5 || d1 < 0); }
+DEV int uv_code(bool pair, bool pair_pos, int d) { return pair ? (pair_pos ? 12400 : 12600) : (d > 0 ? 12900 : 13000); }
+DEV int uv_slot(int hl, int lh, int hh) { return iabs(hl) < 8 ? 0 : iabs(lh) < 8 ? 1 : iabs(hh) < 8 ? 2 : -1; }   /* 0 HL1, 1 LH1, 2 HH1, -1: no free detail cell */
+struct UvRow { int pl[2], hl[2], lh[2], hh[2], o0[2], o1[2]; };   /* a lane's cells of an LL1 row (columns lane, lane + 64): reconstruction, the three details, cll1 at the shifted position and behind it */
+/* The marks of one LL1 row, a wavefront per row: code[k] is the mark of the lane's cell k (0: none) when want_codes; returns whether the row
+ * ends in a pair mark at its last column (wave-uniform).  One wavefront per row, lane l owns columns l and l + 64 of the 128-wide band; the
+ * pair marks are a walk that skips the partner, resolved on the row's "pair here and a free detail cell" mask (alt_runs).  Cell (r, 127)
+ * reads column 128 of its row as its right neighbour: that is the HL detail cell of (r, 0), which (r, 0) may just have marked -- then
+ * neither a pair nor the d == -5 rule can hold at (r, 127). */
+DEV bool uv_row_marks(const UvRow &x, int res_uv, int lane, bool want_codes, int code[2])
+{
+	int d[2], d1[2];
+	for (int k = 0; k < 2; k++) d[k] = x.pl[k] - x.o0[k];
+	/* every rule wants |d| > 3 of the marking cell (a pair 4 .. 6, a single more than res_uv >= 4): a row without one takes no mark and does not
+	 * end in a pair -- seven rows in eight of a q20 batch of the generator's pictures */
+	if (!__any(iabs(d[0]) > 3 || iabs(d[1]) > 3)) { code[0] = code[1] = 0; return false; }
+	const int hl_first = __shfl(x.hl[0], 0);
+	for (int k = 0; k < 2; k++) {
+		int pn = right_of(x.pl, k, 2, 1, lane);
+		if (k == 1 && lane == 63) pn = hl_first;
+		d1[k] = pn - x.o1[k];
+	}
+	uint64_t pp[2], pn_[2], fr[2], sg[2], fhl[2], flh[2], m5[2];
+	for (int k = 0; k < 2; k++) {
+		pp[k] = __ballot(uv_pair_pos(d[k], d1[k]));
+		pn_[k] = __ballot(uv_pair_neg(d[k], d1[k]));
+		fhl[k] = __ballot(iabs(x.hl[k]) < 8); flh[k] = __ballot(iabs(x.lh[k]) < 8);
+		fr[k] = fhl[k] | flh[k] | __ballot(iabs(x.hh[k]) < 8);
+		sg[k] = __ballot(uv_single(d[k], d1[k], res_uv));
+		m5[k] = __ballot(d[k] == -5);
+	}
+	uint64_t f[2] = { (pp[0] | pn_[0]) & fr[0], (pp[1] | pn_[1]) & fr[1] };
+	if ((fhl[0] & 1) && ((f[0] | sg[0]) & 1)) {              /* (r, 0) marks its HL cell */
+		f[1] &= ~(1ull << 63);
+		if (m5[1] >> 63) sg[1] &= ~(1ull << 63);
+	}
+	const M4 fired = alt_runs(M4{ { f[0], f[1], 0, 0 } });
+	const bool ends_in_pair = (fired.w[1] >> 63) != 0;
+	if (!want_codes) return ends_in_pair;
+	const M4 vis = ~up1(fired);
+	for (int k = 0; k < 2; k++) {
+		const bool pair = (fired.w[k] >> lane) & 1;
+		const bool single = !pair && ((vis.w[k] >> lane) & 1) && ((sg[k] >> lane) & 1);
+		code[k] = pair || single ? uv_code(pair, (pp[k] >> lane) & 1, d[k]) : 0;
+	}
+	return ends_in_pair;
+}
+/* The marks of a component's plane (q >= 18).  store: the staged form, the codes go into the detail bands of cproc.  Else only the rows'
+ * shifts are found (shift[], haz[]: H / 2 ints each) and the plane is left alone: the production walk marks in registers. */
+DEV void chroma_marks_par(Ctx *c, int comp, int tid, int *shift, bool store)
 {
 	int16_t *p = c->cproc, *o = c->cll1;
 	const int q = c->q;
-	PROF_BEGIN();
-	if (q >= 18) {
+	{
 		/* :2372-2427.  The reference walks the LL1 band with an index into cll1 that is NOT reset per row: it runs one
 		 * further ahead of the position each time a pair mark is taken at the last column of a row (the skip of the
 		 * partner then eats the first increment of the next row).  So row r compares against cll1 shifted by the
 		 * number of such events in the rows above it.  Whether a row ends in one depends only on its own shift, so
 		 * the shifts are found by iterating "evaluate every row with its current shift, re-count" to a fixed point
-		 * (one round when there is no event, which is the rule), then the rows are marked, all in parallel.
-		 *
-		 * One wavefront per row, lane l owns columns l and l + 64 of the 128-wide band; the pair marks are a walk that
-		 * skips the partner, resolved on the row's "pair here and a free detail cell" mask (alt_runs).  Cell (r, 127)
-		 * reads column 128 of its row as its right neighbour: that is the HL detail cell of (r, 0), which (r, 0)
-		 * may just have marked -- then neither a pair nor the d == -5 rule can hold at (r, 127). */
+		 * (one round when there is no event, which is the rule), then the rows are marked, all in parallel (uv_row_marks). */
 		const int res_uv = q > 17 ? 4 : 5;
 		const int lane = tid & 63, wv = tid >> 6;
-		int *shift = reinterpret_cast<int *>(lds), *haz = shift + H / 2;
+		int *haz = shift + H / 2;
 		/* a row can only end in a pair mark if its last cell is a pair candidate with a free detail cell: where no row's is (the rule), the
 		 * evaluation pass is not needed -- every shift is 0 -- and the rows are marked at once (they were loaded twice: 1.3 GB per batch) */
 		bool last_cand = false;
@@ -2521,8 +2591,7 @@ DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bo
 			shift[tid] = 0; haz[tid] = 0;
 			const int at = tid * H + H / 2 - 1, ko = tid * (H / 2) + H / 2 - 1;
 			const int d = p[at] - o[ko], d1 = p[tid * H + H / 2] - o[ko + 1];
-			const bool pair = (d > 3 && d < 7 && d1 > 2 && d1 < 7) || (d < -3 && d > -7 && d1 < -2 && d1 > -8);
-			last_cand = pair && (iabs(p[at + H / 2]) < 8 || iabs(p[at + Q / 2]) < 8 || iabs(p[at + Q / 2 + H / 2]) < 8);
+			last_cand = (uv_pair_pos(d, d1) || uv_pair_neg(d, d1)) && uv_slot(p[at + H / 2], p[at + Q / 2], p[at + Q / 2 + H / 2]) >= 0;
 		}
 		const int first_pass = __syncthreads_or(last_cand) ? 0 : 1;
 		for (int pass = first_pass;; pass++) {                     /* pass >= 1 with stable shifts: mark */
@@ -2535,6 +2604,7 @@ DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bo
 				BARRIER();
 				mark = !changed;
 			}
+			if (mark && !store) break;                             /* the shifts stand: the walk marks (the test is the same for every thread) */
 			/* a row's twelve cells per lane are requested while the row before is evaluated (rows are independent; a row's marks land in its own row) */
 			int16_t nx[12];
 			auto fetch = [&](int r) {
@@ -2548,46 +2618,22 @@ DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bo
 			};
 			fetch(wv);
 			for (int r = wv; r < H / 2; r += 4) {
-				int pl[2], hl[2], lh[2], hh[2], d[2], d1[2];
+				UvRow x;
 #pragma unroll
 				for (int k = 0; k < 2; k++) {
-					pl[k] = nx[6 * k]; hl[k] = nx[6 * k + 1]; lh[k] = nx[6 * k + 2]; hh[k] = nx[6 * k + 3];
-					d[k] = pl[k] - nx[6 * k + 4];
-					d1[k] = nx[6 * k + 5];                              /* the reference cell of the right neighbour */
+					x.pl[k] = nx[6 * k]; x.hl[k] = nx[6 * k + 1]; x.lh[k] = nx[6 * k + 2]; x.hh[k] = nx[6 * k + 3];
+					x.o0[k] = nx[6 * k + 4]; x.o1[k] = nx[6 * k + 5];       /* (o1: the reference cell of the right neighbour) */
 				}
 				if (r + 4 < H / 2) fetch(r + 4);
-				const int hl_first = __shfl(hl[0], 0);
+				int code[2];
+				const bool ends_in_pair = uv_row_marks(x, res_uv, lane, mark, code);
+				if (!mark) { if (lane == 0) haz[r] = (int)ends_in_pair; continue; }
 				for (int k = 0; k < 2; k++) {
-					int pn = right_of(pl, k, 2, 1, lane);
-					if (k == 1 && lane == 63) pn = hl_first;
-					d1[k] = pn - d1[k];
-				}
-				uint64_t pp[2], pn_[2], fr[2], sg[2], fhl[2], flh[2], m5[2];
-				for (int k = 0; k < 2; k++) {
-					pp[k] = __ballot(d[k] > 3 && d[k] < 7 && d1[k] > 2 && d1[k] < 7);
-					pn_[k] = __ballot(d[k] < -3 && d[k] > -7 && d1[k] < -2 && d1[k] > -8);
-					fhl[k] = __ballot(iabs(hl[k]) < 8); flh[k] = __ballot(iabs(lh[k]) < 8);
-					fr[k] = fhl[k] | flh[k] | __ballot(iabs(hh[k]) < 8);
-					sg[k] = __ballot(iabs(d[k]) > res_uv && (d[k] > 0 || d[k] != -5 || d1[k] < 0));
-					m5[k] = __ballot(d[k] == -5);
-				}
-				uint64_t f[2] = { (pp[0] | pn_[0]) & fr[0], (pp[1] | pn_[1]) & fr[1] };
-				if ((fhl[0] & 1) && ((f[0] | sg[0]) & 1)) {              /* (r, 0) marks its HL cell */
-					f[1] &= ~(1ull << 63);
-					if (m5[1] >> 63) sg[1] &= ~(1ull << 63);
-				}
-				const M4 fired = alt_runs(M4{ { f[0], f[1], 0, 0 } });
-				if (!mark) { if (lane == 0) haz[r] = (int)(fired.w[1] >> 63); continue; }
-				const M4 vis = ~up1(fired);
-				for (int k = 0; k < 2; k++) {
-					const bool pair = (fired.w[k] >> lane) & 1;
-					const bool single = !pair && ((vis.w[k] >> lane) & 1) && ((sg[k] >> lane) & 1);
-					if (!pair && !single) continue;
-					const int16_t code = pair ? (((pp[k] >> lane) & 1) ? 12400 : 12600) : (d[k] > 0 ? 12900 : 13000);
-					const int at = r * H + lane + 64 * k;
-					if (iabs(hl[k]) < 8) p[at + H / 2] = code;
-					else if (iabs(lh[k]) < 8) p[at + Q / 2] = code;
-					else if (iabs(hh[k]) < 8) p[at + Q / 2 + H / 2] = code;
+					if (!code[k]) continue;
+					const int at = r * H + lane + 64 * k, slot = uv_slot(x.hl[k], x.lh[k], x.hh[k]);
+					if (slot == 0) p[at + H / 2] = (int16_t)code[k];
+					else if (slot == 1) p[at + Q / 2] = (int16_t)code[k];
+					else if (slot == 2) p[at + Q / 2 + H / 2] = (int16_t)code[k];
 				}
 			}
 			BARRIER();
@@ -2595,9 +2641,13 @@ DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bo
 		}
 		if (tid == 0) { int ev = 0; for (int r = 0; r < H / 2; r++) ev += haz[r]; c->m->pad = comp ? c->m->pad + (ev << 8) : ev; }   /* diagnostics: rows that ended in a pair mark */
 	}
-	BARRIER();
-	if (!tid) PROF(c, 27);
-	copy_block_par(c->cl2save, H / 2, p, H, H / 2, H / 2, tid);    /* :2431-2439 */
+}
+/* The LL2 band of a component behind the marks (both forms of the tail): the smoothing of q <= 11, the emission with its exception list, the
+ * bit-1 bytes.  It takes the band from cl2save, on an LDS copy (lds: the band's 8 KB and the scans' scratch behind it). */
+DEV void chroma_ll2_emit_par(Ctx *c, int comp, int tid, int16_t *lds, int16_t *clear_plane /* the staged form: the work plane, whose LL2 quadrant the emission clears (production: nobody reads it, the walk takes the quadrant as 0) */)
+{
+	const int q = c->q;
+	PROF_BEGIN();
 	for (int idx = tid; idx < (H / 4) * (H / 4); idx += NT) lds[idx] = c->cl2save[(idx >> 6) * (H / 2) + (idx & 63)];   /* the LL2 band for the emission below */
 	BARRIER();
 	if (q <= 11 && tid < 64) {
@@ -2656,7 +2706,7 @@ DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bo
 		BARRIER();
 		if (tid == 0) { c->exw[e0] = 0; c->exw[e0 + 1] = 0; c->m->exw_len = e0 + 2 + 3 * (int)total; }   /* :2489 (U), :2770 (V) */
 	}
-	for (int idx = tid; idx < (H / 4) * (H / 4); idx += NT) p[(idx >> 6) * H + (idx & 63)] = 0;   /* the emission clears the band */
+	if (clear_plane) for (int idx = tid; idx < (H / 4) * (H / 4); idx += NT) clear_plane[(idx >> 6) * H + (idx & 63)] = 0;   /* the emission clears the band */
 	BARRIER();
 	{                                                              /* bit 1 of every LL2 sample (:2527-2548) */
 		uint8_t *dst = comp ? c->res_v64 : c->res_u64;
@@ -2668,8 +2718,120 @@ DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bo
 		}
 	}
 	if (!tid) PROF(c, 21);
+}
+/* The chroma tail, staged form: every step leaves its plane where the next one (and a stage check) reads it.  Production batches run
+ * chroma_tail_once_par below; this one stays for the stage checks (write_plane) and behind NHW_CHROMA_TAIL_ONCE=0. */
+DEV void chroma_p5_par(Ctx *c, int comp, int tid, int16_t *lds, int *sh_misc, bool write_plane)
+{
+	PROF_BEGIN();
+	if (c->q >= 18) chroma_marks_par(c, comp, tid, reinterpret_cast<int *>(lds), true);
+	BARRIER();
+	if (!tid) PROF(c, 27);
+	copy_block_par(c->cl2save, H / 2, c->cproc, H, H / 2, H / 2, tid);    /* :2431-2439 */
+	chroma_ll2_emit_par(c, comp, tid, lds, c->cproc);
 	BARRIER();
 	quantise_chroma_par(c, comp, tid, lds, write_plane, write_plane);
+	if (!tid) PROF(c, 22);
+}
+
+/* The chroma tail, production form: a wavefront reads each row of the plane once, decides the row's marks in registers and quantises the row
+ * from those registers; cproc is not written at all (in a production batch nothing reads it behind this kernel: the next head stores HL1,
+ * LH1 and HH1, k_chroma_loops the LL1 block).
+ *
+ * Marks are row-local: LL1 row R reads and writes cells of rows R (reconstruction, HL1) and R + 128 (LH1, HH1) and cll1's row R at the row's
+ * shift.  In front of the quantiser row R is [level-2 block row R from cl2save, its LL2 quadrant cleared by the emission | HL1 with marks]
+ * and row R + 128 is [LH1 | HH1 with marks]: the lane layouts of the marks (columns l, l + 64 of a 128-wide band) and of the quantiser
+ * (columns l + 64 k of the 256-wide row) are the same cells, so wavefront w walks LL1 rows 32 w .. 32 w + 31 and quantises the two plane
+ * rows of each in lockstep, sixteen of each parked at a time: flushes 2 w, 2 w + 1 (rows R) and 8 + 2 w, 8 + 2 w + 1 (rows R + 128), 64 rows
+ * and so at most 32768 values in its region of B_CVALS, as before.  B_CNZQ and cfbase are laid out by F, whoever wrote it (cq_flush).
+ *
+ * What crosses rows:
+ *   * the shifts into cll1: found first (chroma_marks_par without the stores; no second read of a row where no row can end in a pair mark);
+ *   * the look from column 255 of plane row r at cell (r + 1, 0) as it stands in front of the quantiser: nf[r + 1], tabulated before the
+ *     walk.  r + 1 < 128: the level-2 block's column 0 (0 inside the LL2 quadrant); r + 1 = 256: what lies behind the plane; else LH1 of
+ *     column 0 of LL1 row R' = r + 1 - 128 BEHIND that row's marks.  Column 0 needs no walk: it is the first cell of its row, so no pair
+ *     before it can skip it (alt_runs: a run's first cell fires; up1 shifts nothing into column 0), hence it takes a pair mark exactly
+ *     when it is a pair candidate with a free detail cell, else a single mark exactly when the single rule holds; the (R, 0)-marks-HL
+ *     exception only changes column 127's outcome.  So its mark is a function of d, d1 of columns 0 and 1 at the row's shift and of its own
+ *     hl, lh, hh, and it lands in LH1 exactly when uv_slot says 1.  (A table for all 128 rows rather than a one-row look-ahead: the row
+ *     behind a wavefront's last is another wavefront's first, and the table costs seven cells a row once.) */
+#define CT_PARKS (2 * 4 * 16 * CQROW)                          /* two sets of sixteen parked rows a wavefront */
+#define CT_LDS_BYTES (CT_PARKS + 2 * (H + 4) + 2 * (H / 2) * 4)   /* + nf + shift, haz */
+DEV void chroma_tail_once_par(Ctx *c, int comp, int tid, int16_t *lds)
+{
+	const int16_t *p = c->cproc, *o = c->cll1, *l2 = c->cl2save;
+	const int q = c->q, lane = tid & 63, wv = tid >> 6;
+	const bool marks = q >= 18;
+	const int res_uv = q > 17 ? 4 : 5;
+	int16_t *nf = lds + CT_PARKS / 2;                              /* the emission's band and scratch lie in the parked rows' space, in front of these */
+	int *shift = reinterpret_cast<int *>(nf + H + 4);
+	static_assert(CT_PARKS % 4 == 0 && CT_PARKS >= (H / 4) * (H / 4) * 2 + 4096, "tables behind the emission's LDS");
+	PROF_BEGIN();
+	if (marks) chroma_marks_par(c, comp, tid, shift, false);
+	BARRIER();
+	if (tid < H / 2) {                                             /* nf[1 .. 127]; nf[128 + R] */
+		if (tid) nf[tid] = tid < H / 4 ? (int16_t)0 : l2[tid * (H / 2)];
+		const int R = tid, at = R * H;
+		int lh = p[at + Q / 2];
+		if (marks) {
+			const int ko = R * (H / 2) + shift[R];
+			const int d = p[at] - o[ko], d1 = p[at + 1] - o[ko + 1], hl = p[at + H / 2], hh = p[at + Q / 2 + H / 2];
+			const bool pair_pos = uv_pair_pos(d, d1), pair = (pair_pos || uv_pair_neg(d, d1)) && uv_slot(hl, lh, hh) >= 0;
+			if ((pair || uv_single(d, d1, res_uv)) && uv_slot(hl, lh, hh) == 1) lh = uv_code(pair, pair_pos, d);
+		}
+		nf[H / 2 + R] = (int16_t)lh;
+	}
+	if (tid == NT - 1) nf[H] = p[Q];
+	if (!tid) PROF(c, 27);
+	chroma_ll2_emit_par(c, comp, tid, lds, nullptr);
+	BARRIER();
+	uint8_t *park_t = reinterpret_cast<uint8_t *>(lds) + wv * 2 * 16 * CQROW, *park_b = park_t + 16 * CQROW;
+	unsigned vtotal = 0;                                            /* V: values this wavefront has appended to the list (wave-uniform) */
+	const int R0 = (H / 8) * wv;
+	int16_t nx[14] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+	auto fetch = [&](int R) {
+		const int sh = marks ? shift[R] : 0;
+#pragma unroll
+		for (int k = 0; k < 2; k++) {
+			const int at = R * H + lane + 64 * k, ko = R * (H / 2) + sh + lane + 64 * k;
+			nx[7 * k + 1] = p[at + H / 2]; nx[7 * k + 2] = p[at + Q / 2]; nx[7 * k + 3] = p[at + Q / 2 + H / 2];
+			if (marks) { nx[7 * k] = p[at]; nx[7 * k + 4] = o[ko]; nx[7 * k + 5] = o[ko + 1]; }   /* below q18 the walk needs neither the reconstruction nor cll1 */
+			nx[7 * k + 6] = l2[R * (H / 2) + lane + 64 * k];
+		}
+	};
+	fetch(R0);
+	for (int i = 0; i < H / 8; i++) {
+		const int R = R0 + i;
+		UvRow x;
+		int ll[2];
+#pragma unroll
+		for (int k = 0; k < 2; k++) {
+			x.pl[k] = nx[7 * k]; x.hl[k] = nx[7 * k + 1]; x.lh[k] = nx[7 * k + 2]; x.hh[k] = nx[7 * k + 3];
+			x.o0[k] = nx[7 * k + 4]; x.o1[k] = nx[7 * k + 5]; ll[k] = nx[7 * k + 6];
+		}
+		if (i + 1 < H / 8) fetch(R + 1);
+		if (marks) {
+			int code[2];
+			uv_row_marks(x, res_uv, lane, true, code);
+#pragma unroll
+			for (int k = 0; k < 2; k++) {
+				const int slot = code[k] ? uv_slot(x.hl[k], x.lh[k], x.hh[k]) : -1;
+				x.hl[k] = slot == 0 ? code[k] : x.hl[k]; x.lh[k] = slot == 1 ? code[k] : x.lh[k]; x.hh[k] = slot == 2 ? code[k] : x.hh[k];
+			}
+		}
+		const int top[4] = { R < H / 4 ? 0 : ll[0], ll[1], x.hl[0], x.hl[1] }, bot[4] = { x.lh[0], x.lh[1], x.hh[0], x.hh[1] };
+		int sym[4];
+		cq_symbols(top, nf[R + 1], lane, sym);
+		for (int k = 0; k < 4; k++) park_t[(i & 15) * CQROW + lane + 64 * k] = (uint8_t)sym[k];
+		cq_symbols(bot, nf[H / 2 + R + 1], lane, sym);
+		for (int k = 0; k < 4; k++) park_b[(i & 15) * CQROW + lane + 64 * k] = (uint8_t)sym[k];
+		if ((i & 15) == 15) {                                      /* sixteen rows of each complete */
+			__threadfence_block();
+			cq_flush(c, comp, park_t, R - 15, wv, vtotal, false, lane);
+			cq_flush(c, comp, park_b, H / 2 + R - 15, wv, vtotal, false, lane);
+			__threadfence_block();
+		}
+	}
 	if (!tid) PROF(c, 22);
 }
 

@@ -1,11 +1,11 @@
 """Regenerates the kernel table of DESIGN.md (between the KERNEL_TABLE markers) from the committed profile summaries, so that the numbers
 cannot drift from the files they cite.   usage: python profiles/make_design_table.py [--check]
-inputs: profiles/l2_dead_stores_kernel_stats_1stream_after.txt (rocprofv3 --kernel-trace --stats, one stream), profiles/l2_dead_stores_pmc_after.json (FETCH_SIZE and
+inputs: profiles/chroma_tail_kernel_stats_1stream_after.txt (rocprofv3 --kernel-trace --stats, one stream), profiles/chroma_tail_pmc_after.json (FETCH_SIZE and
 WRITE_SIZE per kernel from separate --pmc passes; KiB; FETCH_SIZE doubled for gfx950 as MI355X_MICROARCH.md prescribes)."""
 import json, os, re, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STATS = os.path.join(ROOT, "profiles", "l2_dead_stores_kernel_stats_1stream_after.txt")
-PMC = os.path.join(ROOT, "profiles", "l2_dead_stores_pmc_after.json")
+STATS = os.path.join(ROOT, "profiles", "chroma_tail_kernel_stats_1stream_after.txt")
+PMC = os.path.join(ROOT, "profiles", "chroma_tail_pmc_after.json")
 BATCHES = 7.0            # bench.py --steps 5 --warmup 2 in profiles/collect.sh
 PH = ["L1", "L2", "L3", "L4A", "C0", "C2", "C3", "C4", "C5", "FINAL", "L4B", "L4C", "L4D", "LLC", "L4C2"]
 WV = ["DQ1", "DQ0", "EMIT", "QUANT"]
@@ -26,6 +26,7 @@ WHAT = {
     "C0": "chroma: copy", "C2": "chroma: dequantiser simulation 1", "C3": "chroma: tags", "C4": "chroma: dequantiser simulation 2",
     "C5": "chroma: marks (running-index fixed point), LL2 emission, quantiser (wavefront per row); V leaves the merged chroma stream as a list", "LLC": "Z1 chroma LL2 coder", "FINAL": "Z2 packetiser + container",
     "k_l4a": "Y19-Y23 of q >= 17: Y21 small runs (wavefront per row, rows in which nothing fires skipped), Y22 + Y23 as ONE column sweep on registers and class tables (eight workgroups a CU)",
+    "k_chroma_tail": "chroma tail of a batch: the rows' shifts (running-index fixed point), LL2 emission, then ONE walk: a wavefront reads each plane row once, marks it in registers and quantises it (rows without a candidate and all-quiet rows skipped); cproc is not written; V leaves the merged chroma stream as a list",
     "k_y31": "Y31 rewrites on the symbol LIST (non-zero map + values), 512 threads an image; leaves map and offsets in stream order",
     "k_final": "Z2 packetiser (the luma part from its symbol list, both books) + container; a kernel of its own at six wavefronts a SIMD",
     "k_pack_chroma": "Z2's chroma part: words and ranked book entries from the chroma symbol list (on the chroma stream in the forked order)",
