@@ -36,7 +36,6 @@ struct nhw_enc {
 	hipStream_t low_stream[4];    /* quality 1..16: the pre-filter's sub-batches (nhw_launch_low_prefilter) */
 	hipEvent_t low_ev[LOW_EV_COUNT];
 	int low_parts;                /* how many (NHW_LOW_PARTS; 1 = the whole batch in line) */
-	int low_parts_used;           /* ... in the batch that is being queued */
 	int low_chroma;               /* quality 1..16: where the chroma sequence starts (NHW_LOW_CHROMA: 0 behind the front group, 1 behind the colour kernel, 2 behind the last sub-batch's pass A) */
 	hipStream_t ll_stream;        /* the LL2 coder (Y16) beside the second dequantiser simulation; before that, Y5 beside the first */
 	hipEvent_t ll_ev[LL_EV_COUNT];

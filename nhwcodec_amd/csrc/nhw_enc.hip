@@ -6,6 +6,7 @@
  * batch-wide kernel launches: every launch processes the same stage of all n images.
  */
 #include "nhw_enc.h"
+#include "nhw_enc_plan.h"
 
 thread_local std::string nhw_enc_err;
 extern "C" const char *nhw_last_error(void) { return nhw_enc_err.c_str(); }
@@ -145,275 +146,147 @@ int host_buffers(nhw_enc *e, int n)
 	return rc;
 }
 
-/* a chroma component's launches up to the second dequantiser simulation, on stream cs (run_batch; nhw_stage_chroma_loops).  1 = carry on;
- * NHW_OK: the debug stop fell in here */
-#define STAGE_DONE() do { if (e->stop_after && ++stage == e->stop_after) { HIPCHK(hipGetLastError()); return NHW_OK; } } while (0)
-static int chroma_head_launches(nhw_enc *e, const NhwWs &ws, int comp, int n, hipStream_t cs, int &stage)
+/* The executor of a plan's steps (nhw_enc_plan.h): every kernel step is one call of its launcher with the planes of the view ws, every event step
+ * one call of the runtime.  The planner decides what is launched, in which order and on which stream; nothing here does. */
+struct EncIo { const void *d_bgr; void *d_out; uint32_t *d_sizes; int32_t *d_status; };   /* the caller's arrays (a stage hook: none, its plans have no step that takes them) */
+static_assert(EE_START == EV_START && EE_FRONT == EV_FRONT && EE_LUMA == EV_LUMA && EE_CHROMA == EV_CHROMA && EE_END == EV_END && EE_COLOR == EV_COLOR && EE_PREFILTER == EV_PREFILTER,
+              "the plan's stamps are the handle's timing events");
+static hipEvent_t enc_event(nhw_enc *e, int ev, int low_parts_used)
 {
-	const int q = ws.q;
-	const bool low = q <= 16;
-	const bool vp = comp && ws.split_chroma;
-	const Plane<int16_t> cjpeg = ws.plane<int16_t>(vp ? B_CJPEG_V : B_CJPEG), cproc = ws.plane<int16_t>(vp ? B_CPROC_V : B_CPROC);
-	const Plane<int16_t> cll1 = ws.plane<int16_t>(vp ? B_CLL1_V : B_CLL1), cl2save = ws.plane<int16_t>(vp ? B_CL2SAVE_V : B_CL2SAVE);
-	const Plane<const uint8_t> bytes = ws.plane<const uint8_t>(comp ? B_PV : B_PU);
-	const bool widen_in_analysis = q > 14 && !ws.dbg;              /* the analysis reads the byte plane itself (the stage checks keep the copy as a stage of its own) */
-	if (q <= 14) nhw_launch_low_prefilter_chroma(bytes, cjpeg, q, n, cs);   /* :2263 / :2579 */
-	else if (!widen_in_analysis) nhw_launch_phase(PH_C0, ws, comp, cs);
-	STAGE_DONE();
-	NhwAnalysis l1 = NhwAnalysis{ cjpeg, cproc, n, H, H, 0 }.saving(cll1, H / 2, ANA_SAVE_LL);   /* + the copy of LL1 */
-	l1.store = ws.dbg ? ANA_STORE_ALL : ANA_STORE_NO_T_LL_SAVED;   /* production: nor the LL quadrant back into the work plane -- the level-2 analysis reads its copy */
-	if (widen_in_analysis) l1.src8 = bytes;
-	nhw_launch_analysis(l1, cs);
-	if (low) nhw_launch_low_chroma_thin(cproc, n, cs);           /* :2277-2308 / :2590-2621 */
-	STAGE_DONE();
-	STAGE_DONE();
-	if (!ws.dbg) {   /* both closed loops on one residency of the level-2 block, from the copy of LL1 (k_chroma_loops); the stage checks take the seven kernels */
-		nhw_launch_chroma_loops(cproc, cll1, cl2save, ws.plane<const uint8_t>(B_PU), q, comp, ws.compat, n, cs);
-		return 1;
+	switch (ev) {
+	case EE_LUMA_LIST: return e->part_ev[PE_LUMA_LIST];
+	case EE_CHROMA_DONE: return e->part_ev[PE_CHROMA];
+	case EE_LISTS_FORK: return e->part_ev[PE_LISTS_FORK];
+	case EE_LISTS: return e->part_ev[PE_LISTS];
+	case EE_PART_FRONT: return e->part_ev[PE_FRONT];
+	case EE_LL_FORK: return e->ll_ev[LL_EV_FORK];
+	case EE_LL_DONE: return e->ll_ev[LL_EV_DONE];
+	case EE_Y5_FORK: return e->ll_ev[LL_EV_Y5_FORK];
+	case EE_Y5_DONE: return e->ll_ev[LL_EV_Y5_DONE];
+	case EE_PACK_FORK: return e->ll_ev[LL_EV_PACK_FORK];
+	case EE_PACK_DONE: return e->ll_ev[LL_EV_PACK_DONE];
+	case EE_LOW_PASS_A: return e->low_ev[low_ev_pass_a(low_parts_used - 1)];
+	default: assert(ev < EV_COUNT); return e->ev[ev];
 	}
-	const NhwAnalysis l2{ cjpeg, cproc, n, H, H / 2, 1 };
-	nhw_launch_analysis(l2, cs);
-	STAGE_DONE();
-	nhw_launch_phase(PH_C2, ws, comp, cs);
-	STAGE_DONE();
-	nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, cs);
-	STAGE_DONE();
-	nhw_launch_phase(PH_C3, ws, comp, cs);
-	STAGE_DONE();
-	nhw_launch_analysis(l2.saving(cl2save, H / 2, ANA_SAVE_BLOCK), cs);   /* + the copy of the level-2 block */
-	STAGE_DONE();
-	STAGE_DONE();
-	nhw_launch_phase(PH_C4, ws, comp, cs);
-	STAGE_DONE();
-	nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, cs);
-	STAGE_DONE();
-	return 1;
 }
-
-/* the luma plane's launches from the first level-2 analysis to the second, on stream s (run_batch; nhw_stage_luma_loop).  1 = carry on;
- * NHW_OK: the debug stop fell in here */
-static int luma_loop_launches(nhw_enc *e, const NhwWs &ws, int n, hipStream_t s, int &stage, bool y5_beside = false /* run_batch's forked order */,
-                              bool lean = false /* run_batch without a debug stop, outside the compatibility mode: the stores of the level-2 block that nothing reads are left out (below; k_l2_recon) */)
+static int run_steps(nhw_enc *e, const NhwWs &ws, const EncPlan &plan, const EncIo &io, hipStream_t s)
 {
-	const int q = ws.q;
+	const int q = ws.q, n = ws.n;
+	hipStream_t const stream[ES_COUNT] = { s, e->part_stream[0], e->part_stream[1], e->ll_stream };
 	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC), ll1 = ws.plane<int16_t>(B_LL1), l2save = ws.plane<int16_t>(B_L2SAVE);
-	const NhwAnalysis l2{ jpeg, proc, n, W, H, 1 };
-	assert(!lean || (!ws.dbg && !ws.compat));
-	/* Y4: level-2 analysis (:139).  The LL rows come from ll1 (the front's copy of them in natural orientation, res256): outside the stage checks the front
-	 * does not write them into the work plane as well, and this analysis fills that quadrant of the work plane itself (its transposed first-direction plane).
-	 * lean, q > 6: the transposed first-direction plane is not stored.  The first dequantiser simulation, the next kernel that touches the block of
-	 * jpeg, writes every cell of it (wave_ll2 the LL2 quadrant, wave_dequant_details the rest: the case list there) in front of its one reader,
-	 * k_l2_recon; Y5 reads proc and ll1.  (Below q7 there is no simulation and the plane stays.) */
-	NhwAnalysis first = l2.from(ll1, H);
-	if (lean && q > 6) first.store = ANA_STORE_NO_T;
-	nhw_launch_analysis(first, s);
-	STAGE_DONE();
-	if (q > 6) {                                                     /* first closed loop (:141-283) */
-	/* Y5 and the first dequantiser simulation need nothing of each other, and the first kernel that needs both is k_l2_recon (Y8 reads Y5's
-	 * tags, the synthesis the simulation's plane).  Y5 (luma_p1_par, tag_l2_details_par) reads proc and read-modify-writes ll1 (compatibility
-	 * mode: and clears the 512 cells behind ll1); it never touches jpeg.  The simulation (wave_dequant_sim_luma, part 1) reads proc and
-	 * writes jpeg; it never touches ll1, and it writes proc only with keep_p, which is ws.dbg: the stage checks, which do not come here
-	 * (the forked order has no debug stop).  So in the forked order Y5 runs on the LL coder's stream, idle until Y16, beside the simulation. */
-	if (y5_beside) {
-		assert(!ws.dbg);
-		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_Y5_FORK], s));
-		HIPCHK(hipStreamWaitEvent(e->ll_stream, e->ll_ev[LL_EV_Y5_FORK], 0));
-		nhw_launch_phase(PH_L1, ws, 0, e->ll_stream);
-		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_Y5_DONE], e->ll_stream));
-	} else
-	nhw_launch_phase(PH_L1, ws, 0, s);
-	nhw_launch_wave(WV_DQ1, ws, s);          /* every quality (1..16: rationed low bits, no marking passes) */
-	if (y5_beside) HIPCHK(hipStreamWaitEvent(s, e->ll_ev[LL_EV_Y5_DONE], 0));   /* (Y16's later fork onto that stream is behind Y5 by stream order) */
-	STAGE_DONE();
-	if (ws.dbg) {
-	nhw_launch_synthesis(jpeg, proc, n, W, H, 0, s);
-	STAGE_DONE();
-	nhw_launch_phase(PH_L2, ws, 0, s);
-	STAGE_DONE();
-	} else nhw_launch_l2_recon(jpeg, proc, ll1, q > 12 ? l2save : Plane<int16_t>{}, n, s, lean && q > 12);   /* synthesis + Y8 + Y9 on one residency of the block (the stage checks take the three kernels); q > 12: + the second analysis and Y13 (:623-631), still on that residency */
-	if (q <= 12) nhw_launch_analysis(l2, s);                         /* (Y11 / Y12 follow, and Y13's copy behind them) */
-	else if (ws.dbg) nhw_launch_analysis(l2.saving(l2save, H, ANA_SAVE_BLOCK), s);   /* + Y13: copy of the coefficient block */
-	STAGE_DONE();
-	}
-	return 1;
-}
-
-/* the whole launch sequence for the images of one workspace view on one stream; `timed`: record the stage events of nhw_timing */
-static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, hipStream_t s,
-                     int timed /* 0: no events, 1: EV_START .. EV_END (whole batch), 2: EV_LUMA, EV_CHROMA (tail of the first sub-batch; the caller closes with EV_END) */,
-                     int what = 3 /* bit 0: the front launch group (colour, pre-filter, level-1 analysis), bit 1: everything behind it */)
-{
-	NhwWs ws = ws_in;
-	const int q = quality;
-	const bool low = q <= 16;      /* integer colour, the rationed pre-filter of image_processing.c:838-2423 and the other quality 1..16 forms (nhw_low.hip) */
-	const Plane<int16_t> jpeg = ws.plane<int16_t>(B_JPEG), proc = ws.plane<int16_t>(B_PROC);
-	const Plane<uint8_t> pu = ws.plane<uint8_t>(B_PU), pv = ws.plane<uint8_t>(B_PV);
-
-	e->low_parts_used = 1;         /* until the pre-filter below runs in sub-batches: the chroma fork never waits on an event of an earlier batch */
-	int stage = 0;
-	if (what & 1) {
-	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_START], s));
-	/* a1 + a2 + Y2 + Y3: colour + 4:2:0, pre-filter (q<=21, nhw_encoder.c:116-119), level-1 analysis (:125), LL1 copy (:127-135): ONE kernel
-	 * for quality 17..23 (k_front_image with the pre-filter, k_front_plain without: a workgroup walks an image top to bottom).  The luma plane
-	 * never reaches HBM.  Quality 1..16: colour kernel -> luma plane, the rationed pre-filter (nhw_low.hip) -> k_front_plain's input plane. */
 	const Plane<int16_t> yin = ws.plane<int16_t>(B_KMAP);
-	NhwFront f;
-	f.q = q; f.n = n; f.y = yin /* quality 17..23, developer builds only: a plane for a dump */; f.st = ws.plane<uint8_t>(B_ROWSTATE);
-	f.proc = proc; f.jpeg = jpeg; f.ll1 = ws.plane<int16_t>(B_LL1); f.switches = ws.dbg ? 2 : 0;
-	if (low) {
-		nhw_launch_color((const uint8_t *)d_bgr, n, q, jpeg, pu, pv, s);
-		HIPCHK(hipEventRecord(e->ev[EV_COLOR], s));                      /* with the front group, whoever brackets it: nhw_timing.color_dwt_ms / prefilter_ms */
-		STAGE_DONE();
-		{ const int lparts = (timed == 1 && what == 3 && !e->stop_after && n >= 1024) ? e->low_parts : 1;   /* (the stage checks and small batches: in line) */
-		  e->low_parts_used = lparts;
-		  HIPCHK((hipError_t)nhw_launch_low_prefilter(jpeg, yin, proc, ws.plane<uint8_t>(B_SCAN), ws.plane<uint8_t>(B_KEEP), ws.plane<uint8_t>(B_LOWTAB), q, n, s, (e->front_fallback & 1) ? 32 : 0,
-		                                              lparts, e->low_stream, e->low_ev)); }   /* contrast map -> proc plane, flags -> scan buffer: both free until the band kernel / the quantiser; the pair machine's answers -> the q >= 22 plane */
-		HIPCHK(hipEventRecord(e->ev[EV_PREFILTER], s));
-		STAGE_DONE();
-		if (ws.compat) nhw_launch_low_stale(proc, ws.plane<uint8_t>(B_STALE), n, s);   /* compatibility mode only: the map cells the stock binary's heap re-uses */
-	} else {
-		HIPCHK(hipEventRecord(e->ev[EV_COLOR], s)); HIPCHK(hipEventRecord(e->ev[EV_PREFILTER], s));   /* no kernels of their own for colour and pre-filter: both times 0 */
-		STAGE_DONE();
-		if (q < 22) STAGE_DONE();
-		f.bgr = (const uint8_t *)d_bgr; f.pu = pu; f.pv = pv; f.with_prefilter = q < 22; f.switches |= e->front_fallback & 1;
-		if (q > 21) f.keep = ws.plane<int16_t>(B_KEEP);
-	}
-	nhw_launch_front_fused(f, s);
-	if (!low && ws.compat && q < 22) {   /* compatibility mode only: the kernel-map cells the stock binary's heap re-uses are replayed from a luma plane */
-		nhw_launch_color((const uint8_t *)d_bgr, n, q, yin, pu, pv, s);
-		nhw_launch_front_stale(yin, f.st, ws.plane<uint8_t>(B_STALE), n, s);
-	}
-	STAGE_DONE();
-	STAGE_DONE();
-	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_FRONT], s));
-	if (!(what & 2)) { HIPCHK(hipGetLastError()); return NHW_OK; }
-	}
-	/* The chroma sequence needs nothing of the luma tail except the length of the exception list (its own entries go behind the
-	 * luma ones, Y15): it runs on a stream of its own next to the luma tail and fills the issue slots the latency-bound luma kernels
-	 * leave.  (Since round 5 V works in planes of its own and U's symbols are parked in B_UBYTES until V's quantiser merges them: the
-	 * sequence no longer waits for the band plane Y29 is done with, nor V's head for U's quantiser.) */
-	const bool fork = timed == 1 && what == 3 && !e->stop_after && e->chroma_fork;
-	const bool fork_ll = fork && q > 13 && !ws.compat && e->ll_fork;
-	ws.defer_verbatim = fork_ll;
-	hipStream_t cs = fork ? e->part_stream[0] : s;
-	ws.split_chroma = fork;                                          /* (the stage checks and the in-line order keep the reference's one set of planes) */
-	const bool tail_once = e->chroma_tail_once && !e->stop_after && !ws.dbg;   /* every order of this function (forked, in line, a sub-batch's view; the fit paths come through here): nothing in a batch reads cproc behind the chroma tail.  Off under a debug stop, whose stage checks read the planes */
-	auto chroma_head = [&](int comp) -> int { return chroma_head_launches(e, ws, comp, n, cs, stage); };   /* everything up to the second dequantiser simulation */
-	auto chroma_tail = [&](int comp) -> int {                        /* marks, LL2 emission (appends to the exception list), quantiser, stream bytes */
-		nhw_launch_chroma_tail(ws, comp, tail_once, cs);
-		STAGE_DONE();
-		return 1;
-	};
-#define CHROMA(call) do { const int rc_ = (call); if (rc_ != 1) return rc_; } while (0)   /* 1 = carry on; NHW_OK (debug stop) or an error leaves */
-	if (fork) {
-		HIPCHK(hipStreamWaitEvent(cs, !low || e->low_chroma == 0 ? e->ev[EV_FRONT] : (e->low_chroma == 2 && e->low_parts_used > 1) ? e->low_ev[low_ev_pass_a(e->low_parts_used - 1)] : e->ev[EV_COLOR], 0));   /* behind the front launch group: that one is bound by vector issue and has nothing to give (and its time is the roofline figure).  Quality 1..16: behind the colour kernel already -- the rationed pre-filter's chain (k_low_chain) is one wavefront a picture on the scalar unit and leaves the vector units and the memory system idle for milliseconds */
-		CHROMA(chroma_head(0));
-		CHROMA(chroma_head(1));                                      /* V's head in planes of its own, right behind U's: U's quantiser waits for the luma tail, and this stream stood idle until then (2 ms of a q20 step).  (Measured and not taken: V's head on a stream of its own beside U's, +0.3 ms; V's head held back until the second dequantiser simulation is through, +0.4 ms.) */
-	}
-	{ const int rc_ = luma_loop_launches(e, ws, n, s, stage, fork && e->y5_fork, !ws.dbg && !ws.compat); if (rc_ != 1) return rc_; }   /* Y4 .. Y10 (+ Y13's copy for q > 12), every order of this function: forked, in line, a sub-batch's view */
-	if (q <= 12) {                                                   /* Y11 (q <= 11), Y12, then Y13 */
-		nhw_launch_low_ll2(proc, q, n, s);
-		nhw_launch_copy_block(proc, W, ws.plane<int16_t>(B_L2SAVE), H, H, H, n, s);
-	}
-	STAGE_DONE();
-	const bool one_walk = fork && q > 12 && e->ll2_once;             /* the LL2 bump walk once, in the emission: the second simulation finds its cells made (wave_emit_ll2) */
-	/* The second simulation's two marking blocks are the quantiser's loops 2 and 3 on the same cells (wave_dequant_details): it leaves their outcome
-	 * in B_KMAP and the quantiser takes the level-2 details from there.  On wherever the simulation of this very call runs in front of the quantiser
-	 * on these planes -- every order of this function above quality 16 (forked, in line, a sub-batch's view: both kernels are launched below on s, and
-	 * the fit paths come through here) -- and off under a debug stop, whose stage checks read the quantiser's own work plane. */
-	const bool marks = q > 16 && !e->stop_after && !ws.dbg && e->quant_marks;
-	nhw_launch_wave(WV_EMIT, ws, s, one_walk);                       /* Y14, Y15 */
-	/* Y16, the LL2 coder, is a latency-bound parse (0.6 ms at 0.3 TB/s) in front of the vector-bound dequantiser simulation, which only wants its
-	 * list of verbatim samples -- at its very end, to put them back into the block.  Production: the coder runs beside the simulation on a
-	 * stream of its own and the synthesis behind both does the putting back (ws.defer_verbatim).  Not in the compatibility mode and not
-	 * below q14, where the coder's launch also lays out heap neighbours that the passes behind it read (luma_p3_par). */
-	if (fork_ll) {
-		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_FORK], s));
-		HIPCHK(hipStreamWaitEvent(e->ll_stream, e->ll_ev[LL_EV_FORK], 0));
-		nhw_launch_phase(PH_L3, ws, 0, e->ll_stream);
-		HIPCHK(hipEventRecord(e->ll_ev[LL_EV_DONE], e->ll_stream));
-		HIPCHK(hipEventRecord(e->part_ev[PE_LUMA_LIST], e->ll_stream));   /* exception list of the luma plane complete, and the coder through with the bytes behind the luma samples: the chroma emission writes its own there */
-	} else {
-	nhw_launch_phase(PH_L3, ws, 0, s);
-	if (fork) HIPCHK(hipEventRecord(e->part_ev[PE_LUMA_LIST], s));              /* exception list of the luma plane complete */
-	}
-	if (q > 12) {                                                    /* second closed loop (:759-779) */
-	nhw_launch_wave(WV_DQ0, ws, s, one_walk, marks);
-	STAGE_DONE();
-	if (fork_ll) {
-		HIPCHK(hipStreamWaitEvent(s, e->ll_ev[LL_EV_DONE], 0));               /* (the coder is long done: the simulation takes twice its time) */
-		const Plane<const uint8_t> meta = ws.plane<const uint8_t>(B_META), len{ meta.p + offsetof(NhwMeta, ll_mem_len), meta.pitch };
-		nhw_launch_synthesis(jpeg, proc, n, W, H, q <= 21 && !ws.dbg, ws.plane<const uint8_t>(B_LLMEM), len, s);
-	} else
-	nhw_launch_synthesis(jpeg, proc, n, W, H, q <= 21 && !ws.dbg, s);   /* its copy in natural orientation is only read by Y19 (q > 21, :766-777) */
-	STAGE_DONE();
-	}
-	nhw_launch_phase(PH_L4A, ws, 0, s);      /* Y19-Y23 */
-	/* Y24, Y25: the position lists are read by nothing before the packetiser, and what the pass leaves in the residual-code plane by nobody
-	 * at all; below q21 it shares no scratch with the passes behind it either (from q21 on its third list and Y27's snapshot both live in
-	 * the hs plane, and Y29 needs Y24), so there it runs beside them on a stream of its own */
-	const bool fork_lists = fork && q <= 20 && q > 12 && e->lists_fork;
-	if (fork_lists) {
-		HIPCHK(hipEventRecord(e->part_ev[PE_LISTS_FORK], s));
-		HIPCHK(hipStreamWaitEvent(e->part_stream[1], e->part_ev[PE_LISTS_FORK], 0));
-		nhw_launch_phase(PH_L4B, ws, 0, e->part_stream[1]);
-		HIPCHK(hipEventRecord(e->part_ev[PE_LISTS], e->part_stream[1]));
-	} else if (q > 12)
-		nhw_launch_phase(PH_L4B, ws, 0, s);  /* Y24, Y25 (:1498) */
-	nhw_launch_phase(PH_L4C, ws, 0, s);      /* Y26, Y27 */
-	const bool early_join = fork && e->quant_join;
-	const int pack_fork = fork ? e->pack_fork : 0;                   /* every other order: directly in front of k_final (nhw_launch_final) */
-	auto chroma_rest = [&]() -> int {
-		HIPCHK(hipStreamWaitEvent(cs, e->part_ev[PE_LUMA_LIST], 0));
-		CHROMA(chroma_tail(0));
-		CHROMA(chroma_tail(1));
-		/* Z2's chroma part needs V's quantiser and nothing else, and writes only memory of its own (k_pack_chroma): it runs here, while the luma
-		 * stream ends its residual passes, instead of inside the packetiser at the very end, where nothing can run beside it.  Beside Z1 on
-		 * the LL coder's stream, idle since Y16 (NHW_PACK_FORK=2, the default: the join moves back by 0.24 ms, k_final loses 0.35), or behind
-		 * Z1 on this stream (NHW_PACK_FORK=1: the join moves back by the kernel's whole 0.32 ms, as much as k_final loses); either way it is
-		 * through before the join.  NHW_PACK_FORK=0: in front of k_final, as in every other order. */
-		if (pack_fork == 2) {
-			HIPCHK(hipEventRecord(e->ll_ev[LL_EV_PACK_FORK], cs));
-			HIPCHK(hipStreamWaitEvent(e->ll_stream, e->ll_ev[LL_EV_PACK_FORK], 0));
-			nhw_launch_pack_chroma(ws, e->ll_stream);
-			HIPCHK(hipEventRecord(e->ll_ev[LL_EV_PACK_DONE], e->ll_stream));
+	const Plane<uint8_t> pu = ws.plane<uint8_t>(B_PU), pv = ws.plane<uint8_t>(B_PV);
+	const NhwAnalysis l2{ jpeg, proc, n, W, H, 1 };
+	assert(ws.dbg == plan.dbg && ws.split_chroma == plan.split_chroma && ws.defer_verbatim == plan.defer_verbatim);
+	for (int i = 0; i < plan.n; i++) {
+		const EncStep &st = plan.step[i];
+		hipStream_t const on = stream[st.stream];
+		/* a chroma step's component and planes */
+		const int comp = st.a != 0;
+		const bool vp = st.a == 2;
+		const Plane<int16_t> cjpeg = ws.plane<int16_t>(vp ? B_CJPEG_V : B_CJPEG), cproc = ws.plane<int16_t>(vp ? B_CPROC_V : B_CPROC);
+		const Plane<int16_t> cll1 = ws.plane<int16_t>(vp ? B_CLL1_V : B_CLL1), cl2save = ws.plane<int16_t>(vp ? B_CL2SAVE_V : B_CL2SAVE);
+		const Plane<const uint8_t> bytes = ws.plane<const uint8_t>(comp ? B_PV : B_PU);
+		const NhwAnalysis cl2{ cjpeg, cproc, n, H, H / 2, 1 };
+		switch (st.op) {
+		case ENC_STAMP: HIPCHK(hipEventRecord(e->ev[st.a], on)); break;
+		case ENC_RECORD: HIPCHK(hipEventRecord(enc_event(e, st.a, plan.low_parts_used), on)); break;
+		case ENC_WAIT: HIPCHK(hipStreamWaitEvent(on, enc_event(e, st.a, plan.low_parts_used), 0)); break;
+		case ENC_STAGE: break;
+		case ENC_COLOR: nhw_launch_color((const uint8_t *)io.d_bgr, n, q, st.a ? yin : jpeg, pu, pv, on); break;
+		case ENC_LOW_PREFILTER:
+			HIPCHK((hipError_t)nhw_launch_low_prefilter(jpeg, yin, proc, ws.plane<uint8_t>(B_SCAN), ws.plane<uint8_t>(B_KEEP), ws.plane<uint8_t>(B_LOWTAB), q, n, on, st.b ? 32 : 0,
+			                                            st.a, e->low_stream, e->low_ev));
+			break;
+		case ENC_LOW_STALE: nhw_launch_low_stale(proc, ws.plane<uint8_t>(B_STALE), n, on); break;
+		case ENC_FRONT: {
+			NhwFront f;
+			f.q = q; f.n = n; f.y = yin /* quality 17..23, developer builds only: a plane for a dump */; f.st = ws.plane<uint8_t>(B_ROWSTATE);
+			f.proc = proc; f.jpeg = jpeg; f.ll1 = ll1; f.switches = (ws.dbg ? 2 : 0) | st.a;
+			if (q > 16) { f.bgr = (const uint8_t *)io.d_bgr; f.pu = pu; f.pv = pv; f.with_prefilter = q < 22; }
+			if (q > 21) f.keep = ws.plane<int16_t>(B_KEEP);
+			nhw_launch_front_fused(f, on);
+			break;
 		}
-		nhw_launch_phase(PH_LLC, ws, 0, cs);   /* Z1: the chroma LL2 coder appends to the luma one's output (Y16, long done) */
-		if (pack_fork == 1) nhw_launch_pack_chroma(ws, cs);
-		if (pack_fork == 2) HIPCHK(hipStreamWaitEvent(cs, e->ll_ev[LL_EV_PACK_DONE], 0));
-		HIPCHK(hipEventRecord(e->part_ev[PE_CHROMA], cs));
-		return 1;
-	};
-	/* The quantiser is a wavefront an image at 119 registers: four wavefronts fill a SIMD's register file, and it is as fast as its slowest
-	 * wavefront is late.  A side stream's workgroup that sits on a CU when it starts keeps four of its images waiting for a second round (the
-	 * kernel took 3.0 ms beside the chroma sequence, 1.9 alone).  So the side streams are let finish first (they have had the
-	 * multi-round kernels Y19-Y27 to hide behind), and Y31 and the packetiser then run alone as well. */
-	if (early_join) {
-		CHROMA(chroma_rest());
-		if (fork_lists) HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_LISTS], 0));
-		HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_CHROMA], 0));
-	}
-	nhw_launch_wave(WV_QUANT, ws, s, false, marks);                  /* Y28 (+ Y30: the symbols leave in stream order), every quality */
-	if (q > 21) nhw_launch_phase(PH_L4C2, ws, 0, s);   /* Y29 */
-	if (fork && !early_join) CHROMA(chroma_rest());                  /* queued here so that the wait finds its event recorded */
-	nhw_launch_phase(PH_L4D, ws, 0, s);      /* Y31 (Y30, the stream order, is the quantisers' output order) */
-	STAGE_DONE();
-	if (timed) HIPCHK(hipEventRecord(e->ev[EV_LUMA], s));
-
-	if (fork_lists && !early_join) HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_LISTS], 0));
-	if (fork) { if (!early_join) HIPCHK(hipStreamWaitEvent(s, e->part_ev[PE_CHROMA], 0)); }
-	else
-		for (int comp = 0; comp < 2; comp++) {       /* U then V (:2255-2570, :2572-2868) */
-			CHROMA(chroma_head(comp));
-			CHROMA(chroma_tail(comp));
+		case ENC_FRONT_STALE: nhw_launch_front_stale(yin, ws.plane<const uint8_t>(B_ROWSTATE), ws.plane<uint8_t>(B_STALE), n, on); break;
+		case ENC_C_PREFILTER: nhw_launch_low_prefilter_chroma(bytes, cjpeg, q, n, on); break;
+		case ENC_C_WIDEN: nhw_launch_phase(PH_C0, ws, comp, on); break;
+		case ENC_C_ANALYSIS1: {
+			NhwAnalysis l1 = NhwAnalysis{ cjpeg, cproc, n, H, H, 0 }.saving(cll1, H / 2, ANA_SAVE_LL);
+			l1.store = ws.dbg ? ANA_STORE_ALL : ANA_STORE_NO_T_LL_SAVED;
+			if (st.b) l1.src8 = bytes;
+			nhw_launch_analysis(l1, on);
+			break;
 		}
-#undef CHROMA
-	if (timed) HIPCHK(hipEventRecord(e->ev[EV_CHROMA], s));
-	if (!fork) nhw_launch_phase(PH_LLC, ws, 0, s);     /* Z1 */
-	nhw_launch_final(ws, (uint8_t *)d_out, d_sizes, d_status, s, pack_fork != 0);   /* Z2, container */
-	if (timed == 1) HIPCHK(hipEventRecord(e->ev[EV_END], s));
+		case ENC_C_THIN: nhw_launch_low_chroma_thin(cproc, n, on); break;
+		case ENC_C_LOOPS: nhw_launch_chroma_loops(cproc, cll1, cl2save, ws.plane<const uint8_t>(B_PU), q, comp, ws.compat, n, on); break;
+		case ENC_C_ANALYSIS2: nhw_launch_analysis(st.b ? cl2.saving(cl2save, H / 2, ANA_SAVE_BLOCK) : cl2, on); break;
+		case ENC_C_SIM1: nhw_launch_phase(PH_C2, ws, comp, on); break;
+		case ENC_C_SYN: nhw_launch_synthesis(cjpeg, cproc, n, H, H / 2, 0, on); break;
+		case ENC_C_PRECOMP: nhw_launch_phase(PH_C3, ws, comp, on); break;
+		case ENC_C_SIM2: nhw_launch_phase(PH_C4, ws, comp, on); break;
+		case ENC_C_TAIL: nhw_launch_chroma_tail(ws, comp, st.b != 0, on); break;
+		case ENC_Y4: {
+			NhwAnalysis first = l2.from(ll1, H);
+			if (st.a) first.store = ANA_STORE_NO_T;
+			nhw_launch_analysis(first, on);
+			break;
+		}
+		case ENC_Y5: nhw_launch_phase(PH_L1, ws, 0, on); break;
+		case ENC_DQ1: nhw_launch_wave(WV_DQ1, ws, on); break;
+		case ENC_L_SYN1: nhw_launch_synthesis(jpeg, proc, n, W, H, 0, on); break;
+		case ENC_Y8: nhw_launch_phase(PH_L2, ws, 0, on); break;
+		case ENC_L2_RECON: nhw_launch_l2_recon(jpeg, proc, ll1, st.a ? l2save : Plane<int16_t>{}, n, on, st.b != 0); break;
+		case ENC_L_ANALYSIS2: nhw_launch_analysis(st.a ? l2.saving(l2save, H, ANA_SAVE_BLOCK) : l2, on); break;
+		case ENC_LOW_LL2: nhw_launch_low_ll2(proc, q, n, on); break;
+		case ENC_COPY_BLOCK: nhw_launch_copy_block(proc, W, l2save, H, H, H, n, on); break;
+		case ENC_EMIT: nhw_launch_wave(WV_EMIT, ws, on, st.a != 0); break;
+		case ENC_LL_CODER: nhw_launch_phase(PH_L3, ws, 0, on); break;
+		case ENC_DQ0: assert(st.b == ws.defer_verbatim); nhw_launch_wave(WV_DQ0, ws, on, (st.a & 1) != 0, (st.a & 2) != 0); break;
+		case ENC_L_SYN2:
+			if (st.b) {
+				const Plane<const uint8_t> meta = ws.plane<const uint8_t>(B_META), len{ meta.p + offsetof(NhwMeta, ll_mem_len), meta.pitch };
+				nhw_launch_synthesis(jpeg, proc, n, W, H, st.a, ws.plane<const uint8_t>(B_LLMEM), len, on);
+			} else nhw_launch_synthesis(jpeg, proc, n, W, H, st.a, on);
+			break;
+		case ENC_L4A: nhw_launch_phase(PH_L4A, ws, 0, on); break;
+		case ENC_L4B: nhw_launch_phase(PH_L4B, ws, 0, on); break;
+		case ENC_L4C: nhw_launch_phase(PH_L4C, ws, 0, on); break;
+		case ENC_QUANT: nhw_launch_wave(WV_QUANT, ws, on, false, st.a != 0); break;
+		case ENC_L4C2: nhw_launch_phase(PH_L4C2, ws, 0, on); break;
+		case ENC_Y31: nhw_launch_phase(PH_L4D, ws, 0, on); break;
+		case ENC_PACK_CHROMA: nhw_launch_pack_chroma(ws, on); break;
+		case ENC_LLC: nhw_launch_phase(PH_LLC, ws, 0, on); break;
+		case ENC_FINAL: nhw_launch_final(ws, (uint8_t *)io.d_out, io.d_sizes, io.d_status, on, st.a != 0); break;
+		default: assert(!"a step the executor does not know"); break;
+		}
+	}
 	HIPCHK(hipGetLastError());
 	return NHW_OK;
+}
+
+/* what the handle and one call put into the planner */
+static EncIn plan_input(const nhw_enc *e, int n, int quality, int timed, int what)
+{
+	EncIn in = {};
+	in.q = quality; in.stop = e->stop_after; in.compat = e->ws.compat; in.what = what; in.timed = timed; in.big = n >= 1024; in.front_fallback = e->front_fallback & 1;
+	in.low_chroma = e->low_chroma; in.chroma_fork = e->chroma_fork; in.lists_fork = e->lists_fork; in.ll_fork = e->ll_fork; in.quant_join = e->quant_join;
+	in.y5_fork = e->y5_fork; in.ll2_once = e->ll2_once; in.quant_marks = e->quant_marks; in.chroma_tail_once = e->chroma_tail_once; in.pack_fork = e->pack_fork;
+	in.low_parts = e->low_parts;
+	return in;
+}
+
+/* the launch sequence for the images of one workspace view on one stream: check, plan, run.  timed, what: EncIn (nhw_enc_plan.h) */
+static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, hipStream_t s,
+                     int timed, int what, bool *counts_as_timed = nullptr)
+{
+	const EncPlan plan = enc_plan(plan_input(e, n, quality, timed, what));
+	if (!plan.n) { nhw_enc_err = "no launch plan for this call"; return NHW_E_ARG; }
+	NhwWs ws = ws_in;
+	assert(ws.n == n && ws.q == quality && ws.dbg == plan.dbg);
+	ws.split_chroma = plan.split_chroma; ws.defer_verbatim = plan.defer_verbatim;
+	if (counts_as_timed) *counts_as_timed = plan.timed;
+	return run_steps(e, ws, plan, EncIo{ d_bgr, d_out, d_sizes, d_status }, s);
 }
 
 /* Most kernels of the sequence are bound by latency at the occupancy their LDS footprint allows, not by HBM or the ALUs, so a
@@ -432,8 +305,9 @@ extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int qu
 	e->timed = false;                                              /* set again only when a whole, un-stopped batch has recorded every event of nhw_timing */
 	const int parts = (e->stop_after || n < 512) ? 1 : e->parts;
 	if (parts == 1) {
-		const int rc = run_batch(e, ws, d_bgr, n, quality, d_out, d_sizes, d_status, s, 1);
-		if (rc == NHW_OK && !e->stop_after) { e->timed = true; e->timed_parts = 1; e->timed_front_images = n; e->last_n = n; e->last_q = quality; }
+		bool timed = false;
+		const int rc = run_batch(e, ws, d_bgr, n, quality, d_out, d_sizes, d_status, s, 1, 3, &timed);
+		if (rc == NHW_OK && timed) { e->timed = true; e->timed_parts = 1; e->timed_front_images = n; e->last_n = n; e->last_q = quality; }
 		return rc;
 	}
 	/* the front launch group is the part that is bound by the memory system and the ALUs: it runs once for the whole batch */
@@ -447,8 +321,7 @@ extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int qu
 		NhwWs view = ws;
 		view.n = i1 - i0;
 		for (int b = 0; b < B_COUNT; b++) view.off[b] += (size_t)i0 * ws.stride[b];
-		hipStream_t ps_ = e->part_stream[k];
-		HIPCHK(hipStreamWaitEvent(ps_, e->part_ev[PE_FRONT], 0));
+		hipStream_t ps_ = e->part_stream[k];                           /* (its plan begins with the wait for PE_FRONT) */
 		const int rc = run_batch(e, view, (const uint8_t *)d_bgr + (size_t)i0 * (W * W * 3), i1 - i0, quality, (uint8_t *)d_out + (size_t)i0 * NHW_OUT_STRIDE,
 		                         d_sizes + i0, d_status + i0, ps_, k == 0 ? 2 : 0, 2);
 		if (rc != NHW_OK) return rc;
@@ -617,9 +490,10 @@ extern "C" int nhw_stage_chroma_loops(nhw_enc *e, int n, int comp, int form, voi
 	HIPCHK(hipStreamWaitEvent(s, e->ev[EV_END], 0));
 	const Plane<int16_t> cjpeg = ws.plane<int16_t>(B_CJPEG), cproc = ws.plane<int16_t>(B_CPROC), cll1 = ws.plane<int16_t>(B_CLL1), cl2save = ws.plane<int16_t>(B_CL2SAVE);
 	if (form == 0) {
-		int stage = 0;
-		const int rc = chroma_head_launches(e, ws, comp, n, s, stage);
-		if (rc != 1) return rc;
+		EncBuilder b;
+		enc_chroma_head(b, ws.q, false, comp, ES_MAIN);
+		const int rc = run_steps(e, ws, b.p, EncIo{}, s);
+		if (rc != NHW_OK) return rc;
 	} else if (form == 1)
 		nhw_launch_chroma_loops(cproc, cll1, cl2save, ws.plane<const uint8_t>(B_PU), ws.q, comp, ws.compat, n, s);
 	else {
@@ -663,7 +537,7 @@ extern "C" int nhw_stage_chroma_tail(nhw_enc *e, int n, int comp, int form, void
 
 /* A test hook for the luma plane's first closed loop, on B_JPEG, B_PROC, B_LL1 and B_L2SAVE as they stand (a test writes them: nhw_debug_write), for
  * the first n images of the handle's last whole batch at that batch's quality (7 .. 23: below it there is no first closed loop).
- *   form 0: the production kernels from the first level-2 analysis to the second (luma_loop_launches), every plane stored;
+ *   form 0: the production kernels from the first level-2 analysis to the second (enc_luma_loop), every plane stored;
  *   form 1: their last part alone, from the synthesis on: k_l2_recon<true> for q > 12, k_l2_recon<false> and the analysis below it, every plane stored;
  *   forms 6, 7: forms 0, 1 as run_batch launches them outside the compatibility mode, without the stores of the level-2 block that nothing in a
  *           batch reads: the first analysis' transposed plane, and for q > 12 the fused kernel's transposed plane and rows 128 .. 255 of
@@ -689,9 +563,10 @@ extern "C" int nhw_stage_luma_loop(nhw_enc *e, int n, int form, void *stream)
 	const bool lean = form >= 6;
 	if (lean && ws.compat) { nhw_enc_err = "nhw_stage_luma_loop: forms 6 and 7 are not launched in the compatibility mode"; return NHW_E_ARG; }
 	if (form == 0 || form == 6) {
-		int stage = 0;
-		const int rc = luma_loop_launches(e, ws, n, s, stage, false, lean);
-		if (rc != 1) return rc;
+		EncBuilder b;
+		enc_luma_loop(b, ws.q, false, false, lean);
+		const int rc = run_steps(e, ws, b.p, EncIo{}, s);
+		if (rc != NHW_OK) return rc;
 	} else if (form == 1 || form == 7) {
 		nhw_launch_l2_recon(jpeg, proc, ll1, save ? l2save : Plane<int16_t>{}, n, s, lean && save);
 		if (!save) nhw_launch_analysis(l2, s);

@@ -6,6 +6,8 @@
 #include <assert.h>
 #include <stdint.h>
 
+#include "nhw_buf.h"   /* the B_* names of the buffers */
+
 #define W  512      /* luma row stride  (reference 2*IM_DIM) */
 #define H  256      /* chroma row stride (reference IM_DIM) */
 #define Q  65536    /* reference IM_SIZE */
@@ -16,18 +18,20 @@
 /* Per-image buffers are laid out structure-of-arrays over the batch: buffer b of image i lives at
  * base + off[b] + i * stride[b], stride[b] = size + GUARD rounded to 256 B, and GUARD zero bytes precede
  * image 0.  The guards are never written, so they stay zero between batches. */
+/* The buffers' numbers are an interface: nhw_debug_read, nhw_debug_write, nhw_debug_hash and nhw_debug_fill take them, and the stage tests read
+ * them out of this list.  It restates the order of nhw_buf.h; a name that moves there without moving here does not compile (a division by zero
+ * in a constant expression). */
 enum {
-	B_JPEG, B_PROC, B_PU, B_PV, B_CJPEG, B_CPROC, B_LL1, B_L2SAVE, B_CLL1, B_CL2SAVE, B_KEEP, B_FIRST, B_BAND,
-	B_HS, B_KMAP, B_ROWMAP, B_ROWSTATE, B_SCAN, B_LLBYTES, B_LLFULL, B_EXW, B_LLCOMP, B_LLWORD, B_LLMEM, B_RES4,
-	B_RAW, B_PAY, B_CC, B_HALF, B_TMP16,
-	B_R1LIST, B_R1BITS, B_R1WORD, B_R3LIST, B_R3BITS, B_R3WORD, B_R5LIST, B_R5BITS, B_R5WORD,
-	B_R6LIST, B_R6BITS, B_R6WORD, B_CHARRES, B_QSET3,
-	B_RESU64, B_RESV64, B_PACKET, B_BOOK1, B_BOOK2, B_SEL1, B_SEL2, B_S1, B_S2, B_HIST, B_META, B_PROF, B_ROWFLAG, B_SEGMAP, B_STALE,
-	B_NZQ, B_NZS, B_VOFF, B_VALS, B_CNZQ, B_CVALS,   /* the luma symbol stream as a list (nhw_tail_wave.h, wave_quantise_luma): non-zero map as the quantiser writes it, the map and the value offsets in stream order (Y31), the values; CNZQ / CVALS: the chroma part's map and values as the chroma quantiser leaves them */
-	B_CJPEG_V, B_CPROC_V, B_CLL1_V, B_CL2SAVE_V, B_UBYTES,   /* the V plane's own copies of the four chroma work planes (production: NhwWs::split_chroma); UBYTES: where the chroma quantiser parks U's symbols until V's come (it used the band plane, and above q21 waited for Y29 to be through with it) */
-	B_LOWTAB,   /* quality 1..16: the candidate masks pass A of the pre-filter leaves for its order-dependent cells (nhw_low.hip, k_low_pre -> k_low_mapfix): 320 bytes a row */
-	B_CPACK, B_CPACKET,   /* the chroma packetiser's own (k_pack_chroma, NhwChromaPack below): its map and value offsets in stream order, its scratch and what it leaves for k_final; its packet words from word 0 on (a chroma part alone may hold 80000 words) */
-	B_COUNT
+	NHW_WS_BUFFER_ORDER = 1 / (int)(
+		B_JPEG == 0 && B_PROC == 1 && B_PU == 2 && B_PV == 3 && B_CJPEG == 4 && B_CPROC == 5 && B_LL1 == 6 && B_L2SAVE == 7 && B_CLL1 == 8 &&
+		B_CL2SAVE == 9 && B_KEEP == 10 && B_FIRST == 11 && B_BAND == 12 && B_HS == 13 && B_KMAP == 14 && B_ROWMAP == 15 && B_ROWSTATE == 16 &&
+		B_SCAN == 17 && B_LLBYTES == 18 && B_LLFULL == 19 && B_EXW == 20 && B_LLCOMP == 21 && B_LLWORD == 22 && B_LLMEM == 23 && B_RES4 == 24 &&
+		B_RAW == 25 && B_PAY == 26 && B_CC == 27 && B_HALF == 28 && B_TMP16 == 29 && B_R1LIST == 30 && B_R1BITS == 31 && B_R1WORD == 32 &&
+		B_R3LIST == 33 && B_R3BITS == 34 && B_R3WORD == 35 && B_R5LIST == 36 && B_R5BITS == 37 && B_R5WORD == 38 && B_R6LIST == 39 && B_R6BITS == 40 &&
+		B_R6WORD == 41 && B_CHARRES == 42 && B_QSET3 == 43 && B_RESU64 == 44 && B_RESV64 == 45 && B_PACKET == 46 && B_BOOK1 == 47 && B_BOOK2 == 48 &&
+		B_SEL1 == 49 && B_SEL2 == 50 && B_S1 == 51 && B_S2 == 52 && B_HIST == 53 && B_META == 54 && B_PROF == 55 && B_ROWFLAG == 56 && B_SEGMAP == 57 &&
+		B_STALE == 58 && B_NZQ == 59 && B_NZS == 60 && B_VOFF == 61 && B_VALS == 62 && B_CNZQ == 63 && B_CVALS == 64 && B_CJPEG_V == 65 &&
+		B_CPROC_V == 66 && B_CLL1_V == 67 && B_CL2SAVE_V == 68 && B_UBYTES == 69 && B_LOWTAB == 70 && B_CPACK == 71 && B_CPACKET == 72 && B_COUNT == 73)
 };
 
 /* B_CPACK of an image.  k_pack_chroma runs while the luma tail still owns B_NZS / B_VOFF (Y31) and B_RAW (Y25): everything it writes lies here
