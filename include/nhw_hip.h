@@ -753,6 +753,37 @@ int nhw_hist_device(const nhw_picture *d_pics, int n, int channels, uint32_t *d_
  * channels == 1 only t[0] is written.  The histograms need not come from a picture.  Asynchronous on `stream`, capturable. */
 int nhw_tone_from_hist_device(const uint32_t *d_hist, int n, int channels, const uint8_t *d_ops, nhw_tone_table *d_tones, void *stream);
 
+/* ---- blur and sharpen a sample: the rule of a separable filter in front of the pixel's store ----
+ * The one per-sample step of the common recipes that reads a pixel's neighbours -- GaussianBlur with a random sigma (SimCLR, MoCo v2, BYOL, DINO),
+ * RandAugment's Sharpness, a box filter -- is two lists of taps, a mix and a border: one nhw_blur a sample.  This build has the rule (this text and
+ * nhwcodec_amd/csrc/nhw_blur.h, for host and device) and the record; it has no device entry that applies it yet (section 26, "Left out").
+ * The rule (the whole specification).  A picture is W x H, with C = 3 or 1 bytes a pixel.  Each channel is filtered on its own.  p(y, x) is a byte
+ * of the picture.  ix(i, n) depends on the border.  Reflect, without repeating the edge: i < 0 -> -i, and i >= n -> 2 (n - 1) - i; this is torch's
+ * `reflect` padding, which torchvision's gaussian_blur uses.  Replicate: min(max(i, 0), n - 1).  The four steps:
+ *   1. h(y, x) = (sum_{j = 0 .. 2 rx} wx[j] p(y, ix(x + j - rx, W)) + 64) >> 7.  The result lies in 0 .. 65280, with eight fractional bits, and is
+ *      held as 16 bits.
+ *   2. b(y, x) = (sum_{j = 0 .. 2 ry} wy[j] h(ix(y + j - ry, H), x) + 2^22) >> 23.  The result lies in 0 .. 255.  The sum plus the rounding term
+ *      is at most 32768 x 65280 + 2^22 = 2 143 289 344, below 2^31.
+ *   3. z = clamp(p + floor((mix (b - p) + 32768) / 65536), 0, 255).  Halves go up at either sign, as in section 24: an arithmetic shift of a
+ *      signed 32-bit value, |mix (b - p)| < 2^28.
+ *   4. z takes the place of the byte in the pixel's store: the value rule, channel order, layout and row rule of nhw_tensor_format, exactly as
+ *      the resamplers' store applies them.
+ * Three consequences: rx = ry = 0 with a tap of 32768 gives b = p and z = p for every mix; mix = 65536 gives z = b; a constant picture stays
+ * constant.
+ * A blur is within the limits (nhw_blur_within of nhwcodec_amd/csrc/nhw_blur.h) for a W x H picture when rx, ry <= 15; wx[0 .. 2 rx] and
+ * wy[0 .. 2 ry] each sum to 32768; |mix| <= 16 x 65536; border <= 1; and, under reflect, rx < W and ry < H.  The reserved fields are not read.
+ * Beyond the limits the rule's sums may overflow and an index may leave the picture: nothing applies a record that is not within them. */
+#define NHW_BLUR_MAX_RADIUS 15
+#define NHW_BLUR_ONE        32768      /* a tap is in 1/32768 */
+#define NHW_BLUR_MAX_MIX    16         /* |mix| <= 16 * 65536 */
+enum { NHW_BLUR_REFLECT = 0, NHW_BLUR_REPLICATE = 1 };
+typedef struct nhw_blur {              /* 144 bytes, 4-byte aligned */
+	uint16_t wx[32], wy[32];           /* taps 0 .. 2 rx (2 ry); the entries behind them are not read */
+	int32_t  mix;                      /* 1/65536: 65536 the blurred pixel, 0 the picture's own, below 0 sharpens */
+	uint8_t  rx, ry, border, reserved8;
+	uint32_t reserved[2];
+} nhw_blur;
+
 #ifdef __cplusplus
 }
 #endif

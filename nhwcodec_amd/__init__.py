@@ -1130,6 +1130,97 @@ def tone_from_hist_device(hist_u32, ops, tones=None):
     return d_tones
 
 
+# ---------------------------------------------------------------- blur and sharpen a sample
+BLUR_DTYPE = [("wx", "<u2", (32,)), ("wy", "<u2", (32,)), ("mix", "<i4"), ("rx", "u1"), ("ry", "u1"), ("border", "u1"), ("reserved8", "u1"), ("reserved", "<u4", (2,))]   # nhw_blur, 144 bytes
+BLUR_MAX_RADIUS = 15                               # NHW_BLUR_MAX_RADIUS: 31 taps a direction at the most
+BLUR_ONE = 32768                                   # NHW_BLUR_ONE: a tap is in 1/32768, and a direction's taps sum to this
+BLUR_MAX_MIX = 16                                  # NHW_BLUR_MAX_MIX: |mix| is 16 at the most (2^20 / 65536)
+BLUR_BORDERS = {"reflect": 0, "replicate": 1}      # NHW_BLUR_REFLECT, NHW_BLUR_REPLICATE
+
+
+def blur_taps(weights):
+    """The integer taps of a list of weights: any non-negative finite floats, of odd length 31 at the most and not all zero -> a tuple of ints
+    summing to exactly BLUR_ONE.  The weights are normalised in float64, each becomes rint(32768 w), and what the sum then lacks or exceeds
+    goes to the centre tap; raises NhwError where that would make the centre tap negative."""
+    import numpy as np
+    try:
+        w = np.asarray(weights)
+        w = w.astype(np.float64) if w.dtype.kind in "iuf" else None
+    except (TypeError, ValueError):
+        w = None
+    if w is None or w.ndim != 1 or len(w) % 2 != 1 or len(w) > 2 * BLUR_MAX_RADIUS + 1:
+        raise NhwError(f"blur_taps: the weights are a list of numbers of odd length {2 * BLUR_MAX_RADIUS + 1} at the most, got {weights!r}")
+    if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0 or not np.isfinite(w.sum()):
+        raise NhwError(f"blur_taps: the weights must be finite, none below zero and not all zero, got {w.tolist()!r}")
+    t = np.rint(BLUR_ONE * (w / w.sum())).astype(np.int64)
+    t[len(t) // 2] += BLUR_ONE - int(t.sum())
+    if t[len(t) // 2] < 0:
+        raise NhwError(f"blur_taps: the roundings of {w.tolist()!r} leave the centre tap below zero")
+    return tuple(int(v) for v in t)
+
+
+def _blur_radius(radius, what):
+    if isinstance(radius, bool) or not isinstance(radius, numbers.Integral) or not 0 <= radius <= BLUR_MAX_RADIUS:
+        raise NhwError(f"{what}: the radius must be an integer of 0 .. {BLUR_MAX_RADIUS}, got {radius!r}")
+    return int(radius)
+
+
+def blur_gaussian(sigma, radius=None):
+    """torchvision's gaussian_blur weights as taps: exp(-1/2 (x / sigma)^2) on x = -radius .. radius, through blur_taps.  sigma: a finite number
+    above 0; radius: 0 .. BLUR_MAX_RADIUS, or None for min(15, ceil(3 sigma)) and 1 at the least.  (torchvision's kernel_size is 2 radius + 1.)"""
+    import numpy as np
+    if isinstance(sigma, bool) or not isinstance(sigma, numbers.Real) or not math.isfinite(sigma) or not sigma > 0:
+        raise NhwError(f"blur_gaussian: sigma must be a finite number above 0, got {sigma!r}")
+    r = max(1, min(BLUR_MAX_RADIUS, math.ceil(3 * float(sigma)))) if radius is None else _blur_radius(radius, "blur_gaussian")
+    x = np.arange(-r, r + 1, dtype=np.float64)
+    return blur_taps(np.exp(-0.5 * (x / float(sigma)) ** 2))
+
+
+def blur_box(radius):
+    """the box filter of 2 radius + 1 equal weights, through blur_taps"""
+    return blur_taps([1.0] * (2 * _blur_radius(radius, "blur_box") + 1))
+
+
+def _blur_tap_list(taps, what):
+    """a tap list of blur_fixed: integers that already sum to BLUR_ONE are taken as they are, anything else goes through blur_taps"""
+    import numpy as np
+    try:
+        a = np.asarray(taps)
+    except Exception:
+        a = None
+    if a is not None and a.ndim == 1 and a.dtype.kind in "iu" and len(a) % 2 == 1 and len(a) <= 2 * BLUR_MAX_RADIUS + 1 and (a >= 0).all() and int(a.sum()) == BLUR_ONE:
+        return tuple(int(v) for v in a)
+    try:
+        return blur_taps(taps)
+    except NhwError as e:
+        raise NhwError(f"{what}: {e}") from None
+
+
+def blur_fixed(taps_x, taps_y=None, mix=1.0, border="reflect"):
+    """One nhw_blur record (a numpy scalar of BLUR_DTYPE), the separable filter of a sample under the rule of DESIGN.md section 26 -- rows, then
+    columns, then the mix with the picture's own byte.  The rule and the record are what this build has; no device call applies a record yet.
+    taps_x, taps_y: weights as blur_taps takes them, or integers that already sum to BLUR_ONE (what blur_gaussian and blur_box return); taps_y=None
+    means taps_x.  mix: 1 the blurred pixel, 0 the picture's own, below 0 a sharpening (z = p + mix (b - p)); rint(65536 mix) in float64, ties to
+    even, |mix| <= BLUR_MAX_MIX.  border: "reflect" (torch's reflect padding, torchvision's gaussian_blur) or "replicate".  Raises NhwError for a
+    number that is not finite or beyond a limit.
+    GaussianBlur(kernel_size=23, sigma=s) is blur_fixed(blur_gaussian(s, 11)); RandAugment's Sharpness of factor f is blur_fixed([1, 1, 1],
+    mix=1 - f) up to PIL's non-separable 3 x 3 SMOOTH kernel, which this rule does not have."""
+    import numpy as np
+    wx = _blur_tap_list(taps_x, "blur_fixed: taps_x")
+    wy = wx if taps_y is None else _blur_tap_list(taps_y, "blur_fixed: taps_y")
+    if isinstance(mix, bool) or not isinstance(mix, numbers.Real) or not math.isfinite(mix):
+        raise NhwError(f"blur_fixed: mix must be a finite number, got {mix!r}")
+    m = float(np.rint(float(mix) * 65536.0))
+    if abs(m) > BLUR_MAX_MIX * 65536:
+        raise NhwError(f"blur_fixed: mix {mix!r} is beyond the limit of {BLUR_MAX_MIX} in magnitude")
+    if not isinstance(border, str) or border not in BLUR_BORDERS:
+        raise NhwError(f"blur_fixed: border must be one of {sorted(BLUR_BORDERS)}, got {border!r}")
+    rec = np.zeros((), BLUR_DTYPE)
+    rec["wx"][:len(wx)], rec["wy"][:len(wy)] = wx, wy
+    rec["mix"], rec["rx"], rec["ry"], rec["border"] = int(m), len(wx) // 2, len(wy) // 2, BLUR_BORDERS[border]
+    return rec[()]
+
+
 TENSOR_PICTURE_DTYPE = [("addr", "<u8"), ("pitch", "<u8"), ("plane", "<u8"), ("width", "<u4"), ("height", "<u4"), ("first_tile", "<u4"), ("reserved", "<u4")]   # nhw_tensor_picture
 
 
