@@ -784,6 +784,34 @@ typedef struct nhw_blur {              /* 144 bytes, 4-byte aligned */
 	uint32_t reserved[2];
 } nhw_blur;
 
+/* ---- encode grey: one-channel bytes and tensors at one byte a pixel ----
+ * A grey picture is 512 x 512 bytes, rows in the byte path's order; picture i of a batch lies at i * NHW_GREY_BYTES.  The one contract of every
+ * call here: the file is byte for byte the file nhw_enc_batch_device writes for the picture with every grey byte in B, G and R, at the same quality
+ * and compatibility mode, with the same size and the same status.  No colour conversion, chroma staging or 4:2:0 filter runs: the luma is a table
+ * of the byte and the quality (nhw_grey_luma_table), both 4:2:0 planes are 128.  One handle serves colour and grey batches in any order.
+ * Below quality 16 the chroma of such a file does not decode to exactly neutral: the grey decode calls (section 22) are the way to read it.
+ * The colour entry points go on refusing NHW_T_GREY. */
+#define NHW_GREY_BYTES  262144u      /* 512*512 */
+/* L_quality[0 .. 256): the encoder's luma of the pixel B = G = R = g.  Host only: no handle, no GPU call.  NHW_E_ARG for a quality outside 1 .. 23 or a NULL table */
+int nhw_grey_luma_table(int quality, int16_t out[256]);
+/* nhw_enc_batch_device from n grey pictures at d_grey, which must be 16-byte aligned; every other argument and check as there */
+int nhw_enc_batch_device_grey(nhw_enc *e, const void *d_grey, int n, int quality, void *d_out, uint32_t *d_sizes,
+                              int32_t *d_status, void *stream);
+/* nhw_enc_batch from n grey pictures in host memory, through the staging the handle already has */
+int nhw_enc_batch_grey(nhw_enc *e, const uint8_t *grey, int n, int quality, uint8_t *out_arena, size_t arena_cap,
+                       uint64_t *out_off, int32_t *status);
+/* nhw_tensor_to_bytes_device and nhw_enc_batch_device_tensor for one-channel tensors: fmt->channels must be NHW_T_GREY (NHW_T_BGR and NHW_T_RGB
+ * are refused), d_in holds n x 512 x 512 elements -- [n, 1, 512, 512] and [n, 512, 512, 1] are the same memory, so the layout is not read --,
+ * the value rule of an encode runs with scale[0] and bias[0]; d_grey: n * NHW_GREY_BYTES, 16-byte aligned */
+int nhw_tensor_to_bytes_grey_device(const void *d_in, int n, const nhw_tensor_format *fmt, void *d_grey, void *stream);
+int nhw_enc_batch_device_grey_tensor(nhw_enc *e, const void *d_in, int n, const nhw_tensor_format *fmt, int quality,
+                                     void *d_out, int32_t *d_sizes, int32_t *d_status, void *stream);
+/* nhw_tile_pictures_device at one byte a pixel: a table of [H][W] pictures of any alignment and pitch, tile t into d_tiles + (t - tile0) * NHW_GREY_BYTES */
+int nhw_tile_pictures_grey_device(const nhw_picture *d_pics, int n_pics, int tile0, int m, void *d_tiles, void *stream);
+/* nhw_enc_pictures from grey pictures, W x H bytes packed at grey + in_off[i]: the container format is unchanged, every tile file an ordinary .nhw */
+int nhw_enc_pictures_grey(nhw_enc *e, const uint8_t *grey, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                          int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,13 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     a = L.nhw_dec_warps_mapped_to_device.argtypes
     L.nhw_dec_warps_toned_to_device.argtypes = a[:12] + [P] + a[12:]
     L.nhw_hist_device.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P]
+    L.nhw_grey_luma_table.argtypes = [ctypes.c_int, P]                                     # encode grey: their colour calls' arguments
+    L.nhw_enc_batch_device_grey.argtypes = L.nhw_enc_batch_device.argtypes
+    L.nhw_enc_batch_grey.argtypes = L.nhw_enc_batch.argtypes
+    L.nhw_tensor_to_bytes_grey_device.argtypes = L.nhw_tensor_to_bytes_device.argtypes
+    L.nhw_enc_batch_device_grey_tensor.argtypes = L.nhw_enc_batch_device_tensor.argtypes
+    L.nhw_tile_pictures_grey_device.argtypes = L.nhw_tile_pictures_device.argtypes
+    L.nhw_enc_pictures_grey.argtypes = L.nhw_enc_pictures.argtypes
     L.nhw_tone_from_hist_device.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, P]
     return L
 
@@ -282,8 +289,8 @@ class TensorFormat:
     up to rounding).  The attributes scale and bias are the float32 constants the kernels get, as tuples of Python floats.
     channels "GREY" is the one-channel format of Decoder.decode_grey_device and of the calls with `grey` in their names
     (section 23), and of nothing else: scale / bias / mean /
-    std take ONE number (three are refused), the tensor is [1, S, S] or [S, S, 1], and there is no inverse, for encoding from grey is not
-    built."""
+    std take ONE number (three are refused), the tensor is [1, S, S] or [S, S, 1], and its inverse is inverted_grey(), which the grey
+    encode calls take (section 27)."""
 
     def __init__(self, dtype="float32", layout="CHW", channels="RGB", rows="reversed", scale=None, bias=None, mean=None, std=None):
         import numpy as np
@@ -349,7 +356,7 @@ class TensorFormat:
         a result is not finite in float32."""
         import numpy as np
         if self.channels == "GREY":
-            raise NhwError("TensorFormat.inverted: a grey format has no inverse: encoding from grey is not built")
+            raise NhwError("TensorFormat.inverted: a grey format is inverted by inverted_grey(), for the grey encode calls")
         sc, bi = np.array(self.scale, np.float32), np.array(self.bias, np.float32)
         if np.any(sc == 0):
             raise NhwError(f"TensorFormat.inverted: a scale of 0 has no inverse: {self.scale}")
@@ -358,6 +365,22 @@ class TensorFormat:
         if not (np.all(np.isfinite(isc)) and np.all(np.isfinite(ibi))):
             raise NhwError(f"TensorFormat.inverted: scale {self.scale} / bias {self.bias} give no finite float32 inverse")
         return TensorFormat(self.dtype_name, self.layout, self.channels, self.rows, scale=tuple(float(x) for x in isc), bias=tuple(float(x) + 0.0 for x in ibi))
+
+    def inverted_grey(self):
+        """inverted() for a format of channels "GREY": the format that encodes, through the grey encode calls, what a grey
+        decode under this one produced -- the same dtype, layout and rows, and in float32 arithmetic scale' = 1 / scale, bias' = -bias / scale on
+        the one scale and bias.  NhwError for a colour format, a scale of 0 or a result that is not finite in float32."""
+        import numpy as np
+        if self.channels != "GREY":
+            raise NhwError(f"TensorFormat.inverted_grey: the format has channels {self.channels!r}, not \"GREY\": inverted() is its inverse")
+        sc, bi = np.float32(self.scale[0]), np.float32(self.bias[0])
+        if sc == 0:
+            raise NhwError(f"TensorFormat.inverted_grey: a scale of 0 has no inverse: {self.scale[0]}")
+        with np.errstate(all="ignore"):
+            isc, ibi = np.float32(1) / sc, -bi / sc
+        if not (np.isfinite(isc) and np.isfinite(ibi)):
+            raise NhwError(f"TensorFormat.inverted_grey: scale {self.scale[0]} / bias {self.bias[0]} give no finite float32 inverse")
+        return TensorFormat(self.dtype_name, self.layout, "GREY", self.rows, scale=float(isc), bias=float(ibi) + 0.0)
 
     def __repr__(self):
         return f"TensorFormat({self.dtype_name}, {self.layout}, {self.channels}, rows={self.rows}, scale={self.scale}, bias={self.bias})"
@@ -372,6 +395,18 @@ def grey_table(quality: int):
     t = np.empty(256, np.uint8)
     if _library().nhw_grey_table(quality, t.ctypes.data) != 0:
         raise NhwError(f"grey_table: {_library().nhw_dec_last_error().decode()}")
+    return t
+
+
+def grey_luma_table(quality: int):
+    """L_quality (nhw_grey_luma_table): numpy int16 [256], the encoder's luma of the pixel B = G = R = g under that
+    quality -- the identity for quality 20 .. 23, the byte scaled for 17 .. 19, the integer form from 16 down.  Needs no GPU."""
+    import numpy as np
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 23:
+        raise NhwError(f"grey_luma_table: quality must be an integer 1 .. 23, got {quality!r}")
+    t = np.empty(256, np.int16)
+    if _library().nhw_grey_luma_table(quality, t.ctypes.data) != 0:
+        raise NhwError(f"grey_luma_table: {_library().nhw_last_error().decode()}")
     return t
 
 
@@ -426,6 +461,21 @@ def tile_pictures_device(pictures):
     L = _library()
     with torch.cuda.device(dev):
         rc = L.nhw_tile_pictures_device(table.data_ptr(), len(pictures), 0, tiles, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
+
+
+def tile_pictures_grey_device(pictures):
+    """tile_pictures_device at one byte a pixel (nhw_tile_pictures_grey_device): a list of uint8 CUDA tensors [H, W] with
+    strides (pitch >= W, 1) on one device (crop views work without a copy) -> tiles uint8 [T, 512, 512], padded by edge replication.  Ordered on
+    torch's current stream; feeds Encoder.encode_grey_device."""
+    import torch
+    table, tiles, dev = _picture_table(pictures, "tile_pictures_grey_device", channels=1)
+    out = torch.empty((tiles, 512, 512), dtype=torch.uint8, device=dev)
+    L = _library()
+    with torch.cuda.device(dev):
+        rc = L.nhw_tile_pictures_grey_device(table.data_ptr(), len(pictures), 0, tiles, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -1258,6 +1308,24 @@ def tensor_to_bytes_device(x, fmt):
     return out
 
 
+def tensor_to_grey_bytes_device(x, fmt):
+    """tensor_to_bytes_device for one-channel tensors (nhw_tensor_to_bytes_grey_device): x, a contiguous CUDA tensor
+    [n, 1, 512, 512] or [n, 512, 512, 1] of fmt.dtype, fmt of channels "GREY" -> uint8 [n, 512, 512] as Encoder.encode_grey_device takes them, under
+    the same value rule with the format's one scale and bias.  Ordered on torch's current stream."""
+    import torch
+    what = "tensor_to_grey_bytes_device"
+    fmt = _tensor_format(fmt, what, grey=True)
+    n = _tensor_batch(x, fmt, what)
+    out = torch.empty((n, 512, 512), dtype=torch.uint8, device=x.device)
+    L = _library()
+    c = fmt.c_struct()
+    with torch.cuda.device(x.device):
+        rc = L.nhw_tensor_to_bytes_grey_device(x.data_ptr(), n, ctypes.byref(c), out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
+    if rc != 0:
+        raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
+    return out
+
+
 def _tensor_picture_table(tensors, fmt, what):
     """the checked nhw_tensor_picture table of a list of CUDA tensors [3, H, W] (strides (plane, pitch, 1)) or [H, W, 3] (strides (pitch, 3, 1))
     of fmt.dtype on one device -> (table as an int64 CUDA tensor, total tiles, device)"""
@@ -1459,6 +1527,52 @@ class Encoder:
             self._chk(self.lib.nhw_enc_batch_device_tensor(self.h, x.data_ptr(), n, ctypes.byref(c), quality, o.data_ptr(), sizes.data_ptr(), status.data_ptr(), st))
         return o, sizes, status
 
+    def encode_grey_device(self, grey, quality: int = QUALITY_DEFAULT, out=None):
+        """encode_device from grey pictures (nhw_enc_batch_device_grey): grey, a contiguous, 16-byte aligned uint8 CUDA
+        tensor [n, 512, 512], rows in the byte path's order.  File i is byte for byte the file of encode_device on the picture with grey[i] in B,
+        G and R; no colour conversion and no 4:2:0 filter runs.  Returns (out[n,OUT_STRIDE], sizes[n], status[n]) on device."""
+        what = "encode_grey_device"
+        t = self.torch
+        if not (isinstance(grey, t.Tensor) and grey.is_cuda and grey.dtype == t.uint8 and grey.is_contiguous() and grey.dim() == 3 and tuple(grey.shape[1:]) == (512, 512)):
+            raise NhwError(f"{what} wants a contiguous uint8 CUDA tensor of shape [n, 512, 512]")
+        if grey.device.index != self.device:
+            raise NhwError(f"the batch is on cuda:{grey.device.index}, this encoder on cuda:{self.device}")
+        n = grey.shape[0]
+        o, sizes, status = self._device_outputs(what, n, out)
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_enc_batch_device_grey(self.h, grey.data_ptr(), n, quality, o.data_ptr(), sizes.data_ptr(), status.data_ptr(), st))
+        return o, sizes, status
+
+    def encode_grey_tensor_device(self, x, fmt, quality: int = QUALITY_DEFAULT, out=None):
+        """encode_grey_device straight from a one-channel tensor batch (nhw_enc_batch_device_grey_tensor): x and fmt as for
+        tensor_to_grey_bytes_device, on this encoder's device.  The files are those of encode_grey_device(tensor_to_grey_bytes_device(x, fmt))."""
+        what = "encode_grey_tensor_device"
+        fmt = _tensor_format(fmt, what, grey=True)
+        n = _tensor_batch(x, fmt, what, self.device)
+        if n > self.max_batch:
+            raise NhwError(f"{what}: {n} pictures for an encoder of max_batch {self.max_batch}")
+        o, sizes, status = self._device_outputs(what, n, out)
+        c = fmt.c_struct()
+        with _OnTorchStream(self) as st:
+            self._chk(self.lib.nhw_enc_batch_device_grey_tensor(self.h, x.data_ptr(), n, ctypes.byref(c), quality, o.data_ptr(), sizes.data_ptr(), status.data_ptr(), st))
+        return o, sizes, status
+
+    def encode_grey(self, pictures, quality: int = QUALITY_DEFAULT):
+        """pictures: numpy uint8 [n,512,512] on the host, grey -> list of .nhw byte strings (nhw_enc_batch_grey; raises on a per-image failure)."""
+        import numpy as np
+        pictures = np.asarray(pictures)
+        if pictures.dtype != np.uint8 or pictures.ndim != 3 or pictures.shape[1:] != (512, 512):
+            raise NhwError(f"encode_grey wants uint8 [n, 512, 512] (BMP file order), got {pictures.dtype} {pictures.shape}")
+        pictures = np.ascontiguousarray(pictures)
+        n = pictures.shape[0]
+        arena = np.empty(n * OUT_STRIDE, np.uint8)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_enc_batch_grey(self.h, pictures.ctypes.data, n, quality, arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-image status {status.tolist()}")
+        return _split(arena, offs)
+
     def encode(self, images, quality: int = QUALITY_DEFAULT):
         """images: numpy uint8 [n,512,512,3] on the host -> list of .nhw byte strings (raises on a per-image failure)."""
         import numpy as np
@@ -1612,15 +1726,16 @@ class Encoder:
         return self.encode(tiles, quality), shape
 
     @staticmethod
-    def _host_pictures(pictures, what):
-        """a list of numpy uint8 [H, W, 3] -> (n, packed blob, in_off, width, height, tiles, an output arena that holds every container)"""
+    def _host_pictures(pictures, what, grey=False):
+        """a list of numpy uint8 [H, W, 3] ([H, W] with grey) -> (n, packed blob, in_off, width, height, tiles, an output arena that holds every container)"""
         import numpy as np
+        form = "[H, W]" if grey else "[H, W, 3]"
         if not isinstance(pictures, (list, tuple)) or not pictures:
-            raise NhwError(f"{what} wants a non-empty list of uint8 [H, W, 3] arrays")
+            raise NhwError(f"{what} wants a non-empty list of uint8 {form} arrays")
         arrs = [np.ascontiguousarray(p) for p in pictures]
         for i, a in enumerate(arrs):
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
-                raise NhwError(f"{what}: picture {i} is not uint8 [H, W, 3], got {a.dtype} {a.shape}")
+            if a.dtype != np.uint8 or (a.ndim != 2 if grey else a.ndim != 3 or a.shape[2] != 3):
+                raise NhwError(f"{what}: picture {i} is not uint8 {form}, got {a.dtype} {a.shape}")
             picture_tiles(a.shape[1], a.shape[0])
         n = len(arrs)
         width = np.array([a.shape[1] for a in arrs], np.uint32)
@@ -1642,6 +1757,19 @@ class Encoder:
         status = np.empty(n, np.int32)
         self._chk(self.lib.nhw_enc_pictures(self.h, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n, quality,
                                             arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
+        if (status != 0).any():
+            raise NhwError(f"per-picture status {status.tolist()}")
+        return _split(arena, offs)
+
+    def encode_pictures_grey(self, pictures, quality: int = QUALITY_DEFAULT):
+        """encode_pictures from grey pictures (nhw_enc_pictures_grey): a list of numpy uint8 [H, W] -> a list of .nhwp
+        containers, each byte for byte the container of the picture with its bytes in B, G and R; Decoder.decode_pictures_grey reads them."""
+        import numpy as np
+        n, blob, in_off, width, height, _, arena = self._host_pictures(pictures, "encode_pictures_grey", grey=True)
+        offs = np.empty(n + 1, np.uint64)
+        status = np.empty(n, np.int32)
+        self._chk(self.lib.nhw_enc_pictures_grey(self.h, blob.ctypes.data, in_off.ctypes.data, width.ctypes.data, height.ctypes.data, n, quality,
+                                                 arena.ctypes.data, arena.size, offs.ctypes.data, status.ctypes.data))
         if (status != 0).any():
             raise NhwError(f"per-picture status {status.tolist()}")
         return _split(arena, offs)

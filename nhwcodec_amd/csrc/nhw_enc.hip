@@ -7,6 +7,7 @@
  */
 #include "nhw_enc.h"
 #include "nhw_enc_plan.h"
+#include "nhw_grey.h"
 
 thread_local std::string nhw_enc_err;
 extern "C" const char *nhw_last_error(void) { return nhw_enc_err.c_str(); }
@@ -31,6 +32,14 @@ static const size_t k_buf_bytes[B_COUNT] = {
 static size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 extern "C" int nhw_quality_supported(int quality) { return quality >= 1 && quality <= 23; }
+
+/* L_quality (nhw_grey.h) into out[0 .. 256).  Host only: no handle, no GPU call */
+extern "C" int nhw_grey_luma_table(int quality, int16_t out[256])
+{
+	if (!out || !nhw_quality_supported(quality)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	for (int g = 0; g < 256; g++) out[g] = (int16_t)nhw_grey_luma(quality, g);
+	return NHW_OK;
+}
 
 extern "C" int nhw_enc_set_compat(nhw_enc *e, int mode)
 {
@@ -148,7 +157,7 @@ int host_buffers(nhw_enc *e, int n)
 
 /* The executor of a plan's steps (nhw_enc_plan.h): every kernel step is one call of its launcher with the planes of the view ws, every event step
  * one call of the runtime.  The planner decides what is launched, in which order and on which stream; nothing here does. */
-struct EncIo { const void *d_bgr; void *d_out; uint32_t *d_sizes; int32_t *d_status; };   /* the caller's arrays (a stage hook: none, its plans have no step that takes them) */
+struct EncIo { const void *d_bgr; void *d_out; uint32_t *d_sizes; int32_t *d_status; bool grey; };   /* the caller's arrays (a stage hook: none, its plans have no step that takes them); grey: d_bgr holds grey pictures, one byte a pixel */
 static_assert(EE_START == EV_START && EE_FRONT == EV_FRONT && EE_LUMA == EV_LUMA && EE_CHROMA == EV_CHROMA && EE_END == EV_END && EE_COLOR == EV_COLOR && EE_PREFILTER == EV_PREFILTER,
               "the plan's stamps are the handle's timing events");
 static hipEvent_t enc_event(nhw_enc *e, int ev, int low_parts_used)
@@ -193,7 +202,7 @@ static int run_steps(nhw_enc *e, const NhwWs &ws, const EncPlan &plan, const Enc
 		case ENC_RECORD: HIPCHK(hipEventRecord(enc_event(e, st.a, plan.low_parts_used), on)); break;
 		case ENC_WAIT: HIPCHK(hipStreamWaitEvent(on, enc_event(e, st.a, plan.low_parts_used), 0)); break;
 		case ENC_STAGE: break;
-		case ENC_COLOR: nhw_launch_color((const uint8_t *)io.d_bgr, n, q, st.a ? yin : jpeg, pu, pv, on); break;
+		case ENC_COLOR: (io.grey ? nhw_launch_color_grey : nhw_launch_color)((const uint8_t *)io.d_bgr, n, q, st.a ? yin : jpeg, pu, pv, on); break;
 		case ENC_LOW_PREFILTER:
 			HIPCHK((hipError_t)nhw_launch_low_prefilter(jpeg, yin, proc, ws.plane<uint8_t>(B_SCAN), ws.plane<uint8_t>(B_KEEP), ws.plane<uint8_t>(B_LOWTAB), q, n, on, st.b ? 32 : 0,
 			                                            st.a, e->low_stream, e->low_ev));
@@ -203,7 +212,7 @@ static int run_steps(nhw_enc *e, const NhwWs &ws, const EncPlan &plan, const Enc
 			NhwFront f;
 			f.q = q; f.n = n; f.y = yin /* quality 17..23, developer builds only: a plane for a dump */; f.st = ws.plane<uint8_t>(B_ROWSTATE);
 			f.proc = proc; f.jpeg = jpeg; f.ll1 = ll1; f.switches = (ws.dbg ? 2 : 0) | st.a;
-			if (q > 16) { f.bgr = (const uint8_t *)io.d_bgr; f.pu = pu; f.pv = pv; f.with_prefilter = q < 22; }
+			if (q > 16) { f.bgr = (const uint8_t *)io.d_bgr; f.grey = io.grey; f.pu = pu; f.pv = pv; f.with_prefilter = q < 22; }
 			if (q > 21) f.keep = ws.plane<int16_t>(B_KEEP);
 			nhw_launch_front_fused(f, on);
 			break;
@@ -277,7 +286,7 @@ static EncIn plan_input(const nhw_enc *e, int n, int quality, int timed, int wha
 }
 
 /* the launch sequence for the images of one workspace view on one stream: check, plan, run.  timed, what: EncIn (nhw_enc_plan.h) */
-static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, hipStream_t s,
+static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, bool grey, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, hipStream_t s,
                      int timed, int what, bool *counts_as_timed = nullptr)
 {
 	const EncPlan plan = enc_plan(plan_input(e, n, quality, timed, what));
@@ -286,17 +295,18 @@ static int run_batch(nhw_enc *e, const NhwWs &ws_in, const void *d_bgr, int n, i
 	assert(ws.n == n && ws.q == quality && ws.dbg == plan.dbg);
 	ws.split_chroma = plan.split_chroma; ws.defer_verbatim = plan.defer_verbatim;
 	if (counts_as_timed) *counts_as_timed = plan.timed;
-	return run_steps(e, ws, plan, EncIo{ d_bgr, d_out, d_sizes, d_status }, s);
+	return run_steps(e, ws, plan, EncIo{ d_bgr, d_out, d_sizes, d_status, grey }, s);
 }
 
 /* Most kernels of the sequence are bound by latency at the occupancy their LDS footprint allows, not by HBM or the ALUs, so a
  * large batch is cut into sub-batches whose sequences run on streams of their own: kernels of different stages overlap on the
  * CUs.  Images are independent and the workspace is indexed per image, so a sub-batch is just a shifted view of it. */
-extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes,
-                                    int32_t *d_status, void *stream)
+static int batch_device(nhw_enc *e, const void *d_bgr, bool grey, int n, int quality, void *d_out, uint32_t *d_sizes, int32_t *d_status, void *stream)
 {
 	if (!e || !d_bgr || !d_out || !d_sizes || !d_status || n < 1 || n > e->max_batch) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (grey && ((uintptr_t)d_bgr & 15)) { nhw_enc_err = "nhw_enc_batch_device_grey: d_grey must be 16-byte aligned"; return NHW_E_ARG; }
 	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	const size_t picture = grey ? (size_t)W * W : (size_t)W * W * 3;  /* the input advances by the picture's own size */
 	HIPCHK(hipSetDevice(e->device));
 	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
 	const NhwSliceScope slices(e->slice_order);
@@ -306,13 +316,13 @@ extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int qu
 	const int parts = (e->stop_after || n < 512) ? 1 : e->parts;
 	if (parts == 1) {
 		bool timed = false;
-		const int rc = run_batch(e, ws, d_bgr, n, quality, d_out, d_sizes, d_status, s, 1, 3, &timed);
+		const int rc = run_batch(e, ws, d_bgr, grey, n, quality, d_out, d_sizes, d_status, s, 1, 3, &timed);
 		if (rc == NHW_OK && timed) { e->timed = true; e->timed_parts = 1; e->timed_front_images = n; e->last_n = n; e->last_q = quality; }
 		return rc;
 	}
 	/* the front launch group is the part that is bound by the memory system and the ALUs: it runs once for the whole batch */
 	HIPCHK(hipEventRecord(e->ev[EV_START], s));
-	{ const int rc = run_batch(e, ws, d_bgr, n, quality, d_out, d_sizes, d_status, s, 0, 1); if (rc != NHW_OK) return rc; }
+	{ const int rc = run_batch(e, ws, d_bgr, grey, n, quality, d_out, d_sizes, d_status, s, 0, 1); if (rc != NHW_OK) return rc; }
 	HIPCHK(hipEventRecord(e->ev[EV_FRONT], s));
 	HIPCHK(hipEventRecord(e->part_ev[PE_FRONT], s));
 	e->timed_front_images = n;
@@ -322,7 +332,7 @@ extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int qu
 		view.n = i1 - i0;
 		for (int b = 0; b < B_COUNT; b++) view.off[b] += (size_t)i0 * ws.stride[b];
 		hipStream_t ps_ = e->part_stream[k];                           /* (its plan begins with the wait for PE_FRONT) */
-		const int rc = run_batch(e, view, (const uint8_t *)d_bgr + (size_t)i0 * (W * W * 3), i1 - i0, quality, (uint8_t *)d_out + (size_t)i0 * NHW_OUT_STRIDE,
+		const int rc = run_batch(e, view, (const uint8_t *)d_bgr + (size_t)i0 * picture, grey, i1 - i0, quality, (uint8_t *)d_out + (size_t)i0 * NHW_OUT_STRIDE,
 		                         d_sizes + i0, d_status + i0, ps_, k == 0 ? 2 : 0, 2);
 		if (rc != NHW_OK) return rc;
 		HIPCHK(hipEventRecord(e->part_ev[k], ps_));
@@ -331,6 +341,19 @@ extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int qu
 	HIPCHK(hipEventRecord(e->ev[EV_END], s));
 	e->timed = true; e->timed_parts = parts; e->last_n = n; e->last_q = quality;
 	return NHW_OK;
+}
+
+extern "C" int nhw_enc_batch_device(nhw_enc *e, const void *d_bgr, int n, int quality, void *d_out, uint32_t *d_sizes,
+                                    int32_t *d_status, void *stream)
+{
+	return batch_device(e, d_bgr, false, n, quality, d_out, d_sizes, d_status, stream);
+}
+
+/* the same from grey pictures, 512 x 512 bytes each: file i is the file of picture i with every byte in B, G and R */
+extern "C" int nhw_enc_batch_device_grey(nhw_enc *e, const void *d_grey, int n, int quality, void *d_out, uint32_t *d_sizes,
+                                         int32_t *d_status, void *stream)
+{
+	return batch_device(e, d_grey, true, n, quality, d_out, d_sizes, d_status, stream);
 }
 
 extern "C" int nhw_enc_last_timing(nhw_enc *e, nhw_timing *t)

@@ -73,6 +73,20 @@ extern "C" int nhw_enc_batch(nhw_enc *e, const uint8_t *bgr, int n, int quality,
 	return host_download(e, n, out_arena, arena_cap, out_off, status);
 }
 
+/* the same from grey pictures, 262144 bytes each, through the same staging: a picture's slot holds three of them */
+extern "C" int nhw_enc_batch_grey(nhw_enc *e, const uint8_t *grey, int n, int quality, uint8_t *out_arena, size_t arena_cap,
+                                  uint64_t *out_off, int32_t *status)
+{
+	if (!e || !grey || !out_arena || !out_off || !status || n < 1 || n > e->max_batch) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	HIPCHK(hipSetDevice(e->device));
+	{ const int rc = host_buffers(e, n); if (rc) return rc; }
+	hipStream_t s = e->own_stream;
+	HIPCHK(hipMemcpyAsync(e->d_in, grey, (size_t)n * NHW_GREY_BYTES, hipMemcpyHostToDevice, s));
+	{ const int rc = nhw_enc_batch_device_grey(e, e->d_in, n, quality, e->d_out, e->d_sizes, e->d_status, s); if (rc) return rc; }
+	return host_download(e, n, out_arena, arena_cap, out_off, status);
+}
+
 /* SURVEY.md 8(d) synthetic images seed_base .. seed_base+n-1, generated on the device, encoded, and the files brought to the host:
  * `nhw-enc --synthetic` (tools/nhw_enc.c) */
 extern "C" int nhw_enc_synth_batch(nhw_enc *e, int n, uint32_t seed_base, int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
@@ -98,6 +112,13 @@ extern "C" int nhw_tile_pictures_device(const nhw_picture *d_pics, int n_pics, i
 {
 	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_tile_pictures_device")) return rc;
 	HIPCHK(nhw_launch_tile_pad(d_pics, n_pics, tile0, m, (uint8_t *)d_tiles, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_tile_pictures_grey_device(const nhw_picture *d_pics, int n_pics, int tile0, int m, void *d_tiles, void *stream)
+{
+	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_tile_pictures_grey_device")) return rc;
+	HIPCHK(nhw_launch_tile_pad_grey(d_pics, n_pics, tile0, m, (uint8_t *)d_tiles, (hipStream_t)stream));
 	return NHW_OK;
 }
 
@@ -327,6 +348,43 @@ extern "C" int nhw_enc_batch_device_tensor(nhw_enc *e, const void *d_in, int n, 
 	return nhw_enc_batch_device(e, e->d_tensor_bytes, n, quality, d_out, (uint32_t *)d_sizes, d_status, s);
 }
 
+/* the one-channel forms of both: a format of NHW_T_GREY, [n][512][512] elements, grey pictures of 512 x 512 bytes */
+static int tensor_in_args_grey(const void *d_in, const nhw_tensor_format *fmt, NhwTensorArgs *a, const char *who)
+{
+	if (fmt && (fmt->channels == NHW_T_BGR || fmt->channels == NHW_T_RGB)) { nhw_enc_err = std::string(who) + ": a grey call takes NHW_T_GREY, not NHW_T_BGR or NHW_T_RGB"; return NHW_E_ARG; }
+	if (const int rc = nhw_tensor_format_check(fmt, a, nhw_enc_err, true)) return rc;
+	if (!d_in || ((uintptr_t)d_in & 15)) { nhw_enc_err = std::string(who) + ": d_in must be a 16-byte aligned device pointer"; return NHW_E_ARG; }
+	return NHW_OK;
+}
+
+extern "C" int nhw_tensor_to_bytes_grey_device(const void *d_in, int n, const nhw_tensor_format *fmt, void *d_grey, void *stream)
+{
+	NhwTensorArgs a;
+	if (const int rc = tensor_in_args_grey(d_in, fmt, &a, "nhw_tensor_to_bytes_grey_device")) return rc;
+	if (!d_grey || ((uintptr_t)d_grey & 15)) { nhw_enc_err = "nhw_tensor_to_bytes_grey_device: d_grey must be a 16-byte aligned device pointer"; return NHW_E_ARG; }
+	if (n < 1 || n > (1 << 22)) { nhw_enc_err = "nhw_tensor_to_bytes_grey_device: n outside 1 .. 2^22"; return NHW_E_ARG; }
+	HIPCHK(nhw_launch_tensor_to_bytes_grey(d_in, n, fmt->dtype, a, (uint8_t *)d_grey, (hipStream_t)stream));
+	return NHW_OK;
+}
+
+extern "C" int nhw_enc_batch_device_grey_tensor(nhw_enc *e, const void *d_in, int n, const nhw_tensor_format *fmt, int quality,
+                                                void *d_out, int32_t *d_sizes, int32_t *d_status, void *stream)
+{
+	if (!e || !d_out || !d_sizes || !d_status || n < 1 || n > e->max_batch) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	NhwTensorArgs a;
+	if (const int rc = tensor_in_args_grey(d_in, fmt, &a, "nhw_enc_batch_device_grey_tensor")) return rc;
+	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
+	if (fmt->dtype == NHW_T_U8 && fmt->rows == NHW_T_ROWS_FILE) return nhw_enc_batch_device_grey(e, d_in, n, quality, d_out, (uint32_t *)d_sizes, d_status, stream);   /* already the grey pictures */
+	HIPCHK(hipSetDevice(e->device));
+	if (!e->d_tensor_bytes) {                                          /* the first tensor call on the handle: the colour call's scratch, a third of it used here */
+		const int rc = dev_alloc({ dev_buf(e->d_tensor_bytes, (size_t)e->max_batch * NHW_IMG_BYTES) }, "tensor encode scratch", e->max_batch, nhw_enc_err);
+		if (rc) return rc;
+	}
+	hipStream_t s = stream ? (hipStream_t)stream : e->own_stream;
+	HIPCHK(nhw_launch_tensor_to_bytes_grey(d_in, n, fmt->dtype, a, e->d_tensor_bytes, s));
+	return nhw_enc_batch_device_grey(e, e->d_tensor_bytes, n, quality, d_out, (uint32_t *)d_sizes, d_status, s);
+}
+
 extern "C" int nhw_tile_tensors_device(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, const nhw_tensor_format *fmt, void *d_tiles, void *stream)
 {
 	if (const int rc = picture_args(d_pics, n_pics, tile0, m, d_tiles, "nhw_tile_tensors_device")) return rc;
@@ -344,12 +402,13 @@ extern "C" int nhw_sse_pictures_device(const void *d_tiles, const nhw_picture *d
 	return NHW_OK;
 }
 
-/* The pictures of a host call (nhw_enc_pictures, the picture searches): packed (pitch 3 W) at bgr + in_off[i].  pictures_check: the sides
+/* The pictures of a host call (nhw_enc_pictures, the picture searches): packed (pitch 3 W; bpp 1, the grey pictures of section 27: W) at bgr + in_off[i].  pictures_check: the sides
  * and the tile count; first[i] = picture i's first tile, first[n] = all tiles; the descriptors numbered so (addr still 0). */
 struct PicCall {
 	std::vector<nhw_picture> desc;
 	std::vector<int> first;
 	int tiles = 0;
+	uint32_t bpp = 3;            /* bytes a pixel: 3, or 1 (nhw_enc_pictures_grey) */
 };
 
 static int pictures_check(const uint32_t *width, const uint32_t *height, int n, const char *who, PicCall &pc)
@@ -360,7 +419,7 @@ static int pictures_check(const uint32_t *width, const uint32_t *height, int n, 
 	for (int i = 0; i < n; i++) {
 		const int t = nhw_picture_tiles(width[i], height[i]);
 		if (t < 1) { nhw_enc_err = std::string(who) + ": a picture side outside 1..65535"; return NHW_E_ARG; }
-		pc.desc[i] = { 0, 3ull * width[i], width[i], height[i], (uint32_t)tiles, 0 };
+		pc.desc[i] = { 0, (uint64_t)pc.bpp * width[i], width[i], height[i], (uint32_t)tiles, 0 };
 		pc.first[i] = (int)tiles;
 		tiles += (uint64_t)t;
 		if (tiles > INT_MAX / 16) { nhw_enc_err = std::string(who) + ": too many tiles in one call"; return NHW_E_ARG; }
@@ -377,7 +436,7 @@ static int pictures_upload(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_of
 	const int n = (int)pc.desc.size();
 	uint64_t bytes = 0, lo = UINT64_MAX, hi = 0;
 	for (int i = 0; i < n; i++) {
-		const uint64_t sz = 3ull * pc.desc[i].width * pc.desc[i].height;
+		const uint64_t sz = (uint64_t)pc.bpp * pc.desc[i].width * pc.desc[i].height;
 		bytes += sz;
 		lo = in_off[i] < lo ? in_off[i] : lo;
 		hi = in_off[i] + sz > hi ? in_off[i] + sz : hi;
@@ -389,7 +448,7 @@ static int pictures_upload(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_of
 	uint8_t *px = e->pic_px.as<uint8_t>();
 	if (span) HIPCHK(hipMemcpyAsync(px, bgr + lo, hi - lo, hipMemcpyHostToDevice, s));
 	for (uint64_t i = 0, at = 0; i < (uint64_t)n; i++) {
-		const uint64_t sz = 3ull * pc.desc[i].width * pc.desc[i].height;
+		const uint64_t sz = (uint64_t)pc.bpp * pc.desc[i].width * pc.desc[i].height;
 		if (span) pc.desc[i].addr = (uint64_t)(uintptr_t)(px + (in_off[i] - lo));
 		else {
 			HIPCHK(hipMemcpyAsync(px + at, bgr + in_off[i], sz, hipMemcpyHostToDevice, s));
@@ -415,7 +474,7 @@ struct ChunkSse {
  * slots: k_tile_pad straight from the uploaded pictures, the encode, (the SSE step), then the chunk's files compacted and brought back.
  * Tile t's file is files[.. + lens[t]) (back to back in tile order), its status tst[t]. */
 static int encode_tiles(nhw_enc *e, const nhw_picture *d_desc, int np, int tiles, int quality, const ChunkSse *cs, std::vector<uint8_t> &files,
-                        uint32_t *lens, int32_t *tst)
+                        uint32_t *lens, int32_t *tst, bool grey = false /* pictures and tiles of one byte a pixel (section 27; no SSE step) */)
 {
 	hipStream_t s = e->own_stream;
 	const int chunk = tiles < e->max_batch ? tiles : e->max_batch;
@@ -423,8 +482,8 @@ static int encode_tiles(nhw_enc *e, const nhw_picture *d_desc, int np, int tiles
 	files.clear();
 	for (int t0 = 0; t0 < tiles; t0 += chunk) {
 		const int m = tiles - t0 < chunk ? tiles - t0 : chunk;
-		HIPCHK(nhw_launch_tile_pad(d_desc, np, t0, m, e->d_in, s));
-		{ const int rc = nhw_enc_batch_device(e, e->d_in, m, quality, e->d_out, e->d_sizes, e->d_status, s); if (rc) return rc; }
+		HIPCHK((grey ? nhw_launch_tile_pad_grey : nhw_launch_tile_pad)(d_desc, np, t0, m, e->d_in, s));
+		{ const int rc = (grey ? nhw_enc_batch_device_grey : nhw_enc_batch_device)(e, e->d_in, m, quality, e->d_out, e->d_sizes, e->d_status, s); if (rc) return rc; }
 		if (cs) {
 			const int rc = nhw_dec_batch_device(cs->dec, e->d_out, cs->doff, e->d_sizes, m, cs->px, cs->dstatus, nullptr, s);
 			if (rc) { nhw_enc_err = std::string("decode of a rung: ") + nhw_dec_last_error(); return rc; }
@@ -460,7 +519,7 @@ static int encode_containers(nhw_enc *e, const nhw_picture *d_desc, const PicCal
 	std::vector<uint8_t> files;
 	std::vector<uint32_t> lens((size_t)tiles);
 	std::vector<int32_t> tst((size_t)tiles);
-	{ const int rc = encode_tiles(e, d_desc, n, tiles, quality, nullptr, files, lens.data(), tst.data()); if (rc) return rc; }
+	{ const int rc = encode_tiles(e, d_desc, n, tiles, quality, nullptr, files, lens.data(), tst.data(), pc.bpp == 1); if (rc) return rc; }
 	const int *first = pc.first.data();
 	uint64_t at = 0, fpos = 0;
 	for (int i = 0; i < n; i++) {
@@ -481,18 +540,32 @@ static int encode_containers(nhw_enc *e, const nhw_picture *d_desc, const PicCal
 
 /* Upload the pictures, pad and tile them in chunks of max_batch tiles into the host path's input slot, encode each chunk, compact and fetch
  * its files; then one container per picture. */
-extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
-                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+static int enc_pictures(nhw_enc *e, const char *who, uint32_t bpp, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                        int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
 {
 	if (!e || !bgr || !in_off || !width || !height || !out_arena || !out_off || !status || n < 1) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
 	if (!nhw_quality_supported(quality)) { nhw_enc_err = "quality outside 1..23"; return NHW_E_QUALITY; }
 	PicCall pc;
-	{ const int rc = pictures_check(width, height, n, "nhw_enc_pictures", pc); if (rc) return rc; }
+	pc.bpp = bpp;
+	{ const int rc = pictures_check(width, height, n, who, pc); if (rc) return rc; }
 	HIPCHK(hipSetDevice(e->device));
 	{ const int rc = host_buffers(e, pc.tiles < e->max_batch ? pc.tiles : e->max_batch); if (rc) return rc; }
 	{ const int rc = pictures_upload(e, bgr, in_off, pc); if (rc) return rc; }
 	HIPCHK(hipMemcpyAsync(e->pic_desc.p, pc.desc.data(), (size_t)n * sizeof(nhw_picture), hipMemcpyHostToDevice, e->own_stream));
 	return encode_containers(e, e->pic_desc.as<nhw_picture>(), pc, quality, out_arena, arena_cap, out_off, status);
+}
+
+extern "C" int nhw_enc_pictures(nhw_enc *e, const uint8_t *bgr, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	return enc_pictures(e, "nhw_enc_pictures", 3, bgr, in_off, width, height, n, quality, out_arena, arena_cap, out_off, status);
+}
+
+/* the same from grey pictures, [H][W] bytes packed at grey + in_off[i]: the container and its tile files are ordinary ones */
+extern "C" int nhw_enc_pictures_grey(nhw_enc *e, const uint8_t *grey, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
+                                     int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status)
+{
+	return enc_pictures(e, "nhw_enc_pictures_grey", 1, grey, in_off, width, height, n, quality, out_arena, arena_cap, out_off, status);
 }
 
 /* nhw_enc_pictures with the area filter in front: the pictures go up as there; one k_area_to_tensor (uint8, HWC, BGR, file

@@ -18,6 +18,7 @@
 #include "nhw_host.h"
 #include "nhw_ws.h"
 #include "nhw_dwt.h"
+#include "nhw_grey.h"
 
 #pragma clang fp contract(off)
 
@@ -173,6 +174,35 @@ __global__ __launch_bounds__(256) void k_color(const uint8_t *__restrict__ bgr, 
 	}
 }
 
+/* The colour stage of grey bytes, one a pixel: quality 1 .. 16 and the compatibility mode's replay.  One workgroup per
+ * 8 luma rows as k_color, a thread one 16-byte load: the luma is nhw_grey_luma of the byte -- its integer forms: grey16 (nhw_front_image.h) for
+ * FAMILY 0 .. 2, the quality table's multiply for FAMILY 3 -- and both 4:2:0 planes are 128.  No row is staged: nothing reads a neighbour. */
+template <int FAMILY> __device__ __forceinline__ void grey16(const uint4 v, uint32_t fx, uint32_t yw[8]);   /* nhw_front_image.h */
+template <int FAMILY>
+__global__ __launch_bounds__(256) void k_color_grey(const uint8_t *__restrict__ grey, int16_t *__restrict__ yb, size_t y_stride,
+                                                    uint8_t *__restrict__ ub, uint8_t *__restrict__ vb, size_t c_stride, float yq)
+{
+	const int b = blockIdx.x, img = blockIdx.y, t = threadIdx.x;
+	const size_t px = (size_t)(8 * b) * W + 16 * t;                 /* 8 rows of 512 bytes: 256 pieces of 16 */
+	const uint4 v = *reinterpret_cast<const uint4 *>(grey + (size_t)img * (W * W) + px);
+	uint32_t yw[8];
+	if (FAMILY != 3) grey16<FAMILY>(v, __float_as_uint(yq), yw);
+	else {
+		const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+		const int qz = __float_as_int(yq);
+#pragma unroll
+		for (int e = 0; e < 8; e++) {
+			const int g0 = (w[e >> 1] >> (16 * (e & 1))) & 0xFF, g1 = (w[e >> 1] >> (16 * (e & 1) + 8)) & 0xFF;
+			const int y0 = ((220 * g0 * qz + 4194304) >> 23) + 16, y1 = ((220 * g1 * qz + 4194304) >> 23) + 16;
+			yw[e] = (uint32_t)(uint16_t)y0 | ((uint32_t)(uint16_t)y1 << 16);
+		}
+	}
+	uint4 *yo = reinterpret_cast<uint4 *>((int16_t *)((uint8_t *)yb + (size_t)img * y_stride) + px);
+	yo[0] = make_uint4(yw[0], yw[1], yw[2], yw[3]); yo[1] = make_uint4(yw[4], yw[5], yw[6], yw[7]);
+	if (t < 128)                                                    /* chroma rows 4b .. 4b+3 of both planes: 64 pieces of 16 bytes each */
+		*reinterpret_cast<uint4 *>(((t >> 6) ? vb : ub) + (size_t)img * c_stride + (size_t)(4 * b) * H + 16 * (t & 63)) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+}
+
 /* ------------------------------------------------------------------------------------------------
  * luma pre-filter.  Pass A is a 3x3 contrast measure pushed through a 4-bit error-diffusion carry that
  * runs in raster order over the whole interior.  The carry is a 16-state machine; it is parallelised
@@ -272,6 +302,24 @@ static float color_yq(int q, int *family)
 	*family = 3;
 	return __builtin_bit_cast(float, k_qtz[q < 1 ? 1 : q]);
 }
+/* the same for grey bytes: the word grey16 takes (quality 17 .. 19), the quality table's entry below */
+constexpr bool grey_fixed_holds(int q)
+{
+	const uint32_t fx = nhw_grey_luma_fixed(q);
+	for (int g = 0; g < 256; g++) if ((int)(((uint32_t)g * (fx & 0xFFFFu) + (fx >> 16)) >> 16) != nhw_grey_luma(q, g)) return false;
+	return true;
+}
+constexpr bool grey_identity_holds()
+{
+	for (int q = 20; q < 24; q++) for (int g = 0; g < 256; g++) if (nhw_grey_luma(q, g) != g) return false;
+	return true;
+}
+static_assert(grey_fixed_holds(17) && grey_fixed_holds(18) && grey_fixed_holds(19) && grey_identity_holds(), "grey16 is nhw_grey_luma");
+static float grey_yq(int q, int *family)
+{
+	const float yq = color_yq(q, family);
+	return *family == 1 || *family == 2 ? __builtin_bit_cast(float, nhw_grey_luma_fixed(q)) : yq;
+}
 void nhw_launch_color(const uint8_t *bgr, int n, int q, Plane<int16_t> y, Plane<uint8_t> u, Plane<uint8_t> v, hipStream_t s)
 {
 	const dim3 grid(H / 4, n);
@@ -279,6 +327,14 @@ void nhw_launch_color(const uint8_t *bgr, int n, int q, Plane<int16_t> y, Plane<
 	int fam = 0;
 	const float yq = color_yq(q, &fam);
 	(fam == 0 ? k_color<0> : fam == 1 ? k_color<1> : fam == 2 ? k_color<2> : k_color<3>)<<<grid, 256, 0, s>>>(bgr, y.p, y.bytes(), u.p, v.p, u.pitch, yq);   /* quality table of colorspace.c:174-189 (format constants) */
+}
+void nhw_launch_color_grey(const uint8_t *grey, int n, int q, Plane<int16_t> y, Plane<uint8_t> u, Plane<uint8_t> v, hipStream_t s)
+{
+	const dim3 grid(W / 8, n);
+	assert(u.pitch == v.pitch);
+	int fam = 0;
+	const float yq = grey_yq(q, &fam);
+	(fam == 0 ? k_color_grey<0> : fam == 3 ? k_color_grey<3> : k_color_grey<1>)<<<grid, 256, 0, s>>>(grey, y.p, y.bytes(), u.p, v.p, u.pitch, yq);
 }
 
 /* ------------------------------------------------------------------------------------------------
@@ -572,6 +628,7 @@ int nhw_front_set_attrs(const char **where)
                                 if (e_ != hipSuccess) { *where = "hipFuncSetAttribute(" #fn ", MaxDynamicSharedMemorySize)"; return (int)e_; } } while (0)
 	SETATTR((k_front_plain<0, 0>), FP_LDS_BYTES); SETATTR((k_front_plain<1, 0>), FP_LDS_BYTES); SETATTR((k_front_image<1, 1, 0>), FI_LDS_BYTES);
 	SETATTR((k_front_image<1, 1, 1>), FI_LDS_BYTES); SETATTR((k_front_image<1, 1, 2>), FI_LDS_BYTES);
+	SETATTR((k_front_plain<2, 0>), FP_STG_OFF); SETATTR((k_front_image<1, 2, 0>), FI_LDS_BYTES); SETATTR((k_front_image<1, 2, 1>), FI_LDS_BYTES);   /* the grey source forms: FAMILY 1 serves 17 .. 19 */
 	SETATTR(k_dwt_ana<256>, 256 * 258 * sizeof(int16_t)); SETATTR(k_dwt_syn<256>, 256 * 258 * sizeof(int16_t));
 	SETATTR(k_dwt_ana<128>, 128 * 130 * sizeof(int16_t)); SETATTR(k_dwt_syn<128>, 128 * 130 * sizeof(int16_t));
 #undef SETATTR
@@ -609,6 +666,7 @@ void nhw_launch_synthesis(Plane<int16_t> jpeg, Plane<int16_t> proc, int n, int s
 /* the front launch group = ONE kernel.
  * bgr != nullptr: quality 17..23, everything from the BGR bytes (colour, 4:2:0 planes pu / pv, pre-filter for q <= 21, level-1 analysis): k_front_image
  *                 with the pre-filter, k_front_plain without;
+ * grey (with bgr): the bytes are grey pictures, one byte a pixel: the same two kernels in their SRC 2 forms;
  * bgr == nullptr: the luma plane y is the input (quality 1..16 behind their own pre-filter; the analysis stage entry point): k_front_plain.
  * st (optional): the carry at the start of every image row, for the compatibility mode's replay of a few rows (k_front_stale); keep (optional, q >= 22).
  * switches bit 0: every carry segment takes its exact replay (tests); bit 1: a stage check is going to read every plane (nothing is left out). */
@@ -617,7 +675,7 @@ void nhw_launch_front_fused(const NhwFront &f, hipStream_t s)
 	assert(f.pu.pitch == f.pv.pitch && f.proc.pitch == f.jpeg.pitch);
 	Plane<int16_t> keep = f.keep;
 	int fam = 0;
-	const float yq = f.bgr ? color_yq(f.q, &fam) : 0.f;
+	const float yq = !f.bgr ? 0.f : f.grey ? grey_yq(f.q, &fam) : color_yq(f.q, &fam);
 	int fl = (f.switches & 1) | ((f.switches & 2) ? 0x100000 : 0);
 #ifdef NHW_DEV
 	{ const char *e = getenv("NHW_BAND_STOP"); if (e) fl |= atoi(e) << 8; }
@@ -628,6 +686,9 @@ void nhw_launch_front_fused(const NhwFront &f, hipStream_t s)
 #define FI_ARGS(srcp, sstride) srcp, sstride, yq, f.pu.p, f.pv.p, f.pu.pitch, f.st.p, f.st.bytes(), f.proc.p, f.jpeg.p, f.jpeg.pitch, f.ll1.p, f.ll1.pitch, keep.p, keep.pitch, fl
 #define FP_ARGS(srcp, sstride) srcp, sstride, yq, f.pu.p, f.pv.p, f.pu.pitch, f.proc.p, f.jpeg.p, f.jpeg.pitch, f.ll1.p, f.ll1.pitch, keep.p, keep.pitch, fl
 	if (!f.bgr) k_front_plain<0, 0><<<f.n, FI_NT, FP_LDS_BYTES, s>>>(FP_ARGS((const void *)f.y.p, f.y.bytes()));
+	else if (f.grey && !f.with_prefilter) k_front_plain<2, 0><<<f.n, FI_NT, FP_STG_OFF /* no chroma slots */, s>>>(FP_ARGS((const void *)f.bgr, (size_t)0));
+	else if (f.grey && fam == 0) k_front_image<1, 2, 0><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));
+	else if (f.grey) k_front_image<1, 2, 1><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));
 	else if (!f.with_prefilter) k_front_plain<1, 0><<<f.n, FI_NT, FP_LDS_BYTES, s>>>(FP_ARGS((const void *)f.bgr, (size_t)0));
 	else if (fam == 0) k_front_image<1, 1, 0><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));
 	else if (fam == 1) k_front_image<1, 1, 1><<<f.n, FI_NT, FI_LDS_BYTES, s>>>(FI_ARGS((const void *)f.bgr, (size_t)0));

@@ -241,8 +241,39 @@ __device__ unsigned long long g_fi_prof[16];
 #define FI_STAMP(i) do { } while (0)
 #endif
 
+/* 16 grey pixels (one dword x 4) -> their luma, two pixels to a dword.  FAMILY 0 (quality >= 20): the byte itself, one
+ * v_perm a pair.  FAMILY 1, 2 (quality 17 .. 19): nhw_grey_luma's integer form (g M + A) >> 16, one 24-bit multiply-add a pixel and one v_perm
+ * a pair that takes the two high halves; fx = nhw_grey_luma_fixed(q).  A 256-entry table in LDS would cost the same byte extraction, a shift
+ * for the address and one ds_read_u16 a pixel -- an LDS instruction for each multiply-add, in kernels that already wait on LDS. */
+template <int FAMILY>
+__device__ __forceinline__ void grey16(const uint4 v, uint32_t fx, uint32_t yw[8])
+{
+	const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+	for (int c = 0; c < 4; c++) {
+		if (FAMILY == 0) {
+			yw[2 * c] = __builtin_amdgcn_perm(0u, w[c], 0x0c010c00u);
+			yw[2 * c + 1] = __builtin_amdgcn_perm(0u, w[c], 0x0c030c02u);
+		} else {
+			const uint32_t m = fx & 0xFFFFu, a = fx >> 16;
+			uint32_t y[4];
+#pragma unroll
+			for (int k = 0; k < 4; k++) y[k] = ((w[c] >> (8 * k)) & 0xFFu) * m + a;   /* below 2^24 */
+			yw[2 * c] = pack_hi(y[0], y[1]);
+			yw[2 * c + 1] = pack_hi(y[2], y[3]);
+		}
+	}
+}
+/* 128 into the 65536 bytes of both 4:2:0 planes of an image, 1/16 of them a call: 512 threads, one 16-byte store each */
+__device__ __forceinline__ void grey_chroma_fill(uint8_t *__restrict__ pub, uint8_t *__restrict__ pvb, size_t off, int part, int t)
+{
+	*reinterpret_cast<uint4 *>(((t >> 8) ? pvb : pub) + off + (size_t)part * 4096 + 16 * (t & 255)) = make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+}
+
 /* PRE: with the pre-filter (quality 17..21).  SRC 1: from the BGR bytes (quality 17..23).  SRC 0: from a luma plane (quality 1..16
- * behind their own pre-filter, nhw_low.hip; the analysis stage entry point): no colour, no chroma, PRE = 0.
+ * behind their own pre-filter, nhw_low.hip; the analysis stage entry point): no colour, no chroma, PRE = 0.  SRC 2: from grey bytes, one a
+ * pixel (quality 17..23): the luma by grey16 (yq carries nhw_grey_luma_fixed's word), 128 into both 4:2:0 planes, no
+ * chroma staging, filter or carried row.
  * flags bit 0: test switch, every carry segment takes its exact replay instead of the look-back. */
 template <int PRE, int SRC, int FAMILY>
 __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_front_image(const void *__restrict__ srcb, size_t src_stride, float yq, uint8_t *__restrict__ pub, uint8_t *__restrict__ pvb, size_t c_stride,
@@ -261,19 +292,29 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 	uint8_t *const misc = lds + FI_MISC_OFF;                        /* [0]: carry behind the band's last row, [2 + (b & 1)]: hand-over flag of its last pixel pair */
 	const int t0 = threadIdx.x, img = blockIdx.x;
 
-	const uint8_t *const src = (const uint8_t *)srcb + (size_t)img * (SRC ? (size_t)(W * W * 3) : src_stride);
+	const uint8_t *const src = (const uint8_t *)srcb + (size_t)img * (SRC == 2 ? (size_t)(W * W) : SRC ? (size_t)(W * W * 3) : src_stride);
 	int16_t *const proc = procb + (size_t)img * plane_stride, *const jpeg = jpegb + (size_t)img * plane_stride;
 	int16_t *const ll1 = ll1b + (size_t)img * ll1_stride;
 
 	/* the next band's rows, on their way while this band is worked on: image rows 32b+2 .. 32b+33 */
-	constexpr int NPF = SRC ? 6 : 4;
+	constexpr int NPF = SRC == 2 ? 2 : SRC ? 6 : 4;
 	uint4 pf[NPF];
 	auto issue = [&](int b) {
 		const int t = opaque(t0);
 		/* Rows outside the image are asked for as the nearest row inside and not used: no branches here, so that every address is computed before
 		 * the first load goes out (with a branch per item the compiler put a wait for the first item's loads in front of the second item's --
 		 * a memory round trip in the open, every band). */
-		if (SRC) {
+		if (SRC == 2) {
+			const uint4 *rp[2];
+#pragma unroll
+			for (int it = 0; it < 2; it++) {                         /* 16 pixels = 16 bytes an item, two items a thread */
+				int row = FI_BR * b + 2 + (t >> 5) + 16 * it;
+				row = row < 0 ? 0 : row > W - 1 ? W - 1 : row;
+				rp[it] = reinterpret_cast<const uint4 *>(src + (size_t)row * W + 16 * (t & 31));
+			}
+#pragma unroll
+			for (int it = 0; it < 2; it++) pf[it] = *rp[it];
+		} else if (SRC) {
 			const uint4 *rp[2];
 #pragma unroll
 			for (int it = 0; it < 2; it++) {                         /* 16 pixels = 48 bytes an item, two items a thread */
@@ -322,7 +363,22 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 		const int r0 = FI_BR * b;
 		FI_TICK(0);                                     /* image row of luma index 0 */
 		/* ---------------------------------------------------------------- phase 0: the prefetched rows -> luma (and filtered chroma) in LDS */
-		if (SRC) {
+		if (SRC == 2) {
+			const int t = opaque(t0);
+#pragma unroll
+			for (int it = 0; it < 2; it++) {
+				const int i = (t >> 5) + 16 * it, g = t & 31, row = r0 + 2 + i;
+				uint32_t yw[8];
+				if (row >= 0 && row < W) grey16<FAMILY>(pf[it], __float_as_uint(yq), yw);
+				else {
+#pragma unroll
+					for (int e = 0; e < 8; e++) yw[e] = 0;
+				}
+				uint32_t *d = reinterpret_cast<uint32_t *>(ybuf) + (i + 2) * FI_YRD + 8 * g + (g >> 2);   /* as below */
+#pragma unroll
+				for (int e = 0; e < 8; e++) d[e] = yw[e];
+			}
+		} else if (SRC) {
 			const int t = opaque(t0);
 #pragma unroll
 			for (int it = 0; it < 2; it++) {
@@ -363,7 +419,8 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 		if (b >= 0 && b + 1 < W / FI_BR) issue(b + 1);                /* the next band's rows are on their way while this band is worked on */
 		FI_TICK(1); FI_STAMP(1);
 		/* ---------------------------------------------------------------- 4:2:0: vertical [1 2 1]/4 over image rows 2r-1, 2r, 2r+1 (colorspace.c:241-256) */
-		if (SRC) {
+		if (SRC == 2) { if (b >= 0) grey_chroma_fill(pub, pvb, (size_t)img * c_stride, b, opaque(t0)); }
+		else if (SRC) {
 			const int t = opaque(t0);
 			const int pl = t >> 8, rr = (t >> 4) & 15, c16 = t & 15, r = 16 * b + 1 + rr;   /* chroma rows 16b+1 .. 16b+16; the band before the first: row 0 */
 			if (b < 0 ? rr == 15 : r < H) {
@@ -398,7 +455,7 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 			const int t = opaque(t0);
 #pragma unroll 1
 			for (int it = 0; it < 4; it++) {
-				if (it == 2) __syncthreads();                            /* the staging rows become the contrast map */
+				if (it == 2 && SRC != 2) __syncthreads();                /* the staging rows become the contrast map (grey bytes: there are none) */
 				const int k = t + FI_NT * (it & 1), gh = k >> 4;
 				const int rr = (it < 2 ? 17 : 1) + (k & 15), g = (gh & ~7) | ((gh & 1) << 2) | ((gh >> 1) & 3);   /* 16 lanes a group; the two groups of a half-wavefront 16 banks apart */
 				if (r0 + rr > W - 2) continue;
@@ -604,7 +661,7 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 			FI_TICK(6); FI_STAMP(6);
 			FI_DUMP(1, ybuf + FI_YRS, 1);
 		}
-		if (!PRE && SRC) __syncthreads();                              /* the staging rows become rows of the horizontal pass */
+		if (!PRE && SRC == 1) __syncthreads();                         /* the staging rows become rows of the horizontal pass */
 		/* ---------------------------------------------------------------- horizontal pass (filters.c:346-386) of image rows 32b+1 .. 32b+32 (and row 0), four kx an item,
 		 * two outputs to a dword: L(k, k+1) = 6 E(k) + 2 (O(k-1) + O(k)) - (E(k-1) + E(k+1)), H(k, k+1) = 2 O(k) - (E(k) + E(k+1)) with
 		 * E(j) = (x[2j], x[2j+2]), O(j) = (x[2j+1], x[2j+3]) put together from the row's dwords (x[2j], x[2j+1]). */
@@ -745,6 +802,8 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
  * the LDS that frees holds 64 image rows of the horizontal pass instead of 32: the vertical pass makes 32 output rows a time, a column's
  * run in the transposed level-1 plane is 64 bytes (two neighbouring lanes) instead of 32, the rows kept for quality >= 22 go out as whole
  * 128-byte lines, and an image costs 34 barriers instead of 150.
+ * SRC 2: quality 22 / 23 from grey bytes, one a pixel: the luma by grey16, 128 into both 4:2:0 planes a step, no chroma
+ * slots and none of the barriers that only guard them.
  * A step takes 32 image rows, 32s+1 .. 32s+32 (row 0 comes with a step of its own before the first: s = -1), a thread two neighbouring rows
  * of a group of 16 pixels.  4:2:0: chroma row m needs image rows 2m-1, 2m, 2m+1 = a thread's two rows and the first row of the thread below;
  * the first rows go through LDS, the last thread's pair waits there for the next step.
@@ -780,11 +839,11 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 	int16_t *const hbuf = reinterpret_cast<int16_t *>(lds);
 	uint8_t *const stg = lds + FP_STG_OFF;
 	const int t0 = threadIdx.x, img = blockIdx.x;
-	const uint8_t *const src = (const uint8_t *)srcb + (size_t)img * (SRC ? (size_t)(W * W * 3) : src_stride);
+	const uint8_t *const src = (const uint8_t *)srcb + (size_t)img * (SRC == 2 ? (size_t)(W * W) : SRC ? (size_t)(W * W * 3) : src_stride);
 	int16_t *const proc = procb + (size_t)img * plane_stride, *const jpeg = jpegb + (size_t)img * plane_stride;
 	int16_t *const ll1 = ll1b + (size_t)img * ll1_stride;
 
-	constexpr int NPF = SRC ? 6 : 4;
+	constexpr int NPF = SRC == 2 ? 2 : SRC ? 6 : 4;
 	uint4 pf[NPF];
 	auto issue = [&](int s) {                                       /* image rows 32s+1+2j, 32s+2+2j of the thread's group of 16 pixels */
 		const int t = opaque(t0), g = t & 31, j = t >> 5;
@@ -793,11 +852,12 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 		for (int h = 0; h < 2; h++) {
 			int row = 32 * s + 1 + 2 * j + h;
 			row = row < 0 ? 0 : row > W - 1 ? W - 1 : row;
-			rp[h] = SRC ? reinterpret_cast<const uint4 *>(src + (size_t)row * (W * 3) + 48 * g) : reinterpret_cast<const uint4 *>(reinterpret_cast<const int16_t *>(src) + (size_t)row * W + 16 * g);
+			rp[h] = SRC == 2 ? reinterpret_cast<const uint4 *>(src + (size_t)row * W + 16 * g) : SRC ? reinterpret_cast<const uint4 *>(src + (size_t)row * (W * 3) + 48 * g) : reinterpret_cast<const uint4 *>(reinterpret_cast<const int16_t *>(src) + (size_t)row * W + 16 * g);
 		}
 #pragma unroll
 		for (int h = 0; h < 2; h++) {
-			if (SRC) { pf[3 * h] = rp[h][0]; pf[3 * h + 1] = rp[h][1]; pf[3 * h + 2] = rp[h][2]; }
+			if (SRC == 2) pf[h] = rp[h][0];
+			else if (SRC) { pf[3 * h] = rp[h][0]; pf[3 * h + 1] = rp[h][1]; pf[3 * h + 2] = rp[h][2]; }
 			else { pf[2 * h] = rp[h][0]; pf[2 * h + 1] = rp[h][1]; }
 		}
 	};
@@ -814,7 +874,8 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 				const bool live = row >= 0 && row < W;
 				uint32_t X[10], uw[4] = { 0, 0, 0, 0 }, vw[4] = { 0, 0, 0, 0 };
 				if (live) {
-					if (SRC) {
+					if (SRC == 2) grey16<FAMILY>(pf[h], __float_as_uint(yq), X + 1);
+					else if (SRC) {
 						const uint32_t wv[12] = { pf[3 * h].x, pf[3 * h].y, pf[3 * h].z, pf[3 * h].w, pf[3 * h + 1].x, pf[3 * h + 1].y, pf[3 * h + 1].z, pf[3 * h + 1].w,
 						                          pf[3 * h + 2].x, pf[3 * h + 2].y, pf[3 * h + 2].z, pf[3 * h + 2].w };
 						convert16<FAMILY>(wv, yq, X + 1, uw, vw, true);
@@ -830,7 +891,7 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 				X[9] = (uint32_t)__shfl_down((int)X[1], 1);
 				if (g == 0) X[0] = __builtin_amdgcn_perm(X[1], X[2], 0x07060100u);
 				if (g == 31) X[9] = X[8];
-				if (SRC) {
+				if (SRC == 1) {
 					uint32_t lu = (uint32_t)__shfl_up((int)uw[3], 1), lv = (uint32_t)__shfl_up((int)vw[3], 1);
 					if (g == 0) { lu = uw[0] << 16; lv = vw[0] << 16; }
 					cu[h] = chroma_h8(uw, lu); cv[h] = chroma_h8(vw, lv);
@@ -843,7 +904,7 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 					*reinterpret_cast<uint4 *>(hr + H) = make_uint4(Hh[0], Hh[1], Hh[2], Hh[3]);
 				}
 			}
-			if (SRC) {
+			if (SRC == 1) {
 				/* slot of a first row: thread j - 1 finds it; the last thread leaves both its rows for the next step (two pairs, taken in turns) */
 				if (j) { *reinterpret_cast<uint2 *>(stg + (j - 1) * 512 + 8 * g) = cu[0]; *reinterpret_cast<uint2 *>(stg + (j - 1) * 512 + 256 + 8 * g) = cv[0]; }
 				if (j == 15) {
@@ -853,9 +914,10 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 				}
 			}
 		}
-		if (SRC || (s & 1)) __syncthreads();
+		if (SRC == 1 || (s & 1)) __syncthreads();
 		if (s + 1 < W / 32) issue(s + 1);
-		if (SRC && s >= 0) {
+		if (SRC == 2 && s >= 0) grey_chroma_fill(pub, pvb, (size_t)img * c_stride, s, opaque(t0));
+		if (SRC == 1 && s >= 0) {
 			/* 4:2:0 (colorspace.c:241-256): chroma row m = 16s+1+j from the thread's rows 2m-1, 2m and the first row of the thread below; the first
 			 * thread also makes row 16s, which waited for its third row (row 0: (r0 + r1 + 1) >> 1 of image rows 0 and 1) */
 			const int t = opaque(t0), g = t & 31, j = t >> 5, m = 16 * s + 1 + j;
@@ -950,7 +1012,7 @@ __global__ __launch_bounds__(FI_NT) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 			__syncthreads();
 #pragma unroll
 			for (int e = 0; e < 3; e++) { const int k = t + FI_NT * e; if (k < 5 * (FP_RS / 2)) reinterpret_cast<uint32_t *>(hbuf)[k] = hold[e]; }
-		} else if (SRC) __syncthreads();                               /* the chroma slots are free for the next step */
+		} else if (SRC == 1) __syncthreads();                          /* the chroma slots are free for the next step */
 	}
 }
 

@@ -60,6 +60,7 @@ template <typename F> inline void nhw_slices(int nslices, F &&launch)
 /* ------------------------------------------------------------------------------------------------ launchers */
 /* nhw_front.hip */
 void nhw_launch_color(const uint8_t *bgr, int n, int q, Plane<int16_t> y, Plane<uint8_t> u, Plane<uint8_t> v, hipStream_t s);
+void nhw_launch_color_grey(const uint8_t *grey, int n, int q, Plane<int16_t> y, Plane<uint8_t> u, Plane<uint8_t> v, hipStream_t s);   /* the same from grey bytes, one a pixel */
 /* One whole-block analysis level (size 256 or 128) of n images: NhwAnalysis{ jpeg, proc, n, row stride, size, final_level }, the optionals by name.
  * save: a second destination for what the reference copies right behind the transform; src8: the block comes as bytes (a 4:2:0 plane);
  * alt: it is read from another int16 plane.  NO_T: the transposed first-direction plane is not stored; NO_T_LL_SAVED: nor need the LL
@@ -81,6 +82,7 @@ void nhw_launch_synth(uint8_t *bgr, int n, uint32_t seed_base, hipStream_t s);
 struct NhwFront {                           /* the front launch group of n images: the forms and the members are described at nhw_launch_front_fused */
 	const uint8_t *bgr = nullptr; Plane<uint8_t> pu = {}, pv = {}, st = {}; Plane<const int16_t> y = {};
 	Plane<int16_t> proc = {}, jpeg = {}, ll1 = {}, keep = {}; int q = 0, with_prefilter = 0, n = 0, switches = 0;
+	bool grey = false;                       /* bgr holds grey pictures, 512 x 512 bytes each */
 };
 void nhw_launch_front_fused(const NhwFront &f, hipStream_t s);
 void nhw_launch_front_stale(Plane<const int16_t> y, Plane<const uint8_t> st, Plane<uint8_t> stale, int n, hipStream_t s);
@@ -117,6 +119,7 @@ void nhw_launch_fit_compact(const uint8_t *open, const int *idx, int m, int *nex
 hipError_t nhw_launch_sse(const uint8_t *a, const uint8_t *b, int n, uint64_t *sse, hipStream_t s);
 /* nhw_picture.hip: pictures of any size, the .nhwp container */
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s);
+hipError_t nhw_launch_tile_pad_grey(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s);   /* [H][W] pictures, tiles of 512 x 512 bytes */
 hipError_t nhw_launch_untile_crop(const uint8_t *d_tiles, const nhw_picture *d_pics, int n_pics, int tile0, int m, int scale /* 1, 2, 4: tiles of side 512 / scale, the table holds the scaled pictures */, hipStream_t s);
 hipError_t nhw_launch_untile_region(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, int tile0, int m, hipStream_t s);
 hipError_t nhw_launch_untile_window(const uint8_t *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses /* the launch's own range of the use table */, int n_uses, int tile0, int m, int scale, hipStream_t s);

@@ -84,41 +84,42 @@ __device__ __forceinline__ bool tile_of(const P *pics, int n, int tile0, TileRef
 	return true;
 }
 
-/* padded word w of padded row rr of the tile: 16 bytes of picture row min(512 ty + rr, H - 1) from byte column 1536 tx + 16 w on.
- * EDGE: the tile reaches column 3W, so a word may cross it or lie beyond it; those bytes repeat the row's last pixel (a 3-byte period). */
-template <bool EDGE>
+/* padded word w of padded row rr of the tile: 16 bytes of picture row min(512 ty + rr, H - 1) from byte column 512 C tx + 16 w on, C bytes a
+ * pixel: 3, or 1 for the grey pictures of DESIGN.md section 27.  EDGE: the tile reaches column C W, so a word may cross it or lie beyond it;
+ * those bytes repeat the row's last pixel (a C-byte period). */
+template <bool EDGE, int C = 3>
 __device__ __forceinline__ uint4 pad_word(const TileRef &r, int rr, int w)
 {
 	const uint32_t row = 512 * r.ty + rr < r.p.height ? 512 * r.ty + rr : r.p.height - 1;
 	const uintptr_t R = (uintptr_t)(r.p.addr + (uint64_t)row * r.p.pitch);
-	const int rb = 3 * (int)r.p.width, b0 = 1536 * (int)r.tx + 16 * w, nin = rb - b0;
+	const int rb = C * (int)r.p.width, b0 = 512 * C * (int)r.tx + 16 * w, nin = rb - b0;
 	if (!EDGE || nin >= 16) return fetch(R + b0, 0, 16);
 	uint4 v = nin > 0 ? fetch(R + b0, 0, nin) : make_uint4(0, 0, 0, 0);
-	const uint32_t px = fetch(R + rb - 3, 0, 3).x;                     /* B, G, R of the last pixel */
-	const int r0 = b0 % 3;                                             /* padded column b0 + j holds component (r0 + j) % 3 */
+	const uint32_t px = fetch(R + rb - C, 0, C).x;                     /* B, G, R of the last pixel (C = 1: its byte) */
+	const int r0 = b0 % C;                                             /* padded column b0 + j holds component (r0 + j) % C */
 	uint32_t o[4] = { v.x, v.y, v.z, v.w };
 #pragma unroll
 	for (int j = 0; j < 16; j++) {
-		int c = r0 + j % 3;
-		c -= c >= 3 ? 3 : 0;
+		int c = r0 + j % C;
+		c -= c >= C ? C : 0;
 		const uint32_t byte = (px >> (8 * c)) & 0xFF, sh = 8 * (j & 3);
 		if (j >= nin) o[j >> 2] = (o[j >> 2] & ~(0xFFu << sh)) | (byte << sh);
 	}
 	return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-template <bool EDGE>
+template <bool EDGE, int C = 3>
 __device__ __forceinline__ void pad_band(const TileRef &r, uint4 *__restrict__ dst, int band)
 {
-	constexpr int WORDS = TP_ROWS * TP_WORDS, PER = WORDS / TP_THREADS, GROUP = 4;
-	static_assert(WORDS % TP_THREADS == 0 && PER % GROUP == 0, "band layout");
+	constexpr int ROW_WORDS = C * 512 / 16, WORDS = TP_ROWS * ROW_WORDS, PER = WORDS / TP_THREADS, GROUP = 4;
+	static_assert(ROW_WORDS * 3 == TP_WORDS * C && WORDS % TP_THREADS == 0 && PER % GROUP == 0, "band layout");
 #pragma unroll
 	for (int g = 0; g < PER; g += GROUP) {
 		uint4 v[GROUP];
 #pragma unroll
 		for (int k = 0; k < GROUP; k++) {
 			const int i = (g + k) * TP_THREADS + threadIdx.x;
-			v[k] = pad_word<EDGE>(r, band * TP_ROWS + i / TP_WORDS, i % TP_WORDS);
+			v[k] = pad_word<EDGE, C>(r, band * TP_ROWS + i / ROW_WORDS, i % ROW_WORDS);
 		}
 #pragma unroll
 		for (int k = 0; k < GROUP; k++) dst[(g + k) * TP_THREADS + threadIdx.x] = v[k];
@@ -133,6 +134,17 @@ __global__ __launch_bounds__(TP_THREADS) void k_tile_pad(const nhw_picture *__re
 	uint4 *dst = reinterpret_cast<uint4 *>(tiles + (size_t)(blockIdx.x / TP_BANDS) * NHW_IMG_BYTES) + band * TP_ROWS * TP_WORDS;
 	if (1536 * (r.tx + 1) <= 3 * r.p.width) pad_band<false>(r, dst, band);   /* an interior tile column: never the replication path */
 	else pad_band<true>(r, dst, band);
+}
+
+/* the same at one byte a pixel: [H][W] pictures into tiles of 512 x 512 bytes, the same grid and the same aligned access */
+__global__ __launch_bounds__(TP_THREADS) void k_tile_pad_grey(const nhw_picture *__restrict__ pics, int n_pics, int tile0, uint8_t *__restrict__ tiles)
+{
+	TileRef r;
+	if (!tile_of(pics, n_pics, tile0, r)) return;
+	const int band = blockIdx.x % TP_BANDS;
+	uint4 *dst = reinterpret_cast<uint4 *>(tiles + (size_t)(blockIdx.x / TP_BANDS) * (512 * 512)) + band * TP_ROWS * (512 / 16);
+	if (512 * (r.tx + 1) <= r.p.width) pad_band<false, 1>(r, dst, band);
+	else pad_band<true, 1>(r, dst, band);
 }
 
 /* the bytes [j, e) of v to the 16-byte-aligned destination word A, each store inside them: dwords where a whole one is covered, else
@@ -408,6 +420,23 @@ __global__ __launch_bounds__(TB_THREADS) void k_tensor_to_bytes(const uint8_t *_
 	nhw_store_words<3, 3>(bgr + img * NHW_IMG_BYTES + ((size_t)r * 512 + 4 * q) * 3, w);
 }
 
+/* The one-channel form: n contiguous [512][512] tensors -- [n, 1, 512, 512] and [n, 512, 512, 1] are the same memory -- to
+ * grey pictures of 512 x 512 bytes under scale[0] and bias[0].  The same grid and the same 4 pixels a thread: one load of 16, 8 or 4 bytes, one
+ * dword store. */
+template <int DT>
+__global__ __launch_bounds__(TB_THREADS) void k_tensor_to_bytes_grey(const uint8_t *__restrict__ in, NhwTensorArgs a, uint8_t *__restrict__ grey)
+{
+	constexpr int EB = NhwElem<DT>::bytes;
+	const size_t img = blockIdx.x / (TB_QUADS / TB_THREADS);
+	const int i = (blockIdx.x % (TB_QUADS / TB_THREADS)) * TB_THREADS + threadIdx.x, r = i >> 7, q = i & 127;
+	const int rr = a.flip ? 511 - r : r;
+	uint32_t d[EB], w = 0;
+	nhw_load_words<4 * EB, 4 * EB>(in + (img * (512 * 512) + (size_t)rr * 512 + 4 * q) * EB, d);
+#pragma unroll
+	for (int px = 0; px < 4; px++) w |= nhw_tensor_byte<DT>(nhw_unpack_elem<DT>(d, px), a.scale[0], a.bias[0]) << (8 * px);
+	*reinterpret_cast<uint32_t *>(grey + img * (512 * 512) + (size_t)r * 512 + 4 * q) = w;
+}
+
 /* k_tile_pad for tensor pictures: the same grid (tiles x bands of TP_ROWS rows), a thread 4 pixels of a tile row at a time and one 12-byte store,
  * contiguous across the wavefront.  Tile pixel (rr, cc) of tile (ty, tx) is byte-picture pixel (min(512 ty + rr, H - 1), min(512 tx + cc, W - 1));
  * the row flip comes after the clamp of the row, so the replication acts in byte-picture coordinates.  EDGE false (an interior tile column: all
@@ -463,6 +492,15 @@ hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int la
 	return hipGetLastError();
 }
 
+hipError_t nhw_launch_tensor_to_bytes_grey(const void *d_in, int n, int dtype, const NhwTensorArgs &a, uint8_t *d_grey, hipStream_t s)
+{
+	nhw_with_grey_store(dtype, NhwGreyArgs{}, [&](auto st) {
+		constexpr int DT = decltype(st)::dtype;
+		k_tensor_to_bytes_grey<DT><<<n * (TB_QUADS / TB_THREADS), TB_THREADS, 0, s>>>((const uint8_t *)d_in, a, d_grey);
+	});
+	return hipGetLastError();
+}
+
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s)
 {
 	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
@@ -485,6 +523,12 @@ hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int
 hipError_t nhw_launch_tile_pad(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
 {
 	k_tile_pad<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_pics, n_pics, tile0, d_tiles);
+	return hipGetLastError();
+}
+
+hipError_t nhw_launch_tile_pad_grey(const nhw_picture *d_pics, int n_pics, int tile0, int m, uint8_t *d_tiles, hipStream_t s)
+{
+	k_tile_pad_grey<<<m * TP_BANDS, TP_THREADS, 0, s>>>(d_pics, n_pics, tile0, d_tiles);
 	return hipGetLastError();
 }
 

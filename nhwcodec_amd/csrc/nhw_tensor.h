@@ -339,5 +339,7 @@ hipError_t nhw_launch_tone_from_hist(const uint32_t *d_hist, int n, int channels
 /* nhw_picture.hip again, the encoder's side: n 512 x 512 tensors to the byte path's pictures; the tiles [tile0, tile0 + m) of tensor pictures of any size */
 hipError_t nhw_launch_tensor_to_bytes(const void *d_in, int n, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_bgr, hipStream_t s);
 hipError_t nhw_launch_tile_pad_tensor(const nhw_tensor_picture *d_pics, int n_pics, int tile0, int m, int dtype, int layout, const NhwTensorArgs &a, uint8_t *d_tiles, hipStream_t s);
+/* the one-channel form (section 27): n [512][512] tensors to grey pictures of 512 x 512 bytes under scale[0] and bias[0] */
+hipError_t nhw_launch_tensor_to_bytes_grey(const void *d_in, int n, int dtype, const NhwTensorArgs &a, uint8_t *d_grey, hipStream_t s);
 
 #endif

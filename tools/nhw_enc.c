@@ -62,8 +62,9 @@ static void usage(void)
 	        "Budget (MI355X build): %s [-q#] --max-bytes <n> [--min-quality <m>] ...   (single file, --batch, --tiles: the highest quality from -q# down to m whose file fits n bytes)\n"
 	        "PSNR (MI355X build): %s [-q#] --min-psnr <dB> [--min-quality <m>] ...   (single file, --batch, --tiles: the lowest quality from m up to -q# whose decoded picture reaches dB)\n"
 	        "Picture (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp>   (any size: padded 512x512 tiles and the real size in one container)\n"
-	        "Resize (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp> --resize <W>x<H>   (the picture resized to W x H, 1..4096 each, by the area filter first)\n",
-	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
+	        "Resize (MI355X build): %s [-q#] --picture <in.bmp> <out.nhwp> --resize <W>x<H>   (the picture resized to W x H, 1..4096 each, by the area filter first)\n"
+	        "Grey  (MI355X build): %s [-q#] --grey <in.pgm> <out.nhw>   (a binary PGM, P5, 512x512, maxval 255, rows top-down: the file of the picture with every grey in B, G and R; the mirror of nhw-dec --grey)\n",
+	        PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM, PROGRAM);
 }
 
 static void version(void)
@@ -115,6 +116,29 @@ static void load_bmp(const char *path, uint8_t *dst)
 		}
 		free(tmp);
 	}
+}
+
+/* a binary PGM (P5, 512 x 512, maxval 255; comments allowed in the header) into dst[262144], rows in the byte path's order: the PGM's rows are
+ * top-down, as nhw-dec --grey writes them, so PGM row r is row 511 - r.  0, or 1 with a message */
+static int load_pgm(const char *path, uint8_t *dst)
+{
+	FILE *f = fopen(path, "rb");
+	int v[3], k = 0, c, r;
+	if (!f) { printf("menu(): Could not open file: %s\n", path); return 1; }
+	if (fgetc(f) != 'P' || fgetc(f) != '5') { fclose(f); fprintf(stderr, "%s: %s is not a binary PGM (P5)\n", PROGRAM, path); return 1; }
+	while (k < 3) {
+		c = fgetc(f);
+		if (c == '#') { while (c != '\n' && c != EOF) c = fgetc(f); continue; }
+		if (c == ' ' || c == '\t' || c == '\n' || c == '\r') continue;
+		if (c < '0' || c > '9') { fclose(f); fprintf(stderr, "%s: %s: bad PGM header\n", PROGRAM, path); return 1; }
+		for (v[k] = 0; c >= '0' && c <= '9' && v[k] < 100000; c = fgetc(f)) v[k] = 10 * v[k] + (c - '0');
+		k++;                                                             /* c: the one white-space byte behind the number */
+	}
+	if (v[0] != 512 || v[1] != 512 || v[2] != 255) { fclose(f); fprintf(stderr, "%s: %s: --grey wants a 512 x 512 PGM of maxval 255, got %d x %d, maxval %d\n", PROGRAM, path, v[0], v[1], v[2]); return 1; }
+	for (r = 0; r < 512; r++)
+		if (fread(dst + (size_t)(511 - r) * 512, 1, 512, f) < 512) { fclose(f); fprintf(stderr, "%s: %s: the PGM ends before its 262144 bytes\n", PROGRAM, path); return 1; }
+	fclose(f);
+	return 0;
 }
 
 static int write_file(const char *path, const uint8_t *p, size_t n)
@@ -518,7 +542,7 @@ int main(int argc, char **argv)
 	int devlist[16], ndevlist = 0;
 	uint32_t seed = 0;
 	const char *batch_dir = NULL, *outdir = NULL;
-	int tiles = 0, tar = 0, picture = 0;
+	int tiles = 0, tar = 0, picture = 0, grey = 0;
 	int stock_compat = 0;   /* --stock-compat: NHW_COMPAT_GLIBC_ONESHOT, the stock binary's out-of-bounds reads (include/nhw_hip.h) */
 	const char *max_bytes_arg = NULL, *min_quality_arg = NULL;   /* --max-bytes, --min-quality, --min-psnr: checked once the flags are read */
 	const char *min_psnr_arg = NULL;
@@ -570,6 +594,7 @@ int main(int argc, char **argv)
 		if (!strcmp(argv[1], "--tiles")) { tiles = 1; argc -= 1; argv += 1; continue; }
 		if (!strcmp(argv[1], "--tar")) { tar = 1; argc -= 1; argv += 1; continue; }
 		if (!strcmp(argv[1], "--picture")) { picture = 1; argc -= 1; argv += 1; continue; }
+		if (!strcmp(argv[1], "--grey")) { grey = 1; argc -= 1; argv += 1; continue; }
 		for (i = 1; argv[1][i] != '\0'; i++) {
 			const char ch = argv[1][i];
 			if (ch >= '0' && ch <= '9') continue;
@@ -592,6 +617,10 @@ int main(int argc, char **argv)
 	if (!nhw_quality_supported(quality)) {
 		fprintf(stderr, "%s: quality %d is not implemented (supported: 1..23; the reference accepts -q0 but has no tables for it)\n", PROGRAM, quality);
 		return 3;
+	}
+	if (grey && (max_bytes_arg || min_psnr_arg || min_quality_arg || resize_arg || synthetic > 0 || tar || tiles || batch_dir || picture)) {   /* before any file is touched */
+		fprintf(stderr, "%s: --grey works alone, not with --batch, --synthetic, --tar, --tiles, --picture, --max-bytes, --min-psnr, --min-quality or --resize\n", PROGRAM);
+		return 1;
 	}
 	if (picture && (max_bytes_arg || min_psnr_arg || min_quality_arg || synthetic > 0 || tar || tiles || batch_dir)) {   /* before any GPU work */
 		fprintf(stderr, "%s: --picture works alone, not with --max-bytes, --min-psnr, --min-quality, --synthetic, --tar, --tiles or --batch\n", PROGRAM);
@@ -681,6 +710,21 @@ int main(int argc, char **argv)
 	}
 
 	if (argc < 3) { printf("Not enough arguments. Check help.\n"); usage(); return 0; }
+	if (grey) {
+		uint8_t *px = (uint8_t *)malloc(NHW_GREY_BYTES), *arena = (uint8_t *)malloc(NHW_OUT_STRIDE);
+		uint64_t off[2];
+		int32_t st = 0;
+		int bad;
+		if (strcmp(argv[1], argv[2]) == 0) { fprintf(stdout, "Input and output are the same file: '%s'.\n", argv[1]); return 1; }
+		if (load_pgm(argv[1], px)) return 1;
+		if ((rc = nhw_enc_create(0, 1, &enc))) die_lib("nhw_enc_create", rc);
+		if (stock_compat) nhw_enc_set_compat(enc, NHW_COMPAT_GLIBC_ONESHOT);
+		if ((rc = nhw_enc_batch_grey(enc, px, 1, quality, arena, NHW_OUT_STRIDE, off, &st))) die_lib("nhw_enc_batch_grey", rc);
+		bad = emit(argv[2], st, -1, 0, arena + off[0], (size_t)(off[1] - off[0]));
+		nhw_enc_destroy(enc);
+		free(px); free(arena);
+		return bad ? 1 : 0;
+	}
 	if (tar) return encode_tar(argv[1], argv[2], quality, stock_compat);
 	if (picture) return encode_picture(argv[1], argv[2], quality, stock_compat, resize_w, resize_h);
 	if (tiles) {
