@@ -812,6 +812,36 @@ int nhw_tile_pictures_grey_device(const nhw_picture *d_pics, int n_pics, int til
 int nhw_enc_pictures_grey(nhw_enc *e, const uint8_t *grey, const uint64_t *in_off, const uint32_t *width, const uint32_t *height, int n,
                           int quality, uint8_t *out_arena, size_t arena_cap, uint64_t *out_off, int32_t *status);
 
+/* ---- per-sample flip, colour map and tone table in the full-file decode ----
+ * The operations of sections 18, 24 and 25 -- the mirror, the 3 x 4 colour map, the 256-entry tone table -- in the last store of
+ * nhw_dec_batch_device_tensor and nhw_dec_batch_device_grey: a batch of native .nhw files goes to augmented training tensors without a pass over
+ * the bytes.
+ * The rule (the whole specification).  Two inputs are defined first.  Colour form: the bytes B, G, R of a pixel of the plain decode at scale s (1, 2
+ * or 4; S = 512 / s), as the byte path (nhw_dec_batch_device_scaled) stores them.  Grey form: the grey byte of section 22, the luma after the file's
+ * grey table.  File i of a batch has a flag byte d_flags[i], a colour map d_maps[i] and a tone table d_tones[i]; each of the three tables may be
+ * absent (NULL) for the whole call, and an absent table's step is skipped.  The output pixel at byte-path row r, column c is made in this order:
+ *   1. mirror      take the pixel at column c' = S - 1 - c where bit 0 of d_flags[i] is set, else at column c.  Rows are not touched: the format's
+ *                  `rows` keeps its meaning and is independent of the flag.  The other bits of the flag byte are ignored.
+ *   2. colour map  nhw_colour_apply<3>(d_maps[i], b), the rule of section 24 on the three bytes; grey: nhw_colour_apply<1>, m[0][0] and o[0] alone.
+ *   3. tone table  nhw_tone_apply<3>(d_tones[i].t, b), z_i = t[i][y_i] (section 25); grey: nhw_tone_apply<1>, row 0 alone.
+ *   4. the value rule, channel order, layout and row rule of the nhw_tensor_format, as the plain entries apply them.
+ * This is section 26's order "resize, flip, colour, tone, blur, value rule" without the resize and the blur.
+ * A file whose map is not within the limits of section 24 (a non-zero reserved word included) stores nothing: its slot stays untouched, and its
+ * status and quality are those of the plain decode.  A refused file leaves its slot untouched, as in the plain entries.  With all three tables NULL
+ * the call is the plain call, byte for byte: it launches exactly what the plain entry launches.
+ * d_flags (n bytes), d_maps (n nhw_colour_map, 4-byte aligned) and d_tones (n nhw_tone_table, any alignment) are device tables; they are read by
+ * the last kernel, so they must stay valid until the call's work on `stream` is done.
+ * NHW_E_ARG, before anything is launched: exactly the cases of the plain entry, in its order; nothing is refused for the tables, which live on the
+ * device.  Unlike the plain tensor entry, the byte format (NHW_T_U8 / NHW_T_HWC / NHW_T_BGR / NHW_T_ROWS_FILE) with any table present goes through
+ * the operations like every other format.  Asynchronous on `stream`; one handle serves all kinds of call in any order. */
+int nhw_dec_batch_device_tensor_ops(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                    const nhw_tensor_format *fmt, const uint8_t *d_flags, const nhw_colour_map *d_maps,
+                                    const nhw_tone_table *d_tones, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream);
+/* the same for nhw_dec_batch_device_grey: fmt of NHW_T_GREY as that entry takes it, NULL fmt = uint8 [S][S] in file order */
+int nhw_dec_batch_device_grey_ops(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                  const nhw_tensor_format *fmt, const uint8_t *d_flags, const nhw_colour_map *d_maps,
+                                  const nhw_tone_table *d_tones, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.nhw_debug_warp_row_limit.argtypes, L.nhw_debug_warp_row_limit.restype = [ctypes.c_int], None
     L.nhw_grey_table.argtypes = [ctypes.c_int, P]
     L.nhw_dec_batch_device_grey.argtypes = L.nhw_dec_batch_device_tensor.argtypes
+    a = L.nhw_dec_batch_device_tensor.argtypes                                             # the same with flags, maps and tone tables: the three tables behind the format
+    L.nhw_dec_batch_device_tensor_ops.argtypes = L.nhw_dec_batch_device_grey_ops.argtypes = a[:7] + [P, P, P] + a[7:]
     L.nhw_dec_batch_grey.argtypes = L.nhw_dec_batch_scaled.argtypes
     L.nhw_untile_windows_grey_device.argtypes = L.nhw_untile_windows_device.argtypes       # the grey calls: their colour calls' arguments
     L.nhw_resample_grey_to_tensor_device.argtypes = L.nhw_resample_to_tensor_device.argtypes
@@ -1106,6 +1108,24 @@ def _tone_arg(tones, n, what, channels=3):
     return t
 
 
+def _decode_ops(n, flips, colours, tones, what, channels=3):
+    """the per-sample tables of a full-file decode of n files, checked on the host before anything is launched ->
+    (flags, maps, tones): the flag bytes as _crop_flips makes them, the nhw_colour_map table as _colour_table does, the tone tables as
+    _tone_arg does (a CUDA tensor [n, 768] is passed on), each None where the argument is.  colours may be ONE map for all files -- a 3 x 4
+    matrix, the twelve integers of colour_fixed, for grey one pair (gain, offset) -- or n of them."""
+    import numpy as np
+    flags = _crop_flips(flips, n, what)
+    maps = None
+    if colours is not None:
+        try:
+            a = np.asarray(colours)
+        except Exception:
+            a = None
+        one = a is not None and a.dtype.kind in "iuf" and (a.shape == (2,) if channels == 1 else a.shape == (3, 4) or (a.shape == (12,) and a.dtype.kind in "iu"))
+        maps = _colour_table([colours] * n if one else colours, n, what, channels)
+    return flags, maps, _tone_arg(tones, n, what, channels) if tones is not None else None
+
+
 def _host_tones(tones, n, what, channels=3):
     """_tone_arg for the decoder's calls, whose tables are read from host memory: a tensor is no table here"""
     if hasattr(tones, "is_cuda"):
@@ -2060,41 +2080,80 @@ class Decoder:
                                                            status.data_ptr(), quality.data_ptr(), st))
         return px, status, quality
 
-    def decode_tensor_device(self, arena, offsets, lengths, fmt, scale=1, out=None):
+    def _ops_tables(self, n, flips, colours, tones, what, channels):
+        """_decode_ops' tables on this decoder's device -> the three tensors (None where the argument is); the caller keeps them until its call is
+        queued on torch's current stream, where their memory's reuse is ordered behind it"""
+        t = self.torch
+        dev = t.device("cuda", self.device)
+        flags, maps, tabs = _decode_ops(n, flips, colours, tones, what, channels)
+        return (t.from_numpy(flags).to(dev) if flags is not None else None, _device_table(maps, dev) if maps is not None else None,
+                _device_tones(tabs, dev, what) if tabs is not None else None)
+
+    def decode_tensor_device(self, arena, offsets, lengths, fmt, scale=1, out=None, flips=None, colours=None, tones=None):
         """decode_scaled_device straight into a tensor format (nhw_dec_batch_device_tensor): the last kernel stores
         fmt's element type, layout, channel order and row direction from the registers that hold the pixel, with no pass over the bytes.
         Arguments as for decode_scaled_device; fmt: a TensorFormat; out: a contiguous, 16-byte aligned tensor of fmt.dtype with at least
         n * 3 * S * S elements, S = 512 // scale.  Returns (tensor [n, 3, S, S] or [n, S, S, 3], status[n], quality[n]) on the device; a
-        refused file's slot is left untouched."""
+        refused file's slot is left untouched.
+        flips, colours, tones: the per-sample operations in the same store (nhw_dec_batch_device_tensor_ops), each None or
+        as the crop calls take it -- flips: one boolean or flag byte a file ("mirror left-right"); colours: ONE colour map for all files or one a
+        file, a 3 x 4 matrix of floats on (R, G, B, 1) as colour_matrix makes it or the twelve integers of colour_fixed; tones: one tone table a
+        file, uint8 [3, 256] on R, G, B as the tone_* builders make it, or the uint8 CUDA tensor [n, 768] of tone_from_hist_device.  The order
+        is fixed: the plain decode's pixel, mirror, colour map, tone table, then fmt's value rule, channel order, layout and rows.  All are
+        checked on the host before anything is launched; with all three None the call is the plain one."""
         what = "decode_tensor_device"
         fmt = _tensor_format(fmt, what)
         scale = _scale(scale, what)
         side = 512 // scale
+        ops = flips is not None or colours is not None or tones is not None
+        if ops and hasattr(lengths, "shape") and len(lengths.shape) == 1:   # the tables' lengths and limits before a device is looked at
+            _decode_ops(int(lengths.shape[0]), flips, colours, tones, what)
         n = self._device_files(arena, offsets, lengths, what)
         out, px, status, quality = self._device_out(out, what, fmt.dtype, (n,) + fmt.shape(side, side), 16,
                                                     f"contiguous, 16-byte aligned {fmt.dtype} tensor of n*{3 * side * side} elements")
         c = fmt.c_struct()
+        if ops:
+            tabs = self._ops_tables(n, flips, colours, tones, what, 3)
+            with _OnTorchStream(self) as st:
+                self._chk(self.lib.nhw_dec_batch_device_tensor_ops(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, ctypes.byref(c),
+                                                                   *(x.data_ptr() if x is not None else None for x in tabs),
+                                                                   out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
+            return px, status, quality
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_dec_batch_device_tensor(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale, ctypes.byref(c),
                                                            out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
         return px, status, quality
 
-    def decode_grey_device(self, arena, offsets, lengths, scale=1, fmt=None, out=None):
+    def decode_grey_device(self, arena, offsets, lengths, scale=1, fmt=None, out=None, flips=None, colours=None, tones=None):
         """decode_scaled_device as grey (nhw_dec_batch_device_grey): the luma alone, through the grey table of the
         file's quality (grey_table), one channel; the chroma planes are not decoded.  Arguments as for decode_scaled_device.  Without fmt:
         (uint8 pixels [n, S, S], rows in file order, status[n], quality[n]), S = 512 // scale.  With fmt, a TensorFormat of channels "GREY":
         (tensor [n, 1, S, S] or [n, S, S, 1] of fmt.dtype, status, quality).  out: a contiguous, 16-byte aligned tensor of that dtype with at
-        least n * S * S elements.  Status and quality are those of the colour decode; a refused file's slot is left untouched."""
+        least n * S * S elements.  Status and quality are those of the colour decode; a refused file's slot is left untouched.
+        flips, colours, tones: as for decode_tensor_device, in their one-channel forms (nhw_dec_batch_device_grey_ops) --
+        colours: ONE pair (gain, offset) for all files or one a file; tones: one table uint8 [256] a file (or the CUDA tensor [n, 768], of which
+        a file's first 256 bytes are read).  The order is fixed: the grey byte of the plain decode, mirror, map, table, then the value rule and
+        rows.  With all three None the call is the plain one."""
         what = "decode_grey_device"
         if fmt is not None:
             _tensor_format(fmt, what, grey=True)
         scale = _scale(scale, what)
         side = 512 // scale
+        ops = flips is not None or colours is not None or tones is not None
+        if ops and hasattr(lengths, "shape") and len(lengths.shape) == 1:
+            _decode_ops(int(lengths.shape[0]), flips, colours, tones, what, 1)
         n = self._device_files(arena, offsets, lengths, what)
         dtype = self.torch.uint8 if fmt is None else fmt.dtype
         out, px, status, quality = self._device_out(out, what, dtype, (n, side, side) if fmt is None else (n,) + fmt.shape(side, side), 16,
                                                     f"contiguous, 16-byte aligned {dtype} tensor of n*{side * side} elements")
         c = None if fmt is None else fmt.c_struct()
+        if ops:
+            tabs = self._ops_tables(n, flips, colours, tones, what, 1)
+            with _OnTorchStream(self) as st:
+                self._chk(self.lib.nhw_dec_batch_device_grey_ops(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale,
+                                                                 None if c is None else ctypes.byref(c), *(x.data_ptr() if x is not None else None for x in tabs),
+                                                                 out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))
+            return px, status, quality
         with _OnTorchStream(self) as st:
             self._chk(self.lib.nhw_dec_batch_device_grey(self.h, arena.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, scale,
                                                          None if c is None else ctypes.byref(c), out.data_ptr(), status.data_ptr(), quality.data_ptr(), st))

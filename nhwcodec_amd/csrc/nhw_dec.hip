@@ -30,6 +30,7 @@
 #include "nhw_dwt.h"
 #include "nhw_grey.h"
 #include "nhw_tensor.h"
+#include "nhw_tensor_ops.h"
 
 #define DW 512
 #define DH 256
@@ -2092,12 +2093,20 @@ __global__ void k_dec_colour_probe(const uint8_t *__restrict__ yuv, uint8_t *__r
  * parameter.  NhwStoreTensor<dtype, layout> (nhw_tensor.h) writes a tensor format: its put<S, N> takes N = 8 or 4 pixels of one row -- columns N c ..
  * of row r of file img, an S x S picture -- as the 3 N bytes the byte path stores (B, G, R a pixel), and its constants are kernel arguments.
  * StoreBytes is the byte path and only a tag: its stores stay spelled out in the kernels, and it adds no kernel argument, so that instantiation is
- * the code it was before there were formats, instruction for instruction. */
-struct StoreBytes { static constexpr bool bytes = true, grey = false; };
+ * the code it was before there were formats, instruction for instruction.
+ * A policy with `ops` (NhwStoreTensorOps, NhwStoreGreyOps: nhw_tensor_ops.h) has a `begin(img, tid, lds)` as well, which a workgroup
+ * calls once behind the status check with ST::lds bytes of LDS of the policy's own: it reads the file's flag, colour map and tone table, and says whether
+ * the workgroup stores anything.  The policies without it have no such call and no such bytes: their kernels are what they were. */
+struct StoreBytes { static constexpr bool bytes = true, grey = false, ops = false; static constexpr int lds = 0; };
 /* NhwStoreGrey<dtype> (nhw_tensor.h) makes either kernel its grey form: the luma phases as they are, nothing of the chroma
  * loaded or computed, the luma bytes through the grey table of the file's quality (nhw_grey.h; the identity from quality 20 on, where the table is
  * not even built) and one channel stored.  The 256 threads of a workgroup make the 256 entries in LDS, one each. */
 DEV void grey_table_fill(uint8_t *tab, int q, int tid) { if (q < 20) tab[tid] = (uint8_t)nhw_grey_value(q, tid); }
+/* the quality grey4 is to see under store policy st: the file's, or with a map or a tone table folded into the table one that has the table read */
+template <class ST> DEV int grey_q(const ST &st, int q)
+{
+	if constexpr (ST::ops) return st.lut(q) ? 0 : q; else return q;
+}
 /* four luma bytes -> their grey bytes */
 DEV uint32_t grey4(const uint8_t *tab, int q, uint32_t y4)
 {
@@ -2151,10 +2160,12 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 	}
 	const DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (m->status) return;
+	if constexpr (ST::ops) if (!st.begin(img, tid, fl + (ST::grey ? F_GREY_LDS_BYTES : F_LDS_BYTES))) return;   /* (uniform; a tone table staged here is read behind the barriers below) */
 	const int q = m->q, r0 = FR * band, m0 = r0 / 2 - 1;                       /* m0: first m of the band (-1 in band 0: skipped) */
 	const int16_t *A = plane_a(ws, img), *L1 = plane_l1(ws, img);              /* the detail bands; the level-1 LL */
 
-	if constexpr (ST::grey) grey_table_fill(crow, q, tid);                      /* (read behind the barriers of the luma phases) */
+	if constexpr (ST::grey && ST::ops) st.table(crow, img, q, tid);             /* the table with map and tone table folded in */
+	else if constexpr (ST::grey) grey_table_fill(crow, q, tid);                 /* (read behind the barriers of the luma phases) */
 	else for (int k = tid; k < 2 * (FR / 2 + 1) * (DH / 16); k += 256) {
 		const int pl = k / ((FR / 2 + 1) * (DH / 16)), rem = k % ((FR / 2 + 1) * (DH / 16)), rr = rem / (DH / 16), o = rem % (DH / 16);
 		const int src = r0 / 2 + rr < DH ? r0 / 2 + rr : DH - 1;
@@ -2299,7 +2310,7 @@ __global__ __launch_bounds__(256) void k_dec_final(DecWs ws, uint8_t *out, int d
 		for (int it = 0; it < FR / 8; it++) {
 			const int lr = 8 * it + (tid >> 5), r = r0 + lr;
 			const uint4 y16 = *reinterpret_cast<const uint4 *>(ybuf + lr * DW + 16 * t16);
-			const uint32_t w[4] = { grey4(crow, q, y16.x), grey4(crow, q, y16.y), grey4(crow, q, y16.z), grey4(crow, q, y16.w) };
+			const uint32_t w[4] = { grey4(crow, grey_q(st, q), y16.x), grey4(crow, grey_q(st, q), y16.y), grey4(crow, grey_q(st, q), y16.z), grey4(crow, grey_q(st, q), y16.w) };
 			st.template put<DW, 16>(out, img, r, t16, w);
 		}
 	}
@@ -2385,15 +2396,18 @@ template <int S, class ST = StoreBytes, class... Fmt /* as for k_dec_final */> _
 	static_assert(S == 2 || S == 4, "half or quarter scale");
 	constexpr int T = DW / S, NB = T / SC_ROWS, TPR = T / 8, YP = T + 4;   /* tile side, bands a file, threads a row; LDS pitch of a luma row (S = 4): a band's four pieces of a line on different banks */
 	constexpr int YB = S == 4 ? SC_ROWS * YP : 16;
-	__shared__ __attribute__((aligned(16))) uint8_t ybuf[YB + (ST::grey ? 256 : 0)];
-	uint8_t *gtab = ybuf + YB;                                           /* the grey form: its table, [256] */
+	__shared__ __attribute__((aligned(16))) uint8_t ybuf[YB + (ST::grey ? 256 : 0) + ST::lds];
+	uint8_t *gtab = ybuf + YB;                                           /* the grey form: its table, [256]; a policy's own bytes (ST::lds) lie behind */
 	const int tid = threadIdx.x;
 	int img = blockIdx.x / NB, r0 = (blockIdx.x % NB) * SC_ROWS;
 	if constexpr (ST::grey) if (st.a.slice >= 0) { img = blockIdx.x; r0 = st.a.slice * SC_ROWS; }   /* a forced slice order (nhw_host.h): every file's band `slice` */
 	const DecMeta *m = ws.buf<DecMeta>(D_META, img);
 	if (m->status) return;
 	const int q = m->q;
-	if constexpr (ST::grey) { grey_table_fill(gtab, q, tid); if (S != 4) __syncthreads(); }   /* (S = 4: the barrier behind the turn) */
+	if constexpr (ST::ops) if (!st.begin(img, tid, gtab + (ST::grey ? 256 : 0))) return;   /* (uniform) */
+	if constexpr (ST::grey && ST::ops) { st.table(gtab, img, q, tid); if (S != 4) __syncthreads(); }
+	else if constexpr (ST::grey) { grey_table_fill(gtab, q, tid); if (S != 4) __syncthreads(); }   /* (S = 4: the barrier behind the turn) */
+	else if constexpr (ST::lds > 0) { if (S != 4) __syncthreads(); }       /* a tone table staged by begin: the one barrier the half-scale colour form has */
 	if (S == 4) {
 		const int16_t *A = plane_a(ws, img);
 		const int g = tid & 3;
@@ -2415,7 +2429,7 @@ template <int S, class ST = StoreBytes, class... Fmt /* as for k_dec_final */> _
 			y8 = make_uint2(yw[0], yw[1]);
 		}
 		if constexpr (ST::grey) {                                      /* no chroma: the luma through the table, one channel out */
-			const uint32_t g[2] = { grey4(gtab, q, y8.x), grey4(gtab, q, y8.y) };
+			const uint32_t g[2] = { grey4(gtab, grey_q(st, q), y8.x), grey4(gtab, grey_q(st, q), y8.y) };
 			st.template put<T, 8>(out, img, r, c8, g);
 			continue;
 		}
@@ -2558,7 +2572,10 @@ extern "C" int nhw_dec_debug_read(nhw_dec *d, int what, int img, void *dst, size
  * What the last kernel stores: the byte path's pixels, a checked tensor format other than those, or a checked grey
  * format (section 22) -- the kind and that kind's arguments. */
 enum { STORE_BYTES, STORE_TENSOR, STORE_GREY };
-struct DecStore { int kind, dtype, layout; NhwTensorArgs t; NhwGreyArgs g; };
+struct DecStore {
+	int kind, dtype, layout; NhwTensorArgs t; NhwGreyArgs g;
+	bool has_ops; NhwOpsArgs ops;                                 /* section 28: the call has at least one of the three tables (then the kind is never STORE_BYTES) */
+};
 /* f(the store policy object): StoreBytes{}, NhwStoreTensor<...>{ t } or NhwStoreGrey<...>{ g with `slice` } */
 template <class F> static void dec_with_store(const DecStore &o, int slice, F &&f)
 {
@@ -2600,17 +2617,45 @@ static void launch_last(const DecWs &ws, int n, int scale, const DecStore &o, ui
 	});
 }
 
+/* The same three launchers for a call with the per-sample tables: f(NhwStoreTensorOps<...>{ t, ops }) or f(NhwStoreGreyOps<...>{ g
+ * with `slice`, ops }), the same grids and slices, the policy's two arguments, and the policy's LDS behind the kernel's.  They are functions of their
+ * own, behind the plain ones, so that those -- and the order in which the compiler meets the plain kernels -- stay what they were. */
+template <class F> static void dec_with_ops_store(const DecStore &o, int slice, F &&f)
+{
+	if (o.kind == STORE_GREY) { NhwGreyArgs a = o.g; a.slice = slice; nhw_with_grey_ops_store(o.dtype, a, o.ops, f); }
+	else nhw_with_tensor_ops_store(o.dtype, o.layout, o.t, o.ops, f);
+}
+template <int S> static void launch_scaled_ops(const DecWs &ws, int n, const DecStore &o, uint8_t *out, hipStream_t s)
+{
+	constexpr int NB = DW / S / SC_ROWS;
+	auto launch = [&](int sl) {
+		dec_with_ops_store(o, sl, [&](auto st) { k_dec_scaled<S, decltype(st)><<<sl < 0 ? NB * n : n, 256, 0, s>>>(ws, out, st.a, st.o); });
+	};
+	if (o.kind == STORE_GREY) nhw_slices(NB, launch); else launch(-1);
+}
+static void launch_last_ops(const DecWs &ws, int n, int scale, const DecStore &o, uint8_t *out, hipStream_t s)
+{
+	if (scale == 2) return launch_scaled_ops<2>(ws, n, o, out, s);
+	if (scale == 4) return launch_scaled_ops<4>(ws, n, o, out, s);
+	nhw_slices(DW / FR, [&](int sl) {
+		dec_with_ops_store(o, -1, [&](auto st) {
+			using ST = decltype(st);
+			k_dec_final<ST><<<sl < 0 ? (DW / FR) * n : n, 256, (ST::grey ? F_GREY_LDS_BYTES : F_LDS_BYTES) + ST::lds, s>>>(ws, out, 0, sl, st.a, st.o);
+		});
+	});
+}
+
 /* What the four entries refuse, in the order they always have, and the store of a call that passes.  A format's entry checks the format, then the
  * 16-byte alignment its stores need, then that the handle has no debug stop, and only then what every entry checks: the arguments, the scale, and
  * for a scaled decode the debug stop and the 8-byte alignment. */
 enum { ENTRY_BYTES, ENTRY_TENSOR, ENTRY_GREY };
 static int dec_check(int entry, const nhw_tensor_format *fmt, const nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
-                     const void *d_out, const int32_t *d_status, DecStore *o)
+                     const void *d_out, const int32_t *d_status, DecStore *o, const NhwOpsArgs &ops = {})
 {
-	*o = { STORE_BYTES, NHW_T_U8, NHW_T_HWC, {}, { 1.0f, 0.0f, 0, -1 } };
+	*o = { STORE_BYTES, NHW_T_U8, NHW_T_HWC, {}, { 1.0f, 0.0f, 0, -1 }, ops.flags || ops.maps || ops.tones, ops };
 	if (entry == ENTRY_TENSOR) {
 		if (const int rc = nhw_tensor_format_check(fmt, &o->t, nhw_dec_err)) return rc;
-		if (!nhw_tensor_format_is_bytes(fmt)) { o->kind = STORE_TENSOR; o->dtype = fmt->dtype; o->layout = fmt->layout; }
+		if (o->has_ops || !nhw_tensor_format_is_bytes(fmt)) { o->kind = STORE_TENSOR; o->dtype = fmt->dtype; o->layout = fmt->layout; }   /* (with a table the byte format is a tensor format like any other) */
 	}
 	if (entry == ENTRY_GREY) {                                      /* without a format: bytes in file order */
 		o->kind = STORE_GREY;
@@ -2634,10 +2679,10 @@ static int dec_check(int entry, const nhw_tensor_format *fmt, const nhw_dec *d, 
 
 /* one batch at scale 1 (the whole decode), 2 or 4: the steps of its plan (nhw_dec_plan.h), one after the other */
 static int dec_batch(int entry, const nhw_tensor_format *fmt, nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
-                     void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
+                     void *d_out, int32_t *d_status, int32_t *d_quality, void *stream, const NhwOpsArgs &ops = {})
 {
 	DecStore o;
-	if (const int rc = dec_check(entry, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, &o)) return rc;
+	if (const int rc = dec_check(entry, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, &o, ops)) return rc;
 	const DecPlan plan = dec_plan(scale, o.kind == STORE_GREY, d->stop_after, d->chroma_fork);
 	if (!plan.n) { nhw_dec_err = "the debug stop set on the handle is none of 0 .. 11"; return NHW_E_ARG; }
 	HIPCHK(hipSetDevice(d->device));                              /* the handle's device, whatever the calling thread had current */
@@ -2668,7 +2713,7 @@ static int dec_batch(int entry, const nhw_tensor_format *fmt, nhw_dec *d, const 
 		}
 		case DEC_MARKS: k_dec_marks<<<(n + 3) / 4, 256, 0, q>>>(ws); break;
 		case DEC_MARKS_FAR: k_dec_marks_far<<<(n + 3) / 4, 256, 0, q>>>(ws); break;
-		case DEC_LAST: launch_last(ws, n, st.arg, o, (uint8_t *)d_out, q); break;
+		case DEC_LAST: if (o.has_ops) launch_last_ops(ws, n, st.arg, o, (uint8_t *)d_out, q); else launch_last(ws, n, st.arg, o, (uint8_t *)d_out, q); break;
 		case DEC_STATUS: k_dec_status<<<(n + 255) / 256, 256, 0, q>>>(ws, d_status, d_quality); HIPCHK(hipGetLastError()); break;
 		}
 	}
@@ -2701,6 +2746,21 @@ extern "C" int nhw_dec_batch_device_grey(nhw_dec *d, const void *d_nhw, const ui
                                          const nhw_tensor_format *fmt, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
 {
 	return dec_batch(ENTRY_GREY, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream);
+}
+
+/* the two above with the per-sample operations: the same checks, plan and launches, the last kernel with the ops form of the
+ * format's store; with all three tables null, the call above itself */
+extern "C" int nhw_dec_batch_device_tensor_ops(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                               const nhw_tensor_format *fmt, const uint8_t *d_flags, const nhw_colour_map *d_maps,
+                                               const nhw_tone_table *d_tones, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	return dec_batch(ENTRY_TENSOR, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, { d_flags, d_maps, d_tones });
+}
+extern "C" int nhw_dec_batch_device_grey_ops(nhw_dec *d, const void *d_nhw, const uint64_t *d_off, const uint32_t *d_len, int n, int scale,
+                                             const nhw_tensor_format *fmt, const uint8_t *d_flags, const nhw_colour_map *d_maps,
+                                             const nhw_tone_table *d_tones, void *d_out, int32_t *d_status, int32_t *d_quality, void *stream)
+{
+	return dec_batch(ENTRY_GREY, fmt, d, d_nhw, d_off, d_len, n, scale, d_out, d_status, d_quality, stream, { d_flags, d_maps, d_tones });
 }
 
 /* host only: no handle, no GPU call */

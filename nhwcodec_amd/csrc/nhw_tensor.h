@@ -134,12 +134,16 @@ template <int DT, int N> __device__ __forceinline__ void nhw_pack_elems(const ui
  *   CHW: N consecutive elements in each of the three planes -- N * bytes each: 32 (two 16-byte stores), 16 (one), 8 or 4 bytes;
  *   HWC: 3 N consecutive elements -- 96, 48 (16-byte stores), 24 (8-byte stores) or 12 bytes (one store).
  * Consecutive lanes take consecutive pieces either way.  Every address is a multiple of its store's size when `out` is 16-byte aligned (12-byte
- * stores: of 4). */
+ * stores: of 4).
+ * WHO changes nothing in `put`; it only gives a second caller an instantiation of its own.  The policies of nhw_tensor_ops.h end in this `put` with a
+ * piece c that is not the kernel's.  The helpers have internal linkage on the device, and the compiler's interprocedural value propagation runs before
+ * it inlines them: with both callers on ONE instantiation it loses what it knows of c at the kernels' call (c < S / N), and ten of the kernels that
+ * were here before came out with other address arithmetic.  With WHO = 1 for the other caller they are the code they were. */
 template <int DT, int CHW> struct NhwStoreTensor {
-	static constexpr int dtype = DT, layout = CHW;
-	static constexpr bool bytes = false, grey = false;
+	static constexpr int dtype = DT, layout = CHW, lds = 0;             /* lds: the bytes of LDS a policy asks of the kernel for itself; ops: nhw_tensor_ops.h */
+	static constexpr bool bytes = false, grey = false, ops = false;
 	NhwTensorArgs a;
-	template <int S, int N> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
+	template <int S, int N, int WHO = 0 /* the caller: see above NhwStoreTensor */> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
 	{
 		constexpr int EB = NhwElem<DT>::bytes;
 		const int rr = a.flip ? S - 1 - r : r;
@@ -180,10 +184,10 @@ template <int DT, int CHW> struct NhwStoreTensor {
  * slice of the launch (nhw_host.h) for a kernel that has no argument of its own for it, -1 in production. */
 struct NhwGreyArgs { float scale, bias; int flip, slice; };
 template <int DT> struct NhwStoreGrey {
-	static constexpr int dtype = DT;
-	static constexpr bool bytes = false, grey = true;
+	static constexpr int dtype = DT, lds = 0;
+	static constexpr bool bytes = false, grey = true, ops = false;
 	NhwGreyArgs a;
-	template <int S, int N> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
+	template <int S, int N, int WHO = 0 /* the caller: see above NhwStoreTensor */> __device__ __forceinline__ void put(uint8_t *out, int img, int r, int c, const uint32_t *w) const
 	{
 		constexpr int EB = NhwElem<DT>::bytes, K = N * EB / 4;              /* dwords: 16, 8, 4 or 2 */
 		const int rr = a.flip ? S - 1 - r : r;
