@@ -618,6 +618,25 @@ def _filter_limit(filter, w, h, out_w, out_h, what, which):
         raise NhwError(f"{what}: {which} is {w} x {h}, more than {limit} times the output's {out_w} x {out_h} along a side: beyond the {filter} filter's limit")
 
 
+_SAMPLE_ENTRIES = {   # kind: the C entry of a plain colour call, of a plain grey one, of a mapped and of a toned one (either family, by the format)
+    "resample": ("nhw_resample_to_tensor_device", "nhw_resample_grey_to_tensor_device", "nhw_resample_mapped_to_tensor_device", "nhw_resample_toned_to_tensor_device"),
+    "warp": ("nhw_warp_to_tensor_device", "nhw_warp_grey_to_tensor_device", "nhw_warp_mapped_to_tensor_device", "nhw_warp_toned_to_tensor_device"),
+    "crops": ("nhw_dec_crops_to_device_resample", "nhw_dec_crops_grey_to_device", "nhw_dec_crops_mapped_to_device", "nhw_dec_crops_toned_to_device"),
+    "warps": ("nhw_dec_warps_to_device", "nhw_dec_warps_grey_to_device", "nhw_dec_warps_mapped_to_device", "nhw_dec_warps_toned_to_device"),
+}
+
+
+def _sample_entry(lib, kind, channels, colours, tones):
+    """the C entry of a sampling call and its table arguments, which go in front of the output addresses: with tone tables the toned entry, the
+    maps (or None) and the tables; with maps alone the mapped entry and the maps; else the plain entry of the family and nothing"""
+    colour, grey, mapped, toned = _SAMPLE_ENTRIES[kind]
+    if tones is not None:
+        return getattr(lib, toned), (colours, tones)
+    if colours is not None:
+        return getattr(lib, mapped), (colours,)
+    return getattr(lib, colour if channels == 3 else grey), ()
+
+
 def resize_to_tensor_device(pictures, size, fmt, flips=None, filter="two_tap", colours=None, tones=None):
     """Pictures of any sizes to one batch tensor of one size (k_resize_to_tensor, nhw_resize_to_tensor_device): a list of uint8 CUDA tensors
     [H, W, 3] as for pictures_to_tensor_device, size = (out_h, out_w) of 1 .. 4096 each, flips: None or one boolean a picture ("mirror
@@ -668,20 +687,12 @@ def _resize_to_tensor(what, channels, pictures, size, fmt, flips, filter, colour
     d_flags = torch.from_numpy(flags).to(dev) if flags is not None else None
     L = _library()
     c = fmt.c_struct()
-    call = L.nhw_resample_to_tensor_device if channels == 3 else L.nhw_resample_grey_to_tensor_device
     d_maps = _device_table(maps, dev) if colours is not None else None
     d_tones = _device_tones(tabs, dev, what) if tones is not None else None
+    call, tables = _sample_entry(L, "resample", channels, d_maps, d_tones)
     with torch.cuda.device(dev):
-        if tones is not None:
-            rc = L.nhw_resample_toned_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                                                       d_maps.data_ptr() if d_maps is not None else None, d_tones.data_ptr(), addr.data_ptr(),
-                                                       torch.cuda.current_stream(dev).cuda_stream)
-        elif colours is not None:
-            rc = L.nhw_resample_mapped_to_tensor_device(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                                                        d_maps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            rc = call(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
-                      addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        rc = call(table.data_ptr(), n, out_w, out_h, RESAMPLERS[filter], ctypes.byref(c), d_flags.data_ptr() if d_flags is not None else None,
+                  *(t.data_ptr() if t is not None else None for t in tables), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -867,18 +878,12 @@ def _warp_to_tensor(what, channels, pictures, matrices, size, fmt, fill, border,
     d_warps = torch.from_numpy(warps.view(np.int64).copy()).to(dev)
     L = _library()
     c = fmt.c_struct()
-    call = L.nhw_warp_to_tensor_device if channels == 3 else L.nhw_warp_grey_to_tensor_device
     d_maps = _device_table(maps, dev) if colours is not None else None
     d_tones = _device_tones(tabs, dev, what) if tones is not None else None
+    call, tables = _sample_entry(L, "warp", channels, d_maps, d_tones)
     with torch.cuda.device(dev):
-        if tones is not None:
-            rc = L.nhw_warp_toned_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), d_maps.data_ptr() if d_maps is not None else None,
-                                                   d_tones.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        elif colours is not None:
-            rc = L.nhw_warp_mapped_to_tensor_device(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), d_maps.data_ptr(), addr.data_ptr(),
-                                                    torch.cuda.current_stream(dev).cuda_stream)
-        else:
-            rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), addr.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        rc = call(table.data_ptr(), n, out_w, out_h, ctypes.byref(c), d_warps.data_ptr(), *(t.data_ptr() if t is not None else None for t in tables), addr.data_ptr(),
+                  torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
         raise NhwError(f"libnhwhip rc={rc}: {L.nhw_last_error().decode()}")
     return out
@@ -2389,22 +2394,16 @@ class Decoder:
         if filter in _LIMITS:
             for i, r in enumerate(table):
                 _filter_limit(filter, int(r["width"]), int(r["height"]), out_w, out_h, what, f"the window of crop {i}")
-        if tones is not None:
-            return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
-                                        lambda *args: self.lib.nhw_dec_crops_toned_to_device(*args, RESAMPLERS[filter]), channels, maps, tabs), scales
-        if colours is not None:
-            return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
-                                        lambda *args: self.lib.nhw_dec_crops_mapped_to_device(*args, RESAMPLERS[filter]), channels, maps), scales
-        call = self.lib.nhw_dec_crops_to_device_resample if channels == 3 else self.lib.nhw_dec_crops_grey_to_device
+        call, tables = _sample_entry(self.lib, "crops", channels, maps, tabs)
         return self._rects_to_batch(what, blob, offs, len(containers), table, flags, scales, out_w, out_h, fmt, out,
-                                    lambda *args: call(*args, RESAMPLERS[filter]), channels), scales
+                                    lambda *args: call(*args, RESAMPLERS[filter]), channels, tables), scales
 
-    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3, maps=None, tones=None):
+    def _rects_to_batch(self, what, blob, offs, n_containers, table, extra, scales, out_w, out_h, fmt, out, call, channels=3, tables=()):
         """the device side of decode_crops_device and decode_warps_device: the checked batch tensor (`out`, or a new one), and per scale one
         call(handle, blob, offsets, n containers, the scale's rects, their count, scale, out_w, out_h, format, the scale's rows of `extra` --
-        the flag bytes or the nhw_warp table, or None --, the tensors' addresses, statuses) -> rc; with `maps`, the nhw_colour_map table of a mapped call, the
-        scale's rows of it go in front of the addresses; with `tones`, the uint8 [n, 768] table of a toned call, the rows of the maps (or a null pointer)
-        and behind them the rows of the tables do.  Raises on any status that is not NHW_OK"""
+        the flag bytes or the nhw_warp table, or None --, the scale's rows of each of `tables` -- the table arguments of _sample_entry: nothing, the
+        nhw_colour_map table of a mapped call, or the maps (or None, a null pointer) and the uint8 [n, 768] table of a toned call --, the tensors' addresses,
+        statuses) -> rc.  Raises on any status that is not NHW_OK"""
         import numpy as np
         t = self.torch
         n = len(table)
@@ -2423,9 +2422,7 @@ class Decoder:
             idx = np.flatnonzero(np.array(scales) == s)
             sub, a, st = np.ascontiguousarray(table[idx]), np.ascontiguousarray(addr[idx]), np.empty(len(idx), np.int32)
             x = np.ascontiguousarray(extra[idx]) if extra is not None else None
-            mp = (np.ascontiguousarray(maps[idx]),) if maps is not None else (None,) if tones is not None else ()
-            if tones is not None:
-                mp += (np.ascontiguousarray(tones[idx]),)
+            mp = [np.ascontiguousarray(m[idx]) if m is not None else None for m in tables]
             self._chk(call(self.h, blob.ctypes.data, offs.ctypes.data, n_containers, sub.ctypes.data, len(idx), s, out_w, out_h,
                            ctypes.byref(c), x.ctypes.data if x is not None else None, *(m.ctypes.data if m is not None else None for m in mp), a.ctypes.data, st.ctypes.data))
             status[idx] = st
@@ -2481,14 +2478,8 @@ class Decoder:
             rects.append((int(ci),) + win)
             fixed.append(fx)
         blob, offs, table = self._region_args(containers, rects, what)
-        if tones is not None:
-            return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
-                                        self.lib.nhw_dec_warps_toned_to_device, channels, maps, tabs), scales
-        if colours is not None:
-            return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
-                                        self.lib.nhw_dec_warps_mapped_to_device, channels, maps), scales
-        return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out,
-                                    self.lib.nhw_dec_warps_to_device if channels == 3 else self.lib.nhw_dec_warps_grey_to_device, channels), scales
+        call, tables = _sample_entry(self.lib, "warps", channels, maps, tabs)
+        return self._rects_to_batch(what, blob, offs, len(containers), table, _warp_table(fixed, fill, flags), scales, out_w, out_h, fmt, out, call, channels, tables), scales
 
     def region_stats(self):
         """(tiles handed to the decoder, tile-file bytes uploaded) of this handle's last region or window call (nhw_dec_last_region_stats);

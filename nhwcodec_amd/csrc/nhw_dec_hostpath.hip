@@ -185,7 +185,9 @@ enum WindowsMode {
 	WIN_TO_DEVICE,                                               /* dst_addr / dst_pitch: cropped straight into the caller's device memory; nothing is left to do */
 	WIN_TO_TENSORS                                               /* crop, dst_addr the tensors' addresses: packed as for the host form, then resampled or warped (crops_finish) */
 };
-struct CropSpec { NhwTensorOut out; const uint8_t *flags; int filter; const nhw_warp *warps; const nhw_colour_map *maps = nullptr; /* one a rect, or none */ const nhw_tone_table *tones = nullptr; /* one a rect (section 25), or none */ };
+/* what a crop or warp call samples its windows with: NhwSampleCall's fields (nhw_tensor.h) as the caller gave them -- the warps (null: a crop call, under `filter`) and the
+ * tables of ops, one entry a rect, each null for "none", are in HOST memory; crops_finish uploads them */
+struct CropSpec { NhwTensorOut out; int filter; const nhw_warp *warps; NhwOpsArgs ops; };
 struct WindowsCall {
 	WindowsMode mode = WIN_TO_HOST;
 	uint8_t *bgr = nullptr; const uint64_t *out_off = nullptr, *dst_addr = nullptr, *dst_pitch = nullptr;
@@ -217,7 +219,7 @@ static std::vector<uint8_t> crop_refusals(const CropSpec &crop, const nhw_rect *
 	std::vector<uint8_t> refused((size_t)nr);
 	for (int i = 0; i < nr; i++)
 		refused[(size_t)i] = (limit && (rects[i].width > limit * crop.out.w || rects[i].height > limit * crop.out.h)) || (crop.warps && !nhw_warp_within(crop.warps[i])) ||
-		                     (crop.maps && !nhw_colour_within(crop.maps[i]));
+		                     (crop.ops.maps && !nhw_colour_within(crop.ops.maps[i]));
 	return refused;
 }
 
@@ -248,7 +250,7 @@ static int upload_plan(nhw_dec *d, TilePlan &p, bool staged)
  * the nr warps (32 + 8 bytes an entry in front: they are 8-byte aligned) -- k_warp_to_tensor, warps[i] sampling window i along its tilted grid.
  * A mapped call (section 24) has its nr colour maps behind that table, at the next multiple of 8, and launches the mapped forms of the same kernels.
  * A toned call (section 25) has its nr tone tables behind the maps (64 bytes each: a multiple of 8 again), or in their place where it has none,
- * and launches the toned forms. */
+ * and launches the toned forms.  The launch is one call: the tables that are there make the record's (NhwSampleCall), and nhw_launch_sample finds the kernel. */
 static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, const uint64_t *dst_addr, int nr, const int32_t *status, bool grey)
 {
 	static_assert(sizeof(nhw_warp) == 40 && sizeof(nhw_picture) == 32, "the crop table's layout");
@@ -259,34 +261,21 @@ static int crops_finish(nhw_dec *d, const TilePlan &p, const CropSpec &crop, con
 		pics[i] = { p.desc[k].addr, p.desc[k].pitch, p.desc[k].width, p.desc[k].height, 0, 0 };
 		if (status[i] == NHW_OK) oaddr[i] = dst_addr[i];
 	}
+	const NhwOpsArgs &h = crop.ops;                                      /* the caller's tables, in host memory */
 	const size_t pics_bytes = (size_t)nr * sizeof(nhw_picture), addr_bytes = (size_t)nr * 8;
-	const size_t last_bytes = ((size_t)nr * (crop.warps ? sizeof(nhw_warp) : 1) + 7) & ~(size_t)7, maps_bytes = crop.maps ? (size_t)nr * sizeof(nhw_colour_map) : 0;
-	const size_t tones_bytes = crop.tones ? (size_t)nr * sizeof(nhw_tone_table) : 0;
+	const size_t last_bytes = ((size_t)nr * (crop.warps ? sizeof(nhw_warp) : 1) + 7) & ~(size_t)7, maps_bytes = h.maps ? (size_t)nr * sizeof(nhw_colour_map) : 0;
+	const size_t tones_bytes = h.tones ? (size_t)nr * sizeof(nhw_tone_table) : 0;
 	HIPCHK(nhw_grow(d->crop_tab, pics_bytes + addr_bytes + last_bytes + maps_bytes + tones_bytes));
-	uint8_t *tab = d->crop_tab.as<uint8_t>(), *last = tab + pics_bytes + addr_bytes;
-	const nhw_colour_map *d_maps = (const nhw_colour_map *)(last + last_bytes);
-	const nhw_tone_table *d_tones = (const nhw_tone_table *)(last + last_bytes + maps_bytes);
-	const nhw_picture *d_pics = (const nhw_picture *)tab;
-	const uint64_t *d_addr = (const uint64_t *)(tab + pics_bytes);
-	const NhwTensorOut &o = crop.out;
+	uint8_t *tab = d->crop_tab.as<uint8_t>(), *last = tab + pics_bytes + addr_bytes, *maps = last + last_bytes, *tones = maps + maps_bytes;
 	hipStream_t s = d->own_stream;
 	HIPCHK(hipMemcpyAsync(tab, pics.data(), pics_bytes, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync(tab + pics_bytes, oaddr.data(), addr_bytes, hipMemcpyHostToDevice, s));
-	if (crop.maps) HIPCHK(hipMemcpyAsync(last + last_bytes, crop.maps, maps_bytes, hipMemcpyHostToDevice, s));
-	if (crop.tones) HIPCHK(hipMemcpyAsync(last + last_bytes + maps_bytes, crop.tones, tones_bytes, hipMemcpyHostToDevice, s));
-	if (crop.warps) {
-		HIPCHK(hipMemcpyAsync(last, crop.warps, (size_t)nr * sizeof(nhw_warp), hipMemcpyHostToDevice, s));
-		if (crop.tones) HIPCHK(nhw_launch_warp_toned(grey, d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.maps ? d_maps : nullptr, d_tones, d_addr, s));
-		else if (crop.maps) HIPCHK(nhw_launch_warp_mapped(grey, d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_addr, s));
-		else HIPCHK(grey ? nhw_launch_warp_grey(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.a, d_addr, s)
-		            : nhw_launch_warp(d_pics, (const nhw_warp *)last, nr, o.w, o.h, o.dtype, o.layout, o.a, d_addr, s));
-	} else {
-		if (crop.flags) HIPCHK(hipMemcpyAsync(last, crop.flags, (size_t)nr, hipMemcpyHostToDevice, s));
-		if (crop.tones) HIPCHK(nhw_launch_resample_toned(grey, crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, crop.maps ? d_maps : nullptr, d_tones, d_addr, s));
-		else if (crop.maps) HIPCHK(nhw_launch_resample_mapped(grey, crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_maps, d_addr, s));
-		else HIPCHK(grey ? nhw_launch_resample_grey(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.a, crop.flags ? last : nullptr, d_addr, s)
-		            : nhw_launch_resample(crop.filter, d_pics, nr, o.w, o.h, o.dtype, o.layout, o.a, crop.flags ? last : nullptr, d_addr, s));
-	}
+	if (h.maps) HIPCHK(hipMemcpyAsync(maps, h.maps, maps_bytes, hipMemcpyHostToDevice, s));
+	if (h.tones) HIPCHK(hipMemcpyAsync(tones, h.tones, tones_bytes, hipMemcpyHostToDevice, s));
+	if (crop.warps) HIPCHK(hipMemcpyAsync(last, crop.warps, (size_t)nr * sizeof(nhw_warp), hipMemcpyHostToDevice, s));
+	else if (h.flags) HIPCHK(hipMemcpyAsync(last, h.flags, (size_t)nr, hipMemcpyHostToDevice, s));
+	const NhwOpsArgs dev = { crop.warps || !h.flags ? nullptr : last, h.maps ? (const nhw_colour_map *)maps : nullptr, h.tones ? (const nhw_tone_table *)tones : nullptr };
+	HIPCHK(nhw_launch_sample({ (const nhw_picture *)tab, nr, crop.out, grey, crop.filter, crop.warps ? (const nhw_warp *)last : nullptr, dev, (const uint64_t *)(tab + pics_bytes) }, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return NHW_OK;
 }
@@ -351,60 +340,94 @@ extern "C" int nhw_dec_windows_to_device(nhw_dec *d, const uint8_t *blob, const 
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
 }
 
-/* nhw_dec_windows_to_device with a resize behind it (DESIGN.md sections 18 to 20): window i, resampled to out_width x out_height under `filter` and
- * mirrored where bit 0 of flags[i] is set, to the tensor at dst_addr[i].  The three entries are this body, told apart by `newest`: the two older
- * ones take the filters 0 and 1 (nhw_dec_crops_to_device_filter keeps refusing the cubic filter), the newest all three.  A filter an entry does not
- * take is refused in that entry's words and at that entry's place among the checks, which callers can tell apart by the message they get for two
- * mistakes at once: the newest entry looks at the filter first, the older ones at dst_addr and n_rects. */
-struct CropsArgs { uint32_t out_width, out_height; const nhw_tensor_format *fmt; const uint8_t *flags; const uint64_t *dst_addr; int filter; bool newest; };
-static int dec_crops(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale, int32_t *status, const CropsArgs &a)
+/* nhw_dec_windows_to_device with a sampler behind it: window i to the tensor at dst_addr[i], out_width x out_height -- resampled under `filter` and
+ * mirrored where bit 0 of flags[i] is set (DESIGN.md sections 18 to 20), or sampled along the tilted grid of warps[i] in place of filter and flags
+ * (section 21); as colour or as grey (section 23), with a colour map (section 24) or a tone table (section 25) a rect.  The ten entries are one body,
+ * dec_samples, and a row of the table below says what an entry's checks are.
+ * A filter an entry does not take is refused in that entry's words and at that entry's place among the checks, which callers can tell apart by
+ * the message they get for two mistakes at once: the two oldest entries look at dst_addr, the tables and n_rects first (`filter_first` off), every
+ * later one at the filter.  Then come the sides and the format, and dec_windows' own checks. */
+struct SamplesEntry {
+	const char *who;             /* the entry as nhw_tensor_out_check and dec_windows' messages name it */
+	const char *filter_who;      /* ... and as the filter's message does; null: a warp entry, whose `warps` must not be NULL */
+	int last_filter;             /* the filters taken: NHW_FILTER_TWO_TAP .. this one */
+	bool filter_first;
+	NhwFamily family;
+	bool maps, tones;            /* the tables that must not be NULL (a toned entry's maps may be) */
+};
+/* nhw_dec_crops_to_device and nhw_dec_crops_to_device_filter are the row CROPS: the second keeps refusing the cubic filter.  nhw_dec_crops_to_device_resample
+ * takes it and says so under its own name, but is nhw_dec_crops_to_device in every other message */
+static const SamplesEntry
+	CROPS          = { "nhw_dec_crops_to_device",        "nhw_dec_crops_to_device",          NHW_FILTER_AREA,  false, NHW_FAMILY_COLOUR,    false, false },
+	CROPS_RESAMPLE = { "nhw_dec_crops_to_device",        "nhw_dec_crops_to_device_resample", NHW_FILTER_CUBIC, true,  NHW_FAMILY_COLOUR,    false, false },
+	WARPS          = { "nhw_dec_warps_to_device",        nullptr,                            0,                false, NHW_FAMILY_COLOUR,    false, false },
+	CROPS_GREY     = { "nhw_dec_crops_grey_to_device",   "nhw_dec_crops_grey_to_device",     NHW_FILTER_CUBIC, true,  NHW_FAMILY_GREY,      false, false },
+	WARPS_GREY     = { "nhw_dec_warps_grey_to_device",   nullptr,                            0,                false, NHW_FAMILY_GREY,      false, false },
+	CROPS_MAPPED   = { "nhw_dec_crops_mapped_to_device", "nhw_dec_crops_mapped_to_device",   NHW_FILTER_CUBIC, true,  NHW_FAMILY_BY_FORMAT, true,  false },
+	WARPS_MAPPED   = { "nhw_dec_warps_mapped_to_device", nullptr,                            0,                false, NHW_FAMILY_BY_FORMAT, true,  false },
+	CROPS_TONED    = { "nhw_dec_crops_toned_to_device",  "nhw_dec_crops_toned_to_device",    NHW_FILTER_CUBIC, true,  NHW_FAMILY_BY_FORMAT, false, true  },
+	WARPS_TONED    = { "nhw_dec_warps_toned_to_device",  nullptr,                            0,                false, NHW_FAMILY_BY_FORMAT, false, true  };
+
+static int dec_samples(const SamplesEntry &e, nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, int filter, const nhw_warp *warps, const NhwOpsArgs &ops, const uint64_t *dst_addr, int32_t *status)
 {
-	const bool taken = a.filter >= NHW_FILTER_TWO_TAP && a.filter <= (a.newest ? NHW_FILTER_CUBIC : NHW_FILTER_AREA);
-	if (a.newest && !taken) { nhw_dec_err = "nhw_dec_crops_to_device_resample: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!a.dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	if (!taken) { nhw_dec_err = "nhw_dec_crops_to_device: the filter must be NHW_FILTER_TWO_TAP or NHW_FILTER_AREA"; return NHW_E_ARG; }
-	CropSpec crop = { {}, a.flags, a.filter, nullptr };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_to_device", a.out_width, a.out_height, a.fmt, &crop.out, nhw_dec_err)) return rc;
+	static const char *const must[] = { ": the filter must be NHW_FILTER_TWO_TAP or NHW_FILTER_AREA", ": the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC" };
+	const bool taken = !e.filter_who || (filter >= NHW_FILTER_TWO_TAP && filter <= e.last_filter);
+	if (!taken && e.filter_first) { nhw_dec_err = std::string(e.filter_who) + must[e.last_filter == NHW_FILTER_CUBIC]; return NHW_E_ARG; }
+	if (!dst_addr || (!e.filter_who && !warps) || (e.maps && !ops.maps) || (e.tones && !ops.tones) || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
+	if (!taken) { nhw_dec_err = std::string(e.filter_who) + must[e.last_filter == NHW_FILTER_CUBIC]; return NHW_E_ARG; }
 	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = a.dst_addr; c.crop = &crop; c.who = "nhw_dec_crops_to_device";
+	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.grey = nhw_family_grey(e.family, fmt); c.who = e.who;
+	CropSpec crop = { {}, filter, warps, ops };
+	if (const int rc = nhw_tensor_out_check(e.who, out_width, out_height, fmt, &crop.out, nhw_dec_err, c.grey)) return rc;
+	c.crop = &crop;
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
 }
 
 extern "C" int nhw_dec_crops_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                                        uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status)
-{
-	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, status, { out_width, out_height, fmt, flags, dst_addr, NHW_FILTER_TWO_TAP, false });
-}
+{ return dec_samples(CROPS, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, NHW_FILTER_TWO_TAP, nullptr, { flags, nullptr, nullptr }, dst_addr, status); }
 
 extern "C" int nhw_dec_crops_to_device_filter(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status,
-                                              int filter)
-{
-	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, status, { out_width, out_height, fmt, flags, dst_addr, filter, false });
-}
+                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status, int filter)
+{ return dec_samples(CROPS, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, filter, nullptr, { flags, nullptr, nullptr }, dst_addr, status); }
 
 extern "C" int nhw_dec_crops_to_device_resample(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                                uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
-                                                int *status, int filter)
+                                                uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int *status, int filter)
 {
 	static_assert(sizeof(int) == sizeof(int32_t), "the statuses are 32 bits wide");
-	return dec_crops(d, blob, off, n_containers, rects, n_rects, scale, (int32_t *)status, { out_width, out_height, fmt, flags, dst_addr, filter, true });
+	return dec_samples(CROPS_RESAMPLE, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, filter, nullptr, { flags, nullptr, nullptr }, dst_addr, (int32_t *)status);
 }
 
-/* the windows sampled along tilted grids: the crop call with a warp a rect in place of filter and flags */
 extern "C" int nhw_dec_warps_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
-                                       int32_t *status)
-{
-	if (!warps || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.who = "nhw_dec_warps_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
+                                       uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr, int32_t *status)
+{ return dec_samples(WARPS, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, NHW_FILTER_TWO_TAP, warps, {}, dst_addr, status); }
 
-/* ---------------------------------------------------------------------------------------------- the same calls at one byte a pixel */
+extern "C" int nhw_dec_crops_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr, int32_t *status, int filter)
+{ return dec_samples(CROPS_GREY, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, filter, nullptr, { flags, nullptr, nullptr }, dst_addr, status); }
+
+extern "C" int nhw_dec_warps_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr, int32_t *status)
+{ return dec_samples(WARPS_GREY, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, NHW_FILTER_TWO_TAP, warps, {}, dst_addr, status); }
+
+extern "C" int nhw_dec_crops_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps, const uint64_t *dst_addr, int32_t *status, int filter)
+{ return dec_samples(CROPS_MAPPED, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, filter, nullptr, { flags, maps, nullptr }, dst_addr, status); }
+
+extern "C" int nhw_dec_warps_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps, const uint64_t *dst_addr, int32_t *status)
+{ return dec_samples(WARPS_MAPPED, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, NHW_FILTER_TWO_TAP, warps, { nullptr, maps, nullptr }, dst_addr, status); }
+
+extern "C" int nhw_dec_crops_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps, const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status, int filter)
+{ return dec_samples(CROPS_TONED, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, filter, nullptr, { flags, maps, tones }, dst_addr, status); }
+
+extern "C" int nhw_dec_warps_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
+                                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps, const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status)
+{ return dec_samples(WARPS_TONED, d, blob, off, n_containers, rects, n_rects, scale, out_width, out_height, fmt, NHW_FILTER_TWO_TAP, warps, { nullptr, maps, tones }, dst_addr, status); }
+
+/* ---------------------------------------------------------------------------------------------- the window calls at one byte a pixel */
 extern "C" int nhw_dec_windows_grey(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
                                     uint8_t *out, const uint64_t *out_off, int32_t *status)
 {
@@ -418,91 +441,6 @@ extern "C" int nhw_dec_windows_grey_to_device(nhw_dec *d, const uint8_t *blob, c
 {
 	WindowsCall c;
 	c.mode = WIN_TO_DEVICE; c.dst_addr = dst_addr; c.dst_pitch = dst_pitch; c.grey = true; c.who = "nhw_dec_windows_grey_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
-
-/* nhw_dec_crops_to_device_resample's checks in its order -- the filter, then dst_addr and n_rects, then the sides and the format, which must be a grey one */
-extern "C" int nhw_dec_crops_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const uint64_t *dst_addr,
-                                            int32_t *status, int filter)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_grey_to_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	CropSpec crop = { {}, flags, filter, nullptr };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_grey_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, true)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = true; c.who = "nhw_dec_crops_grey_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
-
-extern "C" int nhw_dec_warps_grey_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                            uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const uint64_t *dst_addr,
-                                            int32_t *status)
-{
-	if (!warps || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_grey_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, true)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = true; c.who = "nhw_dec_warps_grey_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
-
-/* ---------------------------------------------------------------------------------------------- the crop and warp calls with a colour map a rect */
-/* nhw_dec_crops_to_device_resample's and nhw_dec_warps_to_device's checks in their order, the NULL map table beside dst_addr; a format that names
- * NHW_T_GREY makes the call the one-channel one */
-extern "C" int nhw_dec_crops_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps,
-                                              const uint64_t *dst_addr, int32_t *status, int filter)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_mapped_to_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!dst_addr || !maps || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = fmt && fmt->channels == NHW_T_GREY;
-	CropSpec crop = { {}, flags, filter, nullptr, maps };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_mapped_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_crops_mapped_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
-
-extern "C" int nhw_dec_warps_mapped_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                              uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
-                                              const uint64_t *dst_addr, int32_t *status)
-{
-	if (!warps || !maps || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = fmt && fmt->channels == NHW_T_GREY;
-	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps, maps };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_mapped_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_warps_mapped_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
-
-/* ... and with a tone table a rect: the mapped calls' checks in their order, the NULL tone table where the NULL map table
- * was; the maps may be NULL here */
-extern "C" int nhw_dec_crops_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *flags, const nhw_colour_map *maps,
-                                             const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status, int filter)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_dec_err = "nhw_dec_crops_toned_to_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!dst_addr || !tones || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = fmt && fmt->channels == NHW_T_GREY;
-	CropSpec crop = { {}, flags, filter, nullptr, maps, tones };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_crops_toned_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_crops_toned_to_device";
-	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
-}
-
-extern "C" int nhw_dec_warps_toned_to_device(nhw_dec *d, const uint8_t *blob, const uint64_t *off, int n_containers, const nhw_rect *rects, int n_rects, int scale,
-                                             uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const nhw_warp *warps, const nhw_colour_map *maps,
-                                             const nhw_tone_table *tones, const uint64_t *dst_addr, int32_t *status)
-{
-	if (!warps || !tones || !dst_addr || n_rects > (1 << 24)) { nhw_dec_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = fmt && fmt->channels == NHW_T_GREY;
-	CropSpec crop = { {}, nullptr, NHW_FILTER_TWO_TAP, warps, maps, tones };
-	if (const int rc = nhw_tensor_out_check("nhw_dec_warps_toned_to_device", out_width, out_height, fmt, &crop.out, nhw_dec_err, grey)) return rc;
-	WindowsCall c;
-	c.mode = WIN_TO_TENSORS; c.dst_addr = dst_addr; c.crop = &crop; c.grey = grey; c.who = "nhw_dec_warps_toned_to_device";
 	return dec_windows(d, blob, off, n_containers, rects, n_rects, scale, status, c);
 }
 

@@ -145,26 +145,28 @@ extern "C" int nhw_untile_regions_device(const void *d_tiles, const nhw_region *
 	return NHW_OK;
 }
 
-/* the crop of a window call: a table of (window, tile) uses over the decoded tiles of the slots [tile0, tile0 + m) */
-extern "C" int nhw_untile_windows_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
-                                         int tile0, int m, int scale, void *stream)
+/* the crop of a window call: a table of (window, tile) uses over the decoded tiles of the slots [tile0, tile0 + m); and of
+ * a grey window call (section 23): the same table and uses over slots of T T bytes, one byte a pixel */
+static int untile_windows(const char *who, decltype(nhw_launch_untile_window) *launch, const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses,
+                          int n_uses, int tile0, int m, int scale, void *stream)
 {
-	if (const int rc = picture_args(d_regs, n_regs, tile0, m, d_tiles, "nhw_untile_windows_device")) return rc;
+	if (const int rc = picture_args(d_regs, n_regs, tile0, m, d_tiles, who)) return rc;
 	if (!d_uses || n_uses < 1 || n_uses > INT_MAX / 16) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = "nhw_untile_windows_device: the scale must be 1, 2 or 4"; return NHW_E_ARG; }
-	HIPCHK(nhw_launch_untile_window((const uint8_t *)d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, (hipStream_t)stream));
+	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = std::string(who) + ": the scale must be 1, 2 or 4"; return NHW_E_ARG; }
+	HIPCHK(launch((const uint8_t *)d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, (hipStream_t)stream));
 	return NHW_OK;
 }
 
-/* ... and of a grey window call: the same table and uses over slots of T T bytes, one byte a pixel */
+extern "C" int nhw_untile_windows_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
+                                         int tile0, int m, int scale, void *stream)
+{
+	return untile_windows("nhw_untile_windows_device", nhw_launch_untile_window, d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, stream);
+}
+
 extern "C" int nhw_untile_windows_grey_device(const void *d_tiles, const nhw_region *d_regs, int n_regs, const nhw_window_use *d_uses, int n_uses,
                                               int tile0, int m, int scale, void *stream)
 {
-	if (const int rc = picture_args(d_regs, n_regs, tile0, m, d_tiles, "nhw_untile_windows_grey_device")) return rc;
-	if (!d_uses || n_uses < 1 || n_uses > INT_MAX / 16) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	if (scale != 1 && scale != 2 && scale != 4) { nhw_enc_err = "nhw_untile_windows_grey_device: the scale must be 1, 2 or 4"; return NHW_E_ARG; }
-	HIPCHK(nhw_launch_untile_window_grey((const uint8_t *)d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, (hipStream_t)stream));
-	return NHW_OK;
+	return untile_windows("nhw_untile_windows_grey_device", nhw_launch_untile_window_grey, d_tiles, d_regs, n_regs, d_uses, n_uses, tile0, m, scale, stream);
 }
 
 /* the pictures of a table to tensors of a format, one pointwise pass */
@@ -177,123 +179,81 @@ extern "C" int nhw_bytes_to_tensor_device(const nhw_picture *d_pics, int n_pics,
 	return NHW_OK;
 }
 
-/* ... and resampled to one size on the way: the pictures of a table to out_width x out_height tensors, one pass of the filter's kernel (DESIGN.md
- * sections 18 to 20).  The three entries are this body; only nhw_resample_to_tensor_device can name a filter that does not exist.  A message
- * names the entry that brought its filter in: through the newest entry the filters 0 and 1 are the older calls themselves, texts included. */
-static int resize_entry(int filter, const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt, const uint8_t *d_flags,
-                        const uint64_t *d_out_addr, void *stream)
+/* ... and sampled into tensors of one size on the way: the pictures of a table to out_width x out_height tensors, one pass of one kernel -- resampled
+ * under a filter (DESIGN.md sections 18 to 20) or along the tilted grids of a device table of warps (section 21), as colour or as grey (section 23),
+ * with a colour map (section 24) or a tone table (section 25) an entry.  The ten entries are one body, sample_entry, which fills in the call's
+ * record (NhwSampleCall, nhw_tensor.h) and launches it; a row of the table below says what an entry's checks are.  Their order is every entry's:
+ * the filter (an entry that takes one), the NULL pointers and n, the sides, the format. */
+struct SampleEntry {
+	const char *who;             /* the entry as the filter's message and nhw_tensor_out_check's name it */
+	bool warp;                   /* d_warps in place of a filter, and never NULL */
+	NhwFamily family;
+	bool maps, tones;            /* the tables that must not be NULL (a toned entry's d_maps may be) */
+	bool by_filter;              /* the sides are refused under the name of the entry that brought the filter in (RESAMPLE alone) */
+};
+/* nhw_resize_, nhw_area_ and nhw_resample_to_tensor_device are one row.  Only the last can name a filter that does not exist, so the filter's message
+ * names it; the sides' message names the entry of the filter: through the newest entry the filters 0 and 1 are the older calls themselves, texts included. */
+static const char *const RESAMPLE_BY_FILTER[] = { "nhw_resize_to_tensor_device", "nhw_area_to_tensor_device", "nhw_resample_to_tensor_device" };
+static const SampleEntry
+	RESAMPLE        = { "nhw_resample_to_tensor_device",        false, NHW_FAMILY_COLOUR,    false, false, true  },
+	WARP            = { "nhw_warp_to_tensor_device",            true,  NHW_FAMILY_COLOUR,    false, false, false },
+	RESAMPLE_GREY   = { "nhw_resample_grey_to_tensor_device",   false, NHW_FAMILY_GREY,      false, false, false },
+	WARP_GREY       = { "nhw_warp_grey_to_tensor_device",       true,  NHW_FAMILY_GREY,      false, false, false },
+	RESAMPLE_MAPPED = { "nhw_resample_mapped_to_tensor_device", false, NHW_FAMILY_BY_FORMAT, true,  false, false },
+	WARP_MAPPED     = { "nhw_warp_mapped_to_tensor_device",     true,  NHW_FAMILY_BY_FORMAT, true,  false, false },
+	RESAMPLE_TONED  = { "nhw_resample_toned_to_tensor_device",  false, NHW_FAMILY_BY_FORMAT, false, true,  false },
+	WARP_TONED      = { "nhw_warp_toned_to_tensor_device",      true,  NHW_FAMILY_BY_FORMAT, false, true,  false };
+
+static int sample_entry(const SampleEntry &e, const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
+                        const nhw_warp *d_warps, const NhwOpsArgs &ops, const uint64_t *d_out_addr, void *stream)
 {
-	static const char *const entry[] = { "nhw_resize_to_tensor_device", "nhw_area_to_tensor_device", "nhw_resample_to_tensor_device" };
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check(entry[filter], out_width, out_height, fmt, &o, nhw_enc_err)) return rc;
-	HIPCHK(nhw_launch_resample(filter, d_pics, n, o.w, o.h, o.dtype, o.layout, o.a, d_flags, d_out_addr, (hipStream_t)stream));
+	if (!e.warp && (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC)) { nhw_enc_err = std::string(e.who) + ": the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
+	if (!d_pics || (e.warp && !d_warps) || (e.maps && !ops.maps) || (e.tones && !ops.tones) || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
+	NhwSampleCall c = { d_pics, n, {}, nhw_family_grey(e.family, fmt), filter, d_warps, ops, d_out_addr };
+	if (const int rc = nhw_tensor_out_check(e.by_filter ? RESAMPLE_BY_FILTER[filter] : e.who, out_width, out_height, fmt, &c.out, nhw_enc_err, c.grey)) return rc;
+	HIPCHK(nhw_launch_sample(c, (hipStream_t)stream));
 	return NHW_OK;
 }
 
 extern "C" int nhw_resize_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                            const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
-{
-	return resize_entry(NHW_FILTER_TWO_TAP, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
-}
+{ return sample_entry(RESAMPLE, d_pics, n, out_width, out_height, NHW_FILTER_TWO_TAP, fmt, nullptr, { d_flags, nullptr, nullptr }, d_out_addr, stream); }
 
 extern "C" int nhw_area_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                          const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
-{
-	return resize_entry(NHW_FILTER_AREA, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
-}
+{ return sample_entry(RESAMPLE, d_pics, n, out_width, out_height, NHW_FILTER_AREA, fmt, nullptr, { d_flags, nullptr, nullptr }, d_out_addr, stream); }
 
 extern "C" int nhw_resample_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
                                              const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
-{
-	return resize_entry(filter, d_pics, n, out_width, out_height, fmt, d_flags, d_out_addr, stream);
-}
+{ return sample_entry(RESAMPLE, d_pics, n, out_width, out_height, filter, fmt, nullptr, { d_flags, nullptr, nullptr }, d_out_addr, stream); }
 
-/* ... or sampled along a tilted grid: the same table and checks, a device table of warps in place of the flags */
 extern "C" int nhw_warp_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                          const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream)
-{
-	if (!d_pics || !d_warps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_warp_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err)) return rc;
-	HIPCHK(nhw_launch_warp(d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
+{ return sample_entry(WARP, d_pics, n, out_width, out_height, 0, fmt, d_warps, {}, d_out_addr, stream); }
 
-/* the one-channel forms of both: pictures of 1 byte a pixel, a grey format, the same checks in the same order */
 extern "C" int nhw_resample_grey_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
                                                   const uint8_t *d_flags, const uint64_t *d_out_addr, void *stream)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_grey_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!d_pics || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_resample_grey_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, true)) return rc;
-	HIPCHK(nhw_launch_resample_grey(filter, d_pics, n, o.w, o.h, o.dtype, o.a, d_flags, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
+{ return sample_entry(RESAMPLE_GREY, d_pics, n, out_width, out_height, filter, fmt, nullptr, { d_flags, nullptr, nullptr }, d_out_addr, stream); }
 
 extern "C" int nhw_warp_grey_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                               const nhw_warp *d_warps, const uint64_t *d_out_addr, void *stream)
-{
-	if (!d_pics || !d_warps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_warp_grey_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, true)) return rc;
-	HIPCHK(nhw_launch_warp_grey(d_pics, d_warps, n, o.w, o.h, o.dtype, o.a, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
-
-/* ... and both with a colour map an entry: the unmapped entries' checks in their order, the NULL map table among the NULL
- * pointers; a format that names NHW_T_GREY makes the call the one-channel one */
-static bool names_grey(const nhw_tensor_format *fmt) { return fmt && fmt->channels == NHW_T_GREY; }
+{ return sample_entry(WARP_GREY, d_pics, n, out_width, out_height, 0, fmt, d_warps, {}, d_out_addr, stream); }
 
 extern "C" int nhw_resample_mapped_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
                                                     const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, void *stream)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_mapped_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!d_pics || !d_maps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = names_grey(fmt);
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_resample_mapped_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
-	HIPCHK(nhw_launch_resample_mapped(grey, filter, d_pics, n, o.w, o.h, o.dtype, o.layout, o.a, d_flags, d_maps, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
+{ return sample_entry(RESAMPLE_MAPPED, d_pics, n, out_width, out_height, filter, fmt, nullptr, { d_flags, d_maps, nullptr }, d_out_addr, stream); }
 
 extern "C" int nhw_warp_mapped_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                                 const nhw_warp *d_warps, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, void *stream)
-{
-	if (!d_pics || !d_warps || !d_maps || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = names_grey(fmt);
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_warp_mapped_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
-	HIPCHK(nhw_launch_warp_mapped(grey, d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
+{ return sample_entry(WARP_MAPPED, d_pics, n, out_width, out_height, 0, fmt, d_warps, { nullptr, d_maps, nullptr }, d_out_addr, stream); }
 
-/* ... and with a tone table an entry: the mapped entries' checks in their order, the NULL tone table among the NULL pointers;
- * the map table may be NULL here */
 extern "C" int nhw_resample_toned_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, int filter, const nhw_tensor_format *fmt,
                                                    const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, void *stream)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) { nhw_enc_err = "nhw_resample_toned_to_tensor_device: the filter must be NHW_FILTER_TWO_TAP, NHW_FILTER_AREA or NHW_FILTER_CUBIC"; return NHW_E_ARG; }
-	if (!d_pics || !d_tones || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = names_grey(fmt);
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_resample_toned_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
-	HIPCHK(nhw_launch_resample_toned(grey, filter, d_pics, n, o.w, o.h, o.dtype, o.layout, o.a, d_flags, d_maps, d_tones, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
+{ return sample_entry(RESAMPLE_TONED, d_pics, n, out_width, out_height, filter, fmt, nullptr, { d_flags, d_maps, d_tones }, d_out_addr, stream); }
 
 extern "C" int nhw_warp_toned_to_tensor_device(const nhw_picture *d_pics, int n, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *fmt,
                                                const nhw_warp *d_warps, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, void *stream)
-{
-	if (!d_pics || !d_warps || !d_tones || !d_out_addr || n < 1 || n > (1 << 24)) { nhw_enc_err = "bad argument"; return NHW_E_ARG; }
-	const bool grey = names_grey(fmt);
-	NhwTensorOut o;
-	if (const int rc = nhw_tensor_out_check("nhw_warp_toned_to_tensor_device", out_width, out_height, fmt, &o, nhw_enc_err, grey)) return rc;
-	HIPCHK(nhw_launch_warp_toned(grey, d_pics, d_warps, n, o.w, o.h, o.dtype, o.layout, o.a, d_maps, d_tones, d_out_addr, (hipStream_t)stream));
-	return NHW_OK;
-}
+{ return sample_entry(WARP_TONED, d_pics, n, out_width, out_height, 0, fmt, d_warps, { nullptr, d_maps, d_tones }, d_out_addr, stream); }
 
 /* the histograms of a table's pictures, and tone tables' rows from histograms (nhw_tone.hip) */
 extern "C" int nhw_hist_device(const nhw_picture *d_pics, int n, int channels, uint32_t *d_hist, void *stream)
@@ -605,7 +565,7 @@ extern "C" int nhw_enc_pictures_resized(nhw_enc *e, const uint8_t *bgr, const ui
 	HIPCHK(hipMemcpyAsync((void *)d_desc, pc.desc.data(), desc_bytes, hipMemcpyHostToDevice, s));
 	HIPCHK(hipMemcpyAsync((void *)d_addr, addr.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
 	const NhwTensorArgs bytes = { { 1.0f, 1.0f, 1.0f }, { 0.0f, 0.0f, 0.0f }, 0, 0 };
-	HIPCHK(nhw_launch_resample(NHW_FILTER_AREA, e->pic_desc.as<nhw_picture>(), n, out_width, out_height, NHW_T_U8, NHW_T_HWC, bytes, nullptr, d_addr, s));
+	HIPCHK(nhw_launch_sample({ e->pic_desc.as<nhw_picture>(), n, { out_width, out_height, NHW_T_U8, NHW_T_HWC, bytes }, false, NHW_FILTER_AREA, nullptr, {}, d_addr }, s));
 	return encode_containers(e, d_desc, pc, quality, out_arena, arena_cap, out_off, status);
 }
 

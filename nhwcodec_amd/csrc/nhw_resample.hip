@@ -1,7 +1,8 @@
 /*
  * nhw_resample.hip -- pictures resampled into tensors of one size (DESIGN.md sections 18 to 20): the two-tap kernel k_resize_to_tensor, the
- * area filter k_area_to_tensor and the cubic filter k_cubic_to_tensor, the axis helpers of each, and their one launcher nhw_launch_resample;
- * and pictures sampled along a tilted grid (section 21): the affine warp k_warp_to_tensor and its launcher nhw_launch_warp, under the same band rule.
+ * area filter k_area_to_tensor and the cubic filter k_cubic_to_tensor, and the axis helpers of each; pictures sampled along a tilted grid
+ * (section 21): the affine warp k_warp_to_tensor; and the one launcher of all four, nhw_launch_sample, which takes a call as one record
+ * (NhwSampleCall, nhw_tensor.h) and finds its kernel: the form (dtype, layout, bytes a pixel), the pack of its tables, the band rule, the filter.
  *
  * The three kernels have one shape.  The table (nhw_picture entries, addr, pitch, width and height read), the flags and the tensors'
  * addresses live in device memory, so the host knows no picture's size: the grid is entries x bands of `rows` output rows, cut by the one
@@ -39,7 +40,7 @@ constexpr int RS_MAX = 4096, RS_ROWS = 64;      /* the largest output side; the 
  * with the entry's picture p, its tensor `out` and whether it is mirrored left-right (bit 0 of flags[k]; flags may be null).  False for an
  * entry that stores nothing: one with a zero or oversize side, a zero address or one that is no multiple of the element size, and, with a
  * filter's reduction limit (`limit`: 0 for the two-tap kernel, which has none), one beyond it on either axis.  False as well for what
- * nhw_launch_resample refuses before it launches -- an output side of 0 or above RS_MAX, a band of no rows or of more than RS_ROWS, a band
+ * nhw_launch_sample refuses before it launches -- an output side of 0 or above RS_MAX, a band of no rows or of more than RS_ROWS, a band
  * below the output -- so that no kernel depends on its launcher for the room of its tables. */
 template <int DT>
 __device__ __forceinline__ bool resample_entry_at(const nhw_picture *__restrict__ pics, const uint8_t *__restrict__ flags, const uint64_t *__restrict__ out_addr, uint32_t out_w,
@@ -554,147 +555,66 @@ static bool resample_bands(int n, uint32_t out_w, uint32_t out_h, int &lg, uint3
 	return true;
 }
 
-/* The four launches, each with the pack M of its kernels: empty for the calls that have no maps, const nhw_colour_map * and the
- * device table of n maps for those that do; behind it const nhw_tone_table * and the table of n tone tables for the toned calls (section 25), whose
- * map table may be null. */
-template <class... M>
-static hipError_t launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                              const uint64_t *d_out_addr, hipStream_t s, M... maps)
+/* f(DT, CHW, C as std::integral_constants) for a checked format and the call's family: the dtype and layout of a colour call with C = 3; the dtype
+ * alone of a grey one, with CHW = 0 and C = 1 */
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> static void with_form(bool grey, int dtype, int layout, F &&f)
 {
-	int lg, bands;
-	uint32_t rows;
-	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
-	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
-		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
-		k_warp_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr, maps...);
-	});
-	return hipGetLastError();
-}
-
-/* f(the dtype as a std::integral_constant) for a checked format: what the one-channel launches are told apart by */
-template <class F> static void with_dtype(int dtype, F &&f)
-{
+	const auto of = [&](auto dt) {
+		if (grey) f(dt, Int<0>{}, Int<1>{});
+		else if (layout == NHW_T_HWC) f(dt, Int<NHW_T_HWC>{}, Int<3>{});
+		else f(dt, Int<NHW_T_CHW>{}, Int<3>{});
+	};
 	switch (dtype) {
-	case NHW_T_U8: f(std::integral_constant<int, NHW_T_U8>{}); break;
-	case NHW_T_F16: f(std::integral_constant<int, NHW_T_F16>{}); break;
-	case NHW_T_BF16: f(std::integral_constant<int, NHW_T_BF16>{}); break;
-	default: f(std::integral_constant<int, NHW_T_F32>{}); break;
+	case NHW_T_U8: of(Int<NHW_T_U8>{}); break;
+	case NHW_T_F16: of(Int<NHW_T_F16>{}); break;
+	case NHW_T_BF16: of(Int<NHW_T_BF16>{}); break;
+	default: of(Int<NHW_T_F32>{}); break;
 	}
 }
 
-template <class... M>
-static hipError_t launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                   const uint64_t *d_out_addr, hipStream_t s, M... maps)
+/* f(the pack M... of the call's kernels) by its tables (DESIGN.md sections 24 and 25): nothing for a call without maps and tone tables, so that it
+ * runs the kernels that have no such arguments; the maps alone; or, for a toned call, the maps -- null where it has none -- and the tone tables */
+template <class F> static void with_pack(const NhwOpsArgs &o, F &&f)
 {
-	int lg, bands;
-	uint32_t rows;
-	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
-	with_dtype(dtype, [&](auto dt) {
-		k_warp_to_tensor<decltype(dt)::value, 0, 1, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, d_warps, out_w, out_h, bands, (int)rows, lg, warp_row_limit, a, d_out_addr, maps...);
-	});
-	return hipGetLastError();
+	if (o.tones) f(o.maps, o.tones);
+	else if (o.maps) f(o.maps);
+	else f();
 }
 
 /* the developer's hook for measurements and tests: every later launch of the process walks by rows where |d| <= limit (-1: blocks for every
  * entry; 2^22: rows for every entry); a limit below -1 puts the rule's own back.  The results are the same bytes whatever the walk. */
 extern "C" void nhw_debug_warp_row_limit(int limit) { warp_row_limit = limit < -1 ? WARP_ROW_LANES : limit; }
 
-template <class... M>
-static hipError_t launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                  const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s, M... maps)
+/* The one launch of a sampling call (NhwSampleCall, nhw_tensor.h): the form and the pack above, the band rule, and the call's kernel -- the warp's
+ * where it has warps, else its filter's. */
+hipError_t nhw_launch_sample(const NhwSampleCall &c, hipStream_t s)
 {
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) return hipErrorInvalidValue;
+	if (!c.warps && (c.filter < NHW_FILTER_TWO_TAP || c.filter > NHW_FILTER_CUBIC)) return hipErrorInvalidValue;
+	const NhwTensorOut &o = c.out;
 	int lg, bands;
 	uint32_t rows;
-	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
-	nhw_with_tensor_store(dtype, layout, a, [&](auto st) {
-		constexpr int DT = decltype(st)::dtype, CHW = decltype(st)::layout;
-		switch (filter) {
-		case NHW_FILTER_TWO_TAP:
-			k_resize_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
-			break;
-		case NHW_FILTER_AREA:
-			k_area_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
-			break;
-		default:
-			k_cubic_to_tensor<DT, CHW, 3, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr, maps...);
-		}
+	if (!resample_bands(c.n, o.w, o.h, lg, rows, bands)) return hipErrorInvalidValue;
+	with_form(c.grey, o.dtype, o.layout, [&](auto dt, auto chw, auto ch) {
+		with_pack(c.ops, [&](auto... m) {
+			constexpr int DT = decltype(dt)::value, CHW = decltype(chw)::value, C = decltype(ch)::value;
+			const int grid = c.n * bands;
+			if (c.warps) {
+				k_warp_to_tensor<DT, CHW, C, decltype(m)...><<<grid, RS_THREADS, 0, s>>>(c.pics, c.warps, o.w, o.h, bands, (int)rows, lg, warp_row_limit, o.a, c.out_addr, m...);
+				return;
+			}
+			switch (c.filter) {
+			case NHW_FILTER_TWO_TAP:
+				k_resize_to_tensor<DT, CHW, C, decltype(m)...><<<grid, RS_THREADS, 0, s>>>(c.pics, o.w, o.h, bands, (int)rows, lg, o.a, c.ops.flags, c.out_addr, m...);
+				break;
+			case NHW_FILTER_AREA:
+				k_area_to_tensor<DT, CHW, C, decltype(m)...><<<grid, RS_THREADS, sizeof(uint2) * ((size_t)o.w + rows), s>>>(c.pics, o.w, o.h, bands, (int)rows, lg, o.a, c.ops.flags, c.out_addr, m...);
+				break;
+			default:
+				k_cubic_to_tensor<DT, CHW, C, decltype(m)...><<<grid, RS_THREADS, 0, s>>>(c.pics, o.w, o.h, bands, (int)rows, o.a, c.ops.flags, c.out_addr, m...);
+			}
+		});
 	});
 	return hipGetLastError();
 }
 
-/* the same launches for one-byte pixels and one-channel tensors: the same filters, band rule and LDS sizes */
-template <class... M>
-static hipError_t launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                       const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s, M... maps)
-{
-	if (filter < NHW_FILTER_TWO_TAP || filter > NHW_FILTER_CUBIC) return hipErrorInvalidValue;
-	int lg, bands;
-	uint32_t rows;
-	if (!resample_bands(n, out_w, out_h, lg, rows, bands)) return hipErrorInvalidValue;
-	with_dtype(dtype, [&](auto dt) {
-		constexpr int DT = decltype(dt)::value;
-		switch (filter) {
-		case NHW_FILTER_TWO_TAP:
-			k_resize_to_tensor<DT, 0, 1, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
-			break;
-		case NHW_FILTER_AREA:
-			k_area_to_tensor<DT, 0, 1, M...><<<n * bands, RS_THREADS, sizeof(uint2) * ((size_t)out_w + rows), s>>>(d_pics, out_w, out_h, bands, (int)rows, lg, a, d_flags, d_out_addr, maps...);
-			break;
-		default:
-			k_cubic_to_tensor<DT, 0, 1, M...><<<n * bands, RS_THREADS, 0, s>>>(d_pics, out_w, out_h, bands, (int)rows, a, d_flags, d_out_addr, maps...);
-		}
-	});
-	return hipGetLastError();
-}
-
-hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                               const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
-{
-	return launch_resample(filter, d_pics, n, out_w, out_h, dtype, layout, a, d_flags, d_out_addr, s);
-}
-hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                    const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s)
-{
-	return launch_resample_grey(filter, d_pics, n, out_w, out_h, dtype, a, d_flags, d_out_addr, s);
-}
-hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                           const uint64_t *d_out_addr, hipStream_t s)
-{
-	return launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s);
-}
-hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                const uint64_t *d_out_addr, hipStream_t s)
-{
-	return launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s);
-}
-/* ... and with a device table of n maps; `grey`: the one-channel kernels, which take no layout */
-hipError_t nhw_launch_resample_mapped(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                      const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (!d_maps) return hipErrorInvalidValue;
-	return grey ? launch_resample_grey(filter, d_pics, n, out_w, out_h, dtype, a, d_flags, d_out_addr, s, d_maps)
-	            : launch_resample(filter, d_pics, n, out_w, out_h, dtype, layout, a, d_flags, d_out_addr, s, d_maps);
-}
-hipError_t nhw_launch_warp_mapped(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
-                                  const NhwTensorArgs &a, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (!d_maps) return hipErrorInvalidValue;
-	return grey ? launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s, d_maps)
-	            : launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s, d_maps);
-}
-/* ... and with a device table of n tone tables, the map table or null in front of it */
-hipError_t nhw_launch_resample_toned(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                     const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (!d_tones) return hipErrorInvalidValue;
-	return grey ? launch_resample_grey(filter, d_pics, n, out_w, out_h, dtype, a, d_flags, d_out_addr, s, d_maps, d_tones)
-	            : launch_resample(filter, d_pics, n, out_w, out_h, dtype, layout, a, d_flags, d_out_addr, s, d_maps, d_tones);
-}
-hipError_t nhw_launch_warp_toned(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
-                                 const NhwTensorArgs &a, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s)
-{
-	if (!d_tones) return hipErrorInvalidValue;
-	return grey ? launch_warp_grey(d_pics, d_warps, n, out_w, out_h, dtype, a, d_out_addr, s, d_maps, d_tones)
-	            : launch_warp(d_pics, d_warps, n, out_w, out_h, dtype, layout, a, d_out_addr, s, d_maps, d_tones);
-}

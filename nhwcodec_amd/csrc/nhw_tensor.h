@@ -45,6 +45,9 @@ inline int nhw_tensor_format_check(const nhw_tensor_format *f, NhwTensorArgs *a,
 }
 /* the tensors of one size that a resampling or warping call makes, as its launcher takes them */
 struct NhwTensorOut { uint32_t w, h; int dtype, layout; NhwTensorArgs a; };
+/* the per-sample tables of a call, entry i for sample i, each null for "none": the flag bytes (bit 0: mirror left-right), the colour maps (DESIGN.md
+ * section 24) and the tone tables (section 25).  What the samplers' call (NhwSampleCall below) and the decode's store policies (nhw_tensor_ops.h) share */
+struct NhwOpsArgs { const uint8_t *flags; const nhw_colour_map *maps; const nhw_tone_table *tones; };
 /* ... and what every such entry checks of them, in this order: the sides, 1 .. 4096 each (the message names the entry), then the format -- as a
  * one-channel entry where `grey` is set */
 inline int nhw_tensor_out_check(const char *who, uint32_t out_width, uint32_t out_height, const nhw_tensor_format *f, NhwTensorOut *o, std::string &err, bool grey = false)
@@ -299,43 +302,42 @@ template <class F> inline void nhw_with_tensor_store(int dtype, int layout, cons
 
 /* nhw_picture.hip: every picture of the table to a tensor of its own size, one pass */
 hipError_t nhw_launch_bytes_to_tensor(const nhw_picture *d_pics, int n_pics, int dtype, int layout, const NhwTensorArgs &a, const uint64_t *d_out_addr, hipStream_t s);
-/* nhw_resample.hip: every picture resampled to out_w x out_h (1 .. 4096 each), mirrored where bit 0 of d_flags[k] is set (d_flags may be null), under
- * the filter NHW_FILTER_TWO_TAP, NHW_FILTER_AREA (section 19: the exact box mean along an axis that shrinks, the two taps along
- * one that does not) or NHW_FILTER_CUBIC (section 20: the Keys cubic, a = -1/2, widened with the reduction).  An entry whose width exceeds
- * nhw_filter_limit(filter) out_w, or its height that many out_h, stores nothing (0: the two taps have no limit) */
+/* nhw_resample.hip: one sampling call, as it goes from a public entry to the launch.  Every picture of the table is sampled into a tensor of out.w x
+ * out.h (1 .. 4096 each) at out_addr[k], with 3 bytes a pixel or, with `grey`, 1 ([out.h][out.w] elements under scale[0] and
+ * bias[0]; no layout is read, and of a warp fill[0] alone).
+ * Without `warps` the call resamples: under the filter NHW_FILTER_TWO_TAP (section 18), NHW_FILTER_AREA (section 19: the exact box mean along an axis
+ * that shrinks, the two taps along one that does not) or NHW_FILTER_CUBIC (section 20: the Keys cubic, a = -1/2, widened with the reduction),
+ * mirrored where bit 0 of ops.flags[k] is set.  An entry whose width exceeds nhw_filter_limit(filter) out.w, or its height that many out.h, stores
+ * nothing (0: the two taps have no limit).
+ * With `warps`, a device table of n, entry k is sampled along the tilted grid of warps[k] (section 21) under the same band rule; filter and ops.flags
+ * are not read.  An entry whose warp is not nhw_warp_within stores nothing: the kernel checks it, and the host paths that know a warp refuse it
+ * with the same words before they launch.
+ * ops.maps and ops.tones are device tables of n, entry k for picture k, each null for "none", and choose the form of the kernel: none of them the
+ * plain one, maps alone the mapped one (section 24; the rule and nhw_colour_within are in nhw_colour.h), tones the toned one (section 25; nhw_tone.h),
+ * which takes the maps as well where there are some.  An entry whose map is not within the limits stores nothing: the kernel checks it, and the
+ * host paths that know a map refuse it before they launch.  Every tone table is valid.
+ * A further per-sample step is one more table here, one more pack in nhw_resample.hip and one more row in the entries' descriptor tables. */
 inline uint32_t nhw_filter_limit(int filter) { return filter == NHW_FILTER_CUBIC ? NHW_CUBIC_MAX_REDUCTION : filter == NHW_FILTER_AREA ? NHW_AREA_MAX_REDUCTION : 0; }
-hipError_t nhw_launch_resample(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                               const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
-/* nhw_resample.hip as well: every picture sampled along the tilted grid of its nhw_warp, under the band rule of
- * nhw_launch_resample.  An entry whose warp is not nhw_warp_within stores nothing: the kernel checks it, and the host paths that know a
- * warp refuse it with the same words before they launch. */
 __host__ __device__ inline bool nhw_warp_within(const nhw_warp &m)
 {
 	constexpr int32_t S = NHW_WARP_MAX_STEP << 16;
 	constexpr int64_t O = 1ll << 40;
 	return m.a >= -S && m.a <= S && m.b >= -S && m.b <= S && m.d >= -S && m.d <= S && m.e >= -S && m.e <= S && m.c >= -O && m.c <= O && m.f >= -O && m.f <= O;
 }
-hipError_t nhw_launch_warp(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                           const uint64_t *d_out_addr, hipStream_t s);
-/* the one-channel forms of both: pictures of 1 byte a pixel to [out_h][out_w] elements under scale[0] and bias[0]; of a
- * warp fill[0] alone is read */
-hipError_t nhw_launch_resample_grey(int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                    const uint8_t *d_flags, const uint64_t *d_out_addr, hipStream_t s);
-hipError_t nhw_launch_warp_grey(const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, const NhwTensorArgs &a,
-                                const uint64_t *d_out_addr, hipStream_t s);
-/* the four launches above with a device table of n colour maps, d_maps[k] for entry k (the rule and nhw_colour_within are in
- * nhw_colour.h): the mapped forms of the same kernels under the same band rule.  `grey`: the one-channel forms, which read no layout.  An entry
- * whose map is not within the limits stores nothing: the kernel checks it, and the host paths that know a map refuse it before they launch. */
-hipError_t nhw_launch_resample_mapped(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                      const uint8_t *d_flags, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s);
-hipError_t nhw_launch_warp_mapped(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
-                                  const NhwTensorArgs &a, const nhw_colour_map *d_maps, const uint64_t *d_out_addr, hipStream_t s);
-/* ... and with a device table of n tone tables as well, d_tones[k] for entry k (the rule is in nhw_tone.h): the toned forms of
- * the same kernels.  d_maps may be null here: no map.  Every table is valid. */
-hipError_t nhw_launch_resample_toned(bool grey, int filter, const nhw_picture *d_pics, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout, const NhwTensorArgs &a,
-                                     const uint8_t *d_flags, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s);
-hipError_t nhw_launch_warp_toned(bool grey, const nhw_picture *d_pics, const nhw_warp *d_warps, int n, uint32_t out_w, uint32_t out_h, int dtype, int layout,
-                                 const NhwTensorArgs &a, const nhw_colour_map *d_maps, const nhw_tone_table *d_tones, const uint64_t *d_out_addr, hipStream_t s);
+struct NhwSampleCall {
+	const nhw_picture *pics; int n;
+	NhwTensorOut out;
+	bool grey;
+	int filter;
+	const nhw_warp *warps;
+	NhwOpsArgs ops;
+	const uint64_t *out_addr;
+};
+hipError_t nhw_launch_sample(const NhwSampleCall &c, hipStream_t s);
+/* the family of a public entry, in its row of the descriptor tables (nhw_enc_hostpath.hip, nhw_dec_hostpath.hip): colour, grey, or -- the mapped and
+ * toned entries -- by the format, where one that names NHW_T_GREY makes the call the one-channel one */
+enum NhwFamily { NHW_FAMILY_COLOUR, NHW_FAMILY_GREY, NHW_FAMILY_BY_FORMAT };
+inline bool nhw_family_grey(NhwFamily family, const nhw_tensor_format *f) { return family == NHW_FAMILY_BY_FORMAT ? f && f->channels == NHW_T_GREY : family == NHW_FAMILY_GREY; }
 /* nhw_tone.hip: the histograms of n pictures of `channels` (3 or 1) bytes a pixel, uint32 [n][channels][256], zeroed on the
  * stream and then counted; and the rows of n tone tables from such histograms under one op byte a sample */
 hipError_t nhw_launch_hist(const nhw_picture *d_pics, int n, int channels, uint32_t *d_hist, hipStream_t s);

@@ -17,8 +17,7 @@
 #include "nhw_grey.h"
 #include "nhw_reverse.h"
 
-/* the device tables of a call, entry i for file i; each may be null */
-struct NhwOpsArgs { const uint8_t *flags; const nhw_colour_map *maps; const nhw_tone_table *tones; };
+/* (the device tables of a call, NhwOpsArgs, entry i for file i: nhw_tensor.h) */
 
 /* bit 0 of the file's flag byte, as a scalar: one byte load a workgroup */
 __device__ __forceinline__ bool nhw_ops_mirror(const uint8_t *flags, int img)
